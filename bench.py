@@ -7,7 +7,8 @@ output arrays, the whole hot path (sample every path point, curvature, curvature
 obstacle validation, per-field metrics) -- and the stream drained; the field records (128 B per field) are RESIDENT IN DEVICE MEMORY when the
 region starts (engine.FieldTable.to_device(): inputs in HBM, as the tier's measurement rule has them; the same call on records in pinned host
 memory, read by the device across PCIe where they lie, rides along as `ms_pinned_records` / `value_pinned_records`).  `value` / `ms_per_step`:
-the median of REPS_SHORT regions of K such calls, each region bracketed by barrier + synchronize.
+ONE region of --steps such calls after --warmup of them, bracketed by barrier + synchronize (--full: also the median of REPS_SHORT regions
+of K such calls, `ms_regions_median`).
 
 `value_step` / `ms_step` is what rounds 1-4 reported as `value`: the hot path re-run on a batch that is already set up (the kernels alone,
 inputs resident in HBM) -- the figure the kernels' roofline fractions refer to.  `end_to_end` (diagnostic) splits a plan call made through
@@ -27,6 +28,12 @@ the time of the optional point-array gather; cfg2 at 0.1 m stays as a weak-scale
 
 `python bench.py --gpus N` starts its own workers (torch.distributed.run, one per GPU) before this process touches the GPU;
 under an external launcher (RANK / WORLD_SIZE set) it is a worker itself.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline and nothing else: it sets up, makes --warmup plan calls, times ONE region of exactly --steps plan
+calls between two fences (`ms_per_step` = the region / --steps, `value` = points x --steps / the region), writes the last call's outputs
+if --dump-outputs DIR is given, and prints the line.  Everything else described above -- the step and sustained regions, the plan call
+on pinned records, the end-to-end split, the roofline, the CPU baselines and the `configs` array -- runs with --full only, behind the
+same headline measurement; its own regions are min(--steps, FULL_STEPS) calls long, so that a --full run takes minutes whatever --steps is.
 """
 import argparse
 import json
@@ -56,13 +63,21 @@ def parse_args():
     ap.add_argument('--steps', type=int, default=1000)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--fields', type=int, default=4096, help='fields of 500 x 200 m per GPU in the headline batch')
-    ap.add_argument('--mode', type=int, default=1, help='1 = fused pipeline (default), 0 = staged pipeline')
+    ap.add_argument('--mode', type=int, default=1, help='(--full) pipeline of the step regions: 1 = fused (default), 0 = staged')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: step and sustained regions, pinned records, end-to-end split, roofline, CPU baselines and --configs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed plan call returned as DIR/<name>.npy (float64; a fixed seeded sample '
+                         'of 2^20 points and 2^16 fields when there are more), e.g. bench_outputs/')
     ap.add_argument('--configs', default='all',
-                    help="'all', 'none' or a comma list of: cfg1_clothoid,cfg1_x16384,cfg1_clothoid_dense,cfg2_ref,cfg2_0.5,cfg2_0.1,cfg3,cfg3_avoid,cfg4,cfg5,single_field")
-    ap.add_argument('--calibrate', type=int, default=0, help='opt-in: also report the dense configs and cfg5 with Batch.alloc(best_of=N) output arrays (never the primary figure)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-budget', type=float, default=8.0, help='seconds of CPU baseline for the headline (the other configs get 3 s each)')
-    return ap.parse_args()
+                    help="(--full) 'all', 'none' or a comma list of: cfg1_clothoid,cfg1_x16384,cfg1_clothoid_dense,cfg2_ref,cfg2_0.5,cfg2_0.1,cfg3,cfg3_avoid,cfg4,cfg5,single_field")
+    ap.add_argument('--calibrate', type=int, default=0, help='(--full) opt-in: also report the dense configs and cfg5 with Batch.alloc(best_of=N) output arrays (never the primary figure)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baselines')
+    ap.add_argument('--cpu-budget', type=float, default=8.0, help='(--full) seconds of CPU baseline for the headline (the other configs get 3 s each)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def self_launch(args):
@@ -144,8 +159,9 @@ REPS = 5          # repetitions of the K-step timed region; the median is report
 # A K = 20 region of the sparse configurations is ~1 ms long -- shorter than the device's clock / power transient after a load sets in
 # (tools/short_region.py, profiles/r04_short_region.log: regions 3-6 of a series read 5-10 % slower than the first two and than everything
 # from the tenth on).  Steps that write < 1 GB are therefore timed over REPS_SHORT regions (25 x K steps, ~30 ms): every region is K steps
-# bracketed as the contract says, all of them are listed in bench_detail.json (timed_region), the median is `value`.
+# bracketed as the contract says, all of them are listed in bench_detail.json (timed_region), the median is each configuration's `value`.
 REPS_SHORT = 25
+FULL_STEPS = 20   # --full: K = min(--steps, FULL_STEPS), the region length of everything but the headline (the K of the kept records)
 SHORT_STEP_BYTES = 1 << 30
 
 
@@ -154,9 +170,10 @@ def median(v):
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
-def fresh_regions(E, torch, table, veh, opt, steps, reps, fence, after_call=None):
+def fresh_regions(E, torch, table, veh, opt, steps, reps, fence, after_call=None, keep_last=False):
     """`reps` regions of `steps` FRESH plan calls (engine.Batch.plan: fcpp_batch_plan + the stream drained; the previous call's batch and
-    arrays are released inside the region, as a caller in a loop releases them) -> (seconds per region, points per call)"""
+    arrays are released inside the region, as a caller in a loop releases them) -> (seconds per region, points per call), and with
+    keep_last the last call's (batch, result) as a third item, still open: the caller closes the batch"""
     dts, batch, res, n_points, k = [], None, None, 0, 0
     drain = torch.cuda.current_stream().synchronize
     for _ in range(max(1, reps)):
@@ -174,9 +191,51 @@ def fresh_regions(E, torch, table, veh, opt, steps, reps, fence, after_call=None
         fence()
         dts.append(time.perf_counter() - t0)
         n_points = batch.total_points
+    if keep_last:
+        return dts, n_points, (batch, res)
     if batch is not None:
         batch.close()
     return dts, n_points
+
+
+def records_on_device(E, table, veh, opt):
+    """Puts the field records in device memory when the device sets the batch up (-> True); a batch the HOST sets up (cfg3's single
+    field, AVOID mode) keeps its records on the host -- the host plans them, a table on the device would be copied back first (30-40 us
+    of every call, measured: cfg3 0.442 -> 0.480 ms) -> False."""
+    probe = E.Batch(table, veh, opt)
+    on_device = probe.setup_path() == 'device'
+    probe.close()
+    if on_device:
+        table.to_device()
+    return on_device
+
+
+DUMP_POINTS = 1 << 20         # --dump-outputs: points of the seeded sample (5 arrays x 8 B x 2^20 = 42 MB) ...
+DUMP_FIELDS = 1 << 16         # ... and fields of the per-field arrays (15 x 8 B x 2^16 = 7.9 MB): at most 50 MB in all
+DUMP_SEED = 1691
+
+
+def dump_outputs(path, batch, res, torch):
+    """--dump-outputs: what the plan call handed its caller -- the point arrays x, y, kappa, v, flagseg (as unsigned), the per-field
+    statistics (stats_<name>) and point counts (field_n_main, field_n_head) -- as <path>/<name>.npy in float64 (every integer exactly).
+    More than DUMP_POINTS points / DUMP_FIELDS fields: a sample of them, drawn from a fixed seed, in index order -- the same indices
+    for the same arguments, so that two builds can be compared array for array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n, nf = int(batch.total_points), int(batch.n_fields)
+    rng = np.random.default_rng(DUMP_SEED)
+    pidx = np.arange(n) if n <= DUMP_POINTS else np.sort(rng.choice(n, DUMP_POINTS, replace=False))
+    fidx = np.arange(nf) if nf <= DUMP_FIELDS else np.sort(rng.choice(nf, DUMP_FIELDS, replace=False))
+    it = torch.as_tensor(pidx, device=res.x.device)
+    arrays = {name: getattr(res, name).index_select(0, it).cpu().numpy().astype(np.float64) for name in ('x', 'y', 'kappa', 'v')}
+    arrays['flagseg'] = res.flagseg.index_select(0, it).cpu().numpy().view(np.uint32).astype(np.float64)
+    for name, col in res.stats().items():
+        arrays[f'stats_{name}'] = col[fidx].astype(np.float64)
+    info = batch.info.array
+    for name in ('n_main', 'n_head'):
+        arrays[f'field_{name}'] = info[name][fidx].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), a)
 
 
 def sustained_regions(E, torch, table, veh, opt, steps, reps, fence):
@@ -228,16 +287,9 @@ def run_planner(E, torch, table, opt, steps, warmup, mode=1, calibrate=0, fence=
     # the field records: resident in DEVICE memory when the timed regions start (records='device', round 5b: FieldTable.to_device() -- inputs in
     # HBM), or in pinned host memory, read by the device across PCIe where they lie ('pinned': rounds 4-5a).  The host paths of the library
     # (cfg3's single field, AVOID mode) copy device records back first -- inside the call, on the clock.
-    # A batch the HOST sets up (cfg3's single field, AVOID mode) keeps its records in pinned host memory: the host plans them, a table on the
-    # device would be copied back first (30-40 us of every call, measured: cfg3 0.442 -> 0.480 ms).
-    if records == 'device' and hasattr(table, 'to_device'):
-        probe = E.Batch(table, veh, opt)
-        on_device = probe.setup_path() == 'device'
-        probe.close()
-        if on_device:
-            table.to_device()
-        else:
-            records = 'pinned'
+    # A batch the HOST sets up (cfg3's single field, AVOID mode) keeps its records in pinned host memory (records_on_device).
+    if records == 'device' and hasattr(table, 'to_device') and not records_on_device(E, table, veh, opt):
+        records = 'pinned'
     if records != 'device' and hasattr(table, 'pin'):
         table.pin()
     for rep in range(max(1, e2e_reps)):
@@ -476,18 +528,19 @@ def compact_line(out):
     """The last stdout line: BASELINE.json's metric on the headline workload -- `value` = the fresh plan call, `value_step` = the hot path on a
     batch already set up -- with `roofline` (the dominant kernel: its own launch duration and fraction, what bounds it, the call's fraction
     as `end_to_end_frac`; every kernel of the step as [ms per launch, points per launch, HBM fraction]) and `cpu_baseline`, plus one short
-    row per configuration.  The full record (per-configuration entries with their setup splits, timed regions, notes) is bench_detail.json."""
-    rf, cfg = out['roofline'], out['config']
+    row per configuration.  The full record (per-configuration entries with their setup splits, timed regions, notes) is bench_detail.json.
+    A plain run (no --full) measures the headline alone: the parts it has no figures for are null."""
+    rf, cfg = out.get('roofline'), out['config']
     tr = out.get('timed_region') or {}
     kern = {}
-    for name, ms in rf['all_kernels_ms'].items():
+    for name, ms in (rf['all_kernels_ms'].items() if rf else ()):
         pts = rf['all_kernels_points'].get(name, 0)
         if ms > 0:
             kern[name] = [_r(ms, 5), int(pts), _r(BYTES_PER_POINT * pts / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if name != 'k_reduce_stats' else None]
     c = {
         'metric': out['metric'], 'value': _r(out['value'], 7), 'unit': out['unit'], 'n_gpus': out['n_gpus'], 'steps': out['steps'], 'warmup': out['warmup'],
         'ms_per_step': _r(out['ms_per_step'], 6), 'higher_is_better': True, 'scaling': out['scaling'], 'vs_baseline': out.get('vs_baseline'),
-        'vs_baseline_of': out.get('vs_baseline_of'), 'dtype': 'f64', 'data': 'synthetic',
+        'vs_baseline_of': out.get('vs_baseline_of'), 'dtype': 'f64', 'data': 'synthetic', 'full': bool(out.get('full')),
         'step': 'one plan call (fcpp_batch_plan: setup on the device + output arrays + the hot path) + stream drained; field records resident in HBM',
         'ms_pinned_records': _r(out.get('ms_pinned_records'), 5), 'value_pinned_records': _r(out.get('value_pinned_records'), 5),
         'value_step': _r(out.get('value_step'), 6), 'ms_step': _r(out.get('ms_step'), 5),
@@ -498,11 +551,12 @@ def compact_line(out):
                      'unit': 'GB/s', 'kernel_ms': _r(rf['kernel_ms'], 5), 'algorithmic_bytes_per_launch': rf['algorithmic_bytes_per_launch'],
                      'valu_frac': _r(rf.get('valu_frac'), 3), 'traffic': rf.get('traffic'), 'traffic_source': (rf.get('traffic_source') or '')[:60] or None,
                      'step_frac': _r(rf['step_frac'], 4), 'end_to_end_frac': _r(out.get('end_to_end_frac'), 4),
-                     'kernel_timing': (rf.get('kernel_timing') or '')[:100], 'kernels': kern},
-        'cpu_baseline': None, 'end_to_end_ms': _r(out['end_to_end']['ms'], 5),
+                     'kernel_timing': (rf.get('kernel_timing') or '')[:100], 'kernels': kern} if rf else None,
+        'cpu_baseline': None, 'end_to_end_ms': _r(out['end_to_end']['ms'], 5) if out.get('end_to_end') else None,
+        'ms_regions_median': _r(out.get('ms_regions_median'), 6),
         'value_clothoid': _r(out.get('value_clothoid'), 6), 'value_step_clothoid': _r(out.get('value_step_clothoid'), 6), 'frac_clothoid': _r(out.get('frac_clothoid'), 3),
         'rccl_ranks': out.get('rccl_ranks'), 'per_rank_points_per_s': out.get('per_rank_points_per_s'),
-        'host_threads': out.get('host_threads'), 'detail': 'bench_detail.json',
+        'host_threads': out.get('host_threads'), 'detail': None if out.get('full') is False else 'bench_detail.json',          # (a plain run writes none)
         # (every region is K plan calls between two fences; their number and the spread ride along, each one's value is in the detail file)
         'timed_regions': {'n': tr.get('reps'), 'reported': 'median', 'first_ms': _r(tr['ms_per_step_each_rep'][0], 5), 'min_ms': _r(min(tr['ms_per_step_each_rep']), 5),
                           'max_ms': _r(max(tr['ms_per_step_each_rep']), 5)} if tr.get('ms_per_step_each_rep') else None,
@@ -521,7 +575,7 @@ def compact_line(out):
         dev = (e.get('setup_ms') or {}).get('device_setup')
         rows[e['name']] = [_r(e.get('ms_fresh'), 4), _r(e.get('value_fresh'), 4), _r(e.get('ms_per_step', e.get('ms_total')), 5),
                            _r(rr.get('step_frac', rr.get('frac')), 3), _r(cpu.get('value'), 4), None if dev is None else ('device' if dev else 'host')]
-    c['configs'] = {'columns': ['ms_plan_call', 'value_plan_call', 'ms_step', 'step_frac', 'cpu_baseline_value', 'setup'], **rows}
+    c['configs'] = {'columns': ['ms_plan_call', 'value_plan_call', 'ms_step', 'step_frac', 'cpu_baseline_value', 'setup'], **rows} if 'configs' in out else None
     line = json.dumps(c, separators=(',', ':'))
     for drop in ('per_rank_points_per_s', 'configs'):          # (never needed so far: a guard, not a plan)
         if len(line) <= COMPACT_LIMIT:
@@ -667,66 +721,97 @@ def main():
                 pending[-1].wait()
         fence()
 
-    # `value`: regions of K FRESH plan calls (Batch.plan + the stream drained), REPS_SHORT of them; `value_step`: the same regions of K steps on
-    # the batch that is already set up, with the kernel's own launch duration by HIP events (what the roofline fraction refers to).  With
-    # several ranks the per-field stats of every call go to rank 0 as before (a device copy into the ring, a gather per GATHER_EVERY calls).
+    # With several ranks the per-field stats of every plan call go to rank 0 (a device copy into the ring, a gather per GATHER_EVERY calls).
     def after_fresh(k, res):
         if use_dist:
             stats_slot(k, res.batch).copy_(res.stats_raw)
         count_and_gather(k, res)
 
-    r = run_planner(E, torch, E.FieldTable.from_rectangles(LH1), E.make_options(), args.steps, args.warmup, mode=args.mode, fence=fence_headline,
-                    after_step=count_and_gather, stats_of=stats_slot if use_dist else None, e2e_reps=50, fresh_steps=args.steps, fresh_reps=REPS_SHORT,
+    # `value` / `ms_per_step`, in every run: --warmup FRESH plan calls (Batch.plan + the stream drained), then ONE region of --steps of them
+    # between two fences, the field records resident in device memory; with several ranks every rank's points over the slowest rank's region.
+    veh1, opt1 = E.make_vehicle(), E.make_options()
+    t_head = E.FieldTable.from_rectangles(LH1)
+    head_records = 'device' if records_on_device(E, t_head, veh1, opt1) else 'pinned'
+    if head_records == 'pinned':
+        t_head.pin()
+    if args.warmup > 0:
+        fresh_regions(E, torch, t_head, veh1, opt1, args.warmup, 1, fence_headline)
+    hdts, head_points, (hbatch, hres) = fresh_regions(E, torch, t_head, veh1, opt1, args.steps, 1, fence_headline, after_fresh, keep_last=True)
+    head_dt, head_total = allmax(hdts[0]), allsum(head_points)
+    out = None
+    if rank == 0:
+        st = hres.stats()
+        assert int(st['n_viol'].sum()) == 0 and np.isfinite(st['main_len_m']).all()
+        assert (hbatch.info[0].n_main, hbatch.info[0].n_head) == (1256, 435)          # README_en.md:206-207
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hbatch, hres, torch)
+        out = {
+            'metric': METRIC, 'value': head_total * args.steps / head_dt, 'unit': 'points/s',
+            'n_gpus': world, **({'forced_dist': 'one-rank RCCL process group, collectives addressed to the rank itself (FCPP_BENCH_FORCE_DIST=1)'} if force_dist else {}),
+            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': head_dt / args.steps * 1e3,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic', 'full': args.full,
+            'step': 'one plan call of the reference for the whole batch (plan_complete_coverage, MLP:387-465: a NEW field set up and its path generated): '
+                    'engine.Batch.plan(table) = fcpp_batch_plan (the setup on the device, the output arrays from the context\'s arena, the hot path) + the stream drained; '
+                    'field records resident in device memory when the region starts (FieldTable.to_device(); ms_pinned_records: the same call on records in pinned host memory); '
+                    'ONE region of --steps calls after --warmup calls',
+            'records': head_records,
+            'config': {
+                'workload': f'cfg1 x {args.fields}: {args.fields} fields of 500 x 200 m per GPU, ARC turns (the reference\'s own model, pinned to its outputs) at the '
+                            f'reference\'s sampling, 1691 points per field; a step = one fresh plan call of the batch '
+                            f'(BASELINE.json configs[0], README_en.md:199-215; default VehicleParams; 2 / 20 / 15 / 20 points per line / U-turn / corner / headland side); '
+                            f'the clothoid turn model on the same batch: value_clothoid, configs[cfg1_clothoid*]',
+                'turn_model': 'arc (reference, pinned)', 'points_per_gpu_step': head_points, 'fields_per_gpu': args.fields,
+                'output_arrays': getattr(hbatch, 'layout', None), 'setup': hbatch.setup_path(),
+            },
+        }
+    hres = None
+    hbatch.close()
+    del hbatch
+    if not args.full:
+        if use_dist:
+            dist.destroy_process_group()
+        if rank == 0:
+            os.write(real_stdout, (compact_line(out) + '\n').encode())
+        return
+
+    # ---- --full: everything else, in regions of K = min(--steps, FULL_STEPS) calls or steps ------------------------------------------
+    # The fresh plan call again, REPS_SHORT regions of K calls (their median: ms_regions_median); `value_step`: the same regions of K steps
+    # on the batch that is already set up, with the kernel's own launch duration by HIP events (what the roofline fraction refers to).
+    K = min(args.steps, FULL_STEPS)
+    r = run_planner(E, torch, E.FieldTable.from_rectangles(LH1), E.make_options(), K, args.warmup, mode=args.mode, fence=fence_headline,
+                    after_step=count_and_gather, stats_of=stats_slot if use_dist else None, e2e_reps=50, fresh_steps=K, fresh_reps=REPS_SHORT,
                     after_fresh=after_fresh, pinned_too=(world == 1))
     sustained = None
     if world == 1:
         t_h = E.FieldTable.from_rectangles(LH1)
         t_h.to_device()
-        sustained = median(sustained_regions(E, torch, t_h, E.make_vehicle(), E.make_options(), args.steps, REPS_SHORT, fence_headline))
+        sustained = median(sustained_regions(E, torch, t_h, E.make_vehicle(), E.make_options(), K, REPS_SHORT, fence_headline))
     dt = allmax(r['dt'])
     fresh_dt = allmax(median(r['fresh']['dts']))
     total_points = allsum(r['points'])
     e2e_ms = allmax(r['end_to_end']['ms'])
     # every rank's own rate (its points x K / its own time of the K-call region), so that the scaling run checks itself
     rates = torch.zeros(world, dtype=torch.float64, device=cdev)
-    rates[rank] = r['points'] * args.steps / median(r['fresh']['dts'])
+    rates[rank] = r['points'] * K / median(r['fresh']['dts'])
     if use_dist:
         dist.all_reduce(rates)
     per_rank_rates = [float(f'{v:.5g}') for v in rates.cpu().tolist()]
-    out = None
     if rank == 0:
-        st = r['res'].stats()
-        assert int(st['n_viol'].sum()) == 0 and np.isfinite(st['main_len_m']).all()
-        assert (r['batch'].info[0].n_main, r['batch'].info[0].n_head) == (1256, 435)          # README_en.md:206-207
-        fresh_ms = fresh_dt / args.steps * 1e3
-        out = {
-            'metric': METRIC, 'value': total_points * args.steps / fresh_dt, 'unit': 'points/s',
-            'n_gpus': world, **({'forced_dist': 'one-rank RCCL process group, collectives addressed to the rank itself (FCPP_BENCH_FORCE_DIST=1)'} if force_dist else {}), 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': fresh_ms,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'step': 'one plan call of the reference for the whole batch (plan_complete_coverage, MLP:387-465: a NEW field set up and its path generated): '
-                    'engine.Batch.plan(table) = fcpp_batch_plan (the setup on the device, the output arrays from the context\'s arena, the hot path) + the stream drained; '
-                    'field records resident in device memory when the region starts (FieldTable.to_device(); ms_pinned_records: the same call on records in pinned host memory)',
-            'timed_region': {'reps': len(r['fresh']['dts']), 'steps_per_rep': args.steps, 'ms_per_step_each_rep': [round(d / args.steps * 1e3, 5) for d in r['fresh']['dts']],
+        out.update({
+            'full_region_steps': K,
+            'timed_region': {'reps': len(r['fresh']['dts']), 'steps_per_rep': K, 'ms_per_step_each_rep': [round(d / K * 1e3, 5) for d in r['fresh']['dts']],
                              'reported': 'median'},
+            'ms_regions_median': fresh_dt / K * 1e3,
             # the hot path on the batch that is set up (rounds 1-4's `value`): K steps per region, the kernels alone
-            'value_step': total_points * args.steps / dt, 'ms_step': dt / args.steps * 1e3, 'timed_region_step': timed_region_of(r),
-            'end_to_end_frac': BYTES_PER_POINT * r['points'] / (fresh_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            'value_step': total_points * K / dt, 'ms_step': dt / K * 1e3, 'timed_region_step': timed_region_of(r),
+            'end_to_end_frac': BYTES_PER_POINT * r['points'] / (out['ms_per_step'] * 1e-3) / 1e9 / HBM_PEAK_GBS,
             **({'ms_pinned_records': r['fresh']['pinned_ms_per_call'], 'value_pinned_records': r['points'] / (r['fresh']['pinned_ms_per_call'] * 1e-3)}
                if r['fresh'].get('pinned_ms_per_call') else {}),
             # two plan calls in flight on two streams: the sustained fresh-batch rate, reported as such
-            **({'value_sustained': total_points * args.steps / sustained, 'ms_sustained': sustained / args.steps * 1e3,
+            **({'value_sustained': total_points * K / sustained, 'ms_sustained': sustained / K * 1e3,
                 'sustained': 'fresh plan calls alternating between two streams, batch k + 1 set up while batch k\'s step runs; not `value`'} if sustained else {}),
             # the same call through the three separate entries (create / alloc / run), split into its parts
             'value_end_to_end': total_points / (e2e_ms * 1e-3), 'end_to_end': r['end_to_end'], 'setup_ms': r['end_to_end']['setup_ms'],
-            'config': {
-                'workload': f'cfg1 x {args.fields}: {args.fields} fields of 500 x 200 m per GPU, ARC turns (the reference\'s own model, pinned to its outputs) at the '
-                            f'reference\'s sampling, 1691 points per field; a step = one fresh plan call of the batch '
-                            f'(BASELINE.json configs[0], README_en.md:199-215; default VehicleParams; 2 / 20 / 15 / 20 points per line / U-turn / corner / headland side); '
-                            f'the clothoid turn model on the same batch: value_clothoid, configs[cfg1_clothoid*]',
-                'turn_model': 'arc (reference, pinned)', 'points_per_gpu_step': r['points'], 'fields_per_gpu': args.fields,
-                'pipeline': 'staged (7 kernels)' if args.mode == 0 else 'fused: k_plan_quiet (closed-form runs and spans) + k_plan_sparse / k_plan_sparse_fields (wave tiles, two points per lane; the latter also reduces its fields) + k_plan_fused (all other tiles) + k_reduce_stats',
-                'quiet_points': r['quiet_points'], 'general_points': r['general_points'], 'output_arrays': r['layout'],
-            },
             'roofline': roofline_of(r, 'cfg1'),
             'cpu_baseline': None,
             'reference_published': REFERENCE_MEASURED,
@@ -734,7 +819,11 @@ def main():
             'per_rank_points_per_s': per_rank_rates,
             'host_threads': host_threads,
             'output_arena': arena,
-        }
+        })
+        out['config'].update({
+            'pipeline': 'staged (7 kernels)' if args.mode == 0 else 'fused: k_plan_quiet (closed-form runs and spans) + k_plan_sparse / k_plan_sparse_fields (wave tiles, two points per lane; the latter also reduces its fields) + k_plan_fused (all other tiles) + k_reduce_stats',
+            'quiet_points': r['quiet_points'], 'general_points': r['general_points'], 'output_arrays': r['layout'],
+        })
         out['config']['setup'] = r['batch'].setup_path() if hasattr(r['batch'], 'setup_path') else 'host'
     if rank == 0 and cpu_on:
         import oracle as orc
@@ -777,7 +866,7 @@ def main():
         T1 = E.FieldTable.from_rectangles(LH1)
         if 'cfg1_clothoid' in want:
             e = planner_config('cfg1_clothoid', f'cfg1 x {args.fields}, clothoid turns (line-clothoid-arc-clothoid-line) at the reference\'s sample counts',
-                               T1, E.make_options(1, 0.0), args.steps, args.warmup,
+                               T1, E.make_options(1, 0.0), K, args.warmup,
                                lambda k: orc.make_field(L=500.0, H=200.0), len(LH1), orc.Options.make(1, 1, 0.0, 0.5), what='500 x 200 m fields, clothoid, reference sampling',
                                e2e_reps=200)
             # (BASELINE.json's metric names the clothoid sampler: the same batch with clothoid turns, at top level beside the pinned arc model)
@@ -787,16 +876,16 @@ def main():
             # the headline's fields, four times as many: 1 GB of output per step -- beyond the 256 MiB Infinity Cache that the headline's 249 MB fit into
             T16 = E.FieldTable.from_rectangles(WL.cfg1_batch(16384))
             planner_config('cfg1_x16384', 'cfg1 x 16384: the headline\'s fields, 16 384 of them (1.0 GB of output per step: beyond the 256 MiB Infinity Cache)',
-                           T16, E.make_options(), args.steps, args.warmup, e2e_reps=100, traffic_key='cfg1')
+                           T16, E.make_options(), K, args.warmup, e2e_reps=100, traffic_key='cfg1')
         if 'cfg1_clothoid_dense' in want:
             planner_config('cfg1_clothoid_dense', f'cfg1 x {args.fields}, clothoid turns, uniform 0.1 m sample spacing',
-                           T1, E.make_options(1, 0.1), max(3, args.steps // 20), 2,
+                           T1, E.make_options(1, 0.1), max(3, K // 20), 2,
                            lambda k: orc.make_field(L=500.0, H=200.0), len(LH1), orc.Options.make(1, 1, 0.1, 0.5), what='500 x 200 m fields, clothoid, 0.1 m',
                            calibrate=args.calibrate, e2e_reps=3)
         LH2 = WL.cfg2_rectangles()
         T2 = E.FieldTable.from_rectangles(LH2)
-        for key, tm, sp, st_, wu in (('cfg2_ref', 0, 0.0, args.steps, args.warmup), ('cfg2_0.5', 1, 0.5, max(5, args.steps // 10), 2),
-                                      ('cfg2_0.1', 1, 0.1, max(3, args.steps // 20), 2)):
+        for key, tm, sp, st_, wu in (('cfg2_ref', 0, 0.0, K, args.warmup), ('cfg2_0.5', 1, 0.5, max(5, K // 10), 2),
+                                      ('cfg2_0.1', 1, 0.1, max(3, K // 20), 2)):
             if key not in want:
                 continue
             wl = (f'cfg2: 1024 random rectangular fields (edges U[100,1000) m, seed 1024), '
@@ -822,7 +911,7 @@ def main():
                 return {'value': p.n / tc, 'unit': 'points/s', 'cores': 1, 'kind': 'port', 'single_core_value': p.n / tc,
                         'sample': f'the whole cfg3 field (5000 x 2000 m, 32 obstacles, clothoid, 0.05 m: {p.n} points) once through oracle/fcpp_oracle.c on one thread, {tc:.1f} s'}
             planner_config('cfg3', 'cfg3: one 5000 x 2000 m field, 32 convex eight-gon obstacles, clothoid turns, 0.05 m sample spacing',
-                           E.FieldTable.from_specs([E.FieldSpec(field_length=L3, field_width=H3, obstacles=obst)]), E.make_options(1, 0.05), max(5, args.steps // 10), 2,
+                           E.FieldTable.from_specs([E.FieldSpec(field_length=L3, field_width=H3, obstacles=obst)]), E.make_options(1, 0.05), max(5, K // 10), 2,
                            extra_fn=cfg3_extra, calibrate=args.calibrate, e2e_reps=3, cpu_fn=cfg3_cpu)
         if 'cfg3_avoid' in want:
             (L3, H3), obst = WL.cfg3_field()
@@ -842,7 +931,7 @@ def main():
             planner_config('cfg3_avoid', 'cfg3 with obstacle-aware swaths (fcpp_options.obstacle_mode = AVOID, SURVEY.md 8f-4): every swath that meets one of '
                            'the 32 obstacles is clipped and driven around it; clothoid turns, 0.05 m',
                            E.FieldTable.from_specs([E.FieldSpec(field_length=L3, field_width=H3, obstacles=obst)]), E.make_options(1, 0.05, avoid_obstacles=True),
-                           max(5, args.steps // 10), 2, extra_fn=cfg3a_extra, e2e_reps=3, cpu_fn=cfg3a_cpu)
+                           max(5, K // 10), 2, extra_fn=cfg3a_extra, e2e_reps=3, cpu_fn=cfg3a_cpu)
         if 'cfg4' in want:
             configs.append(run_cfg4(E, torch, WL, cpu_on))
         if 'single_field' in want:
@@ -852,16 +941,16 @@ def main():
         if rank == 0:
             configs.append(entry)
     if 'cfg5' in want or world > 1:
-        entry = run_cfg5(E, S, WL, torch, dist, np, rank, world, dev, cdev, fence, allmax, max(5, args.steps // 10), cpu_on, args.calibrate)
+        entry = run_cfg5(E, S, WL, torch, dist, np, rank, world, dev, cdev, fence, allmax, max(5, K // 10), cpu_on, args.calibrate)
         if rank == 0:
             configs.append(entry)
     if world > 1 and 'cfg2_0.1' in want:
         LH2 = WL.cfg2_rectangles(seed=1024 + rank)
-        rr = run_planner(E, torch, E.FieldTable.from_rectangles(LH2), E.make_options(1, 0.1), max(3, args.steps // 20), 2, fence=fence, e2e_reps=2)
+        rr = run_planner(E, torch, E.FieldTable.from_rectangles(LH2), E.make_options(1, 0.1), max(3, K // 20), 2, fence=fence, e2e_reps=2)
         dt2, pts2 = allmax(rr['dt']), allsum(rr['points'])
         if rank == 0:
             e = config_entry('cfg2_0.1_weak', f'cfg2 weak-scaled: 1024 random rectangles PER GPU (seed 1024 + rank), clothoid, 0.1 m; rank 0\'s kernels', rr)
-            e.update({'value': pts2 * max(3, args.steps // 20) / dt2, 'points': pts2, 'n_gpus': world, 'scaling': 'weak'})
+            e.update({'value': pts2 * max(3, K // 20) / dt2, 'points': pts2, 'n_gpus': world, 'scaling': 'weak'})
             configs.append(e)
         rr['batch'].close()
 

@@ -75,3 +75,65 @@ def test_compact_line_drops_optional_parts_before_it_grows_past_the_limit():
     assert len(line) <= bench.COMPACT_LIMIT
     d = json.loads(line)
     assert d['roofline'] and d['cpu_baseline']
+
+
+def test_compact_line_of_a_plain_run():
+    """A plain run (no --full) measures the headline alone: its figures are on the line, the parts it does not measure are null."""
+    keep = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data',
+            'step', 'config')
+    out = {k: v for k, v in _fake_out().items() if k in keep}
+    out['full'] = False
+    line = bench.compact_line(out)
+    assert '\n' not in line and len(line) < 4096
+    d = json.loads(line)
+    assert d['metric'] == bench.METRIC and d['unit'] == 'points/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['value'] == 4.2e10 and d['ms_per_step'] == 0.165 and d['steps'] == 20 and d['warmup'] == 5
+    assert d['full'] is False and d['roofline'] is None and d['cpu_baseline'] is None and d['configs'] is None and d['timed_regions'] is None
+    assert d['detail'] is None
+
+
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays of what the plan call returned, a sample drawn from a fixed seed when the batch is larger than the
+    bounds (the same indices in every run), and the bounds keep a dump under 64 MB."""
+    import numpy as np
+    import torch
+    assert 5 * 8 * bench.DUMP_POINTS + 15 * 8 * bench.DUMP_FIELDS < 64 << 20
+    monkeypatch.setattr(bench, 'DUMP_POINTS', 1000)
+    monkeypatch.setattr(bench, 'DUMP_FIELDS', 16)
+    n, nf = 5000, 40
+    rng = np.random.default_rng(7)
+    info = np.zeros(nf, dtype=[('n_main', '<i8'), ('n_head', '<i8')])
+    info['n_main'], info['n_head'] = rng.integers(0, 100, nf), rng.integers(0, 50, nf)
+    stats = {'main_len_m': rng.uniform(0, 1e3, nf), 'n_viol': rng.integers(0, 3, nf)}
+
+    class Batch:
+        total_points, n_fields = n, nf
+
+        class info:
+            array = info
+
+    class Res:
+        x, y, kappa, v = (torch.as_tensor(rng.standard_normal(n)) for _ in range(4))
+        flagseg = torch.as_tensor(rng.integers(-2 ** 31, 2 ** 31, n, dtype=np.int64).astype(np.int32))
+
+        def stats(self):
+            return stats
+
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), Batch, Res(), torch)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(['x.npy', 'y.npy', 'kappa.npy', 'v.npy', 'flagseg.npy', 'stats_main_len_m.npy', 'stats_n_viol.npy',
+                            'field_n_main.npy', 'field_n_head.npy'])
+    for name in names:
+        a, b = np.load(tmp_path / 'a' / name), np.load(tmp_path / 'b' / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    x = np.load(tmp_path / 'a' / 'x.npy')
+    assert x.shape == (1000,)
+    pos = np.searchsorted(Res.x.numpy(), x, sorter=np.argsort(Res.x.numpy()))
+    idx = np.argsort(Res.x.numpy())[pos]
+    assert np.array_equal(Res.x.numpy()[idx], x) and np.all(np.diff(idx) > 0)          # a sample of the points, in index order
+    fs = np.load(tmp_path / 'a' / 'flagseg.npy')
+    assert np.array_equal(fs, Res.flagseg.numpy().view(np.uint32)[idx].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'kappa.npy'), Res.kappa.numpy()[idx])
+    nm = np.load(tmp_path / 'a' / 'field_n_main.npy')
+    assert nm.shape == (16,) and set(nm.tolist()) <= set(info['n_main'].astype(np.float64).tolist())

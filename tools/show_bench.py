@@ -24,7 +24,7 @@ show(d, 'HEADLINE')
 for k in ('value_step', 'ms_step', 'value_sustained', 'ms_sustained', 'value_clothoid'):
     if d.get(k) is not None:
         print(f"{'':22s} {k} = {d[k]:.5g}")
-cfgs = d.get('configs', [])
+cfgs = d.get('configs') or []               # (a plain run's line has none: only --full measures them)
 if isinstance(cfgs, dict):                    # the compact line: a row per configuration under `columns`
     cols = cfgs.get('columns', [])
     print(f"{'':22s} " + ' '.join(f'{c:>18s}' for c in cols))
