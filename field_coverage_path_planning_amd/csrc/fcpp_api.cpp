@@ -218,7 +218,6 @@ struct fcpp_ctx {
     // ev_plan there and waits for it -- lazily, when that other stream shows up: an event recorded between two kernels of the plan call
     // costs 5 us of device time between them (round 5: the three records of a plan call were 16 of its 158 us)
     hipEvent_t ev_plan = nullptr;
-    hipEvent_t ev_chunk[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };      // a large batch's counting pass in chunks beside its planner (launch_devplan_count)
     // the output arena (fcpp_ctx_reserve_outputs): ONE allocation of 4 x pitch + lane bytes; array k of every batch's outputs lies in lane k
     // (lanes `pitch` apart), placed first-fit among the live allocations of the lane -- all five arrays of an allocation at the same offset
     void *arena = nullptr; size_t arena_pitch = 0, arena_lane = 0;
@@ -259,9 +258,6 @@ struct fcpp_batch {
     std::vector<unsigned char> ev_set; // kProfRuns x kStages: the stage launched a kernel in that run
     int prof_runs = 0;
     int last_mode = 0;
-    bool two_streams = true;     // ALU-bound kernels of a step on the context's side stream (FCPP_ONE_STREAM=1 in the environment: off)
-    int two_stream_max = 512;    // ... when there are at most this many general tiles (FCPP_TWO_STREAM_MAX, read at batch creation)
-    int sparse_beside_max = 0;   // ... or at most this many wave tiles (FCPP_SPARSE_BESIDE_MAX; 0 = never: measured, see fcpp_batch_run)
     fcpp_setup_times setup = {};
     const fcpp_field_info *info_dev = nullptr;     // device-side setup: the records in the slab; hp.info is filled from them on demand
     // every stream this batch's kernels were enqueued on (callers re-bind the context's stream between calls: engine.py binds torch's
@@ -454,7 +450,6 @@ int fcpp_ctx_destroy(fcpp_ctx *c)
     for (auto &sl : c->plan_slots) if (sl.p) { (void)hipDeviceSynchronize(); (void)hipFree(sl.p); sl.p = nullptr; }
     if (c->arena) { (void)hipDeviceSynchronize(); (void)hipFree(c->arena); }
     if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
-    for (hipEvent_t e : c->ev_chunk) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->plan_totals_host) (void)hipHostFree(c->plan_totals_host);
     if (c->ga_mirror) (void)hipHostFree(c->ga_mirror);
@@ -670,7 +665,7 @@ int fcpp_plan_points(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *o
     int rc = plan_prepare(*veh, *opt, pc, tt, err);
     if (rc != FCPP_OK) return fail(rc, err);
     const bool on_device = c->setup_mode != FCPP_SETUP_HOST && opt->sample_spacing == 0.0 && opt->obstacle_mode == FCPP_OBSTACLES_FLAG &&
-                           pc.max_prims <= DEVPLAN_PRIMS_CAP && !tune_enabled();
+                           pc.max_prims <= DEVPLAN_PRIMS_CAP;
     if (!on_device) {
         HostPlan hp;
         std::vector<fcpp_field> fcopy;
@@ -783,6 +778,37 @@ int take_slab(fcpp_ctx *c, fcpp_batch *b, std::string &err)
         if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return FCPP_EHIP; } \
     } while (0)
 
+// Host memory for an upload of nb bytes: the context's pinned staging memory, reallocated with `want` bytes when it holds fewer than nb
+// (whatever was being copied out of it drained first), or `pageable` when the upload is larger than kStageMax or pinned memory cannot be had
+int upload_buffer(fcpp_ctx *c, size_t nb, size_t want, std::vector<unsigned char> &pageable, unsigned char *&img, std::string &err)
+{
+    img = nullptr;
+    if (nb <= kStageMax) {
+        DEVCHK(c->stage_wait());
+        if (c->stage_cap < nb) {
+            if (c->stage) { (void)hipHostFree(c->stage); c->stage = nullptr; c->stage_cap = 0; }
+            if (hipHostMalloc(&c->stage, want, hipHostMallocDefault) == hipSuccess) c->stage_cap = want;
+            else { c->stage = nullptr; (void)hipGetLastError(); }
+        }
+        if (c->stage_cap >= nb) img = static_cast<unsigned char *>(c->stage);
+    }
+    if (!img) {
+        try { pageable.resize(nb); } catch (const std::bad_alloc &) { err = "out of host memory"; return FCPP_ENOMEM; }
+        img = pageable.data();
+    }
+    return FCPP_OK;
+}
+
+// the batch's kernel constants, with its template set (on the host by now); true: its U-turns are closed form
+bool set_batch_consts(fcpp_batch *b, const TemplateSet &ts)
+{
+    b->cst = make_const(b->veh, b->opt);
+    b->cst.shapes = ts.shapes.p;
+    b->cst.tmpl_u = ts.tmpl_u.p; b->cst.tmpl_c = ts.tmpl_c.p; b->cst.tmpl_u_dk = ts.tmpl_u_dk.p;
+    b->cst.tmpl_n = (int)ts.tt.nu; b->cst.tmpl_nc = std::max(1, (int)ts.tt.nc);
+    return ts.tt.nu >= 3 && closed_form_turns(b->veh, ts.tt, ts.h_tu, ts.h_dk, b->cst);
+}
+
 // the context's planner scratch for n fields (grow-only), ordered behind the last fill pass that read it
 int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, DevPlanScratch &s, std::string &err)
 {
@@ -845,9 +871,10 @@ int device_fields(const fcpp_field *fields, int64_t n_fields, hipStream_t st, co
 }
 
 // FCPP_OK: the batch is set up (tables on the device, info on the host); kNotOnDevice: not this path's batch; else the error.
-// fresh_templates: the batch's template set is still on its way back from the device (cleared once this path has waited for it)
+// fresh_templates: the batch's template set is still on its way back from the device (cleared once this path has waited for it);
+// field_work, span_line_max: the batch's reference switches (fcpp_batch_create)
 int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_field *fields, const fcpp_polys *obstacles, bool &fresh_templates,
-                     std::string &err)
+                     bool field_work, int64_t span_line_max, std::string &err)
 {
     const fcpp_options &opt = b->opt;
     fcpp_setup_times &tm = b->setup;
@@ -861,9 +888,8 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         if (c->setup_mode == FCPP_SETUP_AUTO && n_fields < small) { err = "a handful of fields: set up by the host"; return kNotOnDevice; }
     }
     const bool dense = opt.sample_spacing != 0.0;          // (round 5: span + quiet runs of the straights + general tiles, k_tile_fields' dense block)
-    if (dense && getenv("FCPP_DENSE_DEVICE") && atoi(getenv("FCPP_DENSE_DEVICE")) == 0) { err = "FCPP_DENSE_DEVICE=0: dense sampling set up by the host"; return kNotOnDevice; }
     if (opt.obstacle_mode != FCPP_OBSTACLES_FLAG) { err = "obstacle-aware swaths are planned on the host"; return kNotOnDevice; }
-    if (tune_enabled()) { err = "FCPP_TUNE: the tuning knobs are the host tiler's"; return kNotOnDevice; }
+    if (!field_work) { err = "FCPP_FIELD_WORK=0: the host tiler's reference path"; return kNotOnDevice; }
     PlanConsts pc;
     TurnTemplates tt;
     int rc = plan_prepare(b->veh, opt, pc, tt, err);
@@ -878,11 +904,7 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
     if (fresh_templates) { DEVCHK(hipStreamSynchronize(st)); fresh_templates = false; }
     c->templates = b->templates;
     const TemplateSet &ts = *b->templates;
-    b->cst = make_const(b->veh, opt);
-    b->cst.shapes = ts.shapes.p;
-    b->cst.tmpl_u = ts.tmpl_u.p; b->cst.tmpl_c = ts.tmpl_c.p; b->cst.tmpl_u_dk = ts.tmpl_u_dk.p;
-    b->cst.tmpl_n = (int)ts.tt.nu; b->cst.tmpl_nc = std::max(1, (int)ts.tt.nc);
-    const bool turn_quiet = ts.tt.nu >= 3 && closed_form_turns(b->veh, ts.tt, ts.h_tu, ts.h_dk, b->cst);
+    const bool turn_quiet = set_batch_consts(b, ts);
     tm.templates_ms += ms_since(t0);
 
     // scratch + the field records
@@ -913,7 +935,7 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
     ImageLayout &lay = b->lay;
     auto common_layout = [&](ImageLayout &l) {
         l = ImageLayout();
-        l.n_fields = n_fields; l.wave_tile_points = 128; l.n_chunks = 0;
+        l.n_fields = n_fields; l.n_chunks = 0;
         l.n_polys = n_polys; l.n_poly_verts = n_polys > 0 ? obstacles->offsets[n_polys] : 0;
         l.info_on_device = true;
     };
@@ -924,16 +946,7 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         const size_t o0 = lay.obs_off, o1 = lay.seg, nb = o1 - o0;
         std::vector<unsigned char> tmp;
         unsigned char *img = nullptr;
-        if (nb <= kStageMax) {
-            DEVCHK(c->stage_wait());
-            if (c->stage_cap < nb) {
-                if (c->stage) { (void)hipHostFree(c->stage); c->stage = nullptr; c->stage_cap = 0; }
-                if (hipHostMalloc(&c->stage, nb + nb / 4, hipHostMallocDefault) == hipSuccess) c->stage_cap = nb + nb / 4;
-                else { c->stage = nullptr; (void)hipGetLastError(); }
-            }
-            if (c->stage_cap >= nb) img = static_cast<unsigned char *>(c->stage);
-        }
-        if (!img) { try { tmp.resize(nb); } catch (const std::bad_alloc &) { err = "out of host memory"; return FCPP_ENOMEM; } img = tmp.data(); }
+        if (const int urc = upload_buffer(c, nb, nb + nb / 4, tmp, img, err); urc != FCPP_OK) return urc;
         fill_obstacles(obstacles, lay, img, o0);
         DEVCHK(hipMemcpyAsync(static_cast<unsigned char *>(b->slab) + o0, img, nb, hipMemcpyHostToDevice, st));
         if (!tmp.empty()) DEVCHK(hipStreamSynchronize(st));
@@ -969,18 +982,16 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         if (lay.total_bytes > ((size_t)1 << 30)) spec = false;
     }
     tc.speculative = spec ? 1 : 0;
-    tc.closed_cut = (getenv("FCPP_WINDOW_CUT") || dense) ? 0 : 1;          // (FCPP_WINDOW_CUT=1: round 4's cut on both sides -- the A/B of the two cuts)
+    tc.closed_cut = dense ? 0 : 1;
     tc.dense = dense ? 1 : 0;
-    tc.span_line_max = (getenv("FCPP_DENSE_SPAN") && atoll(getenv("FCPP_DENSE_SPAN")) <= 0) ? 64 : INT64_MAX;
+    tc.span_line_max = span_line_max;
     if (spec) {
         if ((rc = take_slab(c, b, err)) != FCPP_OK) return rc;
         bind_tables(b);
         if ((rc = upload_obstacles()) != FCPP_OK) return rc;
     }
-    if (!spec && c->side && !c->ev_chunk[0])
-        for (hipEvent_t &e : c->ev_chunk) DEVCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     tc.f0 = 0; tc.f1 = n_fields;
-    int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, n_polys, obstacles != nullptr, tot, spec ? nullptr : c->side, c->ev_chunk, 5);
+    int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, n_polys, obstacles != nullptr, tot);
     if (lrc) { (void)hipStreamSynchronize(st); err = std::string("launch_devplan_count: ") + hipGetErrorString((hipError_t)lrc); return FCPP_EHIP; }   // (drained: the caller's pinned records may still be read)
     if (spec && (rc = launch_fill()) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
     // (the last scan has written the totals and the flags to `tot`, then the phase's generation number to tot[PX_DONE]: polled -- a word
@@ -1074,9 +1085,12 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     std::unique_ptr<fcpp_batch> b(new (std::nothrow) fcpp_batch());
     if (!b) return fail(FCPP_ENOMEM, "out of host memory");
     b->ctx = c; b->veh = *veh; b->opt = *opt; b->n_fields = n_fields;
-    b->two_streams = !(tune_enabled() && getenv("FCPP_ONE_STREAM") != nullptr);
-    b->two_stream_max = std::max(0, std::min(tune_int("FCPP_TWO_STREAM_MAX", 512), 1 << 20));
-    b->sparse_beside_max = std::max(0, std::min(tune_int("FCPP_SPARSE_BESIDE_MAX", 0), 1 << 30));
+    // reference switches, read per batch (tests set them between batches): FCPP_FIELD_WORK=0 plans every wave tile with k_plan_sparse and
+    // reduces every field with k_reduce_stats (the reference of k_plan_sparse_fields; the host tiler's path), FCPP_DENSE_SPAN=0 keeps
+    // round 4's per-line runs for fields without obstacles too (TileConsts::span_line_max)
+    const char *e_fw = getenv("FCPP_FIELD_WORK"), *e_span = getenv("FCPP_DENSE_SPAN");
+    const bool field_work = !(e_fw && atoi(e_fw) == 0);
+    const int64_t span_line_max = e_span && atoll(e_span) <= 0 ? 64 : INT64_MAX;
     fcpp_setup_times &tm = b->setup;
     tm.threads = WorkerPool::width();
     std::string err;
@@ -1099,7 +1113,7 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     // function the host would run (fcpp_planfn.h) runs one thread per field, the tiler's cut one wavefront per field, the totals come
     // back once (they size the tables and the output arrays), the tables are written in place.  The host plans nothing per field.
     {
-        int rc = try_device_setup(c, b.get(), n_fields, fields, obstacles, fresh, err);
+        int rc = try_device_setup(c, b.get(), n_fields, fields, obstacles, fresh, field_work, span_line_max, err);
         if (rc == FCPP_OK) {
             tm.total_ms = ms_since(t_begin);
             c->last_setup = tm;
@@ -1126,11 +1140,7 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     if (fresh) HIPCHK(hipStreamSynchronize(st));
     c->templates = b->templates;
     const TemplateSet &ts = *b->templates;
-    b->cst = make_const(*veh, *opt);
-    b->cst.shapes = ts.shapes.p;
-    b->cst.tmpl_u = ts.tmpl_u.p; b->cst.tmpl_c = ts.tmpl_c.p; b->cst.tmpl_u_dk = ts.tmpl_u_dk.p;
-    b->cst.tmpl_n = (int)ts.tt.nu; b->cst.tmpl_nc = std::max(1, (int)ts.tt.nc);
-    const bool turn_quiet = ts.tt.nu >= 3 && closed_form_turns(*veh, ts.tt, ts.h_tu, ts.h_dk, b->cst);
+    const bool turn_quiet = set_batch_consts(b.get(), ts);
     tm.templates_ms += ms_since(t0);
 
     // ---- 4. tiler: every field's path cut into work for the four kernels, blocks side by side (fcpp_tiler.cpp)
@@ -1145,22 +1155,16 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     // the ends of the reverse fills, three per field of the metric's size, pass with the default tolerance of 1e-6 m: with the millimetre of margin
     // of rounds 2-3a those three points sent half of the headline's wave tiles through the geofence test)
     tc.fence_margin = 1e-7 - opt->geofence_tol;
-    // (tuning knobs, read once per batch and clamped; both change which kernel plans a stretch or which reduction class a path falls
-    // into, i.e. the order of its sums at the last bit: diagnostic builds only)
-    tc.wave_factor = std::max(0, std::min(tune_int("FCPP_WAVE_FACTOR", 24), 64));
-    tc.reduce_wg_max = std::max(256, std::min(tune_int("FCPP_REDUCE_WG_MAX", 1024), 1 << 20));
-    tc.wave_points = tune_int("FCPP_WAVE_POINTS", 128) == 64 ? 64 : 128;
-    tc.field_work = tune_int("FCPP_FIELD_WORK", 1) != 0;
-    tc.field_work_tiles = std::max(1, std::min(tune_int("FCPP_FIELD_WORK_TILES", FIELD_WORK_TILES), FIELD_WORK_TILES));
-    tc.fuse_spans = tc.field_work && ts.tt.nu <= TMPL_LDS_SAMPLES && tune_int("FCPP_FUSE_SPANS", 1) != 0;
-    // the chunk lists are expanded on the device from the host's chunk groups; FCPP_HOST_CHUNKS=1 (the checker, tests/test_gpu_devplan.py) and
-    // the FCPP_CHUNK_SPREAD diagnostic keep the host's own lists
-    tc.device_chunks = !(getenv("FCPP_HOST_CHUNKS") && atoi(getenv("FCPP_HOST_CHUNKS")) != 0) && !getenv("FCPP_CHUNK_SPREAD");
+    tc.field_work = field_work;
+    tc.fuse_spans = tc.field_work && ts.tt.nu <= TMPL_LDS_SAMPLES;
+    // the chunk lists are expanded on the device from the host's chunk groups; FCPP_HOST_CHUNKS=1 (the checker, tests/test_gpu_devplan.py)
+    // keeps the host's own lists
+    tc.device_chunks = !(getenv("FCPP_HOST_CHUNKS") && atoi(getenv("FCPP_HOST_CHUNKS")) != 0);
     // the reference's sampling: the general stretch of every field with a closed-form span is cut in closed form (fcpp_cutfn.h), as the device
     // planner cuts it -- host-built and device-built tables stay equal byte for byte
-    tc.closed_cut = opt->sample_spacing == 0.0 && opt->obstacle_mode == FCPP_OBSTACLES_FLAG && tc.wave_points == CUT_WAVE_LANES && !getenv("FCPP_WINDOW_CUT");
+    tc.closed_cut = opt->sample_spacing == 0.0 && opt->obstacle_mode == FCPP_OBSTACLES_FLAG;
     tc.cut = make_cut_consts(*b->templates, false, turn_quiet, tc.wave_factor, tc.two_a, tc.u_cap, tc.c_line, tc.fence_margin, b->cst);
-    if (getenv("FCPP_DENSE_SPAN") && atoll(getenv("FCPP_DENSE_SPAN")) <= 0) tc.span_line_max = 64;          // (round 4's runs: the A/B)
+    tc.span_line_max = span_line_max;
     BatchTiler tiler;
     ImageLayout &lay = b->lay;
     rc = tiler.plan(b->hp, tc, obstacles, lay, err);
@@ -1171,11 +1175,6 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
         if (rc != FCPP_OK) return fail(rc, err);
     }
     tm.tiler_ms = ms_since(t0);
-    if (getenv("FCPP_DEBUG_TILING"))
-        fprintf(stderr, "[fcpp] tiling: %lld tiles; wave-tile stretches refused: back halo %lld, forward halo %lld, too few outputs %lld, "
-                "primitive span %lld; %lld wave tiles, %lld of them inside the geofence by the host's test\n", (long long)lay.n_tiles,
-                (long long)lay.wave_fail[0], (long long)lay.wave_fail[1], (long long)lay.wave_fail[2], (long long)lay.wave_fail[3],
-                (long long)lay.n_wave, (long long)lay.wave_inside);
 
     // ---- 5. the image: one device allocation (the context's spare if it is large enough), the tables written into pinned memory
     t0 = std::chrono::steady_clock::now();
@@ -1186,20 +1185,8 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     } guard{ b.get() };
     unsigned char *img = nullptr;
     std::vector<unsigned char> pageable;
-    if (lay.upload_bytes <= kStageMax) {
-        HIPCHK(c->stage_wait());
-        if (c->stage_cap < lay.upload_bytes) {
-            if (c->stage) { (void)hipHostFree(c->stage); c->stage = nullptr; c->stage_cap = 0; }
-            const size_t want = std::min(kStageMax, std::max<size_t>(lay.upload_bytes + lay.upload_bytes / 4, (size_t)1 << 20));
-            if (hipHostMalloc(&c->stage, want, hipHostMallocDefault) == hipSuccess) c->stage_cap = want;
-            else { c->stage = nullptr; (void)hipGetLastError(); }
-        }
-        if (c->stage_cap >= lay.upload_bytes) img = static_cast<unsigned char *>(c->stage);
-    }
-    if (!img) {
-        try { pageable.resize(lay.upload_bytes); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-        img = pageable.data();
-    }
+    rc = upload_buffer(c, lay.upload_bytes, std::min(kStageMax, std::max<size_t>(lay.upload_bytes + lay.upload_bytes / 4, (size_t)1 << 20)), pageable, img, err);
+    if (rc != FCPP_OK) return fail(rc, err);
     tiler.fill(b->hp, obstacles, lay, img);
     bind_tables(b.get());
     // (the primitives live in the image now; the host keeps the per-field records for fcpp_batch_info and the staged pipeline's tiling)
@@ -1265,11 +1252,8 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
 {
     if (!b) return fail(FCPP_EINVAL, "batch is NULL");
     // mode 1 (default): quiet tiles (k_plan_quiet, streaming) and general tiles (k_plan_fused) as two launches.
-    // Tuning only: modes 12/13/14 = mode 1 with k_plan_fused compiled for a minimum of 2/3/4 waves per SIMD (default 3).
     // (Measured and dropped: both tile kinds in one grid, and the two kernels on two streams -- the HBM-bound and the
     // ALU-bound kernel do not overlap usefully, the sum of the two launches is the faster schedule.)
-    int variant = 3;
-    if (mode >= 12 && mode <= 14) { variant = mode - 10; mode = 1; }
     if (mode != 0 && mode != 1) return fail(FCPP_EINVAL, "unknown pipeline mode");
     if (mode != b->last_mode) { b->prof_runs = 0; b->last_mode = mode; }
     if (b->n_fields == 0) return FCPP_OK;
@@ -1321,9 +1305,7 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
         // and 0.091 vs 0.085 ms, k_plan_sparse 1.07 instead of 0.69 ms; also with the span kernel held to four or five
         // waves per SIMD).
         hipStream_t sd = st;
-        const bool two = b->two_streams && lay.span_points + lay.chunk_points > 0 &&
-                         ((lay.n_general > 0 && lay.n_general <= b->two_stream_max && lay.n_wave == 0) ||
-                          (b->sparse_beside_max > 0 && lay.n_wave > 0 && lay.n_wave <= b->sparse_beside_max));
+        const bool two = lay.span_points + lay.chunk_points > 0 && lay.n_general > 0 && lay.n_general <= 512 && lay.n_wave == 0;
         if (two) {
             sd = b->ctx->side;
             HIPCHK(hipEventRecord(b->ctx->ev_fork, st));
@@ -1331,14 +1313,13 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
         }
         // the wave tiles of fields that k_plan_sparse_fields does not take (all of them when there are none of those)
         const bool fw = lay.n_field_work > 0;
-        if (!fw) STAGE(2, launch_plan_sparse(sd, lay.n_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial, lay.wave_tile_points / 64));
-        else STAGE(2, launch_plan_sparse(sd, lay.n_open_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial, lay.wave_tile_points / 64,
-                                         t.open_wave_ids));
-        STAGE(3, launch_plan_fused(sd, variant, lay.n_general, t.general_ids, t.tiles, t.fields, t.prims, b->cst, obs, x,
+        if (!fw) STAGE(2, launch_plan_sparse(sd, lay.n_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial));
+        else STAGE(2, launch_plan_sparse(sd, lay.n_open_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial, t.open_wave_ids));
+        STAGE(3, launch_plan_fused(sd, lay.n_general, t.general_ids, t.tiles, t.fields, t.prims, b->cst, obs, x,
                                    y, kappa, v, fs, t.partial));
         if (two) HIPCHK(hipEventRecord(b->ctx->ev_join, sd));
         STAGE(0, launch_plan_quiet(st, lay.n_span_chunks, t.span_chunks, 16, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial));
-        // (straights and U-turns in ONE launch: measured 4 % faster on identical memory than an instance each, tools/ab_quiet.py)
+        // (straights and U-turns in ONE launch: measured 4 % faster on identical memory than an instance each)
         STAGE(1, launch_plan_quiet(st, lay.n_chunks, t.chunks, 14, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial));
         // fields planned and reduced by one workgroup each: after the streaming kernels, whose flag counts their reduction reads
         if (fw) {       // (one launch per class of fields; normally one class holds them all: the stage's events time the first launch)

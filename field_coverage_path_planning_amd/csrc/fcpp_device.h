@@ -38,21 +38,6 @@ struct DevConst {
     const double2 *tmpl_u_dk;         // per U-turn sample k: (|t_k - t_(k-1)|, curvature at t_k), the shape's own segment lengths / curvatures
 };
 
-// Tuning knobs (extra LDS per workgroup = fewer resident waves, wave tiles per workgroup, ...) for tools/ab_knob.py, which flips them
-// between runs of one process on identical memory.  They are LIVE only in a process started with FCPP_TUNE=1 (checked once, when the
-// library is first used); otherwise every knob is its default and no launch path reads the environment.  Callers clamp the values.
-inline bool tune_enabled()
-{
-    static const bool on = [] { const char *v = getenv("FCPP_TUNE"); return v && v[0] == '1'; }();
-    return on;
-}
-inline int tune_int(const char *name, int dflt)
-{
-    if (!tune_enabled()) return dflt;
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 // Per-kernel device timing (fcpp_batch_set_profiling): when the caller has armed g_launch_prof, the next launcher call dispatches
 // its kernel with hipExtLaunchKernelGGL(start, stop): the two events take the dispatch's own begin / end time stamps -- no marker
 // packets between the kernels, so the timed step runs as it does unprofiled -- and the launcher disarms it.
@@ -97,14 +82,13 @@ int launch_run_consts(hipStream_t st, int64_t n_entries, const int32_t *ids, con
                       const DevPrim *prims, const DevConst &cst, TilePartial *partial);
 int launch_build_templates(hipStream_t st, const TurnTemplates &tt, const CacShape *shapes, void *tu, void *tc);
 // ids: tile indices the launch covers (NULL = all tiles in order)
-int launch_plan_fused(hipStream_t st, int variant, int64_t n_tiles, const int32_t *ids, const DevTile *tiles,
+int launch_plan_fused(hipStream_t st, int64_t n_tiles, const int32_t *ids, const DevTile *tiles,
                       const DevField *fields, const DevPrim *prims, const DevConst &cst, const DevObstacles &obs, double *x,
                       double *y, double *kappa, double *v, uint32_t *fs, TilePartial *partial);
-// one wavefront per wave tile; statistics go to partial[wtiles[k].tile]
+// one wavefront per wave tile (two points per lane, fcpp_sparse2_fn.h); statistics go to partial[wtiles[k].tile]
 int launch_plan_sparse(hipStream_t st, int64_t n_wtiles, const DevWaveTile *wtiles, const DevField *fields, const DevPrim *prims,
                        const DevConst &cst, const DevObstacles &obs, double *x, double *y, double *kappa, double *v, uint32_t *fs,
-                       TilePartial *partial, int points_per_lane = 1,        // 1: tiles of <= 64 points, 2: of <= 128 (fcpp_sparse2_fn.h)
-                       const int32_t *ids = nullptr);                       // ids: the launch covers wtiles[ids[k]] (NULL: all in order)
+                       TilePartial *partial, const int32_t *ids = nullptr);  // ids: the launch covers wtiles[ids[k]] (NULL: all in order)
 // one workgroup per field of `work`: its wave tiles planned (two points per lane) and its statistics reduced, written to stats[field]
 int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack *packs, const DevConst &cst, const DevObstacles &obs, double *x,
                               double *y, double *kappa, double *v, uint32_t *fs, TilePartial *partial, int waves, const TilePartial *totals,

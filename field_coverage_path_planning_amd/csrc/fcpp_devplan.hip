@@ -28,11 +28,10 @@ size_t devplan_scratch_layout(int64_t n, int max_prims, DevPlanScratch *o)
 }
 
 // blocks of 1024 fields up to which a batch is "small": ONE scan launch (a workgroup per column walks the fields in chunks of 4096) and
-// -- fcpp_api.cpp -- the speculative capacity layout.  FCPP_SMALL_BLOCKS (read once) for the A/B.
+// -- fcpp_api.cpp -- the speculative capacity layout
 int64_t devplan_small_blocks()
 {
-    static const int64_t v = [] { const char *e = getenv("FCPP_SMALL_BLOCKS"); const int64_t x = e ? atoll(e) : 8; return x < 1 ? 1 : (x > 128 ? 128 : x); }();
-    return v;
+    return 8;
 }
 
 namespace {
@@ -107,7 +106,7 @@ __device__ __forceinline__ double area_centroid_q(double px, double py, int i, d
 }
 }  // namespace p16
 
-// (f0, f1: the fields [f0, f1) of the batch's n -- large batches are planned in chunks, launch_devplan_count)
+// (f0, f1: the fields [f0, f1) of the batch's n -- launch_devplan_count plans the whole batch: 0, n)
 __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, const fcpp_field *__restrict__ fin, fcpp_field_info *__restrict__ info,
                                                       DevField *__restrict__ ftmp, DevPrim *__restrict__ ptmp, int64_t *__restrict__ counts,
                                                       int64_t *__restrict__ totals, int64_t n_polys, int check_obstacles, int64_t gen, int64_t f0, int64_t f1)
@@ -1622,82 +1621,55 @@ __global__ void k_debug_math(int fn, int64_t n, const double *__restrict__ a, co
 }  // namespace
 
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
-                         int64_t n_polys, int check_obstacles, int64_t *totals_host, hipStream_t side, hipEvent_t *ev, int n_ev)
+                         int64_t n_polys, int check_obstacles, int64_t *totals_host)
 {
     if (n <= 0) return 0;
-    // (sixteen lanes per field; FCPP_PLAN_SERIAL=1 -- read once -- keeps the one-thread-per-field kernel: the A/B and the checker of the two)
     // Sixteen lanes per field cut the latency of a plan (23 instead of 35 us for 4096 fields) and, four fields per wavefront, its stores are
-    // denser (cfg5's 65 536 fields: 170 us against 230 for the one-thread kernel); FCPP_PLAN_SERIAL=1 keeps the latter (the A/B, the checker)
+    // denser (cfg5's 65 536 fields: 170 us against 230 for the one-thread kernel); FCPP_PLAN_SERIAL=1 (read once) keeps the latter: the checker
     static const bool plan_serial = getenv("FCPP_PLAN_SERIAL") != nullptr;
-    static const bool one_stream = !(getenv("FCPP_COUNT_CHUNKS") != nullptr && atoi(getenv("FCPP_COUNT_CHUNKS")) >= 2);      // (the chunks: an experiment, see below)
     // The counting pass goes without the fields' point offsets; what depends on them (span_counts) is derived by the scan that follows the
     // pass: small batches ONE scan of one launch (k_scan_small), large ones the scan of the points (its apply kernel derives) and then the
     // scan of the other columns.  (Rounds 4-5a scanned the points of a large batch BEFORE its pass.)
     const bool one_scan = (n + 1023) / 1024 <= devplan_small_blocks();
     DevTileConsts tcc = tc;
     tcc.no_bases = 1;
-    auto plan = [&](hipStream_t q, int64_t f0, int64_t f1) {
-        if (plan_serial) {
-            if (f0 == 0)
-                hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, q, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                                   n_polys, check_obstacles, 0, tc.gen);
-        } else
-            hipLaunchKernelGGL(k_plan_fields16, dim3((unsigned)((f1 - f0 + 3) / 4)), dim3(64), 0, q, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               n_polys, check_obstacles, tc.gen, f0, f1);
+    auto plan = [&]() {
+        if (plan_serial)
+            hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
+                               n_polys, check_obstacles, 0, tc.gen);
+        else
+            hipLaunchKernelGGL(k_plan_fields16, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
+                               n_polys, check_obstacles, tc.gen, (int64_t)0, n);
     };
     // (more fields than one round of wavefronts takes -- 4 per SIMD x 1024 SIMDs with the primitives staged in LDS: they are not staged, five
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
-    auto count = [&](hipStream_t q, int64_t f0, int64_t f1) {
-        tcc.f0 = f0; tcc.f1 = f1;
-        const unsigned grid = (unsigned)((f1 - f0 + TW_WAVES - 1) / TW_WAVES);
+    auto count = [&]() {
+        tcc.f0 = 0; tcc.f1 = n;
+        const unsigned grid = (unsigned)((n + TW_WAVES - 1) / TW_WAVES);
         if (tc.dense)
-            hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, q, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
+            hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
                                s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
         else if (n <= 4096)
-            hipLaunchKernelGGL((k_tile_fields<false, true>), dim3(grid), dim3(64 * TW_WAVES), 0, q, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
+            hipLaunchKernelGGL((k_tile_fields<false, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
                                s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
         else
-            hipLaunchKernelGGL((k_tile_fields<false, false>), dim3(grid), dim3(64 * TW_WAVES), 0, q, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
+            hipLaunchKernelGGL((k_tile_fields<false, false>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
                                s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
     };
-    // Large batches in CHUNKS on two streams (FCPP_COUNT_CHUNKS=2..4; measured and NOT the default): the planner's first load is the transfer
-    // of the field records (128 bytes a field over PCIe: the kernel runs at the link's 50 GB/s), the counting pass of a chunk needs nothing but
-    // its own fields' plans -- beside the planner's next chunk instead of behind its last.  It loses: the planner reaches the link's rate only
-    // with the whole chip's wavefronts waiting on loads, and beside the counting pass it has half of them -- cfg5, four chunks: planner
-    // 60 + 66 + 76 + 85 us instead of 171, counting pass 106 + 86 + 76 + 71 instead of 249, the scans begin at 460 us instead of 421.
-    int n_chunks = 1;
-    if (!one_scan && !plan_serial && !one_stream && side && side != st && ev && n_ev >= 2) {
-        n_chunks = n_ev - 1 < 4 ? n_ev - 1 : 4;
-        if (const char *e = getenv("FCPP_COUNT_CHUNKS")) { const int c = atoi(e); if (c >= 2 && c <= n_ev - 1) n_chunks = c; }
-    }
     if (tc.dense) {
         // dense sampling: the chunks of every quiet run lie on 512-point boundaries of the batch arrays -- the pass needs the point offsets
-        plan(st, 0, n);
+        plan();
         int rc0 = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0);
         if (rc0) return rc0;
         tcc.no_bases = 0;
-        count(st, 0, n);
+        count();
         rc0 = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, 0, tc.gen);
         if (rc0) return rc0;
         const hipError_t e0 = hipGetLastError();
         return e0 == hipSuccess ? 0 : (int)e0;
     }
-    if (n_chunks <= 1) { plan(st, 0, n); count(st, 0, n); }
-    else {
-        const int64_t per = (((n + n_chunks - 1) / n_chunks) + 3) / 4 * 4;      // (whole wavefronts of the planner, whole workgroups of the pass)
-        int used = 0;
-        for (int64_t f0 = 0; f0 < n; f0 += per, ++used) {
-            const int64_t f1 = f0 + per < n ? f0 + per : n;
-            plan(st, f0, f1);
-            hipError_t e = hipEventRecord(ev[used], st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(side, ev[used], 0);
-            if (e != hipSuccess) return (int)e;
-            count(side, f0, f1);
-        }
-        hipError_t e = hipEventRecord(ev[n_ev - 1], side);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev[n_ev - 1], 0);
-        if (e != hipSuccess) return (int)e;
-    }
+    plan();
+    count();
     int rc = 0;
     if (one_scan) {
         rc = launch_scan(st, n, PC_POINTS, PC_COLS, s, totals_host, 1, 1, tc.fuse_spans, tc.speculative ? tc.gen : 0, tc.gen);

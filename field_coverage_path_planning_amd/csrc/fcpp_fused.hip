@@ -843,24 +843,22 @@ int launch_plan_quiet(hipStream_t st, int64_t n_chunks, const DevTile *chunks, i
     if (n_chunks <= 0) return 0;
     const bool staged = cst.tmpl_n > 0 && cst.tmpl_n <= TMPL_LDS, has_obs = obs.offsets != nullptr;
     // Chunks (= wavefronts) per workgroup: eight for long launches of the dense instances -- on ten sets of output arrays each
-    // (tools/ab_knob.py FCPP_QUIET_WPB=4,8 and a sweep over allocations) cfg2 at 0.5 m 1.202 -> 1.190 ms on its fastest set and ~1 % on all
+    // (four against eight, and a sweep over allocations) cfg2 at 0.5 m 1.202 -> 1.190 ms on its fastest set and ~1 % on all
     // others, the dense kernel of cfg2 at 0.1 m 4772 -> 4705 us, cfg3 394 -> 387 us -- four for launches of a few rounds (the headline's
     // 14 120 chunks: 31.9 us, 34.3 with eight) and for the spans at the reference's sampling (STAGED): cfg5 gains 2-5 % with eight on the
     // slow allocations (2.40 -> 2.33, 2.61 -> 2.55 ms) and loses 1 % on the fast ones (2.045 -> 2.07 ms), which calibration finds; two per
     // workgroup: +11 % on cfg5.
-    const int wpb_k = tune_int("FCPP_QUIET_WPB", 0);
-    const int wpb = wpb_k == 8 || wpb_k == 4 ? wpb_k : (n_chunks >= 65536 && !(kinds == 16 && staged) ? 8 : 4);
+    const int wpb = n_chunks >= 65536 && !(kinds == 16 && staged) ? 8 : 4;
     const dim3 grid((unsigned)((n_chunks + wpb - 1) / wpb)), block(64 * wpb);
     // Resident waves of the span kernel are held to FOUR per SIMD by its LDS footprint (34 KiB per four-wave workgroup of 160 KiB per
-    // CU): measured on identical memory (tools/ab_knob.py) cfg5 1.33 vs 1.44 ms at 5-7 waves and 1.59 ms at 3; the other
+    // CU): measured on identical memory cfg5 1.33 vs 1.44 ms at 5-7 waves and 1.59 ms at 3; the other
     // configurations do not care (+-1 %) -- except launches of a few rounds of workgroups, where FIVE per SIMD (27 KiB) end a round
     // earlier: the headline's 3530 workgroups 31.9 vs 33.2 us, step 0.0819 vs 0.0837 ms; cfg2 at the reference's sampling, 2064
     // workgroups, the same either way -- until round 3 put this kernel first in the step: since then four per SIMD are the faster choice
     // there too (headline 31.2 vs 31.8 us, step 0.0679 vs 0.0685 ms; cfg2 at the reference's sampling 23.4 vs 23.6 us).
-    // FCPP_SPAN_LDS / FCPP_QUIET_PAD: bytes, for that tool.
     const int static_lds = (has_obs ? wpb * 2 * OBS_LDS_VERTS * 8 : 32) + (kinds == 16 && staged ? wpb * 3 * TMPL_LDS * 8 : 32);
     const int span_lds = 34 * 1024 * wpb / 4;
-    const int pad = std::min(64 * 1024, kinds == 16 ? std::max(0, tune_int("FCPP_SPAN_LDS", span_lds) - static_lds) : std::max(0, tune_int("FCPP_QUIET_PAD", 0)));
+    const int pad = kinds == 16 ? std::min(64 * 1024, std::max(0, span_lds - static_lds)) : 0;
 #define FCPP_QUIET(K, SD, TL, OB) do { if (wpb == 8) FCPP_LAUNCH((k_plan_quiet<K, SD, TL, OB, 8>), grid, block, pad, st, chunks, fields, prims, cst, obs, x, y, kappa, v, fs, partial, n_chunks); \
                                        else FCPP_LAUNCH((k_plan_quiet<K, SD, TL, OB, 4>), grid, block, pad, st, chunks, fields, prims, cst, obs, x, y, kappa, v, fs, partial, n_chunks); } while (0)
     // Instances: spans fetch their descriptors by scalar loads (SCALAR_DESC: that nearly halved their time in round 1), stage the
@@ -878,21 +876,14 @@ int launch_plan_quiet(hipStream_t st, int64_t n_chunks, const DevTile *chunks, i
     return e == hipSuccess ? 0 : (int)e;
 }
 
-int launch_plan_fused(hipStream_t st, int variant, int64_t n_tiles, const int32_t *ids, const DevTile *tiles,
+int launch_plan_fused(hipStream_t st, int64_t n_tiles, const int32_t *ids, const DevTile *tiles,
                       const DevField *fields, const DevPrim *prims, const DevConst &cst, const DevObstacles &obs, double *x,
                       double *y, double *kappa, double *v, uint32_t *fs, TilePartial *partial)
 {
     if (n_tiles <= 0) return 0;
-    // variant = register budget: minimum waves per SIMD the compiler must allow (3 -> <=168 VGPRs, 4 -> <=128, 2 -> <=256)
-    if (variant == 4)
-        FCPP_LAUNCH(k_plan_fused<4>, dim3((unsigned)n_tiles), dim3(FBLOCK), 0, st, tiles, fields, prims, cst, obs, x, y,
-                           kappa, v, fs, partial, ids);
-    else if (variant == 2)
-        FCPP_LAUNCH(k_plan_fused<2>, dim3((unsigned)n_tiles), dim3(FBLOCK), 0, st, tiles, fields, prims, cst, obs, x, y,
-                           kappa, v, fs, partial, ids);
-    else
-        FCPP_LAUNCH(k_plan_fused<3>, dim3((unsigned)n_tiles), dim3(FBLOCK), 0, st, tiles, fields, prims, cst, obs, x, y,
-                           kappa, v, fs, partial, ids);
+    // register budget: at least three waves per SIMD (<= 168 VGPRs)
+    FCPP_LAUNCH(k_plan_fused<3>, dim3((unsigned)n_tiles), dim3(FBLOCK), 0, st, tiles, fields, prims, cst, obs, x, y,
+                kappa, v, fs, partial, ids);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -3,9 +3,9 @@
 // At the reference's own sampling (2 points per swath line, 20 per U-turn, 15 per corner arc, 20 per headland side, MLP:761-767,
 // 807, 1046, 1013) consecutive samples are metres apart: a sweep constraint reaches over a handful of POINTS, not hundreds, and a
 // lane that owns eight consecutive points (fcpp_fused.hip) walks across two or three primitives.  Here a wavefront owns a
-// "wave tile": up to 64 consecutive points of one field,
-//         [ Hb halo lanes | count output lanes | Hf halo lanes ]          Hb + count + Hf <= 64
-// lane l evaluates point first + l once, neighbours come from the adjacent lanes, and everything a point needs -- chords,
+// "wave tile": up to 128 consecutive points of one field, two per lane (fcpp_sparse2_fn.h),
+//         [ Hb halo points | count output points | Hf halo points ]          Hb + count + Hf <= 128
+// lane l evaluates points first + 2l and first + 2l + 1 once, neighbours come from the adjacent lanes, and everything a point needs -- chords,
 // curvature, clamp, the two min-plus scans, segment metrics -- is a handful of instructions per lane with no loop over items,
 // no LDS and no workgroup barrier.  The halo lanes make the tile self-contained: the HOST chooses them (Tiling::wave_tiles in
 // fcpp_api.cpp, from the same primitives and turn templates) so that
@@ -23,8 +23,8 @@ namespace fcpp {
 
 // SP_WAVES wave tiles per workgroup (independent of each other: no barrier).  Four for launches of a few rounds of workgroups (the
 // headline's 32 768 tiles: 41 us, 43 with two, 45-48 with one), two for long launches (cfg5's 622 016 tiles: 661-682 us, 674-688 with four,
-// 737-752 with eight); measured on the same box, tools/ab_knob.py per build.
-// PTS: points per lane -- 1: wave tiles of up to 64 points (sparse_tile), 2: of up to 128 (sparse_tile2, fcpp_sparse2_fn.h)
+// 737-752 with eight); measured on the same box.
+// PTS: points per lane -- 2: wave tiles of up to 128 points (sparse_tile2, fcpp_sparse2_fn.h)
 template <int SP_WAVES, int PTS>
 __global__ __launch_bounds__(64 * SP_WAVES) void k_plan_sparse(const DevWaveTile *__restrict__ wtiles, const int32_t *__restrict__ ids, int64_t n_wtiles,
                                                                const DevField *__restrict__ fields, const DevPrim *__restrict__ prims,
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void k_plan_sparse(const DevWaveTile
     // XCD-aware order (round 5): workgroups go round robin to the chip's eight XCDs, each with an L2 of its own, and the tiles of ONE field
     // -- five on cfg5, side by side in the list -- read the same field record and primitives: workgroup b takes the slots of position
     // (b mod 8) x (grid / 8) + b / 8, so that every XCD walks one contiguous eighth of the list and a field's records are fetched into one
-    // L2 instead of five (the grid is a multiple of eight: launch_plan_sparse)
+    // L2 instead of five (the grid is a multiple of eight and xcd_map is 1: launch_plan_sparse; 0 would take slot b)
     const unsigned bid = xcd_map ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const int64_t slot = (int64_t)bid * SP_WAVES + wave;
     if (slot >= n_wtiles) return;
@@ -47,8 +47,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void k_plan_sparse(const DevWaveTile
     const DevWaveTile wt = wtiles[ids ? (int64_t)ids[slot] : slot];      // (ids: the wave tiles of the fields k_plan_sparse_fields does not take)
     SparseAcc acc;
     acc.clear();
-    if (PTS == 2) sparse_tile2<false>(wt, fields[wt.field], prims, cst, obs, obs_lds[wave], atab, plds[wave], xo, yo, ko, vo, fso, acc);
-    else sparse_tile(wt, fields[wt.field], prims, cst, obs, obs_lds[wave], atab, plds[wave], xo, yo, ko, vo, fso, acc);
+    sparse_tile2<false>(wt, fields[wt.field], prims, cst, obs, obs_lds[wave], atab, plds[wave], xo, yo, ko, vo, fso, acc);
 
     // the tile's partial statistics: the three sums of a layer (and the three maxima) go through the wave together (wave4_to_hi),
     // groups in which every lane holds zero (the other layer, tiles without curvature) are skipped by a ballot
@@ -212,15 +211,6 @@ __global__ __launch_bounds__(64 * W) void k_plan_sparse_fields(const DevFieldPac
 {
     plan_sparse_fields_body<W, OBS, SPANS>(packs, cst, xo, yo, ko, vo, fso, obs, partial, totals, stats);
 }
-// the same held to eight resident wavefronts per SIMD (the excess registers spilled): A/B under FCPP_TUNE=1 FCPP_FW_OCC8=1
-template <int W, bool OBS, bool SPANS>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_plan_sparse_fields_occ8(const DevFieldPack *__restrict__ packs, DevConst cst, double *__restrict__ xo, double *__restrict__ yo,
-                                                              double *__restrict__ ko, double *__restrict__ vo, uint32_t *__restrict__ fso,
-                                                              DevObstacles obs, TilePartial *__restrict__ partial,
-                                                              const TilePartial *__restrict__ totals, fcpp_field_stats *__restrict__ stats)
-{
-    plan_sparse_fields_body<W, OBS, SPANS>(packs, cst, xo, yo, ko, vo, fso, obs, partial, totals, stats);
-}
 
 // Batch creation: per field of field_work, the closed-form statistics of its quiet runs (their slots, k_run_consts) summed in the order of
 // the field's entries -- the same at every step, so k_plan_sparse_fields adds its tiles' results to ONE record instead of walking the slots
@@ -259,8 +249,7 @@ int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack
 #define FCPP_FW(K, W, OB, SP) FCPP_LAUNCH((K<W, OB, SP>), dim3((unsigned)n_work), dim3(64 * W), 0, st, packs, cst, x, y, kappa, v, fs, obs, partial, totals, stats)
     if (waves != 4) return (int)hipErrorInvalidValue;       // (instances for 5, 6, 8 wavefronts: measured slower than the open list, fcpp_internal.h)
     const bool has_obs = obs.offsets != nullptr;
-    if (tune_int("FCPP_FW_OCC8", 0) && !has_obs && !spans) FCPP_FW(k_plan_sparse_fields_occ8, 4, false, false);
-    else if (has_obs && spans) FCPP_FW(k_plan_sparse_fields, 4, true, true);
+    if (has_obs && spans) FCPP_FW(k_plan_sparse_fields, 4, true, true);
     else if (has_obs) FCPP_FW(k_plan_sparse_fields, 4, true, false);
     else if (spans) FCPP_FW(k_plan_sparse_fields, 4, false, true);
     else FCPP_FW(k_plan_sparse_fields, 4, false, false);
@@ -271,20 +260,13 @@ int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack
 
 int launch_plan_sparse(hipStream_t st, int64_t n_wtiles, const DevWaveTile *wtiles, const DevField *fields, const DevPrim *prims,
                        const DevConst &cst, const DevObstacles &obs, double *x, double *y, double *kappa, double *v, uint32_t *fs,
-                       TilePartial *partial, int points_per_lane, const int32_t *ids)
+                       TilePartial *partial, const int32_t *ids)
 {
     if (n_wtiles <= 0) return 0;
-    const bool two = points_per_lane == 2;
-    const int wpb_k = tune_int("FCPP_SPARSE_WPB", 0);         // (FCPP_TUNE=1 only: 2 or 4 wave tiles per workgroup, tools/ab_knob.py)
-    static const int xcd_map = getenv("FCPP_XCD_MAP") ? atoi(getenv("FCPP_XCD_MAP")) : 1;       // (0: workgroup b takes slot b -- the A/B)
-    auto grid8 = [&](int64_t per) { const int64_t g = (n_wtiles + per - 1) / per; return dim3((unsigned)(xcd_map ? (g + 7) / 8 * 8 : g)); };
-    if (wpb_k == 2 || (wpb_k != 4 && n_wtiles >= (two ? 65536 : 131072))) {
-        if (two) FCPP_LAUNCH((k_plan_sparse<2, 2>), grid8(2), dim3(128), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, xcd_map);
-        else FCPP_LAUNCH((k_plan_sparse<2, 1>), grid8(2), dim3(128), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, xcd_map);
-    } else {
-        if (two) FCPP_LAUNCH((k_plan_sparse<4, 2>), grid8(4), dim3(256), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, xcd_map);
-        else FCPP_LAUNCH((k_plan_sparse<4, 1>), grid8(4), dim3(256), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, xcd_map);
-    }
+    // (the grid rounded up to a multiple of eight for the XCD-aware order of k_plan_sparse)
+    auto grid8 = [&](int64_t per) { const int64_t g = (n_wtiles + per - 1) / per; return dim3((unsigned)((g + 7) / 8 * 8)); };
+    if (n_wtiles >= 65536) FCPP_LAUNCH((k_plan_sparse<2, 2>), grid8(2), dim3(128), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
+    else FCPP_LAUNCH((k_plan_sparse<4, 2>), grid8(4), dim3(256), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -1,8 +1,8 @@
 // fcpp_sparse2_fn.h -- the wave tile of fcpp_sparse.hip with TWO consecutive points per lane: a wavefront owns up to 128 consecutive
-// points of one field, lane l the points 2l ("a") and 2l + 1 ("b") of the tile.  Same arithmetic per point as sparse_tile
-// (fcpp_sparse_fn.h), so a point's results do not depend on which of the two plans it; what changes is the cost per point: the halo
-// points (about ten per tile, whatever its size), the lane moves (a's successor and b's predecessor are the lane's own registers) and
-// the wave-wide reductions of the statistics are paid once per 128 points instead of once per 64.
+// points of one field, lane l the points 2l ("a") and 2l + 1 ("b") of the tile.  Same arithmetic per point as k_plan_fused
+// (fcpp_pointfn.h); against one point per lane what changes is the cost per point: the halo points (about ten per tile, whatever its
+// size), the lane moves (a's successor and b's predecessor are the lane's own registers) and the wave-wide reductions of the statistics
+// are paid once per 128 points instead of once per 64.
 #pragma once
 #include "fcpp_sparse_fn.h"
 

@@ -97,7 +97,7 @@ struct FieldTiler {
     bool wave_tiles(int64_t a, int64_t b)
     {
         const DevField &F = *f;
-        const int WAVE_LANES = tc.wave_points;           // points of a wave tile (fcpp_sparse.hip: one wavefront per wave tile)
+        const int WAVE_LANES = CUT_WAVE_LANES;           // points of a wave tile (fcpp_sparse.hip: one wavefront per wave tile)
         const int64_t n = F.n_total;
         const double cap = tiler_halo_cap(tc.u_cap);
         // d[i - lo] = |p_i - p_(i-1)| for the stretch and WAVE_HALO_MAX + 2 points either side
@@ -241,7 +241,7 @@ struct FieldTiler {
         const int64_t len = b - a;
         if (len <= 0) return;
         // (a field of the closed-form cut: its one general stretch [span, n_total) -- cut as the device planner cuts it, or left to the general kernel)
-        const bool closed = tc.closed_cut && tc.wave_points == CUT_WAVE_LANES && b == f->n_total && a == cut_span_points(*f, tc.cut) && cut_applies(*f, tc.cut, a);
+        const bool closed = tc.closed_cut && b == f->n_total && a == cut_span_points(*f, tc.cut) && cut_applies(*f, tc.cut, a);
         if (closed) { if (wave_ok && wave_tiles_closed(a)) return; }
         else if (wave_ok && wave_tiles(a, b)) return;
         const int64_t k = (len + TILE_POINTS - 1) / TILE_POINTS, base = len / k, rem = len % k;
@@ -387,7 +387,7 @@ struct FieldTiler {
         const int64_t nw = out.w0[k_local + 1] - out.w0[k_local];
         bool general = false;
         for (int64_t i = t0; i < t1 && !general; ++i) general = T[(size_t)i].quiet == 0;
-        const bool is_work = tc.field_work && tc.wave_points == 128 && !general && nw >= 1 && nw <= std::min(tc.field_work_tiles, FIELD_WORK_TILES) && ne <= FIELD_WORK_ENTRIES;
+        const bool is_work = tc.field_work && !general && nw >= 1 && nw <= FIELD_WORK_TILES && ne <= FIELD_WORK_ENTRIES;
         if (is_work) {
             DevFieldWork w;
             memset(&w, 0, sizeof w);
@@ -591,7 +591,7 @@ int BatchTiler::plan_impl(const HostPlan &hp, const TileConsts &tc, const fcpp_p
         }
     });
     lay = ImageLayout();
-    lay.n_fields = n; lay.n_prims = hp.total_prims; lay.wave_tile_points = tc.wave_points;
+    lay.n_fields = n; lay.n_prims = hp.total_prims;
     for (int64_t b = 0; b < nb; ++b) {
         BlockTiles &bt = B[(size_t)b];
         bt.tile_base = lay.n_tiles; bt.wave_base = lay.n_wave; bt.general_base = lay.n_general; bt.stat_base = lay.n_stat;
@@ -709,21 +709,6 @@ void BatchTiler::fill(const HostPlan &hp, const fcpp_polys *polys, const ImageLa
                 }
             }
         });
-    }
-    // diagnostic (FCPP_CHUNK_SPREAD=S): the ORDER of the chunk lists permuted so that consecutive workgroups write chunks N/S apart
-    // instead of neighbours -- which memory the waves in flight cover at any moment (tools/placement_probe.py)
-    if (const char *e = lay.n_chunk_groups == 0 ? getenv("FCPP_CHUNK_SPREAD") : nullptr) {     // (host-written lists only: fcpp_api.cpp)
-        const int64_t S = atoll(e);
-        for (int pass = 0; pass < 2 && S > 1; ++pass) {
-            DevTile *L = at<DevTile>(dst, pass ? lay.span_chunks : lay.chunks);
-            const int64_t N = pass ? lay.n_span_chunks : lay.n_chunks;
-            if (N < 2 * S) continue;
-            int64_t P = N / S;
-            auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
-            while (gcd(P, N) != 1) ++P;
-            std::vector<DevTile> tmp(L, L + N);
-            for (int64_t i = 0; i < N; ++i) L[i] = tmp[(size_t)((__int128)i * P % N)];
-        }
     }
     fill_obstacles(polys, lay, dst);
 }

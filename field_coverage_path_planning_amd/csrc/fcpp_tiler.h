@@ -26,19 +26,17 @@ struct TileConsts {
     bool turn_quiet = false;                  // U-turns of this batch are closed form (closed_form_turns, fcpp_api.cpp)
     double two_a = 0.0, u_cap = 0.0, c_line = 0.0;     // 2 a_lon, (v_max / 3.6)^2, (v_work / 3.6)^2
     double fence_margin = 1e-7;               // a point whose edge functions are all at least this cannot be flagged by the device's geofence test (1e-7 - geofence_tol)
-    int wave_factor = 24;                     // wave tiles where wave_factor * 2a * line step >= u_cap
-    int wave_points = 128;                    // points per wave tile: 64 (one per lane) or 128 (two per lane, fcpp_sparse2_fn.h)
+    static constexpr int wave_factor = 24;    // wave tiles where wave_factor * 2a * line step >= u_cap
     bool field_work = true;                   // fields with few wave tiles and nothing else general: planned and reduced by one workgroup (DevFieldWork)
-    int field_work_tiles = FIELD_WORK_TILES;  // ... at most this many (<= FIELD_WORK_TILES)
     bool fuse_spans = true;                   // ... and that workgroup also writes the field's layer-1 span (its chunks are then not in k_plan_quiet's list)
-    int64_t reduce_wg_max = 1024;             // statistic entries one workgroup reduces; beyond: 64 workgroups + join
+    static constexpr int64_t reduce_wg_max = 1024;     // statistic entries one workgroup reduces; beyond: 64 workgroups + join
     bool closed_cut = false;                  // reference sampling: the general stretch of a field with a closed-form span is cut by fcpp_cutfn.h (as the device planner cuts it)
     CutConsts cut = {};                       // ... with these constants (host copies of the templates and their chord tables)
     // a field's complete passes (line + closed-form U-turn) form ONE span -- one run, one statistics entry, chunks decoded by (pass, offset) -- when
     // its lines' quiet zones are shorter than span_line_max; fields with obstacles keep 64 (their lines and turns stay runs of their own: a line's
     // chunks test the obstacles once per line, a span's chunks pair by pair -- cfg3: 0.36 vs 0.43 ms a step).  Round 5: unlimited for fields without
     // obstacles, whatever the sampling -- 2P - 1 runs per field become one (cfg2 at 0.5 m: a 20 MB image -> 6 MB, the plan call 3.1 -> 2.4 ms,
-    // the step itself 1.23 -> 1.10 ms); FCPP_DENSE_SPAN=0 keeps round 4's runs for the A/B.
+    // the step itself 1.23 -> 1.10 ms); FCPP_DENSE_SPAN=0 keeps round 4's runs (the reference of the sliced reduction's test).
     int64_t span_line_max = INT64_MAX;
     bool device_chunks = false;               // the chunk lists of k_plan_quiet are expanded on the device from chunk groups (fcpp_batch_create; false: written by the host, the checker)
 };
@@ -63,7 +61,6 @@ struct ImageLayout {
     int64_t n_work[4] = { 0, 0, 0, 0 };       // fields of field_work by class (field_work_class: wavefronts of the workgroup); n_field_work = their sum
     int64_t wave_fail[5] = { 0, 0, 0, 0, 0 }; // diagnostics: stretches refused for wave tiles, by reason
     int64_t wave_inside = 0;                  // wave tiles whose outputs the host found inside the geofence
-    int wave_tile_points = 64;                // points per wave tile (TileConsts.wave_points)
 };
 
 // offsets of the tables from their counts; the obstacle part of the image (both also used by the device-side setup, fcpp_api.cpp)

@@ -106,7 +106,6 @@ int main(int argc, char **argv)
         TileConsts tc;
         tc.tu = tu.data(); tc.tc = tcn.data(); tc.nu = tt.nu; tc.nc = tt.nc; tc.templates_ok = true;
         tc.turn_quiet = pick(4) != 0;
-        tc.wave_points = pick(3) ? 128 : 64;
         tc.field_work = pick(4) != 0;
         tc.fuse_spans = tc.field_work && tt.nu <= TMPL_LDS_SAMPLES && pick(3) != 0;
         const double vm = 15.0 / 3.6;
@@ -117,7 +116,7 @@ int main(int argc, char **argv)
         std::vector<Pt2> dku((size_t)tt.nu), dkc((size_t)tt.nc);
         for (int k = 1; k < tt.nu; ++k) { const double dx = tu[(size_t)k].x - tu[(size_t)k - 1].x, dy = tu[(size_t)k].y - tu[(size_t)k - 1].y; dku[(size_t)k] = { sqrt(dx * dx + dy * dy), 0.0 }; }
         for (int k = 1; k < tt.nc; ++k) { const double dx = tcn[(size_t)k].x - tcn[(size_t)k - 1].x, dy = tcn[(size_t)k].y - tcn[(size_t)k - 1].y; dkc[(size_t)k] = { sqrt(dx * dx + dy * dy), 0.0 }; }
-        tc.closed_cut = opt.sample_spacing == 0.0 && opt.obstacle_mode == FCPP_OBSTACLES_FLAG && tc.wave_points == CUT_WAVE_LANES && pick(5) != 0;
+        tc.closed_cut = opt.sample_spacing == 0.0 && opt.obstacle_mode == FCPP_OBSTACLES_FLAG && pick(5) != 0;
         {
             CutConsts &cc = tc.cut;
             memset(&cc, 0, sizeof cc);
@@ -189,7 +188,7 @@ int main(int argc, char **argv)
             if (w.tile < 0 || w.tile >= lay.n_stat || w.field < 0 || w.field >= n || w.tile < SF[w.field] || w.tile >= SF[w.field + 1]) FAIL("wave tile %lld: statistics entry", (long long)k);
             const int32_t wtile = SI[w.tile];
             if (wtile < 0 || wtile >= lay.n_tiles || T[wtile].quiet != 5 || T[wtile].field != w.field || T[wtile].count != w.count) FAIL("wave tile %lld: slot", (long long)k);
-            if (w.hb + w.count + w.hf > tc.wave_points || w.field < 0 || w.field >= n) FAIL("wave tile %lld: lanes", (long long)k);
+            if (w.hb + w.count + w.hf > CUT_WAVE_LANES || w.field < 0 || w.field >= n) FAIL("wave tile %lld: lanes", (long long)k);
             const int64_t first = w.out_base - F[w.field].pt_off;
             if (first < 0 || first + w.hb != T[wtile].start || first + w.hb + w.count + w.hf > F[w.field].n_total) FAIL("wave tile %lld: range", (long long)k);
             if (!mark(w.field, first + w.hb, w.count, "wave tile")) FAIL("wave tile %lld", (long long)k);

@@ -64,7 +64,7 @@ def _run_tiler(driver, seed, rounds, **env):
 
 
 @pytest.mark.parametrize('seed', [1, 2])
-def test_batch_image_is_complete_and_independent_of_threads_and_sharing(tiler_driver, seed):
+def test_batch_image_with_128_point_wave_tiles_is_complete_and_independent_of_threads_and_sharing(tiler_driver, seed):
     """The image fcpp_batch_create uploads: (1) every path point of every field is planned by exactly one general tile, wave tile
     or chunk, all indices in bounds (checked inside the driver); (2) byte-identical for 1, 3 and 8 host threads; (3) the same per-field
     content whether equal fields share one plan (the headline's 4096 equal fields) or are planned one by one."""

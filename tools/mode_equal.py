@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Check that pipeline modes give bit-identical arrays and stats on the bench workload (smaller batch): mode_equal.py 1 31 32"""
+"""Check that pipeline modes give bit-identical arrays and stats on the bench workload (smaller batch): mode_equal.py 1 0"""
 import os
 import sys
 
