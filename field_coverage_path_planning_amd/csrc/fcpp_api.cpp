@@ -226,18 +226,6 @@ struct fcpp_ctx {
     std::vector<hipEvent_t> ev_pool;                // setup events of destroyed batches (fcpp_batch::ev_setup), reused: no event is created per plan call
 };
 
-// device pointers of a batch's tables: all inside ONE allocation laid out by the tiler (fcpp_tiler.h: ImageLayout)
-struct FusedTables {
-    DevField *fields = nullptr; DevPrim *prims = nullptr; DevTile *tiles = nullptr; DevWaveTile *wave_tiles = nullptr;
-    int32_t *general_ids = nullptr; DevTile *chunks = nullptr, *span_chunks = nullptr;
-    int32_t *stat_ids = nullptr; int64_t *stat_first = nullptr, *stat_run = nullptr; int32_t *red_paths = nullptr;
-    DevFieldWork *field_work = nullptr; DevFieldPack *field_packs = nullptr; int32_t *open_wave_ids = nullptr;
-    int64_t *obs_off = nullptr; double *obs_x = nullptr, *obs_y = nullptr, *obs_bbox = nullptr;
-    double *seg = nullptr; int32_t *seg_mask = nullptr;
-    TilePartial *partial = nullptr; char *red_scratch = nullptr; double2 *field_junc = nullptr;
-    TilePartial *work_totals = nullptr;
-};
-
 struct fcpp_batch {
     fcpp_ctx *ctx = nullptr;
     fcpp_vehicle veh;
@@ -246,8 +234,8 @@ struct fcpp_batch {
     HostPlan hp;               // info + field descriptors (the blocks' primitive lists are dropped once the image is built)
     DevConst cst;
     void *slab = nullptr; size_t slab_bytes = 0;
-    ImageLayout lay;           // counts and offsets of the tables in the slab
-    FusedTables t;             // fused pipeline (mode 1): quiet runs, wave tiles, general tiles, reduction lists
+    ImageLayout lay;           // counts and offsets of the tables in the slab (fcpp_slab.h)
+    SlabTables t;              // ... and pointers to them: bind_tables(lay, slab)
     DevTiling til0;            // staged pipeline (mode 0): plain near-equal tiles, built on its first run
     bool til0_built = false;
     std::shared_ptr<TemplateSet> templates;
@@ -354,8 +342,7 @@ static void free_paths_cache(fcpp_ctx *c);
 
 // the constants of the closed-form cut (fcpp_cutfn.h) for a batch: the templates and their chord tables as the HOST copies or as the device
 // arrays (the same values), the rest from the batch's constants (closed_form_turns has run)
-static CutConsts make_cut_consts(TemplateSet &ts, bool device, bool turn_quiet, int wave_factor, double two_a, double u_cap, double c_line,
-                                 double fence_margin, const DevConst &cst)
+static CutConsts make_cut_consts(TemplateSet &ts, bool device, const BatchTileConsts &k, const DevConst &cst)
 {
     CutConsts cc;
     memset(&cc, 0, sizeof cc);
@@ -367,8 +354,8 @@ static CutConsts make_cut_consts(TemplateSet &ts, bool device, bool turn_quiet, 
         cc.tu = reinterpret_cast<const Pt2 *>(ts.h_tu.data()); cc.tc = reinterpret_cast<const Pt2 *>(ts.h_tc.data());
         cc.dk_u = reinterpret_cast<const Pt2 *>(ts.h_dk.data()); cc.dk_c = reinterpret_cast<const Pt2 *>(ts.h_dkc.data());
     }
-    cc.nu = ts.tt.nu; cc.nc = ts.tt.nc; cc.turn_quiet = turn_quiet ? 1 : 0; cc.wave_factor = wave_factor;
-    cc.two_a = two_a; cc.u_cap = u_cap; cc.c_line = c_line; cc.fence_margin = fence_margin;
+    cc.nu = k.nu; cc.nc = k.nc; cc.turn_quiet = k.turn_quiet ? 1 : 0; cc.wave_factor = k.wave_factor;
+    cc.two_a = k.two_a; cc.u_cap = k.u_cap; cc.c_line = k.c_line; cc.fence_margin = k.fence_margin;
     cc.jump[0] = cst.turn_jump[0]; cc.jump[1] = cst.turn_jump[1];
     for (int d = 0; d < 2; ++d) { cc.tc_lo[d] = ts.tc_lo[d]; cc.tc_hi[d] = ts.tc_hi[d]; }
     // the shortest chord of either template (host copies of the device's chord tables: the same values whichever side cuts)
@@ -737,30 +724,6 @@ namespace {
 thread_local double g_trace_totals_ms = 0.0;      // (FCPP_TRACE_PLAN: when the last device setup saw its totals, ms since try_device_setup began)
 constexpr int kNotOnDevice = 1;      // try_device_setup: this batch is the host's (reason in err)
 
-// pointers of the fused pipeline's tables inside the slab
-void bind_tables(fcpp_batch *b)
-{
-    unsigned char *d = static_cast<unsigned char *>(b->slab);
-    const ImageLayout &lay = b->lay;
-    FusedTables &t = b->t;
-    t.fields = reinterpret_cast<DevField *>(d + lay.fields); t.prims = reinterpret_cast<DevPrim *>(d + lay.prims);
-    t.tiles = reinterpret_cast<DevTile *>(d + lay.tiles); t.wave_tiles = reinterpret_cast<DevWaveTile *>(d + lay.wtiles);
-    t.general_ids = reinterpret_cast<int32_t *>(d + lay.general_ids);
-    t.chunks = reinterpret_cast<DevTile *>(d + lay.chunks); t.span_chunks = reinterpret_cast<DevTile *>(d + lay.span_chunks);
-    t.stat_ids = reinterpret_cast<int32_t *>(d + lay.stat_ids); t.stat_first = reinterpret_cast<int64_t *>(d + lay.stat_first);
-    t.stat_run = reinterpret_cast<int64_t *>(d + lay.stat_run); t.red_paths = reinterpret_cast<int32_t *>(d + lay.red_paths);
-    t.field_work = reinterpret_cast<DevFieldWork *>(d + lay.field_work); t.field_packs = reinterpret_cast<DevFieldPack *>(d + lay.field_packs);
-    t.open_wave_ids = reinterpret_cast<int32_t *>(d + lay.open_wave_ids);
-    if (lay.n_polys > 0) {
-        t.obs_off = reinterpret_cast<int64_t *>(d + lay.obs_off); t.obs_x = reinterpret_cast<double *>(d + lay.obs_x);
-        t.obs_y = reinterpret_cast<double *>(d + lay.obs_y); t.obs_bbox = reinterpret_cast<double *>(d + lay.obs_bbox);
-    }
-    t.seg = reinterpret_cast<double *>(d + lay.seg); t.seg_mask = reinterpret_cast<int32_t *>(d + lay.seg_mask);
-    t.partial = reinterpret_cast<TilePartial *>(d + lay.partial); t.red_scratch = d ? reinterpret_cast<char *>(d + lay.red_scratch) : nullptr;
-    t.field_junc = reinterpret_cast<double2 *>(d + lay.field_junc);
-    t.work_totals = reinterpret_cast<TilePartial *>(d + lay.work_totals);
-}
-
 // the batch's device allocation: the context's spare if it is large enough
 int take_slab(fcpp_ctx *c, fcpp_batch *b, std::string &err)
 {
@@ -826,8 +789,7 @@ int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, D
     }
     sl.stream = st; sl.tick = ++c->plan_tick;
     c->plan_cur = k;
-    DevPlanScratch off;
-    const size_t need = devplan_scratch_layout(n_fields, max_prims, &off);
+    const size_t need = devplan_scratch_layout(n_fields, max_prims, nullptr, s);
     if (sl.cap < need) {
         if (sl.p) { DEVCHK(hipDeviceSynchronize()); (void)hipFree(sl.p); sl.p = nullptr; sl.cap = 0; }
         const size_t want = need + need / 4;
@@ -838,12 +800,7 @@ int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, D
     }
     if (!c->plan_totals_host)
         { DEVCHK(hipHostMalloc((void **)&c->plan_totals_host, PLAN_TOTALS * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->plan_totals_host, 0, PLAN_TOTALS * sizeof(int64_t)); }
-    unsigned char *sb = static_cast<unsigned char *>(sl.p);
-    s.fields_in = reinterpret_cast<fcpp_field *>(sb + (size_t)off.fields_in); s.info = reinterpret_cast<fcpp_field_info *>(sb + (size_t)off.info);
-    s.fields_tmp = reinterpret_cast<DevField *>(sb + (size_t)off.fields_tmp); s.prims_tmp = reinterpret_cast<DevPrim *>(sb + (size_t)off.prims_tmp);
-    s.counts = reinterpret_cast<int64_t *>(sb + (size_t)off.counts); s.bases = reinterpret_cast<int64_t *>(sb + (size_t)off.bases);
-    s.blk_sums = reinterpret_cast<int64_t *>(sb + (size_t)off.blk_sums); s.totals = reinterpret_cast<int64_t *>(sb + (size_t)off.totals);
-    s.keep_tiles = reinterpret_cast<DevTile *>(sb + (size_t)off.keep_tiles); s.keep_wtiles = reinterpret_cast<DevWaveTile *>(sb + (size_t)off.keep_wtiles);
+    devplan_scratch_layout(n_fields, max_prims, sl.p, s);
     return FCPP_OK;
 }
 
@@ -870,6 +827,126 @@ int device_fields(const fcpp_field *fields, int64_t n_fields, hipStream_t st, co
     return FCPP_OK;
 }
 
+// What the host tiler and the device tiler both derive from the batch (set_batch_consts has run), computed once.
+void batch_tile_consts(const fcpp_batch &b, bool turn_quiet, bool field_work, int64_t span_line_max, BatchTileConsts &k)
+{
+    k.nu = b.templates->tt.nu; k.nc = b.templates->tt.nc;
+    k.turn_quiet = turn_quiet;
+    k.two_a = 2 * b.cst.a_lon; k.u_cap = b.cst.u_cap; k.c_line = b.cst.ms_work * b.cst.ms_work;
+    // (the device flags a point whose edge function is below -geofence_tol; host and device evaluate a point by the same formulas and
+    // differ by roundings of ~1e-12 m: 1e-7 m of slack is five orders of magnitude of safety -- and lets the points that lie ON the boundary,
+    // the ends of the reverse fills, three per field of the metric's size, pass with the default tolerance of 1e-6 m: with the millimetre of margin
+    // of rounds 2-3a those three points sent half of the headline's wave tiles through the geofence test)
+    k.fence_margin = 1e-7 - b.opt.geofence_tol;
+    k.fuse_spans = field_work && k.nu <= TMPL_LDS_SAMPLES;
+    k.span_line_max = span_line_max;
+}
+
+// the device tiler's constants: the shared ones, the templates on the device, the kernels' fixed parameters
+DevTileConsts dev_tile_consts(const BatchTileConsts &k, const fcpp_batch &b, int max_prims, bool dense, int64_t n_fields, int64_t gen)
+{
+    DevTileConsts tc;
+    tc.tu = reinterpret_cast<const Pt2 *>(b.templates->tmpl_u.p); tc.tc = reinterpret_cast<const Pt2 *>(b.templates->tmpl_c.p);
+    tc.nu = k.nu; tc.nc = k.nc; tc.turn_quiet = k.turn_quiet; tc.fuse_spans = k.fuse_spans; tc.span_line_max = k.span_line_max;
+    tc.two_a = k.two_a; tc.u_cap = k.u_cap; tc.c_line = k.c_line; tc.fence_margin = k.fence_margin;
+    tc.wave_factor = k.wave_factor; tc.field_work_tiles = FIELD_WORK_TILES; tc.reduce_wg_max = TileConsts::reduce_wg_max; tc.max_prims = max_prims;
+    tc.no_bases = 0; tc.speculative = 0; tc.closed_cut = dense ? 0 : 1; tc.dense = dense ? 1 : 0;
+    tc.gen = gen; tc.f0 = 0; tc.f1 = n_fields;
+    tc.cut = make_cut_consts(*b.templates, true, k, b.cst);
+    return tc;
+}
+
+// a device-built slab's layout before its counts: the fields, the obstacle table, fcpp_field_info in the slab
+void device_layout(ImageLayout &l, int64_t n_fields, const fcpp_polys *obstacles)
+{
+    l = ImageLayout();
+    l.n_fields = n_fields; l.info_on_device = true;
+    l.n_polys = obstacles ? obstacles->n_polys : 0; l.n_poly_verts = l.n_polys > 0 ? obstacles->offsets[l.n_polys] : 0;
+}
+
+// SPECULATIVE layout, for small batches (at most 8192 fields: the counting phase's one-scan form): by per-field CAPACITIES, before anything
+// has run, so that the fill pass can be enqueued right behind the last scan -- the host then waits for the totals (they size the output
+// arrays and the steps' launches) while the fill pass already runs, instead of the device waiting for the host's round trip in between.
+// A field beyond the capacities (PF_OVER_CAPACITY: more than eight wave tiles, a span of more than sixteen chunks: big fields, many
+// headland loops) makes the fill pass a no-op; the tables are then laid out from the totals and filled again, as for large batches.
+// Within a table the records lie packed either way: only where each table begins differs.
+void capacity_layout(ImageLayout &l, int64_t n_fields, const fcpp_polys *obstacles, int max_prims)
+{
+    device_layout(l, n_fields, obstacles);
+    const int64_t K = DEVPLAN_KEEP_TILES;
+    l.n_prims = n_fields * max_prims;
+    l.n_tiles = l.n_stat = n_fields * (1 + K); l.n_wave = l.n_general = l.n_open_wave = n_fields * K;
+    l.n_span_chunks = n_fields * SPEC_SPAN_CHUNKS; l.n_runs = n_fields;
+    l.n_red[0] = n_fields; l.n_work[0] = l.n_field_work = n_fields;
+    layout_image(l);
+}
+
+// what the tables hold, from the counting phase's totals (fuse: the spans of fields of field work are their workgroups')
+void counts_from_totals(ImageLayout &l, const int64_t *tot, bool fuse)
+{
+    l.n_prims = tot[PC_PRIMS];
+    l.n_tiles = tot[PC_TILES]; l.n_wave = tot[PC_WAVE]; l.n_general = tot[PC_GENERAL]; l.n_stat = tot[PC_STAT];
+    l.n_span_chunks = fuse ? tot[PC_SPAN_F] : tot[PC_SPAN]; l.n_runs = tot[PC_RUNS];
+    for (int k = 0; k < 4; ++k) l.n_red[k] = tot[PC_CLS0 + k];
+    l.n_work[0] = tot[PC_WORK]; l.n_field_work = tot[PC_WORK]; l.n_open_wave = tot[PC_OPEN];
+    l.quiet_points = tot[PC_SPAN_PTS] + tot[PC_CHUNK_PTS]; l.span_points = tot[PC_SPAN_PTS] - (fuse ? tot[PC_WORK_SPAN_PTS] : 0); l.work_span_points = fuse ? tot[PC_WORK_SPAN_PTS] : 0;
+    l.n_chunks = tot[PC_CHUNKS]; l.chunk_points = tot[PC_CHUNK_PTS]; l.wave_points = tot[PC_WAVE_PTS];
+    l.work_wave_points = tot[PC_WORK_WAVE_PTS]; l.wave_inside = tot[PC_WAVE_INSIDE];
+}
+
+// the batch's layout is decided and its slab is there: the tables' pointers, and the obstacle table into the slab
+int bind_and_upload_obstacles(fcpp_ctx *c, fcpp_batch *b, const fcpp_polys *obstacles, hipStream_t st, std::string &err)
+{
+    const ImageLayout &lay = b->lay;
+    b->t = bind_tables(lay, b->slab);
+    if (lay.n_polys <= 0) return FCPP_OK;
+    // (the obstacle region of the image -- it alone, offsets rebased -- through the context's pinned staging memory, pageable when that
+    // cannot be had; the copy out of the staging memory is asynchronous: the next writer of that memory drains this stream first)
+    const size_t o0 = lay.obs_off, o1 = lay.seg, nb = o1 - o0;
+    std::vector<unsigned char> tmp;
+    unsigned char *img = nullptr;
+    if (const int urc = upload_buffer(c, nb, nb + nb / 4, tmp, img, err); urc != FCPP_OK) return urc;
+    fill_obstacles(obstacles, lay, img, o0);
+    DEVCHK(hipMemcpyAsync(static_cast<unsigned char *>(b->slab) + o0, img, nb, hipMemcpyHostToDevice, st));
+    if (!tmp.empty()) DEVCHK(hipStreamSynchronize(st));
+    else { c->stage_stream = st; c->stage_busy = true; }
+    return FCPP_OK;
+}
+
+// the fill pass (it also computes what the host path launches k_field_junctions, k_run_consts and k_work_totals for, field by field)
+int enqueue_fill(fcpp_batch *b, hipStream_t st, const DevTileConsts &tc, const DevPlanScratch &s, std::string &err)
+{
+    b->cst.field_junc = b->t.field_junc;
+    const int frc = launch_devplan_fill(st, b->n_fields, tc, b->cst, s, b->t);
+    if (frc) { err = std::string("launch_devplan_fill: ") + hipGetErrorString((hipError_t)frc); return FCPP_EHIP; }
+    return FCPP_OK;
+}
+
+// The last scan has written the totals and the flags to `tot`, then the phase's generation number to tot[PX_DONE]: polled -- a word
+// of the host's own pinned memory, there a microsecond after the kernel wrote it -- with the drained stream as the fallback; a speculative
+// fill pass runs on.  No event behind the scan: a record between two kernels holds the second one back by 5 us.  Batches laid out from
+// their totals poll as well: nothing else is in the stream, and the poll sees the word ~10 us before a drained stream reports.
+int await_totals(const int64_t *tot, int64_t gen, hipStream_t st, std::chrono::steady_clock::time_point t_call, std::string &err)
+{
+    const volatile int64_t *done = tot + PX_DONE;
+    const auto t_poll = std::chrono::steady_clock::now();
+    bool seen = false;
+    for (int spin = 0; !seen; ++spin) {
+        seen = *done == gen;
+        if (!seen && (spin & 1023) == 1023 && ms_since(t_poll) > 2.0) break;
+    }
+    if (!seen) DEVCHK(hipStreamSynchronize(st));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    g_trace_totals_ms = ms_since(t_call);
+    // what the counting phase found: an error, a batch for the host after all, or FCPP_OK
+    if (tot[PC_COLS + PF_BAD_OBSTACLES] == gen) { err = "field obstacle range outside the polygon table"; return FCPP_ESIZE; }
+    if (tot[PC_COLS + PF_FALLBACK] == gen) { err = "a field beyond the device planner's limits (general stretch, primitives)"; return kNotOnDevice; }
+    if (tot[PC_POINTS] > kCountCap) { err = "batch too large"; return FCPP_ESIZE; }
+    if (tot[PC_PRIMS] > ((int64_t)1 << 26)) { err = "too many path primitives in one batch: split the batch"; return FCPP_ESIZE; }
+    if (tot[PC_TILES] > INT32_MAX) { err = "too many tiles in one batch: split the batch"; return FCPP_ESIZE; }
+    return FCPP_OK;
+}
+
 // FCPP_OK: the batch is set up (tables on the device, info on the host); kNotOnDevice: not this path's batch; else the error.
 // fresh_templates: the batch's template set is still on its way back from the device (cleared once this path has waited for it);
 // field_work, span_line_max: the batch's reference switches (fcpp_batch_create)
@@ -878,15 +955,13 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
 {
     const fcpp_options &opt = b->opt;
     fcpp_setup_times &tm = b->setup;
+    // ---- decline or accept
     if (c->setup_mode == FCPP_SETUP_HOST) { err = "host setup requested"; return kNotOnDevice; }
     if (n_fields <= 0) { err = "empty batch"; return kNotOnDevice; }
     // (a handful of fields: the device's chain of five dependent launches costs ~110 us whatever the batch, the host's plan + tiler + one copy
     // ~65 us + 3 us per field -- a single 500 x 200 m planner's plan call 0.49 -> 0.44 ms)
-    {
-        const char *e = getenv("FCPP_SMALL_BATCH");          // (fields below which `auto` takes the host: 0 sends every batch it can take to the device -- tools/fuzz_parity.py)
-        const int64_t small = e ? atoll(e) : 16;
-        if (c->setup_mode == FCPP_SETUP_AUTO && n_fields < small) { err = "a handful of fields: set up by the host"; return kNotOnDevice; }
-    }
+    const char *e_small = getenv("FCPP_SMALL_BATCH");    // (fields below which `auto` takes the host: 0 sends every batch it can take to the device -- tools/fuzz_parity.py)
+    if (c->setup_mode == FCPP_SETUP_AUTO && n_fields < (e_small ? atoll(e_small) : 16)) { err = "a handful of fields: set up by the host"; return kNotOnDevice; }
     const bool dense = opt.sample_spacing != 0.0;          // (round 5: span + quiet runs of the straights + general tiles, k_tile_fields' dense block)
     if (opt.obstacle_mode != FCPP_OBSTACLES_FLAG) { err = "obstacle-aware swaths are planned on the host"; return kNotOnDevice; }
     if (!field_work) { err = "FCPP_FIELD_WORK=0: the host tiler's reference path"; return kNotOnDevice; }
@@ -900,146 +975,57 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
     auto t0 = std::chrono::steady_clock::now();
     const auto t_call = t0;
 
-    // templates on the host (closed-form test); a fresh set is on its way back
+    // ---- constants and scratch.  Templates on the host (closed-form test); a fresh set is on its way back
     if (fresh_templates) { DEVCHK(hipStreamSynchronize(st)); fresh_templates = false; }
     c->templates = b->templates;
-    const TemplateSet &ts = *b->templates;
-    const bool turn_quiet = set_batch_consts(b, ts);
+    const bool turn_quiet = set_batch_consts(b, *b->templates);
     tm.templates_ms += ms_since(t0);
 
-    // scratch + the field records
     t0 = std::chrono::steady_clock::now();
     DevPlanScratch s;
     if ((rc = plan_scratch(c, n_fields, pc.max_prims, st, s, err)) != FCPP_OK) return rc;
     const fcpp_field *dev_fields = nullptr;
     if ((rc = device_fields(fields, n_fields, st, s, dev_fields, err)) != FCPP_OK) return rc;
+    BatchTileConsts k;
+    batch_tile_consts(*b, turn_quiet, field_work, span_line_max, k);
+    DevTileConsts tc = dev_tile_consts(k, *b, pc.max_prims, dense, n_fields, ++c->plan_gen);
+    const int64_t *tot = c->plan_totals_host;
 
-    DevTileConsts tc;
-    tc.tu = reinterpret_cast<const Pt2 *>(ts.tmpl_u.p); tc.tc = reinterpret_cast<const Pt2 *>(ts.tmpl_c.p);
-    tc.nu = ts.tt.nu; tc.nc = ts.tt.nc;
-    tc.turn_quiet = turn_quiet; tc.wave_factor = 24; tc.field_work_tiles = FIELD_WORK_TILES; tc.max_prims = pc.max_prims;
-    tc.fuse_spans = ts.tt.nu <= TMPL_LDS_SAMPLES; tc.no_bases = 0;
-    tc.two_a = 2 * b->cst.a_lon; tc.u_cap = b->cst.u_cap; tc.c_line = b->cst.ms_work * b->cst.ms_work;
-    tc.fence_margin = 1e-7 - opt.geofence_tol;
-    tc.reduce_wg_max = 1024;
-    tc.cut = make_cut_consts(*b->templates, true, turn_quiet, tc.wave_factor, tc.two_a, tc.u_cap, tc.c_line, tc.fence_margin, b->cst);
-    const int64_t n_polys = obstacles ? obstacles->n_polys : 0;
-    tc.gen = ++c->plan_gen;
-    int64_t *tot = c->plan_totals_host;
-    // ---- the tables' layout.  SPECULATIVE for small batches (at most 8192 fields: the counting phase's one-scan form): laid out by per-field
-    // CAPACITIES before anything has run, so that the fill pass can be enqueued right behind the last scan -- the host then waits for the
-    // totals (they size the output arrays and the steps' launches) while the fill pass already runs, instead of the device waiting for the
-    // host's round trip in between.  A field beyond the capacities (PF_OVER_CAPACITY: more than eight wave tiles, a span of more than
-    // sixteen chunks: big fields, many headland loops) makes the fill pass a no-op; the tables are then laid out from the totals and filled
-    // again, as for large batches.  Within a table the records lie packed either way: only where each table begins differs.
+    // ---- speculative layout (capacity_layout), its slab and obstacle table
     ImageLayout &lay = b->lay;
-    auto common_layout = [&](ImageLayout &l) {
-        l = ImageLayout();
-        l.n_fields = n_fields; l.n_chunks = 0;
-        l.n_polys = n_polys; l.n_poly_verts = n_polys > 0 ? obstacles->offsets[n_polys] : 0;
-        l.info_on_device = true;
-    };
-    auto upload_obstacles = [&]() -> int {
-        if (lay.n_polys <= 0) return FCPP_OK;
-        // (the obstacle region of the image -- it alone, offsets rebased -- through the context's pinned staging memory, pageable when that
-        // cannot be had; the copy out of the staging memory is asynchronous: the next writer of that memory drains this stream first)
-        const size_t o0 = lay.obs_off, o1 = lay.seg, nb = o1 - o0;
-        std::vector<unsigned char> tmp;
-        unsigned char *img = nullptr;
-        if (const int urc = upload_buffer(c, nb, nb + nb / 4, tmp, img, err); urc != FCPP_OK) return urc;
-        fill_obstacles(obstacles, lay, img, o0);
-        DEVCHK(hipMemcpyAsync(static_cast<unsigned char *>(b->slab) + o0, img, nb, hipMemcpyHostToDevice, st));
-        if (!tmp.empty()) DEVCHK(hipStreamSynchronize(st));
-        else {
-            c->stage_stream = st; c->stage_busy = true;
-        }
-        return FCPP_OK;
-    };
-    DevPlanTables T;
-    auto launch_fill = [&]() -> int {
-        bind_tables(b);
-        T.fields = b->t.fields; T.prims = b->t.prims; T.tiles = b->t.tiles; T.wtiles = b->t.wave_tiles; T.general_ids = b->t.general_ids;
-        T.span_chunks = b->t.span_chunks; T.chunks = b->t.chunks; T.stat_ids = b->t.stat_ids; T.stat_first = b->t.stat_first; T.stat_run = b->t.stat_run;
-        T.red_paths = b->t.red_paths; T.field_work = b->t.field_work; T.field_packs = b->t.field_packs; T.open_wave_ids = b->t.open_wave_ids; T.seg = b->t.seg; T.seg_mask = b->t.seg_mask;
-        T.partial = b->t.partial; T.field_junc = b->t.field_junc; T.work_totals = b->t.work_totals;
-        T.info = reinterpret_cast<fcpp_field_info *>(static_cast<unsigned char *>(b->slab) + lay.info);
-        b->cst.field_junc = b->t.field_junc;
-        // (the fill pass also computes what the host path launches k_field_junctions, k_run_consts and k_work_totals for, field by field)
-        const int frc = launch_devplan_fill(st, n_fields, tc, b->cst, s, T);
-        if (frc) { err = std::string("launch_devplan_fill: ") + hipGetErrorString((hipError_t)frc); return FCPP_EHIP; }
-        return FCPP_OK;
-    };
     const bool exact_only = getenv("FCPP_SETUP_EXACT") != nullptr;              // (the checker of the speculative layout: tests/test_gpu_devplan.py)
     bool spec = (n_fields + 1023) / 1024 <= devplan_small_blocks() && !exact_only && !dense;
     if (spec) {
-        common_layout(lay);
-        const int64_t K = DEVPLAN_KEEP_TILES;
-        lay.n_prims = n_fields * pc.max_prims;
-        lay.n_tiles = lay.n_stat = n_fields * (1 + K); lay.n_wave = lay.n_general = lay.n_open_wave = n_fields * K;
-        lay.n_span_chunks = n_fields * SPEC_SPAN_CHUNKS; lay.n_runs = n_fields;
-        lay.n_red[0] = n_fields; lay.n_work[0] = lay.n_field_work = n_fields;
-        layout_image(lay);
+        capacity_layout(lay, n_fields, obstacles, pc.max_prims);
         if (lay.total_bytes > ((size_t)1 << 30)) spec = false;
     }
     tc.speculative = spec ? 1 : 0;
-    tc.closed_cut = dense ? 0 : 1;
-    tc.dense = dense ? 1 : 0;
-    tc.span_line_max = span_line_max;
     if (spec) {
         if ((rc = take_slab(c, b, err)) != FCPP_OK) return rc;
-        bind_tables(b);
-        if ((rc = upload_obstacles()) != FCPP_OK) return rc;
+        if ((rc = bind_and_upload_obstacles(c, b, obstacles, st, err)) != FCPP_OK) return rc;
     }
-    tc.f0 = 0; tc.f1 = n_fields;
-    int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, n_polys, obstacles != nullptr, tot);
+    // ---- count, and the speculative fill pass right behind it
+    const int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, obstacles ? obstacles->n_polys : 0, obstacles != nullptr, c->plan_totals_host);
     if (lrc) { (void)hipStreamSynchronize(st); err = std::string("launch_devplan_count: ") + hipGetErrorString((hipError_t)lrc); return FCPP_EHIP; }   // (drained: the caller's pinned records may still be read)
-    if (spec && (rc = launch_fill()) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
-    // (the last scan has written the totals and the flags to `tot`, then the phase's generation number to tot[PX_DONE]: polled -- a word
-    // of the host's own pinned memory, there a microsecond after the kernel wrote it -- with the drained stream as the fallback; a speculative
-    // fill pass runs on.  No event behind the scan: a record between two kernels holds the second one back by 5 us.  Batches laid out from
-    // their totals poll as well: nothing else is in the stream, and the poll sees the word ~10 us before a drained stream reports)
-    {
-        volatile int64_t *done = tot + PX_DONE;
-        const auto t_poll = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (int spin = 0; !seen; ++spin) {
-            seen = *done == tc.gen;
-            if (!seen && (spin & 1023) == 1023 && ms_since(t_poll) > 2.0) break;
-        }
-        if (!seen) DEVCHK(hipStreamSynchronize(st));
-        std::atomic_thread_fence(std::memory_order_acquire);
-        g_trace_totals_ms = ms_since(t_call);
-    }
+    if (spec && (rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    // ---- wait for the totals, checks
+    rc = await_totals(tot, tc.gen, st, t_call, err);
     tm.host_plan_ms = ms_since(t0);          // (the plan and the counting pass, on the device)
-    if (tot[PC_COLS + PF_BAD_OBSTACLES] == tc.gen) { err = "field obstacle range outside the polygon table"; return FCPP_ESIZE; }
-    if (tot[PC_COLS + PF_FALLBACK] == tc.gen) { err = "a field beyond the device planner's limits (general stretch, primitives)"; return kNotOnDevice; }
-    if (tot[PC_POINTS] > kCountCap) { err = "batch too large"; return FCPP_ESIZE; }
-    if (tot[PC_PRIMS] > ((int64_t)1 << 26)) { err = "too many path primitives in one batch: split the batch"; return FCPP_ESIZE; }
-    if (tot[PC_TILES] > INT32_MAX) { err = "too many tiles in one batch: split the batch"; return FCPP_ESIZE; }
+    if (rc != FCPP_OK) return rc;
 
     // the spans of fields of field work are written by the fields' own workgroups (k_plan_sparse_fields) when ALL of them are short enough for
     // that -- the span launch of such a batch disappears -- and by k_plan_quiet otherwise (a mix loses: measured on cfg2 at the reference's
     // sampling, a third of its spans fusable, 0.0435 instead of 0.0392 ms)
     t0 = std::chrono::steady_clock::now();
     const bool fuse = tc.fuse_spans && tot[PC_UNFUSABLE] == 0 && tot[PC_WORK_SPAN_PTS] > 0;
-    auto counts_from_totals = [&](ImageLayout &l) {
-        l.n_prims = tot[PC_PRIMS];
-        l.n_tiles = tot[PC_TILES]; l.n_wave = tot[PC_WAVE]; l.n_general = tot[PC_GENERAL]; l.n_stat = tot[PC_STAT];
-        l.n_span_chunks = fuse ? tot[PC_SPAN_F] : tot[PC_SPAN]; l.n_runs = tot[PC_RUNS];
-        for (int k = 0; k < 4; ++k) l.n_red[k] = tot[PC_CLS0 + k];
-        l.n_work[0] = tot[PC_WORK]; l.n_field_work = tot[PC_WORK]; l.n_open_wave = tot[PC_OPEN];
-        l.quiet_points = tot[PC_SPAN_PTS] + tot[PC_CHUNK_PTS]; l.span_points = tot[PC_SPAN_PTS] - (fuse ? tot[PC_WORK_SPAN_PTS] : 0); l.work_span_points = fuse ? tot[PC_WORK_SPAN_PTS] : 0;
-        l.n_chunks = tot[PC_CHUNKS]; l.chunk_points = tot[PC_CHUNK_PTS]; l.wave_points = tot[PC_WAVE_PTS];
-        l.work_wave_points = tot[PC_WORK_WAVE_PTS]; l.wave_inside = tot[PC_WAVE_INSIDE];
-    };
     if (spec && tot[PC_COLS + PF_OVER_CAPACITY] != tc.gen) {
-        counts_from_totals(lay);             // (the tables begin where the capacities put them; what they hold is what the totals say)
+        counts_from_totals(lay, tot, fuse);  // (the tables begin where the capacities put them; what they hold is what the totals say)
         tm.image_ms = ms_since(t0);
     } else {
-        // the image's layout from the totals, the allocation, the obstacle table, the fill pass
+        // ---- exact layout: from the totals, the allocation, the obstacle table, the fill pass
         ImageLayout ex;
-        common_layout(ex);
-        counts_from_totals(ex);
+        device_layout(ex, n_fields, obstacles);
+        counts_from_totals(ex, tot, fuse);
         layout_image(ex);
         if (b->slab && b->slab_bytes < ex.total_bytes) {       // (a speculative slab that is too small: its fill pass was a no-op, but it is in the stream)
             DEVCHK(hipStreamSynchronize(st));
@@ -1047,20 +1033,19 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         }
         lay = ex;
         if (!b->slab && (rc = take_slab(c, b, err)) != FCPP_OK) return rc;
-        bind_tables(b);
-        if ((rc = upload_obstacles()) != FCPP_OK) return rc;
+        if ((rc = bind_and_upload_obstacles(c, b, obstacles, st, err)) != FCPP_OK) return rc;
         tm.image_ms = ms_since(t0);
         t0 = std::chrono::steady_clock::now();
         tc.speculative = 0;
         tc.fuse_spans = fuse;
-        if ((rc = launch_fill()) != FCPP_OK) return rc;
+        if ((rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) return rc;
     }
     tm.image_bytes = (int64_t)((size_t)n_fields * sizeof(fcpp_field) + (lay.n_polys > 0 ? lay.seg - lay.obs_off : 0));
     c->plan_slots[c->plan_cur].pending = true;
     b->setup_stream = st; b->setup_pending = true;
     // fcpp_field_info stays on the device until somebody asks (fcpp_batch_info); the stream is NOT drained: a step enqueued next runs
     // right behind the setup
-    b->info_dev = T.info;
+    b->info_dev = b->t.info;
     b->hp.info.clear();
     b->hp.tt = tt;
     b->hp.total_points = tot[PC_POINTS]; b->hp.total_prims = tot[PC_PRIMS];
@@ -1146,25 +1131,17 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     // ---- 4. tiler: every field's path cut into work for the four kernels, blocks side by side (fcpp_tiler.cpp)
     t0 = std::chrono::steady_clock::now();
     TileConsts tc;
+    batch_tile_consts(*b, turn_quiet, field_work, span_line_max, tc);
     tc.tu = reinterpret_cast<const Pt2 *>(ts.h_tu.data()); tc.tc = reinterpret_cast<const Pt2 *>(ts.h_tc.data());
-    tc.nu = ts.tt.nu; tc.nc = ts.tt.nc; tc.templates_ok = true;
-    tc.turn_quiet = turn_quiet;
-    tc.two_a = 2 * b->cst.a_lon; tc.u_cap = b->cst.u_cap; tc.c_line = b->cst.ms_work * b->cst.ms_work;
-    // (the device flags a point whose edge function is below -geofence_tol; host and device evaluate a point by the same formulas and
-    // differ by roundings of ~1e-12 m: 1e-7 m of slack is five orders of magnitude of safety -- and lets the points that lie ON the boundary,
-    // the ends of the reverse fills, three per field of the metric's size, pass with the default tolerance of 1e-6 m: with the millimetre of margin
-    // of rounds 2-3a those three points sent half of the headline's wave tiles through the geofence test)
-    tc.fence_margin = 1e-7 - opt->geofence_tol;
+    tc.templates_ok = true;
     tc.field_work = field_work;
-    tc.fuse_spans = tc.field_work && ts.tt.nu <= TMPL_LDS_SAMPLES;
     // the chunk lists are expanded on the device from the host's chunk groups; FCPP_HOST_CHUNKS=1 (the checker, tests/test_gpu_devplan.py)
     // keeps the host's own lists
     tc.device_chunks = !(getenv("FCPP_HOST_CHUNKS") && atoi(getenv("FCPP_HOST_CHUNKS")) != 0);
     // the reference's sampling: the general stretch of every field with a closed-form span is cut in closed form (fcpp_cutfn.h), as the device
     // planner cuts it -- host-built and device-built tables stay equal byte for byte
     tc.closed_cut = opt->sample_spacing == 0.0 && opt->obstacle_mode == FCPP_OBSTACLES_FLAG;
-    tc.cut = make_cut_consts(*b->templates, false, turn_quiet, tc.wave_factor, tc.two_a, tc.u_cap, tc.c_line, tc.fence_margin, b->cst);
-    tc.span_line_max = span_line_max;
+    tc.cut = make_cut_consts(*b->templates, false, tc, b->cst);
     BatchTiler tiler;
     ImageLayout &lay = b->lay;
     rc = tiler.plan(b->hp, tc, obstacles, lay, err);
@@ -1188,7 +1165,7 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     rc = upload_buffer(c, lay.upload_bytes, std::min(kStageMax, std::max<size_t>(lay.upload_bytes + lay.upload_bytes / 4, (size_t)1 << 20)), pageable, img, err);
     if (rc != FCPP_OK) return fail(rc, err);
     tiler.fill(b->hp, obstacles, lay, img);
-    bind_tables(b.get());
+    b->t = bind_tables(lay, b->slab);
     // (the primitives live in the image now; the host keeps the per-field records for fcpp_batch_info and the staged pipeline's tiling)
     for (PlanBlock &blk : b->hp.blocks) std::vector<DevPrim>().swap(blk.prims);
     std::vector<int32_t>().swap(b->hp.same_as);
@@ -1201,7 +1178,7 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     if (n_fields > 0) {
         b->cst.field_junc = b->t.field_junc;
         LAUNCHCHK(launch_field_junctions(st, n_fields, b->t.fields, b->cst, b->t.field_junc));
-        LAUNCHCHK(launch_expand_chunks(st, lay.n_chunk_groups, reinterpret_cast<const DevChunkGroup *>(static_cast<unsigned char *>(b->slab) + lay.chunk_groups),
+        LAUNCHCHK(launch_expand_chunks(st, lay.n_chunk_groups, b->t.chunk_groups,
                                        b->t.tiles, b->t.fields, b->t.chunks, b->t.span_chunks));
         // the statistics slots: closed-form statistics of the quiet runs (the same at every step), zeros elsewhere
         LAUNCHCHK(launch_run_consts(st, lay.n_stat, b->t.stat_ids, b->t.stat_run, b->t.tiles, b->t.fields, b->t.prims, b->cst, b->t.partial));
@@ -1295,7 +1272,7 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
         if (e_ != 0) return fail(FCPP_EHIP, std::string(#call) + ": " + hipGetErrorString((hipError_t)e_)); \
     } while (0)
     if (mode == 1) {
-        const FusedTables &t = b->t;
+        const SlabTables &t = b->t;
         const ImageLayout &lay = b->lay;
         // Two streams inside the step where the general tiles are FEW and long-lived (dense sampling of a single large field: a dozen
         // tiles that walk long halos, cfg3: 5873 points in 0.37 ms): beside the HBM-bound streaming kernel they cost nothing (cfg3
@@ -1313,8 +1290,8 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
         }
         // the wave tiles of fields that k_plan_sparse_fields does not take (all of them when there are none of those)
         const bool fw = lay.n_field_work > 0;
-        if (!fw) STAGE(2, launch_plan_sparse(sd, lay.n_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial));
-        else STAGE(2, launch_plan_sparse(sd, lay.n_open_wave, t.wave_tiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial, t.open_wave_ids));
+        if (!fw) STAGE(2, launch_plan_sparse(sd, lay.n_wave, t.wtiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial));
+        else STAGE(2, launch_plan_sparse(sd, lay.n_open_wave, t.wtiles, t.fields, t.prims, b->cst, obs, x, y, kappa, v, fs, t.partial, t.open_wave_ids));
         STAGE(3, launch_plan_fused(sd, lay.n_general, t.general_ids, t.tiles, t.fields, t.prims, b->cst, obs, x,
                                    y, kappa, v, fs, t.partial));
         if (two) HIPCHK(hipEventRecord(b->ctx->ev_join, sd));
@@ -1389,7 +1366,7 @@ int fcpp_batch_plan(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *op
     rc = fcpp_outputs_alloc(c, total, 0, x, y, kappa, v, fs);
     const double t_alloc = trace ? ms_since(t_begin) : 0.0;
     if (rc == FCPP_OK) {
-        if (!stats && b->slab) stats = reinterpret_cast<fcpp_field_stats *>(static_cast<unsigned char *>(b->slab) + b->lay.own_stats);
+        if (!stats) stats = b->t.own_stats;
         rc = fcpp_batch_run(b, *x, *y, *kappa, *v, *fs, stats, 1);
         if (trace) fprintf(stderr, "[fcpp] plan call: entered at %.1f us (CLOCK_MONOTONIC mod 1 s), totals seen %.1f us, create returns %.1f, arrays %.1f, step enqueued %.1f\n",
                            (double)(std::chrono::duration_cast<std::chrono::nanoseconds>(t_begin.time_since_epoch()).count() % 1000000000ll) / 1e3,
@@ -1411,7 +1388,7 @@ int fcpp_batch_plan(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *op
 int fcpp_batch_own_stats(const fcpp_batch *b, fcpp_field_stats **stats)
 {
     if (!b || !stats) return fail(FCPP_EINVAL, "bad arguments");
-    *stats = b->slab ? reinterpret_cast<fcpp_field_stats *>(static_cast<unsigned char *>(b->slab) + b->lay.own_stats) : nullptr;
+    *stats = b->t.own_stats;
     return FCPP_OK;
 }
 
@@ -2043,26 +2020,20 @@ int fcpp_debug_math_dev(fcpp_ctx *c, int fn, int64_t n, const double *a, const d
 int fcpp_batch_debug_table(const fcpp_batch *b, int table, void *dst, int64_t cap, int64_t *bytes_out)
 {
     if (!b || !bytes_out) return fail(FCPP_EINVAL, "bad arguments");
-    const ImageLayout &l = b->lay;
-    const size_t n = (size_t)l.n_fields;
-    const size_t off[] = { l.fields, l.prims, l.tiles, l.wtiles, l.general_ids, l.chunks, l.span_chunks, l.stat_ids, l.stat_first, l.stat_run, l.red_paths,
-                           l.field_work, l.open_wave_ids, l.seg, l.seg_mask, l.partial, l.field_junc, l.work_totals, l.obs_off, l.obs_x, l.obs_y, l.obs_bbox, l.field_packs };
-    const size_t len[] = { n * sizeof(DevField), (size_t)l.n_prims * sizeof(DevPrim), (size_t)l.n_tiles * sizeof(DevTile), (size_t)l.n_wave * sizeof(DevWaveTile),
-                           (size_t)l.n_general * 4, (size_t)l.n_chunks * sizeof(DevTile), (size_t)l.n_span_chunks * sizeof(DevTile), (size_t)l.n_stat * 4,
-                           (n + 1) * 8, (size_t)l.n_stat * 8, n * 4, (size_t)l.n_field_work * sizeof(DevFieldWork), (size_t)l.n_open_wave * 4, n * 64, n * 8,
-                           (size_t)l.n_stat * sizeof(TilePartial), n * 16, (size_t)l.n_field_work * sizeof(TilePartial),
-                           l.n_polys > 0 ? (size_t)(l.n_polys + 1) * 8 : 0, (size_t)l.n_poly_verts * 8, (size_t)l.n_poly_verts * 8, (size_t)l.n_polys * 32,
-                           (size_t)l.n_field_work * sizeof(DevFieldPack) };
-    constexpr int kTables = (int)(sizeof(off) / sizeof(off[0]));
-    if (table < 0 || table >= kTables) return fail(FCPP_EINVAL, "no such table");
-    *bytes_out = (int64_t)len[table];
+    // (the numbers are the ABI's: tests/test_gpu_devplan.py lists them in this order)
+    static const SlabTable kTables[] = { ST_fields, ST_prims, ST_tiles, ST_wtiles, ST_general_ids, ST_chunks, ST_span_chunks, ST_stat_ids, ST_stat_first, ST_stat_run,
+                                         ST_red_paths, ST_field_work, ST_open_wave_ids, ST_seg, ST_seg_mask, ST_partial, ST_field_junc, ST_work_totals,
+                                         ST_obs_off, ST_obs_x, ST_obs_y, ST_obs_bbox, ST_field_packs };
+    if (table < 0 || table >= (int)(sizeof(kTables) / sizeof(kTables[0]))) return fail(FCPP_EINVAL, "no such table");
+    const SlabSpan sp = slab_table(b->lay, kTables[table]);
+    *bytes_out = (int64_t)sp.bytes;
     if (!dst) return FCPP_OK;
-    if (cap < (int64_t)len[table]) return fail(FCPP_ESIZE, "buffer too small");
-    if (len[table] == 0 || n == 0) return FCPP_OK;
+    if (cap < (int64_t)sp.bytes) return fail(FCPP_ESIZE, "buffer too small");
+    if (sp.bytes == 0 || b->lay.n_fields == 0) return FCPP_OK;
     HIPCHK(hipSetDevice(b->ctx->device));
     for (hipStream_t s : b->used_streams) HIPCHK(hipStreamSynchronize(s));          // (the setup's stream is one of them)
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
-    HIPCHK(hipMemcpy(dst, static_cast<const unsigned char *>(b->slab) + off[table], len[table], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dst, static_cast<const unsigned char *>(b->slab) + sp.off, sp.bytes, hipMemcpyDeviceToHost));
     return FCPP_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "fcpp_device.h"
 #include "fcpp_internal.h"
+#include "fcpp_slab.h"
 #include "fcpp_planfn.h"
 #include "fcpp_tilefn.h"
 #include "fcpp_cutfn.h"
@@ -79,17 +80,8 @@ struct DevPlanScratch {
     DevWaveTile *keep_wtiles;     // n x DEVPLAN_KEEP_WROWS
 };
 int64_t devplan_small_blocks();
-size_t devplan_scratch_layout(int64_t n, int max_prims, DevPlanScratch *offsets_as_pointers /* offsets from 0, cast to pointers */);
-
-// the tables the fill pass writes (pointers into the batch's slab, laid out by the host from the totals)
-struct DevPlanTables {
-    DevField *fields; DevPrim *prims; DevTile *tiles; DevWaveTile *wtiles; int32_t *general_ids; DevTile *span_chunks; DevTile *chunks;
-    int32_t *stat_ids; int64_t *stat_first, *stat_run; int32_t *red_paths; DevFieldWork *field_work; DevFieldPack *field_packs; int32_t *open_wave_ids;
-    double *seg; int32_t *seg_mask;
-    // what batch creation computes once from the tables (k_field_junctions, k_run_consts, k_work_totals on the host path), done by the
-    // field's own wavefront here; and the field's fcpp_field_info, kept with the batch for fcpp_batch_info
-    TilePartial *partial; double2 *field_junc; TilePartial *work_totals; fcpp_field_info *info;
-};
+// the scratch for n fields laid out at `base` (null: sizing only); returns its size in bytes
+size_t devplan_scratch_layout(int64_t n, int max_prims, void *base, DevPlanScratch &s);
 
 // the device tiler's LDS window over a field's general stretch (it slides), and the most primitives a field may have (8-bit indices in
 // that window); a batch whose vehicle needs more (31+ headland loops) is set up on the host
@@ -115,8 +107,8 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
 // planner, scan of the points, pass, scan of the other columns)
 // sizing only (fcpp_plan_points): k_plan_fields without primitives; counts[PC_POINTS][field] = points of the field
 int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const DevPlanScratch &s, const fcpp_field *fields);
-// phase 2: the tables.  `bases` / `totals` as phase 1 left them.
-int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const DevPlanTables &t);
+// phase 2: the tables (pointers into the batch's slab, laid out by the host).  `bases` / `totals` as phase 1 left them.
+int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &t);
 // fcpp_math.h on the device (tests): fn 0 sincos, 1 atan2(a, b), 2 acos(a), 3 hypot(a, b)
 int launch_debug_math(hipStream_t st, int fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
 

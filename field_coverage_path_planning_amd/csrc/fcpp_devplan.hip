@@ -9,23 +9,27 @@
 
 namespace fcpp {
 
-size_t devplan_scratch_layout(int64_t n, int max_prims, DevPlanScratch *o)
+size_t devplan_scratch_layout(int64_t n, int max_prims, void *base, DevPlanScratch &s)
 {
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t r = off; off = (off + bytes + 255) & ~(size_t)255; return r; };
+    auto take = [&](auto *&p, size_t count) { p = base ? reinterpret_cast<decltype(p + 0)>(static_cast<unsigned char *>(base) + off) : nullptr; off = (off + count * sizeof(*p) + 255) & ~(size_t)255; };
     const size_t nn = (size_t)(n > 0 ? n : 1), nblk = (nn + 1023) / 1024;
-    o->totals = reinterpret_cast<int64_t *>(take(PLAN_TOTALS * sizeof(int64_t)));      // (first: the flags keep their place whatever n is)
-    o->fields_in = reinterpret_cast<fcpp_field *>(take(nn * sizeof(fcpp_field)));
-    o->info = reinterpret_cast<fcpp_field_info *>(take(nn * sizeof(fcpp_field_info)));
-    o->fields_tmp = reinterpret_cast<DevField *>(take(nn * sizeof(DevField)));
-    o->prims_tmp = reinterpret_cast<DevPrim *>(take(nn * (size_t)max_prims * sizeof(DevPrim)));
-    o->counts = reinterpret_cast<int64_t *>(take(nn * PC_COLS * sizeof(int64_t)));
-    o->bases = reinterpret_cast<int64_t *>(take(nn * PC_COLS * sizeof(int64_t)));
-    o->blk_sums = reinterpret_cast<int64_t *>(take(nblk * PC_COLS * sizeof(int64_t)));
-    o->keep_tiles = reinterpret_cast<DevTile *>(take(nn * DEVPLAN_KEEP_ROWS * sizeof(DevTile)));
-    o->keep_wtiles = reinterpret_cast<DevWaveTile *>(take(nn * DEVPLAN_KEEP_WROWS * sizeof(DevWaveTile)));
+    take(s.totals, PLAN_TOTALS);      // (first: the flags keep their place whatever n is)
+    take(s.fields_in, nn); take(s.info, nn); take(s.fields_tmp, nn); take(s.prims_tmp, nn * (size_t)max_prims);
+    take(s.counts, nn * PC_COLS); take(s.bases, nn * PC_COLS); take(s.blk_sums, nblk * PC_COLS);
+    take(s.keep_tiles, nn * DEVPLAN_KEEP_ROWS); take(s.keep_wtiles, nn * DEVPLAN_KEEP_WROWS);
     return off;
 }
+
+// The fill pass's kernel argument: the tables it writes, in the order the kernels read them (a view of SlabTables, fcpp_slab.h).
+// (partial, field_junc, work_totals: what batch creation computes once from the tables -- k_field_junctions, k_run_consts, k_work_totals
+// on the host path --, done by the field's own wavefront here; info: the field's fcpp_field_info, kept with the batch for fcpp_batch_info)
+#define FCPP_FILL_TABLES(X)                                                                                                          \
+    X(fields) X(prims) X(tiles) X(wtiles) X(general_ids) X(span_chunks) X(chunks) X(stat_ids) X(stat_first) X(stat_run) X(red_paths) \
+    X(field_work) X(field_packs) X(open_wave_ids) X(seg) X(seg_mask) X(partial) X(field_junc) X(work_totals) X(info)
+#define X(name) decltype(SlabTables::name) name;
+struct DevPlanTables { FCPP_FILL_TABLES(X) };
+#undef X
 
 // blocks of 1024 fields up to which a batch is "small": ONE scan launch (a workgroup per column walks the fields in chunks of 4096) and
 // -- fcpp_api.cpp -- the speculative capacity layout
@@ -1709,9 +1713,12 @@ int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const
     return e == hipSuccess ? 0 : (int)e;
 }
 
-int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const DevPlanTables &t)
+int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &tables)
 {
     if (n <= 0) return 0;
+#define X(name) tables.name,
+    const DevPlanTables t = { FCPP_FILL_TABLES(X) };
+#undef X
     if (tc.dense)
         hipLaunchKernelGGL((k_tile_fields<true, true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
                            s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, t);

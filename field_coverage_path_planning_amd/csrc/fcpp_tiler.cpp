@@ -36,8 +36,6 @@ struct BlockTiles {
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // tiler of one block: scratch that lives across its fields
 struct FieldTiler {
     const HostPlan &hp;
@@ -494,50 +492,6 @@ T *at(unsigned char *base, size_t off) { return reinterpret_cast<T *>(base + off
 
 }  // namespace
 
-// the tables' places inside the image from their counts (n_fields, n_prims, n_tiles, ...): the same for an image built on the host and
-// one built on the device (fcpp_devplan.hip)
-void layout_image(ImageLayout &lay)
-{
-    size_t o = 0;
-    auto take = [&](size_t &slot, size_t bytes) { slot = o; o = align256(o + bytes); };
-    take(lay.fields, (size_t)lay.n_fields * sizeof(DevField));
-    take(lay.prims, (size_t)lay.n_prims * sizeof(DevPrim));
-    take(lay.tiles, (size_t)lay.n_tiles * sizeof(DevTile));
-    take(lay.wtiles, (size_t)lay.n_wave * sizeof(DevWaveTile));
-    take(lay.general_ids, (size_t)lay.n_general * sizeof(int32_t));
-    // (chunk lists the device expands from chunk groups lie behind the uploaded part; lists the host -- or the device tiler -- writes lie here)
-    if (lay.n_chunk_groups == 0) {
-        take(lay.chunks, (size_t)lay.n_chunks * sizeof(DevTile));
-        take(lay.span_chunks, (size_t)lay.n_span_chunks * sizeof(DevTile));
-    }
-    take(lay.chunk_groups, (size_t)lay.n_chunk_groups * sizeof(DevChunkGroup));
-    take(lay.stat_ids, (size_t)lay.n_stat * sizeof(int32_t));
-    take(lay.stat_first, (size_t)(lay.n_fields + 1) * sizeof(int64_t));
-    take(lay.stat_run, (size_t)lay.n_stat * sizeof(int64_t));
-    take(lay.red_paths, (size_t)lay.n_fields * sizeof(int32_t));
-    take(lay.field_work, (size_t)lay.n_field_work * sizeof(DevFieldWork));
-    take(lay.field_packs, (size_t)lay.n_field_work * sizeof(DevFieldPack));
-    take(lay.open_wave_ids, (size_t)lay.n_open_wave * sizeof(int32_t));
-    take(lay.obs_off, lay.n_polys > 0 ? (size_t)(lay.n_polys + 1) * sizeof(int64_t) : 0);
-    take(lay.obs_x, (size_t)lay.n_poly_verts * sizeof(double));
-    take(lay.obs_y, (size_t)lay.n_poly_verts * sizeof(double));
-    take(lay.obs_bbox, (size_t)lay.n_polys * 4 * sizeof(double));
-    take(lay.seg, (size_t)lay.n_fields * 8 * sizeof(double));
-    take(lay.seg_mask, (size_t)lay.n_fields * 2 * sizeof(int32_t));
-    lay.upload_bytes = o;
-    if (lay.n_chunk_groups > 0) {
-        take(lay.chunks, (size_t)lay.n_chunks * sizeof(DevTile));
-        take(lay.span_chunks, (size_t)lay.n_span_chunks * sizeof(DevTile));
-    }
-    take(lay.partial, (size_t)lay.n_stat * sizeof(TilePartial));      // one slot per statistics entry
-    take(lay.red_scratch, (size_t)lay.n_red[3] * 64 * 104);
-    take(lay.field_junc, (size_t)lay.n_fields * 2 * sizeof(double));
-    take(lay.work_totals, (size_t)lay.n_field_work * sizeof(TilePartial));   // per field of field_work: the statistics of its quiet runs, summed once
-    take(lay.info, lay.info_on_device ? (size_t)lay.n_fields * sizeof(fcpp_field_info) : 0);   // device-side setup: fcpp_field_info, copied back on demand
-    take(lay.own_stats, (size_t)lay.n_fields * sizeof(fcpp_field_stats));       // fcpp_batch_plan(stats_dev = NULL): the batch's own statistics records
-    lay.total_bytes = o;
-}
-
 // the batch's obstacle polygons (CSR) and one bounding box per polygon
 void fill_obstacles(const fcpp_polys *polys, const ImageLayout &lay, unsigned char *dst, size_t rebase)
 {
@@ -620,57 +574,58 @@ void BatchTiler::fill(const HostPlan &hp, const fcpp_polys *polys, const ImageLa
 {
     const int64_t n = lay.n_fields, nb = (int64_t)hp.blocks.size();
     const std::vector<BlockTiles> &B = *blocks_;
+    const SlabTables T = bind_tables(lay, dst);
     // the classes of the reduction one after the other: [<= 64 entries | <= 256 | <= reduce_wg_max | more], fields in order inside each
     int64_t cls_first[4] = { 0, lay.n_red[0], lay.n_red[0] + lay.n_red[1], lay.n_red[0] + lay.n_red[1] + lay.n_red[2] };
     WorkerPool::parallel_for(nb, [&](int64_t b) {
         const PlanBlock &pb = hp.blocks[(size_t)b];
         const BlockTiles &bt = B[(size_t)b];
         const int64_t nf = pb.f1 - pb.f0;
-        memcpy(at<DevField>(dst, lay.fields) + pb.f0, hp.fields.data() + pb.f0, (size_t)nf * sizeof(DevField));
-        if (!pb.prims.empty()) memcpy(at<DevPrim>(dst, lay.prims) + pb.prim_base, pb.prims.data(), pb.prims.size() * sizeof(DevPrim));
+        memcpy(T.fields + pb.f0, hp.fields.data() + pb.f0, (size_t)nf * sizeof(DevField));
+        if (!pb.prims.empty()) memcpy(T.prims + pb.prim_base, pb.prims.data(), pb.prims.size() * sizeof(DevPrim));
         const int32_t sb = (int32_t)bt.stat_base;
         // the tile of statistics entry e lies in slot e (bt.stat_ids: the entry's tile among the block's tiles)
-        DevTile *td = at<DevTile>(dst, lay.tiles) + bt.stat_base;
+        DevTile *td = T.tiles + bt.stat_base;
         for (size_t e = 0; e < bt.stat_ids.size(); ++e) {
             td[e] = bt.tiles[(size_t)bt.stat_ids[e]];
             if (td[e].quiet == 0) td[e].stat_tile += sb;            // general tiles: their statistics entry
             else if (td[e].quiet != 5) td[e].stat_tile = 0;         // quiet runs: (the host kept the run's length there)
         }
-        DevWaveTile *w = at<DevWaveTile>(dst, lay.wtiles) + bt.wave_base;
+        DevWaveTile *w = T.wtiles + bt.wave_base;
         for (size_t k = 0; k < bt.wtiles.size(); ++k) { w[k] = bt.wtiles[k]; w[k].tile += sb; }
-        int32_t *g = at<int32_t>(dst, lay.general_ids) + bt.general_base;
+        int32_t *g = T.general_ids + bt.general_base;
         for (size_t k = 0; k < bt.general_ids.size(); ++k) g[k] = bt.tiles[(size_t)bt.general_ids[k]].stat_tile + sb;      // (a general tile's slot = its entry)
-        int32_t *si = at<int32_t>(dst, lay.stat_ids) + bt.stat_base;
+        int32_t *si = T.stat_ids + bt.stat_base;
         for (size_t k = 0; k < bt.stat_ids.size(); ++k) si[k] = sb + (int32_t)k;
-        if (!bt.stat_run.empty()) memcpy(at<int64_t>(dst, lay.stat_run) + bt.stat_base, bt.stat_run.data(), bt.stat_run.size() * sizeof(int64_t));
+        if (!bt.stat_run.empty()) memcpy(T.stat_run + bt.stat_base, bt.stat_run.data(), bt.stat_run.size() * sizeof(int64_t));
         if (lay.n_chunk_groups > 0) {
-            DevChunkGroup *gr = at<DevChunkGroup>(dst, lay.chunk_groups) + bt.group_base;
+            DevChunkGroup *gr = T.chunk_groups + bt.group_base;
             for (size_t k = 0; k < bt.groups.size(); ++k) { gr[k] = bt.groups[k]; gr[k].e0 += sb; gr[k].chunk_base += bt.chunk_base; gr[k].span_base += bt.span_base; }
         } else {
-            DevTile *c = at<DevTile>(dst, lay.chunks) + bt.chunk_base;
+            DevTile *c = T.chunks + bt.chunk_base;
             for (size_t k = 0; k < bt.chunks.size(); ++k) { c[k] = bt.chunks[k]; c[k].stat_tile += sb; }
-            DevTile *cs = at<DevTile>(dst, lay.span_chunks) + bt.span_base;
+            DevTile *cs = T.span_chunks + bt.span_base;
             for (size_t k = 0; k < bt.span_chunks.size(); ++k) { cs[k] = bt.span_chunks[k]; cs[k].stat_tile += sb; }
         }
-        int64_t *sf = at<int64_t>(dst, lay.stat_first);
+        int64_t *sf = T.stat_first;
         int64_t run = bt.stat_base;
         for (int64_t k = 0; k < nf; ++k) { sf[pb.f0 + k] = run; run += bt.stat_cnt[k]; }
         if (pb.f1 == n) sf[n] = run;
         int64_t class_off = 0;                    // the records lie class by class: every class is one launch
         for (int c = 0; c < 4; ++c) {
-            DevFieldWork *fw = at<DevFieldWork>(dst, lay.field_work) + class_off + bt.work_base[c];
+            DevFieldWork *fw = T.field_work + class_off + bt.work_base[c];
             for (size_t k = 0; k < bt.work[c].size(); ++k) { fw[k] = bt.work[c][k]; fw[k].w_first += (int32_t)bt.wave_base; fw[k].e_first += sb; }
             class_off += lay.n_work[c];
         }
-        int32_t *ow = at<int32_t>(dst, lay.open_wave_ids) + bt.open_base;
+        int32_t *ow = T.open_wave_ids + bt.open_base;
         for (size_t k = 0; k < bt.open_wave.size(); ++k) ow[k] = bt.open_wave[k] + (int32_t)bt.wave_base;
-        int32_t *rp = at<int32_t>(dst, lay.red_paths);
+        int32_t *rp = T.red_paths;
         for (int cidx = 0; cidx < 4; ++cidx)
             if (!bt.cls[cidx].empty())
                 memcpy(rp + cls_first[cidx] + bt.cls_base[cidx], bt.cls[cidx].data(), bt.cls[cidx].size() * sizeof(int32_t));
         // connector segments (MLP:1313-1355): approach rows [0, n), departure rows [n, 2n)
-        double *seg = at<double>(dst, lay.seg);
-        int32_t *mask = at<int32_t>(dst, lay.seg_mask);
+        double *seg = T.seg;
+        int32_t *mask = T.seg_mask;
         for (int64_t i = pb.f0; i < pb.f1; ++i) {
             const fcpp_field_info &in = hp.info[(size_t)i];
             const bool okf = in.status == FCPP_OK;
@@ -682,14 +637,14 @@ void BatchTiler::fill(const HostPlan &hp, const fcpp_polys *polys, const ImageLa
             mask[n + i] = okf && in.end_kept;
         }
     });
-    if (n == 0) *at<int64_t>(dst, lay.stat_first) = 0;
+    if (n == 0) *T.stat_first = 0;
     // the packs of k_plan_sparse_fields: per field of field work its records gathered from the tables above (fcpp_internal.h: DevFieldPack)
     {
-        const DevFieldWork *fw = at<DevFieldWork>(dst, lay.field_work);
-        const DevWaveTile *wt = at<DevWaveTile>(dst, lay.wtiles);
-        const DevField *fd = at<DevField>(dst, lay.fields);
-        const DevPrim *pr = at<DevPrim>(dst, lay.prims);
-        DevFieldPack *pk = at<DevFieldPack>(dst, lay.field_packs);
+        const DevFieldWork *fw = T.field_work;
+        const DevWaveTile *wt = T.wtiles;
+        const DevField *fd = T.fields;
+        const DevPrim *pr = T.prims;
+        DevFieldPack *pk = T.field_packs;
         const int64_t nw = lay.n_field_work, per = 256;
         WorkerPool::parallel_for((nw + per - 1) / per, [&](int64_t blk) {
             for (int64_t i = blk * per; i < std::min(nw, (blk + 1) * per); ++i) {

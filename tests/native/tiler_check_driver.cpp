@@ -154,15 +154,13 @@ int main(int argc, char **argv)
         tiles_total += lay.n_tiles; wave_total += lay.n_wave;
 
         // ---- the image, checked
-        const DevField *F = reinterpret_cast<const DevField *>(img.data() + lay.fields);
-        const DevPrim *P = reinterpret_cast<const DevPrim *>(img.data() + lay.prims);
-        const DevTile *T = reinterpret_cast<const DevTile *>(img.data() + lay.tiles);
-        const DevWaveTile *Wt = reinterpret_cast<const DevWaveTile *>(img.data() + lay.wtiles);
-        const int32_t *G = reinterpret_cast<const int32_t *>(img.data() + lay.general_ids);
-        const DevTile *C = reinterpret_cast<const DevTile *>(img.data() + lay.chunks), *CS = reinterpret_cast<const DevTile *>(img.data() + lay.span_chunks);
-        const int32_t *SI = reinterpret_cast<const int32_t *>(img.data() + lay.stat_ids);
-        const int64_t *SF = reinterpret_cast<const int64_t *>(img.data() + lay.stat_first), *SR = reinterpret_cast<const int64_t *>(img.data() + lay.stat_run);
-        const int32_t *RP = reinterpret_cast<const int32_t *>(img.data() + lay.red_paths);
+        const SlabTables tb = bind_tables(lay, img.data());
+        const DevField *F = tb.fields;
+        const DevPrim *P = tb.prims;
+        const DevTile *T = tb.tiles, *C = tb.chunks, *CS = tb.span_chunks;
+        const DevWaveTile *Wt = tb.wtiles;
+        const int32_t *G = tb.general_ids, *SI = tb.stat_ids, *RP = tb.red_paths;
+        const int64_t *SF = tb.stat_first, *SR = tb.stat_run;
         if (lay.n_fields != n) FAIL("field count");
         int64_t total = 0;
         for (int i = 0; i < n; ++i) {
@@ -266,8 +264,8 @@ int main(int argc, char **argv)
             }
         }
         {   // the packs of k_plan_sparse_fields: the field's records gathered, and the span its workgroup writes itself (no chunks for it)
-            const DevFieldWork *FW = reinterpret_cast<const DevFieldWork *>(img.data() + lay.field_work);
-            const DevFieldPack *PK = reinterpret_cast<const DevFieldPack *>(img.data() + lay.field_packs);
+            const DevFieldWork *FW = tb.field_work;
+            const DevFieldPack *PK = tb.field_packs;
             int64_t fused_pts = 0;
             for (int64_t k = 0; k < lay.n_field_work; ++k) {
                 const DevFieldPack &pk = PK[k];
@@ -310,8 +308,8 @@ int main(int argc, char **argv)
         {
             std::vector<unsigned char> seen((size_t)n, 0);
             // fields planned and reduced by one workgroup (DevFieldWork) are in no class; their wave tiles are not in the open list
-            const DevFieldWork *FW = reinterpret_cast<const DevFieldWork *>(img.data() + lay.field_work);
-            const int32_t *OW = reinterpret_cast<const int32_t *>(img.data() + lay.open_wave_ids);
+            const DevFieldWork *FW = tb.field_work;
+            const int32_t *OW = tb.open_wave_ids;
             std::vector<unsigned char> wseen((size_t)lay.n_wave, 0);
             for (int64_t k = 0; k < lay.n_field_work; ++k) {
                 const DevFieldWork &w = FW[k];
