@@ -132,6 +132,7 @@ PROTOTYPES = [
     ('fcpp_batch_setup_times', C.c_int, [_VP, C.POINTER(SetupTimes)]),
     ('fcpp_batch_run', C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int]),
     ('fcpp_batch_connectors', C.c_int, [_VP, _VP, _VP]),
+    ('fcpp_batch_trajectory', C.c_int, [_VP] * 9),
     ('fcpp_batch_destroy', C.c_int, [_VP]),
     ('fcpp_batch_set_profiling', C.c_int, [_VP, C.c_int]),
     ('fcpp_batch_stage_times', C.c_int, [_VP, C.c_int, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -145,6 +146,9 @@ PROTOTYPES = [
     ('fcpp_verify', C.c_int, [_VP, C.POINTER(Vehicle), C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     ('fcpp_validate', C.c_int, [_VP, C.POINTER(Vehicle), C.POINTER(Options), C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.POINTER(Polys),
                                C.POINTER(Polys), _VP, _VP, _VP, _VP]),
+    ('fcpp_trajectory', C.c_int, [_VP, C.c_int64, _VP, C.c_int64] + [_VP] * 9),
+    ('fcpp_trajectory_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_double, C.c_int, _VP, _VP]),
+    ('fcpp_trajectory_sample', C.c_int, [_VP, C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, _VP, C.c_int64] + [_VP] * 9),
     ('fcpp_straight_segments', C.c_int, [_VP, C.c_int64, _VP, C.c_int32, _VP]),
     ('fcpp_corner_turns', C.c_int, [_VP, C.POINTER(Vehicle), C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_int32, _VP, _VP]),
     ('fcpp_fresnel', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),

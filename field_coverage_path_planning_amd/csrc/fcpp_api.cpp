@@ -22,6 +22,7 @@
 #include "fcpp_internal.h"
 #include "fcpp_parallel.h"
 #include "fcpp_tiler.h"
+#include "fcpp_traj.h"
 
 using namespace fcpp;
 
@@ -1501,9 +1502,22 @@ int fcpp_batch_destroy(fcpp_batch *b)
 namespace {
 // The tile table of a path set, kept in the context between calls of the standalone operators: a caller that plans and verifies
 // the same paths (the planner mirror does: speed plan, verify, verify again) pays for the host-side tiling and its upload once.
+// The trajectory scan's own tables of a path set (fcpp_trajectory): the blocks of its path-anchored spine and the scan's scratch, built
+// from the offsets on the first trajectory call for them.
+struct TrajTables {
+    DevBuf<TrajBlock> blocks;
+    DevBuf<int64_t> block_first;      // n_paths + 1
+    DevBuf<TrajAgg> agg, pre;         // per tile: its own sums / what enters it, relative to its block
+    DevBuf<TrajAgg> blk, cin;         // per block: its own sums / what enters it, relative to its path
+    DevBuf<int64_t> path_first;       // per path: where its first non-zero step starts
+    int64_t n_blocks = 0;
+    bool built = false;
+};
+
 struct PathTiling {
     std::vector<int64_t> offs;
     DevTiling dt;
+    TrajTables traj;
 };
 
 // offsets on the host: the caller's copy, or read back from the device (one copy + synchronisation); the tile table is rebuilt
@@ -1630,6 +1644,162 @@ int fcpp_verify(fcpp_ctx *c, const fcpp_vehicle *veh, int64_t n_paths, const int
     DevObstacles obs = { nullptr, nullptr, nullptr, nullptr };
     LAUNCHCHK(launch_validate(st, dt.n_tiles, dt.tiles.p, dt.paths.p, nullptr, cst, obs, x, y, kap.p, v, nullptr, dt.partial.p));
     { const int rrc = reduce_paths(c, st, dt, stats); if (rrc) return rrc; }
+    HIPCHK(hipStreamSynchronize(st));
+    return FCPP_OK;
+}
+
+// ---- trajectory: arc length, time stamp and heading per point; fixed-rate sampling (fcpp_traj.hip) ---------------------------------
+namespace {
+int ensure_traj(PathTiling &pt, hipStream_t st)
+{
+    TrajTables &tr = pt.traj;
+    if (tr.built) return FCPP_OK;
+    const int64_t n_paths = (int64_t)pt.offs.size() - 1;
+    std::vector<TrajBlock> blocks;
+    std::vector<int64_t> first((size_t)n_paths + 1, 0);
+    try {
+        int64_t tile0 = 0;
+        for (int64_t p = 0; p < n_paths; ++p) {
+            const int64_t n = pt.offs[(size_t)p + 1] - pt.offs[(size_t)p], nt = (n + TILE_POINTS - 1) / TILE_POINTS;   // (Tiling::build)
+            first[(size_t)p] = (int64_t)blocks.size();
+            for (int64_t k = 0; k < nt; k += TRAJ_BLOCK_TILES)
+                blocks.push_back({ tile0 + k, (int32_t)p, (int32_t)std::min<int64_t>(TRAJ_BLOCK_TILES, nt - k) });
+            tile0 += nt;
+        }
+        first[(size_t)n_paths] = (int64_t)blocks.size();
+        if (tile0 != pt.dt.n_tiles) return fail(FCPP_ESIZE, "trajectory blocks do not match the tile table");
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    tr.n_blocks = (int64_t)blocks.size();
+    HIPCHK(tr.blocks.upload(blocks, st));
+    HIPCHK(tr.block_first.upload(first, st));
+    HIPCHK(tr.agg.alloc((size_t)pt.dt.n_tiles));
+    HIPCHK(tr.pre.alloc((size_t)pt.dt.n_tiles));
+    HIPCHK(tr.blk.alloc((size_t)tr.n_blocks));
+    HIPCHK(tr.cin.alloc((size_t)tr.n_blocks));
+    HIPCHK(tr.path_first.alloc((size_t)n_paths));
+    HIPCHK(hipStreamSynchronize(st));      // (the staging vectors die here)
+    tr.built = true;
+    return FCPP_OK;
+}
+
+int trajectory_paths(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, const double *x,
+                     const double *y, const double *v, const uint32_t *fs, double *s, double *t, double *heading, double *totals)
+{
+    DevTiling *dtp = nullptr;
+    int rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
+    if (rc) return rc;
+    DevTiling &dt = *dtp;
+    hipStream_t st = c->stream;
+    rc = ensure_traj(*c->paths_cache, st);
+    if (rc) return rc;
+    TrajTables &tr = c->paths_cache->traj;
+    LAUNCHCHK(launch_traj_tiles(st, dt.n_tiles, dt.tiles.p, dt.paths.p, x, y, v, tr.agg.p));
+    LAUNCHCHK(launch_traj_blocks(st, tr.n_blocks, tr.blocks.p, tr.agg.p, tr.pre.p, tr.blk.p));
+    LAUNCHCHK(launch_traj_paths(st, n_paths, tr.block_first.p, tr.blk.p, tr.cin.p, tr.path_first.p, totals));
+    if (s || t || heading)
+        LAUNCHCHK(launch_traj_apply(st, dt.n_tiles, dt.tiles.p, dt.paths.p, dt.tile_first.p, tr.block_first.p, x, y, v, fs, tr.pre.p, tr.cin.p,
+                                    tr.path_first.p, s, t, heading));
+    HIPCHK(hipStreamSynchronize(st));
+    return FCPP_OK;
+}
+
+// CSR offsets on the host: the caller's copy or read back; checked like make_tiling checks the paths' (total < 0: any total)
+int host_offsets(fcpp_ctx *c, int64_t n, const int64_t *dev, const int64_t *host, int64_t total, const char *what, std::vector<int64_t> &out)
+{
+    out.assign((size_t)n + 1, 0);
+    if (host) memcpy(out.data(), host, out.size() * sizeof(int64_t));
+    else {
+        HIPCHK(hipMemcpyAsync(out.data(), dev, out.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (out[0] != 0 || (total >= 0 && out.back() != total)) return fail(FCPP_ESIZE, std::string(what) + " do not span [0, total]");
+    for (int64_t p = 0; p < n; ++p)
+        if (out[(size_t)p + 1] < out[(size_t)p]) return fail(FCPP_ESIZE, std::string(what) + " must be non-decreasing");
+    return FCPP_OK;
+}
+}  // namespace
+
+int fcpp_trajectory(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x, const double *y, const double *v,
+                    const uint32_t *flagseg, double *s, double *t, double *heading, double *totals, const int64_t *offsets_host)
+{
+    if (!c || (!offsets && !offsets_host) || (total > 0 && (!x || !y || !v))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    return trajectory_paths(c, n_paths, offsets, offsets_host, total, x, y, v, flagseg, s, t, heading, totals);
+}
+
+int fcpp_batch_trajectory(fcpp_batch *b, const double *x, const double *y, const double *v, const uint32_t *flagseg, double *s, double *t,
+                          double *heading, double *totals)
+{
+    if (!b) return fail(FCPP_EINVAL, "batch is NULL");
+    if (b->n_fields == 0) return FCPP_OK;
+    if (b->hp.total_points > 0 && (!x || !y || !v)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(b->ctx->device));
+    { const int rc = ensure_info(b); if (rc) return rc; }
+    // two paths per field: main work, then headland (a field that raised: two empty paths)
+    std::vector<int64_t> offs;
+    try { offs.assign(2 * (size_t)b->n_fields + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t i = 0; i < b->n_fields; ++i) {
+        const fcpp_field_info &fi = b->hp.info[(size_t)i];
+        offs[2 * (size_t)i + 1] = offs[2 * (size_t)i] + fi.n_main;
+        offs[2 * (size_t)i + 2] = offs[2 * (size_t)i + 1] + fi.n_head;
+    }
+    hipStream_t st = b->ctx->stream;
+    b->note_stream(st);
+    HIPCHK(b->wait_setup(st));
+    return trajectory_paths(b->ctx, 2 * b->n_fields, nullptr, offs.data(), b->hp.total_points, x, y, v, flagseg, s, t, heading, totals);
+}
+
+int fcpp_trajectory_counts(fcpp_ctx *c, int64_t n_paths, const double *totals, double dt, int include_end, int64_t *out_offsets,
+                           int64_t *out_offsets_host)
+{
+    if (!c || !out_offsets || (n_paths > 0 && !totals)) return fail(FCPP_EINVAL, "bad arguments");
+    if (!(dt > 0.0) || !isfinite(dt)) return fail(FCPP_EINVAL, "dt must be positive");
+    if (n_paths < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DevBuf<int64_t> err;
+    HIPCHK(err.alloc(1));
+    LAUNCHCHK(launch_traj_counts(st, n_paths, totals, dt, include_end ? 1 : 0, out_offsets, err.p));
+    int64_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, err.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    if (out_offsets_host)
+        HIPCHK(hipMemcpyAsync(out_offsets_host, out_offsets, ((size_t)n_paths + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad) return fail(FCPP_ESIZE, "a path's total time is negative or not finite, or it has 2^31 samples or more");
+    return FCPP_OK;
+}
+
+int fcpp_trajectory_sample(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x, const double *y,
+                           const double *v, const double *s, const double *t, const double *heading, const uint32_t *flagseg, double dt,
+                           int include_end, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *vs, double *ss,
+                           double *hs, uint32_t *flagseg_s, int64_t *src_index, const int64_t *offsets_host, const int64_t *out_offsets_host)
+{
+    if (!c || (!offsets && !offsets_host) || (!out_offsets && !out_offsets_host) || (total > 0 && (!x || !y || !v || !s || !t || !heading)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    if (!(dt > 0.0) || !isfinite(dt)) return fail(FCPP_EINVAL, "dt must be positive");
+    if (n_paths < 0 || total < 0 || total_samples < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<int64_t> offs, outs;
+    try {
+        int rc = host_offsets(c, n_paths, offsets, offsets_host, total, "offsets", offs);
+        if (rc == FCPP_OK) rc = host_offsets(c, n_paths, out_offsets, out_offsets_host, total_samples, "out_offsets", outs);
+        if (rc) return rc;
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t p = 0; p < n_paths; ++p)
+        if (outs[(size_t)p + 1] - outs[(size_t)p] > INT32_MAX) return fail(FCPP_ESIZE, "a path has 2^31 samples or more");
+    // the kernel reads both tables on the device: a caller that brought only host copies gets them uploaded
+    DevBuf<int64_t> up;
+    if (!offsets || !out_offsets) {
+        std::vector<int64_t> both(offs);
+        both.insert(both.end(), outs.begin(), outs.end());
+        HIPCHK(up.upload(both, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (!offsets) offsets = up.p;
+        if (!out_offsets) out_offsets = up.p + n_paths + 1;
+    }
+    LAUNCHCHK(launch_traj_sample(st, n_paths, offsets, out_offsets, total_samples, x, y, v, s, t, heading, flagseg, dt, include_end ? 1 : 0, xs, ys,
+                                 vs, ss, hs, flagseg_s, src_index));
     HIPCHK(hipStreamSynchronize(st));
     return FCPP_OK;
 }

@@ -435,6 +435,33 @@ class BatchResult:
         info = self.batch.info[i]
         return slice(info.point_offset, info.point_offset + info.n_main + info.n_head)
 
+    def path_offsets(self):
+        """CSR offsets (numpy int64, 2 * n_fields + 1) of the batch's paths as the trajectory entries see them: two per field, main work
+        then headland; a field that raised is two empty paths."""
+        a = self.batch.info.array
+        off = np.zeros(2 * len(a) + 1, dtype=np.int64)
+        off[1::2], off[2::2] = a['n_main'], a['n_head']
+        return np.cumsum(off)
+
+    def trajectory(self):
+        """-> (s, t, heading, totals): arc length [m], time stamp [s] and vehicle heading [rad, (-pi, pi]] of every point of the batch
+        arrays, each counted from the start of its own path (path_offsets(): main work and headland are timed separately, MLP:423-431), and
+        totals of shape (n_fields, 4) = main length, main time, headland length, headland time (fcpp_batch_trajectory)."""
+        torch = _torch()
+        b = self.batch
+        s, t, h = torch.empty_like(self.x), torch.empty_like(self.x), torch.empty_like(self.x)
+        totals = torch.zeros((b.n_fields, 4), dtype=torch.float64, device=self.x.device)
+        b.ctx.bind_stream()
+        L.check(b.lib.fcpp_batch_trajectory(b.handle, _ptr(self.x), _ptr(self.y), _ptr(self.v), _ptr(self.flagseg), _ptr(s), _ptr(t), _ptr(h),
+                                            _ptr(totals)))
+        return s, t, h, totals
+
+    def sample(self, dt, include_end=True):
+        """The batch's trajectories at a fixed time step dt [s] -> dict as trajectory_sample(); sample range out_offsets[2 f] ..
+        out_offsets[2 f + 1] is field f's main work, the next range its headland."""
+        s, t, h, totals = self.trajectory()
+        return _sample(self.batch.ctx, self.x, self.y, self.v, self.flagseg, self.path_offsets(), None, (s, t, h, totals.view(-1, 2)), dt, include_end)
+
 
 class Batch:
     """n independent fields planned together on one GPU (fcpp_batch_*)."""
@@ -836,6 +863,80 @@ def verify(x, y, v, vehicle, offsets=None, device=None):
         col = raw[:, k]
         out[n] = col.view(np.float64).copy() if k < L.STATS_DOUBLES else col.copy()
     return out
+
+
+def _dev_flags(a, device):
+    """flag / segment words as an int32 device tensor (torch has no uint32 arithmetic; the bits are what matters)"""
+    torch = _torch()
+    if a is None:
+        return None
+    if isinstance(a, torch.Tensor):
+        return a.to(device=device, dtype=torch.int32).contiguous()
+    return torch.as_tensor(np.ascontiguousarray(a).astype(np.uint32, copy=False).view(np.int32), device=device)
+
+
+def trajectory(x, y, v, flagseg=None, offsets=None, device=None):
+    """-> (s, t, heading, totals) device tensors (fcpp_trajectory): per point the arc length [m] and the time stamp [s] counted from its
+    path's first point -- the running values of _calculate_path_length / _calculate_work_time, MLP:1290-1311 -- and the vehicle's heading
+    [rad, (-pi, pi]]: the chord that leaves the point, carried over zero steps, turned by pi where flagseg says FCPP_KIND_REVERSE;
+    totals[p] = (length, time) of path p."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    x, y, v = _dev_f64(x, dev), _dev_f64(y, dev), _dev_f64(v, dev)
+    fs = _dev_flags(flagseg, dev)
+    off, off_h = _offsets(offsets, x.numel(), dev)
+    n_paths = off.numel() - 1
+    s, t, h = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    totals = torch.zeros((n_paths, 2), dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_trajectory(ctx.handle, n_paths, _ptr(off), x.numel(), _ptr(x), _ptr(y), _ptr(v), _ptr(fs), _ptr(s), _ptr(t), _ptr(h),
+                                    _ptr(totals), _host_ptr(off_h)))
+    return s, t, h, totals
+
+
+def _sample(ctx, x, y, v, fs, off_h, off, traj, dt, include_end):
+    torch = _torch()
+    dev = x.device
+    s, t, h, totals = traj
+    if off is None:
+        off = torch.as_tensor(off_h, device=dev)
+    n_paths = off.numel() - 1
+    out_off = torch.empty(n_paths + 1, dtype=torch.int64, device=dev)
+    out_h = np.zeros(n_paths + 1, dtype=np.int64)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_trajectory_counts(ctx.handle, n_paths, _ptr(totals), float(dt), int(bool(include_end)), _ptr(out_off), _host_ptr(out_h)))
+    m = int(out_h[-1])
+    out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'v', 's', 'heading')}
+    out['flagseg'] = torch.empty(m, dtype=torch.int32, device=dev)
+    out['src_index'] = torch.empty(m, dtype=torch.int64, device=dev)
+    L.check(ctx.lib.fcpp_trajectory_sample(ctx.handle, n_paths, _ptr(off), x.numel(), _ptr(x), _ptr(y), _ptr(v), _ptr(s), _ptr(t), _ptr(h), _ptr(fs),
+                                           float(dt), int(bool(include_end)), _ptr(out_off), m, _ptr(out['x']), _ptr(out['y']), _ptr(out['v']),
+                                           _ptr(out['s']), _ptr(out['heading']), _ptr(out['flagseg']), _ptr(out['src_index']),
+                                           _host_ptr(off_h), _host_ptr(out_h)))
+    out['out_offsets'] = out_off
+    out['totals'] = totals
+    out['out_offsets_host'] = out_h
+    out['dt'] = float(dt)
+    return out
+
+
+def trajectory_sample(x, y, v, dt, flagseg=None, offsets=None, include_end=True, device=None, traj=None):
+    """The trajectories of the paths at a fixed time step dt [s] (fcpp_trajectory_counts + fcpp_trajectory_sample) -> dict of device
+    tensors 'x', 'y', 'v', 's', 'heading', 'flagseg', 'src_index' (one entry per sample; sample k of path p lies at time k * dt and at
+    index out_offsets[p] + k), 'out_offsets' (n_paths + 1, device; 'out_offsets_host': numpy), 'totals' (length, time per path) and 'dt'.  x, y, s are interpolated linearly
+    within the step the sample falls in, v linearly in time; heading, flag word and src_index are those of the step's first point.  With
+    include_end the last sample of every path is its last point.  traj: the (s, t, heading, totals) of trajectory() for the same paths,
+    when the caller has them already."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    x, y, v = _dev_f64(x, dev), _dev_f64(y, dev), _dev_f64(v, dev)
+    fs = _dev_flags(flagseg, dev)
+    off, off_h = _offsets(offsets, x.numel(), dev)
+    if traj is None:
+        traj = trajectory(x, y, v, fs, offsets, device)
+    return _sample(ctx, x, y, v, fs, off_h, off, traj, dt, include_end)
 
 
 def _polys(polygons):

@@ -19,6 +19,10 @@ README import but the reference never defines (TwoLayerPathPlannerV35/V36, TwoLa
         .verify_all_corners_coverage(result['headland']) / .verify_corner_coverage_grid_based(...)   MLP:1426-1578
         ._calculate_coverage_rate(path, area)                               MLP:1357-1371
 
+Beyond the reference: result['main_work'] / result['headland'] also carry 'arc_length', 'time' and 'heading' (one value per path point:
+the running values of _calculate_path_length / _calculate_work_time and the vehicle's heading, each layer counted from its own first
+point), and .trajectory(dt) returns both layers resampled at a fixed time step.
+
 Not reproduced: matplotlib plotting helpers and the Shapely objects under result['...']['area'] (a plain
 vertex-list polygon is returned instead).  `coverage_rate` is sampled on a 0.1 m grid (`coverage_resolution=`)
 instead of GEOS polygon clipping.
@@ -202,6 +206,8 @@ class TwoLayerPathPlannerV37:
         res = batch.run(self._bufs)
         ap, dp = batch.connectors()
         n_main, n_head = info.n_main, info.n_head
+        # arc length, time stamp and heading per point, each layer counted from its own first point (MLP:423-431 times them separately)
+        traj_s, traj_t, traj_h = (a.cpu().numpy() for a in res.trajectory()[:3])
         # coverage of the headland ring by the headland path, straight from the device arrays (MLP:884, 1357-1371)
         coverage_rate = self._coverage_rate_dev(res.x[n_main:], res.y[n_main:], self._headland_area())
         # (one copy for the four float64 arrays, one for the two connectors: every copy to the host is a synchronisation of its own)
@@ -224,6 +230,7 @@ class TwoLayerPathPlannerV37:
                 'avg_speed_kmh': (main_len / 1000) / (main_pre / 3600) if main_pre > 0 else 0,  # MLP:627 (pre-clamp time)
             },
             'kappa': kappa[:n_main], 'flagseg': fs[:n_main],
+            'arc_length': traj_s[:n_main], 'time': traj_t[:n_main], 'heading': traj_h[:n_main],
         }
         headland = {
             'path': path[n_main:], 'speeds': v[n_main:], 'area': head_area,
@@ -234,6 +241,7 @@ class TwoLayerPathPlannerV37:
                 'coverage_rate': coverage_rate,   # MLP:884 (0..1), sampled at self.coverage_resolution
             },
             'kappa': kappa[n_main:], 'flagseg': fs[n_main:],
+            'arc_length': traj_s[n_main:], 'time': traj_t[n_main:], 'heading': traj_h[n_main:],
         }
         result = {
             'main_work': main_work, 'headland': headland,
@@ -258,6 +266,33 @@ class TwoLayerPathPlannerV37:
         return result
 
     plan = plan_complete_coverage   # README_en.md:274-302
+
+    def trajectory(self, dt: float, include_end: bool = True) -> Dict:
+        """The planned path as a controller follows it: both layers at the fixed time step dt [s] (not in the reference).
+        -> {'main_work': {...}, 'headland': {...}}, each with numpy arrays 'time' (k * dt; the last sample is the layer's last point when
+        include_end), 'path' (n x 2), 'speeds' [km/h], 'arc_length' [m], 'heading' [rad], 'flagseg' and 'src_index' (the index into the
+        layer's own 'path' of the point that starts the step the sample lies in).  x, y and arc length are interpolated linearly within
+        a step, the speed linearly in time."""
+        if self._info.status != L.OK:
+            raise ValueError(f"unsupported field (libfcpp status {self._info.status})")
+        if self._batch is None:
+            self._batch = E.Batch(self._table, self._veh, self._opt, device=self._device)
+        bufs = self._bufs if self._bufs is not None else self._batch.alloc()
+        res = self._batch.run(bufs)
+        smp = res.sample(dt, include_end)
+        off = smp['out_offsets_host']
+        host = {k: smp[k].cpu().numpy() for k in ('x', 'y', 'v', 's', 'heading', 'flagseg', 'src_index')}
+        t_end = smp['totals'].cpu().numpy().reshape(-1)[[1, 3]]
+        out = {}
+        for k, (name, first) in enumerate((('main_work', 0), ('headland', self._info.n_main))):
+            sl = slice(off[k], off[k + 1])
+            tm = np.arange(off[k + 1] - off[k], dtype=np.float64) * float(dt)
+            if include_end and len(tm):
+                tm[-1] = t_end[k]
+            out[name] = {'time': tm, 'path': np.column_stack([host['x'][sl], host['y'][sl]]), 'speeds': host['v'][sl],
+                         'arc_length': host['s'][sl], 'heading': host['heading'][sl], 'flagseg': host['flagseg'][sl].view(np.uint32),
+                         'src_index': host['src_index'][sl] - first}
+        return out
 
     def close(self):
         """release the planner's device batch (also done when the planner is collected)"""

@@ -273,6 +273,12 @@ int fcpp_batch_own_stats(const fcpp_batch *batch, fcpp_field_stats **stats_dev);
 /* _generate_approach_path / _generate_departure_path (MLP:1313-1355): 50 points each, AoS (x,y) per
  * field at [field*100 .. +100); rows of fields without a kept start/end point are left untouched. */
 int fcpp_batch_connectors(fcpp_batch *batch, double *approach_xy_dev, double *departure_xy_dev);
+/* fcpp_trajectory (below) on the batch's own paths: TWO per field, main work then headland (the reference times them separately,
+ * MLP:423-431), so path 2 f starts at point_offset of field f and has n_main points, path 2 f + 1 follows with n_head; a field that raises
+ * is two empty paths.  x / y / v / flagseg: the arrays of fcpp_batch_run.  totals_dev: 4 doubles per field (main length, main time,
+ * headland length, headland time).  Runs after the batch's step on the same stream and synchronises it. */
+int fcpp_batch_trajectory(fcpp_batch *batch, const double *x_dev, const double *y_dev, const double *v_dev, const uint32_t *flagseg_dev,
+                          double *s_dev, double *t_dev, double *heading_dev, double *totals_dev);
 int fcpp_batch_destroy(fcpp_batch *batch);
 /* Per-kernel device timing with HIP events (bench.py's roofline leg).  enable = k > 0: every k-th fcpp_batch_run from now on
  * dispatches each of its kernels with a start and a stop event of its own (hipExtLaunchKernel: the dispatch's time stamps, no
@@ -327,6 +333,42 @@ int fcpp_validate(fcpp_ctx *ctx, const fcpp_vehicle *veh, const fcpp_options *op
                   int64_t total_points, const double *x_dev, const double *y_dev, const double *v_dev, const fcpp_polys *field_polys,
                   const fcpp_polys *obstacles, const int64_t *obstacle_offsets, uint32_t *flags_dev, fcpp_field_stats *stats_dev,
                   const int64_t *offsets_host);
+/* ---- trajectory: what a path-tracking controller follows -------------------------------------------------------------------------
+ * Per point of every path its arc length s, its time stamp t and the heading of the VEHICLE: the running values of
+ * _calculate_path_length (MLP:1294-1296) and _calculate_work_time (MLP:1303-1310, with its 0.1 m/s floor).  Per path p_0 .. p_(n-1), v in km/h:
+ *     d_i = sqrt((x_i - x_(i-1))^2 + (y_i - y_(i-1))^2),  tau_i = d_i / max(((v_(i-1) + v_i) / 2) / 3.6, 0.1)      (the terms fcpp_verify sums)
+ *     s_0 = t_0 = 0,  s_i = d_1 + .. + d_i,  t_i = tau_1 + .. + tau_i;  jumps and duplicate points are steps like any other; paths of 0 or 1
+ *     points: zeros.  s and t never decrease along a path (exactly).
+ *     heading_i = atan2(y_(i+1) - y_i, x_(i+1) - x_i), radians in (-pi, pi]: the chord of the step that LEAVES point i.  A zero step (both
+ *     differences 0) takes the direction of the nearest earlier non-zero step of the path, leading zero steps that of the first non-zero step
+ *     that follows, the last point that of its incoming step; a path without a non-zero step: 0.  With flagseg_dev, a point of kind
+ *     FCPP_KIND_REVERSE is driven backwards: its heading is that direction turned by pi (h > 0: h - pi, else h + pi).
+ * The order of the additions is fixed by the path alone (tiles and the blocks of the scan's spine are counted from the path's first point,
+ * no atomics): a path gives the same bits alone, as path 4711 of a batch, and under any sharding.  s_dev, t_dev, heading_dev (total_points
+ * each) and totals_dev (2 per path: length, time = s and t of its last point) may each be NULL.  offsets_host, the cached tile table and the
+ * error codes as for the other standalone operators; synchronises. */
+int fcpp_trajectory(fcpp_ctx *ctx, int64_t n_paths, const int64_t *offsets_dev, int64_t total_points, const double *x_dev, const double *y_dev,
+                    const double *v_dev, const uint32_t *flagseg_dev /* may be NULL */, double *s_dev, double *t_dev, double *heading_dev,
+                    double *totals_dev, const int64_t *offsets_host);
+/* The trajectory at a fixed time step dt > 0 [s] (a controller's rate instead of the planner's uneven sample points): sample k of path p lies
+ * at time k * dt (one rounding, never accumulated), k = 0 .. K_p - 1, K_p = floor(T_p / dt) + 1, T_p = the path's total time; with
+ * include_end != 0 one more sample AT T_p when the last of them lies before T_p, and the last sample of every path IS its last point.
+ * fcpp_trajectory_counts makes the samples' CSR offsets (n_paths + 1 values) from totals_dev (2 per path as fcpp_trajectory writes them; only
+ * the times are read); out_offsets_host: NULL or room for a copy.  FCPP_EINVAL: dt <= 0; FCPP_ESIZE: a time that is negative or not finite,
+ * a path of 2^31 samples or more.  Synchronises.  (A path without points has T_p = 0 like a path of one point: it gets its one sample, which
+ * fcpp_trajectory_sample fills with NaN, flag word 0 and src_index -1.) */
+int fcpp_trajectory_counts(fcpp_ctx *ctx, int64_t n_paths, const double *totals_dev, double dt, int include_end, int64_t *out_offsets_dev,
+                           int64_t *out_offsets_host);
+/* For the sample at time T: the step i with t_i <= T < t_(i+1) (the LAST such i where steps of zero duration repeat a time; T >= T_p: the last
+ * point), lambda = (T - t_i) / (t_(i+1) - t_i); x, y, s interpolated linearly with lambda, and so is v -- linear IN TIME: the constant
+ * acceleration over a step that the speed planner's sweeps assume; heading and flag word are those of point i, src_index = i (index into
+ * the batch arrays).  s, t, heading are fcpp_trajectory's outputs for the same paths.  Every output may be NULL.  offsets_host /
+ * out_offsets_host spare the read-backs (both tables are checked: FCPP_ESIZE); synchronises. */
+int fcpp_trajectory_sample(fcpp_ctx *ctx, int64_t n_paths, const int64_t *offsets_dev, int64_t total_points, const double *x_dev,
+                           const double *y_dev, const double *v_dev, const double *s_dev, const double *t_dev, const double *heading_dev,
+                           const uint32_t *flagseg_dev /* may be NULL */, double dt, int include_end, const int64_t *out_offsets_dev,
+                           int64_t total_samples, double *xs_dev, double *ys_dev, double *vs_dev, double *ss_dev, double *hs_dev,
+                           uint32_t *flagseg_s_dev, int64_t *src_index_dev, const int64_t *offsets_host, const int64_t *out_offsets_host);
 /* numpy.linspace straight segments (MLP:1013-1022, 1313-1355): seg_dev = n_seg x (x0,y0,x1,y1),
  * out_xy_dev = n_seg x n_points x 2 */
 int fcpp_straight_segments(fcpp_ctx *ctx, int64_t n_seg, const double *seg_dev, int32_t n_points,

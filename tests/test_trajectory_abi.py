@@ -1,0 +1,77 @@
+"""CPU-side tests of the trajectory entries (fcpp_trajectory, fcpp_batch_trajectory, fcpp_trajectory_counts, fcpp_trajectory_sample):
+the header declares them, the ctypes binding takes the documented argument lists, libfcpp.so exports them, and without a GPU the engine
+raises instead of computing anything on the CPU."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# entry -> number of arguments in include/fcpp.h
+ENTRIES = {'fcpp_trajectory': 13, 'fcpp_batch_trajectory': 9, 'fcpp_trajectory_counts': 7, 'fcpp_trajectory_sample': 24}
+
+
+def _header():
+    hdr = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
+    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+
+
+def test_header_declares_the_four_entries():
+    hdr = _header()
+    for name, n_args in ENTRIES.items():
+        m = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, flags=re.S)
+        assert m, name
+        assert len(m.group(1).split(',')) == n_args, (name, m.group(1))
+    assert re.search(r'#define\s+FCPP_ABI_VERSION\s+5\b', hdr)      # additions only
+
+
+def test_prototypes_bind_them_with_the_declared_argument_counts():
+    protos = {n: (res, args) for n, res, args in L.PROTOTYPES}
+    for name, n_args in ENTRIES.items():
+        assert name in protos, name
+        res, args = protos[name]
+        assert res is C.c_int and len(args) == n_args, name
+    # dt is the one floating-point argument; the sizes are 64-bit
+    assert protos['fcpp_trajectory_counts'][1][3] is C.c_double
+    assert protos['fcpp_trajectory_sample'][1][11] is C.c_double
+    assert protos['fcpp_trajectory'][1][1] is C.c_int64 and protos['fcpp_trajectory'][1][3] is C.c_int64
+    assert protos['fcpp_trajectory_sample'][1][14] is C.c_int64
+
+
+def test_library_exports_them():
+    lib = L.load()
+    for name in ENTRIES:
+        assert hasattr(lib, name), name
+    assert lib.fcpp_abi_version() == 5
+
+
+def test_argument_errors_need_no_device():
+    """the checks that come before anything touches the GPU: NULL handles, dt <= 0"""
+    lib = L.load()
+    assert lib.fcpp_trajectory(None, 0, None, 0, None, None, None, None, None, None, None, None, None) == L.EINVAL
+    assert lib.fcpp_batch_trajectory(None, None, None, None, None, None, None, None, None) == L.EINVAL
+    assert lib.fcpp_trajectory_counts(None, 0, None, 1.0, 1, None, None) == L.EINVAL
+    assert lib.fcpp_last_error()
+
+
+def test_engine_surface_exists_and_has_no_cpu_fallback():
+    for name in ('trajectory', 'trajectory_sample'):
+        assert callable(getattr(E, name))
+    for name in ('trajectory', 'sample', 'path_offsets'):
+        assert callable(getattr(E.BatchResult, name))
+    from field_coverage_path_planning_amd import multi_layer_planner_v3 as M
+    assert callable(M.TwoLayerPathPlannerV37.trajectory)
+    import torch
+    if torch.cuda.is_available():       # (with a GPU the calls compute: tests/test_gpu_trajectory.py)
+        return
+    x = np.linspace(0.0, 10.0, 11)
+    with pytest.raises(RuntimeError):
+        E.trajectory(x, np.zeros_like(x), np.full_like(x, 9.0))
+    with pytest.raises(RuntimeError):
+        E.trajectory_sample(x, np.zeros_like(x), np.full_like(x, 9.0), 0.1)
