@@ -102,14 +102,12 @@ struct Tiling {
             paths[(size_t)p] = { offsets[p], n };
             tile_first[(size_t)p] = (int64_t)tiles.size();
             if (n <= 0) continue;
-            const int64_t k = (n + TILE_POINTS - 1) / TILE_POINTS, base = n / k, rem = n % k;
-            int64_t a = 0;
+            const int64_t k = (n + TILE_POINTS - 1) / TILE_POINTS;
+            const TilerSplit<int64_t> sp(n, k);
             for (int64_t i = 0; i < k; ++i) {
-                const int64_t c = base + (i < rem ? 1 : 0);
                 DevTile t;
-                t.field = (int32_t)p; t.start = a; t.count = (int32_t)c; t.quiet = 0; t.stat_tile = 0; t.idx0 = 0; t.off0 = 0;
+                t.field = (int32_t)p; t.start = sp.start(i); t.count = (int32_t)sp.count(i); t.quiet = 0; t.stat_tile = 0; t.idx0 = 0; t.off0 = 0;
                 tiles.push_back(t);
-                a += c;
             }
         }
         tile_first[(size_t)n_paths] = (int64_t)tiles.size();
@@ -852,7 +850,7 @@ DevTileConsts dev_tile_consts(const BatchTileConsts &k, const fcpp_batch &b, int
     tc.two_a = k.two_a; tc.u_cap = k.u_cap; tc.c_line = k.c_line; tc.fence_margin = k.fence_margin;
     tc.wave_factor = k.wave_factor; tc.field_work_tiles = FIELD_WORK_TILES; tc.reduce_wg_max = TileConsts::reduce_wg_max; tc.max_prims = max_prims;
     tc.no_bases = 0; tc.speculative = 0; tc.closed_cut = dense ? 0 : 1; tc.dense = dense ? 1 : 0;
-    tc.gen = gen; tc.f0 = 0; tc.f1 = n_fields;
+    tc.gen = gen;
     tc.cut = make_cut_consts(*b.templates, true, k, b.cst);
     return tc;
 }

@@ -327,12 +327,10 @@ FCPP_HD int cut_tile_eval(const DevField &F, const CutConsts &cc, const PV &pv, 
     const int ke = cut_locate(F, pv, np, s + c - 1, re);
     return cut_tile_eval_at(F, cc, pv, np, cap, s, c, kj, rj, ke, re, Hb, Hf, in);
 }
-// the candidate cuts: T near-equal tiles, T = cut_first_T(G), + 1, ... up to CUT_TILES_MAX; tile t of T: outputs [a + cut_tile_start, + cut_tile_count)
+// the candidate cuts: T near-equal tiles (TilerSplit), T = cut_first_T(G), + 1, ... up to CUT_TILES_MAX
 // (32-bit: a field of this cut has at most CUT_TILES_MAX x 128 general points)
 FCPP_HD int32_t cut_first_T(int32_t G) { return (G + CUT_WAVE_LANES - 1) / CUT_WAVE_LANES; }
 FCPP_HD bool cut_T_possible(int32_t G, int32_t T) { return T <= CUT_TILES_MAX && !(G / T < 8 && T > 1); }      // (fewer than eight outputs per tile: the general kernel's)
-FCPP_HD int32_t cut_tile_start(int32_t G, int32_t T, int32_t t) { const int32_t base = G / T, rem = G - base * T; return t * base + (t < rem ? t : rem); }
-FCPP_HD int32_t cut_tile_count(int32_t G, int32_t T, int32_t t) { const int32_t base = G / T, rem = G - base * T; return base + (t < rem ? 1 : 0); }
 
 // The cut of the general stretch [a, n_total), tile after tile (the host; the device runs the tiles of a candidate cut side by side, a lane
 // each, and takes the same decisions: fcpp_devplan.hip).  pv(k): the field's CutPrim records (cut_prim_info in path order).
@@ -346,8 +344,9 @@ FCPP_HD void cut_field(const DevField &F, const CutConsts &cc, const PV &pv, int
     const double cap = tiler_halo_cap(cc.u_cap);
     for (int32_t T = cut_first_T(G); cut_T_possible(G, T); ++T) {
         bool ok = true;
+        const TilerSplit<int32_t> sp(G, T);
         for (int32_t t = 0; t < T && ok; ++t) {
-            const int64_t s = a + cut_tile_start(G, T, t), c = cut_tile_count(G, T, t);
+            const int64_t s = a + sp.start(t), c = sp.count(t);
             int Hb = 0, Hf = 0;
             bool in = false;
             const int code = cut_tile_eval(F, cc, pv, np, cap, s, c, Hb, Hf, in);

@@ -61,7 +61,6 @@ struct DevTileConsts {
     double two_a, u_cap, c_line, fence_margin;
     int64_t reduce_wg_max;
     int64_t gen;                  // this counting phase's generation number (> 0)
-    int64_t f0, f1;               // counting pass: the fields [f0, f1) (launch_devplan_count sets them to the whole batch)
     CutConsts cut;                // the closed-form cut (fcpp_cutfn.h), templates and chord tables on the device
 };
 

@@ -110,15 +110,14 @@ __device__ __forceinline__ double area_centroid_q(double px, double py, int i, d
 }
 }  // namespace p16
 
-// (f0, f1: the fields [f0, f1) of the batch's n -- launch_devplan_count plans the whole batch: 0, n)
 __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, const fcpp_field *__restrict__ fin, fcpp_field_info *__restrict__ info,
                                                       DevField *__restrict__ ftmp, DevPrim *__restrict__ ptmp, int64_t *__restrict__ counts,
-                                                      int64_t *__restrict__ totals, int64_t n_polys, int check_obstacles, int64_t gen, int64_t f0, int64_t f1)
+                                                      int64_t *__restrict__ totals, int64_t n_polys, int check_obstacles, int64_t gen)
 {
     using namespace p16;
     const int lane = threadIdx.x, l16 = lane & 15, i = lane & 3, lp = l16 >> 2;
-    const int64_t field = f0 + (int64_t)blockIdx.x * 4 + (lane >> 4);
-    if (field >= f1) return;
+    const int64_t field = (int64_t)blockIdx.x * 4 + (lane >> 4);
+    if (field >= n) return;
     PSTAMP(0);
     const fcpp_field f = fin[field];
     if (check_obstacles && l16 == 0 && (f.n_obstacles < 0 || f.obstacle_first < 0 || (f.n_obstacles > 0 && f.obstacle_first + f.n_obstacles > n_polys)))
@@ -527,6 +526,8 @@ __device__ __forceinline__ int64_t wg_incl_scan(int64_t v, int64_t *lds /* 4 */,
 
 // what depends on where a field's span lies in the batch arrays (pt_off): its 512-point chunks, whether its field's own workgroup can write
 // it (at most FUSED_SPAN_CHUNKS of them), the alternatives the host chooses between once it has the totals
+// (n_chunks = tiler_run_chunks(pt_off, S), kept as written: through the helper the scan kernels, which this function is inlined into, come out
+// with their instructions in another order and other scalar registers -- they stay as compiled)
 __device__ __forceinline__ void span_counts(int64_t pt_off, int64_t S, bool is_work, bool fuse_possible, int64_t &c_span, int64_t &c_span_f,
                                             int64_t &c_work_span_pts, int64_t &c_unfusable)
 {
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(256) void k_scan_block_bases(int c0, int64_t *__res
 }
 // phase C: exclusive scan inside each block of 1024 fields + the block's base; grid (blocks, columns)
 // derive: the column of the points also makes the columns that depend on the fields' point offsets (span_counts), from the offsets it has just
-// computed -- the counting pass of a large batch, run in chunks beside the planner, goes without them as a small batch's does
+// computed -- the counting pass of a large batch goes without them as a small batch's does
 __global__ __launch_bounds__(256) void k_scan_apply(int64_t n, int c0, int64_t *__restrict__ counts, const int64_t *__restrict__ blk_sums,
                                                     int64_t nblk, int64_t *__restrict__ bases, int derive, int fuse_possible)
 {
@@ -704,14 +705,16 @@ int launch_scan(hipStream_t st, int64_t n, int c0, int c1, const DevPlanScratch 
 // path's own step lengths -- the points evaluated lane-parallel into LDS, the greedy cut walked wave-uniformly -- or, when a wave tile
 // cannot be formed, into general tiles of up to 512 points.
 // Diagnostic build only (-DFCPP_DIAG_TILE: `make diag-tile`, tools/diag_tile.py; never shipped): 10 ns time stamps of the phases of field
-// 1000's counting pass.
+// 1000's counting pass (WSTAMP: of the window's third round of 64 points).
 #ifdef FCPP_DIAG_TILE
 __device__ unsigned long long g_tile_stamps[40], g_fill_stamps[40];
 #define TSTAMP(k) do { if (!FILL && field == 1000 && lane == 0 && (k) < 40) g_tile_stamps[k] = wall_clock64(); } while (0)
 #define FSTAMP(k) do { if (FILL && field == 1000 && lane == 0 && (k) < 40) g_fill_stamps[k] = wall_clock64(); } while (0)
+#define WSTAMP(k) do { if (w_base == 128) TSTAMP(k); } while (0)
 #else
 #define TSTAMP(k) do { } while (0)
 #define FSTAMP(k) do { } while (0)
+#define WSTAMP(k) do { } while (0)
 #endif
 constexpr int TW_WAVES = 2;                                             // fields per workgroup
 constexpr int TW_NW = DEVPLAN_WINDOW;                                   // points of the LDS window that slides along a general stretch
@@ -733,676 +736,694 @@ struct TileWaveLds {
     uint8_t ins[TW_NW];           // window point w lies inside the geofence with the host's margin
 };
 
-__device__ __forceinline__ int32_t clampi(int64_t v) { return (int32_t)(v < -2 ? -2 : (v > ((int64_t)1 << 30) ? ((int64_t)1 << 30) : v)); }
+// statistics entry e is its own entry, not a run; its slot zeroed
+static_assert(sizeof(TilePartial) == 13 * 8, "thirteen 8-byte components");
+__device__ __forceinline__ void init_entry(const DevPlanTables &T, int64_t e)
+{
+    T.stat_ids[e] = (int32_t)e; T.stat_run[e] = 0;
+    unsigned long long *slot = reinterpret_cast<unsigned long long *>(T.partial + e);
+    for (int w = 0; w < 13; ++w) slot[w] = 0ull;
+}
 
+// the closed-form statistics of the quiet run of entry e (`count` points, tile tl) of field F, as they stand in the run's slot: what
+// k_run_consts computes at batch creation on the host path (the flag counts of the run's points are k_plan_quiet's)
+__device__ __forceinline__ TilePartial run_consts(const DevField &F, double2 junc, int64_t e, int64_t count, const DevTile &tl,
+                                                  const DevPrim *__restrict__ prims, const DevConst &cst)
+{
+    FieldStatView fv;
+    fv.set(F, junc);
+    const DevRun run = { (int32_t)e, 0, count };
+    TilePartial tp = quiet_run_partial(run, tl, fv, prims, cst);
+    tp.n_viol = tp.n_outside = tp.n_in_obstacle = tp.n_adjusted = 0;
+    return tp;
+}
+__device__ __forceinline__ double2 field_junction(const DevField &F, const DevConst &cst)
+{
+    double2 junc = make_double2(0.0, 0.0);
+    if (F.P >= 2 && F.n_line >= 2 && F.n_turn >= 1) junc.x = line_start_curvature(F, cst, 1, junc.y);
+    return junc;
+}
+
+// One field's pass through the tiler: what the launch gave, what the pass decides (the counts), and -- fill pass -- where its records go.
+// tile_fields_body below runs the phases in order; all of them are inlined into the kernel.
 // DENSE: the instance for batches at dense sampling (the dense block and the window cut; no closed-form cut) -- an instance of its own so that
 // the sparse instances keep their registers (with the dense block compiled in, the counting pass of large batches went from 79 to 108
 // vector registers: four wavefronts per SIMD instead of six)
 template <bool FILL, bool STAGE, bool DENSE>
-__device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
-                                                 fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts,
-                                                 const int64_t *__restrict__ bases, int64_t *__restrict__ totals,
-                                                 DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, const DevPlanTables &T)
-{
-    __shared__ TileWaveLds<STAGE> lds_all[TW_WAVES];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int64_t field = (FILL ? 0 : tc.f0) + (int64_t)blockIdx.x * TW_WAVES + wave;      // (the counting pass of a large batch runs in chunks: fields [f0, f1))
-    if (field >= (FILL ? n : tc.f1)) return;
-    TSTAMP(0);
-    FSTAMP(0);
-    TileWaveLds<STAGE> &L = lds_all[wave];
-    const DevField &F = ftmp[field];
-    const DevPrim *prims = ptmp + field * tc.max_prims;
+struct TilePass {
+    // ---- the launch and the field
+    const int64_t n;
+    const DevTileConsts &tc;
+    const DevConst &cst;
+    const DevField &F;
+    const DevPrim *const prims;
+    int64_t *const counts;
+    const int64_t *const bases;
+    int64_t *const totals;
+    DevTile *const keep_tiles;
+    DevWaveTile *const keep_wtiles;
+    const DevPlanTables &T;
+    TileWaveLds<STAGE> &L;
+    const int64_t field;
+    const int lane;
     const int64_t n_total = F.n_total;
-    auto base_of = [&](int col) -> int64_t { return bases[(int64_t)col * n + field]; };
-    // a speculative fill pass does nothing when the counting phase raised a flag: the host sets the batch up again (or elsewhere)
-    if (FILL && tc.speculative) {
-        bool up = false;
-        for (int k = 0; k < PF_COUNT; ++k) up = up || totals[PC_COLS + k] == tc.gen;
-        if (up) return;
-    }
-    // (speculative: the fusing of spans is the host's rule applied here -- all fields of field work have fusable spans, or nothing is fused)
-    const bool fuse_spans = (FILL && tc.speculative) ? (tc.fuse_spans != 0 && totals[PC_UNFUSABLE] == 0 && totals[PC_WORK_SPAN_PTS] > 0) : tc.fuse_spans != 0;
-    // (scanned before either pass -- except before the counting pass of a small batch: tc.no_bases, see span_counts)
-    const bool no_bases = !FILL && tc.no_bases != 0;
-    const int64_t pt_off = no_bases ? 0 : base_of(PC_POINTS);
-
-    // the field's counts (count pass) / positions (fill pass)
-    int64_t c_tiles = 0, c_wave = 0, c_general = 0, c_stat = 0, c_span = 0, c_work = 0, c_open = 0, c_runs = 0, c_span_pts = 0, c_wave_pts = 0,
-            c_work_wave_pts = 0, c_wave_inside = 0, c_work_span_pts = 0, c_span_f = 0, c_unfusable = 0, c_chunks_out = 0, c_chunk_pts_out = 0;
-    bool dense_entries = false;          // (fill pass: the dense block has written the field's entries, slots and chunks itself -- all but the span's)
-    int cls = 0;
-    int64_t wave_base = 0, general_base = 0, stat_base = 0, span_base = 0, prim_base = 0;
-    if (FILL) {
-        wave_base = base_of(PC_WAVE); general_base = base_of(PC_GENERAL); stat_base = base_of(PC_STAT);
-        span_base = base_of(fuse_spans ? PC_SPAN_F : PC_SPAN); prim_base = base_of(PC_PRIMS);
-    }
     const int prim_count = F.prim_count;
-    const int64_t prim_index0 = prim_base;           // batch-wide index of the field's first primitive (fill pass)
-    // fill pass: everything it copies out of the scratch -- the field's descriptor, its fcpp_field_info, its primitives, a word per lane and
-    // round -- is requested here, before the cut: the copies further down then wait for nothing (they were a chain of six round trips)
-    constexpr int NFW = (int)(sizeof(DevField) / 8), NIW = (int)(sizeof(fcpp_field_info) / 8), PWD = (int)(sizeof(DevPrim) / 8), PF_ROUNDS = 7;
-    static_assert(sizeof(DevField) % 8 == 0 && sizeof(DevPrim) % 8 == 0 && sizeof(fcpp_field_info) % 8 == 0 && NFW <= 64 && NIW <= 64, "copied as 8-byte words, a lane each");
-    unsigned long long fw = 0, iw = 0, pw[PF_ROUNDS];
-    const int nwords_p = prim_count * PWD;
-    if (FILL) {
-        if (lane < NFW) fw = reinterpret_cast<const unsigned long long *>(&F)[lane];
-        if (lane < NIW) iw = reinterpret_cast<const unsigned long long *>(&info[field])[lane];
-#pragma unroll
-        for (int j = 0; j < PF_ROUNDS; ++j) { const int k = lane + 64 * j; pw[j] = k < nwords_p ? reinterpret_cast<const unsigned long long *>(prims)[k] : 0ull; }
-        // (pt_off and prim_first become batch-wide: patched by the lane that holds their word)
-        constexpr int W_PT = (int)(offsetof(DevField, pt_off) / 8), W_PF = (int)(offsetof(DevField, prim_first) / 8);
-        constexpr bool PF_HI = (offsetof(DevField, prim_first) % 8) != 0;
-        if (lane == W_PT) fw = (unsigned long long)pt_off;
-        if (lane == (int)(offsetof(fcpp_field_info, point_offset) / 8)) iw = (unsigned long long)pt_off;      // (the planner left it 0)
-        if (lane == W_PF) fw = PF_HI ? ((fw & 0xffffffffull) | ((unsigned long long)(uint32_t)prim_base << 32)) : ((fw & 0xffffffff00000000ull) | (unsigned long long)(uint32_t)prim_base);
-    }
 
+    // ---- the field's counts (count pass) / positions (fill pass)
+    int64_t c_tiles = 0, c_wave = 0, c_general = 0, c_stat = 0, c_span = 0, c_work = 0, c_open = 0, c_runs = 0, c_span_pts = 0, c_wave_pts = 0,
+            c_work_wave_pts = 0, c_wave_inside = 0, c_work_span_pts = 0, c_span_f = 0, c_unfusable = 0, c_chunks = 0, c_chunk_pts = 0;
+    int cls = 0;
+    bool fuse_spans = false, no_bases = false;
+    int64_t pt_off = 0, wave_base = 0, general_base = 0, stat_base = 0, span_base = 0;
+    int64_t prim_index0 = 0;             // batch-wide index of the field's first primitive (fill pass)
+    // what the pass decides
+    int64_t S = 0, span_k = 0, fused_span = 0;      // the span: its points, its near-equal tiles
+    int64_t n_wave = 0, n_general = 0, n_quiet = 0;
     bool fallback = false, is_work = false;
-    TSTAMP(1);
-    FSTAMP(1);
-    int64_t S = 0, span_k = 0, fused_span = 0;
-    int64_t n_wave = 0, n_general = 0;
+    bool dense_entries = false;          // (fill pass: the dense block has written the field's entries, slots and chunks itself -- all but the span's)
     // fill pass, lane t: the field's t-th wave tile as written (t < DEVPLAN_KEEP_TILES), its first primitive within the field and the
     // number of primitives its points lie in (0: none of layer 2) -- what the field's pack takes (DevFieldPack)
     DevWaveTile my_wt;
-    memset(&my_wt, 0, sizeof my_wt);
     int my_p0_rel = 0, my_np = 0;
-    if (n_total > 0) {
-        const int64_t per = (int64_t)F.n_line + F.n_turn, P = F.P, gen_main = F.gen_main;
-        const double line_step_len = fabs(F.line_step);
-        const bool turn_quiet = tc.turn_quiet && F.n_turn == tc.nu && F.line_step > 0.0;
-        const bool wave_ok = F.n_turn == tc.nu && (double)tc.wave_factor * tc.two_a * line_step_len >= tc.u_cap;
-        // (sample_spacing = 0: 2 points per line, 20 per headland straight -- no quiet zone anywhere; dense sampling: the block below)
-        constexpr bool dense = DENSE;
-        if ((!dense && F.n_line >= 64) || prim_count > (dense ? 62 : DEVPLAN_PRIMS_CAP)) fallback = true;
-        int64_t pos = 0;
-        const int64_t need1 = tiler_need_for(tc.c_line, line_step_len, tc.two_a);
+    // fill pass: the words of the field's descriptor, its fcpp_field_info and its primitives, a word per lane and round
+    static constexpr int NFW = (int)(sizeof(DevField) / 8), NIW = (int)(sizeof(fcpp_field_info) / 8), PWD = (int)(sizeof(DevPrim) / 8), PF_ROUNDS = 7;
+    static_assert(sizeof(DevField) % 8 == 0 && sizeof(DevPrim) % 8 == 0 && sizeof(fcpp_field_info) % 8 == 0 && NFW <= 64 && NIW <= 64, "copied as 8-byte words, a lane each");
+    unsigned long long fw = 0, iw = 0, pw[PF_ROUNDS];
+    int nwords_p = 0;
+    // the path's shape (n_total > 0: path_consts)
+    int64_t per = 0, P = 0, gen_main = 0, n_main = 0, need1 = 0, pos = 0;
+    double line_step_len = 0.0, cap = 0.0;
+    bool turn_quiet = false, wave_ok = false;
+    // the window cut's staged copies (stage_window)
+    bool win_staged = false;
+    const DevPrim *wprims = prims;
+    const Pt2 *wtu = tc.tu, *wtc = tc.tc;
+    int32_t my_pstart = INT32_MAX;
+
+    __device__ __forceinline__ int64_t base_of(int col) const { return bases[(int64_t)col * n + field]; }
+    __device__ __forceinline__ int64_t first_entry() const { return span_k > 0 ? 1 : 0; }      // the field's first entry behind its span's
+
+    // ---- 1. the field's header; the fill pass's early loads.  false: a speculative fill pass with nothing to do
+    __device__ __forceinline__ bool header(const fcpp_field_info *__restrict__ info)
+    {
+        // a speculative fill pass does nothing when the counting phase raised a flag: the host sets the batch up again (or elsewhere)
+        if (FILL && tc.speculative) {
+            bool up = false;
+            for (int k = 0; k < PF_COUNT; ++k) up = up || totals[PC_COLS + k] == tc.gen;
+            if (up) return false;
+        }
+        // (speculative: the fusing of spans is the host's rule applied here -- all fields of field work have fusable spans, or nothing is fused)
+        fuse_spans = (FILL && tc.speculative) ? (tc.fuse_spans != 0 && totals[PC_UNFUSABLE] == 0 && totals[PC_WORK_SPAN_PTS] > 0) : tc.fuse_spans != 0;
+        // (scanned before either pass -- except before the counting pass of a small batch: tc.no_bases, see span_counts)
+        no_bases = !FILL && tc.no_bases != 0;
+        pt_off = no_bases ? 0 : base_of(PC_POINTS);
+        if (FILL) {
+            wave_base = base_of(PC_WAVE); general_base = base_of(PC_GENERAL); stat_base = base_of(PC_STAT);
+            span_base = base_of(fuse_spans ? PC_SPAN_F : PC_SPAN); prim_index0 = base_of(PC_PRIMS);
+        }
+        // fill pass: everything it copies out of the scratch -- the field's descriptor, its fcpp_field_info, its primitives, a word per lane and
+        // round -- is requested here, before the cut: the copies further down then wait for nothing (they were a chain of six round trips)
+        nwords_p = prim_count * PWD;
+        if (FILL) {
+            if (lane < NFW) fw = reinterpret_cast<const unsigned long long *>(&F)[lane];
+            if (lane < NIW) iw = reinterpret_cast<const unsigned long long *>(&info[field])[lane];
+#pragma unroll
+            for (int j = 0; j < PF_ROUNDS; ++j) { const int k = lane + 64 * j; pw[j] = k < nwords_p ? reinterpret_cast<const unsigned long long *>(prims)[k] : 0ull; }
+            // (pt_off and prim_first become batch-wide: patched by the lane that holds their word)
+            constexpr int W_PT = (int)(offsetof(DevField, pt_off) / 8), W_PF = (int)(offsetof(DevField, prim_first) / 8);
+            constexpr bool PF_HI = (offsetof(DevField, prim_first) % 8) != 0;
+            if (lane == W_PT) fw = (unsigned long long)pt_off;
+            if (lane == (int)(offsetof(fcpp_field_info, point_offset) / 8)) iw = (unsigned long long)pt_off;      // (the planner left it 0)
+            if (lane == W_PF) fw = PF_HI ? ((fw & 0xffffffffull) | ((unsigned long long)(uint32_t)prim_index0 << 32)) : ((fw & 0xffffffff00000000ull) | (unsigned long long)(uint32_t)prim_index0);
+        }
+        memset(&my_wt, 0, sizeof my_wt);
+        return true;
+    }
+
+    // ---- 2. the path's shape, and whether its complete passes form a span
+    __device__ __forceinline__ void span_decision()
+    {
+        per = (int64_t)F.n_line + F.n_turn; P = F.P; gen_main = F.gen_main;
+        line_step_len = fabs(F.line_step);
+        turn_quiet = tc.turn_quiet && F.n_turn == tc.nu && F.line_step > 0.0;
+        wave_ok = F.n_turn == tc.nu && (double)tc.wave_factor * tc.two_a * line_step_len >= tc.u_cap;
+        // (sample_spacing = 0: 2 points per line, 20 per headland straight -- no quiet zone anywhere; dense sampling: the dense block)
+        if ((!DENSE && F.n_line >= 64) || prim_count > (DENSE ? 62 : DEVPLAN_PRIMS_CAP)) fallback = true;
+        need1 = tiler_need_for(tc.c_line, line_step_len, tc.two_a);
         if (need1 >= 0 && per > 0 && gen_main > 0) {
             const bool span = turn_quiet && P >= 2 && (int64_t)F.n_line - need1 < (F.obs_count > 0 ? (int64_t)64 : tc.span_line_max) && (P - 1) * per < (int64_t)0x7fffffff;
             if (span) { S = (P - 1) * per; span_k = (S + (TILE_POINTS - 2) - 1) / (TILE_POINTS - 2); pos = S; }
         }
-        // ---- the WINDOW cut of one general stretch [a, b) into wave tiles (FieldTiler::wave_tiles): the sparse field's one stretch (fields the
-        // closed-form cut does not take) and, round 5, every stretch of a dense field.  mode 0: counting pass of a sparse field (its first
-        // DEVPLAN_KEEP_TILES tiles kept), 1: its fill pass, 2: a dense field's counting pass (nothing written), 3: its fill pass; e_first / w_first:
-        // the stretch's first statistics entry / wave tile within the field.  -> tiles cut, or -1: the stretch is the general kernel's.
-        const double cap = tiler_halo_cap(tc.u_cap);
-        const int64_t n_main = F.n_main;
-        bool win_staged = false;
-        const DevPrim *wprims = prims;
-        const Pt2 *wtu = tc.tu, *wtc = tc.tc;
-        int32_t my_pstart = INT32_MAX;
-        auto stage_window = [&]() {
-            if (win_staged) return;
-            win_staged = true;
-            const bool lds_prims = STAGE && prim_count <= TW_LDS_PRIMS, lds_tmpl = STAGE && tc.nu + tc.nc <= TW_LDS_TMPL;
-            if (lds_prims && lds_tmpl) {
-                // the usual field: starts, records and templates requested together, then stored -- one round trip to memory, not three
-                static_assert(TW_LDS_PRIMS <= 64 && TW_LDS_TMPL <= 64 && TW_LDS_PRIMS * (sizeof(DevPrim) / 8) <= 6 * 64, "a lane each / six words a lane");
+        cap = tiler_halo_cap(tc.u_cap);
+        n_main = F.n_main;
+    }
+
+    // ---- 3. the WINDOW cut of one general stretch into wave tiles (FieldTiler::wave_tiles): the sparse field's one stretch (fields the
+    // closed-form cut does not take) and, round 5, every stretch of a dense field.
+    // the field's primitive starts (and, STAGE, its primitives and the batch's turn templates) into LDS, once
+    __device__ __forceinline__ void stage_window()
+    {
+        if (win_staged) return;
+        win_staged = true;
+        const bool lds_prims = STAGE && prim_count <= TW_LDS_PRIMS, lds_tmpl = STAGE && tc.nu + tc.nc <= TW_LDS_TMPL;
+        if (lds_prims && lds_tmpl) {
+            // the usual field: starts, records and templates requested together, then stored -- one round trip to memory, not three
+            static_assert(TW_LDS_PRIMS <= 64 && TW_LDS_TMPL <= 64 && TW_LDS_PRIMS * (sizeof(DevPrim) / 8) <= 6 * 64, "a lane each / six words a lane");
+            const unsigned long long *src = reinterpret_cast<const unsigned long long *>(prims);
+            const int nw = prim_count * (int)(sizeof(DevPrim) / 8);
+            const int64_t st = lane < prim_count ? prims[lane].start : 0;
+            unsigned long long w6[6];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) { const int k = lane + 64 * j; w6[j] = k < nw ? src[k] : 0ull; }
+            Pt2 tp = { 0.0, 0.0 };
+            if (lane < tc.nu) tp = tc.tu[lane];
+            else if (lane < tc.nu + tc.nc) tp = tc.tc[lane - tc.nu];
+            if (lane < prim_count) L.pstart[lane] = (int32_t)(st - n_main);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) { const int k = lane + 64 * j; if (k < nw) L.prim_words[k] = w6[j]; }
+            if (lane < tc.nu + tc.nc) L.tmpl[lane] = tp;
+        } else {
+            for (int k = lane; k < prim_count; k += 64) L.pstart[k] = (int32_t)(prims[k].start - n_main);
+            if (lds_prims) {
                 const unsigned long long *src = reinterpret_cast<const unsigned long long *>(prims);
-                const int nw = prim_count * (int)(sizeof(DevPrim) / 8);
-                const int64_t st = lane < prim_count ? prims[lane].start : 0;
-                unsigned long long w6[6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) { const int k = lane + 64 * j; w6[j] = k < nw ? src[k] : 0ull; }
-                Pt2 tp = { 0.0, 0.0 };
-                if (lane < tc.nu) tp = tc.tu[lane];
-                else if (lane < tc.nu + tc.nc) tp = tc.tc[lane - tc.nu];
-                if (lane < prim_count) L.pstart[lane] = (int32_t)(st - n_main);
-#pragma unroll
-                for (int j = 0; j < 6; ++j) { const int k = lane + 64 * j; if (k < nw) L.prim_words[k] = w6[j]; }
-                if (lane < tc.nu + tc.nc) L.tmpl[lane] = tp;
-            } else {
-                for (int k = lane; k < prim_count; k += 64) L.pstart[k] = (int32_t)(prims[k].start - n_main);
-                if (lds_prims) {
-                    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(prims);
-                    for (int k = lane; k < prim_count * (int)(sizeof(DevPrim) / 8); k += 64) L.prim_words[k] = src[k];
-                }
-                if (lds_tmpl) {
-                    for (int k = lane; k < tc.nu; k += 64) L.tmpl[k] = tc.tu[k];
-                    for (int k = lane; k < tc.nc; k += 64) L.tmpl[tc.nu + k] = tc.tc[k];
-                }
+                for (int k = lane; k < prim_count * (int)(sizeof(DevPrim) / 8); k += 64) L.prim_words[k] = src[k];
             }
-            wprims = lds_prims ? reinterpret_cast<const DevPrim *>(L.prim_words) : prims;
-            wtu = lds_tmpl ? L.tmpl : tc.tu; wtc = lds_tmpl ? L.tmpl + tc.nu : tc.tc;
-            wave_sync();                                     // the starts (and the staged records) are in LDS
-            my_pstart = lane < prim_count ? L.pstart[lane] : INT32_MAX;       // (fields of at most 64 primitives: their starts, a lane each)
-            TSTAMP(2);
-        };
-        auto cut_stretch = [&](const int64_t a, const int64_t b, const int mode, const int64_t e_first, const int64_t w_first, int64_t &wave_pts,
-                               int64_t &inside_cnt) -> int64_t {
-            stage_window();
-            // the host evaluates the points [lo - 1, hi) of the stretch at once; here a window of TW_NW points slides along with the cut
-            // (a tile starting at s touches the points [s - 43, s + 171) at most), the points are the same function values wherever the
-            // window lies
-            const int64_t lo_all = (a - WAVE_HALO_MAX - 2 > 1) ? a - WAVE_HALO_MAX - 2 : 1;
-            const int64_t hi_all = (b + WAVE_HALO_MAX + 2 < n_total) ? b + WAVE_HALO_MAX + 2 : n_total;
-            int64_t win0 = 0, win1 = -1;                     // window = path points [win0, win1)
-            auto dist = [&](int64_t i) -> double { return L.d[i - win0 - 1]; };
-            auto prim_of = [&](int64_t i) -> int { return (int)L.pidx[i - win0]; };
-            const int WAVE_LANES = 128;
-            int64_t s = a;
-            int64_t ordinal = 0;
-            bool refused_l = false;
-            while (s < b) {
-                const int64_t need_lo = (s - WAVE_HALO_MAX - 3 > lo_all - 1) ? s - WAVE_HALO_MAX - 3 : lo_all - 1;
-                const int64_t need_hi = (s + WAVE_LANES + WAVE_HALO_MAX + 3 < hi_all) ? s + WAVE_LANES + WAVE_HALO_MAX + 3 : hi_all;
-                if (!(win0 <= need_lo && need_hi <= win1)) {
-                    // ---- the window's points, lane-parallel: step lengths, geofence margin, primitive of every point
-                    wave_sync();
-                    win0 = need_lo; win1 = (win0 + TW_NW < hi_all) ? win0 + TW_NW : hi_all;
-                    const int nwin = (int)(win1 - win0);
-                    double cx = 0.0, cy = 0.0;               // the previous round's last point
-                    for (int w_base = 0; w_base < nwin; w_base += 64) {
-                        const int w = w_base + lane;
-                        const bool valid = w < nwin;
-                        const int64_t i = win0 + (valid ? w : nwin - 1);
-                        double px = 0.0, py = 0.0;
-                        int pk = 0;
-#ifdef FCPP_DIAG_TILE
-#define WSTAMP(k) do { if (w_base == 128) TSTAMP(k); } while (0)
-#else
-#define WSTAMP(k) do { } while (0)
-#endif
-                        WSTAMP(24);
-                        const int64_t i_last = win0 + ((w_base + 63 < nwin) ? w_base + 63 : nwin - 1);      // (wave-uniform)
-                        if (i < gen_main) {
-                            int64_t idx, off;
-                            if (i_last < ((int64_t)1 << 31)) { const uint32_t q32 = (uint32_t)i / (uint32_t)per; idx = q32; off = (int64_t)((uint32_t)i - q32 * (uint32_t)per); }
-                            else { idx = i / per; off = i - idx * per; }
-                            tiler_point_main(F, wtu, idx, off, px, py);
-                        }
-                        if (i_last >= gen_main) {
-                            // layer 2: the primitives this round's points lie in, one after the other (wave-uniform: a handful per
-                            // round) -- every lane's primitive is the last one that starts at or before its point, as a search per lane finds it
-                            const int64_t i_first = win0 + w_base;
-                            const int32_t rel = (int32_t)(i - n_main);
-                            const int32_t rel_lo = i_first > n_main ? (int32_t)(i_first - n_main) : 0, rel_hi = (int32_t)(i_last - n_main);
-                            // every lane's primitive = the last one that starts at or before its point: the first point's by one ballot
-                            // over the starts (a lane each), the few that start inside the round counted in; fields of more than 64
-                            // primitives search per lane
-                            if (prim_count <= 64) {
-                                int k = __popcll(__ballot(my_pstart <= rel_lo)) - 1;
-                                if (k < 0) k = 0;
-                                pk = k;
-                                for (++k; k < prim_count; ++k) {
-                                    const int32_t st_k = __builtin_amdgcn_readlane(my_pstart, k);
-                                    if (st_k > rel_hi) break;
-                                    pk += rel >= st_k ? 1 : 0;
-                                }
-                            } else {
-                                int lo_k = 0, hi_k = prim_count - 1;
-                                while (lo_k < hi_k) { const int m = (lo_k + hi_k + 1) >> 1; if (L.pstart[m] <= rel) lo_k = m; else hi_k = m - 1; }
-                                pk = lo_k;
-                            }
-                            WSTAMP(25);
-                            if (i >= gen_main) {
-                                const DevPrim q = wprims[pk];
-                                tiler_point_prim(q, wtu, wtc, (int)(i - q.start), px, py);
-                            } else pk = 0;
-                        }
-                        WSTAMP(26);
-                        double qx = __shfl_up(px, 1), qy = __shfl_up(py, 1);
-                        if (lane == 0) { qx = cx; qy = cy; }
-                        cx = __shfl(px, 63); cy = __shfl(py, 63);
-                        if (valid) {
-                            if (w >= 1) { const double dx = px - qx, dy = py - qy; L.d[w - 1] = sqrt(dx * dx + dy * dy); }
-                            WSTAMP(27);
-                            L.pidx[w] = (uint8_t)pk;
-                            L.ins[w] = tiler_inside(F, px, py, tc.fence_margin) ? 1 : 0;
-                        }
-                        WSTAMP(28);
-                    }
-                    wave_sync();
-                }
-                // ---- one step of the greedy cut, wave-uniform
-                TSTAMP(3 + 4 * (int)ordinal);
-                const int Hb = tiler_back_halo(dist, s, tc.two_a, cap);
-                TSTAMP(4 + 4 * (int)ordinal);
-                if (Hb < 0) { refused_l = true; break; }
-                const int64_t cmax = (b - s < WAVE_LANES - Hb) ? b - s : WAVE_LANES - Hb;
-                const int64_t first0 = s - Hb;
-                const int pa0 = first0 + Hb + cmax - 1 >= gen_main ? prim_of(first0 > gen_main ? first0 : gen_main) : 0;
-                // the largest count whose forward halo still fits and whose points lie in at most nine primitives: candidates lane-parallel
-                int64_t c = 0;
-                int Hf = -1;
-                for (int64_t cb = 0; cb < cmax; cb += 64) {
-                    const int64_t cand = cmax - cb - lane;
-                    bool ok = false;
-                    int hf = -1;
-                    if (cand >= 1) {
-                        hf = tiler_fwd_halo(dist, s + cand - 1, n_total, tc.two_a, cap);
-                        ok = hf >= 0 && Hb + cand + hf <= WAVE_LANES;
-                        if (ok) { const int64_t last0 = s + cand - 1 + hf; if (last0 >= gen_main && prim_of(last0) - pa0 > 8) ok = false; }
-                    }
-                    const unsigned long long m = __ballot(ok);
-                    if (m) {
-                        const int l0 = __builtin_ctzll(m);
-                        c = cmax - cb - l0;
-                        Hf = __shfl(hf, l0);
-                        break;
-                    }
-                }
-                if (c < (b - s < 8 ? b - s : 8)) { refused_l = true; break; }
-                TSTAMP(5 + 4 * (int)ordinal);
-                const int64_t first = s - Hb, last = s + c - 1 + Hf;
-                // every output point inside the geofence with the margin?
-                bool all_in = true;
-                for (int64_t o0 = 0; o0 < c; o0 += 64) {
-                    const int64_t o = o0 + lane;
-                    const bool bad = o < c && L.ins[s + o - win0] == 0;
-                    if (__ballot(bad)) all_in = false;
-                }
-                int pa = 0, pb = 0;
-                if (last >= gen_main) {
-                    const int64_t fl2 = first > gen_main ? first : gen_main;
-                    pa = prim_of(fl2); pb = prim_of(last);
-                    if (pb - pa > 8) { refused_l = true; break; }
-                    bool bad = false;
-                    for (int k = pa + 1; k <= pb; ++k) if (L.pstart[k] <= L.pstart[k - 1]) bad = true;
-                    if (bad) { refused_l = true; break; }
-                }
-                // (kept by the counting pass, indices relative to the field: a sparse field's first DEVPLAN_KEEP_TILES tiles, a dense field's first
-                // DEVPLAN_KEEP_ROWS over all its stretches -- row = the tile's number within the field)
-                const bool wr_fill = mode == 1 || mode == 3;
-                const bool wr_keep = (mode == 0 && ordinal < DEVPLAN_KEEP_TILES) || (mode == 2 && w_first + ordinal < DEVPLAN_KEEP_ROWS);
-                if ((wr_fill || wr_keep) && lane == 0) {
-                    // (count pass: indices relative to the field -- primitive 0 = the field's first, entry 0 = its first, out_base = first)
-                    const int64_t p_base = wr_fill ? prim_index0 : 0;
-                    DevTile t;
-                    t.field = (int32_t)field; t.count = (int32_t)c; t.start = s; t.quiet = 5; t.stat_tile = Hb | (Hf << 16);
-                    if (first < gen_main) { t.idx0 = (int32_t)(first / per); t.off0 = (int32_t)(first % per); }
-                    else { t.idx0 = (int32_t)(p_base + prim_of(first)); t.off0 = 0; }
-                    DevWaveTile wt;
-                    memset(&wt, 0, sizeof wt);
-                    wt.out_base = (wr_fill ? pt_off : 0) + first; wt.field = (int32_t)field;
-                    wt.tile = (int32_t)((wr_fill ? stat_base : 0) + e_first + ordinal);
-                    wt.count = (uint8_t)c; wt.hb = (uint8_t)Hb; wt.hf = (uint8_t)Hf; wt.inside = all_in ? 1 : 0;
-                    wt.rel_main = clampi(gen_main - first); wt.rel_seam = clampi(n_main - first); wt.rel_last = clampi(n_total - 1 - first);
-                    wt.rel_zero = clampi(-first);
-                    wt.idx0 = t.idx0; wt.off0 = t.off0;
-                    for (int k = 0; k < 8; ++k) wt.thr[k] = 255;
-                    if (last >= gen_main) {
-                        wt.p0 = (int32_t)(p_base + pa);
-                        wt.r0 = (int32_t)(first - (n_main + L.pstart[pa]));
-                        for (int k = pa + 1; k <= pb; ++k) wt.thr[k - pa - 1] = (uint8_t)(n_main + L.pstart[k] - first);
-                    }
-                    if (wr_fill) { T.tiles[stat_base + e_first + ordinal] = t; T.wtiles[wave_base + w_first + ordinal] = wt; }
-                    else { keep_tiles[field * DEVPLAN_KEEP_ROWS + w_first + ordinal] = t; keep_wtiles[field * DEVPLAN_KEEP_WROWS + w_first + ordinal] = wt; }
-                }
-                TSTAMP(6 + 4 * (int)ordinal);
-                inside_cnt += all_in ? 1 : 0;
-                wave_pts += c;
-                ++ordinal;
-                s += c;
-            }
-            return refused_l ? -1 : ordinal;
-        };
-        // ---- DENSE sampling (round 5; FieldTiler::tile_field + derive_field for a field whose complete passes form a span): behind the span the
-        // last swath line and every headland straight have a quiet zone of their own (a run: one tile, one statistics entry, chunks on
-        // 512-point boundaries of the batch arrays); the stretches between the zones are cut into wave tiles (samplings coarse enough for
-        // them -- 0.18 m and up at the default accelerations -- by the window cut above, a stretch after the other; a stretch it refuses
-        // is the general kernel's, as on the host) or into general tiles.  The zones a lane each (lane 0: the last line, lane 1 + k:
-        // primitive k), the stretches a lane each, places by prefix sums over the lanes.  Not taken here (PF_FALLBACK: the host sets the
-        // batch up): fields without a span (obstacles, turns that are not closed form), more than 62 primitives, fields of field work.
-        int64_t n_quiet = 0, c_chunks = 0, c_chunk_pts = 0;
-        if (dense && !fallback) {
-            if (!(S > 0 && F.obs_count == 0 && gen_main == F.n_main)) fallback = true;
-            else {
-                int64_t q_s = 0, q_n = 0;
-                int q_kind = 0, q_i0 = 0, q_o0 = 0;
-                bool valid = false;
-                if (lane == 0) {
-                    const int64_t Z = (int64_t)F.n_line - need1;          // (no margin at its start behind a span; need1 points before the seam to layer 2)
-                    if (Z >= 64) { valid = true; q_s = S; q_n = Z; q_kind = 1; q_i0 = (int)(P - 1); q_o0 = 0; }
-                } else if (lane - 1 < prim_count) {
-                    const DevPrim &pr = prims[lane - 1];
-                    if (pr.kind == PRIM_LINSPACE) {
-                        const double ms = pr.v_nom / 3.6;
-                        const int64_t need2 = tiler_need_for(ms * ms, sqrt(pr.a[4] * pr.a[4] + pr.a[5] * pr.a[5]), tc.two_a);
-                        const int64_t Z = (int64_t)pr.n - 2 * need2;
-                        if (need2 >= 0 && Z >= 64) { valid = true; q_s = pr.start + need2; q_n = Z; q_kind = 2; q_i0 = lane - 1; q_o0 = (int)need2; }
-                    }
-                }
-                const unsigned long long vm = __ballot(valid);
-                const int nq = __popcll(vm), rk = __popcll(vm & ((1ull << lane) - 1ull));
-                // the runs in path order: through the window's bytes into the lanes (lane j: run j and the stretch in front of it)
-                int64_t s_j = 0, z_j = 0, a_j = 0, len_j = 0;
-                int k_j = 0, i_j = 0, o_j = 0;
-                {
-                    int64_t *qs = reinterpret_cast<int64_t *>(L.d), *qn = qs + 64;
-                    int32_t *qk = reinterpret_cast<int32_t *>(qn + 64), *qi = qk + 64, *qo = qi + 64;
-                    static_assert(sizeof(L.d) >= 64 * (8 + 8 + 4 + 4 + 4), "the runs of a dense field fit the window's bytes");
-                    wave_sync();
-                    if (valid) { qs[rk] = q_s; qn[rk] = q_n; qk[rk] = q_kind; qi[rk] = q_i0; qo[rk] = q_o0; }
-                    wave_sync();
-                    if (lane < nq) { s_j = qs[lane]; z_j = qn[lane]; k_j = qk[lane]; i_j = qi[lane]; o_j = qo[lane]; }
-                    // stretch j = [end of run j - 1 (the span's for j = 0), start of run j (the path's end for j = nq))
-                    if (lane <= nq) {
-                        a_j = lane == 0 ? S : qs[lane - 1] + qn[lane - 1];
-                        const int64_t b_j = lane == nq ? n_total : s_j;
-                        len_j = b_j > a_j ? b_j - a_j : 0;
-                    }
-                    wave_sync();                                      // (the window cut writes these bytes)
-                }
-                int64_t ng_j = (len_j + TILE_POINTS - 1) / TILE_POINTS, nw_j = 0;       // general tiles of the stretch -- or its wave tiles
-                int64_t wave_pts = 0, inside_cnt = 0;
-                if (wave_ok) {
-                    // a stretch after the other, in path order.  The counting pass keeps the field's first DEVPLAN_KEEP_ROWS wave tiles (indices and
-                    // entries relative to the field) and, in the row behind them, a byte per stretch: its wave tiles, or 255 -- the general
-                    // kernel's, as the host decides.  The fill pass copies the kept tiles (a lane each); a field with more cuts again, only the
-                    // stretches that take wave tiles, whose records it can therefore write as it goes
-                    unsigned char *verdicts = reinterpret_cast<unsigned char *>(keep_wtiles + field * DEVPLAN_KEEP_WROWS + DEVPLAN_KEEP_ROWS);
-                    unsigned long long refused_mask = 0ull;
-                    bool recut = true;
-                    if (FILL) {
-                        // what the counting pass found: wave tiles per stretch (a lane each).  A field whose wave tiles were all kept is not cut again
-                        const int vb = lane <= nq ? (int)verdicts[lane] : 0;
-                        refused_mask = __ballot(vb == 255);
-                        if (lane <= nq && vb != 255 && len_j > 0) { nw_j = vb; ng_j = 0; }
-                        int64_t tot = nw_j;
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-                        recut = tot > DEVPLAN_KEEP_ROWS;
-                        if (!recut) {
-                            if (lane < tot) {
-                                DevTile t = keep_tiles[field * DEVPLAN_KEEP_ROWS + lane];
-                                DevWaveTile wt = keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane];
-                                const int64_t first = wt.out_base;                       // (kept relative to the field)
-                                const int nl = (int)wt.hb + wt.count + wt.hf;
-                                if (first >= gen_main) { t.idx0 += (int32_t)prim_index0; wt.idx0 = t.idx0; }
-                                if (wt.rel_main < nl) wt.p0 += (int32_t)prim_index0;     // the tile holds points of layer 2
-                                wt.out_base = pt_off + first;
-                                const int64_t e = stat_base + wt.tile;                   // (kept: the entry within the field)
-                                wt.tile = (int32_t)e;
-                                T.tiles[e] = t;
-                                T.wtiles[wave_base + lane] = wt;
-                                T.stat_ids[e] = (int32_t)e; T.stat_run[e] = 0;
-                                unsigned long long *slot = reinterpret_cast<unsigned long long *>(T.partial + e);
-                                for (int w = 0; w < 13; ++w) slot[w] = 0ull;
-                            }
-                        }
-                    }
-                    int64_t e_run = 1, w_run = 0;
-                    if (recut) {
-                        if (FILL && lane <= nq) { nw_j = 0; ng_j = (len_j + TILE_POINTS - 1) / TILE_POINTS; }
-                        for (int j = 0; j <= nq; ++j) {
-                            const int64_t a_s = __shfl(a_j, j), l_s = __shfl(len_j, j);
-                            int64_t t_s = (l_s + TILE_POINTS - 1) / TILE_POINTS;
-                            if (l_s > 0 && !((refused_mask >> j) & 1ull)) {
-                                const int64_t nt = cut_stretch(a_s, a_s + l_s, FILL ? 3 : 2, e_run, w_run, wave_pts, inside_cnt);
-                                if (nt >= 0) {
-                                    if (lane == j) { nw_j = nt; ng_j = 0; }
-                                    if (FILL)
-                                        for (int64_t i = lane; i < nt; i += 64) {
-                                            const int64_t e = stat_base + e_run + i;
-                                            T.stat_ids[e] = (int32_t)e; T.stat_run[e] = 0;
-                                            unsigned long long *slot = reinterpret_cast<unsigned long long *>(T.partial + e);
-                                            for (int w = 0; w < 13; ++w) slot[w] = 0ull;
-                                        }
-                                    t_s = nt; w_run += nt;
-                                } else if (FILL) fallback = true;              // (cannot happen: the counting pass cut this stretch with the same code)
-                                else refused_mask |= 1ull << j;
-                            }
-                            e_run += t_s + 1;
-                        }
-                    }
-                    if (!FILL && lane <= nq) {
-                        // (a stretch of 255 wave tiles or more: not representable in its byte -- 20 000 points without a quiet zone: the host's)
-                        if (nw_j >= 255) fallback = true;
-                        verdicts[lane] = ((refused_mask >> lane) & 1ull) ? (unsigned char)255 : (unsigned char)nw_j;
-                    }
-                    fallback = __ballot(fallback) != 0ull;
-                }
-                const int64_t t_j = lane <= nq ? nw_j + ng_j : 0;                  // entries of the stretch
-                int64_t J_j = 0;
-                if (lane < nq) J_j = (((pt_off + s_j) % TILE_POINTS) + z_j + TILE_POINTS - 1) / TILE_POINTS;
-                int64_t g_incl = lane <= nq ? ng_j : 0, w_incl = nw_j, j_incl = J_j, z_sum = z_j;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int64_t u = __shfl_up(g_incl, o), v = __shfl_up(w_incl, o), w = __shfl_up(j_incl, o), zz = __shfl_up(z_sum, o);
-                    if (lane >= o) { g_incl += u; w_incl += v; j_incl += w; z_sum += zz; }
-                }
-                if (lane > nq) ng_j = 0;
-                const int64_t g_before = g_incl - ng_j, w_before = w_incl - nw_j, j_before = j_incl - J_j;
-                n_general = __shfl(g_incl, 63); n_wave = __shfl(w_incl, 63); c_chunks = __shfl(j_incl, 63); c_chunk_pts = __shfl(z_sum, 63);
-                c_wave_pts = wave_pts; c_wave_inside = inside_cnt;
-                n_quiet = nq;
-                const int64_t E_j = 1 + g_before + w_before + lane;                  // the stretch's first entry within the field
-                if (FILL && !fallback) {
-                    const int64_t chunk_base = base_of(PC_CHUNKS);
-                    // general tiles of stretch `lane`: near-equal, at most 512 points (emit_general)
-                    if (lane <= nq && ng_j > 0) {
-                        const int64_t bs = len_j / ng_j, rem = len_j % ng_j;
-                        for (int64_t i = 0; i < ng_j; ++i) {
-                            const int64_t st = a_j + i * bs + (i < rem ? i : rem), cnt = bs + (i < rem ? 1 : 0);
-                            const int64_t e = stat_base + E_j + i;
-                            const bool l1 = per > 0 && st < gen_main;
-                            DevTile t;
-                            t.field = (int32_t)field; t.start = st; t.count = (int32_t)cnt; t.quiet = 0; t.stat_tile = (int32_t)e;
-                            t.idx0 = l1 ? (int32_t)(st / per) : 0; t.off0 = l1 ? (int32_t)(st % per) : 0;
-                            T.tiles[e] = t;
-                            T.general_ids[general_base + g_before + i] = (int32_t)e;
-                            T.stat_ids[e] = (int32_t)e; T.stat_run[e] = 0;
-                            unsigned long long *slot = reinterpret_cast<unsigned long long *>(T.partial + e);
-                            for (int w = 0; w < 13; ++w) slot[w] = 0ull;
-                        }
-                    }
-                    // the runs: tile, entry, closed-form statistics, chunks
-                    if (lane < nq) {
-                        const int64_t e = stat_base + E_j + t_j;
-                        const int64_t capq = TILE_POINTS - 2, k = (z_j + capq - 1) / capq, bs = z_j / k, rem = z_j % k;
-                        DevTile t;
-                        t.field = (int32_t)field; t.start = s_j; t.count = (int32_t)(bs + (rem > 0 ? 1 : 0)); t.quiet = k_j; t.stat_tile = 0;
-                        t.idx0 = k_j == 2 ? (int32_t)(prim_index0 + i_j) : i_j; t.off0 = o_j;
-                        T.tiles[e] = t;
-                        T.stat_ids[e] = (int32_t)e; T.stat_run[e] = z_j;
-                        double2 junc = make_double2(0.0, 0.0);
-                        if (F.P >= 2 && F.n_line >= 2 && F.n_turn >= 1) junc.x = line_start_curvature(F, cst, 1, junc.y);
-                        FieldStatView fv;
-                        fv.n_line = F.n_line; fv.n_turn = F.n_turn; fv.reverse_order = F.reverse_order; fv.line_step = F.line_step; fv.n_main = F.n_main; fv.junc = junc;
-                        DevTile tl = t;
-                        tl.idx0 = i_j;                                   // (the field's own primitives: `prims`)
-                        const DevRun run = { (int32_t)e, 0, z_j };
-                        TilePartial tp = quiet_run_partial(run, tl, fv, prims, cst);
-                        tp.n_viol = tp.n_outside = tp.n_in_obstacle = tp.n_adjusted = 0;
-                        T.partial[e] = tp;
-                        const int64_t g0r = pt_off + s_j;
-                        const int64_t c_first = (z_j < TILE_POINTS - (g0r % TILE_POINTS)) ? z_j : TILE_POINTS - (g0r % TILE_POINTS);
-                        for (int64_t j = 0; j < J_j; ++j) {
-                            const int64_t done = j == 0 ? 0 : c_first + (j - 1) * TILE_POINTS;
-                            DevTile ch = t;
-                            ch.start = s_j + done; ch.count = (int32_t)(j == 0 ? c_first : ((z_j - done < TILE_POINTS) ? z_j - done : TILE_POINTS));
-                            ch.stat_tile = (int32_t)e; ch.off0 = (int32_t)(t.off0 + done);
-                            T.chunks[chunk_base + j_before + j] = ch;
-                        }
-                    }
-                }
+            if (lds_tmpl) {
+                for (int k = lane; k < tc.nu; k += 64) L.tmpl[k] = tc.tu[k];
+                for (int k = lane; k < tc.nc; k += 64) L.tmpl[tc.nu + k] = tc.tc[k];
             }
         }
+        wprims = lds_prims ? reinterpret_cast<const DevPrim *>(L.prim_words) : prims;
+        wtu = lds_tmpl ? L.tmpl : tc.tu; wtc = lds_tmpl ? L.tmpl + tc.nu : tc.tc;
+        wave_sync();                                     // the starts (and the staged records) are in LDS
+        my_pstart = lane < prim_count ? L.pstart[lane] : INT32_MAX;       // (fields of at most 64 primitives: their starts, a lane each)
+        TSTAMP(2);
+    }
+    // the window's points [win0, win1), lane-parallel: step lengths, geofence margin, primitive of every point
+    __device__ __forceinline__ void load_window(int64_t win0, int64_t win1)
+    {
+        const int nwin = (int)(win1 - win0);
+        double cx = 0.0, cy = 0.0;               // the previous round's last point
+        for (int w_base = 0; w_base < nwin; w_base += 64) {
+            const int w = w_base + lane;
+            const bool valid = w < nwin;
+            const int64_t i = win0 + (valid ? w : nwin - 1);
+            double px = 0.0, py = 0.0;
+            int pk = 0;
+            WSTAMP(24);
+            const int64_t i_last = win0 + ((w_base + 63 < nwin) ? w_base + 63 : nwin - 1);      // (wave-uniform)
+            if (i < gen_main) {
+                int64_t idx, off;
+                if (i_last < ((int64_t)1 << 31)) { const uint32_t q32 = (uint32_t)i / (uint32_t)per; idx = q32; off = (int64_t)((uint32_t)i - q32 * (uint32_t)per); }
+                else { idx = i / per; off = i - idx * per; }
+                tiler_point_main(F, wtu, idx, off, px, py);
+            }
+            if (i_last >= gen_main) {
+                // layer 2: the primitives this round's points lie in, one after the other (wave-uniform: a handful per
+                // round) -- every lane's primitive is the last one that starts at or before its point, as a search per lane finds it
+                const int64_t i_first = win0 + w_base;
+                const int32_t rel = (int32_t)(i - n_main);
+                const int32_t rel_lo = i_first > n_main ? (int32_t)(i_first - n_main) : 0, rel_hi = (int32_t)(i_last - n_main);
+                // every lane's primitive = the last one that starts at or before its point: the first point's by one ballot
+                // over the starts (a lane each), the few that start inside the round counted in; fields of more than 64
+                // primitives search per lane
+                if (prim_count <= 64) {
+                    int k = __popcll(__ballot(my_pstart <= rel_lo)) - 1;
+                    if (k < 0) k = 0;
+                    pk = k;
+                    for (++k; k < prim_count; ++k) {
+                        const int32_t st_k = __builtin_amdgcn_readlane(my_pstart, k);
+                        if (st_k > rel_hi) break;
+                        pk += rel >= st_k ? 1 : 0;
+                    }
+                } else {
+                    int lo_k = 0, hi_k = prim_count - 1;
+                    while (lo_k < hi_k) { const int m = (lo_k + hi_k + 1) >> 1; if (L.pstart[m] <= rel) lo_k = m; else hi_k = m - 1; }
+                    pk = lo_k;
+                }
+                WSTAMP(25);
+                if (i >= gen_main) {
+                    const DevPrim q = wprims[pk];
+                    tiler_point_prim(q, wtu, wtc, (int)(i - q.start), px, py);
+                } else pk = 0;
+            }
+            WSTAMP(26);
+            double qx = __shfl_up(px, 1), qy = __shfl_up(py, 1);
+            if (lane == 0) { qx = cx; qy = cy; }
+            cx = __shfl(px, 63); cy = __shfl(py, 63);
+            if (valid) {
+                if (w >= 1) { const double dx = px - qx, dy = py - qy; L.d[w - 1] = sqrt(dx * dx + dy * dy); }
+                WSTAMP(27);
+                L.pidx[w] = (uint8_t)pk;
+                L.ins[w] = tiler_inside(F, px, py, tc.fence_margin) ? 1 : 0;
+            }
+            WSTAMP(28);
+        }
+    }
+    // the cut of [a, b); e_first / w_first: the stretch's first statistics entry / wave tile within the field.  The fill pass writes the
+    // records where they go; the counting pass keeps, indices relative to the field, a sparse field's first DEVPLAN_KEEP_TILES tiles, a dense
+    // field's first DEVPLAN_KEEP_ROWS over all its stretches (row = the tile's number within the field).  -> tiles cut, or -1: the stretch
+    // is the general kernel's.
+    __device__ __forceinline__ int64_t cut_stretch(const int64_t a, const int64_t b, const int64_t e_first, const int64_t w_first, int64_t &wave_pts, int64_t &inside_cnt)
+    {
+        stage_window();
+        // the host evaluates the points [lo - 1, hi) of the stretch at once; here a window of TW_NW points slides along with the cut
+        // (a tile starting at s touches the points [s - 43, s + 171) at most), the points are the same function values wherever the
+        // window lies
+        const int64_t lo_all = (a - WAVE_HALO_MAX - 2 > 1) ? a - WAVE_HALO_MAX - 2 : 1;
+        const int64_t hi_all = (b + WAVE_HALO_MAX + 2 < n_total) ? b + WAVE_HALO_MAX + 2 : n_total;
+        int64_t win0 = 0, win1 = -1;                     // window = path points [win0, win1)
+        auto dist = [&](int64_t i) -> double { return L.d[i - win0 - 1]; };
+        auto prim_of = [&](int64_t i) -> int { return (int)L.pidx[i - win0]; };
+        const int WAVE_LANES = 128;
+        int64_t s = a;
+        int64_t ordinal = 0;
+        bool refused_l = false;
+        while (s < b) {
+            const int64_t need_lo = (s - WAVE_HALO_MAX - 3 > lo_all - 1) ? s - WAVE_HALO_MAX - 3 : lo_all - 1;
+            const int64_t need_hi = (s + WAVE_LANES + WAVE_HALO_MAX + 3 < hi_all) ? s + WAVE_LANES + WAVE_HALO_MAX + 3 : hi_all;
+            if (!(win0 <= need_lo && need_hi <= win1)) {
+                wave_sync();
+                win0 = need_lo; win1 = (win0 + TW_NW < hi_all) ? win0 + TW_NW : hi_all;
+                load_window(win0, win1);
+                wave_sync();
+            }
+            // ---- one step of the greedy cut, wave-uniform
+            TSTAMP(3 + 4 * (int)ordinal);
+            const int Hb = tiler_back_halo(dist, s, tc.two_a, cap);
+            TSTAMP(4 + 4 * (int)ordinal);
+            if (Hb < 0) { refused_l = true; break; }
+            const int64_t cmax = (b - s < WAVE_LANES - Hb) ? b - s : WAVE_LANES - Hb;
+            const int64_t first0 = s - Hb;
+            const int pa0 = first0 + Hb + cmax - 1 >= gen_main ? prim_of(first0 > gen_main ? first0 : gen_main) : 0;
+            // the largest count whose forward halo still fits and whose points lie in at most nine primitives: candidates lane-parallel
+            int64_t c = 0;
+            int Hf = -1;
+            for (int64_t cb = 0; cb < cmax; cb += 64) {
+                const int64_t cand = cmax - cb - lane;
+                bool ok = false;
+                int hf = -1;
+                if (cand >= 1) {
+                    hf = tiler_fwd_halo(dist, s + cand - 1, n_total, tc.two_a, cap);
+                    ok = hf >= 0 && Hb + cand + hf <= WAVE_LANES;
+                    if (ok) { const int64_t last0 = s + cand - 1 + hf; if (last0 >= gen_main && prim_of(last0) - pa0 > 8) ok = false; }
+                }
+                const unsigned long long m = __ballot(ok);
+                if (m) {
+                    const int l0 = __builtin_ctzll(m);
+                    c = cmax - cb - l0;
+                    Hf = __shfl(hf, l0);
+                    break;
+                }
+            }
+            if (c < (b - s < 8 ? b - s : 8)) { refused_l = true; break; }
+            TSTAMP(5 + 4 * (int)ordinal);
+            const int64_t first = s - Hb, last = s + c - 1 + Hf;
+            // every output point inside the geofence with the margin?
+            bool all_in = true;
+            for (int64_t o0 = 0; o0 < c; o0 += 64) {
+                const int64_t o = o0 + lane;
+                const bool bad = o < c && L.ins[s + o - win0] == 0;
+                if (__ballot(bad)) all_in = false;
+            }
+            int pa = 0, pb = 0;
+            if (last >= gen_main) {
+                const int64_t fl2 = first > gen_main ? first : gen_main;
+                pa = prim_of(fl2); pb = prim_of(last);
+                if (pb - pa > 8) { refused_l = true; break; }
+                bool bad = false;
+                for (int k = pa + 1; k <= pb; ++k) if (L.pstart[k] <= L.pstart[k - 1]) bad = true;
+                if (bad) { refused_l = true; break; }
+            }
+            const bool wr_keep = !FILL && (DENSE ? w_first + ordinal < DEVPLAN_KEEP_ROWS : ordinal < DEVPLAN_KEEP_TILES);
+            if ((FILL || wr_keep) && lane == 0) {
+                WaveTileCut w;
+                w.field = field; w.entry = (FILL ? stat_base : 0) + e_first + ordinal; w.s = s; w.c = c; w.Hb = Hb; w.Hf = Hf; w.inside = all_in;
+                w.pa = pa; w.pb = pb; w.pt_base = FILL ? pt_off : 0; w.prim_base = FILL ? prim_index0 : 0;
+                if (first < gen_main) { w.idx0 = (int32_t)(first / per); w.off0 = (int32_t)(first % per); }
+                else { w.idx0 = (int32_t)(w.prim_base + prim_of(first)); w.off0 = 0; }
+                DevTile t;
+                DevWaveTile wt;
+                tiler_wave_record(w, gen_main, n_main, n_total, [&](int k) -> int64_t { return n_main + L.pstart[k]; }, t, wt);
+                if (FILL) { T.tiles[stat_base + e_first + ordinal] = t; T.wtiles[wave_base + w_first + ordinal] = wt; }
+                else { keep_tiles[field * DEVPLAN_KEEP_ROWS + w_first + ordinal] = t; keep_wtiles[field * DEVPLAN_KEEP_WROWS + w_first + ordinal] = wt; }
+            }
+            TSTAMP(6 + 4 * (int)ordinal);
+            inside_cnt += all_in ? 1 : 0;
+            wave_pts += c;
+            ++ordinal;
+            s += c;
+        }
+        return refused_l ? -1 : ordinal;
+    }
+
+    // a wave tile the counting pass kept (indices and entry relative to its field) made batch-wide; p0_rel / np: the first of the field's
+    // primitives its lanes lie in and their number (0: no lane of layer 2) -- what the field's pack copies
+    __device__ __forceinline__ void rebase_kept(DevTile &t, DevWaveTile &wt, int &p0_rel, int &np) const
+    {
+        const int64_t first = wt.out_base;
+        const int nl = (int)wt.hb + wt.count + wt.hf;
+        if (first >= gen_main) { t.idx0 += (int32_t)prim_index0; wt.idx0 = t.idx0; }
+        p0_rel = np = 0;
+        if (wt.rel_main < nl) {                                  // the tile holds points of layer 2
+            p0_rel = wt.p0;
+            np = 1;
+            for (int k = 0; k < 8; ++k) np += wt.thr[k] != 255 ? 1 : 0;
+            wt.p0 += (int32_t)prim_index0;
+        }
+        wt.out_base = pt_off + first;
+        wt.tile += (int32_t)stat_base;
+    }
+    // general tile i of the near-equal ones (at most 512 points each: emit_general) that `sp` splits the stretch from `a` on into, its entry e
+    __device__ __forceinline__ void write_general_tile(int64_t a, const TilerSplit<int64_t> &sp, int64_t i, int64_t e, int64_t list_pos) const
+    {
+        const int64_t st = a + sp.start(i);
+        const bool l1 = per > 0 && st < gen_main;
+        DevTile t;
+        t.field = (int32_t)field; t.start = st; t.count = (int32_t)sp.count(i); t.quiet = 0; t.stat_tile = (int32_t)e;
+        t.idx0 = l1 ? (int32_t)(st / per) : 0; t.off0 = l1 ? (int32_t)(st % per) : 0;
+        T.tiles[e] = t;
+        T.general_ids[list_pos] = (int32_t)e;
+    }
+
+    // ---- 4. DENSE sampling (round 5; FieldTiler::tile_field + derive_field for a field whose complete passes form a span): behind the span the
+    // last swath line and every headland straight have a quiet zone of their own (a run: one tile, one statistics entry, chunks on
+    // 512-point boundaries of the batch arrays); the stretches between the zones are cut into wave tiles (samplings coarse enough for
+    // them -- 0.18 m and up at the default accelerations -- by the window cut above, a stretch after the other; a stretch it refuses
+    // is the general kernel's, as on the host) or into general tiles.  The zones a lane each (lane 0: the last line, lane 1 + k:
+    // primitive k), the stretches a lane each, places by prefix sums over the lanes.  Not taken here (PF_FALLBACK: the host sets the
+    // batch up): fields without a span (obstacles, turns that are not closed form), more than 62 primitives, fields of field work.
+    struct DenseLane {                   // lane j: run j of the field (j < nq) and the stretch in front of it (j <= nq)
+        int64_t s, z;                    // the run: its first point, its points
+        int kind, i0, o0;                // ... its tile's quiet kind, idx0 (within the field), off0
+        int64_t a, len;                  // the stretch
+        int64_t nw, ng;                  // ... its wave tiles / general tiles
+    };
+    __device__ __forceinline__ void dense_block()
+    {
+        dense_entries = true;
+        if (fallback) return;
+        if (!(S > 0 && F.obs_count == 0 && gen_main == F.n_main)) { fallback = true; return; }
+        DenseLane d = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+        const int nq = dense_runs(d);
+        d.ng = (d.len + TILE_POINTS - 1) / TILE_POINTS;       // general tiles of the stretch -- or its wave tiles
+        int64_t wave_pts = 0, inside_cnt = 0;
+        if (wave_ok) dense_stretches(d, nq, wave_pts, inside_cnt);
+        const int64_t t_j = lane <= nq ? d.nw + d.ng : 0;                  // entries of the stretch
+        int64_t J_j = 0;
+        if (lane < nq) J_j = tiler_run_chunks(pt_off + d.s, d.z);
+        int64_t g_incl = lane <= nq ? d.ng : 0, w_incl = d.nw, j_incl = J_j, z_sum = d.z;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int64_t u = __shfl_up(g_incl, o), v = __shfl_up(w_incl, o), w = __shfl_up(j_incl, o), zz = __shfl_up(z_sum, o);
+            if (lane >= o) { g_incl += u; w_incl += v; j_incl += w; z_sum += zz; }
+        }
+        if (lane > nq) d.ng = 0;
+        const int64_t g_before = g_incl - d.ng, w_before = w_incl - d.nw, j_before = j_incl - J_j;
+        n_general = __shfl(g_incl, 63); n_wave = __shfl(w_incl, 63); c_chunks = __shfl(j_incl, 63); c_chunk_pts = __shfl(z_sum, 63);
+        c_wave_pts = wave_pts; c_wave_inside = inside_cnt;
+        n_quiet = nq;
+        const int64_t E_j = 1 + g_before + w_before + lane;                  // the stretch's first entry within the field
+        if (FILL && !fallback) {
+            // general tiles of stretch `lane`
+            if (lane <= nq && d.ng > 0) {
+                const TilerSplit<int64_t> sp(d.len, d.ng);
+                for (int64_t i = 0; i < d.ng; ++i) {
+                    const int64_t e = stat_base + E_j + i;
+                    write_general_tile(d.a, sp, i, e, general_base + g_before + i);
+                    init_entry(T, e);
+                }
+            }
+            if (lane < nq) dense_run(d, stat_base + E_j + t_j, J_j, base_of(PC_CHUNKS) + j_before);
+        }
+    }
+    // the quiet zones, a lane each, gathered in path order -> their number
+    __device__ __forceinline__ int dense_runs(DenseLane &d)
+    {
+        int64_t q_s = 0, q_n = 0;
+        int q_kind = 0, q_i0 = 0, q_o0 = 0;
+        bool valid = false;
+        if (lane == 0) {
+            const int64_t Z = (int64_t)F.n_line - need1;          // (no margin at its start behind a span; need1 points before the seam to layer 2)
+            if (Z >= 64) { valid = true; q_s = S; q_n = Z; q_kind = 1; q_i0 = (int)(P - 1); q_o0 = 0; }
+        } else if (lane - 1 < prim_count) {
+            const DevPrim &pr = prims[lane - 1];
+            if (pr.kind == PRIM_LINSPACE) {
+                const double ms = pr.v_nom / 3.6;
+                const int64_t need2 = tiler_need_for(ms * ms, sqrt(pr.a[4] * pr.a[4] + pr.a[5] * pr.a[5]), tc.two_a);
+                const int64_t Z = (int64_t)pr.n - 2 * need2;
+                if (need2 >= 0 && Z >= 64) { valid = true; q_s = pr.start + need2; q_n = Z; q_kind = 2; q_i0 = lane - 1; q_o0 = (int)need2; }
+            }
+        }
+        const unsigned long long vm = __ballot(valid);
+        const int nq = __popcll(vm), rk = __popcll(vm & ((1ull << lane) - 1ull));
+        // the runs in path order: through the window's bytes into the lanes
+        int64_t *qs = reinterpret_cast<int64_t *>(L.d), *qn = qs + 64;
+        int32_t *qk = reinterpret_cast<int32_t *>(qn + 64), *qi = qk + 64, *qo = qi + 64;
+        static_assert(sizeof(L.d) >= 64 * (8 + 8 + 4 + 4 + 4), "the runs of a dense field fit the window's bytes");
+        wave_sync();
+        if (valid) { qs[rk] = q_s; qn[rk] = q_n; qk[rk] = q_kind; qi[rk] = q_i0; qo[rk] = q_o0; }
+        wave_sync();
+        if (lane < nq) { d.s = qs[lane]; d.z = qn[lane]; d.kind = qk[lane]; d.i0 = qi[lane]; d.o0 = qo[lane]; }
+        // stretch j = [end of run j - 1 (the span's for j = 0), start of run j (the path's end for j = nq))
+        if (lane <= nq) {
+            d.a = lane == 0 ? S : qs[lane - 1] + qn[lane - 1];
+            const int64_t b_j = lane == nq ? n_total : d.s;
+            d.len = b_j > d.a ? b_j - d.a : 0;
+        }
+        wave_sync();                                      // (the window cut writes these bytes)
+        return nq;
+    }
+    // the stretches that take wave tiles, one after the other, in path order.  The counting pass keeps the field's first DEVPLAN_KEEP_ROWS wave
+    // tiles (indices and entries relative to the field) and, in the row behind them, a byte per stretch: its wave tiles, or 255 -- the general
+    // kernel's, as the host decides.  The fill pass copies the kept tiles (a lane each); a field with more cuts again, only the
+    // stretches that take wave tiles, whose records it can therefore write as it goes
+    __device__ __forceinline__ void dense_stretches(DenseLane &d, int nq, int64_t &wave_pts, int64_t &inside_cnt)
+    {
+        unsigned char *verdicts = reinterpret_cast<unsigned char *>(keep_wtiles + field * DEVPLAN_KEEP_WROWS + DEVPLAN_KEEP_ROWS);
+        unsigned long long refused_mask = 0ull;
+        bool recut = true;
+        if (FILL) {
+            // what the counting pass found: wave tiles per stretch (a lane each).  A field whose wave tiles were all kept is not cut again
+            const int vb = lane <= nq ? (int)verdicts[lane] : 0;
+            refused_mask = __ballot(vb == 255);
+            if (lane <= nq && vb != 255 && d.len > 0) { d.nw = vb; d.ng = 0; }
+            int64_t tot = d.nw;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+            recut = tot > DEVPLAN_KEEP_ROWS;
+            if (!recut && lane < tot) {
+                DevTile t = keep_tiles[field * DEVPLAN_KEEP_ROWS + lane];
+                DevWaveTile wt = keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane];
+                const int64_t e = stat_base + wt.tile;                   // (kept: the entry within the field)
+                int p0_rel, np;
+                rebase_kept(t, wt, p0_rel, np);
+                T.tiles[e] = t;
+                T.wtiles[wave_base + lane] = wt;
+                init_entry(T, e);
+            }
+        }
+        int64_t e_run = 1, w_run = 0;
+        if (recut) {
+            if (FILL && lane <= nq) { d.nw = 0; d.ng = (d.len + TILE_POINTS - 1) / TILE_POINTS; }
+            for (int j = 0; j <= nq; ++j) {
+                const int64_t a_s = __shfl(d.a, j), l_s = __shfl(d.len, j);
+                int64_t t_s = (l_s + TILE_POINTS - 1) / TILE_POINTS;
+                if (l_s > 0 && !((refused_mask >> j) & 1ull)) {
+                    const int64_t nt = cut_stretch(a_s, a_s + l_s, e_run, w_run, wave_pts, inside_cnt);
+                    if (nt >= 0) {
+                        if (lane == j) { d.nw = nt; d.ng = 0; }
+                        if (FILL)
+                            for (int64_t i = lane; i < nt; i += 64) init_entry(T, stat_base + e_run + i);
+                        t_s = nt; w_run += nt;
+                    } else if (FILL) fallback = true;              // (cannot happen: the counting pass cut this stretch with the same code)
+                    else refused_mask |= 1ull << j;
+                }
+                e_run += t_s + 1;
+            }
+        }
+        if (!FILL && lane <= nq) {
+            // (a stretch of 255 wave tiles or more: not representable in its byte -- 20 000 points without a quiet zone: the host's)
+            if (d.nw >= 255) fallback = true;
+            verdicts[lane] = ((refused_mask >> lane) & 1ull) ? (unsigned char)255 : (unsigned char)d.nw;
+        }
+        fallback = __ballot(fallback) != 0ull;
+    }
+    // fill pass, this lane's run: tile, entry e, closed-form statistics, its J chunks from chunk_pos on
+    __device__ __forceinline__ void dense_run(const DenseLane &d, int64_t e, int64_t J, int64_t chunk_pos) const
+    {
+        const int64_t capq = TILE_POINTS - 2, k = (d.z + capq - 1) / capq;
+        DevTile t;
+        t.field = (int32_t)field; t.start = d.s; t.count = (int32_t)TilerSplit<int64_t>(d.z, k).count(0); t.quiet = d.kind; t.stat_tile = 0;
+        t.idx0 = d.kind == 2 ? (int32_t)(prim_index0 + d.i0) : d.i0; t.off0 = d.o0;
+        T.tiles[e] = t;
+        T.stat_ids[e] = (int32_t)e; T.stat_run[e] = d.z;
+        DevTile tl = t;
+        tl.idx0 = d.i0;                                   // (the field's own primitives: `prims`)
+        T.partial[e] = run_consts(F, field_junction(F, cst), e, d.z, tl, prims, cst);
+        for (int64_t j = 0; j < J; ++j) {
+            int64_t done, cnt;
+            tiler_run_chunk(pt_off + d.s, d.z, j, done, cnt);
+            DevTile ch = t;
+            ch.start = d.s + done; ch.count = (int32_t)cnt;
+            ch.stat_tile = (int32_t)e; ch.off0 = (int32_t)(t.off0 + done);
+            T.chunks[chunk_pos + j] = ch;
+        }
+    }
+
+    // ---- 5. sparse sampling: the one general stretch [a, n_total) behind the span -- the fill pass copies the tiles the counting pass kept;
+    // else the closed-form cut (counting pass), the window cut, or general tiles
+    __device__ __forceinline__ void sparse_stretch()
+    {
         const int64_t a = pos, b = n_total, G = b - a;
-        bool use_wave = wave_ok && G > 0 && !fallback && !dense;
+        bool use_wave = wave_ok && G > 0 && !fallback;
+        auto closed = [&]() -> bool { return tc.closed_cut != 0 && a == cut_span_points(F, tc.cut) && cut_applies(F, tc.cut, a); };
         // the count pass has already decided whether the stretch takes wave tiles: the fill pass reads its verdict
         if (FILL && use_wave) {
             const int64_t cw = counts[(int64_t)PC_WAVE * n + field];
             if (cw == 0) use_wave = false;
-            else if (cw <= DEVPLAN_KEEP_TILES || (tc.closed_cut != 0 && a == cut_span_points(F, tc.cut) && cut_applies(F, tc.cut, a))) {       // (a closed-form cut: every tile was kept)
+            else if (cw <= DEVPLAN_KEEP_TILES || closed()) {       // (a closed-form cut: every tile was kept)
                 // the counting pass kept this field's wave tiles: copy them, indices made batch-wide
                 use_wave = false;
                 n_wave = cw;
                 if (lane < cw) {
                     DevTile t = keep_tiles[field * DEVPLAN_KEEP_ROWS + lane];
                     DevWaveTile wt = keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane];
-                    const int64_t first = wt.out_base;                       // (kept relative to the field)
-                    const int nl = (int)wt.hb + wt.count + wt.hf;
-                    if (first >= gen_main) { t.idx0 += (int32_t)prim_index0; wt.idx0 = t.idx0; }
-                    if (wt.rel_main < nl) {                                  // the tile holds points of layer 2
-                        my_p0_rel = wt.p0;
-                        my_np = 1;
-                        for (int k = 0; k < 8; ++k) my_np += wt.thr[k] != 255 ? 1 : 0;
-                        wt.p0 += (int32_t)prim_index0;
-                    }
-                    wt.out_base = pt_off + first;
-                    wt.tile += (int32_t)stat_base;
-                    T.tiles[stat_base + (span_k > 0 ? 1 : 0) + lane] = t;
+                    rebase_kept(t, wt, my_p0_rel, my_np);
+                    T.tiles[stat_base + first_entry() + lane] = t;
                     T.wtiles[wave_base + lane] = wt;
                     my_wt = wt;
                 }
             }
         }
-        // ---- round 5: the general stretch of a field with a closed-form span is cut IN CLOSED FORM (fcpp_cutfn.h, the function the host
-        // tiler runs): the step lengths the halos are sized from are the primitives' own steps and the distances between their end points
-        // -- the primitives a lane each, then the tiles of a candidate cut a lane each -- no point of the stretch is evaluated
-        if (!DENSE && !FILL && use_wave && tc.closed_cut != 0 && a == cut_span_points(F, tc.cut) && cut_applies(F, tc.cut, a)) {
-            use_wave = false;
-            const int64_t n_main = F.n_main;
-            TSTAMP(10);
-            // the templates and their chord tables through LDS (a halo walk reads a chord per step: from device memory every step was a round
-            // trip of its own), requested together with the primitives' records
-            CutConsts lc = tc.cut;
-            const int nt_all = tc.cut.nu + tc.cut.nc;
-            const bool cut_staged = nt_all <= TW_LDS_TMPL;
-            Pt2 tp = { 0.0, 0.0 };
-            if (cut_staged && lane < nt_all) tp = lane < tc.cut.nu ? tc.cut.tu[lane] : tc.cut.tc[lane - tc.cut.nu];
-            // 1. the primitives' records
-            bool p_ok = true;
-            double ex = 0.0, ey = 0.0, fx = 0.0, fy = 0.0;
-            DevPrim q;
-            memset(&q, 0, sizeof q);
-            if (lane < prim_count) q = prims[lane];
-            TSTAMP(15);
-            if (cut_staged) {
-                if (lane < nt_all) L.cut_tmpl()[lane] = tp;
-                lc.tu = L.cut_tmpl(); lc.tc = L.cut_tmpl() + tc.cut.nu;
-                wave_sync();
-            }
-            TSTAMP(16);
-            if (lane < prim_count) {
-                cut_prim_end(q, lc, false, fx, fy);
-                TSTAMP(17);
-                ex = fx; ey = fy;
-                if (q.n > 1) cut_prim_end(q, lc, true, ex, ey);
-            }
-            TSTAMP(11);
-            double px = __shfl_up(ex, 1), py = __shfl_up(ey, 1);          // the point before a primitive's first: its predecessor's last ...
-            if (lane == 0) cut_main_end(F, lc, px, py);                    // ... or the last point of layer 1
-            if (lane < prim_count) {
-                L.cut_rows()[lane] = cut_prim_rec(q, F, lc, px, py, fx, fy, ex, ey, p_ok);
-                L.pstart[lane] = (int32_t)(q.start - n_main);
-            }
-            const bool prims_ok = __ballot(lane < prim_count && !p_ok) == 0ull;
-            wave_sync();
-            TSTAMP(12);
-            // 2. the cut: candidate cuts of T near-equal tiles, the tiles of one a lane each; the decisions of cut_field, taken on the first
-            // tile (in path order) that does not fit
-            struct CutView { const CutPrim *p; __device__ const CutPrim &operator()(int k) const { return p[k]; } };
-            const CutView pv{ L.cut_rows() };
-            const double cap = tiler_halo_cap(tc.u_cap);
-            const int32_t G32 = (int32_t)G;
-            const int32_t cut_start = lane < prim_count ? (int32_t)(q.start - n_main) : INT32_MAX;      // this lane's primitive's first point
-            int nt = 0, Hb = 0, Hf = 0;
-            int64_t s = 0, c = 0;
-            bool in = false;
-            if (prims_ok)
-                for (int32_t T = cut_first_T(G32); cut_T_possible(G32, T); ++T) {
-                    int code = 0;
-                    if (lane < T) { s = a + cut_tile_start(G32, T, lane); c = cut_tile_count(G32, T, lane); }
-                    // the segments of the points s - 1 and s + c - 1 of every tile: the primitives' starts a lane each, a ballot per tile and point
-                    int kj = 0, ke = 0;
-                    int32_t rj = 0, re = 0;
-                    for (int t = 0; t < T; ++t) {
-                        const int64_t j_t = __shfl(s, t) - 1, e_t = __shfl(s + c - 1, t);
-                        const int32_t relj = (int32_t)(j_t - n_main), rele = (int32_t)(e_t - n_main);
-                        const int a_t = __popcll(__ballot(cut_start <= relj)) - 1, b_t = __popcll(__ballot(cut_start <= rele)) - 1;
-                        if (lane == t) { kj = a_t; ke = b_t; }
-                    }
-                    if (lane < T) {
-                        const int64_t Sl = ((int64_t)F.P - 1) * per, j = s - 1, e = s + c - 1;
-                        if (j < Sl) { kj = -2; rj = (int32_t)(j - (Sl - F.n_turn)); } else if (j < n_main) { kj = -1; rj = (int32_t)(j - Sl); } else rj = (int32_t)(j - n_main) - L.cut_rows()[kj < 0 ? 0 : kj].start_rel;
-                        if (e < Sl) { ke = -2; re = (int32_t)(e - (Sl - F.n_turn)); } else if (e < n_main) { ke = -1; re = (int32_t)(e - Sl); } else re = (int32_t)(e - n_main) - L.cut_rows()[ke < 0 ? 0 : ke].start_rel;
-                        code = cut_tile_eval_at(F, lc, pv, prim_count, cap, s, c, kj, rj, ke, re, Hb, Hf, in);
-                    }
-                    const unsigned long long bad = __ballot(code != 0);
-                    if (bad == 0ull) { nt = (int)T; break; }
-                    if (__shfl(code, __builtin_ctzll(bad)) == 1) break;           // a halo too long: the general kernel's
-                }
-            TSTAMP(13);
-            if (nt != 0) {
-                // the last primitive that starts at or before point i >= n_main: the starts a lane each, one ballot per tile and question
-                const int32_t my_start = lane < prim_count ? (int32_t)(q.start - n_main) : INT32_MAX;
-                const int64_t first_l = s - Hb, last_l = s + c - 1 + Hf;
-                int pa_l = 0, pb_l = 0, pf_l = 0;
-                for (int t = 0; t < nt; ++t) {
-                    const int64_t f_t = __shfl(first_l, t), l_t = __shfl(last_l, t);
-                    const int32_t rf = (int32_t)((f_t > gen_main ? f_t : gen_main) - n_main), rl = (int32_t)(l_t - n_main), r1 = (int32_t)(f_t - n_main);
-                    const int a_t = __popcll(__ballot(my_start <= rf)) - 1, b_t = __popcll(__ballot(my_start <= rl)) - 1, f1_t = __popcll(__ballot(my_start <= r1)) - 1;
-                    if (lane == t) { pa_l = a_t < 0 ? 0 : a_t; pb_l = b_t < 0 ? 0 : b_t; pf_l = f1_t < 0 ? 0 : f1_t; }
-                }
-                const int64_t wave_pts = G;
-                const int64_t inside_cnt = __popcll(__ballot(lane < nt && in));
-                if (lane < nt) {
-                    const int64_t first = s - Hb, last = s + c - 1 + Hf;
-                    const int64_t p_base = FILL ? prim_index0 : 0;
-                    DevTile t;
-                    t.field = (int32_t)field; t.count = (int32_t)c; t.start = s; t.quiet = 5; t.stat_tile = Hb | (Hf << 16);
-                    if (first < gen_main) { const uint32_t q32 = (uint32_t)first / (uint32_t)per; t.idx0 = (int32_t)q32; t.off0 = (int32_t)((uint32_t)first - q32 * (uint32_t)per); }   // (first < 2^31: cut_applies)
-                    else { t.idx0 = (int32_t)(p_base + pf_l); t.off0 = 0; }
-                    DevWaveTile wt;
-                    memset(&wt, 0, sizeof wt);
-                    wt.out_base = (FILL ? pt_off : 0) + first; wt.field = (int32_t)field;
-                    wt.tile = (int32_t)((FILL ? stat_base : 0) + (span_k > 0 ? 1 : 0) + lane);
-                    wt.count = (uint8_t)c; wt.hb = (uint8_t)Hb; wt.hf = (uint8_t)Hf; wt.inside = in ? 1 : 0;
-                    wt.rel_main = clampi(gen_main - first); wt.rel_seam = clampi(n_main - first); wt.rel_last = clampi(n_total - 1 - first);
-                    wt.rel_zero = clampi(-first);
-                    wt.idx0 = t.idx0; wt.off0 = t.off0;
-                    for (int k = 0; k < 8; ++k) wt.thr[k] = 255;
-                    if (last >= gen_main) {
-                        const int pa = pa_l, pb = pb_l;
-                        wt.p0 = (int32_t)(p_base + pa);
-                        wt.r0 = (int32_t)(first - (n_main + L.pstart[pa]));
-                        for (int k = pa + 1; k <= pb; ++k) wt.thr[k - pa - 1] = (uint8_t)(n_main + L.pstart[k] - first);
-                    }
-                    if (FILL) { T.tiles[stat_base + (span_k > 0 ? 1 : 0) + lane] = t; T.wtiles[wave_base + lane] = wt; }
-                    else { keep_tiles[field * DEVPLAN_KEEP_ROWS + lane] = t; keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane] = wt; }
-                }
-                n_wave = nt; c_wave_pts = wave_pts; c_wave_inside = inside_cnt;
-                TSTAMP(14);
-            }
-        }
+        if (!FILL && use_wave && closed()) { use_wave = false; closed_cut(a, G); }
         if (use_wave) {
             int64_t wave_pts = 0, inside_cnt = 0;
-            const int64_t nt = cut_stretch(a, b, FILL ? 1 : 0, span_k > 0 ? 1 : 0, 0, wave_pts, inside_cnt);
+            const int64_t nt = cut_stretch(a, b, first_entry(), 0, wave_pts, inside_cnt);
             if (nt >= 0) { n_wave = nt; c_wave_pts = wave_pts; c_wave_inside = inside_cnt; }
             TSTAMP(36);
         }
-        if (G > 0 && n_wave == 0 && !fallback && !dense) {
-            // general tiles of at most 512 points, near-equal
+        if (G > 0 && n_wave == 0 && !fallback) {
             n_general = (G + TILE_POINTS - 1) / TILE_POINTS;
             if (FILL) {
-                const int64_t bs = G / n_general, rem = G % n_general;
-                const bool in1 = per > 0;
-                for (int64_t j = lane; j < n_general; j += 64) {
-                    const int64_t st = a + j * bs + (j < rem ? j : rem), cnt = bs + (j < rem ? 1 : 0);
-                    const bool l1 = in1 && st < gen_main;
-                    DevTile t;
-                    t.field = (int32_t)field; t.start = st; t.count = (int32_t)cnt; t.quiet = 0;
-                    t.stat_tile = (int32_t)(stat_base + (span_k > 0 ? 1 : 0) + j);
-                    t.idx0 = l1 ? (int32_t)(st / per) : 0; t.off0 = l1 ? (int32_t)(st % per) : 0;
-                    T.tiles[stat_base + (span_k > 0 ? 1 : 0) + j] = t;
-                    T.general_ids[general_base + j] = (int32_t)(stat_base + (span_k > 0 ? 1 : 0) + j);
-                }
+                const TilerSplit<int64_t> sp(G, n_general);
+                for (int64_t j = lane; j < n_general; j += 64) write_general_tile(a, sp, j, stat_base + first_entry() + j, general_base + j);
             }
         }
+    }
+    // round 5: the general stretch of a field with a closed-form span is cut IN CLOSED FORM (fcpp_cutfn.h, the function the host
+    // tiler runs): the step lengths the halos are sized from are the primitives' own steps and the distances between their end points
+    // -- the primitives a lane each, then the tiles of a candidate cut a lane each -- no point of the stretch is evaluated.  Counting
+    // pass only: every tile is kept.
+    __device__ __forceinline__ void closed_cut(const int64_t a, const int64_t G)
+    {
+        TSTAMP(10);
+        // the templates and their chord tables through LDS (a halo walk reads a chord per step: from device memory every step was a round
+        // trip of its own), requested together with the primitives' records
+        CutConsts lc = tc.cut;
+        const int nt_all = tc.cut.nu + tc.cut.nc;
+        const bool cut_staged = nt_all <= TW_LDS_TMPL;
+        Pt2 tp = { 0.0, 0.0 };
+        if (cut_staged && lane < nt_all) tp = lane < tc.cut.nu ? tc.cut.tu[lane] : tc.cut.tc[lane - tc.cut.nu];
+        // 1. the primitives' records
+        bool p_ok = true;
+        double ex = 0.0, ey = 0.0, fx = 0.0, fy = 0.0;
+        DevPrim q;
+        memset(&q, 0, sizeof q);
+        if (lane < prim_count) q = prims[lane];
+        TSTAMP(15);
+        if (cut_staged) {
+            if (lane < nt_all) L.cut_tmpl()[lane] = tp;
+            lc.tu = L.cut_tmpl(); lc.tc = L.cut_tmpl() + tc.cut.nu;
+            wave_sync();
+        }
+        TSTAMP(16);
+        if (lane < prim_count) {
+            cut_prim_end(q, lc, false, fx, fy);
+            TSTAMP(17);
+            ex = fx; ey = fy;
+            if (q.n > 1) cut_prim_end(q, lc, true, ex, ey);
+        }
+        TSTAMP(11);
+        double px = __shfl_up(ex, 1), py = __shfl_up(ey, 1);          // the point before a primitive's first: its predecessor's last ...
+        if (lane == 0) cut_main_end(F, lc, px, py);                    // ... or the last point of layer 1
+        if (lane < prim_count) {
+            L.cut_rows()[lane] = cut_prim_rec(q, F, lc, px, py, fx, fy, ex, ey, p_ok);
+            L.pstart[lane] = (int32_t)(q.start - n_main);
+        }
+        const bool prims_ok = __ballot(lane < prim_count && !p_ok) == 0ull;
+        wave_sync();
+        TSTAMP(12);
+        // 2. the cut: candidate cuts of T near-equal tiles, the tiles of one a lane each; the decisions of cut_field, taken on the first
+        // tile (in path order) that does not fit
+        struct CutView { const CutPrim *p; __device__ const CutPrim &operator()(int k) const { return p[k]; } };
+        const CutView pv{ L.cut_rows() };
+        const int32_t G32 = (int32_t)G;
+        const int32_t cut_start = lane < prim_count ? (int32_t)(q.start - n_main) : INT32_MAX;      // this lane's primitive's first point
+        int nt = 0, Hb = 0, Hf = 0;
+        int64_t s = 0, c = 0;
+        bool in = false;
+        if (prims_ok)
+            for (int32_t T = cut_first_T(G32); cut_T_possible(G32, T); ++T) {
+                int code = 0;
+                if (lane < T) { const TilerSplit<int32_t> sp(G32, T); s = a + sp.start(lane); c = sp.count(lane); }
+                // the segments of the points s - 1 and s + c - 1 of every tile: the primitives' starts a lane each, a ballot per tile and point
+                int kj = 0, ke = 0;
+                int32_t rj = 0, re = 0;
+                for (int t = 0; t < T; ++t) {
+                    const int64_t j_t = __shfl(s, t) - 1, e_t = __shfl(s + c - 1, t);
+                    const int32_t relj = (int32_t)(j_t - n_main), rele = (int32_t)(e_t - n_main);
+                    const int a_t = __popcll(__ballot(cut_start <= relj)) - 1, b_t = __popcll(__ballot(cut_start <= rele)) - 1;
+                    if (lane == t) { kj = a_t; ke = b_t; }
+                }
+                if (lane < T) {
+                    const int64_t Sl = ((int64_t)F.P - 1) * per, j = s - 1, e = s + c - 1;
+                    if (j < Sl) { kj = -2; rj = (int32_t)(j - (Sl - F.n_turn)); } else if (j < n_main) { kj = -1; rj = (int32_t)(j - Sl); } else rj = (int32_t)(j - n_main) - L.cut_rows()[kj < 0 ? 0 : kj].start_rel;
+                    if (e < Sl) { ke = -2; re = (int32_t)(e - (Sl - F.n_turn)); } else if (e < n_main) { ke = -1; re = (int32_t)(e - Sl); } else re = (int32_t)(e - n_main) - L.cut_rows()[ke < 0 ? 0 : ke].start_rel;
+                    code = cut_tile_eval_at(F, lc, pv, prim_count, cap, s, c, kj, rj, ke, re, Hb, Hf, in);
+                }
+                const unsigned long long bad = __ballot(code != 0);
+                if (bad == 0ull) { nt = (int)T; break; }
+                if (__shfl(code, __builtin_ctzll(bad)) == 1) break;           // a halo too long: the general kernel's
+            }
+        TSTAMP(13);
+        if (nt == 0) return;
+        // the last primitive that starts at or before point i >= n_main: the starts a lane each, one ballot per tile and question
+        const int64_t first = s - Hb, last_l = s + c - 1 + Hf;
+        int pa_l = 0, pb_l = 0, pf_l = 0;
+        for (int t = 0; t < nt; ++t) {
+            const int64_t f_t = __shfl(first, t), l_t = __shfl(last_l, t);
+            const int32_t rf = (int32_t)((f_t > gen_main ? f_t : gen_main) - n_main), rl = (int32_t)(l_t - n_main), r1 = (int32_t)(f_t - n_main);
+            const int a_t = __popcll(__ballot(cut_start <= rf)) - 1, b_t = __popcll(__ballot(cut_start <= rl)) - 1, f1_t = __popcll(__ballot(cut_start <= r1)) - 1;
+            if (lane == t) { pa_l = a_t < 0 ? 0 : a_t; pb_l = b_t < 0 ? 0 : b_t; pf_l = f1_t < 0 ? 0 : f1_t; }
+        }
+        const int64_t inside_cnt = __popcll(__ballot(lane < nt && in));
+        if (lane < nt) {
+            WaveTileCut w;
+            w.field = field; w.entry = first_entry() + lane; w.s = s; w.c = c; w.Hb = Hb; w.Hf = Hf; w.inside = in;
+            w.pa = pa_l; w.pb = pb_l; w.pt_base = 0; w.prim_base = 0;
+            if (first < gen_main) { const uint32_t q32 = (uint32_t)first / (uint32_t)per; w.idx0 = (int32_t)q32; w.off0 = (int32_t)((uint32_t)first - q32 * (uint32_t)per); }   // (first < 2^31: cut_applies)
+            else { w.idx0 = (int32_t)pf_l; w.off0 = 0; }
+            DevTile t;
+            DevWaveTile wt;
+            tiler_wave_record(w, gen_main, n_main, n_total, [&](int k) -> int64_t { return n_main + L.pstart[k]; }, t, wt);
+            keep_tiles[field * DEVPLAN_KEEP_ROWS + lane] = t; keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane] = wt;
+        }
+        n_wave = nt; c_wave_pts = G; c_wave_inside = inside_cnt;
+        TSTAMP(14);
+    }
+
+    // ---- 6. which kernel plans and reduces the field, and the span's tiles and chunks
+    __device__ __forceinline__ void field_work_and_span()
+    {
         // a field whose general points are all in a few wave tiles is planned AND reduced by one workgroup (k_plan_sparse_fields), which
         // then writes the field's span too (fuse_spans): its chunks are not in k_plan_quiet's list
-        {
-            const int64_t ne0 = (span_k > 0 ? 1 : 0) + n_wave + n_general + n_quiet;
-            const int fw_max = tc.field_work_tiles < FIELD_WORK_TILES ? tc.field_work_tiles : FIELD_WORK_TILES;
-            is_work = n_general == 0 && n_wave >= 1 && n_wave <= fw_max && ne0 <= FIELD_WORK_ENTRIES;
-            // (a dense field of field work -- few wave tiles, nothing general -- gets a pack and a fused span on the host: not built here)
-            if (dense && is_work) { is_work = false; fallback = true; }
-        }
-        // ---- the span's tiles (near-equal, at most 510 points: the closed-form kernel stores aligned pairs) and its chunks on 512-point
+        const int64_t ne0 = first_entry() + n_wave + n_general + n_quiet;
+        const int fw_max = tc.field_work_tiles < FIELD_WORK_TILES ? tc.field_work_tiles : FIELD_WORK_TILES;
+        is_work = n_general == 0 && n_wave >= 1 && n_wave <= fw_max && ne0 <= FIELD_WORK_ENTRIES;
+        // (a dense field of field work -- few wave tiles, nothing general -- gets a pack and a fused span on the host: not built here)
+        if (DENSE && is_work) { is_work = false; fallback = true; }
+        // the span's tiles (near-equal, at most 510 points: the closed-form kernel stores aligned pairs) and its chunks on 512-point
         // boundaries of the batch arrays
         if (span_k > 0) {
             c_runs = 1 + n_quiet; c_span_pts = S;
@@ -1413,17 +1434,15 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
             fused_span = c_work_span_pts;
             if (FILL && fused_span > 0) c_span = 0;          // (no chunk records for a fused span)
             if (FILL) {
-                const int64_t bs = S / span_k, rem = S % span_k;
                 if (lane == 0) {          // (the device's tile table keeps one tile per statistics entry: of the span's run, the first)
                     DevTile t;
-                    t.field = (int32_t)field; t.start = 0; t.count = (int32_t)(bs + (rem > 0 ? 1 : 0)); t.quiet = 4; t.stat_tile = 0;
+                    t.field = (int32_t)field; t.start = 0; t.count = (int32_t)TilerSplit<int64_t>(S, span_k).count(0); t.quiet = 4; t.stat_tile = 0;
                     t.idx0 = 0; t.off0 = 0;
                     T.tiles[stat_base] = t;
                 }
-                const int64_t c_first = (S < TILE_POINTS - (g0 % TILE_POINTS)) ? S : TILE_POINTS - (g0 % TILE_POINTS);
                 for (int64_t j = lane; j < c_span; j += 64) {
-                    const int64_t done = j == 0 ? 0 : c_first + (j - 1) * TILE_POINTS;
-                    const int64_t cnt = j == 0 ? c_first : ((S - done < TILE_POINTS) ? S - done : TILE_POINTS);
+                    int64_t done, cnt;
+                    tiler_run_chunk(g0, S, j, done, cnt);
                     DevTile ch;
                     ch.field = (int32_t)field; ch.start = done; ch.count = (int32_t)cnt; ch.quiet = 4; ch.stat_tile = (int32_t)stat_base;
                     ch.idx0 = (int32_t)(done / per); ch.off0 = (int32_t)(done % per);
@@ -1431,83 +1450,85 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
                 }
             }
         }
-        c_tiles = (span_k > 0 ? 1 : 0) + n_wave + n_general + n_quiet;      // (the tile table holds one tile per statistics entry: of a span / a run, the first)
+        c_tiles = first_entry() + n_wave + n_general + n_quiet;      // (the tile table holds one tile per statistics entry: of a span / a run, the first)
         c_wave = n_wave; c_general = n_general;
-        c_stat = (span_k > 0 ? 1 : 0) + n_wave + n_general + n_quiet;
-        if (dense) { c_chunks_out = c_chunks; c_chunk_pts_out = c_chunk_pts; dense_entries = true; }
+        c_stat = first_entry() + n_wave + n_general + n_quiet;
     }
-    // ---- which kernel reduces the field: its own workgroup (k_plan_sparse_fields) or a class of k_reduce_stats
-    const int64_t ne = c_stat;
-    if (is_work) { c_work = 1; c_work_wave_pts = c_wave_pts; }
-    else { c_open = n_wave; cls = tiler_reduce_class(ne, tc.reduce_wg_max); }
-    if (fallback && lane == 0) atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_FALLBACK), (unsigned long long)tc.gen);
-    if (!FILL && tc.speculative && lane == 0 && (c_tiles > 1 + DEVPLAN_KEEP_TILES || c_wave > DEVPLAN_KEEP_TILES || c_general > DEVPLAN_KEEP_TILES || c_span > SPEC_SPAN_CHUNKS))
-        atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_OVER_CAPACITY), (unsigned long long)tc.gen);
-
-    TSTAMP(37);
-    FSTAMP(2);
-    if (!FILL) {
-        if (lane == 0) {
-            int64_t *c = counts + field;
-            c[(int64_t)PC_TILES * n] = c_tiles; c[(int64_t)PC_WAVE * n] = c_wave; c[(int64_t)PC_GENERAL * n] = c_general; c[(int64_t)PC_STAT * n] = c_stat;
-            c[(int64_t)PC_WORK * n] = c_work; c[(int64_t)PC_OPEN * n] = c_open;
-            if (!no_bases) { c[(int64_t)PC_SPAN * n] = c_span; c[(int64_t)PC_WORK_SPAN_PTS * n] = c_work_span_pts; c[(int64_t)PC_SPAN_F * n] = c_span_f; c[(int64_t)PC_UNFUSABLE * n] = c_unfusable; }
-            c[(int64_t)PC_CLS0 * n] = (!is_work && cls == 0) ? 1 : 0; c[(int64_t)PC_CLS1 * n] = (!is_work && cls == 1) ? 1 : 0;
-            c[(int64_t)PC_CLS2 * n] = (!is_work && cls == 2) ? 1 : 0; c[(int64_t)PC_CLS3 * n] = (!is_work && cls == 3) ? 1 : 0;
-            c[(int64_t)PC_RUNS * n] = c_runs; c[(int64_t)PC_SPAN_PTS * n] = c_span_pts; c[(int64_t)PC_WAVE_PTS * n] = c_wave_pts;
-            c[(int64_t)PC_WORK_WAVE_PTS * n] = c_work_wave_pts; c[(int64_t)PC_WAVE_INSIDE * n] = c_wave_inside;
-            c[(int64_t)PC_CHUNKS * n] = c_chunks_out; c[(int64_t)PC_CHUNK_PTS * n] = c_chunk_pts_out;
-        }
-        TSTAMP(38);
-        return;
+    // which kernel reduces the field: its own workgroup (k_plan_sparse_fields) or a class of k_reduce_stats; the flags
+    __device__ __forceinline__ void reduce_class_and_flags()
+    {
+        if (is_work) { c_work = 1; c_work_wave_pts = c_wave_pts; }
+        else { c_open = n_wave; cls = tiler_reduce_class(c_stat, tc.reduce_wg_max); }
+        if (fallback && lane == 0) atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_FALLBACK), (unsigned long long)tc.gen);
+        if (!FILL && tc.speculative && lane == 0 && (c_tiles > 1 + DEVPLAN_KEEP_TILES || c_wave > DEVPLAN_KEEP_TILES || c_general > DEVPLAN_KEEP_TILES || c_span > SPEC_SPAN_CHUNKS))
+            atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_OVER_CAPACITY), (unsigned long long)tc.gen);
     }
 
-    // ---- fill pass: the field's descriptor and primitives at their final places, the statistics entries, the work lists
-    const bool lds_pack = STAGE && prim_count <= TW_LDS_PRIMS;        // the pack's copies of the primitives come out of LDS
+    // ---- 7. counting pass: the field's row of the count columns
+    __device__ __forceinline__ void write_counts() const
+    {
+        if (lane != 0) return;
+        int64_t *c = counts + field;
+        c[(int64_t)PC_TILES * n] = c_tiles; c[(int64_t)PC_WAVE * n] = c_wave; c[(int64_t)PC_GENERAL * n] = c_general; c[(int64_t)PC_STAT * n] = c_stat;
+        c[(int64_t)PC_WORK * n] = c_work; c[(int64_t)PC_OPEN * n] = c_open;
+        if (!no_bases) { c[(int64_t)PC_SPAN * n] = c_span; c[(int64_t)PC_WORK_SPAN_PTS * n] = c_work_span_pts; c[(int64_t)PC_SPAN_F * n] = c_span_f; c[(int64_t)PC_UNFUSABLE * n] = c_unfusable; }
+        c[(int64_t)PC_CLS0 * n] = (!is_work && cls == 0) ? 1 : 0; c[(int64_t)PC_CLS1 * n] = (!is_work && cls == 1) ? 1 : 0;
+        c[(int64_t)PC_CLS2 * n] = (!is_work && cls == 2) ? 1 : 0; c[(int64_t)PC_CLS3 * n] = (!is_work && cls == 3) ? 1 : 0;
+        c[(int64_t)PC_RUNS * n] = c_runs; c[(int64_t)PC_SPAN_PTS * n] = c_span_pts; c[(int64_t)PC_WAVE_PTS * n] = c_wave_pts;
+        c[(int64_t)PC_WORK_WAVE_PTS * n] = c_work_wave_pts; c[(int64_t)PC_WAVE_INSIDE * n] = c_wave_inside;
+        c[(int64_t)PC_CHUNKS * n] = c_chunks; c[(int64_t)PC_CHUNK_PTS * n] = c_chunk_pts;
+    }
+
+    // ---- 8. fill pass.  The field's descriptor and primitives at their final places (the primitives into LDS too, for the pack)
+    __device__ __forceinline__ bool lds_pack() const { return STAGE && prim_count <= TW_LDS_PRIMS; }        // the pack's copies of the primitives come out of LDS
+    __device__ __forceinline__ void fill_descriptor()
     {
         unsigned long long *dst = reinterpret_cast<unsigned long long *>(&T.fields[field]);
         if (lane < NFW) dst[lane] = fw;
         const unsigned long long *ps = reinterpret_cast<const unsigned long long *>(prims);
-        unsigned long long *pd = reinterpret_cast<unsigned long long *>(T.prims + prim_base);
-        if (lds_pack) wave_sync();                           // (a field cut again above has read its primitives from there)
+        unsigned long long *pd = reinterpret_cast<unsigned long long *>(T.prims + prim_index0);
+        if (lds_pack()) wave_sync();                           // (a field cut again above has read its primitives from there)
 #pragma unroll
         for (int j = 0; j < PF_ROUNDS; ++j) {
             const int k = lane + 64 * j;
-            if (k < nwords_p) { pd[k] = pw[j]; if (lds_pack) L.prim_words[k] = pw[j]; }
+            if (k < nwords_p) { pd[k] = pw[j]; if (lds_pack()) L.prim_words[k] = pw[j]; }
         }
         for (int k = lane + 64 * PF_ROUNDS; k < nwords_p; k += 64) pd[k] = ps[k];
-        if (lds_pack) wave_sync();
+        if (lds_pack()) wave_sync();
     }
-    FSTAMP(3);
-    // entries in path order: the span's run, then the wave tiles / general tiles
-    if (span_k > 0 && lane == 0) { T.stat_ids[stat_base] = (int32_t)stat_base; T.stat_run[stat_base] = S; }
-    if (!dense_entries) {
-        const int64_t e0 = stat_base + (span_k > 0 ? 1 : 0), nt = n_wave + n_general;
-        for (int64_t j = lane; j < nt; j += 64) { T.stat_ids[e0 + j] = (int32_t)(e0 + j); T.stat_run[e0 + j] = 0; }
-    }
-    if (lane == 0) {
-        T.stat_first[field] = stat_base;
-        if (field == n - 1) T.stat_first[n] = stat_base + c_stat;
-        if (is_work) {
-            DevFieldWork w;
-            memset(&w, 0, sizeof w);
-            w.field = (int32_t)field; w.n_tiles = (int32_t)n_wave; w.w_first = (int32_t)wave_base; w.e_first = (int32_t)stat_base; w.n_entries = (int32_t)ne;
-            w.fused_span = (int32_t)fused_span;
-            T.field_work[base_of(PC_WORK)] = w;              // (every such field has at most four tiles: class 0 is the only class in use)
-            DevFieldPack &P = T.field_packs[base_of(PC_WORK)];
-            P.work = w;
-            P.span_points = fused_span;
-            for (int k = 0; k < 6; ++k) P._pad0[k] = 0;
-            P._pad1 = 0.0;
-            for (int k = 0; k < 4; ++k) P._pad2[k] = 0.0;
-        } else {
-            int64_t cls_first = 0;
-            for (int k = 0; k < cls; ++k) cls_first += totals[PC_CLS0 + k];
-            T.red_paths[cls_first + base_of(PC_CLS0 + cls)] = (int32_t)field;
+    // the statistics entries in path order (the span's run, then the wave tiles / general tiles) and the work lists
+    __device__ __forceinline__ void fill_entries_and_lists()
+    {
+        if (span_k > 0 && lane == 0) { T.stat_ids[stat_base] = (int32_t)stat_base; T.stat_run[stat_base] = S; }
+        if (!dense_entries) {
+            const int64_t e0 = stat_base + first_entry(), nt = n_wave + n_general;
+            for (int64_t j = lane; j < nt; j += 64) { T.stat_ids[e0 + j] = (int32_t)(e0 + j); T.stat_run[e0 + j] = 0; }
+        }
+        if (lane == 0) {
+            T.stat_first[field] = stat_base;
+            if (field == n - 1) T.stat_first[n] = stat_base + c_stat;
+            if (is_work) {
+                DevFieldWork w;
+                memset(&w, 0, sizeof w);
+                w.field = (int32_t)field; w.n_tiles = (int32_t)n_wave; w.w_first = (int32_t)wave_base; w.e_first = (int32_t)stat_base; w.n_entries = (int32_t)c_stat;
+                w.fused_span = (int32_t)fused_span;
+                T.field_work[base_of(PC_WORK)] = w;              // (every such field has at most four tiles: class 0 is the only class in use)
+                DevFieldPack &P = T.field_packs[base_of(PC_WORK)];
+                P.work = w;
+                P.span_points = fused_span;
+                for (int k = 0; k < 6; ++k) P._pad0[k] = 0;
+                P._pad1 = 0.0;
+                for (int k = 0; k < 4; ++k) P._pad2[k] = 0.0;
+            } else {
+                int64_t cls_first = 0;
+                for (int k = 0; k < cls; ++k) cls_first += totals[PC_CLS0 + k];
+                T.red_paths[cls_first + base_of(PC_CLS0 + cls)] = (int32_t)field;
+            }
         }
     }
+    // connector segments (MLP:1313-1355): approach rows [0, n), departure rows [n, 2n) -- out of the lanes' words of fcpp_field_info
+    __device__ __forceinline__ void fill_connectors()
     {
-        // connector segments (MLP:1313-1355): approach rows [0, n), departure rows [n, 2n) -- out of the lanes' words of fcpp_field_info
         constexpr int W_AF = (int)(offsetof(fcpp_field_info, approach_from) / 8), W_DF = (int)(offsetof(fcpp_field_info, departure_from) / 8);
         constexpr int W_ST = (int)(offsetof(fcpp_field_info, status) / 8), W_SK = (int)(offsetof(fcpp_field_info, start_kept) / 8), W_EK = (int)(offsetof(fcpp_field_info, end_kept) / 8);
         static_assert(offsetof(fcpp_field_info, approach_to) == offsetof(fcpp_field_info, approach_from) + 16 &&
@@ -1523,13 +1544,16 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
         else if (lane < 8) sg[(n + field) * 4 + (lane - 4)] = cw;
         if (lane == 0) { T.seg_mask[field] = okf && start_kept; T.seg_mask[n + field] = okf && end_kept; }
     }
-    FSTAMP(4);
-    if (!is_work) {
-        const int64_t ob = base_of(PC_OPEN);
-        for (int64_t j = lane; j < n_wave; j += 64) T.open_wave_ids[ob + j] = (int32_t)(wave_base + j);
-    } else {
-        // the field's pack: its tiles (lane t holds tile t: at most four, all kept by the counting pass), its descriptor as written to
-        // the field table, and per tile a copy of its primitives
+    // the open wave tiles' list -- or, for a field of field work, its pack: its tiles (lane t holds tile t: at most four, all kept by the
+    // counting pass), its descriptor as written to the field table, and per tile a copy of its primitives
+    __device__ __forceinline__ void fill_pack()
+    {
+        if (!is_work) {
+            const int64_t ob = base_of(PC_OPEN);
+            for (int64_t j = lane; j < n_wave; j += 64) T.open_wave_ids[ob + j] = (int32_t)(wave_base + j);
+            return;
+        }
+        const bool from_lds = lds_pack();
         DevFieldPack &P = T.field_packs[base_of(PC_WORK)];
         if (lane < FIELD_WORK_TILES) P.tile[lane] = my_wt;               // (lanes without a tile hold zeros)
         {
@@ -1541,30 +1565,25 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
         unsigned long long *pdst = reinterpret_cast<unsigned long long *>(&P.prims[0][0]);
         for (int t = 0; t < FIELD_WORK_TILES; ++t) {
             const int p0 = __shfl(my_p0_rel, t), np = __shfl(my_np, t);
-            for (int k = lane; k < TW; k += 64)
-                pdst[t * TW + k] = (k / PW < np) ? (lds_pack ? L.prim_words[p0 * PW + k] : psrc[(int64_t)p0 * PW + k]) : 0ull;
+            // (a loop per source: one loop over a pointer chosen per lane read LDS through flat loads)
+            if (from_lds) for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? L.prim_words[p0 * PW + k] : 0ull;
+            else for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? psrc[(int64_t)p0 * PW + k] : 0ull;
         }
     }
-    FSTAMP(5);
-    // ---- what the host path computes with three more launches after its copy (k_field_junctions, k_run_consts, k_work_totals), per field:
+    // what the host path computes with three more launches after its copy (k_field_junctions, k_run_consts, k_work_totals), per field:
     // the junction after a U-turn, the closed-form statistics of the field's span in its slot (zeros in the slots of its tiles), and for a
-    // field of field work the sum of its runs' statistics
+    // field of field work the sum of its runs' statistics; the field's fcpp_field_info
+    __device__ __forceinline__ void fill_junction_and_slots()
     {
-        double2 junc = make_double2(0.0, 0.0);
-        if (n_total > 0 && F.P >= 2 && F.n_line >= 2 && F.n_turn >= 1) junc.x = line_start_curvature(F, cst, 1, junc.y);
+        const double2 junc = n_total > 0 ? field_junction(F, cst) : make_double2(0.0, 0.0);
         TilePartial tp;
         memset(&tp, 0, sizeof tp);
         if (span_k > 0) {
             DevTile tl;
             tl.field = (int32_t)field; tl.start = 0; tl.count = 0; tl.quiet = 4; tl.stat_tile = 0; tl.idx0 = 0; tl.off0 = 0;
-            FieldStatView fv;
-            fv.n_line = F.n_line; fv.n_turn = F.n_turn; fv.reverse_order = F.reverse_order; fv.line_step = F.line_step; fv.n_main = F.n_main; fv.junc = junc;
-            const DevRun run = { (int32_t)stat_base, 0, S };
-            tp = quiet_run_partial(run, tl, fv, T.prims, cst);
-            tp.n_viol = tp.n_outside = tp.n_in_obstacle = tp.n_adjusted = 0;
+            tp = run_consts(F, junc, stat_base, S, tl, T.prims, cst);
         }
         FSTAMP(6);
-        static_assert(sizeof(TilePartial) == 13 * 8, "thirteen 8-byte components");
         // slots: entry 0 = the span's (when there is one), the others zero
         unsigned long long *slots = reinterpret_cast<unsigned long long *>(T.partial + stat_base);
         const unsigned long long *tpw = reinterpret_cast<const unsigned long long *>(&tp);
@@ -1592,10 +1611,49 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
             }
         }
         // the field's fcpp_field_info stays with the batch (fcpp_batch_info copies it back when asked)
-        static_assert(sizeof(fcpp_field_info) % 8 == 0, "copied as 8-byte words");
         unsigned long long *id = reinterpret_cast<unsigned long long *>(&T.info[field]);
         if (lane < NIW) id[lane] = iw;
     }
+};
+
+template <bool FILL, bool STAGE, bool DENSE>
+__device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
+                                                 fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts,
+                                                 const int64_t *__restrict__ bases, int64_t *__restrict__ totals,
+                                                 DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, const DevPlanTables &T)
+{
+    __shared__ TileWaveLds<STAGE> lds_all[TW_WAVES];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int64_t field = (int64_t)blockIdx.x * TW_WAVES + wave;
+    if (field >= n) return;
+    TSTAMP(0);
+    FSTAMP(0);
+    TilePass<FILL, STAGE, DENSE> p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, bases, totals, keep_tiles, keep_wtiles, T, lds_all[wave], field, lane };
+    if (!p.header(info)) return;
+    TSTAMP(1);
+    FSTAMP(1);
+    if (p.n_total > 0) {
+        p.span_decision();
+        if (DENSE) p.dense_block();
+        else p.sparse_stretch();
+        p.field_work_and_span();
+    }
+    p.reduce_class_and_flags();
+    TSTAMP(37);
+    FSTAMP(2);
+    if (!FILL) {
+        p.write_counts();
+        TSTAMP(38);
+        return;
+    }
+    p.fill_descriptor();
+    FSTAMP(3);
+    p.fill_entries_and_lists();
+    p.fill_connectors();
+    FSTAMP(4);
+    p.fill_pack();
+    FSTAMP(5);
+    p.fill_junction_and_slots();
     FSTAMP(7);
 }
 
@@ -1643,12 +1701,11 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
                                n_polys, check_obstacles, 0, tc.gen);
         else
             hipLaunchKernelGGL(k_plan_fields16, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               n_polys, check_obstacles, tc.gen, (int64_t)0, n);
+                               n_polys, check_obstacles, tc.gen);
     };
     // (more fields than one round of wavefronts takes -- 4 per SIMD x 1024 SIMDs with the primitives staged in LDS: they are not staged, five
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
     auto count = [&]() {
-        tcc.f0 = 0; tcc.f1 = n;
         const unsigned grid = (unsigned)((n + TW_WAVES - 1) / TW_WAVES);
         if (tc.dense)
             hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,

@@ -370,6 +370,8 @@ struct FieldStatView {
     double line_step;
     int64_t n_main;
     double2 junc;
+    // (the device tiler: the field's record where the planner left it, the junction just computed)
+    __device__ __forceinline__ void set(const DevField &q, double2 j) { n_line = q.n_line; n_turn = q.n_turn; reverse_order = q.reverse_order; line_step = q.line_step; n_main = q.n_main; junc = j; }
     __device__ __forceinline__ void load(const DevField *__restrict__ fields, const DevConst &cst, int64_t field)
     {
         const DevField &q = fields[field];

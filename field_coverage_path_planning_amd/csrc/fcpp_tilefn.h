@@ -1,10 +1,12 @@
 // fcpp_tilefn.h -- the pieces of the tiler that the host tiler (fcpp_tiler.cpp) and the device tiler (fcpp_devplan.hip) must compute
 // bit for bit alike: a path point as the tiler sees it (only distances between consecutive points and the margin to the geofence are
-// taken from it), the halo walks of a wave tile, the margins of a straight.  One source, compiled for both sides with
+// taken from it), the halo walks of a wave tile, the margins of a straight, and the records both write (a wave tile's, the near-equal split
+// of a stretch, the chunks of a run).  One source, compiled for both sides with
 // -ffp-contract=off, so the device-built tables equal the host-built ones byte for byte (tests/test_gpu_devplan.py).
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "fcpp_geom.h"
 #include "fcpp_internal.h"
@@ -133,5 +135,61 @@ FCPP_HD double tiler_halo_cap(double u_cap) { return u_cap * (1.0 + 1e-9) + 1e-1
 
 // reduction class of a path by its statistics entries: 8 lanes, a wavefront, a workgroup, 64 workgroups + join
 FCPP_HD int tiler_reduce_class(int64_t ne, int64_t reduce_wg_max) { return ne <= 64 ? 0 : (ne <= 256 ? 1 : (ne <= reduce_wg_max ? 2 : 3)); }
+
+// ---- the records both tilers write -----------------------------------------------------------------------------------------------------
+// tile i of k near-equal tiles over `len` points (the first len % k one point longer): general tiles of at most TILE_POINTS points, the tiles
+// of a quiet run, the candidate cuts of fcpp_cutfn.h (those in 32 bits)
+// (the division once per split: callers that walk the tiles make the split in front of their loop)
+template <class I>
+struct TilerSplit {
+    I base, rem;
+    FCPP_HD TilerSplit(I len, I k) : base(len / k), rem(len - base * k) {}
+    FCPP_HD I start(I i) const { return i * base + (i < rem ? i : rem); }
+    FCPP_HD I count(I i) const { return base + (i < rem ? 1 : 0); }
+};
+
+// A run of Z points whose first is point g0 of the batch arrays is stored in chunks that end on TILE_POINTS boundaries of those arrays:
+// how many, and chunk j as (points of the run before it, its points)
+FCPP_HD int64_t tiler_run_chunks(int64_t g0, int64_t Z) { return ((g0 % TILE_POINTS) + Z + TILE_POINTS - 1) / TILE_POINTS; }
+FCPP_HD void tiler_run_chunk(int64_t g0, int64_t Z, int64_t j, int64_t &done, int64_t &count)
+{
+    const int64_t c_first = (Z < TILE_POINTS - (g0 % TILE_POINTS)) ? Z : TILE_POINTS - (g0 % TILE_POINTS);
+    done = j == 0 ? 0 : c_first + (j - 1) * TILE_POINTS;
+    count = j == 0 ? c_first : ((Z - done < TILE_POINTS) ? Z - done : TILE_POINTS);
+}
+
+FCPP_HD int32_t tiler_clampi(int64_t v) { return (int32_t)(v < -2 ? -2 : (v > ((int64_t)1 << 30) ? ((int64_t)1 << 30) : v)); }
+
+// One wave tile as a cut describes it: outputs [s, s + c) of the field's path behind Hb halo lanes and before Hf.
+struct WaveTileCut {
+    int64_t field, entry;         // the field (batch-wide) and the tile's statistics entry
+    int64_t s, c;
+    int Hb, Hf;
+    bool inside;                  // every output point inside the geofence with the tiler's margin
+    int32_t idx0, off0;           // lane 0's point s - Hb: (pass, offset in the pass) in layer 1, else (its primitive, 0) -- the caller's division
+    int pa, pb;                   // primitives (within the field) of the tile's first layer-2 lane and of its last lane; read when the tile has such lanes
+    int64_t pt_base, prim_base;   // the field's first point / primitive in the batch's tables; 0: the record stays relative to the field
+};
+// ... as the records the kernels read (fcpp_sparse.hip): the layer-1 decode of lane 0, and where the (at most 8) further primitives start
+// among the lanes.  start_of(k): first point of the field's primitive k.
+template <class StartOf>
+FCPP_HD void tiler_wave_record(const WaveTileCut &w, int64_t gen_main, int64_t n_main, int64_t n_total, const StartOf &start_of, DevTile &t, DevWaveTile &wt)
+{
+    const int64_t first = w.s - w.Hb, last = w.s + w.c - 1 + w.Hf;
+    t.field = (int32_t)w.field; t.count = (int32_t)w.c; t.start = w.s; t.quiet = 5; t.stat_tile = w.Hb | (w.Hf << 16);
+    t.idx0 = w.idx0; t.off0 = w.off0;
+    memset(&wt, 0, sizeof wt);
+    wt.out_base = w.pt_base + first; wt.field = (int32_t)w.field; wt.tile = (int32_t)w.entry;
+    wt.count = (uint8_t)w.c; wt.hb = (uint8_t)w.Hb; wt.hf = (uint8_t)w.Hf; wt.inside = w.inside ? 1 : 0;
+    wt.rel_main = tiler_clampi(gen_main - first); wt.rel_seam = tiler_clampi(n_main - first); wt.rel_last = tiler_clampi(n_total - 1 - first);
+    wt.rel_zero = tiler_clampi(-first);
+    wt.idx0 = t.idx0; wt.off0 = t.off0;
+    for (int k = 0; k < 8; ++k) wt.thr[k] = 255;
+    if (last >= gen_main) {
+        wt.p0 = (int32_t)(w.prim_base + w.pa);
+        wt.r0 = (int32_t)(first - start_of(w.pa));
+        for (int k = w.pa + 1; k <= w.pb; ++k) wt.thr[k - w.pa - 1] = (uint8_t)(start_of(k) - first);
+    }
+}
 
 }  // namespace fcpp

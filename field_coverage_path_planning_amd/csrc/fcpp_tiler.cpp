@@ -87,6 +87,26 @@ struct FieldTiler {
         }
     }
 
+    // the records of one wave tile as a cut found it (tiler_wave_record, fcpp_tilefn.h: the device tiler writes them with the same function)
+    // (pa, pb: the primitives of the tile's first layer-2 lane and of its last lane, read when it has such lanes)
+    void push_wave_tile(int64_t s, int64_t c, int Hb, int Hf, bool inside, int pa, int pb)
+    {
+        const DevField &F = *f;
+        const int64_t first = s - Hb;
+        WaveTileCut w;
+        w.field = p; w.entry = (int64_t)out.tiles.size(); w.s = s; w.c = c; w.Hb = Hb; w.Hf = Hf; w.inside = inside;
+        if (first < F.gen_main) { w.idx0 = (int32_t)(first / per); w.off0 = (int32_t)(first % per); }
+        else { w.idx0 = prim_index0 + prim_of(first); w.off0 = 0; }
+        w.pa = pa; w.pb = pb;
+        w.pt_base = F.pt_off; w.prim_base = prim_index0;
+        DevTile t;
+        DevWaveTile wt;
+        tiler_wave_record(w, F.gen_main, F.n_main, F.n_total, [&](int k) { return prims[k].start; }, t, wt);
+        out.wave_inside += wt.inside;
+        out.wtiles.push_back(wt);
+        out.tiles.push_back(t);
+    }
+
     // Wave tiles of the sparse kernel for the general stretch [a, b): [ Hb halo | count outputs | Hf halo ] <= WAVE_LANES lanes.
     // The halos are sized from the path's own step lengths (see fcpp_sparse.hip): backwards from the point before the first output
     // (whose final speed the segment metrics need) until the couplings 2a|dp| add up to u_cap, a skipped step or the path's start,
@@ -142,37 +162,16 @@ struct FieldTiler {
                 break;
             }
             if (c < std::min<int64_t>(8, b - s)) return refuse(Hf < 0 ? 1 : 2);
-            const int64_t first = s - Hb, last = s + c - 1 + Hf;
-            DevTile t;
-            t.field = (int32_t)p; t.count = (int32_t)c; t.start = s; t.quiet = 5; t.stat_tile = Hb | (Hf << 16);
-            if (first < F.gen_main) { t.idx0 = (int32_t)(first / per); t.off0 = (int32_t)(first % per); }
-            else { t.idx0 = prim_index0 + prim_of(first); t.off0 = 0; }
-            // the self-contained record: layer-1 decode of lane 0, and where the (at most 8) further primitives start among the lanes
-            DevWaveTile wt;
-            memset(&wt, 0, sizeof wt);
-            auto clampi = [](int64_t v) { return (int32_t)std::max<int64_t>(-2, std::min<int64_t>(v, (int64_t)1 << 30)); };
-            wt.out_base = F.pt_off + first; wt.field = (int32_t)p; wt.tile = (int32_t)out.tiles.size();
-            wt.count = (uint8_t)c; wt.hb = (uint8_t)Hb; wt.hf = (uint8_t)Hf; wt.inside = all_inside(s, c) ? 1 : 0;
-            wt.rel_main = clampi(F.gen_main - first); wt.rel_seam = clampi(F.n_main - first); wt.rel_last = clampi(n - 1 - first);
-            wt.rel_zero = clampi(-first);
-            wt.idx0 = t.idx0; wt.off0 = t.off0;
-            for (int k = 0; k < 8; ++k) wt.thr[k] = 255;
+            // (at most nine primitives, their starts strictly ascending: the kernel counts the primitives that start at or before a point as bits
+            // of a mask; an empty primitive -- two starts on one point, no plan has one -- would be counted once)
+            const int64_t last = s + c - 1 + Hf;
+            int pa = 0, pb = 0;
             if (last >= F.gen_main) {
-                const int64_t fl2 = std::max<int64_t>(first, F.gen_main);      // first primitive-generated point of the tile
-                const int pa = prim_of(fl2), pb = prim_of(last);
+                pa = prim_of(std::max<int64_t>(s - Hb, F.gen_main)); pb = prim_of(last);
                 if (pb - pa > 8) return refuse(3);
-                wt.p0 = prim_index0 + pa;
-                wt.r0 = (int32_t)(first - prims[pa].start);
-                for (int k = pa + 1; k <= pb; ++k) {
-                    // (strictly ascending: the kernel counts the primitives that start at or before a point as bits of a mask; an empty
-                    // primitive -- two starts on one point, no plan has one -- would be counted once)
-                    if (prims[k].start <= prims[k - 1].start) return refuse(3);
-                    wt.thr[k - pa - 1] = (uint8_t)(prims[k].start - first);
-                }
+                for (int k = pa + 1; k <= pb; ++k) if (prims[k].start <= prims[k - 1].start) return refuse(3);
             }
-            out.wave_inside += wt.inside;
-            out.wtiles.push_back(wt);
-            out.tiles.push_back(t);
+            push_wave_tile(s, c, Hb, Hf, all_inside(s, c), pa, pb);
             s += c;
         }
         return true;
@@ -185,7 +184,6 @@ struct FieldTiler {
     bool wave_tiles_closed(int64_t a)
     {
         const DevField &F = *f;
-        const int64_t n = F.n_total;
         cprims.resize((size_t)prim_count);
         bool ok = true;
         double lx, ly;
@@ -197,32 +195,9 @@ struct FieldTiler {
         if (fc.status != CUT_OK) { ++out.wave_fail[0]; return false; }
         for (int k = 0; k < fc.n_tiles; ++k) {
             const CutTile &ct = fc.t[k];
-            const int64_t s = ct.s, c = ct.c;
-            const int Hb = ct.hb, Hf = ct.hf;
-            const int64_t first = s - Hb, last = s + c - 1 + Hf;
-            DevTile t;
-            t.field = (int32_t)p; t.count = (int32_t)c; t.start = s; t.quiet = 5; t.stat_tile = Hb | (Hf << 16);
-            if (first < F.gen_main) { t.idx0 = (int32_t)(first / per); t.off0 = (int32_t)(first % per); }
-            else { t.idx0 = prim_index0 + prim_of(first); t.off0 = 0; }
-            DevWaveTile wt;
-            memset(&wt, 0, sizeof wt);
-            auto clampi = [](int64_t v) { return (int32_t)std::max<int64_t>(-2, std::min<int64_t>(v, (int64_t)1 << 30)); };
-            wt.out_base = F.pt_off + first; wt.field = (int32_t)p; wt.tile = (int32_t)out.tiles.size();
-            wt.count = (uint8_t)c; wt.hb = (uint8_t)Hb; wt.hf = (uint8_t)Hf; wt.inside = ct.inside;
-            wt.rel_main = clampi(F.gen_main - first); wt.rel_seam = clampi(F.n_main - first); wt.rel_last = clampi(n - 1 - first);
-            wt.rel_zero = clampi(-first);
-            wt.idx0 = t.idx0; wt.off0 = t.off0;
-            for (int q = 0; q < 8; ++q) wt.thr[q] = 255;
-            if (last >= F.gen_main) {
-                const int64_t fl2 = std::max<int64_t>(first, F.gen_main);
-                const int pa = prim_of(fl2), pb = prim_of(last);
-                wt.p0 = prim_index0 + pa;
-                wt.r0 = (int32_t)(first - prims[pa].start);
-                for (int q = pa + 1; q <= pb; ++q) wt.thr[q - pa - 1] = (uint8_t)(prims[q].start - first);
-            }
-            out.wave_inside += wt.inside;
-            out.wtiles.push_back(wt);
-            out.tiles.push_back(t);
+            const int64_t first = (int64_t)ct.s - ct.hb, last = (int64_t)ct.s + ct.c - 1 + ct.hf;
+            const bool l2 = last >= F.gen_main;
+            push_wave_tile(ct.s, ct.c, ct.hb, ct.hf, ct.inside != 0, l2 ? prim_of(std::max<int64_t>(first, F.gen_main)) : 0, l2 ? prim_of(last) : 0);
         }
         return true;
     }
@@ -242,12 +217,12 @@ struct FieldTiler {
         const bool closed = tc.closed_cut && b == f->n_total && a == cut_span_points(*f, tc.cut) && cut_applies(*f, tc.cut, a);
         if (closed) { if (wave_ok && wave_tiles_closed(a)) return; }
         else if (wave_ok && wave_tiles(a, b)) return;
-        const int64_t k = (len + TILE_POINTS - 1) / TILE_POINTS, base = len / k, rem = len % k;
+        const int64_t k = (len + TILE_POINTS - 1) / TILE_POINTS;
+        const TilerSplit<int64_t> sp(len, k);
         for (int64_t i = 0; i < k; ++i) {
-            const int64_t c = base + (i < rem ? 1 : 0);
-            const bool in1 = per > 0 && a < f->gen_main;      // layer-1 decode of the tile start for the general kernel
-            emit(a, c, 0, in1 ? a / per : 0, in1 ? a % per : 0);
-            a += c;
+            const int64_t st = a + sp.start(i);
+            const bool in1 = per > 0 && st < f->gen_main;      // layer-1 decode of the tile start for the general kernel
+            emit(st, sp.count(i), 0, in1 ? st / per : 0, in1 ? st % per : 0);
         }
     }
     // near-equal quiet tiles of at most TILE_POINTS - 2 points (the kernel stores aligned PAIRS; a tile that starts on an
@@ -257,8 +232,8 @@ struct FieldTiler {
     // At dense sampling the other tiles were most of the tiler's time.)
     void emit_quiet(int64_t zs, int64_t Z, int kind, int64_t i0, int64_t o0)
     {
-        const int64_t cap = TILE_POINTS - 2, k = (Z + cap - 1) / cap, base = Z / k, rem = Z % k;
-        emit(zs, base + (rem > 0 ? 1 : 0), kind, i0, o0);
+        const int64_t cap = TILE_POINTS - 2, k = (Z + cap - 1) / cap;
+        emit(zs, TilerSplit<int64_t>(Z, k).count(0), kind, i0, o0);
         out.tiles.back().stat_tile = (int32_t)Z;
     }
     int64_t need_for(double c_nom, double step_len) const { return tiler_need_for(c_nom, step_len, tc.two_a); }
@@ -415,7 +390,7 @@ struct FieldTiler {
             // the layer-1 span of a field of field work is written by the field's own workgroup (k_plan_sparse_fields): no chunks
             const int64_t g_grp = F.pt_off + a.start;
             if (is_work && a.quiet == 4 && a.start == 0) {
-                const bool fusable = ((g_grp % TILE_POINTS) + total + TILE_POINTS - 1) / TILE_POINTS <= FUSED_SPAN_CHUNKS;
+                const bool fusable = tiler_run_chunks(g_grp, total) <= FUSED_SPAN_CHUNKS;
                 if (!fusable) ++out.unfusable_work;
                 else if (tc.fuse_spans) { fused_span = total; out.work_span_points += total; r = r1; continue; }
             }
@@ -425,11 +400,9 @@ struct FieldTiler {
                 // ... without walking the chunks: chunk j of the group begins c_first + (j - 1) 512 points into it, and the only chunks that go
                 // to the span list are those of a layer-1 span and those with a run boundary strictly inside -- found from the run
                 // boundaries, O(runs) instead of O(points / 512) (a 5000 x 2000 m field at 0.05 m: 800 runs, 123 000 chunks)
-                const int64_t room0 = TILE_POINTS - (g_grp % TILE_POINTS), c_first = std::min(total, room0);
-                const int64_t J = total <= c_first ? 1 : 1 + (total - c_first + TILE_POINTS - 1) / TILE_POINTS;
-                auto chunk_of = [&](int64_t d) { return d < c_first ? (int64_t)0 : 1 + (d - c_first) / TILE_POINTS; };
-                auto chunk_start = [&](int64_t j) { return j == 0 ? (int64_t)0 : c_first + (j - 1) * TILE_POINTS; };
-                auto chunk_count = [&](int64_t j) { return j == 0 ? c_first : std::min<int64_t>(TILE_POINTS, total - chunk_start(j)); };
+                const int64_t J = tiler_run_chunks(g_grp, total);
+                // (the chunk that holds point d < total of the group: the 512-point block of the batch arrays it lies in, counted from the group's first)
+                auto chunk_of = [&](int64_t d) { return (g_grp % TILE_POINTS + d) / TILE_POINTS; };
                 const bool all_span = a.quiet == 4;
                 int64_t spans = 0, span_pts = 0, next_j0 = 0, last_span = -1;
                 auto segments_upto = [&](int64_t j_incl) {       // the segments that begin at or before chunk j_incl: `spans` span chunks lie before them
@@ -449,9 +422,11 @@ struct FieldTiler {
                     for (size_t k = r; k + 1 < r1; ++k) {
                         B += rv[k].count;                              // where run k + 1 begins
                         const int64_t jb = chunk_of(B);
-                        if (B == chunk_start(jb) || jb == last_span) continue;
+                        int64_t jb_start, jb_count;
+                        tiler_run_chunk(g_grp, total, jb, jb_start, jb_count);
+                        if (B == jb_start || jb == last_span) continue;
                         segments_upto(jb);
-                        ++spans; span_pts += chunk_count(jb); last_span = jb;
+                        ++spans; span_pts += jb_count; last_span = jb;
                     }
                 }
                 segments_upto(J - 1);
