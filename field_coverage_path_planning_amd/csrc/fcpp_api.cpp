@@ -19,6 +19,8 @@
 #include "fcpp_ga.h"
 #include "fcpp_device.h"
 #include "fcpp_devplan.h"
+#include "fcpp_dubins.h"
+#include "fcpp_dubinsfn.h"
 #include "fcpp_internal.h"
 #include "fcpp_parallel.h"
 #include "fcpp_tiler.h"
@@ -1907,6 +1909,78 @@ int fcpp_best_connections(fcpp_ctx *c, int64_t n_pairs, const int64_t *fo, const
     return FCPP_OK;
 }
 
+// ---- Dubins connectors (fcpp_dubins.hip; the mathematics: fcpp_dubinsfn.h) --------------------------------------------------------
+int fcpp_dubins_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
+                      const double *th, double radius, int32_t *word, double *seg, double *len)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_dubins_solve(c->stream, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
+    return FCPP_OK;
+}
+
+int fcpp_dubins_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
+                       const double *ty, const double *th, double radius, double *D, int8_t *word)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n_from < 0 || n_to < 0 || n_from > DUB_MAX_POSES || n_to > DUB_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
+    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_dubins_matrix(c->stream, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
+    return FCPP_OK;
+}
+
+int fcpp_dubins_counts(fcpp_ctx *c, int64_t n, const double *len, double spacing, int64_t *out_offsets, int64_t *out_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    if (!out_offsets || (n > 0 && !len)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DevBuf<int64_t> err;
+    HIPCHK(err.alloc(1));
+    LAUNCHCHK(launch_dubins_counts(st, n, len, spacing, out_offsets, err.p));
+    int64_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, err.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    if (out_offsets_host) HIPCHK(hipMemcpyAsync(out_offsets_host, out_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad) return fail(FCPP_ESIZE, "a path's length is negative or infinite, or it has 2^31 samples or more");
+    return FCPP_OK;
+}
+
+int fcpp_dubins_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
+                       const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
+                       double *kappas, const int64_t *out_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
+    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<int64_t> outs;
+    try {
+        const int rc = host_offsets(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", outs);
+        if (rc) return rc;
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t p = 0; p < n; ++p)
+        if (outs[(size_t)p + 1] - outs[(size_t)p] > INT32_MAX) return fail(FCPP_ESIZE, "a path has 2^31 samples or more");
+    DevBuf<int64_t> up;         // the kernel reads the table on the device: a caller that brought only a host copy gets it uploaded
+    if (!out_offsets) {
+        HIPCHK(up.upload(outs, st));
+        out_offsets = up.p;
+    }
+    LAUNCHCHK(launch_dubins_sample(st, n, fx, fy, fh, radius, word, seg, spacing, out_offsets, total_samples, xs, ys, hs, kappas));
+    HIPCHK(hipStreamSynchronize(st));
+    return FCPP_OK;
+}
+
 int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const double *D, int32_t *routes, int32_t *best_route,
                    double *hist, fcpp_ga_result *result)
 {
@@ -2182,6 +2256,23 @@ int fcpp_debug_math_dev(fcpp_ctx *c, int fn, int64_t n, const double *a, const d
     HIPCHK(hipSetDevice(c->device));
     LAUNCHCHK(launch_debug_math(c->stream, fn, n, a, b, out0, out1));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_debug_dubins(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
+                      double radius, int32_t *word, double *seg, double *len)
+{
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        int w;
+        double s0, s1, s2, tot;
+        dubins_solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s0, s1, s2, tot);
+        if (word) word[i] = w;
+        if (seg) { seg[3 * i] = s0; seg[3 * i + 1] = s1; seg[3 * i + 2] = s2; }
+        if (len) len[i] = tot;
+    }
     return FCPP_OK;
 }
 

@@ -463,6 +463,61 @@ class BatchResult:
         return _sample(self.batch.ctx, self.x, self.y, self.v, self.flagseg, self.path_offsets(), None, (s, t, h, totals.view(-1, 2)), dt, include_end)
 
 
+    def drivable_connectors(self, radius=None, spacing=0.5, start_headings=None, end_headings=None):
+        """Connectors a vehicle with a turning radius can drive, in place of the reference's straight lines (MLP:1313-1355): per field up to
+        three Dubins paths (fcpp_dubins_solve / _counts / _sample) --
+          0 approach:  parking pose -> the first point of the headland path (`approach_to`) with that point's heading; fields with a kept start point
+          1 link:      last point of the main work with its heading -> first point of the headland with its heading; fields with both paths
+          2 departure: last point of the headland path (`departure_from`) with its heading -> parking pose; fields with a kept end point
+        radius: default the vehicle's min_turn_radius.  start_headings / end_headings: the parking headings [rad], a scalar or one per field;
+        default the direction of the reference's straight connector.  The poses on the coverage path are gathered on the device from the batch
+        arrays and from trajectory()'s headings.  Fields that raised have no connectors.
+        -> dict: 'x', 'y', 'heading', 'kappa' (device, one entry per sample), 'offsets' (device) / 'offsets_host' (numpy): CSR over the
+        connectors, 'field' and 'kind' (numpy, per connector, sorted by field then kind), 'length', 'word', 'from_poses', 'to_poses' (device)."""
+        torch = _torch()
+        b = self.batch
+        a = b.info.array
+        dev = self.x.device
+        R = float(b.vehicle.min_turn_radius if radius is None else radius)
+        ok = a['status'] == 0
+        first_head = a['point_offset'] + a['n_main']
+        has = (ok & (a['start_kept'] != 0) & (a['n_head'] > 0), ok & (a['n_main'] > 0) & (a['n_head'] > 0), ok & (a['end_kept'] != 0) & (a['n_head'] > 0))
+        field = np.concatenate([np.flatnonzero(h) for h in has]).astype(np.int64)
+        kind = np.concatenate([np.full(int(h.sum()), k, dtype=np.int32) for k, h in enumerate(has)])
+        order = np.lexsort((kind, field))
+        field, kind = field[order], kind[order]
+        m = len(field)
+        # indices into the batch arrays of the poses that lie on the coverage path (0 where the pose is the parking pose), and the parking points
+        fi = np.where(kind == 1, first_head[field] - 1, np.where(kind == 2, first_head[field] + a['n_head'][field] - 1, 0))
+        ti = np.where(kind == 2, 0, first_head[field])
+        park = np.where((kind == 0)[:, None], a['approach_from'][field], a['departure_to'][field]).reshape(m, 2)
+        heads = np.full(m, np.nan)
+        for k, given in ((0, start_headings), (2, end_headings)):
+            if given is not None:
+                g = np.broadcast_to(np.asarray(given, dtype=np.float64), (b.n_fields,))
+                heads[kind == k] = g[field[kind == k]]
+        h = self.trajectory()[2]
+        fi_d, ti_d = torch.as_tensor(fi, device=dev), torch.as_tensor(ti, device=dev)
+        kind_d = torch.as_tensor(kind, device=dev)
+        park_d, heads_d = torch.as_tensor(park, device=dev), torch.as_tensor(heads, device=dev)
+        if self.x.numel() == 0:
+            fi_d, ti_d = fi_d[:0], ti_d[:0]
+        frm = torch.stack((self.x[fi_d], self.y[fi_d], h[fi_d]), dim=1)
+        to = torch.stack((self.x[ti_d], self.y[ti_d], h[ti_d]), dim=1)
+        is_ap, is_dp = (kind_d == 0)[:, None], (kind_d == 2)[:, None]
+        # the parking pose: its heading as given, else along the straight connector of the reference (parking -> path / path -> parking)
+        ap_dir = torch.atan2(to[:, 1] - park_d[:, 1], to[:, 0] - park_d[:, 0])
+        dp_dir = torch.atan2(park_d[:, 1] - frm[:, 1], park_d[:, 0] - frm[:, 0])
+        given = ~torch.isnan(heads_d)
+        ap_pose = torch.cat((park_d, torch.where(given, heads_d, ap_dir)[:, None]), dim=1)
+        dp_pose = torch.cat((park_d, torch.where(given, heads_d, dp_dir)[:, None]), dim=1)
+        frm = torch.where(is_ap, ap_pose, frm)
+        to = torch.where(is_dp, dp_pose, to)
+        out = _dubins_paths(b.ctx, frm, to, R, spacing)
+        out.update(field=field, kind=kind, from_poses=frm, to_poses=to, radius=R)
+        return out
+
+
 class Batch:
     """n independent fields planned together on one GPU (fcpp_batch_*)."""
 
@@ -937,6 +992,78 @@ def trajectory_sample(x, y, v, dt, flagseg=None, offsets=None, include_end=True,
     if traj is None:
         traj = trajectory(x, y, v, fs, offsets, device)
     return _sample(ctx, x, y, v, fs, off_h, off, traj, dt, include_end)
+
+
+def _poses(p, device):
+    """(n, 3) poses (x, y, heading [rad]) -> three contiguous float64 device tensors"""
+    t = _dev_f64(p, device).reshape(-1, 3)
+    return t[:, 0].contiguous(), t[:, 1].contiguous(), t[:, 2].contiguous()
+
+
+def _dubins_solve(ctx, f, t, radius):
+    torch = _torch()
+    n = int(f[0].numel())
+    if int(t[0].numel()) != n:
+        raise ValueError('from_poses and to_poses must hold the same number of poses')
+    dev = f[0].device
+    word = torch.empty(n, dtype=torch.int32, device=dev)
+    seg = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    length = torch.empty(n, dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_dubins_solve(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
+                                      _ptr(word), _ptr(seg), _ptr(length)))
+    return word, seg, length
+
+
+def dubins_solve(from_poses, to_poses, radius, device=None):
+    """Shortest forward-only Dubins path of every pair from_poses[i] -> to_poses[i] (fcpp_dubins_solve) for the turning radius `radius` [m].
+    Poses: (n, 3) arrays or tensors (x, y, heading [rad]).  -> (word, seg, length) device tensors: the winning word (0 LSL, 1 LSR, 2 RSL,
+    3 RSR, 4 RLR, 5 LRL; -1 for a pair with a non-finite input), its three segment lengths [m] (n, 3) and their sum."""
+    ctx = get_context(device)
+    dev = _torch().device('cuda', ctx.device)
+    return _dubins_solve(ctx, _poses(from_poses, dev), _poses(to_poses, dev), radius)
+
+
+def dubins_matrix(from_poses, to_poses, radius, want_words=False, device=None):
+    """The transit matrix D[i][j] = shortest Dubins length from exit pose i to entry pose j (fcpp_dubins_matrix): (n_from, n_to) float64 on
+    the device, the layout ga_fitness / ga_evolve take when both lists are the same nodes.  Not symmetric.  want_words: also the winning
+    words, (n_from, n_to) int8."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    nf, nt = int(f[0].numel()), int(t[0].numel())
+    D = torch.empty((nf, nt), dtype=torch.float64, device=dev)
+    W = torch.empty((nf, nt), dtype=torch.int8, device=dev) if want_words else None
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_dubins_matrix(ctx.handle, nf, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), nt, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
+                                       _ptr(D), _ptr(W)))
+    return (D, W) if want_words else D
+
+
+def _dubins_paths(ctx, from_poses, to_poses, radius, spacing):
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    word, seg, length = _dubins_solve(ctx, f, t, radius)
+    n = int(word.numel())
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    L.check(ctx.lib.fcpp_dubins_counts(ctx.handle, n, _ptr(length), float(spacing), _ptr(off), _host_ptr(off_h)))
+    m = int(off_h[-1])
+    out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'heading', 'kappa')}
+    L.check(ctx.lib.fcpp_dubins_sample(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing),
+                                       _ptr(off), m, _ptr(out['x']), _ptr(out['y']), _ptr(out['heading']), _ptr(out['kappa']), _host_ptr(off_h)))
+    out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
+    return out
+
+
+def dubins_paths(from_poses, to_poses, radius, spacing, device=None):
+    """The shortest Dubins paths of the pairs, sampled every `spacing` metres (fcpp_dubins_solve + _counts + _sample) -> (x, y, heading, kappa,
+    offsets) device tensors: path p owns the samples offsets[p] .. offsets[p + 1]; its first sample is its start pose, sample k lies at arc
+    length k * spacing, its last sample is the path's end.  kappa: +1/radius on left arcs, -1/radius on right arcs, 0 on the straight."""
+    o = _dubins_paths(get_context(device), from_poses, to_poses, radius, spacing)
+    return o['x'], o['y'], o['heading'], o['kappa'], o['offsets']
 
 
 def _polys(polygons):

@@ -440,6 +440,56 @@ int fcpp_best_connections(fcpp_ctx *ctx, int64_t n_pairs, const int64_t *from_of
                           const double *fx_dev, const double *fy_dev, const double *tx_dev, const double *ty_dev,
                           int32_t *best_from_dev, int32_t *best_to_dev, double *best_dist_dev);
 
+/* ---- Dubins connectors: the shortest forward-only path between two POSES for a vehicle with a turning radius --------------------------
+ * Build-defined.  What they replace: the reference's straight 50-point approach / departure lines (MLP:1313-1355, "简单的直线连接"), the
+ * missing link between main work and headland, and the Euclidean transit cost of the scheduler inputs above; its roadmap asks for them
+ * (doc/两层路径规划器 - 深度优化和改进路线图.md section 1.2: shortest path between two poses, sampled at a spacing).  Forward motion only
+ * (Reeds-Shepp paths, which reverse, are not provided).
+ * A pose is (x, y, heading): metres, and radians as fcpp_trajectory writes them (any finite value with |heading| <= 1e5).  All arrays are
+ * device pointers, SoA float64; `radius` > 0 is ONE scalar per call.  Words: 0 LSL, 1 LSR, 2 RSL, 3 RSR, 4 RLR, 5 LRL (L = left /
+ * counter-clockwise arc, R = right arc, S = straight).  For each pair all six closed forms (Dubins 1957; Shkel & LaValle 2001) are evaluated
+ * on the turning circles' centres -- formed from the DIFFERENCE of the two positions, in metres, no normalising rotation or scaling -- the
+ * feasible ones kept and the shortest taken; among equal totals the LOWEST word index wins, so the choice is a function of the inputs alone.
+ * seg: three segment lengths in metres, each >= 0, an arc's length = radius x its angle in [0, 2 pi); total = (seg[0] + seg[1]) + seg[2].
+ * The rules at the edges (csrc/fcpp_dubinsfn.h, one function for host and device: the same bits on both):
+ *   - every arc angle is a difference reduced into [0, 2 pi); a reduced angle ABOVE 2 pi - 2^-43 (within 128 ulp of a full circle) is 0.
+ *     Without it an angle that is mathematically 0 but comes out as -1 ulp would be a full circle of path that is not there -- exactly where
+ *     a start heading points at the goal or two swaths are exactly parallel.  The price: the end pose of such a path may be off by up to
+ *     2^-43 x (radius + straight) metres;
+ *   - with c2 the computed squared distance of the two circle centres a word uses: LSR / RSL are feasible iff c2 >= 4 R^2 (1 - 2^-48), RLR / LRL
+ *     iff c2 <= 16 R^2 (1 + 2^-48); inside those bands of 16 ulp the root's argument is clamped to 0 (the circles touch), beyond them the word is
+ *     infeasible (the shortest length is discontinuous in the poses there: a last bit may decide which word wins);
+ *   - circle centres closer than 2^-40 R count as one centre (no first arc; the straight keeps its tiny length).  Start == goal exactly:
+ *     word 0, lengths 0, 0, 0;
+ *   - a pair with a non-finite coordinate difference or heading (or differences so large that their squares overflow): word -1, lengths and total NaN -- per pair, the call succeeds (as
+ *     fcpp_ga_fitness treats bad genes).
+ * Errors, checked before anything touches the GPU: FCPP_EINVAL for a NULL handle or array, a radius or spacing that is <= 0 or not finite;
+ * FCPP_ESIZE for negative or inconsistent sizes.  Asynchronous on the context's stream unless stated. */
+/* pair i = (from i -> to i), a lane per pair.  word_dev: n int32; seg_dev: 3 per pair; len_dev: n totals.  Any output may be NULL. */
+int fcpp_dubins_solve(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                      const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, int32_t *word_dev,
+                      double *seg_dev, double *len_dev);
+/* The transit matrix: D[i][j] = shortest length from exit pose i to entry pose j, row-major n_from x n_to -- the layout fcpp_ga_fitness /
+ * fcpp_ga_evolve take when both lists are the same nodes.  NOT symmetric; the diagonal of a list against itself is 0.  Entry (i, j) has the
+ * bits fcpp_dubins_solve gives for that pair.  word_dev: NULL or n_from x n_to int8.  At most 2^20 poses per side. */
+int fcpp_dubins_matrix(fcpp_ctx *ctx, int64_t n_from, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                       int64_t n_to, const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, double *D_dev,
+                       int8_t *word_dev);
+/* Solved paths at a fixed spacing [m] (the pattern of fcpp_trajectory_counts / _sample): path p gets K_p = floor(total_p / spacing) + 1
+ * samples at s = k * spacing (one multiplication, never accumulated), plus one more AT total_p when the last of them lies before it: the
+ * first sample is the start pose, the last the path's end.  A path of total 0 has its one sample, a NaN path one sample of NaNs.
+ * fcpp_dubins_counts: the samples' CSR offsets (n + 1) from len_dev; out_offsets_host: NULL or room for a copy.  FCPP_ESIZE: a length that is
+ * negative or infinite, a path of 2^31 samples or more.  Synchronises. */
+int fcpp_dubins_counts(fcpp_ctx *ctx, int64_t n, const double *len_dev, double spacing, int64_t *out_offsets_dev, int64_t *out_offsets_host);
+/* Per sample x, y, heading in (-pi, pi] and the signed curvature (+1/radius on a left arc, -1/radius on a right arc, 0 on the straight),
+ * evaluated from the START OF THE SEGMENT that contains s (the segment start poses are closed forms of the start pose), never from the
+ * previous sample: a path gives the same bits alone and as path 4711 of a batch.  s at a junction belongs to the segment that starts there;
+ * the last sample is the end of the last segment.  word_dev / seg_dev as fcpp_dubins_solve wrote them for the same start poses and
+ * radius.  Every output may be NULL; out_offsets_host spares the read-back (the table is checked: FCPP_ESIZE).  Synchronises. */
+int fcpp_dubins_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev, double radius,
+                       const int32_t *word_dev, const double *seg_dev, double spacing, const int64_t *out_offsets_dev, int64_t total_samples,
+                       double *xs_dev, double *ys_dev, double *hs_dev, double *kappas_dev, const int64_t *out_offsets_host);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -493,6 +543,10 @@ int fcpp_gather(fcpp_ctx *ctx, void *nccl_comm, int rank, int world, int root, i
  * device pointers and synchronises. */
 int fcpp_debug_math(int fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
 int fcpp_debug_math_dev(fcpp_ctx *ctx, int fn, int64_t n, const double *a_dev, const double *b_dev, double *out0_dev, double *out1_dev);
+/* fcpp_dubins_solve's function (csrc/fcpp_dubinsfn.h) evaluated on the HOST, on host pointers: what the device results are compared with
+ * bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
+int fcpp_debug_dubins(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,
+                      const double *to_h, double radius, int32_t *word, double *seg, double *len);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch

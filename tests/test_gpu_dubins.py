@@ -1,0 +1,295 @@
+"""GPU tests of the Dubins connectors (run with -m gpu on an MI355X): the kernels of csrc/fcpp_dubins.hip against the same function on the
+host (fcpp_debug_dubins) BIT FOR BIT, the sampler against the numpy restatement of tests/test_dubins_host.py, the sampled paths through
+the project's own operators (curvature, trajectory, GA fitness), and BatchResult.drivable_connectors / the planner mirror.
+
+Tolerances as in tests/test_dubins_host.py: 1e-9 m, 1e-12 rad; everything the issue calls bit-equal is compared with array_equal."""
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+from tests.test_dubins_host import H_TOL, P_TOL, RADII, host_solve, pose_along, random_pairs, wrap
+
+pytestmark = pytest.mark.gpu
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _special_pairs():
+    """degenerate and non-finite pairs"""
+    f = np.array([[0, 0, 0], [5, 5, 1.0], [0, 0, 0], [0, 0, 0], [np.nan, 0, 0], [0, np.inf, 0], [0, 0, np.nan], [0, 0, 0], [1, 2, 3], [0, 0, 0]],
+                 dtype=np.float64)
+    t = np.array([[10, 0, 0], [5, 5, 1.0], [0, 16, np.pi], [0, 3.2, np.pi], [1, 1, 1], [1, 1, 1], [1, 1, 1], [1, -np.inf, 0], [1, 2, np.inf],
+                  [1e-13, 0, 0]], dtype=np.float64)
+    return f, t
+
+
+def _pairs(R, n=50_000, seed=5):
+    rng = np.random.default_rng(seed)
+    a = random_pairs(rng, n, R, False)
+    b = random_pairs(rng, n, R, True)
+    s = _special_pairs()
+    return np.vstack((a[0], b[0], s[0])), np.vstack((a[1], b[1], s[1]))
+
+
+@pytest.mark.parametrize('R', RADII)
+def test_device_solve_equals_the_host_function_bit_for_bit(R):
+    frm, to = _pairs(R)
+    w, seg, tot = E.dubins_solve(frm, to, R)
+    hw, hseg, htot = host_solve(frm, to, R)
+    assert np.array_equal(_np(w), hw)
+    assert np.array_equal(_bits(_np(seg)), _bits(hseg))         # (NaN pairs included: the same NaN)
+    assert np.array_equal(_bits(_np(tot)), _bits(htot))
+    assert (hw[-10:] == [0, 0, hw[-8], 4, -1, -1, -1, -1, -1, 0]).all()
+
+
+@pytest.mark.parametrize('nf,nt', [(1, 1), (37, 1000), (1000, 37), (513, 513)])
+def test_matrix_entries_equal_the_pair_solve_bit_for_bit(nf, nt):
+    R = 8.0
+    rng = np.random.default_rng(nf * 7919 + nt)
+    frm = random_pairs(rng, nf, R, False)[0]
+    to = np.column_stack((frm[rng.integers(0, nf, nt), :2] + rng.uniform(-4 * R, 4 * R, (nt, 2)), rng.uniform(-np.pi, np.pi, nt)))
+    if nt > 5:
+        to[3] = frm[min(2, nf - 1)]           # one exact self pair
+        to[4, 2] = np.nan                     # a bad column
+    D, W = E.dubins_matrix(frm, to, R, want_words=True)
+    ii, jj = np.meshgrid(np.arange(nf), np.arange(nt), indexing='ij')
+    w, seg, tot = E.dubins_solve(frm[ii.ravel()], to[jj.ravel()], R)
+    assert np.array_equal(_bits(_np(D)).ravel(), _bits(_np(tot)))
+    assert np.array_equal(_np(W).ravel().astype(np.int32), _np(w))
+    assert np.array_equal(_bits(_np(E.dubins_matrix(frm, to, R))), _bits(_np(D)))          # without the words: the same matrix
+    if nf == nt and nf > 1:
+        S = _np(E.dubins_matrix(frm, frm, R))
+        assert not np.diagonal(S).any()
+        assert np.abs(S - S.T).max() > 1.0        # not symmetric
+
+
+def _sampled(frm, to, R, spacing):
+    ctx = E.get_context()
+    return E._dubins_paths(ctx, frm, to, R, spacing)
+
+
+@pytest.mark.parametrize('R,spacing', [(8.0, 0.5), (2.0, 0.1), (25.0, 0.37)])
+def test_sampler_offsets_poses_spacing_and_curvature(R, spacing):
+    rng = np.random.default_rng(9)
+    a, b = random_pairs(rng, 300, R, False), random_pairs(rng, 700, R, True)
+    frm, to = np.vstack((a[0], b[0], [[3.0, 4.0, 0.5], [0, 0, 0]])), np.vstack((a[1], b[1], [[3.0, 4.0, 0.5], [np.nan, 0, 0]]))
+    frm[:300, :2] = frm[:300, :2] * 0.04 + 2000       # (far pairs up to ~280 m apart: a few hundred samples each)
+    to[:300, :2] = to[:300, :2] * 0.04 + 2000
+    o = _sampled(frm, to, R, spacing)
+    tot, word, seg = _np(o['length']), _np(o['word']), _np(o['seg'])
+    off = _np(o['offsets'])
+    assert np.array_equal(off, o['offsets_host'])
+    # the counts rule, in numpy from the device's totals: exact integers
+    K = np.ones(len(tot), dtype=np.int64)
+    fin = ~np.isnan(tot)
+    K[fin] = np.floor(tot[fin] / spacing).astype(np.int64) + 1
+    K[fin] += ((K[fin] - 1) * spacing < tot[fin])
+    assert np.array_equal(off, np.concatenate(([0], np.cumsum(K))))
+    x, y, h, kap = (_np(o[k]) for k in ('x', 'y', 'heading', 'kappa'))
+    assert len(x) == off[-1]
+    # the NaN path: one sample of NaNs; the path of length 0: its one sample is the pose
+    assert K[-1] == 1 and np.isnan([x[-1], y[-1], h[-1], kap[-1]]).all()
+    assert K[-2] == 1 and (x[off[-3]], y[off[-3]], h[off[-3]]) == (3.0, 4.0, 0.5)
+    ok = np.flatnonzero(fin)
+    first, last = off[:-1][ok], off[1:][ok] - 1
+    # first sample = start pose (bit-equal: evaluated from the segment's own start), last sample = goal pose
+    assert np.array_equal(x[first], frm[ok, 0]) and np.array_equal(y[first], frm[ok, 1]) and np.array_equal(h[first], frm[ok, 2])
+    assert np.abs(x[last] - to[ok, 0]).max() <= P_TOL and np.abs(y[last] - to[ok, 1]).max() <= P_TOL
+    assert np.abs(wrap(h[last] - to[ok, 2])).max() <= H_TOL
+    # every sample against the restatement's pose at k * spacing
+    path = np.repeat(np.arange(len(tot)), K)
+    k = np.arange(off[-1]) - off[:-1][path]
+    s = np.minimum(k * spacing, tot[path])
+    s[off[1:] - 1] = tot
+    good = fin[path]
+    rx, ry, rh, turn = pose_along(frm[path][good], R, word[path][good], seg[path][good], s[good], np.longdouble)
+    assert np.abs(x[good] - rx).max() <= P_TOL and np.abs(y[good] - ry).max() <= P_TOL
+    assert np.abs(wrap((h[good] - rh).astype(np.float64))).max() <= H_TOL
+    # kappa is 0 or +-1/R exactly, and names the segment the sample lies in
+    assert np.isin(kap[good], [0.0, 1.0 / R, -1.0 / R]).all()
+    assert np.array_equal(kap[good], np.where(turn == 0, 0.0, np.where(turn > 0, 1.0 / R, -(1.0 / R))))
+    # consecutive samples lie `spacing` apart along the path: the chord never exceeds it, and on an arc it is 2 R sin(spacing / 2R)
+    same = (path[1:] == path[:-1]) & good[1:] & (k[1:] < K[path[1:]] - 1)          # (the step to the end sample is shorter)
+    chord = np.hypot(np.diff(x), np.diff(y))[same]
+    assert (chord <= spacing + P_TOL).all()
+    on_arc = (kap[:-1] == kap[1:])[same] & (kap[:-1] != 0)[same]
+    on_line = (kap[:-1] == 0)[same] & (kap[1:] == 0)[same]
+    # (both samples on the same arc: also not across a junction between two arcs of the same sense, which CCC words do not have)
+    assert on_arc.sum() > 1000 and on_line.sum() > 1000
+    assert np.abs(chord[on_arc] - 2 * R * np.sin(spacing / (2 * R))).max() <= P_TOL
+    assert np.abs(chord[on_line] - spacing).max() <= P_TOL
+
+
+def test_a_path_gives_the_same_bits_alone_and_inside_a_batch():
+    R, spacing = 8.0, 0.25
+    rng = np.random.default_rng(21)
+    frm, to = random_pairs(rng, 6000, R, True)
+    whole = _sampled(frm, to, R, spacing)
+    off = whole['offsets_host']
+    for p in (4711, 0, 5999):
+        alone = _sampled(frm[p:p + 1], to[p:p + 1], R, spacing)
+        sl = slice(off[p], off[p + 1])
+        for key in ('x', 'y', 'heading', 'kappa'):
+            assert np.array_equal(_bits(_np(alone[key])), _bits(_np(whole[key])[sl])), (p, key)
+
+
+def test_sampled_paths_through_curvature_and_trajectory():
+    """engine.curvature is the reference's chord formula (MLP:513-536): turning angle of the two chords over their mean length.  At a sample
+    whose two neighbours lie `spacing` away on the same arc both chords are 2 R sin(phi / 2), phi = spacing / R, and they turn by phi:
+    kappa = phi / (2 R sin(phi / 2)) = (1/R) (phi/2) / sin(phi/2) -- 1.6e-4 above 1/R at 0.5 m and R = 8.  On straights 0.
+    engine.trajectory's heading is the chord's direction: phi / 2 off the tangent the sampler reports, at most spacing / (2 R).
+    The slack on that bound is the number format's, not the headings' 1e-12: the chord is formed from float64 coordinates of magnitude
+    < 8192 m, each rounded to half an ulp (ulp = 2^-40 m = 9.1e-13 m); two end points x two coordinates move the direction of a chord of
+    length c by at most 4 x (ulp / 2) x sqrt(2) / c < 4 ulp / c radians -- 7.3e-12 rad at c = 0.5 m."""
+    R, spacing = 8.0, 0.5
+    rng = np.random.default_rng(33)
+    frm, to = random_pairs(rng, 400, R, True)
+    o = _sampled(frm, to, R, spacing)
+    off = o['offsets_host']
+    x, y, kap, h = (_np(o[k]) for k in ('x', 'y', 'kappa', 'heading'))
+    kc = _np(E.curvature(o['x'], o['y'], offsets=off))
+    path = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    inner = np.zeros(len(x), dtype=bool)
+    inner[1:-1] = (path[2:] == path[:-2]) & (kap[2:] == kap[1:-1]) & (kap[:-2] == kap[1:-1])
+    d_prev, d_next = np.zeros(len(x)), np.zeros(len(x))
+    d_prev[1:], d_next[:-1] = np.hypot(np.diff(x), np.diff(y)), np.hypot(np.diff(x), np.diff(y))
+    phi = spacing / R
+    full = inner & (np.abs(d_prev - 2 * R * np.sin(phi / 2)) < 1e-9) & (np.abs(d_next - 2 * R * np.sin(phi / 2)) < 1e-9) & (kap != 0)
+    assert full.sum() > 5000
+    expect = (1 / R) * (phi / 2) / np.sin(phi / 2)
+    assert np.abs(kc[full] / expect - 1).max() <= 1e-9
+    assert 1.5e-4 < expect * R - 1 < 1.7e-4
+    line = inner & (kap == 0) & (np.abs(d_prev - spacing) < 1e-9) & (np.abs(d_next - spacing) < 1e-9)
+    assert line.sum() > 100 and np.abs(kc[line]).max() <= 1e-9
+    th = _np(E.trajectory(o['x'], o['y'], np.full(len(x), 9.0), offsets=off)[2])
+    has_next = np.zeros(len(x), dtype=bool)
+    has_next[:-1] = (path[1:] == path[:-1]) & (d_next[:-1] > 1e-6)
+    dev = np.abs(wrap(th - h))[has_next]
+    slack = 4 * 2.0 ** -40 / d_next[has_next]
+    print(f'chord vs tangent: max {dev.max():.15f} rad, bound {spacing / (2 * R)} + {slack.max():.2e}')
+    assert (dev <= spacing / (2 * R) + slack + H_TOL).all()
+
+
+def test_asymmetric_matrix_goes_through_ga_fitness_unchanged():
+    R, n = 8.0, 200
+    rng = np.random.default_rng(44)
+    poses = np.column_stack((rng.uniform(0, 2000, (n, 2)), rng.uniform(-np.pi, np.pi, n)))
+    D = E.dubins_matrix(poses, poses, R)
+    Dh = _np(D)
+    assert not np.diagonal(Dh).any() and np.abs(Dh - Dh.T).max() > 1.0
+    routes = np.stack([rng.permutation(n) for _ in range(64)]).astype(np.int32)
+    dist, _ = E.ga_fitness(routes, D, order_mode=0)
+    exp = np.zeros(64)
+    for r in range(64):
+        acc = 0.0
+        for a, b in zip(routes[r], np.roll(routes[r], -1)):
+            acc += Dh[a, b]
+        exp[r] = acc
+    assert np.array_equal(_bits(_np(dist)), _bits(exp))
+
+
+def _check_connectors(res, con, start_headings=None, end_heading=None):
+    a = res.batch.info.array
+    x, y = _np(res.x), _np(res.y)
+    h = _np(res.trajectory()[2])
+    off = con['offsets_host']
+    cx, cy, ch = _np(con['x']), _np(con['y']), _np(con['heading'])
+    field, kind = con['field'], con['kind']
+    length = _np(con['length'])
+    assert len(off) == len(field) + 1 and (np.diff(off) >= 1).all()
+    # which fields have which connector
+    ok = a['status'] == 0
+    for k, want in enumerate((ok & (a['start_kept'] != 0), ok & (a['n_main'] > 0) & (a['n_head'] > 0), ok & (a['end_kept'] != 0))):
+        assert np.array_equal(np.sort(field[kind == k]), np.flatnonzero(want)), k
+    assert not np.isin(field, np.flatnonzero(~ok)).any()
+    assert (np.diff(field) >= 0).all()
+    first_head = a['point_offset'] + a['n_main']
+    for c in range(len(field)):
+        f, k = field[c], kind[c]
+        s, e = off[c], off[c + 1] - 1
+        fh, lh, lm = first_head[f], first_head[f] + a['n_head'][f] - 1, first_head[f] - 1
+        if k == 0:      # parking -> first headland point
+            assert (cx[s], cy[s]) == tuple(a['approach_from'][f])
+            assert np.hypot(x[fh] - a['approach_to'][f][0], y[fh] - a['approach_to'][f][1]) <= P_TOL
+            goal = (x[fh], y[fh], h[fh])
+            if start_headings is None:
+                assert abs(wrap(ch[s] - np.arctan2(y[fh] - cy[s], x[fh] - cx[s]))) <= H_TOL
+            else:
+                assert ch[s] == start_headings[f]
+        elif k == 1:    # last point of the main work -> first point of the headland
+            assert (cx[s], cy[s], ch[s]) == (x[lm], y[lm], h[lm])
+            goal = (x[fh], y[fh], h[fh])
+        else:           # last headland point -> parking
+            assert (cx[s], cy[s], ch[s]) == (x[lh], y[lh], h[lh])
+            assert np.hypot(x[lh] - a['departure_from'][f][0], y[lh] - a['departure_from'][f][1]) <= P_TOL
+            goal = tuple(a['departure_to'][f]) + (ch[e],)
+            if end_heading is None:
+                assert abs(wrap(ch[e] - np.arctan2(goal[1] - y[lh], goal[0] - x[lh]))) <= H_TOL
+            else:
+                assert abs(wrap(ch[e] - end_heading)) <= H_TOL
+        # the goal poses as handed to the solver are the batch arrays' values, bit for bit
+        tp = _np(con['to_poses'])[c]
+        if k != 2:
+            assert tuple(tp) == goal
+        assert abs(cx[e] - goal[0]) <= P_TOL and abs(cy[e] - goal[1]) <= P_TOL and abs(wrap(ch[e] - goal[2])) <= H_TOL
+        assert length[c] >= np.hypot(goal[0] - cx[s], goal[1] - cy[s]) - P_TOL
+    kap = _np(con['kappa'])
+    R = con['radius']
+    assert np.isin(kap, [0.0, 1.0 / R, -1.0 / R]).all()
+
+
+def test_drivable_connectors_on_the_golden_field_and_the_mirror():
+    from field_coverage_path_planning_amd.multi_layer_planner_v3 import TwoLayerPathPlannerV37, VehicleParams
+    spec = [E.FieldSpec(field_length=500.0, field_width=200.0, start_point=(10.0, 10.0), end_point=(490.0, 190.0))]
+    batch = E.Batch(spec, E.make_vehicle())
+    res = batch.run()
+    con = res.drivable_connectors()
+    assert list(con['kind']) == [0, 1, 2] and con['radius'] == 8.0
+    _check_connectors(res, con)
+    # the default parking heading points at the goal: a Dubins path that starts along the chord, never 2 pi R longer than chord + a turn
+    length = _np(con['length'])
+    ap_to = np.array(batch.info[0].approach_to)
+    assert length[0] < np.hypot(*(ap_to - (10.0, 10.0))) + 2 * np.pi * 8.0
+    pl = TwoLayerPathPlannerV37(VehicleParams(), field_length=500, field_width=200, start_point=(10, 10), end_point=(490, 190))
+    before = pl.plan_complete_coverage()
+    d = pl.drivable_connectors()
+    off = con['offsets_host']
+    for k, name in enumerate(('approach', 'link', 'departure')):
+        sl = slice(off[k], off[k + 1])
+        assert np.array_equal(d[name + '_path'], np.column_stack((_np(con['x'])[sl], _np(con['y'])[sl])))
+        assert np.array_equal(d[name + '_heading'], _np(con['heading'])[sl])
+        assert np.array_equal(d[name + '_curvature'], _np(con['kappa'])[sl])
+        assert d[name + '_length'] == length[k]
+    after = pl.plan_complete_coverage()
+    assert set(after) == set(before) and np.array_equal(after['approach_path'], before['approach_path'])
+    # a given parking heading is used as it is; a larger radius and a finer spacing are taken
+    d2 = pl.drivable_connectors(start_heading=1.0, end_heading=-2.0, spacing=0.1)
+    assert d2['approach_heading'][0] == 1.0 and abs(wrap(d2['departure_heading'][-1] + 2.0)) <= H_TOL
+    pl2 = TwoLayerPathPlannerV37(VehicleParams(), field_length=500, field_width=200)
+    d3 = pl2.drivable_connectors()
+    assert d3['approach_path'] is None and d3['departure_path'] is None and d3['link_path'] is not None
+    batch.close()
+
+
+def test_drivable_connectors_on_a_random_batch():
+    from tests.test_gpu_parity import _random_fields
+    specs, _ = _random_fields(77, 72)
+    specs[5] = E.FieldSpec(field_length=15.0, field_width=200.0, start_point=(5.0, 5.0))        # raises: headland wider than the field
+    specs[40] = E.FieldSpec(field_length=15.0, field_width=200.0)
+    batch = E.Batch(specs, E.make_vehicle())
+    res = batch.run()
+    a = batch.info.array
+    assert (a['status'] != 0).sum() >= 2 and (a['start_kept'] != 0).sum() > 10 and (a['end_kept'] != 0).sum() > 10
+    _check_connectors(res, res.drivable_connectors())
+    heads = np.linspace(-3.0, 3.0, len(specs))
+    con = res.drivable_connectors(radius=10.0, spacing=0.25, start_headings=heads, end_headings=0.5)
+    assert con['radius'] == 10.0
+    _check_connectors(res, con, start_headings=heads, end_heading=0.5)
+    batch.close()
