@@ -1,4 +1,5 @@
-// fcpp_api.cpp -- the C ABI declared in include/fcpp.h: argument checking, device buffers, launches.
+// fcpp_api.cpp -- the C ABI declared in include/fcpp.h: the context and its output arena, batch setup and step, GA, cover, gather and the
+// debug entries: argument checking, device buffers, launches.  (The standalone path operators: fcpp_paths.cpp.)
 // No CPU compute path exists here: every operator ends in a HIP kernel launch or fails with FCPP_EHIP.
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
@@ -15,61 +16,22 @@
 #include <string>
 #include <vector>
 
+#include "fcpp_api_internal.h"
 #include "fcpp_cover.h"
 #include "fcpp_ga.h"
-#include "fcpp_device.h"
 #include "fcpp_devplan.h"
-#include "fcpp_dubins.h"
 #include "fcpp_dubinsfn.h"
-#include "fcpp_internal.h"
 #include "fcpp_parallel.h"
-#include "fcpp_tiler.h"
-#include "fcpp_traj.h"
 
 using namespace fcpp;
 
 namespace fcpp { thread_local LaunchProf g_launch_prof; }
 
-namespace {
-thread_local std::string g_err;
+namespace { thread_local std::string g_err; }
 
-int fail(int code, const std::string &msg) { g_err = msg; return code; }
+int fcpp::fail(int code, const std::string &msg) { g_err = msg; return code; }
 
-#define HIPCHK(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return fail(FCPP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
-#define LAUNCHCHK(expr)                                                                                  \
-    do {                                                                                                 \
-        int e_ = (expr);                                                                                 \
-        if (e_ != 0)                                                                                     \
-            return fail(FCPP_EHIP, std::string(#expr) + ": " + hipGetErrorString((hipError_t)e_));       \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        if (count == 0) return hipSuccess;
-        return hipMalloc((void **)&p, count * sizeof(T));
-    }
-    hipError_t upload(const std::vector<T> &h, hipStream_t st)
-    {
-        hipError_t e = alloc(h.size());
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    }
-};
-
-DevConst make_const(const fcpp_vehicle &veh, const fcpp_options &opt)
+DevConst fcpp::make_const(const fcpp_vehicle &veh, const fcpp_options &opt)
 {
     DevConst c;
     c.a_lat = veh.max_lateral_accel; c.a_lon = veh.max_longitudinal_accel; c.sf = veh.safety_factor;
@@ -88,63 +50,7 @@ DevConst make_const(const fcpp_vehicle &veh, const fcpp_options &opt)
     return c;
 }
 
-// plain tile table of a set of paths (the staged pipeline and the standalone operators): tiles never straddle paths, hold at most
-// TILE_POINTS points, a path is cut into near-equal tiles.  (The fused pipeline's tiler lives in fcpp_tiler.cpp.)
-struct Tiling {
-    std::vector<DevPath> paths;
-    std::vector<DevTile> tiles;
-    std::vector<int64_t> tile_first;
-    void build(int64_t n_paths, const int64_t *offsets)
-    {
-        paths.resize((size_t)n_paths);
-        tile_first.assign((size_t)n_paths + 1, 0);
-        tiles.clear();
-        for (int64_t p = 0; p < n_paths; ++p) {
-            const int64_t n = offsets[p + 1] - offsets[p];
-            paths[(size_t)p] = { offsets[p], n };
-            tile_first[(size_t)p] = (int64_t)tiles.size();
-            if (n <= 0) continue;
-            const int64_t k = (n + TILE_POINTS - 1) / TILE_POINTS;
-            const TilerSplit<int64_t> sp(n, k);
-            for (int64_t i = 0; i < k; ++i) {
-                DevTile t;
-                t.field = (int32_t)p; t.start = sp.start(i); t.count = (int32_t)sp.count(i); t.quiet = 0; t.stat_tile = 0; t.idx0 = 0; t.off0 = 0;
-                tiles.push_back(t);
-            }
-        }
-        tile_first[(size_t)n_paths] = (int64_t)tiles.size();
-    }
-};
-
-struct DevTiling {
-    DevBuf<DevPath> paths;
-    DevBuf<DevTile> tiles;
-    DevBuf<int64_t> tile_first;
-    DevBuf<char> agg_f, agg_b;   // Agg = 2 doubles
-    DevBuf<double> carry_f, carry_b;
-    DevBuf<char> spine;          // scratch of the three-level spine (large batches)
-    DevBuf<TilePartial> partial;
-    DevBuf<unsigned long long> n_adj;
-    int64_t n_tiles = 0, n_paths = 0;
-    hipError_t upload(const Tiling &t, hipStream_t st)
-    {
-        n_tiles = (int64_t)t.tiles.size(); n_paths = (int64_t)t.paths.size();
-        hipError_t e;
-        if ((e = paths.upload(t.paths, st)) != hipSuccess) return e;
-        if ((e = tiles.upload(t.tiles, st)) != hipSuccess) return e;
-        if ((e = tile_first.upload(t.tile_first, st)) != hipSuccess) return e;
-        if ((e = agg_f.alloc((size_t)n_tiles * 16)) != hipSuccess) return e;
-        if ((e = agg_b.alloc((size_t)n_tiles * 16)) != hipSuccess) return e;
-        if ((e = carry_f.alloc((size_t)n_tiles)) != hipSuccess) return e;
-        if ((e = carry_b.alloc((size_t)n_tiles)) != hipSuccess) return e;
-        if ((e = spine.alloc((size_t)spine_scratch_bytes(n_tiles))) != hipSuccess) return e;
-        if ((e = partial.alloc((size_t)n_tiles)) != hipSuccess) return e;
-        if ((e = n_adj.alloc((size_t)n_paths)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;   // the staging vectors die here
-        return hipSuccess;
-    }
-};
-
+namespace fcpp {
 // The turn templates of a batch (every field shares the vehicle and the sampling options, hence the shape and the sample count of
 // its U-turns and corner turns): sampled once on the device (k_build_templates), copied back for the tiler's halo sizing and the
 // closed-form test.  A context keeps the last set: a caller that creates batch after batch with one vehicle (the planner mirror does,
@@ -170,62 +76,7 @@ struct TemplateSet {
     }
     bool same(const TurnTemplates &o, double frac) const { return memcmp(&tt, &o, sizeof tt) == 0 && clothoid_frac == frac; }
 };
-}  // namespace
-
-namespace { struct PathTiling; }
-
-struct fcpp_ctx {
-    int device = 0;
-    PathTiling *paths_cache = nullptr;     // tile table of the standalone operators' last path set (make_tiling)
-    hipStream_t own = nullptr, stream = nullptr;
-    // side stream of the fused pipeline: the ALU-bound kernels (wave tiles, general tiles) run beside the HBM-bound streaming
-    // kernels of the same step; ev_fork / ev_join order the two streams inside a step
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // batch setup (fcpp_batch_create): the image of a batch's tables is built in pinned host memory that the context keeps (grow-only,
-    // up to kStageMax; larger images go through a pageable buffer), and the last destroyed batch's device allocation is kept for the
-    // next one (up to kSpareMax): a caller that plans batch after batch allocates nothing after the first
-    void *stage = nullptr; size_t stage_cap = 0;
-    // the stream of the last asynchronous copy out of `stage`: whoever writes that memory next drains it first (a caller that plans batch
-    // after batch has drained it long before: a query; no event -- a record between two kernels holds the second back by 5 us)
-    hipStream_t stage_stream = nullptr; bool stage_busy = false;
-    hipError_t stage_wait()
-    {
-        if (!stage_busy) return hipSuccess;
-        stage_busy = false;
-        hipError_t e = hipStreamSynchronize(stage_stream);
-        if (e != hipSuccess) { (void)hipGetLastError(); e = hipDeviceSynchronize(); }      // (that stream is gone)
-        return e;
-    }
-    void *spare = nullptr; size_t spare_cap = 0;
-    std::shared_ptr<TemplateSet> templates;         // the last batch's turn templates
-    fcpp_setup_times last_setup = {};
-    // device-side setup (fcpp_devplan.h): FCPP_SETUP_AUTO / _HOST / _DEVICE; its scratch (grow-only) and a small pinned block for the
-    // totals that come back in the middle of it
-    int setup_mode = FCPP_SETUP_AUTO;
-    // (up to FOUR scratch allocations, one per stream that sets batches up: a caller that plans batch k + 1 on a second stream while batch k's step
-    // still runs on the first -- the sustained rate of bench.py -- must not wait for that step because its fill pass shared the scratch)
-    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; };
-    static constexpr int kPlanSlots = 4;
-    PlanSlot plan_slots[kPlanSlots];
-    uint64_t plan_tick = 0;
-    int plan_cur = 0;                               // the slot of the setup in progress / of the last one
-    void *verify_scratch = nullptr;                 // sliced reduction of the standalone operators' long paths (reduce_paths)
-    size_t verify_scratch_cap = 0;
-    int64_t *plan_totals_host = nullptr;            // pinned, PC_COLS + PF_COUNT values: the scans of the counting phase write them here
-    unsigned long long *ga_mirror = nullptr;        // pinned, one word: (converged << 32) | generations of the running fcpp_ga_evolve (GaState::mirror)
-    int64_t plan_gen = 0;                           // generation number of the last counting phase (PlanFlag, fcpp_devplan.h)
-    // the stream the last device-side setup was enqueued on (its fill pass may still read the scratch): a setup on ANOTHER stream records
-    // ev_plan there and waits for it -- lazily, when that other stream shows up: an event recorded between two kernels of the plan call
-    // costs 5 us of device time between them (round 5: the three records of a plan call were 16 of its 158 us)
-    hipEvent_t ev_plan = nullptr;
-    // the output arena (fcpp_ctx_reserve_outputs): ONE allocation of 4 x pitch + lane bytes; array k of every batch's outputs lies in lane k
-    // (lanes `pitch` apart), placed first-fit among the live allocations of the lane -- all five arrays of an allocation at the same offset
-    void *arena = nullptr; size_t arena_pitch = 0, arena_lane = 0;
-    struct ArenaBlock { size_t off, len; hipStream_t last = nullptr; bool used = false; };      // last: the stream of the last fcpp_batch_run that wrote the block
-    std::vector<ArenaBlock> arena_live;             // sorted by off
-    std::vector<hipEvent_t> ev_pool;                // setup events of destroyed batches (fcpp_batch::ev_setup), reused: no event is created per plan call
-};
+}  // namespace fcpp
 
 struct fcpp_batch {
     fcpp_ctx *ctx = nullptr;
@@ -338,9 +189,6 @@ static bool closed_form_turns(const fcpp_vehicle &veh, const TurnTemplates &tt, 
     c.turn_time = len / std::max(c.ms_turn, 0.1);
     return true;
 }
-
-static void free_paths_cache(fcpp_ctx *c);
-
 // the constants of the closed-form cut (fcpp_cutfn.h) for a batch: the templates and their chord tables as the HOST copies or as the device
 // arrays (the same values), the rest from the batch's constants (closed_form_turns has run)
 static CutConsts make_cut_consts(TemplateSet &ts, bool device, const BatchTileConsts &k, const DevConst &cst)
@@ -1498,235 +1346,6 @@ int fcpp_batch_destroy(fcpp_batch *b)
     return FCPP_OK;
 }
 
-// ---- standalone operators -------------------------------------------------------------------
-namespace {
-// The tile table of a path set, kept in the context between calls of the standalone operators: a caller that plans and verifies
-// the same paths (the planner mirror does: speed plan, verify, verify again) pays for the host-side tiling and its upload once.
-// The trajectory scan's own tables of a path set (fcpp_trajectory): the blocks of its path-anchored spine and the scan's scratch, built
-// from the offsets on the first trajectory call for them.
-struct TrajTables {
-    DevBuf<TrajBlock> blocks;
-    DevBuf<int64_t> block_first;      // n_paths + 1
-    DevBuf<TrajAgg> agg, pre;         // per tile: its own sums / what enters it, relative to its block
-    DevBuf<TrajAgg> blk, cin;         // per block: its own sums / what enters it, relative to its path
-    DevBuf<int64_t> path_first;       // per path: where its first non-zero step starts
-    int64_t n_blocks = 0;
-    bool built = false;
-};
-
-struct PathTiling {
-    std::vector<int64_t> offs;
-    DevTiling dt;
-    TrajTables traj;
-};
-
-// offsets on the host: the caller's copy, or read back from the device (one copy + synchronisation); the tile table is rebuilt
-// only when they differ from the cached set's
-int make_tiling(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets_dev, const int64_t *offsets_host, int64_t total, DevTiling **out)
-{
-    if (n_paths < 0 || total < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
-    std::vector<int64_t> offs((size_t)n_paths + 1, 0);
-    if (offsets_host) memcpy(offs.data(), offsets_host, offs.size() * sizeof(int64_t));
-    else {
-        HIPCHK(hipMemcpyAsync(offs.data(), offsets_dev, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (offs[0] != 0 || offs.back() != total) return fail(FCPP_ESIZE, "offsets do not span [0, total_points]");
-    for (int64_t p = 0; p < n_paths; ++p)
-        if (offs[(size_t)p + 1] < offs[(size_t)p]) return fail(FCPP_ESIZE, "offsets must be non-decreasing");
-    if (!c->paths_cache || c->paths_cache->offs != offs) {
-        PathTiling *pt = new (std::nothrow) PathTiling();
-        if (!pt) return fail(FCPP_ENOMEM, "out of host memory");
-        Tiling til;
-        til.build(n_paths, offs.data());
-        hipError_t e = pt->dt.upload(til, c->stream);
-        if (e != hipSuccess) { delete pt; return fail(FCPP_EHIP, std::string("tile table upload: ") + hipGetErrorString(e)); }
-        pt->offs.swap(offs);
-        // (work of earlier calls on the old table has completed: every standalone operator synchronises before it returns)
-        delete c->paths_cache;
-        c->paths_cache = pt;
-    }
-    *out = &c->paths_cache->dt;
-    return FCPP_OK;
-}
-
-}  // namespace
-static void free_paths_cache(fcpp_ctx *c) { delete c->paths_cache; c->paths_cache = nullptr; }
-namespace {
-
-DevConst const_from_vehicle(const fcpp_vehicle &veh)
-{
-    fcpp_options o;
-    fcpp_options_default(&o);
-    return make_const(veh, o);
-}
-}  // namespace
-
-int fcpp_curvature(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x,
-                   const double *y, double *kappa, const int64_t *offsets_host)
-{
-    if (!c || (!offsets && !offsets_host) || (total > 0 && (!x || !y || !kappa))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    DevTiling *dtp = nullptr;
-    int rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
-    if (rc) return rc;
-    DevTiling &dt = *dtp;
-    fcpp_vehicle veh;
-    fcpp_vehicle_default(&veh);
-    DevConst cst = const_from_vehicle(veh);
-    DevBuf<double> vtmp;
-    HIPCHK(vtmp.alloc((size_t)total));
-    HIPCHK(hipMemsetAsync(vtmp.p, 0, (size_t)total * sizeof(double), c->stream));
-    LAUNCHCHK(launch_curv_clamp(c->stream, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, 0, x, y, vtmp.p, vtmp.p, kappa, nullptr));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return FCPP_OK;
-}
-
-int fcpp_speed_plan(fcpp_ctx *c, const fcpp_vehicle *veh, int clamp, int64_t n_paths, const int64_t *offsets,
-                    int64_t total, const double *x, const double *y, const double *v_in, double *v_out, double *kappa,
-                    int64_t *n_adjusted, const int64_t *offsets_host)
-{
-    if (!c || !veh || (!offsets && !offsets_host) || (total > 0 && (!x || !y || !v_in || !v_out))) return fail(FCPP_EINVAL, "bad arguments");
-    if (!(veh->max_longitudinal_accel > 0) || !(veh->max_lateral_accel > 0)) return fail(FCPP_EINVAL, "accelerations must be positive");
-    HIPCHK(hipSetDevice(c->device));
-    DevTiling *dtp = nullptr;
-    int rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
-    if (rc) return rc;
-    DevTiling &dt = *dtp;
-    DevConst cst = const_from_vehicle(*veh);
-    hipStream_t st = c->stream;
-    if (n_paths) HIPCHK(hipMemsetAsync(dt.n_adj.p, 0, (size_t)n_paths * sizeof(unsigned long long), st));
-    LAUNCHCHK(launch_curv_clamp(st, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, clamp ? 1 : 0, x, y, v_in, v_out, kappa, dt.n_adj.p));
-    LAUNCHCHK(launch_scan_tiles(st, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, x, y, v_out, dt.agg_f.p, dt.agg_b.p));
-    LAUNCHCHK(launch_scan_spine(st, dt.n_tiles, dt.agg_f.p, dt.agg_b.p, dt.carry_f.p, dt.carry_b.p, dt.spine.p));
-    LAUNCHCHK(launch_scan_apply(st, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, clamp ? 3 : 2, x, y, v_out, v_out,
-                                dt.carry_f.p, dt.carry_b.p));
-    if (n_adjusted && n_paths)
-        HIPCHK(hipMemcpyAsync(n_adjusted, dt.n_adj.p, (size_t)n_paths * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return FCPP_OK;
-}
-
-// The standalone operators' statistics: a path per 64 lanes -- or, for a few LONG paths (one path of 6e7 points is 123 000 tiles: 1.2 ms
-// through one wavefront), every path sliced over 64 workgroups and joined (the fused pipeline's class-3 reduction: 10 us).
-static int reduce_paths(fcpp_ctx *c, hipStream_t st, DevTiling &dt, fcpp_field_stats *stats)
-{
-    if (dt.n_paths > 0 && dt.n_paths <= 64 && dt.n_tiles / dt.n_paths > 2048) {
-        const size_t need = (size_t)dt.n_paths * 64 * 104;
-        if (c->verify_scratch_cap < need) {
-            if (c->verify_scratch) { HIPCHK(hipStreamSynchronize(st)); (void)hipFree(c->verify_scratch); c->verify_scratch = nullptr; c->verify_scratch_cap = 0; }
-            HIPCHK(hipMalloc(&c->verify_scratch, need));
-            c->verify_scratch_cap = need;
-        }
-        LAUNCHCHK(launch_reduce_stats(st, dt.n_paths, dt.partial.p, dt.tile_first.p, nullptr, stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 256,
-                                      c->verify_scratch, 0));
-        return FCPP_OK;
-    }
-    LAUNCHCHK(launch_reduce_stats(st, dt.n_paths, dt.partial.p, dt.tile_first.p, nullptr, stats));
-    return FCPP_OK;
-}
-
-int fcpp_verify(fcpp_ctx *c, const fcpp_vehicle *veh, int64_t n_paths, const int64_t *offsets, int64_t total,
-                const double *x, const double *y, const double *v, fcpp_field_stats *stats, const int64_t *offsets_host)
-{
-    if (!c || !veh || (!offsets && !offsets_host) || !stats || (total > 0 && (!x || !y || !v))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    DevTiling *dtp = nullptr;
-    int rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
-    if (rc) return rc;
-    DevTiling &dt = *dtp;
-    DevConst cst = const_from_vehicle(*veh);
-    hipStream_t st = c->stream;
-    DevBuf<double> kap, vtmp;
-    HIPCHK(kap.alloc((size_t)total));
-    HIPCHK(vtmp.alloc((size_t)total));
-    LAUNCHCHK(launch_curv_clamp(st, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, 0, x, y, v, vtmp.p, kap.p, nullptr));
-    DevObstacles obs = { nullptr, nullptr, nullptr, nullptr };
-    LAUNCHCHK(launch_validate(st, dt.n_tiles, dt.tiles.p, dt.paths.p, nullptr, cst, obs, x, y, kap.p, v, nullptr, dt.partial.p));
-    { const int rrc = reduce_paths(c, st, dt, stats); if (rrc) return rrc; }
-    HIPCHK(hipStreamSynchronize(st));
-    return FCPP_OK;
-}
-
-// ---- trajectory: arc length, time stamp and heading per point; fixed-rate sampling (fcpp_traj.hip) ---------------------------------
-namespace {
-int ensure_traj(PathTiling &pt, hipStream_t st)
-{
-    TrajTables &tr = pt.traj;
-    if (tr.built) return FCPP_OK;
-    const int64_t n_paths = (int64_t)pt.offs.size() - 1;
-    std::vector<TrajBlock> blocks;
-    std::vector<int64_t> first((size_t)n_paths + 1, 0);
-    try {
-        int64_t tile0 = 0;
-        for (int64_t p = 0; p < n_paths; ++p) {
-            const int64_t n = pt.offs[(size_t)p + 1] - pt.offs[(size_t)p], nt = (n + TILE_POINTS - 1) / TILE_POINTS;   // (Tiling::build)
-            first[(size_t)p] = (int64_t)blocks.size();
-            for (int64_t k = 0; k < nt; k += TRAJ_BLOCK_TILES)
-                blocks.push_back({ tile0 + k, (int32_t)p, (int32_t)std::min<int64_t>(TRAJ_BLOCK_TILES, nt - k) });
-            tile0 += nt;
-        }
-        first[(size_t)n_paths] = (int64_t)blocks.size();
-        if (tile0 != pt.dt.n_tiles) return fail(FCPP_ESIZE, "trajectory blocks do not match the tile table");
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    tr.n_blocks = (int64_t)blocks.size();
-    HIPCHK(tr.blocks.upload(blocks, st));
-    HIPCHK(tr.block_first.upload(first, st));
-    HIPCHK(tr.agg.alloc((size_t)pt.dt.n_tiles));
-    HIPCHK(tr.pre.alloc((size_t)pt.dt.n_tiles));
-    HIPCHK(tr.blk.alloc((size_t)tr.n_blocks));
-    HIPCHK(tr.cin.alloc((size_t)tr.n_blocks));
-    HIPCHK(tr.path_first.alloc((size_t)n_paths));
-    HIPCHK(hipStreamSynchronize(st));      // (the staging vectors die here)
-    tr.built = true;
-    return FCPP_OK;
-}
-
-int trajectory_paths(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, const double *x,
-                     const double *y, const double *v, const uint32_t *fs, double *s, double *t, double *heading, double *totals)
-{
-    DevTiling *dtp = nullptr;
-    int rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
-    if (rc) return rc;
-    DevTiling &dt = *dtp;
-    hipStream_t st = c->stream;
-    rc = ensure_traj(*c->paths_cache, st);
-    if (rc) return rc;
-    TrajTables &tr = c->paths_cache->traj;
-    LAUNCHCHK(launch_traj_tiles(st, dt.n_tiles, dt.tiles.p, dt.paths.p, x, y, v, tr.agg.p));
-    LAUNCHCHK(launch_traj_blocks(st, tr.n_blocks, tr.blocks.p, tr.agg.p, tr.pre.p, tr.blk.p));
-    LAUNCHCHK(launch_traj_paths(st, n_paths, tr.block_first.p, tr.blk.p, tr.cin.p, tr.path_first.p, totals));
-    if (s || t || heading)
-        LAUNCHCHK(launch_traj_apply(st, dt.n_tiles, dt.tiles.p, dt.paths.p, dt.tile_first.p, tr.block_first.p, x, y, v, fs, tr.pre.p, tr.cin.p,
-                                    tr.path_first.p, s, t, heading));
-    HIPCHK(hipStreamSynchronize(st));
-    return FCPP_OK;
-}
-
-// CSR offsets on the host: the caller's copy or read back; checked like make_tiling checks the paths' (total < 0: any total)
-int host_offsets(fcpp_ctx *c, int64_t n, const int64_t *dev, const int64_t *host, int64_t total, const char *what, std::vector<int64_t> &out)
-{
-    out.assign((size_t)n + 1, 0);
-    if (host) memcpy(out.data(), host, out.size() * sizeof(int64_t));
-    else {
-        HIPCHK(hipMemcpyAsync(out.data(), dev, out.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (out[0] != 0 || (total >= 0 && out.back() != total)) return fail(FCPP_ESIZE, std::string(what) + " do not span [0, total]");
-    for (int64_t p = 0; p < n; ++p)
-        if (out[(size_t)p + 1] < out[(size_t)p]) return fail(FCPP_ESIZE, std::string(what) + " must be non-decreasing");
-    return FCPP_OK;
-}
-}  // namespace
-
-int fcpp_trajectory(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x, const double *y, const double *v,
-                    const uint32_t *flagseg, double *s, double *t, double *heading, double *totals, const int64_t *offsets_host)
-{
-    if (!c || (!offsets && !offsets_host) || (total > 0 && (!x || !y || !v))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    return trajectory_paths(c, n_paths, offsets, offsets_host, total, x, y, v, flagseg, s, t, heading, totals);
-}
-
 int fcpp_batch_trajectory(fcpp_batch *b, const double *x, const double *y, const double *v, const uint32_t *flagseg, double *s, double *t,
                           double *heading, double *totals)
 {
@@ -1747,238 +1366,6 @@ int fcpp_batch_trajectory(fcpp_batch *b, const double *x, const double *y, const
     b->note_stream(st);
     HIPCHK(b->wait_setup(st));
     return trajectory_paths(b->ctx, 2 * b->n_fields, nullptr, offs.data(), b->hp.total_points, x, y, v, flagseg, s, t, heading, totals);
-}
-
-int fcpp_trajectory_counts(fcpp_ctx *c, int64_t n_paths, const double *totals, double dt, int include_end, int64_t *out_offsets,
-                           int64_t *out_offsets_host)
-{
-    if (!c || !out_offsets || (n_paths > 0 && !totals)) return fail(FCPP_EINVAL, "bad arguments");
-    if (!(dt > 0.0) || !isfinite(dt)) return fail(FCPP_EINVAL, "dt must be positive");
-    if (n_paths < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    DevBuf<int64_t> err;
-    HIPCHK(err.alloc(1));
-    LAUNCHCHK(launch_traj_counts(st, n_paths, totals, dt, include_end ? 1 : 0, out_offsets, err.p));
-    int64_t bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, err.p, sizeof bad, hipMemcpyDeviceToHost, st));
-    if (out_offsets_host)
-        HIPCHK(hipMemcpyAsync(out_offsets_host, out_offsets, ((size_t)n_paths + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad) return fail(FCPP_ESIZE, "a path's total time is negative or not finite, or it has 2^31 samples or more");
-    return FCPP_OK;
-}
-
-int fcpp_trajectory_sample(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x, const double *y,
-                           const double *v, const double *s, const double *t, const double *heading, const uint32_t *flagseg, double dt,
-                           int include_end, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *vs, double *ss,
-                           double *hs, uint32_t *flagseg_s, int64_t *src_index, const int64_t *offsets_host, const int64_t *out_offsets_host)
-{
-    if (!c || (!offsets && !offsets_host) || (!out_offsets && !out_offsets_host) || (total > 0 && (!x || !y || !v || !s || !t || !heading)))
-        return fail(FCPP_EINVAL, "bad arguments");
-    if (!(dt > 0.0) || !isfinite(dt)) return fail(FCPP_EINVAL, "dt must be positive");
-    if (n_paths < 0 || total < 0 || total_samples < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    std::vector<int64_t> offs, outs;
-    try {
-        int rc = host_offsets(c, n_paths, offsets, offsets_host, total, "offsets", offs);
-        if (rc == FCPP_OK) rc = host_offsets(c, n_paths, out_offsets, out_offsets_host, total_samples, "out_offsets", outs);
-        if (rc) return rc;
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    for (int64_t p = 0; p < n_paths; ++p)
-        if (outs[(size_t)p + 1] - outs[(size_t)p] > INT32_MAX) return fail(FCPP_ESIZE, "a path has 2^31 samples or more");
-    // the kernel reads both tables on the device: a caller that brought only host copies gets them uploaded
-    DevBuf<int64_t> up;
-    if (!offsets || !out_offsets) {
-        std::vector<int64_t> both(offs);
-        both.insert(both.end(), outs.begin(), outs.end());
-        HIPCHK(up.upload(both, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (!offsets) offsets = up.p;
-        if (!out_offsets) out_offsets = up.p + n_paths + 1;
-    }
-    LAUNCHCHK(launch_traj_sample(st, n_paths, offsets, out_offsets, total_samples, x, y, v, s, t, heading, flagseg, dt, include_end ? 1 : 0, xs, ys,
-                                 vs, ss, hs, flagseg_s, src_index));
-    HIPCHK(hipStreamSynchronize(st));
-    return FCPP_OK;
-}
-
-int fcpp_validate(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *opt, int64_t n_paths, const int64_t *offsets, int64_t total,
-                  const double *x, const double *y, const double *v, const fcpp_polys *field_polys, const fcpp_polys *obstacles,
-                  const int64_t *obstacle_offsets, uint32_t *flags, fcpp_field_stats *stats, const int64_t *offsets_host)
-{
-    if (!c || !veh || !opt || (!offsets && !offsets_host) || !stats || (total > 0 && (!x || !y || !v || !flags))) return fail(FCPP_EINVAL, "bad arguments");
-    if (!isfinite(opt->geofence_tol)) return fail(FCPP_EINVAL, "geofence_tol must be finite");
-    std::string err;
-    int rc = validate_polys(field_polys, err);
-    if (rc == FCPP_OK) rc = validate_polys(obstacles, err);
-    if (rc != FCPP_OK) return fail(rc, err);
-    if (field_polys && field_polys->n_polys != n_paths) return fail(FCPP_ESIZE, "field_polys must hold one polygon per path");
-    const int64_t n_obst = obstacles ? obstacles->n_polys : 0;
-    if (obstacle_offsets) {
-        if (obstacle_offsets[0] < 0 || obstacle_offsets[n_paths] > n_obst) return fail(FCPP_ESIZE, "obstacle_offsets outside the obstacle table");
-        for (int64_t p = 0; p < n_paths; ++p)
-            if (obstacle_offsets[p + 1] < obstacle_offsets[p]) return fail(FCPP_ESIZE, "obstacle_offsets must be non-decreasing");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    DevTiling *dtp = nullptr;
-    rc = make_tiling(c, n_paths, offsets, offsets_host, total, &dtp);
-    if (rc) return rc;
-    DevTiling &dt = *dtp;
-    DevConst cst = const_from_vehicle(*veh);
-    hipStream_t st = c->stream;
-    // curvature, a_lat flags and the metrics of fcpp_verify; then the polygon tests
-    DevBuf<double> kap, vtmp;
-    HIPCHK(kap.alloc((size_t)total));
-    HIPCHK(vtmp.alloc((size_t)total));
-    LAUNCHCHK(launch_curv_clamp(st, dt.n_tiles, dt.tiles.p, dt.paths.p, cst, 0, x, y, v, vtmp.p, kap.p, nullptr));
-    DevObstacles none = { nullptr, nullptr, nullptr, nullptr };
-    LAUNCHCHK(launch_validate(st, dt.n_tiles, dt.tiles.p, dt.paths.p, nullptr, cst, none, x, y, kap.p, v, nullptr, dt.partial.p));
-    { const int rrc = reduce_paths(c, st, dt, stats); if (rrc) return rrc; }
-    // the polygon tables: one upload (field vertices, obstacle vertices, their offsets, the per-path obstacle ranges)
-    const int64_t nfv = field_polys && n_paths > 0 ? field_polys->offsets[n_paths] : 0, nov = n_obst > 0 ? obstacles->offsets[n_obst] : 0;
-    std::vector<double> hv;
-    std::vector<int64_t> hi;
-    try {
-        hv.reserve((size_t)(2 * (nfv + nov)));
-        if (nfv) { hv.insert(hv.end(), field_polys->x, field_polys->x + nfv); hv.insert(hv.end(), field_polys->y, field_polys->y + nfv); }
-        if (nov) { hv.insert(hv.end(), obstacles->x, obstacles->x + nov); hv.insert(hv.end(), obstacles->y, obstacles->y + nov); }
-        if (field_polys) hi.insert(hi.end(), field_polys->offsets, field_polys->offsets + n_paths + 1);
-        if (n_obst) hi.insert(hi.end(), obstacles->offsets, obstacles->offsets + n_obst + 1);
-        if (obstacle_offsets && n_obst) hi.insert(hi.end(), obstacle_offsets, obstacle_offsets + n_paths + 1);
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    DevBuf<double> dv;
-    DevBuf<int64_t> di;
-    HIPCHK(dv.upload(hv, st));
-    HIPCHK(di.upload(hi, st));
-    const double *fx = dv.p, *fy = dv.p ? dv.p + nfv : nullptr, *ox = dv.p ? dv.p + 2 * nfv : nullptr, *oy = dv.p ? dv.p + 2 * nfv + nov : nullptr;
-    const int64_t *foff = field_polys ? di.p : nullptr;
-    const int64_t *ooff = n_obst ? di.p + (field_polys ? n_paths + 1 : 0) : nullptr;
-    const int64_t *orng = (obstacle_offsets && n_obst) ? ooff + n_obst + 1 : nullptr;
-    LAUNCHCHK(launch_validate_polys(st, dt.n_tiles, dt.tiles.p, dt.paths.p, foff, fx, fy, field_polys ? n_paths : 0, ooff, ox, oy, n_obst, orng,
-                                    opt->geofence_tol, cst.a_lat, x, y, kap.p, v, flags, stats));
-    HIPCHK(hipStreamSynchronize(st));      // (the staging vectors die here)
-    return FCPP_OK;
-}
-
-int fcpp_straight_segments(fcpp_ctx *c, int64_t n_seg, const double *seg, int32_t n_points, double *out)
-{
-    if (!c || n_seg < 0 || n_points < 1 || (n_seg > 0 && (!seg || !out))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_straight(c->stream, n_seg, seg, n_points, nullptr, out));
-    return FCPP_OK;
-}
-
-int fcpp_corner_turns(fcpp_ctx *c, const fcpp_vehicle *veh, int64_t n, const double *corners, const int32_t *ci, const int32_t *rev,
-                      double L, double H, int32_t stride, double *out, int32_t *counts)
-{
-    if (!c || !veh || n < 0 || (n > 0 && (!corners || !ci || !rev || !out || !counts))) return fail(FCPP_EINVAL, "bad arguments");
-    const double R = veh->min_turn_radius;
-    if (!(R > 0)) return fail(FCPP_EINVAL, "min_turn_radius must be positive");
-    const int64_t need = 15 + std::max<int64_t>(10, (int64_t)(3.0 * R / 0.5));
-    if (stride < need) return fail(FCPP_ESIZE, "stride too small for 15 + max(10, int(3R / 0.5)) points");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_corner_turns(c->stream, n, corners, ci, rev, R, L, H, stride, out, counts));
-    return FCPP_OK;
-}
-
-int fcpp_fresnel(fcpp_ctx *c, int64_t n, const double *t, double *cc, double *ss)
-{
-    if (!c || n < 0 || (n > 0 && (!t || !cc || !ss))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_fresnel(c->stream, n, t, cc, ss));
-    return FCPP_OK;
-}
-
-int fcpp_distance_matrix(fcpp_ctx *c, int32_t n, const double *x, const double *y, double *D)
-{
-    if (!c || n < 0 || n > 65535 || (n > 0 && (!x || !y || !D))) return fail(FCPP_EINVAL, "bad arguments (0 <= n <= 65535)");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_distance_matrix(c->stream, n, x, y, D));
-    return FCPP_OK;
-}
-
-int fcpp_best_connections(fcpp_ctx *c, int64_t n_pairs, const int64_t *fo, const int64_t *to, const double *fx, const double *fy,
-                          const double *tx, const double *ty, int32_t *bf, int32_t *bt, double *bd)
-{
-    if (!c || n_pairs < 0 || n_pairs > 0x7fffffffLL || (n_pairs > 0 && (!fo || !to || !bf || !bt || !bd)))
-        return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_best_connections(c->stream, n_pairs, fo, to, fx, fy, tx, ty, bf, bt, bd));
-    return FCPP_OK;
-}
-
-// ---- Dubins connectors (fcpp_dubins.hip; the mathematics: fcpp_dubinsfn.h) --------------------------------------------------------
-int fcpp_dubins_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
-                      const double *th, double radius, int32_t *word, double *seg, double *len)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
-    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_dubins_solve(c->stream, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
-    return FCPP_OK;
-}
-
-int fcpp_dubins_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
-                       const double *ty, const double *th, double radius, double *D, int8_t *word)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n_from < 0 || n_to < 0 || n_from > DUB_MAX_POSES || n_to > DUB_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
-    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_dubins_matrix(c->stream, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
-    return FCPP_OK;
-}
-
-int fcpp_dubins_counts(fcpp_ctx *c, int64_t n, const double *len, double spacing, int64_t *out_offsets, int64_t *out_offsets_host)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
-    if (n < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
-    if (!out_offsets || (n > 0 && !len)) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    DevBuf<int64_t> err;
-    HIPCHK(err.alloc(1));
-    LAUNCHCHK(launch_dubins_counts(st, n, len, spacing, out_offsets, err.p));
-    int64_t bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, err.p, sizeof bad, hipMemcpyDeviceToHost, st));
-    if (out_offsets_host) HIPCHK(hipMemcpyAsync(out_offsets_host, out_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad) return fail(FCPP_ESIZE, "a path's length is negative or infinite, or it has 2^31 samples or more");
-    return FCPP_OK;
-}
-
-int fcpp_dubins_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
-                       const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
-                       double *kappas, const int64_t *out_offsets_host)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
-    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
-    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    std::vector<int64_t> outs;
-    try {
-        const int rc = host_offsets(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", outs);
-        if (rc) return rc;
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    for (int64_t p = 0; p < n; ++p)
-        if (outs[(size_t)p + 1] - outs[(size_t)p] > INT32_MAX) return fail(FCPP_ESIZE, "a path has 2^31 samples or more");
-    DevBuf<int64_t> up;         // the kernel reads the table on the device: a caller that brought only a host copy gets it uploaded
-    if (!out_offsets) {
-        HIPCHK(up.upload(outs, st));
-        out_offsets = up.p;
-    }
-    LAUNCHCHK(launch_dubins_sample(st, n, fx, fy, fh, radius, word, seg, spacing, out_offsets, total_samples, xs, ys, hs, kappas));
-    HIPCHK(hipStreamSynchronize(st));
-    return FCPP_OK;
 }
 
 int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const double *D, int32_t *routes, int32_t *best_route,

@@ -1,4 +1,4 @@
-// fcpp_device.h -- interface between the C-ABI glue (fcpp_api.cpp) and the kernels (fcpp_kernels.hip)
+// fcpp_device.h -- interface between the C-ABI glue (fcpp_api.cpp, fcpp_paths.cpp) and the kernels (fcpp_kernels.hip)
 #pragma once
 #include <stdlib.h>
 #include <hip/hip_runtime_api.h>

@@ -1,4 +1,4 @@
-// fcpp_dubins.h -- interface between the C-ABI glue (fcpp_api.cpp) and the Dubins kernels (fcpp_dubins.hip): the batched shortest-path
+// fcpp_dubins.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the Dubins kernels (fcpp_dubins.hip): the batched shortest-path
 // solve, the all-pairs transit matrix, and the sampler of solved paths at a fixed spacing.  The mathematics is fcpp_dubinsfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -15,10 +15,11 @@
 
 #include "fcpp_dubins.h"
 #include "fcpp_dubinsfn.h"
+#include "fcpp_samplefn.h"
 
 namespace fcpp {
 
-static constexpr int DBLOCK = 256, DNWAVE = DBLOCK / 64;
+static constexpr int DBLOCK = 256;
 static_assert(DUB_COLS == DBLOCK && DUB_ROWS <= DBLOCK, "a lane per column; the first DUB_ROWS lanes prepare the rows");
 
 #define DUB_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -64,52 +65,9 @@ __global__ __launch_bounds__(DBLOCK) void k_dubins_matrix(int64_t n_from, const 
     }
 }
 
-// K_p = floor(total_p / spacing) + 1 samples at k * spacing, and one more AT total_p when the last of them lies before it; a NaN path has
-// one sample.  One workgroup walks the paths 256 at a time (an integer scan: exact in any order), like k_traj_counts.
-__global__ __launch_bounds__(DBLOCK) void k_dubins_counts(int64_t n, const double *__restrict__ len, double spacing,
-                                                          int64_t *__restrict__ out_offsets, int64_t *__restrict__ err)
-{
-    __shared__ int64_t sh[DNWAVE];
-    __shared__ int64_t carry_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int64_t bad = 0;
-    if (tid == 0) carry_sh = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += DBLOCK) {
-        const int64_t p = base + tid;
-        int64_t K = 0;
-        if (p < n) {
-            const double T = len[p], q = floor(T / spacing);
-            if (T != T) K = 1;
-            else if (!(T >= 0.0) || !(q < 2147483646.0)) ++bad;
-            else {
-                K = (int64_t)q + 1;
-                if ((double)(K - 1) * spacing < T) ++K;
-            }
-        }
-        int64_t inc = K;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t pv = __shfl_up(inc, o);
-            if (lane >= o) inc += pv;
-        }
-        if (lane == 63) sh[wave] = inc;
-        __syncthreads();
-        int64_t pre = carry_sh, tot = 0;
-        for (int w = 0; w < DNWAVE; ++w) { if (w < wave) pre += sh[w]; tot += sh[w]; }
-        if (p < n) out_offsets[p] = pre + inc - K;
-        __syncthreads();
-        if (tid == 0) carry_sh += tot;
-        __syncthreads();
-    }
-    if (tid == 0) out_offsets[n] = carry_sh;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
-    __syncthreads();
-    if (lane == 0) sh[wave] = bad;
-    __syncthreads();
-    if (tid == 0) { int64_t b = 0; for (int w = 0; w < DNWAVE; ++w) b += sh[w]; err[0] = b; }
-}
+// The sample counts and offsets: k_sample_counts (fcpp_samplefn.h) over the paths' lengths; the last sample lies AT the path's end, a
+// NaN path has one sample.
+struct DubinsLength { const double *len; __device__ double operator()(int64_t p) const { return len[p]; } };
 
 // A lane per output sample: its path by bisection of out_offsets, then dubins_pose_at from the start of the segment that holds
 // s = k * spacing (one multiplication, never accumulated); the last sample of a path lies AT its total.  32 B written per sample.
@@ -122,12 +80,8 @@ __global__ __launch_bounds__(DBLOCK) void k_dubins_sample(int64_t n, const doubl
 {
     const int64_t q = (int64_t)blockIdx.x * DBLOCK + threadIdx.x;
     if (q >= total_samples) return;
-    int64_t lo = 0, hi = n;                             // the last path p with out_offsets[p] <= q
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (out_offsets[mid] <= q) lo = mid; else hi = mid;
-    }
-    const int64_t p = lo, k = q - out_offsets[p], K = out_offsets[p + 1] - out_offsets[p];
+    int64_t p, k, K;
+    sample_path(out_offsets, n, q, p, k, K);
     const double s0 = seg[3 * p], s1 = seg[3 * p + 1], s2 = seg[3 * p + 2], total = (s0 + s1) + s2;
     double s = (double)k * spacing;
     if (k == K - 1 || s > total) s = total;             // (K - 1) * spacing <= total: the last sample is the path's end either way
@@ -161,7 +115,7 @@ int launch_dubins_matrix(hipStream_t st, int64_t n_from, const double *fx, const
 
 int launch_dubins_counts(hipStream_t st, int64_t n, const double *len, double spacing, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL(k_dubins_counts, dim3(1), dim3(DBLOCK), 0, st, n, len, spacing, out_offsets, err);
+    hipLaunchKernelGGL((k_sample_counts<DBLOCK, DubinsLength>), dim3(1), dim3(DBLOCK), 0, st, n, DubinsLength{ len }, spacing, 1, 1, out_offsets, err);
     DUB_LAUNCH_CHECK();
     return 0;
 }

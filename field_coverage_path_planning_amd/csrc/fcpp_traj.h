@@ -1,4 +1,4 @@
-// fcpp_traj.h -- interface between the C-ABI glue (fcpp_api.cpp) and the trajectory kernels (fcpp_traj.hip):
+// fcpp_traj.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the trajectory kernels (fcpp_traj.hip):
 // per-point arc length, time stamp and heading of caller-supplied paths (fcpp_trajectory) and their sampling at a fixed time step
 // (fcpp_trajectory_counts / fcpp_trajectory_sample).
 #pragma once

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_samplefn.h"
 #include "fcpp_traj.h"
 
 namespace fcpp {
@@ -253,51 +254,8 @@ __global__ __launch_bounds__(TBLOCK) void k_traj_apply(const DevTile *__restrict
 }
 
 // ---- fixed-rate sampling ----------------------------------------------------------------------------------------------------------
-// K_p = floor(T_p / dt) + 1 samples at k * dt, and one more AT T_p when include_end is set and the last of them lies before T_p.
-// One workgroup walks the paths 256 at a time (an integer scan: exact in any order).
-__global__ __launch_bounds__(TBLOCK) void k_traj_counts(int64_t n_paths, const double *__restrict__ totals, double dt, int include_end,
-                                                        int64_t *__restrict__ out_offsets, int64_t *__restrict__ err)
-{
-    __shared__ int64_t sh[TNWAVE];
-    __shared__ int64_t carry_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int64_t bad = 0;
-    if (tid == 0) carry_sh = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_paths; base += TBLOCK) {
-        const int64_t p = base + tid;
-        int64_t K = 0;
-        if (p < n_paths) {
-            const double T = totals[2 * p + 1], q = floor(T / dt);
-            if (!(T >= 0.0) || !(q < 2147483646.0)) ++bad;
-            else {
-                K = (int64_t)q + 1;
-                if (include_end && (double)(K - 1) * dt < T) ++K;
-            }
-        }
-        int64_t inc = K;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t pv = __shfl_up(inc, o);
-            if (lane >= o) inc += pv;
-        }
-        if (lane == 63) sh[wave] = inc;
-        __syncthreads();
-        int64_t pre = carry_sh, tot = 0;
-        for (int w = 0; w < TNWAVE; ++w) { if (w < wave) pre += sh[w]; tot += sh[w]; }
-        if (p < n_paths) out_offsets[p] = pre + inc - K;
-        __syncthreads();
-        if (tid == 0) carry_sh += tot;
-        __syncthreads();
-    }
-    if (tid == 0) out_offsets[n_paths] = carry_sh;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
-    __syncthreads();
-    if (lane == 0) sh[wave] = bad;
-    __syncthreads();
-    if (tid == 0) { int64_t b = 0; for (int w = 0; w < TNWAVE; ++w) b += sh[w]; err[0] = b; }
-}
+// The sample counts and offsets: k_sample_counts (fcpp_samplefn.h) over the paths' total times, one more sample AT T_p with include_end.
+struct TrajTime { const double *totals; __device__ double operator()(int64_t p) const { return totals[2 * p + 1]; } };   // (length, time) per path
 
 // A lane per output sample: its path by bisection of out_offsets, its step by bisection of the path's t (non-decreasing by
 // construction): the LAST i with t_i <= T.  Neighbouring lanes land in the same or adjacent steps, so the last levels of the search
@@ -317,12 +275,8 @@ __global__ __launch_bounds__(TBLOCK) void k_traj_sample(int64_t n_paths, const i
 {
     const int64_t q = (int64_t)blockIdx.x * TBLOCK + threadIdx.x;
     if (q >= total_samples) return;
-    int64_t lo = 0, hi = n_paths;                       // the last path p with out_offsets[p] <= q
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (out_offsets[mid] <= q) lo = mid; else hi = mid;
-    }
-    const int64_t p = lo, k = q - out_offsets[p], K = out_offsets[p + 1] - out_offsets[p];
+    int64_t p, k, K;
+    sample_path(out_offsets, n_paths, q, p, k, K);
     const int64_t a = offsets[p], n = offsets[p + 1] - a;
     if (n <= 0) {                                       // a path without points has no trajectory: its sample says so
         const double nan = __builtin_nan("");
@@ -398,7 +352,7 @@ int launch_traj_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, con
 
 int launch_traj_counts(hipStream_t st, int64_t n_paths, const double *totals, double dt, int include_end, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL(k_traj_counts, dim3(1), dim3(TBLOCK), 0, st, n_paths, totals, dt, include_end, out_offsets, err);
+    hipLaunchKernelGGL((k_sample_counts<TBLOCK, TrajTime>), dim3(1), dim3(TBLOCK), 0, st, n_paths, TrajTime{ totals }, dt, include_end, 0, out_offsets, err);
     TRAJ_LAUNCH_CHECK();
     return 0;
 }

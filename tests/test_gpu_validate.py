@@ -101,7 +101,7 @@ def test_bad_arguments_are_refused():
 
 def test_one_long_path_statistics_through_the_sliced_reduction():
     """A single path of 1.2 million points (2400 tiles): the standalone operators reduce it over 64 workgroups and join (reduce_paths,
-    csrc/fcpp_api.cpp) instead of through one wavefront (1.2 ms for cfg3's path).  The same points as TWO paths take the plain reduction:
+    csrc/fcpp_paths.cpp) instead of through one wavefront (1.2 ms for cfg3's path).  The same points as TWO paths take the plain reduction:
     lengths agree to rounding once the segment across the cut is added, maxima and counts up to the two points at the cut."""
     veh = E.make_vehicle()
     b = E.Batch([E.FieldSpec(field_length=900.0, field_width=420.0)], veh, E.make_options(1, 0.1))
