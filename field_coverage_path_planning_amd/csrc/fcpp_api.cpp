@@ -21,6 +21,7 @@
 #include "fcpp_ga.h"
 #include "fcpp_devplan.h"
 #include "fcpp_dubinsfn.h"
+#include "fcpp_rsfn.h"
 #include "fcpp_parallel.h"
 
 using namespace fcpp;
@@ -1658,6 +1659,23 @@ int fcpp_debug_dubins(int64_t n, const double *fx, const double *fy, const doubl
         dubins_solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s0, s1, s2, tot);
         if (word) word[i] = w;
         if (seg) { seg[3 * i] = s0; seg[3 * i + 1] = s1; seg[3 * i + 2] = s2; }
+        if (len) len[i] = tot;
+    }
+    return FCPP_OK;
+}
+
+int fcpp_debug_rs(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
+                  double radius, int32_t *word, double *seg, double *len)
+{
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        int w;
+        double s[5], tot;
+        rs_solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s, tot);
+        if (word) word[i] = w;
+        if (seg) for (int k = 0; k < 5; ++k) seg[5 * i + k] = s[k];
         if (len) len[i] = tot;
     }
     return FCPP_OK;

@@ -1,5 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
-// caller-supplied paths, the Dubins connectors, the two fixed-step samplers and the small stateless operators.  Like fcpp_api.cpp:
+// caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers and the small stateless
+// operators.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -9,6 +10,7 @@
 
 #include "fcpp_api_internal.h"
 #include "fcpp_dubins.h"
+#include "fcpp_rs.h"
 #include "fcpp_traj.h"
 
 using namespace fcpp;
@@ -149,7 +151,7 @@ int ensure_traj(PathTiling &pt, hipStream_t st)
     return FCPP_OK;
 }
 
-// ---- the fixed-step samplers (fcpp_samplefn.h): what fcpp_trajectory_counts / _sample and fcpp_dubins_counts / _sample share ----------
+// ---- the fixed-step samplers (fcpp_samplefn.h): what fcpp_trajectory_, fcpp_dubins_ and fcpp_rs_counts / _sample share ----------
 // A *_counts entry behind its argument checks: launch(stream, err) fills out_offsets and the error word; both come back, the stream is
 // drained, a bad path is FCPP_ESIZE with the entry's message.
 template <class Launch>
@@ -455,6 +457,59 @@ int fcpp_dubins_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *f
     const int rc = outs.get(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", true);
     if (rc) return rc;
     LAUNCHCHK(launch_dubins_sample(c->stream, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+// ---- Reeds-Shepp connectors (fcpp_rs.hip; the mathematics: fcpp_rsfn.h) -----------------------------------------------------------
+int fcpp_rs_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
+                  const double *th, double radius, int32_t *word, double *seg, double *len)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_rs_solve(c->stream, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
+    return FCPP_OK;
+}
+
+int fcpp_rs_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
+                   const double *ty, const double *th, double radius, double *D, int8_t *word)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n_from < 0 || n_to < 0 || n_from > RS_MAX_POSES || n_to > RS_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
+    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_rs_matrix(c->stream, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
+    return FCPP_OK;
+}
+
+int fcpp_rs_counts(fcpp_ctx *c, int64_t n, const int32_t *word, const double *seg, double spacing, int64_t *out_offsets, int64_t *out_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    if (!out_offsets || (n > 0 && (!word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
+    return sample_counts(c, n, out_offsets, out_offsets_host, "a path has an infinite segment, or 2^31 samples or more",
+                         [&](hipStream_t st, int64_t *err) { return launch_rs_counts(st, n, word, seg, spacing, out_offsets, err); });
+}
+
+int fcpp_rs_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
+                   const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
+                   double *kappas, int8_t *gears, const int64_t *out_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
+    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    SampleOffsets outs;
+    const int rc = outs.get(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", true);
+    if (rc) return rc;
+    LAUNCHCHK(launch_rs_sample(c->stream, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas, gears));
     HIPCHK(hipStreamSynchronize(c->stream));
     return FCPP_OK;
 }

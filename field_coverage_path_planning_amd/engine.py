@@ -463,7 +463,7 @@ class BatchResult:
         return _sample(self.batch.ctx, self.x, self.y, self.v, self.flagseg, self.path_offsets(), None, (s, t, h, totals.view(-1, 2)), dt, include_end)
 
 
-    def drivable_connectors(self, radius=None, spacing=0.5, start_headings=None, end_headings=None):
+    def drivable_connectors(self, radius=None, spacing=0.5, start_headings=None, end_headings=None, reversing=False):
         """Connectors a vehicle with a turning radius can drive, in place of the reference's straight lines (MLP:1313-1355): per field up to
         three Dubins paths (fcpp_dubins_solve / _counts / _sample) --
           0 approach:  parking pose -> the first point of the headland path (`approach_to`) with that point's heading; fields with a kept start point
@@ -473,7 +473,11 @@ class BatchResult:
         default the direction of the reference's straight connector.  The poses on the coverage path are gathered on the device from the batch
         arrays and from trajectory()'s headings.  Fields that raised have no connectors.
         -> dict: 'x', 'y', 'heading', 'kappa' (device, one entry per sample), 'offsets' (device) / 'offsets_host' (numpy): CSR over the
-        connectors, 'field' and 'kind' (numpy, per connector, sorted by field then kind), 'length', 'word', 'from_poses', 'to_poses' (device)."""
+        connectors, 'field' and 'kind' (numpy, per connector, sorted by field then kind), 'length', 'word', 'from_poses', 'to_poses' (device).
+        reversing: the same three connectors as Reeds-Shepp paths (fcpp_rs_solve / _counts / _sample) for a vehicle that also backs up: never
+        longer, and a three-point turn where the swaths lie closer than two radii.  The dict gains 'gear' (int8 per sample: +1 forward, -1
+        reverse; every cusp is two samples with one pose and opposite gears), 'seg' has five signed lengths and 'word' indexes the 48-word
+        table of include/fcpp.h."""
         torch = _torch()
         b = self.batch
         a = b.info.array
@@ -513,7 +517,7 @@ class BatchResult:
         dp_pose = torch.cat((park_d, torch.where(given, heads_d, dp_dir)[:, None]), dim=1)
         frm = torch.where(is_ap, ap_pose, frm)
         to = torch.where(is_dp, dp_pose, to)
-        out = _dubins_paths(b.ctx, frm, to, R, spacing)
+        out = _rs_paths(b.ctx, frm, to, R, spacing) if reversing else _dubins_paths(b.ctx, frm, to, R, spacing)
         out.update(field=field, kind=kind, from_poses=frm, to_poses=to, radius=R)
         return out
 
@@ -1064,6 +1068,76 @@ def dubins_paths(from_poses, to_poses, radius, spacing, device=None):
     length k * spacing, its last sample is the path's end.  kappa: +1/radius on left arcs, -1/radius on right arcs, 0 on the straight."""
     o = _dubins_paths(get_context(device), from_poses, to_poses, radius, spacing)
     return o['x'], o['y'], o['heading'], o['kappa'], o['offsets']
+
+
+def _rs_solve(ctx, f, t, radius):
+    torch = _torch()
+    n = int(f[0].numel())
+    if int(t[0].numel()) != n:
+        raise ValueError('from_poses and to_poses must hold the same number of poses')
+    dev = f[0].device
+    word = torch.empty(n, dtype=torch.int32, device=dev)
+    seg = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    length = torch.empty(n, dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_rs_solve(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
+                                  _ptr(word), _ptr(seg), _ptr(length)))
+    return word, seg, length
+
+
+def rs_solve(from_poses, to_poses, radius, device=None):
+    """Shortest Reeds-Shepp path (forward and reverse motion) of every pair from_poses[i] -> to_poses[i] (fcpp_rs_solve) for the turning
+    radius `radius` [m].  Poses: (n, 3) arrays or tensors (x, y, heading [rad]).  -> (word, seg, length) device tensors: the winning word
+    (0 .. 47, the table of include/fcpp.h: 4 * base + flip + 2 * mirror; -1 for a pair with a non-finite input), its five SIGNED segment
+    lengths [m] (n, 5) -- positive forward, negative reverse, unused ones 0 -- and the sum of their magnitudes."""
+    ctx = get_context(device)
+    dev = _torch().device('cuda', ctx.device)
+    return _rs_solve(ctx, _poses(from_poses, dev), _poses(to_poses, dev), radius)
+
+
+def rs_matrix(from_poses, to_poses, radius, want_words=False, device=None):
+    """The transit matrix of a vehicle that reverses: D[i][j] = shortest Reeds-Shepp length from pose i to pose j (fcpp_rs_matrix),
+    (n_from, n_to) float64 on the device, the layout ga_fitness / ga_evolve take.  A metric: symmetric (to rounding) when both lists are
+    the same poses, with a zero diagonal.  want_words: also the winning words, (n_from, n_to) int8."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    nf, nt = int(f[0].numel()), int(t[0].numel())
+    D = torch.empty((nf, nt), dtype=torch.float64, device=dev)
+    W = torch.empty((nf, nt), dtype=torch.int8, device=dev) if want_words else None
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_rs_matrix(ctx.handle, nf, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), nt, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
+                                   _ptr(D), _ptr(W)))
+    return (D, W) if want_words else D
+
+
+def _rs_paths(ctx, from_poses, to_poses, radius, spacing):
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    word, seg, length = _rs_solve(ctx, f, t, radius)
+    n = int(word.numel())
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    L.check(ctx.lib.fcpp_rs_counts(ctx.handle, n, _ptr(word), _ptr(seg), float(spacing), _ptr(off), _host_ptr(off_h)))
+    m = int(off_h[-1])
+    out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'heading', 'kappa')}
+    out['gear'] = torch.empty(m, dtype=torch.int8, device=dev)
+    L.check(ctx.lib.fcpp_rs_sample(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing),
+                                   _ptr(off), m, _ptr(out['x']), _ptr(out['y']), _ptr(out['heading']), _ptr(out['kappa']), _ptr(out['gear']),
+                                   _host_ptr(off_h)))
+    out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
+    return out
+
+
+def rs_paths(from_poses, to_poses, radius, spacing, device=None):
+    """The shortest Reeds-Shepp paths of the pairs, sampled every `spacing` metres PER GEAR RUN (fcpp_rs_solve + _counts + _sample) ->
+    (x, y, heading, kappa, gear, offsets) device tensors: path p owns the samples offsets[p] .. offsets[p + 1]; its first sample is its start
+    pose, its last the goal; within a run sample k lies k * spacing from the run's start and the run's last sample is its end, so every cusp
+    appears twice, with the same pose and the opposite gear.  heading: the vehicle's (against the motion in reverse); gear: int8 +1 / -1."""
+    o = _rs_paths(get_context(device), from_poses, to_poses, radius, spacing)
+    return o['x'], o['y'], o['heading'], o['kappa'], o['gear'], o['offsets']
 
 
 def _polys(polygons):

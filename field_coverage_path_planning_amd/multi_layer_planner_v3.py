@@ -294,13 +294,16 @@ class TwoLayerPathPlannerV37:
                          'src_index': host['src_index'][sl] - first}
         return out
 
-    def drivable_connectors(self, start_heading: Optional[float] = None, end_heading: Optional[float] = None, spacing: float = 0.5) -> Dict:
+    def drivable_connectors(self, start_heading: Optional[float] = None, end_heading: Optional[float] = None, spacing: float = 0.5,
+                            reversing: bool = False) -> Dict:
         """Connectors a vehicle with min_turn_radius can drive (not in the reference, whose approach / departure paths are straight lines,
-        MLP:1313-1355): shortest forward-only Dubins paths sampled every `spacing` metres --
+        MLP:1313-1355): shortest forward-only Dubins paths -- with reversing=True shortest Reeds-Shepp paths -- sampled every `spacing` metres --
         'approach_path' (start_point -> first headland point, arriving with the path's heading), 'link_path' (last point of the main work ->
         first point of the headland) and 'departure_path' (last headland point -> end_point), each an N x 2 numpy array or None, with
         '..._heading' [rad], '..._curvature' [1/m: +1/R left, -1/R right, 0 straight] per sample and '..._length' [m].
         start_heading / end_heading: the vehicle's heading at the parking points; default along the reference's straight connector.
+        reversing: Reeds-Shepp paths instead (the vehicle may back up: never longer, a three-point turn between close swaths), and
+        '..._gear' per sample (+1 forward, -1 reverse; a cusp is two samples with one pose and opposite gears).
         plan_complete_coverage() and its result are not touched."""
         if self._info.status != L.OK:
             raise ValueError(f"unsupported field (libfcpp status {self._info.status})")
@@ -309,8 +312,9 @@ class TwoLayerPathPlannerV37:
         bufs = self._bufs if self._bufs is not None else self._batch.alloc()
         res = self._batch.run(bufs)
         con = res.drivable_connectors(None, spacing, None if start_heading is None else [float(start_heading)],
-                                      None if end_heading is None else [float(end_heading)])
+                                      None if end_heading is None else [float(end_heading)], reversing=bool(reversing))
         off = con['offsets_host']
+        gear = con['gear'].cpu().numpy() if reversing else None
         x, y, h, k = (con[n].cpu().numpy() for n in ('x', 'y', 'heading', 'kappa'))
         length = con['length'].cpu().numpy()
         out = {}
@@ -318,10 +322,14 @@ class TwoLayerPathPlannerV37:
             at = np.flatnonzero(con['kind'] == kind)
             if len(at) == 0:
                 out.update({name + '_path': None, name + '_heading': None, name + '_curvature': None, name + '_length': None})
+                if reversing:
+                    out[name + '_gear'] = None
                 continue
             sl = slice(off[at[0]], off[at[0] + 1])
             out.update({name + '_path': np.column_stack([x[sl], y[sl]]), name + '_heading': h[sl].copy(), name + '_curvature': k[sl].copy(),
                         name + '_length': float(length[at[0]])})
+            if reversing:
+                out[name + '_gear'] = gear[sl].copy()
         return out
 
     def close(self):

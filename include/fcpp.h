@@ -444,7 +444,7 @@ int fcpp_best_connections(fcpp_ctx *ctx, int64_t n_pairs, const int64_t *from_of
  * Build-defined.  What they replace: the reference's straight 50-point approach / departure lines (MLP:1313-1355, "简单的直线连接"), the
  * missing link between main work and headland, and the Euclidean transit cost of the scheduler inputs above; its roadmap asks for them
  * (doc/两层路径规划器 - 深度优化和改进路线图.md section 1.2: shortest path between two poses, sampled at a spacing).  Forward motion only
- * (Reeds-Shepp paths, which reverse, are not provided).
+ * (paths that also reverse: the Reeds-Shepp connectors below).
  * A pose is (x, y, heading): metres, and radians as fcpp_trajectory writes them (any finite value with |heading| <= 1e5).  All arrays are
  * device pointers, SoA float64; `radius` > 0 is ONE scalar per call.  Words: 0 LSL, 1 LSR, 2 RSL, 3 RSR, 4 RLR, 5 LRL (L = left /
  * counter-clockwise arc, R = right arc, S = straight).  For each pair all six closed forms (Dubins 1957; Shkel & LaValle 2001) are evaluated
@@ -489,6 +489,63 @@ int fcpp_dubins_counts(fcpp_ctx *ctx, int64_t n, const double *len_dev, double s
 int fcpp_dubins_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev, double radius,
                        const int32_t *word_dev, const double *seg_dev, double spacing, const int64_t *out_offsets_dev, int64_t total_samples,
                        double *xs_dev, double *ys_dev, double *hs_dev, double *kappas_dev, const int64_t *out_offsets_host);
+
+/* ---- Reeds-Shepp connectors: the shortest path between two POSES for a vehicle that turns with a radius AND reverses -------------------
+ * Build-defined (the reference's roadmap section 1.2 asks for them beside the Dubins paths; its vehicle already backs up at every outer
+ * headland corner, MLP:1024-1082).  Where two swaths lie closer than two turning radii the forward-only link is a loop of R (pi + 4 g);
+ * the reversing vehicle makes a three-point turn of little more than pi R.  Poses, arrays, radius and errors as for the Dubins entries;
+ * the Dubins range of the headings does NOT carry over: the sine and cosine of the heading DIFFERENCE are taken, so the two headings of a
+ * pair must not differ by more than 1e5 rad -- |heading| <= 5e4 for every pose is always safe.
+ * For each pair all 48 words of Reeds & Shepp (1990) are evaluated -- the base formulas 8.1 - 8.4, 8.7 - 8.11 of the paper under time-flip,
+ * reflection and backwards, on the DIFFERENCE of the two positions rotated into the start frame -- and the shortest feasible one taken; among
+ * equal totals the LOWEST word index wins, so the choice is a function of the inputs alone.
+ * THE WORD TABLE.  word = 4 * base + flip + 2 * mirror; letters L = left / counter-clockwise arc, R = right arc, S = straight; gears + forward,
+ * - reverse:
+ *     base 0  L+ S+ L+        base 3  L+ R- L-        base 6  L+ R- L- R+      base  9  L- S- R- L+
+ *     base 1  L+ S+ R+        base 4  L- R- L+        base 7  L+ R- S- L-      base 10  R- S- R- L+
+ *     base 2  L+ R- L+        base 5  L+ R+ L- R-     base 8  L+ R- S- R-      base 11  L+ R- S- L- R+
+ * flip (bit 0) reverses every gear, mirror (bit 1) swaps L and R: the mirror image of a path has word ^ 2, the path with all gears reversed
+ * word ^ 1.  In bases 7 - 11 the R arcs next to the straight are a quarter circle; in bases 5 and 6 the two middle arcs are equal.
+ * seg: FIVE signed segment lengths in metres per pair, in the order of the word's letters: positive is driven forward, negative in reverse,
+ * an arc's length = radius x its angle in [-pi, pi]; segments the word does not have are exactly 0.
+ * total = (((|seg[0]| + |seg[1]|) + |seg[2]|) + |seg[3]|) + |seg[4]|.
+ * The rules at the edges (csrc/fcpp_rsfn.h, one function for host and device: the same bits on both):
+ *   - every arc angle is reduced into (-pi, pi]; where a word asks for an angle in [0, pi], a reduced value within 2^-43 below 0 is 0 and one
+ *     within 2^-43 above pi is pi (and likewise for [-pi, 0]): an arc that is mathematically 0 but comes out as -1 ulp neither becomes a reverse
+ *     stub nor rules its word out.  The price: the end pose of such a path may be off by up to 2^-43 x (radius + straight) metres;
+ *   - a word's feasibility bound on rho^2 (the computed squared length, in radii, of the vector its formula uses: >= 4, <= 16, >= 8, >= 20 ...)
+ *     holds with a relative band of 2^-48: inside the band the root's or arc cosine's argument is clamped to the edge, beyond it the word is
+ *     infeasible (a last bit may decide which of two words of nearly equal length wins);
+ *   - a vector shorter than 2^-40 radii has no direction and no length (its angle and its length count as 0: the end pose may be off by
+ *     2^-40 x radius metres).  Start == goal exactly: word 0, five zeros, total 0;
+ *   - a pair with a non-finite coordinate difference or heading: word -1, segments and total NaN -- per pair, the call succeeds.
+ * The length is a metric on poses: symmetric, and the matrix of a list against itself has a zero diagonal. */
+/* pair i = (from i -> to i), a lane per pair.  word_dev: n int32; seg_dev: 5 per pair; len_dev: n totals.  Any output may be NULL. */
+int fcpp_rs_solve(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                  const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, int32_t *word_dev,
+                  double *seg_dev, double *len_dev);
+/* The transit matrix of the reversing vehicle: D[i][j] = shortest length from pose i to pose j, row-major n_from x n_to, the layout
+ * fcpp_ga_fitness / fcpp_ga_evolve take.  Entry (i, j) has the bits fcpp_rs_solve gives for that pair.  word_dev: NULL or n_from x n_to
+ * int8.  At most 2^20 poses per side. */
+int fcpp_rs_matrix(fcpp_ctx *ctx, int64_t n_from, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                   int64_t n_to, const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, double *D_dev,
+                   int8_t *word_dev);
+/* Solved paths at a fixed spacing [m], sampled PER GEAR RUN: a run is a maximal stretch of segments of one sign (zero segments aside; at
+ * most three runs, a path of total 0 is one run).  A run of length T_r gets floor(T_r / spacing) + 1 samples at k * spacing from ITS start
+ * (one multiplication, never accumulated), plus one more AT its end when the last of them lies before it.  So every cusp is a sample
+ * twice: as the end of one run and as the start of the next, with the same x, y and heading and the opposite gear.
+ * fcpp_rs_counts: the samples' CSR offsets (n + 1) from the words and segments; a NaN path has one sample.  FCPP_ESIZE: an infinite
+ * segment, a path of 2^31 samples or more.  Synchronises. */
+int fcpp_rs_counts(fcpp_ctx *ctx, int64_t n, const int32_t *word_dev, const double *seg_dev, double spacing, int64_t *out_offsets_dev,
+                   int64_t *out_offsets_host);
+/* Per sample x, y, the VEHICLE's heading in (-pi, pi] (on a reverse run it points against the motion), the signed curvature (+1/radius on
+ * an L arc, -1/radius on an R arc, 0 on the straight) and the gear (int8: +1 forward, -1 reverse; 0 on the one sample of a NaN path),
+ * evaluated from the START OF THE SEGMENT that contains the sample, never from the previous sample: a path gives the same bits alone and
+ * as one path of a batch.  A position at a junction within a run belongs to the segment that starts there.  word_dev / seg_dev as
+ * fcpp_rs_solve wrote them for the same start poses and radius.  Every output may be NULL.  Synchronises. */
+int fcpp_rs_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev, double radius,
+                   const int32_t *word_dev, const double *seg_dev, double spacing, const int64_t *out_offsets_dev, int64_t total_samples,
+                   double *xs_dev, double *ys_dev, double *hs_dev, double *kappas_dev, int8_t *gears_dev, const int64_t *out_offsets_host);
 
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
@@ -547,6 +604,10 @@ int fcpp_debug_math_dev(fcpp_ctx *ctx, int fn, int64_t n, const double *a_dev, c
  * bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
 int fcpp_debug_dubins(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,
                       const double *to_h, double radius, int32_t *word, double *seg, double *len);
+/* fcpp_rs_solve's function (csrc/fcpp_rsfn.h) evaluated on the HOST, on host pointers (seg: 5 per pair): what the device results are
+ * compared with bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
+int fcpp_debug_rs(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,
+                  const double *to_h, double radius, int32_t *word, double *seg, double *len);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch
