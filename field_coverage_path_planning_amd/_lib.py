@@ -163,6 +163,11 @@ PROTOTYPES = [
     ('fcpp_rs_matrix', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP]),
     ('fcpp_rs_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
     ('fcpp_rs_sample', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, C.c_double, _VP, C.c_int64] + [_VP] * 6),
+    ('fcpp_swath_scores', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double, C.c_double, C.c_double]
+     + [_VP] * 4),
+    ('fcpp_swath_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double] + [_VP] * 4),
+    ('fcpp_swath_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double, _VP, C.c_int64]
+     + [_VP] * 6),
     ('fcpp_ga_evolve', C.c_int, [_VP, C.c_int32, C.POINTER(GaConfig), _VP, _VP, _VP, _VP, C.POINTER(GaResult)]),
     ('fcpp_cover_grid', C.c_int, [_VP, C.c_int64, C.POINTER(CoverJob), C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_gather', C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, c_i64_p, _VP, C.c_int]),
@@ -170,6 +175,8 @@ PROTOTYPES = [
     ('fcpp_debug_math_dev', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_debug_dubins', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_rs', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
+    ('fcpp_debug_swaths', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int, C.c_double, C.c_double, C.c_double]
+     + [_VP] * 5 + [C.c_int64] + [_VP] * 6),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
 ]
 

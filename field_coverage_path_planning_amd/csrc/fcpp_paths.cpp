@@ -1,5 +1,5 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
-// caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers and the small stateless
+// caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
 // operators.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
@@ -11,6 +11,8 @@
 #include "fcpp_api_internal.h"
 #include "fcpp_dubins.h"
 #include "fcpp_rs.h"
+#include "fcpp_swath.h"
+#include "fcpp_swathfn.h"
 #include "fcpp_traj.h"
 
 using namespace fcpp;
@@ -187,6 +189,46 @@ struct SampleOffsets {
         return FCPP_OK;
     }
 };
+
+// ---- polygon swaths: what fcpp_swath_scores / _counts / _fill and fcpp_debug_swaths check alike ------------------------------------
+int swath_params(double W, double first, double min_length)
+{
+    if (!(W > 0.0) || !isfinite(W)) return fail(FCPP_EINVAL, "width must be positive and finite");
+    if (!(first >= 0.0) || !(first < W)) return fail(FCPP_EINVAL, "first must lie in [0, width)");
+    if (!(min_length >= 0.0) || !isfinite(min_length)) return fail(FCPP_EINVAL, "min_length must be non-negative and finite");
+    return FCPP_OK;
+}
+
+int swath_sizes(int64_t n, int64_t n_rings, int64_t n_verts, int64_t A)
+{
+    if (n < 0 || n_rings < 0 || n_verts < 0 || A < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    if (A > 0 && n > SWATH_MAX_PAIRS / A) return fail(FCPP_ESIZE, "2^31 (field, angle) pairs or more");
+    return FCPP_OK;
+}
+
+// m angles on the host (the caller's, or read back from the device): finite and within fc_sincos' range
+int swath_angles(fcpp_ctx *c, int64_t m, const double *dev, const double *host)
+{
+    std::vector<double> h;
+    if (!host && m > 0) {
+        try { h.assign((size_t)m, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+        HIPCHK(hipMemcpyAsync(h.data(), dev, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        host = h.data();
+    }
+    for (int64_t j = 0; j < m; ++j)
+        if (!(fabs(host[j]) <= SWATH_MAX_ANGLE)) return fail(FCPP_EINVAL, "angles must be finite, |angle| <= 1e5");
+    return FCPP_OK;
+}
+
+// the two CSR levels of the fields, brought to the host and checked
+int swath_fields(fcpp_ctx *c, int64_t n, const int64_t *ring_dev, const int64_t *ring_host, int64_t n_rings, const int64_t *vert_dev,
+                 const int64_t *vert_host, int64_t n_verts, std::vector<int64_t> &rings, std::vector<int64_t> &verts)
+{
+    int rc = host_offsets(c, n, ring_dev, ring_host, n_rings, "ring_offsets", rings);
+    if (rc == FCPP_OK) rc = host_offsets(c, n_rings, vert_dev, vert_host, n_verts, "vert_offsets", verts);
+    return rc;
+}
 }  // namespace
 
 int fcpp::trajectory_paths(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, const double *x,
@@ -511,6 +553,118 @@ int fcpp_rs_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, c
     if (rc) return rc;
     LAUNCHCHK(launch_rs_sample(c->stream, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas, gears));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+// ---- polygon swaths (fcpp_swath.hip; the rule: fcpp_swathfn.h) --------------------------------------------------------------------
+int fcpp_swath_scores(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                      const double *x, const double *y, int64_t A, const double *angles, double W, double first, double min_length,
+                      int32_t *n_swaths, int32_t *n_lines, double *length, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y)) || (A > 0 && !angles)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = swath_params(W, first, min_length);
+    if (rc == FCPP_OK) rc = swath_sizes(n, n_rings, n_verts, A);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(c, A, angles, nullptr);
+    if (rc) return rc;
+    LAUNCHCHK(launch_swath_count(c->stream, n, A, 0, ring_offsets, vert_offsets, x, y, angles, W, first, min_length, n_swaths, n_lines, length, status));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_swath_counts(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                      const double *x, const double *y, const double *angle, double W, double first, double min_length, int64_t *out_offsets,
+                      int64_t *out_offsets_host, int32_t *n_lines, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!ring_offsets || !vert_offsets || !out_offsets || (n_verts > 0 && (!x || !y)) || (n > 0 && !angle)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = swath_params(W, first, min_length);
+    if (rc == FCPP_OK) rc = swath_sizes(n, n_rings, n_verts, 1);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle, nullptr);
+    if (rc) return rc;
+    DevBuf<int32_t> n_swaths;
+    HIPCHK(n_swaths.alloc((size_t)n));
+    return sample_counts(c, n, out_offsets, out_offsets_host, "the swath counts could not be scanned", [&](hipStream_t st, int64_t *err) {
+        const int e = launch_swath_count(st, n, 1, 1, ring_offsets, vert_offsets, x, y, angle, W, first, min_length, n_swaths.p, n_lines, nullptr, status);
+        return e ? e : launch_swath_offsets(st, n, n_swaths.p, out_offsets, err);
+    });
+}
+
+int fcpp_swath_fill(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                    const double *x, const double *y, const double *angle, double W, double first, double min_length, const int64_t *offsets,
+                    int64_t n_total, double *ax, double *ay, double *bx, double *by, int32_t *line, double *length)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!ring_offsets || !vert_offsets || !offsets || (n_verts > 0 && (!x || !y)) || (n > 0 && !angle)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = swath_params(W, first, min_length);
+    if (rc == FCPP_OK) rc = swath_sizes(n, n_rings, n_verts, 1);
+    if (rc == FCPP_OK && n_total < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle, nullptr);
+    SampleOffsets outs;
+    if (rc == FCPP_OK) rc = outs.get(c, n, offsets, nullptr, n_total, "offsets", true);
+    if (rc) return rc;
+    LAUNCHCHK(launch_swath_fill(c->stream, n, ring_offsets, vert_offsets, x, y, angle, W, first, min_length, outs.dev, ax, ay, bx, by, line, length));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                      const double *y, int64_t A, const double *angles, int per_field, double W, double first, double min_length,
+                      int32_t *n_swaths, int32_t *n_lines, double *length, int32_t *status, int64_t *out_offsets, int64_t cap, double *ax,
+                      double *ay, double *bx, double *by, int32_t *line, double *seg_length)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y)) || (A > 0 && n > 0 && !angles)) return fail(FCPP_EINVAL, "bad arguments");
+    if ((per_field || out_offsets) && A != 1) return fail(FCPP_EINVAL, "per-field angles and records take A = 1");
+    int rc = swath_params(W, first, min_length);
+    if (rc == FCPP_OK) rc = swath_sizes(n, n_rings, n_verts, A);
+    if (rc == FCPP_OK && cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(nullptr, per_field ? n : A, nullptr, angles);
+    if (rc) return rc;
+    std::vector<double> u, w;
+    int64_t at = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t nv = verts[(size_t)rings[(size_t)i + 1]] - verts[(size_t)rings[(size_t)i]];
+        try { u.resize((size_t)nv); w.resize((size_t)nv); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+        if (out_offsets) out_offsets[i] = at;
+        for (int64_t j = 0; j < A; ++j) {
+            const SwathTotals t = swath_field_host(verts.data(), rings[(size_t)i], rings[(size_t)i + 1], x, y, angles[per_field ? i : j], W, first, min_length,
+                                                   u.data(), w.data(), [&](int64_t k, double ua, double ub, double wk, double c, double s, double len) {
+                if (!out_offsets) return;
+                if (at < cap) {
+                    double px, py, qx, qy;
+                    swath_point(ua, wk, c, s, px, py);
+                    swath_point(ub, wk, c, s, qx, qy);
+                    if (ax) ax[at] = px;
+                    if (ay) ay[at] = py;
+                    if (bx) bx[at] = qx;
+                    if (by) by[at] = qy;
+                    if (line) line[at] = (int32_t)k;
+                    if (seg_length) seg_length[at] = len;
+                }
+                ++at;
+            });
+            if (n_swaths) n_swaths[i * A + j] = t.n_swaths;
+            if (n_lines) n_lines[i * A + j] = t.n_lines;
+            if (length) length[i * A + j] = t.length;
+            if (status) status[i * A + j] = t.status;
+        }
+    }
+    if (out_offsets) out_offsets[n] = at;
     return FCPP_OK;
 }
 

@@ -1140,6 +1140,197 @@ def rs_paths(from_poses, to_poses, radius, spacing, device=None):
     return o['x'], o['y'], o['heading'], o['kappa'], o['gear'], o['offsets']
 
 
+# ---- swaths of any polygon field (fcpp_swath_scores / _counts / _fill; the rule: include/fcpp.h) --------------------------------------
+@dataclass
+class PolygonFields:
+    """polygon_fields(): n fields as the two-level CSR of the library, on the device"""
+    ring_offsets: object        # (n + 1) int64: fields -> rings
+    vert_offsets: object        # (n_rings + 1) int64: rings -> vertices
+    x: object                   # (n_verts) float64
+    y: object
+
+    @property
+    def n(self):
+        return int(self.ring_offsets.numel()) - 1
+
+    def _head(self):
+        return (self.n, _ptr(self.ring_offsets), int(self.vert_offsets.numel()) - 1, _ptr(self.vert_offsets), int(self.x.numel()), _ptr(self.x),
+                _ptr(self.y))
+
+
+def _rings(field):
+    if isinstance(field, np.ndarray) and field.ndim == 2:
+        return [field]
+    field = list(field)
+    if field and np.ndim(field[0]) == 1 and len(field[0]) == 2 and np.ndim(field[0][0]) == 0:
+        return [field]                 # one ring given as a vertex list
+    return field
+
+
+def polygon_fields(fields, device=None):
+    """Pack a list of fields for the swath operators.  A field is an (m, 2) array of vertices (one ring) or a list of rings, ring 0 the outer
+    boundary and further rings holes; rings are closed implicitly and may have either orientation (even-odd interior).  Pass the WORK AREA:
+    the boundary already inset by the headland width.  -> PolygonFields on the device (a PolygonFields is returned as it is)."""
+    if isinstance(fields, PolygonFields):
+        return fields
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    ro, vo, xy = [0], [0], []
+    for f in fields:
+        for r in _rings(f):
+            r = np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64).reshape(-1, 2)
+            xy.append(r)
+            vo.append(vo[-1] + len(r))
+        ro.append(len(vo) - 1)
+    xy = np.concatenate(xy) if xy else np.zeros((0, 2))
+    return PolygonFields(torch.as_tensor(np.asarray(ro, dtype=np.int64), device=dev), torch.as_tensor(np.asarray(vo, dtype=np.int64), device=dev),
+                         torch.as_tensor(np.ascontiguousarray(xy[:, 0]), device=dev), torch.as_tensor(np.ascontiguousarray(xy[:, 1]), device=dev))
+
+
+def _first(width, first):
+    return float(width) / 2 if first is None else float(first)
+
+
+def swath_scores(fields, angles, width, first=None, min_length=0.0, device=None):
+    """The angle search (fcpp_swath_scores): every field cut at every track angle of `angles` [rad] into parallel tracks of working width
+    `width`; line 0 lies `first` (default width / 2) above the field's lowest point across the tracks; pieces no longer than min_length are
+    dropped.  -> (n_swaths, n_lines, length, status) device tensors of shape (n, A): swath count, line count, summed swath length [m] and
+    status (0, FCPP_EINVAL or FCPP_EUNSUPPORTED: such a pair has zeros) of field i at angles[j]."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    pf = polygon_fields(fields, device)
+    ang = _dev_f64(angles, dev).reshape(-1)
+    n, A = pf.n, int(ang.numel())
+    n_sw, n_ln, st = (torch.zeros((n, A), dtype=torch.int32, device=dev) for _ in range(3))
+    length = torch.zeros((n, A), dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_swath_scores(ctx.handle, *pf._head(), A, _ptr(ang), float(width), _first(width, first), float(min_length), _ptr(n_sw),
+                                      _ptr(n_ln), _ptr(length), _ptr(st)))
+    return n_sw, n_ln, length, st
+
+
+def best_swath_angle(fields, angles, width, turn_cost=0.0, first=None, min_length=0.0, device=None):
+    """For every field the index into `angles` that minimises length + turn_cost * n_swaths (swath_scores; the argmin is torch's, on the
+    device), ties to the lowest index; -1 for a field whose status is non-zero at every angle.  -> (index (n,) int64, cost (n, A))."""
+    torch = _torch()
+    n_sw, _, length, st = swath_scores(fields, angles, width, first, min_length, device)
+    cost = torch.where(st == 0, length + float(turn_cost) * n_sw.to(torch.float64), torch.full_like(length, float('inf')))
+    if cost.shape[1] == 0:
+        return torch.full((cost.shape[0],), -1, dtype=torch.int64, device=cost.device), cost
+    # the first index that attains the minimum (argmin alone does not promise which of equal entries it returns)
+    idx = (cost == cost.min(dim=1, keepdim=True).values).to(torch.int8).argmax(dim=1)
+    return torch.where((st == 0).any(dim=1), idx, torch.full_like(idx, -1)), cost
+
+
+@dataclass
+class SwathSet:
+    """polygon_swaths(): the swaths of n fields.  Field i owns the records offsets[i] .. offsets[i + 1], ordered by line, then along it."""
+    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy
+    offsets_host: object
+    a: object                   # (m, 2) float64: the end point with the smaller coordinate along the tracks
+    b: object                   # (m, 2)
+    line: object                # (m) int32: the line index k of the swath
+    length: object              # (m) float64
+    status: object              # (n) int32
+    n_lines: object             # (n) int32
+    angle: object               # (n) float64: the track angle of every field
+
+    def poses(self, i):
+        """field i's swaths as poses (x, y, heading): (start, end) driven from a to b -- heading theta -- and (start, end) driven the other
+        way, from b to a with heading theta + pi; each (m_i, 3), ready for dubins_matrix / rs_matrix"""
+        torch = _torch()
+        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+        a, b = self.a[sl], self.b[sl]
+        th = self.angle[i].expand(a.shape[0], 1)
+        fwd = (torch.cat([a, th], dim=1), torch.cat([b, th], dim=1))
+        return fwd, (torch.cat([b, th + np.pi], dim=1), torch.cat([a, th + np.pi], dim=1))
+
+
+def polygon_swaths(fields, angle, width, first=None, min_length=0.0, device=None):
+    """The cut (fcpp_swath_counts + fcpp_swath_fill): every field's swaths at its track angle -- `angle` is a scalar or one value per field.
+    Parameters as for swath_scores.  -> SwathSet."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    pf = polygon_fields(fields, device)
+    n = pf.n
+    ang = _dev_f64(angle, dev).reshape(-1)
+    if ang.numel() == 1 and n != 1:
+        ang = ang.expand(n).contiguous()
+    if ang.numel() != n:
+        raise ValueError('angle must be a scalar or hold one value per field')
+    args = (*pf._head(), _ptr(ang), float(width), _first(width, first), float(min_length))
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    n_ln, st = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_swath_counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(n_ln), _ptr(st)))
+    m = int(off_h[-1])
+    a, b = torch.empty((2, m), dtype=torch.float64, device=dev), torch.empty((2, m), dtype=torch.float64, device=dev)
+    line, length = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.float64, device=dev)
+    L.check(ctx.lib.fcpp_swath_fill(ctx.handle, *args, _ptr(off), m, _ptr(a[0]), _ptr(a[1]), _ptr(b[0]), _ptr(b[1]), _ptr(line), _ptr(length)))
+    return SwathSet(off, off_h, a.t().contiguous(), b.t().contiguous(), line, length, st, n_ln, ang)
+
+
+def _chord_radius(radius, spacing):
+    """The radius R' >= radius of an arc whose polyline, sampled every `spacing` metres, has the chord curvature 1 / radius: curvature()
+    is the chord formula (turning angle of two chords over their mean length), which on an arc of radius R' gives (1/R') x / sin x with
+    x = spacing / (2 R'), ABOVE 1/R'.  So R' = radius * x / sin x, a fixed point reached in a few steps (x / sin x = 1 + x^2/6 + ..)."""
+    R, h = float(radius), float(spacing) / 2
+    for _ in range(50):
+        x = h / R
+        nxt = float(radius) * x / np.sin(x) if x > 0.0 else float(radius)
+        if nxt == R:
+            break
+        R = nxt
+    return R
+
+
+def swath_route(swathset, i, radius, spacing, reversing=False, device=None):
+    """The plain boustrophedon route of field i of a SwathSet: its swaths in their STORED order (by line, then along the line), driven in
+    alternating directions, each sampled every `spacing` metres (its last sample is its end), and consecutive swaths joined by the shortest
+    Dubins path -- Reeds-Shepp if `reversing` -- from the end pose of one to the start pose of the next (dubins_paths / rs_paths).
+    `radius` is the vehicle's least turning radius.  The connectors are planned with the slightly larger radius at which the SAMPLED
+    polyline turns no tighter than 1 / radius by the project's own measure, curvature() (_chord_radius: + 0.016 % at radius 8 and spacing
+    0.5), so the route passes speed_plan's curvature clamp untouched; at a cusp of a reversing connector the chord formula sees a turn on
+    the spot, as on every Reeds-Shepp path.  -> (x, y, heading, part) device tensors; part (int8) is 0 on a swath and 1 on a connector.
+    This order is NOT optimised: it is the stored order, whatever the shape of the field (polygon_swaths + dubins_matrix / rs_matrix give a
+    router what it needs).  A connector is the shortest path between two poses and knows no boundary: it may leave the field or cross a hole;
+    validate() (fcpp_validate) flags that, as for every connector of this library."""
+    torch = _torch()
+    (f_s, f_e), (r_s, r_e) = swathset.poses(i)
+    m = int(f_s.shape[0])
+    dev = f_s.device
+    if m == 0:
+        e = torch.empty(0, dtype=torch.float64, device=dev)
+        return e, e.clone(), e.clone(), torch.empty(0, dtype=torch.int8, device=dev)
+    odd = (torch.arange(m, device=dev) % 2 == 1).unsqueeze(1)
+    start, end = torch.where(odd, r_s, f_s), torch.where(odd, r_e, f_e)
+    con = None
+    if m > 1:
+        con = (rs_paths if reversing else dubins_paths)(end[:-1], start[1:], _chord_radius(radius, spacing), spacing, device=device)
+    c_off = con[-1].cpu().numpy() if con is not None else None
+    length = swathset.length[int(swathset.offsets_host[i]):int(swathset.offsets_host[i + 1])].cpu().numpy()
+    xs, ys, hs, parts = [], [], [], []
+    for j in range(m):
+        K = int(np.floor(length[j] / float(spacing))) + 1
+        t = torch.arange(K, dtype=torch.float64, device=dev) * float(spacing)
+        if (K - 1) * float(spacing) < length[j]:
+            t = torch.cat([t, swathset.length.new_tensor([length[j]])])
+        t = (t / length[j]).clamp(max=1.0)
+        x = start[j, 0] + t * (end[j, 0] - start[j, 0])
+        y = start[j, 1] + t * (end[j, 1] - start[j, 1])
+        x[-1], y[-1] = end[j, 0], end[j, 1]
+        xs.append(x); ys.append(y); hs.append(start[j, 2].expand(x.numel())); parts.append(torch.zeros(x.numel(), dtype=torch.int8, device=dev))
+        if j + 1 < m:
+            sl = slice(int(c_off[j]), int(c_off[j + 1]))
+            xs.append(con[0][sl]); ys.append(con[1][sl]); hs.append(con[2][sl])
+            parts.append(torch.ones(sl.stop - sl.start, dtype=torch.int8, device=dev))
+    return torch.cat(xs), torch.cat(ys), torch.cat(hs), torch.cat(parts)
+
+
 def _polys(polygons):
     """list of vertex lists -> (L.Polys, keep-alive arrays)"""
     offs, px, py = [0], [], []

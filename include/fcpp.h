@@ -547,6 +547,51 @@ int fcpp_rs_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const dou
                    const int32_t *word_dev, const double *seg_dev, double spacing, const int64_t *out_offsets_dev, int64_t total_samples,
                    double *xs_dev, double *ys_dev, double *hs_dev, double *kappas_dev, int8_t *gears_dev, const int64_t *out_offsets_host);
 
+/* ---- swaths of ANY polygon field: the batched cut and the angle search ------------------------------------------------------------------
+ * Build-defined (the reference's swath generator reads a field's bounding box and four corners only).  Standalone like the connectors:
+ * fcpp_batch_plan still takes convex quadrilaterals only and nothing here feeds it.  The caller passes the WORK AREA, already inset by the
+ * headland width: there is no polygon inset here, and no routing order.
+ * A field is a list of rings: ring 0 the outer boundary, further rings holes (obstacles, keep-out areas).  Rings are closed implicitly and
+ * may have either orientation; the interior follows the EVEN-ODD rule.  Two CSR levels: ring_offsets (n + 1: fields -> rings, ending at
+ * n_rings), vert_offsets (n_rings + 1: rings -> vertices, ending at n_verts) over x, y.
+ * THE RULE (csrc/fcpp_swathfn.h, one set of expressions for host and device: the same bits on both), for the track angle theta [rad],
+ * |theta| <= 1e5, the working width W > 0, the offset 0 <= first < W of line 0 and min_length >= 0:
+ *   - (s, c) = the library's own sine and cosine of theta (exactly 0 and 1 for theta = 0).  Every vertex gets u = x c + y s along the tracks
+ *     and w = -x s + y c across them, once, so the two edges at a vertex see the same w; w_min, w_max over all vertices of the field;
+ *   - line k lies at w_k = fl(fl(w_min + first) + fl(k W)); the field has K lines, the k >= 0 with w_k < w_max;
+ *   - an edge (p, q), in ring order, crosses line k iff (w_p <= w_k) != (w_q <= w_k), at u = u_p + (w_k - w_p) / (w_q - w_p) * (u_q - u_p):
+ *     an edge lying ON a line never crosses it, a line through a vertex is counted consistently, every line has an even number of crossings;
+ *   - the crossings of a line sorted by u ascending (ties by ring, then edge) are paired (0, 1), (2, 3), ..; a pair is a swath iff
+ *     u_b - u_a > min_length, so touches of zero length never appear;
+ *   - a swath record: its end points a, b mapped back, (u c - w_k s, u s + w_k c), its line k, its length u_b - u_a.  Within a field the
+ *     records are ordered by k, then by u;
+ *   - the length sum of a (field, angle) pair adds the swath lengths in a fixed order (64 partial sums by k mod 64, each in record order,
+ *     then folded 32, 16, .. 1): host and device give the same bits.
+ * Status per (field, angle), int32: 0; FCPP_EINVAL -- no ring, a ring with fewer than 3 vertices, a vertex that is not finite (or not
+ * finite in the track frame); FCPP_EUNSUPPORTED -- a line with more than FCPP_SWATH_MAX_CROSSINGS crossings, or more than 2^22 lines.  Such a
+ * pair has 0 swaths, 0 lines and length 0; the other fields of the batch are unaffected (the convention of fcpp_batch_plan).
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or array, W <= 0 or not finite, first outside [0, W),
+ * min_length negative or not finite, an angle that is not finite or beyond 1e5 in magnitude; FCPP_ESIZE -- negative sizes, 2^31 (field,
+ * angle) pairs or more, offsets that do not start at 0, decrease, or do not end at the length of the array they index.  (The offsets and
+ * the angles are read back for these checks.)  All three entries synchronise. */
+#define FCPP_SWATH_MAX_CROSSINGS 64
+/* The angle search: n fields x A angles (the list is shared by all fields).  n_swaths, n_lines (int32), length (float64), status (int32):
+ * n x A row-major, entry (i, j) = field i at angles[j]; any may be NULL. */
+int fcpp_swath_scores(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev,
+                      int64_t n_verts, const double *x_dev, const double *y_dev, int64_t A, const double *angles_dev, double W, double first,
+                      double min_length, int32_t *n_swaths_dev, int32_t *n_lines_dev, double *length_dev, int32_t *status_dev);
+/* The cut, count -> scan -> fill like the *_counts / *_sample pairs: field i at angle_dev[i].  fcpp_swath_counts writes the CSR offsets of
+ * the fields' swaths (n + 1; out_offsets_host: NULL or room for a copy), n_lines and status (n each, may be NULL). */
+int fcpp_swath_counts(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev,
+                      int64_t n_verts, const double *x_dev, const double *y_dev, const double *angle_dev, double W, double first,
+                      double min_length, int64_t *out_offsets_dev, int64_t *out_offsets_host, int32_t *n_lines_dev, int32_t *status_dev);
+/* fcpp_swath_fill writes the records of the same fields, angles and parameters at those offsets (n_total = offsets[n]): ax, ay, bx, by,
+ * length (float64) and line (int32), any may be NULL.  A field never writes outside its own range of the offsets. */
+int fcpp_swath_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                    const double *x_dev, const double *y_dev, const double *angle_dev, double W, double first, double min_length,
+                    const int64_t *offsets_dev, int64_t n_total, double *ax_dev, double *ay_dev, double *bx_dev, double *by_dev, int32_t *line_dev,
+                    double *length_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -608,6 +653,15 @@ int fcpp_debug_dubins(int64_t n, const double *from_x, const double *from_y, con
  * compared with bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
 int fcpp_debug_rs(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,
                   const double *to_h, double radius, int32_t *word, double *seg, double *len);
+/* The polygon swath rule (csrc/fcpp_swathfn.h) evaluated on the HOST, on host pointers, for both the scores and the cut: what the device
+ * results are compared with bit for bit.  The angle of pair (i, j) is angles[i] when per_field (then A = 1), else angles[j]; n_swaths,
+ * n_lines, length, status: n x A, any may be NULL.  out_offsets: NULL, or (A = 1) n + 1 CSR offsets of the fields' swaths; the records
+ * below `cap` are written to ax .. seg_length (any may be NULL), so a first call with cap = 0 sizes the second.  The call's errors as
+ * for fcpp_swath_scores.  A diagnostic, not a fallback. */
+int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                      const double *y, int64_t A, const double *angles, int per_field, double W, double first, double min_length,
+                      int32_t *n_swaths, int32_t *n_lines, double *length, int32_t *status, int64_t *out_offsets, int64_t cap, double *ax,
+                      double *ay, double *bx, double *by, int32_t *line, double *seg_length);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch

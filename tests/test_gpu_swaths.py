@@ -1,0 +1,238 @@
+"""GPU tests of the polygon swaths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_swath.hip against the same rule on the host
+(fcpp_debug_swaths) BIT FOR BIT -- counts, lines, statuses, offsets, end points and lengths, and the per-pair length SUMS too: host and
+device add in the same stated order (64 partial sums by line mod 64, then folded), so the sums are compared with array_equal, not to a
+bound.  Then the angle search against the cut, best_swath_angle against numpy's argmin, and swath_route through the project's own
+operators."""
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+from tests.test_swaths_host import COMB, ELL, HOLE, OVER_COMB, RECT, host_cut, host_scores, rings_of, star
+
+pytestmark = pytest.mark.gpu
+
+W, FIRST, MIN_LENGTH = 3.2, 1.6, 0.0
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _square(side, at=(0.0, 0.0)):
+    return np.array([(0, 0), (side, 0), (side, side), (0, side)], dtype=np.float64) + np.asarray(at)
+
+
+NAN_FIELD = np.array(ELL, dtype=np.float64)
+NAN_FIELD[3, 0] = np.nan
+# stars of 3, 7, 65, 257 and 300 vertices: a vertex chunk (63 edges) ends inside a field; squares of 250 m and 900 m: more than 64 and more
+# than 256 lines at any angle, so line blocks are crossed; a disc-like field of one line; one narrower than `first` (no line at any angle)
+KINDS = [('ell', ELL), ('ell_hole', [ELL, HOLE]), ('comb', COMB), ('rect', RECT), ('star3', star(3, 3)), ('star7', star(7, 7)),
+         ('star65', star(65, 65)), ('star257', star(257, 257)), ('star300', star(300, 300)), ('lines78', _square(250.0, (-40.0, 10.0))),
+         ('lines281', _square(900.0)), ('one_line', _square(2.0, (5.0, 5.0))), ('no_line', _square(1.0, (-3.0, 8.0))),
+         ('over_comb', OVER_COMB), ('nan', NAN_FIELD)]
+
+
+def batch(n, seed):
+    """n fields cycling through the kinds (a batch of one is the 65-vertex star), each moved a little, with an angle of its own"""
+    rng = np.random.default_rng(seed)
+    names, fields = [], []
+    for i in range(n):
+        name, f = KINDS[(i + 6) % len(KINDS)]
+        shift = rng.uniform(-20.0, 20.0, 2) * (i >= len(KINDS))
+        names.append(name)
+        fields.append([r + shift for r in rings_of(f)])
+    return names, fields, rng.uniform(-np.pi, np.pi, n)
+
+
+@pytest.fixture(scope='module')
+def host_reference():
+    """the host's cut of every batch, computed once and left unchanged"""
+    out = {}
+    for n in (1, 63, 65, 257):
+        names, fields, angles = batch(n, 100 + n)
+        out[n] = (names, fields, angles, host_cut(fields, angles, W, FIRST, MIN_LENGTH))
+    return out
+
+
+def _assert_cut_equal(dev, host, sl_dev=None, sl_host=None):
+    d = {k: _np(getattr(dev, k)) for k in ('a', 'b', 'line', 'length')}
+    sd = sl_dev if sl_dev is not None else slice(None)
+    sh = sl_host if sl_host is not None else slice(None)
+    assert np.array_equal(d['line'][sd], host['line'][sh])
+    assert np.array_equal(_bits(d['a'][sd]), _bits(host['a'][sh])) and np.array_equal(_bits(d['b'][sd]), _bits(host['b'][sh]))
+    assert np.array_equal(_bits(d['length'][sd]), _bits(host['length'][sh]))
+
+
+@pytest.mark.parametrize('n', [1, 63, 65, 257])
+def test_device_equals_host_bit_for_bit(host_reference, n):
+    names, fields, angles, host = host_reference[n]
+    dev = E.polygon_swaths(fields, angles, W, FIRST, MIN_LENGTH)
+    assert np.array_equal(_np(dev.status), host['status']) and np.array_equal(_np(dev.n_lines), host['n_lines'])
+    assert np.array_equal(_np(dev.offsets), host['offsets']) and np.array_equal(dev.offsets_host, host['offsets'])
+    _assert_cut_equal(dev, host)
+    n_sw, n_ln, length, st = E.swath_scores([f for f in fields], angles[:1], W, FIRST, MIN_LENGTH)
+    assert tuple(n_sw.shape) == (n, 1)
+    # what the kinds are there for
+    for i, name in enumerate(names):
+        if name == 'lines78':
+            assert host['n_lines'][i] > 64
+        if name == 'lines281':
+            assert host['n_lines'][i] > 256
+        if name == 'one_line':
+            assert host['n_lines'][i] == 1 and host['n_swaths'][i] == 1
+        if name == 'no_line':
+            assert host['n_lines'][i] == 0 and host['status'][i] == 0
+        if name == 'nan':
+            assert host['status'][i] == L.EINVAL
+    if n >= 63:
+        assert (host['status'] == L.EINVAL).sum() >= 4 and (host['n_swaths'] > 100).any()
+    # a second call: the same bits
+    again = E.polygon_swaths(fields, angles, W, FIRST, MIN_LENGTH)
+    for k in ('a', 'b', 'length'):
+        assert np.array_equal(_bits(_np(getattr(again, k))), _bits(_np(getattr(dev, k))))
+    assert np.array_equal(_np(again.line), _np(dev.line)) and np.array_equal(_np(again.offsets), _np(dev.offsets))
+
+
+def test_over_cap_comb_is_unsupported_on_the_device():
+    dev = E.polygon_swaths([ELL, OVER_COMB, COMB], 0.0, 5.0, 0.0)
+    host = host_cut([ELL, OVER_COMB, COMB], 0.0, 5.0, 0.0)
+    assert _np(dev.status).tolist() == [0, L.EUNSUPPORTED, 0] == host['status'].tolist()
+    assert np.array_equal(_np(dev.offsets), host['offsets']) and host['offsets'].tolist() == [0, 10, 10, 36]
+    _assert_cut_equal(dev, host)
+
+
+@pytest.mark.parametrize('A', [1, 7, 180])
+def test_scores_equal_the_cut(host_reference, A):
+    """n = 65; every (field, angle) entry against fcpp_swath_counts at that angle and against the host's scores.  length: array_equal --
+    the summation order is fixed on both sides (csrc/fcpp_swathfn.h)."""
+    names, fields, _, _ = host_reference[65]
+    angles = np.linspace(0.0, np.pi, A, endpoint=False) + 0.01
+    pf = E.polygon_fields(fields)
+    n_sw, n_ln, length, st = (_np(t) for t in E.swath_scores(pf, angles, W, FIRST, 2.0))
+    host = host_scores(fields, angles, W, FIRST, 2.0)
+    assert np.array_equal(n_sw, host['n_swaths']) and np.array_equal(n_ln, host['n_lines']) and np.array_equal(st, host['status'])
+    assert np.array_equal(_bits(length), _bits(host['length']))
+    for j in range(A):
+        cut = E.polygon_swaths(pf, float(angles[j]), W, FIRST, 2.0)
+        assert np.array_equal(np.diff(cut.offsets_host), n_sw[:, j]) and np.array_equal(_np(cut.n_lines), n_ln[:, j])
+        assert np.array_equal(_np(cut.status), st[:, j])
+        if j % 45 == 0:
+            # the records' lengths in the stated order give the pair's sum
+            rec, line = _np(cut.length), _np(cut.line)
+            for i in range(len(fields)):
+                sl = slice(cut.offsets_host[i], cut.offsets_host[i + 1])
+                acc = np.zeros(64)
+                for k, v in zip(line[sl], rec[sl]):
+                    acc[k & 63] += v
+                o = 32
+                while o:
+                    acc[:o] = acc[:o] + acc[o:2 * o]
+                    o >>= 1
+                assert _bits(acc[:1])[0] == _bits(length[i:i + 1, j])[0], (i, j)
+
+
+def test_a_field_gives_the_same_bits_alone_and_inside_a_batch(host_reference):
+    names, fields, angles, host = host_reference[257]
+    whole = E.polygon_swaths(fields, angles, W, FIRST, MIN_LENGTH)
+    off = whole.offsets_host
+    for i in (names.index('star300'), names.index('lines281'), names.index('ell_hole'), 256, 200):
+        alone = E.polygon_swaths(fields[i:i + 1], angles[i:i + 1], W, FIRST, MIN_LENGTH)
+        sl = slice(off[i], off[i + 1])
+        assert alone.offsets_host.tolist() == [0, sl.stop - sl.start]
+        for k in ('a', 'b', 'length'):
+            assert np.array_equal(_bits(_np(getattr(alone, k))), _bits(_np(getattr(whole, k))[sl])), (i, k)
+        assert np.array_equal(_np(alone.line), _np(whole.line)[sl])
+
+
+@pytest.mark.parametrize('turn_cost', [0.0, 25.0])
+def test_best_swath_angle(host_reference, turn_cost):
+    names, fields, _, _ = host_reference[65]
+    angles = np.linspace(0.0, np.pi, 36, endpoint=False)
+    angles[7] = angles[3]                                  # equal columns: a tie that must go to the lower index
+    host = host_scores(fields, angles, W, FIRST, 0.0)
+    cost = np.where(host['status'] == 0, host['length'] + turn_cost * host['n_swaths'].astype(np.float64), np.inf)
+    expect = np.where((host['status'] == 0).any(axis=1), np.argmin(cost, axis=1), -1)
+    idx, dev_cost = E.best_swath_angle(fields, angles, W, turn_cost=turn_cost, first=FIRST)
+    assert np.array_equal(_np(idx), expect)
+    assert np.array_equal(_bits(_np(dev_cost)), _bits(cost))
+    assert (expect == -1).sum() >= 4 and not (expect == 7).any()
+
+
+def _route(field, reversing=False):
+    R, spacing, theta = 8.0, 0.5, 0.3
+    ss = E.polygon_swaths([field], theta, 5.0)
+    x, y, h, part = (_np(t) for t in E.swath_route(ss, 0, R, spacing, reversing=reversing))
+    return ss, R, spacing, theta, x, y, h, part
+
+
+def _runs(part):
+    cut = np.flatnonzero(np.diff(part)) + 1
+    return np.concatenate([[0], cut]), np.concatenate([cut, [len(part)]])
+
+
+@pytest.mark.parametrize('field', [ELL, [ELL, HOLE]], ids=['ell', 'ell_hole'])
+def test_swath_route_structure(field):
+    ss, R, spacing, theta, x, y, h, part = _route(field)
+    a, b = _np(ss.a), _np(ss.b)
+    m = len(a)
+    assert m > 10
+    xy = np.column_stack([x, y])
+    for p in np.vstack([a, b]):
+        assert (xy == p).all(axis=1).any()                 # every swath's two end points occur in the route, to the bit
+    starts, ends = _runs(part)
+    assert len(starts) == 2 * m - 1 and part[starts].tolist() == [0, 1] * (m - 1) + [0]
+    on = part == 0
+    dh = np.abs(np.angle(np.exp(1j * (h[on] - theta))))
+    assert (np.minimum(dh, np.abs(dh - np.pi)) <= 1e-12).all()
+    # swath j is driven a -> b for even j, b -> a for odd j; consecutive samples lie at most `spacing` apart, connectors start and end on the swaths
+    for j in range(m):
+        s, e = starts[2 * j], ends[2 * j]
+        first, last = (a[j], b[j]) if j % 2 == 0 else (b[j], a[j])
+        assert np.array_equal(xy[s], first) and np.array_equal(xy[e - 1], last)
+        if j + 1 < m:
+            assert np.hypot(*(xy[e] - last)) <= 1e-9 and np.hypot(*(xy[ends[2 * j + 1] - 1] - xy[starts[2 * j + 2]])) <= 1e-9
+    assert (np.hypot(np.diff(x), np.diff(y)) <= spacing + 1e-9).all()
+    # the reversing vehicle: the same swaths, never a longer route
+    _, _, _, _, xr, yr, hr, pr = _route(field, reversing=True)
+    assert (pr == 0).sum() == on.sum() and len(xr) <= len(x) + 4 * m
+
+
+def _connector_curvature(field):
+    ss, R, spacing, theta, x, y, h, part = _route(field)
+    starts, ends = _runs(part)
+    offs = np.concatenate([starts, [len(part)]])
+    kc = np.abs(_np(E.curvature(x, y, offsets=offs)))
+    inner = np.zeros(len(x), dtype=bool)
+    for s, e in zip(starts, ends):
+        if part[s] == 1:
+            inner[s + 1:e - 1] = True                      # (a connector's first and last sample are its junctions with the swaths)
+    assert inner.sum() > 500
+    return R, spacing, kc[inner]
+
+
+@pytest.mark.parametrize('field', [ELL, [ELL, HOLE]], ids=['ell', 'ell_hole'])
+def test_swath_route_connector_curvature(field):
+    """The issue's bound: engine.curvature of every connector sample (its two junction samples with the swaths excluded) <= 1/R + 1e-6.
+    engine.curvature is the chord formula (turning angle of two chords over their mean length); on an arc of radius r sampled every
+    `spacing` it gives (1/r) x / sin x, x = spacing / (2 r) (tests/test_gpu_dubins.py derives and asserts that value) -- 2.0e-5 above 1/R
+    for r = R = 8 at 0.5 m.  swath_route therefore plans its connectors with the radius r >= R at which that value IS 1/R, and a shorter
+    last step or a junction with a straight only lowers it (x / sin x increases).  The second assertion keeps the route from paying more
+    than that: the tightest samples reach 1/R within 1e-9 relative, the tolerance test_gpu_dubins.py has for the same value."""
+    R, spacing, kc = _connector_curvature(field)
+    print(f'connector curvature: max {kc.max():.15f}, 1/R {1 / R:.15f}, bound {1 / R + 1e-6:.15f}')
+    assert kc.max() <= 1 / R + 1e-6
+    assert kc.max() >= (1 / R) * (1 - 1e-9)
+
+
+def test_chord_radius():
+    """the radius swath_route plans with: the chord curvature of its sampled arc is 1/R to rounding, and it tends to R as the spacing shrinks"""
+    for R, spacing in ((8.0, 0.5), (2.0, 0.1), (8.0, 10.0), (25.0, 0.37)):
+        r = E._chord_radius(R, spacing)
+        x = spacing / (2 * r)
+        assert r > R and abs((1 / r) * x / np.sin(x) - 1 / R) <= 4 * np.finfo(float).eps / R
+    assert E._chord_radius(8.0, 1e-6) - 8.0 < 1e-9 and 8.0013 < E._chord_radius(8.0, 0.5) < 8.00131
