@@ -16,6 +16,7 @@ OBSTACLES_FLAG, OBSTACLES_AVOID = 0, 1
 RING_AS_VERTICES, RING_REVERSED = 0, 1
 KIND_MASK, FLAG_HEADLAND, FLAG_ALAT, FLAG_OUTSIDE, FLAG_OBSTACLE, INDEX_SHIFT = 7, 8, 16, 32, 64, 8
 OUTPUT_PITCH = 24 << 30          # FCPP_OUTPUT_PITCH (include/fcpp.h)
+ROUTE_MAX_SWATHS = 512           # FCPP_ROUTE_MAX_SWATHS
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -168,6 +169,8 @@ PROTOTYPES = [
     ('fcpp_swath_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double] + [_VP] * 4),
     ('fcpp_swath_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double, _VP, C.c_int64]
      + [_VP] * 6),
+    ('fcpp_route_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
+    ('fcpp_route_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_ga_evolve', C.c_int, [_VP, C.c_int32, C.POINTER(GaConfig), _VP, _VP, _VP, _VP, C.POINTER(GaResult)]),
     ('fcpp_cover_grid', C.c_int, [_VP, C.c_int64, C.POINTER(CoverJob), C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_gather', C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, c_i64_p, _VP, C.c_int]),
@@ -177,6 +180,8 @@ PROTOTYPES = [
     ('fcpp_debug_rs', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_swaths', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int, C.c_double, C.c_double, C.c_double]
      + [_VP] * 5 + [C.c_int64] + [_VP] * 6),
+    ('fcpp_debug_route_transit', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP]),
+    ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
 ]
 

@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators.  Like fcpp_api.cpp:
+// operators and the swath router.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -10,6 +10,9 @@
 
 #include "fcpp_api_internal.h"
 #include "fcpp_dubins.h"
+#include "fcpp_parallel.h"
+#include "fcpp_route.h"
+#include "fcpp_routefn.h"
 #include "fcpp_rs.h"
 #include "fcpp_swath.h"
 #include "fcpp_swathfn.h"
@@ -228,6 +231,36 @@ int swath_fields(fcpp_ctx *c, int64_t n, const int64_t *ring_dev, const int64_t 
     int rc = host_offsets(c, n, ring_dev, ring_host, n_rings, "ring_offsets", rings);
     if (rc == FCPP_OK) rc = host_offsets(c, n_rings, vert_dev, vert_host, n_verts, "vert_offsets", verts);
     return rc;
+}
+
+// ---- swath router: what fcpp_route_transit / _solve and their host twins check alike ---------------------------------------------------
+int route_radius(double radius, int mode)
+{
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (mode != 0 && mode != 1) return fail(FCPP_EINVAL, "mode must be 0 (Dubins) or 1 (Reeds-Shepp)");
+    return FCPP_OK;
+}
+
+int route_search(int S, double min_gain, int max_sweeps)
+{
+    if (S < 1 || S > ROUTE_MAX_STARTS) return fail(FCPP_EINVAL, "n_starts must lie in 1 .. 64");
+    if (!(min_gain >= 0.0) || !isfinite(min_gain)) return fail(FCPP_EINVAL, "min_gain must be non-negative and finite");
+    if (max_sweeps < 0 || max_sweeps > ROUTE_MAX_SWEEPS) return fail(FCPP_EINVAL, "max_sweeps must lie in 0 .. 2^20");
+    return FCPP_OK;
+}
+
+// the swath offsets and the block offsets on the host, checked against each other: block i holds (2 m_i)^2 entries, none beyond the cap
+int route_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_dev, const int64_t *soff_host, int64_t n_total, const int64_t *toff_dev,
+                  const int64_t *toff_host, int64_t t_total, std::vector<int64_t> &soff, std::vector<int64_t> &toff)
+{
+    if (n < 0 || n_total < 0 || t_total < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    int rc = host_offsets(c, n, soff_dev, soff_host, n_total, "swath_offsets", soff);
+    if (rc == FCPP_OK) rc = host_offsets(c, n, toff_dev, toff_host, t_total, "t_offsets", toff);
+    if (rc) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (toff[(size_t)i + 1] - toff[(size_t)i] != route_block(soff[(size_t)i + 1] - soff[(size_t)i]))
+            return fail(FCPP_ESIZE, "t_offsets do not match the swath counts: block i holds (2 m_i)^2 entries, none for m_i > 512");
+    return FCPP_OK;
 }
 }  // namespace
 
@@ -665,6 +698,107 @@ int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, c
         }
     }
     if (out_offsets) out_offsets[n] = at;
+    return FCPP_OK;
+}
+
+// ---- swath router (fcpp_route.hip; the rule: fcpp_routefn.h) ------------------------------------------------------------------------
+int fcpp_route_transit(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                       const double *ax, const double *ay, const double *bx, const double *by, const double *angle, double radius, int mode,
+                       const int64_t *t_offsets, const int64_t *t_offsets_host, int64_t t_total, double *T)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!swath_offsets || !t_offsets || (n_total > 0 && (!ax || !ay || !bx || !by)) || (n > 0 && !angle) || (t_total > 0 && !T))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, toff;
+    rc = route_offsets(c, n, swath_offsets, swath_offsets_host, n_total, t_offsets, t_offsets_host, t_total, soff, toff);
+    if (rc == FCPP_OK && (t_total + 255) / 256 > ROUTE_MAX_GROUPS) rc = fail(FCPP_ESIZE, "2^39 transit entries or more");
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle, nullptr);
+    if (rc) return rc;
+    LAUNCHCHK(launch_route_transit(c->stream, n, swath_offsets, ax, ay, bx, by, angle, radius, mode, t_offsets, t_total, T));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_route_solve(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                     const int64_t *t_offsets, const int64_t *t_offsets_host, int64_t t_total, const double *T, const double *E, const double *X,
+                     int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route, double *cost, int32_t *winner,
+                     int32_t *sweeps, int32_t *status, double *stored)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!swath_offsets || !t_offsets || (t_total > 0 && !T)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_search(n_starts, min_gain, max_sweeps);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, toff;
+    rc = route_offsets(c, n, swath_offsets, swath_offsets_host, n_total, t_offsets, t_offsets_host, t_total, soff, toff);
+    if (rc == FCPP_OK && n > ROUTE_MAX_GROUPS / n_starts) rc = fail(FCPP_ESIZE, "2^31 (field, candidate) pairs or more");
+    if (rc) return rc;
+    // what the pick reads is the solve's own when the caller does not want it
+    DevBuf<int32_t> own_tours, applied;
+    DevBuf<double> own_costs, own_stored;
+    if (!tours) { HIPCHK(own_tours.alloc((size_t)n_starts * (size_t)n_total)); tours = own_tours.p; }
+    if (!costs) { HIPCHK(own_costs.alloc((size_t)n * (size_t)n_starts)); costs = own_costs.p; }
+    if (!stored) { HIPCHK(own_stored.alloc((size_t)n)); stored = own_stored.p; }
+    HIPCHK(applied.alloc((size_t)n * (size_t)n_starts));
+    LAUNCHCHK(launch_route_solve(c->stream, n, n_starts, swath_offsets, n_total, t_offsets, T, E, X, min_gain, max_sweeps, tours, costs, applied.p,
+                                 stored));
+    LAUNCHCHK(launch_route_pick(c->stream, n, n_starts, swath_offsets, n_total, tours, costs, applied.p, stored, route, cost, winner, sweeps, status));
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the temporaries die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_route_transit(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                             const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total, double *T)
+{
+    if (!swath_offsets || !t_offsets || (n_total > 0 && (!ax || !ay || !bx || !by)) || (n > 0 && !angle) || (t_total > 0 && !T))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    std::vector<int64_t> soff, toff;
+    rc = route_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, t_offsets, t_total, soff, toff);
+    if (rc == FCPP_OK) rc = swath_angles(nullptr, n, nullptr, angle);
+    if (rc) return rc;
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t s0 = soff[(size_t)i];
+        const int N = (int)(toff[(size_t)i + 1] == toff[(size_t)i] ? 0 : 2 * (soff[(size_t)i + 1] - s0));
+        double *blk = T + toff[(size_t)i];
+        for (int p = 0; p < N; ++p)
+            for (int q = 0; q < N; ++q) {
+                if (!route_canonical(p, q, N)) continue;
+                const double v = mode == 0 ? route_transit<0>(ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, p, q)
+                                           : route_transit<1>(ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, p, q);
+                blk[p * N + q] = v;
+                blk[(q ^ 1) * N + (p ^ 1)] = v;
+            }
+    });
+    return FCPP_OK;
+}
+
+int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
+                     const double *E, const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route,
+                     double *cost, int32_t *winner, int32_t *sweeps, int32_t *status, double *stored)
+{
+    if (!swath_offsets || !t_offsets || (t_total > 0 && !T)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_search(n_starts, min_gain, max_sweeps);
+    if (rc) return rc;
+    std::vector<int64_t> soff, toff;
+    rc = route_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, t_offsets, t_total, soff, toff);
+    if (rc == FCPP_OK && n > ROUTE_MAX_GROUPS / n_starts) rc = fail(FCPP_ESIZE, "2^31 (field, candidate) pairs or more");
+    if (rc) return rc;
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t s0 = soff[(size_t)i];
+        const RouteField f = route_field_host(T + toff[(size_t)i], E ? E + 2 * s0 : nullptr, X ? X + 2 * s0 : nullptr, soff[(size_t)i + 1] - s0, n_starts,
+                                              min_gain, max_sweeps, tours ? tours + s0 : nullptr, n_total, costs ? costs + i * n_starts : nullptr,
+                                              route ? route + s0 : nullptr);
+        if (cost) cost[i] = f.cost;
+        if (winner) winner[i] = f.winner;
+        if (sweeps) sweeps[i] = f.sweeps;
+        if (status) status[i] = f.status;
+        if (stored) stored[i] = f.stored;
+    });
     return FCPP_OK;
 }
 

@@ -1288,16 +1288,18 @@ def _chord_radius(radius, spacing):
     return R
 
 
-def swath_route(swathset, i, radius, spacing, reversing=False, device=None):
-    """The plain boustrophedon route of field i of a SwathSet: its swaths in their STORED order (by line, then along the line), driven in
-    alternating directions, each sampled every `spacing` metres (its last sample is its end), and consecutive swaths joined by the shortest
+def swath_route(swathset, i, radius, spacing, reversing=False, device=None, order=None):
+    """The route of field i of a SwathSet.  order=None: the plain boustrophedon route, its swaths in their STORED order (by line, then along
+    the line), driven in alternating directions; order = an int array of oriented swaths (2 s + d: swath s of the field, d = 0 from a to b,
+    d = 1 from b to a, every swath once) or a SwathRoute of the same SwathSet (route_swaths): the swaths in that order and those directions.
+    Each swath is sampled every `spacing` metres (its last sample is its end), and consecutive swaths are joined by the shortest
     Dubins path -- Reeds-Shepp if `reversing` -- from the end pose of one to the start pose of the next (dubins_paths / rs_paths).
     `radius` is the vehicle's least turning radius.  The connectors are planned with the slightly larger radius at which the SAMPLED
     polyline turns no tighter than 1 / radius by the project's own measure, curvature() (_chord_radius: + 0.016 % at radius 8 and spacing
     0.5), so the route passes speed_plan's curvature clamp untouched; at a cusp of a reversing connector the chord formula sees a turn on
     the spot, as on every Reeds-Shepp path.  -> (x, y, heading, part) device tensors; part (int8) is 0 on a swath and 1 on a connector.
-    This order is NOT optimised: it is the stored order, whatever the shape of the field (polygon_swaths + dubins_matrix / rs_matrix give a
-    router what it needs).  A connector is the shortest path between two poses and knows no boundary: it may leave the field or cross a hole;
+    The stored order is NOT optimised, whatever the shape of the field: route_swaths chooses an order and directions (pass it the same
+    `spacing`, so that it prices the connectors driven here).  A connector is the shortest path between two poses and knows no boundary: it may leave the field or cross a hole;
     validate() (fcpp_validate) flags that, as for every connector of this library."""
     torch = _torch()
     (f_s, f_e), (r_s, r_e) = swathset.poses(i)
@@ -1306,13 +1308,24 @@ def swath_route(swathset, i, radius, spacing, reversing=False, device=None):
     if m == 0:
         e = torch.empty(0, dtype=torch.float64, device=dev)
         return e, e.clone(), e.clone(), torch.empty(0, dtype=torch.int8, device=dev)
-    odd = (torch.arange(m, device=dev) % 2 == 1).unsqueeze(1)
-    start, end = torch.where(odd, r_s, f_s), torch.where(odd, r_e, f_e)
+    length = swathset.length[int(swathset.offsets_host[i]):int(swathset.offsets_host[i + 1])]
+    if order is None:
+        odd = (torch.arange(m, device=dev) % 2 == 1).unsqueeze(1)
+        start, end = torch.where(odd, r_s, f_s), torch.where(odd, r_e, f_e)
+    else:
+        o = order.field(i) if isinstance(order, SwathRoute) else order
+        o = torch.as_tensor(o, device=dev).to(torch.int64).reshape(-1)
+        idx = o >> 1
+        if int(o.numel()) != m or not torch.equal(torch.sort(idx).values, torch.arange(m, device=dev)):
+            raise ValueError('order must hold every swath of the field exactly once, as 2 * swath + direction')
+        odd = (o & 1).to(torch.bool).unsqueeze(1)
+        start, end = torch.where(odd, r_s[idx], f_s[idx]), torch.where(odd, r_e[idx], f_e[idx])
+        length = length[idx]
     con = None
     if m > 1:
         con = (rs_paths if reversing else dubins_paths)(end[:-1], start[1:], _chord_radius(radius, spacing), spacing, device=device)
     c_off = con[-1].cpu().numpy() if con is not None else None
-    length = swathset.length[int(swathset.offsets_host[i]):int(swathset.offsets_host[i + 1])].cpu().numpy()
+    length = length.cpu().numpy()
     xs, ys, hs, parts = [], [], [], []
     for j in range(m):
         K = int(np.floor(length[j] / float(spacing))) + 1
@@ -1329,6 +1342,136 @@ def swath_route(swathset, i, radius, spacing, reversing=False, device=None):
             xs.append(con[0][sl]); ys.append(con[1][sl]); hs.append(con[2][sl])
             parts.append(torch.ones(sl.stop - sl.start, dtype=torch.int8, device=dev))
     return torch.cat(xs), torch.cat(ys), torch.cat(hs), torch.cat(parts)
+
+
+# ---- the swath router (fcpp_route_transit / fcpp_route_solve; the rule: include/fcpp.h) ----------------------------------------------------
+ROUTE_T_BUDGET = 1 << 30         # bytes of transit blocks one call of the library holds: route_swaths solves the fields in chunks below it
+
+
+@dataclass
+class SwathRoute:
+    """route_swaths(): for every field of a SwathSet the order and directions in which to drive its swaths.  Field i owns
+    order[offsets_host[i] : offsets_host[i + 1]] (the SwathSet's offsets): oriented swaths 2 s + d in driving order, s the swath's index
+    within the field, d = 0 from a to b, d = 1 from b to a."""
+    offsets_host: object        # (n + 1) int64, numpy
+    order: object               # (m) int32, device
+    cost: object                # (n) float64: the summed connector lengths of `order` [m] (with the entry / exit connectors, if given)
+    stored_cost: object         # (n) float64: the same for the stored boustrophedon order, what swath_route drives without an order
+    winner: object              # (n) int32: the candidate that gave `order`
+    sweeps: object              # (n) int32: the most moves any candidate of the field applied
+    status: object              # (n) int32: 0, FCPP_EUNSUPPORTED (more than 512 swaths) or FCPP_EINVAL (a non-finite cost): the stored order
+    tours: object               # (starts, m) int32: every candidate's final tour
+    costs: object               # (n, starts) float64: and its cost
+
+    def field(self, i):
+        return self.order[int(self.offsets_host[i]):int(self.offsets_host[i + 1])]
+
+
+def _route_offsets(soff_h):
+    """the transit block offsets of fields with these swath offsets: block i is (2 m_i)^2 entries, none beyond the cap"""
+    m = np.diff(soff_h)
+    toff = np.zeros(len(soff_h), dtype=np.int64)
+    np.cumsum(np.where(m > L.ROUTE_MAX_SWATHS, 0, 4 * m * m), out=toff[1:])
+    return toff
+
+
+def _route_transit(ctx, ss, lo, hi, radius, reversing):
+    """fields lo .. hi of a SwathSet -> (T, toff, toff_h, soff, soff_h, n_total): their transit blocks and the chunk's own offsets"""
+    torch = _torch()
+    dev = ss.a.device
+    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
+    soff_h = np.ascontiguousarray(ss.offsets_host[lo:hi + 1] - s0, dtype=np.int64)
+    toff_h = _route_offsets(soff_h)
+    soff, toff = torch.as_tensor(soff_h, device=dev), torch.as_tensor(toff_h, device=dev)
+    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+    ang = ss.angle[lo:hi].contiguous()
+    T = torch.empty(int(toff_h[-1]), dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_route_transit(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(ang),
+                                       float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]), _ptr(T)))
+    return T, toff, toff_h, soff, soff_h, s1 - s0
+
+
+def _route_chunks(soff_h, budget):
+    """[lo, hi) ranges of consecutive fields whose transit blocks stay within `budget` bytes (a field alone is at most 8 MiB)"""
+    size = np.diff(_route_offsets(soff_h)) * 8
+    out, lo, acc = [], 0, 0
+    for i, b in enumerate(size):
+        if i > lo and acc + b > budget:
+            out.append((lo, i))
+            lo, acc = i, 0
+        acc += int(b)
+    if len(size) > lo or not out:
+        out.append((lo, len(size)))
+    return out
+
+
+def swath_transit(swathset, radius, reversing=False, device=None):
+    """The transit blocks of every field of a SwathSet (fcpp_route_transit) -> (T, offsets): T a flat float64 device tensor, field i's block
+    T[offsets[i] : offsets[i + 1]].reshape(2 m_i, 2 m_i) (offsets: numpy int64), entry [p][q] the shortest Dubins -- Reeds-Shepp if
+    `reversing` -- length from the end of oriented swath p to the start of oriented swath q (p = 2 s + d: swath s from a to b for d = 0, from
+    b to a for d = 1), +inf within one swath; [p][q] and [q ^ 1][p ^ 1] hold equal bits.  A field of more than 512 swaths has no block."""
+    ctx = get_context(device)
+    T, _, toff_h, _, _, _ = _route_transit(ctx, swathset, 0, len(swathset.offsets_host) - 1, radius, reversing)
+    return T, toff_h
+
+
+def _route_ends(ss, pose, at_entry, radius, reversing, device):
+    """E (at_entry) or X of route_swaths: the connector length between each field's pose and every oriented swath's start / from its end"""
+    torch = _torch()
+    dev = ss.a.device
+    pose = _dev_f64(pose, dev).reshape(-1, 3)
+    counts = torch.as_tensor(np.diff(ss.offsets_host), device=dev)
+    if pose.shape[0] != counts.numel():
+        raise ValueError('entry / exit must hold one pose (x, y, heading) per field')
+    th = torch.repeat_interleave(ss.angle, counts).unsqueeze(1)
+    # oriented swath 2 s starts at a and ends at b with heading theta, 2 s + 1 starts at b and ends at a with theta + pi (SwathSet.poses)
+    first, second = (ss.a, ss.b) if at_entry else (ss.b, ss.a)
+    own = torch.stack([torch.cat([first, th], dim=1), torch.cat([second, th + np.pi], dim=1)], dim=1).reshape(-1, 3)
+    far = torch.repeat_interleave(pose, 2 * counts, dim=0)
+    solve = rs_solve if reversing else dubins_solve
+    return (solve(far, own, radius, device)[2] if at_entry else solve(own, far, radius, device)[2]).contiguous()
+
+
+def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, starts=8, min_gain=1e-9, max_sweeps=None, spacing=None, device=None):
+    """Order and direction of every field's swaths (fcpp_route_transit + fcpp_route_solve; the rule: include/fcpp.h) -> SwathRoute.
+    The cost of a tour is the summed length of its connectors -- shortest Dubins paths at the turning radius `radius`, Reeds-Shepp if
+    `reversing` -- plus, with entry / exit (one pose (x, y, heading) per field, or None), the connector from the field's entry pose to
+    the first swath and from the last swath to its exit pose.  `starts` candidate tours per field (the stored boustrophedon, its mirror,
+    nearest-neighbour tours from spread starts) are each improved by segment reversals and or-opt moves until none gains more than
+    min_gain [m] (or max_sweeps moves: None = 8 x the largest swath count + 8); the cheapest wins.  spacing: plan at the radius swath_route
+    drives its connectors with at that sample spacing (_chord_radius), so `cost` is the length swath_route(order=...) drives.  Connectors
+    know no boundary (validate() flags what leaves the field).  Fields are solved in chunks of at most ROUTE_T_BUDGET bytes of transit
+    blocks.  A field of more than 512 swaths keeps its stored order (status FCPP_EUNSUPPORTED)."""
+    ctx = get_context(device)
+    torch = _torch()
+    ss = swathset
+    dev = ss.a.device
+    R = float(radius) if spacing is None else _chord_radius(radius, spacing)
+    soff_all = np.asarray(ss.offsets_host, dtype=np.int64)
+    n, m_all = len(soff_all) - 1, np.diff(soff_all)
+    S = int(starts)
+    if max_sweeps is None:
+        fit = m_all[m_all <= L.ROUTE_MAX_SWATHS]
+        max_sweeps = min(8 * int(fit.max() if fit.size else 0) + 8, 1 << 20)
+    E_all = _route_ends(ss, entry, True, R, reversing, device) if entry is not None else None
+    X_all = _route_ends(ss, exit, False, R, reversing, device) if exit is not None else None
+    order = torch.empty(int(soff_all[-1]), dtype=torch.int32, device=dev)
+    tours = torch.empty((max(S, 0), int(soff_all[-1])), dtype=torch.int32, device=dev)
+    costs = torch.empty((n, max(S, 0)), dtype=torch.float64, device=dev)
+    cost, stored = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
+    winner, sweeps, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    for lo, hi in _route_chunks(soff_all, ROUTE_T_BUDGET):
+        T, toff, toff_h, soff, soff_h, m = _route_transit(ctx, ss, lo, hi, R, reversing)
+        s0 = int(soff_all[lo])
+        Ec = E_all[2 * s0:2 * (s0 + m)] if E_all is not None else None
+        Xc = X_all[2 * s0:2 * (s0 + m)] if X_all is not None else None
+        tr = torch.empty((max(S, 0), m), dtype=torch.int32, device=dev)
+        L.check(ctx.lib.fcpp_route_solve(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), m, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]), _ptr(T),
+                                         _ptr(Ec), _ptr(Xc), S, float(min_gain), int(max_sweeps), _ptr(tr), _ptr(costs[lo:hi]), _ptr(order[s0:s0 + m]),
+                                         _ptr(cost[lo:hi]), _ptr(winner[lo:hi]), _ptr(sweeps[lo:hi]), _ptr(status[lo:hi]), _ptr(stored[lo:hi])))
+        tours[:, s0:s0 + m] = tr
+    return SwathRoute(soff_all, order, cost, stored, winner, sweeps, status, tours, costs)
 
 
 def _polys(polygons):

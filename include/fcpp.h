@@ -550,7 +550,8 @@ int fcpp_rs_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const dou
 /* ---- swaths of ANY polygon field: the batched cut and the angle search ------------------------------------------------------------------
  * Build-defined (the reference's swath generator reads a field's bounding box and four corners only).  Standalone like the connectors:
  * fcpp_batch_plan still takes convex quadrilaterals only and nothing here feeds it.  The caller passes the WORK AREA, already inset by the
- * headland width: there is no polygon inset here, and no routing order.
+ * headland width: there is no polygon inset here.  The records come in the stored order (by line, then along it); the order and direction in
+ * which to DRIVE them is the swath router's, below.
  * A field is a list of rings: ring 0 the outer boundary, further rings holes (obstacles, keep-out areas).  Rings are closed implicitly and
  * may have either orientation; the interior follows the EVEN-ODD rule.  Two CSR levels: ring_offsets (n + 1: fields -> rings, ending at
  * n_rings), vert_offsets (n_rings + 1: rings -> vertices, ending at n_verts) over x, y.
@@ -591,6 +592,60 @@ int fcpp_swath_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, i
                     const double *x_dev, const double *y_dev, const double *angle_dev, double W, double first, double min_length,
                     const int64_t *offsets_dev, int64_t n_total, double *ax_dev, double *ay_dev, double *bx_dev, double *by_dev, int32_t *line_dev,
                     double *length_dev);
+
+/* ---- the swath router: order and direction of one field's swaths --------------------------------------------------------------------------
+ * Build-defined (the reference drives the stored order).  Path planning inside ONE field, batched over fields: nothing here orders fields
+ * or vehicles.  Standalone like the swath entries, whose records it reads; nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_routefn.h, one set of expressions for host and device: the same bits on both).
+ *   - A field has m swath records s = 0 .. m - 1 (fcpp_swath_fill's order) cut at the track angle theta.  Oriented swath p = 2 s + d: d = 0
+ *     drives a -> b with heading theta, d = 1 drives b -> a with heading fl(theta + pi).  p ^ 1 ("p-bar") is the same swath the other way.  N = 2 m.
+ *   - The transit block T of a field, N x N float64 row-major: T[p][q] = the shortest connector length from the exit pose of p to the entry
+ *     pose of q at `radius`, mode 0 Dubins (fcpp_dubins_solve's function), mode 1 Reeds-Shepp (fcpp_rs_solve's); +inf where p and q are the
+ *     same swath.  Every entry is evaluated on its canonical pair -- of (p, q) and (q-bar, p-bar) the one with the smaller p N + q -- and
+ *     both entries get that value: T[p][q] and T[q-bar][p-bar] have equal BITS (a path driven backwards with flipped headings is a path).
+ *   - Block i starts at t_offsets[i] = sum over j < i of (2 m_j)^2 (int64, n + 1 values).  A field whose swath status was non-zero has m = 0;
+ *     a field with m > FCPP_ROUTE_MAX_SWATHS has a block of size 0 and the route status FCPP_EUNSUPPORTED.
+ *   - A tour t[0 .. m - 1] holds one oriented swath of every swath; cost = E[t[0]] + T[t[0]][t[1]] + .. + T[t[m - 2]][t[m - 1]] + X[t[m - 1]],
+ *     added left to right.  E, X: optional, 2 n_total float64 each, field i's N values at 2 swath_offsets[i]: the cost from the field's
+ *     entry pose to each oriented swath and from each oriented swath to the field's exit pose; NULL = zeros.  Below e(u, v) = T[u][v],
+ *     e(START, q) = E[q], e(p, END) = X[p].
+ *   - Candidates c = 0 .. n_starts - 1, 1 <= n_starts <= 64: c = 0 the stored boustrophedon t[k] = 2 k + (k & 1); c = 1 its mirror
+ *     t[k] = 2 k + 1 - (k & 1); c >= 2 nearest neighbour from the oriented swath floor((c - 2) N / (n_starts - 2)): repeatedly the orientation q
+ *     of an unvisited swath with the least T[cur][q], ties to the lowest q (an entry not below +inf, NaN included, counts as +inf).
+ *   - Improvement in sweeps.  A sweep evaluates EVERY move below on the current tour, takes the one with the least delta, ties to the lowest
+ *     code, and applies it iff delta < -min_gain; otherwise the candidate is finished; it also stops after max_sweeps sweeps.  removed and
+ *     added are each summed left to right, delta = added - removed; a NaN delta compares false and is never taken.
+ *       Move A, reverse(i, j), 0 <= i <= j < m, code i m + j: t[i .. j] reversed and every member flipped (i = j turns one swath round).  u = the
+ *         node at i - 1 or START, v = the node at j + 1 or END.  removed = e(u, t[i]) + e(t[j], v); added = e(u, t[j]-bar) + e(t[i]-bar, v).
+ *         (The edges inside keep their value by the equality above.)
+ *       Move B, or-opt, needs m > l: the segment t[i .. i + l - 1], l in {1, 2, 3}, moved to between positions k and k + 1 of the tour, k in
+ *         [-1, m - 1] with k < i - 1 or k >= i + l; r = 0 as it is, r = 1 reversed and flipped.  Code m m + (((l - 1) 2 + r) m + i) (m + 1) + (k + 1).
+ *         f = t[i], g = t[i + l - 1]; (in, out) = (f, g) for r = 0, (g-bar, f-bar) for r = 1; u, v the segment's neighbours, a, b the nodes at k
+ *         and k + 1 (START / END at the ends).  removed = (e(u, f) + e(g, v)) + e(a, b); added = (e(u, v) + e(a, in)) + e(out, b).
+ *     min_gain far above the rounding of a delta (1e-9 m) makes the true cost fall with every applied move; max_sweeps bounds the loop anyway.
+ *   - Per field: every candidate's final cost is recomputed from its final tour; the winner has the least cost, ties to the lowest c;
+ *     sweeps = the largest number of moves any candidate applied (a value below max_sweeps: no candidate stopped on max_sweeps);
+ *     stored = candidate 0's cost AS CONSTRUCTED (what the stored order costs).  Status, int32: 0; FCPP_EUNSUPPORTED for
+ *     m > FCPP_ROUTE_MAX_SWATHS (every candidate's tour is the stored order, the costs NaN); FCPP_EINVAL when `stored` is not finite (a
+ *     non-finite swath, E or X: nothing is improved, every candidate stays as constructed).  For either the route is candidate 0 as
+ *     constructed and the winner 0.  m = 0: an empty tour, cost 0.  m = 1: the cheaper direction under E + X (given a second candidate or a sweep).
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or array, radius <= 0 or not finite, mode not 0 or 1, an
+ * angle not finite or beyond 1e5, n_starts outside 1 .. 64, min_gain negative or not finite, max_sweeps < 0 or > 2^20; FCPP_ESIZE -- negative
+ * sizes, offsets that do not start at 0, decrease or do not end at their total, t_offsets that are not the blocks of the swath offsets.
+ * The offsets are checked on the host: pass the host copies (swath_offsets_host, t_offsets_host) or NULL to have them read back.  Both
+ * entries synchronise. */
+#define FCPP_ROUTE_MAX_SWATHS 512
+/* T_dev (t_total = t_offsets[n] float64): every field's transit block from its records ax .. by (n_total each) and its angle (n). */
+int fcpp_route_transit(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                       const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *angle_dev,
+                       double radius, int mode, const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total, double *T_dev);
+/* tours_dev: n_starts x n_total int32, candidate-major, each field's tour at its swath offsets; costs_dev: n x n_starts float64; route_dev:
+ * n_total int32, the winner's oriented swaths in driving order; cost_dev, stored_dev (float64), winner_dev, sweeps_dev, status_dev (int32):
+ * n each.  Any output may be NULL. */
+int fcpp_route_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                     const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total, const double *T_dev, const double *E_dev,
+                     const double *X_dev, int n_starts, double min_gain, int max_sweeps, int32_t *tours_dev, double *costs_dev,
+                     int32_t *route_dev, double *cost_dev, int32_t *winner_dev, int32_t *sweeps_dev, int32_t *status_dev, double *stored_dev);
 
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
@@ -662,6 +717,14 @@ int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, c
                       const double *y, int64_t A, const double *angles, int per_field, double W, double first, double min_length,
                       int32_t *n_swaths, int32_t *n_lines, double *length, int32_t *status, int64_t *out_offsets, int64_t cap, double *ax,
                       double *ay, double *bx, double *by, int32_t *line, double *seg_length);
+/* The swath router's rule (csrc/fcpp_routefn.h) evaluated on the HOST, on host pointers: fcpp_route_transit's blocks and fcpp_route_solve's
+ * results, what the device results are compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets
+ * are the host's).  Fields are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
+int fcpp_debug_route_transit(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                             const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total, double *T);
+int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
+                     const double *E, const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route,
+                     double *cost, int32_t *winner, int32_t *sweeps, int32_t *status, double *stored);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch

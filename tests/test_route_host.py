@@ -1,0 +1,458 @@
+"""CPU-side tests of the swath router: the four entries exist (header, ctypes binding, libfcpp.so; ABI version still 5), argument errors
+need no device -- and the RULE, through fcpp_debug_route_transit / fcpp_debug_route (csrc/fcpp_routefn.h on the host: the very expressions
+the kernels run), on swaths cut by fcpp_debug_swaths.
+
+Three checkers, none sharing code with the library:
+  * a numpy restatement of the whole rule written from its statement in include/fcpp.h (candidates, every move's code and delta, the
+    tie-breaks, the stop): the same tours integer for integer and the same costs bit for bit, for EVERY candidate.  Sums of two or three
+    float64 terms in numpy round like the library's (-ffp-contract=off), so "bit for bit" is meant literally;
+  * local optimality by another route: every move of the set applied explicitly to a copy of the returned tour and the cost recomputed edge
+    by edge -- no delta formula, no reliance on T[p][q] = T[q^1][p^1];
+  * brute force over all m! 2^m tours of fields with m <= 6.
+Tolerances come from the rule, not from what the code gives: a move may not gain more than min_gain + 1e-9 (1 + cost) -- min_gain is the
+rule's own threshold and 1e-9 relative is the project's length tolerance (tests/test_dubins_host.py), eight orders above the rounding of a
+sum of a few hundred lengths of ~100 m.
+
+R = 6 m, not the usual 8: at W = 3.2 lines five apart are 16 m apart, exactly two turning radii of 8 m, which puts pairs of turning circles
+ON the feasibility edge of the Dubins words; the bits are still equal there, but a restatement that reads lengths is better off elsewhere.
+
+MEASURED on the host twin (square of 40 m with a 16 m hole, angle 0, W = 4, R = 6, 8 starts; test_holed_square_is_routed_better_than_stored
+prints it): Dubins, the stored order costs 585.095 m of connectors, the routed order 254.699 m, ratio 0.435; Reeds-Shepp 374.181 m against
+196.148 m, ratio 0.524."""
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+from tests.test_swaths_host import COMB, ELL, HOLE, RECT, host_cut
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R = 6.0
+MIN_GAIN = 1e-9
+MAX_SWATHS = 512
+HOLED_SQUARE = [[(0, 0), (40, 0), (40, 40), (0, 40)], [(12, 12), (28, 12), (28, 28), (12, 28)]]
+FIELDS = {'holed_square': HOLED_SQUARE, 'ell_hole': [ELL, HOLE], 'rect': RECT, 'comb': COMB}
+
+ENTRIES = {'fcpp_route_transit': 16, 'fcpp_route_solve': 22, 'fcpp_debug_route_transit': 13, 'fcpp_debug_route': 19}
+
+
+@pytest.fixture(scope='module')
+def lib():
+    return L.load()
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def t_offsets(soff):
+    m = np.diff(soff)
+    toff = np.zeros(len(soff), np.int64)
+    np.cumsum(np.where(m > MAX_SWATHS, 0, 4 * m * m), out=toff[1:])
+    return toff
+
+
+def host_transit(cut, radius=R, mode=0, expect=0):
+    """fcpp_debug_route_transit on a host_cut() -> (T flat, toff)"""
+    lib = L.load()
+    soff = cut['offsets']
+    toff = t_offsets(soff)
+    T = np.full(int(toff[-1]), -7.0)
+    ax, ay, bx, by = (np.ascontiguousarray(cut[k]) for k in ('ax', 'ay', 'bx', 'by'))
+    rc = lib.fcpp_debug_route_transit(len(soff) - 1, _p(soff), int(soff[-1]), _p(ax), _p(ay), _p(bx), _p(by), _p(cut['angle']), float(radius), mode,
+                                      _p(toff), int(toff[-1]), _p(T))
+    assert rc == expect, lib.fcpp_last_error()
+    return T, toff
+
+
+def host_route(soff, T, toff, En=None, Xn=None, S=8, min_gain=MIN_GAIN, max_sweeps=None, expect=0):
+    """fcpp_debug_route -> dict of arrays"""
+    lib = L.load()
+    n, nt = len(soff) - 1, int(soff[-1])
+    if max_sweeps is None:
+        max_sweeps = 8 * int(np.diff(soff).max(initial=0)) + 8
+    out = dict(tours=np.full((S, nt), -7, np.int32), costs=np.full((n, S), -7.0), route=np.full(nt, -7, np.int32), cost=np.full(n, -7.0),
+               winner=np.full(n, -7, np.int32), sweeps=np.full(n, -7, np.int32), status=np.full(n, -7, np.int32), stored=np.full(n, -7.0))
+    rc = lib.fcpp_debug_route(n, _p(soff), nt, _p(toff), int(toff[-1]), _p(T), _p(En), _p(Xn), S, float(min_gain), int(max_sweeps), _p(out['tours']),
+                              _p(out['costs']), _p(out['route']), _p(out['cost']), _p(out['winner']), _p(out['sweeps']), _p(out['status']),
+                              _p(out['stored']))
+    assert rc == expect, lib.fcpp_last_error()
+    out['max_sweeps'] = max_sweeps
+    return out
+
+
+def cut_with_angle(fields, angle, W):
+    cut = host_cut(fields, angle, W)
+    cut['angle'] = np.ascontiguousarray(np.broadcast_to(np.asarray(angle, dtype=np.float64), (len(fields),)))
+    return cut
+
+
+def oriented_poses(cut, i):
+    """field i's entry and exit poses per oriented swath, (N, 3) each, as SwathSet.poses forms them"""
+    sl = slice(cut['offsets'][i], cut['offsets'][i + 1])
+    a, b, th = cut['a'][sl], cut['b'][sl], cut['angle'][i]
+    m = len(a)
+    ent, ext = np.zeros((2 * m, 3)), np.zeros((2 * m, 3))
+    ent[0::2, :2], ent[0::2, 2], ext[0::2, :2], ext[0::2, 2] = a, th, b, th
+    ent[1::2, :2], ent[1::2, 2], ext[1::2, :2], ext[1::2, 2] = b, th + np.pi, a, th + np.pi
+    return ent, ext
+
+
+def host_lengths(f, t, radius, mode):
+    """fcpp_debug_dubins / fcpp_debug_rs: the lengths of the pairs f[i] -> t[i]"""
+    lib = L.load()
+    f, t = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3)
+    cols = [np.ascontiguousarray(p[:, k]) for p in (f, t) for k in range(3)]
+    out = np.zeros(len(f))
+    fn = lib.fcpp_debug_rs if mode else lib.fcpp_debug_dubins
+    assert fn(len(f), *[_p(c) for c in cols], float(radius), None, None, _p(out)) == 0
+    return out
+
+
+def ends(cut, mode, radius=R):
+    """E, X (2 n_total each) for an entry pose south-west of every field and an exit pose north-east of it"""
+    En, Xn = [], []
+    for i in range(len(cut['offsets']) - 1):
+        ent, ext = oriented_poses(cut, i)
+        En.append(host_lengths(np.tile([-15.0, -10.0, 0.3], (len(ent), 1)), ent, radius, mode))
+        Xn.append(host_lengths(ext, np.tile([75.0, 60.0, 1.2], (len(ext), 1)), radius, mode))
+    return np.concatenate(En) if En else np.zeros(0), np.concatenate(Xn) if Xn else np.zeros(0)
+
+
+def block(T, toff, cut, i):
+    N = 2 * int(cut['offsets'][i + 1] - cut['offsets'][i])
+    return T[toff[i]:toff[i + 1]].reshape(N, N)
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------------------------
+def ext_matrix(Tb, En, Xn):
+    """(N + 2)^2: row N = START, column N + 1 = END"""
+    N = Tb.shape[0]
+    M = np.zeros((N + 2, N + 2))
+    M[:N, :N] = Tb
+    M[N, :N] = 0.0 if En is None else En
+    M[:N, N + 1] = 0.0 if Xn is None else Xn
+    return M
+
+
+def all_moves(m):
+    """every move of the rule: arrays kind, i, j, l, r, k, code"""
+    rows = [(0, i, j, 0, 0, 0, i * m + j) for i in range(m) for j in range(i, m)]
+    for l in (1, 2, 3):
+        if m <= l:
+            continue
+        for r in (0, 1):
+            for i in range(m - l + 1):
+                for k in range(-1, m):
+                    if k < i - 1 or k >= i + l:
+                        rows.append((1, i, 0, l, r, k, m * m + (((l - 1) * 2 + r) * m + i) * (m + 1) + (k + 1)))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 7).T
+
+
+def ref_cost(M, t):
+    N = M.shape[0] - 2
+    if len(t) == 0:
+        return 0.0
+    c = M[N, t[0]]
+    for k in range(len(t) - 1):
+        c = c + M[t[k], t[k + 1]]
+    return c + M[t[-1], N + 1]
+
+
+def apply_move(t, kind, i, j, l, r, k):
+    t = np.asarray(t)
+    if kind == 0:
+        return np.concatenate([t[:i], t[i:j + 1][::-1] ^ 1, t[j + 1:]])
+    seg = t[i:i + l]
+    if r:
+        seg = seg[::-1] ^ 1
+    rest = np.concatenate([t[:i], t[i + l:]])
+    pos = k + 1 if k < i else k + 1 - l
+    return np.concatenate([rest[:pos], seg, rest[pos:]])
+
+
+def ref_candidate(M, m, c, S, min_gain, max_sweeps, improve=True):
+    N = 2 * m
+    k = np.arange(m)
+    if c == 0:
+        t = 2 * k + (k & 1)
+    elif c == 1:
+        t = 2 * k + 1 - (k & 1)
+    else:
+        cur = (c - 2) * N // (S - 2) if m else 0
+        t, seen = [cur] if m else [], {cur >> 1}
+        while len(t) < m:
+            row = np.where(M[cur, :N] < np.inf, M[cur, :N], np.inf)
+            row[[q for q in range(N) if q >> 1 in seen]] = np.nan
+            cur = int(np.flatnonzero(row == np.nanmin(row))[0])
+            t.append(cur)
+            seen.add(cur >> 1)
+        t = np.asarray(t, dtype=np.int64)
+    applied = 0
+    kind, i, j, l, r, kk, code = all_moves(m)
+    while improve and applied < max_sweeps and len(code):
+        ext = np.concatenate([[N], t, [N + 1]])          # ext[k + 1] = the node at k
+        A = kind == 0
+        d = np.full(len(code), np.nan)
+        u, v, f, g = ext[i[A]], ext[j[A] + 2], t[i[A]], t[j[A]]
+        d[A] = (M[u, g ^ 1] + M[f ^ 1, v]) - (M[u, f] + M[g, v])
+        B = ~A
+        f, g = t[i[B]], t[i[B] + l[B] - 1]
+        inn, out = np.where(r[B] == 1, g ^ 1, f), np.where(r[B] == 1, f ^ 1, g)
+        u, v, a, b = ext[i[B]], ext[i[B] + l[B] + 1], ext[kk[B] + 1], ext[kk[B] + 2]
+        with np.errstate(invalid='ignore'):
+            d[B] = ((M[u, v] + M[a, inn]) + M[out, b]) - ((M[u, f] + M[g, v]) + M[a, b])
+        d = np.where(np.isnan(d), np.inf, d)
+        best = d.min()
+        if not best < -min_gain:
+            break
+        w = np.flatnonzero(d == best)
+        w = w[np.argmin(code[w])]
+        t = apply_move(t, kind[w], i[w], j[w], l[w], r[w], kk[w])
+        applied += 1
+    return t, ref_cost(M, t), applied
+
+
+# ---- tests ----------------------------------------------------------------------------------------------------------------------------
+def test_entries_are_declared_bound_and_exported(lib):
+    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
+    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    assert re.search(r'#define FCPP_ROUTE_MAX_SWATHS %d\b' % MAX_SWATHS, header) and L.ROUTE_MAX_SWATHS == MAX_SWATHS
+    bound = {name: args for name, _, args in L.PROTOTYPES}
+    for name, n_args in ENTRIES.items():
+        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
+        assert m, name
+        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
+        assert hasattr(lib, name)
+    for name in ('swath_transit', 'route_swaths', 'SwathRoute'):
+        assert hasattr(E, name), name
+    assert 'order' in E.swath_route.__code__.co_varnames and 'route_swaths' in E.swath_route.__doc__
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+@pytest.mark.parametrize('W', [4.0, 3.2])
+def test_transit_blocks(W, mode):
+    cut = cut_with_angle(list(FIELDS.values()), [0.0, 0.3, 1.1, 0.0], W)
+    T, toff = host_transit(cut, R, mode)
+    for i in range(len(FIELDS)):
+        Tb = block(T, toff, cut, i)
+        N = len(Tb)
+        assert N == 2 * (cut['offsets'][i + 1] - cut['offsets'][i]) > 0
+        ent, ext = oriented_poses(cut, i)
+        p, q = np.divmod(np.arange(N * N), N)
+        same = (p >> 1) == (q >> 1)
+        assert np.all(np.isposinf(Tb.ravel()[same]))
+        # the canonical pair of an entry: the one with the smaller key
+        swap = (q ^ 1) * N + (p ^ 1) < p * N + q
+        cp, cq = np.where(swap, q ^ 1, p), np.where(swap, p ^ 1, q)
+        want = host_lengths(ext[cp[~same]], ent[cq[~same]], R, mode)
+        assert np.array_equal(bits(Tb.ravel()[~same]), bits(want))
+        assert np.array_equal(bits(Tb), bits(Tb.reshape(N // 2, 2, N // 2, 2)[:, ::-1, :, ::-1].reshape(N, N).T))
+        assert np.all(Tb[~same.reshape(N, N)] >= 0.0)
+
+
+CASES = [(W, mode, with_ends) for W in (4.0, 3.2) for mode in (0, 1) for with_ends in (False, True)]
+
+
+@pytest.fixture(scope='module')
+def solved():
+    """every case once: (cut, T, toff, E, X, result) for the four fields, shared by the tests below and never changed"""
+    out = {}
+    for W, mode, with_ends in CASES:
+        cut = cut_with_angle(list(FIELDS.values()), [0.0, 0.3, 1.1, 0.0], W)
+        T, toff = host_transit(cut, R, mode)
+        En, Xn = ends(cut, mode) if with_ends else (None, None)
+        out[W, mode, with_ends] = (cut, T, toff, En, Xn, host_route(cut['offsets'], T, toff, En, Xn, S=5))
+    return out
+
+
+@pytest.mark.parametrize('W,mode,with_ends', CASES)
+def test_numpy_restatement_every_candidate(solved, W, mode, with_ends):
+    cut, T, toff, En, Xn, res = solved[W, mode, with_ends]
+    soff = cut['offsets']
+    assert np.all(res['status'] == 0)
+    for i in range(len(FIELDS)):
+        m = int(soff[i + 1] - soff[i])
+        sl = slice(2 * soff[i], 2 * soff[i + 1])
+        M = ext_matrix(block(T, toff, cut, i), None if En is None else En[sl], None if Xn is None else Xn[sl])
+        most, costs = 0, []
+        for c in range(5):
+            t, cost, applied = ref_candidate(M, m, c, 5, MIN_GAIN, res['max_sweeps'])
+            assert np.array_equal(t, res['tours'][c, soff[i]:soff[i + 1]]), (i, c)
+            assert bits(cost) == bits(res['costs'][i, c]), (i, c)
+            most = max(most, applied)
+            costs.append(cost)
+        assert res['sweeps'][i] == most < res['max_sweeps']
+        assert res['winner'][i] == int(np.argmin(costs)) and bits(res['cost'][i]) == bits(min(costs))
+        assert np.array_equal(res['route'][soff[i]:soff[i + 1]], res['tours'][res['winner'][i], soff[i]:soff[i + 1]])
+        assert bits(res['stored'][i]) == bits(ref_cost(M, 2 * np.arange(m) + (np.arange(m) & 1)))
+
+
+@pytest.mark.parametrize('W,mode,with_ends', CASES)
+def test_local_optimum_by_explicit_moves(solved, W, mode, with_ends):
+    cut, T, toff, En, Xn, res = solved[W, mode, with_ends]
+    soff = cut['offsets']
+    for i in range(len(FIELDS)):
+        m = int(soff[i + 1] - soff[i])
+        sl = slice(2 * soff[i], 2 * soff[i + 1])
+        M = ext_matrix(block(T, toff, cut, i), None if En is None else En[sl], None if Xn is None else Xn[sl])
+        assert res['sweeps'][i] < res['max_sweeps']          # no candidate stopped on max_sweeps
+        t = res['route'][soff[i]:soff[i + 1]].astype(np.int64)
+        assert np.array_equal(np.sort(t >> 1), np.arange(m))
+        cost = ref_cost(M, t)
+        assert abs(cost - res['cost'][i]) <= 1e-9 * (1 + cost)
+        gains = [cost - ref_cost(M, apply_move(t, *mv[:6])) for mv in all_moves(m).T]
+        assert np.nanmax(gains) <= MIN_GAIN + 1e-9 * (1 + cost), (i, np.nanmax(gains))
+        assert res['cost'][i] <= res['stored'][i]
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+@pytest.mark.parametrize('with_ends', [False, True])
+def test_brute_force_small_fields(mode, with_ends):
+    # cut wide enough for m <= 6: the holed square at W = 14 (3 lines, one through the hole), the L with its hole at W = 15, RECT at W = 1
+    fields, Ws = [HOLED_SQUARE, [ELL, HOLE], RECT], (14.0, 15.0, 1.0)
+    for f, W in zip(fields, Ws):
+        cut = cut_with_angle([f], [0.0], W)
+        m = int(cut['offsets'][1])
+        assert 2 <= m <= 6
+        T, toff = host_transit(cut, R, mode)
+        En, Xn = ends(cut, mode) if with_ends else (None, None)
+        res = host_route(cut['offsets'], T, toff, En, Xn, S=8)
+        M = ext_matrix(block(T, toff, cut, 0), En, Xn)
+        N = 2 * m
+        perms = np.asarray(list(itertools.permutations(range(m))))
+        best = np.inf
+        for dirs in itertools.product((0, 1), repeat=m):
+            t = 2 * perms + np.asarray(dirs)
+            c = M[N, t[:, 0]]
+            for k in range(m - 1):
+                c = c + M[t[:, k], t[:, k + 1]]
+            best = min(best, (c + M[t[:, -1], N + 1]).min())
+        assert np.isfinite(best)
+        assert best <= res['cost'][0] * (1 + 1e-12) and res['cost'][0] <= res['stored'][0]
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_holed_square_is_routed_better_than_stored(mode):
+    """what failed before the router existed: the stored order crosses the hole on every line through it"""
+    cut = cut_with_angle([HOLED_SQUARE], [0.0], 4.0)
+    m = int(cut['offsets'][1])
+    assert m == 14                                # 10 lines, four of them through the hole
+    T, toff = host_transit(cut, R, mode)
+    res = host_route(cut['offsets'], T, toff, S=8)
+    assert res['status'][0] == 0 and res['sweeps'][0] < res['max_sweeps']
+    print('holed square, mode %d: stored %.6f routed %.6f ratio %.4f winner %d' % (mode, res['stored'][0], res['cost'][0],
+                                                                                 res['cost'][0] / res['stored'][0], res['winner'][0]))
+    assert res['cost'][0] < res['stored'][0] - MIN_GAIN
+    assert np.array_equal(np.sort(res['route'] >> 1), np.arange(m))
+    # stored_cost is what a starts = 1, max_sweeps = 0 solve gives
+    plain = host_route(cut['offsets'], T, toff, S=1, max_sweeps=0)
+    assert bits(plain['costs'][0, 0]) == bits(res['stored'][0]) == bits(plain['cost'][0])
+    assert np.array_equal(plain['route'], 2 * np.arange(m) + (np.arange(m) & 1))
+
+
+def test_edges_small_counts_and_statuses():
+    # RECT-like strips 10 m long: a strip k W high has k lines, so m = 0 .. 4; the strip of height 1 has no line at W = 4; a two-vertex
+    # ring gives a non-zero swath status, hence m = 0
+    W = 4.0
+    fields = [[(0, 0), (10, 0), (10, 1), (0, 1)]] + [[(0, 0), (10, 0), (10, W * k), (0, W * k)] for k in (1, 2, 3, 4)] + [[(0, 0), (1, 1)]]
+    cut = cut_with_angle(fields, 0.0, W)
+    assert list(np.diff(cut['offsets'])) == [0, 1, 2, 3, 4, 0] and cut['status'][-1] == L.EINVAL
+    T, toff = host_transit(cut, R, 0)
+    En, Xn = ends(cut, 0)
+    for S, sweeps in ((1, 0), (1, None), (2, 0), (8, None)):
+        res = host_route(cut['offsets'], T, toff, En, Xn, S=S, max_sweeps=sweeps)
+        assert np.all(res['status'] == 0)
+        for i in (0, 5):
+            assert res['cost'][i] == 0.0 and res['stored'][i] == 0.0 and res['winner'][i] == 0 and res['sweeps'][i] == 0
+        # m = 1: the cheaper direction under E + X, given a second candidate or a sweep
+        e0, e1 = En[0] + Xn[0], En[1] + Xn[1]
+        assert bits(res['stored'][1]) == bits(e0)
+        if (S, sweeps) != (1, 0):
+            assert bits(res['cost'][1]) == bits(min(e0, e1)) and res['route'][0] == int(e1 < e0)
+        for i in (2, 3, 4):
+            t = res['route'][cut['offsets'][i]:cut['offsets'][i + 1]]
+            assert np.array_equal(np.sort(t >> 1), np.arange(i)) and res['cost'][i] <= res['stored'][i]
+    # m = 4 against the restatement: segments of l = 3 meet m > l
+    sl = slice(2 * cut['offsets'][4], 2 * cut['offsets'][5])
+    M = ext_matrix(block(T, toff, cut, 4), En[sl], Xn[sl])
+    assert (all_moves(4)[3] == 3).sum() == 2 * 2              # l = 3: i in {0, 1} with one k each, r in {0, 1}
+    res = host_route(cut['offsets'], T, toff, En, Xn, S=8)
+    for c in range(8):
+        t, cost, _ = ref_candidate(M, 4, c, 8, MIN_GAIN, res['max_sweeps'])
+        assert np.array_equal(t, res['tours'][c, cut['offsets'][4]:cut['offsets'][5]]) and bits(cost) == bits(res['costs'][4, c])
+
+
+def test_non_finite_cost_keeps_the_stored_order():
+    cut = cut_with_angle([HOLED_SQUARE, RECT], [0.0, 0.0], 4.0)
+    cut['ax'] = cut['ax'].copy()
+    cut['ax'][3] = np.nan                          # a swath of field 0 that is not finite: its transits are NaN
+    T, toff = host_transit(cut, R, 0)
+    res = host_route(cut['offsets'], T, toff, S=5)
+    m = int(cut['offsets'][1])
+    assert list(res['status']) == [L.EINVAL, 0] and np.isnan(res['stored'][0]) and np.isnan(res['cost'][0])
+    assert res['winner'][0] == 0 and res['sweeps'][0] == 0
+    assert np.array_equal(res['route'][:m], 2 * np.arange(m) + (np.arange(m) & 1))
+    assert np.array_equal(res['tours'][1, :m], 2 * np.arange(m) + 1 - (np.arange(m) & 1))
+    assert np.array_equal(np.sort(res['tours'][4, :m] >> 1), np.arange(m))
+
+
+def test_over_the_cap_is_unsupported_with_the_stored_order():
+    W = 4.0
+    strip = lambda k: [(0, 0), (10, 0), (10, W * k), (0, W * k)]
+    cut = cut_with_angle([strip(513), strip(3)], 0.0, W)
+    assert list(np.diff(cut['offsets'])) == [513, 3]
+    T, toff = host_transit(cut, R, 0)
+    assert list(toff) == [0, 0, 36]
+    res = host_route(cut['offsets'], T, toff, S=3)
+    assert list(res['status']) == [L.EUNSUPPORTED, 0] and np.isnan(res['cost'][0]) and np.all(np.isnan(res['costs'][0]))
+    stored = 2 * np.arange(513) + (np.arange(513) & 1)
+    assert np.array_equal(res['route'][:513], stored) and all(np.array_equal(res['tours'][c, :513], stored) for c in range(3))
+    assert res['winner'][0] == 0 and res['sweeps'][0] == 0 and np.isfinite(res['cost'][1])
+    # 512 is supported (the stored order priced; no sweeps: a sweep at the cap is 1.8e6 moves)
+    cut = cut_with_angle([strip(512)], 0.0, W)
+    T, toff = host_transit(cut, R, 0)
+    res = host_route(cut['offsets'], T, toff, S=1, max_sweeps=0)
+    assert res['status'][0] == 0 and np.isfinite(res['cost'][0]) and toff[1] == 1024 * 1024
+
+
+def test_argument_errors(lib):
+    cut = cut_with_angle([HOLED_SQUARE], [0.0], 4.0)
+    soff, nt = cut['offsets'], int(cut['offsets'][-1])
+    toff = t_offsets(soff)
+    tt = int(toff[-1])
+    T = np.zeros(tt)
+    ax, ay, bx, by = (np.ascontiguousarray(cut[k]) for k in ('ax', 'ay', 'bx', 'by'))
+    ang = cut['angle']
+
+    def transit(n=1, soff=soff, nt=nt, ax=ax, ang=ang, radius=R, mode=0, toff=toff, tt=tt, T=T):
+        return lib.fcpp_debug_route_transit(n, _p(soff), nt, _p(ax), _p(ay), _p(bx), _p(by), _p(ang), float(radius), mode, _p(toff), tt, _p(T))
+
+    def solve(n=1, soff=soff, nt=nt, toff=toff, tt=tt, T=T, S=2, min_gain=1e-9, max_sweeps=4):
+        return lib.fcpp_debug_route(n, _p(soff), nt, _p(toff), tt, _p(T), None, None, S, float(min_gain), max_sweeps, None, None, None, None, None,
+                                    None, None, None)
+    assert transit() == 0 and solve() == 0
+    for kw in (dict(radius=0.0), dict(radius=-1.0), dict(radius=np.inf), dict(radius=np.nan), dict(mode=2), dict(mode=-1), dict(soff=None),
+               dict(toff=None), dict(ax=None), dict(ang=None), dict(T=None), dict(ang=np.array([np.nan])), dict(ang=np.array([2e5]))):
+        assert transit(**kw) == L.EINVAL, kw
+    for kw in (dict(S=0), dict(S=65), dict(min_gain=-1e-9), dict(min_gain=np.inf), dict(min_gain=np.nan), dict(max_sweeps=-1),
+               dict(max_sweeps=(1 << 20) + 1), dict(soff=None), dict(toff=None), dict(T=None)):
+        assert solve(**kw) == L.EINVAL, kw
+    assert solve(max_sweeps=1 << 20, S=64) == 0
+    bad = (dict(n=-1), dict(nt=-1), dict(tt=-1), dict(soff=np.array([1, nt], np.int64)), dict(soff=np.array([0, nt - 1], np.int64)),
+           dict(toff=np.array([0, tt - 4], np.int64), tt=tt - 4), dict(toff=np.array([4, tt], np.int64)), dict(tt=tt + 1),
+           dict(n=2, soff=np.array([0, nt, nt - 1], np.int64), toff=np.array([0, tt, tt], np.int64)))
+    for kw in bad:
+        assert transit(**kw) == L.ESIZE, kw
+        assert solve(**kw) == L.ESIZE, kw
+    # the device entries refuse a NULL handle before anything else
+    assert lib.fcpp_route_transit(None, 1, _p(soff), _p(soff), nt, _p(ax), _p(ay), _p(bx), _p(by), _p(ang), R, 0, _p(toff), _p(toff), tt, _p(T)) == L.EINVAL
+    assert lib.fcpp_route_solve(None, 1, _p(soff), _p(soff), nt, _p(toff), _p(toff), tt, _p(T), None, None, 2, 1e-9, 4, *([None] * 8)) == L.EINVAL
