@@ -298,6 +298,10 @@ int fcpp_batch_point_split(const fcpp_batch *batch, int64_t *quiet_points, int64
 int fcpp_batch_reduce_classes(const fcpp_batch *batch, int64_t *classes_out);
 
 /* ---- standalone operators on caller-supplied paths (CSR offsets, n_paths+1, device) -------
+ * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_* and fcpp_route_*
+ * (tests/test_gpu_guarded.py enforces it for these entries): a device pointer needs only the natural alignment of its element type, an
+ * output is written exactly over its stated extent -- every element of it, nothing beside it --, inputs are never written, and an output
+ * must not overlap an input or another output except where an entry says so.  The other entries keep what their own comments state.
  * The offsets size the launches, so the host needs them: offsets_host (n_paths + 1 values, same content as offsets_dev) spares
  * the call a device-to-host copy and a stream synchronisation; NULL = the library reads offsets_dev back itself.  The tile table
  * built from the offsets is kept in the context and reused while consecutive calls bring the same offsets (compared by

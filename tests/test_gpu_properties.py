@@ -12,20 +12,27 @@ from field_coverage_path_planning_amd import engine as E
 pytestmark = pytest.mark.gpu
 
 
+def ragged_paths(lens, seed, step, n_repeats):
+    """-> (xy, v) of a ragged batch: a random walk cut into paths of the given lengths, n_repeats repeated points or steps below the 1e-6
+    threshold, speeds that jump (also what tests/test_gpu_guarded.py feeds the path operators)"""
+    rng = np.random.default_rng(seed)
+    total = int(sum(lens))
+    xy = np.cumsum(rng.normal(0, step, size=(total, 2)), axis=0) if total else np.zeros((0, 2))
+    for _ in range(n_repeats):
+        if total >= 2:
+            k = int(rng.integers(1, total))
+            xy[k] = xy[k - 1] + (0.0 if rng.random() < 0.5 else 4e-7)
+    v = rng.choice([0.3, 2.5, 4.0, 9.0, 15.0, 28.0], size=total)
+    return xy, v
+
+
 @st.composite
 def ragged_batches(draw):
     n_paths = draw(st.integers(1, 9))
     lens = [draw(st.one_of(st.integers(0, 4), st.integers(5, 80), st.sampled_from([511, 512, 513, 1024, 1025, 1600]))) for _ in range(n_paths)]
     seed = draw(st.integers(0, 2 ** 31 - 1))
-    rng = np.random.default_rng(seed)
-    total = int(sum(lens))
     step = draw(st.sampled_from([0.05, 0.4, 3.0]))
-    xy = np.cumsum(rng.normal(0, step, size=(total, 2)), axis=0) if total else np.zeros((0, 2))
-    for _ in range(draw(st.integers(0, 6))):               # repeated points and steps below the 1e-6 threshold
-        if total >= 2:
-            k = int(rng.integers(1, total))
-            xy[k] = xy[k - 1] + (0.0 if rng.random() < 0.5 else 4e-7)
-    v = rng.choice([0.3, 2.5, 4.0, 9.0, 15.0, 28.0], size=total)
+    xy, v = ragged_paths(lens, seed, step, draw(st.integers(0, 6)))
     a_lon = draw(st.sampled_from([0.05, 1.5, 3.0]))
     a_lat = draw(st.sampled_from([0.5, 2.0]))
     return lens, xy, v, a_lon, a_lat

@@ -12,21 +12,19 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.test_route_host import HOLED_SQUARE, MIN_GAIN, R, bits, cut_with_angle, host_lengths, host_route, host_transit, oriented_poses
+from tests.test_guarded_host import ROUTE_S, ROUTE_STRIPS, ROUTE_W, assert_permutations
+from tests.test_guarded_host import strip as _strip
 from tests.test_swaths_host import ELL, HOLE, rings_of, star
 
 pytestmark = pytest.mark.gpu
 
-W = 3.2
+W = ROUTE_W          # _strip(k): a strip of k working widths of ROUTE_W = 3.2
 NAN_FIELD = np.array(ELL, dtype=np.float64)
 NAN_FIELD[3, 0] = np.nan
 
 
 def _np(t):
     return t.cpu().numpy()
-
-
-def _strip(k):
-    return np.array([(0, 0), (30, 0), (30, W * k), (0, W * k)], dtype=np.float64)
 
 
 KINDS = [(_strip(65), 0.0), (HOLED_SQUARE, 0.0), (_strip(0.25), 0.0), (_strip(1), 0.0), (_strip(2), 0.0), (_strip(3), 0.0), (_strip(4), 0.0),
@@ -121,6 +119,52 @@ def test_solve_equals_host_bit_for_bit(reference, device_cut, monkeypatch, n, mo
         assert len(E._route_chunks(cut['offsets'], E.ROUTE_T_BUDGET)) > 5
         again = E.route_swaths(ss, R, reversing=bool(mode), starts=S, max_sweeps=0)
         assert np.array_equal(_np(again.order), host['route']) and np.array_equal(bits(_np(again.costs)), bits(host['costs']))
+
+
+# ---- tour lengths on the edges of the solve kernel's blocks --------------------------------------------------------------------------------
+# ROUTE_STRIPS: m = 255, 256, 257 -- a tour that ends under, on and over the 256-thread stride -- in both modes; 511 and the cap 512 (int16
+# positions up to 1023, every sweep 1.8e6 moves) Dubins only: their transit blocks are 8 MiB each.
+EDGE_MODES = [(0, len(ROUTE_STRIPS)), (1, 3)]
+
+
+@pytest.fixture(scope='module')
+def edge_reference():
+    """per mode: the host's cut of the strips, its transit blocks and E / X -- computed once, left unchanged"""
+    out = {}
+    for mode, count in EDGE_MODES:
+        fields = [_strip(k) for k in ROUTE_STRIPS[:count]]
+        cut = cut_with_angle(fields, 0.0, W)
+        assert list(np.diff(cut['offsets'])) == list(ROUTE_STRIPS[:count])
+        entry, exit = field_poses(count)
+        out[mode] = (fields, cut, host_transit(cut, R, mode), entry, exit, host_ends(cut, mode, entry, exit))
+    return out
+
+
+@pytest.mark.parametrize('mode,count', EDGE_MODES)
+def test_tour_length_edges_equal_host_bit_for_bit(edge_reference, mode, count):
+    fields, cut, (T, toff), entry, exit, (En, Xn) = edge_reference[mode]
+    ss = E.polygon_swaths(fields, 0.0, W)
+    assert np.array_equal(ss.offsets_host, cut['offsets']) and np.array_equal(bits(_np(ss.a)), bits(cut['a']))
+    devT, dev_toff = E.swath_transit(ss, R, reversing=bool(mode))
+    assert np.array_equal(dev_toff, toff) and np.array_equal(bits(_np(devT)), bits(T))
+    for max_sweeps in (0, 3):
+        host = host_route(cut['offsets'], T, toff, En, Xn, S=ROUTE_S, max_sweeps=max_sweeps)
+        dev = E.route_swaths(ss, R, reversing=bool(mode), entry=entry, exit=exit, starts=ROUTE_S, min_gain=MIN_GAIN, max_sweeps=max_sweeps)
+        assert np.array_equal(_np(dev.tours), host['tours'])
+        assert np.array_equal(bits(_np(dev.costs)), bits(host['costs']))
+        assert np.array_equal(_np(dev.order), host['route']) and np.array_equal(bits(_np(dev.cost)), bits(host['cost']))
+        assert np.array_equal(bits(_np(dev.stored_cost)), bits(host['stored']))
+        for k in ('winner', 'sweeps', 'status'):
+            assert np.array_equal(_np(getattr(dev, k)), host[k]), k
+        # what must actually happen: every field is routed, every tour a permutation, and with sweeps allowed moves ARE applied at the cap
+        assert np.all(host['status'] == 0) and np.isfinite(host['costs']).all()
+        assert_permutations(host['tours'], cut['offsets'])
+        if max_sweeps == 0:
+            assert np.all(host['sweeps'] == 0)
+        else:
+            assert np.all(host['sweeps'] >= 1) and np.all(host['sweeps'] <= 3) and np.all(host['cost'] < host['stored'])
+            if mode == 0:
+                assert cut['offsets'][-1] - cut['offsets'][-2] == 512 and host['sweeps'][-1] >= 1
 
 
 def test_statuses_on_the_device():

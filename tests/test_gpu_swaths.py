@@ -8,6 +8,7 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.test_guarded_host import CAP_FIELDS, EDGE_KINDS, SCORE_ANGLES, assert_edge_shapes, edge_batch
 from tests.test_swaths_host import COMB, ELL, HOLE, OVER_COMB, RECT, host_cut, host_scores, rings_of, star
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +105,57 @@ def test_over_cap_comb_is_unsupported_on_the_device():
     assert _np(dev.status).tolist() == [0, L.EUNSUPPORTED, 0] == host['status'].tolist()
     assert np.array_equal(_np(dev.offsets), host['offsets']) and host['offsets'].tolist() == [0, 10, 10, 36]
     _assert_cut_equal(dev, host)
+
+
+# ---- block edges: the device against the host where the kernel's blocks end --------------------------------------------------------------
+# EDGE_KINDS (tests/test_guarded_host.py, which checks the shapes on the CPU): stars of 62 .. 190 vertices -- a ring that ends exactly on a
+# 63-edge vertex chunk (63, 126, 189) or leaves a one-edge chunk (64, 127) --, a 63-vertex ring with a 64-vertex hole (a chunk edge ON a
+# ring boundary), a square with 70 holes (71 rings: the validity pass strides them 64 at a time) and two spoilt copies of it.
+def _device_cut_equals_host(fields, angles, width, first):
+    host = host_cut(fields, angles, width, first, MIN_LENGTH)
+    dev = E.polygon_swaths(fields, angles, width, first, MIN_LENGTH)
+    assert np.array_equal(_np(dev.status), host['status']) and np.array_equal(_np(dev.n_lines), host['n_lines'])
+    assert np.array_equal(_np(dev.offsets), host['offsets']) and np.array_equal(dev.offsets_host, host['offsets'])
+    assert np.array_equal(np.diff(host['offsets']), host['n_swaths'])
+    _assert_cut_equal(dev, host)
+    return host
+
+
+def _device_scores_equal_host(fields, width, first):
+    host = host_scores(fields, SCORE_ANGLES, width, first, MIN_LENGTH)
+    n_sw, n_ln, length, st = (_np(t) for t in E.swath_scores(fields, SCORE_ANGLES, width, first, MIN_LENGTH))
+    assert np.array_equal(n_sw, host['n_swaths']) and np.array_equal(n_ln, host['n_lines']) and np.array_equal(st, host['status'])
+    assert np.array_equal(_bits(length), _bits(host['length']))
+    return host
+
+
+def test_vertex_chunk_and_ring_count_edges():
+    names, fields, angles = edge_batch()
+    assert names == [k for k, _ in EDGE_KINDS] and {'star63', 'star64', 'star126', 'star127', 'star189', 'ring63_hole64', 'grid71'} <= set(names)
+    host = _device_cut_equals_host(fields, angles, W, FIRST)
+    assert_edge_shapes(names, fields, host)          # vertex counts, 71 rings, status 0 / EINVAL with no records and unchanged offsets
+    sc = _device_scores_equal_host(fields, W, FIRST)
+    for bad in ('grid71_short', 'grid71_nan'):
+        assert (sc['status'][names.index(bad)] == L.EINVAL).all() and (sc['n_swaths'][names.index(bad)] == 0).all()
+    assert (sc['status'][names.index('grid71')] == 0).all()
+    # a field alone: the same bits as inside the batch
+    for name in ('star126', 'ring63_hole64', 'grid71'):
+        i = names.index(name)
+        alone = E.polygon_swaths(fields[i:i + 1], angles[i:i + 1], W, FIRST, MIN_LENGTH)
+        sl = slice(host['offsets'][i], host['offsets'][i + 1])
+        _assert_cut_equal(alone, host, None, sl)
+
+
+def test_exactly_at_the_crossing_cap():
+    """comb(32): 64 crossings on every line through its teeth -- the cap itself, slot 63 of the crossing table; comb(33) beside it is over"""
+    host = _device_cut_equals_host(CAP_FIELDS, 0.0, 5.0, 0.0)
+    assert host['status'].tolist() == [0, L.EUNSUPPORTED] and host['n_swaths'][0] == 2 + 6 * 32 and host['offsets'][2] == host['offsets'][1]
+    assert np.bincount(host['line']).max() == 32
+    _device_scores_equal_host(CAP_FIELDS, 5.0, 0.0)
+    # 80 lines: the capped lines also lie in the second block of 64 lines
+    late = _device_cut_equals_host(CAP_FIELDS, 0.0, 0.5, 0.0)
+    per_line = np.bincount(late['line'], minlength=late['n_lines'][0])
+    assert late['status'].tolist() == [0, L.EUNSUPPORTED] and late['n_lines'][0] > 64 and per_line.max() == 32 and (per_line[64:] == 32).any()
 
 
 @pytest.mark.parametrize('A', [1, 7, 180])
