@@ -169,6 +169,9 @@ PROTOTYPES = [
     ('fcpp_swath_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double] + [_VP] * 4),
     ('fcpp_swath_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_double, C.c_double, C.c_double, _VP, C.c_int64]
      + [_VP] * 6),
+    ('fcpp_inset_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double] + [_VP] * 6),
+    ('fcpp_inset_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double, _VP, _VP, C.c_int64, C.c_int64]
+     + [_VP] * 4),
     ('fcpp_route_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
     ('fcpp_route_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_ga_evolve', C.c_int, [_VP, C.c_int32, C.POINTER(GaConfig), _VP, _VP, _VP, _VP, C.POINTER(GaResult)]),
@@ -180,6 +183,8 @@ PROTOTYPES = [
     ('fcpp_debug_rs', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_swaths', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int, C.c_double, C.c_double, C.c_double]
      + [_VP] * 5 + [C.c_int64] + [_VP] * 6),
+    ('fcpp_debug_inset', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double] + [_VP] * 4
+     + [C.c_int64, C.c_int64] + [_VP] * 4),
     ('fcpp_debug_route_transit', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP]),
     ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),

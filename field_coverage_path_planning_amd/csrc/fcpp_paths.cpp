@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators and the swath router.  Like fcpp_api.cpp:
+// operators, the polygon inset and the swath router.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -10,6 +10,8 @@
 
 #include "fcpp_api_internal.h"
 #include "fcpp_dubins.h"
+#include "fcpp_inset.h"
+#include "fcpp_insetfn.h"
 #include "fcpp_parallel.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
@@ -232,6 +234,55 @@ int swath_fields(fcpp_ctx *c, int64_t n, const int64_t *ring_dev, const int64_t 
     if (rc == FCPP_OK) rc = host_offsets(c, n_rings, vert_dev, vert_host, n_verts, "vert_offsets", verts);
     return rc;
 }
+
+// ---- polygon inset: what fcpp_inset_counts / _fill and fcpp_debug_inset check alike --------------------------------------------------
+int inset_sizes(int64_t n, int64_t n_rings, int64_t n_verts, int64_t D)
+{
+    if (n < 0 || n_rings < 0 || n_verts < 0 || D < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    if (D > 0 && n > INSET_MAX_PAIRS / D) return fail(FCPP_ESIZE, "2^31 (field, distance) pairs or more");
+    return FCPP_OK;
+}
+
+// D distances on the host (the caller's, or read back from the device): positive and finite; arc_step in (0, pi/2]
+int inset_params(fcpp_ctx *c, int64_t D, const double *dev, const double *host, double arc_step)
+{
+    if (!(arc_step > 0.0) || !(arc_step <= INSET_MAX_ARC_STEP)) return fail(FCPP_EINVAL, "arc_step must lie in (0, pi/2]");
+    std::vector<double> h;
+    if (!host && D > 0) {
+        try { h.assign((size_t)D, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+        HIPCHK(hipMemcpyAsync(h.data(), dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        host = h.data();
+    }
+    for (int64_t j = 0; j < D; ++j)
+        if (!(host[j] > 0.0) || !isfinite(host[j])) return fail(FCPP_EINVAL, "distances must be positive and finite");
+    return FCPP_OK;
+}
+
+// the most edges of any field the kernels take
+int inset_max_edges(int64_t n, const std::vector<int64_t> &rings, const std::vector<int64_t> &verts)
+{
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t E = verts[(size_t)rings[(size_t)i + 1]] - verts[(size_t)rings[(size_t)i]];
+        if (E <= INSET_MAX_EDGES) m = std::max(m, E);
+    }
+    return (int)m;
+}
+
+// the piece records of the large fields' launches, alive until the entry has drained the stream
+struct InsetScratch {
+    DevBuf<double> d;
+    DevBuf<int32_t> i;
+    int get(int max_edges, int64_t n_pairs)
+    {
+        size_t nd, ni;
+        inset_scratch_size(max_edges, n_pairs, nd, ni);
+        if (nd) HIPCHK(d.alloc(nd));
+        if (ni) HIPCHK(i.alloc(ni));
+        return FCPP_OK;
+    }
+};
 
 // ---- swath router: what fcpp_route_transit / _solve and their host twins check alike ---------------------------------------------------
 int route_radius(double radius, int mode)
@@ -698,6 +749,112 @@ int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, c
         }
     }
     if (out_offsets) out_offsets[n] = at;
+    return FCPP_OK;
+}
+
+// ---- polygon inset (fcpp_inset.hip; the rule: fcpp_insetfn.h) -----------------------------------------------------------------------
+int fcpp_inset_counts(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                      const double *x, const double *y, int64_t D, const double *dist, double arc_step, int64_t *pair_ring_offsets,
+                      int64_t *pair_ring_offsets_host, int64_t *pair_vert_offsets, int64_t *pair_vert_offsets_host, int32_t *status, double *gap)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!ring_offsets || !vert_offsets || !pair_ring_offsets || !pair_vert_offsets || (n_verts > 0 && (!x || !y)) || (D > 0 && !dist))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = inset_sizes(n, n_rings, n_verts, D);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    rc = inset_params(c, D, dist, nullptr, arc_step);
+    std::vector<int64_t> rings, verts;
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    const int64_t m = n * D;
+    const int max_edges = inset_max_edges(n, rings, verts);
+    hipStream_t st = c->stream;
+    InsetScratch scratch;
+    rc = scratch.get(max_edges, m);
+    if (rc) return rc;
+    DevBuf<int32_t> counts;
+    DevBuf<int64_t> err;
+    HIPCHK(counts.alloc((size_t)(2 * m + 1)));
+    HIPCHK(err.alloc(2));
+    LAUNCHCHK(launch_inset_count(st, n, D, max_edges, ring_offsets, vert_offsets, x, y, dist, arc_step, scratch.d.p, scratch.i.p, counts.p, counts.p + m,
+                                 status, gap));
+    LAUNCHCHK(launch_inset_offsets(st, m, counts.p, pair_ring_offsets, err.p));
+    LAUNCHCHK(launch_inset_offsets(st, m, counts.p + m, pair_vert_offsets, err.p + 1));
+    int64_t bad[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(bad, err.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    if (pair_ring_offsets_host) HIPCHK(hipMemcpyAsync(pair_ring_offsets_host, pair_ring_offsets, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (pair_vert_offsets_host) HIPCHK(hipMemcpyAsync(pair_vert_offsets_host, pair_vert_offsets, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad[0] || bad[1]) return fail(FCPP_ESIZE, "the inset counts could not be scanned");
+    return FCPP_OK;
+}
+
+int fcpp_inset_fill(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                    const double *x, const double *y, int64_t D, const double *dist, double arc_step, const int64_t *pair_ring_offsets,
+                    const int64_t *pair_vert_offsets, int64_t total_rings, int64_t total_verts, int64_t *out_vert_offsets, double *out_x,
+                    double *out_y, int32_t *out_src)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!ring_offsets || !vert_offsets || !pair_ring_offsets || !pair_vert_offsets || (n_verts > 0 && (!x || !y)) || (D > 0 && !dist))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = inset_sizes(n, n_rings, n_verts, D);
+    if (rc == FCPP_OK && (total_rings < 0 || total_verts < 0)) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    rc = inset_params(c, D, dist, nullptr, arc_step);
+    std::vector<int64_t> rings, verts, pro, pvo;
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = host_offsets(c, n * D, pair_ring_offsets, nullptr, total_rings, "pair_ring_offsets", pro);
+    if (rc == FCPP_OK) rc = host_offsets(c, n * D, pair_vert_offsets, nullptr, total_verts, "pair_vert_offsets", pvo);
+    if (rc) return rc;
+    const int max_edges = inset_max_edges(n, rings, verts);
+    InsetScratch scratch;
+    rc = scratch.get(max_edges, n * D);
+    if (rc) return rc;
+    LAUNCHCHK(launch_inset_fill(c->stream, n, D, max_edges, ring_offsets, vert_offsets, x, y, dist, arc_step, scratch.d.p, scratch.i.p, pair_ring_offsets,
+                                pair_vert_offsets, total_rings, total_verts, out_vert_offsets, out_x, out_y, out_src));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_debug_inset(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                     const double *y, int64_t D, const double *dist, double arc_step, int64_t *pair_ring_offsets, int64_t *pair_vert_offsets,
+                     int32_t *status, double *gap, int64_t ring_cap, int64_t vert_cap, int64_t *out_vert_offsets, double *out_x, double *out_y,
+                     int32_t *out_src)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y)) || (D > 0 && !dist)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = inset_sizes(n, n_rings, n_verts, D);
+    if (rc == FCPP_OK && (ring_cap < 0 || vert_cap < 0)) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc == FCPP_OK) rc = inset_params(nullptr, D, nullptr, dist, arc_step);
+    std::vector<int64_t> rings, verts;
+    if (rc == FCPP_OK) rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc) return rc;
+    int64_t ring_at = 0, vert_at = 0;
+    try {
+        InsetWork work;
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < D; ++j) {
+                const int64_t pair = i * D + j;
+                if (pair_ring_offsets) pair_ring_offsets[pair] = ring_at;
+                if (pair_vert_offsets) pair_vert_offsets[pair] = vert_at;
+                const InsetTotals t = inset_field_host(verts.data(), rings[(size_t)i], rings[(size_t)i + 1], x, y, dist[j], arc_step, work,
+                    [&](int32_t r, int32_t off) { if (out_vert_offsets && ring_at + r < ring_cap) out_vert_offsets[ring_at + r] = vert_at + off; },
+                    [&](int32_t at, double vx, double vy, int32_t src) {
+                        if (vert_at + at >= vert_cap) return;
+                        if (out_x) out_x[vert_at + at] = vx;
+                        if (out_y) out_y[vert_at + at] = vy;
+                        if (out_src) out_src[vert_at + at] = src;
+                    });
+                if (status) status[pair] = t.status;
+                if (gap) gap[pair] = t.gap;
+                ring_at += t.n_rings;
+                vert_at += t.n_verts;
+            }
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (pair_ring_offsets) pair_ring_offsets[n * D] = ring_at;
+    if (pair_vert_offsets) pair_vert_offsets[n * D] = vert_at;
+    if (out_vert_offsets && ring_at <= ring_cap) out_vert_offsets[ring_at] = vert_at;
     return FCPP_OK;
 }
 

@@ -1169,8 +1169,9 @@ def _rings(field):
 
 def polygon_fields(fields, device=None):
     """Pack a list of fields for the swath operators.  A field is an (m, 2) array of vertices (one ring) or a list of rings, ring 0 the outer
-    boundary and further rings holes; rings are closed implicitly and may have either orientation (even-odd interior).  Pass the WORK AREA:
-    the boundary already inset by the headland width.  -> PolygonFields on the device (a PolygonFields is returned as it is)."""
+    boundary and further rings holes; rings are closed implicitly and may have either orientation (even-odd interior).  The swath operators take the
+    WORK AREA: headland() makes it from a surveyed boundary (polygon_inset at the headland's width).  -> PolygonFields on the device (a
+    PolygonFields is returned as it is)."""
     if isinstance(fields, PolygonFields):
         return fields
     ctx = get_context(device)
@@ -1186,6 +1187,103 @@ def polygon_fields(fields, device=None):
     xy = np.concatenate(xy) if xy else np.zeros((0, 2))
     return PolygonFields(torch.as_tensor(np.asarray(ro, dtype=np.int64), device=dev), torch.as_tensor(np.asarray(vo, dtype=np.int64), device=dev),
                          torch.as_tensor(np.ascontiguousarray(xy[:, 0]), device=dev), torch.as_tensor(np.ascontiguousarray(xy[:, 1]), device=dev))
+
+
+# ---- headland passes of any polygon field (fcpp_inset_counts / _fill; the rule: include/fcpp.h) -----------------------------------------
+@dataclass
+class InsetSet:
+    """polygon_inset(): the insets of n fields at D distances.  Pair (i, j) = i D + j owns the rings pair_ring_offsets[p] .. [p + 1] and the
+    vertices pair_vert_offsets[p] .. [p + 1]; ring r owns the vertices ring_offsets[r] .. [r + 1].  Rings are closed implicitly, the kept
+    area on their left (outer boundaries counter-clockwise, grown holes clockwise)."""
+    n: int
+    distances: object                   # (D) float64, device
+    pair_ring_offsets: object           # (n D + 1) int64, device; *_host: the numpy copies
+    pair_ring_offsets_host: object
+    pair_vert_offsets: object           # (n D + 1) int64
+    pair_vert_offsets_host: object
+    ring_offsets: object                # (n_rings + 1) int64: rings -> vertices
+    x: object                           # (n_verts) float64
+    y: object
+    src: object                         # (n_verts) int32: the primitive that emitted the vertex, 2 g (edge g's offset) or 2 g + 1 (the arc behind it)
+    status: object                      # (n, D) int32
+    gap: object                         # (n, D) float64: the largest distance between joined pieces [m]
+
+    @property
+    def D(self):
+        return int(self.distances.numel())
+
+    def rings(self, i, j):
+        """the rings of field i at distance j: a list of (m, 2) device tensors"""
+        torch = _torch()
+        p = i * self.D + j
+        r0, r1 = int(self.pair_ring_offsets_host[p]), int(self.pair_ring_offsets_host[p + 1])
+        off = self.ring_offsets[r0:r1 + 1].cpu().numpy()
+        return [torch.stack([self.x[off[k]:off[k + 1]], self.y[off[k]:off[k + 1]]], dim=1) for k in range(r1 - r0)]
+
+    def as_fields(self, j):
+        """the inset of every field at distance j as PolygonFields (a field whose inset is empty, or whose status is non-zero, has no
+        ring there): gathered on the device from the CSR arrays; only the sizes come from the host copies of the offsets"""
+        torch = _torch()
+        dev = self.x.device
+        D = self.D
+        pro_h, pvo_h = self.pair_ring_offsets_host, self.pair_vert_offsets_host
+        pairs = np.arange(self.n, dtype=np.int64) * D + j
+        n_r, n_v = pro_h[pairs + 1] - pro_h[pairs], pvo_h[pairs + 1] - pvo_h[pairs]
+        R, V = int(n_r.sum()), int(n_v.sum())
+        ring_off = torch.as_tensor(np.concatenate([[0], np.cumsum(n_r)]).astype(np.int64), device=dev)
+        pd = torch.as_tensor(pairs, device=dev)
+        cnt_r = self.pair_ring_offsets[pd + 1] - self.pair_ring_offsets[pd]
+        first_r = torch.repeat_interleave(self.pair_ring_offsets[pd] - ring_off[:-1], cnt_r, output_size=R)
+        rid = first_r + torch.arange(R, dtype=torch.int64, device=dev)                  # the rings, in field order
+        cnt_v = self.ring_offsets[rid + 1] - self.ring_offsets[rid]
+        vert_off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        vert_off[1:] = torch.cumsum(cnt_v, dim=0)
+        first_v = torch.repeat_interleave(self.ring_offsets[rid] - vert_off[:-1], cnt_v, output_size=V)
+        vid = first_v + torch.arange(V, dtype=torch.int64, device=dev)
+        return PolygonFields(ring_off, vert_off, self.x[vid].contiguous(), self.y[vid].contiguous())
+
+
+def polygon_inset(fields, distances, arc_step=0.1, device=None):
+    """The inset (fcpp_inset_counts + fcpp_inset_fill): for every field and every distance d [m] of `distances` the boundary of the set of
+    points inside the field that lie at least d from its boundary -- offset edges, and arcs of radius d around reflex vertices drawn as
+    inscribed chords of at most arc_step rad.  The inset may consist of several rings, a hole may merge with the outer boundary, the inset
+    may be empty (0 rings, status 0).  status: 0, FCPP_EINVAL or FCPP_EUNSUPPORTED (more than 1024 edges, a critical distance); such a pair
+    has no rings.  -> InsetSet."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    pf = polygon_fields(fields, device)
+    dist = _dev_f64(distances, dev).reshape(-1)
+    n, D = pf.n, int(dist.numel())
+    m = n * D
+    args = (*pf._head(), D, _ptr(dist), float(arc_step))
+    pro, pvo = torch.empty(m + 1, dtype=torch.int64, device=dev), torch.empty(m + 1, dtype=torch.int64, device=dev)
+    pro_h, pvo_h = np.zeros(m + 1, dtype=np.int64), np.zeros(m + 1, dtype=np.int64)
+    st, gap = torch.zeros((n, D), dtype=torch.int32, device=dev), torch.zeros((n, D), dtype=torch.float64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_inset_counts(ctx.handle, *args, _ptr(pro), _host_ptr(pro_h), _ptr(pvo), _host_ptr(pvo_h), _ptr(st), _ptr(gap)))
+    R, V = int(pro_h[-1]), int(pvo_h[-1])
+    ovo = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    x, y = torch.empty(V, dtype=torch.float64, device=dev), torch.empty(V, dtype=torch.float64, device=dev)
+    src = torch.empty(V, dtype=torch.int32, device=dev)
+    L.check(ctx.lib.fcpp_inset_fill(ctx.handle, *args, _ptr(pro), _ptr(pvo), R, V, _ptr(ovo), _ptr(x), _ptr(y), _ptr(src)))
+    return InsetSet(n, dist, pro, pro_h, pvo, pvo_h, ovo, x, y, src, st, gap)
+
+
+def headland(fields, width, passes, first=None, arc_step=0.1, device=None):
+    """The headland of every field: `passes` >= 1 passes of working width `width` along the boundary (holes included), and what they leave.
+    -> (InsetSet, PolygonFields): the centre lines of passes k = 1 .. passes, the inset at first + (k - 1) width (first: default width / 2),
+    as column k - 1 of the InsetSet; and the work area, the inset at passes x width, which swath_scores, best_swath_angle, polygon_swaths
+    and route_swaths accept as it is.  A field whose work area is empty has no ring there: the swath operators report it as FCPP_EINVAL per
+    field, as they do any field without a ring, and plan the rest."""
+    passes = int(passes)
+    if passes < 1:
+        raise ValueError('passes must be at least 1')
+    pf = polygon_fields(fields, device)
+    f0 = float(width) / 2 if first is None else float(first)
+    lines = polygon_inset(pf, [f0 + k * float(width) for k in range(passes)], arc_step, device)
+    work = polygon_inset(pf, [passes * float(width)], arc_step, device)
+    return lines, work.as_fields(0)
 
 
 def _first(width, first):

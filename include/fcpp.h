@@ -298,7 +298,7 @@ int fcpp_batch_point_split(const fcpp_batch *batch, int64_t *quiet_points, int64
 int fcpp_batch_reduce_classes(const fcpp_batch *batch, int64_t *classes_out);
 
 /* ---- standalone operators on caller-supplied paths (CSR offsets, n_paths+1, device) -------
- * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_* and fcpp_route_*
+ * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_* and fcpp_route_*
  * (tests/test_gpu_guarded.py enforces it for these entries): a device pointer needs only the natural alignment of its element type, an
  * output is written exactly over its stated extent -- every element of it, nothing beside it --, inputs are never written, and an output
  * must not overlap an input or another output except where an entry says so.  The other entries keep what their own comments state.
@@ -553,8 +553,8 @@ int fcpp_rs_sample(fcpp_ctx *ctx, int64_t n, const double *from_x_dev, const dou
 
 /* ---- swaths of ANY polygon field: the batched cut and the angle search ------------------------------------------------------------------
  * Build-defined (the reference's swath generator reads a field's bounding box and four corners only).  Standalone like the connectors:
- * fcpp_batch_plan still takes convex quadrilaterals only and nothing here feeds it.  The caller passes the WORK AREA, already inset by the
- * headland width: there is no polygon inset here.  The records come in the stored order (by line, then along it); the order and direction in
+ * fcpp_batch_plan still takes convex quadrilaterals only and nothing here feeds it.  The caller passes the WORK AREA: a surveyed boundary goes
+ * through the polygon inset below first (fcpp_inset_counts / _fill at the headland's width).  The records come in the stored order (by line, then along it); the order and direction in
  * which to DRIVE them is the swath router's, below.
  * A field is a list of rings: ring 0 the outer boundary, further rings holes (obstacles, keep-out areas).  Rings are closed implicitly and
  * may have either orientation; the interior follows the EVEN-ODD rule.  Two CSR levels: ring_offsets (n + 1: fields -> rings, ending at
@@ -651,6 +651,59 @@ int fcpp_route_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev,
                      const double *X_dev, int n_starts, double min_gain, int max_sweeps, int32_t *tours_dev, double *costs_dev,
                      int32_t *route_dev, double *cost_dev, int32_t *winner_dev, int32_t *sweeps_dev, int32_t *status_dev, double *stored_dev);
 
+/* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
+ * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it
+ * shares and whose input it makes: boundary -> headland pass centre lines -> work area -> swaths -> route.  Nothing here feeds fcpp_batch_plan.
+ * For a field P (ring 0 the outer boundary, further rings holes, as above) and a distance d > 0 the inset is
+ *     I_d(P) = { p inside P : dist(p, boundary of P) >= d }.
+ * Headland pass k of working width W has the centre line  boundary of I_d  at d = first + (k - 1) W (usually first = W / 2); the work area
+ * after m passes is I_(m W).  The boundary of I_d consists of pieces of the edges' inward offset segments and of arcs of radius d around
+ * reflex vertices (the hole side rounds, convex corners stay sharp).  The inset may fall apart into several rings (a narrow neck), a hole
+ * may merge with the outer boundary (a pond near the edge), the inset may be empty (0 rings): all three are ordinary results of status 0.
+ * Input: simple rings of either orientation, holes inside ring 0 and disjoint from one another.  Self-intersecting rings and islands inside
+ * holes give unspecified but bounded output.
+ * THE RULE (csrc/fcpp_insetfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Every ring is oriented by the sign of its shoelace area (summed in vertex order about its first vertex) so that the interior lies on
+ *     the left: ring 0 counter-clockwise, holes clockwise; a ring of the other orientation is traversed backwards.  Edges get the global
+ *     index g in that traversal order; u_g the unit direction, n_g = (-u_y, u_x) the left normal, L_g the length of edge g from p_g to q_g.
+ *   - Primitive 2 g is the offset segment p_g + d n_g + t u_g, 0 <= t <= L_g.  Primitive 2 g + 1 exists when the turn at q_g is to the right:
+ *     the arc q_g + d (n_g cos s + u_g sin s) from n_g (s = 0) to the next edge's normal.
+ *   - A point of a primitive is removed iff its distance to some OTHER edge's segment is below d (1 - 1e-12): a segment skips its own edge,
+ *     an arc its two.  Per (primitive, edge) the parameters at which the primitive meets the edge's two end circles of radius d and two side
+ *     lines at distance d are sorted, and every interval between consecutive ones is judged at its midpoint by the plain point-to-segment
+ *     distance.  (The slack keeps a primitive's own joints; the candidates carry none, so sharp corners are exact.)
+ *   - What survives of a primitive is a set of pieces (start, end); pieces shorter than 1e-9 m are dropped; pieces are numbered by
+ *     (primitive, start parameter).  A field may have at most FCPP_INSET_PIECES_PER_EDGE x its edges pieces.
+ *   - The successor of a piece is the piece whose start is nearest to its end by squared distance, ties to the lowest number.  Walking from
+ *     the lowest unused piece until the walk returns to it gives one ring; rings come in the order of their lowest piece and start there.
+ *     gap = the largest end-to-start distance of the pair's pieces.  A walk that runs into a used piece other than its first is
+ *     FCPP_EUNSUPPORTED: the critical distance at which, say, three offsets pass through one point.
+ *   - A segment piece emits its start point; an arc piece spanning a rad emits ceil(a / arc_step) points at equal angles from its start point
+ *     on, without its end point: all on the circle, so chords are inscribed.  Rings are closed implicitly; the kept area is on the left
+ *     (outer boundaries counter-clockwise, grown holes clockwise).
+ * Status per (field, distance), int32: 0 (an empty inset included); FCPP_EINVAL -- no ring, a ring with fewer than 3 vertices, a vertex that
+ * is not finite; FCPP_EUNSUPPORTED -- more than FCPP_INSET_MAX_EDGES edges, more pieces than the cap, an arc piece of 2^18 points or more,
+ * the degenerate walk.  A pair with a non-zero status has 0 rings, 0 vertices and gap 0; the other pairs of the batch are unaffected.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or array, a distance <= 0 or not finite, arc_step not in
+ * (0, pi/2]; FCPP_ESIZE -- negative sizes, 2^31 (field, distance) pairs or more, offsets that do not start at 0, decrease, or do not end at
+ * the length of the array they index.  (The offsets and the distances are read back for these checks.)  Both entries synchronise.  Fields of
+ * more than 64 edges keep their piece records in device memory for the duration of the call: 208 KiB for each of up to 1024 pairs. */
+#define FCPP_INSET_MAX_EDGES 1024
+#define FCPP_INSET_PIECES_PER_EDGE 4
+/* Counting pass: n fields x D distances (the list is shared by all fields), pair (i, j) = i D + j.  Writes the CSR offsets pairs -> rings and
+ * pairs -> vertices (n D + 1 int64 each; the host pointers: NULL or room for a copy), status (int32) and gap (float64), n D each, may be NULL. */
+int fcpp_inset_counts(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev,
+                      int64_t n_verts, const double *x_dev, const double *y_dev, int64_t D, const double *dist_dev, double arc_step,
+                      int64_t *pair_ring_offsets_dev, int64_t *pair_ring_offsets_host, int64_t *pair_vert_offsets_dev,
+                      int64_t *pair_vert_offsets_host, int32_t *status_dev, double *gap_dev);
+/* fcpp_inset_fill writes the rings of the same fields, distances and arc_step at those offsets: out_vert_offsets_dev (total_rings + 1 int64:
+ * rings -> vertices), out_x_dev, out_y_dev (total_verts float64) and out_src_dev (int32 per vertex: the primitive, 2 g or 2 g + 1, that emitted
+ * it -- odd for arcs, g the source edge).  Any output may be NULL.  A pair never writes outside its own ranges. */
+int fcpp_inset_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                    const double *x_dev, const double *y_dev, int64_t D, const double *dist_dev, double arc_step,
+                    const int64_t *pair_ring_offsets_dev, const int64_t *pair_vert_offsets_dev, int64_t total_rings, int64_t total_verts,
+                    int64_t *out_vert_offsets_dev, double *out_x_dev, double *out_y_dev, int32_t *out_src_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -721,6 +774,14 @@ int fcpp_debug_swaths(int64_t n, const int64_t *ring_offsets, int64_t n_rings, c
                       const double *y, int64_t A, const double *angles, int per_field, double W, double first, double min_length,
                       int32_t *n_swaths, int32_t *n_lines, double *length, int32_t *status, int64_t *out_offsets, int64_t cap, double *ax,
                       double *ay, double *bx, double *by, int32_t *line, double *seg_length);
+/* The polygon inset rule (csrc/fcpp_insetfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device results
+ * are compared with bit for bit.  pair_ring_offsets, pair_vert_offsets (n D + 1), status, gap (n D): any may be NULL.  Ring r of all is
+ * written to out_vert_offsets while r < ring_cap (and the closing entry when the total fits), vertex v to out_x, out_y, out_src while
+ * v < vert_cap: call once with caps of 0 for the sizes, then with them.  A diagnostic, not a fallback. */
+int fcpp_debug_inset(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                     const double *y, int64_t D, const double *dist, double arc_step, int64_t *pair_ring_offsets, int64_t *pair_vert_offsets,
+                     int32_t *status, double *gap, int64_t ring_cap, int64_t vert_cap, int64_t *out_vert_offsets, double *out_x, double *out_y,
+                     int32_t *out_src);
 /* The swath router's rule (csrc/fcpp_routefn.h) evaluated on the HOST, on host pointers: fcpp_route_transit's blocks and fcpp_route_solve's
  * results, what the device results are compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets
  * are the host's).  Fields are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
