@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset and the swath router.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router and the field paths.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -10,6 +10,8 @@
 
 #include "fcpp_api_internal.h"
 #include "fcpp_dubins.h"
+#include "fcpp_fpath.h"
+#include "fcpp_fpathfn.h"
 #include "fcpp_inset.h"
 #include "fcpp_insetfn.h"
 #include "fcpp_parallel.h"
@@ -312,6 +314,31 @@ int route_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_dev, const int64_t
         if (toff[(size_t)i + 1] - toff[(size_t)i] != route_block(soff[(size_t)i + 1] - soff[(size_t)i]))
             return fail(FCPP_ESIZE, "t_offsets do not match the swath counts: block i holds (2 m_i)^2 entries, none for m_i > 512");
     return FCPP_OK;
+}
+
+// ---- field paths: what fcpp_field_path_counts / _fill and fcpp_debug_field_paths check alike ------------------------------------------------
+// the arguments that need no offsets: NULLs, the poses' triples, radius, mode, spacing, the sizes
+int fpath_args(int64_t n, const void *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx, const double *by,
+               const double *length, const double *angle, double radius, int mode, double spacing, const double *ex, const double *ey,
+               const double *eh, const double *xx, const double *xy, const double *xh)
+{
+    if (!swath_offsets || (n_total > 0 && (!ax || !ay || !bx || !by || !length)) || (n > 0 && !angle)) return fail(FCPP_EINVAL, "bad arguments");
+    if (((ex || ey || eh) && !(ex && ey && eh)) || ((xx || xy || xh) && !(xx && xy && xh)))
+        return fail(FCPP_EINVAL, "an entry or exit pose takes all three of x, y and heading");
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n_total < 0 || n > INT32_MAX || n_total > FPATH_MAX_SWATHS) return fail(FCPP_ESIZE, "bad sizes (at most 2^30 swaths)");
+    return FCPP_OK;
+}
+
+// the swath offsets on the host and the angles, checked (read back from the device where the caller has no host copy)
+int fpath_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_dev, const int64_t *soff_host, int64_t n_total, const double *angle_dev,
+                  const double *angle_host, std::vector<int64_t> &soff)
+{
+    int rc = host_offsets(c, n, soff_dev, soff_host, n_total, "swath_offsets", soff);
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle_dev, angle_host);
+    return rc;
 }
 }  // namespace
 
@@ -955,6 +982,149 @@ int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, c
         if (sweeps) sweeps[i] = f.sweeps;
         if (status) status[i] = f.status;
         if (stored) stored[i] = f.stored;
+    });
+    return FCPP_OK;
+}
+
+// ---- field paths (fcpp_fpath.hip; the rule: fcpp_fpathfn.h) ---------------------------------------------------------------------------
+// The fill RECOMPUTES the leg records from its inputs (one more launch of the leg kernel) instead of keeping the counts call's in the
+// context: the two entries stay stateless, and the solves are a small part of the samples' cost.
+int fcpp_field_path_counts(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                           const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,
+                           const int32_t *order, double radius, int mode, double spacing, const double *entry_x, const double *entry_y,
+                           const double *entry_h, const double *exit_x, const double *exit_y, const double *exit_h, int64_t *path_offsets,
+                           int64_t *path_offsets_host, int64_t *leg_offsets, double *work_length, double *transit_length, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!path_offsets || !leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff;
+    rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
+    if (rc) return rc;
+    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
+    const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    DevBuf<FpathLeg> legs;
+    DevBuf<int64_t> cnt;
+    DevBuf<int32_t> seen, own_status;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    HIPCHK(cnt.alloc((size_t)n_slots));
+    HIPCHK(seen.alloc((size_t)n_total));
+    if (!status) { HIPCHK(own_status.alloc((size_t)n)); status = own_status.p; }
+    rc = sample_counts(c, n, path_offsets, path_offsets_host, "a leg or a field has 2^31 samples or more", [&](hipStream_t st, int64_t *err) {
+        if (n_total > 0) { const hipError_t e = hipMemsetAsync(seen.p, 0, (size_t)n_total * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
+        if (n > 0) { const hipError_t e = hipMemsetAsync(status, 0, (size_t)n * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
+        const int e = launch_fpath_legs(st, n, n_total, in, mode, legs.p, cnt.p, seen.p, status);
+        return e ? e : launch_fpath_offsets(st, n, n_total, swath_offsets, legs.p, cnt.p, status, entry_x != nullptr, exit_x != nullptr, leg_offsets,
+                                            path_offsets, work_length, transit_length, err);
+    });
+    return rc;      // (sample_counts has drained the stream: the temporaries die here)
+}
+
+int fcpp_field_path_fill(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                         const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,
+                         const int32_t *order, double radius, int mode, double spacing, const double *entry_x, const double *entry_y,
+                         const double *entry_h, const double *exit_x, const double *exit_y, const double *exit_h, const int64_t *leg_offsets,
+                         int64_t total_samples, double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc == FCPP_OK && (total_samples < 0 || total_samples > ((int64_t)1 << 38))) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff;
+    rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
+    if (rc) return rc;
+    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
+    // The ends of the slot offsets must match the output arrays.  (The fill writes sample q < total_samples of every array and reads the
+    // record of a slot below n_slots whatever lies between the ends: offsets that are not fcpp_field_path_counts' give wrong samples,
+    // never an access outside the arrays.)
+    int64_t ends[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&ends[1], leg_offsets + n_slots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (ends[0] != 0 || ends[1] != total_samples) return fail(FCPP_ESIZE, "leg_offsets do not span [0, total_samples]");
+    const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    DevBuf<FpathLeg> legs;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    LAUNCHCHK(launch_fpath_legs(c->stream, n, n_total, in, mode, legs.p, nullptr, nullptr, nullptr));
+    LAUNCHCHK(launch_fpath_fill(c->stream, n_slots, legs.p, leg_offsets, total_samples, radius, spacing, x, y, heading, kappa, part, gear, leg));
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                           const double *by, const double *length, const double *angle, const int32_t *order, double radius, int mode,
+                           double spacing, const double *entry_x, const double *entry_y, const double *entry_h, const double *exit_x,
+                           const double *exit_y, const double *exit_h, int64_t *path_offsets, int64_t *leg_offsets, double *work_length,
+                           double *transit_length, int32_t *status, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
+                           double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc == FCPP_OK && cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> soff;
+    rc = fpath_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, angle, soff);
+    if (rc) return rc;
+    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
+    const FpathIn in = { soff.data(), ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    std::vector<FpathLeg> legs;
+    std::vector<int64_t> off;
+    std::vector<int32_t> seen;
+    std::vector<char> big;
+    try {
+        legs.resize((size_t)n_slots); off.assign((size_t)n_slots + 1, 0); seen.assign((size_t)n_total, 0); big.assign((size_t)n, 0);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    // the records, the counts (in off, one slot ahead: scanned below), the status and the totals; fields to the library's host threads
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t first = fpath_first_slot(soff.data(), i);
+        double w, t;
+        bool oversize;
+        const int st = mode == 0 ? fpath_field_host<0>(in, i, legs.data() + first, off.data() + first + 1, seen.data() + soff[(size_t)i], w, t, oversize)
+                                 : fpath_field_host<1>(in, i, legs.data() + first, off.data() + first + 1, seen.data() + soff[(size_t)i], w, t, oversize);
+        big[(size_t)i] = oversize;
+        if (status) status[i] = st;
+        if (work_length) work_length[i] = w;
+        if (transit_length) transit_length[i] = t;
+    });
+    for (int64_t i = 0; i < n; ++i)
+        if (big[(size_t)i]) return fail(FCPP_ESIZE, "a leg or a field has 2^31 samples or more");
+    for (int64_t g = 0; g < n_slots; ++g) {
+        off[(size_t)g + 1] += off[(size_t)g];
+        const FpathLeg &lg = legs[(size_t)g];
+        if (leg_word) leg_word[g] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
+        if (leg_seg) for (int k = 0; k < 5; ++k) leg_seg[5 * g + k] = lg.seg[k];
+        if (leg_total) leg_total[g] = lg.total;
+    }
+    if (leg_offsets) memcpy(leg_offsets, off.data(), off.size() * sizeof(int64_t));
+    if (path_offsets) {
+        for (int64_t i = 0; i < n; ++i) path_offsets[i] = off[(size_t)fpath_first_slot(soff.data(), i)];
+        path_offsets[n] = off[(size_t)n_slots];
+    }
+    if (cap == 0 || !(x || y || heading || kappa || part || gear || leg)) return FCPP_OK;
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t first = fpath_first_slot(soff.data(), i), last = fpath_first_slot(soff.data(), i + 1);
+        for (int64_t g = first; g < last; ++g) {
+            const FpathLeg &lg = legs[(size_t)g];
+            const int64_t at = off[(size_t)g], K = off[(size_t)g + 1] - at;
+            for (int64_t k = 0; k < K && at + k < cap; ++k) {
+                double px, py, ph, pk;
+                int pg;
+                fpath_eval(lg, radius, spacing, k, K, px, py, ph, pk, pg);
+                if (x) x[at + k] = px;
+                if (y) y[at + k] = py;
+                if (heading) heading[at + k] = ph;
+                if (kappa) kappa[at + k] = pk;
+                if (part) part[at + k] = (int8_t)lg.part;
+                if (gear) gear[at + k] = (int8_t)pg;
+                if (leg) leg[at + k] = lg.slot;
+            }
+        }
     });
     return FCPP_OK;
 }

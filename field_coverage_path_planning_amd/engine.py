@@ -1572,6 +1572,110 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     return SwathRoute(soff_all, order, cost, stored, winner, sweeps, status, tours, costs)
 
 
+# ---- field paths (fcpp_field_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------------
+@dataclass
+class FieldPaths:
+    """field_paths(): one sampled path per field of a SwathSet, in the CSR form curvature(), speed_plan(), validate() and trajectory()
+    take (offsets=).  Field i owns the samples offsets[i] .. offsets[i + 1]."""
+    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy
+    offsets_host: object
+    x: object                   # (total) float64
+    y: object
+    heading: object             # (total) float64, in (-pi, pi]: the vehicle's heading
+    kappa: object               # (total) float64: signed curvature, 0 on a swath
+    part: object                # (total) int8: 0 swath, 1 connector between swaths, 2 entry connector, 3 exit connector
+    gear: object                # (total) int8: +1, -1 on the reverse runs of a Reeds-Shepp connector
+    leg: object                 # (total) int32: the leg slot within the field: 0 entry, 2 k + 1 the k-th swath driven, 2 k + 2 the connector behind it
+    work_length: object         # (n) float64: the swath lengths in driving order [m]
+    transit_length: object      # (n) float64: the connector lengths, entry and exit included [m]: the route's cost
+    status: object              # (n) int32: 0, or FCPP_EINVAL (an order that is no permutation, a non-finite length or pose): no samples
+    leg_offsets: object         # (2 m_total + n + 1) int64: the first sample of every leg slot; field i's first slot is 2 swath_offsets[i] + i
+
+    def field(self, i):
+        """(x, y, heading, part) of field i: swath_route's tuple"""
+        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+
+
+def _pose_columns(pose, n, dev):
+    """one pose (x, y, heading) per field -> three contiguous device columns (or three None)"""
+    if pose is None:
+        return None, None, None
+    p = _dev_f64(pose, dev).reshape(-1, 3)
+    if p.shape[0] != n:
+        raise ValueError('entry / exit must hold one pose (x, y, heading) per field')
+    p = p.t().contiguous()
+    return p[0], p[1], p[2]
+
+
+def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None):
+    """The path of EVERY field of a SwathSet in one pass on the device (fcpp_field_path_counts + fcpp_field_path_fill) -> FieldPaths.
+    What swath_route gives for one field, for the whole batch and without a host loop: each swath sampled every `spacing` metres (its last
+    sample is its end), consecutive swaths joined by the shortest Dubins path -- Reeds-Shepp if `reversing` -- planned at
+    _chord_radius(radius, spacing) exactly as swath_route plans it, junction samples doubled.  order: None (the stored boustrophedon), a
+    SwathRoute of the same SwathSet (route_swaths: pass it the same `spacing`) or an int array of m_total oriented swaths, each field's
+    local to it.  entry / exit: one pose (x, y, heading) per field, as route_swaths takes them: the connectors it priced are driven (part 2
+    and 3).  A field whose order is no permutation of its swaths, or with a non-finite length or pose, has status FCPP_EINVAL and no samples;
+    the others are unaffected.  Connectors know no boundary (validate() flags what leaves the field)."""
+    ctx = get_context(device)
+    torch = _torch()
+    ss = swathset
+    dev = ss.a.device
+    soff_h = np.ascontiguousarray(ss.offsets_host, dtype=np.int64)
+    n, m = len(soff_h) - 1, int(soff_h[-1])
+    if order is not None:
+        order = order.order if isinstance(order, SwathRoute) else order
+        order = torch.as_tensor(order, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if int(order.numel()) != m:
+            raise ValueError('order must hold one oriented swath per swath of the SwathSet')
+    ax, ay, bx, by = (t[:, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+    ent, ext = _pose_columns(entry, n, dev), _pose_columns(exit, n, dev)
+    args = (n, _ptr(ss.offsets), _host_ptr(soff_h), m, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(ss.length), _ptr(ss.angle), _ptr(order),
+            _chord_radius(radius, spacing), 1 if reversing else 0, float(spacing), *[_ptr(t) for t in ent], *[_ptr(t) for t in ext])
+    off, leg_off = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(2 * m + n + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    work, transit = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_field_path_counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), _ptr(work), _ptr(transit), _ptr(status)))
+    total = int(off_h[-1])
+    x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
+    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
+    leg = torch.empty(total, dtype=torch.int32, device=dev)
+    L.check(ctx.lib.fcpp_field_path_fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), _ptr(leg)))
+    return FieldPaths(off, off_h, x, y, h, kap, part, gear, leg, work, transit, status, leg_off)
+
+
+@dataclass
+class PolygonPlan:
+    """plan_polygon_fields(): every stage's result for the batch"""
+    headland: object            # InsetSet: the centre lines of the headland passes
+    work: object                # PolygonFields: the work areas
+    angle_index: object         # (n) int64: the chosen index into `angles`, -1 where no angle is valid
+    angle: object               # (n) float64: the track angle driven
+    swaths: object              # SwathSet
+    route: object               # SwathRoute
+    paths: object               # FieldPaths
+
+
+def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
+                        arc_step=0.1, device=None):
+    """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
+    `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
+    work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
+    The headland pass rings are returned (headland) but not part of the path."""
+    torch = _torch()
+    lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
+    ang = _dev_f64(angles, work.x.device).reshape(-1)
+    idx, _ = best_swath_angle(work, ang, width, turn_cost, device=device)
+    # (a field without a valid angle is cut at angles[0]: its status there is non-zero, as at every angle)
+    chosen = ang[idx.clamp(min=0)] if ang.numel() else torch.zeros(work.n, dtype=torch.float64, device=work.x.device)
+    ss = polygon_swaths(work, chosen, width, device=device)
+    route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device)
+    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device)
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths)
+
+
 def _polys(polygons):
     """list of vertex lists -> (L.Polys, keep-alive arrays)"""
     offs, px, py = [0], [], []

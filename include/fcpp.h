@@ -298,7 +298,7 @@ int fcpp_batch_point_split(const fcpp_batch *batch, int64_t *quiet_points, int64
 int fcpp_batch_reduce_classes(const fcpp_batch *batch, int64_t *classes_out);
 
 /* ---- standalone operators on caller-supplied paths (CSR offsets, n_paths+1, device) -------
- * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_* and fcpp_route_*
+ * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_*, fcpp_route_* and fcpp_field_path_*
  * (tests/test_gpu_guarded.py enforces it for these entries): a device pointer needs only the natural alignment of its element type, an
  * output is written exactly over its stated extent -- every element of it, nothing beside it --, inputs are never written, and an output
  * must not overlap an input or another output except where an entry says so.  The other entries keep what their own comments state.
@@ -651,6 +651,54 @@ int fcpp_route_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev,
                      const double *X_dev, int n_starts, double min_gain, int max_sweeps, int32_t *tours_dev, double *costs_dev,
                      int32_t *route_dev, double *cost_dev, int32_t *winner_dev, int32_t *sweeps_dev, int32_t *status_dev, double *stored_dev);
 
+/* ---- field paths: every field's routed swaths and connectors as ONE sampled path per field ------------------------------------------------
+ * Build-defined.  The last stage of the polygon-field chain (inset -> angle -> swaths -> route -> PATH), batched like the others: a counts
+ * entry and a fill entry over all fields.  The result is a path set in CSR form (path_offsets), which fcpp_curvature, fcpp_speed_plan,
+ * fcpp_validate and fcpp_trajectory take as it is.  Standalone: nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_fpathfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Leg slots.  A field of m swaths has 2 m + 1 slots: slot 0 the entry connector, slot 2 k + 1 the k-th swath in driving order, slot
+ *     2 k + 2 the connector behind it, the last slot the exit connector.  Field i's first slot is 2 swath_offsets[i] + i.  A slot without
+ *     a leg has no samples: entry / exit without a pose, the one slot of a field with m = 0.  leg_offsets (2 n_total + n + 1 int64) holds
+ *     the first sample of every slot; path_offsets (n + 1) is leg_offsets at the fields' first slots.
+ *   - Driving order.  order = NULL: the stored boustrophedon 2 k + (k & 1).  Else n_total int32, field i's m values at swath_offsets[i]:
+ *     oriented swaths 2 s + d LOCAL to the field, as fcpp_route_solve's route_dev holds them.  An entry outside 0 .. 2 m - 1 or a swath
+ *     named twice gives status[i] = FCPP_EINVAL and no samples for that field -- found on the device; the other fields are unaffected.
+ *   - A swath leg from (sx, sy) to (ex, ey) -- the oriented swath's poses as the router forms them -- of length len = length[s], the
+ *     record's own: floor(len / spacing) + 1 samples, one more at the end when the last lies before it; sample k at
+ *     t = fmin((k spacing) / len, 1), x = sx + t (ex - sx), y likewise; the LAST sample is (ex, ey) itself (a swath of length 0 is that one
+ *     sample).  heading = the oriented heading wrapped into (-pi, pi], curvature 0, gear +1.  A length that is negative, infinite or NaN
+ *     makes the field FCPP_EINVAL.
+ *   - A connector leg: fcpp_dubins_solve's (mode 0) or fcpp_rs_solve's (mode 1) path at `radius` from the exit pose of the leg before (or
+ *     the field's entry pose) to the entry pose of the leg behind (or the field's exit pose), sampled exactly as fcpp_dubins_sample /
+ *     fcpp_rs_sample sample it: the last sample AT the path's end, Reeds-Shepp per gear run with every cusp twice.  Its end lies within
+ *     2^-43 (radius + straight) metres of the next leg's start (the connectors' documented bound).  A pair with no path (word -1: a
+ *     non-finite pose) makes the field FCPP_EINVAL.
+ *   - Junctions stay doubled: a swath's last sample and the connector's first are two samples of one position.
+ *   - part (int8): 0 swath, 1 connector between swaths, 2 entry connector, 3 exit connector.  gear (int8): +1 / -1.  leg (int32): the
+ *     sample's slot within its field.  Every sample is evaluated from its leg alone, never from a neighbouring sample.
+ *   - work_length[i] = the swath lengths added in driving order; transit_length[i] = the connector totals added in the router's order (entry
+ *     first, exit last, left to right): fcpp_route_solve's cost of that order, up to the last bits of the entries the router evaluates
+ *     on the mirrored pair.  Both NaN for a field that is FCPP_EINVAL.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, an entry or exit pose given in part,
+ * radius or spacing <= 0 or not finite, mode not 0 or 1, an angle not finite or beyond 1e5; FCPP_ESIZE -- negative sizes, more than 2^30
+ * swaths, offsets that do not start at 0, decrease or do not end at their total.  FCPP_ESIZE after the count: a leg or a field of 2^31
+ * samples or more.  swath_offsets_host: the host copy, or NULL to have it read back.  Both entries synchronise.
+ * fcpp_field_path_fill recomputes the leg records from the same inputs (nothing is kept in the context between the two calls); every one
+ * of its seven outputs may be NULL. */
+int fcpp_field_path_counts(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                           const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *length_dev,
+                           const double *angle_dev, const int32_t *order_dev, double radius, int mode, double spacing,
+                           const double *entry_x_dev, const double *entry_y_dev, const double *entry_h_dev, const double *exit_x_dev,
+                           const double *exit_y_dev, const double *exit_h_dev, int64_t *path_offsets_dev, int64_t *path_offsets_host,
+                           int64_t *leg_offsets_dev, double *work_length_dev, double *transit_length_dev, int32_t *status_dev);
+int fcpp_field_path_fill(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                         const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *length_dev,
+                         const double *angle_dev, const int32_t *order_dev, double radius, int mode, double spacing,
+                         const double *entry_x_dev, const double *entry_y_dev, const double *entry_h_dev, const double *exit_x_dev,
+                         const double *exit_y_dev, const double *exit_h_dev, const int64_t *leg_offsets_dev, int64_t total_samples,
+                         double *x_dev, double *y_dev, double *heading_dev, double *kappa_dev, int8_t *part_dev, int8_t *gear_dev,
+                         int32_t *leg_dev);
+
 /* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
  * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it
  * shares and whose input it makes: boundary -> headland pass centre lines -> work area -> swaths -> route.  Nothing here feeds fcpp_batch_plan.
@@ -790,6 +838,19 @@ int fcpp_debug_route_transit(int64_t n, const int64_t *swath_offsets, int64_t n_
 int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
                      const double *E, const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route,
                      double *cost, int32_t *winner, int32_t *sweeps, int32_t *status, double *stored);
+/* The field-path rule (csrc/fcpp_fpathfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device results
+ * are compared with bit for bit.  Arguments and the call's errors as for fcpp_field_path_counts / _fill.  path_offsets (n + 1), leg_offsets
+ * (2 n_total + n + 1), work_length, transit_length, status (n): any may be NULL.  leg_word, leg_seg (5 each), leg_total (2 n_total + n slots,
+ * any may be NULL): every slot's record -- a connector's word, segments and total as fcpp_debug_dubins / fcpp_debug_rs give them; a swath's
+ * end point and length in seg[0 .. 2], word -1; zeros and -1 for a slot without a leg.  Sample q of all is written to x .. leg (any may be NULL)
+ * while q < cap: call once with cap = 0 for the sizes, then with them.  Fields are handed to the library's host threads; the results do
+ * not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                           const double *by, const double *length, const double *angle, const int32_t *order, double radius, int mode,
+                           double spacing, const double *entry_x, const double *entry_y, const double *entry_h, const double *exit_x,
+                           const double *exit_y, const double *exit_h, int64_t *path_offsets, int64_t *leg_offsets, double *work_length,
+                           double *transit_length, int32_t *status, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
+                           double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch
