@@ -20,8 +20,7 @@
 #include "fcpp_cover.h"
 #include "fcpp_ga.h"
 #include "fcpp_devplan.h"
-#include "fcpp_dubinsfn.h"
-#include "fcpp_rsfn.h"
+#include "fcpp_connfn.h"
 #include "fcpp_parallel.h"
 
 using namespace fcpp;
@@ -216,6 +215,28 @@ static CutConsts make_cut_consts(TemplateSet &ts, bool device, const BatchTileCo
     if (ts.h_dkc.size() < 2) cc.c_step_min = 0.0;
     return cc;
 }
+
+namespace {
+// fcpp_debug_dubins (MODE 0) / fcpp_debug_rs (MODE 1): the host side of the connectors' one function, a pair at a time
+template <int MODE>
+int debug_conn(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
+               double radius, int32_t *word, double *seg, double *len)
+{
+    constexpr int NSEG = Conn<MODE>::NSEG;
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        int w;
+        double s[NSEG], tot;
+        Conn<MODE>::solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s, tot);
+        if (word) word[i] = w;
+        if (seg) for (int k = 0; k < NSEG; ++k) seg[NSEG * i + k] = s[k];
+        if (len) len[i] = tot;
+    }
+    return FCPP_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1650,35 +1671,13 @@ int fcpp_debug_math_dev(fcpp_ctx *c, int fn, int64_t n, const double *a, const d
 int fcpp_debug_dubins(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
                       double radius, int32_t *word, double *seg, double *len)
 {
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
-    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
-    for (int64_t i = 0; i < n; ++i) {
-        int w;
-        double s0, s1, s2, tot;
-        dubins_solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s0, s1, s2, tot);
-        if (word) word[i] = w;
-        if (seg) { seg[3 * i] = s0; seg[3 * i + 1] = s1; seg[3 * i + 2] = s2; }
-        if (len) len[i] = tot;
-    }
-    return FCPP_OK;
+    return debug_conn<0>(n, fx, fy, fh, tx, ty, th, radius, word, seg, len);
 }
 
 int fcpp_debug_rs(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
                   double radius, int32_t *word, double *seg, double *len)
 {
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
-    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
-    for (int64_t i = 0; i < n; ++i) {
-        int w;
-        double s[5], tot;
-        rs_solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s, tot);
-        if (word) word[i] = w;
-        if (seg) for (int k = 0; k < 5; ++k) seg[5 * i + k] = s[k];
-        if (len) len[i] = tot;
-    }
-    return FCPP_OK;
+    return debug_conn<1>(n, fx, fy, fh, tx, ty, th, radius, word, seg, len);
 }
 
 int fcpp_batch_debug_table(const fcpp_batch *b, int table, void *dst, int64_t cap, int64_t *bytes_out)

@@ -1,5 +1,5 @@
 // fcpp_dubinsfn.h -- the shortest forward-only Dubins path between two poses, and the pose at an arc length along it: ONE function for the
-// host (fcpp_debug_dubins, the tests' checker) and the device (fcpp_dubins.hip), written like fcpp_planfn.h in plain IEEE-754 double
+// host (fcpp_debug_dubins, the tests' checker) and the device (fcpp_conn.hip), written like fcpp_planfn.h in plain IEEE-754 double
 // operations with the transcendentals of fcpp_math.h / fcpp_geom.h (fc_sincos, atan2_fd) and compiled with -ffp-contract=off on both
 // sides, so that both give the same bits.  Build-defined: the reference has no code for it (its roadmap asks for it: doc/两层路径规划器 -
 // 深度优化和改进路线图.md section 1.2; its connectors are straight lines, MLP:1313-1355).

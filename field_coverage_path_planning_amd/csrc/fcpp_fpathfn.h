@@ -3,7 +3,7 @@
 // expressions for the host (fcpp_debug_field_paths, the tests' checker) and the device (fcpp_fpath.hip), written like fcpp_routefn.h in
 // plain IEEE-754 double operations and compiled with -ffp-contract=off on both sides, so that both give the same bits.  Build-defined: the
 // reference has no polygon fields.  Nothing is restated here: the poses are route_pose's, the connectors dubins_solve's / rs_solve's and
-// their samples dubins_pose_at's / rs_pose_in_run's, the count rule is the samplers' (fcpp_samplefn.h, repeated below for the host).
+// their samples, like the count rule, the samplers' own (Conn<MODE>::eval / ::count and sample_count of fcpp_connfn.h).
 //
 // THE RULE (include/fcpp.h states it for callers).
 //   slots     a field of m swaths has 2 m + 1 leg slots: slot 0 the entry connector, slot 2 k + 1 the k-th swath in driving order, slot
@@ -11,7 +11,7 @@
 //             a leg has no samples: entry / exit without a pose, the one slot of a field with m = 0.
 //   order     NULL: the stored boustrophedon route_stored(0, k); else m_total int32, field i's m values at soff[i], each an oriented swath
 //             2 s + d local to the field (SwathRoute.order).  An entry outside 0 .. 2 m - 1 or a swath named twice: the field is EINVAL.
-//   swath     from (sx, sy) to (ex, ey) (route_pose of the oriented swath), len = the record's own length: fpath_count(len, spacing, end)
+//   swath     from (sx, sy) to (ex, ey) (route_pose of the oriented swath), len = the record's own length: sample_count(len, spacing, end)
 //             samples, sample k at t = fmin((k spacing) / len, 1), x = sx + t (ex - sx), y likewise; the LAST sample is (ex, ey) itself (a swath
 //             of length 0 is that one sample); heading dubins_wrap_pi of the oriented heading, curvature 0, gear +1.  A length that is
 //             negative, infinite or NaN: the field is EINVAL.
@@ -57,16 +57,6 @@ struct FpathLeg {
 
 FCPP_HD int64_t fpath_first_slot(const int64_t *soff, int64_t i) { return 2 * soff[i] + i; }
 
-// the samplers' count rule (sample_count of fcpp_samplefn.h): floor(T / step) + 1 samples at k step, one more AT T when with_end is set and
-// the last of them lies before it.  T negative or not finite, or 2^31 samples or more: ++bad and 0.
-FCPP_HD int64_t fpath_count(double T, double step, bool with_end, int64_t &bad)
-{
-    const double q = floor(T / step);
-    if (!(T >= 0.0) || !(q < 2147483646.0)) { ++bad; return 0; }
-    const int64_t K = (int64_t)q + 1;
-    return K + (with_end && (double)(K - 1) * step < T ? 1 : 0);
-}
-
 // the oriented swath at position k of a field's driving order; false when the entry names none
 FCPP_HD bool fpath_oriented(const int32_t *order, int64_t s0, int64_t m, int64_t k, int &p)
 {
@@ -100,7 +90,7 @@ FCPP_HD int64_t fpath_leg(const FpathIn &in, int64_t i, int64_t j, FpathLeg &leg
         leg.x0 = sx; leg.y0 = sy; leg.h0 = dubins_wrap_pi(sh);
         leg.seg[0] = ex; leg.seg[1] = ey; leg.seg[2] = len; leg.total = len;
         if (!(len >= 0.0) || !(len < INFINITY)) { invalid = true; return 0; }
-        const int64_t K = fpath_count(len, in.spacing, true, bad);
+        const int64_t K = sample_count(len, in.spacing, true, false, bad);
         return bad ? FPATH_OVERSIZE : K;
     }
     const bool entry = j == 0, exit = j == 2 * m;
@@ -120,23 +110,10 @@ FCPP_HD int64_t fpath_leg(const FpathIn &in, int64_t i, int64_t j, FpathLeg &leg
     leg.part = entry ? FPATH_PART_ENTRY : (exit ? FPATH_PART_EXIT : FPATH_PART_BETWEEN);
     leg.x0 = x0; leg.y0 = y0; leg.h0 = h0;
     int word;
-    int64_t K = 0;
-    if (MODE == 0) {
-        double s0_, s1_, s2_, total;
-        dubins_solve(x0, y0, h0, x1, y1, h1, in.R, word, s0_, s1_, s2_, total);
-        leg.kind = FPATH_DUBINS; leg.word = word;
-        leg.seg[0] = s0_; leg.seg[1] = s1_; leg.seg[2] = s2_; leg.total = total;
-        if (word < 0) { invalid = true; return 0; }
-        K = fpath_count((s0_ + s1_) + s2_, in.spacing, true, bad);
-    } else {
-        double total;
-        rs_solve(x0, y0, h0, x1, y1, h1, in.R, word, leg.seg, total);
-        leg.kind = FPATH_RS; leg.word = word; leg.total = total;
-        if (word < 0) { invalid = true; return 0; }
-        const RsRuns runs = rs_runs(word, leg.seg);
-        for (int r = 0; r < runs.n; ++r) K += fpath_count(runs.len[r], in.spacing, true, bad);
-        if (K > FPATH_MAX_SAMPLES) ++bad;
-    }
+    Conn<MODE>::solve(x0, y0, h0, x1, y1, h1, in.R, word, leg.seg, leg.total);
+    leg.kind = MODE == 0 ? FPATH_DUBINS : FPATH_RS; leg.word = word;
+    if (word < 0) { invalid = true; return 0; }
+    const int64_t K = Conn<MODE>::count(word, leg.seg, in.spacing, bad);
     return bad ? FPATH_OVERSIZE : K;
 }
 
@@ -153,30 +130,10 @@ FCPP_HD void fpath_eval(const FpathLeg &leg, double R, double spacing, int64_t k
         h = leg.h0; kappa = 0.0; gear = 1;
         return;
     }
-    if (leg.kind == FPATH_DUBINS) {                         // (k_dubins_sample)
-        const double s0 = leg.seg[0], s1 = leg.seg[1], s2 = leg.seg[2], total = (s0 + s1) + s2;
-        double s = (double)k * spacing;
-        if (k >= K - 1 || s > total) s = total;
-        dubins_pose_at(leg.x0, leg.y0, leg.h0, R, leg.word, s0, s1, s2, s, x, y, h, kappa);
-        gear = 1;
-        return;
-    }
-    if (leg.kind == FPATH_RS) {                             // (k_rs_sample)
-        const RsRuns runs = rs_runs(leg.word, leg.seg);
-        int r = 0;
-        int64_t Kr = 0, bad = 0;
-        for (; r < runs.n; ++r) {
-            Kr = fpath_count(runs.len[r], spacing, true, bad);
-            if (k < Kr || r == runs.n - 1) break;
-            k -= Kr;
-        }
-        double e = (double)k * spacing;
-        if (k >= Kr - 1 || e > runs.len[r]) e = runs.len[r];
-        rs_pose_in_run(leg.x0, leg.y0, leg.h0, R, leg.word, leg.seg, runs, r, e, x, y, h, kappa, gear);
-        return;
-    }
     x = y = h = kappa = __builtin_nan("");
     gear = 0;
+    if (leg.kind == FPATH_DUBINS) Conn<0>::eval(leg.x0, leg.y0, leg.h0, R, leg.word, leg.seg, spacing, k, K, x, y, h, kappa, gear);
+    else if (leg.kind == FPATH_RS) Conn<1>::eval(leg.x0, leg.y0, leg.h0, R, leg.word, leg.seg, spacing, k, K, x, y, h, kappa, gear);
 }
 
 // a field's totals from its 2 m + 1 records (a field that is not EINVAL)

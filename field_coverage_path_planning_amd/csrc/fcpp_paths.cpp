@@ -9,7 +9,7 @@
 #include <new>
 
 #include "fcpp_api_internal.h"
-#include "fcpp_dubins.h"
+#include "fcpp_conn.h"
 #include "fcpp_fpath.h"
 #include "fcpp_fpathfn.h"
 #include "fcpp_inset.h"
@@ -17,7 +17,6 @@
 #include "fcpp_parallel.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
-#include "fcpp_rs.h"
 #include "fcpp_swath.h"
 #include "fcpp_swathfn.h"
 #include "fcpp_traj.h"
@@ -160,7 +159,7 @@ int ensure_traj(PathTiling &pt, hipStream_t st)
     return FCPP_OK;
 }
 
-// ---- the fixed-step samplers (fcpp_samplefn.h): what fcpp_trajectory_, fcpp_dubins_ and fcpp_rs_counts / _sample share ----------
+// ---- the fixed-step samplers (fcpp_samplefn.h): what fcpp_trajectory_, fcpp_dubins_ and fcpp_rs_counts / _sample share (the count rule itself: fcpp_connfn.h) ----------
 // A *_counts entry behind its argument checks: launch(stream, err) fills out_offsets and the error word; both come back, the stream is
 // drained, a bad path is FCPP_ESIZE with the entry's message.
 template <class Launch>
@@ -196,6 +195,49 @@ struct SampleOffsets {
         return FCPP_OK;
     }
 };
+
+// ---- connectors: what the Dubins (mode 0) and Reeds-Shepp (mode 1) entries share: the argument checks, the launch ---------------------------
+int conn_solve(fcpp_ctx *c, int mode, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
+               const double *th, double radius, int32_t *word, double *seg, double *len)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
+    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_conn_solve(c->stream, mode, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
+    return FCPP_OK;
+}
+
+int conn_matrix(fcpp_ctx *c, int mode, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
+                const double *ty, const double *th, double radius, double *D, int8_t *word)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (n_from < 0 || n_to < 0 || n_from > CONN_MAX_POSES || n_to > CONN_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
+    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    LAUNCHCHK(launch_conn_matrix(c->stream, mode, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
+    return FCPP_OK;
+}
+
+int conn_sample(fcpp_ctx *c, int mode, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
+                const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
+                double *kappas, int8_t *gears, const int64_t *out_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
+    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    SampleOffsets outs;
+    const int rc = outs.get(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", true);
+    if (rc) return rc;
+    LAUNCHCHK(launch_conn_sample(c->stream, mode, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas, gears));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
 
 // ---- polygon swaths: what fcpp_swath_scores / _counts / _fill and fcpp_debug_swaths check alike ------------------------------------
 int swath_params(double W, double first, double min_length)
@@ -561,29 +603,29 @@ int fcpp_best_connections(fcpp_ctx *c, int64_t n_pairs, const int64_t *fo, const
     return FCPP_OK;
 }
 
-// ---- Dubins connectors (fcpp_dubins.hip; the mathematics: fcpp_dubinsfn.h) --------------------------------------------------------
+// ---- Dubins and Reeds-Shepp connectors (fcpp_conn.hip; the mathematics: fcpp_dubinsfn.h / fcpp_rsfn.h) -----------------------------------
 int fcpp_dubins_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
                       const double *th, double radius, int32_t *word, double *seg, double *len)
 {
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
-    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_dubins_solve(c->stream, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
-    return FCPP_OK;
+    return conn_solve(c, 0, n, fx, fy, fh, tx, ty, th, radius, word, seg, len);
+}
+
+int fcpp_rs_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
+                  const double *th, double radius, int32_t *word, double *seg, double *len)
+{
+    return conn_solve(c, 1, n, fx, fy, fh, tx, ty, th, radius, word, seg, len);
 }
 
 int fcpp_dubins_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
                        const double *ty, const double *th, double radius, double *D, int8_t *word)
 {
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n_from < 0 || n_to < 0 || n_from > DUB_MAX_POSES || n_to > DUB_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
-    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_dubins_matrix(c->stream, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
-    return FCPP_OK;
+    return conn_matrix(c, 0, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word);
+}
+
+int fcpp_rs_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
+                   const double *ty, const double *th, double radius, double *D, int8_t *word)
+{
+    return conn_matrix(c, 1, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word);
 }
 
 int fcpp_dubins_counts(fcpp_ctx *c, int64_t n, const double *len, double spacing, int64_t *out_offsets, int64_t *out_offsets_host)
@@ -596,49 +638,6 @@ int fcpp_dubins_counts(fcpp_ctx *c, int64_t n, const double *len, double spacing
                          [&](hipStream_t st, int64_t *err) { return launch_dubins_counts(st, n, len, spacing, out_offsets, err); });
 }
 
-int fcpp_dubins_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
-                       const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
-                       double *kappas, const int64_t *out_offsets_host)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
-    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
-    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    SampleOffsets outs;
-    const int rc = outs.get(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", true);
-    if (rc) return rc;
-    LAUNCHCHK(launch_dubins_sample(c->stream, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return FCPP_OK;
-}
-
-// ---- Reeds-Shepp connectors (fcpp_rs.hip; the mathematics: fcpp_rsfn.h) -----------------------------------------------------------
-int fcpp_rs_solve(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
-                  const double *th, double radius, int32_t *word, double *seg, double *len)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n < 0 || n > ((int64_t)1 << 36)) return fail(FCPP_ESIZE, "bad sizes");
-    if (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th)) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_rs_solve(c->stream, n, fx, fy, fh, tx, ty, th, radius, word, seg, len));
-    return FCPP_OK;
-}
-
-int fcpp_rs_matrix(fcpp_ctx *c, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to, const double *tx,
-                   const double *ty, const double *th, double radius, double *D, int8_t *word)
-{
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (n_from < 0 || n_to < 0 || n_from > RS_MAX_POSES || n_to > RS_MAX_POSES) return fail(FCPP_ESIZE, "bad sizes (at most 2^20 poses per side)");
-    if ((n_from > 0 && (!fx || !fy || !fh)) || (n_to > 0 && (!tx || !ty || !th))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    LAUNCHCHK(launch_rs_matrix(c->stream, n_from, fx, fy, fh, n_to, tx, ty, th, radius, D, word));
-    return FCPP_OK;
-}
-
 int fcpp_rs_counts(fcpp_ctx *c, int64_t n, const int32_t *word, const double *seg, double spacing, int64_t *out_offsets, int64_t *out_offsets_host)
 {
     if (!c) return fail(FCPP_EINVAL, "context is NULL");
@@ -649,22 +648,18 @@ int fcpp_rs_counts(fcpp_ctx *c, int64_t n, const int32_t *word, const double *se
                          [&](hipStream_t st, int64_t *err) { return launch_rs_counts(st, n, word, seg, spacing, out_offsets, err); });
 }
 
+int fcpp_dubins_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
+                       const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
+                       double *kappas, const int64_t *out_offsets_host)
+{
+    return conn_sample(c, 0, n, fx, fy, fh, radius, word, seg, spacing, out_offsets, total_samples, xs, ys, hs, kappas, nullptr, out_offsets_host);
+}
+
 int fcpp_rs_sample(fcpp_ctx *c, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word,
                    const double *seg, double spacing, const int64_t *out_offsets, int64_t total_samples, double *xs, double *ys, double *hs,
                    double *kappas, int8_t *gears, const int64_t *out_offsets_host)
 {
-    if (!c) return fail(FCPP_EINVAL, "context is NULL");
-    if (!(radius > 0.0) || !isfinite(radius)) return fail(FCPP_EINVAL, "radius must be positive and finite");
-    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
-    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
-    if ((!out_offsets && !out_offsets_host) || (n > 0 && (!fx || !fy || !fh || !word || !seg))) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    SampleOffsets outs;
-    const int rc = outs.get(c, n, out_offsets, out_offsets_host, total_samples, "out_offsets", true);
-    if (rc) return rc;
-    LAUNCHCHK(launch_rs_sample(c->stream, n, fx, fy, fh, radius, word, seg, spacing, outs.dev, total_samples, xs, ys, hs, kappas, gears));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return FCPP_OK;
+    return conn_sample(c, 1, n, fx, fy, fh, radius, word, seg, spacing, out_offsets, total_samples, xs, ys, hs, kappas, gears, out_offsets_host);
 }
 
 // ---- polygon swaths (fcpp_swath.hip; the rule: fcpp_swathfn.h) --------------------------------------------------------------------

@@ -7,7 +7,7 @@
 // CANONICAL pair of an entry evaluates the connector (dubins_solve / rs_solve of fcpp_dubinsfn.h / fcpp_rsfn.h, nothing restated here) and
 // writes both entries that share the value; the other thread leaves.  Which pair is canonical follows the row -- nearly all of a low row,
 // nearly none of a high one -- so wavefronts are all in or all out and the connector is evaluated once per two entries.  Bound by fp64
-// vector issue like k_dubins_matrix / k_rs_matrix; the mirrored entry is a strided 8 B write beside several hundred (Dubins) to several
+// vector issue like k_conn_matrix; the mirrored entry is a strided 8 B write beside several hundred (Dubins) to several
 // thousand (Reeds-Shepp) instructions.
 //
 // k_route_solve: one workgroup of 256 threads per (field, candidate).  The tour lives in LDS as int16 (m <= 512), twice: a move is applied

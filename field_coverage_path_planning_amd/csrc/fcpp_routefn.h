@@ -41,8 +41,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "fcpp_dubinsfn.h"
-#include "fcpp_rsfn.h"
+#include "fcpp_connfn.h"
 
 namespace fcpp {
 
@@ -79,13 +78,8 @@ FCPP_HD double route_transit(const double *ax, const double *ay, const double *b
     route_pose(ax, ay, bx, by, theta, p, true, x0, y0, h0);
     route_pose(ax, ay, bx, by, theta, q, false, x1, y1, h1);
     int word;
-    if (MODE == 0) {
-        double s0, s1, s2;
-        dubins_solve(x0, y0, h0, x1, y1, h1, R, word, s0, s1, s2, total);
-    } else {
-        double seg[5];
-        rs_solve(x0, y0, h0, x1, y1, h1, R, word, seg, total);
-    }
+    double seg[Conn<MODE>::NSEG];
+    Conn<MODE>::solve(x0, y0, h0, x1, y1, h1, R, word, seg, total);
     return total;
 }
 

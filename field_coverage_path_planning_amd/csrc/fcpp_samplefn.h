@@ -1,31 +1,13 @@
-// fcpp_samplefn.h -- device code the fixed-step samplers share (fcpp_traj.hip: a trajectory every dt seconds; fcpp_dubins.hip: a solved
-// path every `spacing` metres; fcpp_rs.hip: the same per gear run): how many samples a path of total T gets, the offsets of all paths' samples, and the path of a sample.
+// fcpp_samplefn.h -- device code the fixed-step samplers share (fcpp_traj.hip: a trajectory every dt seconds; fcpp_conn.hip: a solved
+// connector every `spacing` metres): the offsets of all paths' samples and the path of a sample.  How many samples a path of total T
+// gets is the host+device count rule of fcpp_connfn.h (sample_count, sample_count_runs).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fcpp_connfn.h"
+
 namespace fcpp {
-
-// The count rule: K = floor(T / step) + 1 samples at k * step, and one more AT T when with_end is set and the last of them lies before
-// it.  A total that is negative or not finite, or 2^31 samples or more, counts as bad (K = 0); nan_one: a NaN total is one sample instead.
-__device__ __forceinline__ int64_t sample_count(double T, double step, bool with_end, bool nan_one, int64_t &bad)
-{
-    const double q = floor(T / step);
-    if (nan_one && T != T) return 1;
-    if (!(T >= 0.0) || !(q < 2147483646.0)) { ++bad; return 0; }
-    const int64_t K = (int64_t)q + 1;
-    return K + (with_end && (double)(K - 1) * step < T ? 1 : 0);
-}
-
-// A path sampled PER RUN (fcpp_rs.hip: a Reeds-Shepp path, run by run of one gear): every run of length len[r] by the count rule with its
-// end, so that a junction of two runs is a sample of both.  2^31 samples or more in all count as bad, like one run of that many.
-__device__ __forceinline__ int64_t sample_count_runs(const double *len, int n_runs, double step, int64_t &bad)
-{
-    int64_t K = 0, b = 0;
-    for (int r = 0; r < n_runs; ++r) K += sample_count(len[r], step, true, false, b);
-    if (b || K > 2147483646) { ++bad; return 0; }
-    return K;
-}
 
 // out_offsets (n + 1) = the exclusive scan of the paths' sample counts, err[0] = the number of bad paths.  count_of(p, bad): the samples
 // of path p (0 and ++bad for a bad one).  One workgroup of BLOCK lanes walks the paths BLOCK at a time (an integer scan: exact in any order).

@@ -517,7 +517,7 @@ class BatchResult:
         dp_pose = torch.cat((park_d, torch.where(given, heads_d, dp_dir)[:, None]), dim=1)
         frm = torch.where(is_ap, ap_pose, frm)
         to = torch.where(is_dp, dp_pose, to)
-        out = _rs_paths(b.ctx, frm, to, R, spacing) if reversing else _dubins_paths(b.ctx, frm, to, R, spacing)
+        out = _conn_paths(b.ctx, frm, to, R, spacing, reversing)
         out.update(field=field, kind=kind, from_poses=frm, to_poses=to, radius=R)
         return out
 
@@ -1004,34 +1004,30 @@ def _poses(p, device):
     return t[:, 0].contiguous(), t[:, 1].contiguous(), t[:, 2].contiguous()
 
 
-def _dubins_solve(ctx, f, t, radius):
+def _conn_solve(ctx, f, t, radius, reversing):
+    """fcpp_dubins_solve, or fcpp_rs_solve if `reversing`, on prepared poses -> (word, seg (n, 3) or (n, 5), length)"""
     torch = _torch()
     n = int(f[0].numel())
     if int(t[0].numel()) != n:
         raise ValueError('from_poses and to_poses must hold the same number of poses')
     dev = f[0].device
     word = torch.empty(n, dtype=torch.int32, device=dev)
-    seg = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    seg = torch.empty((n, 5 if reversing else 3), dtype=torch.float64, device=dev)
     length = torch.empty(n, dtype=torch.float64, device=dev)
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_dubins_solve(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
-                                      _ptr(word), _ptr(seg), _ptr(length)))
+    entry = ctx.lib.fcpp_rs_solve if reversing else ctx.lib.fcpp_dubins_solve
+    L.check(entry(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius), _ptr(word), _ptr(seg),
+                  _ptr(length)))
     return word, seg, length
 
 
-def dubins_solve(from_poses, to_poses, radius, device=None):
-    """Shortest forward-only Dubins path of every pair from_poses[i] -> to_poses[i] (fcpp_dubins_solve) for the turning radius `radius` [m].
-    Poses: (n, 3) arrays or tensors (x, y, heading [rad]).  -> (word, seg, length) device tensors: the winning word (0 LSL, 1 LSR, 2 RSL,
-    3 RSR, 4 RLR, 5 LRL; -1 for a pair with a non-finite input), its three segment lengths [m] (n, 3) and their sum."""
+def _conn_solve_poses(from_poses, to_poses, radius, reversing, device):
     ctx = get_context(device)
     dev = _torch().device('cuda', ctx.device)
-    return _dubins_solve(ctx, _poses(from_poses, dev), _poses(to_poses, dev), radius)
+    return _conn_solve(ctx, _poses(from_poses, dev), _poses(to_poses, dev), radius, reversing)
 
 
-def dubins_matrix(from_poses, to_poses, radius, want_words=False, device=None):
-    """The transit matrix D[i][j] = shortest Dubins length from exit pose i to entry pose j (fcpp_dubins_matrix): (n_from, n_to) float64 on
-    the device, the layout ga_fitness / ga_evolve take when both lists are the same nodes.  Not symmetric.  want_words: also the winning
-    words, (n_from, n_to) int8."""
+def _conn_matrix(from_poses, to_poses, radius, want_words, reversing, device):
     ctx = get_context(device)
     torch = _torch()
     dev = torch.device('cuda', ctx.device)
@@ -1040,26 +1036,55 @@ def dubins_matrix(from_poses, to_poses, radius, want_words=False, device=None):
     D = torch.empty((nf, nt), dtype=torch.float64, device=dev)
     W = torch.empty((nf, nt), dtype=torch.int8, device=dev) if want_words else None
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_dubins_matrix(ctx.handle, nf, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), nt, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
-                                       _ptr(D), _ptr(W)))
+    entry = ctx.lib.fcpp_rs_matrix if reversing else ctx.lib.fcpp_dubins_matrix
+    L.check(entry(ctx.handle, nf, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), nt, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius), _ptr(D), _ptr(W)))
     return (D, W) if want_words else D
 
 
-def _dubins_paths(ctx, from_poses, to_poses, radius, spacing):
+def _conn_paths(ctx, from_poses, to_poses, radius, spacing, reversing):
+    """solve + counts + sample -> dict of device tensors; `reversing` adds the samples' gear"""
     torch = _torch()
     dev = torch.device('cuda', ctx.device)
     f, t = _poses(from_poses, dev), _poses(to_poses, dev)
-    word, seg, length = _dubins_solve(ctx, f, t, radius)
+    word, seg, length = _conn_solve(ctx, f, t, radius, reversing)
     n = int(word.numel())
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     off_h = np.zeros(n + 1, dtype=np.int64)
-    L.check(ctx.lib.fcpp_dubins_counts(ctx.handle, n, _ptr(length), float(spacing), _ptr(off), _host_ptr(off_h)))
+    if reversing:
+        L.check(ctx.lib.fcpp_rs_counts(ctx.handle, n, _ptr(word), _ptr(seg), float(spacing), _ptr(off), _host_ptr(off_h)))
+    else:
+        L.check(ctx.lib.fcpp_dubins_counts(ctx.handle, n, _ptr(length), float(spacing), _ptr(off), _host_ptr(off_h)))
     m = int(off_h[-1])
     out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'heading', 'kappa')}
-    L.check(ctx.lib.fcpp_dubins_sample(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing),
-                                       _ptr(off), m, _ptr(out['x']), _ptr(out['y']), _ptr(out['heading']), _ptr(out['kappa']), _host_ptr(off_h)))
+    if reversing:
+        out['gear'] = torch.empty(m, dtype=torch.int8, device=dev)
+    entry = ctx.lib.fcpp_rs_sample if reversing else ctx.lib.fcpp_dubins_sample
+    L.check(entry(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing), _ptr(off), m,
+                  *[_ptr(v) for v in out.values()], _host_ptr(off_h)))
     out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
     return out
+
+
+def _dubins_paths(ctx, from_poses, to_poses, radius, spacing):
+    return _conn_paths(ctx, from_poses, to_poses, radius, spacing, False)
+
+
+def _rs_paths(ctx, from_poses, to_poses, radius, spacing):
+    return _conn_paths(ctx, from_poses, to_poses, radius, spacing, True)
+
+
+def dubins_solve(from_poses, to_poses, radius, device=None):
+    """Shortest forward-only Dubins path of every pair from_poses[i] -> to_poses[i] (fcpp_dubins_solve) for the turning radius `radius` [m].
+    Poses: (n, 3) arrays or tensors (x, y, heading [rad]).  -> (word, seg, length) device tensors: the winning word (0 LSL, 1 LSR, 2 RSL,
+    3 RSR, 4 RLR, 5 LRL; -1 for a pair with a non-finite input), its three segment lengths [m] (n, 3) and their sum."""
+    return _conn_solve_poses(from_poses, to_poses, radius, False, device)
+
+
+def dubins_matrix(from_poses, to_poses, radius, want_words=False, device=None):
+    """The transit matrix D[i][j] = shortest Dubins length from exit pose i to entry pose j (fcpp_dubins_matrix): (n_from, n_to) float64 on
+    the device, the layout ga_fitness / ga_evolve take when both lists are the same nodes.  Not symmetric.  want_words: also the winning
+    words, (n_from, n_to) int8."""
+    return _conn_matrix(from_poses, to_poses, radius, want_words, False, device)
 
 
 def dubins_paths(from_poses, to_poses, radius, spacing, device=None):
@@ -1070,65 +1095,19 @@ def dubins_paths(from_poses, to_poses, radius, spacing, device=None):
     return o['x'], o['y'], o['heading'], o['kappa'], o['offsets']
 
 
-def _rs_solve(ctx, f, t, radius):
-    torch = _torch()
-    n = int(f[0].numel())
-    if int(t[0].numel()) != n:
-        raise ValueError('from_poses and to_poses must hold the same number of poses')
-    dev = f[0].device
-    word = torch.empty(n, dtype=torch.int32, device=dev)
-    seg = torch.empty((n, 5), dtype=torch.float64, device=dev)
-    length = torch.empty(n, dtype=torch.float64, device=dev)
-    ctx.bind_stream()
-    L.check(ctx.lib.fcpp_rs_solve(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
-                                  _ptr(word), _ptr(seg), _ptr(length)))
-    return word, seg, length
-
-
 def rs_solve(from_poses, to_poses, radius, device=None):
     """Shortest Reeds-Shepp path (forward and reverse motion) of every pair from_poses[i] -> to_poses[i] (fcpp_rs_solve) for the turning
     radius `radius` [m].  Poses: (n, 3) arrays or tensors (x, y, heading [rad]).  -> (word, seg, length) device tensors: the winning word
     (0 .. 47, the table of include/fcpp.h: 4 * base + flip + 2 * mirror; -1 for a pair with a non-finite input), its five SIGNED segment
     lengths [m] (n, 5) -- positive forward, negative reverse, unused ones 0 -- and the sum of their magnitudes."""
-    ctx = get_context(device)
-    dev = _torch().device('cuda', ctx.device)
-    return _rs_solve(ctx, _poses(from_poses, dev), _poses(to_poses, dev), radius)
+    return _conn_solve_poses(from_poses, to_poses, radius, True, device)
 
 
 def rs_matrix(from_poses, to_poses, radius, want_words=False, device=None):
     """The transit matrix of a vehicle that reverses: D[i][j] = shortest Reeds-Shepp length from pose i to pose j (fcpp_rs_matrix),
     (n_from, n_to) float64 on the device, the layout ga_fitness / ga_evolve take.  A metric: symmetric (to rounding) when both lists are
     the same poses, with a zero diagonal.  want_words: also the winning words, (n_from, n_to) int8."""
-    ctx = get_context(device)
-    torch = _torch()
-    dev = torch.device('cuda', ctx.device)
-    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
-    nf, nt = int(f[0].numel()), int(t[0].numel())
-    D = torch.empty((nf, nt), dtype=torch.float64, device=dev)
-    W = torch.empty((nf, nt), dtype=torch.int8, device=dev) if want_words else None
-    ctx.bind_stream()
-    L.check(ctx.lib.fcpp_rs_matrix(ctx.handle, nf, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), nt, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), float(radius),
-                                   _ptr(D), _ptr(W)))
-    return (D, W) if want_words else D
-
-
-def _rs_paths(ctx, from_poses, to_poses, radius, spacing):
-    torch = _torch()
-    dev = torch.device('cuda', ctx.device)
-    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
-    word, seg, length = _rs_solve(ctx, f, t, radius)
-    n = int(word.numel())
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    off_h = np.zeros(n + 1, dtype=np.int64)
-    L.check(ctx.lib.fcpp_rs_counts(ctx.handle, n, _ptr(word), _ptr(seg), float(spacing), _ptr(off), _host_ptr(off_h)))
-    m = int(off_h[-1])
-    out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'heading', 'kappa')}
-    out['gear'] = torch.empty(m, dtype=torch.int8, device=dev)
-    L.check(ctx.lib.fcpp_rs_sample(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing),
-                                   _ptr(off), m, _ptr(out['x']), _ptr(out['y']), _ptr(out['heading']), _ptr(out['kappa']), _ptr(out['gear']),
-                                   _host_ptr(off_h)))
-    out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
-    return out
+    return _conn_matrix(from_poses, to_poses, radius, want_words, True, device)
 
 
 def rs_paths(from_poses, to_poses, radius, spacing, device=None):
@@ -1421,8 +1400,8 @@ def swath_route(swathset, i, radius, spacing, reversing=False, device=None, orde
         length = length[idx]
     con = None
     if m > 1:
-        con = (rs_paths if reversing else dubins_paths)(end[:-1], start[1:], _chord_radius(radius, spacing), spacing, device=device)
-    c_off = con[-1].cpu().numpy() if con is not None else None
+        con = _conn_paths(get_context(device), end[:-1], start[1:], _chord_radius(radius, spacing), spacing, reversing)
+    c_off = con['offsets_host'] if con is not None else None
     length = length.cpu().numpy()
     xs, ys, hs, parts = [], [], [], []
     for j in range(m):
@@ -1437,7 +1416,7 @@ def swath_route(swathset, i, radius, spacing, reversing=False, device=None, orde
         xs.append(x); ys.append(y); hs.append(start[j, 2].expand(x.numel())); parts.append(torch.zeros(x.numel(), dtype=torch.int8, device=dev))
         if j + 1 < m:
             sl = slice(int(c_off[j]), int(c_off[j + 1]))
-            xs.append(con[0][sl]); ys.append(con[1][sl]); hs.append(con[2][sl])
+            xs.append(con['x'][sl]); ys.append(con['y'][sl]); hs.append(con['heading'][sl])
             parts.append(torch.ones(sl.stop - sl.start, dtype=torch.int8, device=dev))
     return torch.cat(xs), torch.cat(ys), torch.cat(hs), torch.cat(parts)
 
@@ -1527,8 +1506,8 @@ def _route_ends(ss, pose, at_entry, radius, reversing, device):
     first, second = (ss.a, ss.b) if at_entry else (ss.b, ss.a)
     own = torch.stack([torch.cat([first, th], dim=1), torch.cat([second, th + np.pi], dim=1)], dim=1).reshape(-1, 3)
     far = torch.repeat_interleave(pose, 2 * counts, dim=0)
-    solve = rs_solve if reversing else dubins_solve
-    return (solve(far, own, radius, device)[2] if at_entry else solve(own, far, radius, device)[2]).contiguous()
+    frm, to = (far, own) if at_entry else (own, far)
+    return _conn_solve_poses(frm, to, radius, reversing, device)[2].contiguous()
 
 
 def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, starts=8, min_gain=1e-9, max_sweeps=None, spacing=None, device=None):

@@ -1,4 +1,4 @@
-"""GPU tests of the Dubins connectors (run with -m gpu on an MI355X): the kernels of csrc/fcpp_dubins.hip against the same function on the
+"""GPU tests of the Dubins connectors (run with -m gpu on an MI355X): the kernels of csrc/fcpp_conn.hip against the same function on the
 host (fcpp_debug_dubins) BIT FOR BIT, the sampler against the numpy restatement of tests/test_dubins_host.py, the sampled paths through
 the project's own operators (curvature, trajectory, GA fitness), and BatchResult.drivable_connectors / the planner mirror.
 

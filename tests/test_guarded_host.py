@@ -39,9 +39,8 @@ def solve_pairs(n, reversing=False):
 
 
 def tile_rows(reversing=False):
-    """the row-tile constant of the matrix kernel, from the header the kernel is compiled with"""
-    name, macro = ('fcpp_rs.h', 'RS_ROWS') if reversing else ('fcpp_dubins.h', 'DUB_ROWS')
-    return int(re.search(r'\b%s = (\d+)' % macro, open(os.path.join(CSRC, name)).read()).group(1))
+    """the row-tile constant of the matrix kernel (one for both connector kinds), from the header the kernel is compiled with"""
+    return int(re.search(r'\bCONN_ROWS = (\d+)', open(os.path.join(CSRC, 'fcpp_conn.h')).read()).group(1))
 
 
 def matrix_shapes(reversing=False):

@@ -1,6 +1,6 @@
 """Times the Dubins entries (HIP events around each call, --reps repetitions after --warmup; median, minimum and maximum):
   (a) fcpp_dubins_matrix at 4096 x 4096 and 16384 x 16384 poses drawn as in the tests (positions U[0, 5000)^2, headings U(-pi, pi], R = 8):
-      pairs/s -- beside the number of vector instructions per pair counted in the compiled kernel's ISA (the pair loop of k_dubins_matrix:
+      pairs/s -- beside the number of vector instructions per pair counted in the compiled kernel's ISA (the pair loop of k_conn_matrix<0>:
       every v_* instruction, and those on float64) and the issue-rate bound that follows from it.  On gfx950 a SIMD issues a vector
       instruction for 16 lanes per clock, float64 at the same rate as 32-bit ones: 256 CUs x 4 SIMDs x 16 lanes x clock lane-instructions
       per second.  The count is static (all five argument classes of each atan2 are counted though a lane takes one), so the bound is on
@@ -48,12 +48,12 @@ def _timed(torch, fn, reps, warmup):
 
 
 def isa_counts():
-    """vector instructions in the pair loop of k_dubins_matrix, from the device assembly of csrc/fcpp_dubins.hip (the Makefile's flags)
+    """vector instructions in the pair loop of k_conn_matrix<0>, from the device assembly of csrc/fcpp_conn.hip (the Makefile's flags)
     -> dict, or a note why it could not be counted"""
     hipcc = os.environ.get('HIPCC') or shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     if not os.path.exists(hipcc):
         return {'note': 'not counted: no hipcc'}
-    src = os.path.join(REPO, 'field_coverage_path_planning_amd', 'csrc', 'fcpp_dubins.hip')
+    src = os.path.join(REPO, 'field_coverage_path_planning_amd', 'csrc', 'fcpp_conn.hip')
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, 'dubins.s')
         cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '--cuda-device-only', '-S', '-o', out,
@@ -62,7 +62,7 @@ def isa_counts():
         if r.returncode != 0:
             return {'note': 'not counted: ' + r.stderr[-300:]}
         lines = open(out).read().split('\n')
-    start = next(i for i, l in enumerate(lines) if re.match(r'^_ZN4fcpp15k_dubins_matrix\w*:', l))
+    start = next(i for i, l in enumerate(lines) if re.match(r'^_ZN4fcpp13k_conn_matrixILi0EE\w*:', l))
     end = next(i for i in range(start, len(lines)) if 's_endpgm' in lines[i])
     body = lines[start:end]
     head = next(i for i, l in enumerate(body) if 'Loop Header' in l)
@@ -122,7 +122,7 @@ def main():
     frm = np.column_stack((rng.uniform(0, 5000, (n, 2)), -rng.uniform(-np.pi, np.pi, n)))
     to = np.column_stack((frm[:, :2] + rng.uniform(-1000, 1000, (n, 2)), -rng.uniform(-np.pi, np.pi, n)))
     f, t = E._poses(frm, dev), E._poses(to, dev)
-    word, seg, length = E._dubins_solve(ctx, f, t, R)
+    word, seg, length = E._conn_solve(ctx, f, t, R, False)
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     off_h = np.zeros(n + 1, dtype=np.int64)
     L.check(lib.fcpp_dubins_counts(ctx.handle, n, P(length), args.spacing, P(off), HP(off_h)))

@@ -95,7 +95,7 @@ def main():
     if args.isa:
         isa = json.load(open(args.isa))
     else:
-        isa = {'rs': isa_counts('fcpp_rs.hip', 'k_rs_matrix'), 'dubins': isa_counts('fcpp_dubins.hip', 'k_dubins_matrix')}
+        isa = {'rs': isa_counts('fcpp_conn.hip', 'k_conn_matrixILi1EE'), 'dubins': isa_counts('fcpp_conn.hip', 'k_conn_matrixILi0EE')}
     if args.isa_only:
         line = json.dumps(isa)
         if args.out:
@@ -142,7 +142,7 @@ def main():
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     off_h = np.zeros(n + 1, dtype=np.int64)
     rec['sample'] = {'paths': n, 'spacing': args.spacing}
-    word, seg, length = E._rs_solve(ctx, f, t, R)
+    word, seg, length = E._conn_solve(ctx, f, t, R, True)
     L.check(lib.fcpp_rs_counts(ctx.handle, n, P(word), P(seg), args.spacing, P(off), HP(off_h)))
     m = int(off_h[-1])
     outs = [torch.empty(m, dtype=torch.float64, device=dev) for _ in range(4)]
@@ -151,7 +151,7 @@ def main():
                                                           *[P(o) for o in outs], P(gear), HP(off_h))), args.reps, args.warmup)
     rec['sample']['rs'] = {'samples': m, 'time': st, 'samples_per_s': m / (st['median_ms'] * 1e-3), 'bytes_written_per_s': 33.0 * m / (st['median_ms'] * 1e-3)}
     del outs, gear
-    word, seg, length = E._dubins_solve(ctx, f, t, R)
+    word, seg, length = E._conn_solve(ctx, f, t, R, False)
     L.check(lib.fcpp_dubins_counts(ctx.handle, n, P(length), args.spacing, P(off), HP(off_h)))
     m = int(off_h[-1])
     outs = [torch.empty(m, dtype=torch.float64, device=dev) for _ in range(4)]
