@@ -177,6 +177,10 @@ PROTOTYPES = [
     ('fcpp_field_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 12),
     ('fcpp_field_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 7
      + [C.c_int64] + [_VP] * 7),
+    ('fcpp_headland_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
+     + [_VP] * 7),
+    ('fcpp_headland_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
+     + [_VP, C.c_int64] + [_VP] * 7),
     ('fcpp_ga_evolve', C.c_int, [_VP, C.c_int32, C.POINTER(GaConfig), _VP, _VP, _VP, _VP, C.POINTER(GaResult)]),
     ('fcpp_cover_grid', C.c_int, [_VP, C.c_int64, C.POINTER(CoverJob), C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_gather', C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, c_i64_p, _VP, C.c_int]),
@@ -192,6 +196,8 @@ PROTOTYPES = [
     ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_debug_field_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 14 + [C.c_int64]
      + [_VP] * 7),
+    ('fcpp_debug_headland_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
+     + [_VP] * 10 + [C.c_int64] + [_VP] * 7),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
 ]
 

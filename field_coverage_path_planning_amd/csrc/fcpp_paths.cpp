@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset, the swath router and the field paths.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router, the field paths and the headland paths.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -12,6 +12,8 @@
 #include "fcpp_conn.h"
 #include "fcpp_fpath.h"
 #include "fcpp_fpathfn.h"
+#include "fcpp_hpath.h"
+#include "fcpp_hpathfn.h"
 #include "fcpp_inset.h"
 #include "fcpp_insetfn.h"
 #include "fcpp_parallel.h"
@@ -381,6 +383,20 @@ int fpath_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_dev, const int64_t
     int rc = host_offsets(c, n, soff_dev, soff_host, n_total, "swath_offsets", soff);
     if (rc == FCPP_OK) rc = swath_angles(c, n, angle_dev, angle_host);
     return rc;
+}
+
+// ---- headland paths: what fcpp_headland_path_counts / _fill and fcpp_debug_headland_paths check alike --------------------------------------
+int hpath_args(int64_t n_rings, const void *ring_offsets, int64_t n_verts, const double *x, const double *y, const int32_t *src,
+               const double *ring_dist, double radius, int mode, double spacing, int direction, double smooth_tol)
+{
+    if (!ring_offsets || (n_verts > 0 && (!x || !y || !src)) || (n_rings > 0 && !ring_dist)) return fail(FCPP_EINVAL, "bad arguments");
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    if (direction != 1 && direction != -1) return fail(FCPP_EINVAL, "direction must be +1 (as stored) or -1");
+    if (!(smooth_tol >= 0.0)) return fail(FCPP_EINVAL, "smooth_tol must not be negative");
+    if (n_rings < 0 || n_verts < 0 || n_rings > INT32_MAX || n_verts > HPATH_MAX_VERTS) return fail(FCPP_ESIZE, "bad sizes (at most 2^30 vertices)");
+    return FCPP_OK;
 }
 }  // namespace
 
@@ -1118,6 +1134,144 @@ int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_to
                 if (part) part[at + k] = (int8_t)lg.part;
                 if (gear) gear[at + k] = (int8_t)pg;
                 if (leg) leg[at + k] = lg.slot;
+            }
+        }
+    });
+    return FCPP_OK;
+}
+
+// ---- headland paths (fcpp_hpath.hip; the rule: fcpp_hpathfn.h) ------------------------------------------------------------------------
+// Like the field paths, the fill RECOMPUTES the leg records from its inputs: the two entries stay stateless.
+int fcpp_headland_path_counts(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_offsets, const int64_t *ring_offsets_host, int64_t n_verts,
+                              const double *x, const double *y, const int32_t *src, const double *ring_dist, double radius, int mode,
+                              double spacing, int direction, double smooth_tol, int64_t *path_offsets, int64_t *path_offsets_host,
+                              int64_t *leg_offsets, double *work_length, double *transit_length, double *skipped_length, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!path_offsets || !leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = hpath_args(n_rings, ring_offsets, n_verts, x, y, src, ring_dist, radius, mode, spacing, direction, smooth_tol);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> roff;
+    rc = host_offsets(c, n_rings, ring_offsets, ring_offsets_host, n_verts, "ring_offsets", roff);
+    if (rc) return rc;
+    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
+    const HpathIn in = { ring_offsets, x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
+    DevBuf<HpathLeg> legs;
+    DevBuf<int64_t> cnt;
+    DevBuf<int32_t> drivable, own_status;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    HIPCHK(cnt.alloc((size_t)n_slots));
+    HIPCHK(drivable.alloc((size_t)n_rings));
+    if (!status) { HIPCHK(own_status.alloc((size_t)n_rings)); status = own_status.p; }
+    rc = sample_counts(c, n_rings, path_offsets, path_offsets_host, "a leg or a ring has 2^31 samples or more", [&](hipStream_t st, int64_t *err) {
+        if (n_rings > 0) {
+            hipError_t e = hipMemsetAsync(drivable.p, 0, (size_t)n_rings * sizeof(int32_t), st);
+            if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)n_rings * sizeof(int32_t), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        const int e = launch_hpath_legs(st, n_rings, n_verts, in, mode, legs.p, cnt.p, status, drivable.p);
+        return e ? e : launch_hpath_offsets(st, n_rings, n_verts, ring_offsets, legs.p, cnt.p, status, drivable.p, leg_offsets, path_offsets, work_length,
+                                            transit_length, skipped_length, err);
+    });
+    return rc;      // (sample_counts has drained the stream: the temporaries die here)
+}
+
+int fcpp_headland_path_fill(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_offsets, const int64_t *ring_offsets_host, int64_t n_verts,
+                            const double *x, const double *y, const int32_t *src, const double *ring_dist, double radius, int mode, double spacing,
+                            int direction, double smooth_tol, const int64_t *leg_offsets, int64_t total_samples, double *out_x, double *out_y,
+                            double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = hpath_args(n_rings, ring_offsets, n_verts, x, y, src, ring_dist, radius, mode, spacing, direction, smooth_tol);
+    if (rc == FCPP_OK && (total_samples < 0 || total_samples > ((int64_t)1 << 38))) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> roff;
+    rc = host_offsets(c, n_rings, ring_offsets, ring_offsets_host, n_verts, "ring_offsets", roff);
+    if (rc) return rc;
+    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
+    // The ends of the slot offsets must match the output arrays, as in fcpp_field_path_fill: offsets that are not the counts call's give
+    // wrong samples, never an access outside the arrays.
+    int64_t ends[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&ends[1], leg_offsets + n_slots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (ends[0] != 0 || ends[1] != total_samples) return fail(FCPP_ESIZE, "leg_offsets do not span [0, total_samples]");
+    const HpathIn in = { ring_offsets, x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
+    DevBuf<HpathLeg> legs;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    LAUNCHCHK(launch_hpath_legs(c->stream, n_rings, n_verts, in, mode, legs.p, nullptr, nullptr, nullptr));
+    LAUNCHCHK(launch_hpath_fill(c->stream, n_slots, legs.p, leg_offsets, total_samples, radius, spacing, out_x, out_y, heading, kappa, part, gear, leg));
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int64_t n_verts, const double *x, const double *y, const int32_t *src,
+                              const double *ring_dist, double radius, int mode, double spacing, int direction, double smooth_tol,
+                              int64_t *path_offsets, int64_t *leg_offsets, double *work_length, double *transit_length, double *skipped_length,
+                              int32_t *status, int32_t *leg_kind, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap, double *out_x,
+                              double *out_y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    int rc = hpath_args(n_rings, ring_offsets, n_verts, x, y, src, ring_dist, radius, mode, spacing, direction, smooth_tol);
+    if (rc == FCPP_OK && cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> roff;
+    rc = host_offsets(nullptr, n_rings, nullptr, ring_offsets, n_verts, "ring_offsets", roff);
+    if (rc) return rc;
+    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
+    const HpathIn in = { roff.data(), x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
+    std::vector<HpathLeg> legs;
+    std::vector<int64_t> off;
+    std::vector<char> big;
+    try {
+        legs.resize((size_t)n_slots); off.assign((size_t)n_slots + 1, 0); big.assign((size_t)n_rings, 0);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    // the records, the counts (in off, one slot ahead: scanned below), the status and the totals; rings to the library's host threads
+    WorkerPool::parallel_for(n_rings, [&](int64_t r) {
+        const int64_t first = 2 * roff[(size_t)r];
+        double w, t, s;
+        bool oversize;
+        const int st = mode == 0 ? hpath_ring_host<0>(in, r, legs.data() + first, off.data() + first + 1, w, t, s, oversize)
+                                 : hpath_ring_host<1>(in, r, legs.data() + first, off.data() + first + 1, w, t, s, oversize);
+        big[(size_t)r] = oversize;
+        if (status) status[r] = st;
+        if (work_length) work_length[r] = w;
+        if (transit_length) transit_length[r] = t;
+        if (skipped_length) skipped_length[r] = s;
+    });
+    for (int64_t r = 0; r < n_rings; ++r)
+        if (big[(size_t)r]) return fail(FCPP_ESIZE, "a leg or a ring has 2^31 samples or more");
+    for (int64_t g = 0; g < n_slots; ++g) {
+        off[(size_t)g + 1] += off[(size_t)g];
+        const FpathLeg &lg = legs[(size_t)g].leg;
+        if (leg_kind) leg_kind[g] = lg.kind;
+        if (leg_word) leg_word[g] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
+        if (leg_seg) for (int k = 0; k < 5; ++k) leg_seg[5 * g + k] = lg.seg[k];
+        if (leg_total) leg_total[g] = lg.total;
+    }
+    if (leg_offsets) memcpy(leg_offsets, off.data(), off.size() * sizeof(int64_t));
+    if (path_offsets) {
+        for (int64_t r = 0; r < n_rings; ++r) path_offsets[r] = off[(size_t)(2 * roff[(size_t)r])];
+        path_offsets[n_rings] = off[(size_t)n_slots];
+    }
+    if (cap == 0 || !(out_x || out_y || heading || kappa || part || gear || leg)) return FCPP_OK;
+    WorkerPool::parallel_for(n_rings, [&](int64_t r) {
+        for (int64_t g = 2 * roff[(size_t)r]; g < 2 * roff[(size_t)r + 1]; ++g) {
+            const HpathLeg &lg = legs[(size_t)g];
+            const int64_t at = off[(size_t)g], K = off[(size_t)g + 1] - at;
+            for (int64_t k = 0; k < K && at + k < cap; ++k) {
+                double px, py, ph, pk;
+                int pg;
+                hpath_eval(lg, radius, spacing, k, K, px, py, ph, pk, pg);
+                if (out_x) out_x[at + k] = px;
+                if (out_y) out_y[at + k] = py;
+                if (heading) heading[at + k] = ph;
+                if (kappa) kappa[at + k] = pk;
+                if (part) part[at + k] = (int8_t)lg.leg.part;
+                if (gear) gear[at + k] = (int8_t)pg;
+                if (leg) leg[at + k] = lg.leg.slot;
             }
         }
     });

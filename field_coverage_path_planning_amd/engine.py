@@ -1625,6 +1625,85 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     return FieldPaths(off, off_h, x, y, h, kap, part, gear, leg, work, transit, status, leg_off)
 
 
+# ---- headland paths (fcpp_headland_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------
+@dataclass
+class HeadlandPaths:
+    """headland_paths(): one sampled, closed path per ring of an InsetSet, in the CSR form curvature(), speed_plan(), validate() and
+    trajectory() take (offsets=).  Ring r owns the samples offsets[r] .. offsets[r + 1]."""
+    offsets: object             # (n_rings + 1) int64, device; offsets_host: the numpy copy
+    offsets_host: object
+    x: object                   # (total) float64
+    y: object
+    heading: object             # (total) float64, in (-pi, pi]: the vehicle's heading
+    kappa: object               # (total) float64: signed curvature, 0 on a straight element, -/+ 1 / d on a followed arc
+    part: object                # (total) int8: 0 straight element, 1 connector, 4 followed arc
+    gear: object                # (total) int8: +1, -1 on the reverse runs of a Reeds-Shepp connector
+    leg: object                 # (total) int32: the leg slot within the ring: 2 k the element driven vertex k starts, 2 k + 1 the joint behind it
+    work_length: object         # (n_rings) float64: the straight elements and followed arcs [m]
+    transit_length: object      # (n_rings) float64: the connectors [m]
+    skipped_length: object      # (n_rings) float64: the arcs too tight to follow, bridged by a connector [m]
+    status: object              # (n_rings) int32: 0, FCPP_EINVAL or FCPP_EUNSUPPORTED (no drivable element): no samples
+    leg_offsets: object         # (2 n_verts + 1) int64: the first sample of every leg slot; ring r's first slot is 2 ring_offsets[r]
+    ring_pair: object           # (n_rings, 2) int64, device: the (field, pass) index of every ring
+
+    def ring(self, r):
+        """(x, y, heading, part) of ring r"""
+        sl = slice(int(self.offsets_host[r]), int(self.offsets_host[r + 1]))
+        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+
+
+def _headland_paths(ctx, ring_offsets, x, y, src, ring_dist, R, mode, spacing, direction, smooth_tol, ring_offsets_host=None):
+    """the two C entries on device tensors; R as it is (no chord radius) -> the HeadlandPaths fields but ring_pair"""
+    torch = _torch()
+    dev = x.device
+    nr, nv = int(ring_offsets.numel()) - 1, int(x.numel())
+    roff_h = None if ring_offsets_host is None else np.ascontiguousarray(ring_offsets_host, dtype=np.int64)
+    args = (nr, _ptr(ring_offsets), _host_ptr(roff_h), nv, _ptr(x), _ptr(y), _ptr(src), _ptr(ring_dist), float(R), int(mode), float(spacing),
+            int(direction), float(smooth_tol))
+    off, leg_off = torch.empty(nr + 1, dtype=torch.int64, device=dev), torch.empty(2 * nv + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(nr + 1, dtype=np.int64)
+    work, transit, skipped = (torch.empty(nr, dtype=torch.float64, device=dev) for _ in range(3))
+    status = torch.empty(nr, dtype=torch.int32, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_headland_path_counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), _ptr(work), _ptr(transit), _ptr(skipped),
+                                              _ptr(status)))
+    total = int(off_h[-1])
+    px, py, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
+    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
+    leg = torch.empty(total, dtype=torch.int32, device=dev)
+    L.check(ctx.lib.fcpp_headland_path_fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(px), _ptr(py), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear),
+                                            _ptr(leg)))
+    return off, off_h, px, py, h, kap, part, gear, leg, work, transit, skipped, status, leg_off
+
+
+def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_tol=1e-6, device=None):
+    """EVERY ring of an InsetSet (headland()'s pass centre lines: all fields, all passes) as one sampled, closed, drivable path each, in one
+    pass on the device (fcpp_headland_path_counts + fcpp_headland_path_fill) -> HeadlandPaths.  The straight pieces are driven to their
+    very ends and sampled every `spacing` metres; the arcs around reflex vertices are followed where the pass's distance d is at least the
+    planning radius _chord_radius(radius, spacing) (as field_paths plans) and bridged where it is not (skipped_length); every joint whose
+    heading jumps by more than smooth_tol [rad] is closed by the shortest Dubins path -- Reeds-Shepp if `reversing` -- which at a sharp
+    corner is the bulb turn or the three-point turn.  direction +1 drives a ring as stored (kept area on the left), -1 the other way round;
+    both start at the ring's first vertex.  A ring with a non-finite vertex has status FCPP_EINVAL, one without a drivable element
+    FCPP_EUNSUPPORTED; such rings have no samples and the others are unaffected.  Connectors know no boundary (validate() flags what leaves
+    the field)."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = inset.x.device
+    nr = int(inset.ring_offsets.numel()) - 1
+    pairs = int(inset.pair_ring_offsets.numel()) - 1
+    per_pair = inset.pair_ring_offsets[1:] - inset.pair_ring_offsets[:-1]
+    pair = torch.repeat_interleave(torch.arange(pairs, dtype=torch.int64, device=dev), per_pair, output_size=nr)
+    D = max(inset.D, 1)
+    ring_pair = torch.stack([pair // D, pair % D], dim=1)
+    ring_dist = inset.distances[ring_pair[:, 1]].contiguous() if nr else torch.empty(0, dtype=torch.float64, device=dev)
+    out = _headland_paths(ctx, inset.ring_offsets, inset.x, inset.y, inset.src, ring_dist, _chord_radius(radius, spacing), 1 if reversing else 0,
+                          spacing, direction, smooth_tol)
+    return HeadlandPaths(*out, ring_pair)
+
+
+_drive_headland = headland_paths      # (plan_polygon_fields has a flag of that name)
+
+
 @dataclass
 class PolygonPlan:
     """plan_polygon_fields(): every stage's result for the batch"""
@@ -1635,14 +1714,17 @@ class PolygonPlan:
     swaths: object              # SwathSet
     route: object               # SwathRoute
     paths: object               # FieldPaths
+    headland_paths: object = None       # HeadlandPaths of `headland` when asked for (headland_paths=True), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
-                        arc_step=0.1, device=None):
+                        arc_step=0.1, headland_paths=False, device=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
-    The headland pass rings are returned (headland) but not part of the path."""
+    The headland pass rings are returned (headland) but not part of the path; headland_paths=True also drives them (headland_paths() at the
+    same radius, spacing and `reversing`: one closed loop per ring, PolygonPlan.headland_paths).  The loops are not joined to each other or
+    to the field paths' entries: the connector operators do that from the loops' first poses."""
     torch = _torch()
     lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
     ang = _dev_f64(angles, work.x.device).reshape(-1)
@@ -1652,7 +1734,8 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     ss = polygon_swaths(work, chosen, width, device=device)
     route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device)
     paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device)
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths)
+    hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp)
 
 
 def _polys(polygons):

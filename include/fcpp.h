@@ -752,6 +752,62 @@ int fcpp_inset_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, i
                     const int64_t *pair_ring_offsets_dev, const int64_t *pair_vert_offsets_dev, int64_t total_rings, int64_t total_verts,
                     int64_t *out_vert_offsets_dev, double *out_x_dev, double *out_y_dev, int32_t *out_src_dev);
 
+/* ---- headland paths: every ring of an inset as ONE sampled, closed, drivable path ------------------------------------------------------------
+ * Build-defined.  The rings fcpp_inset_fill writes are bare polygons: straight offset pieces that meet in sharp convex corners, and chords
+ * of arcs of radius d around reflex vertices.  This operator turns every ring of a batch (all fields, all passes) into a loop a vehicle of
+ * turning radius `radius` can drive: the straight pieces driven to their very ends, the arcs followed where d >= radius and bridged where
+ * not, every sharp joint closed by a Dubins (mode 0) or Reeds-Shepp (mode 1) connector -- at a corner, where both poses share one
+ * position, the bulb turn or the three-point turn.  A counts entry and a fill entry over all rings; the result is a path set in CSR form
+ * (path_offsets), which fcpp_curvature, fcpp_speed_plan, fcpp_validate and fcpp_trajectory take as it is.  Standalone: nothing here feeds
+ * fcpp_batch_plan.  Connectors know no boundary, as everywhere: fcpp_validate flags what leaves the field.
+ * Input: n_rings rings, ring r owning the vertices ring_offsets[r] .. ring_offsets[r + 1] of x, y (float64) and src (int32: even for a
+ * vertex that starts a straight piece, odd for a vertex on an arc, equal along one arc -- fcpp_inset_fill's out_src), closed implicitly,
+ * the kept area on the left; ring_dist (n_rings float64): the inset distance d of the ring's (field, distance) pair.
+ * THE RULE (csrc/fcpp_hpathfn.h, one set of expressions for host and device: the same bits on both), per ring of m vertices v_0 .. v_(m-1):
+ *   - Driving order.  direction +1: driven vertex k is v_k and its chord's source s_k = src[k].  direction -1: driven vertex k is
+ *     v_((m - k) mod m) and s_k = src[m - 1 - k].  Both start at v_0.  Driven vertex k owns slot 2 k (an element) and slot 2 k + 1 (the joint
+ *     behind it); ring r's first slot is 2 ring_offsets[r].  leg_offsets (2 n_verts + 1 int64) holds the first sample of every slot;
+ *     path_offsets (n_rings + 1) is leg_offsets at the rings' first slots.
+ *   - Elements.  Driven vertex k starts an element iff k = 0, or s_k is even, or s_k != s_(k-1); the element runs from A = its start vertex
+ *     to B = the next element start, cyclically (the last one ends at v_0).  The arc vertices between only mark the run: they are not
+ *     sampled.  With c = |AB| and h_c the chord's heading: s even is a STRAIGHT element of length c and heading h_c; s odd an ARC element of
+ *     radius d: h = sqrt(max(d^2 - c^2 / 4, 0)), half = atan2(c / 2, h), sweep D = 2 half, length d D.  As stored the arc turns right, curvature
+ *     -1 / d, heading h_c + half at A and h_c - half at B, centre = midpoint + h (u_y, -u_x) with u = (B - A) / c; direction -1 mirrors it: a
+ *     left turn, curvature +1 / d.  An arc is DRIVABLE iff d >= radius; a straight element with c > 0 always.  An element with c = 0 and an
+ *     undrivable arc have no leg: they are skipped.
+ *   - Element leg (slot 2 k).  Straight: sampled as a swath of the field paths -- floor(c / spacing) + 1 samples, one more at the end when
+ *     the last lies before it, sample j at t = fmin((j spacing) / c, 1), the LAST sample B itself; curvature 0, gear +1, part 0.  Followed
+ *     arc: as many samples by the same count rule on d D, sample j at arc length s = j spacing: centre + d (cos, sin) of the start angle -/+ s / d,
+ *     heading likewise; the FIRST sample is A itself, the LAST B itself; curvature -/+ 1 / d, gear +1, part 4.
+ *   - Joint leg (slot 2 k + 1), of a drivable element e only.  f = the next drivable element in driving order, cyclically (e itself when
+ *     it is the only one).  If f directly follows e and |wrap(heading_in(f) - heading_out(e))| <= smooth_tol there is no leg: the loop
+ *     drives straight through.  Otherwise -- a sharp corner, or a joint across skipped elements -- the leg is fcpp_dubins_solve's (mode 0)
+ *     or fcpp_rs_solve's (mode 1) path at `radius` from e's exit pose to f's entry pose, sampled exactly as fcpp_dubins_sample /
+ *     fcpp_rs_sample sample it; part 1.  Its end lies within 2^-43 (radius + straight) metres of f's start (the connectors' bound).
+ *   - Junctions stay doubled, as in the field paths.  The loop is closed: the last sample's pose is the first sample's (to that bound).
+ *   - leg (int32): the sample's slot within its ring.  Every sample is evaluated from its leg alone, never from a neighbouring sample.
+ *   - Totals per ring, added in slot order: work_length = straight elements + followed arcs; transit_length = connectors; skipped_length =
+ *     d D of the undrivable arcs (the centre line that was bridged, not driven).
+ * Status per ring, int32: 0; FCPP_EINVAL -- fewer than 2 vertices, a vertex or distance that is not finite, an arc with d <= 0, a negative
+ * src, a connector without a path (word -1): no samples, NaN totals; FCPP_EUNSUPPORTED -- no drivable element: no samples (work and
+ * transit 0, skipped as summed).  The other rings are unaffected.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, radius or spacing <= 0 or not finite,
+ * mode not 0 or 1, direction not +1 or -1, smooth_tol negative (or NaN); FCPP_ESIZE -- negative sizes, more than 2^30 vertices, offsets
+ * that do not start at 0, decrease or do not end at n_verts.  FCPP_ESIZE after the count: a leg of 2^31 samples or more, a ring above
+ * 2^31 - 2 samples.  ring_offsets_host: the host copy, or NULL to have it read back.  Both entries synchronise.
+ * fcpp_headland_path_fill recomputes the leg records from the same inputs (nothing is kept in the context between the two calls); every
+ * one of its seven outputs may be NULL, as may work_length, transit_length, skipped_length, status and path_offsets_host of the counts. */
+int fcpp_headland_path_counts(fcpp_ctx *ctx, int64_t n_rings, const int64_t *ring_offsets_dev, const int64_t *ring_offsets_host, int64_t n_verts,
+                              const double *x_dev, const double *y_dev, const int32_t *src_dev, const double *ring_dist_dev, double radius,
+                              int mode, double spacing, int direction, double smooth_tol, int64_t *path_offsets_dev,
+                              int64_t *path_offsets_host, int64_t *leg_offsets_dev, double *work_length_dev, double *transit_length_dev,
+                              double *skipped_length_dev, int32_t *status_dev);
+int fcpp_headland_path_fill(fcpp_ctx *ctx, int64_t n_rings, const int64_t *ring_offsets_dev, const int64_t *ring_offsets_host, int64_t n_verts,
+                            const double *x_dev, const double *y_dev, const int32_t *src_dev, const double *ring_dist_dev, double radius,
+                            int mode, double spacing, int direction, double smooth_tol, const int64_t *leg_offsets_dev,
+                            int64_t total_samples, double *out_x_dev, double *out_y_dev, double *heading_dev, double *kappa_dev,
+                            int8_t *part_dev, int8_t *gear_dev, int32_t *leg_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -851,6 +907,19 @@ int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_to
                            const double *exit_y, const double *exit_h, int64_t *path_offsets, int64_t *leg_offsets, double *work_length,
                            double *transit_length, int32_t *status, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
                            double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
+/* The headland-path rule (csrc/fcpp_hpathfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device
+ * results are compared with bit for bit.  Arguments and the call's errors as for fcpp_headland_path_counts / _fill.  path_offsets
+ * (n_rings + 1), leg_offsets (2 n_verts + 1), work_length, transit_length, skipped_length, status (n_rings): any may be NULL.  leg_kind,
+ * leg_word (int32), leg_seg (5 each), leg_total (2 n_verts slots, any may be NULL): every slot's record -- kind 0 no leg, 1 a straight
+ * element (its end point and length in seg[0 .. 2]), 2 / 3 a Dubins / Reeds-Shepp connector (word, segments and total as fcpp_debug_dubins /
+ * fcpp_debug_rs give them), 4 a followed arc (end point, length, curvature in seg[0 .. 3]), 5 a skipped arc (total = d D); word -1 for all
+ * but connectors.  Sample q of all is written to out_x .. leg (any may be NULL) while q < cap: call once with cap = 0 for the sizes, then
+ * with them.  Rings are handed to the library's host threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int64_t n_verts, const double *x, const double *y, const int32_t *src,
+                              const double *ring_dist, double radius, int mode, double spacing, int direction, double smooth_tol,
+                              int64_t *path_offsets, int64_t *leg_offsets, double *work_length, double *transit_length, double *skipped_length,
+                              int32_t *status, int32_t *leg_kind, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
+                              double *out_x, double *out_y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch

@@ -1,0 +1,236 @@
+"""GPU tests of the headland paths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_hpath.hip against the same rule on the host
+(fcpp_debug_headland_paths) BIT FOR BIT on every output -- the rule is one set of host+device expressions, so nothing here is compared to a
+bound; the failed rings and the 40 000-ring batch of tests/test_headland_paths_host.py on the device; the existing path operators fed all
+loops in one call each; plan_polygon_fields(headland_paths=True) against the stage-by-stage calls; and the two device entries through the
+guarded arena.
+
+The batch is that of tests/test_headland_paths_host.py (the shapes of tests/native/inset_sanitize_driver.cpp, the 300-vertex star's ring
+longer than a 256-lane block, so block edges fall inside a ring and inside an arc run), repeated to 65 fields, at the distances 2, 6, 8 and
+60 (which empties every field: pairs without rings), at R = 1.5 (arcs followed) and R = 6 (arcs at d = 2 bridged), both modes, both
+directions, spacing 0.5 and 7 (legs shorter than one step); n = 1 is the rectangle alone, n_rings = 0 a call without rings."""
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+from tests.guarded import Arena
+from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES
+from tests.test_headland_paths_host import (DISTS, FAILED, FAILED_STATUS, R_BRIDGE, R_FOLLOW, RING_KEYS, batch, batch_rings, host_hpaths, many_rectangles,
+                                            raw_rings)
+from tests.test_swaths_host import ELL, HOLE
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ('offsets', 'offsets_host', 'x', 'y', 'heading', 'kappa', 'part', 'gear', 'leg', 'work', 'transit', 'skipped', 'status', 'leg_offsets')
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.reshape(-1).view(np.uint8), b.reshape(-1).view(np.uint8))
+
+
+def device_hpaths(rg, radius, mode=0, spacing=0.5, direction=1, smooth_tol=1e-6, with_host_offsets=True):
+    """the two device entries on the arrays of a ring set -> dict of numpy arrays under host_hpaths' keys"""
+    import torch
+    ctx = E.get_context(None)
+    dev = torch.device('cuda', ctx.device)
+    t = {k: torch.as_tensor(rg[k], device=dev) for k in ('roff', 'x', 'y', 'src', 'dist')}
+    out = E._headland_paths(ctx, t['roff'], t['x'], t['y'], t['src'], t['dist'], radius, mode, spacing, direction, smooth_tol,
+                            rg['roff'] if with_host_offsets else None)
+    return {k: (v if isinstance(v, np.ndarray) else _np(v)) for k, v in zip(NAMES, out)}
+
+
+def assert_equals_host(got, host, nan_totals=False):
+    for k in RING_KEYS:
+        if nan_totals and k in ('work', 'transit', 'skipped'):
+            assert np.array_equal(got[k], host[k], equal_nan=True), k          # (NaN totals: equal as NaN, whatever the payload)
+        else:
+            assert same_bytes(got[k], host[k]), k
+    assert np.array_equal(got['offsets_host'], host['offsets'])
+    for k in SAMPLE_KEYS:
+        assert same_bytes(got[k], host[k]), k
+
+
+@pytest.mark.parametrize('direction', [1, -1], ids=['stored', 'reversed'])
+@pytest.mark.parametrize('mode', [0, 1], ids=['dubins', 'rs'])
+@pytest.mark.parametrize('radius', [R_FOLLOW, R_BRIDGE], ids=['follow', 'bridge'])
+@pytest.mark.parametrize('n', [1, 65])
+def test_device_equals_host_bit_for_bit(n, radius, mode, direction):
+    rg = batch_rings(n)
+    n_rings = len(rg['roff']) - 1
+    if n == 65:
+        assert n_rings > 150 and np.diff(rg['roff']).max() > 256 and (np.bincount(rg['pair'], minlength=n * len(DISTS)) == 0).sum() >= n
+    for spacing in (0.5, 7.0):
+        host = host_hpaths(rg, radius, mode, spacing, direction)
+        got = device_hpaths(rg, radius, mode, spacing, direction, with_host_offsets=spacing == 0.5)
+        assert np.all(host['status'] == 0) and (n == 1 or host['total'] > 10000)
+        assert_equals_host(got, host)
+        if n == 65:
+            assert set(np.unique(host['part']).tolist()) == {0, 1, 4} and ((host['gear'] == -1).any() == bool(mode))
+
+
+def test_no_rings_at_all():
+    rg = raw_rings([])
+    host, got = host_hpaths(rg, R_BRIDGE), device_hpaths(rg, R_BRIDGE)
+    assert host['total'] == 0 and got['offsets'].tolist() == [0] and got['leg_offsets'].tolist() == [0]
+    assert_equals_host(got, host)
+
+
+@pytest.mark.parametrize('mode', [0, 1], ids=['dubins', 'rs'])
+def test_failed_rings_on_the_device(mode):
+    rg = raw_rings(FAILED)
+    host = host_hpaths(rg, R_BRIDGE, mode)
+    assert host['status'].tolist() == FAILED_STATUS
+    got = device_hpaths(rg, R_BRIDGE, mode)
+    assert_equals_host(got, host, nan_totals=True)
+    assert np.isnan(got['work'][np.asarray(FAILED_STATUS) == L.EINVAL]).all()
+    lines, _ = E.headland([[ELL, HOLE]], 4.0, 1)
+    for bad in (dict(radius=-1.0), dict(spacing=float('nan')), dict(direction=0), dict(smooth_tol=-1.0)):
+        with pytest.raises(L.FcppError):
+            E.headland_paths(lines, **{**dict(radius=6.0, spacing=0.5), **bad})
+
+
+def test_forty_thousand_rectangles_on_the_device():
+    rg = many_rectangles()
+    host = host_hpaths(rg, R_FOLLOW, 0, 7.0)
+    got = device_hpaths(rg, R_FOLLOW, 0, 7.0)
+    assert len(host['leg_offsets']) == 320001 and host['total'] > 8 * 40000
+    assert_equals_host(got, host)
+
+
+# ---- the engine: an InsetSet in, the existing path operators on the result ------------------------------------------------------------------
+W = 4.0
+
+
+@pytest.fixture(scope='module')
+def driven():
+    fields = batch(65)
+    lines, _ = E.headland(fields, W, 2)
+    return fields, lines, E.headland_paths(lines, 1.5, 0.5)
+
+
+def test_engine_equals_host(driven):
+    _, lines, hp = driven
+    rg = dict(roff=_np(lines.ring_offsets), x=_np(lines.x), y=_np(lines.y), src=_np(lines.src))
+    pair = np.repeat(np.arange(65 * 2), np.diff(lines.pair_ring_offsets_host))
+    rg['dist'] = np.asarray([W / 2, W / 2 + W])[pair % 2]
+    assert np.array_equal(_np(hp.ring_pair), np.column_stack([pair // 2, pair % 2]))
+    host = host_hpaths(rg, E._chord_radius(1.5, 0.5), 0, 0.5, 1)
+    got = {k: _np(getattr(hp, a)) for k, a in (('offsets', 'offsets'), ('leg_offsets', 'leg_offsets'), ('work', 'work_length'), ('transit', 'transit_length'),
+                                                 ('skipped', 'skipped_length'), ('status', 'status'))}
+    got.update({k: _np(getattr(hp, k)) for k in SAMPLE_KEYS}, offsets_host=hp.offsets_host)
+    assert_equals_host(got, host)
+    assert np.all(host['status'] == 0) and (host['part'] == 4).any() and np.all(host['skipped'] == 0)      # (d = 2 and d = 6: both followed)
+    x, y, h, part = hp.ring(3)
+    a, b = int(hp.offsets_host[3]), int(hp.offsets_host[4])
+    assert same_bytes(_np(x), host['x'][a:b]) and same_bytes(_np(part), host['part'][a:b]) and same_bytes(_np(h), host['heading'][a:b])
+    rev = E.headland_paths(lines, 1.5, 0.5, reversing=True, direction=-1)
+    assert same_bytes(_np(rev.x), host_hpaths(rg, E._chord_radius(1.5, 0.5), 1, 0.5, -1)['x'])
+
+
+def test_path_operators_take_all_loops(driven):
+    _, lines, hp = driven
+    R = 1.5
+    n = int(hp.offsets.numel()) - 1
+    veh = E.make_vehicle(min_turn_radius=R)
+    # a speed just under the clamp's limit at the curvature bound 1 / R + 1e-6 of tests/test_gpu_swaths.py
+    v_lim = np.sqrt(veh.max_lateral_accel / (1 / R + 1e-6)) * veh.safety_factor * 3.6
+    v = np.full(int(hp.x.numel()), 0.999 * v_lim)
+    kap = _np(E.curvature(hp.x, hp.y, offsets=hp.offsets))
+    vout, nadj = E.speed_plan(hp.x, hp.y, v, veh, clamp=True, offsets=hp.offsets)
+    flags, stats = E.validate(hp.x, hp.y, v, veh, offsets=hp.offsets)
+    s, t, th, totals = (_np(a) for a in E.trajectory(hp.x, hp.y, v, offsets=hp.offsets))
+    vout, nadj, flags = _np(vout), _np(nadj), _np(flags)
+    assert nadj.shape == (n,) and totals.shape == (n, 2) and np.all(np.isfinite(kap)) and np.all(np.isfinite(s)) and np.all(np.isfinite(t))
+    length = _np(hp.work_length) + _np(hp.transit_length)
+    # the polyline is inscribed: never longer than the driven length, and shorter by no more than the chords' sagitta share (1 - sinc)
+    assert np.all(totals[:, 0] <= length + 1e-9) and np.all(totals[:, 0] >= length * (np.sin(0.25 / R) / (0.25 / R)) - 1e-9)
+    checked = 0
+    for r in list(range(0, n, 9)) + [n - 1]:
+        sl = slice(int(hp.offsets_host[r]), int(hp.offsets_host[r + 1]))
+        x, y, _, _ = hp.ring(r)
+        assert same_bytes(_np(E.curvature(x, y)), kap[sl])
+        vi, ni = E.speed_plan(x, y, v[sl], veh, clamp=True)
+        assert same_bytes(_np(vi), vout[sl]) and int(ni[0]) == nadj[r]
+        fi, si = E.validate(x, y, v[sl], veh)
+        assert same_bytes(_np(fi), flags[sl])
+        for k in stats:
+            assert same_bytes(si[k][:1], stats[k][r:r + 1]), (k, r)
+        one = E.trajectory(x, y, v[sl])
+        assert same_bytes(_np(one[0]), s[sl]) and same_bytes(_np(one[1]), t[sl]) and same_bytes(_np(one[3])[0], totals[r])
+        checked += 1
+    assert checked >= 10
+
+
+def test_plan_polygon_fields_with_headland_paths():
+    fields = [[ELL, HOLE], batch(3)[2]]
+    angles = np.arange(6) * (np.pi / 6)
+    plain = E.plan_polygon_fields(fields, W, 6.0, 0.5, angles, passes=2)
+    assert plain.headland_paths is None
+    plan = E.plan_polygon_fields(fields, W, 6.0, 0.5, angles, passes=2, reversing=True, headland_paths=True)
+    lines, _ = E.headland(fields, W, 2)
+    want = E.headland_paths(lines, 6.0, 0.5, reversing=True)
+    got = plan.headland_paths
+    assert isinstance(got, E.HeadlandPaths) and np.array_equal(got.offsets_host, want.offsets_host) and got.offsets_host[-1] > 1000
+    for k in SAMPLE_KEYS + ('work_length', 'transit_length', 'skipped_length', 'status', 'leg_offsets', 'ring_pair', 'offsets'):
+        assert same_bytes(_np(getattr(got, k)), _np(getattr(want, k))), k
+    # the rest of the plan is what it is without the flag
+    other = E.plan_polygon_fields(fields, W, 6.0, 0.5, angles, passes=2, reversing=True)
+    assert same_bytes(_np(other.paths.x), _np(plan.paths.x)) and same_bytes(_np(other.paths.leg), _np(plan.paths.leg))
+
+
+# ---- the two device entries through the guarded arena ------------------------------------------------------------------------------------
+COUNT_OUTS = (('offsets', np.int64), ('leg_offsets', np.int64), ('work', np.float64), ('transit', np.float64), ('skipped', np.float64), ('status', np.int32))
+FILL_SUBSETS = [SAMPLE_KEYS, ('part',), ('x',)]
+
+
+@pytest.mark.parametrize('mode', [0, 1], ids=['dubins', 'rs'])
+def test_guarded_buffers(mode):
+    import torch
+    ctx = E.get_context(None)
+    lib, h = ctx.lib, ctx.handle
+    dev = torch.device('cuda', ctx.device)
+    ctx.bind_stream()
+    rg = batch_rings(65)
+    nr, nv = len(rg['roff']) - 1, len(rg['x'])
+    host = host_hpaths(rg, R_FOLLOW, mode, 0.5, -1)
+    sizes = dict(offsets=nr + 1, leg_offsets=2 * nv + 1, work=nr, transit=nr, skipped=nr, status=nr)
+
+    def arena(extra=()):
+        A = Arena()
+        for k in ('roff', 'x', 'y', 'src', 'dist'):
+            A.input('in_' + k, rg[k])          # (the samples' x and y are outputs of the fill)
+        for k, a in extra:
+            A.input(k, a)
+        return A
+
+    def head(A, roff_host):
+        return (h, nr, A.ptr('in_roff'), E._host_ptr(roff_host), nv, A.ptr('in_x'), A.ptr('in_y'), A.ptr('in_src'), A.ptr('in_dist'), R_FOLLOW, mode, 0.5, -1,
+                1e-6)
+
+    for outs in (RING_KEYS, ('offsets', 'leg_offsets')):
+        A = arena()
+        for k, dt in COUNT_OUTS:
+            if k in outs:
+                A.output(k, dt, sizes[k])
+        A.build(dev)
+        off_h = np.full(nr + 1, -1, np.int64)
+        # (the second call has the library read the ring offsets back from the arena)
+        rc = lib.fcpp_headland_path_counts(*head(A, rg['roff'] if outs is RING_KEYS else None), A.ptr('offsets'), E._host_ptr(off_h), A.ptr('leg_offsets'),
+                                           A.ptr('work'), A.ptr('transit'), A.ptr('skipped'), A.ptr('status'))
+        assert rc == L.OK, lib.fcpp_last_error()
+        A.check({k: host[k] for k in outs})
+        assert np.array_equal(off_h, host['offsets'])
+    for outs in FILL_SUBSETS:
+        A = arena([('leg_offsets', host['leg_offsets'])])
+        for k in SAMPLE_KEYS:
+            if k in outs:
+                A.output(k, SAMPLE_TYPES[k], host['total'])
+        A.build(dev)
+        rc = lib.fcpp_headland_path_fill(*head(A, rg['roff']), A.ptr('leg_offsets'), host['total'], *[A.ptr(k) for k in SAMPLE_KEYS])
+        assert rc == L.OK, lib.fcpp_last_error()
+        A.check({k: host[k] for k in outs})
