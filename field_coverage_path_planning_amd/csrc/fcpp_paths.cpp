@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset, the swath router, the field paths and the headland paths.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router, the field paths, the headland paths and the polygon coverage.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -17,6 +17,8 @@
 #include "fcpp_inset.h"
 #include "fcpp_insetfn.h"
 #include "fcpp_parallel.h"
+#include "fcpp_pcover.h"
+#include "fcpp_pcoverfn.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
 #include "fcpp_swath.h"
@@ -1275,6 +1277,202 @@ int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int6
             }
         }
     });
+    return FCPP_OK;
+}
+
+}  // extern "C"
+
+// ---- polygon coverage (fcpp_pcover.hip; the rule: fcpp_pcoverfn.h) ----------------------------------------------------------------------
+namespace {
+// what fcpp_polygon_cover_sizes, fcpp_polygon_cover and fcpp_debug_polygon_cover check alike
+int pcover_args(int64_t n, const void *ring_offsets, int64_t n_rings, const void *vert_offsets, int64_t n_verts, const double *x, const double *y,
+                double W, double res)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y))) return fail(FCPP_EINVAL, "bad arguments");
+    if (!(W > 0.0) || !isfinite(W)) return fail(FCPP_EINVAL, "width must be positive and finite");
+    if (!(res > 0.0) || !isfinite(res)) return fail(FCPP_EINVAL, "res must be positive and finite");
+    if (n < 0 || n_rings < 0 || n_verts < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    return FCPP_OK;
+}
+
+int pcover_path_args(int64_t n, int caps, int64_t n_paths, const void *path_offsets, int64_t total_points, const double *x, const double *y,
+                     const void *field_path_offsets)
+{
+    if (!path_offsets || !field_path_offsets || (total_points > 0 && (!x || !y))) return fail(FCPP_EINVAL, "bad arguments");
+    if (caps != 0 && caps != 1) return fail(FCPP_EINVAL, "caps must be 0 (flat) or 1 (round)");
+    if (n_paths < 0 || total_points < 0 || n_paths > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    return FCPP_OK;
+}
+
+// The paths of the fields, on the host and checked: poff (n_paths + 1), fpo (n + 1) and ids (fpo[n] entries, or NULL for the identity).
+// -> the chunk table in field order and the fields' first chunks.
+int pcover_chunks(int64_t n, int64_t n_paths, const std::vector<int64_t> &poff, const std::vector<int64_t> &fpo, const int64_t *ids,
+                  std::vector<PcoverChunk> &chunks, std::vector<int64_t> &chunk_first)
+{
+    const int64_t S = fpo[(size_t)n];
+    if (!ids && S > n_paths) return fail(FCPP_ESIZE, "field_path_offsets name more paths than there are");
+    try {
+        chunk_first.assign((size_t)n + 1, 0);
+        chunks.clear();
+        for (int64_t i = 0; i < n; ++i) {
+            chunk_first[(size_t)i] = (int64_t)chunks.size();
+            for (int64_t s = fpo[(size_t)i]; s < fpo[(size_t)i + 1]; ++s) {
+                const int64_t p = ids ? ids[s] : s;
+                if (p < 0 || p >= n_paths) return fail(FCPP_EINVAL, "path_ids must lie in [0, n_paths)");
+                const int64_t p0 = poff[(size_t)p], p1 = poff[(size_t)p + 1];
+                for (int64_t k = p0; k + 1 < p1; k += PCOVER_CHUNK)
+                    chunks.push_back({ k, p0, p1, (int32_t)std::min<int64_t>(PCOVER_CHUNK, p1 - 1 - k), (int32_t)p });
+            }
+            if ((int64_t)chunks.size() > INT32_MAX) return fail(FCPP_ESIZE, "2^31 chunks of paths or more");
+        }
+        chunk_first[(size_t)n] = (int64_t)chunks.size();
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    return FCPP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fcpp_polygon_cover_sizes(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                             const double *x, const double *y, double width, double res, void *dims, int64_t *cell_offsets,
+                             int64_t *cell_offsets_host, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!dims || !cell_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = pcover_args(n, ring_offsets, n_rings, vert_offsets, n_verts, x, y, width, res);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    return sample_counts(c, n, cell_offsets, cell_offsets_host, "the cells could not be scanned", [&](hipStream_t st, int64_t *err) {
+        const int e = launch_pcover_sizes(st, n, ring_offsets, vert_offsets, x, y, width, res, (PcoverDims *)dims, status);
+        return e ? e : launch_pcover_offsets(st, n, (const PcoverDims *)dims, cell_offsets, nullptr, err);
+    });
+}
+
+// Like the path operators' fill entries, the cover call RECOMPUTES the grids from its inputs: the two entries stay stateless, and the
+// kernels place every field by the offsets computed here -- the caller's offsets only have to end at the same total.
+int fcpp_polygon_cover(fcpp_ctx *c, int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts,
+                       const double *x, const double *y, double width, double res, int caps, int64_t n_paths, const int64_t *path_offsets,
+                       const int64_t *path_offsets_host, int64_t total_points, const double *px, const double *py, const uint8_t *work,
+                       const int32_t *pass, const int64_t *field_path_offsets, const int64_t *path_ids, const int64_t *cell_offsets,
+                       const int64_t *cell_offsets_host, uint8_t *grid, int64_t *counts, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && !counts) || (grid && !cell_offsets && !cell_offsets_host)) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = pcover_args(n, ring_offsets, n_rings, vert_offsets, n_verts, x, y, width, res);
+    if (rc == FCPP_OK) rc = pcover_path_args(n, caps, n_paths, path_offsets, total_points, px, py, field_path_offsets);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<int64_t> rings, verts, poff, fpo, ids;
+    rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = host_offsets(c, n_paths, path_offsets, path_offsets_host, total_points, "path_offsets", poff);
+    if (rc) return rc;
+    try { fpo.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    HIPCHK(hipMemcpyAsync(fpo.data(), field_path_offsets, fpo.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (fpo[0] != 0) return fail(FCPP_ESIZE, "field_path_offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (fpo[(size_t)i + 1] < fpo[(size_t)i]) return fail(FCPP_ESIZE, "field_path_offsets must be non-decreasing");
+    if (fpo[(size_t)n] > ((int64_t)1 << 31)) return fail(FCPP_ESIZE, "field_path_offsets name 2^31 paths or more");
+    if (path_ids && fpo[(size_t)n] > 0) {
+        try { ids.assign((size_t)fpo[(size_t)n], 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+        HIPCHK(hipMemcpyAsync(ids.data(), path_ids, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    std::vector<PcoverChunk> chunks;
+    std::vector<int64_t> chunk_first;
+    rc = pcover_chunks(n, n_paths, poff, fpo, path_ids ? ids.data() : nullptr, chunks, chunk_first);
+    if (rc) return rc;
+
+    DevBuf<PcoverDims> dims;
+    DevBuf<int64_t> cell_first, tile_first, err, d_chunk_first;
+    DevBuf<int32_t> own_status;
+    DevBuf<PcoverChunk> d_chunks;
+    DevBuf<PcoverBox> boxes;
+    HIPCHK(dims.alloc((size_t)n));
+    HIPCHK(cell_first.alloc((size_t)n + 1));
+    HIPCHK(tile_first.alloc((size_t)n + 1));
+    HIPCHK(err.alloc(1));
+    if (!status) { HIPCHK(own_status.alloc((size_t)n)); status = own_status.p; }
+    LAUNCHCHK(launch_pcover_sizes(st, n, ring_offsets, vert_offsets, x, y, width, res, dims.p, status));
+    LAUNCHCHK(launch_pcover_offsets(st, n, dims.p, cell_first.p, tile_first.p, err.p));
+    int64_t totals[3] = { 0, 0, 0 };           // cells, tiles, the caller's cells
+    HIPCHK(hipMemcpyAsync(&totals[0], cell_first.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&totals[1], tile_first.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (grid) {
+        if (cell_offsets_host) totals[2] = cell_offsets_host[n];
+        else HIPCHK(hipMemcpyAsync(&totals[2], cell_offsets + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (n > 0) HIPCHK(hipMemsetAsync(counts, 0, (size_t)n * 4 * sizeof(int64_t), st));
+    HIPCHK(d_chunks.upload(chunks, st));
+    HIPCHK(d_chunk_first.upload(chunk_first, st));
+    HIPCHK(boxes.alloc(chunks.size()));
+    HIPCHK(hipStreamSynchronize(st));
+    if (grid && totals[2] != totals[0]) return fail(FCPP_ESIZE, "cell_offsets do not end at the cells of these fields: call fcpp_polygon_cover_sizes");
+    if (totals[1] > INT32_MAX) return fail(FCPP_ESIZE, "2^31 tiles or more");
+    const PcoverPaths P = { px, py, work, pass };
+    const PcoverFields F = { ring_offsets, vert_offsets, x, y, dims.p, cell_first.p, tile_first.p, d_chunk_first.p };
+    LAUNCHCHK(launch_pcover_boxes(st, (int64_t)chunks.size(), d_chunks.p, P, boxes.p));
+    LAUNCHCHK(launch_pcover_tiles(st, n, totals[1], F, width, res, caps, d_chunks.p, boxes.p, P, grid, (unsigned long long *)counts));
+    HIPCHK(hipStreamSynchronize(st));          // (the tables die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                             const double *y, double width, double res, int caps, int64_t n_paths, const int64_t *path_offsets, int64_t total_points,
+                             const double *px, const double *py, const uint8_t *work, const int32_t *pass, const int64_t *field_path_offsets,
+                             const int64_t *path_ids, void *dims_out, int64_t *cell_offsets, int64_t cell_cap, uint8_t *grid, int64_t *counts,
+                             int32_t *status)
+{
+    int rc = pcover_args(n, ring_offsets, n_rings, vert_offsets, n_verts, x, y, width, res);
+    if (rc == FCPP_OK && counts) rc = pcover_path_args(n, caps, n_paths, path_offsets, total_points, px, py, field_path_offsets);
+    if (rc == FCPP_OK && cell_cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> rings, verts, poff, fpo, cells;
+    rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc) return rc;
+    std::vector<PcoverDims> dims;
+    try { dims.resize((size_t)n); cells.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t i = 0; i < n; ++i) {
+        const int st = pcover_field_dims_host(verts.data(), rings[(size_t)i], rings[(size_t)i + 1], x, y, width, res, dims[(size_t)i]);
+        if (status) status[i] = st;
+        cells[(size_t)i + 1] = cells[(size_t)i] + dims[(size_t)i].nx * dims[(size_t)i].ny;
+    }
+    if (dims_out && n > 0) memcpy(dims_out, dims.data(), dims.size() * sizeof(PcoverDims));
+    if (cell_offsets) memcpy(cell_offsets, cells.data(), cells.size() * sizeof(int64_t));
+    if (!counts) return FCPP_OK;
+    rc = host_offsets(nullptr, n_paths, nullptr, path_offsets, total_points, "path_offsets", poff);
+    if (rc) return rc;
+    try { fpo.assign(field_path_offsets, field_path_offsets + n + 1); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    std::vector<PcoverChunk> chunks;          // (built only for the checks the device entry makes: the same errors for the same arguments)
+    std::vector<int64_t> chunk_first;
+    if (fpo[0] != 0) return fail(FCPP_ESIZE, "field_path_offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (fpo[(size_t)i + 1] < fpo[(size_t)i]) return fail(FCPP_ESIZE, "field_path_offsets must be non-decreasing");
+    if (fpo[(size_t)n] > ((int64_t)1 << 31)) return fail(FCPP_ESIZE, "field_path_offsets name 2^31 paths or more");
+    rc = pcover_chunks(n, n_paths, poff, fpo, path_ids, chunks, chunk_first);
+    if (rc) return rc;
+    const bool want_grid = grid && cells[(size_t)n] <= cell_cap;
+    const PcoverPaths P = { px, py, work, pass };
+    // fields to the library's host threads: every field writes only its own counts and cells
+    try {
+        WorkerPool::parallel_for(n, [&](int64_t i) {
+            const PcoverDims &d = dims[(size_t)i];
+            const int64_t nc = d.nx * d.ny, r0 = rings[(size_t)i], r1 = rings[(size_t)i + 1];
+            int64_t *cnt = counts + 4 * i;
+            cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+            if (nc == 0) return;
+            std::vector<uint8_t> own;
+            std::vector<int32_t> first((size_t)nc);
+            std::vector<double> cross((size_t)(verts[(size_t)r1] - verts[(size_t)r0]));
+            uint8_t *bits = want_grid ? grid + cells[(size_t)i] : (own.resize((size_t)nc), own.data());
+            pcover_field_host(verts.data(), r0, r1, x, y, d, width, res, caps, poff.data(), P, path_ids, fpo[(size_t)i], fpo[(size_t)i + 1], bits,
+                              first.data(), cross.data(), cnt);
+        });
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
     return FCPP_OK;
 }
 

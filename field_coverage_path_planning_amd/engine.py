@@ -1701,6 +1701,146 @@ def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_
     return HeadlandPaths(*out, ring_pair)
 
 
+# ---- polygon coverage (fcpp_polygon_cover_sizes / fcpp_polygon_cover; the rule: include/fcpp.h) -----------------------------------------
+@dataclass
+class PolygonCoverage:
+    """polygon_coverage(): what the working passes of a path set cover of every field, on a grid of res x res cells"""
+    counts: object              # (n, 4) int64, device: cells inside; inside and covered; inside and overlapped; covered and not inside
+    res: float
+    status: object              # (n) int32: 0, FCPP_EINVAL (the swath rule) or FCPP_EUNSUPPORTED (more than 2^28 cells): no cells, zero counts
+    dims: object                # (n, 4) int64, device: gx, gy (float64 bits: origin()), nx, ny
+    cell_offsets: object        # (n + 1) int64, device; cell_offsets_host: the numpy copy
+    cell_offsets_host: object
+    cells: object = None        # (total cells) uint8 when asked for (want_grid): bit 0 inside, bit 1 covered, bit 2 overlapped
+
+    def _area(self, k):
+        return self.counts[:, k].to(_torch().float64) * (self.res * self.res)
+
+    @property
+    def field_area(self):
+        return self._area(0)
+
+    @property
+    def covered_area(self):
+        return self._area(1)
+
+    @property
+    def missed_area(self):
+        return self._area(0) - self._area(1)
+
+    @property
+    def overlap_area(self):
+        return self._area(2)
+
+    @property
+    def spill_area(self):
+        return self._area(3)
+
+    @property
+    def rate(self):
+        """covered / inside per field; NaN for a field without cells"""
+        f64 = _torch().float64
+        return self.counts[:, 1].to(f64) / self.counts[:, 0].to(f64)
+
+    def origin(self):
+        """(n, 2) float64: gx, gy -- cell (a, b) of field i is sampled at origin[i] + (a + 0.5, b + 0.5) res"""
+        return self.dims[:, :2].contiguous().view(_torch().float64)
+
+    def grid(self, i):
+        """field i's cells as an (ny, nx) view (want_grid=True)"""
+        if self.cells is None:
+            raise ValueError('polygon_coverage(..., want_grid=True) keeps the cells')
+        nx, ny = (int(v) for v in self.dims[i, 2:].tolist())
+        return self.cells[int(self.cell_offsets_host[i]):int(self.cell_offsets_host[i + 1])].view(ny, nx)
+
+
+def _cover_path_set(ps, first_path, dev):
+    """one path set -> (offsets, offsets_host or None, x, y, path_field int64, work uint8, pass int32), all on the device"""
+    torch = _torch()
+    if isinstance(ps, FieldPaths):
+        np_ = int(ps.offsets.numel()) - 1
+        return (ps.offsets, ps.offsets_host, ps.x, ps.y, torch.arange(np_, dtype=torch.int64, device=dev), (ps.part == 0).to(torch.uint8), ps.leg)
+    if isinstance(ps, HeadlandPaths):
+        nr, total = int(ps.offsets.numel()) - 1, int(ps.x.numel())
+        ring = torch.repeat_interleave(torch.arange(nr, dtype=torch.int32, device=dev), ps.offsets[1:] - ps.offsets[:-1], output_size=total)
+        return (ps.offsets, ps.offsets_host, ps.x, ps.y, ps.ring_pair[:, 0].contiguous(), ((ps.part == 0) | (ps.part == 4)).to(torch.uint8), -1 - ring)
+    offsets, x, y, path_field, work, pas = ps
+    x, y = _dev_f64(x, dev).reshape(-1), _dev_f64(y, dev).reshape(-1)
+    total = int(x.numel())
+    off, off_h = _offsets(offsets, total, dev)
+    np_ = int(off.numel()) - 1
+    pf = torch.zeros(np_, dtype=torch.int64, device=dev) if path_field is None else torch.as_tensor(path_field, device=dev).to(torch.int64).reshape(-1)
+    w = torch.ones(total, dtype=torch.uint8, device=dev) if work is None else (torch.as_tensor(work, device=dev).reshape(-1) != 0).to(torch.uint8)
+    if pas is None:
+        pas = torch.repeat_interleave(torch.arange(first_path, first_path + np_, dtype=torch.int32, device=dev), off[1:] - off[:-1], output_size=total)
+    else:
+        pas = torch.as_tensor(pas, device=dev).to(torch.int32).reshape(-1)
+    if int(pf.numel()) != np_ or int(w.numel()) != total or int(pas.numel()) != total or int(y.numel()) != total:
+        raise ValueError('a path set needs one field per path and one work flag and pass id per sample')
+    return off, off_h, x, y, pf, w, pas
+
+
+def _cover_paths(paths, n, dev):
+    """the path sets of polygon_coverage, concatenated on the device -> (n_paths, total, path_offsets, its host copy or None, x, y, work,
+    pass, field_path_offsets, path_ids): what fcpp_polygon_cover takes"""
+    torch = _torch()
+    if isinstance(paths, (FieldPaths, HeadlandPaths)) or (isinstance(paths, tuple) and len(paths) == 6
+                                                          and not isinstance(paths[0], (FieldPaths, HeadlandPaths, tuple))):
+        paths = (paths,)
+    sets, first = [], 0
+    for ps in paths:
+        sets.append(_cover_path_set(ps, first, dev))
+        first += int(sets[-1][0].numel()) - 1
+    n_paths = first
+    starts = np.concatenate([[0], np.cumsum([int(s[2].numel()) for s in sets])]).astype(np.int64)
+    total = int(starts[-1])
+    cat = lambda k, dt: (torch.cat([s[k] for s in sets]) if sets else torch.empty(0, dtype=dt, device=dev)).contiguous()
+    x, y, owner, work, pas = cat(2, torch.float64), cat(3, torch.float64), cat(4, torch.int64), cat(5, torch.uint8), cat(6, torch.int32)
+    poff = torch.cat([s[0][:-1] + int(starts[k]) for k, s in enumerate(sets)] + [torch.full((1,), total, dtype=torch.int64, device=dev)]).contiguous()
+    poff_h = None
+    if all(s[1] is not None for s in sets):
+        poff_h = np.ascontiguousarray(np.concatenate([np.asarray(s[1][:-1], dtype=np.int64) + starts[k] for k, s in enumerate(sets)] + [[total]]),
+                                      dtype=np.int64)
+    if n_paths and (n == 0 or int(owner.min()) < 0 or int(owner.max()) >= n):
+        raise ValueError('path_field must name a field of the batch')
+    ids = torch.argsort(owner, stable=True).contiguous()
+    fpo = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        fpo[1:] = torch.cumsum(torch.bincount(owner, minlength=n), dim=0)
+    return n_paths, total, poff, poff_h, x, y, work, pas, fpo, ids
+
+
+def polygon_coverage(fields, width, res, paths=(), caps='flat', want_grid=False, device=None):
+    """The coverage report of a batch of polygon fields (fcpp_polygon_cover_sizes + fcpp_polygon_cover) -> PolygonCoverage.  `fields` are the
+    SURVEYED boundaries (what headland() was given, not the work area), `width` the working width, `res` the cell size [m].  paths: one or
+    more FieldPaths / HeadlandPaths, or tuples (offsets, x, y, path_field, work, pass) -- path_field: the field of every path (None: field
+    0), work: a flag per sample (None: all work), pass: an id per sample (None: the path's index); they are concatenated on the device.
+    Only the working samples cover: the swaths of field paths (pass id: the leg), the straight elements and followed arcs of headland loops
+    (one id per ring, negative: distinct from the legs).  A cell is covered iff a working segment passes within width / 2 of its centre,
+    runs ending flat (caps='flat') or round ('round': fcpp_cover_grid's predicate), overlapped iff segments of two different pass ids do.
+    Per field: counts, field_area, covered_area, missed_area, overlap_area, spill_area (covered outside the boundary or inside a hole), rate;
+    want_grid=True keeps the cells (grid(i))."""
+    ctx = get_context(device)
+    torch = _torch()
+    pf = polygon_fields(fields, device)
+    dev = pf.x.device
+    n = pf.n
+    if caps not in ('flat', 'round'):
+        raise ValueError("caps must be 'flat' or 'round'")
+    n_paths, total, poff, poff_h, x, y, work, pas, fpo, ids = _cover_paths(paths, n, dev)
+    dims = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    coff, coff_h = torch.empty(n + 1, dtype=torch.int64, device=dev), np.zeros(n + 1, dtype=np.int64)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_polygon_cover_sizes(ctx.handle, *pf._head(), float(width), float(res), _ptr(dims), _ptr(coff), _host_ptr(coff_h), _ptr(status)))
+    cells = torch.empty(int(coff_h[-1]), dtype=torch.uint8, device=dev) if want_grid else None
+    L.check(ctx.lib.fcpp_polygon_cover(ctx.handle, *pf._head(), float(width), float(res), 1 if caps == 'round' else 0, n_paths, _ptr(poff),
+                                       _host_ptr(poff_h), total, _ptr(x), _ptr(y), _ptr(work), _ptr(pas), _ptr(fpo), _ptr(ids), _ptr(coff),
+                                       _host_ptr(coff_h), _ptr(cells), _ptr(counts), _ptr(status)))
+    return PolygonCoverage(counts, float(res), status, dims, coff, coff_h, cells)
+
+
 _drive_headland = headland_paths      # (plan_polygon_fields has a flag of that name)
 
 
@@ -1715,17 +1855,21 @@ class PolygonPlan:
     route: object               # SwathRoute
     paths: object               # FieldPaths
     headland_paths: object = None       # HeadlandPaths of `headland` when asked for (headland_paths=True), else None
+    coverage: object = None             # PolygonCoverage of `fields` under paths (and headland_paths) when asked for (coverage_resolution), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
-                        arc_step=0.1, headland_paths=False, device=None):
+                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
     The headland pass rings are returned (headland) but not part of the path; headland_paths=True also drives them (headland_paths() at the
     same radius, spacing and `reversing`: one closed loop per ring, PolygonPlan.headland_paths).  The loops are not joined to each other or
-    to the field paths' entries: the connector operators do that from the loops' first poses."""
+    to the field paths' entries: the connector operators do that from the loops' first poses.  coverage_resolution [m]: also report what the
+    plan covers of the ORIGINAL fields (polygon_coverage at that cell size over the field paths, and the headland loops if they were driven:
+    PolygonPlan.coverage); nothing else in the chain changes."""
     torch = _torch()
+    fields = polygon_fields(fields, device)
     lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
     ang = _dev_f64(angles, work.x.device).reshape(-1)
     idx, _ = best_swath_angle(work, ang, width, turn_cost, device=device)
@@ -1735,7 +1879,10 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device)
     paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device)
     hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp)
+    cov = None
+    if coverage_resolution is not None:
+        cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device)
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov)
 
 
 def _polys(polygons):

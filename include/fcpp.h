@@ -808,6 +808,55 @@ int fcpp_headland_path_fill(fcpp_ctx *ctx, int64_t n_rings, const int64_t *ring_
                             int64_t total_samples, double *out_x_dev, double *out_y_dev, double *heading_dev, double *kappa_dev,
                             int8_t *part_dev, int8_t *gear_dev, int32_t *leg_dev);
 
+/* ---- polygon coverage: what a sampled path set covers of fields given as rings -------------------------------------------------------------
+ * Build-defined.  The last stage of the polygon chain: per field, on a grid of cells, the area inside the SURVEYED boundary, the part of it
+ * the working passes cover, the part two different passes cover (double application), and what they cover outside the boundary or inside a
+ * hole.  fcpp_cover_grid answers this for quads (four half-planes, one polyline, a host array of jobs, every tile culling every segment);
+ * this operator takes rings with holes, a whole path set with a work mask and pass ids, and keeps a tile's work independent of its field's
+ * sample count.  Standalone: nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_pcoverfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Fields.  The two-level CSR of the swath operators (ring_offsets, vert_offsets, x, y), even-odd interior.
+ *   - Grid of field i.  r = width / 2, m = ceil(r / res) margin cells; gx = x_min - m res, gy = y_min - m res;
+ *     nx = ceil((x_max - x_min) / res) + 2 m, ny likewise; cell (a, b) is sampled at (gx + ((double)a + 0.5) res, gy + ((double)b + 0.5) res):
+ *     fcpp_cover_grid's expression with ox = gx, oy = gy, shift = 0.5.  A failed field has an empty grid and zero counts, its paths are
+ *     ignored; the other fields are unaffected.
+ *   - Inside.  A cell is inside iff an odd number of edges cross its row at u < X -- the half-open crossing rule of the swaths in the frame
+ *     theta = 0: an edge (p, q) crosses row Y iff (y_p <= Y) != (y_q <= Y), at u = x_p + (Y - y_p) / (y_q - y_p) (x_q - x_p).
+ *   - Paths.  One sampled path set in the CSR form every path operator emits (path_offsets, x, y).  Field i owns the paths
+ *     path_ids[field_path_offsets[i] .. field_path_offsets[i + 1]) (int64; path_ids NULL: the identity).  work (uint8 per sample, NULL: all
+ *     samples work), pass (int32 per sample, NULL: the path's index).
+ *   - Working segments.  Segment (k, k + 1) of a path works iff both samples work and both are finite; its pass is pass[k].  An end of a
+ *     working segment is a JOINT iff the neighbouring segment of the same path on that side also works.
+ *   - Covered.  With a -> b the segment, p the cell, dot = (p - a).(b - a), len2 = |b - a|^2, cross = (b - a) x (p - a), strictly:
+ *         0 < dot < len2 : cross^2 < r^2 len2
+ *         dot <= 0       : a joint: |p - a|^2 < r^2;  a flat end: dot == 0 and cross^2 < r^2 len2
+ *         dot >= len2    : a joint: |p - b|^2 < r^2;  a flat end: dot == len2 and cross^2 < r^2 len2
+ *     so a run of working segments sweeps a rectangle with rounded interior joints, as an implement does.  caps = 1 makes every end round:
+ *     the predicate is then bit for bit fcpp_cover_grid's with strict = 1.
+ *   - Overlapped.  A cell is overlapped iff working segments of at least two different pass ids cover it.
+ *   - counts (int64, 4 per field, zeroed by the call): cells inside; inside and covered; inside and overlapped; covered and not inside
+ *     (spill, within the grid).  grid (optional): one byte per cell, row-major [b][a], field i's at cell_offsets[i]: bit 0 inside, bit 1
+ *     covered, bit 2 overlapped.
+ * Status per field, int32: 0; FCPP_EINVAL -- no ring, a ring with fewer than 3 vertices, a vertex that is not finite; FCPP_EUNSUPPORTED --
+ * more than 2^28 cells.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, width or res <= 0 or not finite, caps not
+ * 0 or 1, a path id outside [0, n_paths); FCPP_ESIZE -- negative sizes, offsets that do not start at 0, decrease or do not end at their
+ * total, cell offsets that do not end at these fields' cells, 2^31 tiles or chunks of 256 segments or more.
+ * fcpp_polygon_cover_sizes: dims_dev -- n records of 32 bytes (gx, gy as float64; nx, ny as int64); cell_offsets_dev (n + 1 int64), its copy
+ * to cell_offsets_host (or NULL); status_dev (or NULL).  fcpp_polygon_cover recomputes the grids from the same inputs (nothing is kept in the
+ * context between the two calls); path_offsets_host and cell_offsets_host: the host copies, or NULL to have what is needed read back;
+ * work_dev, pass_dev, path_ids_dev, grid_dev and status_dev may be NULL (cell_offsets too when grid_dev is).  Inputs are never written,
+ * outputs exactly over their extent, natural alignment suffices.  Both entries synchronise. */
+int fcpp_polygon_cover_sizes(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev,
+                             int64_t n_verts, const double *x_dev, const double *y_dev, double width, double res, void *dims_dev,
+                             int64_t *cell_offsets_dev, int64_t *cell_offsets_host, int32_t *status_dev);
+int fcpp_polygon_cover(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                       const double *x_dev, const double *y_dev, double width, double res, int caps, int64_t n_paths,
+                       const int64_t *path_offsets_dev, const int64_t *path_offsets_host, int64_t total_points, const double *px_dev,
+                       const double *py_dev, const uint8_t *work_dev, const int32_t *pass_dev, const int64_t *field_path_offsets_dev,
+                       const int64_t *path_ids_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, uint8_t *grid_dev,
+                       int64_t *counts_dev, int32_t *status_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -920,6 +969,16 @@ int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int6
                               int64_t *path_offsets, int64_t *leg_offsets, double *work_length, double *transit_length, double *skipped_length,
                               int32_t *status, int32_t *leg_kind, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
                               double *out_x, double *out_y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
+/* The polygon-coverage rule (csrc/fcpp_pcoverfn.h) evaluated on the HOST, on host pointers, sizes and cover in one call: what the device
+ * results are compared with bit for bit.  Arguments and the call's errors as for fcpp_polygon_cover_sizes / fcpp_polygon_cover.  dims
+ * (n records of 32 bytes), cell_offsets (n + 1), status (n): any may be NULL.  counts (4 n) NULL: the sizes only, the paths are not read.
+ * grid (may be NULL) is written when all cells fit in cell_cap: call once without it for the sizes, then with it.  Fields are handed to
+ * the library's host threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                             const double *y, double width, double res, int caps, int64_t n_paths, const int64_t *path_offsets,
+                             int64_t total_points, const double *px, const double *py, const uint8_t *work, const int32_t *pass,
+                             const int64_t *field_path_offsets, const int64_t *path_ids, void *dims, int64_t *cell_offsets, int64_t cell_cap,
+                             uint8_t *grid, int64_t *counts, int32_t *status);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch
