@@ -189,6 +189,7 @@ PROTOTYPES = [
     ('fcpp_gather', C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, c_i64_p, _VP, C.c_int]),
     ('fcpp_debug_math', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_debug_math_dev', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, _VP]),
+    ('fcpp_debug_offsets', C.c_int, [C.c_int64, C.c_int, _VP, _VP, _VP]),
     ('fcpp_debug_dubins', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_rs', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_swaths', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int, C.c_double, C.c_double, C.c_double]

@@ -666,8 +666,12 @@ int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, D
         const size_t want = need + need / 4;
         if (hipMalloc(&sl.p, want) != hipSuccess) { (void)hipGetLastError(); sl.p = nullptr; err = "out of device memory for the planner's scratch"; return FCPP_ENOMEM; }
         sl.cap = want;
-        // (the flags live at the start of the allocation and are never cleared again: they hold generation numbers)
-        DEVCHK(hipMemsetAsync(sl.p, 0, PLAN_TOTALS * sizeof(int64_t), st));
+        // (the flags live at the start of the allocation and are never cleared again: they hold generation numbers; behind them the two
+        // buffers of aggregates, zero from here on whenever a setup begins: try_device_setup)
+        DevPlanScratch head;
+        devplan_scratch_layout(1, 1, sl.p, head);
+        DEVCHK(hipMemsetAsync(sl.p, 0, (size_t)(reinterpret_cast<unsigned char *>(head.agg + 2 * (size_t)OFF_WORDS) - static_cast<unsigned char *>(sl.p)), st));
+        sl.agg_flip = 0; sl.agg_dirty = false;
     }
     if (!c->plan_totals_host)
         { DEVCHK(hipHostMalloc((void **)&c->plan_totals_host, PLAN_TOTALS * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->plan_totals_host, 0, PLAN_TOTALS * sizeof(int64_t)); }
@@ -788,7 +792,7 @@ int bind_and_upload_obstacles(fcpp_ctx *c, fcpp_batch *b, const fcpp_polys *obst
 int enqueue_fill(fcpp_batch *b, hipStream_t st, const DevTileConsts &tc, const DevPlanScratch &s, std::string &err)
 {
     b->cst.field_junc = b->t.field_junc;
-    const int frc = launch_devplan_fill(st, b->n_fields, tc, b->cst, s, b->t);
+    const int frc = launch_devplan_fill(st, b->n_fields, tc, b->cst, s, b->t, b->ctx->plan_totals_host);
     if (frc) { err = std::string("launch_devplan_fill: ") + hipGetErrorString((hipError_t)frc); return FCPP_EHIP; }
     return FCPP_OK;
 }
@@ -871,14 +875,24 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         if (lay.total_bytes > ((size_t)1 << 30)) spec = false;
     }
     tc.speculative = spec ? 1 : 0;
+    fcpp_ctx::PlanSlot &slot = c->plan_slots[c->plan_cur];
     if (spec) {
         if ((rc = take_slab(c, b, err)) != FCPP_OK) return rc;
         if ((rc = bind_and_upload_obstacles(c, b, obstacles, st, err)) != FCPP_OK) return rc;
+        // The aggregates of the two levels (fcpp_offsetfn.h) are cleared by NO command in the stream: the slot has two buffers, this setup adds
+        // into one (zero: the slot's allocation or the fill pass of its last speculative setup left it so) and its fill pass, which runs whatever
+        // the flags say, zeroes the other for the next.  Only a setup that ends between its first launch and its fill pass (a launch error)
+        // leaves them unknown: agg_dirty, and both are cleared in front of the next speculative setup of the slot.
+        if (slot.agg_dirty) { DEVCHK(hipMemsetAsync(s.agg, 0, 2 * (size_t)OFF_WORDS * sizeof(int64_t), st)); slot.agg_dirty = false; slot.agg_flip = 0; }
+        if (slot.agg_flip) std::swap(s.agg, s.agg_next);
+        slot.agg_flip ^= 1;
+        slot.agg_dirty = true;
     }
-    // ---- count, and the speculative fill pass right behind it
+    // ---- plan and count, and the speculative fill pass right behind them (it publishes the totals: no scan in between)
     const int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, obstacles ? obstacles->n_polys : 0, obstacles != nullptr, c->plan_totals_host);
     if (lrc) { (void)hipStreamSynchronize(st); err = std::string("launch_devplan_count: ") + hipGetErrorString((hipError_t)lrc); return FCPP_EHIP; }   // (drained: the caller's pinned records may still be read)
     if (spec && (rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    if (spec) slot.agg_dirty = false;
     // ---- wait for the totals, checks
     rc = await_totals(tot, tc.gen, st, t_call, err);
     tm.host_plan_ms = ms_since(t0);          // (the plan and the counting pass, on the device)
@@ -907,6 +921,8 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         if ((rc = bind_and_upload_obstacles(c, b, obstacles, st, err)) != FCPP_OK) return rc;
         tm.image_ms = ms_since(t0);
         t0 = std::chrono::steady_clock::now();
+        // (after a speculative counting phase no scan has run: the pass wrote every column, the scan makes the positions of the exact layout)
+        if (spec) { const int src = launch_devplan_rescan(st, n_fields, s); if (src) { err = std::string("launch_devplan_rescan: ") + hipGetErrorString((hipError_t)src); return FCPP_EHIP; } }
         tc.speculative = 0;
         tc.fuse_spans = fuse;
         if ((rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) return rc;
@@ -1655,6 +1671,18 @@ int fcpp_debug_math(int fn, int64_t n, const double *a, const double *b, double 
         else if (fn == 1) out0[i] = atan2_fd(a[i], b[i]);
         else if (fn == 2) out0[i] = fc_acos(a[i]);
         else out0[i] = fc_hypot(a[i], b[i]);
+    }
+    return FCPP_OK;
+}
+
+int fcpp_debug_offsets(int64_t n, int n_cols, const int64_t *counts, int64_t *prefix, int64_t *totals)
+{
+    if (n < 1 || n > OFF_FIELDS_MAX || n_cols < 1 || n_cols > PC_COLS || !counts || !prefix || !totals) return fail(FCPP_EINVAL, "bad arguments");
+    std::vector<int64_t> agg((size_t)OFF_WORDS);
+    for (int col = 0; col < n_cols; ++col) {
+        offset_aggregate(counts, n, col, agg.data());
+        for (int64_t i = 0; i < n; ++i) prefix[(int64_t)col * n + i] = offset_prefix(agg.data(), counts, n, col, i);
+        totals[col] = offset_total(agg.data(), n, col);
     }
     return FCPP_OK;
 }

@@ -145,7 +145,9 @@ struct fcpp_ctx {
     int setup_mode = FCPP_SETUP_AUTO;
     // (up to FOUR scratch allocations, one per stream that sets batches up: a caller that plans batch k + 1 on a second stream while batch k's step
     // still runs on the first -- the sustained rate of bench.py -- must not wait for that step because its fill pass shared the scratch)
-    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; };
+    // (agg_flip: which of the slot's two buffers of aggregates the next speculative setup accumulates into -- DevPlanScratch.agg; agg_dirty: a
+    // speculative setup ended between its planner and its fill pass, which would have zeroed the other buffer: both are cleared before the next)
+    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; int agg_flip = 0; bool agg_dirty = false; };
     static constexpr int kPlanSlots = 4;
     PlanSlot plan_slots[kPlanSlots];
     uint64_t plan_tick = 0;

@@ -11,6 +11,8 @@
 //                      quiet zone (last line, headland straights) + a lane per stretch between them (general tiles, or wave tiles by the
 //                      window cut, a stretch after the other)
 //   k_scan_*           exclusive scans over the fields of the per-field counts; the totals go to the host's pinned memory (polled)
+//                      (not launched by the speculative setup of a small batch: there every kernel adds its counts into per-block aggregates
+//                      and the next kernel takes a field's offsets from them -- fcpp_offsetfn.h, "two levels" below)
 //   k_tile_fields<1>   the records written at their scanned positions: the tables of ImageLayout, equal byte for byte to what BatchTiler::fill
 //                      writes on the host (tests/test_gpu_devplan.py)
 // Only the 128-byte fcpp_field records go to the device and the totals (one small copy) and fcpp_field_info come back.
@@ -24,6 +26,7 @@
 #include "fcpp_planfn.h"
 #include "fcpp_tilefn.h"
 #include "fcpp_cutfn.h"
+#include "fcpp_offsetfn.h"
 
 namespace fcpp {
 
@@ -42,6 +45,7 @@ enum PlanFlag : int { PF_FALLBACK = 0, PF_BAD_OBSTACLES = 1, PF_OVER_CAPACITY = 
 // behind the flags: [PX_ARRIVED] the columns of the counting phase's last scan that have published their totals (device only), [PX_DONE] the
 // generation number of the phase whose totals are complete -- written to the host's copy by the last column to arrive: the host polls it
 // (a word in its own pinned memory) instead of waiting for an event
+static_assert(PC_COLS <= OFF_ROW, "a block's row of aggregates holds every column");
 constexpr int PX_ARRIVED = PC_COLS + PF_COUNT, PX_DONE = PC_COLS + PF_COUNT + 1, PLAN_TOTALS = PC_COLS + PF_COUNT + 2;
 // (PF_OVER_CAPACITY: a speculative setup -- tables laid out by per-field capacities, the fill pass enqueued before the host has the totals
 // -- met a field beyond them: SPEC_* below; the host then lays the tables out from the totals and fills them again)
@@ -53,8 +57,9 @@ struct DevTileConsts {
     int32_t nu, nc;
     int32_t turn_quiet, wave_factor, field_work_tiles, max_prims, fuse_spans;
     int32_t no_bases;             // counting pass of a small batch: the fields' point offsets are not known yet (ONE scan, after the pass)
-    int32_t speculative;          // the tables are laid out by capacities: the counting pass and the scan watch them, the fill pass decides
-                                  // the fusing of spans itself and does nothing when a flag of this generation is up
+    int32_t speculative;          // the tables are laid out by capacities: the counting pass watches them, the fill pass decides the fusing of
+                                  // spans itself and does nothing when a flag of this generation is up.  No scan is launched: both passes take
+                                  // their offsets from the two levels of fcpp_offsetfn.h (DevPlanScratch.agg), the fill pass publishes the totals
     int32_t closed_cut;           // the general stretches of fields with a closed-form span are cut in closed form (fcpp_cutfn.h); 0: by the window cut of round 4
     int32_t dense;                // sample_spacing > 0: span of all complete passes + quiet runs of the straights + general tiles between them (k_tile_fields, "dense")
     int64_t span_line_max;        // TileConsts.span_line_max
@@ -73,6 +78,11 @@ struct DevPlanScratch {
     int64_t *counts, *bases;      // PC_COLS x n
     int64_t *blk_sums;            // PC_COLS x blocks of 1024 fields
     int64_t *totals;              // PLAN_TOTALS
+    // two levels (fcpp_offsetfn.h), speculative setups: agg[col][block of OFF_B fields] = the block's sum of the column, added up with atomics by
+    // the planner (PC_POINTS) and the counting pass (every other column), read by the NEXT kernel only.  Two buffers per plan slot, zero when
+    // the slot is allocated: a setup accumulates into `agg`, its fill pass zeroes `agg_next`, the next setup of the slot swaps them -- no
+    // clearing command in the stream (fcpp_api.cpp: try_device_setup, which also says what happens after a setup that ended in between)
+    int64_t *agg, *agg_next;      // OFF_WORDS each: OFF_NB rows of OFF_ROW words, PC_COLS of them used
     // the counting pass keeps the first DEVPLAN_KEEP_TILES wave tiles of every field (records with field-relative indices): the fill pass
     // copies and rebases them instead of cutting the field again (fields with more are cut again)
     DevTile *keep_tiles;          // n x DEVPLAN_KEEP_ROWS
@@ -99,6 +109,8 @@ static_assert(sizeof(DevWaveTile) == 64, "a row of the kept wave tiles holds the
 // one scan that follows the pass, from the offsets it has just computed (span_counts): one launch and one scan fewer in front of the pass.
 // phase 1: plan + count.  Enqueues k_plan_fields, the scans and the counting pass; afterwards totals[] holds the sums and the flags, and so
 // does totals_host (pinned host memory the device can write, or null) once the stream has got there: the scans write it themselves.
+// tc.speculative (at most OFF_FIELDS_MAX fields, reference sampling): planner and counting pass only -- the pass has the point offsets from
+// the planner's aggregates, writes every column and adds it to the aggregates; the totals are published by the speculative fill pass.
 // fields: the records as the device reaches them (s.fields_in after a copy, or the caller's pinned memory).
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
                          int64_t n_polys, int check_obstacles, int64_t *totals_host);
@@ -107,7 +119,11 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
 // sizing only (fcpp_plan_points): k_plan_fields without primitives; counts[PC_POINTS][field] = points of the field
 int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const DevPlanScratch &s, const fcpp_field *fields);
 // phase 2: the tables (pointers into the batch's slab, laid out by the host).  `bases` / `totals` as phase 1 left them.
-int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &t);
+// tc.speculative: positions from the two levels; one more workgroup publishes the totals, the flags and tc.gen to totals_host (the host
+// polls it: await_totals) and zeroes s.agg_next -- also when the flags make the pass a no-op.
+int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &t, int64_t *totals_host);
+// the exact layout after a speculative counting phase (over capacity): the scan of all columns as the pass wrote them -> bases, totals
+int launch_devplan_rescan(hipStream_t st, int64_t n, const DevPlanScratch &s);
 // fcpp_math.h on the device (tests): fn 0 sincos, 1 atan2(a, b), 2 acos(a), 3 hypot(a, b)
 int launch_debug_math(hipStream_t st, int fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
 

@@ -15,6 +15,8 @@ size_t devplan_scratch_layout(int64_t n, int max_prims, void *base, DevPlanScrat
     auto take = [&](auto *&p, size_t count) { p = base ? reinterpret_cast<decltype(p + 0)>(static_cast<unsigned char *>(base) + off) : nullptr; off = (off + count * sizeof(*p) + 255) & ~(size_t)255; };
     const size_t nn = (size_t)(n > 0 ? n : 1), nblk = (nn + 1023) / 1024;
     take(s.totals, PLAN_TOTALS);      // (first: the flags keep their place whatever n is)
+    take(s.agg, 2 * (size_t)OFF_WORDS);      // (and so do the two buffers of aggregates, zeroed with the flags when the slot is allocated)
+    s.agg_next = s.agg ? s.agg + (size_t)OFF_WORDS : nullptr;
     take(s.fields_in, nn); take(s.info, nn); take(s.fields_tmp, nn); take(s.prims_tmp, nn * (size_t)max_prims);
     take(s.counts, nn * PC_COLS); take(s.bases, nn * PC_COLS); take(s.blk_sums, nblk * PC_COLS);
     take(s.keep_tiles, nn * DEVPLAN_KEEP_ROWS); take(s.keep_wtiles, nn * DEVPLAN_KEEP_WROWS);
@@ -40,6 +42,14 @@ int64_t devplan_small_blocks()
 
 namespace {
 
+// a field's count of column `col` into the column's aggregate of the field's block (fcpp_offsetfn.h; agg null: not a speculative setup).
+// An integer atomic whose result nobody takes: nothing waits for it but the kernel's end, and only the next kernel reads the aggregates.
+__device__ __forceinline__ void agg_add(int64_t *agg, int col, int64_t field, int64_t v)
+{
+    if (agg && v != 0)
+        (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(agg) + offset_at(col, field / OFF_B), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- k_plan_fields: one thread per field, the host's own plan function ----------------------------------------------------------------
 struct DevSink {
     DevPrim *base;
@@ -56,7 +66,7 @@ struct DevSink {
 
 __global__ __launch_bounds__(64) void k_plan_fields(int64_t n, PlanConsts pc, const fcpp_field *__restrict__ fin, fcpp_field_info *__restrict__ info,
                                                     DevField *__restrict__ ftmp, DevPrim *__restrict__ ptmp, int64_t *__restrict__ counts,
-                                                    int64_t *__restrict__ totals, int64_t n_polys, int check_obstacles, int count_only, int64_t gen)
+                                                    int64_t *__restrict__ totals, int64_t *__restrict__ agg, int64_t n_polys, int check_obstacles, int count_only, int64_t gen)
 {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
@@ -67,6 +77,7 @@ __global__ __launch_bounds__(64) void k_plan_fields(int64_t n, PlanConsts pc, co
     DevSink sink{ count_only ? nullptr : ptmp + i * pc.max_prims, count_only ? 0 : pc.max_prims, 0 };
     const int64_t npts = plan_field_t(pc, f, info[i], ftmp[i], sink);
     counts[(int64_t)PC_POINTS * n + i] = npts;
+    agg_add(agg, PC_POINTS, i, npts);
     if (count_only) return;
     counts[(int64_t)PC_PRIMS * n + i] = ftmp[i].prim_count;
     if (sink.n > pc.max_prims) atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_FALLBACK), (unsigned long long)gen);
@@ -112,7 +123,7 @@ __device__ __forceinline__ double area_centroid_q(double px, double py, int i, d
 
 __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, const fcpp_field *__restrict__ fin, fcpp_field_info *__restrict__ info,
                                                       DevField *__restrict__ ftmp, DevPrim *__restrict__ ptmp, int64_t *__restrict__ counts,
-                                                      int64_t *__restrict__ totals, int64_t n_polys, int check_obstacles, int64_t gen)
+                                                      int64_t *__restrict__ totals, int64_t *__restrict__ agg, int64_t n_polys, int check_obstacles, int64_t gen)
 {
     using namespace p16;
     const int lane = threadIdx.x, l16 = lane & 15, i = lane & 3, lp = l16 >> 2;
@@ -144,6 +155,7 @@ __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, 
         if (w0) {
             counts[(int64_t)PC_POINTS * n + field] = npts;
             counts[(int64_t)PC_PRIMS * n + field] = prim_count;
+            agg_add(agg, PC_POINTS, field, npts);
             if (n_pushed > pc.max_prims) atomicMax(reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_FALLBACK), (unsigned long long)gen);
         }
     };
@@ -483,12 +495,11 @@ __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, 
 }
 
 // a column's total to the host's copy; the flags (generation numbers, see PlanFlag) with the first column of the last scan
-__device__ __forceinline__ void publish_total(const int64_t *totals, int64_t *mirror, int col, int64_t value, bool flags, bool over_elsewhere = false)
+__device__ __forceinline__ void publish_total(const int64_t *totals, int64_t *mirror, int col, int64_t value, bool flags)
 {
     if (!mirror) return;
     mirror[col] = value;
-    // (over_elsewhere: PF_OVER_CAPACITY may still be raised by the workgroup of PC_SPAN in this very launch -- that one publishes it)
-    if (flags) for (int k = 0; k < PF_COUNT; ++k) if (!(over_elsewhere && k == PF_OVER_CAPACITY)) mirror[PC_COLS + k] = totals[PC_COLS + k];
+    if (flags) for (int k = 0; k < PF_COUNT; ++k) mirror[PC_COLS + k] = totals[PC_COLS + k];
 }
 
 // the last scan of a counting phase: a column's workgroup has published its total; the last one to arrive tells the host (PX_DONE)
@@ -603,10 +614,9 @@ __global__ __launch_bounds__(256) void k_scan_apply(int64_t n, int c0, int64_t *
 // pass for the headline's 4096 fields.  derive: the columns that depend on the fields' point offsets (span_counts) are made here, by
 // their own workgroups, from the offsets (a scan of PC_POINTS of their own), the spans' lengths (PC_SPAN_PTS) and PC_WORK.
 __global__ __launch_bounds__(1024) void k_scan_small(int64_t n, int c0, int64_t *__restrict__ counts, int64_t *__restrict__ bases, int64_t *__restrict__ totals,
-                                                     int64_t *__restrict__ mirror, int with_flags, int derive, int fuse_possible, int64_t spec_gen, int64_t done_gen)
+                                                     int64_t *__restrict__ mirror, int with_flags, int derive, int fuse_possible, int64_t done_gen)
 {
     __shared__ int64_t lds[16];
-    int over = 0;                        // (spec_gen > 0: a speculative setup -- a span of more chunks than its layout has room for raises PF_OVER_CAPACITY)
     const int col = c0 + blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // exclusive scan over the workgroup's 4096 elements (four a thread): -> the base of the thread's first, tot = the chunk's sum
@@ -649,7 +659,6 @@ __global__ __launch_bounds__(1024) void k_scan_small(int64_t n, int c0, int64_t 
                 int64_t c_span, c_span_f, c_wsp, c_unf;
                 span_counts(off, S[k], work[k] != 0, fuse_possible != 0, c_span, c_span_f, c_wsp, c_unf);
                 v[k] = col == PC_SPAN ? c_span : (col == PC_SPAN_F ? c_span_f : (col == PC_WORK_SPAN_PTS ? c_wsp : c_unf));
-                if (col == PC_SPAN && c_span > SPEC_SPAN_CHUNKS) over = 1;
                 if (base + k < n) counts[(int64_t)col * n + base + k] = v[k];
                 off += pts[k];
             }
@@ -663,17 +672,9 @@ __global__ __launch_bounds__(1024) void k_scan_small(int64_t n, int c0, int64_t 
         for (int k = 0; k < 4; ++k) { if (base + k < n) bases[(int64_t)col * n + base + k] = run; run += v[k]; }
         carry += tot;
     }
-    const bool spec_span = derive && spec_gen > 0 && col == PC_SPAN;
-    if (spec_span) over = __syncthreads_or(over);
     if (threadIdx.x == 0) {
         totals[col] = carry;
-        publish_total(totals, mirror, col, carry, with_flags && blockIdx.x == 0, derive && spec_gen > 0);
-        if (spec_span) {
-            unsigned long long *flag = reinterpret_cast<unsigned long long *>(totals + PC_COLS + PF_OVER_CAPACITY);
-            if (over) atomicMax(flag, (unsigned long long)spec_gen);
-            const int64_t v = over ? spec_gen : totals[PC_COLS + PF_OVER_CAPACITY];      // (the counting pass may have raised it)
-            if (mirror) mirror[PC_COLS + PF_OVER_CAPACITY] = v;
-        }
+        publish_total(totals, mirror, col, carry, with_flags && blockIdx.x == 0);
         if (with_flags) publish_done(totals, mirror, (int)gridDim.x, done_gen);
     }
 }
@@ -681,12 +682,12 @@ __global__ __launch_bounds__(1024) void k_scan_small(int64_t n, int c0, int64_t 
 // mirror: the totals' copy in the host's pinned memory (or null), written by the scans themselves -- no copy command behind them;
 // with_flags: the flags the earlier kernels raised go along (the last scan of the counting phase)
 int launch_scan(hipStream_t st, int64_t n, int c0, int c1, const DevPlanScratch &s, int64_t *mirror, int with_flags, int derive = 0, int fuse_possible = 0,
-                int64_t spec_gen = 0, int64_t done_gen = 0)
+                int64_t done_gen = 0)
 {
     const int64_t nblk = (n + 1023) / 1024;
     const int nc = c1 - c0;
     if (nblk <= devplan_small_blocks()) {
-        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)nc), dim3(1024), 0, st, n, c0, s.counts, s.bases, s.totals, mirror, with_flags, derive, fuse_possible, spec_gen, done_gen);
+        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)nc), dim3(1024), 0, st, n, c0, s.counts, s.bases, s.totals, mirror, with_flags, derive, fuse_possible, done_gen);
         const hipError_t e0 = hipGetLastError();
         return e0 == hipSuccess ? 0 : (int)e0;
     }
@@ -780,6 +781,7 @@ struct TilePass {
     int64_t *const counts;
     const int64_t *const bases;
     int64_t *const totals;
+    int64_t *const agg;                  // the aggregates of this setup (speculative setups: two_level)
     DevTile *const keep_tiles;
     DevWaveTile *const keep_wtiles;
     const DevPlanTables &T;
@@ -794,7 +796,12 @@ struct TilePass {
             c_work_wave_pts = 0, c_wave_inside = 0, c_work_span_pts = 0, c_span_f = 0, c_unfusable = 0, c_chunks = 0, c_chunk_pts = 0;
     int cls = 0;
     bool fuse_spans = false, no_bases = false;
+    // speculative setups: no scan has run -- the field's positions are prefixes from two levels (fcpp_offsetfn.h), a lane's share of each
+    // loaded in header() and summed over the wavefront where the position is first needed
+    bool two_level = false;
+    int64_t pt_part = 0;                 // counting pass: this lane's share of the field's point offset, in flight during the cut
     int64_t pt_off = 0, wave_base = 0, general_base = 0, stat_base = 0, span_base = 0;
+    int64_t work_base = 0, open_base = 0, cls_base = 0, cls_first = 0;      // fill pass: the field's places in the work lists
     int64_t prim_index0 = 0;             // batch-wide index of the field's first primitive (fill pass)
     // what the pass decides
     int64_t S = 0, span_k = 0, fused_span = 0;      // the span: its points, its near-equal tiles
@@ -821,26 +828,51 @@ struct TilePass {
     int32_t my_pstart = INT32_MAX;
 
     __device__ __forceinline__ int64_t base_of(int col) const { return bases[(int64_t)col * n + field]; }
+    // two levels: prefix / total of a column, loaded and summed on the spot (all lanes of the wavefront)
+    __device__ __forceinline__ int64_t prefix_of(int col) const { return off_wave_sum(offset_prefix_part(agg, counts, n, col, field, lane)); }
+    __device__ __forceinline__ int64_t total_of(int col) const { return off_wave_sum(offset_total_part(agg, (int)offset_blocks(n), col, lane)); }
+    __device__ __forceinline__ int64_t work_pos() const { return two_level ? work_base : base_of(PC_WORK); }      // the field's place among the fields of field work
     __device__ __forceinline__ int64_t first_entry() const { return span_k > 0 ? 1 : 0; }      // the field's first entry behind its span's
 
     // ---- 1. the field's header; the fill pass's early loads.  false: a speculative fill pass with nothing to do
     __device__ __forceinline__ bool header(const fcpp_field_info *__restrict__ info)
     {
-        // a speculative fill pass does nothing when the counting phase raised a flag: the host sets the batch up again (or elsewhere)
-        if (FILL && tc.speculative) {
+        two_level = !DENSE && tc.speculative != 0;
+        no_bases = !FILL && tc.no_bases != 0;
+        int64_t p0 = 0, p1 = 0, t0 = 0, t1 = 0, in_a = 0, in_b = 0, in_c = 0;
+        if (two_level && !FILL) {
+            // counting pass: the planner's aggregates of the points and the block's point counts are requested here and summed behind the cut
+            pt_part = offset_prefix_part(agg, counts, n, PC_POINTS, field, lane);
+        } else if (two_level) {
+            // fill pass: ONE round of loads -- the flags, the blocks' rows of aggregates (every column's first level and total at once), and of the
+            // field's own block the counts in front of it, a lane per field.  Within the capacities (no flag up: else the pass ends here) a field
+            // has at most 255 primitives, nine tiles and entries, eight wave / general tiles and sixteen span chunks: the sums of these columns
+            // over the block's 63 fields fit sixteen bits each, four columns share a word and a wave sum; the points (< 2^31 a field) the low 48 bits
+            int64_t flag[PF_COUNT];
+            for (int k = 0; k < PF_COUNT; ++k) flag[k] = totals[PC_COLS + k];
+            const int r = (int)(field % OFF_B);
+            const int64_t *cb = counts + (field - r) + lane;
+            auto cnt = [&](int col) -> int64_t { return lane < r ? cb[(int64_t)col * n] : 0; };
+            in_a = cnt(PC_POINTS) | (cnt(PC_PRIMS) << 48);
+            in_b = cnt(PC_WAVE) | (cnt(PC_GENERAL) << 16) | (cnt(PC_STAT) << 32) | (cnt(PC_SPAN) << 48);
+            in_c = cnt(PC_SPAN_F) | (cnt(PC_WORK) << 16) | (cnt(PC_OPEN) << 32) | (cnt(PC_CLS0) << 48);
+            offset_row_sums(agg, (int)(field / OFF_B), (int)offset_blocks(n), lane, p0, p1, t0, t1);
+            // a speculative fill pass does nothing when the counting phase raised a flag: the host sets the batch up again (or elsewhere)
             bool up = false;
-            for (int k = 0; k < PF_COUNT; ++k) up = up || totals[PC_COLS + k] == tc.gen;
+            for (int k = 0; k < PF_COUNT; ++k) up = up || flag[k] == tc.gen;
             if (up) return false;
         }
-        // (speculative: the fusing of spans is the host's rule applied here -- all fields of field work have fusable spans, or nothing is fused)
-        fuse_spans = (FILL && tc.speculative) ? (tc.fuse_spans != 0 && totals[PC_UNFUSABLE] == 0 && totals[PC_WORK_SPAN_PTS] > 0) : tc.fuse_spans != 0;
-        // (scanned before either pass -- except before the counting pass of a small batch: tc.no_bases, see span_counts)
-        no_bases = !FILL && tc.no_bases != 0;
-        pt_off = no_bases ? 0 : base_of(PC_POINTS);
-        if (FILL) {
-            wave_base = base_of(PC_WAVE); general_base = base_of(PC_GENERAL); stat_base = base_of(PC_STAT);
-            span_base = base_of(fuse_spans ? PC_SPAN_F : PC_SPAN); prim_index0 = base_of(PC_PRIMS);
-        }
+        if (!two_level) {
+            // (speculative: the fusing of spans is the host's rule applied by the fill pass -- all fields of field work have fusable spans, or
+            // nothing is fused)
+            fuse_spans = tc.fuse_spans != 0;
+            // (scanned before either pass -- except before the counting pass of a small batch: tc.no_bases, see span_counts)
+            pt_off = no_bases ? 0 : base_of(PC_POINTS);
+            if (FILL) {
+                wave_base = base_of(PC_WAVE); general_base = base_of(PC_GENERAL); stat_base = base_of(PC_STAT);
+                span_base = base_of(fuse_spans ? PC_SPAN_F : PC_SPAN); prim_index0 = base_of(PC_PRIMS);
+            }
+        } else if (!FILL) fuse_spans = tc.fuse_spans != 0;
         // fill pass: everything it copies out of the scratch -- the field's descriptor, its fcpp_field_info, its primitives, a word per lane and
         // round -- is requested here, before the cut: the copies further down then wait for nothing (they were a chain of six round trips)
         nwords_p = prim_count * PWD;
@@ -849,6 +881,17 @@ struct TilePass {
             if (lane < NIW) iw = reinterpret_cast<const unsigned long long *>(&info[field])[lane];
 #pragma unroll
             for (int j = 0; j < PF_ROUNDS; ++j) { const int k = lane + 64 * j; pw[j] = k < nwords_p ? reinterpret_cast<const unsigned long long *>(prims)[k] : 0ull; }
+            if (two_level) {
+                // (the copies above are on their way; the shares were requested before them)
+                const uint64_t sa = (uint64_t)off_wave_sum(in_a), sb = (uint64_t)off_wave_sum(in_b), sc = (uint64_t)off_wave_sum(in_c);
+                fuse_spans = tc.fuse_spans != 0 && offset_col(t0, t1, PC_UNFUSABLE) == 0 && offset_col(t0, t1, PC_WORK_SPAN_PTS) > 0;
+                pt_off = offset_col(p0, p1, PC_POINTS) + (int64_t)(sa & 0xffffffffffffull); prim_index0 = offset_col(p0, p1, PC_PRIMS) + (int64_t)(sa >> 48);
+                wave_base = offset_col(p0, p1, PC_WAVE) + (int64_t)(sb & 0xffff); general_base = offset_col(p0, p1, PC_GENERAL) + (int64_t)((sb >> 16) & 0xffff);
+                stat_base = offset_col(p0, p1, PC_STAT) + (int64_t)((sb >> 32) & 0xffff);
+                span_base = fuse_spans ? offset_col(p0, p1, PC_SPAN_F) + (int64_t)(sc & 0xffff) : offset_col(p0, p1, PC_SPAN) + (int64_t)(sb >> 48);
+                work_base = offset_col(p0, p1, PC_WORK) + (int64_t)((sc >> 16) & 0xffff); open_base = offset_col(p0, p1, PC_OPEN) + (int64_t)((sc >> 32) & 0xffff);
+                cls_base = offset_col(p0, p1, PC_CLS0) + (int64_t)(sc >> 48);
+            }
             // (pt_off and prim_first become batch-wide: patched by the lane that holds their word)
             constexpr int W_PT = (int)(offsetof(DevField, pt_off) / 8), W_PF = (int)(offsetof(DevField, prim_first) / 8);
             constexpr bool PF_HI = (offsetof(DevField, prim_first) % 8) != 0;
@@ -1427,6 +1470,7 @@ struct TilePass {
         // boundaries of the batch arrays
         if (span_k > 0) {
             c_runs = 1 + n_quiet; c_span_pts = S;
+            if (!FILL && two_level) pt_off = off_wave_sum(pt_part);      // (counting pass of a speculative setup: the loads of header())
             const int64_t g0 = pt_off;                           // the span starts the path
             // (counting pass: fuse_spans = fusing is possible for this batch, both alternatives are counted; fill pass: the host's
             // decision -- all fields of field work have fusable spans, or nothing is fused)
@@ -1479,6 +1523,23 @@ struct TilePass {
         c[(int64_t)PC_CHUNKS * n] = c_chunks; c[(int64_t)PC_CHUNK_PTS * n] = c_chunk_pts;
     }
 
+    // counting pass of a speculative setup: the row just written, added to the aggregates of the field's block -- a lane per column, one
+    // atomic instruction nobody waits for (the points' column is the planner's)
+    __device__ __forceinline__ void add_counts_to_aggregates() const
+    {
+        if (!two_level) return;
+        const int64_t row[PC_COLS] = { 0, prim_count, c_tiles, c_wave, c_general, c_stat, c_span, c_work, c_open, (!is_work && cls == 0) ? 1 : 0, (!is_work && cls == 1) ? 1 : 0,
+                                       (!is_work && cls == 2) ? 1 : 0, (!is_work && cls == 3) ? 1 : 0, c_runs, c_span_pts, c_wave_pts, c_work_wave_pts, c_wave_inside,
+                                       c_work_span_pts, c_span_f, c_unfusable, c_chunks, c_chunk_pts };
+        static_assert(PC_POINTS == 0 && PC_PRIMS == 1 && PC_TILES == 2 && PC_WAVE == 3 && PC_GENERAL == 4 && PC_STAT == 5 && PC_SPAN == 6 && PC_WORK == 7 && PC_OPEN == 8 &&
+                      PC_CLS0 == 9 && PC_CLS3 == 12 && PC_RUNS == 13 && PC_SPAN_PTS == 14 && PC_WAVE_PTS == 15 && PC_WORK_WAVE_PTS == 16 && PC_WAVE_INSIDE == 17 &&
+                      PC_WORK_SPAN_PTS == 18 && PC_SPAN_F == 19 && PC_UNFUSABLE == 20 && PC_CHUNKS == 21 && PC_CHUNK_PTS == 22 && PC_COLS == 23, "the row in column order");
+        int64_t v = 0;
+#pragma unroll
+        for (int k = 1; k < PC_COLS; ++k) if (lane == k) v = row[k];
+        if (lane < PC_COLS) agg_add(agg, lane, field, v);
+    }
+
     // ---- 8. fill pass.  The field's descriptor and primitives at their final places (the primitives into LDS too, for the pack)
     __device__ __forceinline__ bool lds_pack() const { return STAGE && prim_count <= TW_LDS_PRIMS; }        // the pack's copies of the primitives come out of LDS
     __device__ __forceinline__ void fill_descriptor()
@@ -1504,6 +1565,9 @@ struct TilePass {
             const int64_t e0 = stat_base + first_entry(), nt = n_wave + n_general;
             for (int64_t j = lane; j < nt; j += 64) { T.stat_ids[e0 + j] = (int32_t)(e0 + j); T.stat_run[e0 + j] = 0; }
         }
+        // (two levels: a field within the capacities has at most nine entries, class 0 -- its place was summed in header(); another class
+        // would take its sums here, all lanes)
+        if (two_level && !is_work && cls > 0) { cls_base = prefix_of(PC_CLS0 + cls); for (int k = 0; k < cls; ++k) cls_first += total_of(PC_CLS0 + k); }
         if (lane == 0) {
             T.stat_first[field] = stat_base;
             if (field == n - 1) T.stat_first[n] = stat_base + c_stat;
@@ -1512,17 +1576,16 @@ struct TilePass {
                 memset(&w, 0, sizeof w);
                 w.field = (int32_t)field; w.n_tiles = (int32_t)n_wave; w.w_first = (int32_t)wave_base; w.e_first = (int32_t)stat_base; w.n_entries = (int32_t)c_stat;
                 w.fused_span = (int32_t)fused_span;
-                T.field_work[base_of(PC_WORK)] = w;              // (every such field has at most four tiles: class 0 is the only class in use)
-                DevFieldPack &P = T.field_packs[base_of(PC_WORK)];
+                T.field_work[work_pos()] = w;              // (every such field has at most four tiles: class 0 is the only class in use)
+                DevFieldPack &P = T.field_packs[work_pos()];
                 P.work = w;
                 P.span_points = fused_span;
                 for (int k = 0; k < 6; ++k) P._pad0[k] = 0;
                 P._pad1 = 0.0;
                 for (int k = 0; k < 4; ++k) P._pad2[k] = 0.0;
             } else {
-                int64_t cls_first = 0;
-                for (int k = 0; k < cls; ++k) cls_first += totals[PC_CLS0 + k];
-                T.red_paths[cls_first + base_of(PC_CLS0 + cls)] = (int32_t)field;
+                if (!two_level) { for (int k = 0; k < cls; ++k) cls_first += totals[PC_CLS0 + k]; cls_base = base_of(PC_CLS0 + cls); }
+                T.red_paths[cls_first + cls_base] = (int32_t)field;
             }
         }
     }
@@ -1549,12 +1612,12 @@ struct TilePass {
     __device__ __forceinline__ void fill_pack()
     {
         if (!is_work) {
-            const int64_t ob = base_of(PC_OPEN);
+            const int64_t ob = two_level ? open_base : base_of(PC_OPEN);
             for (int64_t j = lane; j < n_wave; j += 64) T.open_wave_ids[ob + j] = (int32_t)(wave_base + j);
             return;
         }
         const bool from_lds = lds_pack();
-        DevFieldPack &P = T.field_packs[base_of(PC_WORK)];
+        DevFieldPack &P = T.field_packs[work_pos()];
         if (lane < FIELD_WORK_TILES) P.tile[lane] = my_wt;               // (lanes without a tile hold zeros)
         {
             unsigned long long *dst = reinterpret_cast<unsigned long long *>(&P.field);
@@ -1607,7 +1670,7 @@ struct TilePass {
                     t.max_kappa = fmax(t.max_kappa, tp.max_kappa); t.max_alat = fmax(t.max_alat, tp.max_alat); t.max_jump = fmax(t.max_jump, tp.max_jump);
                     t.n_viol += tp.n_viol; t.n_adjusted += tp.n_adjusted;
                 }
-                T.work_totals[base_of(PC_WORK)] = t;
+                T.work_totals[work_pos()] = t;
             }
         }
         // the field's fcpp_field_info stays with the batch (fcpp_batch_info copies it back when asked)
@@ -1616,19 +1679,52 @@ struct TilePass {
     }
 };
 
+// The fill pass of a speculative setup, its first workgroup: what the last scan of a counting phase does for the host, without a scan.
+// Wavefront 0 sums every column's aggregates (total(col), fcpp_offsetfn.h) and writes the totals, the flags and then the phase's generation
+// number to the host's copy (await_totals polls that word) -- whatever the flags say: a pass they make a no-op is waited for as well.
+// Wavefront 1 zeroes the OTHER buffer of aggregates, the one the slot's next setup accumulates into (nothing of this setup reads or writes it).
+__device__ __forceinline__ void publish_two_level(int64_t n, int64_t gen, int64_t *__restrict__ totals, const int64_t *__restrict__ agg, int64_t *__restrict__ agg_next,
+                                                  int64_t *__restrict__ mirror, int wave, int lane)
+{
+    if (wave == 1) {
+        for (int k = lane; k < OFF_WORDS; k += 64) agg_next[k] = 0;
+        return;
+    }
+    if (wave != 0) return;
+    int64_t flag[PF_COUNT];
+#pragma unroll
+    for (int k = 0; k < PF_COUNT; ++k) flag[k] = totals[PC_COLS + k];
+    int64_t p0, p1, t0, t1;
+    offset_row_sums(agg, 0, (int)offset_blocks(n), lane, p0, p1, t0, t1);
+    // lane c: total(c) -- lane l holds the totals of columns 2 (l & 15) and 2 (l & 15) + 1; lanes PC_COLS + k: flag k
+    const int64_t other = __shfl(t1, lane >> 1), even = __shfl(t0, lane >> 1);
+    int64_t mine = (lane & 1) ? other : even;
+#pragma unroll
+    for (int k = 0; k < PF_COUNT; ++k) if (lane == PC_COLS + k) mine = flag[k];
+    if (lane < PC_COLS) { totals[lane] = mine; publish_total(totals, mirror, lane, mine, false); }
+    if (!mirror) return;
+    if (lane >= PC_COLS && lane < PC_COLS + PF_COUNT) mirror[lane] = mine;      // (the flags as loaded above, a lane each)
+    __threadfence_system();
+    if (lane == 0) reinterpret_cast<volatile int64_t *>(mirror)[PX_DONE] = gen;
+}
+
 template <bool FILL, bool STAGE, bool DENSE>
 __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
                                                  fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts,
-                                                 const int64_t *__restrict__ bases, int64_t *__restrict__ totals,
+                                                 const int64_t *__restrict__ bases, int64_t *__restrict__ totals, int64_t *__restrict__ agg,
+                                                 int64_t *__restrict__ agg_next, int64_t *__restrict__ mirror,
                                                  DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, const DevPlanTables &T)
 {
     __shared__ TileWaveLds<STAGE> lds_all[TW_WAVES];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int64_t field = (int64_t)blockIdx.x * TW_WAVES + wave;
+    // the fill pass of a speculative setup has one workgroup more, the first: it publishes the totals and zeroes the other buffer of aggregates
+    const int publisher = (FILL && !DENSE && tc.speculative) ? 1 : 0;
+    if (FILL && !DENSE && publisher && blockIdx.x == 0) { publish_two_level(n, tc.gen, totals, agg, agg_next, mirror, wave, lane); return; }
+    const int64_t field = ((int64_t)blockIdx.x - publisher) * TW_WAVES + wave;
     if (field >= n) return;
     TSTAMP(0);
     FSTAMP(0);
-    TilePass<FILL, STAGE, DENSE> p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, bases, totals, keep_tiles, keep_wtiles, T, lds_all[wave], field, lane };
+    TilePass<FILL, STAGE, DENSE> p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, bases, totals, agg, keep_tiles, keep_wtiles, T, lds_all[wave], field, lane };
     if (!p.header(info)) return;
     TSTAMP(1);
     FSTAMP(1);
@@ -1643,6 +1739,7 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
     FSTAMP(2);
     if (!FILL) {
         p.write_counts();
+        p.add_counts_to_aggregates();
         TSTAMP(38);
         return;
     }
@@ -1660,10 +1757,11 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
 template <bool FILL, bool STAGE, bool DENSE = false>
 __global__ __launch_bounds__(64 * TW_WAVES, 4) void k_tile_fields(int64_t n, DevTileConsts tc, DevConst cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
                                                               fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts,
-                                                              const int64_t *__restrict__ bases, int64_t *__restrict__ totals,
+                                                              const int64_t *__restrict__ bases, int64_t *__restrict__ totals, int64_t *__restrict__ agg,
+                                                              int64_t *__restrict__ agg_next, int64_t *__restrict__ mirror,
                                                               DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, DevPlanTables T)
 {
-    tile_fields_body<FILL, STAGE, DENSE>(n, tc, cst, ftmp, ptmp, info, counts, bases, totals, keep_tiles, keep_wtiles, T);
+    tile_fields_body<FILL, STAGE, DENSE>(n, tc, cst, ftmp, ptmp, info, counts, bases, totals, agg, agg_next, mirror, keep_tiles, keep_wtiles, T);
 }
 // (Measured and not kept: the fill pass of a large batch held to six wavefronts per SIMD -- 85 registers, 225 spilled, the primitives not staged:
 // cfg5 390 instead of 235 us.)
@@ -1693,15 +1791,20 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
     // pass: small batches ONE scan of one launch (k_scan_small), large ones the scan of the points (its apply kernel derives) and then the
     // scan of the other columns.  (Rounds 4-5a scanned the points of a large batch BEFORE its pass.)
     const bool one_scan = (n + 1023) / 1024 <= devplan_small_blocks();
+    // A speculative setup launches no scan at all: the planner adds the fields' points into the aggregates of their blocks, the pass takes its
+    // point offsets from them (so it writes the span columns itself, as a dense pass does) and adds its own columns; the fill pass goes on from there
+    const bool two_level = tc.speculative != 0;
+    if (two_level && (tc.dense || n > OFF_FIELDS_MAX || !s.agg)) return (int)hipErrorInvalidValue;
+    int64_t *const agg = two_level ? s.agg : nullptr;
     DevTileConsts tcc = tc;
-    tcc.no_bases = 1;
+    tcc.no_bases = two_level ? 0 : 1;
     auto plan = [&]() {
         if (plan_serial)
             hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               n_polys, check_obstacles, 0, tc.gen);
+                               agg, n_polys, check_obstacles, 0, tc.gen);
         else
             hipLaunchKernelGGL(k_plan_fields16, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               n_polys, check_obstacles, tc.gen);
+                               agg, n_polys, check_obstacles, tc.gen);
     };
     // (more fields than one round of wavefronts takes -- 4 per SIMD x 1024 SIMDs with the primitives staged in LDS: they are not staged, five
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
@@ -1709,13 +1812,13 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
         const unsigned grid = (unsigned)((n + TW_WAVES - 1) / TW_WAVES);
         if (tc.dense)
             hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
+                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
         else if (n <= 4096)
             hipLaunchKernelGGL((k_tile_fields<false, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
+                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
         else
             hipLaunchKernelGGL((k_tile_fields<false, false>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, DevPlanTables());
+                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
     };
     if (tc.dense) {
         // dense sampling: the chunks of every quiet run lie on 512-point boundaries of the batch arrays -- the pass needs the point offsets
@@ -1724,7 +1827,7 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
         if (rc0) return rc0;
         tcc.no_bases = 0;
         count();
-        rc0 = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, 0, tc.gen);
+        rc0 = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
         if (rc0) return rc0;
         const hipError_t e0 = hipGetLastError();
         return e0 == hipSuccess ? 0 : (int)e0;
@@ -1732,15 +1835,19 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
     plan();
     count();
     int rc = 0;
+    if (two_level) {
+        const hipError_t e2 = hipGetLastError();
+        return e2 == hipSuccess ? 0 : (int)e2;
+    }
     if (one_scan) {
-        rc = launch_scan(st, n, PC_POINTS, PC_COLS, s, totals_host, 1, 1, tc.fuse_spans, tc.speculative ? tc.gen : 0, tc.gen);
+        rc = launch_scan(st, n, PC_POINTS, PC_COLS, s, totals_host, 1, 1, tc.fuse_spans, tc.gen);
         if (rc) return rc;
         const hipError_t e1 = hipGetLastError();
         return e1 == hipSuccess ? 0 : (int)e1;
     }
     rc = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0, 1, tc.fuse_spans);
     if (rc) return rc;
-    rc = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, 0, tc.gen);
+    rc = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
     if (rc) return rc;
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
@@ -1765,23 +1872,31 @@ int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                       (int64_t)0, 0, 1, (int64_t)0);
+                       (int64_t *)nullptr, (int64_t)0, 0, 1, (int64_t)0);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
-int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &tables)
+int launch_devplan_rescan(hipStream_t st, int64_t n, const DevPlanScratch &s)
 {
     if (n <= 0) return 0;
+    return launch_scan(st, n, PC_POINTS, PC_COLS, s, nullptr, 0);
+}
+
+int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &tables, int64_t *totals_host)
+{
+    if (n <= 0) return 0;
+    const bool two_level = tc.speculative != 0;
+    if (two_level && (tc.dense || n > OFF_FIELDS_MAX || !s.agg || !s.agg_next)) return (int)hipErrorInvalidValue;
 #define X(name) tables.name,
     const DevPlanTables t = { FCPP_FILL_TABLES(X) };
 #undef X
     if (tc.dense)
         hipLaunchKernelGGL((k_tile_fields<true, true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
-                           s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, t);
-    else
-        hipLaunchKernelGGL((k_tile_fields<true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
-                           s.info, s.counts, s.bases, s.totals, s.keep_tiles, s.keep_wtiles, t);
+                           s.info, s.counts, s.bases, s.totals, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, t);
+    else      // (speculative: one workgroup more, the publisher -- tile_fields_body)
+        hipLaunchKernelGGL((k_tile_fields<true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES) + (two_level ? 1u : 0u)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
+                           s.info, s.counts, s.bases, s.totals, two_level ? s.agg : nullptr, two_level ? s.agg_next : nullptr, two_level ? totals_host : nullptr, s.keep_tiles, s.keep_wtiles, t);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

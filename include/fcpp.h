@@ -910,6 +910,10 @@ int fcpp_gather(fcpp_ctx *ctx, void *nccl_comm, int rank, int world, int root, i
  * device pointers and synchronises. */
 int fcpp_debug_math(int fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
 int fcpp_debug_math_dev(fcpp_ctx *ctx, int fn, int64_t n, const double *a_dev, const double *b_dev, double *out0_dev, double *out1_dev);
+/* The device setup's rule for a field's table offsets without a scan (csrc/fcpp_offsetfn.h: the exclusive prefix of a count column from the
+ * per-block aggregates and the counts of the field's own block), its HOST version on host pointers: counts[col * n + i], n_cols columns of
+ * n <= 8192 fields -> prefix[col * n + i] and totals[col].  What the kernels' offsets are checked against; a diagnostic, not a fallback. */
+int fcpp_debug_offsets(int64_t n, int n_cols, const int64_t *counts, int64_t *prefix, int64_t *totals);
 /* fcpp_dubins_solve's function (csrc/fcpp_dubinsfn.h) evaluated on the HOST, on host pointers: what the device results are compared with
  * bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
 int fcpp_debug_dubins(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,
