@@ -17,6 +17,7 @@ RING_AS_VERTICES, RING_REVERSED = 0, 1
 KIND_MASK, FLAG_HEADLAND, FLAG_ALAT, FLAG_OUTSIDE, FLAG_OBSTACLE, INDEX_SHIFT = 7, 8, 16, 32, 64, 8
 OUTPUT_PITCH = 24 << 30          # FCPP_OUTPUT_PITCH (include/fcpp.h)
 ROUTE_MAX_SWATHS = 512           # FCPP_ROUTE_MAX_SWATHS
+CLEAR_EDGE_CHUNK = 256           # FCPP_CLEAR_EDGE_CHUNK
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -174,6 +175,10 @@ PROTOTYPES = [
      + [_VP] * 4),
     ('fcpp_route_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
     ('fcpp_route_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
+    ('fcpp_conn_clear', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
+     + [_VP] * 6),
+    ('fcpp_route_transit_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP, C.c_int64,
+                                          _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
     ('fcpp_field_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 12),
     ('fcpp_field_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 7
      + [C.c_int64] + [_VP] * 7),
@@ -198,6 +203,10 @@ PROTOTYPES = [
      + [C.c_int64, C.c_int64] + [_VP] * 4),
     ('fcpp_debug_route_transit', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP]),
     ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
+    ('fcpp_debug_conn_clear', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
+     + [_VP] * 6),
+    ('fcpp_debug_route_transit_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP,
+                                                C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
     ('fcpp_debug_field_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 14 + [C.c_int64]
      + [_VP] * 7),
     ('fcpp_debug_headland_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]

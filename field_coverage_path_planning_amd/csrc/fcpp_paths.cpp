@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset, the swath router, the field paths, the headland paths and the polygon coverage.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router, the connector clearance, the field paths, the headland paths and the polygon coverage.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -9,6 +9,8 @@
 #include <new>
 
 #include "fcpp_api_internal.h"
+#include "fcpp_clear.h"
+#include "fcpp_clearfn.h"
 #include "fcpp_conn.h"
 #include "fcpp_fpath.h"
 #include "fcpp_fpathfn.h"
@@ -359,6 +361,36 @@ int route_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_dev, const int64_t
     for (int64_t i = 0; i < n; ++i)
         if (toff[(size_t)i + 1] - toff[(size_t)i] != route_block(soff[(size_t)i + 1] - soff[(size_t)i]))
             return fail(FCPP_ESIZE, "t_offsets do not match the swath counts: block i holds (2 m_i)^2 entries, none for m_i > 512");
+    return FCPP_OK;
+}
+
+// ---- connector clearance: what fcpp_conn_clear / fcpp_route_transit_clear and their host twins check alike -----------------------------------
+int clear_conn_args(int mode, int64_t n, const double *fx, const double *fy, const double *fh, double radius, const int32_t *word, const double *seg,
+                    const int64_t *pair_field, int64_t n_fields, const void *ring_offsets, int64_t n_rings, const void *vert_offsets,
+                    int64_t n_verts, const double *x, const double *y)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y)) || (n > 0 && (!fx || !fy || !fh || !word || !seg || !pair_field)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    if (n < 0 || n_fields < 0 || n_rings < 0 || n_verts < 0 || n_fields > INT32_MAX || (n + CLEAR_TILE - 1) / CLEAR_TILE > CLEAR_MAX_GROUPS)
+        return fail(FCPP_ESIZE, "bad sizes");
+    return FCPP_OK;
+}
+
+int clear_penalty(double penalty)
+{
+    if (!(penalty >= 0.0) || !isfinite(penalty)) return fail(FCPP_EINVAL, "penalty must be non-negative and finite");
+    return FCPP_OK;
+}
+
+// the workgroups of k_clear_transit: CLEAR_TILE entries of one field's block each
+int clear_tiles(int64_t n, const std::vector<int64_t> &toff, std::vector<int64_t> &tile_off)
+{
+    try { tile_off.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t i = 0; i < n; ++i)
+        tile_off[(size_t)i + 1] = tile_off[(size_t)i] + (toff[(size_t)i + 1] - toff[(size_t)i] + CLEAR_TILE - 1) / CLEAR_TILE;
+    if (tile_off[(size_t)n] > CLEAR_MAX_GROUPS) return fail(FCPP_ESIZE, "2^39 transit entries or more");
     return FCPP_OK;
 }
 
@@ -995,6 +1027,117 @@ int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, c
         if (sweeps) sweeps[i] = f.sweeps;
         if (status) status[i] = f.status;
         if (stored) stored[i] = f.stored;
+    });
+    return FCPP_OK;
+}
+
+// ---- connector clearance (fcpp_clear.hip; the rule: fcpp_clearfn.h) -------------------------------------------------------------------
+int fcpp_conn_clear(fcpp_ctx *c, int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, double radius,
+                    const int32_t *word, const double *seg, const int64_t *pair_field, int64_t n_fields, const int64_t *ring_offsets,
+                    int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y, int32_t *crossings,
+                    int8_t *inside, double *first_s, int32_t *field_status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    int rc = clear_conn_args(mode, n, from_x, from_y, from_h, radius, word, seg, pair_field, n_fields, ring_offsets, n_rings, vert_offsets, n_verts, x, y);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n_fields, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    LAUNCHCHK(launch_clear_field_status(c->stream, F, field_status));
+    LAUNCHCHK(launch_clear_conn(c->stream, mode, n, from_x, from_y, from_h, radius, word, seg, pair_field, F, crossings, inside, first_s));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_route_transit_clear(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                             const double *ax, const double *ay, const double *bx, const double *by, const double *angle, double radius, int mode,
+                             const int64_t *t_offsets, const int64_t *t_offsets_host, int64_t t_total, const int64_t *ring_offsets,
+                             int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y, double penalty,
+                             double *T, uint8_t *B)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!swath_offsets || !t_offsets || !ring_offsets || !vert_offsets || (n_total > 0 && (!ax || !ay || !bx || !by)) || (n > 0 && !angle) ||
+        (t_total > 0 && (!T || !B)) || (n_verts > 0 && (!x || !y)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_radius(radius, mode);
+    if (rc == FCPP_OK) rc = clear_penalty(penalty);
+    if (rc == FCPP_OK && (n_rings < 0 || n_verts < 0)) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, toff, rings, verts, tile_off;
+    rc = route_offsets(c, n, swath_offsets, swath_offsets_host, n_total, t_offsets, t_offsets_host, t_total, soff, toff);
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = clear_tiles(n, toff, tile_off);
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle, nullptr);
+    if (rc) return rc;
+    DevBuf<int64_t> tiles;
+    HIPCHK(tiles.alloc((size_t)n + 1));
+    HIPCHK(hipMemcpyAsync(tiles.p, tile_off.data(), tile_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    const ClearFields F = { n, ring_offsets, vert_offsets, x, y };
+    LAUNCHCHK(launch_clear_transit(c->stream, n, swath_offsets, ax, ay, bx, by, angle, radius, mode, t_offsets, tiles.p, tile_off[(size_t)n], F, penalty,
+                                   T, B));
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the tile offsets die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_conn_clear(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, double radius, const int32_t *word,
+                          const double *seg, const int64_t *pair_field, int64_t n_fields, const int64_t *ring_offsets, int64_t n_rings,
+                          const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y, int32_t *crossings, int8_t *inside,
+                          double *first_s, int32_t *field_status)
+{
+    int rc = clear_conn_args(mode, n, from_x, from_y, from_h, radius, word, seg, pair_field, n_fields, ring_offsets, n_rings, vert_offsets, n_verts, x, y);
+    if (rc) return rc;
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(nullptr, n_fields, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc) return rc;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    if (field_status) WorkerPool::parallel_for(n_fields, [&](int64_t f) { field_status[f] = clear_field_status(F, f); });
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const ClearResult r = mode == 0 ? clear_path<0>(F, pair_field[i], from_x[i], from_y[i], from_h[i], radius, word[i], seg + 3 * i)
+                                        : clear_path<1>(F, pair_field[i], from_x[i], from_y[i], from_h[i], radius, word[i], seg + 5 * i);
+        if (crossings) crossings[i] = r.crossings;
+        if (inside) inside[i] = r.inside;
+        if (first_s) first_s[i] = r.first_s;
+    });
+    return FCPP_OK;
+}
+
+int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                   const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
+                                   const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                   const double *y, double penalty, double *T, uint8_t *B)
+{
+    if (!swath_offsets || !t_offsets || !ring_offsets || !vert_offsets || (n_total > 0 && (!ax || !ay || !bx || !by)) || (n > 0 && !angle) ||
+        (t_total > 0 && (!T || !B)) || (n_verts > 0 && (!x || !y)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_radius(radius, mode);
+    if (rc == FCPP_OK) rc = clear_penalty(penalty);
+    if (rc == FCPP_OK && (n_rings < 0 || n_verts < 0)) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> soff, toff, rings, verts;
+    rc = route_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, t_offsets, t_total, soff, toff);
+    if (rc == FCPP_OK) rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(nullptr, n, nullptr, angle);
+    if (rc) return rc;
+    const ClearFields F = { n, ring_offsets, vert_offsets, x, y };
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t s0 = soff[(size_t)i];
+        const int N = (int)(toff[(size_t)i + 1] == toff[(size_t)i] ? 0 : 2 * (soff[(size_t)i + 1] - s0));
+        double *Tb = T + toff[(size_t)i];
+        uint8_t *Bb = B + toff[(size_t)i];
+        for (int p = 0; p < N; ++p)
+            for (int q = 0; q < N; ++q) {
+                if (!route_canonical(p, q, N)) continue;
+                const int e = p * N + q, e2 = (q ^ 1) * N + (p ^ 1);
+                bool blocked = false;
+                if ((p >> 1) != (q >> 1))
+                    blocked = mode == 0 ? clear_transit_blocked<0>(F, i, ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, p, q)
+                                        : clear_transit_blocked<1>(F, i, ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, p, q);
+                Bb[e] = Bb[e2] = blocked ? 1 : 0;
+                if (blocked) { const double v = Tb[e] + penalty; Tb[e] = v; Tb[e2] = v; }
+            }
     });
     return FCPP_OK;
 }

@@ -1376,8 +1376,9 @@ def swath_route(swathset, i, radius, spacing, reversing=False, device=None, orde
     0.5), so the route passes speed_plan's curvature clamp untouched; at a cusp of a reversing connector the chord formula sees a turn on
     the spot, as on every Reeds-Shepp path.  -> (x, y, heading, part) device tensors; part (int8) is 0 on a swath and 1 on a connector.
     The stored order is NOT optimised, whatever the shape of the field: route_swaths chooses an order and directions (pass it the same
-    `spacing`, so that it prices the connectors driven here).  A connector is the shortest path between two poses and knows no boundary: it may leave the field or cross a hole;
-    validate() (fcpp_validate) flags that, as for every connector of this library."""
+    `spacing`, so that it prices the connectors driven here).  A connector is the shortest path between two poses and knows no boundary
+    unless `clear_of` is given to route_swaths: it may leave the field or cross a hole; validate() (fcpp_validate) flags that, as for every
+    connector of this library, and connector_clearance tests it exactly."""
     torch = _torch()
     (f_s, f_e), (r_s, r_e) = swathset.poses(i)
     m = int(f_s.shape[0])
@@ -1439,6 +1440,10 @@ class SwathRoute:
     status: object              # (n) int32: 0, FCPP_EUNSUPPORTED (more than 512 swaths) or FCPP_EINVAL (a non-finite cost): the stored order
     tours: object               # (starts, m) int32: every candidate's final tour
     costs: object               # (n, starts) float64: and its cost
+    blocked: object = None      # with clear_of: (n) int32, the connectors of `order` AS DRIVEN that are not clear, entry and exit included
+    blocked_stored: object = None       # with clear_of: the same for the stored boustrophedon order
+    length: object = None       # with clear_of: (n) float64, the summed connector lengths of `order` without any penalty [m]
+    clearance: object = None    # with clear_of: the FieldPathClearance behind `blocked` and `length`: every connector of `order`, leg by leg
 
     def field(self, i):
         return self.order[int(self.offsets_host[i]):int(self.offsets_host[i + 1])]
@@ -1483,18 +1488,61 @@ def _route_chunks(soff_h, budget):
     return out
 
 
-def swath_transit(swathset, radius, reversing=False, device=None):
+def _fields_slice(pf, ro_h, vo_h, lo, hi):
+    """fields lo .. hi of a PolygonFields as one of their own (ro_h, vo_h: host copies of its two offset arrays)"""
+    if lo == 0 and hi == pf.n:
+        return pf
+    r0, r1 = int(ro_h[lo]), int(ro_h[hi])
+    v0, v1 = int(vo_h[r0]), int(vo_h[r1])
+    return PolygonFields((pf.ring_offsets[lo:hi + 1] - r0).contiguous(), (pf.vert_offsets[r0:r1 + 1] - v0).contiguous(), pf.x[v0:v1].contiguous(),
+                         pf.y[v0:v1].contiguous())
+
+
+def _route_transit_clear(ctx, ss, lo, hi, radius, reversing, pf, penalty, T, toff, toff_h, soff, soff_h):
+    """fcpp_route_transit_clear on the chunk _route_transit made: T in / out -> B (uint8, T's layout); pf: the chunk's own fields"""
+    torch = _torch()
+    dev = ss.a.device
+    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
+    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+    ang = ss.angle[lo:hi].contiguous()
+    B = torch.empty(int(toff_h[-1]), dtype=torch.uint8, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_route_transit_clear(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by),
+                                             _ptr(ang), float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]),
+                                             *pf._head()[1:], float(penalty), _ptr(T), _ptr(B)))
+    return B
+
+
+def _clear_fields(clear_of, n, device):
+    pf = polygon_fields(clear_of, device)
+    if pf.n != n:
+        raise ValueError('clear_of must hold one field per field of the SwathSet')
+    return pf
+
+
+def swath_transit(swathset, radius, reversing=False, device=None, clear_of=None, blocked_penalty=1.0e6):
     """The transit blocks of every field of a SwathSet (fcpp_route_transit) -> (T, offsets): T a flat float64 device tensor, field i's block
     T[offsets[i] : offsets[i + 1]].reshape(2 m_i, 2 m_i) (offsets: numpy int64), entry [p][q] the shortest Dubins -- Reeds-Shepp if
     `reversing` -- length from the end of oriented swath p to the start of oriented swath q (p = 2 s + d: swath s from a to b for d = 0, from
-    b to a for d = 1), +inf within one swath; [p][q] and [q ^ 1][p ^ 1] hold equal bits.  A field of more than 512 swaths has no block."""
+    b to a for d = 1), +inf within one swath; [p][q] and [q ^ 1][p ^ 1] hold equal bits.  A field of more than 512 swaths has no block.
+    clear_of (one field per field of the SwathSet, as polygon_fields takes them): every connector is also tested against its field
+    (fcpp_route_transit_clear; the rule: include/fcpp.h) -> (T, offsets, B): B uint8 with T's layout, 1 where the connector is not clear,
+    and there T holds length + blocked_penalty.  The default penalty of 1e6 m is a condition, not a measurement: it lies beyond any
+    route's transit total (512 swaths at field-diameter transits stay far below it), so one blocked connector outweighs every order
+    without one; and it is small enough that a delta of three penalised entries (3e6, ulp 4.7e-10) still resolves the router's min_gain
+    of 1e-9 m in double.  blocked_penalty = 0 reports B and leaves T as it is."""
     ctx = get_context(device)
-    T, _, toff_h, _, _, _ = _route_transit(ctx, swathset, 0, len(swathset.offsets_host) - 1, radius, reversing)
-    return T, toff_h
+    n = len(swathset.offsets_host) - 1
+    T, toff, toff_h, soff, soff_h, _ = _route_transit(ctx, swathset, 0, n, radius, reversing)
+    if clear_of is None:
+        return T, toff_h
+    pf = _clear_fields(clear_of, n, device)
+    B = _route_transit_clear(ctx, swathset, 0, n, radius, reversing, pf, blocked_penalty, T, toff, toff_h, soff, soff_h)
+    return T, toff_h, B
 
 
-def _route_ends(ss, pose, at_entry, radius, reversing, device):
-    """E (at_entry) or X of route_swaths: the connector length between each field's pose and every oriented swath's start / from its end"""
+def _route_end_pairs(ss, pose, at_entry):
+    """the pairs behind E (at_entry) or X of route_swaths: each field's pose and every oriented swath's start / end -> (from, to), (2 m, 3)"""
     torch = _torch()
     dev = ss.a.device
     pose = _dev_f64(pose, dev).reshape(-1, 3)
@@ -1506,11 +1554,24 @@ def _route_ends(ss, pose, at_entry, radius, reversing, device):
     first, second = (ss.a, ss.b) if at_entry else (ss.b, ss.a)
     own = torch.stack([torch.cat([first, th], dim=1), torch.cat([second, th + np.pi], dim=1)], dim=1).reshape(-1, 3)
     far = torch.repeat_interleave(pose, 2 * counts, dim=0)
-    frm, to = (far, own) if at_entry else (own, far)
-    return _conn_solve_poses(frm, to, radius, reversing, device)[2].contiguous()
+    return (far, own) if at_entry else (own, far)
 
 
-def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, starts=8, min_gain=1e-9, max_sweeps=None, spacing=None, device=None):
+def _route_ends(ss, pose, at_entry, radius, reversing, device, clear_of=None, penalty=0.0):
+    """E (at_entry) or X of route_swaths: the connector length between each field's pose and every oriented swath's start / from its end;
+    clear_of (PolygonFields): + penalty where that connector is not clear of its field"""
+    torch = _torch()
+    frm, to = _route_end_pairs(ss, pose, at_entry)
+    if clear_of is None:
+        return _conn_solve_poses(frm, to, radius, reversing, device)[2].contiguous()
+    counts = torch.as_tensor(np.diff(ss.offsets_host), device=ss.a.device)
+    pair_field = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64, device=ss.a.device), 2 * counts)
+    c = _connector_clearance(frm, to, clear_of, pair_field, radius, reversing, device)
+    return torch.where(c.clear, c.length, c.length + float(penalty)).contiguous()
+
+
+def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, starts=8, min_gain=1e-9, max_sweeps=None, spacing=None, device=None,
+                 clear_of=None, blocked_penalty=1.0e6):
     """Order and direction of every field's swaths (fcpp_route_transit + fcpp_route_solve; the rule: include/fcpp.h) -> SwathRoute.
     The cost of a tour is the summed length of its connectors -- shortest Dubins paths at the turning radius `radius`, Reeds-Shepp if
     `reversing` -- plus, with entry / exit (one pose (x, y, heading) per field, or None), the connector from the field's entry pose to
@@ -1518,8 +1579,16 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     nearest-neighbour tours from spread starts) are each improved by segment reversals and or-opt moves until none gains more than
     min_gain [m] (or max_sweeps moves: None = 8 x the largest swath count + 8); the cheapest wins.  spacing: plan at the radius swath_route
     drives its connectors with at that sample spacing (_chord_radius), so `cost` is the length swath_route(order=...) drives.  Connectors
-    know no boundary (validate() flags what leaves the field).  Fields are solved in chunks of at most ROUTE_T_BUDGET bytes of transit
-    blocks.  A field of more than 512 swaths keeps its stored order (status FCPP_EUNSUPPORTED)."""
+    know no boundary (validate() flags what leaves the field) unless `clear_of` is given.  Fields are solved in chunks of at most
+    ROUTE_T_BUDGET bytes of transit blocks.  A field of more than 512 swaths keeps its stored order (status FCPP_EUNSUPPORTED).
+    clear_of (one field per field of the SwathSet, as polygon_fields takes them -- the surveyed boundary with its ponds, say, while the
+    swaths lie in its inset): every transit, entry and exit connector that is not clear of its field (fcpp_route_transit_clear,
+    fcpp_conn_clear; the rule: include/fcpp.h) is priced at length + blocked_penalty (swath_transit explains the default), so the order
+    avoids blocked connectors where another order can; no connector is re-shaped.  `cost` stays what the solver returned, penalties
+    included; SwathRoute.length is the order's summed connector length without them, SwathRoute.blocked / blocked_stored count the
+    connectors of the order / of the stored boustrophedon that are still not clear (field_path_clearance says which).  They are counted
+    on the connectors AS DRIVEN: a block entry holds its canonical pair's connector, and where two words tie in length the connector
+    driven for the mirrored entry may be the other one."""
     ctx = get_context(device)
     torch = _torch()
     ss = swathset
@@ -1531,8 +1600,12 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     if max_sweeps is None:
         fit = m_all[m_all <= L.ROUTE_MAX_SWATHS]
         max_sweeps = min(8 * int(fit.max() if fit.size else 0) + 8, 1 << 20)
-    E_all = _route_ends(ss, entry, True, R, reversing, device) if entry is not None else None
-    X_all = _route_ends(ss, exit, False, R, reversing, device) if exit is not None else None
+    pf = ro_h = vo_h = None
+    if clear_of is not None:
+        pf = _clear_fields(clear_of, n, device)
+        ro_h, vo_h = pf.ring_offsets.cpu().numpy(), pf.vert_offsets.cpu().numpy()
+    E_all = _route_ends(ss, entry, True, R, reversing, device, pf, blocked_penalty) if entry is not None else None
+    X_all = _route_ends(ss, exit, False, R, reversing, device, pf, blocked_penalty) if exit is not None else None
     order = torch.empty(int(soff_all[-1]), dtype=torch.int32, device=dev)
     tours = torch.empty((max(S, 0), int(soff_all[-1])), dtype=torch.int32, device=dev)
     costs = torch.empty((n, max(S, 0)), dtype=torch.float64, device=dev)
@@ -1540,6 +1613,8 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     winner, sweeps, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     for lo, hi in _route_chunks(soff_all, ROUTE_T_BUDGET):
         T, toff, toff_h, soff, soff_h, m = _route_transit(ctx, ss, lo, hi, R, reversing)
+        if pf is not None:
+            _route_transit_clear(ctx, ss, lo, hi, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi), blocked_penalty, T, toff, toff_h, soff, soff_h)
         s0 = int(soff_all[lo])
         Ec = E_all[2 * s0:2 * (s0 + m)] if E_all is not None else None
         Xc = X_all[2 * s0:2 * (s0 + m)] if X_all is not None else None
@@ -1548,7 +1623,127 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
                                          _ptr(Ec), _ptr(Xc), S, float(min_gain), int(max_sweeps), _ptr(tr), _ptr(costs[lo:hi]), _ptr(order[s0:s0 + m]),
                                          _ptr(cost[lo:hi]), _ptr(winner[lo:hi]), _ptr(sweeps[lo:hi]), _ptr(status[lo:hi]), _ptr(stored[lo:hi])))
         tours[:, s0:s0 + m] = tr
-    return SwathRoute(soff_all, order, cost, stored, winner, sweeps, status, tours, costs)
+    route = SwathRoute(soff_all, order, cost, stored, winner, sweeps, status, tours, costs)
+    if pf is not None:
+        driven = _legs_clearance(ss, pf, R, reversing, order, entry, exit, device)
+        route.blocked, route.length, route.clearance = driven.blocked, driven.length, driven
+        route.blocked_stored = _legs_clearance(ss, pf, R, reversing, None, entry, exit, device).blocked
+    return route
+
+
+# ---- connector clearance (fcpp_conn_clear / fcpp_route_transit_clear; the rule: include/fcpp.h) ------------------------------------------
+@dataclass
+class ConnectorClearance:
+    """connector_clearance(): solved connectors against the rings of their fields, one entry per pair"""
+    clear: object               # (n) bool: inside and crossings == 0
+    crossings: object           # (n) int32: the points where the connector crosses an edge of its field
+    inside: object              # (n) int8: even-odd membership of the connector's start point
+    first_s: object             # (n) float64: the arc length to the first crossing [m]; +inf without one, NaN for an unsolved pair or a bad field
+    length: object              # (n) float64: the connector's length [m]
+    field_status: object        # (n_fields) int32: 0, or FCPP_EINVAL (no ring, a ring of fewer than 3 vertices, a non-finite vertex)
+
+
+def _connector_clearance(frm, to, pf, pair_field, radius, reversing, device):
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    f, t = _poses(frm, dev), _poses(to, dev)
+    word, seg, length = _conn_solve(ctx, f, t, radius, reversing)
+    n = int(word.numel())
+    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
+    if pair_field.numel() == 1 and n != 1:
+        pair_field = pair_field.expand(n)
+    if pair_field.numel() != n:
+        raise ValueError('pair_field must be a scalar or hold one field index per pair')
+    pair_field = pair_field.contiguous()
+    crossings = torch.empty(n, dtype=torch.int32, device=dev)
+    inside = torch.empty(n, dtype=torch.int8, device=dev)
+    first_s = torch.empty(n, dtype=torch.float64, device=dev)
+    status = torch.empty(pf.n, dtype=torch.int32, device=dev)
+    L.check(ctx.lib.fcpp_conn_clear(ctx.handle, 1 if reversing else 0, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg),
+                                    _ptr(pair_field), *pf._head(), _ptr(crossings), _ptr(inside), _ptr(first_s), _ptr(status)))
+    return ConnectorClearance((inside == 1) & (crossings == 0), crossings, inside, first_s, length, status)
+
+
+def connector_clearance(from_poses, to_poses, fields, pair_field, radius, reversing=False, device=None):
+    """Solve, then test (fcpp_dubins_solve / fcpp_rs_solve + fcpp_conn_clear; the rule: include/fcpp.h): is the shortest Dubins --
+    Reeds-Shepp if `reversing` -- connector of every pair from_poses[i] -> to_poses[i] clear of field pair_field[i] of `fields` (what
+    polygon_fields takes: rings, even-odd interior)?  The test is exact, piece against edge, not by samples.  pair_field: one index per
+    pair (or one for all); -1 means no region: clear.  A margin is no parameter: pass polygon_inset(fields, [margin]).as_fields(0).
+    Nothing is re-shaped.  -> ConnectorClearance."""
+    return _connector_clearance(from_poses, to_poses, polygon_fields(fields, device), pair_field, radius, reversing, device)
+
+
+@dataclass
+class FieldPathClearance:
+    """field_path_clearance(): the connector legs of every field's path against its field.  One entry per connector leg that exists,
+    ordered by field, then by slot."""
+    field: object               # (L) int64: the leg's field
+    slot: object                # (L) int32: its leg slot within the field, FieldPaths.leg's numbering: 0 entry, 2 k + 2 behind the k-th swath driven
+    clear: object               # (L) bool
+    crossings: object           # (L) int32
+    first_s: object             # (L) float64: arc length along the leg to its first crossing [m]
+    leg_length: object          # (L) float64: the leg's length [m]
+    blocked: object             # (n) int32: the legs of the field that are not clear
+    length: object              # (n) float64: the field's summed connector length [m]
+    field_status: object        # (n) int32: fcpp_conn_clear's status of the field tested against
+
+
+def _legs_clearance(ss, pf, R, reversing, order, entry, exit, device):
+    """the connector legs of the fields' driving orders, built on the device as field_paths forms them, solved at R and tested"""
+    torch = _torch()
+    dev = ss.a.device
+    soff_h = np.ascontiguousarray(ss.offsets_host, dtype=np.int64)
+    n, m = len(soff_h) - 1, int(soff_h[-1])
+    counts = torch.as_tensor(np.diff(soff_h), device=dev)
+    fld = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)         # the field of every driven position
+    k = torch.arange(m, dtype=torch.int64, device=dev) - ss.offsets[fld]                          # and its rank in the order
+    if order is None:
+        o = 2 * k + (k & 1)
+    else:
+        order = order.order if isinstance(order, SwathRoute) else order
+        o = torch.as_tensor(order, device=dev).to(torch.int64).reshape(-1)
+        if int(o.numel()) != m:
+            raise ValueError('order must hold one oriented swath per swath of the SwathSet')
+        if m and bool(((o < 0) | (o >= 2 * counts[fld])).any()):
+            raise ValueError('order must hold oriented swaths 2 s + d local to their field')
+        if m and bool((torch.bincount(ss.offsets[fld] + (o >> 1), minlength=m) != 1).any()):
+            raise ValueError('order must hold every swath of a field exactly once (field_paths gives such a field FCPP_EINVAL and no samples)')
+    sw, d = ss.offsets[fld] + (o >> 1), (o & 1).to(torch.bool).unsqueeze(1)
+    th = ss.angle[fld].unsqueeze(1)
+    h = torch.where(d, th + np.pi, th)
+    ent = torch.cat([torch.where(d, ss.b[sw], ss.a[sw]), h], dim=1)                               # where the oriented swath is entered / left
+    ext = torch.cat([torch.where(d, ss.a[sw], ss.b[sw]), h], dim=1)
+    inner = k + 1 < counts[fld]
+    frm, to, lf, slot = [ext[inner]], [ent[1:][inner[:-1]]], [fld[inner]], [2 * k[inner] + 2]
+    has = torch.nonzero(counts > 0).reshape(-1)
+    first, last = ss.offsets[has], ss.offsets[has + 1] - 1
+    if entry is not None:
+        p = torch.stack(_pose_columns(entry, n, dev), dim=1)
+        frm.append(p[has]); to.append(ent[first]); lf.append(has); slot.append(torch.zeros_like(has))
+    if exit is not None:
+        p = torch.stack(_pose_columns(exit, n, dev), dim=1)
+        frm.append(ext[last]); to.append(p[has]); lf.append(has); slot.append(2 * counts[has])
+    frm, to, lf, slot = torch.cat(frm), torch.cat(to), torch.cat(lf), torch.cat(slot)
+    by_slot = torch.argsort(2 * ss.offsets[lf] + lf + slot)                                       # a field's first slot is 2 soff + i
+    frm, to, lf, slot = frm[by_slot].contiguous(), to[by_slot].contiguous(), lf[by_slot], slot[by_slot]
+    c = _connector_clearance(frm, to, pf, lf, R, reversing, device)
+    blocked = torch.zeros(n, dtype=torch.int32, device=dev)
+    blocked.index_add_(0, lf, (~c.clear).to(torch.int32))
+    # a field's lengths summed in slot order, one segment per field (an atomic float sum has no fixed order)
+    length = torch.segment_reduce(c.length, 'sum', lengths=torch.bincount(lf, minlength=n), initial=0.0)
+    return FieldPathClearance(lf, slot.to(torch.int32), c.clear, c.crossings, c.first_s, c.length, blocked, length, c.field_status)
+
+
+def field_path_clearance(swathset, fields, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None):
+    """The connector legs field_paths drives -- same order, entry / exit, and _chord_radius(radius, spacing) -- tested against `fields`
+    (one per field of the SwathSet, as polygon_fields takes them): the legs' poses are formed on the device, solved and passed to
+    fcpp_conn_clear.  -> FieldPathClearance: per connector leg clear / crossings / first_s under FieldPaths.leg's slot numbering, and the
+    blocked legs per field (what route_swaths(clear_of=...) reports as SwathRoute.blocked / .clearance for the same arguments).  The swath
+    legs are not tested: they lie in the work area they were cut from.  An order that is no permutation of a field's swaths raises
+    ValueError here (field_paths gives that field FCPP_EINVAL and no samples)."""
+    n = len(swathset.offsets_host) - 1
+    return _legs_clearance(swathset, _clear_fields(fields, n, device), _chord_radius(radius, spacing), reversing, order, entry, exit, device)
 
 
 # ---- field paths (fcpp_field_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------------
@@ -1595,7 +1790,8 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     SwathRoute of the same SwathSet (route_swaths: pass it the same `spacing`) or an int array of m_total oriented swaths, each field's
     local to it.  entry / exit: one pose (x, y, heading) per field, as route_swaths takes them: the connectors it priced are driven (part 2
     and 3).  A field whose order is no permutation of its swaths, or with a non-finite length or pose, has status FCPP_EINVAL and no samples;
-    the others are unaffected.  Connectors know no boundary (validate() flags what leaves the field)."""
+    the others are unaffected.  Connectors know no boundary (validate() flags what leaves the field) unless `clear_of` is given to
+    route_swaths; field_path_clearance tests the connectors driven here."""
     ctx = get_context(device)
     torch = _torch()
     ss = swathset
@@ -1856,10 +2052,11 @@ class PolygonPlan:
     paths: object               # FieldPaths
     headland_paths: object = None       # HeadlandPaths of `headland` when asked for (headland_paths=True), else None
     coverage: object = None             # PolygonCoverage of `fields` under paths (and headland_paths) when asked for (coverage_resolution), else None
+    clearance: object = None            # FieldPathClearance of `paths` against clear_of when given, else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
-                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None):
+                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -1867,7 +2064,10 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     same radius, spacing and `reversing`: one closed loop per ring, PolygonPlan.headland_paths).  The loops are not joined to each other or
     to the field paths' entries: the connector operators do that from the loops' first poses.  coverage_resolution [m]: also report what the
     plan covers of the ORIGINAL fields (polygon_coverage at that cell size over the field paths, and the headland loops if they were driven:
-    PolygonPlan.coverage); nothing else in the chain changes."""
+    PolygonPlan.coverage); nothing else in the chain changes.  clear_of: None leaves the plan as it is; 'boundary' routes the swaths so
+    that the connectors stay clear of the surveyed `fields` (holes are ponds) where an order allows it, and reports what stays blocked
+    (route_swaths(clear_of=...): PolygonPlan.clearance is its SwathRoute.clearance, what field_path_clearance gives for the path); a PolygonFields, or anything polygon_fields takes, is used
+    as given.  No connector is re-shaped, and the headland loops' corner connectors are not tested."""
     torch = _torch()
     fields = polygon_fields(fields, device)
     lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
@@ -1876,13 +2076,15 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     # (a field without a valid angle is cut at angles[0]: its status there is non-zero, as at every angle)
     chosen = ang[idx.clamp(min=0)] if ang.numel() else torch.zeros(work.n, dtype=torch.float64, device=work.x.device)
     ss = polygon_swaths(work, chosen, width, device=device)
-    route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device)
+    region = None if clear_of is None else (fields if isinstance(clear_of, str) and clear_of == 'boundary' else polygon_fields(clear_of, device))
+    route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device, clear_of=region)
     paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device)
+    clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
     cov = None
     if coverage_resolution is not None:
         cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device)
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov)
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr)
 
 
 def _polys(polygons):

@@ -651,6 +651,67 @@ int fcpp_route_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev,
                      const double *X_dev, int n_starts, double min_gain, int max_sweeps, int32_t *tours_dev, double *costs_dev,
                      int32_t *route_dev, double *cost_dev, int32_t *winner_dev, int32_t *sweeps_dev, int32_t *status_dev, double *stored_dev);
 
+/* ---- connector clearance: solved connectors against the rings of a field ---------------------------------------------------------------------
+ * Build-defined (the reference's connectors are straight lines that nothing tests).  Every connector of this library is the shortest Dubins or
+ * Reeds-Shepp path between two poses and knows no boundary.  These entries TEST solved connectors against polygon fields -- exactly, piece
+ * against edge, not by samples -- so that the swath router can avoid the blocked ones through its T / E / X arrays and what stays blocked is
+ * reported.  No path is re-shaped.  Standalone like the router's entries; nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_clearfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Region: a field of the two-level CSR of the swath entries above -- rings, closed implicitly, either orientation, even-odd interior.
+ *     Edge g of a ring runs from vertex g to the next (the last back to the first): the points A + t e, 0 <= t < 1, e = fl(B - A).  There
+ *     is NO margin parameter: pass the field's inset (fcpp_inset_counts / _fill at the margin) for one.
+ *   - Path: start pose, radius, word and seg as fcpp_dubins_solve (mode 0: 3 segments) or fcpp_rs_solve (mode 1: 5 signed segments) wrote
+ *     them.  Piece k is segment k where seg[k] != 0, from P_k to Q_k: Q_k the position at the END of segment k by the samplers' closed form
+ *     (fcpp_dubins_sample / fcpp_rs_sample: from the start of the segment, never chained), P_k the Q of the piece before, the start pose for
+ *     the first.  A straight piece is the segment P Q.  An arc has the centre c = P +- radius (-sin h, cos h) (+ for L, - for R; h the
+ *     heading at P), runs from P to Q counter-clockwise for L forward or R reverse, else clockwise, and is WIDE when |seg[k]| / radius > pi.
+ *     s_k = |seg[0]| + .. + |seg[k - 1]| added left to right.
+ *   - Straight piece against edge, with e_p = Q - P:  o1 = e_p x (A - P), o2 = e_p x (B - P), o3 = e x (P - A), o4 = e x (Q - A).  They
+ *     cross iff (o1 >= 0) != (o2 >= 0) and (o3 >= 0) != (o4 >= 0): half-open on both, so a path through a vertex is counted on ONE of the
+ *     two edges there, never twice for one pair, and collinear overlap is no crossing.  At s = s_k + fmin(o3 / (o3 - o4), 1) |seg[k]|.
+ *   - Arc piece against edge: f = A - c, a = e.e, b = f.e, q = f.f - radius^2, D = b b - a q.  For D > 0 (an edge that only touches the circle
+ *     does not cross) each root t = (-b -+ sqrt D) / a with 0 <= t < 1 gives d = f + t e, which lies within the arc's sweep iff, with
+ *     u = P - c, v = Q - c, c1 = u x d, c2 = d x v (both negated for a clockwise arc):  narrow arc: c1 >= 0 and c2 >= 0 and (u.d >= 0 or
+ *     v.d >= 0);  wide arc: not (c1 < 0 and c2 < 0) -- cross and dot products against the arc's end directions, no angle is taken to
+ *     decide.  Every root kept is a crossing (an arc may cross one edge twice); it lies at s = s_k + fmin(radius x angle, |seg[k]|),
+ *     angle = atan2(c1, u.d) brought into [0, 2 pi).
+ *   - Per (path, field): crossings (int32) = the (straight piece, edge) pairs that cross plus the kept roots of the (arc piece, edge)
+ *     pairs -- the points where the path crosses the boundary; first_s (float64) = the least s of a crossing,
+ *     +inf if there is none; inside (int8) = even-odd membership of the path's START point S from the same loop over the edges -- an
+ *     edge counts iff (A.y > S.y) != (B.y > S.y) and (S.x - A.x) e.y < (S.y - A.y) e.x for e.y > 0, > for e.y < 0;
+ *     clear = inside and crossings == 0.
+ *   - An unsolved path (word outside the mode's table, a NaN segment, a start pose that is not finite): crossings 0, inside 0, first_s NaN,
+ *     not clear.  pair_field = -1 means "no region": crossings 0, inside 1, first_s +inf, clear.
+ *   - field_status (int32 per field): 0, or FCPP_EINVAL for a field with no ring, a ring of fewer than 3 vertices or a vertex that is not
+ *     finite; every path tested against such a field -- or naming a field outside -1 .. n_fields - 1 -- gets the unsolved path's result.
+ *     The other fields are unaffected.
+ * There is NO cap on the edges of a field: the kernels walk them in LDS chunks of FCPP_CLEAR_EDGE_CHUNK edges (48 B each: 12 KiB of the
+ * workgroup's 64 KiB).
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or array (outputs aside), radius <= 0 or not finite, mode not
+ * 0 or 1, an angle not finite or beyond 1e5, penalty negative or not finite; FCPP_ESIZE -- negative sizes, offsets that do not start at 0,
+ * decrease or do not end at their total, t_offsets that are not the blocks of the swath offsets.  (The CSR offsets are read back for these
+ * checks.)  Both entries synchronise. */
+#define FCPP_CLEAR_EDGE_CHUNK 256
+/* Elementwise, a lane per path: path i starts at (from_x, from_y, from_h)[i] with word_dev[i] and seg_dev[3 i ..) (mode 0) or [5 i ..)
+ * (mode 1), and is tested against field pair_field_dev[i] (int64) of the CSR.  Pairs are expected grouped by field; no result depends on
+ * it.  crossings_dev (n int32), inside_dev (n int8), first_s_dev (n float64), field_status_dev (n_fields int32): any may be NULL. */
+int fcpp_conn_clear(fcpp_ctx *ctx, int mode, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                    double radius, const int32_t *word_dev, const double *seg_dev, const int64_t *pair_field_dev, int64_t n_fields,
+                    const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts, const double *x_dev,
+                    const double *y_dev, int32_t *crossings_dev, int8_t *inside_dev, double *first_s_dev, int32_t *field_status_dev);
+/* The matrix form over every field's transit block: fcpp_route_transit's arguments, then the fields' CSR (field i of the swaths is field i
+ * of the CSR: ring_offsets holds n + 1 values), the penalty [m], T_dev (IN / OUT: the blocks as fcpp_route_transit wrote them) and B_dev
+ * (uint8, T's layout and offsets).  Every canonical pair's connector is solved again, as fcpp_route_transit picks and solves it, and tested
+ * once against its field: B[p][q] = B[q-bar][p-bar] = !clear, and where the pair is blocked T[p][q] = T[q-bar][p-bar] = fl(T[p][q] + penalty)
+ * -- one sum, written to both, so the two keep EQUAL BITS (move A of the router relies on it).  Entries within one swath stay +inf with
+ * B = 0.  penalty 0 reports without changing T.  A field beyond FCPP_ROUTE_MAX_SWATHS has no block; every pair of a field whose status
+ * would be FCPP_EINVAL is blocked. */
+int fcpp_route_transit_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                             const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *angle_dev,
+                             double radius, int mode, const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total,
+                             const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                             const double *x_dev, const double *y_dev, double penalty, double *T_dev, uint8_t *B_dev);
+
 /* ---- field paths: every field's routed swaths and connectors as ONE sampled path per field ------------------------------------------------
  * Build-defined.  The last stage of the polygon-field chain (inset -> angle -> swaths -> route -> PATH), batched like the others: a counts
  * entry and a fill entry over all fields.  The result is a path set in CSR form (path_offsets), which fcpp_curvature, fcpp_speed_plan,
@@ -759,7 +820,8 @@ int fcpp_inset_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, i
  * not, every sharp joint closed by a Dubins (mode 0) or Reeds-Shepp (mode 1) connector -- at a corner, where both poses share one
  * position, the bulb turn or the three-point turn.  A counts entry and a fill entry over all rings; the result is a path set in CSR form
  * (path_offsets), which fcpp_curvature, fcpp_speed_plan, fcpp_validate and fcpp_trajectory take as it is.  Standalone: nothing here feeds
- * fcpp_batch_plan.  Connectors know no boundary, as everywhere: fcpp_validate flags what leaves the field.
+ * fcpp_batch_plan.  Connectors know no boundary, as everywhere: fcpp_validate flags what leaves the field, and the connector clearance above
+ * tests them exactly (fcpp_conn_clear on the legs' poses).
  * Input: n_rings rings, ring r owning the vertices ring_offsets[r] .. ring_offsets[r + 1] of x, y (float64) and src (int32: even for a
  * vertex that starts a straight piece, odd for a vertex on an arc, equal along one arc -- fcpp_inset_fill's out_src), closed implicitly,
  * the kept area on the left; ring_dist (n_rings float64): the inset distance d of the ring's (field, distance) pair.
@@ -947,6 +1009,17 @@ int fcpp_debug_route_transit(int64_t n, const int64_t *swath_offsets, int64_t n_
 int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
                      const double *E, const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route,
                      double *cost, int32_t *winner, int32_t *sweeps, int32_t *status, double *stored);
+/* The clearance rule (csrc/fcpp_clearfn.h) evaluated on the HOST, on host pointers: what fcpp_conn_clear and fcpp_route_transit_clear are
+ * compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets are the host's).  Paths and fields
+ * are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
+int fcpp_debug_conn_clear(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, double radius,
+                          const int32_t *word, const double *seg, const int64_t *pair_field, int64_t n_fields, const int64_t *ring_offsets,
+                          int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y, int32_t *crossings,
+                          int8_t *inside, double *first_s, int32_t *field_status);
+int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                   const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
+                                   const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                   const double *y, double penalty, double *T, uint8_t *B);
 /* The field-path rule (csrc/fcpp_fpathfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device results
  * are compared with bit for bit.  Arguments and the call's errors as for fcpp_field_path_counts / _fill.  path_offsets (n + 1), leg_offsets
  * (2 n_total + n + 1), work_length, transit_length, status (n): any may be NULL.  leg_word, leg_seg (5 each), leg_total (2 n_total + n slots,
