@@ -1,6 +1,6 @@
 // fcpp_fpathfn.h -- field paths: the sampled path of every field of a batch from its cut swaths (fcpp_swath_fill's records), a driving order
 // (the stored boustrophedon or fcpp_route_solve's route) and the connectors between them, with optional entry and exit poses.  ONE set of
-// expressions for the host (fcpp_debug_field_paths, the tests' checker) and the device (fcpp_fpath.hip), written like fcpp_routefn.h in
+// expressions for the host (fcpp_debug_field_paths, the tests' checker) and the device (fcpp_legs.hip), written like fcpp_routefn.h in
 // plain IEEE-754 double operations and compiled with -ffp-contract=off on both sides, so that both give the same bits.  Build-defined: the
 // reference has no polygon fields.  Nothing is restated here: the poses are route_pose's, the connectors dubins_solve's / rs_solve's and
 // their samples, like the count rule, the samplers' own (Conn<MODE>::eval / ::count and sample_count of fcpp_connfn.h).
@@ -147,6 +147,19 @@ FCPP_HD void fpath_totals(const FpathLeg *legs, int64_t m, bool has_entry, bool 
     transit = sum + (has_exit ? legs[2 * m].total : 0.0);
 }
 
+// ---- the host twins' count rule, for every leg rule: a failed group's counts are 0; -> a leg or the group has 2^31 samples or more -------
+inline bool leg_counts_host(int64_t *cnt, int64_t n_slots, bool ok)
+{
+    bool oversize = false;
+    int64_t sum = 0;
+    for (int64_t j = 0; j < n_slots; ++j) {
+        if (!ok) cnt[j] = 0;
+        else if (cnt[j] < 0) { oversize = true; cnt[j] = 0; }
+        sum += cnt[j];
+    }
+    return oversize || sum > FPATH_MAX_SAMPLES;
+}
+
 // ---- the host twin: one field ---------------------------------------------------------------------------------------------------------
 // legs, cnt: the field's 2 m + 1 slots; seen: m entries of scratch.  -> the status; a failed field's counts are 0, its totals NaN.
 template <int MODE>
@@ -155,7 +168,6 @@ inline int fpath_field_host(const FpathIn &in, int64_t i, FpathLeg *legs, int64_
 {
     const int64_t s0 = in.soff[i], m = in.soff[i + 1] - s0, n_slots = 2 * (m > 0 ? m : 0) + 1;
     int status = FPATH_OK;
-    oversize = false;
     for (int64_t k = 0; k < m; ++k) seen[k] = 0;
     for (int64_t j = 0; j < n_slots; ++j) {
         bool invalid;
@@ -163,16 +175,30 @@ inline int fpath_field_host(const FpathIn &in, int64_t i, FpathLeg *legs, int64_
         if (!invalid && in.order && (j & 1) && m > 0 && seen[in.order[s0 + (j - 1) / 2] >> 1]++ != 0) invalid = true;
         if (invalid) status = FPATH_EINVAL;
     }
-    int64_t sum = 0;
-    for (int64_t j = 0; j < n_slots; ++j) {
-        if (status != FPATH_OK) cnt[j] = 0;
-        else if (cnt[j] < 0) { oversize = true; cnt[j] = 0; }
-        sum += cnt[j];
-    }
-    if (sum > FPATH_MAX_SAMPLES) oversize = true;
+    oversize = leg_counts_host(cnt, n_slots, status == FPATH_OK);
     if (status == FPATH_OK) fpath_totals(legs, m, in.ex != nullptr, in.xx != nullptr, work, transit);
     else work = transit = __builtin_nan("");
     return status;
 }
+
+// ---- the leg set of the field paths: all that the kernels, launchers and entries shared by the leg-path operators (fcpp_legs.hip, -------
+// fcpp_paths.cpp) ask of one.  A GROUP (here a field) owns a contiguous run of leg slots, first_slot(g) .. first_slot(g + 1).
+struct FieldLegs {
+    typedef FpathIn In;
+    typedef FpathLeg Leg;
+    static constexpr int N_TOTALS = 2;                                     // work, transit
+    static FCPP_HD int64_t first_slot(const In &in, int64_t g) { return fpath_first_slot(in.soff, g); }
+    static FCPP_HD const FpathLeg &base(const Leg &lg) { return lg; }
+    static FCPP_HD void eval(const Leg &lg, double R, double spacing, int64_t k, int64_t K, double &x, double &y, double &h, double &kappa, int &gear)
+    {
+        fpath_eval(lg, R, spacing, k, K, x, y, h, kappa, gear);
+    }
+    // the totals of group g (legs: its first record): NaN unless the field is OK
+    static FCPP_HD void totals(const In &in, const Leg *legs, int64_t g, int status, double *t)
+    {
+        t[0] = t[1] = __builtin_nan("");
+        if (status == FPATH_OK) fpath_totals(legs, in.soff[g + 1] - in.soff[g], in.ex != nullptr, in.xx != nullptr, t[0], t[1]);
+    }
+};
 
 }  // namespace fcpp

@@ -1,6 +1,6 @@
 // fcpp_hpathfn.h -- headland paths: every ring of a polygon inset (fcpp_inset_fill's x, y, src: the centre line of one headland pass) as ONE
 // sampled, closed, drivable path.  ONE set of expressions for the host (fcpp_debug_headland_paths, the tests' checker) and the device
-// (fcpp_hpath.hip), written like fcpp_fpathfn.h in plain IEEE-754 double operations with the transcendentals of fcpp_math.h / fcpp_geom.h
+// (fcpp_legs.hip), written like fcpp_fpathfn.h in plain IEEE-754 double operations with the transcendentals of fcpp_math.h / fcpp_geom.h
 // (fc_sincos, atan2_fd, fc_hypot) and compiled with -ffp-contract=off on both sides, so that both give the same bits.  Build-defined: the
 // reference has no polygon fields.  The straight elements are sampled by fpath_eval's swath rule, the connectors solved, counted and
 // sampled by Conn<MODE> (fcpp_connfn.h); what is written HERE is the rule that turns a ring into elements and joints, and the followed arc.
@@ -221,7 +221,6 @@ inline int hpath_ring_host(const HpathIn &in, int64_t r, HpathLeg *legs, int64_t
 {
     const int64_t m = in.roff[r + 1] - in.roff[r];
     bool any_invalid = m < 2, any_drivable = false;
-    oversize = false;
     for (int64_t k = 0; k < m; ++k) {
         bool invalid, drivable;
         hpath_legs<MODE>(in, r, k, legs[2 * k], legs[2 * k + 1], cnt[2 * k], cnt[2 * k + 1], invalid, drivable);
@@ -229,16 +228,29 @@ inline int hpath_ring_host(const HpathIn &in, int64_t r, HpathLeg *legs, int64_t
         any_drivable = any_drivable || drivable;
     }
     const int status = any_invalid ? HPATH_EINVAL : (any_drivable ? HPATH_OK : HPATH_EUNSUPPORTED);
-    int64_t sum = 0;
-    for (int64_t j = 0; j < 2 * m; ++j) {
-        if (status != HPATH_OK) cnt[j] = 0;
-        else if (cnt[j] < 0) { oversize = true; cnt[j] = 0; }
-        sum += cnt[j];
-    }
-    if (sum > FPATH_MAX_SAMPLES) oversize = true;
+    oversize = leg_counts_host(cnt, 2 * m, status == HPATH_OK);
     if (status != HPATH_EINVAL) hpath_totals(legs, m, work, transit, skipped);
     else work = transit = skipped = __builtin_nan("");
     return status;
 }
+
+// ---- the leg set of the headland paths (what FieldLegs of fcpp_fpathfn.h is to the field paths): a group is a ring ----------------------
+struct RingLegs {
+    typedef HpathIn In;
+    typedef HpathLeg Leg;
+    static constexpr int N_TOTALS = 3;                                     // work, transit, skipped
+    static FCPP_HD int64_t first_slot(const In &in, int64_t g) { return 2 * in.roff[g]; }
+    static FCPP_HD const FpathLeg &base(const Leg &lg) { return lg.leg; }
+    static FCPP_HD void eval(const Leg &lg, double R, double spacing, int64_t k, int64_t K, double &x, double &y, double &h, double &kappa, int &gear)
+    {
+        hpath_eval(lg, R, spacing, k, K, x, y, h, kappa, gear);
+    }
+    // the totals of group g (legs: its first record): NaN only for EINVAL (a ring without a drivable element keeps what was skipped)
+    static FCPP_HD void totals(const In &in, const Leg *legs, int64_t g, int status, double *t)
+    {
+        t[0] = t[1] = t[2] = __builtin_nan("");
+        if (status != HPATH_EINVAL) hpath_totals(legs, in.roff[g + 1] - in.roff[g], t[0], t[1], t[2]);
+    }
+};
 
 }  // namespace fcpp

@@ -12,12 +12,11 @@
 #include "fcpp_clear.h"
 #include "fcpp_clearfn.h"
 #include "fcpp_conn.h"
-#include "fcpp_fpath.h"
 #include "fcpp_fpathfn.h"
-#include "fcpp_hpath.h"
 #include "fcpp_hpathfn.h"
 #include "fcpp_inset.h"
 #include "fcpp_insetfn.h"
+#include "fcpp_legs.h"
 #include "fcpp_parallel.h"
 #include "fcpp_pcover.h"
 #include "fcpp_pcoverfn.h"
@@ -66,6 +65,17 @@ int host_offsets(fcpp_ctx *c, int64_t n, const int64_t *dev, const int64_t *host
     if (out[0] != 0 || out.back() != total) return fail(FCPP_ESIZE, std::string(what) + " do not span [0, total]");
     for (int64_t p = 0; p < n; ++p)
         if (out[(size_t)p + 1] < out[(size_t)p]) return fail(FCPP_ESIZE, std::string(what) + " must be non-decreasing");
+    return FCPP_OK;
+}
+
+// m doubles on the host: the caller's copy, or read back from the device into `own` (one copy + synchronisation)
+int host_doubles(fcpp_ctx *c, int64_t m, const double *dev, const double *&host, std::vector<double> &own)
+{
+    if (host || m <= 0) return FCPP_OK;
+    try { own.assign((size_t)m, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    HIPCHK(hipMemcpyAsync(own.data(), dev, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    host = own.data();
     return FCPP_OK;
 }
 
@@ -264,13 +274,9 @@ int swath_sizes(int64_t n, int64_t n_rings, int64_t n_verts, int64_t A)
 // m angles on the host (the caller's, or read back from the device): finite and within fc_sincos' range
 int swath_angles(fcpp_ctx *c, int64_t m, const double *dev, const double *host)
 {
-    std::vector<double> h;
-    if (!host && m > 0) {
-        try { h.assign((size_t)m, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-        HIPCHK(hipMemcpyAsync(h.data(), dev, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        host = h.data();
-    }
+    std::vector<double> own;
+    const int rc = host_doubles(c, m, dev, host, own);
+    if (rc) return rc;
     for (int64_t j = 0; j < m; ++j)
         if (!(fabs(host[j]) <= SWATH_MAX_ANGLE)) return fail(FCPP_EINVAL, "angles must be finite, |angle| <= 1e5");
     return FCPP_OK;
@@ -297,13 +303,9 @@ int inset_sizes(int64_t n, int64_t n_rings, int64_t n_verts, int64_t D)
 int inset_params(fcpp_ctx *c, int64_t D, const double *dev, const double *host, double arc_step)
 {
     if (!(arc_step > 0.0) || !(arc_step <= INSET_MAX_ARC_STEP)) return fail(FCPP_EINVAL, "arc_step must lie in (0, pi/2]");
-    std::vector<double> h;
-    if (!host && D > 0) {
-        try { h.assign((size_t)D, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-        HIPCHK(hipMemcpyAsync(h.data(), dev, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        host = h.data();
-    }
+    std::vector<double> own;
+    const int rc = host_doubles(c, D, dev, host, own);
+    if (rc) return rc;
     for (int64_t j = 0; j < D; ++j)
         if (!(host[j] > 0.0) || !isfinite(host[j])) return fail(FCPP_EINVAL, "distances must be positive and finite");
     return FCPP_OK;
@@ -430,6 +432,109 @@ int hpath_args(int64_t n_rings, const void *ring_offsets, int64_t n_verts, const
     if (direction != 1 && direction != -1) return fail(FCPP_EINVAL, "direction must be +1 (as stored) or -1");
     if (!(smooth_tol >= 0.0)) return fail(FCPP_EINVAL, "smooth_tol must not be negative");
     if (n_rings < 0 || n_verts < 0 || n_rings > INT32_MAX || n_verts > HPATH_MAX_VERTS) return fail(FCPP_ESIZE, "bad sizes (at most 2^30 vertices)");
+    return FCPP_OK;
+}
+// ---- leg paths: what the field paths' and the headland paths' three entries are behind their argument checks, on the leg set P ------------
+// (FieldLegs / RingLegs of the rule headers; the kernels: fcpp_legs.hip).  A fill RECOMPUTES the leg records from its inputs (one more
+// launch of the rule kernel) instead of keeping the counts call's in the context: the entries stay stateless, and the solves are a small
+// part of the samples' cost.
+// *_counts: the temporaries (n_scratch: the int32 scratch of the rule kernel), the call's own status buffer when the caller passes none
+template <class P>
+int legs_counts(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, int64_t n_scratch, const typename P::In &in, int mode, const char *esize,
+                int64_t *path_offsets, int64_t *path_offsets_host, int64_t *leg_offsets, const LegTotals &totals, int32_t *status)
+{
+    DevBuf<typename P::Leg> legs;
+    DevBuf<int64_t> cnt;
+    DevBuf<int32_t> scratch, own_status;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    HIPCHK(cnt.alloc((size_t)n_slots));
+    HIPCHK(scratch.alloc((size_t)n_scratch));
+    if (!status) { HIPCHK(own_status.alloc((size_t)n_groups)); status = own_status.p; }
+    return sample_counts(c, n_groups, path_offsets, path_offsets_host, esize, [&](hipStream_t st, int64_t *err) {
+        if (n_scratch > 0) { const hipError_t e = hipMemsetAsync(scratch.p, 0, (size_t)n_scratch * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
+        if (n_groups > 0) { const hipError_t e = hipMemsetAsync(status, 0, (size_t)n_groups * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
+        const int e = launch_legs(st, n_groups, n_slots, in, mode, legs.p, cnt.p, scratch.p, status);
+        return e ? e : launch_leg_offsets(st, n_groups, n_slots, in, legs.p, cnt.p, status, scratch.p, leg_offsets, path_offsets, totals, err);
+    });      // (sample_counts has drained the stream: the temporaries die here)
+}
+
+// *_fill.  The ends of the slot offsets must match the output arrays.  (The fill writes sample q < total_samples of every array and reads
+// the record of a slot below n_slots whatever lies between the ends: offsets that are not the counts call's give wrong samples, never an
+// access outside the arrays.)
+template <class P>
+int legs_fill(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, const typename P::In &in, int mode, const int64_t *leg_offsets, int64_t total_samples,
+              double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    int64_t ends[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&ends[1], leg_offsets + n_slots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (ends[0] != 0 || ends[1] != total_samples) return fail(FCPP_ESIZE, "leg_offsets do not span [0, total_samples]");
+    DevBuf<typename P::Leg> legs;
+    HIPCHK(legs.alloc((size_t)n_slots));
+    LAUNCHCHK(launch_legs(c->stream, n_groups, n_slots, in, mode, legs.p, nullptr, nullptr, nullptr));
+    LAUNCHCHK(launch_leg_fill<P>(c->stream, n_slots, legs.p, leg_offsets, total_samples, in.R, in.spacing, x, y, heading, kappa, part, gear, leg));
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
+    return FCPP_OK;
+}
+
+// fcpp_debug_*: group(g, legs, cnt, t, oversize) -> status is the rule's host twin of one group (its records, its counts -- in off, one
+// slot ahead: scanned below -- and its totals); groups go to the library's host threads.  `in` holds host pointers.
+template <class P, class Group>
+int legs_host(int64_t n_groups, int64_t n_slots, const typename P::In &in, const char *esize, Group group, int64_t *path_offsets, int64_t *leg_offsets,
+              const LegTotals &totals, int32_t *status, int32_t *leg_kind, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap, double *x,
+              double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    std::vector<typename P::Leg> legs;
+    std::vector<int64_t> off;
+    std::vector<char> big;
+    try {
+        legs.resize((size_t)n_slots); off.assign((size_t)n_slots + 1, 0); big.assign((size_t)n_groups, 0);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    WorkerPool::parallel_for(n_groups, [&](int64_t g) {
+        const int64_t first = P::first_slot(in, g);
+        double t[P::N_TOTALS];
+        bool oversize;
+        const int st = group(g, legs.data() + first, off.data() + first + 1, t, oversize);
+        big[(size_t)g] = oversize;
+        if (status) status[g] = st;
+        for (int k = 0; k < P::N_TOTALS; ++k)
+            if (totals.p[k]) totals.p[k][g] = t[k];
+    });
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (big[(size_t)g]) return fail(FCPP_ESIZE, esize);
+    for (int64_t p = 0; p < n_slots; ++p) {
+        off[(size_t)p + 1] += off[(size_t)p];
+        const FpathLeg &lg = P::base(legs[(size_t)p]);
+        if (leg_kind) leg_kind[p] = lg.kind;
+        if (leg_word) leg_word[p] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
+        if (leg_seg) for (int k = 0; k < 5; ++k) leg_seg[5 * p + k] = lg.seg[k];
+        if (leg_total) leg_total[p] = lg.total;
+    }
+    if (leg_offsets) memcpy(leg_offsets, off.data(), off.size() * sizeof(int64_t));
+    if (path_offsets) {
+        for (int64_t g = 0; g < n_groups; ++g) path_offsets[g] = off[(size_t)P::first_slot(in, g)];
+        path_offsets[n_groups] = off[(size_t)n_slots];
+    }
+    if (cap == 0 || !(x || y || heading || kappa || part || gear || leg)) return FCPP_OK;
+    WorkerPool::parallel_for(n_groups, [&](int64_t g) {
+        for (int64_t p = P::first_slot(in, g); p < P::first_slot(in, g + 1); ++p) {
+            const typename P::Leg &lg = legs[(size_t)p];
+            const int64_t at = off[(size_t)p], K = off[(size_t)p + 1] - at;
+            for (int64_t k = 0; k < K && at + k < cap; ++k) {
+                double px, py, ph, pk;
+                int pg;
+                P::eval(lg, in.R, in.spacing, k, K, px, py, ph, pk, pg);
+                if (x) x[at + k] = px;
+                if (y) y[at + k] = py;
+                if (heading) heading[at + k] = ph;
+                if (kappa) kappa[at + k] = pk;
+                if (part) part[at + k] = (int8_t)P::base(lg).part;
+                if (gear) gear[at + k] = (int8_t)pg;
+                if (leg) leg[at + k] = P::base(lg).slot;
+            }
+        }
+    });
     return FCPP_OK;
 }
 }  // namespace
@@ -1142,9 +1247,7 @@ int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int6
     return FCPP_OK;
 }
 
-// ---- field paths (fcpp_fpath.hip; the rule: fcpp_fpathfn.h) ---------------------------------------------------------------------------
-// The fill RECOMPUTES the leg records from its inputs (one more launch of the leg kernel) instead of keeping the counts call's in the
-// context: the two entries stay stateless, and the solves are a small part of the samples' cost.
+// ---- field paths and headland paths (fcpp_legs.hip; the rules: fcpp_fpathfn.h, fcpp_hpathfn.h): argument checks, then the leg paths' skeleton ----
 int fcpp_field_path_counts(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
                            const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,
                            const int32_t *order, double radius, int mode, double spacing, const double *entry_x, const double *entry_y,
@@ -1160,23 +1263,9 @@ int fcpp_field_path_counts(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets,
     std::vector<int64_t> soff;
     rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
     if (rc) return rc;
-    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
     const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
-    DevBuf<FpathLeg> legs;
-    DevBuf<int64_t> cnt;
-    DevBuf<int32_t> seen, own_status;
-    HIPCHK(legs.alloc((size_t)n_slots));
-    HIPCHK(cnt.alloc((size_t)n_slots));
-    HIPCHK(seen.alloc((size_t)n_total));
-    if (!status) { HIPCHK(own_status.alloc((size_t)n)); status = own_status.p; }
-    rc = sample_counts(c, n, path_offsets, path_offsets_host, "a leg or a field has 2^31 samples or more", [&](hipStream_t st, int64_t *err) {
-        if (n_total > 0) { const hipError_t e = hipMemsetAsync(seen.p, 0, (size_t)n_total * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
-        if (n > 0) { const hipError_t e = hipMemsetAsync(status, 0, (size_t)n * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
-        const int e = launch_fpath_legs(st, n, n_total, in, mode, legs.p, cnt.p, seen.p, status);
-        return e ? e : launch_fpath_offsets(st, n, n_total, swath_offsets, legs.p, cnt.p, status, entry_x != nullptr, exit_x != nullptr, leg_offsets,
-                                            path_offsets, work_length, transit_length, err);
-    });
-    return rc;      // (sample_counts has drained the stream: the temporaries die here)
+    return legs_counts<FieldLegs>(c, n, n > 0 ? 2 * n_total + n : 0, n_total, in, mode, "a leg or a field has 2^31 samples or more", path_offsets,
+                                  path_offsets_host, leg_offsets, { { work_length, transit_length, nullptr } }, status);
 }
 
 int fcpp_field_path_fill(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
@@ -1195,22 +1284,8 @@ int fcpp_field_path_fill(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, c
     std::vector<int64_t> soff;
     rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
     if (rc) return rc;
-    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
-    // The ends of the slot offsets must match the output arrays.  (The fill writes sample q < total_samples of every array and reads the
-    // record of a slot below n_slots whatever lies between the ends: offsets that are not fcpp_field_path_counts' give wrong samples,
-    // never an access outside the arrays.)
-    int64_t ends[2] = { 0, 0 };
-    HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], leg_offsets + n_slots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (ends[0] != 0 || ends[1] != total_samples) return fail(FCPP_ESIZE, "leg_offsets do not span [0, total_samples]");
     const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
-    DevBuf<FpathLeg> legs;
-    HIPCHK(legs.alloc((size_t)n_slots));
-    LAUNCHCHK(launch_fpath_legs(c->stream, n, n_total, in, mode, legs.p, nullptr, nullptr, nullptr));
-    LAUNCHCHK(launch_fpath_fill(c->stream, n_slots, legs.p, leg_offsets, total_samples, radius, spacing, x, y, heading, kappa, part, gear, leg));
-    HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
-    return FCPP_OK;
+    return legs_fill<FieldLegs>(c, n, n > 0 ? 2 * n_total + n : 0, in, mode, leg_offsets, total_samples, x, y, heading, kappa, part, gear, leg);
 }
 
 int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
@@ -1227,66 +1302,19 @@ int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_to
     std::vector<int64_t> soff;
     rc = fpath_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, angle, soff);
     if (rc) return rc;
-    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
     const FpathIn in = { soff.data(), ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
-    std::vector<FpathLeg> legs;
-    std::vector<int64_t> off;
     std::vector<int32_t> seen;
-    std::vector<char> big;
-    try {
-        legs.resize((size_t)n_slots); off.assign((size_t)n_slots + 1, 0); seen.assign((size_t)n_total, 0); big.assign((size_t)n, 0);
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    // the records, the counts (in off, one slot ahead: scanned below), the status and the totals; fields to the library's host threads
-    WorkerPool::parallel_for(n, [&](int64_t i) {
-        const int64_t first = fpath_first_slot(soff.data(), i);
-        double w, t;
-        bool oversize;
-        const int st = mode == 0 ? fpath_field_host<0>(in, i, legs.data() + first, off.data() + first + 1, seen.data() + soff[(size_t)i], w, t, oversize)
-                                 : fpath_field_host<1>(in, i, legs.data() + first, off.data() + first + 1, seen.data() + soff[(size_t)i], w, t, oversize);
-        big[(size_t)i] = oversize;
-        if (status) status[i] = st;
-        if (work_length) work_length[i] = w;
-        if (transit_length) transit_length[i] = t;
-    });
-    for (int64_t i = 0; i < n; ++i)
-        if (big[(size_t)i]) return fail(FCPP_ESIZE, "a leg or a field has 2^31 samples or more");
-    for (int64_t g = 0; g < n_slots; ++g) {
-        off[(size_t)g + 1] += off[(size_t)g];
-        const FpathLeg &lg = legs[(size_t)g];
-        if (leg_word) leg_word[g] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
-        if (leg_seg) for (int k = 0; k < 5; ++k) leg_seg[5 * g + k] = lg.seg[k];
-        if (leg_total) leg_total[g] = lg.total;
-    }
-    if (leg_offsets) memcpy(leg_offsets, off.data(), off.size() * sizeof(int64_t));
-    if (path_offsets) {
-        for (int64_t i = 0; i < n; ++i) path_offsets[i] = off[(size_t)fpath_first_slot(soff.data(), i)];
-        path_offsets[n] = off[(size_t)n_slots];
-    }
-    if (cap == 0 || !(x || y || heading || kappa || part || gear || leg)) return FCPP_OK;
-    WorkerPool::parallel_for(n, [&](int64_t i) {
-        const int64_t first = fpath_first_slot(soff.data(), i), last = fpath_first_slot(soff.data(), i + 1);
-        for (int64_t g = first; g < last; ++g) {
-            const FpathLeg &lg = legs[(size_t)g];
-            const int64_t at = off[(size_t)g], K = off[(size_t)g + 1] - at;
-            for (int64_t k = 0; k < K && at + k < cap; ++k) {
-                double px, py, ph, pk;
-                int pg;
-                fpath_eval(lg, radius, spacing, k, K, px, py, ph, pk, pg);
-                if (x) x[at + k] = px;
-                if (y) y[at + k] = py;
-                if (heading) heading[at + k] = ph;
-                if (kappa) kappa[at + k] = pk;
-                if (part) part[at + k] = (int8_t)lg.part;
-                if (gear) gear[at + k] = (int8_t)pg;
-                if (leg) leg[at + k] = lg.slot;
-            }
-        }
-    });
-    return FCPP_OK;
+    try { seen.assign((size_t)n_total, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    return legs_host<FieldLegs>(n, n > 0 ? 2 * n_total + n : 0, in, "a leg or a field has 2^31 samples or more",
+                                [&](int64_t i, FpathLeg *legs, int64_t *cnt, double *t, bool &oversize) {
+                                    int32_t *sn = seen.data() + soff[(size_t)i];
+                                    return mode == 0 ? fpath_field_host<0>(in, i, legs, cnt, sn, t[0], t[1], oversize)
+                                                     : fpath_field_host<1>(in, i, legs, cnt, sn, t[0], t[1], oversize);
+                                },
+                                path_offsets, leg_offsets, { { work_length, transit_length, nullptr } }, status, nullptr, leg_word, leg_seg, leg_total, cap,
+                                x, y, heading, kappa, part, gear, leg);
 }
 
-// ---- headland paths (fcpp_hpath.hip; the rule: fcpp_hpathfn.h) ------------------------------------------------------------------------
-// Like the field paths, the fill RECOMPUTES the leg records from its inputs: the two entries stay stateless.
 int fcpp_headland_path_counts(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_offsets, const int64_t *ring_offsets_host, int64_t n_verts,
                               const double *x, const double *y, const int32_t *src, const double *ring_dist, double radius, int mode,
                               double spacing, int direction, double smooth_tol, int64_t *path_offsets, int64_t *path_offsets_host,
@@ -1300,26 +1328,9 @@ int fcpp_headland_path_counts(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_
     std::vector<int64_t> roff;
     rc = host_offsets(c, n_rings, ring_offsets, ring_offsets_host, n_verts, "ring_offsets", roff);
     if (rc) return rc;
-    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
     const HpathIn in = { ring_offsets, x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
-    DevBuf<HpathLeg> legs;
-    DevBuf<int64_t> cnt;
-    DevBuf<int32_t> drivable, own_status;
-    HIPCHK(legs.alloc((size_t)n_slots));
-    HIPCHK(cnt.alloc((size_t)n_slots));
-    HIPCHK(drivable.alloc((size_t)n_rings));
-    if (!status) { HIPCHK(own_status.alloc((size_t)n_rings)); status = own_status.p; }
-    rc = sample_counts(c, n_rings, path_offsets, path_offsets_host, "a leg or a ring has 2^31 samples or more", [&](hipStream_t st, int64_t *err) {
-        if (n_rings > 0) {
-            hipError_t e = hipMemsetAsync(drivable.p, 0, (size_t)n_rings * sizeof(int32_t), st);
-            if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)n_rings * sizeof(int32_t), st);
-            if (e != hipSuccess) return (int)e;
-        }
-        const int e = launch_hpath_legs(st, n_rings, n_verts, in, mode, legs.p, cnt.p, status, drivable.p);
-        return e ? e : launch_hpath_offsets(st, n_rings, n_verts, ring_offsets, legs.p, cnt.p, status, drivable.p, leg_offsets, path_offsets, work_length,
-                                            transit_length, skipped_length, err);
-    });
-    return rc;      // (sample_counts has drained the stream: the temporaries die here)
+    return legs_counts<RingLegs>(c, n_rings, n_rings > 0 ? 2 * n_verts : 0, n_rings, in, mode, "a leg or a ring has 2^31 samples or more", path_offsets,
+                                 path_offsets_host, leg_offsets, { { work_length, transit_length, skipped_length } }, status);
 }
 
 int fcpp_headland_path_fill(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_offsets, const int64_t *ring_offsets_host, int64_t n_verts,
@@ -1336,21 +1347,9 @@ int fcpp_headland_path_fill(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_of
     std::vector<int64_t> roff;
     rc = host_offsets(c, n_rings, ring_offsets, ring_offsets_host, n_verts, "ring_offsets", roff);
     if (rc) return rc;
-    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
-    // The ends of the slot offsets must match the output arrays, as in fcpp_field_path_fill: offsets that are not the counts call's give
-    // wrong samples, never an access outside the arrays.
-    int64_t ends[2] = { 0, 0 };
-    HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], leg_offsets + n_slots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (ends[0] != 0 || ends[1] != total_samples) return fail(FCPP_ESIZE, "leg_offsets do not span [0, total_samples]");
     const HpathIn in = { ring_offsets, x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
-    DevBuf<HpathLeg> legs;
-    HIPCHK(legs.alloc((size_t)n_slots));
-    LAUNCHCHK(launch_hpath_legs(c->stream, n_rings, n_verts, in, mode, legs.p, nullptr, nullptr, nullptr));
-    LAUNCHCHK(launch_hpath_fill(c->stream, n_slots, legs.p, leg_offsets, total_samples, radius, spacing, out_x, out_y, heading, kappa, part, gear, leg));
-    HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
-    return FCPP_OK;
+    return legs_fill<RingLegs>(c, n_rings, n_rings > 0 ? 2 * n_verts : 0, in, mode, leg_offsets, total_samples, out_x, out_y, heading, kappa, part, gear,
+                               leg);
 }
 
 int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int64_t n_verts, const double *x, const double *y, const int32_t *src,
@@ -1365,62 +1364,14 @@ int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int6
     std::vector<int64_t> roff;
     rc = host_offsets(nullptr, n_rings, nullptr, ring_offsets, n_verts, "ring_offsets", roff);
     if (rc) return rc;
-    const int64_t n_slots = n_rings > 0 ? 2 * n_verts : 0;
     const HpathIn in = { roff.data(), x, y, src, ring_dist, radius, spacing, smooth_tol, direction };
-    std::vector<HpathLeg> legs;
-    std::vector<int64_t> off;
-    std::vector<char> big;
-    try {
-        legs.resize((size_t)n_slots); off.assign((size_t)n_slots + 1, 0); big.assign((size_t)n_rings, 0);
-    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
-    // the records, the counts (in off, one slot ahead: scanned below), the status and the totals; rings to the library's host threads
-    WorkerPool::parallel_for(n_rings, [&](int64_t r) {
-        const int64_t first = 2 * roff[(size_t)r];
-        double w, t, s;
-        bool oversize;
-        const int st = mode == 0 ? hpath_ring_host<0>(in, r, legs.data() + first, off.data() + first + 1, w, t, s, oversize)
-                                 : hpath_ring_host<1>(in, r, legs.data() + first, off.data() + first + 1, w, t, s, oversize);
-        big[(size_t)r] = oversize;
-        if (status) status[r] = st;
-        if (work_length) work_length[r] = w;
-        if (transit_length) transit_length[r] = t;
-        if (skipped_length) skipped_length[r] = s;
-    });
-    for (int64_t r = 0; r < n_rings; ++r)
-        if (big[(size_t)r]) return fail(FCPP_ESIZE, "a leg or a ring has 2^31 samples or more");
-    for (int64_t g = 0; g < n_slots; ++g) {
-        off[(size_t)g + 1] += off[(size_t)g];
-        const FpathLeg &lg = legs[(size_t)g].leg;
-        if (leg_kind) leg_kind[g] = lg.kind;
-        if (leg_word) leg_word[g] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
-        if (leg_seg) for (int k = 0; k < 5; ++k) leg_seg[5 * g + k] = lg.seg[k];
-        if (leg_total) leg_total[g] = lg.total;
-    }
-    if (leg_offsets) memcpy(leg_offsets, off.data(), off.size() * sizeof(int64_t));
-    if (path_offsets) {
-        for (int64_t r = 0; r < n_rings; ++r) path_offsets[r] = off[(size_t)(2 * roff[(size_t)r])];
-        path_offsets[n_rings] = off[(size_t)n_slots];
-    }
-    if (cap == 0 || !(out_x || out_y || heading || kappa || part || gear || leg)) return FCPP_OK;
-    WorkerPool::parallel_for(n_rings, [&](int64_t r) {
-        for (int64_t g = 2 * roff[(size_t)r]; g < 2 * roff[(size_t)r + 1]; ++g) {
-            const HpathLeg &lg = legs[(size_t)g];
-            const int64_t at = off[(size_t)g], K = off[(size_t)g + 1] - at;
-            for (int64_t k = 0; k < K && at + k < cap; ++k) {
-                double px, py, ph, pk;
-                int pg;
-                hpath_eval(lg, radius, spacing, k, K, px, py, ph, pk, pg);
-                if (out_x) out_x[at + k] = px;
-                if (out_y) out_y[at + k] = py;
-                if (heading) heading[at + k] = ph;
-                if (kappa) kappa[at + k] = pk;
-                if (part) part[at + k] = (int8_t)lg.leg.part;
-                if (gear) gear[at + k] = (int8_t)pg;
-                if (leg) leg[at + k] = lg.leg.slot;
-            }
-        }
-    });
-    return FCPP_OK;
+    return legs_host<RingLegs>(n_rings, n_rings > 0 ? 2 * n_verts : 0, in, "a leg or a ring has 2^31 samples or more",
+                               [&](int64_t r, HpathLeg *legs, int64_t *cnt, double *t, bool &oversize) {
+                                   return mode == 0 ? hpath_ring_host<0>(in, r, legs, cnt, t[0], t[1], t[2], oversize)
+                                                    : hpath_ring_host<1>(in, r, legs, cnt, t[0], t[1], t[2], oversize);
+                               },
+                               path_offsets, leg_offsets, { { work_length, transit_length, skipped_length } }, status, leg_kind, leg_word, leg_seg, leg_total,
+                               cap, out_x, out_y, heading, kappa, part, gear, leg);
 }
 
 }  // extern "C"

@@ -63,15 +63,23 @@ __global__ __launch_bounds__(BLOCK) void k_path_counts(int64_t n, CountOf count_
     sample_scan<BLOCK>(n, count_of, out_offsets, err);
 }
 
-// sample q of all: p = the last path with out_offsets[p] <= q, k = its index in that path, K = the path's samples
-__device__ __forceinline__ void sample_path(const int64_t *__restrict__ out_offsets, int64_t n, int64_t q, int64_t &p, int64_t &k, int64_t &K)
+// the last index i of 0 .. n - 1 with key(i) <= q, for a non-decreasing key with key(0) <= q: the path of a sample, the group of a slot
+template <class Key>
+__device__ __forceinline__ int64_t last_at_or_before(int64_t n, int64_t q, Key key)
 {
     int64_t lo = 0, hi = n;
     while (hi - lo > 1) {
         const int64_t mid = lo + (hi - lo) / 2;
-        if (out_offsets[mid] <= q) lo = mid; else hi = mid;
+        if (key(mid) <= q) lo = mid; else hi = mid;
     }
-    p = lo; k = q - out_offsets[p]; K = out_offsets[p + 1] - out_offsets[p];
+    return lo;
+}
+
+// sample q of all: p = the last path with out_offsets[p] <= q, k = its index in that path, K = the path's samples
+__device__ __forceinline__ void sample_path(const int64_t *__restrict__ out_offsets, int64_t n, int64_t q, int64_t &p, int64_t &k, int64_t &K)
+{
+    p = last_at_or_before(n, q, [&](int64_t i) { return out_offsets[i]; });
+    k = q - out_offsets[p]; K = out_offsets[p + 1] - out_offsets[p];
 }
 
 }  // namespace fcpp

@@ -1782,6 +1782,25 @@ def _pose_columns(pose, n, dev):
     return p[0], p[1], p[2]
 
 
+def _leg_paths(ctx, counts, fill, args, n_groups, n_slots, n_totals, dev):
+    """What field_paths and headland_paths share: the counts entry, the total read from its host offsets, the seven sample columns, the fill
+    entry -> (offsets, offsets_host, x, y, heading, kappa, part, gear, leg, *totals, status, leg_offsets).  args: the entries' common
+    arguments behind the handle; n_totals: the per-group float64 totals the counts entry writes."""
+    torch = _torch()
+    off, leg_off = torch.empty(n_groups + 1, dtype=torch.int64, device=dev), torch.empty(n_slots + 1, dtype=torch.int64, device=dev)
+    off_h = np.zeros(n_groups + 1, dtype=np.int64)
+    totals = [torch.empty(n_groups, dtype=torch.float64, device=dev) for _ in range(n_totals)]
+    status = torch.empty(n_groups, dtype=torch.int32, device=dev)
+    ctx.bind_stream()
+    L.check(counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), *[_ptr(t) for t in totals], _ptr(status)))
+    total = int(off_h[-1])
+    x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
+    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
+    leg = torch.empty(total, dtype=torch.int32, device=dev)
+    L.check(fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), _ptr(leg)))
+    return (off, off_h, x, y, h, kap, part, gear, leg, *totals, status, leg_off)
+
+
 def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None):
     """The path of EVERY field of a SwathSet in one pass on the device (fcpp_field_path_counts + fcpp_field_path_fill) -> FieldPaths.
     What swath_route gives for one field, for the whole batch and without a host loop: each swath sampled every `spacing` metres (its last
@@ -1807,18 +1826,7 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     ent, ext = _pose_columns(entry, n, dev), _pose_columns(exit, n, dev)
     args = (n, _ptr(ss.offsets), _host_ptr(soff_h), m, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(ss.length), _ptr(ss.angle), _ptr(order),
             _chord_radius(radius, spacing), 1 if reversing else 0, float(spacing), *[_ptr(t) for t in ent], *[_ptr(t) for t in ext])
-    off, leg_off = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(2 * m + n + 1, dtype=torch.int64, device=dev)
-    off_h = np.zeros(n + 1, dtype=np.int64)
-    work, transit = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    ctx.bind_stream()
-    L.check(ctx.lib.fcpp_field_path_counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), _ptr(work), _ptr(transit), _ptr(status)))
-    total = int(off_h[-1])
-    x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
-    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
-    leg = torch.empty(total, dtype=torch.int32, device=dev)
-    L.check(ctx.lib.fcpp_field_path_fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), _ptr(leg)))
-    return FieldPaths(off, off_h, x, y, h, kap, part, gear, leg, work, transit, status, leg_off)
+    return FieldPaths(*_leg_paths(ctx, ctx.lib.fcpp_field_path_counts, ctx.lib.fcpp_field_path_fill, args, n, 2 * m + n, 2, dev))
 
 
 # ---- headland paths (fcpp_headland_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------
@@ -1850,26 +1858,12 @@ class HeadlandPaths:
 
 def _headland_paths(ctx, ring_offsets, x, y, src, ring_dist, R, mode, spacing, direction, smooth_tol, ring_offsets_host=None):
     """the two C entries on device tensors; R as it is (no chord radius) -> the HeadlandPaths fields but ring_pair"""
-    torch = _torch()
     dev = x.device
     nr, nv = int(ring_offsets.numel()) - 1, int(x.numel())
     roff_h = None if ring_offsets_host is None else np.ascontiguousarray(ring_offsets_host, dtype=np.int64)
     args = (nr, _ptr(ring_offsets), _host_ptr(roff_h), nv, _ptr(x), _ptr(y), _ptr(src), _ptr(ring_dist), float(R), int(mode), float(spacing),
             int(direction), float(smooth_tol))
-    off, leg_off = torch.empty(nr + 1, dtype=torch.int64, device=dev), torch.empty(2 * nv + 1, dtype=torch.int64, device=dev)
-    off_h = np.zeros(nr + 1, dtype=np.int64)
-    work, transit, skipped = (torch.empty(nr, dtype=torch.float64, device=dev) for _ in range(3))
-    status = torch.empty(nr, dtype=torch.int32, device=dev)
-    ctx.bind_stream()
-    L.check(ctx.lib.fcpp_headland_path_counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), _ptr(work), _ptr(transit), _ptr(skipped),
-                                              _ptr(status)))
-    total = int(off_h[-1])
-    px, py, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
-    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
-    leg = torch.empty(total, dtype=torch.int32, device=dev)
-    L.check(ctx.lib.fcpp_headland_path_fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(px), _ptr(py), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear),
-                                            _ptr(leg)))
-    return off, off_h, px, py, h, kap, part, gear, leg, work, transit, skipped, status, leg_off
+    return _leg_paths(ctx, ctx.lib.fcpp_headland_path_counts, ctx.lib.fcpp_headland_path_fill, args, nr, 2 * nv, 3, dev)
 
 
 def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_tol=1e-6, device=None):

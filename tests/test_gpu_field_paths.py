@@ -1,4 +1,4 @@
-"""GPU tests of the field paths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_fpath.hip against the same rule on the host
+"""GPU tests of the field paths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_legs.hip against the same rule on the host
 (fcpp_debug_field_paths) BIT FOR BIT on every output -- the rule is one set of host+device expressions, so nothing here is compared to a
 bound; then against the parent's per-field path, swath_route, through the project's own operators; the existing path operators fed the
 whole batch in one call each; plan_polygon_fields against the stage-by-stage calls; and the two device entries through the guarded arena.
@@ -20,6 +20,7 @@ from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
 from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES, host_paths, stored_order, wrap_diff
 from tests.test_gpu_route import W, batch, field_poses
+from tests import test_leg_paths_pinned as PIN
 from tests.test_guarded_host import strip
 from tests.test_route_host import HOLED_SQUARE, R, bits, cut_with_angle
 from tests.test_swaths_host import ELL, HOLE
@@ -94,6 +95,22 @@ def test_device_equals_host_bit_for_bit(reference, routes, n, mode, routed, ends
         if mode:
             assert (host['gear'] == -1).any() or n == 1
         assert set(np.unique(host['part']).tolist()) == ({0, 1, 2, 3} if ends else {0, 1})
+
+
+@pytest.mark.parametrize('name', PIN.FIELD_NAMES)
+def test_device_gives_the_recorded_field_paths(name):
+    """the device entries on the cases of tests/test_leg_paths_pinned.py against the recording: the per-field and per-slot arrays byte for
+    byte, the seven sample columns by their SHA-256"""
+    import torch
+    cut, kw = PIN.field_cases()[name]
+    dev = torch.device('cuda', E.get_context(None).device)
+    t = {k: torch.as_tensor(np.array(cut[k]), device=dev) for k in ('offsets', 'a', 'b', 'line', 'length', 'angle')}
+    ss = E.SwathSet(t['offsets'], cut['offsets'], t['a'], t['b'], t['line'], t['length'], None, None, t['angle'])
+    fp = E.field_paths(ss, R, kw['spacing'], reversing=bool(kw['mode']), order=kw['order'], entry=kw['entry'], exit=kw['exit'])
+    got = {k: _np(getattr(fp, DEV_NAMES[k])) for k in FIELD_KEYS}
+    got.update({k: _np(getattr(fp, k)) for k in SAMPLE_KEYS})
+    PIN.assert_pinned(name, got, PIN.FIELD_FULL, PIN.DIGESTS)
+    assert np.array_equal(fp.offsets_host, got['offsets'])
 
 
 def test_failed_fields_on_the_device(reference):

@@ -1,4 +1,4 @@
-"""GPU tests of the headland paths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_hpath.hip against the same rule on the host
+"""GPU tests of the headland paths (run with -m gpu on an MI355X): the kernels of csrc/fcpp_legs.hip against the same rule on the host
 (fcpp_debug_headland_paths) BIT FOR BIT on every output -- the rule is one set of host+device expressions, so nothing here is compared to a
 bound; the failed rings and the 40 000-ring batch of tests/test_headland_paths_host.py on the device; the existing path operators fed all
 loops in one call each; plan_polygon_fields(headland_paths=True) against the stage-by-stage calls; and the two device entries through the
@@ -18,6 +18,7 @@ from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES
 from tests.test_headland_paths_host import (DISTS, FAILED, FAILED_STATUS, R_BRIDGE, R_FOLLOW, RING_KEYS, batch, batch_rings, host_hpaths, many_rectangles,
                                             raw_rings)
 from tests.test_swaths_host import ELL, HOLE
+from tests import test_leg_paths_pinned as PIN
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +72,16 @@ def test_device_equals_host_bit_for_bit(n, radius, mode, direction):
         assert_equals_host(got, host)
         if n == 65:
             assert set(np.unique(host['part']).tolist()) == {0, 1, 4} and ((host['gear'] == -1).any() == bool(mode))
+
+
+@pytest.mark.parametrize('name', PIN.RING_NAMES)
+def test_device_gives_the_recorded_headland_paths(name):
+    """the device entries on the cases of tests/test_leg_paths_pinned.py against the recording: the per-ring and per-slot arrays byte for
+    byte, the seven sample columns by their SHA-256"""
+    rg, kw = PIN.headland_cases()[name]
+    got = device_hpaths(rg, kw['radius'], kw['mode'], kw['spacing'], kw['direction'])
+    PIN.assert_pinned(name, got, PIN.RING_FULL, PIN.DIGESTS)
+    assert np.array_equal(got['offsets_host'], got['offsets'])
 
 
 def test_no_rings_at_all():
