@@ -214,6 +214,7 @@ PROTOTYPES = [
     ('fcpp_debug_polygon_cover', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int64, _VP, C.c_int64]
      + [_VP] * 8 + [C.c_int64] + [_VP] * 3),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
+    ('fcpp_ctx_direct_steps', C.c_int, [_VP, c_i64_p, c_i64_p, c_i64_p]),
 ]
 
 _lib = None

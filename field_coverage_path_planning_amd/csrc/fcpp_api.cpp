@@ -130,6 +130,13 @@ struct fcpp_batch {
         if (e == hipSuccess) setup_seen.push_back(s);
         return e;
     }
+    // fcpp_batch_plan ran this batch's step directly off the counting pass of its setup (fcpp_devplan.h: DevTileConsts.direct) and enqueued no
+    // fill pass: the tables are filled when somebody asks for them (ensure_tables) or when another setup takes the plan slot whose scratch
+    // they are filled from (plan_scratch) -- the unchanged fill pass with its publisher off, on the setup's stream
+    bool tables_pending = false;
+    int tables_slot = -1;
+    fcpp::DevTileConsts tables_tc;
+    fcpp::DevPlanScratch tables_scratch;
     ~fcpp_batch() { for (hipEvent_t e : events) (void)hipEventDestroy(e); if (ev_setup) (void)hipEventDestroy(ev_setup); }
 };
 
@@ -592,6 +599,16 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 }
 
 namespace {
+// What fcpp_batch_plan hands down to the device setup: outputs are wanted.  A speculative setup without obstacle polygons then sizes the output
+// arrays from the early point total, while the counting pass runs, and enqueues the step right behind that pass (DevTileConsts.direct).
+struct PlanOutputs {
+    fcpp_field_stats *stats = nullptr;      // the caller's records; null: the batch's own
+    double *x = nullptr, *y = nullptr, *kappa = nullptr, *v = nullptr;
+    uint32_t *fs = nullptr;
+    int64_t points = 0;                     // what the arrays were sized for
+    bool allocated = false;                 // the arrays are there
+    bool stepped = false;                   // ... and the direct step has written them and the statistics: no fcpp_batch_run
+};
 thread_local double g_trace_totals_ms = 0.0;      // (FCPP_TRACE_PLAN: when the last device setup saw its totals, ms since try_device_setup began)
 constexpr int kNotOnDevice = 1;      // try_device_setup: this batch is the host's (reason in err)
 
@@ -643,6 +660,32 @@ bool set_batch_consts(fcpp_batch *b, const TemplateSet &ts)
     return ts.tt.nu >= 3 && closed_form_turns(b->veh, ts.tt, ts.h_tu, ts.h_dk, b->cst);
 }
 
+// The fill pass a direct setup left out, on the setup's stream (behind the step): from the plan slot's scratch, which nobody has touched
+// since -- counts, kept rows and the setup's buffer of aggregates are as the counting pass left them.  Does nothing for any other batch.
+// `now`: the stream of the call that asks.  A setup stream the caller has destroyed since (as ev_plan and wait_setup allow for): whatever ran
+// there is drained with the device, and the fill pass goes to `now`, which becomes the batch's setup stream.
+int flush_tables(fcpp_batch *b, hipStream_t now, std::string &err)
+{
+    if (!b->tables_pending) return FCPP_OK;
+    fcpp_ctx *c = b->ctx;
+    b->tables_pending = false;
+    fcpp_ctx::PlanSlot *sl = b->tables_slot >= 0 ? &c->plan_slots[b->tables_slot] : nullptr;
+    if (sl && sl->tables_batch == b) sl->tables_batch = nullptr;
+    b->cst.field_junc = b->t.field_junc;
+    ++c->direct_fills;
+    int frc = launch_devplan_fill(b->setup_stream, b->n_fields, b->tables_tc, b->cst, b->tables_scratch, b->t, nullptr);
+    if (frc && now != b->setup_stream) {
+        (void)hipGetLastError();
+        if (hipDeviceSynchronize() != hipSuccess) { err = "the device after a batch's setup stream was destroyed"; return FCPP_EHIP; }
+        if (sl && sl->stream == b->setup_stream) sl->stream = now;
+        b->setup_stream = now; b->setup_seen.clear();
+        b->note_stream(now);
+        frc = launch_devplan_fill(now, b->n_fields, b->tables_tc, b->cst, b->tables_scratch, b->t, nullptr);
+    }
+    if (frc) { err = std::string("launch_devplan_fill: ") + hipGetErrorString((hipError_t)frc); return FCPP_EHIP; }
+    return FCPP_OK;
+}
+
 // the context's planner scratch for n fields (grow-only), ordered behind the last fill pass that read it
 int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, DevPlanScratch &s, std::string &err)
 {
@@ -652,6 +695,8 @@ int plan_scratch(fcpp_ctx *c, int64_t n_fields, int max_prims, hipStream_t st, D
     if (k < 0) for (int i = 0; i < fcpp_ctx::kPlanSlots; ++i) if (!c->plan_slots[i].p) { k = i; break; }
     if (k < 0) { k = 0; for (int i = 1; i < fcpp_ctx::kPlanSlots; ++i) if (c->plan_slots[i].tick < c->plan_slots[k].tick) k = i; }
     fcpp_ctx::PlanSlot &sl = c->plan_slots[k];
+    // (a batch whose tables are still to be filled from this slot's scratch: its fill pass goes first, on the stream of its setup)
+    if (sl.tables_batch) { const int frc = flush_tables(sl.tables_batch, st, err); if (frc != FCPP_OK) return frc; }
     if (sl.pending && sl.stream != st) {       // (that batch's fill pass, on another stream, may still read the scratch)
         if (!c->ev_plan) DEVCHK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming));
         if (hipEventRecord(c->ev_plan, sl.stream) == hipSuccess) DEVCHK(hipStreamWaitEvent(st, c->ev_plan, 0));
@@ -725,7 +770,7 @@ DevTileConsts dev_tile_consts(const BatchTileConsts &k, const fcpp_batch &b, int
     tc.nu = k.nu; tc.nc = k.nc; tc.turn_quiet = k.turn_quiet; tc.fuse_spans = k.fuse_spans; tc.span_line_max = k.span_line_max;
     tc.two_a = k.two_a; tc.u_cap = k.u_cap; tc.c_line = k.c_line; tc.fence_margin = k.fence_margin;
     tc.wave_factor = k.wave_factor; tc.field_work_tiles = FIELD_WORK_TILES; tc.reduce_wg_max = TileConsts::reduce_wg_max; tc.max_prims = max_prims;
-    tc.no_bases = 0; tc.speculative = 0; tc.closed_cut = dense ? 0 : 1; tc.dense = dense ? 1 : 0;
+    tc.no_bases = 0; tc.speculative = 0; tc.closed_cut = dense ? 0 : 1; tc.dense = dense ? 1 : 0; tc.direct = 0;
     tc.gen = gen;
     tc.cut = make_cut_consts(*b.templates, true, k, b.cst);
     return tc;
@@ -826,7 +871,7 @@ int await_totals(const int64_t *tot, int64_t gen, hipStream_t st, std::chrono::s
 // fresh_templates: the batch's template set is still on its way back from the device (cleared once this path has waited for it);
 // field_work, span_line_max: the batch's reference switches (fcpp_batch_create)
 int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_field *fields, const fcpp_polys *obstacles, bool &fresh_templates,
-                     bool field_work, int64_t span_line_max, std::string &err)
+                     bool field_work, int64_t span_line_max, std::string &err, PlanOutputs *po)
 {
     const fcpp_options &opt = b->opt;
     fcpp_setup_times &tm = b->setup;
@@ -876,6 +921,12 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
     }
     tc.speculative = spec ? 1 : 0;
     fcpp_ctx::PlanSlot &slot = c->plan_slots[c->plan_cur];
+    // the direct step (fcpp_batch_plan, no obstacle polygons; FCPP_DIRECT=0, read per call, switches it off: the checker of
+    // tests/test_gpu_direct_step.py) -- attempted while the context's last speculative setup qualified for it
+    const char *e_direct = getenv("FCPP_DIRECT");
+    const bool no_polys = !obstacles || obstacles->n_polys == 0;
+    const bool direct = po && spec && no_polys && tc.fuse_spans && c->direct_ok && !(e_direct && atoi(e_direct) == 0);
+    if (direct) tc.direct = DIRECT_COUNT;
     if (spec) {
         if ((rc = take_slab(c, b, err)) != FCPP_OK) return rc;
         if ((rc = bind_and_upload_obstacles(c, b, obstacles, st, err)) != FCPP_OK) return rc;
@@ -889,9 +940,36 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         slot.agg_dirty = true;
     }
     // ---- plan and count, and the speculative fill pass right behind them (it publishes the totals: no scan in between)
-    const int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, obstacles ? obstacles->n_polys : 0, obstacles != nullptr, c->plan_totals_host);
+    const int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, obstacles ? obstacles->n_polys : 0, obstacles != nullptr, c->plan_totals_host,
+                                         direct ? &b->cst : nullptr);
     if (lrc) { (void)hipStreamSynchronize(st); err = std::string("launch_devplan_count: ") + hipGetErrorString((hipError_t)lrc); return FCPP_EHIP; }   // (drained: the caller's pinned records may still be read)
-    if (spec && (rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    // ---- direct: the point total is final once the planner has run -- the counting launch's first workgroup writes it; the output arrays are
+    // allocated and the step enqueued while the counting pass runs.  The step applies the batch rule itself and publishes the totals.
+    bool direct_step = false;
+    if (direct) {
+        const volatile int64_t *early = tot + PX_EARLY_GEN;
+        const auto t_poll = std::chrono::steady_clock::now();
+        bool seen = false;
+        for (int spin = 0; !seen; ++spin) {
+            seen = *early == tc.gen;
+            if (!seen && (spin & 1023) == 1023 && ms_since(t_poll) > 2.0) break;
+        }
+        if (!seen) DEVCHK(hipStreamSynchronize(st));
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const int64_t points = tot[PX_EARLY_POINTS];
+        // (a total beyond the limits, or no room for the arrays: the setup goes on as without the direct step and reports what it finds)
+        if (*early == tc.gen && points >= 0 && points <= kCountCap &&
+            fcpp_outputs_alloc(c, points, 0, &po->x, &po->y, &po->kappa, &po->v, &po->fs) == FCPP_OK) {
+            po->allocated = true; po->points = points;
+            const int drc = launch_plan_sparse_direct(st, n_fields, tc.gen, s, b->cst, po->x, po->y, po->kappa, po->v, po->fs,
+                                                      po->stats ? po->stats : b->t.own_stats, c->plan_totals_host);
+            if (drc) { (void)hipStreamSynchronize(st); err = std::string("launch_plan_sparse_direct: ") + hipGetErrorString((hipError_t)drc); return FCPP_EHIP; }
+            direct_step = true;
+            ++c->direct_steps;
+        }
+        tc.direct = direct_step ? DIRECT_FILL : 0;      // (a fill pass behind the step has no publisher)
+    }
+    if (spec && !direct_step && (rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) { (void)hipStreamSynchronize(st); return rc; }
     if (spec) slot.agg_dirty = false;
     // ---- wait for the totals, checks
     rc = await_totals(tot, tc.gen, st, t_call, err);
@@ -903,7 +981,16 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
     // sampling, a third of its spans fusable, 0.0435 instead of 0.0392 ms)
     t0 = std::chrono::steady_clock::now();
     const bool fuse = tc.fuse_spans && tot[PC_UNFUSABLE] == 0 && tot[PC_WORK_SPAN_PTS] > 0;
-    if (spec && tot[PC_COLS + PF_OVER_CAPACITY] != tc.gen) {
+    const bool within = spec && tot[PC_COLS + PF_OVER_CAPACITY] != tc.gen;
+    // the batch rule of the direct step, as its workgroups applied it: every field a field of field work, every span fused, no flag up
+    const bool qualifies = within && fuse && tot[PC_WORK] == n_fields && no_polys;
+    if (spec) c->direct_ok = qualifies;
+    bool taken = false;
+    if (direct_step) {
+        if (qualifies && tot[PC_POINTS] == po->points) taken = true;      // the batch is done: no fill pass until somebody asks for the tables
+        else if (within && (rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) return rc;      // declined: the fill pass, its publisher off
+    }
+    if (within) {
         counts_from_totals(lay, tot, fuse);  // (the tables begin where the capacities put them; what they hold is what the totals say)
         tm.image_ms = ms_since(t0);
     } else {
@@ -923,13 +1010,19 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
         t0 = std::chrono::steady_clock::now();
         // (after a speculative counting phase no scan has run: the pass wrote every column, the scan makes the positions of the exact layout)
         if (spec) { const int src = launch_devplan_rescan(st, n_fields, s); if (src) { err = std::string("launch_devplan_rescan: ") + hipGetErrorString((hipError_t)src); return FCPP_EHIP; } }
-        tc.speculative = 0;
+        tc.speculative = 0; tc.direct = 0;
         tc.fuse_spans = fuse;
         if ((rc = enqueue_fill(b, st, tc, s, err)) != FCPP_OK) return rc;
     }
     tm.image_bytes = (int64_t)((size_t)n_fields * sizeof(fcpp_field) + (lay.n_polys > 0 ? lay.seg - lay.obs_off : 0));
     c->plan_slots[c->plan_cur].pending = true;
     b->setup_stream = st; b->setup_pending = true;
+    if (taken) {
+        b->tables_pending = true; b->tables_slot = c->plan_cur; b->tables_tc = tc; b->tables_scratch = s;
+        slot.tables_batch = b;
+        po->stepped = true;
+        ++c->direct_taken;
+    }
     // fcpp_field_info stays on the device until somebody asks (fcpp_batch_info); the stream is NOT drained: a step enqueued next runs
     // right behind the setup
     b->info_dev = b->t.info;
@@ -945,8 +1038,9 @@ int try_device_setup(fcpp_ctx *c, fcpp_batch *b, int64_t n_fields, const fcpp_fi
 #undef DEVCHK
 }  // namespace
 
-int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *opt, int64_t n_fields,
-                      const fcpp_field *fields, const fcpp_polys *obstacles, fcpp_batch **out)
+// fcpp_batch_create; po: fcpp_batch_plan wants outputs (PlanOutputs), else null
+static int batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *opt, int64_t n_fields,
+                        const fcpp_field *fields, const fcpp_polys *obstacles, fcpp_batch **out, PlanOutputs *po)
 {
     if (!c || !veh || !opt || !out || n_fields < 0 || (n_fields > 0 && !fields))
         return fail(FCPP_EINVAL, "bad arguments");
@@ -985,7 +1079,7 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     // function the host would run (fcpp_planfn.h) runs one thread per field, the tiler's cut one wavefront per field, the totals come
     // back once (they size the tables and the output arrays), the tables are written in place.  The host plans nothing per field.
     {
-        int rc = try_device_setup(c, b.get(), n_fields, fields, obstacles, fresh, field_work, span_line_max, err);
+        int rc = try_device_setup(c, b.get(), n_fields, fields, obstacles, fresh, field_work, span_line_max, err, po);
         if (rc == FCPP_OK) {
             tm.total_ms = ms_since(t_begin);
             c->last_setup = tm;
@@ -1084,15 +1178,43 @@ int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *
     return FCPP_OK;
 }
 
+// the tables of a batch whose step ran directly (fcpp_batch::tables_pending): every entry that reads b->t beyond own_stats calls this first
+static int ensure_tables(fcpp_batch *b)
+{
+    if (!b->tables_pending) return FCPP_OK;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    std::string err;
+    const int rc = flush_tables(b, b->ctx->stream, err);
+    return rc == FCPP_OK ? FCPP_OK : fail(rc, err);
+}
+
+int fcpp_batch_create(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *opt, int64_t n_fields,
+                      const fcpp_field *fields, const fcpp_polys *obstacles, fcpp_batch **out)
+{
+    return batch_create(c, veh, opt, n_fields, fields, obstacles, out, nullptr);
+}
+
 // fcpp_field_info of a batch set up on the device: copied back when first needed
 static int ensure_info(fcpp_batch *b)
 {
     if (!b->info_dev || !b->hp.info.empty() || b->n_fields == 0) return FCPP_OK;
     HIPCHK(hipSetDevice(b->ctx->device));
+    { const int rc = ensure_tables(b); if (rc) return rc; }
     try { b->hp.info.resize((size_t)b->n_fields); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
     for (hipStream_t s : b->used_streams) HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipMemcpy(b->hp.info.data(), b->info_dev, (size_t)b->n_fields * sizeof(fcpp_field_info), hipMemcpyDeviceToHost));
     return FCPP_OK;
+}
+
+// output arrays from the context's arena: their block remembers the stream that writes it (fcpp_outputs_free)
+static void note_arena_writer(fcpp_ctx *c, const double *x, hipStream_t st)
+{
+    if (!c->arena || !x) return;
+    const char *p = reinterpret_cast<const char *>(x), *a0 = static_cast<const char *>(c->arena);
+    if (p >= a0 && p < a0 + c->arena_lane) {
+        const size_t off = (size_t)(p - a0);
+        for (auto &blk : c->arena_live) if (off >= blk.off && off < blk.off + blk.len) { blk.last = st; blk.used = true; break; }
+    }
 }
 
 int fcpp_batch_setup_times(const fcpp_batch *b, fcpp_setup_times *out)
@@ -1126,14 +1248,9 @@ int fcpp_batch_run(fcpp_batch *b, double *x, double *y, double *kappa, double *v
     HIPCHK(hipSetDevice(b->ctx->device));
     hipStream_t st = b->ctx->stream;
     b->note_stream(st);
+    { const int rc = ensure_tables(b); if (rc) return rc; }
     HIPCHK(b->wait_setup(st));
-    if (fcpp_ctx *c = b->ctx; c->arena && x) {      // output arrays from the context's arena: their block remembers the stream that writes it (fcpp_outputs_free)
-        const char *p = reinterpret_cast<const char *>(x), *a0 = static_cast<const char *>(c->arena);
-        if (p >= a0 && p < a0 + c->arena_lane) {
-            const size_t off = (size_t)(p - a0);
-            for (auto &blk : c->arena_live) if (off >= blk.off && off < blk.off + blk.len) { blk.last = st; blk.used = true; break; }
-        }
-    }
+    note_arena_writer(b->ctx, x, st);
     if (mode == 0 && !b->til0_built) {      // the staged pipeline's own tiling: plain tiles of at most TILE_POINTS points
         { const int rc = ensure_info(b); if (rc) return rc; }
         Tiling t0;
@@ -1246,13 +1363,27 @@ int fcpp_batch_plan(fcpp_ctx *c, const fcpp_vehicle *veh, const fcpp_options *op
     fcpp_batch *b = nullptr;
     static const bool trace = getenv("FCPP_TRACE_PLAN") != nullptr;      // (diagnostic: the host's side of a plan call, microseconds since its start, to stderr)
     const auto t_begin = std::chrono::steady_clock::now();
-    int rc = fcpp_batch_create(c, veh, opt, n_fields, fields, obstacles, &b);
+    // (outputs are wanted: a speculative device setup may allocate the arrays itself, from the early point total, and run the step directly
+    // behind its counting pass -- try_device_setup)
+    PlanOutputs po;
+    po.stats = stats;
+    int rc = batch_create(c, veh, opt, n_fields, fields, obstacles, &b, &po);
+    if (rc != FCPP_OK || (po.allocated && po.points != b->hp.total_points)) {       // (the arrays of a setup that did not end as it began)
+        if (po.allocated) { const std::string keep = g_err; (void)hipStreamSynchronize(c->stream); (void)fcpp_outputs_free(c, po.x); g_err = keep; }
+        po.allocated = false;
+    }
     if (rc != FCPP_OK) return rc;
     const double t_create = trace ? ms_since(t_begin) : 0.0;
     const int64_t total = b->hp.total_points;
-    rc = fcpp_outputs_alloc(c, total, 0, x, y, kappa, v, fs);
+    if (po.allocated) { *x = po.x; *y = po.y; *kappa = po.kappa; *v = po.v; *fs = po.fs; }
+    else rc = fcpp_outputs_alloc(c, total, 0, x, y, kappa, v, fs);
     const double t_alloc = trace ? ms_since(t_begin) : 0.0;
-    if (rc == FCPP_OK) {
+    if (rc == FCPP_OK && po.stepped) {
+        // the step has run: what fcpp_batch_run notes besides its launches (the batch's stream was noted at creation)
+        b->last_mode = 1;
+        note_arena_writer(c, *x, c->stream);
+        if (trace) fprintf(stderr, "[fcpp] plan call, direct step: totals seen %.1f us, create returns %.1f\n", g_trace_totals_ms * 1e3, t_create * 1e3);
+    } else if (rc == FCPP_OK) {
         if (!stats) stats = b->t.own_stats;
         rc = fcpp_batch_run(b, *x, *y, *kappa, *v, *fs, stats, 1);
         if (trace) fprintf(stderr, "[fcpp] plan call: entered at %.1f us (CLOCK_MONOTONIC mod 1 s), totals seen %.1f us, create returns %.1f, arrays %.1f, step enqueued %.1f\n",
@@ -1355,6 +1486,7 @@ int fcpp_batch_connectors(fcpp_batch *b, double *approach_xy, double *departure_
     HIPCHK(hipSetDevice(b->ctx->device));
     hipStream_t st = b->ctx->stream;
     b->note_stream(st);
+    { const int rc = ensure_tables(b); if (rc) return rc; }
     HIPCHK(b->wait_setup(st));
     if (approach_xy) LAUNCHCHK(launch_straight(st, b->n_fields, b->t.seg, 50, b->t.seg_mask, approach_xy));
     if (departure_xy)
@@ -1367,6 +1499,10 @@ int fcpp_batch_destroy(fcpp_batch *b)
     if (!b) return FCPP_OK;
     fcpp_ctx *c = b->ctx;
     (void)hipSetDevice(c->device);
+    if (b->tables_pending) {      // (a fill pass nobody asked for is dropped, not run)
+        b->tables_pending = false;
+        if (b->tables_slot >= 0 && c->plan_slots[b->tables_slot].tables_batch == b) c->plan_slots[b->tables_slot].tables_batch = nullptr;
+    }
     // (the tables may become the next batch's: nothing that reads them may still be running -- on whichever streams this batch ran)
     // (every stream the batch was created, stepped or read on is noted in used_streams; the context's CURRENT stream is not drained for its own
     // sake: it may be another batch's -- a caller with two plan calls in flight on two streams would wait for the other call's step here)
@@ -1708,6 +1844,15 @@ int fcpp_debug_rs(int64_t n, const double *fx, const double *fy, const double *f
     return debug_conn<1>(n, fx, fy, fh, tx, ty, th, radius, word, seg, len);
 }
 
+int fcpp_ctx_direct_steps(const fcpp_ctx *c, int64_t *launched, int64_t *taken, int64_t *fills)
+{
+    if (!c) return fail(FCPP_EINVAL, "ctx is NULL");
+    if (launched) *launched = c->direct_steps;
+    if (taken) *taken = c->direct_taken;
+    if (fills) *fills = c->direct_fills;
+    return FCPP_OK;
+}
+
 int fcpp_batch_debug_table(const fcpp_batch *b, int table, void *dst, int64_t cap, int64_t *bytes_out)
 {
     if (!b || !bytes_out) return fail(FCPP_EINVAL, "bad arguments");
@@ -1722,6 +1867,7 @@ int fcpp_batch_debug_table(const fcpp_batch *b, int table, void *dst, int64_t ca
     if (cap < (int64_t)sp.bytes) return fail(FCPP_ESIZE, "buffer too small");
     if (sp.bytes == 0 || b->lay.n_fields == 0) return FCPP_OK;
     HIPCHK(hipSetDevice(b->ctx->device));
+    { const int rc = ensure_tables(const_cast<fcpp_batch *>(b)); if (rc) return rc; }
     for (hipStream_t s : b->used_streams) HIPCHK(hipStreamSynchronize(s));          // (the setup's stream is one of them)
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
     HIPCHK(hipMemcpy(dst, static_cast<const unsigned char *>(b->slab) + sp.off, sp.bytes, hipMemcpyDeviceToHost));

@@ -147,7 +147,10 @@ struct fcpp_ctx {
     // still runs on the first -- the sustained rate of bench.py -- must not wait for that step because its fill pass shared the scratch)
     // (agg_flip: which of the slot's two buffers of aggregates the next speculative setup accumulates into -- DevPlanScratch.agg; agg_dirty: a
     // speculative setup ended between its planner and its fill pass, which would have zeroed the other buffer: both are cleared before the next)
-    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; int agg_flip = 0; bool agg_dirty = false; };
+    // (tables_batch: the batch whose step ran directly off the slot's counting pass and whose tables are still to be filled from the slot's scratch
+    // -- fcpp_batch::tables_pending; whoever takes the slot next enqueues that fill pass first: plan_scratch)
+    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; int agg_flip = 0; bool agg_dirty = false;
+                      fcpp_batch *tables_batch = nullptr; };
     static constexpr int kPlanSlots = 4;
     PlanSlot plan_slots[kPlanSlots];
     uint64_t plan_tick = 0;
@@ -157,6 +160,10 @@ struct fcpp_ctx {
     int64_t *plan_totals_host = nullptr;            // pinned, PC_COLS + PF_COUNT values: the scans of the counting phase write them here
     unsigned long long *ga_mirror = nullptr;        // pinned, one word: (converged << 32) | generations of the running fcpp_ga_evolve (GaState::mirror)
     int64_t plan_gen = 0;                           // generation number of the last counting phase (PlanFlag, fcpp_devplan.h)
+    // fcpp_batch_plan's direct step (fcpp_devplan.h: DevTileConsts.direct) is attempted while the last speculative setup's batch qualified for it
+    // (or there was none): a caller of batches that do not -- mixed classes, unfusable spans -- pays the empty launch once, not per call
+    bool direct_ok = true;
+    int64_t direct_steps = 0, direct_taken = 0, direct_fills = 0;      // launched / batches taken / their fill passes enqueued later (fcpp_ctx_direct_steps: tests)
     // the stream the last device-side setup was enqueued on (its fill pass may still read the scratch): a setup on ANOTHER stream records
     // ev_plan there and waits for it -- lazily, when that other stream shows up: an event recorded between two kernels of the plan call
     // costs 5 us of device time between them (round 5: the three records of a plan call were 16 of its 158 us)

@@ -46,7 +46,10 @@ enum PlanFlag : int { PF_FALLBACK = 0, PF_BAD_OBSTACLES = 1, PF_OVER_CAPACITY = 
 // generation number of the phase whose totals are complete -- written to the host's copy by the last column to arrive: the host polls it
 // (a word in its own pinned memory) instead of waiting for an event
 static_assert(PC_COLS <= OFF_ROW, "a block's row of aggregates holds every column");
-constexpr int PX_ARRIVED = PC_COLS + PF_COUNT, PX_DONE = PC_COLS + PF_COUNT + 1, PLAN_TOTALS = PC_COLS + PF_COUNT + 2;
+constexpr int PX_ARRIVED = PC_COLS + PF_COUNT, PX_DONE = PC_COLS + PF_COUNT + 1;
+// behind PX_DONE, the host's copy only: a direct setup's counting launch (DevTileConsts.direct) writes the batch's point total -- the planner's
+// aggregates, complete before the pass begins -- and then its generation number: the host sizes the output arrays while the pass runs
+constexpr int PX_EARLY_POINTS = PC_COLS + PF_COUNT + 2, PX_EARLY_GEN = PC_COLS + PF_COUNT + 3, PLAN_TOTALS = PC_COLS + PF_COUNT + 4;
 // (PF_OVER_CAPACITY: a speculative setup -- tables laid out by per-field capacities, the fill pass enqueued before the host has the totals
 // -- met a field beyond them: SPEC_* below; the host then lays the tables out from the totals and fills them again)
 constexpr int SPEC_SPAN_CHUNKS = 16;         // span chunks per field a speculative layout has room for (tiles: 1 + DEVPLAN_KEEP_TILES, wave / general tiles: DEVPLAN_KEEP_TILES)
@@ -62,12 +65,18 @@ struct DevTileConsts {
                                   // their offsets from the two levels of fcpp_offsetfn.h (DevPlanScratch.agg), the fill pass publishes the totals
     int32_t closed_cut;           // the general stretches of fields with a closed-form span are cut in closed form (fcpp_cutfn.h); 0: by the window cut of round 4
     int32_t dense;                // sample_spacing > 0: span of all complete passes + quiet runs of the straights + general tiles between them (k_tile_fields, "dense")
+    int32_t direct;               // speculative setups of fcpp_batch_plan.  DIRECT_COUNT, counting pass: every field of field work with a fusable span gets
+                                  // its pack and its run totals in the scratch (DevPlanScratch.direct_packs / direct_totals), the step is launched
+                                  // from them (launch_plan_sparse_direct) and publishes the totals; one workgroup more writes PX_EARLY_POINTS.
+                                  // DIRECT_FILL, fill pass: the totals were published by that step -- no publisher workgroup
     int64_t span_line_max;        // TileConsts.span_line_max
     double two_a, u_cap, c_line, fence_margin;
     int64_t reduce_wg_max;
     int64_t gen;                  // this counting phase's generation number (> 0)
     CutConsts cut;                // the closed-form cut (fcpp_cutfn.h), templates and chord tables on the device
 };
+
+enum : int32_t { DIRECT_COUNT = 1, DIRECT_FILL = 2 };
 
 // the device planner's scratch: one allocation the context keeps (grow-only); all pointers device
 struct DevPlanScratch {
@@ -87,6 +96,11 @@ struct DevPlanScratch {
     // copies and rebases them instead of cutting the field again (fields with more are cut again)
     DevTile *keep_tiles;          // n x DEVPLAN_KEEP_ROWS
     DevWaveTile *keep_wtiles;     // n x DEVPLAN_KEEP_WROWS
+    // direct setups (DevTileConsts.direct), indexed by field: the pack of a field of field work with a fusable span as the fill pass would lay it
+    // out (positions the step never reads stay relative to the field; work.n_tiles = -1: not such a field) and its work_totals record
+    DevFieldPack *direct_packs;   // n (batches of at most OFF_FIELDS_MAX fields)
+    TilePartial *direct_totals;   // n
+    double2 *direct_junc;         // n: the field's junction after a U-turn (the step's DevConst.field_junc: the batch's own table is the fill pass's)
 };
 int64_t devplan_small_blocks();
 // the scratch for n fields laid out at `base` (null: sizing only); returns its size in bytes
@@ -112,8 +126,9 @@ static_assert(sizeof(DevWaveTile) == 64, "a row of the kept wave tiles holds the
 // tc.speculative (at most OFF_FIELDS_MAX fields, reference sampling): planner and counting pass only -- the pass has the point offsets from
 // the planner's aggregates, writes every column and adds it to the aggregates; the totals are published by the speculative fill pass.
 // fields: the records as the device reaches them (s.fields_in after a copy, or the caller's pinned memory).
+// tc.direct (speculative, no obstacle polygons): cst = the batch's kernel constants (the span's closed-form statistics), see DevTileConsts.direct
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
-                         int64_t n_polys, int check_obstacles, int64_t *totals_host);
+                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst = nullptr);
 // (tc.dense: the counting pass needs the fields' point offsets -- the chunks of every quiet run lie on 512-point boundaries of the batch arrays --:
 // planner, scan of the points, pass, scan of the other columns)
 // sizing only (fcpp_plan_points): k_plan_fields without primitives; counts[PC_POINTS][field] = points of the field
@@ -126,5 +141,50 @@ int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, cons
 int launch_devplan_rescan(hipStream_t st, int64_t n, const DevPlanScratch &s);
 // fcpp_math.h on the device (tests): fn 0 sincos, 1 atan2(a, b), 2 acos(a), 3 hypot(a, b)
 int launch_debug_math(hipStream_t st, int fn, int64_t n, const double *a, const double *b, double *out0, double *out1);
+// the step of a direct setup (fcpp_sparse.hip): one workgroup per FIELD from s.direct_packs / s.direct_totals, enqueued right behind the counting
+// pass; every workgroup applies the batch rule to the aggregates' totals itself (no flag of generation `gen` up, every field a field of field
+// work, every span fusable) and returns when it fails; one workgroup more publishes the totals as the fill pass's publisher does
+int launch_plan_sparse_direct(hipStream_t st, int64_t n, int64_t gen, const DevPlanScratch &s, const DevConst &cst, double *x, double *y, double *kappa,
+                              double *v, uint32_t *fs, fcpp_field_stats *stats, int64_t *totals_host);
+
+#if defined(__HIPCC__)
+// a column's total to the host's copy; the flags (generation numbers, see PlanFlag) with the first column of the last scan
+__device__ __forceinline__ void publish_total(const int64_t *totals, int64_t *mirror, int col, int64_t value, bool flags)
+{
+    if (!mirror) return;
+    mirror[col] = value;
+    if (flags) for (int k = 0; k < PF_COUNT; ++k) mirror[PC_COLS + k] = totals[PC_COLS + k];
+}
+
+// The publisher of a speculative setup -- the first workgroup of its fill pass, or of its direct step: what the last scan of a counting phase
+// does for the host, without a scan.
+// Wavefront 0 sums every column's aggregates (total(col), fcpp_offsetfn.h) and writes the totals, the flags and then the phase's generation
+// number to the host's copy (await_totals polls that word) -- whatever the flags say: a pass they make a no-op is waited for as well.
+// Wavefront 1 zeroes the OTHER buffer of aggregates, the one the slot's next setup accumulates into (nothing of this setup reads or writes it).
+__device__ __forceinline__ void publish_two_level(int64_t n, int64_t gen, int64_t *__restrict__ totals, const int64_t *__restrict__ agg, int64_t *__restrict__ agg_next,
+                                                  int64_t *__restrict__ mirror, int wave, int lane)
+{
+    if (wave == 1) {
+        for (int k = lane; k < OFF_WORDS; k += 64) agg_next[k] = 0;
+        return;
+    }
+    if (wave != 0) return;
+    int64_t flag[PF_COUNT];
+#pragma unroll
+    for (int k = 0; k < PF_COUNT; ++k) flag[k] = totals[PC_COLS + k];
+    int64_t p0, p1, t0, t1;
+    offset_row_sums(agg, 0, (int)offset_blocks(n), lane, p0, p1, t0, t1);
+    // lane c: total(c) -- lane l holds the totals of columns 2 (l & 15) and 2 (l & 15) + 1; lanes PC_COLS + k: flag k
+    const int64_t other = __shfl(t1, lane >> 1), even = __shfl(t0, lane >> 1);
+    int64_t mine = (lane & 1) ? other : even;
+#pragma unroll
+    for (int k = 0; k < PF_COUNT; ++k) if (lane == PC_COLS + k) mine = flag[k];
+    if (lane < PC_COLS) { totals[lane] = mine; publish_total(totals, mirror, lane, mine, false); }
+    if (!mirror) return;
+    if (lane >= PC_COLS && lane < PC_COLS + PF_COUNT) mirror[lane] = mine;      // (the flags as loaded above, a lane each)
+    __threadfence_system();
+    if (lane == 0) reinterpret_cast<volatile int64_t *>(mirror)[PX_DONE] = gen;
+}
+#endif
 
 }  // namespace fcpp

@@ -20,6 +20,8 @@ size_t devplan_scratch_layout(int64_t n, int max_prims, void *base, DevPlanScrat
     take(s.fields_in, nn); take(s.info, nn); take(s.fields_tmp, nn); take(s.prims_tmp, nn * (size_t)max_prims);
     take(s.counts, nn * PC_COLS); take(s.bases, nn * PC_COLS); take(s.blk_sums, nblk * PC_COLS);
     take(s.keep_tiles, nn * DEVPLAN_KEEP_ROWS); take(s.keep_wtiles, nn * DEVPLAN_KEEP_WROWS);
+    const size_t nd = n <= OFF_FIELDS_MAX ? nn : 0;      // (direct setups: small batches only)
+    take(s.direct_packs, nd); take(s.direct_totals, nd); take(s.direct_junc, nd);
     return off;
 }
 
@@ -494,14 +496,7 @@ __global__ __launch_bounds__(64) void k_plan_fields16(int64_t n, PlanConsts pc, 
 #undef P16_FAIL
 }
 
-// a column's total to the host's copy; the flags (generation numbers, see PlanFlag) with the first column of the last scan
-__device__ __forceinline__ void publish_total(const int64_t *totals, int64_t *mirror, int col, int64_t value, bool flags)
-{
-    if (!mirror) return;
-    mirror[col] = value;
-    if (flags) for (int k = 0; k < PF_COUNT; ++k) mirror[PC_COLS + k] = totals[PC_COLS + k];
-}
-
+// (publish_total, a column's total to the host's copy: fcpp_devplan.h)
 // the last scan of a counting phase: a column's workgroup has published its total; the last one to arrive tells the host (PX_DONE)
 __device__ __forceinline__ void publish_done(int64_t *totals, int64_t *mirror, int n_cols, int64_t done_gen)
 {
@@ -770,7 +765,8 @@ __device__ __forceinline__ double2 field_junction(const DevField &F, const DevCo
 // DENSE: the instance for batches at dense sampling (the dense block and the window cut; no closed-form cut) -- an instance of its own so that
 // the sparse instances keep their registers (with the dense block compiled in, the counting pass of large batches went from 79 to 108
 // vector registers: four wavefronts per SIMD instead of six)
-template <bool FILL, bool STAGE, bool DENSE>
+// DIRECT: the counting pass of a direct setup (k_tile_fields_direct): write_direct below
+template <bool FILL, bool STAGE, bool DENSE, bool DIRECT>
 struct TilePass {
     // ---- the launch and the field
     const int64_t n;
@@ -812,6 +808,12 @@ struct TilePass {
     // number of primitives its points lie in (0: none of layer 2) -- what the field's pack takes (DevFieldPack)
     DevWaveTile my_wt;
     int my_p0_rel = 0, my_np = 0;
+    bool wt_in_lanes = false;            // (direct counting pass: the closed-form cut has left tile t in lane t; else the tiles are read back from the kept rows)
+    // direct counting pass: where the field's records go (set by tile_fields_body), and what of them the closed-form cut has already written
+    DevFieldPack *d_pack = nullptr;
+    TilePartial *d_total = nullptr;
+    double2 *d_junc = nullptr;
+    bool d_early = false;
     // fill pass: the words of the field's descriptor, its fcpp_field_info and its primitives, a word per lane and round
     static constexpr int NFW = (int)(sizeof(DevField) / 8), NIW = (int)(sizeof(fcpp_field_info) / 8), PWD = (int)(sizeof(DevPrim) / 8), PF_ROUNDS = 7;
     static_assert(sizeof(DevField) % 8 == 0 && sizeof(DevPrim) % 8 == 0 && sizeof(fcpp_field_info) % 8 == 0 && NFW <= 64 && NIW <= 64, "copied as 8-byte words, a lane each");
@@ -843,6 +845,8 @@ struct TilePass {
         if (two_level && !FILL) {
             // counting pass: the planner's aggregates of the points and the block's point counts are requested here and summed behind the cut
             pt_part = offset_prefix_part(agg, counts, n, PC_POINTS, field, lane);
+            // (direct: the descriptor's words for the field's pack, a lane each, on their way during the cut as well)
+            if (DIRECT && lane < NFW) fw = reinterpret_cast<const unsigned long long *>(&F)[lane];
         } else if (two_level) {
             // fill pass: ONE round of loads -- the flags, the blocks' rows of aggregates (every column's first level and total at once), and of the
             // field's own block the counts in front of it, a lane per field.  Within the capacities (no flag up: else the pass ends here) a field
@@ -1374,6 +1378,14 @@ struct TilePass {
         DevPrim q;
         memset(&q, 0, sizeof q);
         if (lane < prim_count) q = prims[lane];
+        // (direct: what of the field's records does not depend on the cut goes out here, while the loads above are on their way)
+        if (DIRECT) { write_direct_early(); d_early = true; }
+        if (DIRECT && lds_pack() && lane < prim_count) {          // (the pack's copies of the primitives come out of LDS: write_direct)
+            unsigned long long qw[PWD];
+            memcpy(qw, &q, sizeof q);
+#pragma unroll
+            for (int w = 0; w < PWD; ++w) L.prim_words[lane * PWD + w] = qw[w];
+        }
         TSTAMP(15);
         if (cut_staged) {
             if (lane < nt_all) L.cut_tmpl()[lane] = tp;
@@ -1451,7 +1463,9 @@ struct TilePass {
             DevWaveTile wt;
             tiler_wave_record(w, gen_main, n_main, n_total, [&](int k) -> int64_t { return n_main + L.pstart[k]; }, t, wt);
             keep_tiles[field * DEVPLAN_KEEP_ROWS + lane] = t; keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane] = wt;
+            if (DIRECT) my_wt = wt;
         }
+        if (DIRECT) wt_in_lanes = true;
         n_wave = nt; c_wave_pts = G; c_wave_inside = inside_cnt;
         TSTAMP(14);
     }
@@ -1538,6 +1552,85 @@ struct TilePass {
 #pragma unroll
         for (int k = 1; k < PC_COLS; ++k) if (lane == k) v = row[k];
         if (lane < PC_COLS) agg_add(agg, lane, field, v);
+    }
+
+    // ---- 7b. counting pass of a direct setup: what the step's workgroup reads of the field, in the scratch at the field's index -- its pack as
+    // fill_entries_and_lists / fill_pack lay it out and the work_totals record of fill_junction_and_slots.  Only where the points go in the
+    // batch arrays is batch-wide (the descriptor's pt_off, the tiles' out_base: the counting pass has the field's point offset); entries, wave
+    // tiles and primitives keep their indices within the field -- the step reads none of them.  A field the step cannot take (not of field
+    // work, or a span that cannot be fused): work.n_tiles = -1.
+    // the part that needs nothing of the cut: the descriptor with the field's point offset, the junction, the span's closed-form statistics
+    // summed as fill_junction_and_slots sums them (harmless for a field that turns out not to take a pack: nobody reads them)
+    __device__ __forceinline__ void write_direct_early()
+    {
+        const int64_t off = off_wave_sum(pt_part);
+        if (lane == (int)(offsetof(DevField, pt_off) / 8)) fw = (unsigned long long)off;
+        if (lane < NFW) reinterpret_cast<unsigned long long *>(&d_pack->field)[lane] = fw;
+        DevTile tl;
+        tl.field = (int32_t)field; tl.start = 0; tl.count = 0; tl.quiet = 4; tl.stat_tile = 0; tl.idx0 = 0; tl.off0 = 0;
+        const double2 junc = field_junction(F, cst);
+        TilePartial tp;
+        memset(&tp, 0, sizeof tp);
+        if (span_k > 0) tp = run_consts(F, junc, 0, S, tl, prims, cst);
+        if (lane == 0) {
+            *d_junc = junc;
+            TilePartial t;
+            memset(&t, 0, sizeof t);
+            if (span_k > 0) {
+                t.main_len += tp.main_len; t.main_time_pre += tp.main_time_pre; t.main_time += tp.main_time;
+                t.head_len += tp.head_len; t.head_time_pre += tp.head_time_pre; t.head_time += tp.head_time;
+                t.max_kappa = fmax(t.max_kappa, tp.max_kappa); t.max_alat = fmax(t.max_alat, tp.max_alat); t.max_jump = fmax(t.max_jump, tp.max_jump);
+                t.n_viol += tp.n_viol; t.n_adjusted += tp.n_adjusted;
+            }
+            *d_total = t;
+        }
+    }
+    // (every field of field work gets a pack, as from the fill pass: one WITHOUT a span -- a single pass, or passes that form none -- with
+    // span_points = 0 and zero run totals; one whose span cannot be fused fails the batch rule for everybody and needs none)
+    __device__ __forceinline__ void write_direct()
+    {
+        DevFieldPack &P = *d_pack;
+        if (!(is_work && (span_k == 0 || fused_span > 0))) {
+            if (lane == 0) { DevFieldWork w; memset(&w, 0, sizeof w); w.field = (int32_t)field; w.n_tiles = -1; P.work = w; }
+            return;
+        }
+        if (!d_early) write_direct_early();
+        if (span_k == 0) pt_off = off_wave_sum(pt_part);           // (field_work_and_span sums it for fields with a span only)
+        if (!wt_in_lanes) {
+            // (the window cut: lane 0 wrote the kept rows one after the other; every tile of such a field is kept)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            if (lane < n_wave) my_wt = keep_wtiles[field * DEVPLAN_KEEP_WROWS + lane];
+        }
+        if (lane < n_wave) {          // (as rebase_kept: the primitives the tile's lanes lie in)
+            const int nl = (int)my_wt.hb + my_wt.count + my_wt.hf;
+            if (my_wt.rel_main < nl) {
+                my_p0_rel = my_wt.p0;
+                my_np = 1;
+                for (int k = 0; k < 8; ++k) my_np += my_wt.thr[k] != 255 ? 1 : 0;
+            }
+            my_wt.out_base += pt_off;
+        }
+        if (lane < FIELD_WORK_TILES) P.tile[lane] = my_wt;               // (lanes without a tile hold zeros)
+        const bool from_lds = lds_pack();
+        if (from_lds) wave_sync();
+        constexpr int PW = PWD, TW = PACK_TILE_PRIMS * PW;
+        const unsigned long long *psrc = reinterpret_cast<const unsigned long long *>(prims);
+        unsigned long long *pdst = reinterpret_cast<unsigned long long *>(&P.prims[0][0]);
+        for (int t = 0; t < FIELD_WORK_TILES; ++t) {
+            const int p0 = __shfl(my_p0_rel, t), np = __shfl(my_np, t);
+            if (from_lds) for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? L.prim_words[p0 * PW + k] : 0ull;
+            else for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? psrc[(int64_t)p0 * PW + k] : 0ull;
+        }
+        if (lane == 0) {
+            DevFieldWork w;
+            memset(&w, 0, sizeof w);
+            w.field = (int32_t)field; w.n_tiles = (int32_t)n_wave; w.w_first = 0; w.e_first = 0; w.n_entries = (int32_t)c_stat; w.fused_span = (int32_t)fused_span;
+            P.work = w;
+            P.span_points = fused_span;
+            for (int k = 0; k < 6; ++k) P._pad0[k] = 0;
+            P._pad1 = 0.0;
+            for (int k = 0; k < 4; ++k) P._pad2[k] = 0.0;
+        }
     }
 
     // ---- 8. fill pass.  The field's descriptor and primitives at their final places (the primitives into LDS too, for the pack)
@@ -1679,52 +1772,41 @@ struct TilePass {
     }
 };
 
-// The fill pass of a speculative setup, its first workgroup: what the last scan of a counting phase does for the host, without a scan.
-// Wavefront 0 sums every column's aggregates (total(col), fcpp_offsetfn.h) and writes the totals, the flags and then the phase's generation
-// number to the host's copy (await_totals polls that word) -- whatever the flags say: a pass they make a no-op is waited for as well.
-// Wavefront 1 zeroes the OTHER buffer of aggregates, the one the slot's next setup accumulates into (nothing of this setup reads or writes it).
-__device__ __forceinline__ void publish_two_level(int64_t n, int64_t gen, int64_t *__restrict__ totals, const int64_t *__restrict__ agg, int64_t *__restrict__ agg_next,
-                                                  int64_t *__restrict__ mirror, int wave, int lane)
+// (the first workgroup of a speculative setup's fill pass: publish_two_level, fcpp_devplan.h -- shared with the direct step)
+
+// The counting launch of a direct setup, its first workgroup: the batch's point total -- the sum of the planner's aggregates, complete since
+// the planner ended -- and then the generation number to the host's copy: the host allocates the output arrays from it while the pass runs
+__device__ __forceinline__ void publish_early_points(int64_t n, int64_t gen, const int64_t *__restrict__ agg, int64_t *__restrict__ mirror, int wave, int lane)
 {
-    if (wave == 1) {
-        for (int k = lane; k < OFF_WORDS; k += 64) agg_next[k] = 0;
-        return;
-    }
-    if (wave != 0) return;
-    int64_t flag[PF_COUNT];
-#pragma unroll
-    for (int k = 0; k < PF_COUNT; ++k) flag[k] = totals[PC_COLS + k];
-    int64_t p0, p1, t0, t1;
-    offset_row_sums(agg, 0, (int)offset_blocks(n), lane, p0, p1, t0, t1);
-    // lane c: total(c) -- lane l holds the totals of columns 2 (l & 15) and 2 (l & 15) + 1; lanes PC_COLS + k: flag k
-    const int64_t other = __shfl(t1, lane >> 1), even = __shfl(t0, lane >> 1);
-    int64_t mine = (lane & 1) ? other : even;
-#pragma unroll
-    for (int k = 0; k < PF_COUNT; ++k) if (lane == PC_COLS + k) mine = flag[k];
-    if (lane < PC_COLS) { totals[lane] = mine; publish_total(totals, mirror, lane, mine, false); }
-    if (!mirror) return;
-    if (lane >= PC_COLS && lane < PC_COLS + PF_COUNT) mirror[lane] = mine;      // (the flags as loaded above, a lane each)
+    if (wave != 0 || !mirror) return;
+    const int64_t total = off_wave_sum(offset_total_part(agg, (int)offset_blocks(n), PC_POINTS, lane));
+    if (lane == 0) mirror[PX_EARLY_POINTS] = total;
     __threadfence_system();
-    if (lane == 0) reinterpret_cast<volatile int64_t *>(mirror)[PX_DONE] = gen;
+    if (lane == 0) reinterpret_cast<volatile int64_t *>(mirror)[PX_EARLY_GEN] = gen;
 }
 
-template <bool FILL, bool STAGE, bool DENSE>
+template <bool FILL, bool STAGE, bool DENSE, bool DIRECT>
 __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
                                                  fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts,
                                                  const int64_t *__restrict__ bases, int64_t *__restrict__ totals, int64_t *__restrict__ agg,
                                                  int64_t *__restrict__ agg_next, int64_t *__restrict__ mirror,
-                                                 DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, const DevPlanTables &T)
+                                                 DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, const DevPlanTables &T,
+                                                 DevFieldPack *__restrict__ direct_packs, TilePartial *__restrict__ direct_totals, double2 *__restrict__ direct_junc)
 {
+    static_assert(!DIRECT || (!FILL && !DENSE), "the direct records are the sparse counting pass's");
     __shared__ TileWaveLds<STAGE> lds_all[TW_WAVES];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     // the fill pass of a speculative setup has one workgroup more, the first: it publishes the totals and zeroes the other buffer of aggregates
-    const int publisher = (FILL && !DENSE && tc.speculative) ? 1 : 0;
+    // (not behind a direct step, which has done both: DIRECT_FILL); the counting launch of a direct setup has one more as well: the early point total
+    const int publisher = DIRECT ? 1 : ((FILL && !DENSE && tc.speculative && tc.direct != DIRECT_FILL) ? 1 : 0);
+    if (DIRECT && blockIdx.x == 0) { publish_early_points(n, tc.gen, agg, mirror, wave, lane); return; }
     if (FILL && !DENSE && publisher && blockIdx.x == 0) { publish_two_level(n, tc.gen, totals, agg, agg_next, mirror, wave, lane); return; }
     const int64_t field = ((int64_t)blockIdx.x - publisher) * TW_WAVES + wave;
     if (field >= n) return;
     TSTAMP(0);
     FSTAMP(0);
-    TilePass<FILL, STAGE, DENSE> p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, bases, totals, agg, keep_tiles, keep_wtiles, T, lds_all[wave], field, lane };
+    TilePass<FILL, STAGE, DENSE, DIRECT> p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, bases, totals, agg, keep_tiles, keep_wtiles, T, lds_all[wave], field, lane };
+    if (DIRECT) { p.d_pack = &direct_packs[field]; p.d_total = &direct_totals[field]; p.d_junc = &direct_junc[field]; }
     if (!p.header(info)) return;
     TSTAMP(1);
     FSTAMP(1);
@@ -1740,6 +1822,7 @@ __device__ __forceinline__ void tile_fields_body(int64_t n, const DevTileConsts 
     if (!FILL) {
         p.write_counts();
         p.add_counts_to_aggregates();
+        if (DIRECT) p.write_direct();
         TSTAMP(38);
         return;
     }
@@ -1761,7 +1844,20 @@ __global__ __launch_bounds__(64 * TW_WAVES, 4) void k_tile_fields(int64_t n, Dev
                                                               int64_t *__restrict__ agg_next, int64_t *__restrict__ mirror,
                                                               DevTile *__restrict__ keep_tiles, DevWaveTile *__restrict__ keep_wtiles, DevPlanTables T)
 {
-    tile_fields_body<FILL, STAGE, DENSE>(n, tc, cst, ftmp, ptmp, info, counts, bases, totals, agg, agg_next, mirror, keep_tiles, keep_wtiles, T);
+    tile_fields_body<FILL, STAGE, DENSE, false>(n, tc, cst, ftmp, ptmp, info, counts, bases, totals, agg, agg_next, mirror, keep_tiles, keep_wtiles, T, nullptr, nullptr, nullptr);
+}
+// The counting pass of a DIRECT setup (DevTileConsts.direct; at most OFF_FIELDS_MAX fields, no obstacle polygons): the same pass, and every
+// field the step's workgroup can take gets its DevFieldPack and its run totals here -- the step is launched from them right behind this kernel,
+// the fill pass leaves the plan call's chain.  An instance of its own: the other counting passes stay as compiled.
+template <bool STAGE>
+__global__ __launch_bounds__(64 * TW_WAVES, 4) void k_tile_fields_direct(int64_t n, DevTileConsts tc, DevConst cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
+                                                                     fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts, int64_t *__restrict__ totals,
+                                                                     int64_t *__restrict__ agg, int64_t *__restrict__ mirror, DevTile *__restrict__ keep_tiles,
+                                                                     DevWaveTile *__restrict__ keep_wtiles, DevFieldPack *__restrict__ direct_packs,
+                                                                     TilePartial *__restrict__ direct_totals, double2 *__restrict__ direct_junc)
+{
+    tile_fields_body<false, STAGE, false, true>(n, tc, cst, ftmp, ptmp, info, counts, nullptr, totals, agg, nullptr, mirror, keep_tiles, keep_wtiles, DevPlanTables(),
+                                                direct_packs, direct_totals, direct_junc);
 }
 // (Measured and not kept: the fill pass of a large batch held to six wavefronts per SIMD -- 85 registers, 225 spilled, the primitives not staged:
 // cfg5 390 instead of 235 us.)
@@ -1781,9 +1877,10 @@ __global__ void k_debug_math(int fn, int64_t n, const double *__restrict__ a, co
 }  // namespace
 
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
-                         int64_t n_polys, int check_obstacles, int64_t *totals_host)
+                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst)
 {
     if (n <= 0) return 0;
+    if (tc.direct == DIRECT_COUNT && (!tc.speculative || tc.dense || n_polys > 0 || !cst || !totals_host || !s.direct_packs)) return (int)hipErrorInvalidValue;
     // Sixteen lanes per field cut the latency of a plan (23 instead of 35 us for 4096 fields) and, four fields per wavefront, its stores are
     // denser (cfg5's 65 536 fields: 170 us against 230 for the one-thread kernel); FCPP_PLAN_SERIAL=1 (read once) keeps the latter: the checker
     static const bool plan_serial = getenv("FCPP_PLAN_SERIAL") != nullptr;
@@ -1810,7 +1907,14 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
     auto count = [&]() {
         const unsigned grid = (unsigned)((n + TW_WAVES - 1) / TW_WAVES);
-        if (tc.dense)
+        if (tc.direct == DIRECT_COUNT) {       // (one workgroup more, the first: the early point total -- tile_fields_body)
+            if (n <= 4096)
+                hipLaunchKernelGGL((k_tile_fields_direct<true>), dim3(grid + 1u), dim3(64 * TW_WAVES), 0, st, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts,
+                                   s.totals, agg, totals_host, s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
+            else
+                hipLaunchKernelGGL((k_tile_fields_direct<false>), dim3(grid + 1u), dim3(64 * TW_WAVES), 0, st, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts,
+                                   s.totals, agg, totals_host, s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
+        } else if (tc.dense)
             hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
                                s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
         else if (n <= 4096)

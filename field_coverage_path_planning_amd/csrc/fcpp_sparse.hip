@@ -18,6 +18,7 @@
 // kernels plans a stretch.  Stretches whose halos would not fit (dense sampling) stay with k_plan_fused.
 #include "fcpp_sparse2_fn.h"
 #include "fcpp_quiet_fn.h"
+#include "fcpp_devplan.h"
 
 namespace fcpp {
 
@@ -102,12 +103,22 @@ __device__ __forceinline__ void field_span_chunk(const DevFieldPack &pk, int wav
     quiet_tile<16, true, OBS>(tl, &f, nullptr, cst, obs, obs_lds, tlds, xo, yo, ko, vo, fso, cnt, cnt + 1);
 }
 
-template <int W, bool OBS, bool SPANS>
+// DIRECT: the step of a direct setup (fcpp_devplan.h: DevTileConsts.direct), enqueued right behind the counting pass -- one workgroup per FIELD
+// of the batch, packs and run totals as that pass wrote them into the planner's scratch.  The host has not seen the totals yet: every wavefront
+// applies the batch rule itself, as the fill pass's header() does (no flag of this generation up; every field a field of field work, every
+// span fusable -- then no run but the fused span exists, and the slots of `partial`, zero by construction, are neither read nor cleared), and
+// leaves when the rule fails or its field has no pack (work.n_tiles < 0).
+struct DirectRule {
+    int64_t n = 0, gen = 0;
+    const int64_t *plan_totals = nullptr, *agg = nullptr;
+};
+template <int W, bool OBS, bool SPANS, bool DIRECT = false>
 __device__ __forceinline__ void plan_sparse_fields_body(const DevFieldPack *__restrict__ packs,
                                                               DevConst cst, double *__restrict__ xo, double *__restrict__ yo,
                                                               double *__restrict__ ko, double *__restrict__ vo, uint32_t *__restrict__ fso,
                                                               DevObstacles obs, TilePartial *__restrict__ partial,
-                                                              const TilePartial *__restrict__ totals, fcpp_field_stats *__restrict__ stats)
+                                                              const TilePartial *__restrict__ totals, fcpp_field_stats *__restrict__ stats,
+                                                              const DirectRule rule = DirectRule())
 {
     __shared__ double obs_lds[W][OBS ? 2 * OBS_LDS_VERTS : 1];
     __shared__ TilePartial red[FIELD_WORK_TILES];
@@ -120,8 +131,23 @@ __device__ __forceinline__ void plan_sparse_fields_body(const DevFieldPack *__re
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     atan_tab_stage(atab);
     // everything of the field at addresses that follow from the workgroup's index (DevFieldPack)
-    const DevFieldPack &pk = packs[blockIdx.x];
+    const unsigned wg = DIRECT ? blockIdx.x - 1u : blockIdx.x;          // (direct: the launch's first workgroup is the publisher)
+    const DevFieldPack &pk = packs[wg];
     const DevFieldWork w = pk.work;
+    if (DIRECT) {
+        // (the loads of the flags and of the aggregates' rows go out with those of the work record and the arc-tangent table)
+        int64_t flag[PF_COUNT];
+#pragma unroll
+        for (int k = 0; k < PF_COUNT; ++k) flag[k] = rule.plan_totals[PC_COLS + k];
+        const int nblk = (int)offset_blocks(rule.n);
+        const int64_t a_work = offset_total_part(rule.agg, nblk, PC_WORK, lane), a_unf = offset_total_part(rule.agg, nblk, PC_UNFUSABLE, lane),
+                      a_wsp = offset_total_part(rule.agg, nblk, PC_WORK_SPAN_PTS, lane);
+        bool ok = off_wave_sum(a_work) == rule.n && off_wave_sum(a_unf) == 0 && off_wave_sum(a_wsp) > 0;
+#pragma unroll
+        for (int k = 0; k < PF_COUNT; ++k) ok = ok && flag[k] != rule.gen;
+        if (!ok || w.n_tiles < 0) return;
+        __builtin_amdgcn_sched_barrier(0);       // (the rule's sums are dead here: nothing of the tile phase is scheduled in among them)
+    }
 #ifdef FCPP_DIAG_SPARSE
     if (g_sparse_stop == -2) return;
 #endif
@@ -170,13 +196,13 @@ __device__ __forceinline__ void plan_sparse_fields_body(const DevFieldPack *__re
     static_assert(sizeof(TilePartial) == 13 * 8 && sizeof(fcpp_field_stats) == 13 * 8, "statistics records are thirteen 8-byte components");
     unsigned long long run_v = 0, c_out = 0, c_obs = 0;
     if (wave == 0) {
-        if (lane < 13) run_v = reinterpret_cast<const unsigned long long *>(&totals[blockIdx.x])[lane];
-        if (lane < w.n_entries) { const TilePartial &slot = partial[w.e_first + lane]; c_out = (unsigned long long)slot.n_outside; c_obs = (unsigned long long)slot.n_in_obstacle; }
+        if (lane < 13) run_v = reinterpret_cast<const unsigned long long *>(&totals[wg])[lane];
+        if (!DIRECT && lane < w.n_entries) { const TilePartial &slot = partial[w.e_first + lane]; c_out = (unsigned long long)slot.n_outside; c_obs = (unsigned long long)slot.n_in_obstacle; }
     }
     // (the barrier orders the tiles' results and the span counts in LDS only: no wait for the loads above or for anybody's stores)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (wave != 0) return;
-    if ((c_out | c_obs) != 0ull) { partial[w.e_first + lane].n_outside = 0; partial[w.e_first + lane].n_in_obstacle = 0; }   // collected anew in the next step
+    if (!DIRECT && (c_out | c_obs) != 0ull) { partial[w.e_first + lane].n_outside = 0; partial[w.e_first + lane].n_in_obstacle = 0; }   // collected anew in the next step
     if (lane < W) { c_out += span_cnt[lane][0]; c_obs += span_cnt[lane][1]; }
     if (__ballot((c_out | c_obs) != 0ull) != 0ull) {             // (rare) points of the field's runs were flagged in this step
 #pragma unroll
@@ -210,6 +236,26 @@ __global__ __launch_bounds__(64 * W) void k_plan_sparse_fields(const DevFieldPac
                                                               const TilePartial *__restrict__ totals, fcpp_field_stats *__restrict__ stats)
 {
     plan_sparse_fields_body<W, OBS, SPANS>(packs, cst, xo, yo, ko, vo, fso, obs, partial, totals, stats);
+}
+
+// The step of a direct setup: workgroup 0 the publisher of the setup's totals (publish_two_level, as the first workgroup of a speculative fill
+// pass: totals, flags, the done word, the other buffer of aggregates zeroed -- first, so that the host has the totals while the step runs),
+// workgroup 1 + f the field f
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_plan_sparse_fields_direct(const DevFieldPack *__restrict__ packs, DevConst cst, double *__restrict__ xo, double *__restrict__ yo,
+                                                                     double *__restrict__ ko, double *__restrict__ vo, uint32_t *__restrict__ fso,
+                                                                     const TilePartial *__restrict__ totals, fcpp_field_stats *__restrict__ stats, int64_t n, int64_t gen,
+                                                                     int64_t *__restrict__ plan_totals, const int64_t *__restrict__ agg, int64_t *__restrict__ agg_next,
+                                                                     int64_t *__restrict__ mirror)
+{
+    if (blockIdx.x == 0) {
+        publish_two_level(n, gen, plan_totals, agg, agg_next, mirror, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (int)(threadIdx.x & 63));
+        return;
+    }
+    DevObstacles obs = { nullptr, nullptr, nullptr, nullptr };
+    DirectRule rule;
+    rule.n = n; rule.gen = gen; rule.plan_totals = plan_totals; rule.agg = agg;
+    plan_sparse_fields_body<W, false, true, true>(packs, cst, xo, yo, ko, vo, fso, obs, nullptr, totals, stats, rule);
 }
 
 // Batch creation: per field of field_work, the closed-form statistics of its quiet runs (their slots, k_run_consts) summed in the order of
@@ -254,6 +300,19 @@ int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack
     else if (spans) FCPP_FW(k_plan_sparse_fields, 4, false, true);
     else FCPP_FW(k_plan_sparse_fields, 4, false, false);
 #undef FCPP_FW
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int launch_plan_sparse_direct(hipStream_t st, int64_t n, int64_t gen, const DevPlanScratch &s, const DevConst &cst, double *x, double *y, double *kappa,
+                              double *v, uint32_t *fs, fcpp_field_stats *stats, int64_t *totals_host)
+{
+    if (n <= 0) return 0;
+    if (n > OFF_FIELDS_MAX || !s.direct_packs || !s.agg || !s.agg_next || !totals_host) return (int)hipErrorInvalidValue;
+    DevConst dc = cst;
+    dc.field_junc = s.direct_junc;       // (the batch's own table is written by the fill pass, which a direct setup has not run)
+    FCPP_LAUNCH((k_plan_sparse_fields_direct<4>), dim3((unsigned)n + 1u), dim3(64 * 4), 0, st, s.direct_packs, dc, x, y, kappa, v, fs, s.direct_totals, stats, n, gen,
+                s.totals, s.agg, s.agg_next, totals_host);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

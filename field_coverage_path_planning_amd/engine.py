@@ -45,6 +45,18 @@ class Context:
             self._arena = self.outputs_info()[:2]
         return self._arena
 
+    def direct_steps(self):
+        """Direct steps Batch.plan has launched on this context so far (fcpp_ctx_direct_steps): the step enqueued right behind the device
+        setup's counting pass, before the totals are back; the batch's tables are then filled when somebody asks for them."""
+        return self.direct_counts()[0]
+
+    def direct_counts(self):
+        """-> (direct steps launched, calls whose batch was TAKEN -- no fill pass and no run in the call --, fill passes of taken batches
+        enqueued since: somebody asked for the tables, or another setup took the plan slot)"""
+        n, t, f = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self.lib.fcpp_ctx_direct_steps(self.handle, C.byref(n), C.byref(t), C.byref(f)))
+        return n.value, t.value, f.value
+
     def reserve_outputs(self, lane_gib=24.0, pitch_gib=24.0):
         """Give the context its output ARENA (fcpp_ctx_reserve_outputs): one device allocation of 4 x pitch + lane, made once -- it takes
         the driver seconds, so it belongs to start-up, not to a plan call -- in which Batch.alloc() then places the five output arrays of

@@ -1063,6 +1063,11 @@ int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_r
  * offsets / x / y / bounding boxes, 22 the packs of k_plan_sparse_fields.  tests/test_gpu_devplan.py compares the tables of a batch set up on the device with those of the
  * same batch set up on the host. */
 int fcpp_batch_debug_table(const fcpp_batch *batch, int table, void *dst, int64_t cap_bytes, int64_t *bytes_out);
+/* The direct step of fcpp_batch_plan on this context so far (the step of a speculative device setup enqueued right behind the counting pass,
+   before the host has the totals: batches without obstacle polygons; FCPP_DIRECT=0 switches the path off).  launched: steps enqueued;
+   taken: of those, the calls whose batch qualified -- no fill pass and no fcpp_batch_run in the call; fills: fill passes of taken batches
+   enqueued since, because somebody asked for the tables or another setup took the plan slot.  Any pointer may be NULL.  Tests. */
+int fcpp_ctx_direct_steps(const fcpp_ctx *ctx, int64_t *launched, int64_t *taken, int64_t *fills);
 
 #ifdef __cplusplus
 }

@@ -17,8 +17,9 @@ def short(n):
 calls, cur = [], None
 for r in rows:
     n = short(r['Kernel_Name'])
-    # (a large batch's planner and counting pass run in chunks: a call begins with the first planner launch after a fill pass)
-    if n.startswith('k_plan_fields') and (cur is None or any(x[0].startswith('k_tile_fields<true') for x in cur)):
+    # (a large batch's planner and counting pass run in chunks: a call begins with the first planner launch after a fill pass -- or after the
+    # step that ran directly off the counting pass, when the call had no fill pass)
+    if n in ('k_plan_fields', 'k_plan_fields16') and (cur is None or any(x[0].startswith(('k_tile_fields<true', 'k_plan_sparse_fields')) for x in cur)):
         cur = []
         calls.append(cur)
     if cur is not None:
