@@ -225,6 +225,15 @@ static CutConsts make_cut_consts(TemplateSet &ts, bool device, const BatchTileCo
 
 namespace {
 // fcpp_debug_dubins (MODE 0) / fcpp_debug_rs (MODE 1): the host side of the connectors' one function, a pair at a time
+// (one pair, kept out of line: with the 48 words inlined into the loop below the host compiler's loop passes take minutes to hours over
+//  them; a call changes no bit)
+template <int MODE>
+__attribute__((noinline)) void debug_conn_pair(double x0, double y0, double h0, double x1, double y1, double h1, double radius, int &w, double *s,
+                                               double &tot)
+{
+    Conn<MODE>::solve(x0, y0, h0, x1, y1, h1, radius, w, s, tot);
+}
+
 template <int MODE>
 int debug_conn(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
                double radius, int32_t *word, double *seg, double *len)
@@ -236,7 +245,7 @@ int debug_conn(int64_t n, const double *fx, const double *fy, const double *fh, 
     for (int64_t i = 0; i < n; ++i) {
         int w;
         double s[NSEG], tot;
-        Conn<MODE>::solve(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s, tot);
+        debug_conn_pair<MODE>(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, w, s, tot);
         if (word) word[i] = w;
         if (seg) for (int k = 0; k < NSEG; ++k) seg[NSEG * i + k] = s[k];
         if (len) len[i] = tot;

@@ -79,53 +79,71 @@ FCPP_HD DubinsPose dubins_prep(double x, double y, double h, double R)
     return { x, y, h, R * sn, R * cs };
 }
 
-// all six words evaluated, the shortest selected (no branch by word)
-FCPP_HD void dubins_solve_prepped(const DubinsPose &f, const DubinsPose &t, double R, int &word, double &seg0, double &seg1, double &seg2, double &total)
+// What the word enumeration hands every candidate to.  DubinsBest is the solver's own: the shortest feasible word, among equal totals the
+// lowest index (the candidates come in word order).  fcpp_solveclearfn.h brings accumulators that keep more than one.
+struct DubinsBest {
+    double best = INFINITY, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+    int bw = 0;
+    FCPP_HD void take(int w, bool ok, double c0, double c1, double c2)
+    {
+        const double tt = (c0 + c1) + c2;
+        if (ok && tt < best) { best = tt; bw = w; b0 = c0; b1 = c1; b2 = c2; }
+    }
+};
+
+// all six words evaluated (no branch by word), each handed to acc.take(word, feasible, seg0, seg1, seg2)
+template <class ACC>
+FCPP_HD void dubins_words(const DubinsPose &f, const DubinsPose &t, double R, ACC &acc)
 {
     const double dx = t.x - f.x, dy = t.y - f.y;
     const double sm = f.s - t.s, sp = f.s + t.s, cm = f.c - t.c, cp = f.c + t.c;
     const double R2 = R * R, twoR = 2.0 * R, near = R * kDubCoincide;
     const double h0 = f.h, h1 = t.h;
-    double best = INFINITY, b0 = 0.0, b1 = 0.0, b2 = 0.0;
-    int bw = 0;
-#define FCPP_DUBINS_CANDIDATE(w, ok, l0, l1, l2)                                            \
-    do {                                                                                    \
-        const double c0_ = (l0), c1_ = (l1), c2_ = (l2), tt_ = (c0_ + c1_) + c2_;           \
-        if ((ok) && tt_ < best) { best = tt_; bw = (w); b0 = c0_; b1 = c1_; b2 = c2_; }     \
-    } while (0)
     // left centre -> left centre, right centre -> right centre
     const double lx = dx + sm, ly = dy - cm, rx = dx - sm, ry = dy + cm;
     const double Dl2 = lx * lx + ly * ly, Dr2 = rx * rx + ry * ry;
     const double Dl = sqrt(Dl2), Dr = sqrt(Dr2);
     const double phl = Dl >= near ? atan2_fd(ly, lx) : h0, phr = Dr >= near ? atan2_fd(ry, rx) : h0;
-    FCPP_DUBINS_CANDIDATE(0, true, R * dubins_arc(phl - h0), Dl, R * dubins_arc(h1 - phl));
+    acc.take(0, true, R * dubins_arc(phl - h0), Dl, R * dubins_arc(h1 - phl));
     {   // LSR: left centre -> right centre
         const double ux = dx + sp, uy = dy - cp, e = (ux * ux + uy * uy) - 4.0 * R2;
         const double p = sqrt(fmax(e, 0.0)), psi = atan2_fd(twoR * ux + p * uy, p * ux - twoR * uy);
-        FCPP_DUBINS_CANDIDATE(1, e >= -4.0 * R2 * kDubEdge, R * dubins_arc(psi - h0), p, R * dubins_arc(psi - h1));
+        acc.take(1, e >= -4.0 * R2 * kDubEdge, R * dubins_arc(psi - h0), p, R * dubins_arc(psi - h1));
     }
     {   // RSL: right centre -> left centre
         const double wx = dx - sp, wy = dy + cp, e = (wx * wx + wy * wy) - 4.0 * R2;
         const double p = sqrt(fmax(e, 0.0)), psi = atan2_fd(p * wy - twoR * wx, p * wx + twoR * wy);
-        FCPP_DUBINS_CANDIDATE(2, e >= -4.0 * R2 * kDubEdge, R * dubins_arc(h0 - psi), p, R * dubins_arc(h1 - psi));
+        acc.take(2, e >= -4.0 * R2 * kDubEdge, R * dubins_arc(h0 - psi), p, R * dubins_arc(h1 - psi));
     }
-    FCPP_DUBINS_CANDIDATE(3, true, R * dubins_arc(h0 - phr), Dr, R * dubins_arc(phr - h1));
+    acc.take(3, true, R * dubins_arc(h0 - phr), Dr, R * dubins_arc(phr - h1));
     {   // RLR
         const double e = 16.0 * R2 - Dr2, g = atan2_fd(sqrt(fmax(e, 0.0)), Dr);
         const double a0 = dubins_arc(((h0 - phr) + g) + kHalfPi), am = dubins_arc(kPi + 2.0 * g), a2 = dubins_arc(((h0 - h1) - a0) + am);
-        FCPP_DUBINS_CANDIDATE(4, e >= -16.0 * R2 * kDubEdge, R * a0, R * am, R * a2);
+        acc.take(4, e >= -16.0 * R2 * kDubEdge, R * a0, R * am, R * a2);
     }
     {   // LRL
         const double e = 16.0 * R2 - Dl2, g = atan2_fd(sqrt(fmax(e, 0.0)), Dl);
         const double a0 = dubins_arc(((phl - h0) + g) + kHalfPi), am = dubins_arc(kPi + 2.0 * g), a2 = dubins_arc(((h1 - h0) - a0) + am);
-        FCPP_DUBINS_CANDIDATE(5, e >= -16.0 * R2 * kDubEdge, R * a0, R * am, R * a2);
+        acc.take(5, e >= -16.0 * R2 * kDubEdge, R * a0, R * am, R * a2);
     }
-#undef FCPP_DUBINS_CANDIDATE
-    const bool ok = dubins_finite(dx) && dubins_finite(dy) && dubins_finite(h0) && dubins_finite(h1) && dubins_finite(best);
+}
+
+// are the pair's inputs such that a word can be had at all?  (the solvers' "word -1" rule, the totals aside)
+FCPP_HD bool dubins_inputs_finite(const DubinsPose &f, const DubinsPose &t)
+{
+    return dubins_finite(t.x - f.x) && dubins_finite(t.y - f.y) && dubins_finite(f.h) && dubins_finite(t.h);
+}
+
+// the shortest word selected
+FCPP_HD void dubins_solve_prepped(const DubinsPose &f, const DubinsPose &t, double R, int &word, double &seg0, double &seg1, double &seg2, double &total)
+{
+    DubinsBest b;
+    dubins_words(f, t, R, b);
+    const bool ok = dubins_inputs_finite(f, t) && dubins_finite(b.best);
     const double nan = __builtin_nan("");
-    word = ok ? bw : -1;
-    seg0 = ok ? b0 : nan; seg1 = ok ? b1 : nan; seg2 = ok ? b2 : nan;
-    total = ok ? best : nan;
+    word = ok ? b.bw : -1;
+    seg0 = ok ? b.b0 : nan; seg1 = ok ? b.b1 : nan; seg2 = ok ? b.b2 : nan;
+    total = ok ? b.best : nan;
 }
 
 FCPP_HD void dubins_solve(double x0, double y0, double h0, double x1, double y1, double h1, double R, int &word, double &seg0, double &seg1,

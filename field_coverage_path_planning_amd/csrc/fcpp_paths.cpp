@@ -22,6 +22,7 @@
 #include "fcpp_pcoverfn.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
+#include "fcpp_solveclear.h"
 #include "fcpp_swath.h"
 #include "fcpp_swathfn.h"
 #include "fcpp_traj.h"
@@ -394,6 +395,39 @@ int clear_tiles(int64_t n, const std::vector<int64_t> &toff, std::vector<int64_t
         tile_off[(size_t)i + 1] = tile_off[(size_t)i] + (toff[(size_t)i + 1] - toff[(size_t)i] + CLEAR_TILE - 1) / CLEAR_TILE;
     if (tile_off[(size_t)n] > CLEAR_MAX_GROUPS) return fail(FCPP_ESIZE, "2^39 transit entries or more");
     return FCPP_OK;
+}
+
+// ---- clear connectors: what fcpp_conn_solve_clear and its host twin check alike
+int solve_clear_args(int mode, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty,
+                            const double *th, double radius, const int64_t *pair_field, int64_t n_fields, const void *ring_offsets, int64_t n_rings,
+                            const void *vert_offsets, int64_t n_verts, const double *x, const double *y)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y)) || (n > 0 && (!fx || !fy || !fh || !tx || !ty || !th || !pair_field)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    // (n below 2^31: the word kernel's grid, a wavefront per pair at most)
+    if (n < 0 || n_fields < 0 || n_rings < 0 || n_verts < 0 || n_fields > INT32_MAX || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    return FCPP_OK;
+}
+
+// every candidate of every pair: fcpp_debug_conn_words
+template <int MODE>
+void debug_conn_words(int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
+                             double radius, uint8_t *ok, double *seg, double *total)
+{
+    constexpr int NW = SolveClearWords<MODE>::NW, NSEG = Conn<MODE>::NSEG;
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        SolveClearAll<MODE> all;
+        const bool fin = solve_clear_words<MODE>(fx[i], fy[i], fh[i], tx[i], ty[i], th[i], radius, all);
+        for (int w = 0; w < NW; ++w) {
+            const bool have = fin && all.ok[w];
+            if (ok) ok[i * NW + w] = have ? 1 : 0;
+            if (total) total[i * NW + w] = have ? all.total[w] : __builtin_nan("");
+            if (seg)
+                for (int k = 0; k < NSEG; ++k) seg[(i * NW + w) * NSEG + k] = have ? all.seg[w][k] : __builtin_nan("");
+        }
+    });
 }
 
 // ---- field paths: what fcpp_field_path_counts / _fill and fcpp_debug_field_paths check alike ------------------------------------------------
@@ -1243,6 +1277,94 @@ int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int6
                 Bb[e] = Bb[e2] = blocked ? 1 : 0;
                 if (blocked) { const double v = Tb[e] + penalty; Tb[e] = v; Tb[e2] = v; }
             }
+    });
+    return FCPP_OK;
+}
+
+// ---- clear connectors (fcpp_solveclear.hip; the rule: fcpp_solveclearfn.h) -------------------------------------------------------------
+int fcpp_conn_solve_clear(fcpp_ctx *c, int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                          const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                          const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y,
+                          int32_t *word, double *seg, double *len, int32_t *rank, int32_t *crossings, int32_t *field_status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    int rc = solve_clear_args(mode, n, from_x, from_y, from_h, to_x, to_y, to_h, radius, pair_field, n_fields, ring_offsets, n_rings, vert_offsets,
+                              n_verts, x, y);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(c, n_fields, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    const SolveClearIo io = { from_x, from_y, from_h, to_x, to_y, to_h, pair_field, word, seg, len, rank, crossings };
+    LAUNCHCHK(launch_clear_field_status(c->stream, F, field_status));
+    c->solve_clear_listed = 0;
+    if (n > 0 && (word || seg || len || rank || crossings)) {
+        DevBuf<int64_t> list;
+        DevBuf<unsigned long long> count;
+        HIPCHK(list.alloc((size_t)n));
+        HIPCHK(count.alloc(1));
+        HIPCHK(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), c->stream));
+        LAUNCHCHK(launch_solve_clear_pairs(c->stream, mode, n, io, radius, F, list.p, count.p));
+        unsigned long long listed = 0;
+        HIPCHK(hipMemcpyAsync(&listed, count.p, sizeof listed, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (listed > (unsigned long long)n) return fail(FCPP_EHIP, "the first pass listed more pairs than there are");
+        c->solve_clear_listed = (int64_t)listed;
+        if (listed > 0) {
+            LAUNCHCHK(launch_solve_clear_words(c->stream, mode, (int64_t)listed, list.p, io, radius, F));
+            ++c->solve_clear_word_launches;
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));          // (the list dies here)
+        return FCPP_OK;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_ctx_solve_clear_passes(const fcpp_ctx *c, int64_t *listed, int64_t *word_launches)
+{
+    if (!c) return fail(FCPP_EINVAL, "ctx is NULL");
+    if (listed) *listed = c->solve_clear_listed;
+    if (word_launches) *word_launches = c->solve_clear_word_launches;
+    return FCPP_OK;
+}
+
+int fcpp_debug_conn_words(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                          const double *to_y, const double *to_h, double radius, uint8_t *ok, double *seg, double *total)
+{
+    if (n > 0 && (!from_x || !from_y || !from_h || !to_x || !to_y || !to_h)) return fail(FCPP_EINVAL, "bad arguments");
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    if (n < 0) return fail(FCPP_ESIZE, "bad sizes");
+    if (mode == 0) debug_conn_words<0>(n, from_x, from_y, from_h, to_x, to_y, to_h, radius, ok, seg, total);
+    else debug_conn_words<1>(n, from_x, from_y, from_h, to_x, to_y, to_h, radius, ok, seg, total);
+    return FCPP_OK;
+}
+
+int fcpp_debug_conn_solve_clear(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                                const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                                const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                const double *y, int32_t *word, double *seg, double *len, int32_t *rank, int32_t *crossings, int32_t *field_status)
+{
+    int rc = solve_clear_args(mode, n, from_x, from_y, from_h, to_x, to_y, to_h, radius, pair_field, n_fields, ring_offsets, n_rings, vert_offsets,
+                              n_verts, x, y);
+    if (rc) return rc;
+    std::vector<int64_t> rings, verts;
+    rc = swath_fields(nullptr, n_fields, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc) return rc;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    if (field_status) WorkerPool::parallel_for(n_fields, [&](int64_t f) { field_status[f] = clear_field_status(F, f); });
+    const int nseg = mode == 0 ? 3 : 5;
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const SolveClearResult r = mode == 0 ? solve_clear<0>(F, pair_field[i], from_x[i], from_y[i], from_h[i], to_x[i], to_y[i], to_h[i], radius)
+                                             : solve_clear<1>(F, pair_field[i], from_x[i], from_y[i], from_h[i], to_x[i], to_y[i], to_h[i], radius);
+        if (word) word[i] = r.word;
+        if (seg)
+            for (int k = 0; k < nseg; ++k) seg[i * nseg + k] = r.seg[k];
+        if (len) len[i] = r.len;
+        if (rank) rank[i] = r.rank;
+        if (crossings) crossings[i] = r.crossings;
     });
     return FCPP_OK;
 }

@@ -108,23 +108,28 @@ FCPP_HD double rs_neg(double a, bool &ok) { return 0.0 - rs_pos(-a, ok); }
 
 struct RsBest { double total; int word; double s0, s1, s2, s3, s4; };
 
+// What the word enumeration hands every candidate to: rs_keep(acc, word, feasible, total, five signed lengths).  This overload is the
+// solver's own -- the shortest feasible word, among equal totals the lowest index; fcpp_solveclearfn.h brings accumulators that keep more.
 FCPP_HD void rs_keep(RsBest &b, int w, bool ok, double tt, double l0, double l1, double l2, double l3, double l4)
 {
     if (ok && (tt < b.total || (tt == b.total && w < b.word))) { b.total = tt; b.word = w; b.s0 = l0; b.s1 = l1; b.s2 = l2; b.s3 = l3; b.s4 = l4; }
 }
 // candidates of 3, 4, 5 segments in units of R; sg = -1 under a flip
 // (straight_m: the straight of 8.1 and 8.2 comes in metres, formed without the division by R: an axis-aligned straight is exact)
-FCPP_HD void rs_take3(RsBest &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, bool straight_m = false)
+template <class ACC>
+FCPP_HD void rs_take3(ACC &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, bool straight_m = false)
 {
     const double l0 = (R * a0) * sg, l1 = (straight_m ? a1 : R * a1) * sg, l2 = (R * a2) * sg;
     rs_keep(b, w, ok, (fabs(l0) + fabs(l1)) + fabs(l2), l0, l1, l2, 0.0, 0.0);
 }
-FCPP_HD void rs_take4(RsBest &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, double a3)
+template <class ACC>
+FCPP_HD void rs_take4(ACC &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, double a3)
 {
     const double l0 = (R * a0) * sg, l1 = (R * a1) * sg, l2 = (R * a2) * sg, l3 = (R * a3) * sg;
     rs_keep(b, w, ok, ((fabs(l0) + fabs(l1)) + fabs(l2)) + fabs(l3), l0, l1, l2, l3, 0.0);
 }
-FCPP_HD void rs_take5(RsBest &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, double a3, double a4)
+template <class ACC>
+FCPP_HD void rs_take5(ACC &b, double R, double sg, int w, bool ok, double a0, double a1, double a2, double a3, double a4)
 {
     const double l0 = (R * a0) * sg, l1 = (R * a1) * sg, l2 = (R * a2) * sg, l3 = (R * a3) * sg, l4 = (R * a4) * sg;
     rs_keep(b, w, ok, (((fabs(l0) + fabs(l1)) + fabs(l2)) + fabs(l3)) + fabs(l4), l0, l1, l2, l3, l4);
@@ -157,7 +162,8 @@ FCPP_HD RsVec rs_polar_plus(double X, double Y, double Yp2)
 
 // The words of a "minus" vector under identity and flip (mirror: the caller passes the mirrored vector and -phi).  back: the vector is
 // that of the backwards pose, the segments come in reverse order (bases 4 and 9 instead of 0, 2, 3, 7).
-FCPP_HD void rs_minus_words(RsBest &b, double R, const RsVec &V, double phi, int mirror, bool back, double rho_m = 0.0)
+template <class ACC>
+FCPP_HD void rs_minus_words(ACC &b, double R, const RsVec &V, double phi, int mirror, bool back, double rho_m = 0.0)
 {
     const double e4 = V.rho2 - 4.0, r = sqrt(fmax(e4, 0.0));
     const double e16 = 16.0 - V.rho2, as = atan2_fd(V.rho, sqrt(fmax(e16, 0.0)));      // asin(rho / 4)
@@ -194,7 +200,8 @@ FCPP_HD void rs_minus_words(RsBest &b, double R, const RsVec &V, double phi, int
 }
 
 // The words of a "plus" vector: bases 1, 5, 6, 8, 11; backwards only base 10.
-FCPP_HD void rs_plus_words(RsBest &b, double R, const RsVec &V, double phi, int mirror, bool back, double r_m = 0.0)
+template <class ACC>
+FCPP_HD void rs_plus_words(ACC &b, double R, const RsVec &V, double phi, int mirror, bool back, double r_m = 0.0)
 {
     // (the backwards plus vectors come through rs_polar, e4 = rho^2 - 4 as it is: there it only decides base 10's edge rho >= 2, where the word's
     //  straight is 0 and a word of nearly the same length competes -- no root is taken of it)
@@ -263,8 +270,9 @@ FCPP_HD RsPose rs_prep(double x, double y, double h)
     return { x, y, h, sn, cs };
 }
 
-// all 48 words evaluated, the shortest selected (no branch by word).  seg: five signed lengths.
-FCPP_HD void rs_solve_prepped(const RsPose &f, const RsPose &t, double R, int &word, double *seg, double &total)
+// all 48 words evaluated (no branch by word), each handed to rs_keep(acc, ...)
+template <class ACC>
+FCPP_HD void rs_words(const RsPose &f, const RsPose &t, double R, ACC &b)
 {
     const double dx = t.x - f.x, dy = t.y - f.y, inv = 1.0 / R;
     const double xm = dx * f.cs + dy * f.sn, ym = dy * f.cs - dx * f.sn, x = xm * inv, y = ym * inv;
@@ -272,7 +280,6 @@ FCPP_HD void rs_solve_prepped(const RsPose &f, const RsPose &t, double R, int &w
     double s, c;
     fc_sincos(phi, s, c);
     const double xb = x * c + y * s, yb = x * s - y * c;
-    RsBest b = { INFINITY, 0, 0.0, 0.0, 0.0, 0.0, 0.0 };
     const double Rs = R * s, Rc = R * c, ax = xm - Rs, ay = (ym - R) + Rc, bx = xm + Rs, by = (-ym - R) + Rc;      // the 8.1 vectors in metres
     rs_minus_words(b, R, rs_polar(x - s, (y - 1.0) + c), phi, 0, false, sqrt(ax * ax + ay * ay));
     rs_minus_words(b, R, rs_polar(x + s, (-y - 1.0) + c), -phi, 1, false, sqrt(bx * bx + by * by));
@@ -286,7 +293,20 @@ FCPP_HD void rs_solve_prepped(const RsPose &f, const RsPose &t, double R, int &w
     rs_minus_words(b, R, rs_polar(xb + s, (-yb - 1.0) + c), -phi, 1, true);
     rs_plus_words(b, R, rs_polar(xb + s, (yb - 1.0) - c), phi, 0, true);
     rs_plus_words(b, R, rs_polar(xb - s, (-yb - 1.0) - c), -phi, 1, true);
-    const bool ok = dubins_finite(dx) && dubins_finite(dy) && dubins_finite(f.h) && dubins_finite(t.h) && dubins_finite(b.total);
+}
+
+// are the pair's inputs such that a word can be had at all?  (the solvers' "word -1" rule, the totals aside)
+FCPP_HD bool rs_inputs_finite(const RsPose &f, const RsPose &t)
+{
+    return dubins_finite(t.x - f.x) && dubins_finite(t.y - f.y) && dubins_finite(f.h) && dubins_finite(t.h);
+}
+
+// the shortest word selected.  seg: five signed lengths.
+FCPP_HD void rs_solve_prepped(const RsPose &f, const RsPose &t, double R, int &word, double *seg, double &total)
+{
+    RsBest b = { INFINITY, 0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    rs_words(f, t, R, b);
+    const bool ok = rs_inputs_finite(f, t) && dubins_finite(b.total);
     const double nan = __builtin_nan("");
     word = ok ? b.word : -1;
     // (+ 0.0: a segment of length 0 under a flip is +0, not -0)

@@ -1053,12 +1053,10 @@ def _conn_matrix(from_poses, to_poses, radius, want_words, reversing, device):
     return (D, W) if want_words else D
 
 
-def _conn_paths(ctx, from_poses, to_poses, radius, spacing, reversing):
-    """solve + counts + sample -> dict of device tensors; `reversing` adds the samples' gear"""
+def _conn_sample_solved(ctx, f, word, seg, length, radius, spacing, reversing):
+    """counts + sample of SOLVED connectors that start at the prepared poses f -> dict of device tensors; `reversing` adds the samples' gear"""
     torch = _torch()
-    dev = torch.device('cuda', ctx.device)
-    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
-    word, seg, length = _conn_solve(ctx, f, t, radius, reversing)
+    dev = word.device
     n = int(word.numel())
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     off_h = np.zeros(n + 1, dtype=np.int64)
@@ -1075,6 +1073,14 @@ def _conn_paths(ctx, from_poses, to_poses, radius, spacing, reversing):
                   *[_ptr(v) for v in out.values()], _host_ptr(off_h)))
     out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
     return out
+
+
+def _conn_paths(ctx, from_poses, to_poses, radius, spacing, reversing):
+    """solve + counts + sample -> dict of device tensors; `reversing` adds the samples' gear"""
+    dev = _torch().device('cuda', ctx.device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    word, seg, length = _conn_solve(ctx, f, t, radius, reversing)
+    return _conn_sample_solved(ctx, f, word, seg, length, radius, spacing, reversing)
 
 
 def _dubins_paths(ctx, from_poses, to_poses, radius, spacing):
@@ -1684,6 +1690,64 @@ def connector_clearance(from_poses, to_poses, fields, pair_field, radius, revers
     pair (or one for all); -1 means no region: clear.  A margin is no parameter: pass polygon_inset(fields, [margin]).as_fields(0).
     Nothing is re-shaped.  -> ConnectorClearance."""
     return _connector_clearance(from_poses, to_poses, polygon_fields(fields, device), pair_field, radius, reversing, device)
+
+
+@dataclass
+class ClearConnectors:
+    """clear_connectors(): per pair the shortest word that stays inside the pair's field, one entry per pair"""
+    word: object                # (n) int32: the word driven (-1: unsolved pair)
+    seg: object                 # (n, 3) or (n, 5) float64: its segments, as dubins_solve / rs_solve give them
+    length: object              # (n) float64: its length [m]
+    rank: object                # (n) int32: its position among the pair's candidates by (length, word); 0 the shortest; -1: no word is clear
+    crossings: object           # (n) int32: 0 for rank >= 0; for rank -1 the crossings of the shortest word, which is the one returned
+    shortest_length: object     # (n) float64: the shortest word's length [m]: what dubins_solve / rs_solve give
+    field_status: object        # (n_fields) int32: fcpp_conn_clear's status of every field
+    radius: float
+    reversing: bool
+    _start: object = None       # the prepared start poses
+    _device: object = None
+
+    def paths(self, spacing):
+        """The words sampled every `spacing` metres by the connectors' own samplers (fcpp_dubins_counts / _sample, fcpp_rs_counts /
+        _sample) -> (x, y, heading, kappa, offsets), for reversing=True (x, y, heading, kappa, gear, offsets), as dubins_paths / rs_paths."""
+        ctx = get_context(self._device)
+        o = _conn_sample_solved(ctx, self._start, self.word, self.seg, self.length, self.radius, spacing, self.reversing)
+        if self.reversing:
+            return o['x'], o['y'], o['heading'], o['kappa'], o['gear'], o['offsets']
+        return o['x'], o['y'], o['heading'], o['kappa'], o['offsets']
+
+
+def clear_connectors(from_poses, to_poses, fields, pair_field, radius, reversing=False, device=None):
+    """Per pair from_poses[i] -> to_poses[i] the SHORTEST Dubins -- Reeds-Shepp if `reversing` -- word that stays inside field
+    pair_field[i] of `fields` (fcpp_conn_solve_clear; the rule: include/fcpp.h): the solvers' 6 / 48 candidates in the order (length,
+    word), each tested as connector_clearance tests the shortest one, the first clear one kept.  rank says which it was; rank -1: none is
+    clear and the shortest word is returned with its crossings.  pair_field: one index per pair (or one for all); -1 means no region.  One
+    word per pair -- no via points; a margin is no parameter: pass polygon_inset(fields, [margin]).as_fields(0).  -> ClearConnectors."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    pf = polygon_fields(fields, device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    n = int(f[0].numel())
+    if int(t[0].numel()) != n:
+        raise ValueError('from_poses and to_poses must hold the same number of poses')
+    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
+    if pair_field.numel() == 1 and n != 1:
+        pair_field = pair_field.expand(n)
+    if pair_field.numel() != n:
+        raise ValueError('pair_field must be a scalar or hold one field index per pair')
+    pair_field = pair_field.contiguous()
+    word = torch.empty(n, dtype=torch.int32, device=dev)
+    seg = torch.empty((n, 5 if reversing else 3), dtype=torch.float64, device=dev)
+    length = torch.empty(n, dtype=torch.float64, device=dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    crossings = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(pf.n, dtype=torch.int32, device=dev)
+    shortest = _conn_solve(ctx, f, t, radius, reversing)[2]
+    L.check(ctx.lib.fcpp_conn_solve_clear(ctx.handle, 1 if reversing else 0, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]),
+                                          float(radius), _ptr(pair_field), *pf._head(), _ptr(word), _ptr(seg), _ptr(length), _ptr(rank),
+                                          _ptr(crossings), _ptr(status)))
+    return ClearConnectors(word, seg, length, rank, crossings, shortest, status, float(radius), bool(reversing), f, device)
 
 
 @dataclass

@@ -655,7 +655,8 @@ int fcpp_route_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev,
  * Build-defined (the reference's connectors are straight lines that nothing tests).  Every connector of this library is the shortest Dubins or
  * Reeds-Shepp path between two poses and knows no boundary.  These entries TEST solved connectors against polygon fields -- exactly, piece
  * against edge, not by samples -- so that the swath router can avoid the blocked ones through its T / E / X arrays and what stays blocked is
- * reported.  No path is re-shaped.  Standalone like the router's entries; nothing here feeds fcpp_batch_plan.
+ * reported.  No path is re-shaped by THESE entries (fcpp_conn_solve_clear below chooses another word).  Standalone like the router's
+ * entries; nothing here feeds fcpp_batch_plan.
  * THE RULE (csrc/fcpp_clearfn.h, one set of expressions for host and device: the same bits on both).
  *   - Region: a field of the two-level CSR of the swath entries above -- rings, closed implicitly, either orientation, even-odd interior.
  *     Edge g of a ring runs from vertex g to the next (the last back to the first): the points A + t e, 0 <= t < 1, e = fl(B - A).  There
@@ -711,6 +712,39 @@ int fcpp_route_transit_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offs
                              double radius, int mode, const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total,
                              const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
                              const double *x_dev, const double *y_dev, double penalty, double *T_dev, uint8_t *B_dev);
+
+/* ---- clear connectors: per pair of poses the shortest word that stays off the field's rings -------------------------------------------------
+ * Build-defined.  The entries above test a SOLVED connector; this one chooses: both solvers evaluate every word of a pair (6 Dubins, 48
+ * Reeds-Shepp) and keep the shortest -- here the shortest one that is CLEAR of the pair's field is kept.  One word per pair, no via points, no
+ * detours along the headland, no margin (pass the inset).  Standalone like the clearance entries; nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).  Nothing geometric is added: the
+ * candidates come out of the solvers' own word enumerations and are tested by the clearance rule above.
+ *   - Candidates of a pair: the words the solver finds feasible with a finite total, each with exactly the seg and total bits
+ *     fcpp_dubins_solve / fcpp_rs_solve would write had that word won -- their rules at the edges unchanged (the 2^-43 angle snap, the 2^-48
+ *     feasibility bands, + 0.0 on Reeds-Shepp segments).  A pair the solvers leave unsolved (an input that is not finite) has none.
+ *   - Order: (total, word) ascending, the solvers' own tie rule.  The candidate at position 0 is the solvers' answer.
+ *   - A candidate is tested as fcpp_conn_clear tests a solved path against field pair_field[i]: clear = inside and crossings == 0.
+ *   - Result per pair: word (int32), seg (3 / 5 float64), len (float64, the word's total), rank, crossings (int32).
+ *       rank >= 0: the candidate at that position of the order is the first clear one; crossings 0.  rank 0 has the bits of the solvers.
+ *       rank -1:   no candidate is clear.  The SHORTEST word is returned -- the caller still has a drivable path -- with ITS crossings.
+ *                  `inside` belongs to the start point alone: a start that is not inside decides this for all words at once.
+ *       pair_field -1 ("no region"): the shortest word, rank 0, crossings 0.
+ *       an unsolved pair (word -1, seg and len NaN; whatever pair_field says, -1 included), a field whose status is FCPP_EINVAL, a field
+ *       index outside -1 .. n_fields - 1: rank -1 with the solvers' own output and crossings 0 -- fcpp_conn_clear's "unsolved path".
+ *   - word and seg feed fcpp_dubins_counts / _sample, fcpp_rs_counts / _sample and fcpp_conn_clear as they are.
+ * Two launches: a lane per pair solves and tests the shortest word and lists the pairs that are inside but cross; the call reads the list's
+ * length back and, unless it is 0, a second kernel looks at a listed pair's words with a lane per word.
+ * from_* / to_* (n float64 each), pair_field_dev (n int64), the fields' CSR as for fcpp_conn_clear.  word_dev, seg_dev, len_dev, rank_dev,
+ * crossings_dev (n each, seg 3 n or 5 n), field_status_dev (n_fields int32): any may be NULL.  Errors of the call as for fcpp_conn_clear;
+ * n is at most 2^31 - 1.  Synchronises. */
+int fcpp_conn_solve_clear(fcpp_ctx *ctx, int mode, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                          const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, const int64_t *pair_field_dev,
+                          int64_t n_fields, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                          const double *x_dev, const double *y_dev, int32_t *word_dev, double *seg_dev, double *len_dev, int32_t *rank_dev,
+                          int32_t *crossings_dev, int32_t *field_status_dev);
+/* listed: the pairs the first pass of this context's LAST fcpp_conn_solve_clear handed to the second; word_launches: the second-pass launches
+ * of all its calls so far (a call that lists nothing launches none).  Either may be NULL.  For tests. */
+int fcpp_ctx_solve_clear_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *word_launches);
 
 /* ---- field paths: every field's routed swaths and connectors as ONE sampled path per field ------------------------------------------------
  * Build-defined.  The last stage of the polygon-field chain (inset -> angle -> swaths -> route -> PATH), batched like the others: a counts
@@ -1020,6 +1054,18 @@ int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int6
                                    const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
                                    const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
                                    const double *y, double penalty, double *T, uint8_t *B);
+/* The clear-connector rule (csrc/fcpp_solveclearfn.h) evaluated on the HOST, on host pointers.  fcpp_debug_conn_words: ALL candidates of
+ * every pair -- ok (uint8), total (float64): n x W, seg: n x W x S float64, W = 6, S = 3 (mode 0) or W = 48, S = 5 (mode 1); a word that is
+ * no candidate has ok 0 and NaN.  Any output may be NULL.  Test infrastructure only.  fcpp_debug_conn_solve_clear: what
+ * fcpp_conn_solve_clear is compared with bit for bit; arguments, outputs and the call's errors as for it (the offsets are the host's).
+ * Pairs are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
+int fcpp_debug_conn_words(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                          const double *to_y, const double *to_h, double radius, uint8_t *ok, double *seg, double *total);
+int fcpp_debug_conn_solve_clear(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                                const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                                const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                const double *y, int32_t *word, double *seg, double *len, int32_t *rank, int32_t *crossings,
+                                int32_t *field_status);
 /* The field-path rule (csrc/fcpp_fpathfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device results
  * are compared with bit for bit.  Arguments and the call's errors as for fcpp_field_path_counts / _fill.  path_offsets (n + 1), leg_offsets
  * (2 n_total + n + 1), work_length, transit_length, status (n): any may be NULL.  leg_word, leg_seg (5 each), leg_total (2 n_total + n slots,
