@@ -185,6 +185,11 @@ PROTOTYPES = [
     ('fcpp_field_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 12),
     ('fcpp_field_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 7
      + [C.c_int64] + [_VP] * 7),
+    ('fcpp_field_path_counts_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6
+     + [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP] + [_VP] * 14),
+    ('fcpp_field_path_fill_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6
+     + [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP] + [_VP, C.c_int64] + [_VP] * 7),
+    ('fcpp_ctx_field_path_clear_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
     ('fcpp_headland_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
      + [_VP] * 7),
     ('fcpp_headland_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
@@ -215,6 +220,8 @@ PROTOTYPES = [
      + [_VP] * 8),
     ('fcpp_debug_field_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 14 + [C.c_int64]
      + [_VP] * 7),
+    ('fcpp_debug_field_paths_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6
+     + [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP] + [_VP] * 13 + [C.c_int64] + [_VP] * 7),
     ('fcpp_debug_headland_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
      + [_VP] * 10 + [C.c_int64] + [_VP] * 7),
     ('fcpp_debug_polygon_cover', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int64, _VP, C.c_int64]

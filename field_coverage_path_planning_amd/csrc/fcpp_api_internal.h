@@ -166,6 +166,8 @@ struct fcpp_ctx {
     int64_t direct_steps = 0, direct_taken = 0, direct_fills = 0;      // launched / batches taken / their fill passes enqueued later (fcpp_ctx_direct_steps: tests)
     // fcpp_conn_solve_clear: the pairs its first pass listed in the last call, and the second-pass launches so far (fcpp_ctx_solve_clear_passes: tests)
     int64_t solve_clear_listed = 0, solve_clear_word_launches = 0;
+    // fcpp_field_path_counts_clear / _fill_clear: the same two figures of the clear field paths (fcpp_ctx_field_path_clear_passes: tests)
+    int64_t fpath_clear_listed = 0, fpath_clear_word_launches = 0;
     // the stream the last device-side setup was enqueued on (its fill pass may still read the scratch): a setup on ANOTHER stream records
     // ev_plan there and waits for it -- lazily, when that other stream shows up: an event recorded between two kernels of the plan call
     // costs 5 us of device time between them (round 5: the three records of a plan call were 16 of its 158 us)

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "fcpp_routefn.h"
+#include "fcpp_solveclearfn.h"
 
 namespace fcpp {
 
@@ -65,6 +66,32 @@ FCPP_HD bool fpath_oriented(const int32_t *order, int64_t s0, int64_t m, int64_t
     return p >= 0 && (int64_t)p < 2 * m;
 }
 
+// The poses of the connector in (even) slot j of field i, 0 <= j <= 2 m, m > 0: from the exit pose of the leg before (or the field's entry
+// pose) to the entry pose of the leg behind (or the field's exit pose), route_pose's UNWRAPPED headings -- what fpath_leg hands to the solver
+// and the clear stage (below) to solve_clear.  false: the slot has no leg (no entry / exit pose) or, with invalid set, no poses (an order
+// entry out of range).
+FCPP_HD bool fpath_conn_poses(const FpathIn &in, int64_t i, int64_t j, double &x0, double &y0, double &h0, double &x1, double &y1, double &h1,
+                              bool &invalid)
+{
+    const int64_t s0 = in.soff[i], m = in.soff[i + 1] - s0;
+    const double *ax = in.ax + s0, *ay = in.ay + s0, *bx = in.bx + s0, *by = in.by + s0;
+    const double theta = in.angle[i];
+    const bool entry = j == 0, exit = j == 2 * m;
+    if ((entry && !in.ex) || (exit && !in.xx)) return false;
+    int p;
+    if (entry) { x0 = in.ex[i]; y0 = in.ey[i]; h0 = in.eh[i]; }
+    else {
+        if (!fpath_oriented(in.order, s0, m, j / 2 - 1, p)) { invalid = true; return false; }
+        route_pose(ax, ay, bx, by, theta, p, true, x0, y0, h0);
+    }
+    if (exit) { x1 = in.xx[i]; y1 = in.xy[i]; h1 = in.xh[i]; }
+    else {
+        if (!fpath_oriented(in.order, s0, m, j / 2, p)) { invalid = true; return false; }
+        route_pose(ax, ay, bx, by, theta, p, false, x1, y1, h1);
+    }
+    return true;
+}
+
 // Slot j of field i: its record, and -> its sample count (0 without a leg, FPATH_OVERSIZE).  invalid: the slot makes its field EINVAL
 // (an order entry out of range, a bad length, an unsolvable connector); a swath named twice is the caller's to find (it needs all slots).
 template <int MODE>
@@ -76,10 +103,10 @@ FCPP_HD int64_t fpath_leg(const FpathIn &in, int64_t i, int64_t j, FpathLeg &leg
     for (int k = 0; k < 5; ++k) leg.seg[k] = 0.0;
     invalid = false;
     if (m <= 0 || j < 0 || j > 2 * m) return 0;
-    const double *ax = in.ax + s0, *ay = in.ay + s0, *bx = in.bx + s0, *by = in.by + s0;
-    const double theta = in.angle[i];
     int64_t bad = 0;
     if (j & 1) {
+        const double *ax = in.ax + s0, *ay = in.ay + s0, *bx = in.bx + s0, *by = in.by + s0;
+        const double theta = in.angle[i];
         int p;
         if (!fpath_oriented(in.order, s0, m, (j - 1) / 2, p)) { invalid = true; return 0; }
         const double len = in.length[s0 + (p >> 1)];
@@ -93,20 +120,9 @@ FCPP_HD int64_t fpath_leg(const FpathIn &in, int64_t i, int64_t j, FpathLeg &leg
         const int64_t K = sample_count(len, in.spacing, true, false, bad);
         return bad ? FPATH_OVERSIZE : K;
     }
-    const bool entry = j == 0, exit = j == 2 * m;
-    if ((entry && !in.ex) || (exit && !in.xx)) return 0;
     double x0, y0, h0, x1, y1, h1;
-    int p;
-    if (entry) { x0 = in.ex[i]; y0 = in.ey[i]; h0 = in.eh[i]; }
-    else {
-        if (!fpath_oriented(in.order, s0, m, j / 2 - 1, p)) { invalid = true; return 0; }
-        route_pose(ax, ay, bx, by, theta, p, true, x0, y0, h0);
-    }
-    if (exit) { x1 = in.xx[i]; y1 = in.xy[i]; h1 = in.xh[i]; }
-    else {
-        if (!fpath_oriented(in.order, s0, m, j / 2, p)) { invalid = true; return 0; }
-        route_pose(ax, ay, bx, by, theta, p, false, x1, y1, h1);
-    }
+    if (!fpath_conn_poses(in, i, j, x0, y0, h0, x1, y1, h1, invalid)) return 0;
+    const bool entry = j == 0, exit = j == 2 * m;
     leg.part = entry ? FPATH_PART_ENTRY : (exit ? FPATH_PART_EXIT : FPATH_PART_BETWEEN);
     leg.x0 = x0; leg.y0 = y0; leg.h0 = h0;
     int word;
@@ -162,11 +178,17 @@ inline bool leg_counts_host(int64_t *cnt, int64_t n_slots, bool ok)
 
 // ---- the host twin: one field ---------------------------------------------------------------------------------------------------------
 // legs, cnt: the field's 2 m + 1 slots; seen: m entries of scratch.  -> the status; a failed field's counts are 0, its totals NaN.
-template <int MODE>
-inline int fpath_field_host(const FpathIn &in, int64_t i, FpathLeg *legs, int64_t *cnt, int32_t *seen, double &work, double &transit,
-                            bool &oversize)
+inline int64_t fpath_field_slots(const FpathIn &in, int64_t i)
 {
-    const int64_t s0 = in.soff[i], m = in.soff[i + 1] - s0, n_slots = 2 * (m > 0 ? m : 0) + 1;
+    const int64_t m = in.soff[i + 1] - in.soff[i];
+    return 2 * (m > 0 ? m : 0) + 1;
+}
+
+// the records and raw counts of the field's slots -> the status
+template <int MODE>
+inline int fpath_field_records(const FpathIn &in, int64_t i, FpathLeg *legs, int64_t *cnt, int32_t *seen)
+{
+    const int64_t s0 = in.soff[i], m = in.soff[i + 1] - s0, n_slots = fpath_field_slots(in, i);
     int status = FPATH_OK;
     for (int64_t k = 0; k < m; ++k) seen[k] = 0;
     for (int64_t j = 0; j < n_slots; ++j) {
@@ -175,9 +197,72 @@ inline int fpath_field_host(const FpathIn &in, int64_t i, FpathLeg *legs, int64_
         if (!invalid && in.order && (j & 1) && m > 0 && seen[in.order[s0 + (j - 1) / 2] >> 1]++ != 0) invalid = true;
         if (invalid) status = FPATH_EINVAL;
     }
-    oversize = leg_counts_host(cnt, n_slots, status == FPATH_OK);
-    if (status == FPATH_OK) fpath_totals(legs, m, in.ex != nullptr, in.xx != nullptr, work, transit);
+    return status;
+}
+
+// the counts as the scan takes them and the totals, from the records
+inline void fpath_field_finish(const FpathIn &in, int64_t i, int status, const FpathLeg *legs, int64_t *cnt, double &work, double &transit,
+                               bool &oversize)
+{
+    oversize = leg_counts_host(cnt, fpath_field_slots(in, i), status == FPATH_OK);
+    if (status == FPATH_OK) fpath_totals(legs, in.soff[i + 1] - in.soff[i], in.ex != nullptr, in.xx != nullptr, work, transit);
     else work = transit = __builtin_nan("");
+}
+
+template <int MODE>
+inline int fpath_field_host(const FpathIn &in, int64_t i, FpathLeg *legs, int64_t *cnt, int32_t *seen, double &work, double &transit,
+                            bool &oversize)
+{
+    const int status = fpath_field_records<MODE>(in, i, legs, cnt, seen);
+    fpath_field_finish(in, i, status, legs, cnt, work, transit, oversize);
+    return status;
+}
+
+// ---- the CLEAR field paths: drive, per connector, the shortest word that stays off the field's region ---------------------------------
+// THE CLEAR RULE (include/fcpp.h states it for callers).  The field paths above with ONE difference: in a field of status OK the record of
+// every connector slot -- word, seg, total -- is what solve_clear<MODE> (fcpp_solveclearfn.h) gives for the slot's poses
+// (fpath_conn_poses), R and field i of a region CSR (field i of the swaths is field i of the CSR).  rank >= 0: that candidate of the pair,
+// rank 0 the record as it was.  rank -1 (no candidate clear, a start outside the region, a region field of status CLEAR_EINVAL): the
+// shortest word, as it was, with its crossings -- the leg is still driven.  Counts, samples, junctions, part / gear / leg and the totals
+// follow from the records as above.  Per slot rank and crossings: 0 on a swath slot, a slot without a leg and in a field that is EINVAL
+// (whose records stay what the rule above made them).  Per field blocked = its legs of rank -1, reshaped = its legs of rank > 0.
+// The device (fcpp_solveclear.hip) does not solve again: it tests the record's word (solve_clear_test, as solve_clear_first does) and
+// looks at the other words with a lane per word; the bits are solve_clear's.
+FCPP_HD bool fpath_is_conn(const FpathLeg &leg) { return (leg.kind == FPATH_DUBINS || leg.kind == FPATH_RS) && leg.word >= 0; }
+
+// a chosen word into a connector's record -> its sample count
+template <int MODE>
+FCPP_HD int64_t fpath_set_word(FpathLeg &leg, int word, const double *seg, double total, double spacing)
+{
+    leg.word = word;
+    for (int k = 0; k < Conn<MODE>::NSEG; ++k) leg.seg[k] = seg[k];
+    leg.total = total;
+    int64_t bad = 0;
+    const int64_t K = Conn<MODE>::count(word, leg.seg, spacing, bad);
+    return bad ? FPATH_OVERSIZE : K;
+}
+
+// rank, crossings: the field's 2 m + 1 slots; the rest as fpath_field_host
+template <int MODE>
+inline int fpath_field_clear_host(const FpathIn &in, const ClearFields &F, int64_t i, FpathLeg *legs, int64_t *cnt, int32_t *seen, int32_t *rank,
+                                  int32_t *crossings, int32_t &blocked, int32_t &reshaped, double &work, double &transit, bool &oversize)
+{
+    const int64_t n_slots = fpath_field_slots(in, i);
+    const int status = fpath_field_records<MODE>(in, i, legs, cnt, seen);
+    blocked = reshaped = 0;
+    for (int64_t j = 0; j < n_slots; ++j) rank[j] = crossings[j] = 0;
+    for (int64_t j = 0; status == FPATH_OK && j < n_slots; j += 2) {
+        if (!fpath_is_conn(legs[j])) continue;
+        double x0, y0, h0, x1, y1, h1;
+        bool invalid = false;
+        if (!fpath_conn_poses(in, i, j, x0, y0, h0, x1, y1, h1, invalid)) continue;      // (the record exists: so do the poses)
+        const SolveClearResult r = solve_clear<MODE>(F, i, x0, y0, h0, x1, y1, h1, in.R);
+        if (r.word < 0) continue;                                                        // (the record is solved: so is r)
+        cnt[j] = fpath_set_word<MODE>(legs[j], r.word, r.seg, r.len, in.spacing);
+        rank[j] = r.rank; crossings[j] = r.crossings;
+        blocked += r.rank < 0; reshaped += r.rank > 0;
+    }
+    fpath_field_finish(in, i, status, legs, cnt, work, transit, oversize);
     return status;
 }
 

@@ -2,7 +2,8 @@
 // (rule and leg set: fcpp_fpathfn.h, FieldLegs) and the headland paths (fcpp_hpathfn.h, RingLegs).  Both are records -> scan -> groups ->
 // samples: a group (a field, a ring) owns a run of leg slots, a rule kernel writes a record and a sample count per slot, the counts are
 // scanned into slot offsets, a lane per group writes its path offset and totals, a lane per sample evaluates its slot's record.  Only the
-// rule kernels (launch_legs) and what precedes the scan (launch_leg_offsets) are an operator's own.
+// rule kernels (launch_legs) and what precedes the scan (launch_leg_offsets) are an operator's own.  The clear field paths put one stage
+// between the fields' records and the scan (fcpp_solveclear.h: launch_fpath_clear_*); nothing here changes for it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

@@ -473,9 +473,15 @@ int hpath_args(int64_t n_rings, const void *ring_offsets, int64_t n_verts, const
 // launch of the rule kernel) instead of keeping the counts call's in the context: the entries stay stateless, and the solves are a small
 // part of the samples' cost.
 // *_counts: the temporaries (n_scratch: the int32 scratch of the rule kernel), the call's own status buffer when the caller passes none
-template <class P>
+// stage(stream, legs, cnt, status) -> 0 or a hipError_t value: what an entry does to the records between the rule kernel and the scan
+struct NoLegStage {
+    template <class Leg> int operator()(hipStream_t, Leg *, int64_t *, const int32_t *) const { return 0; }
+};
+
+template <class P, class Stage = NoLegStage>
 int legs_counts(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, int64_t n_scratch, const typename P::In &in, int mode, const char *esize,
-                int64_t *path_offsets, int64_t *path_offsets_host, int64_t *leg_offsets, const LegTotals &totals, int32_t *status)
+                int64_t *path_offsets, int64_t *path_offsets_host, int64_t *leg_offsets, const LegTotals &totals, int32_t *status,
+                Stage &&stage = Stage())
 {
     DevBuf<typename P::Leg> legs;
     DevBuf<int64_t> cnt;
@@ -487,7 +493,8 @@ int legs_counts(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, int64_t n_scratc
     return sample_counts(c, n_groups, path_offsets, path_offsets_host, esize, [&](hipStream_t st, int64_t *err) {
         if (n_scratch > 0) { const hipError_t e = hipMemsetAsync(scratch.p, 0, (size_t)n_scratch * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
         if (n_groups > 0) { const hipError_t e = hipMemsetAsync(status, 0, (size_t)n_groups * sizeof(int32_t), st); if (e != hipSuccess) return (int)e; }
-        const int e = launch_legs(st, n_groups, n_slots, in, mode, legs.p, cnt.p, scratch.p, status);
+        int e = launch_legs(st, n_groups, n_slots, in, mode, legs.p, cnt.p, scratch.p, status);
+        if (e == 0) e = stage(st, legs.p, cnt.p, status);
         return e ? e : launch_leg_offsets(st, n_groups, n_slots, in, legs.p, cnt.p, status, scratch.p, leg_offsets, path_offsets, totals, err);
     });      // (sample_counts has drained the stream: the temporaries die here)
 }
@@ -495,9 +502,9 @@ int legs_counts(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, int64_t n_scratc
 // *_fill.  The ends of the slot offsets must match the output arrays.  (The fill writes sample q < total_samples of every array and reads
 // the record of a slot below n_slots whatever lies between the ends: offsets that are not the counts call's give wrong samples, never an
 // access outside the arrays.)
-template <class P>
+template <class P, class Stage = NoLegStage>
 int legs_fill(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, const typename P::In &in, int mode, const int64_t *leg_offsets, int64_t total_samples,
-              double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+              double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg, Stage &&stage = Stage())
 {
     int64_t ends[2] = { 0, 0 };
     HIPCHK(hipMemcpyAsync(&ends[0], leg_offsets, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -507,6 +514,7 @@ int legs_fill(fcpp_ctx *c, int64_t n_groups, int64_t n_slots, const typename P::
     DevBuf<typename P::Leg> legs;
     HIPCHK(legs.alloc((size_t)n_slots));
     LAUNCHCHK(launch_legs(c->stream, n_groups, n_slots, in, mode, legs.p, nullptr, nullptr, nullptr));
+    LAUNCHCHK(stage(c->stream, legs.p, (int64_t *)nullptr, (const int32_t *)nullptr));
     LAUNCHCHK(launch_leg_fill<P>(c->stream, n_slots, legs.p, leg_offsets, total_samples, in.R, in.spacing, x, y, heading, kappa, part, gear, leg));
     HIPCHK(hipStreamSynchronize(c->stream));      // (the records die here)
     return FCPP_OK;
@@ -569,6 +577,60 @@ int legs_host(int64_t n_groups, int64_t n_slots, const typename P::In &in, const
             }
         }
     });
+    return FCPP_OK;
+}
+
+// ---- the clear field paths: what the records go through between the rule kernel and the scan (kernels: fcpp_solveclear.hip) -----------------
+// First pass, the list's length read back, the second pass unless it is 0, then (a counts call) the per-slot and per-field reports.  The
+// fill passes no outputs: records only.  The buffers live in the stage, which outlives the entry's last synchronisation.
+struct FpathClearStage {
+    fcpp_ctx *c;
+    int mode;
+    int64_t n, n_total;
+    FpathIn in;
+    ClearFields F;
+    int32_t *rank = nullptr, *crossings = nullptr, *leg_word = nullptr;
+    double *leg_seg = nullptr, *leg_total = nullptr;
+    int32_t *blocked = nullptr, *reshaped = nullptr, *region_status = nullptr;
+    DevBuf<int64_t> list;
+    DevBuf<unsigned long long> count;
+    DevBuf<int32_t> own_rank;
+
+    int operator()(hipStream_t st, FpathLeg *legs, int64_t *cnt, const int32_t *status)
+    {
+        const int64_t n_conn = n_total + n, n_slots = 2 * n_total + n;
+        c->fpath_clear_listed = 0;
+        if (n <= 0) return 0;
+        hipError_t e = (hipError_t)launch_clear_field_status(st, F, region_status);
+        if (e == hipSuccess) e = list.alloc((size_t)n_conn);
+        if (e == hipSuccess) e = count.alloc(1);
+        if (e == hipSuccess && !rank && (blocked || reshaped)) { e = own_rank.alloc((size_t)n_slots); rank = own_rank.p; }
+        if (e == hipSuccess) e = hipMemsetAsync(count.p, 0, sizeof(unsigned long long), st);
+        if (e == hipSuccess && rank) e = hipMemsetAsync(rank, 0, (size_t)n_slots * sizeof(int32_t), st);
+        if (e == hipSuccess && crossings) e = hipMemsetAsync(crossings, 0, (size_t)n_slots * sizeof(int32_t), st);
+        if (e != hipSuccess) return (int)e;
+        int rc = launch_fpath_clear_slots(st, mode, n, n_conn, in.soff, in.R, legs, status, F, rank, crossings, list.p, count.p);
+        if (rc) return rc;
+        unsigned long long listed = 0;
+        e = hipMemcpyAsync(&listed, count.p, sizeof listed, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return (int)e;
+        if (listed > (unsigned long long)n_conn) return (int)hipErrorUnknown;      // (more slots listed than there are)
+        c->fpath_clear_listed = (int64_t)listed;
+        if (listed > 0) {
+            rc = launch_fpath_clear_words(st, mode, (int64_t)listed, list.p, in, F, legs, cnt, rank, crossings);
+            if (rc) return rc;
+            ++c->fpath_clear_word_launches;
+        }
+        return launch_fpath_clear_report(st, n, n_slots, in.soff, legs, rank, leg_word, leg_seg, leg_total, blocked, reshaped);
+    }
+};
+
+// the region CSR of the clear field paths: what fcpp_conn_clear checks of its fields, for n fields
+int fpath_region_args(int64_t n, const void *ring_offsets, int64_t n_rings, const void *vert_offsets, int64_t n_verts, const double *x, const double *y)
+{
+    if (!ring_offsets || !vert_offsets || (n_verts > 0 && (!x || !y))) return fail(FCPP_EINVAL, "bad arguments");
+    if (n < 0 || n_rings < 0 || n_verts < 0) return fail(FCPP_ESIZE, "bad sizes");
     return FCPP_OK;
 }
 }  // namespace
@@ -1435,6 +1497,114 @@ int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_to
                                 },
                                 path_offsets, leg_offsets, { { work_length, transit_length, nullptr } }, status, nullptr, leg_word, leg_seg, leg_total, cap,
                                 x, y, heading, kappa, part, gear, leg);
+}
+
+// ---- the clear field paths: the entries above with the region CSR and the stage between the records and the scan ----------------------------
+int fcpp_field_path_counts_clear(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                                 const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,
+                                 const int32_t *order, double radius, int mode, double spacing, const double *entry_x, const double *entry_y,
+                                 const double *entry_h, const double *exit_x, const double *exit_y, const double *exit_h,
+                                 const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                 const double *y, int64_t *path_offsets, int64_t *path_offsets_host, int64_t *leg_offsets, double *work_length,
+                                 double *transit_length, int32_t *status, int32_t *leg_rank, int32_t *leg_crossings, int32_t *leg_word,
+                                 double *leg_seg, double *leg_total, int32_t *blocked, int32_t *reshaped, int32_t *region_status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!path_offsets || !leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc == FCPP_OK) rc = fpath_region_args(n, ring_offsets, n_rings, vert_offsets, n_verts, x, y);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, rings, verts;
+    rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    FpathClearStage stage = { c, mode, n, n_total, in, { n, ring_offsets, vert_offsets, x, y } };
+    stage.rank = leg_rank; stage.crossings = leg_crossings; stage.leg_word = leg_word; stage.leg_seg = leg_seg; stage.leg_total = leg_total;
+    stage.blocked = blocked; stage.reshaped = reshaped; stage.region_status = region_status;
+    return legs_counts<FieldLegs>(c, n, n > 0 ? 2 * n_total + n : 0, n_total, in, mode, "a leg or a field has 2^31 samples or more", path_offsets,
+                                  path_offsets_host, leg_offsets, { { work_length, transit_length, nullptr } }, status, stage);
+}
+
+int fcpp_field_path_fill_clear(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                               const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,
+                               const int32_t *order, double radius, int mode, double spacing, const double *entry_x, const double *entry_y,
+                               const double *entry_h, const double *exit_x, const double *exit_y, const double *exit_h,
+                               const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *rx,
+                               const double *ry, const int64_t *leg_offsets, int64_t total_samples, double *x, double *y, double *heading,
+                               double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if (!leg_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc == FCPP_OK) rc = fpath_region_args(n, ring_offsets, n_rings, vert_offsets, n_verts, rx, ry);
+    if (rc == FCPP_OK && (total_samples < 0 || total_samples > ((int64_t)1 << 38))) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, rings, verts;
+    rc = fpath_offsets(c, n, swath_offsets, swath_offsets_host, n_total, angle, nullptr, soff);
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc) return rc;
+    const FpathIn in = { swath_offsets, ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    FpathClearStage stage = { c, mode, n, n_total, in, { n, ring_offsets, vert_offsets, rx, ry } };
+    return legs_fill<FieldLegs>(c, n, n > 0 ? 2 * n_total + n : 0, in, mode, leg_offsets, total_samples, x, y, heading, kappa, part, gear, leg, stage);
+}
+
+int fcpp_ctx_field_path_clear_passes(const fcpp_ctx *c, int64_t *listed, int64_t *word_launches)
+{
+    if (!c) return fail(FCPP_EINVAL, "ctx is NULL");
+    if (listed) *listed = c->fpath_clear_listed;
+    if (word_launches) *word_launches = c->fpath_clear_word_launches;
+    return FCPP_OK;
+}
+
+int fcpp_debug_field_paths_clear(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                 const double *by, const double *length, const double *angle, const int32_t *order, double radius, int mode,
+                                 double spacing, const double *entry_x, const double *entry_y, const double *entry_h, const double *exit_x,
+                                 const double *exit_y, const double *exit_h, const int64_t *ring_offsets, int64_t n_rings,
+                                 const int64_t *vert_offsets, int64_t n_verts, const double *rx, const double *ry, int64_t *path_offsets,
+                                 int64_t *leg_offsets, double *work_length, double *transit_length, int32_t *status, int32_t *leg_rank,
+                                 int32_t *leg_crossings, int32_t *leg_word, double *leg_seg, double *leg_total, int32_t *blocked,
+                                 int32_t *reshaped, int32_t *region_status, int64_t cap, double *x, double *y, double *heading, double *kappa,
+                                 int8_t *part, int8_t *gear, int32_t *leg)
+{
+    int rc = fpath_args(n, swath_offsets, n_total, ax, ay, bx, by, length, angle, radius, mode, spacing, entry_x, entry_y, entry_h, exit_x, exit_y,
+                        exit_h);
+    if (rc == FCPP_OK) rc = fpath_region_args(n, ring_offsets, n_rings, vert_offsets, n_verts, rx, ry);
+    if (rc == FCPP_OK && cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> soff, rings, verts;
+    rc = fpath_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, angle, soff);
+    if (rc == FCPP_OK) rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc) return rc;
+    const FpathIn in = { soff.data(), ax, ay, bx, by, length, angle, order, radius, spacing, entry_x, entry_y, entry_h, exit_x, exit_y, exit_h };
+    const ClearFields F = { n, ring_offsets, vert_offsets, rx, ry };
+    const int64_t n_slots = n > 0 ? 2 * n_total + n : 0;
+    std::vector<int32_t> seen, rank, cross;
+    try {
+        seen.assign((size_t)n_total, 0); rank.assign((size_t)n_slots, 0); cross.assign((size_t)n_slots, 0);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (region_status) WorkerPool::parallel_for(n, [&](int64_t f) { region_status[f] = clear_field_status(F, f); });
+    rc = legs_host<FieldLegs>(n, n_slots, in, "a leg or a field has 2^31 samples or more",
+                              [&](int64_t i, FpathLeg *legs, int64_t *cnt, double *t, bool &oversize) {
+                                  int32_t *sn = seen.data() + soff[(size_t)i];
+                                  int32_t *rk = rank.data() + fpath_first_slot(soff.data(), i), *cr = cross.data() + fpath_first_slot(soff.data(), i);
+                                  int32_t b, r;
+                                  const int st = mode == 0 ? fpath_field_clear_host<0>(in, F, i, legs, cnt, sn, rk, cr, b, r, t[0], t[1], oversize)
+                                                           : fpath_field_clear_host<1>(in, F, i, legs, cnt, sn, rk, cr, b, r, t[0], t[1], oversize);
+                                  if (blocked) blocked[i] = b;
+                                  if (reshaped) reshaped[i] = r;
+                                  return st;
+                              },
+                              path_offsets, leg_offsets, { { work_length, transit_length, nullptr } }, status, nullptr, leg_word, leg_seg, leg_total, cap,
+                              x, y, heading, kappa, part, gear, leg);
+    if (rc) return rc;
+    if (leg_rank && n_slots > 0) memcpy(leg_rank, rank.data(), rank.size() * sizeof(int32_t));
+    if (leg_crossings && n_slots > 0) memcpy(leg_crossings, cross.data(), cross.size() * sizeof(int32_t));
+    return FCPP_OK;
 }
 
 int fcpp_headland_path_counts(fcpp_ctx *c, int64_t n_rings, const int64_t *ring_offsets, const int64_t *ring_offsets_host, int64_t n_verts,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "fcpp_fpathfn.h"
 #include "fcpp_solveclearfn.h"
 
 namespace fcpp {
@@ -26,5 +27,21 @@ int launch_solve_clear_pairs(hipStream_t st, int mode, int64_t n, const SolveCle
                              unsigned long long *count);
 // Second pass, a group of lanes per listed pair (8 for mode 0, 64 for mode 1), a lane per word.
 int launch_solve_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const SolveClearIo &io, double R, const ClearFields &F);
+
+// The clear field paths (the rule: fcpp_fpathfn.h): the same two passes over the connector slots of the leg records launch_legs wrote
+// (legs, cnt: 2 n_total + n slots; F: the region CSR, field i of the swaths is field i of it; n_conn = n_total + n connector slots).
+// rank, crossings (per slot, zeroed by the caller), status (the fields' path status) and cnt may be NULL: records only (the fill's pass).
+// First pass, a lane per connector slot: the record's word tested, rank and crossings written, the slots to look at appended to list
+// (room for n_conn), their number added to *count (zeroed by the caller).
+int launch_fpath_clear_slots(hipStream_t st, int mode, int64_t n, int64_t n_conn, const int64_t *soff, double R, const FpathLeg *legs,
+                             const int32_t *status, const ClearFields &F, int32_t *rank, int32_t *crossings, int64_t *list,
+                             unsigned long long *count);
+// Second pass, a group of lanes per listed slot: the winner's word into the record, its count, rank and crossings.
+int launch_fpath_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const FpathIn &in, const ClearFields &F, FpathLeg *legs,
+                             int64_t *cnt, int32_t *rank, int32_t *crossings);
+// A lane per slot: the records' word, seg (5 each) and total; a lane per field: blocked and reshaped from rank.  Any output may be NULL
+// (rank NULL: no blocked / reshaped).
+int launch_fpath_clear_report(hipStream_t st, int64_t n, int64_t n_slots, const int64_t *soff, const FpathLeg *legs, const int32_t *rank,
+                              int32_t *leg_word, double *leg_seg, double *leg_total, int32_t *blocked, int32_t *reshaped);
 
 }  // namespace fcpp

@@ -20,16 +20,24 @@
 // the winner, counted from a ballot.  The winner's lane overwrites the pair's result -- when no word is clear the winner is the shortest
 // word and what it writes is what the first pass wrote.  No result depends on the list's order and no entry has two writers in a launch.
 // No lane leaves before the shuffles: lanes without a pair or a word carry the key of an infeasible word and write nothing.
+//
+// The CLEAR FIELD PATHS (fcpp_field_path_counts_clear / _fill_clear) run the same two passes over the connector slots of the leg records
+// k_fpath_legs wrote: k_fpath_clear_slots and k_fpath_clear_words below share the append (solve_clear_append) and the whole second-pass
+// body (solve_clear_group) with the two kernels above; only where the poses come from and where the winner writes differ.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_samplefn.h"
 #include "fcpp_solveclear.h"
 #include "fcpp_solveclearfn.h"
 
 namespace fcpp {
 
 static constexpr int SBLOCK = SOLVECLEAR_BLOCK;
+
+// the lanes of a second-pass group: a lane per word, a power of two, within a wavefront
+template <int MODE> struct SolveClearGroup { static constexpr int G = MODE == 0 ? 8 : 64; };
 
 #define SOLVECLEAR_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
@@ -46,45 +54,49 @@ __device__ __forceinline__ void solve_clear_store(const SolveClearIo &io, int64_
     if (io.crossings) io.crossings[i] = crossings;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(SBLOCK) void k_solve_clear_pairs(int64_t n, SolveClearIo io, double R, ClearFields F, int64_t *__restrict__ list,
-                                                              unsigned long long *__restrict__ count)
+// The append of both first passes.  Called by every lane of the wavefront; `more` lanes get a place each.
+__device__ __forceinline__ void solve_clear_append(bool more, int64_t item, int64_t *__restrict__ list, unsigned long long *__restrict__ count)
 {
-    constexpr int NSEG = Conn<MODE>::NSEG;
-    const int64_t i = (int64_t)blockIdx.x * SBLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    bool more = false;
-    if (i < n) {
-        SolveClearResult r;
-        more = solve_clear_first<MODE>(F, io.pair_field[i], io.fx[i], io.fy[i], io.fh[i], io.tx[i], io.ty[i], io.th[i], R, r);
-        solve_clear_store<NSEG>(io, i, r.word, r.seg, r.len, r.rank, r.crossings);
-    }
     const unsigned long long m = __ballot(more);
     if (m == 0) return;                                   // (uniform over the wavefront)
     const int leader = __ffsll((long long)m) - 1;
     unsigned long long base = 0;
     if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(m));
     base = __shfl(base, leader);
-    // (at most one entry per pair: base + position < n, the room the caller gave)
-    if (more) list[base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = i;
+    // (at most one entry per item: base + position stays below the room the caller gave)
+    if (more) list[base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = item;
 }
 
 template <int MODE>
-__global__ __launch_bounds__(SBLOCK) void k_solve_clear_words(int64_t count, const int64_t *__restrict__ list, SolveClearIo io, double R, ClearFields F)
+__global__ __launch_bounds__(SBLOCK) void k_solve_clear_pairs(int64_t n, SolveClearIo io, double R, ClearFields F, int64_t *__restrict__ list,
+                                                              unsigned long long *__restrict__ count)
 {
-    constexpr int NSEG = Conn<MODE>::NSEG, NW = SolveClearWords<MODE>::NW, G = MODE == 0 ? 8 : 64;
+    constexpr int NSEG = Conn<MODE>::NSEG;
+    const int64_t i = (int64_t)blockIdx.x * SBLOCK + threadIdx.x;
+    bool more = false;
+    if (i < n) {
+        SolveClearResult r;
+        more = solve_clear_first<MODE>(F, io.pair_field[i], io.fx[i], io.fy[i], io.fh[i], io.tx[i], io.ty[i], io.th[i], R, r);
+        solve_clear_store<NSEG>(io, i, r.word, r.seg, r.len, r.rank, r.crossings);
+    }
+    solve_clear_append(more, i, list, count);
+}
+
+// The body of both second passes: lane w of a group of G looks at word w of the group's pair (have: the group has one; f its field, a
+// valid one) and the group's winner hands (word, seg, total, rank, crossings) to store.  Called by every lane of the wavefront.
+template <int MODE, class Store>
+__device__ __forceinline__ void solve_clear_group(bool have, int64_t f, double x0, double y0, double h0, double x1, double y1, double h1, double R,
+                                                  const ClearFields &F, const Store &store)
+{
+    constexpr int NW = SolveClearWords<MODE>::NW, G = SolveClearGroup<MODE>::G;
     static_assert(NW <= G && 64 % G == 0 && SBLOCK % G == 0, "a lane per word, groups within a wavefront");
-    const int64_t t = (int64_t)blockIdx.x * SBLOCK + threadIdx.x, j = t / G;
     const int lane = threadIdx.x & 63, w = lane & (G - 1);
-    const bool have = j < count;
-    const int64_t i = have ? list[j] : 0;
-    const double x0 = have ? io.fx[i] : 0.0, y0 = have ? io.fy[i] : 0.0, h0 = have ? io.fh[i] : 0.0;
 
     SolveClearOne<MODE> one(w);
     int key = 2, crossings = 0;                           // 0 clear, 1 not clear, 2 no candidate
     if (have && w < NW) {
-        const int64_t f = io.pair_field[i];
-        const bool fin = solve_clear_words<MODE>(x0, y0, h0, io.tx[i], io.ty[i], io.th[i], R, one);
+        const bool fin = solve_clear_words<MODE>(x0, y0, h0, x1, y1, h1, R, one);
         // (a listed pair is solved and names a valid field; checked again so that a lane never walks a field that is not there)
         if (fin && one.ok && f >= 0 && f < F.n) {
             bool valid;
@@ -108,7 +120,115 @@ __global__ __launch_bounds__(SBLOCK) void k_solve_clear_words(int64_t count, con
     const unsigned long long mask = __ballot(before);
     const unsigned long long group = G == 64 ? mask : (mask >> (lane & ~(G - 1))) & ((1ull << G) - 1ull);
     if (!have || bk == 2 || w != bw) return;
-    solve_clear_store<NSEG>(io, i, w, one.seg, one.total, bk == 0 ? (int)__popcll(group) : -1, bk == 0 ? 0 : crossings);
+    store(w, one.seg, one.total, bk == 0 ? (int)__popcll(group) : -1, bk == 0 ? 0 : crossings);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(SBLOCK) void k_solve_clear_words(int64_t count, const int64_t *__restrict__ list, SolveClearIo io, double R, ClearFields F)
+{
+    constexpr int NSEG = Conn<MODE>::NSEG, G = SolveClearGroup<MODE>::G;
+    const int64_t t = (int64_t)blockIdx.x * SBLOCK + threadIdx.x, j = t / G;
+    const bool have = j < count;
+    const int64_t i = have ? list[j] : 0;
+    const double x0 = have ? io.fx[i] : 0.0, y0 = have ? io.fy[i] : 0.0, h0 = have ? io.fh[i] : 0.0;
+    const double x1 = have ? io.tx[i] : 0.0, y1 = have ? io.ty[i] : 0.0, h1 = have ? io.th[i] : 0.0;
+    solve_clear_group<MODE>(have, have ? io.pair_field[i] : -1, x0, y0, h0, x1, y1, h1, R, F,
+                            [&](int word, const double *seg, double total, int rank, int crossings) {
+                                solve_clear_store<NSEG>(io, i, word, seg, total, rank, crossings);
+                            });
+}
+
+// ---- the clear field paths (the rule: fcpp_fpathfn.h) -- between k_fpath_legs and the scan ------------------------------------------------
+// k_fpath_clear_slots, a lane per CONNECTOR slot: field i owns m_i + 1 of them, the field by bisection of soff[i] + i.  The lane does not
+// solve: word, seg and start pose are the record's, as k_fpath_legs wrote it; it tests that word against field i of the region
+// (solve_clear_test), writes the slot's rank and crossings by solve_clear_first's decision rules and appends a slot whose word starts
+// inside a valid region field but crosses (solve_clear_append).  Slots without a solved connector and fields that failed are skipped: their
+// rank and crossings stay the 0 the call set.  Against fcpp_conn_solve_clear on the legs' poses this saves the second solve of every
+// connector -- the record already holds the shortest word -- and the gather of six pose arrays and a field index per leg on the host side;
+// static reasoning, nothing measured.
+template <int MODE>
+__global__ __launch_bounds__(SBLOCK) void k_fpath_clear_slots(int64_t n, int64_t n_conn, const int64_t *__restrict__ soff, double R,
+                                                              const FpathLeg *__restrict__ legs, const int32_t *__restrict__ status, ClearFields F,
+                                                              int32_t *__restrict__ rank, int32_t *__restrict__ crossings,
+                                                              int64_t *__restrict__ list, unsigned long long *__restrict__ count)
+{
+    const int64_t c = (int64_t)blockIdx.x * SBLOCK + threadIdx.x;
+    bool more = false;
+    int64_t p = 0;
+    if (c < n_conn) {
+        const int64_t i = last_at_or_before(n, c, [&](int64_t f) { return soff[f] + f; });      // the field that holds connector slot c
+        p = fpath_first_slot(soff, i) + 2 * (c - (soff[i] + i));
+        const FpathLeg &lg = legs[p];      // (read where it lies: a copy with its indexed segments would live in scratch)
+        if (fpath_is_conn(lg) && (!status || status[i] == FPATH_OK) && i < F.n) {
+            bool valid;
+            const ClearResult r = solve_clear_test<MODE>(F, i, lg.x0, lg.y0, lg.h0, R, lg.word, lg.seg, valid);
+            int rk = -1, cr = 0;
+            if (valid) {
+                if (r.clear) rk = 0;
+                else { cr = r.crossings; more = r.inside != 0; }
+            }
+            if (rank) rank[p] = rk;
+            if (crossings) crossings[p] = cr;
+        }
+    }
+    solve_clear_append(more, p, list, count);
+}
+
+// k_fpath_clear_words, a group of lanes per listed slot: solve_clear_group on the slot's poses (fpath_conn_poses: the very poses the
+// record was solved from).  The winner's lane overwrites the record's word, seg and total, the slot's count, rank and crossings; the
+// other lanes of the group read the record's field and slot only, which nobody writes.
+template <int MODE>
+__global__ __launch_bounds__(SBLOCK) void k_fpath_clear_words(int64_t count, const int64_t *__restrict__ list, FpathIn in, ClearFields F,
+                                                              FpathLeg *__restrict__ legs, int64_t *__restrict__ cnt, int32_t *__restrict__ rank,
+                                                              int32_t *__restrict__ crossings)
+{
+    constexpr int G = SolveClearGroup<MODE>::G;
+    const int64_t t = (int64_t)blockIdx.x * SBLOCK + threadIdx.x, j = t / G;
+    bool have = j < count;
+    const int64_t p = have ? list[j] : 0;
+    int64_t f = -1;
+    double x0 = 0.0, y0 = 0.0, h0 = 0.0, x1 = 0.0, y1 = 0.0, h1 = 0.0;
+    if (have) {
+        bool invalid = false;
+        f = legs[p].field;
+        have = fpath_conn_poses(in, f, legs[p].slot, x0, y0, h0, x1, y1, h1, invalid);      // (a listed slot has a record: so poses)
+    }
+    solve_clear_group<MODE>(have, f, x0, y0, h0, x1, y1, h1, in.R, F, [&](int word, const double *seg, double total, int rk, int cr) {
+        const int64_t K = fpath_set_word<MODE>(legs[p], word, seg, total, in.spacing);
+        if (cnt) cnt[p] = K;
+        if (rank) rank[p] = rk;
+        if (crossings) crossings[p] = cr;
+    });
+}
+
+// k_fpath_clear_report, a lane per slot: the record's word, seg and total in fcpp_debug_field_paths' layout; then a lane per field: its
+// legs of rank -1 and of rank > 0 (m_i + 1 loads).
+__global__ __launch_bounds__(SBLOCK) void k_fpath_clear_report(int64_t n, int64_t n_slots, const int64_t *__restrict__ soff,
+                                                               const FpathLeg *__restrict__ legs, const int32_t *__restrict__ rank,
+                                                               int32_t *__restrict__ leg_word, double *__restrict__ leg_seg,
+                                                               double *__restrict__ leg_total, int32_t *__restrict__ blocked,
+                                                               int32_t *__restrict__ reshaped)
+{
+    const int64_t g = (int64_t)blockIdx.x * SBLOCK + threadIdx.x;
+    if (g < n_slots) {
+        const FpathLeg &lg = legs[g];
+        if (leg_word) leg_word[g] = lg.kind == FPATH_DUBINS || lg.kind == FPATH_RS ? lg.word : -1;
+        if (leg_seg) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) leg_seg[5 * g + k] = lg.seg[k];
+        }
+        if (leg_total) leg_total[g] = lg.total;
+        return;
+    }
+    const int64_t i = g - n_slots;
+    if (i >= n || !rank) return;
+    int32_t b = 0, r = 0;
+    for (int64_t p = fpath_first_slot(soff, i); p < fpath_first_slot(soff, i + 1); p += 2) {
+        b += rank[p] < 0;
+        r += rank[p] > 0;
+    }
+    if (blocked) blocked[i] = b;
+    if (reshaped) reshaped[i] = r;
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
@@ -126,10 +246,44 @@ int launch_solve_clear_pairs(hipStream_t st, int mode, int64_t n, const SolveCle
 int launch_solve_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const SolveClearIo &io, double R, const ClearFields &F)
 {
     if (count <= 0) return 0;
-    const int64_t per = SBLOCK / (mode == 0 ? 8 : 64);
+    const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
     const dim3 grid((unsigned)((count + per - 1) / per));
     if (mode == 0) hipLaunchKernelGGL(k_solve_clear_words<0>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
     else hipLaunchKernelGGL(k_solve_clear_words<1>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
+    SOLVECLEAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_fpath_clear_slots(hipStream_t st, int mode, int64_t n, int64_t n_conn, const int64_t *soff, double R, const FpathLeg *legs,
+                             const int32_t *status, const ClearFields &F, int32_t *rank, int32_t *crossings, int64_t *list,
+                             unsigned long long *count)
+{
+    if (n <= 0 || n_conn <= 0) return 0;
+    const dim3 grid((unsigned)((n_conn + SBLOCK - 1) / SBLOCK));
+    if (mode == 0) hipLaunchKernelGGL(k_fpath_clear_slots<0>, grid, dim3(SBLOCK), 0, st, n, n_conn, soff, R, legs, status, F, rank, crossings, list, count);
+    else hipLaunchKernelGGL(k_fpath_clear_slots<1>, grid, dim3(SBLOCK), 0, st, n, n_conn, soff, R, legs, status, F, rank, crossings, list, count);
+    SOLVECLEAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_fpath_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const FpathIn &in, const ClearFields &F, FpathLeg *legs,
+                             int64_t *cnt, int32_t *rank, int32_t *crossings)
+{
+    if (count <= 0) return 0;
+    const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
+    const dim3 grid((unsigned)((count + per - 1) / per));
+    if (mode == 0) hipLaunchKernelGGL(k_fpath_clear_words<0>, grid, dim3(SBLOCK), 0, st, count, list, in, F, legs, cnt, rank, crossings);
+    else hipLaunchKernelGGL(k_fpath_clear_words<1>, grid, dim3(SBLOCK), 0, st, count, list, in, F, legs, cnt, rank, crossings);
+    SOLVECLEAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_fpath_clear_report(hipStream_t st, int64_t n, int64_t n_slots, const int64_t *soff, const FpathLeg *legs, const int32_t *rank,
+                              int32_t *leg_word, double *leg_seg, double *leg_total, int32_t *blocked, int32_t *reshaped)
+{
+    if (n <= 0 || !(leg_word || leg_seg || leg_total || blocked || reshaped)) return 0;
+    const dim3 grid((unsigned)((n_slots + n + SBLOCK - 1) / SBLOCK));
+    hipLaunchKernelGGL(k_fpath_clear_report, grid, dim3(SBLOCK), 0, st, n, n_slots, soff, legs, rank, leg_word, leg_seg, leg_total, blocked, reshaped);
     SOLVECLEAR_LAUNCH_CHECK();
     return 0;
 }

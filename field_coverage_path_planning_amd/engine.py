@@ -1840,6 +1840,15 @@ class FieldPaths:
     transit_length: object      # (n) float64: the connector lengths, entry and exit included [m]: the route's cost
     status: object              # (n) int32: 0, or FCPP_EINVAL (an order that is no permutation, a non-finite length or pose): no samples
     leg_offsets: object         # (2 m_total + n + 1) int64: the first sample of every leg slot; field i's first slot is 2 swath_offsets[i] + i
+    # field_paths(clear_of=...) only (None otherwise); per leg slot like leg_offsets, the rule: include/fcpp.h, "clear field paths"
+    leg_rank: object = None     # int32: the driven word's place among the pair's candidates; -1: no candidate is clear, the shortest is driven
+    leg_crossings: object = None    # int32: the driven word's boundary crossings (0 unless rank is -1)
+    leg_word: object = None     # int32: the driven connector's word, -1 on a slot that is no connector
+    leg_seg: object = None      # (slots, 5) float64: its segments (a swath's end point and length in [0 .. 2])
+    leg_total: object = None    # float64: its length
+    blocked: object = None      # (n) int32: the field's connector legs of rank -1
+    reshaped: object = None     # (n) int32: the field's connector legs of rank > 0
+    region_status: object = None    # (n) int32: 0, or FCPP_EINVAL for a region field with no ring, a ring of fewer than 3 vertices, a non-finite vertex
 
     def field(self, i):
         """(x, y, heading, part) of field i: swath_route's tuple"""
@@ -1877,7 +1886,7 @@ def _leg_paths(ctx, counts, fill, args, n_groups, n_slots, n_totals, dev):
     return (off, off_h, x, y, h, kap, part, gear, leg, *totals, status, leg_off)
 
 
-def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None):
+def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None, clear_of=None):
     """The path of EVERY field of a SwathSet in one pass on the device (fcpp_field_path_counts + fcpp_field_path_fill) -> FieldPaths.
     What swath_route gives for one field, for the whole batch and without a host loop: each swath sampled every `spacing` metres (its last
     sample is its end), consecutive swaths joined by the shortest Dubins path -- Reeds-Shepp if `reversing` -- planned at
@@ -1886,7 +1895,12 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     local to it.  entry / exit: one pose (x, y, heading) per field, as route_swaths takes them: the connectors it priced are driven (part 2
     and 3).  A field whose order is no permutation of its swaths, or with a non-finite length or pose, has status FCPP_EINVAL and no samples;
     the others are unaffected.  Connectors know no boundary (validate() flags what leaves the field) unless `clear_of` is given to
-    route_swaths; field_path_clearance tests the connectors driven here."""
+    route_swaths; field_path_clearance tests the connectors driven here.
+    clear_of (a PolygonFields or anything polygon_fields takes, one region per field of the SwathSet): every connector drives the shortest
+    word that stays off its region's rings, as clear_connectors chooses it (fcpp_field_path_counts_clear + fcpp_field_path_fill_clear);
+    where no word is clear the shortest is still driven.  FieldPaths then holds leg_rank, leg_crossings, leg_word, leg_seg, leg_total
+    per leg slot and blocked, reshaped, region_status per field; connector_clearance on the legs' start poses, leg_word and leg_seg
+    agrees with leg_rank.  Without clear_of nothing changes, down to the entries called."""
     ctx = get_context(device)
     torch = _torch()
     ss = swathset
@@ -1902,7 +1916,20 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     ent, ext = _pose_columns(entry, n, dev), _pose_columns(exit, n, dev)
     args = (n, _ptr(ss.offsets), _host_ptr(soff_h), m, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(ss.length), _ptr(ss.angle), _ptr(order),
             _chord_radius(radius, spacing), 1 if reversing else 0, float(spacing), *[_ptr(t) for t in ent], *[_ptr(t) for t in ext])
-    return FieldPaths(*_leg_paths(ctx, ctx.lib.fcpp_field_path_counts, ctx.lib.fcpp_field_path_fill, args, n, 2 * m + n, 2, dev))
+    if clear_of is None:
+        return FieldPaths(*_leg_paths(ctx, ctx.lib.fcpp_field_path_counts, ctx.lib.fcpp_field_path_fill, args, n, 2 * m + n, 2, dev))
+    pf = _clear_fields(clear_of, n, device)          # (holds the region's tensors until the entries have returned)
+    region = pf._head()[1:]
+    n_slots = 2 * m + n
+    slot_i32 = lambda: torch.empty(n_slots, dtype=torch.int32, device=dev)
+    field_i32 = lambda: torch.empty(n, dtype=torch.int32, device=dev)
+    extra = (slot_i32(), slot_i32(), slot_i32(), torch.empty((n_slots, 5), dtype=torch.float64, device=dev),
+             torch.empty(n_slots, dtype=torch.float64, device=dev), field_i32(), field_i32(), field_i32())
+
+    def counts(handle, *a):
+        return ctx.lib.fcpp_field_path_counts_clear(handle, *a, *[_ptr(t) for t in extra])
+
+    return FieldPaths(*_leg_paths(ctx, counts, ctx.lib.fcpp_field_path_fill_clear, args + tuple(region), n, n_slots, 2, dev), *extra)
 
 
 # ---- headland paths (fcpp_headland_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------
@@ -2126,7 +2153,7 @@ class PolygonPlan:
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
-                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None):
+                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2137,7 +2164,12 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     PolygonPlan.coverage); nothing else in the chain changes.  clear_of: None leaves the plan as it is; 'boundary' routes the swaths so
     that the connectors stay clear of the surveyed `fields` (holes are ponds) where an order allows it, and reports what stays blocked
     (route_swaths(clear_of=...): PolygonPlan.clearance is its SwathRoute.clearance, what field_path_clearance gives for the path); a PolygonFields, or anything polygon_fields takes, is used
-    as given.  No connector is re-shaped, and the headland loops' corner connectors are not tested."""
+    as given.  reshape=True (with clear_of; ValueError without): the field paths drive, per connector, the shortest word that stays off the
+    same region the router was given (field_paths(clear_of=...)): PolygonPlan.paths.blocked / .reshaped report the path as driven, while
+    PolygonPlan.clearance stays what it is, the shortest-word legs as routed.  The router's matrix is not priced with the clear word's
+    length, and the headland loops' corner connectors are neither tested nor re-shaped."""
+    if reshape and clear_of is None:
+        raise ValueError('reshape=True needs clear_of: the region the connectors have to stay clear of')
     torch = _torch()
     fields = polygon_fields(fields, device)
     lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
@@ -2148,7 +2180,8 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     ss = polygon_swaths(work, chosen, width, device=device)
     region = None if clear_of is None else (fields if isinstance(clear_of, str) and clear_of == 'boundary' else polygon_fields(clear_of, device))
     route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device, clear_of=region)
-    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device)
+    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device,
+                        clear_of=region if reshape else None)
     clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
     cov = None

@@ -794,6 +794,57 @@ int fcpp_field_path_fill(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_
                          double *x_dev, double *y_dev, double *heading_dev, double *kappa_dev, int8_t *part_dev, int8_t *gear_dev,
                          int32_t *leg_dev);
 
+/* ---- clear field paths: the field paths, every connector driven by the shortest word that stays off a region ---------------------------------
+ * Build-defined.  fcpp_field_path_counts / _fill drive the shortest word of every connector whatever it crosses; these two drive, per
+ * connector, the word fcpp_conn_solve_clear chooses.  One word per connector: no via points, no detours along the headland, no margin (pass
+ * the inset); the router's matrix is not priced with the chosen word's length.  Standalone: nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_fpathfn.h over csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).  The clear
+ * field path of a batch is the field path above with ONE difference: in a field whose path status is FCPP_OK the record of every connector
+ * slot -- word, seg, total -- is what fcpp_conn_solve_clear gives for the slot's from-pose and to-pose (the very poses the connector above is
+ * solved from: the oriented swaths' poses with the router's unwrapped headings, the field's entry / exit pose), `radius`, and field i of the
+ * region CSR (field i of the swaths is field i of the CSR: ring_offsets holds n + 1 values ending at n_rings).
+ *   - rank >= 0: the leg drives that candidate of the pair's (total, word) order; rank 0 keeps the bits of the entries above.
+ *   - rank -1 (no candidate clear, a start outside the region, a region field of status FCPP_EINVAL): the shortest word, as above, with its
+ *     crossings (0 for a region of status FCPP_EINVAL).  The leg is still driven.
+ *   - A pair with no path (word -1) makes the path field FCPP_EINVAL, as above.
+ *   - Sample counts, sampling, doubled junctions, part / gear / leg follow from the record as above; transit_length is the sum of the
+ *     chosen totals in the same order.
+ * Per slot (2 n_total + n each): leg_rank, leg_crossings (int32; 0 on a swath slot, on a slot without a leg and in a path field that is
+ * FCPP_EINVAL), leg_word (int32; -1 unless the slot is a connector), leg_seg (5 float64), leg_total (float64) -- the last three in
+ * fcpp_debug_field_paths' layout (a swath's end point and length in seg[0 .. 2]; a failed field's records as the rule above left them), so
+ * that the driven connectors go to fcpp_conn_clear and fcpp_dubins_sample / fcpp_rs_sample as they are.  Per field (n each, int32):
+ * blocked = its connector legs of rank -1, reshaped = those of rank > 0, region_status = fcpp_conn_clear's field_status of region field i.
+ * Any of the eight may be NULL.
+ * Launches: the rule kernel of the entries above, then a lane per connector slot tests the RECORD's word (no second solve) and lists the
+ * slots whose word starts inside a valid region but crosses; the call reads the list's length back and, unless it is 0, a second kernel
+ * looks at a listed slot's words with a lane per word and overwrites the record; then the scan and the rest as above.
+ * fcpp_field_path_fill_clear recomputes the records the same way; leg_offsets_dev is the counts call's.
+ * Errors of the CALL, found before any kernel runs: those of fcpp_field_path_counts and those fcpp_conn_clear finds in its fields' CSR (a
+ * NULL region array, negative sizes, offsets that do not start at 0, decrease or do not end at their total).  Both entries synchronise. */
+int fcpp_field_path_counts_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                                 const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev,
+                                 const double *length_dev, const double *angle_dev, const int32_t *order_dev, double radius, int mode,
+                                 double spacing, const double *entry_x_dev, const double *entry_y_dev, const double *entry_h_dev,
+                                 const double *exit_x_dev, const double *exit_y_dev, const double *exit_h_dev,
+                                 const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                                 const double *x_dev, const double *y_dev, int64_t *path_offsets_dev, int64_t *path_offsets_host,
+                                 int64_t *leg_offsets_dev, double *work_length_dev, double *transit_length_dev, int32_t *status_dev,
+                                 int32_t *leg_rank_dev, int32_t *leg_crossings_dev, int32_t *leg_word_dev, double *leg_seg_dev,
+                                 double *leg_total_dev, int32_t *blocked_dev, int32_t *reshaped_dev, int32_t *region_status_dev);
+int fcpp_field_path_fill_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                               const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *length_dev,
+                               const double *angle_dev, const int32_t *order_dev, double radius, int mode, double spacing,
+                               const double *entry_x_dev, const double *entry_y_dev, const double *entry_h_dev, const double *exit_x_dev,
+                               const double *exit_y_dev, const double *exit_h_dev, const int64_t *ring_offsets_dev, int64_t n_rings,
+                               const int64_t *vert_offsets_dev, int64_t n_verts, const double *region_x_dev, const double *region_y_dev,
+                               const int64_t *leg_offsets_dev, int64_t total_samples, double *x_dev, double *y_dev, double *heading_dev,
+                               double *kappa_dev, int8_t *part_dev, int8_t *gear_dev, int32_t *leg_dev);
+/* listed: the connector slots the first pass of this context's LAST clear field-path call (counts or fill) handed to the second;
+ * word_launches: the second-pass launches of all such calls so far (a call that lists nothing launches none).  Either may be NULL.  The
+ * counts call skips the fields whose path status is FCPP_EINVAL; the fill keeps no status and also looks at their legs, which have no
+ * samples, so its `listed` may be larger.  For tests; fcpp_ctx_solve_clear_passes keeps its meaning. */
+int fcpp_ctx_field_path_clear_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *word_launches);
+
 /* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
  * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it
  * shares and whose input it makes: boundary -> headland pass centre lines -> work area -> swaths -> route.  Nothing here feeds fcpp_batch_plan.
@@ -1079,6 +1130,19 @@ int fcpp_debug_field_paths(int64_t n, const int64_t *swath_offsets, int64_t n_to
                            const double *exit_y, const double *exit_h, int64_t *path_offsets, int64_t *leg_offsets, double *work_length,
                            double *transit_length, int32_t *status, int32_t *leg_word, double *leg_seg, double *leg_total, int64_t cap,
                            double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
+/* The clear field-path rule evaluated on the HOST, counts and fill in one call like fcpp_debug_field_paths: what
+ * fcpp_field_path_counts_clear / _fill_clear are compared with bit for bit.  Arguments, outputs and the call's errors as for them (the
+ * offsets are the host's); it applies the sequential form of the clear-connector rule to every connector slot.  A diagnostic, not a
+ * fallback. */
+int fcpp_debug_field_paths_clear(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                 const double *by, const double *length, const double *angle, const int32_t *order, double radius, int mode,
+                                 double spacing, const double *entry_x, const double *entry_y, const double *entry_h, const double *exit_x,
+                                 const double *exit_y, const double *exit_h, const int64_t *ring_offsets, int64_t n_rings,
+                                 const int64_t *vert_offsets, int64_t n_verts, const double *region_x, const double *region_y,
+                                 int64_t *path_offsets, int64_t *leg_offsets, double *work_length, double *transit_length, int32_t *status,
+                                 int32_t *leg_rank, int32_t *leg_crossings, int32_t *leg_word, double *leg_seg, double *leg_total,
+                                 int32_t *blocked, int32_t *reshaped, int32_t *region_status, int64_t cap, double *x, double *y,
+                                 double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg);
 /* The headland-path rule (csrc/fcpp_hpathfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device
  * results are compared with bit for bit.  Arguments and the call's errors as for fcpp_headland_path_counts / _fill.  path_offsets
  * (n_rings + 1), leg_offsets (2 n_verts + 1), work_length, transit_length, skipped_length, status (n_rings): any may be NULL.  leg_kind,

@@ -9,6 +9,9 @@
       same batch, once, with the device results compared bit for bit;
   (d) the parent's way: swath_route(order=route) in a Python loop over the FIRST --loop-fields fields, host clock around the loop with a
       synchronise at its end, reported per field; the ratio to (b) is per field against per field and covers those fields only.
+--clear-of: instead of (b) - (d), the counts and fill CALLS of the plain entries and of the clear entries (fcpp_field_path_counts_clear /
+_fill_clear; regions: the star fields' own boundaries) on the same batch and order, ALTERNATING plain and clear within every repetition;
+with the slots the first pass listed and the blocked / reshaped sums.  No ratio is fixed in advance: the plain entries are the comparator.
 Prints ONE JSON line (and writes it to --out).  Needs a GPU; bench.py's metric is not touched by this."""
 import argparse
 import json
@@ -43,6 +46,7 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--no-host', action='store_true')
+    ap.add_argument('--clear-of', action='store_true', help='time the clear entries beside the plain ones (regions: the fields themselves)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -64,6 +68,11 @@ def main():
     m = np.diff(soff_h)
     nt = int(soff_h[-1])
     rec['swaths'] = {'total': nt, 'mean': float(m.mean()), 'max': int(m.max()), 'leg_slots': 2 * nt + n}
+
+    if args.clear_of:
+        rec['tool'] = 'bench_field_paths --clear-of'
+        rec.update(clear_bench(torch, ctx, ss, route, pf, n, nt, soff_h, R, sp, rev, args.reps, args.warmup))
+        return emit(rec, args.out)
 
     box = {}
 
@@ -141,12 +150,80 @@ def main():
                                    'ratio_per_field': per_field / (rec['field_paths_ms'] / n),
                                    'note': 'the loop ran on the first %d fields only; the ratio compares time per field, nothing is extrapolated' % k}
 
+    emit(rec, args.out)
+
+
+def emit(rec, path):
     out = json.dumps(rec)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as fh:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as fh:
             fh.write(out + '\n')
     print(out)
+
+
+def clear_bench(torch, ctx, ss, route, pf, n, nt, soff_h, R, sp, rev, reps, warmup):
+    """the four calls, plain and clear alternating within every repetition, each between two HIP events -> the record's entries"""
+    import ctypes as C
+    lib, P, HP = ctx.lib, E._ptr, E._host_ptr
+    dev = ss.a.device
+    n_slots = 2 * nt + n
+    ax, ay, bx, by = (t[:, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+    order = route.order.to(torch.int32).contiguous()
+    head = (ctx.handle, n, P(ss.offsets), HP(soff_h), nt, P(ax), P(ay), P(bx), P(by), P(ss.length), P(ss.angle), P(order), E._chord_radius(R, sp),
+            1 if rev else 0, sp, *([None] * 6))
+    region = pf._head()[1:]
+    i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)
+    bufs = {}
+    for kind in ('plain', 'clear'):
+        bufs[kind] = dict(off=torch.empty(n + 1, dtype=torch.int64, device=dev), leg_off=torch.empty(n_slots + 1, dtype=torch.int64, device=dev),
+                          off_h=np.zeros(n + 1, dtype=np.int64), work=torch.empty(n, dtype=torch.float64, device=dev),
+                          transit=torch.empty(n, dtype=torch.float64, device=dev), status=i32(n))
+    extra = [i32(n_slots), i32(n_slots), i32(n_slots), torch.empty((n_slots, 5), dtype=torch.float64, device=dev),
+             torch.empty(n_slots, dtype=torch.float64, device=dev), i32(n), i32(n), i32(n)]
+    ctx.bind_stream()
+
+    def counts(kind):
+        b = bufs[kind]
+        tail = (P(b['off']), HP(b['off_h']), P(b['leg_off']), P(b['work']), P(b['transit']), P(b['status']))
+        if kind == 'plain':
+            L.check(lib.fcpp_field_path_counts(*head, *tail))
+        else:
+            L.check(lib.fcpp_field_path_counts_clear(*head, *region, *tail, *[P(t) for t in extra]))
+
+    def fill(kind):
+        b = bufs[kind]
+        tail = (P(b['leg_off']), b['total'], *[P(t) for t in b['samples']])
+        if kind == 'plain':
+            L.check(lib.fcpp_field_path_fill(*head, *tail))
+        else:
+            L.check(lib.fcpp_field_path_fill_clear(*head, *region, *tail))
+
+    for kind in ('plain', 'clear'):
+        counts(kind)
+        b = bufs[kind]
+        b['total'] = int(b['off_h'][-1])
+        b['samples'] = [torch.empty(b['total'], dtype=dt, device=dev)
+                        for dt in (torch.float64, torch.float64, torch.float64, torch.float64, torch.int8, torch.int8, torch.int32)]
+    listed, launches = C.c_int64(0), C.c_int64(0)
+    L.check(lib.fcpp_ctx_field_path_clear_passes(ctx.handle, C.byref(listed), C.byref(launches)))
+    times = {(call, kind): [] for call in ('counts', 'fill') for kind in ('plain', 'clear')}
+    for rep in range(warmup + reps):
+        for call, fn in (('counts', counts), ('fill', fill)):
+            for kind in ('plain', 'clear'):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn(kind)
+                e1.record()
+                e1.synchronize()
+                if rep >= warmup:
+                    times[call, kind].append(e0.elapsed_time(e1))
+    stat = lambda v: {'median_ms': float(np.median(v)), 'min_ms': float(np.min(v)), 'max_ms': float(np.max(v))}
+    out = {'%s_call_%s' % (call, kind): stat(v) for (call, kind), v in times.items()}
+    out['samples'] = {kind: bufs[kind]['total'] for kind in bufs}
+    out['clear'] = {'connector_slots': nt + n, 'listed': int(listed.value), 'blocked': int(extra[5].sum().item()), 'reshaped': int(extra[6].sum().item()),
+                    'region_status_nonzero': int((extra[7] != 0).sum().item()), 'status_nonzero': int((bufs['clear']['status'] != 0).sum().item())}
+    return out
 
 
 if __name__ == '__main__':
