@@ -1606,7 +1606,7 @@ int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const doub
             if ((spin & 4095) == 4095 && ms_since(t_wait) > 2000.0) return -1;
         }
     };
-    if (ga_generation_fits(n, pop)) {
+    if (ga_launch_plan(n, pop).one_launch) {
         // One launch per generation (k_ga_generation): the population in buffer a -> its statistics and elites (the bookkeeping of
         // generation g - 1) and its children (generation g) at once; the launch after the last generation only evaluates the final
         // population.  cfg4: 77 -> 55 us per generation (45 us with the DPP arg-max of the elite selection).
@@ -1829,6 +1829,15 @@ int fcpp_debug_offsets(int64_t n, int n_cols, const int64_t *counts, int64_t *pr
         for (int64_t i = 0; i < n; ++i) prefix[(int64_t)col * n + i] = offset_prefix(agg.data(), counts, n, col, i);
         totals[col] = offset_total(agg.data(), n, col);
     }
+    return FCPP_OK;
+}
+
+int fcpp_debug_ga_launch_plan(fcpp_ctx *c, int32_t n, int32_t pop, int32_t *out)
+{
+    if (!c || !out || n < 2 || n > GA_MAX_NODES || pop < 2 || (pop & 1)) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    const GaLaunchPlan p = ga_launch_plan(n, pop);
+    out[0] = p.one_launch ? 1 : 0; out[1] = (int32_t)p.groups; out[2] = p.base; out[3] = p.extra; out[4] = p.per_wg; out[5] = (int32_t)p.lds;
     return FCPP_OK;
 }
 

@@ -700,10 +700,13 @@ int launch_ga_check_perm(hipStream_t st, int n, int pop, const int32_t *routes, 
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// lds ints of one pair: 4 n genes + n presence bytes, rounded to 16 bytes, + the 2 x 64 tournament candidates
+static inline size_t ga_pair_lds_ints(int n) { return GA_PAIR_LDS_HEAD(n) + 128; }
+
 int launch_ga_pairs(hipStream_t st, int n, int pop, const double *D, const int32_t *cur, const double *cur_fit, int32_t *nxt,
                     double *nxt_fit, double *nxt_dist, const fcpp_ga_config &cfg, int gen, const GaState *state)
 {
-    const size_t lds = (GA_PAIR_LDS_HEAD(n) + 128) * sizeof(int32_t);
+    const size_t lds = ga_pair_lds_ints(n) * sizeof(int32_t);
     hipLaunchKernelGGL(k_ga_pairs, dim3((unsigned)(pop / 2)), dim3(64), lds, st, n, pop, D, cur, cur_fit, nxt, nxt_fit, nxt_dist, cfg, gen,
                        state);
     hipError_t e = hipGetLastError();
@@ -720,9 +723,6 @@ int launch_ga_stats_elite(hipStream_t st, int n, int pop, const int32_t *cur, co
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
-
-// lds ints of one pair: 4 n genes + n presence bytes, rounded to 16 bytes
-static inline size_t ga_pair_lds_ints(int n) { return GA_PAIR_LDS_HEAD(n) + 128; }
 
 // how a launch spreads pop / 2 pairs over its workgroups: -> pair workgroups; base / extra as k_ga_generation reads them; per_wg = the most pairs of one
 static unsigned ga_pair_groups(int n, int pop, int &base, int &extra, int &per_wg)
@@ -752,16 +752,28 @@ bool ga_generation_fits(int n, int pop)
     return pop <= GA_LDS_POP && ga_pair_lds_ints(n) * sizeof(int32_t) * GA_PAIRS_PER_WG <= 60 * 1024;
 }
 
+GaLaunchPlan ga_launch_plan(int n, int pop)
+{
+    GaLaunchPlan p = {};
+    const size_t pl = ga_pair_lds_ints(n) * sizeof(int32_t);
+    p.one_launch = ga_generation_fits(n, pop);
+    if (p.one_launch) {
+        p.groups = ga_pair_groups(n, pop, p.base, p.extra, p.per_wg);
+        p.lds = std::max(pl * (size_t)p.per_wg, (size_t)pop * sizeof(double));
+    } else {      // k_ga_pairs: a workgroup of one wavefront per pair
+        p.groups = (unsigned)(pop / 2); p.base = 1; p.extra = 0; p.per_wg = 1;
+        p.lds = pl;
+    }
+    return p;
+}
+
 int launch_ga_generation(hipStream_t st, int n, int pop, const double *D, const int32_t *cur, const double *cur_fit, const double *cur_dist,
                          int32_t *nxt, double *nxt_fit, double *nxt_dist, const fcpp_ga_config &cfg, int gen, GaState *state,
                          int32_t *best_route, double *hist)
 {
-    const size_t pl = ga_pair_lds_ints(n);
-    int base = 0, extra = 0, per_wg = 0;
-    const unsigned blocks = ga_pair_groups(n, pop, base, extra, per_wg) + 2u;
-    const size_t lds = std::max(pl * sizeof(int32_t) * (size_t)per_wg, (size_t)pop * sizeof(double));
-    hipLaunchKernelGGL(k_ga_generation, dim3(blocks), dim3(SB), lds, st, n, pop, D, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen,
-                       (int)pl, base, extra, state, best_route, hist);
+    const GaLaunchPlan p = ga_launch_plan(n, pop);
+    hipLaunchKernelGGL(k_ga_generation, dim3(p.groups + 2u), dim3(SB), p.lds, st, n, pop, D, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen,
+                       (int)ga_pair_lds_ints(n), p.base, p.extra, state, best_route, hist);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -1061,6 +1061,11 @@ int fcpp_debug_math_dev(fcpp_ctx *ctx, int fn, int64_t n, const double *a_dev, c
  * per-block aggregates and the counts of the field's own block), its HOST version on host pointers: counts[col * n + i], n_cols columns of
  * n <= 8192 fields -> prefix[col * n + i] and totals[col].  What the kernels' offsets are checked against; a diagnostic, not a fallback. */
 int fcpp_debug_offsets(int64_t n, int n_cols, const int64_t *counts, int64_t *prefix, int64_t *totals);
+/* What fcpp_ga_evolve will launch per generation for n_nodes and population_size on the context's device -- host code, the function its
+ * launchers read; out (a HOST pointer) = { 1: one launch per generation (k_ga_generation), 0: two launches on two streams; pair workgroups;
+ * base; extra (workgroup b takes base + (b < extra) pairs); the most pairs of one workgroup; dynamic LDS bytes of the pair launch }.  So
+ * that a test which names a path proves it took that path.  n_nodes and population_size as for fcpp_ga_evolve. */
+int fcpp_debug_ga_launch_plan(fcpp_ctx *ctx, int32_t n_nodes, int32_t population_size, int32_t *out);
 /* fcpp_dubins_solve's function (csrc/fcpp_dubinsfn.h) evaluated on the HOST, on host pointers: what the device results are compared with
  * bit for bit, and what tests the mathematics on a machine without a GPU.  A diagnostic, not a fallback. */
 int fcpp_debug_dubins(int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x, const double *to_y,

@@ -14,6 +14,8 @@ tensor for the device entries -- so that all three show:
   check      after the call (and a synchronise): every guard byte is still 0xA5; every input slot has the bits that were put in; every
              output slot has the bits of expected[name]; a slot declared written=False is still all 0x5A; and no ELEMENT of expected[name]
              is the all-0x5A pattern, so "still pre-filled" and "correct" exclude each other (a condition on the inputs the caller chose).
+  in-out     a slot the call reads and writes (inout): pre-filled with the input and checked against expected[name] like an output; an
+             expected element may be the all-0x5A pattern only where the input element is that very value.
 An output passed as NULL has no slot.  Failures raise GuardError (an AssertionError) whose message names the slot.
 """
 import ctypes as C
@@ -30,8 +32,9 @@ class GuardError(AssertionError):
 
 
 class _Slot:
-    def __init__(self, name, dtype, count, data, written):
+    def __init__(self, name, dtype, count, data, written, inout=False):
         self.name, self.dtype, self.count, self.data, self.written = name, np.dtype(dtype), int(count), data, written
+        self.inout = inout          # data = the input the slot is pre-filled with; checked like an output
         self.start = self.end = -1
 
     @property
@@ -66,6 +69,11 @@ class Arena:
     def input(self, name, array, dtype=None):
         a = np.ascontiguousarray(array, dtype=dtype)
         return self._add(_Slot(name, a.dtype, a.size, _as_bytes(a, a.dtype).copy(), False))
+
+    def inout(self, name, array, dtype=None):
+        """a slot the call reads AND writes: pre-filled with the input, checked against expected[name]"""
+        a = np.ascontiguousarray(array, dtype=dtype)
+        return self._add(_Slot(name, a.dtype, a.size, _as_bytes(a, a.dtype).copy(), True, inout=True))
 
     def output(self, name, dtype, count, written=True):
         """written=False: a slot the call is handed (or not) and must leave alone"""
@@ -138,10 +146,10 @@ class Arena:
 
     # ---- the check ------------------------------------------------------------------------------------------------------------------
     def check(self, expected):
-        """expected: {name: array} for exactly the written output slots.  -> {name: array} of what the slots hold"""
+        """expected: {name: array} for exactly the written output slots and the in-out slots.  -> {name: array} of what the slots hold"""
         img = self.snapshot()
         slots = list(self._slots.values())
-        outputs = {s.name for s in slots if s.data is None and s.written}
+        outputs = {s.name for s in slots if s.inout or (s.data is None and s.written)}
         if set(expected) != outputs:
             raise GuardError('expected values for %s, written output slots %s' % (sorted(expected), sorted(outputs)))
         # 1: the guards
@@ -164,7 +172,7 @@ class Arena:
         got = {}
         for s in slots:
             have = img[s.start:s.end]
-            if s.data is not None:
+            if s.data is not None and not s.inout:
                 # 2: the inputs
                 bad = np.flatnonzero(have != s.data)
                 if bad.size:
@@ -182,10 +190,18 @@ class Arena:
                 raise GuardError('expected[%r]: %s x %d, the slot holds %s x %d' % (s.name, e.dtype, e.size, s.dtype, s.count))
             want = _as_bytes(e, s.dtype)
             size = s.dtype.itemsize
-            prefilled = np.flatnonzero((want.reshape(-1, size) == FILL_BYTE).all(axis=1))
+            is_fill = (want.reshape(-1, size) == FILL_BYTE).all(axis=1)
+            if s.inout:          # (an element the call may leave as it was put in)
+                is_fill &= (want.reshape(-1, size) != s.data.reshape(-1, size)).any(axis=1)
+            prefilled = np.flatnonzero(is_fill)
             if prefilled.size:
                 raise GuardError('expected[%r][%d] is the pre-fill pattern itself: choose other inputs' % (s.name, prefilled[0]))
             bad = np.flatnonzero((have.reshape(-1, size) != want.reshape(-1, size)).any(axis=1))
+            if bad.size and s.inout:
+                k = int(bad[0])
+                untouched = int((have.reshape(-1, size)[bad] == s.data.reshape(-1, size)[bad]).all(axis=1).sum())
+                raise GuardError('in-out slot %r: %d of %d elements differ (%d of them still the input), the first element %d: %r, expected %r'
+                                 % (s.name, bad.size, s.count, untouched, k, have.view(s.dtype)[k:k + 1].tolist(), want.view(s.dtype)[k:k + 1].tolist()))
             if bad.size:
                 k = int(bad[0])
                 untouched = int((have.reshape(-1, size)[bad] == FILL_BYTE).all(axis=1).sum())

@@ -2,7 +2,8 @@
 
 First the harness proves itself: deliberately wrong writers written in numpy -- one element past the end, one in front of the start, the
 last element left out, a bit of an input flipped -- must each fail the check with a message that names the slot, for every element size the
-device tests use.  That is what shows tests/test_gpu_guarded.py would fail on such a kernel.
+device tests use.  That is what shows tests/test_gpu_guarded.py would fail on such a kernel.  In-out slots (a buffer the call reads and
+rewrites, as fcpp_ga_evolve's population) are proved the same way: left untouched where a change was expected, or written beside.
 
 Then fcpp_debug_dubins, fcpp_debug_rs, fcpp_debug_swaths, fcpp_debug_route_transit and fcpp_debug_route run through a numpy arena on the
 batches the device tests use (defined here, imported there): the twins stay inside their buffers, leave their inputs alone and give the
@@ -227,6 +228,59 @@ def test_wrong_values_prefill_values_and_forbidden_slots_are_caught():
     for bad in ({}, dict(RIGHT, quiet=np.zeros(1)), dict(RIGHT, y=RIGHT['y'][:6]), dict(RIGHT, idx=RIGHT['idx'].astype(np.int64))):
         with pytest.raises(GuardError):
             _toy().check(bad)
+
+
+def _toy_inout():
+    """x is read, `state` is read and rewritten (every element but the third changes), y is written"""
+    state = 10 + np.arange(5, dtype=np.int32)
+    want = {'state': np.array([20, 21, 12, 23, 24], dtype=np.int32), 'y': np.ones(5)}
+    A = Arena().input('x', X_IN).inout('state', state).output('y', np.float64, 5).build()
+    assert A.address('state') % 8 == 4 and np.array_equal(A.view('state'), state)          # pre-filled with the input
+    return A, state, want
+
+
+def test_inout_slots_are_checked_like_outputs():
+    A, state, want = _toy_inout()
+    A.view('y')[:] = 1.0
+    # left untouched when a change was expected
+    with pytest.raises(GuardError, match=r"in-out slot 'state': 4 of 5 elements differ \(4 of them still the input\), the first element 0"):
+        A.check(want)
+    # the expected values must name it
+    with pytest.raises(GuardError, match='expected values for'):
+        A.check({'y': want['y']})
+    A.view('state')[:] = want['state']
+    got = A.check(want)
+    assert np.array_equal(got['state'], want['state']) and np.array_equal(got['y'], want['y'])
+    # one wrong element
+    A.view('state')[1] = 7
+    with pytest.raises(GuardError, match=r"in-out slot 'state': 1 of 5 elements differ \(0 of them still the input\), the first element 1"):
+        A.check(want)
+
+
+@pytest.mark.parametrize('side', ['behind', 'in front'])
+def test_a_write_beside_an_inout_slot_is_caught(side):
+    A, state, want = _toy_inout()
+    A.view('y')[:] = 1.0
+    A.view('state')[:] = want['state']
+    s, e = A.span('state')
+    if side == 'behind':
+        A.raw[e:e + 4] = A.raw[e - 4:e]
+    else:
+        A.raw[s - 4:s] = A.raw[s:s + 4]
+    with pytest.raises(GuardError, match=r"guard bytes were written.*%s" % ("behind the end of slot 'state'" if side == 'behind' else "in front of slot 'state'")):
+        A.check(want)
+
+
+def test_inout_prefill_pattern_rule():
+    """an expected element that IS the 0x5A pattern is refused -- unless the input element already was that value (the call may leave it)"""
+    fill = np.frombuffer(bytes([FILL_BYTE] * 4), dtype=np.int32)[0]
+    A = Arena().inout('state', np.array([1, fill, 3], dtype=np.int32)).build()
+    A.view('state')[:] = [5, fill, 6]
+    A.check({'state': np.array([5, fill, 6], dtype=np.int32)})
+    A = Arena().inout('state', np.array([1, 2, 3], dtype=np.int32)).build()
+    A.view('state')[:] = [5, fill, 6]
+    with pytest.raises(GuardError, match=r"expected\['state'\]\[1\] is the pre-fill pattern"):
+        A.check({'state': np.array([5, fill, 6], dtype=np.int32)})
 
 
 # ---- 2: the host twins through a numpy arena ------------------------------------------------------------------------------------------

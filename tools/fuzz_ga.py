@@ -22,13 +22,15 @@ a = ap.parse_args()
 rng = np.random.default_rng(a.seed)
 t0, runs, fails = time.time(), 0, 0
 while time.time() - t0 < a.seconds:
-    n = int(rng.choice([2, 3, 7, 33, 64, 65, 128, 129, 200, 400, 520, 700]))
-    pop = 2 * int(rng.integers(2, 40)) if rng.random() < 0.7 else 2 * int(rng.integers(40, 3300))
-    if n > 300:
+    n = int(rng.choice([2, 3, 7, 33, 64, 65, 128, 129, 200, 256, 257, 320, 398, 400, 520, 700]))
+    u = rng.random()
+    # (one in ten: the populations whose pairs the one-launch kernel spreads over all compute units, 9 to 13 a workgroup on 256 of them)
+    pop = 2 * int(rng.integers(2, 40)) if u < 0.7 else 2 * int(rng.integers(40, 3300)) if u < 0.9 else 2 * int(rng.integers(1779, 3073))
+    if n > 398:
         pop = min(pop, 128)
     elite = int(rng.integers(0, min(pop - 1, 80)))
     tour = int(rng.integers(1, min(pop, 64) + 1))
-    cfg = dict(max_generations=int(rng.integers(1, 40 if pop * n < 200000 else 6)), elite_size=elite, tournament_size=tour,
+    cfg = dict(max_generations=int(rng.integers(1, 40 if pop * n < 200000 else 6 if pop * n < 1000000 else 3)), elite_size=elite, tournament_size=tour,
                convergence_threshold=int(rng.choice([3, 8, 1000])), crossover_rate=float(rng.choice([0.0, 0.5, 0.85, 1.0])),
                mutation_rate=float(rng.choice([0.0, 0.02, 0.5, 1.0])))
     seed = int(rng.integers(0, 2 ** 62))
