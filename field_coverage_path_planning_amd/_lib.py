@@ -203,6 +203,7 @@ PROTOTYPES = [
     ('fcpp_debug_math', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_debug_math_dev', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_debug_offsets', C.c_int, [C.c_int64, C.c_int, _VP, _VP, _VP]),
+    ('fcpp_debug_setup_rule', C.c_int, [C.c_int, _VP, _VP]),
     ('fcpp_debug_ga_launch_plan', C.c_int, [_VP, C.c_int32, C.c_int32, _VP]),
     ('fcpp_debug_dubins', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_rs', C.c_int, [C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),

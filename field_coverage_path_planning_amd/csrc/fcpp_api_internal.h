@@ -1,5 +1,5 @@
-// fcpp_api_internal.h -- what the host translation units behind include/fcpp.h share: fcpp_api.cpp (context, output arena, batch setup and
-// step) and fcpp_paths.cpp (the standalone path operators).  Private to csrc/.
+// fcpp_api_internal.h -- what the host translation units behind include/fcpp.h share: fcpp_api.cpp (context, output arena, a batch's step), fcpp_setup.cpp
+// (batch setup) and fcpp_paths.cpp (the standalone path operators).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -10,6 +10,7 @@
 
 #include "fcpp_device.h"
 #include "fcpp_internal.h"
+#include "fcpp_setuprule.h"
 #include "fcpp_tiler.h"
 
 namespace fcpp {
@@ -104,7 +105,7 @@ struct DevTiling {
     }
 };
 
-struct TemplateSet;     // a batch's turn templates (fcpp_api.cpp)
+struct TemplateSet;     // a batch's turn templates (fcpp_batch.h)
 struct PathTiling;      // the standalone operators' last path set (fcpp_paths.cpp)
 void free_paths_cache(fcpp_ctx *c);
 
@@ -145,12 +146,12 @@ struct fcpp_ctx {
     int setup_mode = FCPP_SETUP_AUTO;
     // (up to FOUR scratch allocations, one per stream that sets batches up: a caller that plans batch k + 1 on a second stream while batch k's step
     // still runs on the first -- the sustained rate of bench.py -- must not wait for that step because its fill pass shared the scratch)
-    // (agg_flip: which of the slot's two buffers of aggregates the next speculative setup accumulates into -- DevPlanScratch.agg; agg_dirty: a
-    // speculative setup ended between its planner and its fill pass, which would have zeroed the other buffer: both are cleared before the next)
+    // (SlotAggregates, fcpp_setuprule.h: which of the slot's two buffers of aggregates the next speculative setup accumulates into --
+    // DevPlanScratch.agg -- and whether both are to be cleared first: begin_aggregates() / aggregates_settled())
     // (tables_batch: the batch whose step ran directly off the slot's counting pass and whose tables are still to be filled from the slot's scratch
     // -- fcpp_batch::tables_pending; whoever takes the slot next enqueues that fill pass first: plan_scratch)
-    struct PlanSlot { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0; int agg_flip = 0; bool agg_dirty = false;
-                      fcpp_batch *tables_batch = nullptr; };
+    struct PlanSlot : fcpp::SlotAggregates { void *p = nullptr; size_t cap = 0; hipStream_t stream = nullptr; bool pending = false; uint64_t tick = 0;
+                                             fcpp_batch *tables_batch = nullptr; };
     static constexpr int kPlanSlots = 4;
     PlanSlot plan_slots[kPlanSlots];
     uint64_t plan_tick = 0;

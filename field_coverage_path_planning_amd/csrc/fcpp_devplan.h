@@ -90,7 +90,7 @@ struct DevPlanScratch {
     // two levels (fcpp_offsetfn.h), speculative setups: agg[col][block of OFF_B fields] = the block's sum of the column, added up with atomics by
     // the planner (PC_POINTS) and the counting pass (every other column), read by the NEXT kernel only.  Two buffers per plan slot, zero when
     // the slot is allocated: a setup accumulates into `agg`, its fill pass zeroes `agg_next`, the next setup of the slot swaps them -- no
-    // clearing command in the stream (fcpp_api.cpp: try_device_setup, which also says what happens after a setup that ended in between)
+    // clearing command in the stream (fcpp_setuprule.h: SlotAggregates, which also says what happens after a setup that ended in between)
     int64_t *agg, *agg_next;      // OFF_WORDS each: OFF_NB rows of OFF_ROW words, PC_COLS of them used
     // the counting pass keeps the first DEVPLAN_KEEP_TILES wave tiles of every field (records with field-relative indices): the fill pass
     // copies and rebases them instead of cutting the field again (fields with more are cut again)
@@ -135,7 +135,7 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
 int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const DevPlanScratch &s, const fcpp_field *fields);
 // phase 2: the tables (pointers into the batch's slab, laid out by the host).  `bases` / `totals` as phase 1 left them.
 // tc.speculative: positions from the two levels; one more workgroup publishes the totals, the flags and tc.gen to totals_host (the host
-// polls it: await_totals) and zeroes s.agg_next -- also when the flags make the pass a no-op.
+// polls it: DeviceSetup::await, fcpp_setup.cpp) and zeroes s.agg_next -- also when the flags make the pass a no-op.
 int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, const DevConst &cst, const DevPlanScratch &s, const SlabTables &t, int64_t *totals_host);
 // the exact layout after a speculative counting phase (over capacity): the scan of all columns as the pass wrote them -> bases, totals
 int launch_devplan_rescan(hipStream_t st, int64_t n, const DevPlanScratch &s);
@@ -159,7 +159,7 @@ __device__ __forceinline__ void publish_total(const int64_t *totals, int64_t *mi
 // The publisher of a speculative setup -- the first workgroup of its fill pass, or of its direct step: what the last scan of a counting phase
 // does for the host, without a scan.
 // Wavefront 0 sums every column's aggregates (total(col), fcpp_offsetfn.h) and writes the totals, the flags and then the phase's generation
-// number to the host's copy (await_totals polls that word) -- whatever the flags say: a pass they make a no-op is waited for as well.
+// number to the host's copy (DeviceSetup::await polls that word) -- whatever the flags say: a pass they make a no-op is waited for as well.
 // Wavefront 1 zeroes the OTHER buffer of aggregates, the one the slot's next setup accumulates into (nothing of this setup reads or writes it).
 __device__ __forceinline__ void publish_two_level(int64_t n, int64_t gen, int64_t *__restrict__ totals, const int64_t *__restrict__ agg, int64_t *__restrict__ agg_next,
                                                   int64_t *__restrict__ mirror, int wave, int lane)

@@ -19,10 +19,10 @@
 
 namespace fcpp {
 
-// what this tiler and the device's (fcpp_devplan.h: DevTileConsts) both derive from the batch: computed once per batch (fcpp_api.cpp: batch_tile_consts)
+// what this tiler and the device's (fcpp_devplan.h: DevTileConsts) both derive from the batch: computed once per batch (fcpp_setup.cpp: batch_tile_consts)
 struct BatchTileConsts {
     int nu = 0, nc = 0;                       // samples of the U-turn / corner templates
-    bool turn_quiet = false;                  // U-turns of this batch are closed form (closed_form_turns, fcpp_api.cpp)
+    bool turn_quiet = false;                  // U-turns of this batch are closed form (closed_form_turns, fcpp_setup.cpp)
     double two_a = 0.0, u_cap = 0.0, c_line = 0.0;     // 2 a_lon, (v_max / 3.6)^2, (v_work / 3.6)^2
     double fence_margin = 1e-7;               // a point whose edge functions are all at least this cannot be flagged by the device's geofence test (1e-7 - geofence_tol)
     static constexpr int wave_factor = 24;    // wave tiles where wave_factor * 2a * line step >= u_cap
@@ -46,7 +46,7 @@ struct TileConsts : BatchTileConsts {
     bool device_chunks = false;               // the chunk lists of k_plan_quiet are expanded on the device from chunk groups (fcpp_batch_create; false: written by the host, the checker)
 };
 
-// the obstacle part of the image (also used by the device-side setup, fcpp_api.cpp)
+// the obstacle part of the image (also used by the device-side setup, fcpp_setup.cpp)
 // (rebase: dst holds the image from byte `rebase` on -- the obstacle region alone when rebase = lay.obs_off)
 void fill_obstacles(const fcpp_polys *polys, const ImageLayout &lay, unsigned char *dst, size_t rebase = 0);
 

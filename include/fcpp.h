@@ -1061,6 +1061,18 @@ int fcpp_debug_math_dev(fcpp_ctx *ctx, int fn, int64_t n, const double *a_dev, c
  * per-block aggregates and the counts of the field's own block), its HOST version on host pointers: counts[col * n + i], n_cols columns of
  * n <= 8192 fields -> prefix[col * n + i] and totals[col].  What the kernels' offsets are checked against; a diagnostic, not a fallback. */
 int fcpp_debug_offsets(int64_t n, int n_cols, const int64_t *counts, int64_t *prefix, int64_t *totals);
+/* The decisions of a batch's device setup (csrc/fcpp_setuprule.h: the functions the setup itself reads), evaluated on the host, on host
+ * pointers; booleans as 0 / 1.
+ *   what 0, setup_accept: in = { setup mode, fields, small-batch threshold, obstacle mode, field_work, max_prims } -> out[0] = 0: accepted, or
+ *           the decline: 1 host setup requested, 2 empty batch, 3 a handful of fields, 4 obstacle mode, 5 FCPP_FIELD_WORK=0, 6 too many primitives
+ *   what 1, setup_begin: in = { fields, exact_only, dense, bytes of the capacity layout, outputs wanted, no polygons, fuse_spans, direct_ok,
+ *           FCPP_DIRECT } -> out = { spec, direct, the capacity layout is looked at }
+ *   what 2, setup_end: in = { spec, direct_step, early point total, PC_UNFUSABLE, PC_WORK_SPAN_PTS, PC_WORK, PC_POINTS, the flag PF_OVER_CAPACITY,
+ *           generation, fields, fuse_spans, no polygons } -> out = { fuse, within, qualifies, taken, refill }
+ *   what 3, a plan slot's two buffers of aggregates over a sequence of events: in = { k <= 4096, event 0 .. k-1 }; event 0: a speculative setup
+ *           that settles, 1: one that never settles (a launch error), 2: the slot is allocated afresh -> out[2 i], out[2 i + 1] = what setup i
+ *           does first: { clear both buffers, add into the second } (-1, -1 for event 2).  A diagnostic, not a fallback. */
+int fcpp_debug_setup_rule(int what, const int64_t *in, int64_t *out);
 /* What fcpp_ga_evolve will launch per generation for n_nodes and population_size on the context's device -- host code, the function its
  * launchers read; out (a HOST pointer) = { 1: one launch per generation (k_ga_generation), 0: two launches on two streams; pair workgroups;
  * base; extra (workgroup b takes base + (b < extra) pairs); the most pairs of one workgroup; dynamic LDS bytes of the pair launch }.  So

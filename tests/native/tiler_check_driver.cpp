@@ -142,7 +142,7 @@ int main(int argc, char **argv)
         ImageLayout lay;
         rc = tiler.plan(hp, tc, &polys, lay, err);
         if (rc != FCPP_OK) FAIL("tiler.plan: %s", err.c_str());
-        if (tc.fuse_spans && lay.unfusable_work > 0) {          // all spans of fields of field work are fused, or none (fcpp_api.cpp)
+        if (tc.fuse_spans && lay.unfusable_work > 0) {          // all spans of fields of field work are fused, or none (fcpp_setup.cpp)
             tc.fuse_spans = false;
             rc = tiler.plan(hp, tc, &polys, lay, err);
             if (rc != FCPP_OK) FAIL("tiler.plan (again): %s", err.c_str());
