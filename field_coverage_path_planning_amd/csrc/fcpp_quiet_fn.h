@@ -11,8 +11,11 @@ namespace fcpp {
 #ifndef FCPP_DENSE_NT
 #define FCPP_DENSE_NT 0      // (1: a build for the A/B)
 #endif
-typedef double st_pair_f64 __attribute__((ext_vector_type(2)));
-typedef uint32_t st_pair_u32 __attribute__((ext_vector_type(2)));
+// (a pair is one 16-byte / 8-byte element per lane whose ADDRESS is only that of its first value: 8-byte / 4-byte aligned, which global
+// memory instructions accept -- a caller's x_dev may lie at 8 (mod 16), and an odd out_base puts every pair there: the types say so, as
+// fcpp_sparse2_fn.h's pair stores do)
+typedef double st_pair_f64 __attribute__((ext_vector_type(2), aligned(8)));
+typedef uint32_t st_pair_u32 __attribute__((ext_vector_type(2), aligned(4)));
 template <bool NT>
 __device__ __forceinline__ void st2(double *ptr, double a, double b)
 {

@@ -254,7 +254,10 @@ int fcpp_batch_setup_times(const fcpp_batch *batch, fcpp_setup_times *out);
  * arrays of total_points elements; stats_dev has n_fields entries.
  * mode 0: staged pipeline (one kernel per operator, 7 launches); mode 1: fused single-pass kernels
  * (each point is written once, nothing is read back: closed-form runs and spans, wave tiles at sparse sampling,
- * general tiles) -- same results. */
+ * general tiles) -- same results.
+ * Buffers: the contract of the standalone operators below (natural alignment is enough -- x_dev at 8 (mod 16), flagseg_dev at 4 (mod 8) --,
+ * each of the six outputs is written exactly over its extent, every point and every field's statistics record -- zeros for a field that
+ * raises -- whatever the buffers held, and nothing beside them), in both modes; tests/test_gpu_step_guarded.py enforces it. */
 int fcpp_batch_run(fcpp_batch *batch, double *x_dev, double *y_dev, double *kappa_dev, double *v_dev,
                    uint32_t *flagseg_dev, fcpp_field_stats *stats_dev, int mode);
 /* The reference's plan call for a whole batch in ONE entry: plan_complete_coverage (MLP:387-465) sets a NEW field up and generates its path in
@@ -264,14 +267,18 @@ int fcpp_batch_run(fcpp_batch *batch, double *x_dev, double *y_dev, double *kapp
  * stats_dev: n_fields records of the caller's, or NULL: the batch's own (fcpp_batch_own_stats; they live as long as the batch).
  * Asynchronous like fcpp_batch_run: the arrays are complete when the context's stream is.
  * The batch stays valid for further fcpp_batch_run calls on the same arrays (or others) until fcpp_batch_destroy.  On an error nothing is
- * left allocated.  bench.py's headline step is this call + the stream drained. */
+ * left allocated.  bench.py's headline step is this call + the stream drained.
+ * Buffers: as fcpp_batch_run -- whichever step the call takes (the direct step behind the counting pass, or fcpp_batch_run) writes every one of
+ * the total_points elements of the five arrays it returns and nothing behind them, whatever the arena's memory held, and stats_dev needs
+ * only the alignment of its 8-byte members (tests/test_gpu_step_guarded.py). */
 int fcpp_batch_plan(fcpp_ctx *ctx, const fcpp_vehicle *veh, const fcpp_options *opt, int64_t n_fields, const fcpp_field *fields,
                     const fcpp_polys *obstacles, fcpp_field_stats *stats_dev, fcpp_batch **batch, double **x_dev, double **y_dev,
                     double **kappa_dev, double **v_dev, uint32_t **flagseg_dev, int64_t *total_points);
 /* the statistics records a batch keeps for callers that bring none (n_fields records inside the batch's own device allocation) */
 int fcpp_batch_own_stats(const fcpp_batch *batch, fcpp_field_stats **stats_dev);
 /* _generate_approach_path / _generate_departure_path (MLP:1313-1355): 50 points each, AoS (x,y) per
- * field at [field*100 .. +100); rows of fields without a kept start/end point are left untouched. */
+ * field at [field*100 .. +100); rows of fields without a kept start/end point, and of fields that raise, are left untouched.
+ * Either pointer may be NULL. */
 int fcpp_batch_connectors(fcpp_batch *batch, double *approach_xy_dev, double *departure_xy_dev);
 /* fcpp_trajectory (below) on the batch's own paths: TWO per field, main work then headland (the reference times them separately,
  * MLP:423-431), so path 2 f starts at point_offset of field f and has n_main points, path 2 f + 1 follows with n_head; a field that raises
@@ -301,7 +308,12 @@ int fcpp_batch_reduce_classes(const fcpp_batch *batch, int64_t *classes_out);
  * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_*, fcpp_route_* and fcpp_field_path_*
  * (tests/test_gpu_guarded.py enforces it for these entries): a device pointer needs only the natural alignment of its element type, an
  * output is written exactly over its stated extent -- every element of it, nothing beside it --, inputs are never written, and an output
- * must not overlap an input or another output except where an entry says so.  The other entries keep what their own comments state.
+ * must not overlap an input or another output except where an entry says so.  The same holds, enforced by
+ * tests/test_gpu_step_guarded.py, for fcpp_batch_run, fcpp_batch_plan, fcpp_batch_connectors, fcpp_batch_trajectory (above) and for
+ * fcpp_verify, fcpp_validate, fcpp_straight_segments, fcpp_corner_turns, fcpp_fresnel and fcpp_cover_grid; two of them write an output
+ * only in part and leave the rest of it untouched: fcpp_batch_connectors the rows of fields that raise or have no kept start / end point,
+ * fcpp_corner_turns the points of a corner's row behind its counts_dev[2k] + counts_dev[2k+1].  The other entries keep what their own
+ * comments state.
  * The offsets size the launches, so the host needs them: offsets_host (n_paths + 1 values, same content as offsets_dev) spares
  * the call a device-to-host copy and a stream synchronisation; NULL = the library reads offsets_dev back itself.  The tile table
  * built from the offsets is kept in the context and reused while consecutive calls bring the same offsets (compared by

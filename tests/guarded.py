@@ -16,6 +16,9 @@ tensor for the device entries -- so that all three show:
              is the all-0x5A pattern, so "still pre-filled" and "correct" exclude each other (a condition on the inputs the caller chose).
   in-out     a slot the call reads and writes (inout): pre-filled with the input and checked against expected[name] like an output; an
              expected element may be the all-0x5A pattern only where the input element is that very value.
+  mask       an output the call may write only in part (the connector rows of fields without a kept point, the unused tail of a corner's
+             row): a boolean mask of the elements it must leave alone, given to output() or to check().  Those must still hold the pre-fill;
+             all the others are checked as ever, the pre-fill rule included.
 An output passed as NULL has no slot.  Failures raise GuardError (an AssertionError) whose message names the slot.
 """
 import ctypes as C
@@ -32,9 +35,10 @@ class GuardError(AssertionError):
 
 
 class _Slot:
-    def __init__(self, name, dtype, count, data, written, inout=False):
+    def __init__(self, name, dtype, count, data, written, inout=False, keep=None):
         self.name, self.dtype, self.count, self.data, self.written = name, np.dtype(dtype), int(count), data, written
         self.inout = inout          # data = the input the slot is pre-filled with; checked like an output
+        self.keep = keep            # bool per element of an output: True = the call must leave it alone (None: it writes them all)
         self.start = self.end = -1
 
     @property
@@ -75,9 +79,20 @@ class Arena:
         a = np.ascontiguousarray(array, dtype=dtype)
         return self._add(_Slot(name, a.dtype, a.size, _as_bytes(a, a.dtype).copy(), True, inout=True))
 
-    def output(self, name, dtype, count, written=True):
-        """written=False: a slot the call is handed (or not) and must leave alone"""
-        return self._add(_Slot(name, dtype, int(np.prod(count)), None, written))
+    def output(self, name, dtype, count, written=True, keep=None):
+        """written=False: a slot the call is handed (or not) and must leave alone; keep: a boolean mask, one entry per element, of the
+        elements the call must leave alone (check(keep=...) may bring it instead, when only the call's results tell)"""
+        n = int(np.prod(count))
+        return self._add(_Slot(name, dtype, n, None, written, keep=self._mask(name, keep, n)))
+
+    @staticmethod
+    def _mask(name, keep, count):
+        if keep is None:
+            return None
+        m = np.ascontiguousarray(keep).reshape(-1)
+        if m.dtype != np.bool_ or m.size != count:
+            raise ValueError('slot %r: the mask is %s x %d, the slot has %d elements' % (name, m.dtype, m.size, count))
+        return m.copy()
 
     # ---- layout ---------------------------------------------------------------------------------------------------------------------
     def build(self, device=None):
@@ -145,13 +160,21 @@ class Arena:
         return image[s.start:s.end].copy().view(s.dtype)
 
     # ---- the check ------------------------------------------------------------------------------------------------------------------
-    def check(self, expected):
-        """expected: {name: array} for exactly the written output slots and the in-out slots.  -> {name: array} of what the slots hold"""
+    def check(self, expected, keep=None):
+        """expected: {name: array} for exactly the written output slots and the in-out slots.  keep: {name: boolean mask} of elements of
+        written output slots that the call must leave alone (in place of a mask given to output(); what expected[name] holds there is not
+        looked at).  -> {name: array} of what the slots hold"""
         img = self.snapshot()
         slots = list(self._slots.values())
         outputs = {s.name for s in slots if s.inout or (s.data is None and s.written)}
         if set(expected) != outputs:
             raise GuardError('expected values for %s, written output slots %s' % (sorted(expected), sorted(outputs)))
+        masks = {s.name: s.keep for s in slots if s.keep is not None}
+        for name, m in (keep or {}).items():
+            s = self._slots.get(name)
+            if s is None or s.inout or s.data is not None or not s.written:
+                raise GuardError('a mask for %r, which is no written output slot' % name)
+            masks[name] = self._mask(name, m, s.count)
         # 1: the guards
         guard = np.ones(len(img), dtype=bool)
         for s in slots:
@@ -193,10 +216,20 @@ class Arena:
             is_fill = (want.reshape(-1, size) == FILL_BYTE).all(axis=1)
             if s.inout:          # (an element the call may leave as it was put in)
                 is_fill &= (want.reshape(-1, size) != s.data.reshape(-1, size)).any(axis=1)
+            differ = (have.reshape(-1, size) != want.reshape(-1, size)).any(axis=1)
+            kept = masks.get(s.name)
+            if kept is not None:          # (the elements the call must leave alone: still the pre-fill, whatever expected[name] holds there)
+                touched = np.flatnonzero(kept & (have.reshape(-1, size) != FILL_BYTE).any(axis=1))
+                if touched.size:
+                    k = int(touched[0])
+                    raise GuardError('output slot %r: %d of the %d elements the call must leave alone were written, the first element %d: %r'
+                                     % (s.name, touched.size, int(kept.sum()), k, have.view(s.dtype)[k:k + 1].tolist()))
+                is_fill &= ~kept
+                differ &= ~kept
             prefilled = np.flatnonzero(is_fill)
             if prefilled.size:
                 raise GuardError('expected[%r][%d] is the pre-fill pattern itself: choose other inputs' % (s.name, prefilled[0]))
-            bad = np.flatnonzero((have.reshape(-1, size) != want.reshape(-1, size)).any(axis=1))
+            bad = np.flatnonzero(differ)
             if bad.size and s.inout:
                 k = int(bad[0])
                 untouched = int((have.reshape(-1, size)[bad] == s.data.reshape(-1, size)[bad]).all(axis=1).sum())

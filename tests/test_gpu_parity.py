@@ -98,11 +98,21 @@ def _compare_with_oracle_mode(mode, specs, ofields, veh_arr, opt_kw, xy_tol, k_t
         specs = E.as_table(specs).to_device()
     batch = E.Batch(specs, _veh(veh_arr), o)
     res = batch.run(mode=mode)
+    _compare_result_with_oracle(batch, res, _oracle_plans(ofields, veh_arr, o), xy_tol, k_tol, v_tol)
+    batch.close()
+
+
+def _oracle_plans(ofields, veh_arr, o):
+    """-> [(rc, plan)] of the oracle for every field under the fcpp_options o"""
+    oopt = orc.Options.make(o.turn_model, o.clothoid_fit, o.sample_spacing, o.clothoid_frac, o.geofence_tol, o.obstacle_mode, o.ring_order)
+    return [orc.plan_field(of, orc.Vehicle.make(veh_arr), oopt) for of in ofields]
+
+
+def _compare_result_with_oracle(batch, res, plans, xy_tol=XY_TOL, k_tol=K_TOL, v_tol=V_TOL):
+    """the comparisons of a step's result (a BatchResult of `batch`, whichever arrays it was run into) with the oracle's plans"""
     x, y, v, k, fs = _np(res.x), _np(res.y), _np(res.v), _np(res.kappa), _np(res.flagseg).view(np.uint32)
     st = res.stats()
-    oopt = orc.Options.make(o.turn_model, o.clothoid_fit, o.sample_spacing, o.clothoid_frac, o.geofence_tol, o.obstacle_mode, o.ring_order)
-    for i, of in enumerate(ofields):
-        rc, p = orc.plan_field(of, orc.Vehicle.make(veh_arr), oopt)
+    for i, (rc, p) in enumerate(plans):
         info = batch.info[i]
         assert rc == info.status
         if rc != 0:
@@ -121,7 +131,14 @@ def _compare_with_oracle_mode(mode, specs, ofields, veh_arr, opt_kw, xy_tol, k_t
                                    [p.max_kappa, p.max_alat, p.max_jump], rtol=1e-7, atol=max(k_tol, 1e-11))
         assert (st['n_viol'][i], st['n_outside'][i], st['n_in_obstacle'][i], st['n_adjusted'][i]) == \
             (p.n_viol, p.n_outside, p.n_in_obstacle, p.n_adjusted), i
-    batch.close()
+
+
+def _dense_tols(opt):
+    """(xy_tol, k_tol, v_tol) of the build-defined sampling modes: curvature from a 3-point stencil amplifies coordinate rounding by
+    ~4 / ds^2 (the tolerances test_dense_and_clothoid_sampling_vs_oracle and the obstacle-aware tests below spell out)"""
+    ds = opt.get('sample_spacing', 0.0) or 0.5
+    k_tol = max(K_TOL, 4e-12 / ds ** 2)
+    return 1e-9, k_tol, max(V_TOL, 200 * k_tol)
 
 
 def _random_fields(seed, n, para=False, with_obstacles=False, with_points=True):

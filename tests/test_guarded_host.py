@@ -3,7 +3,9 @@
 First the harness proves itself: deliberately wrong writers written in numpy -- one element past the end, one in front of the start, the
 last element left out, a bit of an input flipped -- must each fail the check with a message that names the slot, for every element size the
 device tests use.  That is what shows tests/test_gpu_guarded.py would fail on such a kernel.  In-out slots (a buffer the call reads and
-rewrites, as fcpp_ga_evolve's population) are proved the same way: left untouched where a change was expected, or written beside.
+rewrites, as fcpp_ga_evolve's population) are proved the same way: left untouched where a change was expected, or written beside.  So is an
+output the call may write only in part (a mask of the elements it must leave alone: fcpp_batch_connectors' rows, fcpp_corner_turns' row
+tails): a write into a masked element is caught, a skipped unmasked one is, a correct partial write passes.
 
 Then fcpp_debug_dubins, fcpp_debug_rs, fcpp_debug_swaths, fcpp_debug_route_transit and fcpp_debug_route run through a numpy arena on the
 batches the device tests use (defined here, imported there): the twins stay inside their buffers, leave their inputs alone and give the
@@ -281,6 +283,73 @@ def test_inout_prefill_pattern_rule():
     A.view('state')[:] = [5, fill, 6]
     with pytest.raises(GuardError, match=r"expected\['state'\]\[1\] is the pre-fill pattern"):
         A.check({'state': np.array([5, fill, 6], dtype=np.int32)})
+
+
+def _toy_masked(at_check):
+    """rows of 3: the call writes rows 0 and 2 and the first element of row 1 -- the rest of row 1 it must leave alone"""
+    keep = np.zeros(9, dtype=bool)
+    keep[4:6] = True
+    want = {'rows': 100.0 + np.arange(9), 'n': np.array([3, 1, 3], dtype=np.int32)}
+    A = Arena().input('x', X_IN).output('rows', np.float64, 9, keep=None if at_check else keep).output('n', np.int32, 3).build()
+    A.view('n')[:] = want['n']
+    A.view('rows')[~keep] = want['rows'][~keep]
+    return A, want, ({'rows': keep} if at_check else None)
+
+
+@pytest.mark.parametrize('at_check', [False, True], ids=['mask at output()', 'mask at check()'])
+def test_a_partly_written_output(at_check):
+    # a correct partial write passes, whatever the expected values say where the mask is set -- the pre-fill pattern included
+    A, want, keep = _toy_masked(at_check)
+    got = A.check(want, keep=keep)
+    assert np.array_equal(got['rows'][:4], want['rows'][:4]) and (got['rows'][4:6].view(np.uint8) == FILL_BYTE).all()
+    A.check(dict(want, rows=np.where(np.arange(9) == 4, A.view('rows')[4], want['rows'])), keep=keep)
+    # a write into a masked element is caught, the right value too
+    A, want, keep = _toy_masked(at_check)
+    A.view('rows')[5] = want['rows'][5]
+    with pytest.raises(GuardError, match=r"output slot 'rows': 1 of the 2 elements the call must leave alone were written, the first element 5"):
+        A.check(want, keep=keep)
+    # one byte of a masked element
+    A, want, keep = _toy_masked(at_check)
+    A.view('rows').view(np.uint8)[8 * 4 + 7] ^= 0x80
+    with pytest.raises(GuardError, match=r"must leave alone were written, the first element 4"):
+        A.check(want, keep=keep)
+    # a skipped unmasked element is caught as ever
+    A, want, keep = _toy_masked(at_check)
+    A.view('rows').view(np.uint8)[8 * 3:8 * 4] = FILL_BYTE
+    with pytest.raises(GuardError, match=r"output slot 'rows': 1 of 9 elements differ \(1 of them still pre-filled\), the first element 3"):
+        A.check(want, keep=keep)
+    # ... and so are a wrong value, an unmasked expected element that is the pre-fill pattern, and a write beside the slot
+    A, want, keep = _toy_masked(at_check)
+    A.view('rows')[8] += 1.0
+    with pytest.raises(GuardError, match=r"output slot 'rows': 1 of 9 elements differ \(0 of them still pre-filled\), the first element 8"):
+        A.check(want, keep=keep)
+    A, want, keep = _toy_masked(at_check)
+    fill = np.frombuffer(bytes([FILL_BYTE] * 8), dtype=np.float64)[0]
+    A.view('rows')[6] = fill
+    with pytest.raises(GuardError, match=r"expected\['rows'\]\[6\] is the pre-fill pattern"):
+        A.check(dict(want, rows=np.where(np.arange(9) == 6, fill, want['rows'])), keep=keep)
+    A, want, keep = _toy_masked(at_check)
+    s, e = A.span('rows')
+    A.raw[e:e + 8] = A.raw[e - 8:e]
+    with pytest.raises(GuardError, match=r"guard bytes were written.*behind the end of slot 'rows'"):
+        A.check(want, keep=keep)
+
+
+def test_masks_are_for_written_outputs_of_their_size():
+    keep = np.zeros(9, dtype=bool)
+    with pytest.raises(ValueError, match='mask'):
+        Arena().output('rows', np.float64, 9, keep=keep[:8])
+    with pytest.raises(ValueError, match='mask'):
+        Arena().output('rows', np.float64, 9, keep=keep.astype(np.int8))
+    A, want, _ = _toy_masked(True)
+    for bad in ({'x': np.zeros(7, dtype=bool)}, {'missing': keep}):
+        with pytest.raises(GuardError, match='no written output slot'):
+            A.check(want, keep=bad)
+    with pytest.raises(ValueError, match='mask'):
+        A.check(want, keep={'rows': keep[:8]})
+    # without a mask the untouched elements of row 1 fail as skipped elements
+    with pytest.raises(GuardError, match=r"output slot 'rows': 2 of 9 elements differ \(2 of them still pre-filled\), the first element 4"):
+        A.check(want)
 
 
 # ---- 2: the host twins through a numpy arena ------------------------------------------------------------------------------------------
