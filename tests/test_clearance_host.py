@@ -142,15 +142,25 @@ def even_odd(pt, a, b):
     return int(np.count_nonzero(c & (x < xi))) % 2 == 1
 
 
-def oracle(xs, ys, field):
-    """chords of the sampled path against the edges of the field -> (clear, decided, s of the first crossing chord's start or inf)"""
+def oracle(xs, ys, field, near_box=None):
+    """chords of the sampled path against the edges of the field -> (clear, decided, s of the first crossing chord's start or inf).
+    near_box [m]: for a field of many small rings, the chords are tested only against the edges whose own box meets the path's box grown
+    by near_box (an edge outside it neither crosses a chord nor comes within near_box of one; near_box must exceed NEAR); the start
+    point's parity counts every edge"""
     a, b = edges_of(field)
     P = np.column_stack([xs, ys])
+    inside = even_odd(P[0], a, b)
+    if near_box is not None:
+        assert near_box > NEAR
+        lo, hi = P.min(axis=0) - near_box, P.max(axis=0) + near_box
+        keep = ~((np.maximum(a, b) < lo).any(axis=1) | (np.minimum(a, b) > hi).any(axis=1))
+        a, b = a[keep], b[keep]
+        if not len(a):
+            return bool(inside), True, None
     p, q = P[:-1, None, :], P[1:, None, :]
     A, Bv = a[None], b[None]
     cross = ((_orient(p, q, A) > 0) != (_orient(p, q, Bv) > 0)) & ((_orient(A, Bv, p) > 0) != (_orient(A, Bv, q) > 0))
     hit = cross.any(axis=1)
-    inside = even_odd(P[0], a, b)
     if hit.any():
         return False, True, int(np.argmax(hit))
     near = min(_dist_point_segments(P, a, b).min(), _dist_point_segments(a, P[:-1], P[1:]).min() if len(P) > 1 else np.inf)
@@ -422,3 +432,76 @@ def test_holed_square_routed_with_clearance_is_blocked_no_more_than_without(mode
     # recorded on the host twin, so that the case cannot decay to 0 <= 0: at R = 6 nearly every Dubins turn leaves the 40 m square, the
     # three-point turns stay inside but for one
     assert counts == ([13, 12] if mode == 0 else [1, 1])
+
+
+# ---- a region of 259 rings -------------------------------------------------------------------------------------------------------------------
+# The device's transit kernel reads a region's ring sizes 256 at a time (a workgroup's threads): rings 256 .. 258 are its second round, and
+# its edge chunks find an edge's ring by bisection over all 259.  The region: the 258 triangular holes of tests/test_inset_host.py at
+# half scale (1.35 m wide on a pitch of 5 m, the lattice 85 m x 80 m; the last three, rings 256 .. 258, alone in the top row) in an
+# outline with room around the lattice.  Pose pairs beside the lattice, around the last row's holes and over the lattice; a work of two
+# swaths (W = 4, R = 6, as the strips above) whose left ends stand 0.3 m right of the last hole.
+def many_ring_region(spoil=None):
+    from tests.test_inset_host import holed_square, spoilt_last_ring
+    rings = holed_square(scale=0.5)
+    rings[0] = np.array([(-30.0, -12.0), (125.0, -12.0), (125.0, 120.0), (-30.0, 120.0)])
+    return spoilt_last_ring(rings, spoil) if spoil else rings
+
+
+MANY_RINGS = many_ring_region()
+MANY_RINGS_CUT = MANY_RINGS[:-3]          # without the rings of the second round: what an answer would be if nobody looked at them
+MANY_RINGS_N = 96
+
+
+def many_ring_pairs(n=MANY_RINGS_N, seed=4):
+    rng = np.random.default_rng(seed)
+    c = MANY_RINGS[-1].mean(axis=0)
+
+    def around(lo, hi, m):
+        frm = np.column_stack([rng.uniform(lo[0], hi[0], m), rng.uniform(lo[1], hi[1], m), rng.uniform(-np.pi, np.pi, m)])
+        d, a = rng.uniform(2, 10, m), rng.uniform(-np.pi, np.pi, m)
+        return frm, np.column_stack([frm[:, 0] + d * np.cos(a), frm[:, 1] + d * np.sin(a), rng.uniform(-np.pi, np.pi, m)])
+    parts = [around((-24, -4), (-14, 100), n // 3), around((c[0] - 12, c[1] + 1.5), (c[0] + 6, c[1] + 6), n // 3), around((2, 2), (80, 72), n - 2 * (n // 3))]
+    return np.vstack([p[0] for p in parts]), np.vstack([p[1] for p in parts])
+
+
+def many_ring_work():
+    c = MANY_RINGS[-1].mean(axis=0)
+    x0, y0 = c[0] + 0.3, c[1] - 2.0
+    return [(x0, y0), (x0 + 26.0, y0), (x0 + 26.0, y0 + 7.0), (x0, y0 + 7.0)]
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_many_ring_region_the_last_rings_decide_and_the_oracle_agrees(mode):
+    R = 4.0
+    assert len(MANY_RINGS) == 259 and sum(len(r) for r in MANY_RINGS) == 778 > 3 * L.CLEAR_EDGE_CHUNK
+    frm, to = many_ring_pairs()
+    full = clearance(frm, to, [MANY_RINGS], 0, R, mode)
+    cut = clearance(frm, to, [MANY_RINGS_CUT], 0, R, mode)
+    by_last = full['crossings'] != cut['crossings']
+    print(f'mode {mode}: {full["clear"].sum()} clear, {by_last.sum()} cross a ring of index >= 256')
+    assert by_last.sum() >= 3 and full['clear'].sum() >= 20 and (full['crossings'] > 0).sum() >= 10 and full['field_status'].tolist() == [0]
+    # the spoilt regions: the status of a field whose LAST ring is degenerate or not finite, and every pair as in a bad field
+    for how in ('short', 'nan'):
+        bad = clearance(frm, to, [many_ring_region(how)], 0, R, mode)
+        assert bad['field_status'].tolist() == [L.EINVAL] and not bad['clear'].any() and np.isnan(bad['first_s']).all()
+    # the chord oracle, its cap unchanged
+    smp, word, seg, _ = sampled(frm, to, R, mode)
+    assert np.array_equal(word, full['word'])
+    undecided = 0
+    for i, (x, y, _) in enumerate(smp):
+        clear, decided, _ = oracle(x, y, MANY_RINGS, near_box=0.5)
+        if not decided:
+            undecided += 1
+            continue
+        assert clear == bool(full['clear'][i]), (mode, i, frm[i], to[i])
+    print(f'mode {mode}: {undecided} of {len(smp)} undecided')
+    assert undecided <= 0.02 * len(smp)
+    # the transit block of the work beside the last hole
+    tcut = cut_with_angle([many_ring_work()], 0.0, 4.0)
+    T, toff = host_transit(tcut, 6.0, mode)
+    B = host_transit_clear(tcut, [MANY_RINGS], T.copy(), toff, 6.0, mode, 0.0).reshape(4, 4)
+    Bc = host_transit_clear(tcut, [MANY_RINGS_CUT], T.copy(), toff, 6.0, mode, 0.0).reshape(4, 4)
+    other = (np.arange(4)[:, None] >> 1) != (np.arange(4)[None, :] >> 1)
+    assert (B != Bc).sum() >= 2 and (B[other] == 0).any() and (B[other] == 1).any() and not Bc[other].all()
+    for how in ('short', 'nan'):
+        assert host_transit_clear(tcut, [many_ring_region(how)], T.copy(), toff, 6.0, mode, 0.0).reshape(4, 4)[other].all()

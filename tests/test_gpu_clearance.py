@@ -3,14 +3,15 @@ twins give -- integers exactly, first_s and T bit for bit, both modes -- on the 
 a triangular hole, a field of FCPP_CLEAR_EDGE_CHUNK + 1 edges with the swaths inside it (a second LDS chunk that holds one edge, on which the start points'
 parity and the right-hand turns' crossings hang), a field whose first chunk a turn skips by its box, fields of 0, 1, 2 and 33 swaths (66
 oriented swaths: the canonical pairs of a row straddle a 64-lane boundary), a batch with a field without rings and an invalid one in the
-middle, n = 0, 1, 65 paths with pair_field unsorted and with -1.  Then the engine's layers on top of them."""
+middle, n = 0, 1, 65 paths with pair_field unsorted and with -1; a region of 259 rings (the ring loop's second round of 256) whose last
+rings decide answers, intact and with the LAST ring spoilt.  Then the engine's layers on top of them."""
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
-from tests.test_clearance_host import (PENALTY, REGION, SQUARE_HOLE, WORK, WORK_R, bits, clearance, driven_blocked, host_clear, host_solve,
-                                       host_transit_clear)
+from tests.test_clearance_host import (MANY_RINGS, MANY_RINGS_CUT, PENALTY, REGION, SQUARE_HOLE, WORK, WORK_R, bits, clearance, driven_blocked,
+                                       host_clear, host_solve, host_transit_clear, many_ring_pairs, many_ring_region, many_ring_work)
 from tests.test_route_host import cut_with_angle, host_transit
 from tests.test_swaths_host import pack
 
@@ -190,6 +191,68 @@ def test_the_second_lds_chunk_decides_results(transit_case, mode):
     right = [(2 * s, 2 * t + 1) for s in range(5) for t in range(5) if s != t]            # leaves at b (x = 60), enters at b
     assert all(cut['bx'][s >> 1] == 60.0 for s, _ in right)
     assert any(c[s, t] == 0 and 60.0 - T[s, t] > pond_x1 + 6.0 for s, t in right)        # the whole path stays right of the pond's box
+
+
+# ---- a region of 259 rings: the second round of the ring loop ---------------------------------------------------------------------------------
+# (tests/test_clearance_host.py builds the region, checks it against the chord oracle and asserts that rings 256 .. 258 decide answers)
+def many_ring_regions():
+    """the region, its two copies with the LAST ring spoilt, and the region without its last three rings"""
+    return [MANY_RINGS, many_ring_region('short'), MANY_RINGS_CUT, many_ring_region('nan')]
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_region_of_259_rings_elementwise(gpu, mode):
+    R = 4.0
+    frm, to = many_ring_pairs()
+    n = len(frm)
+    frm, to, pair_field = np.tile(frm, (4, 1)), np.tile(to, (4, 1)), np.repeat(np.arange(4), n)
+    word, seg, _ = host_solve(frm, to, R, mode)
+    fields = many_ring_regions()
+    want = host_clear(mode, frm, R, word, seg, pair_field, fields)
+    assert want['field_status'].tolist() == [0, L.EINVAL, 0, L.EINVAL]
+    full, cut = want['crossings'][:n], want['crossings'][2 * n:3 * n]
+    assert (full != cut).sum() >= 3 and want['clear'][:n].sum() >= 20 and not want['clear'][n:2 * n].any() and not want['clear'][3 * n:].any()
+    got = device_clear(gpu, mode, frm, R, word, seg, pair_field, fields)
+    for k in ('crossings', 'inside', 'field_status'):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(bits(got['first_s']), bits(want['first_s']))
+
+
+@pytest.fixture(scope='module')
+def many_ring_transit():
+    cut = cut_with_angle([many_ring_work()] * 4, 0.0, 4.0)
+    assert np.diff(cut['offsets']).tolist() == [2] * 4
+    per_mode = {}
+    for mode in (0, 1):
+        T0, toff = host_transit(cut, 6.0, mode)
+        Tp = T0.copy()
+        B = host_transit_clear(cut, many_ring_regions(), Tp, toff, 6.0, mode, PENALTY)
+        per_mode[mode] = (T0, Tp, B, toff)
+    return cut, per_mode
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_region_of_259_rings_transit_block(gpu, many_ring_transit, mode):
+    """the ring sizes are read 256 at a time: a LAST ring of two vertices blocks the whole field only if round two reads it; the edges of
+    rings 256 .. 258 sit in the fourth edge chunk with their ring found by bisection over 259 offsets"""
+    import torch
+    ctx, dev = gpu
+    cut, per_mode = many_ring_transit
+    T0, Tp, B, toff = per_mode[mode]
+    b = B.reshape(4, 4, 4)
+    other = (np.arange(4)[:, None] >> 1) != (np.arange(4)[None, :] >> 1)
+    assert (b[0] != b[2]).sum() >= 2 and (b[0][other] == 0).any() and b[1][other].all() and b[3][other].all() and not b[2][other].all()
+    soff = cut['offsets']
+    ro, vo, x, y = (_t(a, dev) for a in pack(many_ring_regions()))
+    d = {k: _t(cut[k], dev) for k in ('ax', 'ay', 'bx', 'by', 'angle')}
+    soff_d, toff_d = _t(soff, dev), _t(toff, dev)
+    T = _t(T0.copy(), dev)
+    Bd = torch.full((int(toff[-1]),), 7, dtype=torch.uint8, device=dev)
+    L.check(ctx.lib.fcpp_route_transit_clear(ctx.handle, len(soff) - 1, _ptr(soff_d), soff.ctypes.data, int(soff[-1]), _ptr(d['ax']), _ptr(d['ay']),
+                                             _ptr(d['bx']), _ptr(d['by']), _ptr(d['angle']), 6.0, mode, _ptr(toff_d), None, int(toff[-1]), _ptr(ro),
+                                             int(vo.numel()) - 1, _ptr(vo), int(x.numel()), _ptr(x), _ptr(y), PENALTY, _ptr(T), _ptr(Bd)))
+    assert np.array_equal(Bd.cpu().numpy(), B)
+    assert np.array_equal(bits(T.cpu().numpy()), bits(Tp))
 
 
 # ---- the engine's layers ------------------------------------------------------------------------------------------------------------------

@@ -92,14 +92,10 @@ def transit_case():
     return cut, per_mode
 
 
-@pytest.mark.parametrize('mode', [0, 1])
-@pytest.mark.parametrize('penalty', [0.0, PENALTY])
-@pytest.mark.parametrize('where', ['device', 'host'])
-def test_route_transit_clear_stays_in_bounds(gpu, transit_case, mode, penalty, where):
-    cut, per_mode = transit_case
+def transit_on_an_arena(gpu, cut, regions, per_mode, mode, penalty, where):
     T0, Tp, B, toff = per_mode[mode]
     soff = cut['offsets']
-    ro, vo, x, y = pack(REGIONS)
+    ro, vo, x, y = pack(regions)
     A = Arena()
     for name, a in (('soff', soff), ('ax', cut['ax']), ('ay', cut['ay']), ('bx', cut['bx']), ('by', cut['by']), ('angle', cut['angle']), ('toff', toff),
                     ('ro', ro), ('vo', vo), ('x', x), ('y', y)):
@@ -124,3 +120,23 @@ def test_route_transit_clear_stays_in_bounds(gpu, transit_case, mode, penalty, w
         rc = gpu.lib.fcpp_debug_route_transit_clear(n, A.ptr('soff'), nt, *head, *tail)
     assert rc == L.OK, gpu.lib.fcpp_last_error()
     A.check({'T': Tp, 'B': B} if penalty else {'B': B})
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+@pytest.mark.parametrize('penalty', [0.0, PENALTY])
+@pytest.mark.parametrize('where', ['device', 'host'])
+def test_route_transit_clear_stays_in_bounds(gpu, transit_case, mode, penalty, where):
+    cut, per_mode = transit_case
+    transit_on_an_arena(gpu, cut, REGIONS, per_mode, mode, penalty, where)
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_region_of_259_rings_stays_in_bounds(gpu, mode):
+    """the new shape class, a region of more rings than the transit kernel has threads (tests/test_gpu_clearance.py), once per mode"""
+    from tests.test_gpu_clearance import many_ring_regions
+    from tests.test_clearance_host import many_ring_work
+    cut = cut_with_angle([many_ring_work()] * 4, 0.0, 4.0)
+    T0, toff = host_transit(cut, R_TRANSIT, mode)
+    Tp = T0.copy()
+    B = host_transit_clear(cut, many_ring_regions(), Tp, toff, R_TRANSIT, mode, PENALTY)
+    transit_on_an_arena(gpu, cut, many_ring_regions(), {mode: (T0, Tp, B, toff)}, mode, PENALTY, 'device')

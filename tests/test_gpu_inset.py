@@ -6,14 +6,19 @@ polygon_swaths -> route_swaths with every swath end point at least two working w
 The host reference is computed once per KIND of field at the three distances and shared: the rule takes every (field, distance) pair on
 its own (tests/test_inset_host.py::test_statuses_leave_the_neighbours_alone asserts that on the host), so a batch's expected arrays are
 the kinds' arrays laid end to end.  The edge counts straddle a wavefront (63 / 64 / 65: the one-wavefront kernel ends at 64 edges) and a
-workgroup (256 / 257), the batch sizes 1 / 63 / 65 / 257 straddle them for the scan; 1024 is the edge cap and 1025 is over it."""
+workgroup (256 / 257), the batch sizes 1 / 63 / 65 / 257 straddle them for the scan; 1024 is the edge cap and 1025 is over it.
+
+Second rounds.  The workgroup kernel is launched 1024 pairs at a time: batches of 1023 / 1024 / 1025 / 2049 pairs end just under one
+launch, at its end, one pair into a second launch and one pair into a third (LAUNCH_BATCHES).  The kernel's loops over a field's rings
+stride by the workgroup's 256 threads: the field of 259 rings (tests/test_inset_host.py: HOLED) drives them into a second round, and
+the two copies whose LAST ring alone is spoilt are EINVAL only if that round looks at it."""
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
-from tests.test_inset_host import DUMBBELL, POND_EDGE, SQUARE, HostInset, boundary_distance
+from tests.test_inset_host import DUMBBELL, HOLED, HOLED_DISTS, POND_EDGE, SQUARE, HostInset, boundary_distance, spoilt_last_ring
 from tests.test_swaths_host import COMB, ELL, HOLE, RECT, pack, rings_of, star
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +104,113 @@ def test_small_fields_one_wavefront_kernel(kinds_host, n):
     picks = [small[(i + 8) % len(small)] for i in range(n)]
     dev = E.polygon_inset([KINDS[k][1] for k in picks], DISTS, ARC_STEP)
     assert_equal_bits(dev, expected(kinds_host, picks, (0, 1, 2)))
+
+
+# ---- more than one launch of the workgroup kernel ------------------------------------------------------------------------------------------
+LAUNCH_PAIRS = 1024          # INSET_LAUNCH_PAIRS of csrc/fcpp_inset.hip
+# (fields, distance columns): 1023 = 341 x 3, 1024 = 512 x 2, 1025 = 205 x 5 (columns may repeat), 2049 = 683 x 3, 1025 = 1025 x 1
+LAUNCH_BATCHES = [(341, (0, 1, 2)), (512, (0, 2)), (205, (0, 1, 2, 0, 1)), (683, (0, 1, 2)), (1025, (1,))]
+
+
+def launch_picks(n, last):
+    """KINDS cycled to n fields, turned so that the last field is the kind `last`"""
+    names = [k for k, _ in KINDS]
+    return [(i - (n - 1) + names.index(last)) % len(KINDS) for i in range(n)]
+
+
+def assert_drives_the_launches(picks, cols, want, last_has_rings):
+    """the CPU side of the launch tests: what the batch is named for, from the inputs and the twin's answer"""
+    m = len(picks) * len(cols)
+    launches = -(-m // LAUNCH_PAIRS)
+    assert len(want['status']) == m and launches == {1023: 1, 1024: 1, 1025: 2, 2049: 3}[m]
+    assert KINDS[picks[-1]][0] in ('star65', 'empty', 'nan') and sorted(set(picks)) == list(range(len(KINDS)))
+    assert max(len(np.concatenate(rings_of(KINDS[k][1]))) for k in picks) > 64          # the workgroup kernel, not the one-wavefront one
+    assert (want['pro'][-1] > want['pro'][-2]) == last_has_rings
+    grows = np.diff(want['pro']) > 0
+    for edge in range(LAUNCH_PAIRS, m, LAUNCH_PAIRS):          # pairs with rings just before every launch edge, and behind it
+        assert grows[edge - 3 * len(KINDS):edge].any() and (grows[edge:].any() or not last_has_rings)
+    if m == 2049:
+        assert grows[LAUNCH_PAIRS:2 * LAUNCH_PAIRS].sum() > 500 and np.count_nonzero(want['status'][LAUNCH_PAIRS:2 * LAUNCH_PAIRS]) > 100
+
+
+# every batch ending in a pair with rings; where a later launch exists, also ending in an empty inset and in a status (the launch's last
+# workgroup returns early there and must still write the end of the rings' offsets)
+LAUNCH_CASES = [(n, cols, 'star65') for n, cols in LAUNCH_BATCHES] + [(n, cols, last) for n, cols in LAUNCH_BATCHES[2:] for last in ('empty', 'nan')]
+LAUNCH_IDS = ['%dx%d-%s' % (n, len(c), last) for n, c, last in LAUNCH_CASES]
+
+
+@pytest.mark.parametrize('n,cols,last', LAUNCH_CASES, ids=LAUNCH_IDS)
+def test_more_pairs_than_one_launch(kinds_host, n, cols, last):
+    """pair = pair0 + blockIdx.x with the slabs by blockIdx.x; out_vert_offsets[total_rings] from the LAST launch, whether its pair has
+    rings or returns early (empty, a status).  The inputs' side is asserted without a device in tests/test_inset_host.py."""
+    picks = launch_picks(n, last)
+    want = expected(kinds_host, picks, cols)
+    assert_drives_the_launches(picks, cols, want, last == 'star65')
+    dev = E.polygon_inset([KINDS[k][1] for k in picks], [DISTS[j] for j in cols], ARC_STEP)
+    assert_equal_bits(dev, want)
+
+
+# ---- more rings than the workgroup has threads ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def holed_host():
+    fields = [spoilt_last_ring(HOLED, 'nan'), HOLED, [ELL, HOLE], spoilt_last_ring(HOLED, 'short')]
+    return fields, HostInset(fields, HOLED_DISTS, ARC_STEP)
+
+
+def holed_want(h):
+    return dict(pro=h.pro, pvo=h.pvo, ovo=h.ovo, x=h.x, y=h.y, src=h.src, status=h.status.reshape(-1), gap=h.gap.reshape(-1))
+
+
+def test_more_rings_than_threads(holed_host):
+    """the validity pass and the orientation pass stride over the field's rings by 256: rings 256 .. 258 are the second round's.  The
+    spoilt copies are sound up to ring 257; the intact field's last holes are oriented (and so inset) only by that round."""
+    fields, h = holed_host
+    assert [len(f) for f in fields] == [259, 259, 2, 259]
+    assert h.status.tolist() == [[L.EINVAL] * 3, [0] * 3, [0] * 3, [L.EINVAL] * 3]
+    n_out = [len(h.rings(1, j)) for j in range(3)]
+    assert n_out[0] == n_out[1] == 259 and 1 < n_out[2] != 259          # apart, apart, merged: read from the twin
+    dev = E.polygon_inset(fields, HOLED_DISTS, ARC_STEP)
+    assert_equal_bits(dev, holed_want(h))
+
+
+def guarded_counts_and_fill(fields, dists, want):
+    """fcpp_inset_counts and fcpp_inset_fill once each, every output on a guarded arena"""
+    ctx = E.get_context(None)
+    ctx.bind_stream()
+    import torch
+    dev = torch.device('cuda', ctx.device)
+    ro, vo, x, y = pack(fields)
+    n, D = len(fields), len(dists)
+    m, R, V = n * D, int(want['pro'][-1]), int(want['pvo'][-1])
+
+    def inputs(A):
+        return A.input('ro', ro).input('vo', vo).input('x', x).input('y', y).input('dist', np.asarray(dists, dtype=np.float64))
+
+    def head(A):
+        return (n, A.ptr('ro'), len(vo) - 1, A.ptr('vo'), len(x), A.ptr('x'), A.ptr('y'), D, A.ptr('dist'), ARC_STEP)
+
+    A = inputs(Arena())
+    A.output('pro', np.int64, m + 1).output('pvo', np.int64, m + 1).output('status', np.int32, m).output('gap', np.float64, m).build(dev)
+    assert ctx.lib.fcpp_inset_counts(ctx.handle, *head(A), A.ptr('pro'), None, A.ptr('pvo'), None, A.ptr('status'), A.ptr('gap')) == L.OK
+    A.check({k: want[k] for k in ('pro', 'pvo', 'status', 'gap')})
+    A = inputs(Arena()).input('pro', want['pro']).input('pvo', want['pvo'])
+    A.output('ovo', np.int64, R + 1).output('ox', np.float64, V).output('oy', np.float64, V).output('src', np.int32, V).build(dev)
+    assert ctx.lib.fcpp_inset_fill(ctx.handle, *head(A), A.ptr('pro'), A.ptr('pvo'), R, V, A.ptr('ovo'), A.ptr('ox'), A.ptr('oy'), A.ptr('src')) == L.OK
+    A.check(dict(ovo=want['ovo'], ox=want['x'], oy=want['y'], src=want['src']))
+
+
+def test_guarded_second_launch(kinds_host):
+    """1025 pairs: the one pair of the second launch writes its counts, its rings and the end of the rings' offsets, and nothing beside"""
+    n, cols = LAUNCH_BATCHES[2]
+    picks = launch_picks(n, 'star65')
+    want = expected(kinds_host, picks, cols)
+    assert len(want['status']) == 1025 and want['pro'][-1] > want['pro'][-2]
+    guarded_counts_and_fill([KINDS[k][1] for k in picks], [DISTS[j] for j in cols], want)
+
+
+def test_guarded_more_rings_than_threads(holed_host):
+    fields, h = holed_host
+    guarded_counts_and_fill(fields, HOLED_DISTS, holed_want(h))
 
 
 # ---- the guarded arena ------------------------------------------------------------------------------------------------------------------

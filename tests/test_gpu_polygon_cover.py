@@ -3,14 +3,16 @@
 and 65 fields chosen for the kernels' edges: a grid of exactly 64 and of 65 columns, partial tiles in both directions, a path of more
 than 256 samples (chunk edges inside a run), a field of more than 256 edges, both caps, with and without work / pass / path_ids / the
 grid / the host copies of the offsets; against fcpp_cover_grid (a device operator against a device operator); through
-plan_polygon_fields; and on guarded buffers (tests/guarded.py)."""
+plan_polygon_fields; and on guarded buffers (tests/guarded.py).  Second rounds: one field under 65 / 256 / 257 / 513 chunks (the ballot words
+and rounds of the chunk loop), tiles that may and may not stop early, fields of 64 / 65 / 259 rings."""
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
-from tests.test_polygon_cover_host import FIVE, RECT40, SQ30, STAR300, _arc, _zigzag, host_cover, layout, line, swaths
+from tests.test_polygon_cover_host import (EARLY, FIVE, MANY_CHUNKS, RECT40, RES_RINGS, SQ30, STAR300, W_RINGS, _arc, _zigzag, early_exit_case,
+                                            field_chunks, host_cover, layout, line, many_chunks_case, many_rings_case, swaths)
 from tests.test_swaths_host import ELL, HOLE, pack, star
 
 pytestmark = pytest.mark.gpu
@@ -177,6 +179,35 @@ def test_batch_of_65_bare_paths_without_host_offsets_or_grid(gpu, batch65):
     same(dev_cover(gpu, fields, lays['bare'], caps=1, host_offsets=True, want_grid=False), h, with_grid=False)
 
 
+# ---- second rounds: the chunk loop's ballot words and rounds, the early exit, the ring loops -----------------------------------------------------
+# (tests/test_polygon_cover_host.py asserts without a device that every case reaches what it is named for)
+@pytest.mark.parametrize('caps', [0, 1])
+@pytest.mark.parametrize('count,permuted', MANY_CHUNKS)
+def test_many_chunks_of_one_field(gpu, count, permuted, caps):
+    """65 / 256 / 257 / 513 chunks: chunk base + w * 64 + bit of ballot words 1 .. 3, and of the second and third round of 256"""
+    fields, lay = many_chunks_case(count, permuted)
+    assert len(field_chunks(lay, 1)) == count
+    same(dev_cover(gpu, fields, lay, caps=caps), host_cover(fields, W, RES, lay, caps=caps))
+
+
+@pytest.mark.parametrize('rows,reverse', EARLY)
+def test_a_tile_stops_only_when_all_its_cells_are_overlapped(gpu, rows, reverse):
+    """the twin skips nothing.  'cover', listed order: every tile is all overlapped after 14 chunks and stops before the second round;
+    reversed, the covering rows come last and stopping early would lose them.  'five': the margin rows stay open, no tile may stop,
+    and what the later rounds' paths add there must show."""
+    fields, lay, _ = early_exit_case(rows, reverse)
+    same(dev_cover(gpu, fields, lay), host_cover(fields, W, RES, lay))
+
+
+def test_many_rings(gpu):
+    """259 rings (the sizes kernel's fifth round of 64, the tile kernel's bisection over 259 rings), 64 and 65 rings, and the copies
+    whose LAST ring alone is spoilt: sizes, status, the inside bit and the counts"""
+    fields, lay = many_rings_case()
+    host = host_cover(fields, W_RINGS, RES_RINGS, lay)
+    assert host['status'].tolist() == [0, -1, 0, -1, 0, -1, -1, -1] and host['counts'][[0, 2, 4], 1].all()
+    same(dev_cover(gpu, fields, lay, res=RES_RINGS, width=W_RINGS), host)
+
+
 # ---- against fcpp_cover_grid --------------------------------------------------------------------------------------------------------------------
 def test_round_caps_equal_cover_grid_on_the_rectangle(gpu):
     path = np.concatenate([LONG, swaths(FIVE)[0][::-1], swaths(FIVE)[4], [[50.0, 30.0]]])
@@ -223,20 +254,37 @@ def test_plan_polygon_fields_reports_what_polygon_coverage_gives(gpu):
 
 
 # ---- guarded buffers ----------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('full', [True, False], ids=['all_arrays', 'optional_arrays_null'])
+def _second_rounds_together():
+    """the 257-path field and the 259-ring field in one batch, at the coarser resolution"""
+    from tests.test_inset_host import HOLED
+    fields, lay = many_chunks_case(257, True)
+    assert len(field_chunks(lay, 1)) == 257 and len(HOLED) == 259
+    poff = lay['path_offsets']
+    paths = [np.column_stack([lay['x'][a:b], lay['y'][a:b]]) for a, b in zip(poff[:-1], poff[1:])]
+    owner = np.empty(len(paths), np.int64)
+    owner[lay['path_ids']] = np.repeat(np.arange(2), np.diff(lay['field_path_offsets']))
+    pas = [lay['pass'][a] for a in poff[:-1]]
+    return fields + [HOLED], layout(3, paths + [line(-3, -3, 173, 163, 60)], owner.tolist() + [2], pas=pas + [9], work=[None] * (len(paths) + 1))
+
+
+@pytest.mark.parametrize('full', [True, False, 'second_rounds'], ids=['all_arrays', 'optional_arrays_null', 'second_rounds'])
 def test_guarded_buffers(gpu, full):
     fields = [RECT40, NARROW65, [(0, 0), (10, 0), (10, np.nan), (0, 10)], [ELL, HOLE]]
     paths = swaths(FIVE) + [LONG, line(101, 2, 112, 2, 30), line(1, 1, 9, 9, 4), _zigzag(3, 40, (-5, -5), (65, 55))]
     owner = [0] * 6 + [1, 2, 3]
     rng = np.random.default_rng(2)
-    if full:
+    W, RES = 4.0, 0.25
+    if full == 'second_rounds':
+        fields, lay = _second_rounds_together()
+        RES = RES_RINGS
+    elif full:
         lay = layout(4, paths, owner, work=[(rng.uniform(size=len(p)) < 0.9).astype(np.uint8) for p in paths], pas=[k % 3 for k in range(len(paths))],
                      order=rng.permutation(len(paths)).tolist())
     else:
         lay = layout(4, paths, owner)
     host = host_cover(fields, W, RES, lay, caps=0)
     ro, vo, x, y = pack(fields)
-    n, total = 4, int(host['cell_offsets'][-1])
+    n, total = len(fields), int(host['cell_offsets'][-1])
     # (no expected element may be all 0x5A bytes: the counts, offsets and dims of these fields are not)
     A = Arena().input('ro', ro).input('vo', vo).input('x', x).input('y', y)
     A.output('dims', np.int64, 4 * n).output('coff', np.int64, n + 1).output('status', np.int32, n).build(gpu.dev)

@@ -1,7 +1,7 @@
 """The clear connectors on the device (run with -m gpu on an MI355X): fcpp_conn_solve_clear equals its host twin bit for bit in every output,
 for both modes, at the sizes where a wavefront or a workgroup ends, against regions of 3 and of FCPP_CLEAR_EDGE_CHUNK - 1 / + 0 / + 1 edges,
 with pair_field grouped and shuffled and -1 / out-of-range entries mixed in; the list between the two passes (nothing listed: the second
-launch is skipped; everything listed; one pair at a wavefront's edge); and engine.clear_connectors against the ABI.
+launch is skipped; everything listed; one pair at a wavefront's edge); a region of 259 rings; and engine.clear_connectors against the ABI.
 The field-path entries of the issue (fcpp_field_path_counts_clear / _fill_clear, reshape=) are not part of this change."""
 import ctypes as C
 
@@ -114,6 +114,22 @@ def test_device_equals_the_host_twin(gpu, mode, n, grouped):
         assert ((want['rank'] == -1) & (want['crossings'] > 0)).any() and (want['word'] == -1).sum() == 2
         listed, _ = passes(gpu[0])
         assert listed >= np.count_nonzero(want['rank'] >= 1)
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+def test_region_of_259_rings(gpu, mode):
+    """the region of tests/test_clearance_host.py whose rings 256 .. 258 decide answers, its copies with the LAST ring spoilt, and the
+    region without those rings: ranks, words and crossings as the twin gives them, and the spoilt regions' status"""
+    from tests.test_clearance_host import MANY_RINGS, MANY_RINGS_CUT, many_ring_pairs, many_ring_region
+    fields = [MANY_RINGS, many_ring_region('short'), MANY_RINGS_CUT, many_ring_region('nan')]
+    frm, to = many_ring_pairs()
+    n = len(frm)
+    frm, to, pair_field = np.tile(frm, (4, 1)), np.tile(to, (4, 1)), np.repeat(np.arange(4), n)
+    want = host_solve_clear(mode, frm, to, R, pair_field, fields)
+    assert want['field_status'].tolist() == [0, L.EINVAL, 0, L.EINVAL]
+    full, cut = want['rank'][:n], want['rank'][2 * n:3 * n]
+    assert (full != cut).sum() >= 2 and (full == 0).sum() >= 20 and (full >= 1).any() and (full == -1).any()
+    same(device_solve_clear(gpu, mode, frm, to, R, pair_field, fields), want)
 
 
 # ---- 2. the list between the passes --------------------------------------------------------------------------------------------------

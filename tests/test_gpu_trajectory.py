@@ -328,6 +328,40 @@ def test_fixed_rate_samples(golden_kernels, dt):
     batch.close()
 
 
+def many_paths_lens(n_paths):
+    """lengths from {0, 1, 2, 3 .. 40} for 257 or 513 paths with empty paths in a row across path 256: the count scan (one workgroup of
+    256, a path per thread per round) carries its running offset into round two over paths that add one sample each.  257: the one path
+    of round two is empty; 513: round three's one path has 40 points, behind three empty ones"""
+    rng = np.random.default_rng(n_paths)
+    lens = np.where(rng.random(n_paths) < 0.25, rng.integers(0, 3, n_paths), rng.integers(3, 41, n_paths))
+    lens[253:259] = 0
+    if n_paths == 513:
+        lens[509:512], lens[512] = 0, 40
+    return lens
+
+
+def check_many_paths_lens(n_paths, lens):
+    assert len(lens) == n_paths > 256 and {0, 1, 2} <= set(lens.tolist()) and lens.max() == 40 and lens.min() == 0
+    assert (lens[253:min(259, n_paths)] == 0).all() and lens[252] > 0 and (lens[:253] >= 3).sum() > 150
+    if n_paths == 513:
+        assert lens[259] > 0 and (lens[259:509] >= 3).sum() > 150 and lens[509:513].tolist() == [0, 0, 0, 40]
+
+
+@pytest.mark.parametrize('n_paths', [257, 513])
+def test_fixed_rate_samples_of_more_paths_than_a_workgroup(n_paths):
+    """fcpp_trajectory_counts' own instantiation of the shared scan (the paths' total times) in its second and third round of 256 paths,
+    and the sampler's bisection of a sample's path over 257 / 513 offsets with runs of equal ones (the inputs' side is asserted without a
+    device in tests/test_trajectory_abi.py)"""
+    from tests.test_gpu_properties import ragged_paths
+    lens = many_paths_lens(n_paths)
+    check_many_paths_lens(n_paths, lens)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    xy, v = ragged_paths(lens, n_paths, 0.4, 6)
+    x, y = np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+    for include_end in (True, False):
+        _check_samples(x, y, v, off, None, 0.1, include_end, f'{n_paths} paths end {include_end}')
+
+
 # ---- 8: argument errors ---------------------------------------------------------------------------------------------------------------
 def test_argument_errors(golden_kernels):
     import torch

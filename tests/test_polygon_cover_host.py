@@ -301,3 +301,173 @@ def test_the_path_table_may_be_permuted():
     for other in (forced, perm):
         assert np.array_equal(other['grid'], grouped['grid']) and np.array_equal(other['counts'], grouped['counts'])
     assert grouped['counts'][:, 1].all()
+
+
+# ---- second rounds: many chunks, the early exit, many rings ----------------------------------------------------------------------------------
+# The device's tile kernel tests a field's chunk boxes 256 at a time, one ballot word per wavefront of 64, and stops a tile once all its cells
+# are overlapped; the sizes kernel reads a field's rings 64 at a time.  None of that is in the twin, so the twin's checkers cannot see it:
+# tests/test_gpu_polygon_cover.py runs the cases below on the device, and the tests here assert -- from the inputs, the 256-segment chunk
+# rule and numpy -- that every case reaches the round it is named for.
+CHUNK, TILE, WORDS = 256, 64, (64, 128, 192, 256)
+W4, RES4 = 4.0, 0.25
+SIDE = [(100, 100), (130, 100), (130, 130), (100, 130)]          # a second field before RECT40, so that its chunks do not start at 0
+
+
+def short_paths(seed, count, lo=(-1.0, -1.0), hi=(41.0, 21.0), step=1.5):
+    """`count` paths of 2 or 3 samples, steps of at most `step` m along each axis, starting anywhere in lo .. hi: one chunk each"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        m = int(rng.integers(2, 4))
+        out.append(rng.uniform(lo, hi) + np.cumsum(rng.uniform(-step, step, (m, 2)), axis=0))
+    return out
+
+
+def field_chunks(lay, f):
+    """the chunks of field f in the order the glue lists them (fcpp_paths.cpp: pcover_chunks, restated): (path, first sample, segments)"""
+    fpo, poff, ids = lay['field_path_offsets'], lay['path_offsets'], lay['path_ids']
+    out = []
+    for s in range(fpo[f], fpo[f + 1]):
+        p = s if ids is None else int(ids[s])
+        out += [(p, k, min(CHUNK, poff[p + 1] - 1 - k)) for k in range(poff[p], poff[p + 1] - 1, CHUNK)]
+    return out
+
+
+def tile_hits(lay, f, dims_row, width, res):
+    """(tiles, chunks) bool: the box of the chunk's samples grown by width / 2 meets the rectangle of the tile's cell centres (every
+    segment of these cases works, so a chunk's box is its samples' box)"""
+    gx, gy = dims_row[:2].copy().view(np.float64)
+    nx, ny = int(dims_row[2]), int(dims_row[3])
+    boxes = np.array([[lay['x'][k:k + c + 1].min(), lay['y'][k:k + c + 1].min(), lay['x'][k:k + c + 1].max(), lay['y'][k:k + c + 1].max()]
+                      for _, k, c in field_chunks(lay, f)]).reshape(-1, 4)
+    tiles = []
+    for ty in range(-(-ny // TILE)):
+        for tx in range(-(-nx // TILE)):
+            i1, j1 = min(tx * TILE + TILE - 1, nx - 1), min(ty * TILE + TILE - 1, ny - 1)
+            tiles.append([gx + (tx * TILE + 0.5) * res, gy + (ty * TILE + 0.5) * res, gx + (i1 + 0.5) * res, gy + (j1 + 0.5) * res])
+    t, r = np.array(tiles)[:, None, :], width / 2
+    b = boxes[None, :, :]
+    return ~((b[..., 0] - t[..., 2] > r) | (t[..., 0] - b[..., 2] > r) | (b[..., 1] - t[..., 3] > r) | (t[..., 1] - b[..., 3] > r))
+
+
+def many_chunks_case(count, permuted):
+    """[SIDE, RECT40]: RECT40 under `count` short paths with five pass ids; SIDE's three paths stand between them in storage.  Steps of
+    at most 0.1 m: with flat ends a path sweeps a strip 4 m long and a cell or two wide, so even 513 of them leave most cells open and
+    every further one changes the grid"""
+    paths = short_paths(count, count, step=0.1) + swaths((104, 112, 120), 100.0, 130.0)
+    owner = [1] * count + [0] * 3
+    pas = [k % 5 for k in range(count)] + [0, 1, 2]
+    order = np.random.default_rng(count + 1).permutation(len(paths)).tolist() if permuted else [0, count, 1, count + 1, count + 2] + list(range(2, count))
+    return [SIDE, RECT40], layout(2, paths, owner, pas=pas, order=order)
+
+
+MANY_CHUNKS = [(c, p) for c in (65, 256, 257, 513) for p in (False, True)]
+
+
+@pytest.mark.parametrize('count,permuted', MANY_CHUNKS)
+def test_many_chunks_cases_reach_the_ballot_words_they_are_named_for(count, permuted):
+    fields, lay = many_chunks_case(count, permuted)
+    chunks = field_chunks(lay, 1)
+    assert len(chunks) == count and len(field_chunks(lay, 0)) == 3 and lay['path_ids'] is not None          # RECT40's chunks start at 3
+    assert all(c in (1, 2) for _, _, c in chunks) and len(set(lay['pass'].tolist())) == 5
+    out = host_cover(fields, W4, RES4, lay)
+    assert (out['nx'][1], out['ny'][1]) == (176, 96)          # 3 x 2 tiles
+    hits = tile_hits(lay, 1, out['dims'][1], W4, RES4)
+    assert hits.shape == (6, count)
+    for word in WORDS:          # chunks whose index within the field is at least 64 / 128 / 192 (later ballot words) / 256 (round two)
+        assert hits[:, word:].any() == (count > word), word
+        if count >= word + 64:
+            assert hits[:, word:].any(axis=1).all()          # ... in every tile, where a whole word of chunks lies there
+    # and every ballot word's chunks change the answer: the twin's grid of the field's first 64 k chunks differs from that of its first
+    # 64 (k + 1) (the rule does not depend on the order, so a device that loads the wrong chunk for a later word cannot give this grid)
+    grids = [host_cover(fields, W4, RES4, dict(lay, field_path_offsets=np.array([0, 3, 3 + min(k, count)], np.int64)))['grid']
+             for k in range(0, count + 64, 64)]
+    assert np.array_equal(grids[-1], out['grid']) and all(not np.array_equal(a, b) for a, b in zip(grids[:-1], grids[1:]))
+    assert out['counts'][1, 1] > 0 and out['counts'][1, 2] > 0 and out['counts'][1, 3] > 0
+
+
+# the early exit: COVER_ROWS each driven twice with different pass ids and reaching past the grid overlap EVERY cell of the grid, margin
+# cells included (a tile stops only when all its valid cells are overlapped, and every tile of this grid has margin cells); FIVE alone
+# overlaps every in-field cell and leaves the margin rows open, so no tile may stop
+COVER_ROWS = (-2,) + FIVE + (22,)
+EARLY = [(rows, rev) for rows in ('five', 'cover') for rev in (False, True)]
+
+
+def early_exit_case(rows, reverse):
+    ys = FIVE if rows == 'five' else COVER_ROWS
+    first = swaths(ys, -5.0, 45.0) + swaths(ys, -5.0, 45.0)
+    pas = list(range(len(ys))) + list(range(100, 100 + len(ys)))
+    more = short_paths(503, 250, (2.0, 2.0), (38.0, 18.0)) + short_paths(504, 127, (-1.5, -1.5), (41.5, -0.5)) \
+        + short_paths(505, 126, (-1.5, 20.5), (41.5, 21.5))          # inside the field, in the lower and in the upper margin rows
+    paths = first + more
+    pas += list(range(200, 200 + len(more)))
+    order = list(range(len(paths)))[::-1] if reverse else None
+    return [RECT40], layout(1, paths, pas=pas, order=order), len(first)
+
+
+@pytest.mark.parametrize('rows,reverse', EARLY)
+def test_early_exit_cases_overlap_what_they_are_named_for(rows, reverse):
+    fields, lay, n_first = early_exit_case(rows, reverse)
+    chunks = field_chunks(lay, 0)
+    assert len(chunks) == n_first + 503 > 2 * CHUNK and n_first == {'five': 10, 'cover': 14}[rows]
+    # the twin on the covering rows alone
+    ys = FIVE if rows == 'five' else COVER_ROWS
+    alone = host_cover(fields, W4, RES4, layout(1, swaths(ys, -5.0, 45.0) * 2, pas=list(range(len(ys))) + list(range(100, 100 + len(ys)))))
+    g = alone['grids'][0]
+    assert ((g[(g & 1) == 1] & 5) == 5).all() and alone['counts'][0].tolist()[:3] == [12800, 12800, 12800]
+    tiles = [g[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE] for ty in range(2) for tx in range(3)]
+    done = [bool(((t & 4) != 0).all()) for t in tiles]
+    assert done == [rows == 'cover'] * 6
+    # the covering rows stand in the first round of 256 chunks (listed order) or behind all 503 others (reversed: rounds two and three)
+    where = [k for k, (p, _, _) in enumerate(chunks) if lay['path_offsets'][p + 1] - lay['path_offsets'][p] == 3 and lay['x'][lay['path_offsets'][p]] == -5.0]
+    assert len(where) == n_first and (min(where) == 503 > CHUNK if reverse else max(where) < CHUNK)
+    # the later paths lie in every tile, inside the field and in the margin rows, and bring new pass ids: nothing they add may show
+    # where the rows already overlap, and all of it must show where they do not
+    hits = tile_hits(lay, 0, alone['dims'][0], W4, RES4)
+    late = [k for k in range(len(chunks)) if k not in where]
+    assert hits[:, late].any(axis=1).all()
+    full = host_cover(fields, W4, RES4, lay)
+    changed = np.count_nonzero(full['grids'][0] != g)
+    assert (changed == 0) == (rows == 'cover') and (rows == 'cover' or changed > 300)
+
+
+# many rings: the field of 259 rings (tests/test_inset_host.py), its two copies with the LAST ring spoilt, and fields of exactly 64 and 65
+# rings with their spoilt copies (the sizes kernel reads 64 rings a round)
+def many_ring_fields():
+    from tests.test_inset_host import HOLED, holed_square, spoilt_last_ring
+    r64, r65 = holed_square(63, cols=8), holed_square(64, cols=8)
+    return [HOLED, spoilt_last_ring(HOLED, 'short'), r64, spoilt_last_ring(r65, 'nan'), r65, spoilt_last_ring(HOLED, 'nan'),
+            spoilt_last_ring(r65, 'short'), spoilt_last_ring(r64, 'nan')]
+
+
+MANY_RING_PATHS = [line(-3, -3, 173, 163, 60), line(-3, -3, 83, 83, 30), line(-3, 83, 83, -3, 30)]
+W_RINGS, RES_RINGS = 4.0, 0.5
+
+
+def many_rings_case():
+    return many_ring_fields(), layout(8, MANY_RING_PATHS, owner=[0, 2, 4])
+
+
+def test_many_ring_fields_inside_bit_equals_point_in_polygon_per_ring():
+    """the oracle's point_in_polygon per ring, asked for the cells of the ring's bounding box grown by a cell (a point outside a ring's
+    bounding box is outside the ring); no cell centre lies on an edge: centres are odd multiples of 0.25, the outline is integer, the
+    holes' vertices end in .1 .. .9 and their edges slant"""
+    fields, lay = many_rings_case()
+    assert [len(f) for f in fields] == [259, 259, 64, 65, 65, 259, 65, 64]
+    out = host_cover(fields, W_RINGS, RES_RINGS, lay)
+    assert out['status'].tolist() == [0, EINVAL, 0, EINVAL, 0, EINVAL, EINVAL, EINVAL]
+    assert (out['nx'][0], out['ny'][0]) == (348, 328) and not out['dims'][[1, 3, 5, 6, 7]].any() and not out['counts'][[1, 3, 5, 6, 7]].any()
+    for i in (0, 2, 4):
+        nx, ny, gx, gy = int(out['nx'][i]), int(out['ny'][i]), out['gx'][i], out['gy'][i]
+        want = np.zeros((ny, nx), np.uint8)
+        for r in fields[i]:
+            a0, b0 = (int(v) for v in np.floor((r.min(axis=0) - (gx, gy)) / RES_RINGS) - 1)
+            a1, b1 = (int(v) for v in np.ceil((r.max(axis=0) - (gx, gy)) / RES_RINGS) + 1)
+            for b in range(max(b0, 0), min(b1, ny)):
+                for a in range(max(a0, 0), min(a1, nx)):
+                    want[b, a] ^= orc.point_in_polygon(gx + (a + 0.5) * RES_RINGS, gy + (b + 0.5) * RES_RINGS, r)
+        assert np.array_equal(out['grids'][i] & 1, want), i
+        holes = sum(np.count_nonzero(want[int((r[:, 1].min() - gy) / RES_RINGS):int((r[:, 1].max() - gy) / RES_RINGS) + 1,
+                                          int((r[:, 0].min() - gx) / RES_RINGS):int((r[:, 0].max() - gx) / RES_RINGS) + 1] == 0) > 0 for r in fields[i][1:])
+        assert holes == len(fields[i]) - 1          # every hole, the last one included, takes cells out
+        assert out['counts'][i][1] > 0 and out['counts'][i][3] > 0

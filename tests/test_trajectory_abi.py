@@ -75,3 +75,11 @@ def test_engine_surface_exists_and_has_no_cpu_fallback():
         E.trajectory(x, np.zeros_like(x), np.full_like(x, 9.0))
     with pytest.raises(RuntimeError):
         E.trajectory_sample(x, np.zeros_like(x), np.full_like(x, 9.0), 0.1)
+
+
+@pytest.mark.parametrize('n_paths', [257, 513])
+def test_the_many_path_batches_cross_the_scan_rounds_they_are_named_for(n_paths):
+    """the inputs of tests/test_gpu_trajectory.py::test_fixed_rate_samples_of_more_paths_than_a_workgroup: more paths than the count scan's
+    256 threads, lengths 0, 1, 2 and up to 40, empty paths in a row across path 256"""
+    from tests import test_gpu_trajectory as G
+    G.check_many_paths_lens(n_paths, G.many_paths_lens(n_paths))
