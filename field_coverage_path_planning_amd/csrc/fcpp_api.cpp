@@ -129,6 +129,7 @@ int fcpp_ctx_create(int device_id, fcpp_ctx **out)
         return fail(FCPP_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     }
     c->stream = c->own;
+    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess) { (void)hipGetLastError(); c->n_cu = 0; }
     if (const char *e = getenv("FCPP_SETUP")) c->setup_mode = !strcmp(e, "host") ? FCPP_SETUP_HOST : (!strcmp(e, "device") ? FCPP_SETUP_DEVICE : FCPP_SETUP_AUTO);
     *out = c;
     return FCPP_OK;
@@ -726,36 +727,52 @@ int fcpp_batch_trajectory(fcpp_batch *b, const double *x, const double *y, const
     return trajectory_paths(b->ctx, 2 * b->n_fields, nullptr, offs.data(), b->hp.total_points, x, y, v, flagseg, s, t, heading, totals);
 }
 
-int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const double *D, int32_t *routes, int32_t *best_route,
-                   double *hist, fcpp_ga_result *result)
-{
-    if (!c || !cfg || !D || !routes || !best_route || !result) return fail(FCPP_EINVAL, "bad arguments");
-    const int pop = cfg->population_size;
-    if (n < 2 || n > GA_MAX_NODES) return fail(FCPP_EUNSUPPORTED, "n_nodes must be in [2, 2048]");
-    if (pop < 2 || (pop & 1) || cfg->elite_size < 0 || cfg->elite_size >= pop || cfg->tournament_size < 1 ||
-        cfg->tournament_size > 64 || cfg->tournament_size > pop || cfg->max_generations < 0)
-        return fail(FCPP_EINVAL, "population_size must be even and > elite_size; 1 <= tournament_size <= min(64, population_size)");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
+namespace {
+// One fcpp_ga_evolve call, step by step: setup, check_permutations, one of the two loops (loop_one_launch / loop_two_streams), read_back.
+struct GaRun {
+    fcpp_ctx *const c; const int n, pop; const fcpp_ga_config &cfg;
+    const double *const D; int32_t *const routes, *const best_route; double *const hist;      // the call's arguments
+    hipStream_t st = nullptr;
     DevBuf<int32_t> scratch;
     DevBuf<double> fd;             // fitness / distance of both buffers
     DevBuf<GaState> state;
-    HIPCHK(scratch.alloc((size_t)pop * n));
-    HIPCHK(fd.alloc((size_t)pop * 4));
-    HIPCHK(state.alloc(1));
-    HIPCHK(hipMemsetAsync(state.p, 0, sizeof(GaState), st));
-    // the run's progress in a word of pinned memory the bookkeeping role writes (GaState::mirror): followed without draining the stream
-    if (!c->ga_mirror && hipHostMalloc((void **)&c->ga_mirror, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { c->ga_mirror = nullptr; (void)hipGetLastError(); }
-    volatile unsigned long long *mir = c->ga_mirror;
-    void *mirror_dp = nullptr;                      // (the word as the device addresses it; lives until the copy below has read it)
-    if (mir) {
-        *mir = 0ull;
-        if (hipHostGetDevicePointer(&mirror_dp, c->ga_mirror, 0) == hipSuccess && mirror_dp) {
-            HIPCHK(hipMemcpyAsync(reinterpret_cast<unsigned char *>(state.p) + offsetof(GaState, mirror), &mirror_dp, sizeof mirror_dp, hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));       // (once per run, in front of its first launch)
-        } else { mir = nullptr; (void)hipGetLastError(); }
+    int32_t *buf[2] = { nullptr, nullptr };
+    double *fit[2] = { nullptr, nullptr }, *dist[2] = { nullptr, nullptr };
+    volatile unsigned long long *mir = nullptr;     // the mirror word, or null: no such word
+    GaState h = {};
+
+    // argument checks, the buffers, and the run's progress in a word of pinned memory the bookkeeping role writes (GaState::mirror):
+    // followed without draining the stream
+    int setup()
+    {
+        if (n < 2 || n > GA_MAX_NODES) return fail(FCPP_EUNSUPPORTED, "n_nodes must be in [2, 2048]");
+        if (pop < 2 || (pop & 1) || cfg.elite_size < 0 || cfg.elite_size >= pop || cfg.tournament_size < 1 ||
+            cfg.tournament_size > 64 || cfg.tournament_size > pop || cfg.max_generations < 0)
+            return fail(FCPP_EINVAL, "population_size must be even and > elite_size; 1 <= tournament_size <= min(64, population_size)");
+        HIPCHK(hipSetDevice(c->device));
+        st = c->stream;
+        HIPCHK(scratch.alloc((size_t)pop * n));
+        HIPCHK(fd.alloc((size_t)pop * 4));
+        HIPCHK(state.alloc(1));
+        HIPCHK(hipMemsetAsync(state.p, 0, sizeof(GaState), st));
+        buf[0] = routes; buf[1] = scratch.p;
+        fit[0] = fd.p; fit[1] = fd.p + 2 * (size_t)pop; dist[0] = fd.p + pop; dist[1] = fd.p + 3 * (size_t)pop;
+        if (!c->ga_mirror && hipHostMalloc((void **)&c->ga_mirror, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { c->ga_mirror = nullptr; (void)hipGetLastError(); }
+        mir = c->ga_mirror;
+        void *mirror_dp = nullptr;                      // (the word as the device addresses it; lives until the copy below has read it)
+        if (mir) {
+            *mir = 0ull;
+            if (hipHostGetDevicePointer(&mirror_dp, c->ga_mirror, 0) == hipSuccess && mirror_dp) {
+                HIPCHK(hipMemcpyAsync(reinterpret_cast<unsigned char *>(state.p) + offsetof(GaState, mirror), &mirror_dp, sizeof mirror_dp, hipMemcpyHostToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));       // (once per run, in front of its first launch)
+            } else { mir = nullptr; (void)hipGetLastError(); }
+        }
+        return FCPP_OK;
     }
-    {   // the initial population must consist of permutations: the kernels index D and their LDS marks by gene
+
+    // the initial population must consist of permutations: the kernels index D and their LDS marks by gene
+    int check_permutations()
+    {
         DevBuf<int32_t> bad;
         int32_t hb = 0;
         HIPCHK(bad.alloc(1));
@@ -764,14 +781,13 @@ int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const doub
         HIPCHK(hipMemcpyAsync(&hb, bad.p, sizeof hb, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (hb) return fail(FCPP_EINVAL, "routes must hold permutations of 0 .. n_nodes-1");
+        return FCPP_OK;
     }
-    int32_t *buf[2] = { routes, scratch.p };
-    double *fit[2] = { fd.p, fd.p + 2 * (size_t)pop }, *dist[2] = { fd.p + pop, fd.p + 3 * (size_t)pop };
-    LAUNCHCHK(launch_ga_fitness(st, n, pop, D, routes, dist[0], fit[0], 0));                       // GA:64
-    GaState h = {};
+
     // the pipelined convergence check (round 5b): has the bookkeeping of generation g - 63 been done (mirror word: generations >= g - 63)?
-    // -> 1: the run has converged, 0: go on, -1: no mirror word / not seen within 2 s (the caller falls back to a copy back + drained stream)
-    auto follow = [&](int g) -> int {
+    // -> 1: the run has converged, 0: go on, -1: no mirror word / not seen within 2 s (progress() falls back to a copy back + drained stream)
+    int follow(int g) const
+    {
         if (!mir) return -1;
         const auto t_wait = std::chrono::steady_clock::now();
         for (int spin = 0;; ++spin) {
@@ -780,29 +796,40 @@ int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const doub
             if ((long long)(w & 0xffffffffull) >= (long long)g - 63) return 0;
             if ((spin & 4095) == 4095 && ms_since(t_wait) > 2000.0) return -1;
         }
-    };
-    if (ga_launch_plan(n, pop).one_launch) {
-        // One launch per generation (k_ga_generation): the population in buffer a -> its statistics and elites (the bookkeeping of
-        // generation g - 1) and its children (generation g) at once; the launch after the last generation only evaluates the final
-        // population.  cfg4: 77 -> 55 us per generation (45 us with the DPP arg-max of the elite selection).
-        for (int g = 0; g <= cfg->max_generations; ++g) {
+    }
+
+    // Both loops' look at the run after every 32nd generation's launches (the kernels are no-ops once converged; stop launching them) -> stop.
+    // Round 5b: the check is PIPELINED.  The bookkeeping role of launch L leaves `generations` = L in the mirror word, so the
+    // host waits -- on that word, not on the stream -- only until launch g - 63 is through: two blocks of 32 launches are in
+    // flight at most, the device never runs dry at a check (it used to: a copy back and a drained stream every 32 generations,
+    // ~20 us of idle device each = 0.5 us of a generation's 10), and a converged run is noticed within 64 launches (no-ops by then).
+    // drain: the stream the bookkeeping runs on, for the fallback.  -> 1: stop, 0: go on, < 0: an error code
+    int progress(int g, hipStream_t drain)
+    {
+        const int f = follow(g);
+        if (f >= 0) return f;
+        HIPCHK(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, drain));
+        HIPCHK(hipStreamSynchronize(drain));
+        return h.converged ? 1 : 0;
+    }
+
+    // One launch per generation (k_ga_generation): the population in buffer a -> its statistics and elites (the bookkeeping of
+    // generation g - 1) and its children (generation g) at once; the launch after the last generation only evaluates the final
+    // population.  cfg4: 77 -> 55 us per generation (45 us with the DPP arg-max of the elite selection).
+    int loop_one_launch()
+    {
+        for (int g = 0; g <= cfg.max_generations; ++g) {
             const int a = g & 1, b = a ^ 1;
-            LAUNCHCHK(launch_ga_generation(st, n, pop, D, buf[a], fit[a], dist[a], buf[b], fit[b], dist[b], *cfg, g, state.p, best_route, hist));
-            if ((g & 31) == 31) {                      // the kernel is a no-op once converged; stop launching it
-                // Round 5b: the check is PIPELINED.  The bookkeeping role of launch L leaves `generations` = L in the mirror word, so the
-                // host waits -- on that word, not on the stream -- only until launch g - 63 is through: two blocks of 32 launches are in
-                // flight at most, the device never runs dry at a check (it used to: a copy back and a drained stream every 32 generations,
-                // ~20 us of idle device each = 0.5 us of a generation's 10), and a converged run is noticed within 64 launches (no-ops by then).
-                const int f = follow(g);
-                if (f == 1) break;
-                if (f == 0) continue;
-                HIPCHK(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                if (h.converged) break;
+            LAUNCHCHK(launch_ga_generation(st, c->n_cu, n, pop, D, buf[a], fit[a], dist[a], buf[b], fit[b], dist[b], cfg, g, state.p, best_route, hist));
+            if ((g & 31) == 31) {
+                const int p = progress(g, st);
+                if (p < 0) return p;
+                if (p) break;
             }
         }
-    } else {
-    LAUNCHCHK(launch_ga_stats_elite(st, n, pop, buf[0], fit[0], dist[0], buf[1], fit[1], dist[1], *cfg, -1, state.p, best_route, hist));
+        return FCPP_OK;
+    }
+
     // Larger tours: two launches per generation on two streams.  Population g + 1 (buffer b) = the children k_ga_pairs(g) makes of population g (buffer a) + the elites of population
     // g, which k_ga_stats_elite(g - 1) copied into b's last rows while it evaluated population g.  So k_ga_stats_elite(g) -- statistics
     // of population g + 1, its elites into a's last rows -- and k_ga_pairs(g + 1) -- children of population g + 1 into a's other rows --
@@ -810,48 +837,69 @@ int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const doub
     // single-workgroup bookkeeping (the longer of the two) on its side stream, a generation costs the longer kernel instead of the sum
     // (measured on cfg4, which normally takes the one-launch path: 77 -> 72 us, the cross-stream waits cost ~13 us a generation).  The pairs of the generation that follows convergence may still run (they read the flag at their start):
     // they write the buffer that is NOT the final population.
-    struct Events {
-        hipEvent_t p[2] = { nullptr, nullptr }, s[2] = { nullptr, nullptr };
-        ~Events() { for (int k = 0; k < 2; ++k) { if (p[k]) (void)hipEventDestroy(p[k]); if (s[k]) (void)hipEventDestroy(s[k]); } }
-    } ev;
-    for (int k = 0; k < 2; ++k) {
-        HIPCHK(hipEventCreateWithFlags(&ev.p[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev.s[k], hipEventDisableTiming));
-    }
-    hipStream_t sd = c->side;
-    HIPCHK(hipEventRecord(ev.s[1], st));              // k_ga_stats_elite(-1) ran on the main stream
-    HIPCHK(hipStreamWaitEvent(sd, ev.s[1], 0));
-    HIPCHK(hipEventRecord(ev.s[0], st));              // (so that every event a stream waits on has been recorded)
-    for (int g = 0; g < cfg->max_generations; ++g) {
-        const int a = g & 1, b = a ^ 1;               // generation g: buffer a -> buffer b
-        HIPCHK(hipStreamWaitEvent(st, ev.s[g & 1], 0));                // the elites of population g are in a: k_ga_stats_elite(g - 2)
-        LAUNCHCHK(launch_ga_pairs(st, n, pop, D, buf[a], fit[a], buf[b], fit[b], dist[b], *cfg, g, state.p));
-        HIPCHK(hipEventRecord(ev.p[g & 1], st));
-        HIPCHK(hipStreamWaitEvent(sd, ev.p[g & 1], 0));                 // the children of population g are in b
-        LAUNCHCHK(launch_ga_stats_elite(sd, n, pop, buf[b], fit[b], dist[b], buf[a], fit[a], dist[a], *cfg, g, state.p, best_route, hist));
-        HIPCHK(hipEventRecord(ev.s[g & 1], sd));
-        if ((g & 31) == 31) {                          // the kernels are no-ops once converged; stop launching them (pipelined check, as above)
-            const int f = follow(g);
-            if (f == 1) break;
-            if (f == 0) continue;
-            HIPCHK(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, sd));
-            HIPCHK(hipStreamSynchronize(sd));
-            if (h.converged) break;
+    int loop_two_streams()
+    {
+        LAUNCHCHK(launch_ga_stats_elite(st, n, pop, buf[0], fit[0], dist[0], buf[1], fit[1], dist[1], cfg, -1, state.p, best_route, hist));
+        struct Events {
+            hipEvent_t p[2] = { nullptr, nullptr }, s[2] = { nullptr, nullptr };
+            ~Events() { for (int k = 0; k < 2; ++k) { if (p[k]) (void)hipEventDestroy(p[k]); if (s[k]) (void)hipEventDestroy(s[k]); } }
+        } ev;
+        for (int k = 0; k < 2; ++k) {
+            HIPCHK(hipEventCreateWithFlags(&ev.p[k], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&ev.s[k], hipEventDisableTiming));
         }
+        hipStream_t sd = c->side;
+        HIPCHK(hipEventRecord(ev.s[1], st));              // k_ga_stats_elite(-1) ran on the main stream
+        HIPCHK(hipStreamWaitEvent(sd, ev.s[1], 0));
+        HIPCHK(hipEventRecord(ev.s[0], st));              // (so that every event a stream waits on has been recorded)
+        for (int g = 0; g < cfg.max_generations; ++g) {
+            const int a = g & 1, b = a ^ 1;               // generation g: buffer a -> buffer b
+            HIPCHK(hipStreamWaitEvent(st, ev.s[g & 1], 0));                // the elites of population g are in a: k_ga_stats_elite(g - 2)
+            LAUNCHCHK(launch_ga_pairs(st, n, pop, D, buf[a], fit[a], buf[b], fit[b], dist[b], cfg, g, state.p));
+            HIPCHK(hipEventRecord(ev.p[g & 1], st));
+            HIPCHK(hipStreamWaitEvent(sd, ev.p[g & 1], 0));                 // the children of population g are in b
+            LAUNCHCHK(launch_ga_stats_elite(sd, n, pop, buf[b], fit[b], dist[b], buf[a], fit[a], dist[a], cfg, g, state.p, best_route, hist));
+            HIPCHK(hipEventRecord(ev.s[g & 1], sd));
+            if ((g & 31) == 31) {
+                const int p = progress(g, sd);
+                if (p < 0) return p;
+                if (p) break;
+            }
+        }
+        HIPCHK(hipStreamSynchronize(sd));
+        return FCPP_OK;
     }
-    HIPCHK(hipStreamSynchronize(sd));
+
+    // the state comes back; the final population goes to `routes` if the last completed generation left it in the scratch buffer
+    int read_back(fcpp_ga_result *result)
+    {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h.generations & 1)                             // the last completed generation wrote the scratch buffer
+            HIPCHK(hipMemcpyAsync(routes, scratch.p, (size_t)pop * n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        result->generations = h.generations;                               // GA:122-127 (generation + 1)
+        result->convergence_gen = h.generations - 1 - h.gwi;
+        result->best_distance = h.best_dist;
+        result->best_fitness = h.best_fit;
+        return FCPP_OK;
     }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h.generations & 1)                             // the last completed generation wrote the scratch buffer
-        HIPCHK(hipMemcpyAsync(routes, scratch.p, (size_t)pop * n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    result->generations = h.generations;                               // GA:122-127 (generation + 1)
-    result->convergence_gen = h.generations - 1 - h.gwi;
-    result->best_distance = h.best_dist;
-    result->best_fitness = h.best_fit;
-    return FCPP_OK;
+};
+}  // namespace
+
+int fcpp_ga_evolve(fcpp_ctx *c, int32_t n, const fcpp_ga_config *cfg, const double *D, int32_t *routes, int32_t *best_route,
+                   double *hist, fcpp_ga_result *result)
+{
+    if (!c || !cfg || !D || !routes || !best_route || !result) return fail(FCPP_EINVAL, "bad arguments");
+    GaRun r{ c, n, cfg->population_size, *cfg, D, routes, best_route, hist };
+    int rc;
+    if ((rc = r.setup()) != FCPP_OK) return rc;
+    if ((rc = r.check_permutations()) != FCPP_OK) return rc;
+    LAUNCHCHK(launch_ga_fitness(r.st, n, r.pop, D, routes, r.dist[0], r.fit[0], 0));                       // GA:64
+    rc = ga_launch_plan(n, r.pop, c->n_cu).one_launch ? r.loop_one_launch() : r.loop_two_streams();
+    if (rc != FCPP_OK) return rc;
+    return r.read_back(result);
 }
 
 int fcpp_cover_grid(fcpp_ctx *c, int64_t n_jobs, const fcpp_cover_job *jobs, int64_t n_pts, const double *px, const double *py,
@@ -1039,8 +1087,7 @@ int fcpp_debug_setup_rule(int what, const int64_t *in, int64_t *out)
 int fcpp_debug_ga_launch_plan(fcpp_ctx *c, int32_t n, int32_t pop, int32_t *out)
 {
     if (!c || !out || n < 2 || n > GA_MAX_NODES || pop < 2 || (pop & 1)) return fail(FCPP_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    const GaLaunchPlan p = ga_launch_plan(n, pop);
+    const GaLaunchPlan p = ga_launch_plan(n, pop, c->n_cu);
     out[0] = p.one_launch ? 1 : 0; out[1] = (int32_t)p.groups; out[2] = p.base; out[3] = p.extra; out[4] = p.per_wg; out[5] = (int32_t)p.lds;
     return FCPP_OK;
 }

@@ -160,6 +160,7 @@ struct fcpp_ctx {
     size_t verify_scratch_cap = 0;
     int64_t *plan_totals_host = nullptr;            // pinned, PC_COLS + PF_COUNT values: the scans of the counting phase write them here
     unsigned long long *ga_mirror = nullptr;        // pinned, one word: (converged << 32) | generations of the running fcpp_ga_evolve (GaState::mirror)
+    int n_cu = 0;                                   // compute units of `device`, read at creation (0: the query failed); ga_launch_plan spreads the GA's pairs over them
     int64_t plan_gen = 0;                           // generation number of the last counting phase (PlanFlag, fcpp_devplan.h)
     // fcpp_batch_plan's direct step (fcpp_devplan.h: DevTileConsts.direct) is attempted while the last speculative setup's batch qualified for it
     // (or there was none): a caller of batches that do not -- mixed classes, unfusable spans -- pays the empty launch once, not per call

@@ -31,11 +31,9 @@ int launch_ga_pairs(hipStream_t st, int n, int pop, const double *D, const int32
 int launch_ga_stats_elite(hipStream_t st, int n, int pop, const int32_t *cur, const double *cur_fit, const double *cur_dist, int32_t *nxt,
                           double *nxt_fit, double *nxt_dist, const fcpp_ga_config &cfg, int gen, GaState *state, int32_t *best_route,
                           double *hist);
-// one generation in one launch: statistics / elites of `cur` (generation index gen - 1) beside its children (generation index gen);
-// for tours and populations whose LDS needs fit (ga_generation_fits)
-bool ga_generation_fits(int n, int pop);
-// what fcpp_ga_evolve launches per generation for (n, pop) on the current device -- the one description the launchers and
-// fcpp_debug_ga_launch_plan read.  one_launch: k_ga_generation (groups pair workgroups beside its two roles; workgroup b takes
+// what fcpp_ga_evolve launches per generation for (n, pop) on a device of n_cu compute units (fcpp_ctx::n_cu; 0 = not known: eight pairs
+// per workgroup) -- a pure function, the one description the launchers and fcpp_debug_ga_launch_plan read.  one_launch (tours and
+// populations whose LDS needs fit): k_ga_generation (groups pair workgroups beside its two roles; workgroup b takes
 // base + (b < extra) pairs, per_wg the most of one; lds = its dynamic LDS bytes), else k_ga_pairs beside k_ga_stats_elite on two
 // streams (groups = pop / 2 workgroups of one pair; lds = k_ga_pairs' dynamic LDS bytes)
 struct GaLaunchPlan {
@@ -44,8 +42,10 @@ struct GaLaunchPlan {
     int base, extra, per_wg;
     size_t lds;
 };
-GaLaunchPlan ga_launch_plan(int n, int pop);
-int launch_ga_generation(hipStream_t st, int n, int pop, const double *D, const int32_t *cur, const double *cur_fit, const double *cur_dist,
+GaLaunchPlan ga_launch_plan(int n, int pop, int n_cu);
+// one generation in one launch (ga_launch_plan(n, pop, n_cu).one_launch): statistics / elites of `cur` (generation index gen - 1) beside
+// its children (generation index gen)
+int launch_ga_generation(hipStream_t st, int n_cu, int n, int pop, const double *D, const int32_t *cur, const double *cur_fit, const double *cur_dist,
                          int32_t *nxt, double *nxt_fit, double *nxt_dist, const fcpp_ga_config &cfg, int gen, GaState *state,
                          int32_t *best_route, double *hist);
 

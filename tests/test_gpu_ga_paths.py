@@ -11,6 +11,7 @@ from types import SimpleNamespace
 
 import numpy as np
 import pytest
+import torch
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
@@ -107,6 +108,10 @@ def test_pair_spreading(kind):
             pytest.fail('population %d is not spread over more than 8 pairs a workgroup on this device: %r' % (pop, vars(p)))
         assert p.per_wg <= 16 and p.lds <= 60 * 1024
         assert kind == 'pop6144' or (p.extra > 0) == (kind == 'extra')
+        # the plan is made for the context's own device: the pairs go to (its compute units - 2) workgroups
+        ctx = E.get_context(None)
+        cu = torch.cuda.get_device_properties(ctx.device).multi_processor_count
+        assert p.groups == min(pairs, cu - 2)
     D, routes = G.problem(pop, n, pop)
     run(D, routes, G.config(max_generations=3, elite_size=7, tournament_size=5), pop)
 
