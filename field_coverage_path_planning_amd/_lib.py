@@ -179,6 +179,9 @@ PROTOTYPES = [
      + [_VP] * 6),
     ('fcpp_route_transit_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP, C.c_int64,
                                           _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
+    ('fcpp_route_transit_priced', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP, C.c_int64,
+                                           _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
+    ('fcpp_ctx_route_priced_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
     ('fcpp_conn_solve_clear', C.c_int, [_VP, C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 8),
     ('fcpp_ctx_solve_clear_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
@@ -217,6 +220,8 @@ PROTOTYPES = [
      + [_VP] * 6),
     ('fcpp_debug_route_transit_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP,
                                                 C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
+    ('fcpp_debug_route_transit_priced', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP,
+                                                 C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
     ('fcpp_debug_conn_words', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_conn_solve_clear', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 8),

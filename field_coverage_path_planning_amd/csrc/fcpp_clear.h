@@ -22,5 +22,12 @@ int launch_clear_conn(hipStream_t st, int mode, int64_t n, const double *fx, con
 int launch_clear_transit(hipStream_t st, int64_t n, const int64_t *soff, const double *ax, const double *ay, const double *bx, const double *by,
                          const double *angle, double R, int mode, const int64_t *toff, const int64_t *tile_off, int64_t n_tiles,
                          const ClearFields &F, double penalty, double *T, uint8_t *B);
+// The first pass of the priced transit block (fcpp_route_transit_priced): the same walk with T out only -- every canonical pair's complete
+// answer to both mirrored entries of T and K (int8, may be NULL) -- and the global indices of the entries whose other words have to be
+// looked at appended to list (room for every canonical pair: t_total / 2), their number added to *count (zeroed by the caller).  The
+// second pass is launch_route_priced_words of fcpp_solveclear.h.
+int launch_route_priced_first(hipStream_t st, int64_t n, const int64_t *soff, const double *ax, const double *ay, const double *bx,
+                              const double *by, const double *angle, double R, int mode, const int64_t *toff, const int64_t *tile_off,
+                              int64_t n_tiles, const ClearFields &F, double penalty, double *T, int8_t *K, int64_t *list, unsigned long long *count);
 
 }  // namespace fcpp

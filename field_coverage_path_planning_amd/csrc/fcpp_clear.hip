@@ -16,6 +16,13 @@
 // the loop.  The lane that owns the canonical pair writes both mirrored entries of B, and of T where the pair is blocked: no entry has
 // two writers, no atomics.  Bound by fp64 vector issue: per (piece, edge) four cross products for a straight, a discriminant for an arc.
 //
+// k_clear_transit<MODE, true> is the FIRST PASS of the priced transit block (fcpp_route_transit_priced; the second one is
+// k_route_priced_words of fcpp_solveclear.hip): the same walk, but T is out only -- the owning lane keeps the pair's total and writes a
+// complete answer to both mirrored entries, the total with K = 0 where the shortest word is clear, fl(total + penalty) with K = -1 where
+// it is not, +inf with K = 0 within one swath -- and it appends the entry's global index to the list iff the field is valid, the start is
+// inside and the word crosses (solve_clear_first's decision; solve_clear_append of fcpp_listfn.h).  One body: the flag only changes what
+// the owning lane does after the edge loop.
+//
 // k_clear_conn: the same edge loop with a lane per path, the edges read from GLOBAL memory through the field's CSR (clear_walk).  Paths
 // grouped by field make all lanes of a wavefront read the same vertex -- one cache line, served by the vector L1 -- and paths that are not
 // grouped are still right: nothing is staged per wavefront, so no result depends on the grouping and no uniformity has to be detected.
@@ -26,6 +33,7 @@
 
 #include "fcpp_clear.h"
 #include "fcpp_clearfn.h"
+#include "fcpp_listfn.h"
 
 namespace fcpp {
 
@@ -50,12 +58,14 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
-template <int MODE>
+// PRICED: B is K (int8: 0 or -1 as a byte; may be NULL), T is out only, list / count take the entries to look at again
+template <int MODE, bool PRICED>
 __global__ __launch_bounds__(CBLOCK) void k_clear_transit(int64_t n, const int64_t *__restrict__ soff, const double *__restrict__ ax,
                                                           const double *__restrict__ ay, const double *__restrict__ bx,
                                                           const double *__restrict__ by, const double *__restrict__ angle, double R,
                                                           const int64_t *__restrict__ toff, const int64_t *__restrict__ tile_off,
-                                                          ClearFields F, double penalty, double *__restrict__ T, uint8_t *__restrict__ B)
+                                                          ClearFields F, double penalty, double *__restrict__ T, uint8_t *__restrict__ B,
+                                                          int64_t *__restrict__ list, unsigned long long *__restrict__ count)
 {
     constexpr int NSEG = Conn<MODE>::NSEG;
     __shared__ ClearEdge sh_e[CLEAR_EDGE_CHUNK];
@@ -78,7 +88,7 @@ __global__ __launch_bounds__(CBLOCK) void k_clear_transit(int64_t n, const int64
 
     ClearPiece pc[NSEG];
     ClearBox box = { 0.0, 0.0, 0.0, 0.0 };
-    double sx = 0.0, sy = 0.0;
+    double sx = 0.0, sy = 0.0, total = INFINITY;
     bool solved = false;
 #pragma unroll
     for (int k = 0; k < NSEG; ++k) {
@@ -87,7 +97,7 @@ __global__ __launch_bounds__(CBLOCK) void k_clear_transit(int64_t n, const int64
         pc[k].wide = false;
     }
     if (pair) {
-        double h0, x1, y1, h1, total, seg[NSEG];
+        double h0, x1, y1, h1, seg[NSEG];
         int word;
         route_pose(ax + s0, ay + s0, bx + s0, by + s0, angle[i], p, true, sx, sy, h0);
         route_pose(ax + s0, ay + s0, bx + s0, by + s0, angle[i], q, false, x1, y1, h1);
@@ -141,17 +151,32 @@ __global__ __launch_bounds__(CBLOCK) void k_clear_transit(int64_t n, const int64
             }
     }
     const bool valid = __syncthreads_or(bad) == 0;
+    const ClearResult res = clear_finish(solved, valid, acc);
+    const bool blocked = pair && !res.clear;
+    if constexpr (PRICED) {
+        // (every lane of the wavefront: a lane that owns no pair lists nothing.  inside != 0 says solved and valid as well)
+        solve_clear_append(blocked && res.inside != 0, toff[i] + e, list, count);
+    }
     if (!canon) return;
     double *Tb = T + toff[i];
-    uint8_t *Bb = B + toff[i];
     const int64_t e2 = (int64_t)(q ^ 1) * N + (p ^ 1);
-    const bool blocked = pair && !clear_finish(solved, valid, acc).clear;
-    Bb[e] = blocked ? 1 : 0;
-    Bb[e2] = blocked ? 1 : 0;
-    if (blocked) {
-        const double v = Tb[e] + penalty;
+    if constexpr (PRICED) {
+        const double v = blocked ? total + penalty : total;          // (within one swath: total is still the +inf it was set to)
         Tb[e] = v;
         Tb[e2] = v;
+        if (B) {
+            B[toff[i] + e] = blocked ? 0xff : 0;
+            B[toff[i] + e2] = blocked ? 0xff : 0;
+        }
+    } else {
+        uint8_t *Bb = B + toff[i];
+        Bb[e] = blocked ? 1 : 0;
+        Bb[e2] = blocked ? 1 : 0;
+        if (blocked) {
+            const double v = Tb[e] + penalty;
+            Tb[e] = v;
+            Tb[e2] = v;
+        }
     }
 }
 
@@ -207,9 +232,28 @@ int launch_clear_transit(hipStream_t st, int64_t n, const int64_t *soff, const d
     if (n <= 0 || n_tiles <= 0) return 0;
     const dim3 grid((unsigned)n_tiles);
     if (mode == 0)
-        hipLaunchKernelGGL(k_clear_transit<0>, grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B);
+        hipLaunchKernelGGL((k_clear_transit<0, false>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
+                           nullptr, nullptr);
     else
-        hipLaunchKernelGGL(k_clear_transit<1>, grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B);
+        hipLaunchKernelGGL((k_clear_transit<1, false>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
+                           nullptr, nullptr);
+    CLEAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_route_priced_first(hipStream_t st, int64_t n, const int64_t *soff, const double *ax, const double *ay, const double *bx,
+                              const double *by, const double *angle, double R, int mode, const int64_t *toff, const int64_t *tile_off,
+                              int64_t n_tiles, const ClearFields &F, double penalty, double *T, int8_t *K, int64_t *list, unsigned long long *count)
+{
+    if (n <= 0 || n_tiles <= 0) return 0;
+    const dim3 grid((unsigned)n_tiles);
+    uint8_t *B = reinterpret_cast<uint8_t *>(K);
+    if (mode == 0)
+        hipLaunchKernelGGL((k_clear_transit<0, true>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B, list,
+                           count);
+    else
+        hipLaunchKernelGGL((k_clear_transit<1, true>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B, list,
+                           count);
     CLEAR_LAUNCH_CHECK();
     return 0;
 }

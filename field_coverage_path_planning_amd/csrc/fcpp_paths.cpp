@@ -1431,6 +1431,109 @@ int fcpp_debug_conn_solve_clear(int mode, int64_t n, const double *from_x, const
     return FCPP_OK;
 }
 
+// ---- the priced transit block (fcpp_clear.hip, fcpp_solveclear.hip; the rule: priced_transit of fcpp_solveclearfn.h) ---------------------
+// what fcpp_route_transit_priced and its host twin check alike before the offsets
+static int route_priced_args(const void *swath_offsets, const void *t_offsets, const void *ring_offsets, const void *vert_offsets, int64_t n,
+                             int64_t n_total, const double *ax, const double *ay, const double *bx, const double *by, const double *angle, double radius,
+                             int mode, int64_t t_total, int64_t n_rings, int64_t n_verts, const double *x, const double *y, double penalty, const double *T)
+{
+    if (!swath_offsets || !t_offsets || !ring_offsets || !vert_offsets || (n_total > 0 && (!ax || !ay || !bx || !by)) || (n > 0 && !angle) ||
+        (t_total > 0 && !T) || (n_verts > 0 && (!x || !y)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    int rc = route_radius(radius, mode);
+    if (rc == FCPP_OK) rc = clear_penalty(penalty);
+    if (rc == FCPP_OK && (n_rings < 0 || n_verts < 0)) rc = fail(FCPP_ESIZE, "bad sizes");
+    return rc;
+}
+
+int fcpp_route_transit_priced(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
+                              const double *ax, const double *ay, const double *bx, const double *by, const double *angle, double radius, int mode,
+                              const int64_t *t_offsets, const int64_t *t_offsets_host, int64_t t_total, const int64_t *ring_offsets,
+                              int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y, double penalty,
+                              double *T, int8_t *K)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    int rc = route_priced_args(swath_offsets, t_offsets, ring_offsets, vert_offsets, n, n_total, ax, ay, bx, by, angle, radius, mode, t_total, n_rings,
+                               n_verts, x, y, penalty, T);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> soff, toff, rings, verts, tile_off;
+    rc = route_offsets(c, n, swath_offsets, swath_offsets_host, n_total, t_offsets, t_offsets_host, t_total, soff, toff);
+    if (rc == FCPP_OK) rc = swath_fields(c, n, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = clear_tiles(n, toff, tile_off);
+    if (rc == FCPP_OK) rc = swath_angles(c, n, angle, nullptr);
+    // (the second pass's grid: at most a workgroup per 4 listed entries, t_total / 2 of them)
+    if (rc == FCPP_OK && t_total / 8 >= CLEAR_MAX_GROUPS) rc = fail(FCPP_ESIZE, "2^34 transit entries or more");
+    if (rc) return rc;
+    c->route_priced_listed = 0;
+    if (n <= 0 || t_total <= 0) return FCPP_OK;
+    DevBuf<int64_t> tiles, list;
+    DevBuf<unsigned long long> count;
+    const int64_t room = t_total / 2;                     // the canonical pairs of different swaths: half of a block less its 2 N own-swath entries
+    HIPCHK(tiles.alloc((size_t)n + 1));
+    HIPCHK(list.alloc((size_t)(room > 0 ? room : 1)));
+    HIPCHK(count.alloc(1));
+    HIPCHK(hipMemcpyAsync(tiles.p, tile_off.data(), tile_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), c->stream));
+    const ClearFields F = { n, ring_offsets, vert_offsets, x, y };
+    LAUNCHCHK(launch_route_priced_first(c->stream, n, swath_offsets, ax, ay, bx, by, angle, radius, mode, t_offsets, tiles.p, tile_off[(size_t)n], F,
+                                        penalty, T, K, list.p, count.p));
+    unsigned long long listed = 0;
+    HIPCHK(hipMemcpyAsync(&listed, count.p, sizeof listed, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (listed > (unsigned long long)room) return fail(FCPP_EHIP, "the first pass listed more entries than there are canonical pairs");
+    c->route_priced_listed = (int64_t)listed;
+    if (listed > 0) {
+        LAUNCHCHK(launch_route_priced_words(c->stream, mode, (int64_t)listed, list.p, n, swath_offsets, ax, ay, bx, by, angle, radius, t_offsets, t_total,
+                                            F, T, K));
+        ++c->route_priced_word_launches;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));              // (the tile offsets and the list die here)
+    return FCPP_OK;
+}
+
+int fcpp_ctx_route_priced_passes(const fcpp_ctx *c, int64_t *listed, int64_t *word_launches)
+{
+    if (!c) return fail(FCPP_EINVAL, "ctx is NULL");
+    if (listed) *listed = c->route_priced_listed;
+    if (word_launches) *word_launches = c->route_priced_word_launches;
+    return FCPP_OK;
+}
+
+int fcpp_debug_route_transit_priced(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                    const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
+                                    const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                    const double *y, double penalty, double *T, int8_t *K)
+{
+    int rc = route_priced_args(swath_offsets, t_offsets, ring_offsets, vert_offsets, n, n_total, ax, ay, bx, by, angle, radius, mode, t_total, n_rings,
+                               n_verts, x, y, penalty, T);
+    if (rc) return rc;
+    std::vector<int64_t> soff, toff, rings, verts;
+    rc = route_offsets(nullptr, n, nullptr, swath_offsets, n_total, nullptr, t_offsets, t_total, soff, toff);
+    if (rc == FCPP_OK) rc = swath_fields(nullptr, n, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = swath_angles(nullptr, n, nullptr, angle);
+    if (rc) return rc;
+    const ClearFields F = { n, ring_offsets, vert_offsets, x, y };
+    WorkerPool::parallel_for(n, [&](int64_t i) {
+        const int64_t s0 = soff[(size_t)i];
+        const int N = (int)(toff[(size_t)i + 1] == toff[(size_t)i] ? 0 : 2 * (soff[(size_t)i + 1] - s0));
+        double *Tb = T + toff[(size_t)i];
+        int8_t *Kb = K ? K + toff[(size_t)i] : nullptr;
+        for (int p = 0; p < N; ++p)
+            for (int q = 0; q < N; ++q) {
+                if (!route_canonical(p, q, N)) continue;
+                const int e = p * N + q, e2 = (q ^ 1) * N + (p ^ 1);
+                PricedTransit r = { INFINITY, 0, false };
+                if ((p >> 1) != (q >> 1))
+                    r = mode == 0 ? priced_transit<0>(F, i, ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, penalty, p, q)
+                                  : priced_transit<1>(F, i, ax + s0, ay + s0, bx + s0, by + s0, angle[i], radius, penalty, p, q);
+                Tb[e] = Tb[e2] = r.t;
+                if (Kb) Kb[e] = Kb[e2] = (int8_t)r.rank;
+            }
+    });
+    return FCPP_OK;
+}
+
 // ---- field paths and headland paths (fcpp_legs.hip; the rules: fcpp_fpathfn.h, fcpp_hpathfn.h): argument checks, then the leg paths' skeleton ----
 int fcpp_field_path_counts(fcpp_ctx *c, int64_t n, const int64_t *swath_offsets, const int64_t *swath_offsets_host, int64_t n_total,
                            const double *ax, const double *ay, const double *bx, const double *by, const double *length, const double *angle,

@@ -28,6 +28,13 @@ int launch_solve_clear_pairs(hipStream_t st, int mode, int64_t n, const SolveCle
 // Second pass, a group of lanes per listed pair (8 for mode 0, 64 for mode 1), a lane per word.
 int launch_solve_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const SolveClearIo &io, double R, const ClearFields &F);
 
+// The second pass of the priced transit block (fcpp_route_transit_priced; the first one is launch_route_priced_first of fcpp_clear.h): a
+// group of lanes per listed entry of T (global indices below t_total, canonical pairs, each once; count at most 2^31 - 1 groups' worth:
+// checked by the caller).  A winner of rank >= 0 writes its total to both mirrored entries of T and its rank to K (int8, may be NULL).
+int launch_route_priced_words(hipStream_t st, int mode, int64_t count, const int64_t *list, int64_t n, const int64_t *soff, const double *ax,
+                              const double *ay, const double *bx, const double *by, const double *angle, double R, const int64_t *toff,
+                              int64_t t_total, const ClearFields &F, double *T, int8_t *K);
+
 // The clear field paths (the rule: fcpp_fpathfn.h): the same two passes over the connector slots of the leg records launch_legs wrote
 // (legs, cnt: 2 n_total + n slots; F: the region CSR, field i of the swaths is field i of it; n_conn = n_total + n connector slots).
 // rank, crossings (per slot, zeroed by the caller), status (the fields' path status) and cnt may be NULL: records only (the fill's pass).

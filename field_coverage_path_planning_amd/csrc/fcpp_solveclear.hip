@@ -24,10 +24,15 @@
 // The CLEAR FIELD PATHS (fcpp_field_path_counts_clear / _fill_clear) run the same two passes over the connector slots of the leg records
 // k_fpath_legs wrote: k_fpath_clear_slots and k_fpath_clear_words below share the append (solve_clear_append) and the whole second-pass
 // body (solve_clear_group) with the two kernels above; only where the poses come from and where the winner writes differ.
+//
+// The PRICED TRANSIT BLOCK (fcpp_route_transit_priced) has its first pass in fcpp_clear.hip -- k_clear_transit's tiled walk, which lists
+// entries of T through the same append (fcpp_listfn.h) -- and its second pass here: k_route_priced_words, solve_clear_group on the poses
+// of a listed entry's pair.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_listfn.h"
 #include "fcpp_samplefn.h"
 #include "fcpp_solveclear.h"
 #include "fcpp_solveclearfn.h"
@@ -52,20 +57,6 @@ __device__ __forceinline__ void solve_clear_store(const SolveClearIo &io, int64_
     if (io.len) io.len[i] = len;
     if (io.rank) io.rank[i] = rank;
     if (io.crossings) io.crossings[i] = crossings;
-}
-
-// The append of both first passes.  Called by every lane of the wavefront; `more` lanes get a place each.
-__device__ __forceinline__ void solve_clear_append(bool more, int64_t item, int64_t *__restrict__ list, unsigned long long *__restrict__ count)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned long long m = __ballot(more);
-    if (m == 0) return;                                   // (uniform over the wavefront)
-    const int leader = __ffsll((long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(m));
-    base = __shfl(base, leader);
-    // (at most one entry per item: base + position stays below the room the caller gave)
-    if (more) list[base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = item;
 }
 
 template <int MODE>
@@ -136,6 +127,46 @@ __global__ __launch_bounds__(SBLOCK) void k_solve_clear_words(int64_t count, con
                             [&](int word, const double *seg, double total, int rank, int crossings) {
                                 solve_clear_store<NSEG>(io, i, word, seg, total, rank, crossings);
                             });
+}
+
+// ---- the priced transit block (fcpp_route_transit_priced) -- behind k_clear_transit<MODE, true> of fcpp_clear.hip -------------------------
+// k_route_priced_words, a group of lanes per listed ENTRY of T: the entry's field by bisection of the block offsets (a field without a
+// block owns no entry: the last field that starts at or before the entry is the one that holds it), (p, q) from its place in the block,
+// the poses by route_pose as the first pass formed them, then solve_clear_group as it is.  A winner of rank >= 0 writes its total and rank
+// to both mirrored entries; with no clear word nothing is written and the first pass's answer stands.  Listed entries are canonical
+// pairs, each listed once: no entry has two writers, no atomics.  The edges come from global memory through the CSR.
+template <int MODE>
+__global__ __launch_bounds__(SBLOCK) void k_route_priced_words(int64_t count, const int64_t *__restrict__ list, int64_t n,
+                                                               const int64_t *__restrict__ soff, const double *__restrict__ ax,
+                                                               const double *__restrict__ ay, const double *__restrict__ bx,
+                                                               const double *__restrict__ by, const double *__restrict__ angle, double R,
+                                                               const int64_t *__restrict__ toff, int64_t t_total, ClearFields F,
+                                                               double *__restrict__ T, int8_t *__restrict__ K)
+{
+    constexpr int G = SolveClearGroup<MODE>::G;
+    const int64_t t = (int64_t)blockIdx.x * SBLOCK + threadIdx.x, j = t / G;
+    bool have = j < count;
+    const int64_t g = have ? list[j] : 0;
+    int64_t f = -1, e2 = 0;
+    double x0 = 0.0, y0 = 0.0, h0 = 0.0, x1 = 0.0, y1 = 0.0, h1 = 0.0;
+    have = have && g >= 0 && g < t_total;                  // (a listed entry lies in T: checked again so that nothing is written beside it)
+    if (have) {
+        f = last_at_or_before(n, g, [&](int64_t i) { return toff[i]; });
+        const int64_t s0 = soff[f], N = 2 * (soff[f + 1] - s0), e = g - toff[f];
+        have = N > 0 && e < N * N && toff[f + 1] - toff[f] == N * N;
+        if (have) {
+            const int p = (int)(e / N), q = (int)(e - (int64_t)p * N);
+            e2 = toff[f] + (int64_t)(q ^ 1) * N + (p ^ 1);
+            route_pose(ax + s0, ay + s0, bx + s0, by + s0, angle[f], p, true, x0, y0, h0);
+            route_pose(ax + s0, ay + s0, bx + s0, by + s0, angle[f], q, false, x1, y1, h1);
+        }
+    }
+    solve_clear_group<MODE>(have, f, x0, y0, h0, x1, y1, h1, R, F, [&](int, const double *, double total, int rank, int) {
+        if (rank < 0) return;
+        T[g] = total;
+        T[e2] = total;
+        if (K) { K[g] = (int8_t)rank; K[e2] = (int8_t)rank; }
+    });
 }
 
 // ---- the clear field paths (the rule: fcpp_fpathfn.h) -- between k_fpath_legs and the scan ------------------------------------------------
@@ -250,6 +281,19 @@ int launch_solve_clear_words(hipStream_t st, int mode, int64_t count, const int6
     const dim3 grid((unsigned)((count + per - 1) / per));
     if (mode == 0) hipLaunchKernelGGL(k_solve_clear_words<0>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
     else hipLaunchKernelGGL(k_solve_clear_words<1>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
+    SOLVECLEAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_route_priced_words(hipStream_t st, int mode, int64_t count, const int64_t *list, int64_t n, const int64_t *soff, const double *ax,
+                              const double *ay, const double *bx, const double *by, const double *angle, double R, const int64_t *toff,
+                              int64_t t_total, const ClearFields &F, double *T, int8_t *K)
+{
+    if (count <= 0 || n <= 0) return 0;
+    const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
+    const dim3 grid((unsigned)((count + per - 1) / per));
+    if (mode == 0) hipLaunchKernelGGL(k_route_priced_words<0>, grid, dim3(SBLOCK), 0, st, count, list, n, soff, ax, ay, bx, by, angle, R, toff, t_total, F, T, K);
+    else hipLaunchKernelGGL(k_route_priced_words<1>, grid, dim3(SBLOCK), 0, st, count, list, n, soff, ax, ay, bx, by, angle, R, toff, t_total, F, T, K);
     SOLVECLEAR_LAUNCH_CHECK();
     return 0;
 }

@@ -195,4 +195,23 @@ FCPP_HD SolveClearResult solve_clear(const ClearFields &F, int64_t f, double x0,
     return r;
 }
 
+// ---- the priced transit block (include/fcpp.h: fcpp_route_transit_priced) ------------------------------------------------------------------
+// the canonical pair (p, q) of field i's block, p and q of different swaths: the rule above on the poses route_transit solves, against
+// field i -> what both mirrored entries of T and K hold.  The clear word's own total; with no clear word (rank -1) the shortest word's
+// total + penalty, one sum.  listed: the first pass hands the pair to the second.
+struct PricedTransit { double t; int32_t rank; bool listed; };
+
+template <int MODE>
+FCPP_HD PricedTransit priced_transit(const ClearFields &F, int64_t i, const double *ax, const double *ay, const double *bx, const double *by,
+                                     double theta, double R, double penalty, int p, int q)
+{
+    double x0, y0, h0, x1, y1, h1;
+    route_pose(ax, ay, bx, by, theta, p, true, x0, y0, h0);
+    route_pose(ax, ay, bx, by, theta, q, false, x1, y1, h1);
+    SolveClearResult r;
+    const bool listed = solve_clear_first<MODE>(F, i, x0, y0, h0, x1, y1, h1, R, r);
+    if (listed) solve_clear_rest<MODE>(F, i, x0, y0, h0, x1, y1, h1, R, r);
+    return { r.rank >= 0 ? r.len : r.len + penalty, r.rank, listed };
+}
+
 }  // namespace fcpp

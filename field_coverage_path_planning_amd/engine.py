@@ -1462,6 +1462,7 @@ class SwathRoute:
     blocked_stored: object = None       # with clear_of: the same for the stored boustrophedon order
     length: object = None       # with clear_of: (n) float64, the summed connector lengths of `order` without any penalty [m]
     clearance: object = None    # with clear_of: the FieldPathClearance behind `blocked` and `length`: every connector of `order`, leg by leg
+    reshaped: object = None     # with price_clear: (n) int32, the connectors of `order` whose clear word is not the shortest one (rank > 0)
 
     def field(self, i):
         return self.order[int(self.offsets_host[i]):int(self.offsets_host[i + 1])]
@@ -1531,6 +1532,26 @@ def _route_transit_clear(ctx, ss, lo, hi, radius, reversing, pf, penalty, T, tof
     return B
 
 
+def _route_transit_priced(ctx, ss, lo, hi, radius, reversing, pf, penalty):
+    """fields lo .. hi of a SwathSet -> (T, K, toff, toff_h, soff, soff_h, n_total): their PRICED transit blocks (fcpp_route_transit_priced:
+    T out only, K int8 with T's layout) and the chunk's own offsets; pf: the chunk's own fields"""
+    torch = _torch()
+    dev = ss.a.device
+    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
+    soff_h = np.ascontiguousarray(ss.offsets_host[lo:hi + 1] - s0, dtype=np.int64)
+    toff_h = _route_offsets(soff_h)
+    soff, toff = torch.as_tensor(soff_h, device=dev), torch.as_tensor(toff_h, device=dev)
+    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+    ang = ss.angle[lo:hi].contiguous()
+    T = torch.empty(int(toff_h[-1]), dtype=torch.float64, device=dev)
+    K = torch.empty(int(toff_h[-1]), dtype=torch.int8, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_route_transit_priced(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by),
+                                              _ptr(ang), float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]),
+                                              *pf._head()[1:], float(penalty), _ptr(T), _ptr(K)))
+    return T, K, toff, toff_h, soff, soff_h, s1 - s0
+
+
 def _clear_fields(clear_of, n, device):
     pf = polygon_fields(clear_of, device)
     if pf.n != n:
@@ -1538,7 +1559,7 @@ def _clear_fields(clear_of, n, device):
     return pf
 
 
-def swath_transit(swathset, radius, reversing=False, device=None, clear_of=None, blocked_penalty=1.0e6):
+def swath_transit(swathset, radius, reversing=False, device=None, clear_of=None, blocked_penalty=1.0e6, price_clear=False):
     """The transit blocks of every field of a SwathSet (fcpp_route_transit) -> (T, offsets): T a flat float64 device tensor, field i's block
     T[offsets[i] : offsets[i + 1]].reshape(2 m_i, 2 m_i) (offsets: numpy int64), entry [p][q] the shortest Dubins -- Reeds-Shepp if
     `reversing` -- length from the end of oriented swath p to the start of oriented swath q (p = 2 s + d: swath s from a to b for d = 0, from
@@ -1548,9 +1569,17 @@ def swath_transit(swathset, radius, reversing=False, device=None, clear_of=None,
     and there T holds length + blocked_penalty.  The default penalty of 1e6 m is a condition, not a measurement: it lies beyond any
     route's transit total (512 swaths at field-diameter transits stay far below it), so one blocked connector outweighs every order
     without one; and it is small enough that a delta of three penalised entries (3e6, ulp 4.7e-10) still resolves the router's min_gain
-    of 1e-9 m in double.  blocked_penalty = 0 reports B and leaves T as it is."""
+    of 1e-9 m in double.  blocked_penalty = 0 reports B and leaves T as it is.
+    price_clear=True (with clear_of; ValueError without): the PRICED blocks (fcpp_route_transit_priced) -> (T, offsets, K): every transit
+    holds the length of the shortest word that is clear of its field -- what clear_connectors and field_paths(clear_of=...) drive for the
+    pair -- and K (int8, T's layout) that word's rank; where no word is clear K is -1 and T the shortest length + blocked_penalty."""
+    if price_clear and clear_of is None:
+        raise ValueError('price_clear=True needs clear_of: the region the connectors have to stay clear of')
     ctx = get_context(device)
     n = len(swathset.offsets_host) - 1
+    if price_clear:
+        T, K, _, toff_h, _, _, _ = _route_transit_priced(ctx, swathset, 0, n, radius, reversing, _clear_fields(clear_of, n, device), blocked_penalty)
+        return T, toff_h, K
     T, toff, toff_h, soff, soff_h, _ = _route_transit(ctx, swathset, 0, n, radius, reversing)
     if clear_of is None:
         return T, toff_h
@@ -1575,21 +1604,25 @@ def _route_end_pairs(ss, pose, at_entry):
     return (far, own) if at_entry else (own, far)
 
 
-def _route_ends(ss, pose, at_entry, radius, reversing, device, clear_of=None, penalty=0.0):
+def _route_ends(ss, pose, at_entry, radius, reversing, device, clear_of=None, penalty=0.0, price_clear=False):
     """E (at_entry) or X of route_swaths: the connector length between each field's pose and every oriented swath's start / from its end;
-    clear_of (PolygonFields): + penalty where that connector is not clear of its field"""
+    clear_of (PolygonFields): + penalty where that connector is not clear of its field; price_clear: the shortest clear word's length
+    (clear_connectors), + penalty where no word is clear"""
     torch = _torch()
     frm, to = _route_end_pairs(ss, pose, at_entry)
     if clear_of is None:
         return _conn_solve_poses(frm, to, radius, reversing, device)[2].contiguous()
     counts = torch.as_tensor(np.diff(ss.offsets_host), device=ss.a.device)
     pair_field = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64, device=ss.a.device), 2 * counts)
+    if price_clear:
+        c = clear_connectors(frm, to, clear_of, pair_field, radius, reversing, device)
+        return torch.where(c.rank < 0, c.length + float(penalty), c.length).contiguous()
     c = _connector_clearance(frm, to, clear_of, pair_field, radius, reversing, device)
     return torch.where(c.clear, c.length, c.length + float(penalty)).contiguous()
 
 
 def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, starts=8, min_gain=1e-9, max_sweeps=None, spacing=None, device=None,
-                 clear_of=None, blocked_penalty=1.0e6):
+                 clear_of=None, blocked_penalty=1.0e6, price_clear=False):
     """Order and direction of every field's swaths (fcpp_route_transit + fcpp_route_solve; the rule: include/fcpp.h) -> SwathRoute.
     The cost of a tour is the summed length of its connectors -- shortest Dubins paths at the turning radius `radius`, Reeds-Shepp if
     `reversing` -- plus, with entry / exit (one pose (x, y, heading) per field, or None), the connector from the field's entry pose to
@@ -1606,7 +1639,14 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     included; SwathRoute.length is the order's summed connector length without them, SwathRoute.blocked / blocked_stored count the
     connectors of the order / of the stored boustrophedon that are still not clear (field_path_clearance says which).  They are counted
     on the connectors AS DRIVEN: a block entry holds its canonical pair's connector, and where two words tie in length the connector
-    driven for the mirrored entry may be the other one."""
+    driven for the mirrored entry may be the other one.
+    price_clear=True (with clear_of; ValueError without): every transit, entry and exit connector is priced at the length of the SHORTEST
+    CLEAR word of its pair (fcpp_route_transit_priced, clear_connectors) -- the word field_paths(clear_of=...) drives for it -- and at the
+    shortest length + blocked_penalty only where no word is clear: the router optimises the path that is driven with reshaping.
+    SwathRoute.length and .blocked are then those of the clear words as driven (clear_connectors on the legs' poses: blocked counts rank
+    -1), SwathRoute.reshaped counts the legs of rank > 0; .clearance and .blocked_stored keep their meaning, the shortest words tested."""
+    if price_clear and clear_of is None:
+        raise ValueError('price_clear=True needs clear_of: the region the connectors have to stay clear of')
     ctx = get_context(device)
     torch = _torch()
     ss = swathset
@@ -1622,16 +1662,20 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     if clear_of is not None:
         pf = _clear_fields(clear_of, n, device)
         ro_h, vo_h = pf.ring_offsets.cpu().numpy(), pf.vert_offsets.cpu().numpy()
-    E_all = _route_ends(ss, entry, True, R, reversing, device, pf, blocked_penalty) if entry is not None else None
-    X_all = _route_ends(ss, exit, False, R, reversing, device, pf, blocked_penalty) if exit is not None else None
+    E_all = _route_ends(ss, entry, True, R, reversing, device, pf, blocked_penalty, price_clear) if entry is not None else None
+    X_all = _route_ends(ss, exit, False, R, reversing, device, pf, blocked_penalty, price_clear) if exit is not None else None
     order = torch.empty(int(soff_all[-1]), dtype=torch.int32, device=dev)
     tours = torch.empty((max(S, 0), int(soff_all[-1])), dtype=torch.int32, device=dev)
     costs = torch.empty((n, max(S, 0)), dtype=torch.float64, device=dev)
     cost, stored = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
     winner, sweeps, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     for lo, hi in _route_chunks(soff_all, ROUTE_T_BUDGET):
-        T, toff, toff_h, soff, soff_h, m = _route_transit(ctx, ss, lo, hi, R, reversing)
-        if pf is not None:
+        if price_clear:
+            T, _, toff, toff_h, soff, soff_h, m = _route_transit_priced(ctx, ss, lo, hi, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi),
+                                                                        blocked_penalty)
+        else:
+            T, toff, toff_h, soff, soff_h, m = _route_transit(ctx, ss, lo, hi, R, reversing)
+        if pf is not None and not price_clear:
             _route_transit_clear(ctx, ss, lo, hi, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi), blocked_penalty, T, toff, toff_h, soff, soff_h)
         s0 = int(soff_all[lo])
         Ec = E_all[2 * s0:2 * (s0 + m)] if E_all is not None else None
@@ -1646,6 +1690,13 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
         driven = _legs_clearance(ss, pf, R, reversing, order, entry, exit, device)
         route.blocked, route.length, route.clearance = driven.blocked, driven.length, driven
         route.blocked_stored = _legs_clearance(ss, pf, R, reversing, None, entry, exit, device).blocked
+    if price_clear:
+        frm, to, lf, _ = _leg_pairs(ss, order, entry, exit)
+        c = clear_connectors(frm, to, pf, lf, R, reversing, device)
+        per_field = torch.bincount(lf, minlength=n)
+        route.blocked, route.reshaped = (torch.zeros(n, dtype=torch.int32, device=dev).index_add_(0, lf, w.to(torch.int32))
+                                         for w in (c.rank < 0, c.rank > 0))
+        route.length = torch.segment_reduce(c.length, 'sum', lengths=per_field, initial=0.0)
     return route
 
 
@@ -1765,8 +1816,9 @@ class FieldPathClearance:
     field_status: object        # (n) int32: fcpp_conn_clear's status of the field tested against
 
 
-def _legs_clearance(ss, pf, R, reversing, order, entry, exit, device):
-    """the connector legs of the fields' driving orders, built on the device as field_paths forms them, solved at R and tested"""
+def _leg_pairs(ss, order, entry, exit):
+    """the connector legs of the fields' driving orders, built on the device as field_paths forms them -> (from, to, field, slot), ordered by
+    field, then by slot"""
     torch = _torch()
     dev = ss.a.device
     soff_h = np.ascontiguousarray(ss.offsets_host, dtype=np.int64)
@@ -1802,7 +1854,15 @@ def _legs_clearance(ss, pf, R, reversing, order, entry, exit, device):
         frm.append(ext[last]); to.append(p[has]); lf.append(has); slot.append(2 * counts[has])
     frm, to, lf, slot = torch.cat(frm), torch.cat(to), torch.cat(lf), torch.cat(slot)
     by_slot = torch.argsort(2 * ss.offsets[lf] + lf + slot)                                       # a field's first slot is 2 soff + i
-    frm, to, lf, slot = frm[by_slot].contiguous(), to[by_slot].contiguous(), lf[by_slot], slot[by_slot]
+    return frm[by_slot].contiguous(), to[by_slot].contiguous(), lf[by_slot], slot[by_slot]
+
+
+def _legs_clearance(ss, pf, R, reversing, order, entry, exit, device):
+    """the connector legs of the fields' driving orders (_leg_pairs), solved at R and tested"""
+    torch = _torch()
+    dev = ss.a.device
+    n = len(ss.offsets_host) - 1
+    frm, to, lf, slot = _leg_pairs(ss, order, entry, exit)
     c = _connector_clearance(frm, to, pf, lf, R, reversing, device)
     blocked = torch.zeros(n, dtype=torch.int32, device=dev)
     blocked.index_add_(0, lf, (~c.clear).to(torch.int32))
@@ -2153,7 +2213,8 @@ class PolygonPlan:
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
-                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False):
+                        arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
+                        price_clear=False):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2166,10 +2227,14 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     (route_swaths(clear_of=...): PolygonPlan.clearance is its SwathRoute.clearance, what field_path_clearance gives for the path); a PolygonFields, or anything polygon_fields takes, is used
     as given.  reshape=True (with clear_of; ValueError without): the field paths drive, per connector, the shortest word that stays off the
     same region the router was given (field_paths(clear_of=...)): PolygonPlan.paths.blocked / .reshaped report the path as driven, while
-    PolygonPlan.clearance stays what it is, the shortest-word legs as routed.  The router's matrix is not priced with the clear word's
-    length, and the headland loops' corner connectors are neither tested nor re-shaped."""
+    PolygonPlan.clearance stays what it is, the shortest-word legs as routed.  price_clear=True (with reshape=True; ValueError without:
+    the route would be priced with words nobody drives): the router's matrix holds the clear words' lengths
+    (route_swaths(price_clear=True)), so route.length is paths.transit_length and route.blocked is paths.blocked.  The headland loops'
+    corner connectors are neither tested nor re-shaped."""
     if reshape and clear_of is None:
         raise ValueError('reshape=True needs clear_of: the region the connectors have to stay clear of')
+    if price_clear and not reshape:
+        raise ValueError('price_clear=True needs reshape=True: the route would be priced with words the field paths do not drive')
     torch = _torch()
     fields = polygon_fields(fields, device)
     lines, work = headland(fields, width, passes, arc_step=arc_step, device=device)
@@ -2179,7 +2244,8 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     chosen = ang[idx.clamp(min=0)] if ang.numel() else torch.zeros(work.n, dtype=torch.float64, device=work.x.device)
     ss = polygon_swaths(work, chosen, width, device=device)
     region = None if clear_of is None else (fields if isinstance(clear_of, str) and clear_of == 'boundary' else polygon_fields(clear_of, device))
-    route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device, clear_of=region)
+    route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device, clear_of=region,
+                         **({'price_clear': True} if price_clear else {}))
     paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device,
                         clear_of=region if reshape else None)
     clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))

@@ -724,6 +724,32 @@ int fcpp_route_transit_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offs
                              double radius, int mode, const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total,
                              const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
                              const double *x_dev, const double *y_dev, double penalty, double *T_dev, uint8_t *B_dev);
+/* The PRICED transit block: every transit priced by the word that fcpp_conn_solve_clear would drive for it, not by a penalty on the shortest
+ * one.  Build-defined.  The arguments of fcpp_route_transit_clear, but T_dev is OUT ONLY -- every entry of every block is written, no
+ * fcpp_route_transit call is needed first -- and K_dev (int8, T's layout and offsets; may be NULL) takes the place of B_dev.  Offsets, the
+ * canonical-pair rule, equal bits in mirrored entries and +inf within one swath are as for fcpp_route_transit.
+ *   - For a canonical pair (p, q) of different swaths the poses are p's exit and q's entry, the field is field i of the CSR, and the rule of
+ *     the clear connectors below (fcpp_conn_solve_clear: candidates, order (total, word), test, rank) is applied to that pair.
+ *   - rank >= 0: T[p][q] = T[q-bar][p-bar] = that candidate's len -- the word's own total, no penalty -- and K = rank (below 48).
+ *   - rank -1 (no word is clear: a start that is not inside the field, a field whose status is FCPP_EINVAL, an unsolved pair):
+ *     T = fl(len of the shortest word + penalty), one sum written to both mirrored entries, and K = -1.
+ *   - Entries within one swath: T = +inf, K = 0.
+ * So where K == 0, T has the bits fcpp_route_transit writes; where K == -1, the bits fcpp_route_transit_clear writes with the same penalty;
+ * K != 0 exactly where fcpp_route_transit_clear's B == 1; and elementwise plain <= priced <= penalised.  penalty 0 is allowed.  A field
+ * beyond FCPP_ROUTE_MAX_SWATHS has no block and nothing of it is written.
+ * Two launches, for the reason fcpp_conn_solve_clear gives: the first is fcpp_route_transit_clear's tiled walk, in which the lane that
+ * owns a canonical pair writes the complete answer for the shortest word and lists the entry iff its field is valid, its start is inside
+ * and the shortest word crosses; the call reads the list's length back and, unless it is 0, a second kernel looks at a listed entry's
+ * words with a lane per word and overwrites T and K where one of them is clear.  Errors of the call as for fcpp_route_transit_clear
+ * (FCPP_ESIZE also for 2^34 entries or more).  Synchronises. */
+int fcpp_route_transit_priced(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                              const double *ax_dev, const double *ay_dev, const double *bx_dev, const double *by_dev, const double *angle_dev,
+                              double radius, int mode, const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total,
+                              const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                              const double *x_dev, const double *y_dev, double penalty, double *T_dev, int8_t *K_dev);
+/* listed: the entries the first pass of this context's LAST fcpp_route_transit_priced handed to the second; word_launches: the second-pass
+ * launches of all its calls so far (a call that lists nothing launches none).  Either may be NULL.  For tests. */
+int fcpp_ctx_route_priced_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *word_launches);
 
 /* ---- clear connectors: per pair of poses the shortest word that stays off the field's rings -------------------------------------------------
  * Build-defined.  The entries above test a SOLVED connector; this one chooses: both solvers evaluate every word of a pair (6 Dubins, 48
@@ -809,7 +835,7 @@ int fcpp_field_path_fill(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_
 /* ---- clear field paths: the field paths, every connector driven by the shortest word that stays off a region ---------------------------------
  * Build-defined.  fcpp_field_path_counts / _fill drive the shortest word of every connector whatever it crosses; these two drive, per
  * connector, the word fcpp_conn_solve_clear chooses.  One word per connector: no via points, no detours along the headland, no margin (pass
- * the inset); the router's matrix is not priced with the chosen word's length.  Standalone: nothing here feeds fcpp_batch_plan.
+ * the inset); fcpp_route_transit_priced gives the router the matrix of the chosen words' lengths.  Standalone: nothing here feeds fcpp_batch_plan.
  * THE RULE (csrc/fcpp_fpathfn.h over csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).  The clear
  * field path of a batch is the field path above with ONE difference: in a field whose path status is FCPP_OK the record of every connector
  * slot -- word, seg, total -- is what fcpp_conn_solve_clear gives for the slot's from-pose and to-pose (the very poses the connector above is
@@ -1134,6 +1160,13 @@ int fcpp_debug_route_transit_clear(int64_t n, const int64_t *swath_offsets, int6
                                    const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
                                    const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
                                    const double *y, double penalty, double *T, uint8_t *B);
+/* The priced transit block evaluated on the HOST, on host pointers: what fcpp_route_transit_priced is compared with bit for bit -- per
+ * canonical pair the sequential form of the clear-connector rule (fcpp_debug_conn_solve_clear's) on the poses fcpp_debug_route_transit
+ * solves.  Arguments, outputs and the call's errors as for it (the offsets are the host's); K may be NULL.  A diagnostic, not a fallback. */
+int fcpp_debug_route_transit_priced(int64_t n, const int64_t *swath_offsets, int64_t n_total, const double *ax, const double *ay, const double *bx,
+                                    const double *by, const double *angle, double radius, int mode, const int64_t *t_offsets, int64_t t_total,
+                                    const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                                    const double *y, double penalty, double *T, int8_t *K);
 /* The clear-connector rule (csrc/fcpp_solveclearfn.h) evaluated on the HOST, on host pointers.  fcpp_debug_conn_words: ALL candidates of
  * every pair -- ok (uint8), total (float64): n x W, seg: n x W x S float64, W = 6, S = 3 (mode 0) or W = 48, S = 5 (mode 1); a word that is
  * no candidate has ok 0 and NaN.  Any output may be NULL.  Test infrastructure only.  fcpp_debug_conn_solve_clear: what

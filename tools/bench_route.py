@@ -6,6 +6,10 @@
       fields with a stored cost above 0, the share of fields improved and the most moves a candidate applied;
   (d) the host twin (fcpp_debug_route_transit + fcpp_debug_route) on the library's host threads (FCPP_THREADS, at most 16) on the same
       batch, once, with the device results compared bit for bit.
+  (e) --clear-of boundary --price-clear: the transit blocks against the fields' own boundaries, the penalty form (fcpp_route_transit +
+      fcpp_route_transit_clear) and the priced form (fcpp_route_transit_priced) timed ALTERNATING within each repetition; the entries the
+      priced form's first pass listed over the canonical pairs; and the mean connector length per field as driven with reshaping
+      (clear_connectors on the legs) of the route on the penalty matrix and of the route on the priced one.
 The timed calls include the entries' own argument checks and their synchronisation.  Prints ONE JSON line (and writes it to --out).
 Needs a GPU; bench.py's metric is not touched by this."""
 import argparse
@@ -21,7 +25,7 @@ sys.path.insert(0, REPO)
 
 from field_coverage_path_planning_amd import _lib as L          # noqa: E402
 from field_coverage_path_planning_amd import engine as E        # noqa: E402
-from tools.bench_swaths import _timed, stars                     # noqa: E402
+from tools.bench_swaths import _stat, _timed, stars              # noqa: E402
 
 
 def main():
@@ -36,8 +40,13 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--no-host', action='store_true')
+    ap.add_argument('--clear-of', choices=['boundary'], default=None)
+    ap.add_argument('--price-clear', action='store_true')
+    ap.add_argument('--penalty', type=float, default=1.0e6)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.price_clear and args.clear_of is None:
+        raise SystemExit('--price-clear needs --clear-of boundary')
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('bench_route needs a GPU: there is no CPU path to time')
@@ -81,6 +90,54 @@ def main():
                                  'most_moves': int(route.sweeps.max().item()), 'mean_cost_over_stored': float((c[ok] / s0[ok]).mean()),
                                  'improved_share': float((c[ok] < s0[ok] - 1e-9).mean()), 'status_nonzero': int((st != 0).sum())}
     rec['transit_plus_solve_ms'] = ts['median_ms']
+
+    if args.clear_of is not None:
+        import ctypes as C
+        ro_h, vo_h = pf.ring_offsets.cpu().numpy(), pf.vert_offsets.cpu().numpy()
+        parts = [E._fields_slice(pf, ro_h, vo_h, lo, hi) for lo, hi in chunks]
+        listed = [0]
+
+        def penalised():
+            for (lo, hi), part in zip(chunks, parts):
+                c = E._route_transit(ctx, ss, lo, hi, R, bool(mode))
+                E._route_transit_clear(ctx, ss, lo, hi, R, bool(mode), part, args.penalty, c[0], c[1], c[2], c[3], c[4])
+
+        def priced():
+            listed[0] = 0
+            for (lo, hi), part in zip(chunks, parts):
+                E._route_transit_priced(ctx, ss, lo, hi, R, bool(mode), part, args.penalty)
+                got = C.c_int64(0)
+                L.check(lib.fcpp_ctx_route_priced_passes(ctx.handle, C.byref(got), None))
+                listed[0] += got.value
+
+        def stamp(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+        forms = (('penalty', penalised), ('priced', priced)) if args.price_clear else (('penalty', penalised),)
+        ms = {k: [] for k, _ in forms}
+        for k in range(args.warmup + args.reps):          # alternating: both forms see the same clocks and the same neighbours
+            for name, fn in forms:
+                t = stamp(fn)
+                if k >= args.warmup:
+                    ms[name].append(t)
+        fit = m[m <= L.ROUTE_MAX_SWATHS]
+        pairs = int((2 * fit * (fit - 1)).sum())          # canonical pairs of different swaths: (N^2 - 2 N) / 2, N = 2 m
+        rec['clear_transit'] = {'penalty': args.penalty, 'canonical_pairs': pairs, 'penalty_form': _stat(ms['penalty'])}
+        if args.price_clear:
+            rec['clear_transit'].update(priced_form=_stat(ms['priced']), listed=listed[0], listed_share=listed[0] / max(pairs, 1))
+            driven = {}
+            for name, kw in (('penalty', {}), ('priced', {'price_clear': True})):
+                r = E.route_swaths(ss, R, reversing=bool(mode), starts=S, min_gain=1e-9, max_sweeps=max_sweeps, clear_of=pf,
+                                   blocked_penalty=args.penalty, **kw)
+                frm, to, lf, _ = E._leg_pairs(ss, r.order, None, None)
+                c = E.clear_connectors(frm, to, pf, lf, R, bool(mode))
+                driven[name] = {'mean_driven_length_m': float(c.length.sum().item()) / n, 'blocked_legs': int((c.rank < 0).sum().item()),
+                                'reshaped_legs': int((c.rank > 0).sum().item())}
+            rec['clear_transit']['routes_driven_with_reshaping'] = driven
 
     if not args.no_host:
         hp = lambda a: a.ctypes.data
