@@ -18,6 +18,9 @@ KIND_MASK, FLAG_HEADLAND, FLAG_ALAT, FLAG_OUTSIDE, FLAG_OBSTACLE, INDEX_SHIFT = 
 OUTPUT_PITCH = 24 << 30          # FCPP_OUTPUT_PITCH (include/fcpp.h)
 ROUTE_MAX_SWATHS = 512           # FCPP_ROUTE_MAX_SWATHS
 CLEAR_EDGE_CHUNK = 256           # FCPP_CLEAR_EDGE_CHUNK
+TRANSIT_MAX_STATIONS = 2048      # FCPP_TRANSIT_MAX_STATIONS
+PART_LOOP_RIDE = 5               # FCPP_PART_LOOP_RIDE
+TRANSIT_BLOCK = 256              # threads of a workgroup of the loop-transit kernels, the pick pass's tile of stations
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -193,6 +196,12 @@ PROTOTYPES = [
     ('fcpp_field_path_fill_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6
      + [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP] + [_VP, C.c_int64] + [_VP] * 7),
     ('fcpp_ctx_field_path_clear_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
+    ('fcpp_loop_transit_solve', C.c_int, [_VP, C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]
+     + [C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 6 + [_VP, _VP, C.c_int64] + [_VP] * 15),
+    ('fcpp_loop_transit_counts', C.c_int, [_VP, C.c_int, C.c_int64] + [_VP] * 8 + [C.c_int64, _VP, _VP, C.c_int64, C.c_double, _VP, _VP]),
+    ('fcpp_loop_transit_fill', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double] + [_VP] * 8 + [C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5
+     + [C.c_double, _VP, _VP, C.c_int64] + [_VP] * 6),
+    ('fcpp_ctx_loop_transit_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
     ('fcpp_headland_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
      + [_VP] * 7),
     ('fcpp_headland_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
@@ -225,6 +234,8 @@ PROTOTYPES = [
     ('fcpp_debug_conn_words', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, _VP, _VP]),
     ('fcpp_debug_conn_solve_clear', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 8),
+    ('fcpp_debug_loop_transits', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]
+     + [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [_VP, C.c_int64, C.c_double] + [_VP] * 15 + [_VP, C.c_int64] + [_VP] * 6),
     ('fcpp_debug_field_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 14 + [C.c_int64]
      + [_VP] * 7),
     ('fcpp_debug_field_paths_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6

@@ -172,6 +172,8 @@ struct fcpp_ctx {
     int64_t fpath_clear_listed = 0, fpath_clear_word_launches = 0;
     // fcpp_route_transit_priced: the same two figures of the priced transit block (fcpp_ctx_route_priced_passes: tests)
     int64_t route_priced_listed = 0, route_priced_word_launches = 0;
+    // fcpp_loop_transit_solve: the same two figures of the loop transits' stations pass (fcpp_ctx_loop_transit_passes: tests)
+    int64_t transit_listed = 0, transit_word_launches = 0;
     // the stream the last device-side setup was enqueued on (its fill pass may still read the scratch): a setup on ANOTHER stream records
     // ev_plan there and waits for it -- lazily, when that other stream shows up: an event recorded between two kernels of the plan call
     // costs 5 us of device time between them (round 5: the three records of a plan call were 16 of its 158 us)

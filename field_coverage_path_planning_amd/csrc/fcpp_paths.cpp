@@ -26,6 +26,8 @@
 #include "fcpp_swath.h"
 #include "fcpp_swathfn.h"
 #include "fcpp_traj.h"
+#include "fcpp_transit.h"
+#include "fcpp_transitfn.h"
 
 using namespace fcpp;
 
@@ -1767,6 +1769,298 @@ int fcpp_debug_headland_paths(int64_t n_rings, const int64_t *ring_offsets, int6
                                },
                                path_offsets, leg_offsets, { { work_length, transit_length, skipped_length } }, status, leg_kind, leg_word, leg_seg, leg_total,
                                cap, out_x, out_y, heading, kappa, part, gear, leg);
+}
+
+}  // extern "C"
+
+// ---- loop transits (fcpp_transit.hip; the rule: fcpp_transitfn.h) -------------------------------------------------------------------------
+namespace {
+// what the loop-transit entries and the host twin check alike of their loop set, before the offsets
+int transit_loop_args(int64_t n_loops, const void *loop_offsets, int64_t n_samples, bool arrays)
+{
+    if (!loop_offsets || (n_samples > 0 && !arrays)) return fail(FCPP_EINVAL, "bad arguments");
+    if (n_loops < 0 || n_samples < 0 || n_loops > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    return FCPP_OK;
+}
+
+int transit_solve_args(int mode, int64_t n, const double *fx, const double *fy, const double *fh, const double *tx, const double *ty, const double *th,
+                       double radius, const int64_t *pair_field, int64_t n_fields, const void *ring_offsets, int64_t n_rings, const void *vert_offsets,
+                       int64_t n_verts, const double *x, const double *y, int64_t n_loops, const void *loop_offsets, int64_t n_samples, bool arrays,
+                       const void *field_loops, int64_t stride)
+{
+    int rc = solve_clear_args(mode, n, fx, fy, fh, tx, ty, th, radius, pair_field, n_fields, ring_offsets, n_rings, vert_offsets, n_verts, x, y);
+    if (rc == FCPP_OK) rc = transit_loop_args(n_loops, loop_offsets, n_samples, arrays);
+    if (rc) return rc;
+    if (!field_loops) return fail(FCPP_EINVAL, "bad arguments");
+    if (stride < 1) return fail(FCPP_EINVAL, "stride must be at least 1");
+    return FCPP_OK;
+}
+
+int transit_spacing(double radius, int mode, double spacing)
+{
+    const int rc = route_radius(radius, mode);
+    if (rc) return rc;
+    if (!(spacing > 0.0) || !isfinite(spacing)) return fail(FCPP_EINVAL, "spacing must be positive and finite");
+    return FCPP_OK;
+}
+
+bool transit_rec_args(int64_t n, const TransitRec &rec)
+{
+    return n <= 0 || (rec.found && rec.loop && rec.i && rec.j && rec.in_word && rec.in_seg && rec.out_word && rec.out_seg);
+}
+}  // namespace
+
+extern "C" {
+
+int fcpp_loop_transit_solve(fcpp_ctx *c, int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                            const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                            const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y,
+                            int64_t n_loops, const int64_t *loop_offsets, const int64_t *loop_offsets_host, int64_t n_samples, const double *loop_x,
+                            const double *loop_y, const double *loop_h, const double *loop_s, const int8_t *loop_part, const int8_t *loop_gear,
+                            const int64_t *field_loops, const int64_t *field_loops_host, int64_t stride, int32_t *found, int64_t *loop, int64_t *st_i,
+                            int64_t *st_j, int32_t *in_word, double *in_seg, double *in_len, int32_t *in_rank, int32_t *out_word, double *out_seg,
+                            double *out_len, int32_t *out_rank, double *ride, double *total, int32_t *status)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    int rc = transit_solve_args(mode, n, from_x, from_y, from_h, to_x, to_y, to_h, radius, pair_field, n_fields, ring_offsets, n_rings, vert_offsets,
+                                n_verts, x, y, n_loops, loop_offsets ? (const void *)loop_offsets : (const void *)loop_offsets_host, n_samples,
+                                loop_x && loop_y && loop_h && loop_s && loop_part && loop_gear,
+                                field_loops ? (const void *)field_loops : (const void *)field_loops_host, stride);
+    if (rc) return rc;
+    if (!loop_offsets || !field_loops) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<int64_t> rings, verts, loff, floops;
+    rc = swath_fields(c, n_fields, ring_offsets, nullptr, n_rings, vert_offsets, nullptr, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = host_offsets(c, n_loops, loop_offsets, loop_offsets_host, n_samples, "loop_offsets", loff);
+    if (rc == FCPP_OK) rc = host_offsets(c, n_fields, field_loops, field_loops_host, n_loops, "field_loops", floops);
+    if (rc) return rc;
+    c->transit_listed = 0;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    const TransitLoops L = { n_fields, n_loops, field_loops, loop_offsets, loop_x, loop_y, loop_h, nullptr, loop_s, loop_part, loop_gear, stride };
+    const TransitIo io = { from_x, from_y, from_h, to_x, to_y, to_h, pair_field, found, loop, st_i, st_j, in_word, in_seg, in_len, in_rank,
+                           out_word, out_seg, out_len, out_rank, ride, total, status };
+    if (n <= 0) return FCPP_OK;
+    DevBuf<int64_t> st_idx, st_loop, n_st, pick_l, pick_i, pick_j, list;
+    DevBuf<int32_t> loops_ok, region_status;
+    DevBuf<double> val;
+    DevBuf<unsigned long long> count;
+    HIPCHK(st_idx.alloc((size_t)n_samples));
+    HIPCHK(st_loop.alloc((size_t)n_samples));
+    HIPCHK(n_st.alloc((size_t)n_fields));
+    HIPCHK(loops_ok.alloc((size_t)n_fields));
+    HIPCHK(region_status.alloc((size_t)n_fields));
+    HIPCHK(pick_l.alloc((size_t)n));
+    HIPCHK(pick_i.alloc((size_t)n));
+    HIPCHK(pick_j.alloc((size_t)n));
+    HIPCHK(count.alloc(1));
+    TransitTemp T = { st_idx.p, st_loop.p, n_st.p, loops_ok.p, region_status.p, nullptr, pick_l.p, pick_i.p, pick_j.p };
+    LAUNCHCHK(launch_clear_field_status(st, F, region_status.p));
+    LAUNCHCHK(launch_transit_stations(st, L, T));
+    // the station counts come back: the stations pass's grid is sized by the largest a pair can use
+    std::vector<int64_t> nst;
+    try { nst.assign((size_t)n_fields, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (n_fields > 0) HIPCHK(hipMemcpyAsync(nst.data(), n_st.p, (size_t)n_fields * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t most = 0;
+    for (int64_t f = 0; f < n_fields; ++f) most = std::max(most, std::min<int64_t>(nst[(size_t)f], TRANSIT_MAX_STATIONS));
+    const int64_t per = (most + TRANSIT_BLOCK - 1) / TRANSIT_BLOCK * TRANSIT_BLOCK;
+    if (per > 0 && n > (((int64_t)1 << 36) / (2 * per))) return fail(FCPP_ESIZE, "2^36 (pair, side, station) items or more");
+    const int64_t items = n * 2 * per;
+    if (items > 0) {
+        HIPCHK(val.alloc((size_t)items));
+        HIPCHK(list.alloc((size_t)items));
+        T.val = val.p;
+        HIPCHK(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), st));
+        LAUNCHCHK(launch_transit_sides(st, mode, n, per, io, radius, F, L, T, list.p, count.p));
+        unsigned long long listed = 0;
+        HIPCHK(hipMemcpyAsync(&listed, count.p, sizeof listed, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (listed > (unsigned long long)items) return fail(FCPP_EHIP, "the first pass listed more items than there are");
+        c->transit_listed = (int64_t)listed;
+        if (listed > 0) {
+            LAUNCHCHK(launch_transit_words(st, mode, (int64_t)listed, list.p, n, per, io, radius, F, L, T));
+            ++c->transit_word_launches;
+        }
+    }
+    LAUNCHCHK(launch_transit_pick(st, n, per, io, L, T));
+    LAUNCHCHK(launch_transit_finish(st, mode, n, io, radius, F, L, T));
+    HIPCHK(hipStreamSynchronize(st));          // (the temporaries die here)
+    return FCPP_OK;
+}
+
+int fcpp_ctx_loop_transit_passes(const fcpp_ctx *c, int64_t *listed, int64_t *word_launches)
+{
+    if (!c) return fail(FCPP_EINVAL, "ctx is NULL");
+    if (listed) *listed = c->transit_listed;
+    if (word_launches) *word_launches = c->transit_word_launches;
+    return FCPP_OK;
+}
+
+int fcpp_loop_transit_counts(fcpp_ctx *c, int mode, int64_t n, const int32_t *found, const int64_t *loop, const int64_t *st_i, const int64_t *st_j,
+                             const int32_t *in_word, const double *in_seg, const int32_t *out_word, const double *out_seg, int64_t n_loops,
+                             const int64_t *loop_offsets, const int64_t *loop_offsets_host, int64_t n_samples, double spacing,
+                             int64_t *path_offsets, int64_t *path_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    const TransitRec rec = { found, loop, st_i, st_j, in_word, in_seg, out_word, out_seg };
+    int rc = transit_spacing(1.0, mode, spacing);
+    if (rc == FCPP_OK) rc = transit_loop_args(n_loops, loop_offsets, n_samples, true);
+    if (rc) return rc;
+    if (!transit_rec_args(n, rec) || !path_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    if (n < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> loff;
+    rc = host_offsets(c, n_loops, loop_offsets, loop_offsets_host, n_samples, "loop_offsets", loff);
+    if (rc) return rc;
+    return sample_counts(c, n, path_offsets, path_offsets_host, "a transit has 2^31 samples or more", [&](hipStream_t st, int64_t *err) {
+        return launch_transit_counts(st, mode, n, rec, n_loops, loop_offsets, spacing, path_offsets, err);
+    });
+}
+
+int fcpp_loop_transit_fill(fcpp_ctx *c, int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, double radius,
+                           const int32_t *found, const int64_t *loop, const int64_t *st_i, const int64_t *st_j, const int32_t *in_word,
+                           const double *in_seg, const int32_t *out_word, const double *out_seg, int64_t n_loops, const int64_t *loop_offsets,
+                           const int64_t *loop_offsets_host, int64_t n_samples, const double *loop_x, const double *loop_y, const double *loop_h,
+                           const double *loop_kappa, const int8_t *loop_gear, double spacing, const int64_t *path_offsets,
+                           const int64_t *path_offsets_host, int64_t total_samples, double *out_x, double *out_y, double *heading, double *kappa,
+                           int8_t *part, int8_t *gear)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    const TransitRec rec = { found, loop, st_i, st_j, in_word, in_seg, out_word, out_seg };
+    int rc = transit_spacing(radius, mode, spacing);
+    if (rc == FCPP_OK) rc = transit_loop_args(n_loops, loop_offsets, n_samples, loop_x && loop_y && loop_h && loop_kappa && loop_gear);
+    if (rc) return rc;
+    if (!transit_rec_args(n, rec) || !path_offsets || (n > 0 && (!from_x || !from_y || !from_h))) return fail(FCPP_EINVAL, "bad arguments");
+    if (n < 0 || n > INT32_MAX || total_samples < 0 || total_samples > ((int64_t)1 << 38)) return fail(FCPP_ESIZE, "bad sizes");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> loff;
+    rc = host_offsets(c, n_loops, loop_offsets, loop_offsets_host, n_samples, "loop_offsets", loff);
+    if (rc) return rc;
+    SampleOffsets outs;
+    rc = outs.get(c, n, path_offsets, path_offsets_host, total_samples, "path_offsets", true);
+    if (rc) return rc;
+    const TransitLoops L = { 0, n_loops, nullptr, loop_offsets, loop_x, loop_y, loop_h, loop_kappa, nullptr, nullptr, loop_gear, 1 };
+    LAUNCHCHK(launch_transit_fill(c->stream, mode, n, rec, L, from_x, from_y, from_h, radius, spacing, outs.dev, total_samples, out_x, out_y, heading,
+                                  kappa, part, gear));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPP_OK;
+}
+
+int fcpp_debug_loop_transits(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                             const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                             const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x, const double *y,
+                             int64_t n_loops, const int64_t *loop_offsets, int64_t n_samples, const double *loop_x, const double *loop_y,
+                             const double *loop_h, const double *loop_kappa, const double *loop_s, const int8_t *loop_part, const int8_t *loop_gear,
+                             const int64_t *field_loops, int64_t stride, double spacing, int32_t *found, int64_t *loop, int64_t *st_i, int64_t *st_j,
+                             int32_t *in_word, double *in_seg, double *in_len, int32_t *in_rank, int32_t *out_word, double *out_seg, double *out_len,
+                             int32_t *out_rank, double *ride, double *total, int32_t *status, int64_t *path_offsets, int64_t cap, double *out_x,
+                             double *out_y, double *heading, double *kappa, int8_t *part, int8_t *gear)
+{
+    int rc = transit_solve_args(mode, n, from_x, from_y, from_h, to_x, to_y, to_h, radius, pair_field, n_fields, ring_offsets, n_rings, vert_offsets,
+                                n_verts, x, y, n_loops, loop_offsets, n_samples, loop_x && loop_y && loop_h && loop_kappa && loop_s && loop_part && loop_gear,
+                                field_loops, stride);
+    if (rc == FCPP_OK) rc = transit_spacing(radius, mode, spacing);
+    if (rc == FCPP_OK && cap < 0) rc = fail(FCPP_ESIZE, "bad sizes");
+    if (rc) return rc;
+    std::vector<int64_t> rings, verts, loff, floops;
+    rc = swath_fields(nullptr, n_fields, nullptr, ring_offsets, n_rings, nullptr, vert_offsets, n_verts, rings, verts);
+    if (rc == FCPP_OK) rc = host_offsets(nullptr, n_loops, nullptr, loop_offsets, n_samples, "loop_offsets", loff);
+    if (rc == FCPP_OK) rc = host_offsets(nullptr, n_fields, nullptr, field_loops, n_loops, "field_loops", floops);
+    if (rc) return rc;
+    const ClearFields F = { n_fields, ring_offsets, vert_offsets, x, y };
+    const TransitLoops L = { n_fields, n_loops, field_loops, loop_offsets, loop_x, loop_y, loop_h, loop_kappa, loop_s, loop_part, loop_gear, stride };
+    const int nseg = mode == 0 ? 3 : 5;
+    // per field: the region's status, the loops' validity, the stations (at the place of the field's first sample)
+    std::vector<int32_t> region_status, loops_ok;
+    std::vector<int64_t> n_st, st_idx, st_loop, cnt;
+    std::vector<TransitResult> res;
+    try {
+        region_status.assign((size_t)n_fields, 0); loops_ok.assign((size_t)n_fields, 0); n_st.assign((size_t)n_fields, 0);
+        st_idx.assign((size_t)n_samples, 0); st_loop.assign((size_t)n_samples, 0); cnt.assign((size_t)n + 1, 0); res.resize((size_t)n);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    WorkerPool::parallel_for(n_fields, [&](int64_t f) {
+        region_status[(size_t)f] = clear_field_status(F, f);
+        loops_ok[(size_t)f] = transit_field_loops_ok(L, f) ? 1 : 0;
+        const int64_t base = field_loops[f + 1] > field_loops[f] ? loop_offsets[field_loops[f]] : 0;
+        n_st[(size_t)f] = transit_field_stations(L, f, st_idx.data() + base, st_loop.data() + base);
+    });
+    std::vector<char> big((size_t)n, 0), nomem((size_t)n, 0);
+    WorkerPool::parallel_for(n, [&](int64_t p) {
+        const int64_t f = pair_field[p];
+        const double x0 = from_x[p], y0 = from_y[p], h0 = from_h[p], x1 = to_x[p], y1 = to_y[p], h1 = to_h[p];
+        const int stt = transit_pair_status(x0, y0, h0, x1, y1, h1, f, n_fields, region_status.data(), loops_ok.data(), n_st.data());
+        TransitPick pick = transit_pick_none();
+        if (stt == TRANSIT_OK && n_st[(size_t)f] > 0) {
+            const int64_t base = loop_offsets[field_loops[f]], m = n_st[(size_t)f];
+            std::vector<double> in, out;
+            try { in.assign((size_t)m, 0.0); out.assign((size_t)m, 0.0); } catch (const std::bad_alloc &) { nomem[(size_t)p] = 1; return; }
+            pick = mode == 0 ? transit_pick_host<0>(F, L, f, x0, y0, h0, x1, y1, h1, radius, m, st_idx.data() + base, st_loop.data() + base, in.data(), out.data())
+                             : transit_pick_host<1>(F, L, f, x0, y0, h0, x1, y1, h1, radius, m, st_idx.data() + base, st_loop.data() + base, in.data(), out.data());
+        }
+        const TransitResult r = mode == 0 ? transit_finish<0>(F, L, f, x0, y0, h0, x1, y1, h1, radius, stt, pick)
+                                          : transit_finish<1>(F, L, f, x0, y0, h0, x1, y1, h1, radius, stt, pick);
+        res[(size_t)p] = r;
+        if (found) found[p] = r.found;
+        if (loop) loop[p] = r.loop;
+        if (st_i) st_i[p] = r.i;
+        if (st_j) st_j[p] = r.j;
+        if (in_word) in_word[p] = r.in.word;
+        if (out_word) out_word[p] = r.out.word;
+        for (int k = 0; k < nseg; ++k) {
+            if (in_seg) in_seg[p * nseg + k] = r.in.seg[k];
+            if (out_seg) out_seg[p * nseg + k] = r.out.seg[k];
+        }
+        if (in_len) in_len[p] = r.in.len;
+        if (out_len) out_len[p] = r.out.len;
+        if (in_rank) in_rank[p] = r.in.rank;
+        if (out_rank) out_rank[p] = r.out.rank;
+        if (ride) ride[p] = r.ride;
+        if (total) total[p] = r.total;
+        if (status) status[p] = r.status;
+    });
+    for (int64_t p = 0; p < n; ++p)
+        if (nomem[(size_t)p]) return fail(FCPP_ENOMEM, "out of host memory");
+    if (!path_offsets && (cap == 0 || !(out_x || out_y || heading || kappa || part || gear))) return FCPP_OK;
+    // the sampled paths, from the results as a caller would hand them back (one pair at a time: NSEG segments in place)
+    auto rec_of = [&](const TransitResult &r, int32_t &fnd, int64_t *ids, int32_t *words) {
+        fnd = r.found; ids[0] = r.loop; ids[1] = r.i; ids[2] = r.j; words[0] = r.in.word; words[1] = r.out.word;
+        return TransitRec{ &fnd, ids, ids + 1, ids + 2, words, r.in.seg, words + 1, r.out.seg };
+    };
+    WorkerPool::parallel_for(n, [&](int64_t p) {
+        int32_t fnd, words[2];
+        int64_t ids[3], a, b, c2, bad = 0;
+        const TransitRec rec = rec_of(res[(size_t)p], fnd, ids, words);
+        if (mode == 0) transit_counts<0>(rec, n_loops, loop_offsets, spacing, 0, a, b, c2, bad);
+        else transit_counts<1>(rec, n_loops, loop_offsets, spacing, 0, a, b, c2, bad);
+        cnt[(size_t)p + 1] = a + b + c2;
+        big[(size_t)p] = bad != 0;
+    });
+    for (int64_t p = 0; p < n; ++p) {
+        if (big[(size_t)p]) return fail(FCPP_ESIZE, "a transit has 2^31 samples or more");
+        cnt[(size_t)p + 1] += cnt[(size_t)p];
+    }
+    if (path_offsets) memcpy(path_offsets, cnt.data(), cnt.size() * sizeof(int64_t));
+    if (cap == 0 || !(out_x || out_y || heading || kappa || part || gear)) return FCPP_OK;
+    WorkerPool::parallel_for(n, [&](int64_t p) {
+        int32_t fnd, words[2];
+        int64_t ids[3];
+        const TransitRec rec = rec_of(res[(size_t)p], fnd, ids, words);
+        const int64_t at = cnt[(size_t)p], K = cnt[(size_t)p + 1] - at;
+        for (int64_t k = 0; k < K && at + k < cap; ++k) {
+            double px, py, ph, pk;
+            int pp, pg;
+            if (mode == 0) transit_eval<0>(rec, L, from_x + p, from_y + p, from_h + p, radius, spacing, 0, k, K, px, py, ph, pk, pp, pg);
+            else transit_eval<1>(rec, L, from_x + p, from_y + p, from_h + p, radius, spacing, 0, k, K, px, py, ph, pk, pp, pg);
+            if (out_x) out_x[at + k] = px;
+            if (out_y) out_y[at + k] = py;
+            if (heading) heading[at + k] = ph;
+            if (kappa) kappa[at + k] = pk;
+            if (part) part[at + k] = (int8_t)pp;
+            if (gear) gear[at + k] = (int8_t)pg;
+        }
+    });
+    return FCPP_OK;
 }
 
 }  // extern "C"

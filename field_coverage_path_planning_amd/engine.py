@@ -1773,7 +1773,7 @@ def clear_connectors(from_poses, to_poses, fields, pair_field, radius, reversing
     pair_field[i] of `fields` (fcpp_conn_solve_clear; the rule: include/fcpp.h): the solvers' 6 / 48 candidates in the order (length,
     word), each tested as connector_clearance tests the shortest one, the first clear one kept.  rank says which it was; rank -1: none is
     clear and the shortest word is returned with its crossings.  pair_field: one index per pair (or one for all); -1 means no region.  One
-    word per pair -- no via points; a margin is no parameter: pass polygon_inset(fields, [margin]).as_fields(0).  -> ClearConnectors."""
+    word per pair -- via points and rides along a headland loop are loop_transits'; a margin is no parameter: pass polygon_inset(fields, [margin]).as_fields(0).  -> ClearConnectors."""
     ctx = get_context(device)
     torch = _torch()
     dev = torch.device('cuda', ctx.device)
@@ -1909,6 +1909,11 @@ class FieldPaths:
     blocked: object = None      # (n) int32: the field's connector legs of rank -1
     reshaped: object = None     # (n) int32: the field's connector legs of rank > 0
     region_status: object = None    # (n) int32: 0, or FCPP_EINVAL for a region field with no ring, a ring of fewer than 3 vertices, a non-finite vertex
+    # field_paths(clear_of=..., loops=...) only (None otherwise): the rank -1 legs that ride a headland loop round the obstacle.  Plain
+    # attributes set on the result, not constructor arguments: the members above are the entries' outputs in their order
+    detoured = None             # (n) int32: the field's connector legs whose samples are a loop transit's; `blocked` counts the rest
+    leg_transit = None          # (slots) int64: the slot's index into `transits`, -1 where the slot's own record is driven
+    transits = None             # LoopTransits of the rank -1 legs, ordered by field, then by slot
 
     def field(self, i):
         """(x, y, heading, part) of field i: swath_route's tuple"""
@@ -1946,7 +1951,7 @@ def _leg_paths(ctx, counts, fill, args, n_groups, n_slots, n_totals, dev):
     return (off, off_h, x, y, h, kap, part, gear, leg, *totals, status, leg_off)
 
 
-def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None, clear_of=None):
+def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None, clear_of=None, loops=None):
     """The path of EVERY field of a SwathSet in one pass on the device (fcpp_field_path_counts + fcpp_field_path_fill) -> FieldPaths.
     What swath_route gives for one field, for the whole batch and without a host loop: each swath sampled every `spacing` metres (its last
     sample is its end), consecutive swaths joined by the shortest Dubins path -- Reeds-Shepp if `reversing` -- planned at
@@ -1960,7 +1965,15 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     word that stays off its region's rings, as clear_connectors chooses it (fcpp_field_path_counts_clear + fcpp_field_path_fill_clear);
     where no word is clear the shortest is still driven.  FieldPaths then holds leg_rank, leg_crossings, leg_word, leg_seg, leg_total
     per leg slot and blocked, reshaped, region_status per field; connector_clearance on the legs' start poses, leg_word and leg_seg
-    agrees with leg_rank.  Without clear_of nothing changes, down to the entries called."""
+    agrees with leg_rank.  Without clear_of nothing changes, down to the entries called.
+    loops (with clear_of; a HeadlandPaths or a sequence of them, e.g. both directions): every rank -1 leg for which loop_transits finds a
+    transit -- a clear connector onto a headland loop, a ride along it, a clear connector off it -- has its samples replaced by the
+    transit's (part 1 on its connectors, FCPP_PART_LOOP_RIDE on the ride; `leg` stays the slot).  offsets, leg_offsets and transit_length
+    follow; blocked counts the legs that are still driven through the region, detoured those that ride; leg_transit and transits say
+    which.  The per-slot records (leg_word, leg_seg, leg_total, leg_rank) stay those of the word that was not driven.  The ride itself is
+    not tested against the region.  Without loops nothing changes, down to the entries called."""
+    if loops is not None and clear_of is None:
+        raise ValueError('loops needs clear_of: the region the transits have to stay clear of')
     ctx = get_context(device)
     torch = _torch()
     ss = swathset
@@ -1989,7 +2002,10 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
     def counts(handle, *a):
         return ctx.lib.fcpp_field_path_counts_clear(handle, *a, *[_ptr(t) for t in extra])
 
-    return FieldPaths(*_leg_paths(ctx, counts, ctx.lib.fcpp_field_path_fill_clear, args + tuple(region), n, n_slots, 2, dev), *extra)
+    fp = FieldPaths(*_leg_paths(ctx, counts, ctx.lib.fcpp_field_path_fill_clear, args + tuple(region), n, n_slots, 2, dev), *extra)
+    if loops is None:
+        return fp
+    return _detour_field_paths(fp, ss, pf, loops, _chord_radius(radius, spacing), spacing, reversing, order, entry, exit, device)
 
 
 # ---- headland paths (fcpp_headland_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------
@@ -2012,6 +2028,7 @@ class HeadlandPaths:
     status: object              # (n_rings) int32: 0, FCPP_EINVAL or FCPP_EUNSUPPORTED (no drivable element): no samples
     leg_offsets: object         # (2 n_verts + 1) int64: the first sample of every leg slot; ring r's first slot is 2 ring_offsets[r]
     ring_pair: object           # (n_rings, 2) int64, device: the (field, pass) index of every ring
+    spacing: object = None      # the sample spacing the loops were driven at [m] (loop_transits turns station_step into a stride by it)
 
     def ring(self, r):
         """(x, y, heading, part) of ring r"""
@@ -2051,7 +2068,212 @@ def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_
     ring_dist = inset.distances[ring_pair[:, 1]].contiguous() if nr else torch.empty(0, dtype=torch.float64, device=dev)
     out = _headland_paths(ctx, inset.ring_offsets, inset.x, inset.y, inset.src, ring_dist, _chord_radius(radius, spacing), 1 if reversing else 0,
                           spacing, direction, smooth_tol)
-    return HeadlandPaths(*out, ring_pair)
+    return HeadlandPaths(*out, ring_pair, float(spacing))
+
+
+# ---- loop transits (fcpp_loop_transit_solve / _counts / _fill; the rule: include/fcpp.h) ------------------------------------------------
+@dataclass
+class TransitPaths:
+    """LoopTransits.paths(): one sampled path per pair, in the CSR form curvature(), speed_plan(), validate() and trajectory() take"""
+    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy.  A pair that is not found has no samples
+    offsets_host: object
+    x: object                   # (total) float64
+    y: object
+    heading: object
+    kappa: object
+    part: object                # (total) int8: 1 on the two connectors, FCPP_PART_LOOP_RIDE (5) on the ride
+    gear: object                # (total) int8
+
+
+@dataclass
+class LoopTransits:
+    """loop_transits(): per pair the cheapest "clear connector onto a loop, ride, clear connector off it", one entry per pair"""
+    found: object               # (n) int32
+    loop: object                # (n) int64: the loop ridden, an index into the loop set as loop_transits arranged it (loops sorted by field); -1
+    st_i: object                # (n) int64: the stations where the ride starts and ends, sample indices into that loop set; -1
+    st_j: object
+    in_word: object             # (n) int32, (n, 3 / 5), (n), (n) int32: the connector onto the loop, as clear_connectors gives it
+    in_seg: object
+    in_length: object
+    in_rank: object
+    out_word: object            # the connector off the loop
+    out_seg: object
+    out_length: object
+    out_rank: object
+    ride: object                # (n) float64: the arc length ridden [m]
+    total: object               # (n) float64: in + ride + out [m]; +inf where no transit is found
+    status: object              # (n) int32: 0, FCPP_EINVAL (a non-finite pose, a bad region or loop field), FCPP_EUNSUPPORTED (too many stations)
+    radius: float
+    reversing: bool
+    stride: int
+    loop_set: object = None     # dict of the arranged loop set's device tensors: offsets, x, y, heading, kappa, s, part, gear, field_loops
+    _start: object = None
+    _device: object = None
+
+    def paths(self, spacing):
+        """The transits sampled (fcpp_loop_transit_counts + fcpp_loop_transit_fill): the connectors every `spacing` metres by the
+        connectors' own samplers, the ride the loop's own samples -> TransitPaths."""
+        ctx = get_context(self._device)
+        torch = _torch()
+        ls, f = self.loop_set, self._start
+        dev = self.found.device
+        n = int(self.found.numel())
+        mode = 1 if self.reversing else 0
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        off_h = np.zeros(n + 1, dtype=np.int64)
+        rec = [_ptr(t) for t in (self.found, self.loop, self.st_i, self.st_j, self.in_word, self.in_seg, self.out_word, self.out_seg)]
+        lhead = (int(ls['offsets'].numel()) - 1, _ptr(ls['offsets']), _host_ptr(ls['offsets_host']), int(ls['x'].numel()))
+        ctx.bind_stream()
+        L.check(ctx.lib.fcpp_loop_transit_counts(ctx.handle, mode, n, *rec, *lhead, float(spacing), _ptr(off), _host_ptr(off_h)))
+        total = int(off_h[-1])
+        x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
+        part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
+        L.check(ctx.lib.fcpp_loop_transit_fill(ctx.handle, mode, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(self.radius), *rec, *lhead,
+                                               _ptr(ls['x']), _ptr(ls['y']), _ptr(ls['heading']), _ptr(ls['kappa']), _ptr(ls['gear']), float(spacing),
+                                               _ptr(off), _host_ptr(off_h), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear)))
+        return TransitPaths(off, off_h, x, y, h, kap, part, gear)
+
+
+def _loop_set(loops, n_fields, dev, device):
+    """HeadlandPaths (one or several, e.g. both directions) -> the loop set of the transit entries: the loops sorted by field (stable: a
+    field's loops in the order given), their samples gathered, s from trajectory(), field_loops from ring_pair -> (dict, spacing)"""
+    torch = _torch()
+    loops = [loops] if isinstance(loops, HeadlandPaths) else list(loops)
+    cols = {k: [] for k in ('x', 'y', 'heading', 'kappa', 's', 'part', 'gear')}
+    fld, start, lens, base, spacing = [], [], [], 0, None
+    for hp in loops:
+        total = int(hp.x.numel())
+        s = trajectory(hp.x, hp.y, torch.ones(total, dtype=torch.float64, device=dev), offsets=hp.offsets, device=device)[0] if total else hp.x
+        for k, t in zip(cols, (hp.x, hp.y, hp.heading, hp.kappa, s, hp.part, hp.gear)):
+            cols[k].append(t.to(dev))
+        off = hp.offsets.to(dev)
+        fld.append(hp.ring_pair[:, 0].to(dev)); start.append(off[:-1] + base); lens.append(off[1:] - off[:-1])
+        base += total
+        spacing = hp.spacing if spacing is None else spacing
+    i64 = lambda ts: torch.cat(ts) if ts else torch.zeros(0, dtype=torch.int64, device=dev)
+    fld, start, lens = i64(fld), i64(start), i64(lens)
+    order = torch.argsort(fld, stable=True)
+    fld, start, lens = fld[order], start[order], lens[order]
+    off = torch.zeros(int(lens.numel()) + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(lens, 0)
+    off_h = off.cpu().numpy()
+    total = int(off_h[-1])
+    idx = torch.repeat_interleave(start - off[:-1], lens, output_size=total) + torch.arange(total, dtype=torch.int64, device=dev)
+    ls = {k: (torch.cat(v)[idx].contiguous() if v else torch.zeros(0, dtype=torch.float64 if k not in ('part', 'gear') else torch.int8, device=dev))
+          for k, v in cols.items()}
+    fl = torch.searchsorted(fld, torch.arange(n_fields + 1, dtype=torch.int64, device=dev)).to(torch.int64).contiguous()
+    ls.update(offsets=off, offsets_host=off_h, field_loops=fl, field_loops_host=fl.cpu().numpy())
+    if spacing is None:          # (loops that do not say: the mean step of their samples)
+        steps = total - int(lens.numel())
+        last = off[1:][lens > 0] - 1
+        spacing = float(ls['s'][last].sum()) / steps if steps > 0 else 1.0
+    return ls, spacing
+
+
+def _loop_transits(ctx, f, t, pf, pair_field, ls, radius, reversing, stride, device):
+    torch = _torch()
+    dev = f[0].device
+    n = int(f[0].numel())
+    ns = 5 if reversing else 3
+    i32 = lambda: torch.empty(n, dtype=torch.int32, device=dev)
+    i64 = lambda: torch.empty(n, dtype=torch.int64, device=dev)
+    f64 = lambda *shape: torch.empty((n,) + shape, dtype=torch.float64, device=dev)
+    out = (i32(), i64(), i64(), i64(), i32(), f64(ns), f64(), i32(), i32(), f64(ns), f64(), i32(), f64(), f64(), i32())
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_loop_transit_solve(ctx.handle, 1 if reversing else 0, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]),
+                                            float(radius), _ptr(pair_field), *pf._head(), int(ls['offsets'].numel()) - 1, _ptr(ls['offsets']),
+                                            _host_ptr(ls['offsets_host']), int(ls['x'].numel()), _ptr(ls['x']), _ptr(ls['y']), _ptr(ls['heading']),
+                                            _ptr(ls['s']), _ptr(ls['part']), _ptr(ls['gear']), _ptr(ls['field_loops']), _host_ptr(ls['field_loops_host']),
+                                            int(stride), *[_ptr(o) for o in out]))
+    return LoopTransits(*out, float(radius), bool(reversing), int(stride), ls, f, device)
+
+
+def loop_transits(from_poses, to_poses, fields, pair_field, loops, radius, reversing=False, station_step=None, device=None):
+    """Per pair from_poses[i] -> to_poses[i] the cheapest LOOP TRANSIT (fcpp_loop_transit_solve; the rule: include/fcpp.h): the shortest clear
+    Dubins -- Reeds-Shepp if `reversing` -- connector (as clear_connectors chooses it, against field pair_field[i] of `fields`) onto a
+    station of one of the field's headland loops, a ride forwards along that loop, and the shortest clear connector off it, over all loops
+    of the field and all pairs of stations.  loops: a HeadlandPaths or a sequence of them (pass direction=+1 and direction=-1 to offer both
+    ways round); a loop serves the field its ring belongs to (ring_pair).  Stations: every max(1, round(station_step / spacing)) -th
+    sample of a loop that lies on a straight element or a followed arc; station_step defaults to `radius`.  At most
+    FCPP_TRANSIT_MAX_STATIONS stations per field (status FCPP_EUNSUPPORTED beyond: raise station_step).  pair_field: one index per pair (or
+    one for all), 0 .. n_fields - 1.  The ride is not tested against the region: a headland pass lies inside its field by construction,
+    its corner connectors may not (validate() flags that).  -> LoopTransits; .paths(spacing) samples them."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    pf = polygon_fields(fields, device)
+    f, t = _poses(from_poses, dev), _poses(to_poses, dev)
+    n = int(f[0].numel())
+    if int(t[0].numel()) != n:
+        raise ValueError('from_poses and to_poses must hold the same number of poses')
+    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
+    if pair_field.numel() == 1 and n != 1:
+        pair_field = pair_field.expand(n)
+    if pair_field.numel() != n:
+        raise ValueError('pair_field must be a scalar or hold one field index per pair')
+    ls, spacing = _loop_set(loops, pf.n, dev, device)
+    step = float(radius) if station_step is None else float(station_step)
+    if not step > 0.0:
+        raise ValueError('station_step must be positive')
+    return _loop_transits(ctx, f, t, pf, pair_field.contiguous(), ls, radius, reversing, max(1, int(round(step / spacing))), device)
+
+
+def _detour_field_paths(fp, ss, pf, loops, R, spacing, reversing, order, entry, exit, device):
+    """field_paths(loops=...): the rank -1 legs of a clear field path through loop_transits at the planning radius R; the found ones'
+    samples spliced in by one gather on the device"""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = fp.x.device
+    soff_h = np.ascontiguousarray(ss.offsets_host, dtype=np.int64)
+    n, m = len(soff_h) - 1, int(soff_h[-1])
+    n_slots = 2 * m + n
+    frm, to, lf, slot = _leg_pairs(ss, order, entry, exit)
+    g = 2 * ss.offsets[lf] + lf + slot                                   # the legs' global slots
+    ok = fp.status[lf] == 0 if int(lf.numel()) else torch.zeros(0, dtype=torch.bool, device=dev)
+    pick = torch.nonzero(ok & (fp.leg_rank[g] < 0) & (fp.leg_word[g] >= 0)).reshape(-1)
+    g, lf, slot = g[pick], lf[pick].contiguous(), slot[pick]
+    f = tuple(frm[pick][:, k].contiguous() for k in range(3))
+    t = tuple(to[pick][:, k].contiguous() for k in range(3))
+    ls, loop_spacing = _loop_set(loops, n, dev, device)
+    lt = _loop_transits(ctx, f, t, pf, lf, ls, R, reversing, max(1, int(round(R / loop_spacing))), device)
+    tp = lt.paths(spacing)
+    leg_transit = torch.full((n_slots,), -1, dtype=torch.int64, device=dev)
+    hit = lt.found == 1
+    leg_transit[g[hit]] = torch.nonzero(hit).reshape(-1)
+    detoured = torch.zeros(n, dtype=torch.int32, device=dev)
+    detoured.index_add_(0, lf[hit], torch.ones(int(hit.sum()), dtype=torch.int32, device=dev))
+    # the gather: per slot where its samples start in [the plain path's samples; the transits' samples] and how many they are
+    old_off, plain_total = fp.leg_offsets, int(fp.x.numel())
+    cnt, src = old_off[1:] - old_off[:-1], old_off[:-1].clone()
+    det = leg_transit >= 0
+    tr = leg_transit[det]
+    cnt[det] = tp.offsets[tr + 1] - tp.offsets[tr]
+    src[det] = plain_total + tp.offsets[tr]
+    leg_off = torch.zeros(n_slots + 1, dtype=torch.int64, device=dev)
+    leg_off[1:] = torch.cumsum(cnt, 0)
+    first = 2 * ss.offsets + torch.arange(n + 1, dtype=torch.int64, device=dev)
+    first[n] = n_slots
+    off = leg_off[first].contiguous()
+    off_h = off.cpu().numpy()
+    total = int(off_h[-1])
+    idx = torch.repeat_interleave(src - leg_off[:-1], cnt, output_size=total) + torch.arange(total, dtype=torch.int64, device=dev)
+    t_cnt = tp.offsets[1:] - tp.offsets[:-1]
+    t_leg = torch.repeat_interleave(slot.to(torch.int32), t_cnt, output_size=int(tp.x.numel()))
+    both = lambda a, b: torch.cat([a, b])[idx].contiguous()
+    # a detoured field's transit length: its connector slots' lengths in slot order, a detoured slot's the transit's total
+    leg_len = fp.leg_total.clone()
+    leg_len[g[hit]] = lt.total[hit]
+    slots_of = first[1:] - first[:-1]
+    fld_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), slots_of, output_size=n_slots)
+    even = (torch.arange(n_slots, dtype=torch.int64, device=dev) - first[fld_of]) % 2 == 0
+    per_field = (slots_of + 1) // 2
+    summed = torch.segment_reduce(leg_len[even], 'sum', lengths=per_field, initial=0.0)
+    transit = torch.where(detoured > 0, summed, fp.transit_length)
+    out = FieldPaths(off, off_h, both(fp.x, tp.x), both(fp.y, tp.y), both(fp.heading, tp.heading), both(fp.kappa, tp.kappa), both(fp.part, tp.part),
+                     both(fp.gear, tp.gear), both(fp.leg, t_leg), fp.work_length, transit, fp.status, leg_off, fp.leg_rank, fp.leg_crossings,
+                     fp.leg_word, fp.leg_seg, fp.leg_total, fp.blocked - detoured, fp.reshaped, fp.region_status)
+    out.detoured, out.leg_transit, out.transits = detoured, leg_transit, lt
+    return out
 
 
 # ---- polygon coverage (fcpp_polygon_cover_sizes / fcpp_polygon_cover; the rule: include/fcpp.h) -----------------------------------------
@@ -2210,11 +2432,12 @@ class PolygonPlan:
     headland_paths: object = None       # HeadlandPaths of `headland` when asked for (headland_paths=True), else None
     coverage: object = None             # PolygonCoverage of `fields` under paths (and headland_paths) when asked for (coverage_resolution), else None
     clearance: object = None            # FieldPathClearance of `paths` against clear_of when given, else None
+    transits: object = None             # LoopTransits of the rank -1 legs of `paths` when asked for (detour=True), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
                         arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
-                        price_clear=False):
+                        price_clear=False, detour=False):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2230,7 +2453,12 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     PolygonPlan.clearance stays what it is, the shortest-word legs as routed.  price_clear=True (with reshape=True; ValueError without:
     the route would be priced with words nobody drives): the router's matrix holds the clear words' lengths
     (route_swaths(price_clear=True)), so route.length is paths.transit_length and route.blocked is paths.blocked.  The headland loops'
-    corner connectors are neither tested nor re-shaped."""
+    corner connectors are neither tested nor re-shaped.  detour=True (with reshape=True and headland_paths=True; ValueError without): the
+    legs for which no word is clear ride the plan's own headland loops, driven in both directions, round the obstacle
+    (field_paths(loops=...)): PolygonPlan.transits is paths.transits, paths.blocked the legs that stay blocked, paths.detoured those that
+    ride.  The router does not price the transits: route.length then differs from paths.transit_length on a detoured field."""
+    if detour and not (reshape and headland_paths):
+        raise ValueError('detour=True needs reshape=True and headland_paths=True: the loops the blocked legs ride')
     if reshape and clear_of is None:
         raise ValueError('reshape=True needs clear_of: the region the connectors have to stay clear of')
     if price_clear and not reshape:
@@ -2246,14 +2474,15 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     region = None if clear_of is None else (fields if isinstance(clear_of, str) and clear_of == 'boundary' else polygon_fields(clear_of, device))
     route = route_swaths(ss, radius, reversing=reversing, entry=entry, exit=exit, starts=starts, spacing=spacing, device=device, clear_of=region,
                          **({'price_clear': True} if price_clear else {}))
-    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device,
-                        clear_of=region if reshape else None)
-    clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
+    both = (hp, _drive_headland(lines, radius, spacing, reversing=reversing, direction=-1, device=device)) if detour else None
+    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device,
+                        clear_of=region if reshape else None, **({'loops': both} if detour else {}))
+    clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     cov = None
     if coverage_resolution is not None:
         cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device)
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr)
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr, paths.transits if detour else None)
 
 
 def _polys(polygons):

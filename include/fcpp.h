@@ -753,8 +753,8 @@ int fcpp_ctx_route_priced_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *
 
 /* ---- clear connectors: per pair of poses the shortest word that stays off the field's rings -------------------------------------------------
  * Build-defined.  The entries above test a SOLVED connector; this one chooses: both solvers evaluate every word of a pair (6 Dubins, 48
- * Reeds-Shepp) and keep the shortest -- here the shortest one that is CLEAR of the pair's field is kept.  One word per pair, no via points, no
- * detours along the headland, no margin (pass the inset).  Standalone like the clearance entries; nothing here feeds fcpp_batch_plan.
+ * Reeds-Shepp) and keep the shortest -- here the shortest one that is CLEAR of the pair's field is kept.  One word per pair, no margin
+ * (pass the inset); via points and detours along the headland are the loop transits' (fcpp_loop_transit_solve, below).  Standalone like the clearance entries; nothing here feeds fcpp_batch_plan.
  * THE RULE (csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).  Nothing geometric is added: the
  * candidates come out of the solvers' own word enumerations and are tested by the clearance rule above.
  *   - Candidates of a pair: the words the solver finds feasible with a finite total, each with exactly the seg and total bits
@@ -834,8 +834,8 @@ int fcpp_field_path_fill(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_
 
 /* ---- clear field paths: the field paths, every connector driven by the shortest word that stays off a region ---------------------------------
  * Build-defined.  fcpp_field_path_counts / _fill drive the shortest word of every connector whatever it crosses; these two drive, per
- * connector, the word fcpp_conn_solve_clear chooses.  One word per connector: no via points, no detours along the headland, no margin (pass
- * the inset); fcpp_route_transit_priced gives the router the matrix of the chosen words' lengths.  Standalone: nothing here feeds fcpp_batch_plan.
+ * connector, the word fcpp_conn_solve_clear chooses.  One word per connector, no margin (pass the inset); a leg without a clear word can ride a headland loop
+ * (fcpp_loop_transit_solve, below: engine.field_paths(loops=...) splices such transits in); fcpp_route_transit_priced gives the router the matrix of the chosen words' lengths.  Standalone: nothing here feeds fcpp_batch_plan.
  * THE RULE (csrc/fcpp_fpathfn.h over csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).  The clear
  * field path of a batch is the field path above with ONE difference: in a field whose path status is FCPP_OK the record of every connector
  * slot -- word, seg, total -- is what fcpp_conn_solve_clear gives for the slot's from-pose and to-pose (the very poses the connector above is
@@ -882,6 +882,88 @@ int fcpp_field_path_fill_clear(fcpp_ctx *ctx, int64_t n, const int64_t *swath_of
  * counts call skips the fields whose path status is FCPP_EINVAL; the fill keeps no status and also looks at their legs, which have no
  * samples, so its `listed` may be larger.  For tests; fcpp_ctx_solve_clear_passes keeps its meaning. */
 int fcpp_ctx_field_path_clear_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *word_launches);
+
+/* ---- loop transits: a blocked leg rides a headland loop round the obstacle ------------------------------------------------------------------
+ * Build-defined.  The clear connectors above give ONE word per pair; where no word is clear (rank -1) the leg still crosses the pond.  A
+ * LOOP TRANSIT of a pair P -> Q is three pieces: a clear connector from P to a station i of a loop, the loop's own samples from i forward
+ * to a station j of the same loop, a clear connector from station j to Q.  fcpp_loop_transit_solve finds, per pair, the cheapest one over
+ * all loops of the pair's field and all station pairs; fcpp_loop_transit_counts / _fill sample it.  Standalone: nothing here feeds
+ * fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_transitfn.h over csrc/fcpp_solveclearfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Loops: a path set in the samplers' CSR form as fcpp_headland_path_fill writes it: loop l owns the samples loop_offsets[l] ..
+ *     loop_offsets[l + 1] of loop_x, loop_y, loop_h (heading), loop_kappa, loop_part, loop_gear, and loop_s, the arc length of every sample
+ *     from its loop's first sample -- fcpp_trajectory's s for that path set, which never decreases.  S_l is the s of the loop's last sample.
+ *     field_loops (n_fields + 1, ending at n_loops): field f is served by the loops field_loops[f] .. field_loops[f + 1].  A loop is closed
+ *     and driven FORWARDS only, in its sample order; pass the direction = +1 and direction = -1 loops as two loops to offer both.
+ *   - Stations: the samples of a loop with local index k mod stride == 0 (stride >= 1), part 0 or 4 (a straight element, a followed arc:
+ *     never a corner connector) and gear +1.  The station's pose is the sample's (x, y, heading).
+ *   - in_i: the len fcpp_conn_solve_clear gives for P -> station i against region field pair_field[p]; out_j the same for station j -> Q.
+ *     +inf unless rank >= 0.  Nothing is added to the geometry of a connector.
+ *   - ride(i, j) = fl(s_j - s_i) for j >= i, fl(fl(S_l - s_i) + s_j) for j < i (the ride wraps over the loop's end).  i == j is a via point.
+ *   - C = fl(fl(in_i + ride) + out_j).  The transit of a pair is the least C below +inf over (l, i, j), ties by (C, l, i, j) ascending.
+ *   - Result per pair: found (int32), loop (int64), st_i, st_j (int64: the stations' GLOBAL sample indices into the loop arrays; -1 if not
+ *     found), the two connectors' word (int32), seg (3 / 5 float64), len, rank (int32) as fcpp_conn_solve_clear writes them, ride, total
+ *     (float64; C) and status (int32).  Not found: words -1, seg, len and ride NaN, ranks -1, total +inf.
+ *   - status: 0 for a pair that is handled; FCPP_EINVAL for a pose that is not finite, a pair_field outside 0 .. n_fields - 1 (there is no
+ *     "no region" here), a region field whose status is FCPP_EINVAL, a field with a loop whose first or last s is not finite;
+ *     FCPP_EUNSUPPORTED for a field of more than FCPP_TRANSIT_MAX_STATIONS stations (raise the stride).  A pair whose field has no loop or no
+ *     station is simply not found, with status 0.
+ *   - THE RIDE IS NOT TESTED against the region: a headland pass lies inside its field by construction.  Its corner connectors (part 1)
+ *     may not, as everywhere; fcpp_validate flags that.  One loop per transit: no ride on two loops.
+ * The sampled path of a found pair (fcpp_loop_transit_counts / _fill), in this order: the in-connector sampled as fcpp_dubins_sample /
+ * fcpp_rs_sample sample it (part 1); the loop's samples i .. j copied bit for bit, through the loop's end when j < i, with part
+ * FCPP_PART_LOOP_RIDE and their own gear and kappa; the out-connector from station j's pose (part 1).  Junctions stay doubled as in the field
+ * paths.  A pair that is not found has no samples.  path_offsets (n + 1) is the CSR fcpp_curvature, fcpp_speed_plan, fcpp_validate and
+ * fcpp_trajectory take.  The counts and fill entries take the solve's outputs back as inputs; a record that names no two samples of one
+ * loop counts as not found.  Every fill output may be NULL.
+ * Launches of the solve: a wavefront per field lists its stations; the station counts are read back; the stations pass is the two passes of
+ * fcpp_conn_solve_clear on the (pair, side, station) items -- the second is skipped when the first lists nothing; the pick pass, a
+ * workgroup per pair, reduces (C, i, j) lexicographically; a lane per pair writes the result.  Temporaries: 16 B per (pair, side, station
+ * slot), the slots the batch's largest station count rounded up to 256.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, radius or spacing <= 0 or not finite,
+ * mode not 0 or 1, stride < 1; FCPP_ESIZE -- negative sizes, n or n_loops above 2^31 - 1, offsets that do not start at 0, decrease or do
+ * not end at their total, 2^36 (pair, side, station slot) items or more.  FCPP_ESIZE after the count: a transit of 2^31 samples or more.
+ * The *_host offsets: the host copy, or NULL to have it read back.  All three entries synchronise. */
+#define FCPP_TRANSIT_MAX_STATIONS 2048
+#define FCPP_PART_LOOP_RIDE 5
+int fcpp_loop_transit_solve(fcpp_ctx *ctx, int mode, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                            const double *to_x_dev, const double *to_y_dev, const double *to_h_dev, double radius, const int64_t *pair_field_dev,
+                            int64_t n_fields, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                            const double *x_dev, const double *y_dev, int64_t n_loops, const int64_t *loop_offsets_dev,
+                            const int64_t *loop_offsets_host, int64_t n_samples, const double *loop_x_dev, const double *loop_y_dev,
+                            const double *loop_h_dev, const double *loop_s_dev, const int8_t *loop_part_dev, const int8_t *loop_gear_dev,
+                            const int64_t *field_loops_dev, const int64_t *field_loops_host, int64_t stride, int32_t *found_dev, int64_t *loop_dev,
+                            int64_t *st_i_dev, int64_t *st_j_dev, int32_t *in_word_dev, double *in_seg_dev, double *in_len_dev, int32_t *in_rank_dev,
+                            int32_t *out_word_dev, double *out_seg_dev, double *out_len_dev, int32_t *out_rank_dev, double *ride_dev,
+                            double *total_dev, int32_t *status_dev);
+int fcpp_loop_transit_counts(fcpp_ctx *ctx, int mode, int64_t n, const int32_t *found_dev, const int64_t *loop_dev, const int64_t *st_i_dev,
+                             const int64_t *st_j_dev, const int32_t *in_word_dev, const double *in_seg_dev, const int32_t *out_word_dev,
+                             const double *out_seg_dev, int64_t n_loops, const int64_t *loop_offsets_dev, const int64_t *loop_offsets_host,
+                             int64_t n_samples, double spacing, int64_t *path_offsets_dev, int64_t *path_offsets_host);
+int fcpp_loop_transit_fill(fcpp_ctx *ctx, int mode, int64_t n, const double *from_x_dev, const double *from_y_dev, const double *from_h_dev,
+                           double radius, const int32_t *found_dev, const int64_t *loop_dev, const int64_t *st_i_dev, const int64_t *st_j_dev,
+                           const int32_t *in_word_dev, const double *in_seg_dev, const int32_t *out_word_dev, const double *out_seg_dev,
+                           int64_t n_loops, const int64_t *loop_offsets_dev, const int64_t *loop_offsets_host, int64_t n_samples,
+                           const double *loop_x_dev, const double *loop_y_dev, const double *loop_h_dev, const double *loop_kappa_dev,
+                           const int8_t *loop_gear_dev, double spacing, const int64_t *path_offsets_dev, const int64_t *path_offsets_host,
+                           int64_t total_samples, double *x_dev, double *y_dev, double *heading_dev, double *kappa_dev, int8_t *part_dev,
+                           int8_t *gear_dev);
+/* listed: the (pair, side, station) items the first launch of the stations pass of this context's LAST fcpp_loop_transit_solve handed to the
+ * second; word_launches: the second launches of all its calls so far (a call that lists nothing launches none).  Either may be NULL.  For
+ * tests. */
+int fcpp_ctx_loop_transit_passes(const fcpp_ctx *ctx, int64_t *listed, int64_t *word_launches);
+/* The host twin, the same bits: fcpp_loop_transit_solve's outputs (any may be NULL), path_offsets (n + 1, may be NULL) and the samples
+ * below cap (cap 0 or all six NULL: none).  Host pointers throughout.  Test infrastructure only. */
+int fcpp_debug_loop_transits(int mode, int64_t n, const double *from_x, const double *from_y, const double *from_h, const double *to_x,
+                             const double *to_y, const double *to_h, double radius, const int64_t *pair_field, int64_t n_fields,
+                             const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                             const double *y, int64_t n_loops, const int64_t *loop_offsets, int64_t n_samples, const double *loop_x,
+                             const double *loop_y, const double *loop_h, const double *loop_kappa, const double *loop_s, const int8_t *loop_part,
+                             const int8_t *loop_gear, const int64_t *field_loops, int64_t stride, double spacing, int32_t *found, int64_t *loop,
+                             int64_t *st_i, int64_t *st_j, int32_t *in_word, double *in_seg, double *in_len, int32_t *in_rank, int32_t *out_word,
+                             double *out_seg, double *out_len, int32_t *out_rank, double *ride, double *total, int32_t *status,
+                             int64_t *path_offsets, int64_t cap, double *out_x, double *out_y, double *heading, double *kappa, int8_t *part,
+                             int8_t *gear);
 
 /* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
  * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it

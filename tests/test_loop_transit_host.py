@@ -1,0 +1,271 @@
+"""CPU-side tests of the loop transits: the entries exist (header, ctypes binding, libfcpp.so; ABI version still 5), argument errors need no
+device -- and the RULE, through fcpp_debug_loop_transits (csrc/fcpp_transitfn.h over csrc/fcpp_solveclearfn.h on the host: the very
+expressions the kernels run).
+
+The oracle shares no code with the operator: in and out per station come from the existing fcpp_debug_conn_solve_clear, the minimum of the
+rule's C = fl(fl(in + ride) + out) is taken by brute force in numpy over all (l, i, j), ties by (C, l, i, j).  The twin must return the same
+(l, i, j) and the same bits for total, words and segs.  The one tolerance is the connectors' documented bound on where a connector ends,
+2^-43 (radius + straight), asserted at 1e-9 m as tests/test_field_paths_host.py asserts it.
+
+The scene (tests/loop_transit_cases.py; the figures are recorded in DESIGN.md section 8): HOLED_SQUARE (40 m, pond 12 .. 28), work area
+its inset by 3 m, W = 4, angle 0, stored order, Dubins R = 2; loops: the ring 2.5 m outside the pond in both directions."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from field_coverage_path_planning_amd import engine as E
+from tests import loop_transit_cases as C
+from tests.test_clearance_host import host_clear
+from tests.test_route_host import HOLED_SQUARE, bits, host_lengths
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = {'fcpp_loop_transit_solve': 46, 'fcpp_loop_transit_counts': 18, 'fcpp_loop_transit_fill': 34, 'fcpp_ctx_loop_transit_passes': 3,
+           'fcpp_debug_loop_transits': 53}
+P_TOL = 1e-9
+OPEN = [[(-100, -100), (100, -100), (100, 100), (-100, 100)]]
+
+
+def straight_loop(pts_per_side=10, side=9.0, part=0, x0=0.0, y0=0.0):
+    """a square loop of straight samples, counter-clockwise from (x0, y0), the corners doubled as two headings"""
+    t = np.linspace(0.0, side, pts_per_side)
+    x = np.concatenate([x0 + t, np.full_like(t, x0 + side), x0 + side - t, np.full_like(t, x0)])
+    y = np.concatenate([np.full_like(t, y0), y0 + t, np.full_like(t, y0 + side), y0 + side - t])
+    h = np.repeat([0.0, np.pi / 2, np.pi, -np.pi / 2], pts_per_side)
+    n = len(x)
+    return dict(x=x, y=y, heading=h, kappa=np.zeros(n), part=np.full(n, part, np.int8), gear=np.ones(n, np.int8))
+
+
+def check_against_oracle(mode, frm, to, radius, pf, fields, ls, stride, got=None):
+    got = C.host_transits(mode, frm, to, radius, pf, fields, ls, stride) if got is None else got
+    want = C.brute(mode, frm, to, radius, pf, fields, ls, stride)
+    for p, w in enumerate(want):
+        assert got['status'][p] == 0
+        for k in ('found', 'loop', 'st_i', 'st_j'):
+            assert got[k][p] == w[k], (k, p, got[k][p], w[k])
+        assert bits(got['total'][p]) == bits(w['total']), p
+        if not w['found']:
+            assert got['in_word'][p] == -1 and got['out_word'][p] == -1 and np.isnan(got['ride'][p]) and np.all(np.isnan(got['in_seg'][p]))
+            assert got['in_rank'][p] == -1 and got['out_rank'][p] == -1 and got['offsets'][p + 1] == got['offsets'][p]
+            continue
+        for k in ('in_word', 'out_word', 'in_rank', 'out_rank'):
+            assert got[k][p] == w[k], (k, p)
+        for k in ('in_seg', 'out_seg', 'in_len', 'out_len'):
+            assert np.array_equal(bits(got[k][p]), bits(w[k])), (k, p)
+    return got
+
+
+def check_consequences(mode, frm, to, radius, pf, fields, ls, got, true_s=True):
+    frm, to = np.asarray(frm, dtype=np.float64).reshape(-1, 3), np.asarray(to, dtype=np.float64).reshape(-1, 3)
+    hit = np.flatnonzero(got['found'] == 1)
+    if len(hit) == 0:
+        return
+    pose = np.column_stack([ls['x'], ls['y'], ls['heading']])
+    fld = np.broadcast_to(np.asarray(pf, dtype=np.int64), (len(frm),))[hit]
+    # both connectors are clear by the existing clearance twin
+    assert np.all(host_clear(mode, frm[hit], radius, got['in_word'][hit], got['in_seg'][hit], fld, fields)['clear'])
+    assert np.all(host_clear(mode, pose[got['st_j'][hit]], radius, got['out_word'][hit], got['out_seg'][hit], fld, fields)['clear'])
+    # no transit beats the pair's shortest word (where s is the loops' arc length)
+    assert not true_s or np.all(got['total'][hit] >= host_lengths(frm[hit], to[hit], radius, mode))
+    off = got['offsets']
+    for p in hit:
+        sl = slice(int(off[p]), int(off[p + 1]))
+        part = got['p_part'][sl]
+        ride = np.flatnonzero(part == L.PART_LOOP_RIDE)
+        l, i, j = int(got['loop'][p]), int(got['st_i'][p]), int(got['st_j'][p])
+        g0, g1 = int(ls['off'][l]), int(ls['off'][l + 1])
+        idx = np.arange(i, j + 1) if j >= i else np.concatenate([np.arange(i, g1), np.arange(g0, j + 1)])
+        assert len(ride) == len(idx) and np.all(np.diff(ride) == 1)
+        assert np.all(part[:ride[0]] == 1) and np.all(part[ride[-1] + 1:] == 1) and ride[0] > 0 and ride[-1] < len(part) - 1
+        for k in ('x', 'y', 'heading', 'kappa', 'gear'):
+            assert np.array_equal(got['p_' + k][sl][ride].view(np.uint8), np.ascontiguousarray(ls[k][idx]).view(np.uint8)), (k, p)
+        # ends: P and Q within the connectors' bound; junctions doubled
+        x, y = got['p_x'][sl], got['p_y'][sl]
+        assert np.hypot(x[0] - frm[p, 0], y[0] - frm[p, 1]) == 0.0
+        assert np.hypot(x[-1] - to[p, 0], y[-1] - to[p, 1]) < P_TOL
+        assert np.hypot(x[ride[0] - 1] - x[ride[0]], y[ride[0] - 1] - y[ride[0]]) < P_TOL
+        assert np.hypot(x[ride[-1] + 1] - x[ride[-1]], y[ride[-1] + 1] - y[ride[-1]]) == 0.0
+
+
+# ---- 1. the entries --------------------------------------------------------------------------------------------------------------------
+def test_entries_are_declared_bound_and_exported():
+    lib = L.load()
+    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
+    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    assert re.search(r'#define FCPP_TRANSIT_MAX_STATIONS %d\b' % L.TRANSIT_MAX_STATIONS, header) and L.TRANSIT_MAX_STATIONS >= 1024
+    assert re.search(r'#define FCPP_PART_LOOP_RIDE %d\b' % L.PART_LOOP_RIDE, header) and L.PART_LOOP_RIDE == 5
+    bound = {name: args for name, _, args in L.PROTOTYPES}
+    for name, n_args in ENTRIES.items():
+        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
+        assert m, name
+        assert len(m.group(1).split(',')) == n_args == len(bound[name]), (name, len(m.group(1).split(',')), len(bound[name]))
+        assert hasattr(lib, name)
+    import dataclasses
+    import inspect
+    assert 'loops' in inspect.signature(E.field_paths).parameters and 'detour' in inspect.signature(E.plan_polygon_fields).parameters
+    assert list(inspect.signature(E.loop_transits).parameters) == ['from_poses', 'to_poses', 'fields', 'pair_field', 'loops', 'radius', 'reversing',
+                                                                    'station_step', 'device']
+    assert all(hasattr(E.FieldPaths, k) and getattr(E.FieldPaths, k) is None for k in ('detoured', 'leg_transit', 'transits'))
+    assert 'transits' in [f.name for f in dataclasses.fields(E.PolygonPlan)] and hasattr(E.LoopTransits, 'paths')
+    with pytest.raises(ValueError):
+        E.plan_polygon_fields([HOLED_SQUARE], 4.0, 2.0, 0.5, [0.0], detour=True)
+
+
+# ---- 2. the scene ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('mode', [0, 1])
+def test_scene_against_the_oracle(mode):
+    sc = C.scene(mode)
+    b = sc['blocked']
+    if mode == 0:
+        assert len(b) >= 1
+    got = check_against_oracle(mode, sc['frm'][b], sc['to'][b], C.SCENE_R, 0, sc['region'], sc['ls'], C.SCENE_STRIDE)
+    check_consequences(mode, sc['frm'][b], sc['to'][b], C.SCENE_R, 0, sc['region'], sc['ls'], got)
+    print('mode', mode, 'blocked', len(b), 'found', int(got['found'].sum()), 'totals', got['total'])
+    if mode == 0:
+        assert got['found'].sum() >= 1
+
+
+def test_scene_blocked_falls_by_detoured():
+    """the splice field_paths(loops=...) does, restated on the host twin's results: every rank -1 leg with a found transit is no longer
+    blocked, and fcpp_debug_conn_clear says none of the new connectors is blocked"""
+    sc = C.scene(0)
+    b = sc['blocked']
+    plain_blocked = int(sc['plain']['blocked'][0])
+    assert plain_blocked == len(b) >= 1
+    got = C.host_transits(0, sc['frm'][b], sc['to'][b], C.SCENE_R, 0, sc['region'], sc['ls'], C.SCENE_STRIDE)
+    detoured = int(got['found'].sum())
+    assert detoured >= 1 and plain_blocked - detoured == int(np.sum(got['found'] == 0))
+    hit = got['found'] == 1
+    pose = np.column_stack([sc['ls']['x'], sc['ls']['y'], sc['ls']['heading']])
+    c_in = host_clear(0, sc['frm'][b][hit], C.SCENE_R, got['in_word'][hit], got['in_seg'][hit], 0, sc['region'])
+    c_out = host_clear(0, pose[got['st_j'][hit]], C.SCENE_R, got['out_word'][hit], got['out_seg'][hit], 0, sc['region'])
+    assert np.all(c_in['clear']) and np.all(c_out['clear']) and np.all(c_in['crossings'] == 0) and np.all(c_out['crossings'] == 0)
+
+
+# ---- 3. edge cases -----------------------------------------------------------------------------------------------------------------------
+def test_wrap_via_point_and_both_stride_rounds():
+    loop = straight_loop()
+    frm = [(-3.0, 6.0, -np.pi / 2), (-5.0, 0.0, 0.0), (4.0, -4.0, np.pi / 2)]
+    to = [(6.0, -3.0, 0.0), (14.0, 0.0, 0.0), (4.0, 14.0, np.pi / 2)]
+    # the loop's own arc length: in the open a via point is never beaten
+    ls = C.pack_loops([(0, loop)], 1)
+    for stride in (1, 3):
+        got = check_against_oracle(0, frm, to, 1.0, 0, OPEN, ls, stride)
+        check_consequences(0, frm, to, 1.0, 0, OPEN, ls, got)
+        assert np.all(got['found'] == 1) and np.all(got['st_i'] % stride == 0) and np.all(got['st_j'] % stride == 0)
+    # s is an input: on a loop that is cheap to ride (a hundredth of its length) P gets on where it is, on the last side, and the ride
+    # wraps over the loop's end to the first side, where Q is
+    cheap = C.pack_loops([(0, loop)], 1, s=lambda off, x, y: 0.01 * C.arc_length(off, x, y))
+    for stride in (1, 3):
+        got = check_against_oracle(0, frm, to, 1.0, 0, OPEN, cheap, stride)
+        check_consequences(0, frm, to, 1.0, 0, OPEN, cheap, got, true_s=False)
+        i, j = int(got['st_i'][0]), int(got['st_j'][0])
+        assert j < i, 'the first pair wraps'
+        S = cheap['s'][-1]
+        assert bits(got['ride'][0]) == bits((S - cheap['s'][i]) + cheap['s'][j])
+    # a via point: i == j where a single station is all there is
+    got = check_against_oracle(0, frm, to, 1.0, 0, OPEN, ls, 1000)
+    assert np.all(got['found'] == 1) and np.all(got['st_i'] == 0) and np.all(got['st_j'] == 0) and np.all(got['ride'] == 0.0)
+    check_consequences(0, frm, to, 1.0, 0, OPEN, ls, got)
+
+
+def test_fields_without_loops_or_stations_and_bad_inputs():
+    loop, conn = straight_loop(), straight_loop(part=1)
+    fields = OPEN + OPEN + OPEN + [[[(0, 0), (9, 0), (np.nan, 9)]]] + OPEN
+    # field 0: a loop; field 1: none; field 2: a loop of connector samples only; field 3: a bad region; field 4: a loop whose s is not finite
+    ls = C.pack_loops([(0, loop), (2, conn), (3, loop), (4, loop)], 5)
+    ls['s'][ls['off'][4] - 1] = np.nan
+    frm = np.array([(-5.0, 0.0, 0.0)] * 6 + [(np.nan, 0.0, 0.0), (-5.0, 0.0, np.inf)])
+    to = np.array([(14.0, 0.0, 0.0)] * 8)
+    pf = np.array([0, 1, 2, 3, 4, 7, 0, 0])
+    got = C.host_transits(0, frm, to, 1.0, pf, fields, ls, 2)
+    assert list(got['status']) == [0, 0, 0, L.EINVAL, L.EINVAL, L.EINVAL, L.EINVAL, L.EINVAL]
+    assert list(got['found']) == [1, 0, 0, 0, 0, 0, 0, 0]
+    miss = got['found'] == 0
+    assert np.all(got['loop'][miss] == -1) and np.all(got['st_i'][miss] == -1) and np.all(got['st_j'][miss] == -1)
+    assert np.all(np.isinf(got['total'][miss])) and np.all(np.diff(got['offsets'])[miss] == 0)
+    check_against_oracle(0, frm[:3], to[:3], 1.0, pf[:3], fields, ls, 2)
+    # gear -1 samples are no stations either
+    back = dict(loop, gear=np.full(len(loop['x']), -1, np.int8))
+    got = C.host_transits(0, frm[:1], to[:1], 1.0, 0, OPEN, C.pack_loops([(0, back)], 1), 1)
+    assert got['found'][0] == 0 and got['status'][0] == 0
+
+
+def test_station_cap():
+    n = L.TRANSIT_MAX_STATIONS + 1
+    t = np.linspace(0.0, 50.0, n)
+    line = dict(x=t, y=np.zeros(n), heading=np.zeros(n), kappa=np.zeros(n), part=np.zeros(n, np.int8), gear=np.ones(n, np.int8))
+    ls = C.pack_loops([(0, line)], 1)
+    frm, to = [(-5.0, 0.0, 0.0)], [(60.0, 0.0, 0.0)]
+    got = C.host_transits(0, frm, to, 1.0, 0, OPEN, ls, 1)
+    assert got['status'][0] == L.EUNSUPPORTED and got['found'][0] == 0 and np.isinf(got['total'][0])
+    got = C.host_transits(0, frm, to, 1.0, 0, OPEN, ls, 2)          # (1025 stations)
+    assert got['status'][0] == 0 and got['found'][0] == 1
+
+
+def test_reeds_shepp_small():
+    ls = C.pack_loops([(0, straight_loop())], 1)
+    frm, to = [(-3.0, 6.0, np.pi / 2), (4.0, -4.0, -np.pi / 2)], [(6.0, -3.0, np.pi), (4.0, 14.0, np.pi / 2)]
+    got = check_against_oracle(1, frm, to, 1.5, 0, OPEN, ls, 3)
+    check_consequences(1, frm, to, 1.5, 0, OPEN, ls, got)
+    assert np.all(got['found'] == 1)
+
+
+def test_second_round_cases_reach_the_rounds_they_are_named_for():
+    """the inputs of tests/test_gpu_loop_transit.py's second-round cases, asserted on the CPU: the station counts sit at the kernels'
+    workgroup and tile size (L.TRANSIT_BLOCK; a wavefront's 64 samples a step is below it), the first launch of the stations pass lists more
+    items than one workgroup of the second holds, the region has one edge more than a chunk, the batch more pairs than a workgroup"""
+    from tests.test_solve_clear_host import host_solve_clear
+    assert L.TRANSIT_BLOCK == 256 and L.TRANSIT_MAX_STATIONS > 2 * L.TRANSIT_BLOCK + 1
+    for mode in (0, 1):
+        for stations in (L.TRANSIT_BLOCK - 1, L.TRANSIT_BLOCK, L.TRANSIT_BLOCK + 1, 2 * L.TRANSIT_BLOCK + 1):
+            fields, ls, frm, to = C.second_round_case(mode, stations)
+            assert len(ls['x']) == stations and np.all(ls['part'] == 0) and np.all(ls['gear'] == 1) and np.all(np.diff(ls['s']) > 0)
+            got = C.host_transits(mode, frm, to, 1.5, 0, fields, ls, 1, paths=False)
+            assert np.all(got['status'] == 0) and got['found'].sum() >= 1
+        # the connectors whose shortest word starts inside and crosses are the listed ones: a rank above 0 is among them
+        pose = np.column_stack([ls['x'], ls['y'], ls['heading']])
+        listed = sum(int((host_solve_clear(mode, np.tile(p, (len(pose), 1)), pose, 1.5, 0, fields)['rank'] > 0).sum()) for p in frm)
+        assert listed > 64
+    fields, ls, frm, to = C.chunk_plus_one_case()
+    assert sum(len(r) for r in fields[0]) == L.CLEAR_EDGE_CHUNK + 1
+    fields, ls, frm, to = C.many_pairs_case()
+    assert len(frm) == L.TRANSIT_BLOCK + 1
+    got = C.host_transits(0, frm, to, 1.5, 0, fields, ls, 1)
+    assert got['found'].sum() > L.TRANSIT_BLOCK and np.all(np.diff(got['offsets'])[got['found'] == 1] > 0)
+    check_against_oracle(0, frm[:6], to[:6], 1.5, 0, fields, ls, 1)
+
+
+# ---- 4. errors of the call ---------------------------------------------------------------------------------------------------------------
+def test_argument_errors():
+    ls = C.pack_loops([(0, straight_loop())], 1)
+    frm, to = [(-5.0, 0.0, 0.0)], [(14.0, 0.0, 0.0)]
+    def call(expect, radius=1.0, stride=1, spacing=0.5, **kw):
+        return C.host_transits(0, frm, to, radius, 0, OPEN, ls, stride, spacing=spacing, expect=expect, paths=False, **kw)
+
+    assert call(0)['found'][0] == 1
+    for kw in (dict(fx=None), dict(fy=None), dict(fh=None), dict(tx=None), dict(ty=None), dict(th=None), dict(pf=None), dict(ro=None), dict(vo=None),
+               dict(rx=None), dict(ry=None), dict(loff=None), dict(field_loops=None), dict(loop_x=None), dict(loop_y=None), dict(loop_heading=None),
+               dict(loop_kappa=None), dict(loop_s=None), dict(loop_part=None), dict(loop_gear=None), dict(radius=0.0), dict(radius=np.nan), dict(radius=-1.0),
+               dict(radius=np.inf), dict(spacing=0.0), dict(spacing=np.nan), dict(spacing=np.inf), dict(stride=0), dict(stride=-3)):
+        call(L.EINVAL, **kw)
+    assert L.load().fcpp_debug_loop_transits(2, *([0] * 52)) == L.EINVAL          # (mode)
+    n_s = len(ls['x'])
+    for kw in (dict(n=-1), dict(n_fields=-1), dict(n_rings=-1), dict(n_verts=-1), dict(n_loops=-1), dict(n_samples=-1), dict(cap=-1),
+               dict(loff=np.array([1, n_s], np.int64)), dict(loff=np.array([0, n_s - 1], np.int64)), dict(n_loops=2, loff=np.array([0, n_s + 1, n_s], np.int64)),
+               dict(field_loops=np.array([0, 2], np.int64)), dict(field_loops=np.array([1, 1], np.int64)), dict(ro=np.array([0, 2], np.int64)),
+               dict(vo=np.array([0, 3], np.int64)), dict(n_samples=n_s + 1)):
+        call(L.ESIZE, **kw)
+    # any output may be NULL
+    got = C.host_transits(0, frm, to, 1.0, 0, OPEN, ls, 1, paths=False, drop=('found', 'in_seg', 'total', 'status', 'offsets'))
+    assert got['found'][0] == -9 and got['loop'][0] == 0 and got['total'][0] == -9
+    # no pairs
+    assert C.host_transits(0, np.zeros((0, 3)), np.zeros((0, 3)), 1.0, np.zeros(0, np.int64), OPEN, ls, 1)['offsets'][0] == 0
+    # the device entries need a context
+    lib = L.load()
+    assert lib.fcpp_loop_transit_solve(None, *([0] * 45)) == L.EINVAL
+    assert lib.fcpp_loop_transit_counts(None, *([0] * 17)) == L.EINVAL
+    assert lib.fcpp_loop_transit_fill(None, *([0] * 33)) == L.EINVAL
+    assert lib.fcpp_ctx_loop_transit_passes(None, None, None) == L.EINVAL
