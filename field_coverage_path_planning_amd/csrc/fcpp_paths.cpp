@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset, the swath router, the connector clearance, the field paths, the headland paths and the polygon coverage.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router, the connector clearance, the field paths, the headland paths, the polygon coverage and its regions.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -20,6 +20,8 @@
 #include "fcpp_parallel.h"
 #include "fcpp_pcover.h"
 #include "fcpp_pcoverfn.h"
+#include "fcpp_regionfn.h"
+#include "fcpp_regions.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
 #include "fcpp_solveclear.h"
@@ -2256,6 +2258,173 @@ int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_r
                               first.data(), cross.data(), cnt);
         });
     } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    return FCPP_OK;
+}
+
+}  // extern "C"
+
+// ---- coverage regions (fcpp_regions.hip; the rule: fcpp_regionfn.h) ---------------------------------------------------------------------
+namespace {
+// The grids of a call on the host, checked before any kernel runs: the fields' dims and cell offsets (the caller's host copy, or read
+// back), and what the kernels place their work by: the fields' first tiles and first numbering blocks.
+struct RegionTables {
+    std::vector<RegionDims> dims;
+    std::vector<int64_t> cells, tile_first, block_first;
+};
+
+int region_tables(fcpp_ctx *c, int64_t n, const void *dims, const int64_t *cell_offsets, const int64_t *cell_offsets_host, RegionTables &T)
+{
+    if (n < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    try {
+        T.dims.resize((size_t)n); T.cells.assign((size_t)n + 1, 0); T.tile_first.assign((size_t)n + 1, 0); T.block_first.assign((size_t)n + 1, 0);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (c) {
+        if (n > 0) HIPCHK(hipMemcpyAsync(T.dims.data(), dims, (size_t)n * sizeof(RegionDims), hipMemcpyDeviceToHost, c->stream));
+        if (!cell_offsets_host) HIPCHK(hipMemcpyAsync(T.cells.data(), cell_offsets, T.cells.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (cell_offsets_host) memcpy(T.cells.data(), cell_offsets_host, T.cells.size() * sizeof(int64_t));
+    } else {
+        if (n > 0) memcpy(T.dims.data(), dims, (size_t)n * sizeof(RegionDims));
+        memcpy(T.cells.data(), cell_offsets, T.cells.size() * sizeof(int64_t));
+    }
+    if (T.cells[0] != 0) return fail(FCPP_ESIZE, "cell_offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t nx = T.dims[(size_t)i].nx, ny = T.dims[(size_t)i].ny, nc = T.cells[(size_t)i + 1] - T.cells[(size_t)i];
+        if (nc < 0) return fail(FCPP_ESIZE, "cell_offsets must be non-decreasing");
+        if (nx < 0 || ny < 0 || nx > REGION_MAX_CELLS || ny > REGION_MAX_CELLS || nx * ny > REGION_MAX_CELLS)
+            return fail(FCPP_ESIZE, "a field's grid is negative or has more than 2^28 cells");
+        if (nx * ny != nc) return fail(FCPP_ESIZE, "cell_offsets disagree with dims: a field's cells are not nx ny");
+        T.tile_first[(size_t)i + 1] = T.tile_first[(size_t)i] + ((nx + REGION_TILE - 1) / REGION_TILE) * ((ny + REGION_TILE - 1) / REGION_TILE);
+        T.block_first[(size_t)i + 1] = T.block_first[(size_t)i] + (nc + REGION_BLOCK_CELLS - 1) / REGION_BLOCK_CELLS;
+    }
+    if (T.tile_first[(size_t)n] > INT32_MAX || T.block_first[(size_t)n] > INT32_MAX) return fail(FCPP_ESIZE, "2^31 tiles or numbering blocks or more");
+    return FCPP_OK;
+}
+
+// region offsets on the host, checked: start at 0, never decrease, end at n_regions
+int region_offsets_check(const std::vector<int64_t> &ro, int64_t n, int64_t n_regions)
+{
+    if (ro[0] != 0) return fail(FCPP_ESIZE, "region_offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (ro[(size_t)i + 1] < ro[(size_t)i]) return fail(FCPP_ESIZE, "region_offsets must be non-decreasing");
+    if (ro[(size_t)n] != n_regions) return fail(FCPP_ESIZE, "n_regions is not the total of region_offsets");
+    return FCPP_OK;
+}
+
+// the seam kernel's launch: workgroups per compute unit of the context's device (each strides over the seam lanes)
+int region_seam_blocks(const fcpp_ctx *c) { return 4 * (c->n_cu > 0 ? c->n_cu : 64); }
+
+struct RegionDevice {
+    DevBuf<int64_t> tile_first, block_first, block_count, block_prefix, err;
+    RegionFields F;
+    int upload(fcpp_ctx *c, const RegionTables &T, const void *dims, const int64_t *cell_offsets)
+    {
+        HIPCHK(tile_first.upload(T.tile_first, c->stream));
+        HIPCHK(block_first.upload(T.block_first, c->stream));
+        HIPCHK(block_count.alloc((size_t)T.block_first.back()));
+        HIPCHK(block_prefix.alloc((size_t)T.block_first.back() + 1));
+        HIPCHK(err.alloc(1));
+        F = { (const RegionDims *)dims, cell_offsets, tile_first.p, block_first.p };
+        return FCPP_OK;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int fcpp_cover_regions_counts(fcpp_ctx *c, int64_t n, const void *dims, const int64_t *cell_offsets, const int64_t *cell_offsets_host,
+                              const uint8_t *grid, int mask, int value, int connectivity, int32_t *labels, int64_t *region_offsets,
+                              int64_t *region_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && !dims) || !cell_offsets || !region_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    if (!region_args_ok(mask, value, connectivity))
+        return fail(FCPP_EINVAL, "mask and value must lie in 0 .. 255 with value & ~mask == 0, connectivity must be 4 or 8");
+    HIPCHK(hipSetDevice(c->device));
+    RegionTables T;
+    int rc = region_tables(c, n, dims, cell_offsets, cell_offsets_host, T);
+    if (rc) return rc;
+    if (T.cells[(size_t)n] > 0 && (!grid || !labels)) return fail(FCPP_EINVAL, "bad arguments");
+    hipStream_t st = c->stream;
+    RegionDevice D;
+    rc = D.upload(c, T, dims, cell_offsets);
+    if (rc) return rc;
+    const int64_t n_tiles = T.tile_first[(size_t)n], n_blocks = T.block_first[(size_t)n];
+    LAUNCHCHK(launch_region_tiles(st, n, n_tiles, D.F, grid, mask, value, connectivity, labels));
+    LAUNCHCHK(launch_region_seams(st, n, n_tiles, D.F, connectivity, labels, region_seam_blocks(c)));
+    LAUNCHCHK(launch_region_count(st, n, n_blocks, D.F, 1, labels, D.block_count.p));
+    LAUNCHCHK(launch_region_offsets(st, n, n_blocks, D.F, D.block_count.p, D.block_prefix.p, D.err.p, region_offsets));
+    if (region_offsets_host)
+        HIPCHK(hipMemcpyAsync(region_offsets_host, region_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));          // (the tables die here)
+    return FCPP_OK;
+}
+
+// Like the cover call, the fill call RECOMPUTES what it needs (the roots' ranks) from its inputs: nothing is kept in the context.
+int fcpp_cover_regions_fill(fcpp_ctx *c, int64_t n, const void *dims, const int64_t *cell_offsets, const int64_t *cell_offsets_host, int32_t *labels,
+                            const int64_t *region_offsets, const int64_t *region_offsets_host, int64_t n_regions, void *records)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && !dims) || !cell_offsets || !region_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    if (n_regions < 0) return fail(FCPP_ESIZE, "bad sizes");
+    HIPCHK(hipSetDevice(c->device));
+    RegionTables T;
+    int rc = region_tables(c, n, dims, cell_offsets, cell_offsets_host, T);
+    if (rc) return rc;
+    if ((T.cells[(size_t)n] > 0 && !labels) || (n_regions > 0 && !records)) return fail(FCPP_EINVAL, "bad arguments");
+    hipStream_t st = c->stream;
+    std::vector<int64_t> ro;
+    try { ro.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (region_offsets_host) memcpy(ro.data(), region_offsets_host, ro.size() * sizeof(int64_t));
+    else {
+        HIPCHK(hipMemcpyAsync(ro.data(), region_offsets, ro.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    rc = region_offsets_check(ro, n, n_regions);
+    if (rc) return rc;
+    RegionDevice D;
+    rc = D.upload(c, T, dims, cell_offsets);
+    if (rc) return rc;
+    const int64_t n_blocks = T.block_first[(size_t)n];
+    if (n_regions > 0) HIPCHK(hipMemsetAsync(records, 0, (size_t)n_regions * sizeof(RegionRecord), st));
+    LAUNCHCHK(launch_region_count(st, n, n_blocks, D.F, 0, labels, D.block_count.p));
+    LAUNCHCHK(launch_region_offsets(st, n, n_blocks, D.F, D.block_count.p, D.block_prefix.p, D.err.p, nullptr));
+    LAUNCHCHK(launch_region_first(st, n, n_blocks, D.F, labels, D.block_prefix.p, region_offsets, (RegionRecord *)records));
+    LAUNCHCHK(launch_region_fill(st, n, n_blocks, D.F, labels, region_offsets, (RegionRecord *)records));
+    HIPCHK(hipStreamSynchronize(st));          // (the tables die here)
+    return FCPP_OK;
+}
+
+int fcpp_debug_cover_regions(int64_t n, const void *dims, const int64_t *cell_offsets, const uint8_t *grid, int mask, int value, int connectivity,
+                             int64_t *region_offsets, int64_t region_cap, void *records, int32_t *labels_counts, int32_t *labels_fill)
+{
+    if ((n > 0 && !dims) || !cell_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    if (!region_args_ok(mask, value, connectivity))
+        return fail(FCPP_EINVAL, "mask and value must lie in 0 .. 255 with value & ~mask == 0, connectivity must be 4 or 8");
+    if (region_cap < 0) return fail(FCPP_ESIZE, "bad sizes");
+    RegionTables T;
+    const int rc = region_tables(nullptr, n, dims, cell_offsets, nullptr, T);
+    if (rc) return rc;
+    if (T.cells[(size_t)n] > 0 && !grid) return fail(FCPP_EINVAL, "bad arguments");
+    std::vector<std::vector<RegionRecord>> per;
+    std::vector<int64_t> ro;
+    // fields to the library's host threads: every field writes only its own records and labels
+    try {
+        per.resize((size_t)n); ro.assign((size_t)n + 1, 0);
+        WorkerPool::parallel_for(n, [&](int64_t i) {
+            const int64_t nx = T.dims[(size_t)i].nx, ny = T.dims[(size_t)i].ny, at = T.cells[(size_t)i];
+            if (nx * ny == 0) return;
+            std::vector<int32_t> parent((size_t)(nx * ny));
+            region_field_host(grid + at, nx, ny, mask, value, connectivity, parent.data(), labels_counts ? labels_counts + at : nullptr,
+                              labels_fill ? labels_fill + at : nullptr, per[(size_t)i]);
+        });
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    for (int64_t i = 0; i < n; ++i) ro[(size_t)i + 1] = ro[(size_t)i] + (int64_t)per[(size_t)i].size();
+    if (region_offsets) memcpy(region_offsets, ro.data(), ro.size() * sizeof(int64_t));
+    if (records && ro[(size_t)n] <= region_cap)
+        for (int64_t i = 0; i < n; ++i)
+            if (!per[(size_t)i].empty())
+                memcpy((RegionRecord *)records + ro[(size_t)i], per[(size_t)i].data(), per[(size_t)i].size() * sizeof(RegionRecord));
     return FCPP_OK;
 }
 

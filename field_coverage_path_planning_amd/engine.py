@@ -2328,6 +2328,10 @@ class PolygonCoverage:
         nx, ny = (int(v) for v in self.dims[i, 2:].tolist())
         return self.cells[int(self.cell_offsets_host[i]):int(self.cell_offsets_host[i + 1])].view(ny, nx)
 
+    def regions(self, **kw):
+        """coverage_regions(self, **kw): the connected patches of one kind of cell (want_grid=True)"""
+        return coverage_regions(self, **kw)
+
 
 def _cover_path_set(ps, first_path, dev):
     """one path set -> (offsets, offsets_host or None, x, y, path_field int64, work uint8, pass int32), all on the device"""
@@ -2416,6 +2420,107 @@ def polygon_coverage(fields, width, res, paths=(), caps='flat', want_grid=False,
     return PolygonCoverage(counts, float(res), status, dims, coff, coff_h, cells)
 
 
+# ---- coverage regions (fcpp_cover_regions_counts / _fill; the rule: include/fcpp.h) -----------------------------------------------------
+REGION_KINDS = {'missed': (3, 1), 'overlapped': (4, 4), 'spill': (3, 2), 'covered': (3, 3)}
+
+
+@dataclass
+class CoverageRegions:
+    """coverage_regions(): the connected patches of one kind of cell of every field, in ascending key (smallest cell index) per field"""
+    offsets: object             # (n + 1) int64, device: field i's KEPT regions are offsets[i] .. offsets[i + 1]; offsets_host: the numpy copy
+    offsets_host: object
+    first: object               # (k) int64: the region's key, its smallest field-local cell index b nx + a
+    cells: object               # (k) int64
+    bbox: object                # (k, 4) int32: a_min, a_max, b_min, b_max
+    sums: object                # (k, 2) int64: the sums of the members' column and row indices
+    area: object                # (k) float64: cells res^2 [m^2]
+    centroid: object            # (k, 2) float64, world metres: gx + (sum_a / cells + 0.5) res, likewise in y
+    bounds: object              # (k, 4) float64, world metres: x_min, y_min, x_max, y_max of the region's cells (gx + a_min res .. gx + (a_max + 1) res)
+    dropped: object             # (n, 2) int64: the regions below min_area that were left out, and their cells
+    kind: object                # the name, or the (mask, value) pair
+    connectivity: int
+    coverage: object            # the PolygonCoverage the regions are of
+    labels: object = None       # (total cells) int32 when asked for (want_labels): the index of the cell's region among its field's KEPT regions, -1 for a non-member, -2 for a cell of a dropped region
+
+    def field(self, i):
+        """the slice of field i's regions in first .. bounds"""
+        return slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+
+    def label_grid(self, i):
+        """field i's labels as an (ny, nx) view (want_labels=True)"""
+        if self.labels is None:
+            raise ValueError('coverage_regions(..., want_labels=True) keeps the labels')
+        cov = self.coverage
+        nx, ny = (int(v) for v in cov.dims[i, 2:].tolist())
+        return self.labels[int(cov.cell_offsets_host[i]):int(cov.cell_offsets_host[i + 1])].view(ny, nx)
+
+
+def coverage_regions(coverage, kind='missed', connectivity=4, min_area=0.0, want_labels=False, device=None):
+    """The connected regions of one kind of cell in a PolygonCoverage made with want_grid=True (fcpp_cover_regions_counts + _fill) ->
+    CoverageRegions.  kind: 'missed' (inside and not covered), 'overlapped', 'spill' (covered and not inside), 'covered', or a
+    (mask, value) pair: cell c is a member iff (cells[c] & mask) == value.  connectivity 4 or 8; neighbours exist only inside one field's
+    grid.  The device labels and numbers EVERY region; min_area [m^2] then filters the records (not the cells): the kept regions keep
+    their order, `dropped` says per field how many regions and cells were left out, and with want_labels the label grid is renumbered to
+    the kept regions (-2 for a cell of a dropped one)."""
+    torch = _torch()
+    if coverage.cells is None:
+        raise ValueError('coverage_regions needs the cells: polygon_coverage(..., want_grid=True)')
+    if isinstance(kind, str):
+        if kind not in REGION_KINDS:
+            raise ValueError('kind must be one of %s or a (mask, value) pair' % ', '.join(sorted(REGION_KINDS)))
+        mask, value = REGION_KINDS[kind]
+    else:
+        mask, value = (int(v) for v in kind)
+    if connectivity not in (4, 8):
+        raise ValueError('connectivity must be 4 or 8')
+    dev = coverage.cells.device
+    ctx = get_context(dev.index if device is None else device)
+    n = int(coverage.dims.shape[0])
+    dims, coff = coverage.dims.contiguous(), coverage.cell_offsets.contiguous()
+    coff_h = np.ascontiguousarray(coverage.cell_offsets_host, dtype=np.int64)
+    total = int(coff_h[-1])
+    labels = torch.empty(total, dtype=torch.int32, device=dev)
+    roff, roff_h = torch.empty(n + 1, dtype=torch.int64, device=dev), np.zeros(n + 1, dtype=np.int64)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_cover_regions_counts(ctx.handle, n, _ptr(dims), _ptr(coff), _host_ptr(coff_h), _ptr(coverage.cells), mask, value,
+                                              int(connectivity), _ptr(labels), _ptr(roff), _host_ptr(roff_h)))
+    k = int(roff_h[-1])
+    rec = torch.empty((k, 6), dtype=torch.int64, device=dev)          # 48 bytes per record
+    L.check(ctx.lib.fcpp_cover_regions_fill(ctx.handle, n, _ptr(dims), _ptr(coff), _host_ptr(coff_h), _ptr(labels), _ptr(roff), _host_ptr(roff_h), k,
+                                            _ptr(rec)))
+    res = float(coverage.res)
+    field_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), roff[1:] - roff[:-1], output_size=k)
+    dropped = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+    if min_area > 0.0:
+        keep = rec[:, 1].to(torch.float64) * (res * res) >= float(min_area)
+        gone = ~keep
+        dropped[:, 0].index_add_(0, field_of, gone.to(torch.int64))
+        dropped[:, 1].index_add_(0, field_of, torch.where(gone, rec[:, 1], torch.zeros_like(rec[:, 1])))
+        kept_before = torch.cumsum(keep.to(torch.int64), dim=0) - keep.to(torch.int64)
+        new_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        new_off[1:] = torch.cumsum(torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, field_of, keep.to(torch.int64)), dim=0)
+        if want_labels and k:
+            # one gather: a region's new index within its field, -2 when it was dropped; slot k serves the non-members
+            remap = torch.cat([torch.where(keep, kept_before - new_off[field_of], torch.full_like(kept_before, -2)),
+                               torch.full((1,), -1, dtype=torch.int64, device=dev)]).to(torch.int32)
+            cell_field = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), coff[1:] - coff[:-1], output_size=total)
+            slot = torch.where(labels >= 0, labels.to(torch.int64) + roff[cell_field], torch.full((1,), k, dtype=torch.int64, device=dev))
+            labels = remap[slot]
+        rec, field_of, roff = rec[keep], field_of[keep], new_off
+        roff_h = roff.cpu().numpy()
+    org = coverage.origin()[field_of]                                   # (k, 2)
+    box = rec[:, 2:4].contiguous().view(torch.int32).reshape(-1, 4)
+    cells = rec[:, 1]
+    sums = rec[:, 4:6].contiguous()
+    f64 = torch.float64
+    centroid = org + (sums.to(f64) / cells.to(f64).unsqueeze(1) + 0.5) * res
+    lo = torch.stack([box[:, 0], box[:, 2]], dim=1).to(f64)
+    hi = torch.stack([box[:, 1], box[:, 3]], dim=1).to(f64) + 1.0
+    bounds = torch.cat([org + lo * res, org + hi * res], dim=1)
+    return CoverageRegions(roff, roff_h, rec[:, 0].contiguous(), cells.contiguous(), box, sums, cells.to(f64) * (res * res), centroid, bounds, dropped,
+                           kind, int(connectivity), coverage, labels if want_labels else None)
+
+
 _drive_headland = headland_paths      # (plan_polygon_fields has a flag of that name)
 
 
@@ -2433,11 +2538,12 @@ class PolygonPlan:
     coverage: object = None             # PolygonCoverage of `fields` under paths (and headland_paths) when asked for (coverage_resolution), else None
     clearance: object = None            # FieldPathClearance of `paths` against clear_of when given, else None
     transits: object = None             # LoopTransits of the rank -1 legs of `paths` when asked for (detour=True), else None
+    missed: object = None               # CoverageRegions of the missed cells of `coverage` when asked for (missed_min_area), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
                         arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
-                        price_clear=False, detour=False):
+                        price_clear=False, detour=False, missed_min_area=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2456,7 +2562,12 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     corner connectors are neither tested nor re-shaped.  detour=True (with reshape=True and headland_paths=True; ValueError without): the
     legs for which no word is clear ride the plan's own headland loops, driven in both directions, round the obstacle
     (field_paths(loops=...)): PolygonPlan.transits is paths.transits, paths.blocked the legs that stay blocked, paths.detoured those that
-    ride.  The router does not price the transits: route.length then differs from paths.transit_length on a detoured field."""
+    ride.  The router does not price the transits: route.length then differs from paths.transit_length on a detoured field.
+    missed_min_area [m^2] (with coverage_resolution; ValueError without): the coverage keeps its cells and PolygonPlan.missed holds the
+    connected missed patches of at least that area (coverage_regions(kind='missed', min_area=...)); None: the chain makes exactly the calls
+    it makes without it."""
+    if missed_min_area is not None and coverage_resolution is None:
+        raise ValueError('missed_min_area needs coverage_resolution: the grid the missed regions are found on')
     if detour and not (reshape and headland_paths):
         raise ValueError('detour=True needs reshape=True and headland_paths=True: the loops the blocked legs ride')
     if reshape and clear_of is None:
@@ -2481,8 +2592,10 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     cov = None
     if coverage_resolution is not None:
-        cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device)
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr, paths.transits if detour else None)
+        cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device,
+                               **({} if missed_min_area is None else {'want_grid': True}))
+    missed = None if missed_min_area is None else coverage_regions(cov, kind='missed', min_area=float(missed_min_area), device=device)
+    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr, paths.transits if detour else None, missed)
 
 
 def _polys(polygons):

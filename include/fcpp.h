@@ -1124,6 +1124,44 @@ int fcpp_polygon_cover(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev
                        const int64_t *path_ids_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, uint8_t *grid_dev,
                        int64_t *counts_dev, int32_t *status_dev);
 
+/* ---- coverage regions: the missed, overlapped, spilled or covered patches of the coverage grids ------------------------------------------------
+ * Build-defined.  fcpp_polygon_cover says how much of a field a plan misses; this operator says WHERE that ground lies and in how many
+ * patches: connected-component labelling of a batch of byte grids, on the device, where the grids are.  Standalone: nothing here feeds
+ * fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_regionfn.h, one set of expressions for host and device; all integers: the same values on both, whatever the order).
+ *   - Input.  The grids exactly as fcpp_polygon_cover writes them: dims (n records of 32 bytes: gx, gy as float64; nx, ny as int64),
+ *     cell_offsets (n + 1 int64), one byte per cell, row-major [b][a].  A field with an empty grid (a failed field) has no regions; its
+ *     neighbours are unaffected.
+ *   - Members.  Cell c is a member iff (grid[c] & mask) == value, mask and value in 0 .. 255.  The named kinds: missed (mask 3, value 1:
+ *     inside and not covered), overlapped (4, 4), spill (3, 2: covered and not inside), covered (3, 3).
+ *   - Neighbours.  connectivity 4: W, E, N, S; 8: plus the four diagonals.  Neighbours exist only inside ONE field's nx x ny grid: cell
+ *     (nx - 1, b) and cell (0, b + 1) are not neighbours, nor are the last row of field i and the first row of field i + 1.
+ *   - Regions.  A region is a maximal connected set of members.  Its KEY is the smallest field-local cell index b nx + a among its cells;
+ *     the regions of a field are numbered 0, 1, .. in ascending key.  Numbering, records and labels are a function of the input alone.
+ *   - Record, 48 bytes per region, region k of field i at region_offsets[i] + k: first (int64: the key), cells (int64), a_min, a_max,
+ *     b_min, b_max (int32: the bounding box in cells), sum_a, sum_b (int64: the sums of the members' column and row indices; a field has
+ *     at most 2^28 cells, so every sum stays below 2^56).  The centroid is gx + (sum_a / cells + 0.5) res, likewise in y.  Integer atomics
+ *     only (add, min, max): order-independent.  Out of scope: second moments (they can overflow int64 on a thin grid), orientation, the
+ *     outline of a region.
+ *   - Labels, int32 per cell, the caller's array, which lives across the two calls (nothing is kept in the context): after
+ *     fcpp_cover_regions_counts a member holds its region's key, after fcpp_cover_regions_fill its region's index within its field; a
+ *     non-member holds -1 after both.
+ * fcpp_cover_regions_counts labels every cell, resolves the keys and writes the regions' CSR offsets (region_offsets_dev, n + 1; its copy
+ * to region_offsets_host, or NULL).  fcpp_cover_regions_fill writes the records (n_regions = region_offsets[n]; it zeroes them itself) and
+ * rewrites labels from keys to indices; it takes the labels and offsets of the counts call on the same grids.  cell_offsets_host,
+ * region_offsets_host of the fill: the host copies, or NULL to have them read back (the kernels read the device arrays either way).
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, mask or value outside 0 .. 255,
+ * value & ~mask non-zero, connectivity not 4 or 8; FCPP_ESIZE -- negative sizes, cell or region offsets that do not start at 0 or
+ * decrease, cell offsets that disagree with dims (nx ny against their differences), a grid of more than 2^28 cells, an n_regions that
+ * is not the region offsets' total, 2^31 tiles or more.  Inputs are never written, outputs exactly over their extent, natural alignment
+ * suffices.  Both entries synchronise. */
+int fcpp_cover_regions_counts(fcpp_ctx *ctx, int64_t n, const void *dims_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host,
+                              const uint8_t *grid_dev, int mask, int value, int connectivity, int32_t *labels_dev, int64_t *region_offsets_dev,
+                              int64_t *region_offsets_host);
+int fcpp_cover_regions_fill(fcpp_ctx *ctx, int64_t n, const void *dims_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host,
+                            int32_t *labels_dev, const int64_t *region_offsets_dev, const int64_t *region_offsets_host, int64_t n_regions,
+                            void *records_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -1310,6 +1348,14 @@ int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_r
                              int64_t total_points, const double *px, const double *py, const uint8_t *work, const int32_t *pass,
                              const int64_t *field_path_offsets, const int64_t *path_ids, void *dims, int64_t *cell_offsets, int64_t cell_cap,
                              uint8_t *grid, int64_t *counts, int32_t *status);
+/* The coverage-region rule (csrc/fcpp_regionfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device
+ * results are compared with exactly -- a sequential two-pass union-find per field over the same member and neighbour functions (the result
+ * is unique, so the order of work does not show).  Arguments and the call's errors as for fcpp_cover_regions_counts.  region_offsets
+ * (n + 1), labels_counts, labels_fill (one int32 per cell: the labels after the counts call / after the fill call): any may be NULL.
+ * records (may be NULL) is written when all regions fit in region_cap: call once with 0 for the sizes, then with them.  Fields are handed
+ * to the library's host threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_cover_regions(int64_t n, const void *dims, const int64_t *cell_offsets, const uint8_t *grid, int mask, int value, int connectivity,
+                             int64_t *region_offsets, int64_t region_cap, void *records, int32_t *labels_counts, int32_t *labels_fill);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch
