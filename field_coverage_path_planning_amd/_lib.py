@@ -211,6 +211,12 @@ PROTOTYPES = [
                                      C.c_int64] + [_VP] * 11),
     ('fcpp_cover_regions_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
     ('fcpp_cover_regions_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    ('fcpp_patch_sizes', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_double, C.c_double, C.c_double,
+                                   _VP, _VP, _VP]),
+    ('fcpp_patch_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_double, C.c_double, C.c_double,
+                                    _VP, C.c_int64, C.c_int64] + [_VP] * 5),
+    ('fcpp_patch_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_double, _VP, _VP, C.c_int64, _VP, C.c_double, C.c_double, C.c_double, _VP, C.c_int64,
+                                  C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 7),
     ('fcpp_ga_evolve', C.c_int, [_VP, C.c_int32, C.POINTER(GaConfig), _VP, _VP, _VP, _VP, C.POINTER(GaResult)]),
     ('fcpp_cover_grid', C.c_int, [_VP, C.c_int64, C.POINTER(CoverJob), C.c_int64, _VP, _VP, _VP, _VP]),
     ('fcpp_gather', C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, c_i64_p, _VP, C.c_int]),
@@ -247,6 +253,8 @@ PROTOTYPES = [
     ('fcpp_debug_polygon_cover', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int64, _VP, C.c_int64]
      + [_VP] * 8 + [C.c_int64] + [_VP] * 3),
     ('fcpp_debug_cover_regions', C.c_int, [C.c_int64, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
+    ('fcpp_debug_patch_swaths', C.c_int, [C.c_int64, _VP, _VP, C.c_double, _VP, _VP, C.c_int64, _VP, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP,
+                                          C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64] + [_VP] * 7),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
     ('fcpp_ctx_direct_steps', C.c_int, [_VP, c_i64_p, c_i64_p, c_i64_p]),
 ]

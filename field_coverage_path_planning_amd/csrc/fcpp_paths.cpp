@@ -1,6 +1,6 @@
 // fcpp_paths.cpp -- the standalone path operators of include/fcpp.h: curvature, speed plan, verify / validate and the trajectory of
 // caller-supplied paths, the Dubins and Reeds-Shepp connectors, the fixed-step samplers, the polygon swaths and the small stateless
-// operators, the polygon inset, the swath router, the connector clearance, the field paths, the headland paths, the polygon coverage and its regions.  Like fcpp_api.cpp:
+// operators, the polygon inset, the swath router, the connector clearance, the field paths, the headland paths, the polygon coverage, its regions and the patch passes over them.  Like fcpp_api.cpp:
 // argument checking, device buffers, launches; every path operator drains the context's stream before it returns.
 #include <math.h>
 #include <string.h>
@@ -18,6 +18,8 @@
 #include "fcpp_insetfn.h"
 #include "fcpp_legs.h"
 #include "fcpp_parallel.h"
+#include "fcpp_patch.h"
+#include "fcpp_patchfn.h"
 #include "fcpp_pcover.h"
 #include "fcpp_pcoverfn.h"
 #include "fcpp_regionfn.h"
@@ -2425,6 +2427,191 @@ int fcpp_debug_cover_regions(int64_t n, const void *dims, const int64_t *cell_of
         for (int64_t i = 0; i < n; ++i)
             if (!per[(size_t)i].empty())
                 memcpy((RegionRecord *)records + ro[(size_t)i], per[(size_t)i].data(), per[(size_t)i].size() * sizeof(RegionRecord));
+    return FCPP_OK;
+}
+
+}  // extern "C"
+
+// ---- patch passes (fcpp_patch.hip; the rule: fcpp_patchfn.h) ------------------------------------------------------------------------------
+namespace {
+// what every patch entry checks of its scalars and its region offsets, before any kernel runs
+int patch_call_args(fcpp_ctx *c, int64_t n, double res, double width, double margin, double join, const int64_t *region_offsets,
+                    const int64_t *region_offsets_host, int64_t n_regions, std::vector<int64_t> &ro)
+{
+    if (!patch_args_ok(res, width, margin, join))
+        return fail(FCPP_EINVAL, "res and width must be positive, 0 <= margin with width - 2 margin > 0, join >= 0, all finite");
+    if (n < 0 || n > INT32_MAX || n_regions < 0) return fail(FCPP_ESIZE, "bad sizes");
+    try { ro.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (!c || region_offsets_host) memcpy(ro.data(), region_offsets_host ? region_offsets_host : region_offsets, ro.size() * sizeof(int64_t));
+    else {
+        HIPCHK(hipMemcpyAsync(ro.data(), region_offsets, ro.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return region_offsets_check(ro, n, n_regions);
+}
+
+// the field angles on the host, checked
+int patch_angles(fcpp_ctx *c, int64_t n, const double *angle, std::vector<double> &th)
+{
+    try { th.assign((size_t)n, 0.0); } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    if (n > 0 && c) {
+        HIPCHK(hipMemcpyAsync(th.data(), angle, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } else if (n > 0) memcpy(th.data(), angle, (size_t)n * sizeof(double));
+    for (int64_t i = 0; i < n; ++i)
+        if (!patch_angle_ok(th[(size_t)i])) return fail(FCPP_EINVAL, "a field's angle is not finite or beyond 1e5 in magnitude");
+    return FCPP_OK;
+}
+
+// the runs kernel's launch: workgroups per compute unit of the context's device (each wavefront strides over the lines)
+int patch_runs_blocks(const fcpp_ctx *c) { return 4 * (c->n_cu > 0 ? c->n_cu : 64); }
+
+PatchRule patch_rule(double res, double width, double margin, double join) { return { res, width - 2.0 * margin, margin, patch_join_bins(join, res) }; }
+}  // namespace
+
+extern "C" {
+
+int fcpp_patch_sizes(fcpp_ctx *c, int64_t n, const void *dims, const int64_t *cell_offsets, const int64_t *cell_offsets_host, double res,
+                     const int32_t *labels, const int64_t *region_offsets, const int64_t *region_offsets_host, int64_t n_regions, const double *angle,
+                     double width, double margin, double join, double *frame, void *records, int64_t *totals_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && (!dims || !angle || !frame)) || !cell_offsets || !region_offsets || !totals_host) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> ro;
+    int rc = patch_call_args(c, n, res, width, margin, join, region_offsets, region_offsets_host, n_regions, ro);
+    if (rc) return rc;
+    RegionTables T;
+    rc = region_tables(c, n, dims, cell_offsets, cell_offsets_host, T);
+    if (rc) return rc;
+    if ((T.cells[(size_t)n] > 0 && !labels) || (n_regions > 0 && !records)) return fail(FCPP_EINVAL, "bad arguments");
+    std::vector<double> th;
+    rc = patch_angles(c, n, angle, th);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    DevBuf<int64_t> block_first, line_first, word_first, err;
+    HIPCHK(block_first.upload(T.block_first, st));
+    HIPCHK(line_first.alloc((size_t)n_regions + 1));
+    HIPCHK(word_first.alloc((size_t)n_regions + 1));
+    HIPCHK(err.alloc(1));
+    const PatchFields F = { (const RegionDims *)dims, cell_offsets, block_first.p, region_offsets, frame };
+    const PatchRule rule = patch_rule(res, width, margin, join);
+    if (n_regions > 0) HIPCHK(hipMemsetAsync(records, 0, (size_t)n_regions * sizeof(PatchRecord), st));
+    LAUNCHCHK(launch_patch_frame(st, n, angle, frame));
+    if (n_regions > 0) LAUNCHCHK(launch_patch_extent(st, n, T.block_first[(size_t)n], F, rule, labels, (PatchRecord *)records));
+    LAUNCHCHK(launch_patch_layout(st, n_regions, rule, (PatchRecord *)records, line_first.p, word_first.p, err.p));
+    HIPCHK(hipMemcpyAsync(totals_host, line_first.p + n_regions, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(totals_host + 1, word_first.p + n_regions, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));          // (the tables die here)
+    return FCPP_OK;
+}
+
+int fcpp_patch_counts(fcpp_ctx *c, int64_t n, const void *dims, const int64_t *cell_offsets, const int64_t *cell_offsets_host, double res,
+                      const int32_t *labels, const int64_t *region_offsets, const int64_t *region_offsets_host, int64_t n_regions, const double *frame,
+                      double width, double margin, double join, const void *records, int64_t n_lines, int64_t n_words, uint64_t *bitmap,
+                      int64_t *line_counts, int64_t *line_offsets, int64_t *swath_offsets, int64_t *swath_offsets_host)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && (!dims || !frame)) || !cell_offsets || !region_offsets || !line_offsets || !swath_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> ro;
+    int rc = patch_call_args(c, n, res, width, margin, join, region_offsets, region_offsets_host, n_regions, ro);
+    if (rc) return rc;
+    if (n_lines < 0 || n_words < 0) return fail(FCPP_ESIZE, "bad sizes");
+    RegionTables T;
+    rc = region_tables(c, n, dims, cell_offsets, cell_offsets_host, T);
+    if (rc) return rc;
+    if ((T.cells[(size_t)n] > 0 && !labels) || (n_regions > 0 && !records) || (n_words > 0 && !bitmap) || (n_lines > 0 && !line_counts))
+        return fail(FCPP_EINVAL, "bad arguments");
+    hipStream_t st = c->stream;
+    DevBuf<int64_t> block_first, err;
+    HIPCHK(block_first.upload(T.block_first, st));
+    HIPCHK(err.alloc(1));
+    const PatchFields F = { (const RegionDims *)dims, cell_offsets, block_first.p, region_offsets, frame };
+    const PatchRule rule = patch_rule(res, width, margin, join);
+    const PatchSwaths none = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
+    if (n_words > 0) HIPCHK(hipMemsetAsync(bitmap, 0, (size_t)n_words * sizeof(uint64_t), st));
+    if (n_lines > 0) HIPCHK(hipMemsetAsync(line_counts, 0, (size_t)n_lines * sizeof(int64_t), st));
+    if (n_regions > 0)
+        LAUNCHCHK(launch_patch_mark(st, n, T.block_first[(size_t)n], F, rule, labels, (const PatchRecord *)records, n_words, (unsigned long long *)bitmap));
+    LAUNCHCHK(launch_patch_runs(st, 0, n, n_regions, n_lines, n_words, F, rule, (const PatchRecord *)records, (const unsigned long long *)bitmap,
+                                line_counts, nullptr, none, patch_runs_blocks(c)));
+    LAUNCHCHK(launch_patch_offsets(st, n, n_regions, n_lines, F, (const PatchRecord *)records, line_counts, line_offsets, err.p, swath_offsets));
+    if (swath_offsets_host)
+        HIPCHK(hipMemcpyAsync(swath_offsets_host, swath_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));          // (the tables die here)
+    return FCPP_OK;
+}
+
+int fcpp_patch_fill(fcpp_ctx *c, int64_t n, const void *dims, double res, const int64_t *region_offsets, const int64_t *region_offsets_host,
+                    int64_t n_regions, const double *frame, double width, double margin, double join, const void *records, int64_t n_lines,
+                    int64_t n_words, const uint64_t *bitmap, const int64_t *line_offsets, int64_t n_swaths, double *ax, double *ay, double *bx, double *by,
+                    int32_t *line, double *length, int64_t *region)
+{
+    if (!c) return fail(FCPP_EINVAL, "context is NULL");
+    if ((n > 0 && (!dims || !frame)) || !region_offsets || !line_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int64_t> ro;
+    int rc = patch_call_args(c, n, res, width, margin, join, region_offsets, region_offsets_host, n_regions, ro);
+    if (rc) return rc;
+    if (n_lines < 0 || n_words < 0 || n_swaths < 0) return fail(FCPP_ESIZE, "bad sizes");
+    if ((n_regions > 0 && !records) || (n_words > 0 && !bitmap) || (n_swaths > 0 && (!ax || !ay || !bx || !by || !line || !length || !region)))
+        return fail(FCPP_EINVAL, "bad arguments");
+    hipStream_t st = c->stream;
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, line_offsets + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total != n_swaths) return fail(FCPP_ESIZE, "n_swaths is not the total of line_offsets");
+    const PatchFields F = { (const RegionDims *)dims, nullptr, nullptr, region_offsets, frame };
+    const PatchRule rule = patch_rule(res, width, margin, join);
+    const PatchSwaths out = { ax, ay, bx, by, length, line, region, n_swaths };
+    if (n_swaths > 0)
+        LAUNCHCHK(launch_patch_runs(st, 1, n, n_regions, n_lines, n_words, F, rule, (const PatchRecord *)records, (const unsigned long long *)bitmap,
+                                    nullptr, line_offsets, out, patch_runs_blocks(c)));
+    HIPCHK(hipStreamSynchronize(st));
+    return FCPP_OK;
+}
+
+int fcpp_debug_patch_swaths(int64_t n, const void *dims, const int64_t *cell_offsets, double res, const int32_t *labels, const int64_t *region_offsets,
+                            int64_t n_regions, const double *angle, double width, double margin, double join, double *frame, void *records,
+                            int64_t *totals, int64_t word_cap, uint64_t *bitmap, int64_t line_cap, int64_t *line_counts, int64_t *line_offsets,
+                            int64_t *swath_offsets, int64_t swath_cap, double *ax, double *ay, double *bx, double *by, int32_t *line, double *length,
+                            int64_t *region)
+{
+    if ((n > 0 && (!dims || !angle)) || !cell_offsets || !region_offsets) return fail(FCPP_EINVAL, "bad arguments");
+    std::vector<int64_t> ro;
+    int rc = patch_call_args(nullptr, n, res, width, margin, join, region_offsets, nullptr, n_regions, ro);
+    if (rc) return rc;
+    if (word_cap < 0 || line_cap < 0 || swath_cap < 0) return fail(FCPP_ESIZE, "bad sizes");
+    RegionTables T;
+    rc = region_tables(nullptr, n, dims, cell_offsets, nullptr, T);
+    if (rc) return rc;
+    if (T.cells[(size_t)n] > 0 && !labels) return fail(FCPP_EINVAL, "bad arguments");
+    std::vector<double> th;
+    rc = patch_angles(nullptr, n, angle, th);
+    if (rc) return rc;
+    PatchHost o;
+    try {
+        // fields to the library's host threads: every field writes only its own regions' keys, words, counts and swaths
+        patch_host(n, T.dims.data(), T.cells.data(), res, labels, ro.data(), th.data(), width, margin, join,
+                   [](int64_t cnt, auto fn) { WorkerPool::parallel_for(cnt, fn); }, o);
+    } catch (const std::bad_alloc &) { return fail(FCPP_ENOMEM, "out of host memory"); }
+    auto put = [](void *dst, const void *src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+    put(frame, o.frame.data(), o.frame.size() * sizeof(double));
+    put(records, o.records.data(), o.records.size() * sizeof(PatchRecord));
+    if (totals) { totals[0] = o.n_lines; totals[1] = o.n_words; totals[2] = o.n_swaths; }
+    put(swath_offsets, o.swath_offsets.data(), o.swath_offsets.size() * sizeof(int64_t));
+    if (o.n_words <= word_cap) put(bitmap, o.bitmap.data(), o.bitmap.size() * sizeof(uint64_t));
+    if (o.n_lines <= line_cap) {
+        put(line_counts, o.line_counts.data(), o.line_counts.size() * sizeof(int64_t));
+        put(line_offsets, o.line_offsets.data(), o.line_offsets.size() * sizeof(int64_t));
+    }
+    if (o.n_swaths <= swath_cap) {
+        const size_t m8 = (size_t)o.n_swaths * sizeof(double);
+        put(ax, o.ax.data(), m8); put(ay, o.ay.data(), m8); put(bx, o.bx.data(), m8); put(by, o.by.data(), m8); put(length, o.length.data(), m8);
+        put(line, o.line.data(), (size_t)o.n_swaths * sizeof(int32_t));
+        put(region, o.region.data(), (size_t)o.n_swaths * sizeof(int64_t));
+    }
     return FCPP_OK;
 }
 

@@ -2521,6 +2521,77 @@ def coverage_regions(coverage, kind='missed', connectivity=4, min_area=0.0, want
                            kind, int(connectivity), coverage, labels if want_labels else None)
 
 
+# ---- patch passes (fcpp_patch_sizes / _counts / _fill; the rule: include/fcpp.h) ---------------------------------------------------------
+@dataclass
+class PatchInfo:
+    """patch_swaths(): what the patch passes know beyond a SwathSet"""
+    region: object              # (m) int64: the global index (into the CoverageRegions' records) of every swath's region
+    n_lines: object             # (k) int64: the lines K of every region
+    n_bins: object              # (k) int64: the bins B along each of its lines
+    status: object              # (k) int32: 0, or FCPP_EUNSUPPORTED (more than 2^22 lines, or 2^31 bitmap words or more): no swaths
+    frame: object               # (n, 2) float64: sin and cos of every field's track angle
+    records: object             # (k, 8) int64: the 64-byte records as the library wrote them (u_min, w_lo as float64 bits, K, B, first line, first word, status, u_max)
+    margin: float
+    join: float
+
+
+def patch_swaths(regions, width, angle, margin=None, join=None, device=None):
+    """Straight working passes over every kept region of a CoverageRegions made with want_labels=True (fcpp_patch_sizes + _counts + _fill)
+    -> (SwathSet, PatchInfo).  The passes lie parallel to the field's tracks -- `angle` is a scalar or one value per field -- in strips of
+    width - 2 margin across them, centred on the region's extent; along a line they reach from the first to the last cell of every run of
+    cells, `margin` beyond both, and runs less than `join` metres apart are driven as one.  margin defaults to res / 2 (at angle 0 the
+    whole cell squares are covered), join to `width`.  Every member cell lies within (width - 2 margin) / 2 of its line and at least
+    `margin` inside a swath's ends.  The SwathSet is an ordinary one (route_swaths, field_paths, polygon_coverage take it): its status is 0
+    for every field, n_lines the lines of all the field's regions; a region the rule does not support (PatchInfo.status) has no swaths.
+    Out of scope: shifting a line inward where a sliver along the boundary makes the pass spill outside (a second polygon_coverage reports
+    the spill), an angle per region, clipping against holes beyond what `join` decides."""
+    torch = _torch()
+    if regions.labels is None:
+        raise ValueError('patch_swaths needs the labels: coverage_regions(..., want_labels=True)')
+    cov = regions.coverage
+    dev = regions.labels.device
+    ctx = get_context(dev.index if device is None else device)
+    n = int(cov.dims.shape[0])
+    res = float(cov.res)
+    margin = res / 2 if margin is None else float(margin)
+    join = float(width) if join is None else float(join)
+    ang = _dev_f64(angle, dev).reshape(-1)
+    if ang.numel() == 1 and n != 1:
+        ang = ang.expand(n).contiguous()
+    if ang.numel() != n:
+        raise ValueError('angle must be a scalar or hold one value per field')
+    dims, coff, labels, roff = cov.dims.contiguous(), cov.cell_offsets.contiguous(), regions.labels.contiguous(), regions.offsets.contiguous()
+    coff_h = np.ascontiguousarray(cov.cell_offsets_host, dtype=np.int64)
+    roff_h = np.ascontiguousarray(regions.offsets_host, dtype=np.int64)
+    k = int(roff_h[-1])
+    i64 = torch.int64
+    frame = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    rec = torch.empty((k, 8), dtype=i64, device=dev)                 # 64 bytes per record
+    totals = np.zeros(2, dtype=np.int64)
+    rule = (float(width), margin, join)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_patch_sizes(ctx.handle, n, _ptr(dims), _ptr(coff), _host_ptr(coff_h), res, _ptr(labels), _ptr(roff), _host_ptr(roff_h), k,
+                                     _ptr(ang), *rule, _ptr(frame), _ptr(rec), _host_ptr(totals)))
+    n_lines, n_words = int(totals[0]), int(totals[1])
+    bitmap, cnt = torch.empty(n_words, dtype=i64, device=dev), torch.empty(n_lines, dtype=i64, device=dev)
+    loff, soff = torch.empty(n_lines + 1, dtype=i64, device=dev), torch.empty(n + 1, dtype=i64, device=dev)
+    soff_h = np.zeros(n + 1, dtype=np.int64)
+    L.check(ctx.lib.fcpp_patch_counts(ctx.handle, n, _ptr(dims), _ptr(coff), _host_ptr(coff_h), res, _ptr(labels), _ptr(roff), _host_ptr(roff_h), k,
+                                      _ptr(frame), *rule, _ptr(rec), n_lines, n_words, _ptr(bitmap), _ptr(cnt), _ptr(loff), _ptr(soff),
+                                      _host_ptr(soff_h)))
+    m = int(soff_h[-1])
+    a, b = torch.empty((2, m), dtype=torch.float64, device=dev), torch.empty((2, m), dtype=torch.float64, device=dev)
+    line, length = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.float64, device=dev)
+    region = torch.empty(m, dtype=i64, device=dev)
+    L.check(ctx.lib.fcpp_patch_fill(ctx.handle, n, _ptr(dims), res, _ptr(roff), _host_ptr(roff_h), k, _ptr(frame), *rule, _ptr(rec), n_lines, n_words,
+                                    _ptr(bitmap), _ptr(loff), m, _ptr(a[0]), _ptr(a[1]), _ptr(b[0]), _ptr(b[1]), _ptr(line), _ptr(length), _ptr(region)))
+    field_of = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), roff[1:] - roff[:-1], output_size=k)
+    lines_of_field = torch.zeros(n, dtype=i64, device=dev).index_add_(0, field_of, rec[:, 2]).to(torch.int32)
+    status = rec[:, 6].contiguous().view(torch.int32).reshape(-1, 2)[:, 0].contiguous()
+    ss = SwathSet(soff, soff_h, a.t().contiguous(), b.t().contiguous(), line, length, torch.zeros(n, dtype=torch.int32, device=dev), lines_of_field, ang)
+    return ss, PatchInfo(region, rec[:, 2].contiguous(), rec[:, 3].contiguous(), status, frame, rec, margin, join)
+
+
 _drive_headland = headland_paths      # (plan_polygon_fields has a flag of that name)
 
 
@@ -2539,11 +2610,15 @@ class PolygonPlan:
     clearance: object = None            # FieldPathClearance of `paths` against clear_of when given, else None
     transits: object = None             # LoopTransits of the rank -1 legs of `paths` when asked for (detour=True), else None
     missed: object = None               # CoverageRegions of the missed cells of `coverage` when asked for (missed_min_area), else None
+    patch: object = None                # SwathSet of the patch passes over `missed` when asked for (patch=True), else None
+    patch_info: object = None           # PatchInfo of `patch`
+    patch_paths: object = None          # FieldPaths over `patch`, routed per field
+    coverage_after: object = None       # PolygonCoverage of `fields` under the plan's paths AND patch_paths, its cells kept
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
                         arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
-                        price_clear=False, detour=False, missed_min_area=None):
+                        price_clear=False, detour=False, missed_min_area=None, patch=False):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2565,7 +2640,14 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     ride.  The router does not price the transits: route.length then differs from paths.transit_length on a detoured field.
     missed_min_area [m^2] (with coverage_resolution; ValueError without): the coverage keeps its cells and PolygonPlan.missed holds the
     connected missed patches of at least that area (coverage_regions(kind='missed', min_area=...)); None: the chain makes exactly the calls
-    it makes without it."""
+    it makes without it.
+    patch=True (with missed_min_area; ValueError without): the missed regions keep their labels, patch_swaths lays passes over them at
+    each field's chosen angle (PolygonPlan.patch, .patch_info), route_swaths + field_paths drive them at the same radius, spacing and
+    `reversing` (.patch_paths), and a second polygon_coverage over the plan's path sets plus the patch paths -- their pass ids are
+    leg + 2^30, apart from the first set's legs and the rings' negative ids -- says what is covered then (.coverage_after, cells kept).
+    The patch paths are not joined to the field path; patch=False: the chain makes exactly the calls it makes without it."""
+    if patch and missed_min_area is None:
+        raise ValueError('patch=True needs missed_min_area: the regions the patch passes are laid over')
     if missed_min_area is not None and coverage_resolution is None:
         raise ValueError('missed_min_area needs coverage_resolution: the grid the missed regions are found on')
     if detour and not (reshape and headland_paths):
@@ -2594,8 +2676,17 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     if coverage_resolution is not None:
         cov = polygon_coverage(fields, width, coverage_resolution, paths=(paths,) if hp is None else (paths, hp), device=device,
                                **({} if missed_min_area is None else {'want_grid': True}))
-    missed = None if missed_min_area is None else coverage_regions(cov, kind='missed', min_area=float(missed_min_area), device=device)
-    return PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr, paths.transits if detour else None, missed)
+    missed = None if missed_min_area is None else coverage_regions(cov, kind='missed', min_area=float(missed_min_area), device=device,
+                                                                   **({'want_labels': True} if patch else {}))
+    plan = PolygonPlan(lines, work, idx, chosen, ss, route, paths, hp, cov, clr, paths.transits if detour else None, missed)
+    if patch:
+        plan.patch, plan.patch_info = patch_swaths(missed, width, chosen, device=device)
+        proute = route_swaths(plan.patch, radius, reversing=reversing, spacing=spacing, device=device)
+        pp = plan.patch_paths = field_paths(plan.patch, radius, spacing, reversing=reversing, order=proute, device=device)
+        as_set = (pp.offsets, pp.x, pp.y, torch.arange(fields.n, dtype=torch.int64, device=pp.x.device), pp.part == 0, pp.leg + (1 << 30))
+        plan.coverage_after = polygon_coverage(fields, width, coverage_resolution, paths=((paths,) if hp is None else (paths, hp)) + (as_set,),
+                                               want_grid=True, device=device)
+    return plan
 
 
 def _polys(polygons):

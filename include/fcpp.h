@@ -1162,6 +1162,57 @@ int fcpp_cover_regions_fill(fcpp_ctx *ctx, int64_t n, const void *dims_dev, cons
                             int32_t *labels_dev, const int64_t *region_offsets_dev, const int64_t *region_offsets_host, int64_t n_regions,
                             void *records_dev);
 
+/* ---- patch passes: swaths over the member cells of coverage regions ------------------------------------------------------------------------------
+ * Build-defined.  fcpp_cover_regions_fill says where the missed ground lies; this operator lays straight working passes over it, parallel
+ * to the field's tracks, on the device, where the grids and labels are.  The passes come out as swath records (the SoA of fcpp_swath_fill
+ * plus the region of every swath), so the router, the field paths and a second fcpp_polygon_cover take them.  Standalone.
+ * THE RULE (csrc/fcpp_patchfn.h, one set of expressions for host and device).
+ *   - Input.  The grids as fcpp_polygon_cover writes them: dims, cell_offsets and res.  labels, int32 per cell: a value >= 0 is the
+ *     cell's region index within its field, any negative value means not a member (-1 / -2 both).  region_offsets (n + 1), one track
+ *     angle theta per field (finite, |theta| <= 1e5), width W, margin m (0 <= m, We = W - 2 m > 0), join j >= 0.
+ *   - Frame.  (s, c) = fc_sincos(theta), written per field to frame (n x 2 float64: s, c).  Cell (a, b) has the grid-local centre
+ *     x = ((double)a + 0.5) res, y = ((double)b + 0.5) res; u = x c + y s runs along the tracks, w = -x s + y c across them.  The grid
+ *     origin (gx, gy) is added only at the output.
+ *   - Extent, per region: u_min, u_max, w_min, w_max over its members; exact min / max, so the order of work does not show.
+ *   - Lines.  K = floor((w_max - w_min) / We) + 1, w_lo = w_min - (fl(K We) - (w_max - w_min)) / 2; line k lies at
+ *     w_k = w_lo + ((double)k + 0.5) We; a member belongs to line clamp(floor((w - w_lo) / We), 0, K - 1).
+ *   - Bins along a line.  h = res, B = floor((u_max - u_min) / h) + 1; a member falls in bin clamp(floor((u - u_min) / h), 0, B - 1).
+ *     Bit (region, k, q) is set iff some member falls there: line k of a region is ceil(B / 64) words of 64 bits at
+ *     first_word + k ceil(B / 64), bin q bit q mod 64 of word q / 64.  Everything after the two floors is integer work.
+ *   - Runs.  J = floor(j / h).  On a line a set bin q starts a run iff none of the bins q - J - 1 .. q - 1 is set; a run ends at the last
+ *     set bin before the next start, or at the line's last set bin.
+ *   - Swath of a run q0 .. q1 on line k: u_a = u_min + (double)q0 h - m, u_b = u_min + (double)(q1 + 1) h + m, the end points
+ *     (u c - w_k s + gx, u s + w_k c + gy), length u_b - u_a; a is the end with the smaller u.  Within a field the swaths are ordered by
+ *     region, then k, then u; `line` is the number of lines of the field's earlier regions plus k, `region` the global region index.
+ *   - Record, 64 bytes per region: u_min, w_lo (float64), K, B, first_line, first_word (int64: the lines / words of all earlier regions
+ *     of the call), status (int32), 0 (int32), u_max (float64).  status FCPP_EUNSUPPORTED for K > 2^22 or K ceil(B / 64) >= 2^31: K = B = 0,
+ *     no swaths.  A region whose label never occurs has no members, no lines and status 0.
+ *   - Guarantees: every member lies within We / 2 across its line and at least m inside a swath's ends along it (to 1e-9 m, the rounding
+ *     of w_k and u_a); with m = res / 2 the whole cell square is covered at theta = 0.
+ * Memory is the caller's, nothing is kept in the context.  fcpp_patch_sizes writes frame, the records and to totals_host[0 .. 1] the
+ * lines and 64-bit bitmap words of the call.  fcpp_patch_counts takes the caller's bitmap (n_words) and line_counts (n_lines int64), zeroed
+ * or not: it zeroes them, marks, counts the runs of every line and writes line_offsets (n_lines + 1: the swaths before every line) and
+ * swath_offsets (n + 1: the swaths before every field; its copy to swath_offsets_host, or NULL).  fcpp_patch_fill writes the n_swaths =
+ * line_offsets[n_lines] swath records, every element exactly once.  cell_offsets_host, region_offsets_host: the host copies, or NULL to
+ * have them read back.  Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, res or W not
+ * positive, m < 0, W - 2 m <= 0, j < 0, any of them or an angle not finite, |theta| > 1e5; FCPP_ESIZE -- negative sizes, offsets that do
+ * not start at 0 or decrease, cell offsets that disagree with dims, a grid of more than 2^28 cells, an n_regions or n_swaths that is not
+ * its offsets' total.  Inputs are never written, outputs exactly over their extent, natural alignment suffices.  All three synchronise. */
+int fcpp_patch_sizes(fcpp_ctx *ctx, int64_t n, const void *dims_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, double res,
+                     const int32_t *labels_dev, const int64_t *region_offsets_dev, const int64_t *region_offsets_host, int64_t n_regions,
+                     const double *angle_dev, double width, double margin, double join, double *frame_dev, void *records_dev,
+                     int64_t *totals_host);
+int fcpp_patch_counts(fcpp_ctx *ctx, int64_t n, const void *dims_dev, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, double res,
+                      const int32_t *labels_dev, const int64_t *region_offsets_dev, const int64_t *region_offsets_host, int64_t n_regions,
+                      const double *frame_dev, double width, double margin, double join, const void *records_dev, int64_t n_lines,
+                      int64_t n_words, uint64_t *bitmap_dev, int64_t *line_counts_dev, int64_t *line_offsets_dev, int64_t *swath_offsets_dev,
+                      int64_t *swath_offsets_host);
+int fcpp_patch_fill(fcpp_ctx *ctx, int64_t n, const void *dims_dev, double res, const int64_t *region_offsets_dev,
+                    const int64_t *region_offsets_host, int64_t n_regions, const double *frame_dev, double width, double margin, double join,
+                    const void *records_dev, int64_t n_lines, int64_t n_words, const uint64_t *bitmap_dev, const int64_t *line_offsets_dev,
+                    int64_t n_swaths, double *ax_dev, double *ay_dev, double *bx_dev, double *by_dev, int32_t *line_dev, double *length_dev,
+                    int64_t *region_dev);
+
 /* ---- coverage rasterisation -------------------------------------------------
  * Replaces the Shapely calls of verify_corner_coverage_grid_based (MLP:1426-1509: `LineString(path).buffer(W/2)
  * .contains(Point)` per 0.1 m grid cell of a 2R x 2R corner square, first for the turn, then for the reverse fill on
@@ -1356,6 +1407,17 @@ int fcpp_debug_polygon_cover(int64_t n, const int64_t *ring_offsets, int64_t n_r
  * to the library's host threads; the results do not depend on their number.  A diagnostic, not a fallback. */
 int fcpp_debug_cover_regions(int64_t n, const void *dims, const int64_t *cell_offsets, const uint8_t *grid, int mask, int value, int connectivity,
                              int64_t *region_offsets, int64_t region_cap, void *records, int32_t *labels_counts, int32_t *labels_fill);
+/* The patch-pass rule (csrc/fcpp_patchfn.h) evaluated on the HOST, on host pointers, sizes, counts and fill in one call: what the device
+ * results are compared with, every value equal.  Arguments and the call's errors as for fcpp_patch_sizes.  frame (2 n), records
+ * (64 bytes per region), totals (3: lines, bitmap words, swaths), swath_offsets (n + 1): any may be NULL.  bitmap is written when the
+ * words fit in word_cap, line_counts and line_offsets (lines + 1) when the lines fit in line_cap, the swath arrays when the swaths fit in
+ * swath_cap: call once with 0 for the totals, then with them.  Fields are handed to the library's host threads; the results do not depend
+ * on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_patch_swaths(int64_t n, const void *dims, const int64_t *cell_offsets, double res, const int32_t *labels, const int64_t *region_offsets,
+                            int64_t n_regions, const double *angle, double width, double margin, double join, double *frame, void *records,
+                            int64_t *totals, int64_t word_cap, uint64_t *bitmap, int64_t line_cap, int64_t *line_counts, int64_t *line_offsets,
+                            int64_t *swath_offsets, int64_t swath_cap, double *ax, double *ay, double *bx, double *by, int32_t *line,
+                            double *length, int64_t *region);
 /* One of a batch's device tables copied to the host (dst = NULL: only its size in *bytes_out): 0 field descriptors, 1 primitives, 2 tiles,
  * 3 wave tiles, 4 general tile ids, 5 chunks, 6 span chunks, 7 statistics entry -> tile, 8 first entry per field, 9 run length per entry,
  * 10 reduction lists, 11 field work, 12 open wave tile ids, 13 connector segments, 14 connector masks, 15 statistics slots (after batch

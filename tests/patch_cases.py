@@ -1,0 +1,312 @@
+"""Label grids, a numpy oracle and the host twin's call for the patch-pass tests (tests/test_patch_host.py checks the twin against the oracle;
+tests/test_gpu_patch.py the device entries against the twin on the same grids).  A grid is a (ny, nx) int32 array of labels: a value >= 0
+is the cell's region index within its field, a negative value is no member."""
+import numpy as np
+
+from field_coverage_path_planning_amd import _lib as L
+
+REC = np.dtype([('u_min', np.float64), ('w_lo', np.float64), ('K', np.int64), ('B', np.int64), ('first_line', np.int64), ('first_word', np.int64),
+                ('status', np.int32), ('zero', np.int32), ('u_max', np.float64)])
+assert REC.itemsize == 64
+W, RES = 4.0, 0.25
+ANGLES = (0.0, np.pi / 2, 0.3, -1.1)
+JOINS = (0.0, W)
+BLOCK_CELLS = 4096          # the kernels' numbering block
+RUNS_WAVES_PER_CU = 16      # the runs kernel's launch: at most 4 workgroups of 4 wavefronts per compute unit, a wavefront per line
+MI355X_CUS = 256
+MAX_LINES = 1 << 22
+SWATH_KEYS = ('ax', 'ay', 'bx', 'by', 'line', 'length', 'region')
+KEYS = ('frame', 'records', 'totals', 'bitmap', 'line_counts', 'line_offsets', 'swath_offsets') + SWATH_KEYS
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+def lab(shape, where=None, value=0):
+    """a (ny, nx) label grid: `value` where `where` (all of it when None), -1 elsewhere"""
+    g = np.full(shape, -1, np.int32)
+    g[np.ones(shape, bool) if where is None else where] = value
+    return g
+
+
+def pack(grids, n_regions=None):
+    """list of (ny, nx) int32 label grids -> dims (n, 4 int64: gx, gy as float64 bits, nx, ny), cell_offsets (n + 1), labels (flat),
+    region_offsets (n + 1).  n_regions: per field, None = its largest label + 1"""
+    n = len(grids)
+    dims = np.zeros((n, 4), np.int64)
+    dims[:, 0] = (10.0 + 3.5 * np.arange(n, dtype=np.float64)).view(np.int64)
+    dims[:, 1] = (-2.25 * np.arange(n, dtype=np.float64) - 1.0).view(np.int64)
+    for i, g in enumerate(grids):
+        dims[i, 2], dims[i, 3] = g.shape[1], g.shape[0]
+    off = np.concatenate([[0], np.cumsum([g.size for g in grids])]).astype(np.int64)
+    flat = np.concatenate([np.ascontiguousarray(g, dtype=np.int32).reshape(-1) for g in grids] + [np.zeros(0, np.int32)])
+    if n_regions is None:
+        n_regions = [int(g.max(initial=-1)) + 1 for g in grids]
+    roff = np.concatenate([[0], np.cumsum(n_regions)]).astype(np.int64)
+    return dims, off, flat, roff
+
+
+def angles_of(packed, angle):
+    n = len(packed[0])
+    return np.array(np.broadcast_to(np.asarray(angle, np.float64), (n,)), dtype=np.float64)          # (a writable copy)
+
+
+def twin(packed, angle, width=W, res=RES, margin=None, join=None, expect=0):
+    """fcpp_debug_patch_swaths -> dict of everything the three device entries write"""
+    lib = L.load()
+    dims, off, flat, roff = packed
+    n, k = len(dims), int(roff[-1])
+    margin = res / 2 if margin is None else margin
+    join = width if join is None else join
+    th = angles_of(packed, angle)
+    frame, rec, totals = np.full(2 * n, -7.0), np.zeros(k, REC), np.full(3, -7, np.int64)
+    soff = np.full(n + 1, -7, np.int64)
+    head = (n, _p(dims), _p(off), float(res), _p(flat), _p(roff), k, _p(th), float(width), float(margin), float(join))
+    rc = lib.fcpp_debug_patch_swaths(*head, _p(frame), _p(rec), _p(totals), 0, None, 0, None, None, _p(soff), 0, *([None] * 7))
+    assert rc == expect, (rc, lib.fcpp_last_error())
+    if expect:
+        return None
+    nl, nw, ms = (int(v) for v in totals)
+    bitmap, cnt, loff = np.full(nw, 7, np.uint64), np.full(nl, -7, np.int64), np.full(nl + 1, -7, np.int64)
+    f8 = lambda: np.full(ms, -7.0)
+    ax, ay, bx, by, length, line, region = f8(), f8(), f8(), f8(), f8(), np.full(ms, -7, np.int32), np.full(ms, -7, np.int64)
+    totals2 = np.zeros(3, np.int64)
+    rc = lib.fcpp_debug_patch_swaths(*head, _p(frame), _p(rec), _p(totals2), nw, _p(bitmap), nl, _p(cnt), _p(loff), _p(soff), ms, _p(ax), _p(ay), _p(bx),
+                                     _p(by), _p(line), _p(length), _p(region))
+    assert rc == 0 and np.array_equal(totals, totals2), lib.fcpp_last_error()
+    return dict(frame=frame.reshape(n, 2), records=rec, totals=totals, bitmap=bitmap, line_counts=cnt, line_offsets=loff, swath_offsets=soff,
+                ax=ax, ay=ay, bx=bx, by=by, line=line, length=length, region=region)
+
+
+def members(packed, frame, res=RES):
+    """every member of the call -> (field, global region, u, w), with the frame's bits: the expressions of the rule in float64 numpy"""
+    dims, off, flat, roff = packed
+    out = [[np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0)], [np.zeros(0)]]
+    for i in range(len(dims)):
+        nx, ny = int(dims[i, 2]), int(dims[i, 3])
+        g = flat[off[i]:off[i + 1]].reshape(ny, nx)
+        b, a = np.nonzero((g >= 0) & (g < roff[i + 1] - roff[i]))
+        s, c = frame[i]
+        x, y = (a.astype(np.float64) + 0.5) * res, (b.astype(np.float64) + 0.5) * res
+        out[0].append(np.full(len(a), i, np.int64)); out[1].append(roff[i] + g[b, a].astype(np.int64))
+        out[2].append(x * c + y * s); out[3].append(-x * s + y * c)
+    return tuple(np.concatenate(o) for o in out)
+
+
+def oracle(packed, frame, width=W, res=RES, margin=None, join=None):
+    """the rule in numpy, from the twin's frame (so u and w have the twin's bits) -> the dict twin() gives"""
+    dims, off, flat, roff = packed
+    n, k = len(dims), int(roff[-1])
+    margin = res / 2 if margin is None else margin
+    join = width if join is None else join
+    We, h = width - 2.0 * margin, res
+    J = int(min(np.floor(join / h), 2.0 ** 40))
+    fld, reg, u, w = members(packed, frame, res)
+    rec = np.zeros(k, REC)
+    ext = {name: np.full(k, v) for name, v in (('u_min', np.inf), ('u_max', -np.inf), ('w_min', np.inf), ('w_max', -np.inf))}
+    np.minimum.at(ext['u_min'], reg, u); np.maximum.at(ext['u_max'], reg, u)
+    np.minimum.at(ext['w_min'], reg, w); np.maximum.at(ext['w_max'], reg, w)
+    has = np.isfinite(ext['u_min'])
+    span = np.where(has, ext['w_max'] - ext['w_min'], 0.0)
+    Kd = np.floor(span / We) + 1.0
+    Bd = np.floor(np.where(has, ext['u_max'] - ext['u_min'], 0.0) / h) + 1.0
+    bad = has & ((Kd > MAX_LINES) | (Bd > 2.0 ** 40))
+    K, B = np.where(has & ~bad, Kd, 0).astype(np.int64), np.where(has & ~bad, Bd, 0).astype(np.int64)
+    wpl = (B + 63) // 64
+    bad |= K * wpl >= 2 ** 31
+    K[bad], B[bad], wpl[bad] = 0, 0, 0
+    rec['u_min'], rec['u_max'] = np.where(has, ext['u_min'], 0.0), np.where(has, ext['u_max'], 0.0)
+    rec['w_lo'] = np.where(K > 0, ext['w_min'] - (K.astype(np.float64) * We - span) / 2.0, 0.0)
+    rec['K'], rec['B'], rec['status'] = K, B, np.where(bad, L.EUNSUPPORTED, 0)
+    rec['first_line'] = np.cumsum(K) - K
+    rec['first_word'] = np.cumsum(K * wpl) - K * wpl
+    nl, nw = int(K.sum()), int((K * wpl).sum())
+    live = K[reg] > 0
+    fld, reg, u, w = fld[live], reg[live], u[live], w[live]
+    kk = np.clip(np.floor((w - rec['w_lo'][reg]) / We), 0, K[reg] - 1).astype(np.int64)
+    qq = np.clip(np.floor((u - rec['u_min'][reg]) / h), 0, B[reg] - 1).astype(np.int64)
+    line = rec['first_line'][reg] + kk
+    bitmap = np.zeros(nw, np.uint64)
+    np.bitwise_or.at(bitmap, rec['first_word'][reg] + kk * wpl[reg] + qq // 64, np.uint64(1) << (qq % 64).astype(np.uint64))
+    # the set bins in (line, q) order, once each
+    both = np.unique(np.stack([line, qq], axis=1), axis=0) if len(line) else np.zeros((0, 2), np.int64)
+    ln, q = both[:, 0], both[:, 1]
+    new_line = np.ones(len(ln), bool)
+    new_line[1:] = ln[1:] != ln[:-1]
+    start = new_line.copy()
+    start[1:] |= (q[1:] - q[:-1]) > J + 1
+    last = np.ones(len(ln), bool)
+    last[:-1] = start[1:]
+    cnt = np.bincount(ln[start], minlength=nl).astype(np.int64)
+    loff = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    s_line, q0, q1 = ln[start], q[start], q[last]
+    s_reg = np.searchsorted(rec['first_line'] + K, s_line, side='right')          # the region whose lines hold s_line
+    s_fld = np.searchsorted(roff, s_reg, side='right') - 1
+    first_of_field = np.concatenate([rec['first_line'], [nl]])[roff]
+    soff = loff[first_of_field]
+    wk = rec['w_lo'][s_reg] + ((s_line - rec['first_line'][s_reg]).astype(np.float64) + 0.5) * We
+    ua = rec['u_min'][s_reg] + q0.astype(np.float64) * h - margin
+    ub = rec['u_min'][s_reg] + (q1 + 1).astype(np.float64) * h + margin
+    s, c = frame[s_fld, 0], frame[s_fld, 1]
+    org = dims[:, :2].copy().view(np.float64)[s_fld]
+    return dict(frame=frame, records=rec, totals=np.array([nl, nw, len(q0)], np.int64), bitmap=bitmap, line_counts=cnt, line_offsets=loff,
+                swath_offsets=soff, ax=(ua * c - wk * s) + org[:, 0], ay=(ua * s + wk * c) + org[:, 1], bx=(ub * c - wk * s) + org[:, 0],
+                by=(ub * s + wk * c) + org[:, 1], line=(s_line - first_of_field[s_fld]).astype(np.int32), length=ub - ua, region=s_reg)
+
+
+def same(a, b):
+    """two results agree in every value (== on the float64 too); returns the first name that differs, or None"""
+    for k in KEYS:
+        x, y = np.asarray(a[k]), np.asarray(b[k])
+        if x.shape != y.shape or not np.array_equal(x, y):
+            return k
+    return None
+
+
+def cover_errors(packed, got, width=W, res=RES, margin=None):
+    """the cover property -> (worst distance across a line beyond We / 2, worst shortfall of the margin along it), over every member of a
+    supported region; both <= 1e-9 says the rule holds"""
+    margin = res / 2 if margin is None else margin
+    We = width - 2.0 * margin
+    rec = got['records']
+    fld, reg, u, w = members(packed, got['frame'], res)
+    live = rec['K'][reg] > 0
+    reg, u, w = reg[live], u[live], w[live]
+    k = np.clip(np.floor((w - rec['w_lo'][reg]) / We), 0, rec['K'][reg] - 1).astype(np.int64)
+    wk = rec['w_lo'][reg] + (k + 0.5) * We
+    across = float(np.max(np.abs(w - wk) - We / 2, initial=-np.inf))
+    # the swaths of a member's line: it must lie at least `margin` inside one of them
+    roff = np.asarray(packed[3])
+    s_fld = np.searchsorted(roff, got['region'], side='right') - 1
+    s_line = got['line'] + np.concatenate([rec['first_line'], [0]])[roff[s_fld]]          # the swaths' global lines: ascending
+    org = packed[0][:, :2].copy().view(np.float64)
+    fr = got['frame'][s_fld]
+    ua = (got['ax'] - org[s_fld, 0]) * fr[:, 1] + (got['ay'] - org[s_fld, 1]) * fr[:, 0]
+    ub = (got['bx'] - org[s_fld, 0]) * fr[:, 1] + (got['by'] - org[s_fld, 1]) * fr[:, 0]
+    line = rec['first_line'][reg] + k
+    assert (np.diff(s_line) >= 0).all()
+    s_sorted = s_line
+    lo, hi = np.searchsorted(s_sorted, line, side='left'), np.searchsorted(s_sorted, line, side='right')
+    # (few swaths per line: the best swath of every member by one pass per rank)
+    best = np.full(len(u), -np.inf)
+    for j in range(int((hi - lo).max(initial=0))):
+        idx = np.minimum(lo + j, len(s_sorted) - 1)
+        ok = lo + j < hi
+        inside = np.minimum(u - ua[idx], ub[idx] - u)
+        best = np.where(ok, np.maximum(best, inside), best)
+    along = float(np.max(margin - best, initial=-np.inf))
+    return across, along
+
+
+# ---- the shapes -----------------------------------------------------------------------------------------------------------------------
+def ring(n=60, hole_rows=(13, 47), hole_cols=(20, 40)):
+    w = np.ones((n, n), bool)
+    w[hole_rows[0]:hole_rows[1], hole_cols[0]:hole_cols[1]] = False
+    return lab((n, n), w)
+
+
+def _serpentine(n=130):
+    w = np.zeros((n, n), bool)
+    w[0::2, :] = True
+    w[1::4, n - 1] = True
+    w[3::4, 0] = True
+    return w
+
+
+def checkerboard(ny=100, nx=200):
+    """ny nx / 2 single-cell regions, numbered in row-major order"""
+    ii, jj = np.arange(ny)[:, None], np.arange(nx)[None, :]
+    on = (ii + jj) % 2 == 0
+    g = np.full((ny, nx), -1, np.int32)
+    g[on] = np.arange(np.count_nonzero(on), dtype=np.int32)
+    return g
+
+
+def blobs(seed, ny=50, nx=70, cell=10, fill=0.6):
+    """regions that are the random members of cell x cell squares (not connected: the rule does not ask for it)"""
+    rng = np.random.default_rng(seed)
+    g = ((np.arange(ny)[:, None] // cell) * -(-nx // cell) + np.arange(nx)[None, :] // cell).astype(np.int32)
+    g[rng.random((ny, nx)) >= fill] = -1
+    return g
+
+
+def shapes():
+    """name -> (list of label grids, regions per field or None = largest label + 1)"""
+    el = np.zeros((30, 40), bool)
+    el[:, :6] = True
+    el[:5, :] = True
+    ii = np.arange(50)
+    stairs = np.zeros((50, 50), bool)
+    stairs[ii, ii] = True
+    minus2 = blobs(3)
+    minus2[minus2 == 4] = -2
+    minus2[minus2 > 4] -= 1
+    absent = blobs(5)
+    absent[absent == 7] = -1          # label 7 never occurs, the larger ones keep their numbers
+    return {
+        'single_cell': ([lab((1, 1))], None),
+        'sliver_row': ([lab((1, 300))], None),
+        'sliver_column': ([lab((300, 1))], None),
+        'el': ([lab((30, 40), el)], None),
+        'ring': ([ring()], None),
+        'staircase': ([lab((50, 50), stairs)], None),
+        'serpentine_130': ([lab((130, 130), _serpentine())], None),
+        'checkerboard': ([checkerboard()], None),
+        'blobs': ([blobs(1), blobs(2, 33, 129, 8, 0.3)], None),
+        'empty_between': ([lab((30, 40), el), np.zeros((0, 0), np.int32), lab((1, 1)), lab((7, 9), np.zeros((7, 9), bool))], None),
+        'minus_two': ([minus2], None),
+        'absent_label': ([absent, lab((3, 3))], [int(absent.max()) + 3, 1]),
+    }
+
+
+def mixed_batch(n=65, seed=5):
+    """n fields of mixed sizes, 1 x 1 up to 200 x 150, some empty, up to 12 regions each, about half the cells members"""
+    rng = np.random.default_rng(seed)
+    grids = []
+    for i in range(n):
+        if i % 9 == 4:
+            grids.append(np.zeros((0, 0), np.int32))
+            continue
+        nx, ny = (1, 1) if i == 0 else (200, 150) if i == 1 else (int(rng.integers(1, 201)), int(rng.integers(1, 151)))
+        g = blobs(int(rng.integers(1 << 30)), ny, nx, int(rng.integers(3, 60)), 0.5)
+        grids.append(np.minimum(g, 11).astype(np.int32))
+    return grids
+
+
+def mixed_angles(n, seed=6):
+    rng = np.random.default_rng(seed)
+    th = rng.uniform(-3.2, 3.2, n)
+    th[::7] = 0.0
+    th[3::11] = np.pi / 2
+    return th
+
+
+# ---- second rounds of the kernels' strided loops ------------------------------------------------------------------
+def long_sliver(n=9000, gap=(4091, 4101)):
+    """1 x n at res 0.25, theta = 0: ONE line of ceil(n / 64) = 141 words, three rounds of the runs kernel's 64 lanes; `gap` empty bins
+    straddle bin 4096, the first bin of round two"""
+    w = np.ones((1, n), bool)
+    w[0, gap[0]:gap[1]] = False
+    return lab((1, n), w)
+
+
+def runs_round_lines(n_cu):
+    """the lines ONE round of the runs kernel's launch covers"""
+    return RUNS_WAVES_PER_CU * n_cu
+
+
+def many_lines(n_cu):
+    """isolated single-cell regions, one line each: more lines than one round of the runs kernel on n_cu compute units"""
+    want = runs_round_lines(n_cu) + 300
+    nx = 200
+    ny = -(-2 * want // nx)
+    return checkerboard(ny, nx)
+
+
+def two_labels_two_words():
+    """a 1 x 200 field whose first wavefront (cells 0 .. 63) holds two regions, the second of them bins of two bitmap words at theta = 0:
+    region 0 = cells 0 .. 19 and 150 .. 199 (its bins 0 .. 199), region 1 = cells 20 .. 149 (its bins 0 .. 129)"""
+    g = np.zeros((1, 200), np.int32)
+    g[0, 20:150] = 1
+    return g

@@ -1,0 +1,204 @@
+"""The patch passes on the host (fcpp_debug_patch_swaths: csrc/fcpp_patchfn.h, the expressions the kernels run) against a numpy oracle
+written in tests/patch_cases.py, which takes (s, c) from the twin's frame so that its u and w have the twin's bits: records, bitmaps, run
+counts, offsets, `line`, `region` and the end points, all compared with ==, on every shape of the cases module at four angles and two
+joins; the cover property the rule promises, at 1e-9; the call's errors; the region statuses; and one end-to-end case through the host
+twins of the polygon cover and its regions.  tests/test_gpu_patch.py compares the device entries with this twin."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from tests import cover_region_cases as C
+from tests import patch_cases as P
+from tests.test_polygon_cover_host import RECT40, host_cover, layout, swaths
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = {'fcpp_patch_sizes': 17, 'fcpp_patch_counts': 22, 'fcpp_patch_fill': 24, 'fcpp_debug_patch_swaths': 28}
+SHAPES = P.shapes()
+TOL = 1e-9
+
+
+def test_entries_are_declared_bound_and_exported():
+    lib = L.load()
+    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
+    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    protos = {name: args for name, _, args in L.PROTOTYPES}
+    for name, n_args in ENTRIES.items():
+        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
+        assert m and len(m.group(1).split(',')) == n_args == len(protos[name]), name
+        assert hasattr(lib, name)
+
+
+@pytest.mark.parametrize('join', P.JOINS)
+@pytest.mark.parametrize('angle', P.ANGLES)
+@pytest.mark.parametrize('name', sorted(SHAPES))
+def test_twin_equals_the_numpy_oracle(name, angle, join):
+    grids, n_reg = SHAPES[name]
+    packed = P.pack(grids, n_reg)
+    got = P.twin(packed, angle, join=join)
+    want = P.oracle(packed, got['frame'], join=join)
+    assert P.same(got, want) is None, P.same(got, want)
+    rec = got['records']
+    print(name, angle, join, got['totals'].tolist(), rec['K'][:6].tolist(), rec['B'][:6].tolist())
+    # what the rule says of every result
+    assert (rec['status'] == 0).all() and (rec['zero'] == 0).all()
+    assert got['totals'].tolist() == [rec['K'].sum(), (rec['K'] * ((rec['B'] + 63) // 64)).sum(), len(got['ax'])]
+    assert got['swath_offsets'][0] == 0 and got['swath_offsets'][-1] == len(got['ax']) and (np.diff(got['swath_offsets']) >= 0).all()
+    assert (got['length'] > 0).all() and (np.diff(got['region']) >= 0).all()
+    across, along = P.cover_errors(packed, got)
+    print('cover', across, along)
+    assert across <= TOL and along <= TOL
+    if name == 'absent_label':
+        assert rec['K'][7] == 0 and rec['B'][7] == 0 and rec['status'][7] == 0 and not (got['region'] == 7).any()
+        assert (rec['K'][-3:-1] == 0).all()          # the two indices past the largest label of field 0
+    if name == 'empty_between':
+        assert np.diff(got['swath_offsets'])[[1, 3]].tolist() == [0, 0] and np.diff(got['swath_offsets'])[2] == 1
+
+
+def test_frame_is_fc_sincos_and_exact_at_zero():
+    packed = P.pack([P.lab((2, 3))] * 4)
+    got = P.twin(packed, np.array(P.ANGLES))
+    assert got['frame'][0].tolist() == [0.0, 1.0]
+    assert np.abs(got['frame'][:, 0] - np.sin(P.ANGLES)).max() < 1e-15 and np.abs(got['frame'][:, 1] - np.cos(P.ANGLES)).max() < 1e-15
+
+
+def test_a_hole_taller_than_two_strips_splits_a_line_unless_joined():
+    """the 60 x 60 ring at res 0.25, W = 4, theta = 0: We = 3.75 m is 15 rows, the hole is 34 rows high and 20 bins (5 m) wide"""
+    packed = P.pack([P.ring()])
+    split = P.twin(packed, 0.0, join=0.0)
+    assert split['records']['K'][0] == 4 and split['records']['B'][0] == 60
+    assert split['line_counts'].tolist() == [1, 2, 2, 1]
+    two = split['line'] == 1
+    assert np.allclose(split['length'][two], [20 * 0.25 + 0.25, 20 * 0.25 + 0.25])
+    just_short = P.twin(packed, 0.0, join=20 * P.RES - 0.01)          # J = 19: a gap of 20 empty bins still splits
+    assert just_short['line_counts'].tolist() == [1, 2, 2, 1]
+    joined = P.twin(packed, 0.0, join=20 * P.RES)
+    assert joined['line_counts'].tolist() == [1, 1, 1, 1] and np.allclose(joined['length'], 60 * 0.25 + 0.25)
+    # a hole lower than a strip never splits (the issue's 20-cell hole)
+    low = P.twin(P.pack([P.ring(60, (20, 33), (20, 40))]), 0.0, join=0.0)
+    assert low['line_counts'].max() == 1
+
+
+def test_whole_cell_squares_are_covered_at_angle_zero_under_the_default_margin():
+    grids, n_reg = SHAPES['el']
+    packed = P.pack(grids, n_reg)
+    got = P.twin(packed, 0.0, join=0.0)
+    gx, gy = packed[0][0, :2].copy().view(np.float64)
+    b, a = np.nonzero(grids[0] >= 0)
+    rec = got['records'][0]
+    We = P.W - P.RES
+    for x_lo, y_lo in zip(gx + a * P.RES, gy + b * P.RES):
+        hit = (got['ax'] <= x_lo + TOL) & (got['bx'] >= x_lo + P.RES - TOL) & (got['ay'] - P.W / 2 <= y_lo + TOL) & (got['ay'] + P.W / 2 >= y_lo + P.RES - TOL)
+        assert hit.any()
+    assert np.array_equal(got['ay'], got['by']) and np.allclose(got['ay'] - gy, rec['w_lo'] + (got['line'] + 0.5) * We)
+
+
+def test_margin_and_width_move_the_ends_and_the_lines():
+    packed = P.pack([P.lab((40, 100))])
+    for margin, K in ((0.0, 3), (0.125, 3), (1.0, 5)):
+        got = P.twin(packed, 0.0, margin=margin, join=0.0)
+        assert got['records']['K'][0] == K == int(np.floor(39 * 0.25 / (P.W - 2 * margin))) + 1
+        assert np.allclose(got['length'], 100 * 0.25 + 2 * margin) and len(got['length']) == K
+        across, along = P.cover_errors(packed, got, margin=margin)
+        assert across <= TOL and along <= TOL
+
+
+def test_a_region_too_fine_for_its_lines_is_unsupported_and_the_others_stay():
+    g = P.lab((3, 3), None, 1)
+    g[0, 0] = g[2, 2] = 0          # region 0: two cells 0.5 m apart across the tracks; region 1: the rest
+    packed = P.pack([g])
+    got = P.twin(packed, 0.0, width=1e-7, margin=0.0, join=0.0)          # We = 1e-7: 5e6 lines > 2^22
+    rec = got['records']
+    assert rec['status'].tolist() == [L.EUNSUPPORTED, L.EUNSUPPORTED] and got['totals'].tolist() == [0, 0, 0]
+    got = P.twin(packed, 0.0, width=2e-7, margin=0.0, join=0.0)          # 2.5e6 lines: fine
+    assert got['records']['status'].tolist() == [0, 0] and got['records']['K'][0] == 2500001
+    assert P.same(got, P.oracle(packed, got['frame'], width=2e-7, margin=0.0, join=0.0)) is None
+    one = P.lab((1, 2), None, 1)
+    one[0, 0] = 0
+    mixed = P.twin(P.pack([g, one]), 0.0, width=1e-7, margin=0.0, join=0.0)
+    assert mixed['records']['status'].tolist() == [L.EUNSUPPORTED, L.EUNSUPPORTED, 0, 0] and mixed['swath_offsets'].tolist() == [0, 0, 2]
+
+
+def test_call_errors():
+    lib = L.load()
+    packed = P.pack([P.lab((4, 5)), P.lab((2, 2))])
+    dims, off, flat, roff = packed
+    for kw in (dict(width=0.0), dict(width=-1.0), dict(margin=-0.1), dict(margin=2.0), dict(margin=3.0), dict(join=-1.0), dict(width=np.nan),
+               dict(margin=np.nan), dict(join=np.inf), dict(res=0.0), dict(res=-0.25), dict(res=np.inf)):
+        P.twin(packed, 0.0, expect=L.EINVAL, **kw)
+    for th in (np.nan, np.inf, 1.0001e5, -2e5):
+        P.twin(packed, np.array([0.0, th]), expect=L.EINVAL)
+    assert P.twin(packed, np.array([1e5, -1e5])) is not None
+    th = np.zeros(2)
+    tot = np.zeros(3, np.int64)
+
+    def call(n=2, d=dims, o=off, f=flat, r=roff, k=None, a=th, caps=(0, 0, 0)):
+        k = int(roff[-1]) if k is None else k
+        return lib.fcpp_debug_patch_swaths(n, P._p(d), P._p(o), 0.25, P._p(f), P._p(r), k, P._p(a), 4.0, 0.125, 4.0, None, None, P._p(tot), caps[0], None,
+                                           caps[1], None, None, None, caps[2], *([None] * 7))
+    assert call() == 0 and tot.tolist() == [2, 2, 2]
+    for kw in (dict(d=None), dict(o=None), dict(f=None), dict(r=None), dict(a=None)):
+        assert call(**kw) == L.EINVAL, kw
+    assert call(n=-1) == L.ESIZE and call(k=-1) == L.ESIZE and call(k=3) == L.ESIZE and call(k=1) == L.ESIZE
+    for caps in ((-1, 0, 0), (0, -1, 0), (0, 0, -1)):
+        assert call(caps=caps) == L.ESIZE
+    bad = off.copy(); bad[0] = 1
+    assert call(o=bad) == L.ESIZE
+    bad = off.copy(); bad[2] += 1
+    assert call(o=bad) == L.ESIZE
+    bad = dims.copy(); bad[0, 2] = -5
+    assert call(d=bad) == L.ESIZE
+    bad = roff.copy(); bad[0] = 1
+    assert call(r=bad) == L.ESIZE
+    bad = roff.copy(); bad[1] = 3
+    assert call(r=bad) == L.ESIZE
+    assert b'' != lib.fcpp_last_error()
+    # no field at all is a valid call
+    assert call(n=0, o=off[:1].copy(), r=roff[:1].copy(), k=0) == 0 and tot.tolist() == [0, 0, 0]
+
+
+def test_second_round_cases_reach_the_rounds_they_are_named_for():
+    """what tests/test_gpu_patch.py drives the kernels' strided loops with, asserted from the inputs and the twin"""
+    g = P.long_sliver()
+    packed = P.pack([g])
+    split = P.twin(packed, 0.0, join=0.0)
+    rec = split['records'][0]
+    assert (rec['K'], rec['B']) == (1, 9000) and split['totals'].tolist() == [1, 141, 2] and 141 > 2 * 64          # three rounds of 64 lanes
+    # the second run starts in round two (word 64 and up), the set bin before it lies in round one
+    q0 = np.round((split['ax'] - split['ax'][0]) / P.RES).astype(int)
+    assert q0.tolist() == [0, 4101] and 4101 // 64 == 64 and 4090 // 64 == 63
+    assert P.same(split, P.oracle(packed, split['frame'], join=0.0)) is None
+    joined = P.twin(packed, 0.0, join=P.W)          # J = 16 > the 10 empty bins
+    assert joined['totals'].tolist() == [1, 141, 1] and np.allclose(joined['length'], 9000 * 0.25 + 0.25)
+    many = P.many_lines(P.MI355X_CUS)
+    t = P.twin(P.pack([many]), 0.3)
+    assert t['totals'][0] == np.count_nonzero(many >= 0) > P.runs_round_lines(P.MI355X_CUS) == 4096
+    cb = SHAPES['checkerboard'][0][0]
+    assert cb.max() + 1 == 10000 > 256 * 39 and cb.size > C.BLOCK_CELLS and cb.size % C.BLOCK_CELLS          # 40 rounds of the scan; blocks
+    two = P.two_labels_two_words()
+    t = P.twin(P.pack([two]), 0.0)
+    assert len(set(two[0, :64].tolist())) == 2 and t['records']['B'].tolist() == [200, 130] and t['line_counts'].tolist() == [2, 1]
+
+
+def test_patches_over_the_missed_strips_of_a_rectangle():
+    """40 x 20 m under three passes of width 4 m at y = 2, 10, 18 (tests/test_cover_regions_host.py): the strips 4 < y < 8 and 12 < y < 16
+    are missed.  Through the host twins of the cover and its regions, then one patch pass down the middle of each strip"""
+    res = 0.25
+    out = host_cover([RECT40], 4.0, res, layout(1, swaths((2, 10, 18))))
+    dims, off, flat = out['dims'], out['cell_offsets'], out['grid']
+    reg = C.twin(None, *C.KINDS['missed'], 4, packed=(dims, off, flat))
+    assert reg['records']['cells'].tolist() == [2560, 2560]
+    packed = (dims, off, reg['index'], reg['offsets'])
+    got = P.twin(packed, 0.0, width=4.0, res=res, margin=0.0, join=0.0)
+    assert got['records']['K'].tolist() == [1, 1] and got['records']['B'].tolist() == [160, 160] and got['totals'].tolist() == [2, 6, 2]
+    assert np.allclose(got['ay'], [6.0, 14.0], atol=1e-12) and np.array_equal(got['ay'], got['by'])
+    assert np.allclose(got['ax'], 0.125, atol=1e-12) and np.allclose(got['bx'], 40.125, atol=1e-12) and np.allclose(got['length'], 40.0, atol=1e-12)
+    assert got['line'].tolist() == [0, 1] and got['region'].tolist() == [0, 1]
+    assert P.same(got, P.oracle(packed, got['frame'], width=4.0, res=res, margin=0.0, join=0.0)) is None
+    # under the default margin the strips' 16 rows of centres span exactly We = 3.75 m: two lines each
+    got = P.twin(packed, 0.0, width=4.0, res=res)
+    assert got['records']['K'].tolist() == [2, 2] and np.allclose(got['ax'], 0.0, atol=1e-12)
+    across, along = P.cover_errors(packed, got, width=4.0, res=res)
+    assert across <= TOL and along <= TOL
