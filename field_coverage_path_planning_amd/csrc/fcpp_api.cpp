@@ -1,5 +1,5 @@
 // fcpp_api.cpp -- the C ABI declared in include/fcpp.h: the context and its output arena, a batch's entries and step, GA, cover, gather and the
-// debug entries: argument checking, device buffers, launches.  (A batch's setup: fcpp_setup.cpp; the standalone path operators: fcpp_paths.cpp.)
+// debug entries: argument checking, device buffers, launches.  (A batch's setup: fcpp_setup.cpp; the standalone path operators: fcpp_paths.cpp, fcpp_glue_*.cpp.)
 // No CPU compute path exists here: every operator ends in a HIP kernel launch or fails with FCPP_EHIP.
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>

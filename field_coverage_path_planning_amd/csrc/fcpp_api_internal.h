@@ -1,5 +1,5 @@
 // fcpp_api_internal.h -- what the host translation units behind include/fcpp.h share: fcpp_api.cpp (context, output arena, a batch's step), fcpp_setup.cpp
-// (batch setup) and fcpp_paths.cpp (the standalone path operators).  Private to csrc/.
+// (batch setup), fcpp_paths.cpp and fcpp_glue_*.cpp (the standalone path operators, one glue file per family).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

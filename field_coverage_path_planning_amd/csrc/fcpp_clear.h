@@ -1,4 +1,4 @@
-// fcpp_clear.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the connector clearance kernels (fcpp_clear.hip): solved
+// fcpp_clear.h -- interface between the C-ABI glue (fcpp_glue_conn.cpp, fcpp_glue_route.cpp) and the connector clearance kernels (fcpp_clear.hip): solved
 // connectors against the rings of their field, elementwise and over every field's transit block.  The rule is fcpp_clearfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

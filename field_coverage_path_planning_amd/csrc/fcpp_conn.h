@@ -1,4 +1,4 @@
-// fcpp_conn.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the connector kernels (fcpp_conn.hip): the batched shortest-path
+// fcpp_conn.h -- interface between the C-ABI glue (fcpp_glue_conn.cpp) and the connector kernels (fcpp_conn.hip): the batched shortest-path
 // solve, the all-pairs transit matrix, and the sampler of solved paths at a fixed spacing (Reeds-Shepp: run by run of one gear).
 // mode 0 Dubins, 1 Reeds-Shepp; the interface of both is fcpp_connfn.h, the mathematics fcpp_dubinsfn.h / fcpp_rsfn.h.
 #pragma once

@@ -1,4 +1,4 @@
-// fcpp_inset.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the polygon inset kernels (fcpp_inset.hip): the ring and vertex
+// fcpp_inset.h -- interface between the C-ABI glue (fcpp_glue_polygon.cpp) and the polygon inset kernels (fcpp_inset.hip): the ring and vertex
 // counts of (field, distance) pairs, their CSR offsets, and the rings at those offsets.  The rule is fcpp_insetfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,4 +1,4 @@
-// fcpp_legs.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the kernels of the leg-path operators (fcpp_legs.hip): the field paths
+// fcpp_legs.h -- interface between the C-ABI glue (fcpp_glue_legs.cpp) and the kernels of the leg-path operators (fcpp_legs.hip): the field paths
 // (rule and leg set: fcpp_fpathfn.h, FieldLegs) and the headland paths (fcpp_hpathfn.h, RingLegs).  Both are records -> scan -> groups ->
 // samples: a group (a field, a ring) owns a run of leg slots, a rule kernel writes a record and a sample count per slot, the counts are
 // scanned into slot offsets, a lane per group writes its path offset and totals, a lane per sample evaluates its slot's record.  Only the

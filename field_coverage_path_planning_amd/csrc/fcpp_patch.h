@@ -1,4 +1,4 @@
-// fcpp_patch.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the patch-pass kernels (fcpp_patch.hip): the regions' extents and
+// fcpp_patch.h -- interface between the C-ABI glue (fcpp_glue_cover.cpp) and the patch-pass kernels (fcpp_patch.hip): the regions' extents and
 // layout, the bitmaps of their lines, the runs of every line and the swath records.  The rule is fcpp_patchfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

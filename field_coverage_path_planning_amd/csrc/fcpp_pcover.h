@@ -1,4 +1,4 @@
-// fcpp_pcover.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the polygon-coverage kernels (fcpp_pcover.hip): the fields' grids and
+// fcpp_pcover.h -- interface between the C-ABI glue (fcpp_glue_cover.cpp) and the polygon-coverage kernels (fcpp_pcover.hip): the fields' grids and
 // status, the offsets of their cells and tiles, the bounding boxes of the paths' chunks, and the tiles' rasterisation.  The rule is
 // fcpp_pcoverfn.h.
 #pragma once

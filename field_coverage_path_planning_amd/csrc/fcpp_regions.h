@@ -1,4 +1,4 @@
-// fcpp_regions.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the coverage-region kernels (fcpp_regions.hip): the labelling of
+// fcpp_regions.h -- interface between the C-ABI glue (fcpp_glue_cover.cpp) and the coverage-region kernels (fcpp_regions.hip): the labelling of
 // the fields' tiles, the merge over the tile seams, the numbering of the regions and their records.  The rule is fcpp_regionfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,4 +1,4 @@
-// fcpp_route.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the swath router's kernels (fcpp_route.hip): the transit blocks
+// fcpp_route.h -- interface between the C-ABI glue (fcpp_glue_route.cpp) and the swath router's kernels (fcpp_route.hip): the transit blocks
 // of the fields' oriented swaths, the candidate tours and the winner per field.  The rule is fcpp_routefn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

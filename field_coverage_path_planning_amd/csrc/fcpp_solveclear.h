@@ -1,4 +1,4 @@
-// fcpp_solveclear.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the clear-connector kernels (fcpp_solveclear.hip).  The rule is
+// fcpp_solveclear.h -- interface between the C-ABI glue (fcpp_glue_conn.cpp, fcpp_glue_route.cpp, fcpp_glue_legs.cpp) and the clear-connector kernels (fcpp_solveclear.hip).  The rule is
 // fcpp_solveclearfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

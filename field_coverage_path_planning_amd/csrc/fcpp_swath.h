@@ -1,4 +1,4 @@
-// fcpp_swath.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the polygon swath kernels (fcpp_swath.hip): the counts and length
+// fcpp_swath.h -- interface between the C-ABI glue (fcpp_glue_polygon.cpp) and the polygon swath kernels (fcpp_swath.hip): the counts and length
 // sums of (field, angle) pairs, the CSR offsets of the fields' swaths, and the swath records at those offsets.  The rule is fcpp_swathfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

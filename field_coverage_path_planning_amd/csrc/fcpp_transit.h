@@ -1,4 +1,4 @@
-// fcpp_transit.h -- interface between the C-ABI glue (fcpp_paths.cpp) and the loop-transit kernels (fcpp_transit.hip).  The rule is
+// fcpp_transit.h -- interface between the C-ABI glue (fcpp_glue_legs.cpp) and the loop-transit kernels (fcpp_transit.hip).  The rule is
 // fcpp_transitfn.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -324,7 +324,7 @@ def short_paths(seed, count, lo=(-1.0, -1.0), hi=(41.0, 21.0), step=1.5):
 
 
 def field_chunks(lay, f):
-    """the chunks of field f in the order the glue lists them (fcpp_paths.cpp: pcover_chunks, restated): (path, first sample, segments)"""
+    """the chunks of field f in the order the glue lists them (fcpp_glue_cover.cpp: pcover_chunks, restated): (path, first sample, segments)"""
     fpo, poff, ids = lay['field_path_offsets'], lay['path_offsets'], lay['path_ids']
     out = []
     for s in range(fpo[f], fpo[f + 1]):
