@@ -20,6 +20,9 @@ ROUTE_MAX_SWATHS = 512           # FCPP_ROUTE_MAX_SWATHS
 CLEAR_EDGE_CHUNK = 256           # FCPP_CLEAR_EDGE_CHUNK
 TRANSIT_MAX_STATIONS = 2048      # FCPP_TRANSIT_MAX_STATIONS
 PART_LOOP_RIDE = 5               # FCPP_PART_LOOP_RIDE
+MISSION_MAX_STATIONS = 1024      # FCPP_MISSION_MAX_STATIONS
+PART_JOIN = 6                    # FCPP_PART_JOIN
+MISSION_BLOCK = 256              # threads of a workgroup of the mission-path kernels: four wavefronts, a target node each
 TRANSIT_BLOCK = 256              # threads of a workgroup of the loop-transit kernels, the pick pass's tile of stations
 
 c_double_p = C.POINTER(C.c_double)
@@ -202,6 +205,12 @@ PROTOTYPES = [
     ('fcpp_loop_transit_fill', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double] + [_VP] * 8 + [C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5
      + [C.c_double, _VP, _VP, C.c_int64] + [_VP] * 6),
     ('fcpp_ctx_loop_transit_passes', C.c_int, [_VP, c_i64_p, c_i64_p]),
+    ('fcpp_mission_solve', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 11
+     + [C.c_double, C.c_int64] + [_VP] * 8),
+    ('fcpp_mission_counts', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5
+     + [C.c_double] + [_VP] * 3),
+    ('fcpp_mission_fill', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 9
+     + [C.c_double, C.c_double] + [_VP] * 6 + [C.c_int64] + [_VP] * 8),
     ('fcpp_headland_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
      + [_VP] * 7),
     ('fcpp_headland_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
@@ -244,6 +253,8 @@ PROTOTYPES = [
      + [_VP] * 8),
     ('fcpp_debug_loop_transits', C.c_int, [C.c_int, C.c_int64] + [_VP] * 6 + [C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]
      + [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [_VP, C.c_int64, C.c_double] + [_VP] * 15 + [_VP, C.c_int64] + [_VP] * 6),
+    ('fcpp_debug_mission_paths', C.c_int, [C.c_int, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64] + [_VP] * 12
+     + [C.c_double, C.c_int64, C.c_double] + [_VP] * 10 + [C.c_int64] + [_VP] * 8),
     ('fcpp_debug_field_paths', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 14 + [C.c_int64]
      + [_VP] * 7),
     ('fcpp_debug_field_paths_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 7 + [C.c_double, C.c_int, C.c_double] + [_VP] * 6

@@ -2276,6 +2276,235 @@ def _detour_field_paths(fp, ss, pf, loops, R, spacing, reversing, order, entry, 
     return out
 
 
+# ---- mission paths (fcpp_mission_solve / _counts / _fill; the rule: include/fcpp.h) ------------------------------------------------------
+@dataclass
+class MissionPaths:
+    """mission_paths(): ONE sampled path per field -- its items joined in driving order -- in the CSR form curvature(), speed_plan(),
+    validate() and trajectory() take (offsets=).  Field i owns the samples offsets[i] .. offsets[i + 1]."""
+    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy
+    offsets_host: object
+    x: object                   # (total) float64
+    y: object
+    heading: object
+    kappa: object
+    part: object                # (total) int8: the source sample's part, FCPP_PART_JOIN (6) on a joint
+    gear: object                # (total) int8
+    slot: object                # (total) int32: the slot within the field: 2 j the joint into kept item j, 2 j + 1 the item, the last the exit joint
+    src: object                 # (total) int64: the source sample's index into the concatenated item sets, -1 on a joint
+    src_set: object             # (total) int32: the position in `items` of the set the sample was copied from, -1 on a joint
+    status: object              # (n) int32: 0, FCPP_EINVAL (a chosen pose that is not finite), FCPP_EUNSUPPORTED (a loop of more than 1024 stations): no samples
+    transit_length: object      # (n) float64: the joints' lengths in driving order [m]
+    skipped: object             # (n) int32: the items without a sample or, closed, without a station: they drive nothing
+    item_offsets: object        # (n + 1) int64: field i's items are item_offsets[i] .. item_offsets[i + 1], in driving order
+    item_path: object           # (items) int64: the path driven, an index into the concatenated item sets
+    item_closed: object         # (items) int32
+    item_set: object            # (items) int32: the position in `items` of the item's set
+    item_station: object        # (items) int64: the sample a loop is entered and left at (an index like src); -1 for an open or a skipped item
+    slot_offsets: object        # (2 items + n + 1) int64: the first sample of every slot; field i's first slot is 2 item_offsets[i] + i
+    slot_item: object           # (slots) int64: the item of an item slot, else -1
+    slot_word: object           # (slots) int32: a joint's word, else -1
+    slot_seg: object            # (slots, 5) float64: its segments
+    slot_total: object          # (slots) float64: its length
+    radius: float               # the planning radius the joints were solved at
+    reversing: bool
+    stride: int
+    set_starts: object = None   # (sets + 1) numpy int64: where every set's samples start in the concatenation
+    blocked: object = None      # (n) int32 with clear_of: the field's joints for which no word is clear of its region (they are driven as they are)
+
+    def field(self, i):
+        """(x, y, heading, part) of field i: swath_route's tuple"""
+        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+
+    def cover_set(self, pass_ids=None, work=None):
+        """The tuple (offsets, x, y, path_field, work, pass) polygon_coverage takes, gathered through src.  pass_ids / work: one entry per
+        set of `items`, each a tensor per source sample of that set or None -- the defaults polygon_coverage uses for a FieldPaths (work:
+        the swaths, pass: the leg) or a HeadlandPaths (work: straight elements and followed arcs, pass: -1 - ring); a tuple-form set needs both
+        given.  Joints do not work."""
+        torch = _torch()
+        dev = self.x.device
+        n_sets = len(self._sets)
+        pass_ids = [None] * n_sets if pass_ids is None else list(pass_ids)
+        work = [None] * n_sets if work is None else list(work)
+        if len(pass_ids) != n_sets or len(work) != n_sets:
+            raise ValueError('pass_ids and work take one entry (or None) per item set')
+        ws, ps = [], []
+        for k, st in enumerate(self._sets):
+            total = int(self.set_starts[k + 1] - self.set_starts[k])
+            w, p = work[k], pass_ids[k]
+            if (w is None or p is None) and not isinstance(st, (FieldPaths, HeadlandPaths)):
+                raise ValueError('a tuple-form item set needs its pass ids and work flags given')
+            if w is None or p is None:
+                d = _cover_path_set(st, 0, dev)
+                w, p = (d[5] if w is None else w), (d[6] if p is None else p)
+            w = (torch.as_tensor(w, device=dev).reshape(-1) != 0).to(torch.uint8)
+            p = torch.as_tensor(p, device=dev).to(torch.int32).reshape(-1)
+            if int(w.numel()) != total or int(p.numel()) != total:
+                raise ValueError('pass_ids and work hold one value per sample of their set')
+            ws.append(w); ps.append(p)
+        copied = self.src >= 0
+        at = self.src.clamp(min=0)
+        cat = lambda ts, dt: torch.cat(ts + [torch.zeros(1, dtype=dt, device=dev)])          # (one spare element: a set list without a sample)
+        w = torch.where(copied, cat(ws, torch.uint8)[at], torch.zeros((), dtype=torch.uint8, device=dev))
+        pas = torch.where(copied, cat(ps, torch.int32)[at], torch.zeros((), dtype=torch.int32, device=dev))
+        n = int(self.offsets.numel()) - 1
+        return (self.offsets, self.x, self.y, torch.arange(n, dtype=torch.int64, device=dev), w, pas)
+
+    _sets = ()
+
+
+def _mission_set(st, dev, innermost_first):
+    """one item set -> (offsets, x, y, heading, kappa, part, gear, field int64 per path, closed bool, the paths' order within the set)"""
+    torch = _torch()
+    if isinstance(st, FieldPaths):
+        npth = int(st.offsets.numel()) - 1
+        return (st.offsets, st.x, st.y, st.heading, st.kappa, st.part, st.gear, torch.arange(npth, dtype=torch.int64, device=dev), False,
+                torch.arange(npth, dtype=torch.int64, device=dev))
+    if isinstance(st, HeadlandPaths):
+        npth = int(st.offsets.numel()) - 1
+        order = torch.argsort(-st.ring_pair[:, 1], stable=True) if innermost_first else torch.arange(npth, dtype=torch.int64, device=dev)
+        return (st.offsets, st.x, st.y, st.heading, st.kappa, st.part, st.gear, st.ring_pair[:, 0].to(dev), True, order.to(dev))
+    offsets, x, y, heading, kappa, part, gear, field, closed = st
+    x = _dev_f64(x, dev).reshape(-1)
+    total = int(x.numel())
+    off, _ = _offsets(offsets, total, dev)
+    npth = int(off.numel()) - 1
+    field = torch.as_tensor(field, device=dev).to(torch.int64).reshape(-1)
+    if field.numel() == 1 and npth != 1:
+        field = field.expand(npth)
+    i8 = lambda a: torch.as_tensor(a, device=dev).to(torch.int8).reshape(-1).contiguous()
+    cols = (off, x, _dev_f64(y, dev).reshape(-1), _dev_f64(heading, dev).reshape(-1), _dev_f64(kappa, dev).reshape(-1), i8(part), i8(gear))
+    if any(int(c.numel()) != total for c in cols[1:]) or int(field.numel()) != npth:
+        raise ValueError('an item set needs six columns of one length and one field per path')
+    return cols + (field.contiguous(), bool(closed), torch.arange(npth, dtype=torch.int64, device=dev))
+
+
+def _mission_table(items, dev, innermost_first=False, n_fields=None, entry=None, exit=None):
+    """the item sets concatenated into one path set and the fields' item table, as fcpp_mission_solve takes them -> dict"""
+    n = n_fields
+    torch = _torch()
+    sets = [_mission_set(st, dev, innermost_first) for st in items]
+    if n is None:
+        n = max([int(s[7].max()) + 1 for s in sets if int(s[7].numel())] + [0])
+        for p in (entry, exit):
+            n = n if p is None else max(n, int(torch.as_tensor(p).reshape(-1, 3).shape[0]))
+    first = np.concatenate([[0], np.cumsum([int(s[0].numel()) - 1 for s in sets])]).astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum([int(s[1].numel()) for s in sets])]).astype(np.int64)
+    total_in = int(starts[-1])
+    cat = lambda k, dt: (torch.cat([s[k].to(dev) for s in sets]) if sets else torch.empty(0, dtype=dt, device=dev)).contiguous()
+    x, y, h, kap = (cat(k, torch.float64) for k in (1, 2, 3, 4))
+    part, gear = cat(5, torch.int8), cat(6, torch.int8)
+    poff = torch.cat([s[0][:-1].to(dev) + int(starts[k]) for k, s in enumerate(sets)] + [torch.full((1,), total_in, dtype=torch.int64, device=dev)]).contiguous()
+    i64 = lambda ts: torch.cat(ts) if ts else torch.zeros(0, dtype=torch.int64, device=dev)
+    fld = i64([s[7][s[9]] for s in sets])
+    ipath = i64([s[9] + int(first[k]) for k, s in enumerate(sets)])
+    iset = i64([torch.full((int(s[9].numel()),), k, dtype=torch.int64, device=dev) for k, s in enumerate(sets)])
+    iclosed = i64([torch.full((int(s[9].numel()),), int(s[8]), dtype=torch.int64, device=dev) for s in sets])
+    if int(fld.numel()) and (int(fld.min()) < 0 or int(fld.max()) >= n):
+        raise ValueError('an item names a field outside 0 .. n_fields - 1')
+    order = torch.argsort(fld, stable=True)
+    fld, ipath, iset, iclosed = fld[order], ipath[order].contiguous(), iset[order].to(torch.int32), iclosed[order].to(torch.int32).contiguous()
+    n_items = int(ipath.numel())
+    ioff = torch.searchsorted(fld, torch.arange(n + 1, dtype=torch.int64, device=dev)).to(torch.int64).contiguous()
+    ioff_h, ipath_h, poff_h = ioff.cpu().numpy(), ipath.cpu().numpy(), poff.cpu().numpy()
+    lens = poff_h[1:] - poff_h[:-1]
+    longest = int(lens[ipath_h[iclosed.cpu().numpy() != 0]].max()) if n_items and bool((iclosed != 0).any()) else 0
+    return dict(n=n, first=first, starts=starts, total_in=total_in, x=x, y=y, h=h, kap=kap, part=part, gear=gear, poff=poff, poff_h=poff_h, ioff=ioff,
+                ioff_h=ioff_h, ipath=ipath, ipath_h=ipath_h, iset=iset, iclosed=iclosed, n_items=n_items, longest=longest)
+
+
+def mission_paths(items, radius, spacing, reversing=False, entry=None, exit=None, station_step=None, device=None, innermost_first=False,
+                  n_fields=None, clear_of=None):
+    """ONE drivable path per field from its path sets (fcpp_mission_solve + _counts + _fill; the rule: include/fcpp.h) -> MissionPaths.
+    items: a sequence, in DRIVING ORDER, of FieldPaths (open, path i belongs to field i), HeadlandPaths (closed loops, field =
+    ring_pair[:, 0]; its rings in stored order, or the innermost pass first with innermost_first=True) or tuples (offsets, x, y, heading,
+    kappa, part, gear, field, closed).  A field's items are ordered by (position in `items`, path order within the set).  Consecutive
+    items, and the entry / exit pose (one (x, y, heading) per field), are joined by the shortest Dubins path -- Reeds-Shepp if `reversing`
+    -- planned at _chord_radius(radius, spacing) as the field paths plan; every closed loop is entered at the station that makes the joints
+    shortest in all, driven for one lap and left there.  Stations: every max(1, round(station_step / set spacing))-th sample of a loop
+    that lies on a straight element or a followed arc; by default the stride that gives the longest loop at most 128 stations.  A loop of
+    more than FCPP_MISSION_MAX_STATIONS stations fails its field (status FCPP_EUNSUPPORTED: raise station_step).  The ORDER of the items is
+    the caller's; joints know no boundary (validate() flags what leaves the field) -- with clear_of (one region per field) the chosen joints
+    are run through clear_connectors and `blocked` counts, per field, those without a clear word; the stations stay chosen by the plain
+    lengths."""
+    ctx = get_context(device)
+    torch = _torch()
+    dev = torch.device('cuda', ctx.device)
+    items = list(items)
+    t = _mission_table(items, dev, innermost_first, n_fields, entry, exit)
+    n, first, starts, total_in, n_items, longest = t['n'], t['first'], t['starts'], t['total_in'], t['n_items'], t['longest']
+    x, y, h, kap, part, gear, poff, poff_h = t['x'], t['y'], t['h'], t['kap'], t['part'], t['gear'], t['poff'], t['poff_h']
+    ioff, ioff_h, ipath, ipath_h, iset, iclosed = t['ioff'], t['ioff_h'], t['ipath'], t['ipath_h'], t['iset'], t['iclosed']
+    if station_step is None:
+        stride = max(1, -(-(longest - 1) // 128))
+    else:
+        if not float(station_step) > 0.0:
+            raise ValueError('station_step must be positive')
+        set_spacing = next((st.spacing for st in items if isinstance(st, HeadlandPaths) and st.spacing), spacing)
+        stride = max(1, int(round(float(station_step) / float(set_spacing))))
+    R, mode = _chord_radius(radius, spacing), 1 if reversing else 0
+    ent, ext = _pose_columns(entry, n, dev), _pose_columns(exit, n, dev)
+    n_slots = 2 * n_items + n if n else 0
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    transit = torch.empty(n, dtype=torch.float64, device=dev)
+    skipped = torch.empty(n, dtype=torch.int32, device=dev)
+    # (a failed field's per-item and per-slot rows are not written: they keep these values)
+    station = torch.full((n_items,), -1, dtype=torch.int64, device=dev)
+    slot_item = torch.full((n_slots,), -1, dtype=torch.int64, device=dev)
+    slot_word = torch.full((n_slots,), -1, dtype=torch.int32, device=dev)
+    slot_seg = torch.full((n_slots, 5), float('nan'), dtype=torch.float64, device=dev)
+    slot_total = torch.full((n_slots,), float('nan'), dtype=torch.float64, device=dev)
+    head = (mode, n, _ptr(ioff), _host_ptr(ioff_h), n_items, _ptr(ipath), _host_ptr(ipath_h), _ptr(iclosed), int(first[-1]), _ptr(poff), _host_ptr(poff_h),
+            total_in)
+    rec = (_ptr(status), _ptr(station), _ptr(slot_item), _ptr(slot_word), _ptr(slot_seg))
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_mission_solve(ctx.handle, *head, _ptr(x), _ptr(y), _ptr(h), _ptr(part), _ptr(gear), *[_ptr(t) for t in ent], *[_ptr(t) for t in ext],
+                                       R, stride, _ptr(status), _ptr(transit), _ptr(skipped), _ptr(station), _ptr(slot_item), _ptr(slot_word),
+                                       _ptr(slot_seg), _ptr(slot_total)))
+    off, off_h = torch.empty(n + 1, dtype=torch.int64, device=dev), np.zeros(n + 1, dtype=np.int64)
+    slot_off = torch.empty(n_slots + 1, dtype=torch.int64, device=dev)
+    L.check(ctx.lib.fcpp_mission_counts(ctx.handle, *head, *rec, float(spacing), _ptr(off), _host_ptr(off_h), _ptr(slot_off)))
+    total = int(off_h[-1])
+    ox, oy, oh, ok = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
+    opart, ogear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
+    oslot, osrc = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int64, device=dev)
+    L.check(ctx.lib.fcpp_mission_fill(ctx.handle, *head, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), *[_ptr(t) for t in ent], R,
+                                      float(spacing), *rec, _ptr(slot_off), total, _ptr(ox), _ptr(oy), _ptr(oh), _ptr(ok), _ptr(opart), _ptr(ogear),
+                                      _ptr(oslot), _ptr(osrc)))
+    src_set = (torch.searchsorted(torch.as_tensor(starts[1:], device=dev), osrc, right=True).to(torch.int32)
+               if len(items) else torch.zeros(total, dtype=torch.int32, device=dev))
+    src_set = torch.where(osrc >= 0, src_set, torch.full((), -1, dtype=torch.int32, device=dev))
+    mp = MissionPaths(off, off_h, ox, oy, oh, ok, opart, ogear, oslot, osrc, src_set, status, transit, skipped, ioff, ipath, iclosed, iset, station,
+                      slot_off, slot_item, slot_word, slot_seg, slot_total, float(R), bool(reversing), int(stride), starts)
+    mp._sets = tuple(items)
+    if clear_of is not None:
+        mp.blocked = _mission_blocked(mp, _clear_fields(clear_of, n, device), ent, ext, device)
+    return mp
+
+
+def _mission_blocked(mp, pf, ent, ext, device):
+    """the chosen joints through clear_connectors against their field's region -> per field the joints without a clear word"""
+    torch = _torch()
+    dev = mp.x.device
+    n = int(mp.offsets.numel()) - 1
+    blocked = torch.zeros(n, dtype=torch.int32, device=dev)
+    joint = torch.nonzero(mp.slot_word >= 0).reshape(-1)
+    if int(joint.numel()) == 0:
+        return blocked
+    first = 2 * mp.item_offsets + torch.arange(n + 1, dtype=torch.int64, device=dev)
+    f = torch.searchsorted(first, joint, right=True) - 1
+    a, b = mp.slot_offsets[joint], mp.slot_offsets[joint + 1]
+    total = int(mp.x.numel())
+    sample = torch.stack([mp.x, mp.y, mp.heading], dim=1)
+    pose = lambda cols: torch.stack(cols, dim=1)[f] if cols[0] is not None else torch.zeros((int(f.numel()), 3), dtype=torch.float64, device=dev)
+    at_entry, at_exit = (joint == first[f]).unsqueeze(1), (b == mp.offsets[f + 1]).unsqueeze(1)
+    frm = torch.where(at_entry, pose(ent), sample[(a - 1).clamp(min=0)])
+    to = torch.where(at_exit, pose(ext), sample[b.clamp(max=total - 1)])
+    cc = clear_connectors(frm, to, pf, f, mp.radius, reversing=mp.reversing, device=device)
+    blocked.index_add_(0, f, (cc.rank < 0).to(torch.int32))
+    return blocked
+
+
 # ---- polygon coverage (fcpp_polygon_cover_sizes / fcpp_polygon_cover; the rule: include/fcpp.h) -----------------------------------------
 @dataclass
 class PolygonCoverage:
@@ -2614,17 +2843,18 @@ class PolygonPlan:
     patch_info: object = None           # PatchInfo of `patch`
     patch_paths: object = None          # FieldPaths over `patch`, routed per field
     coverage_after: object = None       # PolygonCoverage of `fields` under the plan's paths AND patch_paths, its cells kept
+    mission: object = None              # MissionPaths: loops, field path and patch passes joined into one drive per field (mission=...), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
                         arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
-                        price_clear=False, detour=False, missed_min_area=None, patch=False):
+                        price_clear=False, detour=False, missed_min_area=None, patch=False, mission=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
     The headland pass rings are returned (headland) but not part of the path; headland_paths=True also drives them (headland_paths() at the
-    same radius, spacing and `reversing`: one closed loop per ring, PolygonPlan.headland_paths).  The loops are not joined to each other or
-    to the field paths' entries: the connector operators do that from the loops' first poses.  coverage_resolution [m]: also report what the
+    same radius, spacing and `reversing`: one closed loop per ring, PolygonPlan.headland_paths).  The loops are joined to each other and
+    to the field paths by mission= (below).  coverage_resolution [m]: also report what the
     plan covers of the ORIGINAL fields (polygon_coverage at that cell size over the field paths, and the headland loops if they were driven:
     PolygonPlan.coverage); nothing else in the chain changes.  clear_of: None leaves the plan as it is; 'boundary' routes the swaths so
     that the connectors stay clear of the surveyed `fields` (holes are ponds) where an order allows it, and reports what stays blocked
@@ -2645,7 +2875,17 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     each field's chosen angle (PolygonPlan.patch, .patch_info), route_swaths + field_paths drive them at the same radius, spacing and
     `reversing` (.patch_paths), and a second polygon_coverage over the plan's path sets plus the patch paths -- their pass ids are
     leg + 2^30, apart from the first set's legs and the rings' negative ids -- says what is covered then (.coverage_after, cells kept).
-    The patch paths are not joined to the field path; patch=False: the chain makes exactly the calls it makes without it."""
+    The patch paths are joined to the field path by mission=; patch=False: the chain makes exactly the calls it makes without it.
+    mission='headland_first' | 'headland_last' (with headland_paths=True; ValueError without): ONE drivable path per field
+    (mission_paths(): PolygonPlan.mission), gate -> loops -> swaths -> patch passes -> gate.  'headland_first' drives the passes outermost
+    -> innermost, then `paths`, then patch_paths if present; 'headland_last' drives `paths`, the patch paths, then the passes innermost ->
+    outermost.  entry / exit then belong to the MISSION: the router still prices them, the field paths are built without them.  With
+    clear_of the chosen joints are tested against the same region (mission.blocked).  None: the chain makes exactly the calls it makes
+    without it."""
+    if mission not in (None, 'headland_first', 'headland_last'):
+        raise ValueError("mission must be None, 'headland_first' or 'headland_last'")
+    if mission is not None and not headland_paths:
+        raise ValueError('mission needs headland_paths=True: the loops the mission drives')
     if patch and missed_min_area is None:
         raise ValueError('patch=True needs missed_min_area: the regions the patch passes are laid over')
     if missed_min_area is not None and coverage_resolution is None:
@@ -2669,8 +2909,9 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
                          **({'price_clear': True} if price_clear else {}))
     hp = _drive_headland(lines, radius, spacing, reversing=reversing, device=device) if headland_paths else None
     both = (hp, _drive_headland(lines, radius, spacing, reversing=reversing, direction=-1, device=device)) if detour else None
-    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, entry=entry, exit=exit, device=device,
-                        clear_of=region if reshape else None, **({'loops': both} if detour else {}))
+    path_ends = {} if mission is not None else {'entry': entry, 'exit': exit}          # (a mission's gates are joined to its first and last item)
+    paths = field_paths(ss, radius, spacing, reversing=reversing, order=route, device=device, clear_of=region if reshape else None,
+                        **path_ends, **({'loops': both} if detour else {}))
     clr = route.clearance          # (the legs field_paths drives: route_swaths planned at the same _chord_radius(radius, spacing))
     cov = None
     if coverage_resolution is not None:
@@ -2686,6 +2927,11 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
         as_set = (pp.offsets, pp.x, pp.y, torch.arange(fields.n, dtype=torch.int64, device=pp.x.device), pp.part == 0, pp.leg + (1 << 30))
         plan.coverage_after = polygon_coverage(fields, width, coverage_resolution, paths=((paths,) if hp is None else (paths, hp)) + (as_set,),
                                                want_grid=True, device=device)
+    if mission is not None:
+        open_sets = (paths,) if plan.patch_paths is None else (paths, plan.patch_paths)
+        plan.mission = mission_paths((hp,) + open_sets if mission == 'headland_first' else open_sets + (hp,), radius, spacing, reversing=reversing,
+                                     entry=entry, exit=exit, device=device, innermost_first=mission == 'headland_last', n_fields=fields.n,
+                                     clear_of=region)
     return plan
 
 

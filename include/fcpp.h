@@ -965,6 +965,89 @@ int fcpp_debug_loop_transits(int mode, int64_t n, const double *from_x, const do
                              int64_t *path_offsets, int64_t cap, double *out_x, double *out_y, double *heading, double *kappa, int8_t *part,
                              int8_t *gear);
 
+/* ---- mission paths: headland loops, field path and patch passes joined into ONE drive per field ---------------------------------------------
+ * Build-defined.  The field paths, the headland paths and the patch passes each give a path set; nothing above joins them.  A MISSION PATH
+ * drives, per field, a list of ITEMS in the caller's order -- each a path of ONE path set, open or a closed loop -- with a connector (a
+ * JOINT) between consecutive items and from / to an optional entry / exit pose.  A closed loop may be entered at any of its stations and is
+ * left there again after one lap; fcpp_mission_solve chooses every loop's station so that the joints are shortest in all,
+ * fcpp_mission_counts / _fill sample the result.  Standalone: nothing here feeds fcpp_batch_plan.
+ * THE RULE (csrc/fcpp_missionfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Paths: a path set in the samplers' CSR form as the *_path_fill entries write it: path p owns the samples path_offsets[p] ..
+ *     path_offsets[p + 1] (n_p of them) of x, y, heading, kappa, part, gear.  Concatenate several sets into one.
+ *   - Items: field f owns the items item_offsets[f] .. item_offsets[f + 1], in DRIVING ORDER.  item_path (int64): the path the item drives;
+ *     item_closed (int32): 0 open -- driven from its first sample to its last -- else a closed loop whose last sample repeats its first pose.
+ *   - Nodes: an open item has one node, in-pose its first sample, out-pose its last.  A closed item's nodes are its stations, the loop
+ *     transits' rule: the samples of local index k with k mod stride == 0 (stride >= 1), part 0 or 4 and gear +1 -- and k < n_p - 1;
+ *     in-pose = out-pose = the sample's (x, y, heading).  The entry and the exit pose of a field (three columns each, NULL: none) are
+ *     layers of one node.
+ *   - An item whose path has no samples, and a closed item without a station, is SKIPPED: it drives nothing, is counted in `skipped`, and
+ *     the items around it are joined to each other.
+ *   - Cost: d(a, b) is the total fcpp_dubins_solve (mode 0) / fcpp_rs_solve (mode 1) give at `radius` from out(a) to in(b).  c_0 = 0, or
+ *     fl(0 + d(entry, .)) with an entry; c_j[b] = min over a of fl(c_(j-1)[a] + d(a, b)), a sum that is not below +inf (NaN: a pose that is
+ *     not finite) counting as +inf; the predecessor of b is the LOWEST a that attains the minimum.  The end is the lowest b of the last
+ *     layer that attains the minimum, after the exit's edge fl(c[b] + d(b, exit)) when there is an exit.  The backtrack gives one node per
+ *     kept item.  transit_length: the chosen joints' totals added in driving order from 0 -- the chain of additions of the optimum.
+ *   - Slots: a field of m items has 2 m + 1 slots, its first 2 item_offsets[f] + f.  KEPT item j (the j-th not skipped) owns slot 2 j, the
+ *     joint INTO it (empty for the first without an entry), and slot 2 j + 1, itself; slot 2 k behind the field's k kept items holds the
+ *     exit joint (empty without an exit; with k = 0 the joint entry -> exit if both are given).  The slots behind are empty.
+ *   - Samples: a joint as fcpp_dubins_sample / fcpp_rs_sample sample it from the out-pose before it, part FCPP_PART_JOIN, its own gear and
+ *     kappa.  An open item: its samples as they are.  A closed item entered at local index k: the samples k, k + 1 .. n_p - 1, 0, 1 .. k --
+ *     n_p + 1 of them, the seam a doubled junction like every other.  Copied samples keep x, y, heading, kappa, part and gear bit for bit.
+ *     Beside the six columns every sample has slot (int32, local to its field) and src (int64: the source sample's index into the path
+ *     set, -1 on a joint), by which pass ids, work flags or anything else per source sample can be gathered.  Junctions stay doubled.
+ *   - Per field: status (int32), transit_length (float64), skipped (int32).  status FCPP_EUNSUPPORTED: a closed item of more than
+ *     FCPP_MISSION_MAX_STATIONS stations (raise the stride); FCPP_EINVAL: a chosen joint without a word, i.e. a chosen in- or out-pose, entry
+ *     or exit pose that is not finite.  Such a field has no samples and transit_length NaN, its per-item and per-slot rows are NOT
+ *     written, and the other fields are unaffected.
+ *   - Per item: item_station (int64), the chosen station's GLOBAL sample index; -1 for an open or a skipped item.
+ *   - Per slot: slot_item (int64: the item of an item slot, else -1), slot_word (int32), slot_seg (5 float64, the field paths' record
+ *     layout: three used by mode 0, the rest 0), slot_total (float64) of a joint; word -1, seg and total NaN on every other slot.
+ * fcpp_mission_counts: slot_offsets (2 n_items + n_fields + 1) and path_offsets (n_fields + 1; the CSR fcpp_curvature, fcpp_speed_plan,
+ * fcpp_validate and fcpp_trajectory take) from the solve's outputs handed back; a record that names no item of its field or no sample of
+ * the item's path counts as empty.  fcpp_mission_fill: the samples; every output may be NULL.
+ * Launches of the solve: a wavefront per item lists its stations; a workgroup per field walks its layers, the two cost vectors in LDS, a
+ * wavefront per target node, its lanes over the source nodes, (cost, a) reduced lexicographically; a lane per field backtracks and writes
+ * the records.  Temporaries: 12 B per (item, station slot).  Nothing is kept in the context.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, an entry or exit pose with fewer than
+ * three columns, radius or spacing <= 0 or not finite, mode not 0 or 1, stride < 1; FCPP_ESIZE -- negative sizes, more than 2^30 items,
+ * offsets that do not start at 0, decrease or do not end at their total, an item_path outside 0 .. n_paths - 1, slot_offsets that do not span
+ * [0, total_samples].  FCPP_ESIZE after the count: a slot or a field of more than 2^31 - 2 samples.  The *_host tables: the host copy, or
+ * NULL to have it read back.  All three entries synchronise. */
+#define FCPP_MISSION_MAX_STATIONS 1024
+#define FCPP_PART_JOIN 6
+int fcpp_mission_solve(fcpp_ctx *ctx, int mode, int64_t n_fields, const int64_t *item_offsets_dev, const int64_t *item_offsets_host, int64_t n_items,
+                       const int64_t *item_path_dev, const int64_t *item_path_host, const int32_t *item_closed_dev, int64_t n_paths,
+                       const int64_t *path_offsets_dev, const int64_t *path_offsets_host, int64_t n_samples, const double *x_dev,
+                       const double *y_dev, const double *heading_dev, const int8_t *part_dev, const int8_t *gear_dev, const double *entry_x_dev,
+                       const double *entry_y_dev, const double *entry_h_dev, const double *exit_x_dev, const double *exit_y_dev,
+                       const double *exit_h_dev, double radius, int64_t stride, int32_t *status_dev, double *transit_length_dev,
+                       int32_t *skipped_dev, int64_t *item_station_dev, int64_t *slot_item_dev, int32_t *slot_word_dev, double *slot_seg_dev,
+                       double *slot_total_dev);
+int fcpp_mission_counts(fcpp_ctx *ctx, int mode, int64_t n_fields, const int64_t *item_offsets_dev, const int64_t *item_offsets_host, int64_t n_items,
+                        const int64_t *item_path_dev, const int64_t *item_path_host, const int32_t *item_closed_dev, int64_t n_paths,
+                        const int64_t *path_offsets_dev, const int64_t *path_offsets_host, int64_t n_samples, const int32_t *status_dev,
+                        const int64_t *item_station_dev, const int64_t *slot_item_dev, const int32_t *slot_word_dev, const double *slot_seg_dev,
+                        double spacing, int64_t *out_path_offsets_dev, int64_t *out_path_offsets_host, int64_t *slot_offsets_dev);
+int fcpp_mission_fill(fcpp_ctx *ctx, int mode, int64_t n_fields, const int64_t *item_offsets_dev, const int64_t *item_offsets_host, int64_t n_items,
+                      const int64_t *item_path_dev, const int64_t *item_path_host, const int32_t *item_closed_dev, int64_t n_paths,
+                      const int64_t *path_offsets_dev, const int64_t *path_offsets_host, int64_t n_samples, const double *x_dev, const double *y_dev,
+                      const double *heading_dev, const double *kappa_dev, const int8_t *part_dev, const int8_t *gear_dev,
+                      const double *entry_x_dev, const double *entry_y_dev, const double *entry_h_dev, double radius, double spacing,
+                      const int32_t *status_dev, const int64_t *item_station_dev, const int64_t *slot_item_dev, const int32_t *slot_word_dev,
+                      const double *slot_seg_dev, const int64_t *slot_offsets_dev, int64_t total_samples, double *out_x_dev, double *out_y_dev,
+                      double *out_heading_dev, double *out_kappa_dev, int8_t *out_part_dev, int8_t *out_gear_dev, int32_t *out_slot_dev,
+                      int64_t *out_src_dev);
+/* The host twin, the same bits: solve + counts + fill in one call.  Every output may be NULL; the samples below cap (cap 0 or all eight
+ * NULL: none).  Host pointers throughout.  Test infrastructure only. */
+int fcpp_debug_mission_paths(int mode, int64_t n_fields, const int64_t *item_offsets, int64_t n_items, const int64_t *item_path,
+                             const int32_t *item_closed, int64_t n_paths, const int64_t *path_offsets, int64_t n_samples, const double *x,
+                             const double *y, const double *heading, const double *kappa, const int8_t *part, const int8_t *gear,
+                             const double *entry_x, const double *entry_y, const double *entry_h, const double *exit_x, const double *exit_y,
+                             const double *exit_h, double radius, int64_t stride, double spacing, int32_t *status, double *transit_length,
+                             int32_t *skipped, int64_t *item_station, int64_t *slot_item, int32_t *slot_word, double *slot_seg, double *slot_total,
+                             int64_t *out_path_offsets, int64_t *slot_offsets, int64_t cap, double *out_x, double *out_y, double *out_heading,
+                             double *out_kappa, int8_t *out_part, int8_t *out_gear, int32_t *out_slot, int64_t *out_src);
+
 /* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
  * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it
  * shares and whose input it makes: boundary -> headland pass centre lines -> work area -> swaths -> route.  Nothing here feeds fcpp_batch_plan.

@@ -1,0 +1,333 @@
+"""What the mission-path tests share: the host twin's caller (fcpp_debug_mission_paths), path sets concatenated as the Python layer does it,
+the numpy oracle (d(a, b) from fcpp_debug_dubins / fcpp_debug_rs, the min-plus chain and the first-lowest argmin in numpy: no code shared
+with csrc/fcpp_missionfn.h), the numpy rebuild of the samples, and the scenes: HOLED_SQUARE with two headland passes (outer and pond rings),
+its field path and a patch set; a batch of synthetic fields with every special case of the rule."""
+import functools
+
+import numpy as np
+
+from field_coverage_path_planning_amd import _lib as L
+from tests.test_field_paths_host import host_paths, host_solve_full, stored_order, wrap_diff
+from tests.test_headland_paths_host import host_hpaths
+from tests.test_inset_host import HostInset
+from tests.test_route_host import HOLED_SQUARE, cut_with_angle, host_lengths
+
+COLS = (('x', np.float64), ('y', np.float64), ('heading', np.float64), ('kappa', np.float64), ('part', np.int8), ('gear', np.int8))
+FIELD_OUTS = (('status', np.int32), ('transit_length', np.float64), ('skipped', np.int32))
+ITEM_OUTS = (('item_station', np.int64),)
+SLOT_OUTS = (('slot_item', np.int64), ('slot_word', np.int32), ('slot_seg', np.float64), ('slot_total', np.float64))
+SOLVE_OUTS = FIELD_OUTS + ITEM_OUTS + SLOT_OUTS
+SAMPLE_OUTS = COLS + (('slot', np.int32), ('src', np.int64))
+P_TOL = 1e-9          # the connectors' documented bound on where a sampled connector ends [m]
+
+SCENE_W, SCENE_R, SCENE_SPACING, SCENE_STRIDE = 2.0, 1.5, 0.5, 4
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+def _cols(pose):
+    if pose is None:
+        return None, None, None
+    pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(-1, 3)
+    return tuple(np.ascontiguousarray(pose[:, k]) for k in range(3))
+
+
+def pack_sets(sets):
+    """path sets (dicts: offsets and the six columns) -> one set, and the first path of every set in it"""
+    first = np.concatenate([[0], np.cumsum([len(s['offsets']) - 1 for s in sets])]).astype(np.int64)
+    base = np.concatenate([[0], np.cumsum([len(s['x']) for s in sets])]).astype(np.int64)
+    ps = {k: np.ascontiguousarray(np.concatenate([np.asarray(s[k]) for s in sets] + [np.zeros(0, t)]).astype(t)) for k, t in COLS}
+    ps['offsets'] = np.ascontiguousarray(np.concatenate([np.asarray(s['offsets'][:-1]) + base[k] for k, s in enumerate(sets)] + [[base[-1]]]), dtype=np.int64)
+    return ps, first
+
+
+def path_set(paths):
+    """a list of column dicts -> a path set"""
+    off = np.concatenate([[0], np.cumsum([len(p['x']) for p in paths])]).astype(np.int64)
+    ps = {k: np.concatenate([np.asarray(p[k]) for p in paths] + [np.zeros(0, t)]).astype(t) for k, t in COLS}
+    ps['offsets'] = off
+    return ps
+
+
+def items_of(fields):
+    """per field a list of (path, closed) -> item_off, item_path, item_closed"""
+    off = np.concatenate([[0], np.cumsum([len(f) for f in fields])]).astype(np.int64)
+    flat = [it for f in fields for it in f]
+    return off, np.asarray([p for p, _ in flat], np.int64).reshape(-1), np.asarray([c for _, c in flat], np.int32).reshape(-1)
+
+
+def first_slots(item_off):
+    return 2 * item_off + np.arange(len(item_off))
+
+
+def host_mission(mode, ps, items, radius, stride, spacing, entry=None, exit=None, expect=0, samples=True, drop=(), **kw):
+    """fcpp_debug_mission_paths: sized with cap = 0, then filled -> dict of arrays (the call's error code under 'rc').  Outputs are
+    pre-filled with -9 so that the rows the call leaves alone show.  kw: arguments replaced (by the names used below)"""
+    lib = L.load()
+    item_off, item_path, item_closed = items
+    a = dict(n_fields=len(item_off) - 1, item_off=item_off, n_items=len(item_path), item_path=item_path, item_closed=item_closed,
+             n_paths=len(ps['offsets']) - 1, path_off=ps['offsets'], n_samples=len(ps['x']), radius=float(radius), stride=stride, spacing=float(spacing))
+    a.update({k: ps[k] for k, _ in COLS})
+    a.update(kw)
+    nf, ni = max(a['n_fields'], 0), max(a['n_items'], 0)
+    ns = 2 * ni + nf if nf else 0
+    out = {}
+    for group, n in (('FIELD_OUTS', nf), ('ITEM_OUTS', ni), ('SLOT_OUTS', ns)):
+        for k, t in globals()[group]:
+            out[k] = np.full((n, 5) if k == 'slot_seg' else n, -9, t)
+    out['offsets'], out['slot_offsets'] = np.full(nf + 1, -9, np.int64), np.full(ns + 1, -9, np.int64)
+    ent, ext = _cols(entry), _cols(exit)
+    ptr = lambda k: None if k in drop else _p(out[k])
+    head = (mode, a['n_fields'], _p(a['item_off']), a['n_items'], _p(a['item_path']), _p(a['item_closed']), a['n_paths'], _p(a['path_off']), a['n_samples'],
+            *[_p(a[k]) for k, _ in COLS], *[_p(c) for c in ent], *[_p(c) for c in ext], a['radius'], a['stride'], a['spacing'],
+            *[ptr(k) for k, _ in SOLVE_OUTS], ptr('offsets'), ptr('slot_offsets'))
+    rc = lib.fcpp_debug_mission_paths(*head, 0, *([None] * 8))
+    assert rc == expect, lib.fcpp_last_error()
+    out['rc'] = rc
+    if rc or not samples or 'offsets' in drop:
+        return out
+    total = int(out['offsets'][-1])
+    for k, t in SAMPLE_OUTS:
+        out['p_' + k] = np.full(total, 77, t)
+    assert lib.fcpp_debug_mission_paths(*head, total, *[_p(out['p_' + k]) for k, _ in SAMPLE_OUTS]) == 0
+    return out
+
+
+# ---- the oracle ---------------------------------------------------------------------------------------------------------------------------
+def nodes_of(ps, path, closed, stride):
+    """-> the global samples of the item's nodes (in == out for a closed item), or (in, out) of an open one"""
+    p0, p1 = int(ps['offsets'][path]), int(ps['offsets'][path + 1])
+    if not closed:
+        return (np.array([p0]), np.array([p1 - 1])) if p1 > p0 else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    g = p0 + np.arange(0, max(p1 - p0 - 1, 0), stride)
+    g = g[np.isin(ps['part'][g], (0, 4)) & (ps['gear'][g] == 1)]
+    return g, g
+
+
+def oracle(mode, ps, items, radius, stride, entry=None, exit=None):
+    """per field: status, skipped, transit, the chosen station per item (-1: open or skipped) and the joints in driving order as
+    (local slot, from pose, to pose); None beyond status and skipped for a field that fails"""
+    item_off, item_path, item_closed = items
+    pose = np.column_stack([ps['x'], ps['y'], ps['heading']])
+    res = []
+    for f in range(len(item_off) - 1):
+        layers, skipped, status = [], 0, 0
+        for i in range(int(item_off[f]), int(item_off[f + 1])):
+            gin, gout = nodes_of(ps, int(item_path[i]), bool(item_closed[i]), stride)
+            if len(gin) == 0:
+                skipped += 1
+            else:
+                layers.append((i, gin, gout))
+            if item_closed[i] and len(gin) > L.MISSION_MAX_STATIONS:
+                status = L.EUNSUPPORTED
+        if status:
+            res.append(dict(status=status, skipped=skipped))
+            continue
+        ent = None if entry is None else np.asarray(entry, dtype=np.float64).reshape(-1, 3)[f]
+        ext = None if exit is None else np.asarray(exit, dtype=np.float64).reshape(-1, 3)[f]
+        c, prev_out, preds = (None, None, []) if ent is None else (np.zeros(1), ent[None, :], [])
+        for i, gin, gout in layers:
+            n = len(gin)
+            if c is None:
+                c_new, pred = np.zeros(n), np.zeros(n, np.int64)
+            else:
+                m = len(c)
+                D = host_lengths(np.repeat(prev_out, n, axis=0), np.tile(pose[gin], (m, 1)), radius, mode).reshape(m, n)
+                S = c[:, None] + D
+                S = np.where(S < np.inf, S, np.inf)
+                pred = np.argmin(S, axis=0)
+                c_new = S[pred, np.arange(n)]
+            preds.append(pred)
+            c, prev_out = c_new, pose[gout]
+        chosen = {}
+        if layers:
+            S = c if ext is None else c + host_lengths(prev_out, np.tile(ext, (len(c), 1)), radius, mode)
+            b = int(np.argmin(np.where(S < np.inf, S, np.inf)))
+            for (i, gin, gout), pred in zip(layers[::-1], preds[::-1]):
+                chosen[i] = b
+                b = int(pred[b])
+        station = {int(i): -1 for i in range(int(item_off[f]), int(item_off[f + 1]))}
+        joints, frm, j = [], ent, 0
+        for i, gin, gout in layers:
+            if frm is not None:
+                joints.append((2 * j, frm, pose[gin[chosen[i]]]))
+            if item_closed[i]:
+                station[i] = int(gin[chosen[i]])
+            frm = pose[gout[chosen[i]]]
+            j += 1
+        if frm is not None and ext is not None:
+            joints.append((2 * j, frm, ext))
+        transit, recs = 0.0, []
+        for s, a, b in joints:
+            word, seg, tot = host_solve_full(a, b, radius, mode)
+            recs.append((s, a, b, int(word[0]), seg[0], float(tot[0])))
+            transit = transit + float(tot[0])
+        if any(r[3] < 0 for r in recs):
+            res.append(dict(status=L.EINVAL, skipped=skipped))
+            continue
+        res.append(dict(status=0, skipped=skipped, transit=transit, station=station, joints=recs, kept=[i for i, _, _ in layers]))
+    return res
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def check_against_oracle(mode, got, ps, items, radius, stride, entry=None, exit=None):
+    """the twin's records against the oracle's: equal stations, equal bits of transit_length, word, seg, total; failed rows left alone"""
+    item_off = items[0]
+    want = oracle(mode, ps, items, radius, stride, entry, exit)
+    fs = first_slots(item_off)
+    ns = 5 if mode else 3
+    for f, w in enumerate(want):
+        assert got['status'][f] == w['status'] and got['skipped'][f] == w['skipped'], f
+        isl, ssl = slice(int(item_off[f]), int(item_off[f + 1])), slice(int(fs[f]), int(fs[f + 1]))
+        if w['status']:
+            assert np.isnan(got['transit_length'][f]) and got['offsets'][f + 1] == got['offsets'][f]
+            assert np.all(got['item_station'][isl] == -9) and np.all(got['slot_item'][ssl] == -9) and np.all(got['slot_word'][ssl] == -9)
+            assert np.all(got['slot_seg'][ssl] == -9) and np.all(got['slot_total'][ssl] == -9)
+            continue
+        assert bits(got['transit_length'][f]) == bits(w['transit']), (f, got['transit_length'][f], w['transit'])
+        assert [int(v) for v in got['item_station'][isl]] == [w['station'][i] for i in range(isl.start, isl.stop)], f
+        joint = {s: (word, seg, tot) for s, _, _, word, seg, tot in w['joints']}
+        for s in range(ssl.stop - ssl.start):
+            g = ssl.start + s
+            if s in joint:
+                word, seg, tot = joint[s]
+                assert got['slot_item'][g] == -1 and got['slot_word'][g] == word and bits(got['slot_total'][g]) == bits(tot)
+                assert np.array_equal(bits(got['slot_seg'][g][:ns]), bits(seg)) and np.all(got['slot_seg'][g][ns:] == 0.0)
+            else:
+                kept = w['kept']
+                assert got['slot_item'][g] == (kept[s // 2] if s % 2 == 1 and s // 2 < len(kept) else -1), (f, s)
+                assert got['slot_word'][g] == -1 and np.isnan(got['slot_total'][g]) and np.all(np.isnan(got['slot_seg'][g]))
+    return want
+
+
+def check_samples(mode, got, ps, items, radius, spacing, entry=None):
+    """the samples rebuilt in numpy: the rotation, the copied columns bit for bit through src, the joints from the out-pose before them to
+    within P_TOL of the in-pose behind them, junctions doubled, slot and offsets consistent"""
+    item_off, item_path, item_closed = items
+    fs, so = first_slots(item_off), got['slot_offsets']
+    assert so[0] == 0 and np.all(np.diff(so) >= 0) and so[-1] == len(got['p_x'])
+    assert np.array_equal(got['offsets'], so[fs])
+    src = got['p_src']
+    copied = src >= 0
+    for k, _ in COLS:
+        assert np.array_equal(got['p_' + k][copied].view(np.uint8), ps[k][src[copied]].view(np.uint8)), k
+    assert np.all(got['p_part'][~copied] == L.PART_JOIN) and np.all(np.abs(got['p_gear'][~copied]) == 1)
+    if mode == 0:
+        assert np.all(got['p_gear'][~copied] == 1)
+    pose = np.column_stack([got['p_x'], got['p_y'], got['p_heading']])
+    for f in range(len(item_off) - 1):
+        if got['status'][f]:
+            continue
+        prev_out = None if entry is None else np.asarray(entry, dtype=np.float64).reshape(-1, 3)[f]
+        pending = None          # a joint's last sample, waiting for the in-pose behind it
+        for g in range(int(fs[f]), int(fs[f + 1])):
+            sl = slice(int(so[g]), int(so[g + 1]))
+            assert np.all(got['p_slot'][sl] == g - fs[f])
+            it = int(got['slot_item'][g])
+            if it >= 0:
+                p0, p1 = int(ps['offsets'][item_path[it]]), int(ps['offsets'][item_path[it] + 1])
+                if item_closed[it]:
+                    k0 = int(got['item_station'][it]) - p0
+                    assert 0 <= k0 < p1 - p0 - 1
+                    want = p0 + (k0 + np.arange(p1 - p0 + 1)) % (p1 - p0)
+                else:
+                    want = np.arange(p0, p1)
+                assert np.array_equal(src[sl], want), (f, g)
+                if pending is not None:
+                    assert np.hypot(*(pending[:2] - pose[sl.start][:2])) <= P_TOL and wrap_diff(pending[2], pose[sl.start][2]) <= P_TOL, (f, g)
+                    pending = None
+                prev_out = pose[sl.stop - 1]
+            elif got['slot_word'][g] >= 0:
+                assert sl.stop - sl.start >= 2 and np.all(src[sl] == -1) and prev_out is not None
+                assert np.hypot(*(pose[sl.start][:2] - prev_out[:2])) <= P_TOL and wrap_diff(pose[sl.start][2], prev_out[2]) <= P_TOL, (f, g)
+                if mode == 0:
+                    T = float(got['slot_total'][g])
+                    K = int(np.floor(T / spacing)) + 1
+                    assert sl.stop - sl.start == K + (1 if (K - 1) * spacing < T else 0)
+                    step = np.hypot(np.diff(got['p_x'][sl]), np.diff(got['p_y'][sl]))
+                    assert np.all(step <= spacing + P_TOL)
+                pending = pose[sl.stop - 1]
+            else:
+                assert sl.stop == sl.start
+        if pending is not None:          # (the exit joint: checked by the caller against the exit pose)
+            got.setdefault('last', {})[f] = pending
+
+
+# ---- synthetic paths ----------------------------------------------------------------------------------------------------------------------
+def circle_loop(n, r, cx=0.0, cy=0.0, part=0, start=0.0):
+    """a closed loop of n + 1 samples, the last repeating the first pose"""
+    a = start + 2.0 * np.pi * (np.arange(n + 1) % n) / n
+    return dict(x=cx + r * np.cos(a), y=cy + r * np.sin(a), heading=np.arctan2(np.cos(a), -np.sin(a)), kappa=np.full(n + 1, 1.0 / r),
+                part=np.full(n + 1, part, np.int8), gear=np.ones(n + 1, np.int8))
+
+
+def line(x0, y0, x1, y1, n):
+    t = np.linspace(0.0, 1.0, n)
+    return dict(x=x0 + t * (x1 - x0), y=y0 + t * (y1 - y0), heading=np.full(n, np.arctan2(y1 - y0, x1 - x0)), kappa=np.zeros(n),
+                part=np.zeros(n, np.int8), gear=np.ones(n, np.int8))
+
+
+def empty():
+    return {k: np.zeros(0, t) for k, t in COLS}
+
+
+def batch_scene():
+    """-> ps, items, stride, and what each field is there for (stride 1: every sample short of the last is a candidate)"""
+    nan_line = line(0.0, 0.0, 10.0, 0.0, 21)
+    nan_line['x'] = nan_line['x'].copy()
+    nan_line['x'][-1] = np.nan
+    paths = [line(-20.0, -5.0, 20.0, -5.0, 41),                  # 0
+             line(20.0, 5.0, -20.0, 5.0, 41),                    # 1
+             circle_loop(130, 12.0),                             # 2: 130 stations
+             circle_loop(70, 7.0, 1.0, 2.0, start=1.0),          # 3: 70 stations
+             empty(),                                            # 4: a failed ring
+             circle_loop(16, 5.0, part=1),                       # 5: a loop without a station
+             nan_line,                                           # 6
+             circle_loop(L.MISSION_MAX_STATIONS, 40.0),          # 7: exactly 1024 stations
+             circle_loop(L.MISSION_MAX_STATIONS + 1, 40.0),      # 8: 1025
+             circle_loop(9, 3.0, -4.0, 1.0, part=4)]             # 9
+    fields = [[(0, 0), (1, 0)],                                  # 0: no loops
+              [(2, 1), (3, 1), (9, 1)],                          # 1: only loops; 130 sources against 70 targets
+              [(9, 1), (4, 1), (0, 0), (5, 1), (4, 0), (3, 1)],  # 2: skipped items of every kind between kept ones
+              [(6, 0), (3, 1)],                                  # 3: a chosen pose that is not finite
+              [(0, 0), (7, 1), (1, 0)],                          # 4: exactly the limit
+              [(0, 0), (8, 1), (1, 0)],                          # 5: one more
+              [],                                                # 6: no items
+              [(1, 0)],                                          # 7: one open item
+              [(3, 1)],                                          # 8: one loop
+              [(4, 0), (5, 1)]]                                  # 9: nothing kept
+    return path_set(paths), items_of(fields), 1
+
+
+def batch_ends(n):
+    k = np.arange(n, dtype=np.float64)
+    return np.column_stack([-30.0 - k, -20.0 + 2 * k, 0.3 + 0.1 * k]), np.column_stack([35.0 + k, 25.0 - k, 1.2 - 0.2 * k])
+
+
+# ---- the scene: HOLED_SQUARE, two passes -------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def holed_scene(mode=0):
+    """-> ps, items (headland first: the passes outermost first, then the field path, then the patch set), the sets' first paths"""
+    hi = HostInset([HOLED_SQUARE], [SCENE_W / 2, 3 * SCENE_W / 2])
+    pair = np.repeat(np.arange(2), np.diff(hi.pro))
+    rg = dict(roff=hi.ovo.copy(), x=hi.x, y=hi.y, src=hi.src, dist=np.asarray([SCENE_W / 2, 3 * SCENE_W / 2])[pair])
+    hp = host_hpaths(rg, SCENE_R, mode=mode, spacing=SCENE_SPACING)
+    assert np.all(hp['status'] == 0) and len(hp['offsets']) - 1 == 4          # (an outer and a pond ring per pass)
+    work = HostInset([HOLED_SQUARE], [2 * SCENE_W]).rings(0, 0)
+    cut = cut_with_angle([work], 0.0, SCENE_W)
+    fp = host_paths(cut, SCENE_R, SCENE_SPACING, mode=mode, order=stored_order(cut['offsets']))
+    pcut = cut_with_angle([[(30.0, 30.5), (38.0, 30.5), (38.0, 37.5), (30.0, 37.5)]], 0.0, SCENE_W)
+    pp = host_paths(pcut, SCENE_R, SCENE_SPACING, mode=mode, order=stored_order(pcut['offsets']))
+    assert fp['status'][0] == 0 and pp['status'][0] == 0 and pp['total'] > 0
+    ps, first = pack_sets([hp, fp, pp])
+    items = items_of([[(int(first[0]) + r, 1) for r in range(4)] + [(int(first[1]), 0), (int(first[2]), 0)]])
+    return ps, items, first
+
+
+def holed_ends():
+    return np.array([[-5.0, -3.0, 0.4]]), np.array([[45.0, 44.0, 1.0]])
