@@ -22,6 +22,7 @@ TRANSIT_MAX_STATIONS = 2048      # FCPP_TRANSIT_MAX_STATIONS
 PART_LOOP_RIDE = 5               # FCPP_PART_LOOP_RIDE
 MISSION_MAX_STATIONS = 1024      # FCPP_MISSION_MAX_STATIONS
 PART_JOIN = 6                    # FCPP_PART_JOIN
+SPEED_REST_START, SPEED_REST_END, SPEED_STOP_AT_CUSPS = 1, 2, 4      # FCPP_SPEED_*
 MISSION_BLOCK = 256              # threads of a workgroup of the mission-path kernels: four wavefronts, a target node each
 TRANSIT_BLOCK = 256              # threads of a workgroup of the loop-transit kernels, the pick pass's tile of stations
 
@@ -101,6 +102,12 @@ class CoverJob(C.Structure):
                 ('nx', C.c_int32), ('ny', C.c_int32), ('n_a', C.c_int32), ('n_b', C.c_int32),
                 ('pts_first', C.c_int64), ('grid_first', C.c_int64), ('strict', C.c_int32), ('region', C.c_int32),
                 ('outer', C.c_double * 12), ('inner', C.c_double * 12)]
+
+
+class SpeedParams(C.Structure):
+    """fcpp_speed_params (include/fcpp.h)"""
+    _fields_ = [('nominal_kmh', C.c_double * 8)] + [(n, C.c_double) for n in (
+        'reverse_kmh', 'turn_kmh', 'a_lat', 'a_acc', 'a_dec', 'safety_factor', 'kappa_eps')] + [('flags', C.c_uint32), ('_pad', C.c_uint32)]
 
 
 SETUP_AUTO, SETUP_HOST, SETUP_DEVICE = 0, 1, 2      # fcpp_ctx_set_setup
@@ -211,6 +218,8 @@ PROTOTYPES = [
      + [C.c_double] + [_VP] * 3),
     ('fcpp_mission_fill', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 9
      + [C.c_double, C.c_double] + [_VP] * 6 + [C.c_int64] + [_VP] * 8),
+    ('fcpp_path_speeds', C.c_int, [_VP, C.POINTER(SpeedParams), C.c_int64, _VP, C.c_int64] + [_VP] * 9),
+    ('fcpp_debug_path_speeds', C.c_int, [C.POINTER(SpeedParams), C.c_int64, _VP, C.c_int64] + [_VP] * 8),
     ('fcpp_headland_path_counts', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]
      + [_VP] * 7),
     ('fcpp_headland_path_fill', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double]

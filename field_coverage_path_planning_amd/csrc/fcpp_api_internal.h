@@ -113,6 +113,9 @@ void free_paths_cache(fcpp_ctx *c);
 int trajectory_paths(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, const double *x,
                      const double *y, const double *v, const uint32_t *fs, double *s, double *t, double *heading, double *totals);
 
+// the tile table of a path set on a checked context (fcpp_paths.cpp: path_set, the context's cache), for the path operators of other glue files
+int path_tiling(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, DevTiling **out);
+
 }  // namespace fcpp
 
 struct fcpp_ctx {

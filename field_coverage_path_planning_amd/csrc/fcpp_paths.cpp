@@ -150,6 +150,14 @@ int fcpp::trajectory_paths(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets,
     return FCPP_OK;
 }
 
+int fcpp::path_tiling(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, const int64_t *offsets_host, int64_t total, DevTiling **out)
+{
+    PathTiling *ps = nullptr;
+    const int rc = path_set(c, n_paths, offsets, offsets_host, total, &ps);
+    if (rc == FCPP_OK) *out = &ps->dt;
+    return rc;
+}
+
 extern "C" {
 
 int fcpp_curvature(fcpp_ctx *c, int64_t n_paths, const int64_t *offsets, int64_t total, const double *x,

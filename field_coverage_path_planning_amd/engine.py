@@ -2821,6 +2821,83 @@ def patch_swaths(regions, width, angle, margin=None, join=None, device=None):
     return ss, PatchInfo(region, rec[:, 2].contiguous(), rec[:, 3].contiguous(), status, frame, rec, margin, join)
 
 
+# ---- path speeds (fcpp_path_speeds; the rule: include/fcpp.h) -----------------------------------------------------------------------------
+@dataclass
+class PathSpeeds:
+    """path_speeds(): the speed of every sample of a path set, in the units and CSR form trajectory(), validate() and trajectory_sample()
+    take.  Path p owns the samples offsets[p] .. offsets[p + 1]."""
+    v: object                   # (total) float64 [km/h]: the greatest profile under the caps and the two acceleration limits; 0 at a stop
+    cap: object                 # (total) float64 [km/h]: the pointwise cap, 0 at a stop
+    status: object              # (n) int32: 0, or FCPP_EINVAL (a sample that is not finite, a part outside 0 .. 7, a gear other than +-1): v and cap NaN
+    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy or None
+    offsets_host: object
+    x: object = None            # the path set's columns the speeds belong to (what trajectory() below reads)
+    y: object = None
+    gear: object = None
+    params: object = None       # the L.SpeedParams of the call
+
+    def trajectory(self):
+        """trajectory() of the paths at these speeds, the gear -1 samples flagged FCPP_KIND_REVERSE so that the headings are the vehicle's
+        -> (s, t, heading, totals); totals[p] = (length, time) of path p"""
+        fs = (self.gear < 0).to(_torch().int32) * L.KIND_REVERSE
+        return trajectory(self.x, self.y, self.v, flagseg=fs, offsets=self.offsets if self.offsets_host is None else self.offsets_host,
+                          device=self.v.device.index)
+
+
+def speed_params(vehicle, reverse_kmh=2.5, turn_kmh=None, a_dec=None, rest_start=True, rest_end=True, stop_at_cusps=True, nominal=None):
+    """L.SpeedParams from a vehicle: parts 0 and 4 work at max_work_speed_kmh, parts 1, 2, 3, 5, 6 (and the spare 7) drive at
+    max_headland_speed_kmh (nominal: eight values by part instead); turn_kmh = headland_turn_speed_kmh; a_acc = max_longitudinal_accel and
+    a_dec likewise unless given; a_lat, safety_factor and kappa_eps = 1e-6 as the reference has them (MLP:496-499); reverse_kmh: MLP:1080"""
+    p = L.SpeedParams()
+    if nominal is None:
+        nominal = [vehicle.max_work_speed_kmh if k in (0, 4) else vehicle.max_headland_speed_kmh for k in range(8)]
+    if len(nominal) != 8:
+        raise ValueError('nominal takes eight speeds, one per part 0 .. 7')
+    for k in range(8):
+        p.nominal_kmh[k] = float(nominal[k])
+    p.reverse_kmh = float(reverse_kmh)
+    p.turn_kmh = float(vehicle.headland_turn_speed_kmh if turn_kmh is None else turn_kmh)
+    p.a_lat, p.safety_factor, p.kappa_eps = vehicle.max_lateral_accel, vehicle.safety_factor, 1e-6
+    p.a_acc = vehicle.max_longitudinal_accel
+    p.a_dec = float(vehicle.max_longitudinal_accel if a_dec is None else a_dec)
+    p.flags = (L.SPEED_REST_START if rest_start else 0) | (L.SPEED_REST_END if rest_end else 0) | (L.SPEED_STOP_AT_CUSPS if stop_at_cusps else 0)
+    return p
+
+
+def path_speeds(paths, vehicle, reverse_kmh=2.5, turn_kmh=None, a_dec=None, rest_start=True, rest_end=True, stop_at_cusps=True, nominal=None,
+                device=None):
+    """The speed profile of sampled paths (fcpp_path_speeds) -> PathSpeeds.  paths: a FieldPaths, HeadlandPaths, TransitPaths or
+    MissionPaths, or a tuple (offsets, x, y, kappa, part, gear).  Caps from part, gear and the stored kappa (speed_params() says which);
+    the vehicle stands at every Reeds-Shepp cusp (stop_at_cusps) and at the path ends (rest_start, rest_end); in between the greatest
+    profile that speeds up by at most max_longitudinal_accel and brakes by at most a_dec."""
+    torch = _torch()
+    if isinstance(paths, (tuple, list)):
+        offsets, x, y, kappa, part, gear = paths
+    else:
+        offsets, x, y, kappa, part, gear = (paths.offsets if paths.offsets_host is None else paths.offsets_host, paths.x, paths.y, paths.kappa,
+                                            paths.part, paths.gear)
+    if device is None and isinstance(x, torch.Tensor) and x.is_cuda:
+        device = x.device.index
+    ctx = get_context(device)
+    dev = torch.device('cuda', ctx.device)
+    x, y, kappa = _dev_f64(x, dev), _dev_f64(y, dev), _dev_f64(kappa, dev)
+    i8 = lambda a: (a.to(device=dev, dtype=torch.int8).contiguous() if isinstance(a, torch.Tensor)
+                    else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int8), device=dev))
+    part, gear = i8(part), i8(gear)
+    total = x.numel()
+    if not (y.numel() == kappa.numel() == part.numel() == gear.numel() == total):
+        raise ValueError('x, y, kappa, part and gear hold one value per sample')
+    off, off_h = _offsets(offsets, total, dev)
+    n = off.numel() - 1
+    prm = speed_params(vehicle, reverse_kmh, turn_kmh, a_dec, rest_start, rest_end, stop_at_cusps, nominal)
+    v, cap = torch.empty_like(x), torch.empty_like(x)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ctx.bind_stream()
+    L.check(ctx.lib.fcpp_path_speeds(ctx.handle, C.byref(prm), n, _ptr(off), total, _ptr(x), _ptr(y), _ptr(kappa), _ptr(part), _ptr(gear), _ptr(v),
+                                     _ptr(cap), _ptr(status), _host_ptr(off_h)))
+    return PathSpeeds(v, cap, status, off, off_h, x, y, gear, prm)
+
+
 _drive_headland = headland_paths      # (plan_polygon_fields has a flag of that name)
 
 
@@ -2844,11 +2921,12 @@ class PolygonPlan:
     patch_paths: object = None          # FieldPaths over `patch`, routed per field
     coverage_after: object = None       # PolygonCoverage of `fields` under the plan's paths AND patch_paths, its cells kept
     mission: object = None              # MissionPaths: loops, field path and patch passes joined into one drive per field (mission=...), else None
+    speeds: object = None               # PathSpeeds of `mission` when there is one, else of `paths` (speeds=vehicle), else None
 
 
 def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_cost=0.0, reversing=False, starts=8, entry=None, exit=None,
                         arc_step=0.1, headland_paths=False, coverage_resolution=None, device=None, clear_of=None, reshape=False,
-                        price_clear=False, detour=False, missed_min_area=None, patch=False, mission=None):
+                        price_clear=False, detour=False, missed_min_area=None, patch=False, mission=None, speeds=None):
     """The whole chain for a batch of polygon fields, every stage one batched call on the device: headland(passes) -> best_swath_angle over
     `angles` -> polygon_swaths at each field's best angle -> route_swaths(spacing=spacing) -> field_paths.  -> PolygonPlan.  A field whose
     work area is empty, or for which no angle is valid, carries its stage's status (swaths.status) and has no samples; the rest is planned.
@@ -2881,7 +2959,10 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
     -> innermost, then `paths`, then patch_paths if present; 'headland_last' drives `paths`, the patch paths, then the passes innermost ->
     outermost.  entry / exit then belong to the MISSION: the router still prices them, the field paths are built without them.  With
     clear_of the chosen joints are tested against the same region (mission.blocked).  None: the chain makes exactly the calls it makes
-    without it."""
+    without it.
+    speeds=vehicle: the speed of every sample of the drive (path_speeds() at its defaults for that vehicle: PolygonPlan.speeds) -- of
+    `mission` when there is one, else of `paths`; its trajectory() gives time stamps and totals.  None: the chain makes exactly the calls
+    it makes without it."""
     if mission not in (None, 'headland_first', 'headland_last'):
         raise ValueError("mission must be None, 'headland_first' or 'headland_last'")
     if mission is not None and not headland_paths:
@@ -2932,6 +3013,8 @@ def plan_polygon_fields(fields, width, radius, spacing, angles, passes=1, turn_c
         plan.mission = mission_paths((hp,) + open_sets if mission == 'headland_first' else open_sets + (hp,), radius, spacing, reversing=reversing,
                                      entry=entry, exit=exit, device=device, innermost_first=mission == 'headland_last', n_fields=fields.n,
                                      clear_of=region)
+    if speeds is not None:
+        plan.speeds = path_speeds(plan.mission if plan.mission is not None else paths, speeds, device=device)
     return plan
 
 

@@ -1048,6 +1048,54 @@ int fcpp_debug_mission_paths(int mode, int64_t n_fields, const int64_t *item_off
                              int64_t *out_path_offsets, int64_t *slot_offsets, int64_t cap, double *out_x, double *out_y, double *out_heading,
                              double *out_kappa, int8_t *out_part, int8_t *out_gear, int32_t *out_slot, int64_t *out_src);
 
+/* ---- path speeds: the accel-limited speed profile of the polygon chain's paths -----------------------------------------------------------------
+ * Build-defined.  The sampled paths above (field paths, headland paths, loop transits, mission paths) carry per sample an exact pose, a
+ * signed kappa, a part and a gear, but no speed; fcpp_speed_plan cannot supply it: it mirrors the reference's two loops (MLP:467-600), which
+ * restart at every step below 1e-6 m -- every doubled junction and cusp of these paths --, take curvature from chords and never stop.
+ * fcpp_path_speeds gives v in the units and CSR form fcpp_trajectory, fcpp_validate and fcpp_trajectory_sample take.
+ * THE RULE (csrc/fcpp_speedfn.h, one set of expressions for host and device).  Per path p of n samples, speeds in m/s inside, u = v^2:
+ *   - Cap: c_i = the smallest of (nominal_kmh[part_i] / 3.6)^2; (reverse_kmh / 3.6)^2 where gear_i = -1; and, where |kappa_i| > kappa_eps,
+ *     (turn_kmh / 3.6)^2 and (sqrt(a_lat / |kappa_i|) * safety_factor)^2 -- the reference's formula (MLP:496-499) on the stored kappa.
+ *     nominal_kmh is indexed by part: 0 straight working piece, 1 / 2 / 3 connectors, 4 followed arc, FCPP_PART_LOOP_RIDE, FCPP_PART_JOIN.
+ *   - Stops: c_i = 0 at sample 0 with FCPP_SPEED_REST_START, at sample n - 1 with FCPP_SPEED_REST_END, and with FCPP_SPEED_STOP_AT_CUSPS at
+ *     every sample whose gear differs from its predecessor's or its successor's within the path (both samples of a doubled cusp).
+ *   - Steps: d_i = the chord from sample i - 1 to i, fcpp_trajectory's expression.  No threshold: a zero step passes the value on unchanged.
+ *   - Profile: u_i = min over j of  c_j + 2 a_acc (d_(j+1) + .. + d_i) for j <= i  and  c_j + 2 a_dec (d_(i+1) + .. + d_j) for j >= i -- the
+ *     forward sweep u_i = min(c_i, u_(i-1) + 2 a_acc d_i) followed by the backward sweep with a_dec: the greatest profile under the caps and
+ *     both limits.  v_i = sqrt(u_i) * 3.6 [km/h], cap_i = sqrt(c_i) * 3.6.  The device composes the maps in a scan, the host twin walks the
+ *     two sweeps: the same non-negative terms in other groupings, |v_dev - v_host| <= (n + 4) 2^-52 v; cap and the stops (exactly 0) are
+ *     the same bits.  A path's bits may depend on where its tiles lie in the batch, to the same bound.
+ *   - status (int32 per path): 0, or FCPP_EINVAL for a path with a non-finite x, y or kappa, a part outside 0 .. 7 or a gear other than
+ *     +-1: NaN in v and cap over the whole path (every element is still written), found on the device; the other paths are unaffected.
+ *   - Empty and one-sample paths are legal.  v_out and cap_out may each be NULL.
+ * Launches: caps + tile aggregates, the blocked spine of fcpp_speed_plan's scan, apply.  Temporaries: the context's tile table of the path
+ * set (shared with the other path operators).  Traffic: 26 B read twice and 16 B written per sample.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle, parameter block or required array, a parameter that is not
+ * finite and positive (turn_kmh and the nominals may be +inf; a nominal may be 0, a stop), an unknown flag; FCPP_ESIZE -- negative sizes,
+ * offsets that do not span [0, total_points] or decrease.  offsets_host: the host copy, or NULL to have it read back.  Synchronises.
+ * Out of scope: dwell time at a gear change, jerk limits, speed-dependent widths. */
+#define FCPP_SPEED_REST_START 1u
+#define FCPP_SPEED_REST_END 2u
+#define FCPP_SPEED_STOP_AT_CUSPS 4u
+typedef struct fcpp_speed_params {
+    double nominal_kmh[8];      /* by part */
+    double reverse_kmh;         /* cap of the gear -1 samples */
+    double turn_kmh;            /* cap where |kappa| > kappa_eps */
+    double a_lat;               /* [m/s^2] */
+    double a_acc, a_dec;        /* [m/s^2] speeding up, braking */
+    double safety_factor;
+    double kappa_eps;           /* [1/m] */
+    uint32_t flags;             /* FCPP_SPEED_* */
+    uint32_t _pad;
+} fcpp_speed_params;
+int fcpp_path_speeds(fcpp_ctx *ctx, const fcpp_speed_params *params, int64_t n_paths, const int64_t *offsets_dev, int64_t total_points,
+                     const double *x_dev, const double *y_dev, const double *kappa_dev, const int8_t *part_dev, const int8_t *gear_dev,
+                     double *v_out_dev, double *cap_out_dev, int32_t *status_out_dev, const int64_t *offsets_host);
+/* The host twin: the plain sequential two-sweep form of the same header.  Host pointers throughout.  Test infrastructure only. */
+int fcpp_debug_path_speeds(const fcpp_speed_params *params, int64_t n_paths, const int64_t *offsets, int64_t total_points, const double *x,
+                           const double *y, const double *kappa, const int8_t *part, const int8_t *gear, double *v_out, double *cap_out,
+                           int32_t *status_out);
+
 /* ---- headland passes of ANY polygon field: the batched inset --------------------------------------------------------------------------
  * Build-defined (the reference insets a convex quadrilateral by mitres, MLP:867-877).  Standalone like the swath entries, whose field layout it
  * shares and whose input it makes: boundary -> headland pass centre lines -> work area -> swaths -> route.  Nothing here feeds fcpp_batch_plan.
