@@ -888,6 +888,73 @@ def _host_ptr(a):
     return C.c_void_p(a.ctypes.data if a is not None else 0)
 
 
+# ---- the CSR toolkit of the polygon chain's bindings ("the binding layer") -------------------------------------------------
+def _owners(off, total, dtype=None):
+    """the row of every element of a CSR table with the (n + 1) offsets `off`: (total) int64, or `dtype`, on off's device"""
+    torch = _torch()
+    rows = torch.arange(int(off.numel()) - 1, dtype=dtype or torch.int64, device=off.device)
+    return torch.repeat_interleave(rows, off[1:] - off[:-1], output_size=total)
+
+
+def _one_per(t, n, name, each):
+    """a tensor of one value, or of one value per `each`, as n contiguous values; ValueError in the words of `name`"""
+    t = t.reshape(-1)
+    if t.numel() == 1 and n != 1:
+        t = t.expand(n)
+    if t.numel() != n:
+        raise ValueError('%s must be a scalar or hold one %s' % (name, each))
+    return t.contiguous()
+
+
+def _join_csr(offsets, hosts, columns, dtypes, dev):
+    """Several CSR tables laid end to end.  offsets[k]: table k's (n_k + 1) offsets, a tensor; hosts[k]: their numpy copy or None;
+    columns[k]: its element columns, one per entry of `dtypes` -> (first, starts, offsets, offsets_host, columns): where table k's rows
+    and elements start in the join (numpy, one value more than tables), the shifted offsets on `dev`, their host copy when every table
+    brought one (else None), the concatenated columns."""
+    torch = _torch()
+    first = np.concatenate([[0], np.cumsum([int(o.numel()) - 1 for o in offsets])]).astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum([int(c[0].numel()) for c in columns])]).astype(np.int64)
+    total = int(starts[-1])
+    cols = [(torch.cat([c[j].to(dev) for c in columns]) if columns else torch.empty(0, dtype=dt, device=dev)).contiguous()
+            for j, dt in enumerate(dtypes)]
+    off = torch.cat([o[:-1].to(dev) + int(starts[k]) for k, o in enumerate(offsets)] + [torch.full((1,), total, dtype=torch.int64, device=dev)]).contiguous()
+    off_h = None
+    if all(h is not None for h in hosts):
+        off_h = np.ascontiguousarray(np.concatenate([np.asarray(h[:-1], dtype=np.int64) + starts[k] for k, h in enumerate(hosts)] + [[total]]),
+                                     dtype=np.int64)
+    return first, starts, off, off_h, cols
+
+
+def _group_by(owner, n, error=None):
+    """rows by owner -> (order, group_offsets): the stable order that sorts `owner` (an owner's rows stay as given) and the (n + 1) offsets
+    of owners 0 .. n - 1 within it.  error: the ValueError's text for an owner outside 0 .. n - 1; None does not look (such rows then
+    belong to no group)."""
+    torch = _torch()
+    if error is not None and int(owner.numel()) and bool(((owner < 0) | (owner >= n)).any()):
+        raise ValueError(error)
+    order = torch.argsort(owner, stable=True)
+    return order, torch.searchsorted(owner[order], torch.arange(n + 1, dtype=torch.int64, device=owner.device)).to(torch.int64).contiguous()
+
+
+def _counts_fill(n, dev, counts, fill, columns):
+    """The two-call shape of every operator that sizes its own output: (n + 1) offsets and their host copy, the counts entry --
+    counts(offsets, offsets_host), pointers -- writes both; the total is read from the HOST copy; one column of `total` elements per dtype of
+    `columns`; fill(offsets, offsets_host, total, *columns) -> (offsets, offsets_host, *columns).  No stream is bound here."""
+    torch = _torch()
+    off, off_h = torch.empty(n + 1, dtype=torch.int64, device=dev), np.zeros(n + 1, dtype=np.int64)
+    L.check(counts(_ptr(off), _host_ptr(off_h)))
+    total = int(off_h[-1])
+    cols = [torch.empty(total, dtype=dt, device=dev) for dt in columns]
+    L.check(fill(_ptr(off), _host_ptr(off_h), total, *[_ptr(c) for c in cols]))
+    return (off, off_h, *cols)
+
+
+def _sample_columns(*extra):
+    """the dtypes of a path set's six sample columns x, y, heading, kappa, part, gear, and of the caller's behind them"""
+    torch = _torch()
+    return (torch.float64,) * 4 + (torch.int8,) * 2 + extra
+
+
 def curvature(x, y, offsets=None, device=None):
     ctx = get_context(device)
     torch = _torch()
@@ -1058,19 +1125,18 @@ def _conn_sample_solved(ctx, f, word, seg, length, radius, spacing, reversing):
     torch = _torch()
     dev = word.device
     n = int(word.numel())
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    off_h = np.zeros(n + 1, dtype=np.int64)
-    if reversing:
-        L.check(ctx.lib.fcpp_rs_counts(ctx.handle, n, _ptr(word), _ptr(seg), float(spacing), _ptr(off), _host_ptr(off_h)))
-    else:
-        L.check(ctx.lib.fcpp_dubins_counts(ctx.handle, n, _ptr(length), float(spacing), _ptr(off), _host_ptr(off_h)))
-    m = int(off_h[-1])
-    out = {k: torch.empty(m, dtype=torch.float64, device=dev) for k in ('x', 'y', 'heading', 'kappa')}
-    if reversing:
-        out['gear'] = torch.empty(m, dtype=torch.int8, device=dev)
-    entry = ctx.lib.fcpp_rs_sample if reversing else ctx.lib.fcpp_dubins_sample
-    L.check(entry(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing), _ptr(off), m,
-                  *[_ptr(v) for v in out.values()], _host_ptr(off_h)))
+
+    def counts(off, off_h):
+        if reversing:
+            return ctx.lib.fcpp_rs_counts(ctx.handle, n, _ptr(word), _ptr(seg), float(spacing), off, off_h)
+        return ctx.lib.fcpp_dubins_counts(ctx.handle, n, _ptr(length), float(spacing), off, off_h)
+
+    def fill(off, off_h, m, *cols):
+        entry = ctx.lib.fcpp_rs_sample if reversing else ctx.lib.fcpp_dubins_sample
+        return entry(ctx.handle, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(radius), _ptr(word), _ptr(seg), float(spacing), off, m, *cols, off_h)
+
+    off, off_h, *cols = _counts_fill(n, dev, counts, fill, (torch.float64,) * 4 + ((torch.int8,) if reversing else ()))
+    out = dict(zip(('x', 'y', 'heading', 'kappa', 'gear'), cols))          # (gear: the fifth column, with `reversing`)
     out.update(offsets=off, offsets_host=off_h, word=word, seg=seg, length=length, spacing=float(spacing))
     return out
 
@@ -1351,11 +1417,7 @@ def polygon_swaths(fields, angle, width, first=None, min_length=0.0, device=None
     dev = torch.device('cuda', ctx.device)
     pf = polygon_fields(fields, device)
     n = pf.n
-    ang = _dev_f64(angle, dev).reshape(-1)
-    if ang.numel() == 1 and n != 1:
-        ang = ang.expand(n).contiguous()
-    if ang.numel() != n:
-        raise ValueError('angle must be a scalar or hold one value per field')
+    ang = _one_per(_dev_f64(angle, dev), n, 'angle', 'value per field')
     args = (*pf._head(), _ptr(ang), float(width), _first(width, first), float(min_length))
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     off_h = np.zeros(n + 1, dtype=np.int64)
@@ -1476,21 +1538,43 @@ def _route_offsets(soff_h):
     return toff
 
 
-def _route_transit(ctx, ss, lo, hi, radius, reversing):
-    """fields lo .. hi of a SwathSet -> (T, toff, toff_h, soff, soff_h, n_total): their transit blocks and the chunk's own offsets"""
-    torch = _torch()
-    dev = ss.a.device
-    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
-    soff_h = np.ascontiguousarray(ss.offsets_host[lo:hi + 1] - s0, dtype=np.int64)
-    toff_h = _route_offsets(soff_h)
-    soff, toff = torch.as_tensor(soff_h, device=dev), torch.as_tensor(toff_h, device=dev)
-    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
-    ang = ss.angle[lo:hi].contiguous()
-    T = torch.empty(int(toff_h[-1]), dtype=torch.float64, device=dev)
+@dataclass
+class _RouteChunk:
+    """fields lo .. hi of a SwathSet as the router's entries take them, with offsets of the chunk's own; built once per chunk"""
+    soff: object                # (hi - lo + 1) int64, device: the chunk's swath offsets; soff_h: the numpy copy
+    soff_h: object
+    toff: object                # (hi - lo + 1) int64, device: its transit block offsets (_route_offsets); toff_h: the numpy copy
+    toff_h: object
+    ends: object                # ax, ay, bx, by: the swaths' end points as four contiguous columns
+    ang: object                 # (hi - lo) float64: the fields' track angles
+    m: int                      # the chunk's swaths
+
+    @classmethod
+    def of(cls, ss, lo, hi):
+        torch = _torch()
+        dev = ss.a.device
+        s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
+        soff_h = np.ascontiguousarray(ss.offsets_host[lo:hi + 1] - s0, dtype=np.int64)
+        toff_h = _route_offsets(soff_h)
+        ends = tuple(t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
+        return cls(torch.as_tensor(soff_h, device=dev), soff_h, torch.as_tensor(toff_h, device=dev), toff_h, ends, ss.angle[lo:hi].contiguous(), s1 - s0)
+
+    def block(self, dtype):
+        """an unwritten tensor of the transit blocks' layout"""
+        return _torch().empty(int(self.toff_h[-1]), dtype=dtype, device=self.soff.device)
+
+    def head(self, radius, reversing):
+        """the arguments the three transit entries share, behind the handle"""
+        return (len(self.soff_h) - 1, _ptr(self.soff), _host_ptr(self.soff_h), self.m, *[_ptr(t) for t in self.ends], _ptr(self.ang), float(radius),
+                1 if reversing else 0, _ptr(self.toff), _host_ptr(self.toff_h), int(self.toff_h[-1]))
+
+
+def _route_transit(ctx, ch, radius, reversing):
+    """fcpp_route_transit on a _RouteChunk -> T: its transit blocks"""
+    T = ch.block(_torch().float64)
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_route_transit(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(ang),
-                                       float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]), _ptr(T)))
-    return T, toff, toff_h, soff, soff_h, s1 - s0
+    L.check(ctx.lib.fcpp_route_transit(ctx.handle, *ch.head(radius, reversing), _ptr(T)))
+    return T
 
 
 def _route_chunks(soff_h, budget):
@@ -1517,39 +1601,23 @@ def _fields_slice(pf, ro_h, vo_h, lo, hi):
                          pf.y[v0:v1].contiguous())
 
 
-def _route_transit_clear(ctx, ss, lo, hi, radius, reversing, pf, penalty, T, toff, toff_h, soff, soff_h):
-    """fcpp_route_transit_clear on the chunk _route_transit made: T in / out -> B (uint8, T's layout); pf: the chunk's own fields"""
-    torch = _torch()
-    dev = ss.a.device
-    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
-    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
-    ang = ss.angle[lo:hi].contiguous()
-    B = torch.empty(int(toff_h[-1]), dtype=torch.uint8, device=dev)
+def _route_transit_clear(ctx, ch, radius, reversing, pf, penalty, T):
+    """fcpp_route_transit_clear on the chunk whose blocks T _route_transit made: T in / out -> B (uint8, T's layout); pf: the chunk's own
+    fields"""
+    B = ch.block(_torch().uint8)
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_route_transit_clear(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by),
-                                             _ptr(ang), float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]),
-                                             *pf._head()[1:], float(penalty), _ptr(T), _ptr(B)))
+    L.check(ctx.lib.fcpp_route_transit_clear(ctx.handle, *ch.head(radius, reversing), *pf._head()[1:], float(penalty), _ptr(T), _ptr(B)))
     return B
 
 
-def _route_transit_priced(ctx, ss, lo, hi, radius, reversing, pf, penalty):
-    """fields lo .. hi of a SwathSet -> (T, K, toff, toff_h, soff, soff_h, n_total): their PRICED transit blocks (fcpp_route_transit_priced:
-    T out only, K int8 with T's layout) and the chunk's own offsets; pf: the chunk's own fields"""
+def _route_transit_priced(ctx, ch, radius, reversing, pf, penalty):
+    """fcpp_route_transit_priced on a _RouteChunk -> (T, K): its PRICED transit blocks (T out only) and K (int8, T's layout); pf: the chunk's
+    own fields"""
     torch = _torch()
-    dev = ss.a.device
-    s0, s1 = int(ss.offsets_host[lo]), int(ss.offsets_host[hi])
-    soff_h = np.ascontiguousarray(ss.offsets_host[lo:hi + 1] - s0, dtype=np.int64)
-    toff_h = _route_offsets(soff_h)
-    soff, toff = torch.as_tensor(soff_h, device=dev), torch.as_tensor(toff_h, device=dev)
-    ax, ay, bx, by = (t[s0:s1, k].contiguous() for t in (ss.a, ss.b) for k in (0, 1))
-    ang = ss.angle[lo:hi].contiguous()
-    T = torch.empty(int(toff_h[-1]), dtype=torch.float64, device=dev)
-    K = torch.empty(int(toff_h[-1]), dtype=torch.int8, device=dev)
+    T, K = ch.block(torch.float64), ch.block(torch.int8)
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_route_transit_priced(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), s1 - s0, _ptr(ax), _ptr(ay), _ptr(bx), _ptr(by),
-                                              _ptr(ang), float(radius), 1 if reversing else 0, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]),
-                                              *pf._head()[1:], float(penalty), _ptr(T), _ptr(K)))
-    return T, K, toff, toff_h, soff, soff_h, s1 - s0
+    L.check(ctx.lib.fcpp_route_transit_priced(ctx.handle, *ch.head(radius, reversing), *pf._head()[1:], float(penalty), _ptr(T), _ptr(K)))
+    return T, K
 
 
 def _clear_fields(clear_of, n, device):
@@ -1577,15 +1645,14 @@ def swath_transit(swathset, radius, reversing=False, device=None, clear_of=None,
         raise ValueError('price_clear=True needs clear_of: the region the connectors have to stay clear of')
     ctx = get_context(device)
     n = len(swathset.offsets_host) - 1
+    ch = _RouteChunk.of(swathset, 0, n)
     if price_clear:
-        T, K, _, toff_h, _, _, _ = _route_transit_priced(ctx, swathset, 0, n, radius, reversing, _clear_fields(clear_of, n, device), blocked_penalty)
-        return T, toff_h, K
-    T, toff, toff_h, soff, soff_h, _ = _route_transit(ctx, swathset, 0, n, radius, reversing)
+        T, K = _route_transit_priced(ctx, ch, radius, reversing, _clear_fields(clear_of, n, device), blocked_penalty)
+        return T, ch.toff_h, K
+    T = _route_transit(ctx, ch, radius, reversing)
     if clear_of is None:
-        return T, toff_h
-    pf = _clear_fields(clear_of, n, device)
-    B = _route_transit_clear(ctx, swathset, 0, n, radius, reversing, pf, blocked_penalty, T, toff, toff_h, soff, soff_h)
-    return T, toff_h, B
+        return T, ch.toff_h
+    return T, ch.toff_h, _route_transit_clear(ctx, ch, radius, reversing, _clear_fields(clear_of, n, device), blocked_penalty, T)
 
 
 def _route_end_pairs(ss, pose, at_entry):
@@ -1612,8 +1679,7 @@ def _route_ends(ss, pose, at_entry, radius, reversing, device, clear_of=None, pe
     frm, to = _route_end_pairs(ss, pose, at_entry)
     if clear_of is None:
         return _conn_solve_poses(frm, to, radius, reversing, device)[2].contiguous()
-    counts = torch.as_tensor(np.diff(ss.offsets_host), device=ss.a.device)
-    pair_field = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64, device=ss.a.device), 2 * counts)
+    pair_field = _owners(2 * ss.offsets, 2 * int(ss.offsets_host[-1]))
     if price_clear:
         c = clear_connectors(frm, to, clear_of, pair_field, radius, reversing, device)
         return torch.where(c.rank < 0, c.length + float(penalty), c.length).contiguous()
@@ -1670,20 +1736,22 @@ def route_swaths(swathset, radius, reversing=False, entry=None, exit=None, start
     cost, stored = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
     winner, sweeps, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     for lo, hi in _route_chunks(soff_all, ROUTE_T_BUDGET):
+        ch = _RouteChunk.of(ss, lo, hi)
+        m = ch.m
         if price_clear:
-            T, _, toff, toff_h, soff, soff_h, m = _route_transit_priced(ctx, ss, lo, hi, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi),
-                                                                        blocked_penalty)
+            T, _ = _route_transit_priced(ctx, ch, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi), blocked_penalty)
         else:
-            T, toff, toff_h, soff, soff_h, m = _route_transit(ctx, ss, lo, hi, R, reversing)
-        if pf is not None and not price_clear:
-            _route_transit_clear(ctx, ss, lo, hi, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi), blocked_penalty, T, toff, toff_h, soff, soff_h)
+            T = _route_transit(ctx, ch, R, reversing)
+            if pf is not None:
+                _route_transit_clear(ctx, ch, R, reversing, _fields_slice(pf, ro_h, vo_h, lo, hi), blocked_penalty, T)
         s0 = int(soff_all[lo])
         Ec = E_all[2 * s0:2 * (s0 + m)] if E_all is not None else None
         Xc = X_all[2 * s0:2 * (s0 + m)] if X_all is not None else None
         tr = torch.empty((max(S, 0), m), dtype=torch.int32, device=dev)
-        L.check(ctx.lib.fcpp_route_solve(ctx.handle, hi - lo, _ptr(soff), _host_ptr(soff_h), m, _ptr(toff), _host_ptr(toff_h), int(toff_h[-1]), _ptr(T),
-                                         _ptr(Ec), _ptr(Xc), S, float(min_gain), int(max_sweeps), _ptr(tr), _ptr(costs[lo:hi]), _ptr(order[s0:s0 + m]),
-                                         _ptr(cost[lo:hi]), _ptr(winner[lo:hi]), _ptr(sweeps[lo:hi]), _ptr(status[lo:hi]), _ptr(stored[lo:hi])))
+        L.check(ctx.lib.fcpp_route_solve(ctx.handle, hi - lo, _ptr(ch.soff), _host_ptr(ch.soff_h), m, _ptr(ch.toff), _host_ptr(ch.toff_h),
+                                         int(ch.toff_h[-1]), _ptr(T), _ptr(Ec), _ptr(Xc), S, float(min_gain), int(max_sweeps), _ptr(tr),
+                                         _ptr(costs[lo:hi]), _ptr(order[s0:s0 + m]), _ptr(cost[lo:hi]), _ptr(winner[lo:hi]), _ptr(sweeps[lo:hi]),
+                                         _ptr(status[lo:hi]), _ptr(stored[lo:hi])))
         tours[:, s0:s0 + m] = tr
     route = SwathRoute(soff_all, order, cost, stored, winner, sweeps, status, tours, costs)
     if pf is not None:
@@ -1712,6 +1780,11 @@ class ConnectorClearance:
     field_status: object        # (n_fields) int32: 0, or FCPP_EINVAL (no ring, a ring of fewer than 3 vertices, a non-finite vertex)
 
 
+def _pair_field(pair_field, n, dev):
+    """the field index of every pair, given as one per pair or one for all -> (n) int64, contiguous, on the device"""
+    return _one_per(_torch().as_tensor(pair_field, device=dev).to(_torch().int64), n, 'pair_field', 'field index per pair')
+
+
 def _connector_clearance(frm, to, pf, pair_field, radius, reversing, device):
     ctx = get_context(device)
     torch = _torch()
@@ -1719,12 +1792,7 @@ def _connector_clearance(frm, to, pf, pair_field, radius, reversing, device):
     f, t = _poses(frm, dev), _poses(to, dev)
     word, seg, length = _conn_solve(ctx, f, t, radius, reversing)
     n = int(word.numel())
-    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
-    if pair_field.numel() == 1 and n != 1:
-        pair_field = pair_field.expand(n)
-    if pair_field.numel() != n:
-        raise ValueError('pair_field must be a scalar or hold one field index per pair')
-    pair_field = pair_field.contiguous()
+    pair_field = _pair_field(pair_field, n, dev)
     crossings = torch.empty(n, dtype=torch.int32, device=dev)
     inside = torch.empty(n, dtype=torch.int8, device=dev)
     first_s = torch.empty(n, dtype=torch.float64, device=dev)
@@ -1782,12 +1850,7 @@ def clear_connectors(from_poses, to_poses, fields, pair_field, radius, reversing
     n = int(f[0].numel())
     if int(t[0].numel()) != n:
         raise ValueError('from_poses and to_poses must hold the same number of poses')
-    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
-    if pair_field.numel() == 1 and n != 1:
-        pair_field = pair_field.expand(n)
-    if pair_field.numel() != n:
-        raise ValueError('pair_field must be a scalar or hold one field index per pair')
-    pair_field = pair_field.contiguous()
+    pair_field = _pair_field(pair_field, n, dev)
     word = torch.empty(n, dtype=torch.int32, device=dev)
     seg = torch.empty((n, 5 if reversing else 3), dtype=torch.float64, device=dev)
     length = torch.empty(n, dtype=torch.float64, device=dev)
@@ -1824,7 +1887,7 @@ def _leg_pairs(ss, order, entry, exit):
     soff_h = np.ascontiguousarray(ss.offsets_host, dtype=np.int64)
     n, m = len(soff_h) - 1, int(soff_h[-1])
     counts = torch.as_tensor(np.diff(soff_h), device=dev)
-    fld = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)         # the field of every driven position
+    fld = _owners(ss.offsets, m)                                                                  # the field of every driven position
     k = torch.arange(m, dtype=torch.int64, device=dev) - ss.offsets[fld]                          # and its rank in the order
     if order is None:
         o = 2 * k + (k & 1)
@@ -1884,17 +1947,50 @@ def field_path_clearance(swathset, fields, radius, spacing, reversing=False, ord
 
 # ---- field paths (fcpp_field_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------------
 @dataclass
-class FieldPaths:
-    """field_paths(): one sampled path per field of a SwathSet, in the CSR form curvature(), speed_plan(), validate() and trajectory()
-    take (offsets=).  Field i owns the samples offsets[i] .. offsets[i + 1]."""
+class PathSet:
+    """Sampled paths in the CSR form curvature(), speed_plan(), validate() and trajectory() take (offsets=): path p owns the samples
+    offsets[p] .. offsets[p + 1].  What every path-set result of the polygon chain begins with; the methods say what the consumers
+    (polygon_coverage, mission_paths, loop_transits) need to know of a set, and the kinds of set override them."""
     offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy
     offsets_host: object
     x: object                   # (total) float64
     y: object
     heading: object             # (total) float64, in (-pi, pi]: the vehicle's heading
-    kappa: object               # (total) float64: signed curvature, 0 on a swath
-    part: object                # (total) int8: 0 swath, 1 connector between swaths, 2 entry connector, 3 exit connector
+    kappa: object               # (total) float64: signed curvature
+    part: object                # (total) int8: the FCPP_PART_* of the sample
     gear: object                # (total) int8: +1, -1 on the reverse runs of a Reeds-Shepp connector
+
+    closed = False              # whether every path is a loop (its last sample joins its first)
+
+    def path(self, i):
+        """(x, y, heading, part) of path i: swath_route's tuple"""
+        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+
+    def _paths(self, dtype=None):
+        return _torch().arange(int(self.offsets.numel()) - 1, dtype=dtype or _torch().int64, device=self.x.device)
+
+    def path_field(self):
+        """(n) int64: the field of every path; path i is field i's"""
+        return self._paths()
+
+    def drive_order(self, innermost_first=False):
+        """(n) int64: the order in which a mission drives the set's paths; as stored"""
+        return self._paths()
+
+    def work(self):
+        """(total) bool: the samples that work (cover); the straight work parts, 0 and 4"""
+        return (self.part == 0) | (self.part == 4)
+
+    def pass_id(self):
+        """(total) int32: the id of the pass a sample belongs to (two different ids over one cell overlap); the path's index"""
+        return _owners(self.offsets, int(self.x.numel()), _torch().int32)
+
+
+@dataclass
+class FieldPaths(PathSet):
+    """field_paths(): one sampled path per field of a SwathSet: a PathSet whose path i is field i's.  kappa is 0 on a swath; part: 0 swath,
+    1 connector between swaths, 2 entry connector, 3 exit connector."""
     leg: object                 # (total) int32: the leg slot within the field: 0 entry, 2 k + 1 the k-th swath driven, 2 k + 2 the connector behind it
     work_length: object         # (n) float64: the swath lengths in driving order [m]
     transit_length: object      # (n) float64: the connector lengths, entry and exit included [m]: the route's cost
@@ -1915,10 +2011,15 @@ class FieldPaths:
     leg_transit = None          # (slots) int64: the slot's index into `transits`, -1 where the slot's own record is driven
     transits = None             # LoopTransits of the rank -1 legs, ordered by field, then by slot
 
-    def field(self, i):
-        """(x, y, heading, part) of field i: swath_route's tuple"""
-        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
-        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+    field = PathSet.path        # (x, y, heading, part) of field i
+
+    def work(self):
+        """the swaths"""
+        return self.part == 0
+
+    def pass_id(self):
+        """the leg"""
+        return self.leg
 
 
 def _pose_columns(pose, n, dev):
@@ -1937,18 +2038,13 @@ def _leg_paths(ctx, counts, fill, args, n_groups, n_slots, n_totals, dev):
     entry -> (offsets, offsets_host, x, y, heading, kappa, part, gear, leg, *totals, status, leg_offsets).  args: the entries' common
     arguments behind the handle; n_totals: the per-group float64 totals the counts entry writes."""
     torch = _torch()
-    off, leg_off = torch.empty(n_groups + 1, dtype=torch.int64, device=dev), torch.empty(n_slots + 1, dtype=torch.int64, device=dev)
-    off_h = np.zeros(n_groups + 1, dtype=np.int64)
+    leg_off = torch.empty(n_slots + 1, dtype=torch.int64, device=dev)
     totals = [torch.empty(n_groups, dtype=torch.float64, device=dev) for _ in range(n_totals)]
     status = torch.empty(n_groups, dtype=torch.int32, device=dev)
     ctx.bind_stream()
-    L.check(counts(ctx.handle, *args, _ptr(off), _host_ptr(off_h), _ptr(leg_off), *[_ptr(t) for t in totals], _ptr(status)))
-    total = int(off_h[-1])
-    x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
-    part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
-    leg = torch.empty(total, dtype=torch.int32, device=dev)
-    L.check(fill(ctx.handle, *args, _ptr(leg_off), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), _ptr(leg)))
-    return (off, off_h, x, y, h, kap, part, gear, leg, *totals, status, leg_off)
+    samples = _counts_fill(n_groups, dev, lambda off, off_h: counts(ctx.handle, *args, off, off_h, _ptr(leg_off), *[_ptr(t) for t in totals], _ptr(status)),
+                           lambda off, off_h, total, *cols: fill(ctx.handle, *args, _ptr(leg_off), total, *cols), _sample_columns(torch.int32))
+    return (*samples, *totals, status, leg_off)
 
 
 def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=None, exit=None, device=None, clear_of=None, loops=None):
@@ -2010,17 +2106,9 @@ def field_paths(swathset, radius, spacing, reversing=False, order=None, entry=No
 
 # ---- headland paths (fcpp_headland_path_counts / _fill; the rule: include/fcpp.h) -------------------------------------------------------
 @dataclass
-class HeadlandPaths:
-    """headland_paths(): one sampled, closed path per ring of an InsetSet, in the CSR form curvature(), speed_plan(), validate() and
-    trajectory() take (offsets=).  Ring r owns the samples offsets[r] .. offsets[r + 1]."""
-    offsets: object             # (n_rings + 1) int64, device; offsets_host: the numpy copy
-    offsets_host: object
-    x: object                   # (total) float64
-    y: object
-    heading: object             # (total) float64, in (-pi, pi]: the vehicle's heading
-    kappa: object               # (total) float64: signed curvature, 0 on a straight element, -/+ 1 / d on a followed arc
-    part: object                # (total) int8: 0 straight element, 1 connector, 4 followed arc
-    gear: object                # (total) int8: +1, -1 on the reverse runs of a Reeds-Shepp connector
+class HeadlandPaths(PathSet):
+    """headland_paths(): one sampled, closed path per ring of an InsetSet: a PathSet whose path r is ring r.  kappa is 0 on a straight
+    element, -/+ 1 / d on a followed arc; part: 0 straight element, 1 connector, 4 followed arc."""
     leg: object                 # (total) int32: the leg slot within the ring: 2 k the element driven vertex k starts, 2 k + 1 the joint behind it
     work_length: object         # (n_rings) float64: the straight elements and followed arcs [m]
     transit_length: object      # (n_rings) float64: the connectors [m]
@@ -2030,10 +2118,20 @@ class HeadlandPaths:
     ring_pair: object           # (n_rings, 2) int64, device: the (field, pass) index of every ring
     spacing: object = None      # the sample spacing the loops were driven at [m] (loop_transits turns station_step into a stride by it)
 
-    def ring(self, r):
-        """(x, y, heading, part) of ring r"""
-        sl = slice(int(self.offsets_host[r]), int(self.offsets_host[r + 1]))
-        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+    closed = True
+    ring = PathSet.path         # (x, y, heading, part) of ring r
+
+    def path_field(self):
+        """the ring's field"""
+        return self.ring_pair[:, 0]
+
+    def drive_order(self, innermost_first=False):
+        """as stored, or (stable) the innermost pass first"""
+        return _torch().argsort(-self.ring_pair[:, 1], stable=True) if innermost_first else self._paths()
+
+    def pass_id(self):
+        """-1 - ring: negative, distinct from a field path's legs (work: the base's, the straight elements and the followed arcs)"""
+        return -1 - _owners(self.offsets, int(self.x.numel()), _torch().int32)
 
 
 def _headland_paths(ctx, ring_offsets, x, y, src, ring_dist, R, mode, spacing, direction, smooth_tol, ring_offsets_host=None):
@@ -2060,9 +2158,7 @@ def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_
     torch = _torch()
     dev = inset.x.device
     nr = int(inset.ring_offsets.numel()) - 1
-    pairs = int(inset.pair_ring_offsets.numel()) - 1
-    per_pair = inset.pair_ring_offsets[1:] - inset.pair_ring_offsets[:-1]
-    pair = torch.repeat_interleave(torch.arange(pairs, dtype=torch.int64, device=dev), per_pair, output_size=nr)
+    pair = _owners(inset.pair_ring_offsets, nr)
     D = max(inset.D, 1)
     ring_pair = torch.stack([pair // D, pair % D], dim=1)
     ring_dist = inset.distances[ring_pair[:, 1]].contiguous() if nr else torch.empty(0, dtype=torch.float64, device=dev)
@@ -2073,16 +2169,9 @@ def headland_paths(inset, radius, spacing, reversing=False, direction=1, smooth_
 
 # ---- loop transits (fcpp_loop_transit_solve / _counts / _fill; the rule: include/fcpp.h) ------------------------------------------------
 @dataclass
-class TransitPaths:
-    """LoopTransits.paths(): one sampled path per pair, in the CSR form curvature(), speed_plan(), validate() and trajectory() take"""
-    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy.  A pair that is not found has no samples
-    offsets_host: object
-    x: object                   # (total) float64
-    y: object
-    heading: object
-    kappa: object
-    part: object                # (total) int8: 1 on the two connectors, FCPP_PART_LOOP_RIDE (5) on the ride
-    gear: object                # (total) int8
+class TransitPaths(PathSet):
+    """LoopTransits.paths(): one sampled path per pair -- a pair that is not found has no samples.  part: 1 on the two connectors,
+    FCPP_PART_LOOP_RIDE (5) on the ride."""
 
 
 @dataclass
@@ -2114,54 +2203,41 @@ class LoopTransits:
         """The transits sampled (fcpp_loop_transit_counts + fcpp_loop_transit_fill): the connectors every `spacing` metres by the
         connectors' own samplers, the ride the loop's own samples -> TransitPaths."""
         ctx = get_context(self._device)
-        torch = _torch()
         ls, f = self.loop_set, self._start
-        dev = self.found.device
         n = int(self.found.numel())
         mode = 1 if self.reversing else 0
-        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        off_h = np.zeros(n + 1, dtype=np.int64)
         rec = [_ptr(t) for t in (self.found, self.loop, self.st_i, self.st_j, self.in_word, self.in_seg, self.out_word, self.out_seg)]
         lhead = (int(ls['offsets'].numel()) - 1, _ptr(ls['offsets']), _host_ptr(ls['offsets_host']), int(ls['x'].numel()))
         ctx.bind_stream()
-        L.check(ctx.lib.fcpp_loop_transit_counts(ctx.handle, mode, n, *rec, *lhead, float(spacing), _ptr(off), _host_ptr(off_h)))
-        total = int(off_h[-1])
-        x, y, h, kap = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
-        part, gear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
-        L.check(ctx.lib.fcpp_loop_transit_fill(ctx.handle, mode, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(self.radius), *rec, *lhead,
-                                               _ptr(ls['x']), _ptr(ls['y']), _ptr(ls['heading']), _ptr(ls['kappa']), _ptr(ls['gear']), float(spacing),
-                                               _ptr(off), _host_ptr(off_h), total, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear)))
-        return TransitPaths(off, off_h, x, y, h, kap, part, gear)
+        return TransitPaths(*_counts_fill(
+            n, self.found.device, lambda *off: ctx.lib.fcpp_loop_transit_counts(ctx.handle, mode, n, *rec, *lhead, float(spacing), *off),
+            lambda *out: ctx.lib.fcpp_loop_transit_fill(ctx.handle, mode, n, _ptr(f[0]), _ptr(f[1]), _ptr(f[2]), float(self.radius), *rec, *lhead,
+                                                        _ptr(ls['x']), _ptr(ls['y']), _ptr(ls['heading']), _ptr(ls['kappa']), _ptr(ls['gear']),
+                                                        float(spacing), *out), _sample_columns()))
 
 
 def _loop_set(loops, n_fields, dev, device):
     """HeadlandPaths (one or several, e.g. both directions) -> the loop set of the transit entries: the loops sorted by field (stable: a
     field's loops in the order given), their samples gathered, s from trajectory(), field_loops from ring_pair -> (dict, spacing)"""
     torch = _torch()
-    loops = [loops] if isinstance(loops, HeadlandPaths) else list(loops)
-    cols = {k: [] for k in ('x', 'y', 'heading', 'kappa', 's', 'part', 'gear')}
-    fld, start, lens, base, spacing = [], [], [], 0, None
+    loops = [loops] if isinstance(loops, PathSet) else list(loops)
+    names = ('x', 'y', 'heading', 'kappa', 's', 'part', 'gear')
+    cols, spacing = [], None
     for hp in loops:
         total = int(hp.x.numel())
         s = trajectory(hp.x, hp.y, torch.ones(total, dtype=torch.float64, device=dev), offsets=hp.offsets, device=device)[0] if total else hp.x
-        for k, t in zip(cols, (hp.x, hp.y, hp.heading, hp.kappa, s, hp.part, hp.gear)):
-            cols[k].append(t.to(dev))
-        off = hp.offsets.to(dev)
-        fld.append(hp.ring_pair[:, 0].to(dev)); start.append(off[:-1] + base); lens.append(off[1:] - off[:-1])
-        base += total
+        cols.append((hp.x, hp.y, hp.heading, hp.kappa, s, hp.part, hp.gear))
         spacing = hp.spacing if spacing is None else spacing
+    _, _, joined, _, cols = _join_csr([hp.offsets for hp in loops], [None] * len(loops), cols, (torch.float64,) * 5 + (torch.int8,) * 2, dev)
     i64 = lambda ts: torch.cat(ts) if ts else torch.zeros(0, dtype=torch.int64, device=dev)
-    fld, start, lens = i64(fld), i64(start), i64(lens)
-    order = torch.argsort(fld, stable=True)
-    fld, start, lens = fld[order], start[order], lens[order]
+    order, fl = _group_by(i64([hp.path_field().to(dev) for hp in loops]), n_fields)
+    start, lens = joined[:-1][order], (joined[1:] - joined[:-1])[order]
     off = torch.zeros(int(lens.numel()) + 1, dtype=torch.int64, device=dev)
     off[1:] = torch.cumsum(lens, 0)
     off_h = off.cpu().numpy()
     total = int(off_h[-1])
     idx = torch.repeat_interleave(start - off[:-1], lens, output_size=total) + torch.arange(total, dtype=torch.int64, device=dev)
-    ls = {k: (torch.cat(v)[idx].contiguous() if v else torch.zeros(0, dtype=torch.float64 if k not in ('part', 'gear') else torch.int8, device=dev))
-          for k, v in cols.items()}
-    fl = torch.searchsorted(fld, torch.arange(n_fields + 1, dtype=torch.int64, device=dev)).to(torch.int64).contiguous()
+    ls = {k: c[idx].contiguous() for k, c in zip(names, cols)}
     ls.update(offsets=off, offsets_host=off_h, field_loops=fl, field_loops_host=fl.cpu().numpy())
     if spacing is None:          # (loops that do not say: the mean step of their samples)
         steps = total - int(lens.numel())
@@ -2206,16 +2282,12 @@ def loop_transits(from_poses, to_poses, fields, pair_field, loops, radius, rever
     n = int(f[0].numel())
     if int(t[0].numel()) != n:
         raise ValueError('from_poses and to_poses must hold the same number of poses')
-    pair_field = torch.as_tensor(pair_field, device=dev).to(torch.int64).reshape(-1)
-    if pair_field.numel() == 1 and n != 1:
-        pair_field = pair_field.expand(n)
-    if pair_field.numel() != n:
-        raise ValueError('pair_field must be a scalar or hold one field index per pair')
+    pair_field = _pair_field(pair_field, n, dev)
     ls, spacing = _loop_set(loops, pf.n, dev, device)
     step = float(radius) if station_step is None else float(station_step)
     if not step > 0.0:
         raise ValueError('station_step must be positive')
-    return _loop_transits(ctx, f, t, pf, pair_field.contiguous(), ls, radius, reversing, max(1, int(round(step / spacing))), device)
+    return _loop_transits(ctx, f, t, pf, pair_field, ls, radius, reversing, max(1, int(round(step / spacing))), device)
 
 
 def _detour_field_paths(fp, ss, pf, loops, R, spacing, reversing, order, entry, exit, device):
@@ -2264,7 +2336,7 @@ def _detour_field_paths(fp, ss, pf, loops, R, spacing, reversing, order, entry, 
     leg_len = fp.leg_total.clone()
     leg_len[g[hit]] = lt.total[hit]
     slots_of = first[1:] - first[:-1]
-    fld_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), slots_of, output_size=n_slots)
+    fld_of = _owners(first, n_slots)
     even = (torch.arange(n_slots, dtype=torch.int64, device=dev) - first[fld_of]) % 2 == 0
     per_field = (slots_of + 1) // 2
     summed = torch.segment_reduce(leg_len[even], 'sum', lengths=per_field, initial=0.0)
@@ -2278,18 +2350,10 @@ def _detour_field_paths(fp, ss, pf, loops, R, spacing, reversing, order, entry, 
 
 # ---- mission paths (fcpp_mission_solve / _counts / _fill; the rule: include/fcpp.h) ------------------------------------------------------
 @dataclass
-class MissionPaths:
-    """mission_paths(): ONE sampled path per field -- its items joined in driving order -- in the CSR form curvature(), speed_plan(),
-    validate() and trajectory() take (offsets=).  Field i owns the samples offsets[i] .. offsets[i + 1]."""
-    offsets: object             # (n + 1) int64, device; offsets_host: the numpy copy
-    offsets_host: object
-    x: object                   # (total) float64
-    y: object
-    heading: object
-    kappa: object
-    part: object                # (total) int8: the source sample's part, FCPP_PART_JOIN (6) on a joint
-    gear: object                # (total) int8
-    slot: object                # (total) int32: the slot within the field: 2 j the joint into kept item j, 2 j + 1 the item, the last the exit joint
+class MissionPaths(PathSet):
+    """mission_paths(): ONE sampled path per field -- its items joined in driving order: a PathSet whose path i is field i's.  part: the
+    source sample's part, FCPP_PART_JOIN (6) on a joint."""
+    slot: object               # (total) int32: the slot within the field: 2 j the joint into kept item j, 2 j + 1 the item, the last the exit joint
     src: object                 # (total) int64: the source sample's index into the concatenated item sets, -1 on a joint
     src_set: object             # (total) int32: the position in `items` of the set the sample was copied from, -1 on a joint
     status: object              # (n) int32: 0, FCPP_EINVAL (a chosen pose that is not finite), FCPP_EUNSUPPORTED (a loop of more than 1024 stations): no samples
@@ -2311,16 +2375,13 @@ class MissionPaths:
     set_starts: object = None   # (sets + 1) numpy int64: where every set's samples start in the concatenation
     blocked: object = None      # (n) int32 with clear_of: the field's joints for which no word is clear of its region (they are driven as they are)
 
-    def field(self, i):
-        """(x, y, heading, part) of field i: swath_route's tuple"""
-        sl = slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
-        return self.x[sl], self.y[sl], self.heading[sl], self.part[sl]
+    field = PathSet.path        # (x, y, heading, part) of field i
 
     def cover_set(self, pass_ids=None, work=None):
         """The tuple (offsets, x, y, path_field, work, pass) polygon_coverage takes, gathered through src.  pass_ids / work: one entry per
-        set of `items`, each a tensor per source sample of that set or None -- the defaults polygon_coverage uses for a FieldPaths (work:
-        the swaths, pass: the leg) or a HeadlandPaths (work: straight elements and followed arcs, pass: -1 - ring); a tuple-form set needs both
-        given.  Joints do not work."""
+        set of `items`, each a tensor per source sample of that set or None -- the set's own work() and pass_id(), what polygon_coverage uses
+        for it (a FieldPaths: the swaths, the leg; a HeadlandPaths: straight elements and followed arcs, -1 - ring); a tuple-form set needs
+        both given.  Joints do not work."""
         torch = _torch()
         dev = self.x.device
         n_sets = len(self._sets)
@@ -2332,12 +2393,10 @@ class MissionPaths:
         for k, st in enumerate(self._sets):
             total = int(self.set_starts[k + 1] - self.set_starts[k])
             w, p = work[k], pass_ids[k]
-            if (w is None or p is None) and not isinstance(st, (FieldPaths, HeadlandPaths)):
+            if (w is None or p is None) and not isinstance(st, PathSet):
                 raise ValueError('a tuple-form item set needs its pass ids and work flags given')
-            if w is None or p is None:
-                d = _cover_path_set(st, 0, dev)
-                w, p = (d[5] if w is None else w), (d[6] if p is None else p)
-            w = (torch.as_tensor(w, device=dev).reshape(-1) != 0).to(torch.uint8)
+            w, p = (st.work() if w is None else w), (st.pass_id() if p is None else p)
+            w =(torch.as_tensor(w, device=dev).reshape(-1) != 0).to(torch.uint8)
             p = torch.as_tensor(p, device=dev).to(torch.int32).reshape(-1)
             if int(w.numel()) != total or int(p.numel()) != total:
                 raise ValueError('pass_ids and work hold one value per sample of their set')
@@ -2347,70 +2406,70 @@ class MissionPaths:
         cat = lambda ts, dt: torch.cat(ts + [torch.zeros(1, dtype=dt, device=dev)])          # (one spare element: a set list without a sample)
         w = torch.where(copied, cat(ws, torch.uint8)[at], torch.zeros((), dtype=torch.uint8, device=dev))
         pas = torch.where(copied, cat(ps, torch.int32)[at], torch.zeros((), dtype=torch.int32, device=dev))
-        n = int(self.offsets.numel()) - 1
-        return (self.offsets, self.x, self.y, torch.arange(n, dtype=torch.int64, device=dev), w, pas)
+        return (self.offsets, self.x, self.y, self.path_field(), w, pas)
 
     _sets = ()
 
 
 def _mission_set(st, dev, innermost_first):
-    """one item set -> (offsets, x, y, heading, kappa, part, gear, field int64 per path, closed bool, the paths' order within the set)"""
+    """mission_paths' normaliser: a PathSet, or the tuple (offsets, x, y, heading, kappa, part, gear, field, closed) -> (PathSet, the field
+    of every path int64, closed, the paths' order within the set)"""
     torch = _torch()
-    if isinstance(st, FieldPaths):
-        npth = int(st.offsets.numel()) - 1
-        return (st.offsets, st.x, st.y, st.heading, st.kappa, st.part, st.gear, torch.arange(npth, dtype=torch.int64, device=dev), False,
-                torch.arange(npth, dtype=torch.int64, device=dev))
-    if isinstance(st, HeadlandPaths):
-        npth = int(st.offsets.numel()) - 1
-        order = torch.argsort(-st.ring_pair[:, 1], stable=True) if innermost_first else torch.arange(npth, dtype=torch.int64, device=dev)
-        return (st.offsets, st.x, st.y, st.heading, st.kappa, st.part, st.gear, st.ring_pair[:, 0].to(dev), True, order.to(dev))
+    if isinstance(st, PathSet):
+        return st, st.path_field().to(dev), st.closed, st.drive_order(innermost_first).to(dev)
     offsets, x, y, heading, kappa, part, gear, field, closed = st
     x = _dev_f64(x, dev).reshape(-1)
     total = int(x.numel())
-    off, _ = _offsets(offsets, total, dev)
+    off, off_h = _offsets(offsets, total, dev)
     npth = int(off.numel()) - 1
     field = torch.as_tensor(field, device=dev).to(torch.int64).reshape(-1)
     if field.numel() == 1 and npth != 1:
         field = field.expand(npth)
     i8 = lambda a: torch.as_tensor(a, device=dev).to(torch.int8).reshape(-1).contiguous()
-    cols = (off, x, _dev_f64(y, dev).reshape(-1), _dev_f64(heading, dev).reshape(-1), _dev_f64(kappa, dev).reshape(-1), i8(part), i8(gear))
-    if any(int(c.numel()) != total for c in cols[1:]) or int(field.numel()) != npth:
+    ps = PathSet(off, off_h, x, _dev_f64(y, dev).reshape(-1), _dev_f64(heading, dev).reshape(-1), _dev_f64(kappa, dev).reshape(-1), i8(part), i8(gear))
+    if any(int(c.numel()) != total for c in (ps.y, ps.heading, ps.kappa, ps.part, ps.gear)) or int(field.numel()) != npth:
         raise ValueError('an item set needs six columns of one length and one field per path')
-    return cols + (field.contiguous(), bool(closed), torch.arange(npth, dtype=torch.int64, device=dev))
+    return ps, field.contiguous(), bool(closed), ps.drive_order()
+
+
+@dataclass
+class _MissionTable:
+    """_mission_table(): the item sets of a mission as the mission entries take them"""
+    n: int                      # fields
+    first: object               # (sets + 1) numpy int64: where every set's paths start among the joined paths
+    starts: object              # (sets + 1) numpy int64: and its samples among the joined samples
+    paths: object               # PathSet: the sets joined, offsets_host always there
+    ioff: object                # (n + 1) int64: field i's items are ioff[i] .. ioff[i + 1], in driving order; ioff_h: the numpy copy
+    ioff_h: object
+    ipath: object               # (items) int64: the joined path an item drives; ipath_h: the numpy copy
+    ipath_h: object
+    iset: object                # (items) int32: the position in `items` of the item's set
+    iclosed: object             # (items) int32: whether it is a loop
+    longest: int                # the samples of the longest loop, 0 without one
 
 
 def _mission_table(items, dev, innermost_first=False, n_fields=None, entry=None, exit=None):
-    """the item sets concatenated into one path set and the fields' item table, as fcpp_mission_solve takes them -> dict"""
+    """the item sets joined into one path set and the fields' item table, as fcpp_mission_solve takes them -> _MissionTable"""
     n = n_fields
     torch = _torch()
     sets = [_mission_set(st, dev, innermost_first) for st in items]
     if n is None:
-        n = max([int(s[7].max()) + 1 for s in sets if int(s[7].numel())] + [0])
+        n = max([int(f.max()) + 1 for _, f, _, _ in sets if int(f.numel())] + [0])
         for p in (entry, exit):
             n = n if p is None else max(n, int(torch.as_tensor(p).reshape(-1, 3).shape[0]))
-    first = np.concatenate([[0], np.cumsum([int(s[0].numel()) - 1 for s in sets])]).astype(np.int64)
-    starts = np.concatenate([[0], np.cumsum([int(s[1].numel()) for s in sets])]).astype(np.int64)
-    total_in = int(starts[-1])
-    cat = lambda k, dt: (torch.cat([s[k].to(dev) for s in sets]) if sets else torch.empty(0, dtype=dt, device=dev)).contiguous()
-    x, y, h, kap = (cat(k, torch.float64) for k in (1, 2, 3, 4))
-    part, gear = cat(5, torch.int8), cat(6, torch.int8)
-    poff = torch.cat([s[0][:-1].to(dev) + int(starts[k]) for k, s in enumerate(sets)] + [torch.full((1,), total_in, dtype=torch.int64, device=dev)]).contiguous()
+    first, starts, poff, poff_h, cols = _join_csr([ps.offsets for ps, *_ in sets], [ps.offsets_host for ps, *_ in sets],
+                                                  [(ps.x, ps.y, ps.heading, ps.kappa, ps.part, ps.gear) for ps, *_ in sets], _sample_columns(), dev)
     i64 = lambda ts: torch.cat(ts) if ts else torch.zeros(0, dtype=torch.int64, device=dev)
-    fld = i64([s[7][s[9]] for s in sets])
-    ipath = i64([s[9] + int(first[k]) for k, s in enumerate(sets)])
-    iset = i64([torch.full((int(s[9].numel()),), k, dtype=torch.int64, device=dev) for k, s in enumerate(sets)])
-    iclosed = i64([torch.full((int(s[9].numel()),), int(s[8]), dtype=torch.int64, device=dev) for s in sets])
-    if int(fld.numel()) and (int(fld.min()) < 0 or int(fld.max()) >= n):
-        raise ValueError('an item names a field outside 0 .. n_fields - 1')
-    order = torch.argsort(fld, stable=True)
-    fld, ipath, iset, iclosed = fld[order], ipath[order].contiguous(), iset[order].to(torch.int32), iclosed[order].to(torch.int32).contiguous()
-    n_items = int(ipath.numel())
-    ioff = torch.searchsorted(fld, torch.arange(n + 1, dtype=torch.int64, device=dev)).to(torch.int64).contiguous()
-    ioff_h, ipath_h, poff_h = ioff.cpu().numpy(), ipath.cpu().numpy(), poff.cpu().numpy()
+    per_item = lambda value, o: torch.full((int(o.numel()),), int(value), dtype=torch.int64, device=dev)
+    order, ioff = _group_by(i64([f[o] for _, f, _, o in sets]), n, 'an item names a field outside 0 .. n_fields - 1')
+    ipath = i64([o + int(first[k]) for k, (*_, o) in enumerate(sets)])[order].contiguous()
+    iset = i64([per_item(k, o) for k, (*_, o) in enumerate(sets)])[order].to(torch.int32)
+    iclosed = i64([per_item(closed, o) for _, _, closed, o in sets])[order].to(torch.int32).contiguous()
+    ipath_h = ipath.cpu().numpy()
+    poff_h = poff.cpu().numpy() if poff_h is None else poff_h
     lens = poff_h[1:] - poff_h[:-1]
-    longest = int(lens[ipath_h[iclosed.cpu().numpy() != 0]].max()) if n_items and bool((iclosed != 0).any()) else 0
-    return dict(n=n, first=first, starts=starts, total_in=total_in, x=x, y=y, h=h, kap=kap, part=part, gear=gear, poff=poff, poff_h=poff_h, ioff=ioff,
-                ioff_h=ioff_h, ipath=ipath, ipath_h=ipath_h, iset=iset, iclosed=iclosed, n_items=n_items, longest=longest)
+    longest = int(lens[ipath_h[iclosed.cpu().numpy() != 0]].max()) if len(ipath_h) and bool((iclosed != 0).any()) else 0
+    return _MissionTable(n, first, starts, PathSet(poff, poff_h, *cols), ioff, ioff.cpu().numpy(), ipath, ipath_h, iset, iclosed, longest)
 
 
 def mission_paths(items, radius, spacing, reversing=False, entry=None, exit=None, station_step=None, device=None, innermost_first=False,
@@ -2432,15 +2491,13 @@ def mission_paths(items, radius, spacing, reversing=False, entry=None, exit=None
     dev = torch.device('cuda', ctx.device)
     items = list(items)
     t = _mission_table(items, dev, innermost_first, n_fields, entry, exit)
-    n, first, starts, total_in, n_items, longest = t['n'], t['first'], t['starts'], t['total_in'], t['n_items'], t['longest']
-    x, y, h, kap, part, gear, poff, poff_h = t['x'], t['y'], t['h'], t['kap'], t['part'], t['gear'], t['poff'], t['poff_h']
-    ioff, ioff_h, ipath, ipath_h, iset, iclosed = t['ioff'], t['ioff_h'], t['ipath'], t['ipath_h'], t['iset'], t['iclosed']
+    n, n_items, ps = t.n, len(t.ipath_h), t.paths
     if station_step is None:
-        stride = max(1, -(-(longest - 1) // 128))
+        stride = max(1, -(-(t.longest - 1) // 128))
     else:
         if not float(station_step) > 0.0:
             raise ValueError('station_step must be positive')
-        set_spacing = next((st.spacing for st in items if isinstance(st, HeadlandPaths) and st.spacing), spacing)
+        set_spacing = next((s for s in (getattr(st, 'spacing', None) for st in items) if s), spacing)
         stride = max(1, int(round(float(station_step) / float(set_spacing))))
     R, mode = _chord_radius(radius, spacing), 1 if reversing else 0
     ent, ext = _pose_columns(entry, n, dev), _pose_columns(exit, n, dev)
@@ -2454,28 +2511,24 @@ def mission_paths(items, radius, spacing, reversing=False, entry=None, exit=None
     slot_word = torch.full((n_slots,), -1, dtype=torch.int32, device=dev)
     slot_seg = torch.full((n_slots, 5), float('nan'), dtype=torch.float64, device=dev)
     slot_total = torch.full((n_slots,), float('nan'), dtype=torch.float64, device=dev)
-    head = (mode, n, _ptr(ioff), _host_ptr(ioff_h), n_items, _ptr(ipath), _host_ptr(ipath_h), _ptr(iclosed), int(first[-1]), _ptr(poff), _host_ptr(poff_h),
-            total_in)
+    head = (mode, n, _ptr(t.ioff), _host_ptr(t.ioff_h), n_items, _ptr(t.ipath), _host_ptr(t.ipath_h), _ptr(t.iclosed), int(t.first[-1]), _ptr(ps.offsets),
+            _host_ptr(ps.offsets_host), int(t.starts[-1]))
     rec = (_ptr(status), _ptr(station), _ptr(slot_item), _ptr(slot_word), _ptr(slot_seg))
     ctx.bind_stream()
-    L.check(ctx.lib.fcpp_mission_solve(ctx.handle, *head, _ptr(x), _ptr(y), _ptr(h), _ptr(part), _ptr(gear), *[_ptr(t) for t in ent], *[_ptr(t) for t in ext],
-                                       R, stride, _ptr(status), _ptr(transit), _ptr(skipped), _ptr(station), _ptr(slot_item), _ptr(slot_word),
-                                       _ptr(slot_seg), _ptr(slot_total)))
-    off, off_h = torch.empty(n + 1, dtype=torch.int64, device=dev), np.zeros(n + 1, dtype=np.int64)
+    L.check(ctx.lib.fcpp_mission_solve(ctx.handle, *head, _ptr(ps.x), _ptr(ps.y), _ptr(ps.heading), _ptr(ps.part), _ptr(ps.gear), *[_ptr(c) for c in ent],
+                                       *[_ptr(c) for c in ext], R, stride, _ptr(status), _ptr(transit), _ptr(skipped), _ptr(station), _ptr(slot_item),
+                                       _ptr(slot_word), _ptr(slot_seg), _ptr(slot_total)))
     slot_off = torch.empty(n_slots + 1, dtype=torch.int64, device=dev)
-    L.check(ctx.lib.fcpp_mission_counts(ctx.handle, *head, *rec, float(spacing), _ptr(off), _host_ptr(off_h), _ptr(slot_off)))
-    total = int(off_h[-1])
-    ox, oy, oh, ok = (torch.empty(total, dtype=torch.float64, device=dev) for _ in range(4))
-    opart, ogear = torch.empty(total, dtype=torch.int8, device=dev), torch.empty(total, dtype=torch.int8, device=dev)
-    oslot, osrc = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int64, device=dev)
-    L.check(ctx.lib.fcpp_mission_fill(ctx.handle, *head, _ptr(x), _ptr(y), _ptr(h), _ptr(kap), _ptr(part), _ptr(gear), *[_ptr(t) for t in ent], R,
-                                      float(spacing), *rec, _ptr(slot_off), total, _ptr(ox), _ptr(oy), _ptr(oh), _ptr(ok), _ptr(opart), _ptr(ogear),
-                                      _ptr(oslot), _ptr(osrc)))
-    src_set = (torch.searchsorted(torch.as_tensor(starts[1:], device=dev), osrc, right=True).to(torch.int32)
-               if len(items) else torch.zeros(total, dtype=torch.int32, device=dev))
+    *samples, osrc = _counts_fill(
+        n, dev, lambda off, off_h: ctx.lib.fcpp_mission_counts(ctx.handle, *head, *rec, float(spacing), off, off_h, _ptr(slot_off)),
+        lambda off, off_h, total, *cols: ctx.lib.fcpp_mission_fill(ctx.handle, *head, _ptr(ps.x), _ptr(ps.y), _ptr(ps.heading), _ptr(ps.kappa),
+                                                                   _ptr(ps.part), _ptr(ps.gear), *[_ptr(c) for c in ent], R, float(spacing), *rec,
+                                                                   _ptr(slot_off), total, *cols), _sample_columns(torch.int32, torch.int64))
+    src_set = (torch.searchsorted(torch.as_tensor(t.starts[1:], device=dev), osrc, right=True).to(torch.int32)
+               if len(items) else torch.zeros(int(osrc.numel()), dtype=torch.int32, device=dev))
     src_set = torch.where(osrc >= 0, src_set, torch.full((), -1, dtype=torch.int32, device=dev))
-    mp = MissionPaths(off, off_h, ox, oy, oh, ok, opart, ogear, oslot, osrc, src_set, status, transit, skipped, ioff, ipath, iclosed, iset, station,
-                      slot_off, slot_item, slot_word, slot_seg, slot_total, float(R), bool(reversing), int(stride), starts)
+    mp = MissionPaths(*samples, osrc, src_set, status, transit, skipped, t.ioff, t.ipath, t.iclosed, t.iset, station, slot_off, slot_item, slot_word,
+                      slot_seg, slot_total, float(R), bool(reversing), int(stride), t.starts)
     mp._sets = tuple(items)
     if clear_of is not None:
         mp.blocked = _mission_blocked(mp, _clear_fields(clear_of, n, device), ent, ext, device)
@@ -2562,16 +2615,12 @@ class PolygonCoverage:
         return coverage_regions(self, **kw)
 
 
-def _cover_path_set(ps, first_path, dev):
-    """one path set -> (offsets, offsets_host or None, x, y, path_field int64, work uint8, pass int32), all on the device"""
+def _cover_set(ps, first_path, dev):
+    """polygon_coverage's normaliser: a PathSet, or the tuple (offsets, x, y, path_field, work, pass) -> (PathSet -- of a tuple only its
+    offsets, x and y --, path_field int64, work uint8, pass int32), all on the device"""
     torch = _torch()
-    if isinstance(ps, FieldPaths):
-        np_ = int(ps.offsets.numel()) - 1
-        return (ps.offsets, ps.offsets_host, ps.x, ps.y, torch.arange(np_, dtype=torch.int64, device=dev), (ps.part == 0).to(torch.uint8), ps.leg)
-    if isinstance(ps, HeadlandPaths):
-        nr, total = int(ps.offsets.numel()) - 1, int(ps.x.numel())
-        ring = torch.repeat_interleave(torch.arange(nr, dtype=torch.int32, device=dev), ps.offsets[1:] - ps.offsets[:-1], output_size=total)
-        return (ps.offsets, ps.offsets_host, ps.x, ps.y, ps.ring_pair[:, 0].contiguous(), ((ps.part == 0) | (ps.part == 4)).to(torch.uint8), -1 - ring)
+    if isinstance(ps, PathSet):
+        return ps, ps.path_field(), ps.work().to(torch.uint8), ps.pass_id()
     offsets, x, y, path_field, work, pas = ps
     x, y = _dev_f64(x, dev).reshape(-1), _dev_f64(y, dev).reshape(-1)
     total = int(x.numel())
@@ -2579,43 +2628,28 @@ def _cover_path_set(ps, first_path, dev):
     np_ = int(off.numel()) - 1
     pf = torch.zeros(np_, dtype=torch.int64, device=dev) if path_field is None else torch.as_tensor(path_field, device=dev).to(torch.int64).reshape(-1)
     w = torch.ones(total, dtype=torch.uint8, device=dev) if work is None else (torch.as_tensor(work, device=dev).reshape(-1) != 0).to(torch.uint8)
-    if pas is None:
-        pas = torch.repeat_interleave(torch.arange(first_path, first_path + np_, dtype=torch.int32, device=dev), off[1:] - off[:-1], output_size=total)
-    else:
-        pas = torch.as_tensor(pas, device=dev).to(torch.int32).reshape(-1)
+    pas = first_path + _owners(off, total, torch.int32) if pas is None else torch.as_tensor(pas, device=dev).to(torch.int32).reshape(-1)
     if int(pf.numel()) != np_ or int(w.numel()) != total or int(pas.numel()) != total or int(y.numel()) != total:
         raise ValueError('a path set needs one field per path and one work flag and pass id per sample')
-    return off, off_h, x, y, pf, w, pas
+    return PathSet(off, off_h, x, y, None, None, None, None), pf, w, pas
 
 
 def _cover_paths(paths, n, dev):
-    """the path sets of polygon_coverage, concatenated on the device -> (n_paths, total, path_offsets, its host copy or None, x, y, work,
-    pass, field_path_offsets, path_ids): what fcpp_polygon_cover takes"""
+    """the path sets of polygon_coverage, joined on the device -> (n_paths, total, path_offsets, its host copy or None, x, y, work, pass,
+    field_path_offsets, path_ids): what fcpp_polygon_cover takes"""
     torch = _torch()
-    if isinstance(paths, (FieldPaths, HeadlandPaths)) or (isinstance(paths, tuple) and len(paths) == 6
-                                                          and not isinstance(paths[0], (FieldPaths, HeadlandPaths, tuple))):
-        paths = (paths,)
-    sets, first = [], 0
+    if isinstance(paths, PathSet) or (isinstance(paths, tuple) and len(paths) == 6 and not isinstance(paths[0], (PathSet, tuple))):
+        paths = (paths,)          # (one set, itself or as a tuple, not a sequence of sets)
+    sets, n_paths = [], 0
     for ps in paths:
-        sets.append(_cover_path_set(ps, first, dev))
-        first += int(sets[-1][0].numel()) - 1
-    n_paths = first
-    starts = np.concatenate([[0], np.cumsum([int(s[2].numel()) for s in sets])]).astype(np.int64)
-    total = int(starts[-1])
-    cat = lambda k, dt: (torch.cat([s[k] for s in sets]) if sets else torch.empty(0, dtype=dt, device=dev)).contiguous()
-    x, y, owner, work, pas = cat(2, torch.float64), cat(3, torch.float64), cat(4, torch.int64), cat(5, torch.uint8), cat(6, torch.int32)
-    poff = torch.cat([s[0][:-1] + int(starts[k]) for k, s in enumerate(sets)] + [torch.full((1,), total, dtype=torch.int64, device=dev)]).contiguous()
-    poff_h = None
-    if all(s[1] is not None for s in sets):
-        poff_h = np.ascontiguousarray(np.concatenate([np.asarray(s[1][:-1], dtype=np.int64) + starts[k] for k, s in enumerate(sets)] + [[total]]),
-                                      dtype=np.int64)
-    if n_paths and (n == 0 or int(owner.min()) < 0 or int(owner.max()) >= n):
-        raise ValueError('path_field must name a field of the batch')
-    ids = torch.argsort(owner, stable=True).contiguous()
-    fpo = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    if n:
-        fpo[1:] = torch.cumsum(torch.bincount(owner, minlength=n), dim=0)
-    return n_paths, total, poff, poff_h, x, y, work, pas, fpo, ids
+        sets.append(_cover_set(ps, n_paths, dev))
+        n_paths += int(sets[-1][0].offsets.numel()) - 1
+    _, starts, poff, poff_h, (x, y, work, pas) = _join_csr([ps.offsets for ps, *_ in sets], [ps.offsets_host for ps, *_ in sets],
+                                                           [(ps.x, ps.y, w, p) for ps, _, w, p in sets],
+                                                           (torch.float64, torch.float64, torch.uint8, torch.int32), dev)
+    owner = torch.cat([f.to(dev) for _, f, _, _ in sets]) if sets else torch.zeros(0, dtype=torch.int64, device=dev)
+    ids, fpo = _group_by(owner, n, 'path_field must name a field of the batch')
+    return n_paths, int(starts[-1]), poff, poff_h, x, y, work, pas, fpo, ids
 
 
 def polygon_coverage(fields, width, res, paths=(), caps='flat', want_grid=False, device=None):
@@ -2718,7 +2752,7 @@ def coverage_regions(coverage, kind='missed', connectivity=4, min_area=0.0, want
     L.check(ctx.lib.fcpp_cover_regions_fill(ctx.handle, n, _ptr(dims), _ptr(coff), _host_ptr(coff_h), _ptr(labels), _ptr(roff), _host_ptr(roff_h), k,
                                             _ptr(rec)))
     res = float(coverage.res)
-    field_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), roff[1:] - roff[:-1], output_size=k)
+    field_of = _owners(roff, k)
     dropped = torch.zeros((n, 2), dtype=torch.int64, device=dev)
     if min_area > 0.0:
         keep = rec[:, 1].to(torch.float64) * (res * res) >= float(min_area)
@@ -2732,8 +2766,7 @@ def coverage_regions(coverage, kind='missed', connectivity=4, min_area=0.0, want
             # one gather: a region's new index within its field, -2 when it was dropped; slot k serves the non-members
             remap = torch.cat([torch.where(keep, kept_before - new_off[field_of], torch.full_like(kept_before, -2)),
                                torch.full((1,), -1, dtype=torch.int64, device=dev)]).to(torch.int32)
-            cell_field = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), coff[1:] - coff[:-1], output_size=total)
-            slot = torch.where(labels >= 0, labels.to(torch.int64) + roff[cell_field], torch.full((1,), k, dtype=torch.int64, device=dev))
+            slot = torch.where(labels >= 0, labels.to(torch.int64) + roff[_owners(coff, total)], torch.full((1,), k, dtype=torch.int64, device=dev))
             labels = remap[slot]
         rec, field_of, roff = rec[keep], field_of[keep], new_off
         roff_h = roff.cpu().numpy()
@@ -2784,11 +2817,7 @@ def patch_swaths(regions, width, angle, margin=None, join=None, device=None):
     res = float(cov.res)
     margin = res / 2 if margin is None else float(margin)
     join = float(width) if join is None else float(join)
-    ang = _dev_f64(angle, dev).reshape(-1)
-    if ang.numel() == 1 and n != 1:
-        ang = ang.expand(n).contiguous()
-    if ang.numel() != n:
-        raise ValueError('angle must be a scalar or hold one value per field')
+    ang = _one_per(_dev_f64(angle, dev), n, 'angle', 'value per field')
     dims, coff, labels, roff = cov.dims.contiguous(), cov.cell_offsets.contiguous(), regions.labels.contiguous(), regions.offsets.contiguous()
     coff_h = np.ascontiguousarray(cov.cell_offsets_host, dtype=np.int64)
     roff_h = np.ascontiguousarray(regions.offsets_host, dtype=np.int64)
@@ -2814,8 +2843,7 @@ def patch_swaths(regions, width, angle, margin=None, join=None, device=None):
     region = torch.empty(m, dtype=i64, device=dev)
     L.check(ctx.lib.fcpp_patch_fill(ctx.handle, n, _ptr(dims), res, _ptr(roff), _host_ptr(roff_h), k, _ptr(frame), *rule, _ptr(rec), n_lines, n_words,
                                     _ptr(bitmap), _ptr(loff), m, _ptr(a[0]), _ptr(a[1]), _ptr(b[0]), _ptr(b[1]), _ptr(line), _ptr(length), _ptr(region)))
-    field_of = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), roff[1:] - roff[:-1], output_size=k)
-    lines_of_field = torch.zeros(n, dtype=i64, device=dev).index_add_(0, field_of, rec[:, 2]).to(torch.int32)
+    lines_of_field = torch.zeros(n, dtype=i64, device=dev).index_add_(0, _owners(roff, k), rec[:, 2]).to(torch.int32)
     status = rec[:, 6].contiguous().view(torch.int32).reshape(-1, 2)[:, 0].contiguous()
     ss = SwathSet(soff, soff_h, a.t().contiguous(), b.t().contiguous(), line, length, torch.zeros(n, dtype=torch.int32, device=dev), lines_of_field, ang)
     return ss, PatchInfo(region, rec[:, 2].contiguous(), rec[:, 3].contiguous(), status, frame, rec, margin, join)
@@ -2871,11 +2899,10 @@ def path_speeds(paths, vehicle, reverse_kmh=2.5, turn_kmh=None, a_dec=None, rest
     the vehicle stands at every Reeds-Shepp cusp (stop_at_cusps) and at the path ends (rest_start, rest_end); in between the greatest
     profile that speeds up by at most max_longitudinal_accel and brakes by at most a_dec."""
     torch = _torch()
-    if isinstance(paths, (tuple, list)):
+    if isinstance(paths, (tuple, list)):          # (the tuple form as a PathSet: its columns as given, no heading)
         offsets, x, y, kappa, part, gear = paths
-    else:
-        offsets, x, y, kappa, part, gear = (paths.offsets if paths.offsets_host is None else paths.offsets_host, paths.x, paths.y, paths.kappa,
-                                            paths.part, paths.gear)
+        paths = PathSet(offsets, None, x, y, None, kappa, part, gear)
+    offsets, x, y, kappa, part, gear = paths.offsets if paths.offsets_host is None else paths.offsets_host, paths.x, paths.y, paths.kappa, paths.part, paths.gear
     if device is None and isinstance(x, torch.Tensor) and x.is_cuda:
         device = x.device.index
     ctx = get_context(device)

@@ -81,19 +81,19 @@ def main():
 
     def transit():
         for lo, hi in chunks:
-            E._route_transit(ctx, ss, lo, hi, R, bool(mode))
+            E._route_transit(ctx, E._RouteChunk.of(ss, lo, hi), R, bool(mode))
     tr = _timed(torch, transit, args.reps, args.warmup)
     rec['transit'] = {'time': tr, 'entries_per_s': tt / (tr['median_ms'] * 1e-3)}
 
     # the clearance alone: the blocks are made outside the timed region, every repetition penalises a fresh copy
-    made = [E._route_transit(ctx, ss, lo, hi, R, bool(mode)) for lo, hi in chunks]
+    recs = [E._RouteChunk.of(ss, lo, hi) for lo, hi in chunks]
+    made = [E._route_transit(ctx, ch, R, bool(mode)) for ch in recs]
     parts = [E._fields_slice(pf, ro_h, vo_h, lo, hi) for lo, hi in chunks]
     box = {}
 
     def clear():
-        box['T'] = [c[0].clone() for c in made]
-        box['B'] = [E._route_transit_clear(ctx, ss, lo, hi, R, bool(mode), part, args.penalty, T, c[1], c[2], c[3], c[4])
-                    for (lo, hi), part, T, c in zip(chunks, parts, box['T'], made)]
+        box['T'] = [T.clone() for T in made]
+        box['B'] = [E._route_transit_clear(ctx, ch, R, bool(mode), part, args.penalty, T) for ch, part, T in zip(recs, parts, box['T'])]
     tc = _timed(torch, clear, args.reps, args.warmup)
     B = torch.cat(box['B']).cpu().numpy()
     T = torch.cat(box['T']).cpu().numpy()

@@ -29,7 +29,8 @@ def one_mode(args, torch, ctx, dev, polys, reversing):
                                  np.linspace(0.0, np.pi, args.angles, endpoint=False), passes=args.passes, reversing=reversing, headland_paths=True)
     t = E._mission_table([plan.headland_paths, plan.paths], dev, n_fields=n)
     del plan
-    n_items, stride = t['n_items'], max(1, -(-(t['longest'] - 1) // args.stations))
+    n_items, ps, total_in = len(t.ipath_h), t.paths, int(t.starts[-1])
+    stride = max(1, -(-(t.longest - 1) // args.stations))
     R = E._chord_radius(args.radius, args.spacing)
     n_slots = 2 * n_items + n
     i32, i64, f64 = torch.int32, torch.int64, torch.float64
@@ -37,13 +38,13 @@ def one_mode(args, torch, ctx, dev, polys, reversing):
     station, slot_item = torch.full((n_items,), -1, dtype=i64, device=dev), torch.full((n_slots,), -1, dtype=i64, device=dev)
     slot_word, slot_seg = torch.full((n_slots,), -1, dtype=i32, device=dev), torch.full((n_slots, 5), float('nan'), dtype=f64, device=dev)
     slot_total = torch.empty(n_slots, dtype=f64, device=dev)
-    head = (mode, n, P(t['ioff']), HP(t['ioff_h']), n_items, P(t['ipath']), HP(t['ipath_h']), P(t['iclosed']), int(t['first'][-1]), P(t['poff']),
-            HP(t['poff_h']), t['total_in'])
+    head = (mode, n, P(t.ioff), HP(t.ioff_h), n_items, P(t.ipath), HP(t.ipath_h), P(t.iclosed), int(t.first[-1]), P(ps.offsets),
+            HP(ps.offsets_host), total_in)
     rec = (P(status), P(station), P(slot_item), P(slot_word), P(slot_seg))
     ctx.bind_stream()
 
     def solve():
-        L.check(lib.fcpp_mission_solve(ctx.handle, *head, P(t['x']), P(t['y']), P(t['h']), P(t['part']), P(t['gear']), *([None] * 6), R, stride, P(status),
+        L.check(lib.fcpp_mission_solve(ctx.handle, *head, P(ps.x), P(ps.y), P(ps.heading), P(ps.part), P(ps.gear), *([None] * 6), R, stride, P(status),
                                        P(transit), P(skipped), P(station), P(slot_item), P(slot_word), P(slot_seg), P(slot_total)))
     solve()
     off, off_h, slot_off = torch.empty(n + 1, dtype=i64, device=dev), np.zeros(n + 1, np.int64), torch.empty(n_slots + 1, dtype=i64, device=dev)
@@ -55,7 +56,7 @@ def one_mode(args, torch, ctx, dev, polys, reversing):
     cols = [torch.empty(total, dtype=dt, device=dev) for dt in (f64, f64, f64, f64, torch.int8, torch.int8, i32, i64)]
 
     def fill():
-        L.check(lib.fcpp_mission_fill(ctx.handle, *head, P(t['x']), P(t['y']), P(t['h']), P(t['kap']), P(t['part']), P(t['gear']), None, None, None, R,
+        L.check(lib.fcpp_mission_fill(ctx.handle, *head, P(ps.x), P(ps.y), P(ps.heading), P(ps.kappa), P(ps.part), P(ps.gear), None, None, None, R,
                                       args.spacing, *rec, P(slot_off), total, *[P(c) for c in cols]))
     ms = {'solve': [], 'counts': [], 'fill': []}
     for r in range(args.warmup + args.reps):
@@ -63,14 +64,14 @@ def one_mode(args, torch, ctx, dev, polys, reversing):
             v = _event_ms(torch, fn)
             if r >= args.warmup:
                 ms[name].append(v)
-    closed = t['iclosed'] != 0
-    lens = torch.as_tensor(t['poff_h'][1:] - t['poff_h'][:-1], device=dev)[t['ipath']]
+    closed = t.iclosed != 0
+    lens = torch.as_tensor(np.diff(ps.offsets_host), device=dev)[t.ipath]
     nodes = torch.where(closed, torch.clamp((lens - 2) // stride + 1, min=0), torch.ones_like(lens))
     # (an upper bound: the candidates of every loop; the solves of a transition are the product of the two layers' nodes)
-    ioff_h = t['ioff_h']
+    ioff_h = t.ioff_h
     nd = nodes.cpu().numpy()
     solves = int(sum(int((nd[a:b - 1] * nd[a + 1:b]).sum()) for a, b in zip(ioff_h[:-1], ioff_h[1:]) if b - a > 1))
-    out = {'stride': stride, 'items': n_items, 'loops': int(closed.sum().item()), 'samples_in': t['total_in'], 'samples_out': total,
+    out = {'stride': stride, 'items': n_items, 'loops': int(closed.sum().item()), 'samples_in': total_in, 'samples_out': total,
            'failed_fields': int((status != 0).sum().item()), 'skipped_items': int(skipped.sum().item()), 'candidate_solves_at_most': solves,
            'transit_length_m': float(transit[status == 0].sum().item())}
     for name in ('solve', 'counts', 'fill'):
@@ -80,14 +81,14 @@ def one_mode(args, torch, ctx, dev, polys, reversing):
     if kf > 0:
         hi = int(ioff_h[kf])
         c = lambda a: np.ascontiguousarray(a.cpu().numpy())
-        hx, hy, hh, hk, hpart, hgear, hclosed = (c(t[k]) for k in ('x', 'y', 'h', 'kap', 'part', 'gear', 'iclosed'))
-        hioff, hipath = np.ascontiguousarray(ioff_h[:kf + 1]), np.ascontiguousarray(t['ipath_h'][:hi])
+        hx, hy, hh, hk, hpart, hgear, hclosed = (c(a) for a in (ps.x, ps.y, ps.heading, ps.kappa, ps.part, ps.gear, t.iclosed))
+        hioff, hipath = np.ascontiguousarray(ioff_h[:kf + 1]), np.ascontiguousarray(t.ipath_h[:hi])
         hs = 2 * hi + kf
         o = dict(status=np.zeros(kf, np.int32), transit=np.zeros(kf), skipped=np.zeros(kf, np.int32), station=np.full(hi, -1, np.int64),
                  slot_item=np.full(hs, -1, np.int64), slot_word=np.full(hs, -1, np.int32), slot_seg=np.full((hs, 5), np.nan), slot_total=np.zeros(hs),
                  off=np.zeros(kf + 1, np.int64), slot_off=np.zeros(hs + 1, np.int64))
         hp = lambda a: None if a is None else a.ctypes.data
-        hhead = (mode, kf, hp(hioff), hi, hp(hipath), hp(hclosed), int(t['first'][-1]), hp(t['poff_h']), t['total_in'], hp(hx), hp(hy), hp(hh), hp(hk),
+        hhead = (mode, kf, hp(hioff), hi, hp(hipath), hp(hclosed), int(t.first[-1]), hp(ps.offsets_host), total_in, hp(hx), hp(hy), hp(hh), hp(hk),
                  hp(hpart), hp(hgear), *([None] * 6), R, stride, args.spacing, *[hp(o[k]) for k in ('status', 'transit', 'skipped', 'station', 'slot_item',
                                                                                                    'slot_word', 'slot_seg', 'slot_total', 'off', 'slot_off')])
         assert lib.fcpp_debug_mission_paths(*hhead, 0, *([None] * 8)) == 0, lib.fcpp_last_error()

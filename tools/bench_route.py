@@ -75,7 +75,7 @@ def main():
 
     def transit():
         for lo, hi in chunks:
-            E._route_transit(ctx, ss, lo, hi, R, bool(mode))
+            E._route_transit(ctx, E._RouteChunk.of(ss, lo, hi), R, bool(mode))
     tr = _timed(torch, transit, args.reps, args.warmup)
     rec['transit'] = {'entries': tt, 'time': tr, 'entries_per_s': tt / (tr['median_ms'] * 1e-3)}
     box = {}
@@ -99,13 +99,13 @@ def main():
 
         def penalised():
             for (lo, hi), part in zip(chunks, parts):
-                c = E._route_transit(ctx, ss, lo, hi, R, bool(mode))
-                E._route_transit_clear(ctx, ss, lo, hi, R, bool(mode), part, args.penalty, c[0], c[1], c[2], c[3], c[4])
+                ch = E._RouteChunk.of(ss, lo, hi)
+                E._route_transit_clear(ctx, ch, R, bool(mode), part, args.penalty, E._route_transit(ctx, ch, R, bool(mode)))
 
         def priced():
             listed[0] = 0
             for (lo, hi), part in zip(chunks, parts):
-                E._route_transit_priced(ctx, ss, lo, hi, R, bool(mode), part, args.penalty)
+                E._route_transit_priced(ctx, E._RouteChunk.of(ss, lo, hi), R, bool(mode), part, args.penalty)
                 got = C.c_int64(0)
                 L.check(lib.fcpp_ctx_route_priced_passes(ctx.handle, C.byref(got), None))
                 listed[0] += got.value
