@@ -33,6 +33,7 @@
 
 #include "fcpp_clear.h"
 #include "fcpp_clearfn.h"
+#include "fcpp_launch.h"
 #include "fcpp_listfn.h"
 
 namespace fcpp {
@@ -40,8 +41,6 @@ namespace fcpp {
 static constexpr int CBLOCK = 256;            // k_clear_transit (= CLEAR_TILE = CLEAR_EDGE_CHUNK), k_clear_conn
 static constexpr int CWAVES = CBLOCK / 64;
 static_assert(CBLOCK == CLEAR_TILE && CBLOCK == CLEAR_EDGE_CHUNK, "a thread per entry of the tile and per staged edge");
-
-#define CLEAR_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 struct __attribute__((aligned(16))) ClearEdge { double x0, y0, x1, y1, ex, ey; };
 
@@ -209,20 +208,16 @@ __global__ __launch_bounds__(CBLOCK) void k_clear_field_status(ClearFields F, in
 int launch_clear_field_status(hipStream_t st, const ClearFields &F, int32_t *status)
 {
     if (F.n <= 0 || !status) return 0;
-    hipLaunchKernelGGL(k_clear_field_status, dim3((unsigned)((F.n + CBLOCK - 1) / CBLOCK)), dim3(CBLOCK), 0, st, F, status);
-    CLEAR_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_clear_field_status, blocks_for(F.n, CBLOCK), CBLOCK, F, status);
 }
 
 int launch_clear_conn(hipStream_t st, int mode, int64_t n, const double *fx, const double *fy, const double *fh, double R, const int32_t *word,
                       const double *seg, const int64_t *pair_field, const ClearFields &F, int32_t *crossings, int8_t *inside, double *first_s)
 {
     if (n <= 0 || (!crossings && !inside && !first_s)) return 0;
-    const dim3 grid((unsigned)((n + CBLOCK - 1) / CBLOCK));
-    if (mode == 0) hipLaunchKernelGGL(k_clear_conn<0>, grid, dim3(CBLOCK), 0, st, n, fx, fy, fh, R, word, seg, pair_field, F, crossings, inside, first_s);
-    else hipLaunchKernelGGL(k_clear_conn<1>, grid, dim3(CBLOCK), 0, st, n, fx, fy, fh, R, word, seg, pair_field, F, crossings, inside, first_s);
-    CLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_clear_conn<M()>, blocks_for(n, CBLOCK), CBLOCK, n, fx, fy, fh, R, word, seg, pair_field, F, crossings, inside, first_s);
+    });
 }
 
 int launch_clear_transit(hipStream_t st, int64_t n, const int64_t *soff, const double *ax, const double *ay, const double *bx, const double *by,
@@ -230,15 +225,10 @@ int launch_clear_transit(hipStream_t st, int64_t n, const int64_t *soff, const d
                          const ClearFields &F, double penalty, double *T, uint8_t *B)
 {
     if (n <= 0 || n_tiles <= 0) return 0;
-    const dim3 grid((unsigned)n_tiles);
-    if (mode == 0)
-        hipLaunchKernelGGL((k_clear_transit<0, false>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
-                           nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((k_clear_transit<1, false>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
-                           nullptr, nullptr);
-    CLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_clear_transit<M(), false>, (unsigned)n_tiles, CBLOCK, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
+                      nullptr, nullptr);
+    });
 }
 
 int launch_route_priced_first(hipStream_t st, int64_t n, const int64_t *soff, const double *ax, const double *ay, const double *bx,
@@ -246,16 +236,11 @@ int launch_route_priced_first(hipStream_t st, int64_t n, const int64_t *soff, co
                               int64_t n_tiles, const ClearFields &F, double penalty, double *T, int8_t *K, int64_t *list, unsigned long long *count)
 {
     if (n <= 0 || n_tiles <= 0) return 0;
-    const dim3 grid((unsigned)n_tiles);
     uint8_t *B = reinterpret_cast<uint8_t *>(K);
-    if (mode == 0)
-        hipLaunchKernelGGL((k_clear_transit<0, true>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B, list,
-                           count);
-    else
-        hipLaunchKernelGGL((k_clear_transit<1, true>), grid, dim3(CBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B, list,
-                           count);
-    CLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_clear_transit<M(), true>, (unsigned)n_tiles, CBLOCK, n, soff, ax, ay, bx, by, angle, R, toff, tile_off, F, penalty, T, B,
+                      list, count);
+    });
 }
 
 }  // namespace fcpp

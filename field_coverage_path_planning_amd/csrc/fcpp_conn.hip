@@ -22,21 +22,13 @@
 
 #include "fcpp_conn.h"
 #include "fcpp_connfn.h"
+#include "fcpp_launch.h"
 #include "fcpp_samplefn.h"
 
 namespace fcpp {
 
 static constexpr int CBLOCK = 256;
 static_assert(CONN_COLS == CBLOCK && CONN_ROWS <= CBLOCK, "a lane per column; the first CONN_ROWS lanes prepare the rows");
-
-#define CONN_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-// a launch of kernel<0> or kernel<1> by mode, as launch_route_transit does
-#define CONN_LAUNCH(kernel, mode, grid, ...)                                                      \
-    do {                                                                                          \
-        if ((mode) == 0) hipLaunchKernelGGL(kernel<0>, grid, dim3(CBLOCK), 0, st, __VA_ARGS__);   \
-        else hipLaunchKernelGGL(kernel<1>, grid, dim3(CBLOCK), 0, st, __VA_ARGS__);               \
-        CONN_LAUNCH_CHECK();                                                                      \
-    } while (0)
 
 template <int MODE>
 __global__ __launch_bounds__(CBLOCK) void k_conn_solve(int64_t n, const double *__restrict__ fx, const double *__restrict__ fy,
@@ -130,31 +122,29 @@ int launch_conn_solve(hipStream_t st, int mode, int64_t n, const double *fx, con
                       const double *ty, const double *th, double R, int32_t *word, double *seg, double *len)
 {
     if (n <= 0) return 0;
-    CONN_LAUNCH(k_conn_solve, mode, dim3((unsigned)((n + CBLOCK - 1) / CBLOCK)), n, fx, fy, fh, tx, ty, th, R, word, seg, len);
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_conn_solve<M()>, blocks_for(n, CBLOCK), CBLOCK, n, fx, fy, fh, tx, ty, th, R, word, seg, len);
+    });
 }
 
 int launch_conn_matrix(hipStream_t st, int mode, int64_t n_from, const double *fx, const double *fy, const double *fh, int64_t n_to,
                        const double *tx, const double *ty, const double *th, double R, double *D, int8_t *word)
 {
     if (n_from <= 0 || n_to <= 0) return 0;
-    const dim3 grid((unsigned)((n_to + CONN_COLS - 1) / CONN_COLS), (unsigned)((n_from + CONN_ROWS - 1) / CONN_ROWS));
-    CONN_LAUNCH(k_conn_matrix, mode, grid, n_from, fx, fy, fh, n_to, tx, ty, th, R, D, word);
-    return 0;
+    const dim3 grid(blocks_for(n_to, CONN_COLS), blocks_for(n_from, CONN_ROWS));
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_conn_matrix<M()>, grid, CBLOCK, n_from, fx, fy, fh, n_to, tx, ty, th, R, D, word);
+    });
 }
 
 int launch_dubins_counts(hipStream_t st, int64_t n, const double *len, double spacing, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL((k_sample_counts<CBLOCK, DubinsLength>), dim3(1), dim3(CBLOCK), 0, st, n, DubinsLength{ len }, spacing, 1, 1, out_offsets, err);
-    CONN_LAUNCH_CHECK();
-    return 0;
+    return launch_sample_counts<CBLOCK>(st, n, DubinsLength{ len }, spacing, 1, 1, out_offsets, err);
 }
 
 int launch_rs_counts(hipStream_t st, int64_t n, const int32_t *word, const double *seg, double spacing, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL((k_path_counts<CBLOCK, RsCount>), dim3(1), dim3(CBLOCK), 0, st, n, RsCount{ word, seg, spacing }, out_offsets, err);
-    CONN_LAUNCH_CHECK();
-    return 0;
+    return launch_path_counts<CBLOCK>(st, n, RsCount{ word, seg, spacing }, out_offsets, err);
 }
 
 int launch_conn_sample(hipStream_t st, int mode, int64_t n, const double *fx, const double *fy, const double *fh, double R, const int32_t *word,
@@ -162,9 +152,10 @@ int launch_conn_sample(hipStream_t st, int mode, int64_t n, const double *fx, co
                        double *kappas, int8_t *gears)
 {
     if (total_samples <= 0 || n <= 0) return 0;
-    CONN_LAUNCH(k_conn_sample, mode, dim3((unsigned)((total_samples + CBLOCK - 1) / CBLOCK)), n, fx, fy, fh, R, word, seg, spacing, out_offsets,
-                total_samples, xs, ys, hs, kappas, gears);
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_conn_sample<M()>, blocks_for(total_samples, CBLOCK), CBLOCK, n, fx, fy, fh, R, word, seg, spacing, out_offsets,
+                      total_samples, xs, ys, hs, kappas, gears);
+    });
 }
 
 }  // namespace fcpp

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "fcpp_cover.h"
+#include "fcpp_launch.h"
 
 namespace fcpp {
 
@@ -136,9 +137,7 @@ int launch_cover(hipStream_t st, int64_t n_jobs, int64_t n_tiles, const DevCover
                  uint8_t *grid, unsigned long long *counts)
 {
     if (n_jobs <= 0 || n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_cover, dim3((unsigned)n_tiles), dim3(256), 0, st, n_jobs, jobs, px, py, grid, counts);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_cover, (unsigned)n_tiles, 256, n_jobs, jobs, px, py, grid, counts);
 }
 
 }  // namespace fcpp

@@ -39,7 +39,7 @@ struct DevConst {
 };
 
 // Per-kernel device timing (fcpp_batch_set_profiling): when the caller has armed g_launch_prof, the next launcher call dispatches
-// its kernel with hipExtLaunchKernelGGL(start, stop): the two events take the dispatch's own begin / end time stamps -- no marker
+// its kernel with the two events (launch_stage, fcpp_launch.h): they take the dispatch's own begin / end time stamps -- no marker
 // packets between the kernels, so the timed step runs as it does unprofiled -- and the launcher disarms it.
 struct LaunchProf { hipEvent_t start = nullptr, stop = nullptr; };
 extern thread_local LaunchProf g_launch_prof;

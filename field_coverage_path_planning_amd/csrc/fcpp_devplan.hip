@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "fcpp_devplan.h"
+#include "fcpp_launch.h"
 #include "fcpp_quiet_fn.h"
 
 namespace fcpp {
@@ -681,16 +682,12 @@ int launch_scan(hipStream_t st, int64_t n, int c0, int c1, const DevPlanScratch 
 {
     const int64_t nblk = (n + 1023) / 1024;
     const int nc = c1 - c0;
-    if (nblk <= devplan_small_blocks()) {
-        hipLaunchKernelGGL(k_scan_small, dim3((unsigned)nc), dim3(1024), 0, st, n, c0, s.counts, s.bases, s.totals, mirror, with_flags, derive, fuse_possible, done_gen);
-        const hipError_t e0 = hipGetLastError();
-        return e0 == hipSuccess ? 0 : (int)e0;
-    }
-    hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nblk, (unsigned)nc), dim3(256), 0, st, n, c0, s.counts, s.blk_sums, nblk);
-    hipLaunchKernelGGL(k_scan_block_bases, dim3((unsigned)nc), dim3(256), 0, st, c0, s.blk_sums, nblk, s.totals, mirror, with_flags, done_gen);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nblk, (unsigned)nc), dim3(256), 0, st, n, c0, s.counts, s.blk_sums, nblk, s.bases, derive, fuse_possible);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (nblk <= devplan_small_blocks())
+        return launch(st, k_scan_small, (unsigned)nc, 1024, n, c0, s.counts, s.bases, s.totals, mirror, with_flags, derive, fuse_possible, done_gen);
+    const dim3 grid((unsigned)nblk, (unsigned)nc);
+    if (int e = launch(st, k_scan_block_sums, grid, 256, n, c0, s.counts, s.blk_sums, nblk)) return e;
+    if (int e = launch(st, k_scan_block_bases, (unsigned)nc, 256, c0, s.blk_sums, nblk, s.totals, mirror, with_flags, done_gen)) return e;
+    return launch(st, k_scan_apply, grid, 256, n, c0, s.counts, s.blk_sums, nblk, s.bases, derive, fuse_possible);
 }
 
 // ---- k_tile_fields: one wavefront per field, the tiler's cut at the reference's sampling -------------------------------------------------
@@ -1897,64 +1894,39 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
     tcc.no_bases = two_level ? 0 : 1;
     auto plan = [&]() {
         if (plan_serial)
-            hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               agg, n_polys, check_obstacles, 0, tc.gen);
-        else
-            hipLaunchKernelGGL(k_plan_fields16, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                               agg, n_polys, check_obstacles, tc.gen);
+            return launch(st, k_plan_fields, blocks_for(n, 64), 64, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals, agg,
+                          n_polys, check_obstacles, 0, tc.gen);
+        return launch(st, k_plan_fields16, blocks_for(n, 4), 64, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals, agg, n_polys,
+                      check_obstacles, tc.gen);
     };
     // (more fields than one round of wavefronts takes -- 4 per SIMD x 1024 SIMDs with the primitives staged in LDS: they are not staged, five
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
     auto count = [&]() {
-        const unsigned grid = (unsigned)((n + TW_WAVES - 1) / TW_WAVES);
+        const unsigned grid = blocks_for(n, TW_WAVES);
         if (tc.direct == DIRECT_COUNT) {       // (one workgroup more, the first: the early point total -- tile_fields_body)
-            if (n <= 4096)
-                hipLaunchKernelGGL((k_tile_fields_direct<true>), dim3(grid + 1u), dim3(64 * TW_WAVES), 0, st, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts,
-                                   s.totals, agg, totals_host, s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
-            else
-                hipLaunchKernelGGL((k_tile_fields_direct<false>), dim3(grid + 1u), dim3(64 * TW_WAVES), 0, st, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts,
-                                   s.totals, agg, totals_host, s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
-        } else if (tc.dense)
-            hipLaunchKernelGGL((k_tile_fields<false, true, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
-        else if (n <= 4096)
-            hipLaunchKernelGGL((k_tile_fields<false, true>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
-        else
-            hipLaunchKernelGGL((k_tile_fields<false, false>), dim3(grid), dim3(64 * TW_WAVES), 0, st, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp,
-                               s.info, s.counts, s.bases, s.totals, agg, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
+            const auto kernel = n <= 4096 ? k_tile_fields_direct<true> : k_tile_fields_direct<false>;
+            return launch(st, kernel, grid + 1u, 64 * TW_WAVES, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts, s.totals, agg, totals_host,
+                          s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
+        }
+        auto kernel = k_tile_fields<false, true, true>;
+        if (!tc.dense) kernel = n <= 4096 ? k_tile_fields<false, true> : k_tile_fields<false, false>;
+        return launch(st, kernel, grid, 64 * TW_WAVES, n, tcc, DevConst(), s.fields_tmp, s.prims_tmp, s.info, s.counts, s.bases, s.totals, agg,
+                      nullptr, nullptr, s.keep_tiles, s.keep_wtiles, DevPlanTables());
     };
     if (tc.dense) {
         // dense sampling: the chunks of every quiet run lie on 512-point boundaries of the batch arrays -- the pass needs the point offsets
-        plan();
-        int rc0 = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0);
-        if (rc0) return rc0;
+        if (int e = plan()) return e;
+        if (int e = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0)) return e;
         tcc.no_bases = 0;
-        count();
-        rc0 = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
-        if (rc0) return rc0;
-        const hipError_t e0 = hipGetLastError();
-        return e0 == hipSuccess ? 0 : (int)e0;
+        if (int e = count()) return e;
+        return launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
     }
-    plan();
-    count();
-    int rc = 0;
-    if (two_level) {
-        const hipError_t e2 = hipGetLastError();
-        return e2 == hipSuccess ? 0 : (int)e2;
-    }
-    if (one_scan) {
-        rc = launch_scan(st, n, PC_POINTS, PC_COLS, s, totals_host, 1, 1, tc.fuse_spans, tc.gen);
-        if (rc) return rc;
-        const hipError_t e1 = hipGetLastError();
-        return e1 == hipSuccess ? 0 : (int)e1;
-    }
-    rc = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0, 1, tc.fuse_spans);
-    if (rc) return rc;
-    rc = launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
-    if (rc) return rc;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (int e = plan()) return e;
+    if (int e = count()) return e;
+    if (two_level) return 0;
+    if (one_scan) return launch_scan(st, n, PC_POINTS, PC_COLS, s, totals_host, 1, 1, tc.fuse_spans, tc.gen);
+    if (int e = launch_scan(st, n, PC_POINTS, PC_PRIMS + 1, s, totals_host, 0, 1, tc.fuse_spans)) return e;
+    return launch_scan(st, n, PC_TILES, PC_COLS, s, totals_host, 1, 0, 0, tc.gen);
 }
 
 #ifdef FCPP_DIAG_TILE
@@ -1975,10 +1947,8 @@ extern "C" __attribute__((visibility("default"))) int fcpp_diag_fill_stamps(unsi
 int launch_devplan_points(hipStream_t st, int64_t n, const PlanConsts &pc, const DevPlanScratch &s, const fcpp_field *fields)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_plan_fields, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals,
-                       (int64_t *)nullptr, (int64_t)0, 0, 1, (int64_t)0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_plan_fields, blocks_for(n, 64), 64, n, pc, fields, s.info, s.fields_tmp, s.prims_tmp, s.counts, s.totals, nullptr, 0, 0, 1,
+                  0);
 }
 
 int launch_devplan_rescan(hipStream_t st, int64_t n, const DevPlanScratch &s)
@@ -1996,21 +1966,18 @@ int launch_devplan_fill(hipStream_t st, int64_t n, const DevTileConsts &tc, cons
     const DevPlanTables t = { FCPP_FILL_TABLES(X) };
 #undef X
     if (tc.dense)
-        hipLaunchKernelGGL((k_tile_fields<true, true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
-                           s.info, s.counts, s.bases, s.totals, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, s.keep_tiles, s.keep_wtiles, t);
-    else      // (speculative: one workgroup more, the publisher -- tile_fields_body)
-        hipLaunchKernelGGL((k_tile_fields<true, true>), dim3((unsigned)((n + TW_WAVES - 1) / TW_WAVES) + (two_level ? 1u : 0u)), dim3(64 * TW_WAVES), 0, st, n, tc, cst, s.fields_tmp, s.prims_tmp,
-                           s.info, s.counts, s.bases, s.totals, two_level ? s.agg : nullptr, two_level ? s.agg_next : nullptr, two_level ? totals_host : nullptr, s.keep_tiles, s.keep_wtiles, t);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+        return launch(st, k_tile_fields<true, true, true>, blocks_for(n, TW_WAVES), 64 * TW_WAVES, n, tc, cst, s.fields_tmp, s.prims_tmp, s.info,
+                      s.counts, s.bases, s.totals, nullptr, nullptr, nullptr, s.keep_tiles, s.keep_wtiles, t);
+    // (speculative: one workgroup more, the publisher -- tile_fields_body)
+    return launch(st, k_tile_fields<true, true>, blocks_for(n, TW_WAVES) + (two_level ? 1u : 0u), 64 * TW_WAVES, n, tc, cst, s.fields_tmp,
+                  s.prims_tmp, s.info, s.counts, s.bases, s.totals, two_level ? s.agg : nullptr, two_level ? s.agg_next : nullptr,
+                  two_level ? totals_host : nullptr, s.keep_tiles, s.keep_wtiles, t);
 }
 
 int launch_debug_math(hipStream_t st, int fn, int64_t n, const double *a, const double *b, double *out0, double *out1)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fn, n, a, b, out0, out1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_debug_math, blocks_for(n, 256), 256, fn, n, a, b, out0, out1);
 }
 
 }  // namespace fcpp

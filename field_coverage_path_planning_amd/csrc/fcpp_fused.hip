@@ -22,6 +22,7 @@
 // chunks before (after) the tile until the accumulated 2a*distance exceeds u_cap or the path ends.  The
 // recomputation uses the same arithmetic as the owning tile, so results do not depend on the tiling.
 #include <algorithm>
+#include "fcpp_launch.h"
 #include "fcpp_quiet_fn.h"
 
 namespace fcpp {
@@ -812,28 +813,25 @@ __global__ void k_build_template_metrics(int n, const double2 *__restrict__ t, d
 int launch_field_junctions(hipStream_t st, int64_t n_fields, const DevField *fields, const DevConst &cst, void *junc)
 {
     if (n_fields <= 0) return 0;
-    hipLaunchKernelGGL(k_field_junctions, dim3((unsigned)((n_fields + 255) / 256)), dim3(256), 0, st, n_fields, fields, cst, (double2 *)junc);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_field_junctions, blocks_for(n_fields, 256), 256, n_fields, fields, cst, (double2 *)junc);
 }
 
 int launch_build_template_metrics(hipStream_t st, int n, const void *tmpl, void *dk)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_build_template_metrics, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const double2 *)tmpl, (double2 *)dk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_build_template_metrics, blocks_for(n, 256), 256, n, (const double2 *)tmpl, (double2 *)dk);
 }
 
 int launch_build_templates(hipStream_t st, const TurnTemplates &tt, const CacShape *shapes, void *tu, void *tc)
 {
     const int n = tt.nu > tt.nc ? tt.nu : tt.nc;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_build_templates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tt, shapes, (double2 *)tu,
-                       (double2 *)tc);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_build_templates, blocks_for(n, 256), 256, tt, shapes, (double2 *)tu, (double2 *)tc);
 }
+
+// k_plan_quiet<K, SD, TL, OB, wpb> for a launch's wpb of 8 or 4
+template <int K, bool SD, bool TL, bool OB>
+static auto quiet_kernel(int wpb) { return wpb == 8 ? k_plan_quiet<K, SD, TL, OB, 8> : k_plan_quiet<K, SD, TL, OB, 4>; }
 
 // kinds: which chunk kinds the list holds -- 14: straights and U-turns, 16: layer-1 spans
 int launch_plan_quiet(hipStream_t st, int64_t n_chunks, const DevTile *chunks, int kinds, const DevField *fields, const DevPrim *prims,
@@ -849,7 +847,6 @@ int launch_plan_quiet(hipStream_t st, int64_t n_chunks, const DevTile *chunks, i
     // slow allocations (2.40 -> 2.33, 2.61 -> 2.55 ms) and loses 1 % on the fast ones (2.045 -> 2.07 ms), which calibration finds; two per
     // workgroup: +11 % on cfg5.
     const int wpb = n_chunks >= 65536 && !(kinds == 16 && staged) ? 8 : 4;
-    const dim3 grid((unsigned)((n_chunks + wpb - 1) / wpb)), block(64 * wpb);
     // Resident waves of the span kernel are held to FOUR per SIMD by its LDS footprint (34 KiB per four-wave workgroup of 160 KiB per
     // CU): measured on identical memory cfg5 1.33 vs 1.44 ms at 5-7 waves and 1.59 ms at 3; the other
     // configurations do not care (+-1 %) -- except launches of a few rounds of workgroups, where FIVE per SIMD (27 KiB) end a round
@@ -859,21 +856,20 @@ int launch_plan_quiet(hipStream_t st, int64_t n_chunks, const DevTile *chunks, i
     const int static_lds = (has_obs ? wpb * 2 * OBS_LDS_VERTS * 8 : 32) + (kinds == 16 && staged ? wpb * 3 * TMPL_LDS * 8 : 32);
     const int span_lds = 34 * 1024 * wpb / 4;
     const int pad = kinds == 16 ? std::min(64 * 1024, std::max(0, span_lds - static_lds)) : 0;
-#define FCPP_QUIET(K, SD, TL, OB) do { if (wpb == 8) FCPP_LAUNCH((k_plan_quiet<K, SD, TL, OB, 8>), grid, block, pad, st, chunks, fields, prims, cst, obs, x, y, kappa, v, fs, partial, n_chunks); \
-                                       else FCPP_LAUNCH((k_plan_quiet<K, SD, TL, OB, 4>), grid, block, pad, st, chunks, fields, prims, cst, obs, x, y, kappa, v, fs, partial, n_chunks); } while (0)
+    auto quiet = [&](auto kernel) {
+        return launch_stage(st, kernel, blocks_for(n_chunks, wpb), { 64 * wpb, (size_t)pad }, chunks, fields, prims, cst, obs, x, y, kappa, v, fs,
+                            partial, n_chunks);
+    };
     // Instances: spans fetch their descriptors by scalar loads (SCALAR_DESC: that nearly halved their time in round 1), stage the
     // turn template in LDS when it is the reference's short one (STAGED), and every instance exists with and without the polygon
     // tests (OBS; without: 68 instead of 93 vector registers and no scalar spills in the span kernel, 80 instead of 116 in the dense
     // one -- cfg2 at 0.5 m 1.63 -> 1.39 ms).
-    if (kinds == 16 && staged && !has_obs) FCPP_QUIET(16, true, true, false);
-    else if (kinds == 16 && staged) FCPP_QUIET(16, true, true, true);
-    else if (kinds == 16 && !has_obs) FCPP_QUIET(16, true, false, false);
-    else if (kinds == 16) FCPP_QUIET(16, true, false, true);
-    else if (!has_obs) FCPP_QUIET(14, false, false, false);
-    else FCPP_QUIET(14, false, false, true);
-#undef FCPP_QUIET
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (kinds == 16 && staged && !has_obs) return quiet(quiet_kernel<16, true, true, false>(wpb));
+    if (kinds == 16 && staged) return quiet(quiet_kernel<16, true, true, true>(wpb));
+    if (kinds == 16 && !has_obs) return quiet(quiet_kernel<16, true, false, false>(wpb));
+    if (kinds == 16) return quiet(quiet_kernel<16, true, false, true>(wpb));
+    if (!has_obs) return quiet(quiet_kernel<14, false, false, false>(wpb));
+    return quiet(quiet_kernel<14, false, false, true>(wpb));
 }
 
 int launch_plan_fused(hipStream_t st, int64_t n_tiles, const int32_t *ids, const DevTile *tiles,
@@ -882,10 +878,7 @@ int launch_plan_fused(hipStream_t st, int64_t n_tiles, const int32_t *ids, const
 {
     if (n_tiles <= 0) return 0;
     // register budget: at least three waves per SIMD (<= 168 VGPRs)
-    FCPP_LAUNCH(k_plan_fused<3>, dim3((unsigned)n_tiles), dim3(FBLOCK), 0, st, tiles, fields, prims, cst, obs, x, y,
-                kappa, v, fs, partial, ids);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_stage(st, k_plan_fused<3>, (unsigned)n_tiles, FBLOCK, tiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, ids);
 }
 
 }  // namespace fcpp

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "fcpp_ga.h"
+#include "fcpp_launch.h"
 
 namespace fcpp {
 
@@ -798,16 +799,13 @@ __global__ __launch_bounds__(64) void k_ga_check_perm(int n, int pop, const int3
 
 int launch_ga_check_perm(hipStream_t st, int n, int pop, const int32_t *routes, int32_t *bad)
 {
-    hipLaunchKernelGGL(k_ga_check_perm, dim3((unsigned)pop), dim3(64), 0, st, n, pop, routes, bad);
-    return (int)hipGetLastError();      // (hipSuccess is 0)
+    return launch(st, k_ga_check_perm, (unsigned)pop, 64, n, pop, routes, bad);
 }
 
 int launch_ga_pairs(hipStream_t st, int n, int pop, const double *D, const int32_t *cur, const double *cur_fit, int32_t *nxt,
                     double *nxt_fit, double *nxt_dist, const fcpp_ga_config &cfg, int gen, const GaState *state)
 {
-    hipLaunchKernelGGL(k_ga_pairs, dim3((unsigned)(pop / 2)), dim3(64), PairSlice::bytes(n), st, n, pop, D, cur, cur_fit, nxt, nxt_fit, nxt_dist,
-                       cfg, gen, state);
-    return (int)hipGetLastError();      // (hipSuccess is 0)
+    return launch(st, k_ga_pairs, (unsigned)(pop / 2), { 64, PairSlice::bytes(n) }, n, pop, D, cur, cur_fit, nxt, nxt_fit, nxt_dist, cfg, gen, state);
 }
 
 int launch_ga_stats_elite(hipStream_t st, int n, int pop, const int32_t *cur, const double *cur_fit, const double *cur_dist, int32_t *nxt,
@@ -815,9 +813,7 @@ int launch_ga_stats_elite(hipStream_t st, int n, int pop, const int32_t *cur, co
                           double *hist)
 {
     const size_t lds = pop <= GA_LDS_POP ? (size_t)pop * sizeof(double) : 0;
-    hipLaunchKernelGGL(k_ga_stats_elite, dim3(1), dim3(SB), lds, st, n, pop, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen, state,
-                       best_route, hist);
-    return (int)hipGetLastError();      // (hipSuccess is 0)
+    return launch(st, k_ga_stats_elite, 1, { SB, lds }, n, pop, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen, state, best_route, hist);
 }
 
 // how a launch spreads pop / 2 pairs over its workgroups on n_cu compute units: -> pair workgroups; base / extra as k_ga_generation reads them;
@@ -859,9 +855,8 @@ int launch_ga_generation(hipStream_t st, int n_cu, int n, int pop, const double 
                          int32_t *best_route, double *hist)
 {
     const GaLaunchPlan p = ga_launch_plan(n, pop, n_cu);
-    hipLaunchKernelGGL(k_ga_generation, dim3(p.groups + 2u), dim3(SB), p.lds, st, n, pop, D, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen,
-                       (int)PairSlice::ints(n), p.base, p.extra, state, best_route, hist);
-    return (int)hipGetLastError();      // (hipSuccess is 0)
+    return launch(st, k_ga_generation, p.groups + 2u, { SB, p.lds }, n, pop, D, cur, cur_fit, cur_dist, nxt, nxt_fit, nxt_dist, cfg, gen,
+                  (int)PairSlice::ints(n), p.base, p.extra, state, best_route, hist);
 }
 
 }  // namespace fcpp

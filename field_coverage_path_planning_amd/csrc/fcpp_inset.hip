@@ -21,13 +21,12 @@
 
 #include "fcpp_inset.h"
 #include "fcpp_insetfn.h"
+#include "fcpp_launch.h"
 #include "fcpp_samplefn.h"
 
 namespace fcpp {
 
 static constexpr int IBLOCK = 256;          // the offsets scan
-
-#define INSET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // exclusive scan of v over the workgroup; total in every lane
 template <int BLOCK>
@@ -249,20 +248,17 @@ static int inset_launch(hipStream_t st, int64_t n, int64_t D, int max_edges, con
     if (n <= 0 || D <= 0) return 0;
     const int64_t n_pairs = n * D;
     if (max_edges <= INSET_SMALL_EDGES) {
-        hipLaunchKernelGGL((k_inset<64, INSET_SMALL_EDGES, true, FILL>), dim3((unsigned)n_pairs), dim3(64), 0, st, (int64_t)0, n_pairs, D, ring_offsets,
-                           vert_offsets, x, y, dist, arc_step, scratch_d, scratch_i, n_rings, n_verts, status, gap, pair_ring_offsets,
-                           pair_vert_offsets, total_rings, total_verts, out_vert_offsets, out_x, out_y, out_src);
-        INSET_LAUNCH_CHECK();
-        return 0;
+        return launch(st, k_inset<64, INSET_SMALL_EDGES, true, FILL>, (unsigned)n_pairs, 64, (int64_t)0, n_pairs, D, ring_offsets, vert_offsets, x, y,
+                      dist, arc_step, scratch_d, scratch_i, n_rings, n_verts, status, gap, pair_ring_offsets, pair_vert_offsets, total_rings,
+                      total_verts, out_vert_offsets, out_x, out_y, out_src);
     }
     if (!scratch_d || !scratch_i) return (int)hipErrorInvalidValue;
     // (launches on one stream run one after another: the slabs of a launch are free when the next one starts)
     for (int64_t pair0 = 0; pair0 < n_pairs; pair0 += INSET_LAUNCH_PAIRS) {
         const int64_t m = n_pairs - pair0 < INSET_LAUNCH_PAIRS ? n_pairs - pair0 : INSET_LAUNCH_PAIRS;
-        hipLaunchKernelGGL((k_inset<256, INSET_MAX_EDGES, false, FILL>), dim3((unsigned)m), dim3(256), 0, st, pair0, n_pairs, D, ring_offsets,
-                           vert_offsets, x, y, dist, arc_step, scratch_d, scratch_i, n_rings, n_verts, status, gap, pair_ring_offsets,
-                           pair_vert_offsets, total_rings, total_verts, out_vert_offsets, out_x, out_y, out_src);
-        INSET_LAUNCH_CHECK();
+        if (int e = launch(st, k_inset<256, INSET_MAX_EDGES, false, FILL>, (unsigned)m, 256, pair0, n_pairs, D, ring_offsets, vert_offsets, x, y,
+                           dist, arc_step, scratch_d, scratch_i, n_rings, n_verts, status, gap, pair_ring_offsets, pair_vert_offsets, total_rings,
+                           total_verts, out_vert_offsets, out_x, out_y, out_src)) return e;
     }
     return 0;
 }
@@ -277,9 +273,7 @@ int launch_inset_count(hipStream_t st, int64_t n, int64_t D, int max_edges, cons
 
 int launch_inset_offsets(hipStream_t st, int64_t m, const int32_t *counts, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL((k_path_counts<IBLOCK, InsetCount>), dim3(1), dim3(IBLOCK), 0, st, m, InsetCount{ counts }, out_offsets, err);
-    INSET_LAUNCH_CHECK();
-    return 0;
+    return launch_path_counts<IBLOCK>(st, m, InsetCount{ counts }, out_offsets, err);
 }
 
 int launch_inset_fill(hipStream_t st, int64_t n, int64_t D, int max_edges, const int64_t *ring_offsets, const int64_t *vert_offsets,

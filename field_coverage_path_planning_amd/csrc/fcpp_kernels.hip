@@ -23,6 +23,7 @@
 
 #include <string.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_quiet_fn.h"
 
 namespace fcpp {
@@ -696,15 +697,11 @@ __global__ __launch_bounds__(64) void k_best_connections(int64_t n_pairs, const 
 // --------------------------------------------------------------------------------------------
 // launchers (called from fcpp_api.cpp)
 // --------------------------------------------------------------------------------------------
-#define FCPP_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 int launch_generate(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevField *fields,
                     const DevPrim *prims, const DevConst &cst, double *x, double *y, double *v, uint32_t *fs)
 {
     if (n_tiles <= 0) return 0;
-    FCPP_LAUNCH(k_generate, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tiles, fields, prims, cst, x, y, v, fs);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch_stage(st, k_generate, (unsigned)n_tiles, BLOCK, tiles, fields, prims, cst, x, y, v, fs);
 }
 
 int launch_curv_clamp(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths,
@@ -712,20 +709,14 @@ int launch_curv_clamp(hipStream_t st, int64_t n_tiles, const DevTile *tiles, con
                       double *v_out, double *kappa, unsigned long long *n_adjusted)
 {
     if (n_tiles <= 0) return 0;
-    FCPP_LAUNCH(k_curv_clamp, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tiles, paths, cst, do_clamp, x, y,
-                       v_in, v_out, kappa, n_adjusted);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch_stage(st, k_curv_clamp, (unsigned)n_tiles, BLOCK, tiles, paths, cst, do_clamp, x, y, v_in, v_out, kappa, n_adjusted);
 }
 
 int launch_scan_tiles(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths, const DevConst &cst,
                       const double *x, const double *y, const double *v_in, void *agg_f, void *agg_b)
 {
     if (n_tiles <= 0) return 0;
-    FCPP_LAUNCH(k_scan_tiles, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tiles, paths, cst, x, y, v_in,
-                       (Agg *)agg_f, (Agg *)agg_b);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch_stage(st, k_scan_tiles, (unsigned)n_tiles, BLOCK, tiles, paths, cst, x, y, v_in, (Agg *)agg_f, (Agg *)agg_b);
 }
 
 int64_t spine_scratch_bytes(int64_t n_tiles)
@@ -738,24 +729,17 @@ int launch_scan_spine(hipStream_t st, int64_t n_tiles, const void *agg_f, const 
                       double *carry_b, void *scratch)
 {
     if (n_tiles <= 0) return 0;
-    if (n_tiles <= SPINE_BLOCK || !scratch) {       // one workgroup walks every tile aggregate
-        FCPP_LAUNCH(k_scan_spine, dim3(1), dim3(BLOCK), 0, st, n_tiles, (const Agg *)agg_f, (const Agg *)agg_b, carry_f, carry_b);
-        FCPP_LAUNCH_CHECK();
-        return 0;
-    }
+    if (n_tiles <= SPINE_BLOCK || !scratch)         // one workgroup walks every tile aggregate
+        return launch_stage(st, k_scan_spine, 1, BLOCK, n_tiles, (const Agg *)agg_f, (const Agg *)agg_b, carry_f, carry_b);
     const int64_t nb = (n_tiles + SPINE_BLOCK - 1) / SPINE_BLOCK;
     Agg *block_f = (Agg *)scratch, *block_b = block_f + nb;
     double *cin_f = (double *)(block_b + nb), *cin_b = cin_f + nb;
     const dim3 grid((unsigned)nb, 2u);
-    FCPP_LAUNCH(k_spine_blocks<false>, grid, dim3(BLOCK), 0, st, n_tiles, nb, (const Agg *)agg_f, (const Agg *)agg_b, block_f, block_b,
-                (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (double *)nullptr);
-    FCPP_LAUNCH_CHECK();
-    FCPP_LAUNCH(k_scan_spine, dim3(1), dim3(BLOCK), 0, st, nb, (const Agg *)block_f, (const Agg *)block_b, cin_f, cin_b);
-    FCPP_LAUNCH_CHECK();
-    FCPP_LAUNCH(k_spine_blocks<true>, grid, dim3(BLOCK), 0, st, n_tiles, nb, (const Agg *)agg_f, (const Agg *)agg_b, block_f, block_b,
-                (const double *)cin_f, (const double *)cin_b, carry_f, carry_b);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    if (int e = launch_stage(st, k_spine_blocks<false>, grid, BLOCK, n_tiles, nb, (const Agg *)agg_f, (const Agg *)agg_b, block_f, block_b, nullptr,
+                             nullptr, nullptr, nullptr)) return e;
+    if (int e = launch_stage(st, k_scan_spine, 1, BLOCK, nb, block_f, block_b, cin_f, cin_b)) return e;
+    return launch_stage(st, k_spine_blocks<true>, grid, BLOCK, n_tiles, nb, (const Agg *)agg_f, (const Agg *)agg_b, block_f, block_b, cin_f, cin_b,
+                        carry_f, carry_b);
 }
 
 int launch_scan_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths, const DevConst &cst,
@@ -763,10 +747,7 @@ int launch_scan_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, con
                       const double *carry_f, const double *carry_b)
 {
     if (n_tiles <= 0) return 0;
-    FCPP_LAUNCH(k_scan_apply, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tiles, paths, cst, min_n, x, y, v_in,
-                       v_out, carry_f, carry_b);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch_stage(st, k_scan_apply, (unsigned)n_tiles, BLOCK, tiles, paths, cst, min_n, x, y, v_in, v_out, carry_f, carry_b);
 }
 
 int launch_validate(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths,
@@ -774,10 +755,7 @@ int launch_validate(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const
                     const double *y, const double *kappa, const double *v, uint32_t *fs, TilePartial *partial)
 {
     if (n_tiles <= 0) return 0;
-    FCPP_LAUNCH(k_validate, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tiles, paths, fields, cst, obs, x, y,
-                       kappa, v, fs, partial);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch_stage(st, k_validate, (unsigned)n_tiles, BLOCK, tiles, paths, fields, cst, obs, x, y, kappa, v, fs, partial);
 }
 
 // ---- fcpp_validate: geofence / obstacle flags of CALLER-SUPPLIED paths against arbitrary simple polygons -----------------------------------
@@ -912,10 +890,8 @@ int launch_validate_polys(hipStream_t st, int64_t n_tiles, const DevTile *tiles,
 {
     if (n_tiles <= 0) return 0;
     const DevPolySet f = { field_off, field_x, field_y, n_field }, o = { obst_off, obst_x, obst_y, n_obst };
-    hipLaunchKernelGGL(k_validate_polys, dim3((unsigned)((n_tiles + VAL_TILES_PER_WG - 1) / VAL_TILES_PER_WG)), dim3(BLOCK), 0, st, n_tiles, tiles, paths, f, o, obst_range,
-                       tol, a_lat, x, y, kappa, v, flags, stats);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_validate_polys, blocks_for(n_tiles, VAL_TILES_PER_WG), BLOCK, n_tiles, tiles, paths, f, o, obst_range, tol, a_lat, x, y,
+                  kappa, v, flags, stats);
 }
 
 // Batch creation (fused pipeline): the statistics slots of a batch, one per entry.  The slot of a quiet run gets the run's closed-form
@@ -945,9 +921,7 @@ int launch_run_consts(hipStream_t st, int64_t n_entries, const int32_t *ids, con
                       const DevPrim *prims, const DevConst &cst, TilePartial *partial)
 {
     if (n_entries <= 0) return 0;
-    hipLaunchKernelGGL(k_run_consts, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, st, n_entries, ids, run_count, tiles, fields, prims, cst, partial);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_run_consts, blocks_for(n_entries, 256), 256, n_entries, ids, run_count, tiles, fields, prims, cst, partial);
 }
 
 // The chunk lists of k_plan_quiet from the chunk groups the host listed (fcpp_tiler.cpp: derive_field, whose loop this is, with the same
@@ -1006,9 +980,7 @@ int launch_expand_chunks(hipStream_t st, int64_t n_segments, const DevChunkGroup
                          DevTile *chunks, DevTile *span_chunks)
 {
     if (n_segments <= 0) return 0;
-    hipLaunchKernelGGL(k_expand_chunks, dim3((unsigned)n_segments), dim3(64), 0, st, n_segments, groups, tiles, fields, chunks, span_chunks);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_expand_chunks, (unsigned)n_segments, 64, n_segments, groups, tiles, fields, chunks, span_chunks);
 }
 
 // group = lanes per path: 8, 64, or 256 (a workgroup per path)
@@ -1022,46 +994,38 @@ int launch_reduce_stats(hipStream_t st, int64_t n_list, TilePartial *partial, co
     memset(&c0, 0, sizeof c0);
     const DevConst &c = cst ? *cst : c0;
     if (group == 8)
-        FCPP_LAUNCH(k_reduce_stats<8>, dim3((unsigned)((n_list + 31) / 32)), dim3(256), 0, st, n_list, path_list, tile_first, partial, n_adjusted,
-                    stats, ids, run_count, tiles, fields, prims, c, clear_counts);
-    else if (group == 256 && scratch) {
-        FCPP_LAUNCH(k_reduce_stats_slice, dim3((unsigned)(n_list * REDUCE_SPLIT)), dim3(256), 0, st, path_list, tile_first, partial, ids, run_count,
-                    tiles, fields, prims, c, (StatAcc *)scratch, clear_counts);
-        hipLaunchKernelGGL(k_reduce_stats_join, dim3((unsigned)n_list), dim3(64), 0, st, path_list, (const StatAcc *)scratch, n_adjusted, stats);
-    } else if (group == 256)
-        FCPP_LAUNCH(k_reduce_stats_wg, dim3((unsigned)n_list), dim3(256), 0, st, n_list, path_list, tile_first, partial, n_adjusted, stats, ids,
-                    run_count, tiles, fields, prims, c, clear_counts);
-    else
-        FCPP_LAUNCH(k_reduce_stats<64>, dim3((unsigned)((n_list + 3) / 4)), dim3(256), 0, st, n_list, path_list, tile_first, partial, n_adjusted,
-                    stats, ids, run_count, tiles, fields, prims, c, clear_counts);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+        return launch_stage(st, k_reduce_stats<8>, blocks_for(n_list, 32), 256, n_list, path_list, tile_first, partial, n_adjusted, stats, ids,
+                            run_count, tiles, fields, prims, c, clear_counts);
+    if (group == 256 && scratch) {
+        if (int e = launch_stage(st, k_reduce_stats_slice, (unsigned)(n_list * REDUCE_SPLIT), 256, path_list, tile_first, partial, ids, run_count,
+                                 tiles, fields, prims, c, (StatAcc *)scratch, clear_counts)) return e;
+        return launch(st, k_reduce_stats_join, (unsigned)n_list, 64, path_list, (const StatAcc *)scratch, n_adjusted, stats);
+    }
+    if (group == 256)
+        return launch_stage(st, k_reduce_stats_wg, (unsigned)n_list, 256, n_list, path_list, tile_first, partial, n_adjusted, stats, ids, run_count,
+                            tiles, fields, prims, c, clear_counts);
+    return launch_stage(st, k_reduce_stats<64>, blocks_for(n_list, 4), 256, n_list, path_list, tile_first, partial, n_adjusted, stats, ids, run_count,
+                        tiles, fields, prims, c, clear_counts);
 }
 
 int launch_distance_matrix(hipStream_t st, int n, const double *x, const double *y, double *D)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_distance_matrix, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, st, n, x, y, D);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_distance_matrix, dim3(blocks_for(n, 256), (unsigned)n), 256, n, x, y, D);
 }
 
 int launch_best_connections(hipStream_t st, int64_t n_pairs, const int64_t *fo, const int64_t *to, const double *fx, const double *fy,
                             const double *tx, const double *ty, int32_t *bf, int32_t *bt, double *bd)
 {
     if (n_pairs <= 0) return 0;
-    hipLaunchKernelGGL(k_best_connections, dim3((unsigned)n_pairs), dim3(64), 0, st, n_pairs, fo, to, fx, fy, tx, ty, bf, bt, bd);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_best_connections, (unsigned)n_pairs, 64, n_pairs, fo, to, fx, fy, tx, ty, bf, bt, bd);
 }
 
 int launch_straight(hipStream_t st, int64_t n_seg, const double *seg, int n_pts, const int32_t *mask, double *out)
 {
     const int64_t n = n_seg * n_pts;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_straight, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n_seg, seg, n_pts, mask, out);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_straight, blocks_for(n, 256), 256, n_seg, seg, n_pts, mask, out);
 }
 
 int launch_corner_turns(hipStream_t st, int64_t n, const double *corners, const int32_t *ci, const int32_t *rev, double R, double L,
@@ -1069,28 +1033,20 @@ int launch_corner_turns(hipStream_t st, int64_t n, const double *corners, const 
 {
     if (n <= 0) return 0;
     const int64_t total = n * stride;
-    hipLaunchKernelGGL(k_corner_turns, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, corners, ci, rev, R, L, H, stride, out,
-                       counts);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_corner_turns, blocks_for(total, 256), 256, n, corners, ci, rev, R, L, H, stride, out, counts);
 }
 
 int launch_fresnel(hipStream_t st, int64_t n, const double *t, double *c, double *s)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_fresnel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, t, c, s);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_fresnel, blocks_for(n, 256), 256, n, t, c, s);
 }
 
 int launch_ga_fitness(hipStream_t st, int n, int64_t pop, const double *D, const int32_t *routes, double *dist,
                       double *fit, int order_mode)
 {
     if (pop <= 0) return 0;
-    hipLaunchKernelGGL(k_ga_fitness, dim3((unsigned)((pop + NWAVE - 1) / NWAVE)), dim3(BLOCK), 0, st, n, pop, D, routes,
-                       dist, fit, order_mode);
-    FCPP_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_ga_fitness, blocks_for(pop, NWAVE), BLOCK, n, pop, D, routes, dist, fit, order_mode);
 }
 
 }  // namespace fcpp

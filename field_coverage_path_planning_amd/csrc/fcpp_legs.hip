@@ -54,14 +54,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_legs.h"
 #include "fcpp_samplefn.h"
 
 namespace fcpp {
 
 static constexpr int LBLOCK = 256;
-
-#define LEGS_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // ---- the rule kernels -------------------------------------------------------------------------------------------------------------
 template <int MODE>
@@ -189,15 +188,12 @@ __global__ __launch_bounds__(LBLOCK) void k_leg_fill(int64_t n_slots, const type
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
-static unsigned leg_grid(int64_t lanes) { return (unsigned)((lanes + LBLOCK - 1) / LBLOCK); }
-
 int launch_legs(hipStream_t st, int64_t n, int64_t n_slots, const FpathIn &in, int mode, FpathLeg *legs, int64_t *cnt, int32_t *scratch, int32_t *status)
 {
     if (n <= 0) return 0;
-    if (mode == 0) hipLaunchKernelGGL(k_fpath_legs<0>, dim3(leg_grid(n_slots)), dim3(LBLOCK), 0, st, n, n_slots, in, legs, cnt, scratch, status);
-    else hipLaunchKernelGGL(k_fpath_legs<1>, dim3(leg_grid(n_slots)), dim3(LBLOCK), 0, st, n, n_slots, in, legs, cnt, scratch, status);
-    LEGS_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_fpath_legs<M()>, blocks_for(n_slots, LBLOCK), LBLOCK, n, n_slots, in, legs, cnt, scratch, status);
+    });
 }
 
 int launch_legs(hipStream_t st, int64_t n_rings, int64_t n_slots, const HpathIn &in, int mode, HpathLeg *legs, int64_t *cnt, int32_t *scratch,
@@ -205,10 +201,9 @@ int launch_legs(hipStream_t st, int64_t n_rings, int64_t n_slots, const HpathIn 
 {
     const int64_t n_verts = n_slots / 2;
     if (n_rings <= 0 || n_verts <= 0) return 0;
-    if (mode == 0) hipLaunchKernelGGL(k_hpath_legs<0>, dim3(leg_grid(n_verts)), dim3(LBLOCK), 0, st, n_rings, n_verts, in, legs, cnt, status, scratch);
-    else hipLaunchKernelGGL(k_hpath_legs<1>, dim3(leg_grid(n_verts)), dim3(LBLOCK), 0, st, n_rings, n_verts, in, legs, cnt, status, scratch);
-    LEGS_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_hpath_legs<M()>, blocks_for(n_verts, LBLOCK), LBLOCK, n_rings, n_verts, in, legs, cnt, status, scratch);
+    });
 }
 
 // the scan of the slots' counts as count_of takes them, then the groups
@@ -216,11 +211,8 @@ template <class P, class CountOf>
 static int leg_offsets(hipStream_t st, int64_t n_groups, int64_t n_slots, const typename P::In &in, const typename P::Leg *legs, CountOf count_of,
                        const int32_t *status, int64_t *leg_off, int64_t *path_off, const LegTotals &totals, int64_t *err)
 {
-    hipLaunchKernelGGL((k_path_counts<LBLOCK, CountOf>), dim3(1), dim3(LBLOCK), 0, st, n_slots, count_of, leg_off, err);
-    LEGS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_leg_groups<P>, dim3(leg_grid(n_groups + 1)), dim3(LBLOCK), 0, st, n_groups, n_slots, in, legs, status, leg_off, path_off, totals, err);
-    LEGS_LAUNCH_CHECK();
-    return 0;
+    if (int e = launch_path_counts<LBLOCK>(st, n_slots, count_of, leg_off, err)) return e;
+    return launch(st, k_leg_groups<P>, blocks_for(n_groups + 1, LBLOCK), LBLOCK, n_groups, n_slots, in, legs, status, leg_off, path_off, totals, err);
 }
 
 int launch_leg_offsets(hipStream_t st, int64_t n, int64_t n_slots, const FpathIn &in, const FpathLeg *legs, int64_t *cnt, int32_t *status,
@@ -233,12 +225,10 @@ int launch_leg_offsets(hipStream_t st, int64_t n_rings, int64_t n_slots, const H
                        const int32_t *scratch, int64_t *leg_off, int64_t *path_off, const LegTotals &totals, int64_t *err)
 {
     if (n_rings > 0) {
-        hipLaunchKernelGGL(k_hpath_mark, dim3(leg_grid(n_rings)), dim3(LBLOCK), 0, st, n_rings, in.roff, scratch, status);
-        LEGS_LAUNCH_CHECK();
+        if (int e = launch(st, k_hpath_mark, blocks_for(n_rings, LBLOCK), LBLOCK, n_rings, in.roff, scratch, status)) return e;
     }
     if (n_slots > 0) {
-        hipLaunchKernelGGL(k_hpath_settle, dim3(leg_grid(n_slots)), dim3(LBLOCK), 0, st, n_slots, legs, status, cnt);
-        LEGS_LAUNCH_CHECK();
+        if (int e = launch(st, k_hpath_settle, blocks_for(n_slots, LBLOCK), LBLOCK, n_slots, legs, status, cnt)) return e;
     }
     return leg_offsets<RingLegs>(st, n_rings, n_slots, in, legs, HpathCount{ cnt }, status, leg_off, path_off, totals, err);
 }
@@ -248,10 +238,8 @@ int launch_leg_fill(hipStream_t st, int64_t n_slots, const typename P::Leg *legs
                     double *x, double *y, double *heading, double *kappa, int8_t *part, int8_t *gear, int32_t *leg)
 {
     if (total_samples <= 0 || n_slots <= 0) return 0;
-    hipLaunchKernelGGL(k_leg_fill<P>, dim3(leg_grid(total_samples)), dim3(LBLOCK), 0, st, n_slots, legs, leg_off, total_samples, R, spacing, x, y, heading,
-                       kappa, part, gear, leg);
-    LEGS_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_leg_fill<P>, blocks_for(total_samples, LBLOCK), LBLOCK, n_slots, legs, leg_off, total_samples, R, spacing, x, y, heading,
+                  kappa, part, gear, leg);
 }
 
 template int launch_leg_fill<FieldLegs>(hipStream_t, int64_t, const FpathLeg *, const int64_t *, int64_t, double, double, double *, double *, double *,

@@ -26,6 +26,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_mission.h"
 #include "fcpp_samplefn.h"
 
@@ -33,8 +34,6 @@ namespace fcpp {
 
 static constexpr int MBLOCK = MISSION_BLOCK;
 static constexpr int MWAVES = MBLOCK / 64;
-
-#define MISSION_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 __global__ __launch_bounds__(MBLOCK) void k_mission_stations(MissionIn in, MissionTemp T)
 {
@@ -186,46 +185,36 @@ __global__ __launch_bounds__(MBLOCK) void k_mission_fill(MissionIn in, MissionRe
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
-static unsigned mission_grid(int64_t lanes) { return (unsigned)((lanes + MBLOCK - 1) / MBLOCK); }
-
 int launch_mission_stations(hipStream_t st, const MissionIn &in, const MissionTemp &T)
 {
     if (in.n_items <= 0) return 0;
-    hipLaunchKernelGGL(k_mission_stations, dim3(mission_grid(in.n_items * 64)), dim3(MBLOCK), 0, st, in, T);
-    MISSION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_mission_stations, blocks_for(in.n_items * 64, MBLOCK), MBLOCK, in, T);
 }
 
 int launch_mission_layers(hipStream_t st, int mode, const MissionIn &in, const MissionTemp &T)
 {
     if (in.n_fields <= 0) return 0;
-    if (mode == 0) hipLaunchKernelGGL(k_mission_layers<0>, dim3((unsigned)in.n_fields), dim3(MBLOCK), 0, st, in, T);
-    else hipLaunchKernelGGL(k_mission_layers<1>, dim3((unsigned)in.n_fields), dim3(MBLOCK), 0, st, in, T);
-    MISSION_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_mission_layers<M()>, (unsigned)in.n_fields, MBLOCK, in, T);
+    });
 }
 
 int launch_mission_finish(hipStream_t st, int mode, const MissionIn &in, const MissionTemp &T, const MissionOut &out)
 {
     if (in.n_fields <= 0) return 0;
-    if (mode == 0) hipLaunchKernelGGL(k_mission_finish<0>, dim3(mission_grid(in.n_fields)), dim3(MBLOCK), 0, st, in, T, out);
-    else hipLaunchKernelGGL(k_mission_finish<1>, dim3(mission_grid(in.n_fields)), dim3(MBLOCK), 0, st, in, T, out);
-    MISSION_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_mission_finish<M()>, blocks_for(in.n_fields, MBLOCK), MBLOCK, in, T, out);
+    });
 }
 
 int launch_mission_counts(hipStream_t st, int mode, const MissionIn &in, const MissionRec &rec, double spacing, int64_t *slot_offsets,
                           int64_t *path_offsets, int64_t *err)
 {
     const int64_t n_slots = 2 * in.n_items + in.n_fields;
-    if (mode == 0)
-        hipLaunchKernelGGL((k_path_counts<MBLOCK, MissionCount<0>>), dim3(1), dim3(MBLOCK), 0, st, n_slots, MissionCount<0>{ in, rec, spacing }, slot_offsets, err);
-    else
-        hipLaunchKernelGGL((k_path_counts<MBLOCK, MissionCount<1>>), dim3(1), dim3(MBLOCK), 0, st, n_slots, MissionCount<1>{ in, rec, spacing }, slot_offsets, err);
-    MISSION_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mission_path_offsets, dim3(mission_grid(in.n_fields + 1)), dim3(MBLOCK), 0, st, in, slot_offsets, path_offsets);
-    MISSION_LAUNCH_CHECK();
-    return 0;
+    const int e = by_mode(mode, [&](auto M) {
+        return launch_path_counts<MBLOCK>(st, n_slots, MissionCount<M()>{ in, rec, spacing }, slot_offsets, err);
+    });
+    return e ? e : launch(st, k_mission_path_offsets, blocks_for(in.n_fields + 1, MBLOCK), MBLOCK, in, slot_offsets, path_offsets);
 }
 
 int launch_mission_fill(hipStream_t st, int mode, const MissionIn &in, const MissionRec &rec, double spacing, const int64_t *slot_offsets,
@@ -233,15 +222,10 @@ int launch_mission_fill(hipStream_t st, int mode, const MissionIn &in, const Mis
                         int64_t *src)
 {
     if (in.n_fields <= 0 || total_samples <= 0) return 0;
-    const dim3 grid(mission_grid(total_samples));
-    if (mode == 0)
-        hipLaunchKernelGGL(k_mission_fill<0>, grid, dim3(MBLOCK), 0, st, in, rec, spacing, slot_offsets, total_samples, x, y, heading, kappa, part, gear,
-                           slot, src);
-    else
-        hipLaunchKernelGGL(k_mission_fill<1>, grid, dim3(MBLOCK), 0, st, in, rec, spacing, slot_offsets, total_samples, x, y, heading, kappa, part, gear,
-                           slot, src);
-    MISSION_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_mission_fill<M()>, blocks_for(total_samples, MBLOCK), MBLOCK, in, rec, spacing, slot_offsets, total_samples, x, y,
+                      heading, kappa, part, gear, slot, src);
+    });
 }
 
 }  // namespace fcpp

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_patch.h"
 #include "fcpp_patchfn.h"
 #include "fcpp_samplefn.h"
@@ -36,8 +37,6 @@ static constexpr int PWAVES = PBLOCK / 64;
 static constexpr int PWAVE_CELLS = REGION_BLOCK_CELLS / PWAVES;            // consecutive cells per wavefront of a numbering block
 static constexpr int PROUNDS = PWAVE_CELLS / 64;
 typedef unsigned long long u64;
-
-#define PATCH_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 __device__ __forceinline__ u64 patch_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -306,35 +305,27 @@ __global__ __launch_bounds__(PBLOCK) void k_patch_offsets(int64_t n, int64_t n_r
 int launch_patch_frame(hipStream_t st, int64_t n, const double *angle, double *frame)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_patch_frame, dim3((unsigned)((n + PBLOCK - 1) / PBLOCK)), dim3(PBLOCK), 0, st, n, angle, frame);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_patch_frame, blocks_for(n, PBLOCK), PBLOCK, n, angle, frame);
 }
 
 int launch_patch_extent(hipStream_t st, int64_t n, int64_t n_blocks, const PatchFields &f, const PatchRule &rule, const int32_t *labels,
                         PatchRecord *records)
 {
     if (n <= 0 || n_blocks <= 0) return 0;
-    hipLaunchKernelGGL(k_patch_extent, dim3((unsigned)n_blocks), dim3(PBLOCK), 0, st, n, f, rule, labels, records);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_patch_extent, (unsigned)n_blocks, PBLOCK, n, f, rule, labels, records);
 }
 
 int launch_patch_layout(hipStream_t st, int64_t n_regions, const PatchRule &rule, PatchRecord *records, int64_t *line_first, int64_t *word_first,
                         int64_t *err)
 {
-    hipLaunchKernelGGL(k_patch_layout, dim3(1), dim3(PBLOCK), 0, st, n_regions, rule, records, line_first, word_first, err);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_patch_layout, 1, PBLOCK, n_regions, rule, records, line_first, word_first, err);
 }
 
 int launch_patch_mark(hipStream_t st, int64_t n, int64_t n_blocks, const PatchFields &f, const PatchRule &rule, const int32_t *labels,
                       const PatchRecord *records, int64_t n_words, unsigned long long *bitmap)
 {
     if (n <= 0 || n_blocks <= 0 || n_words <= 0) return 0;
-    hipLaunchKernelGGL(k_patch_mark, dim3((unsigned)n_blocks), dim3(PBLOCK), 0, st, n, f, rule, labels, records, n_words, bitmap);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_patch_mark, (unsigned)n_blocks, PBLOCK, n, f, rule, labels, records, n_words, bitmap);
 }
 
 int launch_patch_runs(hipStream_t st, int fill, int64_t n, int64_t n_regions, int64_t n_lines, int64_t n_words, const PatchFields &f,
@@ -344,24 +335,16 @@ int launch_patch_runs(hipStream_t st, int fill, int64_t n, int64_t n_regions, in
     if (n <= 0 || n_regions <= 0 || n_lines <= 0) return 0;
     const int64_t need = (n_lines + PWAVES - 1) / PWAVES;
     const int64_t blocks = need < (int64_t)max_blocks ? need : (int64_t)max_blocks;
-    const dim3 grid((unsigned)(blocks > 0 ? blocks : 1));
-    if (fill) hipLaunchKernelGGL(k_patch_runs<true>, grid, dim3(PBLOCK), 0, st, n, n_regions, n_lines, n_words, f, rule, records, bitmap, line_counts,
-                                 line_offsets, out);
-    else hipLaunchKernelGGL(k_patch_runs<false>, grid, dim3(PBLOCK), 0, st, n, n_regions, n_lines, n_words, f, rule, records, bitmap, line_counts,
-                            line_offsets, out);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, fill ? k_patch_runs<true> : k_patch_runs<false>, (unsigned)(blocks > 0 ? blocks : 1), PBLOCK, n, n_regions, n_lines, n_words, f,
+                  rule, records, bitmap, line_counts, line_offsets, out);
 }
 
 int launch_patch_offsets(hipStream_t st, int64_t n, int64_t n_regions, int64_t n_lines, const PatchFields &f, const PatchRecord *records,
                          const int64_t *line_counts, int64_t *line_offsets, int64_t *err, int64_t *swath_offsets)
 {
-    hipLaunchKernelGGL((k_path_counts<PBLOCK, PatchLineCount>), dim3(1), dim3(PBLOCK), 0, st, n_lines, PatchLineCount{ line_counts }, line_offsets, err);
-    PATCH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_patch_offsets, dim3((unsigned)((n + 1 + PBLOCK - 1) / PBLOCK)), dim3(PBLOCK), 0, st, n, n_regions, n_lines, f.region_first,
-                       records, line_offsets, swath_offsets);
-    PATCH_LAUNCH_CHECK();
-    return 0;
+    if (int e = launch_path_counts<PBLOCK>(st, n_lines, PatchLineCount{ line_counts }, line_offsets, err)) return e;
+    return launch(st, k_patch_offsets, blocks_for(n + 1, PBLOCK), PBLOCK, n, n_regions, n_lines, f.region_first, records, line_offsets,
+                  swath_offsets);
 }
 
 }  // namespace fcpp

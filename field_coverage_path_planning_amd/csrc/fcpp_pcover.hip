@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_pcover.h"
 #include "fcpp_pcoverfn.h"
 #include "fcpp_samplefn.h"
@@ -34,8 +35,6 @@ namespace fcpp {
 static constexpr int PBLOCK = 256;
 static constexpr int PT = PCOVER_TILE;
 static constexpr int PQ = PT * PT / PBLOCK;        // cells per thread
-
-#define PCOVER_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 __global__ __launch_bounds__(PBLOCK) void k_pcover_sizes(int64_t n, const int64_t *__restrict__ roff, const int64_t *__restrict__ voff,
                                                          const double *__restrict__ x, const double *__restrict__ y, double W, double res,
@@ -281,21 +280,16 @@ int launch_pcover_sizes(hipStream_t st, int64_t n, const int64_t *ring_offsets, 
 {
     if (n <= 0) return 0;
     const int per = PBLOCK / 64;
-    hipLaunchKernelGGL(k_pcover_sizes, dim3((unsigned)((n + per - 1) / per)), dim3(PBLOCK), 0, st, n, ring_offsets, vert_offsets, x, y, W, res, dims,
-                       status);
-    PCOVER_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_pcover_sizes, blocks_for(n, per), PBLOCK, n, ring_offsets, vert_offsets, x, y, W, res, dims, status);
 }
 
 int launch_pcover_offsets(hipStream_t st, int64_t n, const PcoverDims *dims, int64_t *cell_first, int64_t *tile_first, int64_t *err)
 {
     if (cell_first) {
-        hipLaunchKernelGGL((k_path_counts<PBLOCK, PcoverCellCount>), dim3(1), dim3(PBLOCK), 0, st, n, PcoverCellCount{ dims }, cell_first, err);
-        PCOVER_LAUNCH_CHECK();
+        if (int e = launch_path_counts<PBLOCK>(st, n, PcoverCellCount{ dims }, cell_first, err)) return e;
     }
     if (tile_first) {
-        hipLaunchKernelGGL((k_path_counts<PBLOCK, PcoverTileCount>), dim3(1), dim3(PBLOCK), 0, st, n, PcoverTileCount{ dims }, tile_first, err);
-        PCOVER_LAUNCH_CHECK();
+        if (int e = launch_path_counts<PBLOCK>(st, n, PcoverTileCount{ dims }, tile_first, err)) return e;
     }
     return 0;
 }
@@ -303,18 +297,14 @@ int launch_pcover_offsets(hipStream_t st, int64_t n, const PcoverDims *dims, int
 int launch_pcover_boxes(hipStream_t st, int64_t n_chunks, const PcoverChunk *chunks, const PcoverPaths &paths, PcoverBox *boxes)
 {
     if (n_chunks <= 0) return 0;
-    hipLaunchKernelGGL(k_pcover_boxes, dim3((unsigned)n_chunks), dim3(PBLOCK), 0, st, n_chunks, chunks, paths, boxes);
-    PCOVER_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_pcover_boxes, (unsigned)n_chunks, PBLOCK, n_chunks, chunks, paths, boxes);
 }
 
 int launch_pcover_tiles(hipStream_t st, int64_t n, int64_t n_tiles, const PcoverFields &f, double W, double res, int caps, const PcoverChunk *chunks,
                         const PcoverBox *boxes, const PcoverPaths &paths, uint8_t *grid, unsigned long long *counts)
 {
     if (n <= 0 || n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_pcover_tiles, dim3((unsigned)n_tiles), dim3(PBLOCK), 0, st, n, f, W, res, caps, chunks, boxes, paths, grid, counts);
-    PCOVER_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_pcover_tiles, (unsigned)n_tiles, PBLOCK, n, f, W, res, caps, chunks, boxes, paths, grid, counts);
 }
 
 }  // namespace fcpp

@@ -32,6 +32,7 @@
 #include "fcpp_regions.h"
 #include "fcpp_regionfn.h"
 #include "fcpp_samplefn.h"
+#include "fcpp_launch.h"
 
 namespace fcpp {
 
@@ -40,8 +41,6 @@ static constexpr int RT = REGION_TILE;
 static constexpr int RQ = RT * RT / RBLOCK;                     // cells per thread of a tile
 static constexpr int RWAVE_CELLS = REGION_BLOCK_CELLS / (RBLOCK / 64);     // consecutive cells per wavefront of a numbering block
 static constexpr int RROUNDS = RWAVE_CELLS / 64;
-
-#define REGION_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // a parent word, read or written while other lanes, wavefronts or workgroups do the same: relaxed atomics of the scope that shares it
 template <int SCOPE>
@@ -350,9 +349,7 @@ int launch_region_tiles(hipStream_t st, int64_t n, int64_t n_tiles, const Region
                         int connectivity, int32_t *labels)
 {
     if (n <= 0 || n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_region_tiles, dim3((unsigned)n_tiles), dim3(RBLOCK), 0, st, n, f, grid, mask, value, connectivity, labels);
-    REGION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_region_tiles, (unsigned)n_tiles, RBLOCK, n, f, grid, mask, value, connectivity, labels);
 }
 
 int launch_region_seams(hipStream_t st, int64_t n, int64_t n_tiles, const RegionFields &f, int connectivity, int32_t *labels, int max_blocks)
@@ -360,29 +357,21 @@ int launch_region_seams(hipStream_t st, int64_t n, int64_t n_tiles, const Region
     if (n <= 0 || n_tiles <= 0) return 0;
     const int64_t need = (n_tiles * (2 * RT) + RBLOCK - 1) / RBLOCK;
     const int64_t blocks = need < (int64_t)max_blocks ? need : (int64_t)max_blocks;
-    hipLaunchKernelGGL(k_region_seams, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(RBLOCK), 0, st, n, n_tiles, f, connectivity, labels);
-    REGION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_region_seams, (unsigned)(blocks > 0 ? blocks : 1), RBLOCK, n, n_tiles, f, connectivity, labels);
 }
 
 int launch_region_count(hipStream_t st, int64_t n, int64_t n_blocks, const RegionFields &f, int flatten, int32_t *labels, int64_t *block_count)
 {
     if (n <= 0 || n_blocks <= 0) return 0;
-    if (flatten) hipLaunchKernelGGL(k_region_count<true>, dim3((unsigned)n_blocks), dim3(RBLOCK), 0, st, n, f, labels, block_count);
-    else hipLaunchKernelGGL(k_region_count<false>, dim3((unsigned)n_blocks), dim3(RBLOCK), 0, st, n, f, labels, block_count);
-    REGION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, flatten ? k_region_count<true> : k_region_count<false>, (unsigned)n_blocks, RBLOCK, n, f, labels, block_count);
 }
 
 int launch_region_offsets(hipStream_t st, int64_t n, int64_t n_blocks, const RegionFields &f, const int64_t *block_count, int64_t *block_prefix,
                           int64_t *err, int64_t *region_offsets)
 {
-    hipLaunchKernelGGL((k_path_counts<RBLOCK, RegionBlockCount>), dim3(1), dim3(RBLOCK), 0, st, n_blocks, RegionBlockCount{ block_count }, block_prefix, err);
-    REGION_LAUNCH_CHECK();
+    if (int e = launch_path_counts<RBLOCK>(st, n_blocks, RegionBlockCount{ block_count }, block_prefix, err)) return e;
     if (region_offsets) {
-        hipLaunchKernelGGL(k_region_offsets, dim3((unsigned)((n + 1 + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, st, n, f.block_first, block_prefix,
-                           region_offsets);
-        REGION_LAUNCH_CHECK();
+        if (int e = launch(st, k_region_offsets, blocks_for(n + 1, RBLOCK), RBLOCK, n, f.block_first, block_prefix, region_offsets)) return e;
     }
     return 0;
 }
@@ -391,18 +380,14 @@ int launch_region_first(hipStream_t st, int64_t n, int64_t n_blocks, const Regio
                         const int64_t *region_offsets, RegionRecord *records)
 {
     if (n <= 0 || n_blocks <= 0) return 0;
-    hipLaunchKernelGGL(k_region_first, dim3((unsigned)n_blocks), dim3(RBLOCK), 0, st, n, f, labels, block_prefix, region_offsets, records);
-    REGION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_region_first, (unsigned)n_blocks, RBLOCK, n, f, labels, block_prefix, region_offsets, records);
 }
 
 int launch_region_fill(hipStream_t st, int64_t n, int64_t n_blocks, const RegionFields &f, int32_t *labels, const int64_t *region_offsets,
                        RegionRecord *records)
 {
     if (n <= 0 || n_blocks <= 0) return 0;
-    hipLaunchKernelGGL(k_region_fill, dim3((unsigned)n_blocks), dim3(RBLOCK), 0, st, n, f, labels, region_offsets, records);
-    REGION_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_region_fill, (unsigned)n_blocks, RBLOCK, n, f, labels, region_offsets, records);
 }
 
 }  // namespace fcpp

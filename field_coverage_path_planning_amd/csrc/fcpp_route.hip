@@ -21,6 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_route.h"
 #include "fcpp_routefn.h"
 
@@ -29,8 +30,6 @@ namespace fcpp {
 static constexpr int RBLOCK = 256;            // k_route_transit, k_route_solve
 static constexpr int RWAVES = RBLOCK / 64;
 static constexpr int PBLOCK = 64;             // k_route_pick
-
-#define ROUTE_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 template <int MODE>
 __global__ __launch_bounds__(RBLOCK) void k_route_transit(int64_t n, const int64_t *__restrict__ soff, const double *__restrict__ ax,
@@ -190,11 +189,9 @@ int launch_route_transit(hipStream_t st, int64_t n, const int64_t *soff, const d
                          const double *angle, double R, int mode, const int64_t *toff, int64_t t_total, double *T)
 {
     if (n <= 0 || t_total <= 0) return 0;
-    const dim3 grid((unsigned)((t_total + RBLOCK - 1) / RBLOCK));
-    if (mode == 0) hipLaunchKernelGGL(k_route_transit<0>, grid, dim3(RBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, T);
-    else hipLaunchKernelGGL(k_route_transit<1>, grid, dim3(RBLOCK), 0, st, n, soff, ax, ay, bx, by, angle, R, toff, T);
-    ROUTE_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_route_transit<M()>, blocks_for(t_total, RBLOCK), RBLOCK, n, soff, ax, ay, bx, by, angle, R, toff, T);
+    });
 }
 
 int launch_route_solve(hipStream_t st, int64_t n, int S, const int64_t *soff, int64_t n_total, const int64_t *toff, const double *T,
@@ -202,10 +199,7 @@ int launch_route_solve(hipStream_t st, int64_t n, int S, const int64_t *soff, in
                        double *stored)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_route_solve, dim3((unsigned)(n * S)), dim3(RBLOCK), 0, st, S, soff, n_total, toff, T, E, X, min_gain, max_sweeps, tours,
-                       costs, applied, stored);
-    ROUTE_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_route_solve, (unsigned)(n * S), RBLOCK, S, soff, n_total, toff, T, E, X, min_gain, max_sweeps, tours, costs, applied, stored);
 }
 
 int launch_route_pick(hipStream_t st, int64_t n, int S, const int64_t *soff, int64_t n_total, const int32_t *tours, const double *costs,
@@ -213,10 +207,7 @@ int launch_route_pick(hipStream_t st, int64_t n, int S, const int64_t *soff, int
                       int32_t *status)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_route_pick, dim3((unsigned)n), dim3(PBLOCK), 0, st, S, soff, n_total, tours, costs, applied, stored, route, cost, winner,
-                       sweeps, status);
-    ROUTE_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_route_pick, (unsigned)n, PBLOCK, S, soff, n_total, tours, costs, applied, stored, route, cost, winner, sweeps, status);
 }
 
 }  // namespace fcpp

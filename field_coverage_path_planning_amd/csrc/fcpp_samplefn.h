@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "fcpp_connfn.h"
+#include "fcpp_launch.h"
 
 namespace fcpp {
 
@@ -61,6 +62,19 @@ template <int BLOCK, class CountOf>
 __global__ __launch_bounds__(BLOCK) void k_path_counts(int64_t n, CountOf count_of, int64_t *__restrict__ out_offsets, int64_t *__restrict__ err)
 {
     sample_scan<BLOCK>(n, count_of, out_offsets, err);
+}
+
+// the launches of the two: one workgroup of BLOCK lanes, whatever n
+template <int BLOCK, class TotalOf>
+inline int launch_sample_counts(hipStream_t st, int64_t n, TotalOf total_of, double step, int with_end, int nan_one, int64_t *out_offsets, int64_t *err)
+{
+    return launch(st, k_sample_counts<BLOCK, TotalOf>, 1, BLOCK, n, total_of, step, with_end, nan_one, out_offsets, err);
+}
+
+template <int BLOCK, class CountOf>
+inline int launch_path_counts(hipStream_t st, int64_t n, CountOf count_of, int64_t *out_offsets, int64_t *err)
+{
+    return launch(st, k_path_counts<BLOCK, CountOf>, 1, BLOCK, n, count_of, out_offsets, err);
 }
 
 // the last index i of 0 .. n - 1 with key(i) <= q, for a non-decreasing key with key(0) <= q: the path of a sample, the group of a slot

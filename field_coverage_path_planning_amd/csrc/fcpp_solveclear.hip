@@ -32,6 +32,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_listfn.h"
 #include "fcpp_samplefn.h"
 #include "fcpp_solveclear.h"
@@ -41,8 +42,6 @@
 namespace fcpp {
 
 static constexpr int SBLOCK = SOLVECLEAR_BLOCK;
-
-#define SOLVECLEAR_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 template <int NSEG>
 __device__ __forceinline__ void solve_clear_store(const SolveClearIo &io, int64_t i, int word, const double *seg, double len, int rank, int crossings)
@@ -225,22 +224,18 @@ int launch_solve_clear_pairs(hipStream_t st, int mode, int64_t n, const SolveCle
                              unsigned long long *count)
 {
     if (n <= 0) return 0;
-    const dim3 grid((unsigned)((n + SBLOCK - 1) / SBLOCK));
-    if (mode == 0) hipLaunchKernelGGL(k_solve_clear_pairs<0>, grid, dim3(SBLOCK), 0, st, n, io, R, F, list, count);
-    else hipLaunchKernelGGL(k_solve_clear_pairs<1>, grid, dim3(SBLOCK), 0, st, n, io, R, F, list, count);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_solve_clear_pairs<M()>, blocks_for(n, SBLOCK), SBLOCK, n, io, R, F, list, count);
+    });
 }
 
 int launch_solve_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const SolveClearIo &io, double R, const ClearFields &F)
 {
     if (count <= 0) return 0;
     const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
-    const dim3 grid((unsigned)((count + per - 1) / per));
-    if (mode == 0) hipLaunchKernelGGL(k_solve_clear_words<0>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
-    else hipLaunchKernelGGL(k_solve_clear_words<1>, grid, dim3(SBLOCK), 0, st, count, list, io, R, F);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_solve_clear_words<M()>, blocks_for(count, per), SBLOCK, count, list, io, R, F);
+    });
 }
 
 int launch_route_priced_words(hipStream_t st, int mode, int64_t count, const int64_t *list, int64_t n, const int64_t *soff, const double *ax,
@@ -249,11 +244,10 @@ int launch_route_priced_words(hipStream_t st, int mode, int64_t count, const int
 {
     if (count <= 0 || n <= 0) return 0;
     const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
-    const dim3 grid((unsigned)((count + per - 1) / per));
-    if (mode == 0) hipLaunchKernelGGL(k_route_priced_words<0>, grid, dim3(SBLOCK), 0, st, count, list, n, soff, ax, ay, bx, by, angle, R, toff, t_total, F, T, K);
-    else hipLaunchKernelGGL(k_route_priced_words<1>, grid, dim3(SBLOCK), 0, st, count, list, n, soff, ax, ay, bx, by, angle, R, toff, t_total, F, T, K);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_route_priced_words<M()>, blocks_for(count, per), SBLOCK, count, list, n, soff, ax, ay, bx, by, angle, R, toff, t_total, F,
+                      T, K);
+    });
 }
 
 int launch_fpath_clear_slots(hipStream_t st, int mode, int64_t n, int64_t n_conn, const int64_t *soff, double R, const FpathLeg *legs,
@@ -261,11 +255,10 @@ int launch_fpath_clear_slots(hipStream_t st, int mode, int64_t n, int64_t n_conn
                              unsigned long long *count)
 {
     if (n <= 0 || n_conn <= 0) return 0;
-    const dim3 grid((unsigned)((n_conn + SBLOCK - 1) / SBLOCK));
-    if (mode == 0) hipLaunchKernelGGL(k_fpath_clear_slots<0>, grid, dim3(SBLOCK), 0, st, n, n_conn, soff, R, legs, status, F, rank, crossings, list, count);
-    else hipLaunchKernelGGL(k_fpath_clear_slots<1>, grid, dim3(SBLOCK), 0, st, n, n_conn, soff, R, legs, status, F, rank, crossings, list, count);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_fpath_clear_slots<M()>, blocks_for(n_conn, SBLOCK), SBLOCK, n, n_conn, soff, R, legs, status, F, rank, crossings, list,
+                      count);
+    });
 }
 
 int launch_fpath_clear_words(hipStream_t st, int mode, int64_t count, const int64_t *list, const FpathIn &in, const ClearFields &F, FpathLeg *legs,
@@ -273,21 +266,17 @@ int launch_fpath_clear_words(hipStream_t st, int mode, int64_t count, const int6
 {
     if (count <= 0) return 0;
     const int64_t per = SBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
-    const dim3 grid((unsigned)((count + per - 1) / per));
-    if (mode == 0) hipLaunchKernelGGL(k_fpath_clear_words<0>, grid, dim3(SBLOCK), 0, st, count, list, in, F, legs, cnt, rank, crossings);
-    else hipLaunchKernelGGL(k_fpath_clear_words<1>, grid, dim3(SBLOCK), 0, st, count, list, in, F, legs, cnt, rank, crossings);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_fpath_clear_words<M()>, blocks_for(count, per), SBLOCK, count, list, in, F, legs, cnt, rank, crossings);
+    });
 }
 
 int launch_fpath_clear_report(hipStream_t st, int64_t n, int64_t n_slots, const int64_t *soff, const FpathLeg *legs, const int32_t *rank,
                               int32_t *leg_word, double *leg_seg, double *leg_total, int32_t *blocked, int32_t *reshaped)
 {
     if (n <= 0 || !(leg_word || leg_seg || leg_total || blocked || reshaped)) return 0;
-    const dim3 grid((unsigned)((n_slots + n + SBLOCK - 1) / SBLOCK));
-    hipLaunchKernelGGL(k_fpath_clear_report, grid, dim3(SBLOCK), 0, st, n, n_slots, soff, legs, rank, leg_word, leg_seg, leg_total, blocked, reshaped);
-    SOLVECLEAR_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_fpath_clear_report, blocks_for(n_slots + n, SBLOCK), SBLOCK, n, n_slots, soff, legs, rank, leg_word, leg_seg, leg_total,
+                  blocked, reshaped);
 }
 
 }  // namespace fcpp

@@ -19,6 +19,7 @@
 #include "fcpp_sparse2_fn.h"
 #include "fcpp_quiet_fn.h"
 #include "fcpp_devplan.h"
+#include "fcpp_launch.h"
 
 namespace fcpp {
 
@@ -282,9 +283,7 @@ __global__ void k_work_totals(int64_t n_work, const DevFieldWork *__restrict__ w
 int launch_work_totals(hipStream_t st, int64_t n_work, const DevFieldWork *work, const int64_t *stat_run, const TilePartial *partial, TilePartial *totals)
 {
     if (n_work <= 0) return 0;
-    hipLaunchKernelGGL(k_work_totals, dim3((unsigned)((n_work + 255) / 256)), dim3(256), 0, st, n_work, work, stat_run, partial, totals);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch(st, k_work_totals, blocks_for(n_work, 256), 256, n_work, work, stat_run, partial, totals);
 }
 
 int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack *packs, const DevConst &cst, const DevObstacles &obs, double *x,
@@ -292,16 +291,13 @@ int launch_plan_sparse_fields(hipStream_t st, int64_t n_work, const DevFieldPack
                               fcpp_field_stats *stats, bool spans)
 {
     if (n_work <= 0) return 0;
-#define FCPP_FW(K, W, OB, SP) FCPP_LAUNCH((K<W, OB, SP>), dim3((unsigned)n_work), dim3(64 * W), 0, st, packs, cst, x, y, kappa, v, fs, obs, partial, totals, stats)
     if (waves != 4) return (int)hipErrorInvalidValue;       // (instances for 5, 6, 8 wavefronts: measured slower than the open list, fcpp_internal.h)
     const bool has_obs = obs.offsets != nullptr;
-    if (has_obs && spans) FCPP_FW(k_plan_sparse_fields, 4, true, true);
-    else if (has_obs) FCPP_FW(k_plan_sparse_fields, 4, true, false);
-    else if (spans) FCPP_FW(k_plan_sparse_fields, 4, false, true);
-    else FCPP_FW(k_plan_sparse_fields, 4, false, false);
-#undef FCPP_FW
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    auto fw = [&](auto kernel) { return launch_stage(st, kernel, (unsigned)n_work, 64 * 4, packs, cst, x, y, kappa, v, fs, obs, partial, totals, stats); };
+    if (has_obs && spans) return fw(k_plan_sparse_fields<4, true, true>);
+    if (has_obs) return fw(k_plan_sparse_fields<4, true, false>);
+    if (spans) return fw(k_plan_sparse_fields<4, false, true>);
+    return fw(k_plan_sparse_fields<4, false, false>);
 }
 
 int launch_plan_sparse_direct(hipStream_t st, int64_t n, int64_t gen, const DevPlanScratch &s, const DevConst &cst, double *x, double *y, double *kappa,
@@ -311,10 +307,8 @@ int launch_plan_sparse_direct(hipStream_t st, int64_t n, int64_t gen, const DevP
     if (n > OFF_FIELDS_MAX || !s.direct_packs || !s.agg || !s.agg_next || !totals_host) return (int)hipErrorInvalidValue;
     DevConst dc = cst;
     dc.field_junc = s.direct_junc;       // (the batch's own table is written by the fill pass, which a direct setup has not run)
-    FCPP_LAUNCH((k_plan_sparse_fields_direct<4>), dim3((unsigned)n + 1u), dim3(64 * 4), 0, st, s.direct_packs, dc, x, y, kappa, v, fs, s.direct_totals, stats, n, gen,
-                s.totals, s.agg, s.agg_next, totals_host);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_stage(st, k_plan_sparse_fields_direct<4>, (unsigned)n + 1u, 64 * 4, s.direct_packs, dc, x, y, kappa, v, fs, s.direct_totals, stats,
+                        n, gen, s.totals, s.agg, s.agg_next, totals_host);
 }
 
 int launch_plan_sparse(hipStream_t st, int64_t n_wtiles, const DevWaveTile *wtiles, const DevField *fields, const DevPrim *prims,
@@ -324,10 +318,9 @@ int launch_plan_sparse(hipStream_t st, int64_t n_wtiles, const DevWaveTile *wtil
     if (n_wtiles <= 0) return 0;
     // (the grid rounded up to a multiple of eight for the XCD-aware order of k_plan_sparse)
     auto grid8 = [&](int64_t per) { const int64_t g = (n_wtiles + per - 1) / per; return dim3((unsigned)((g + 7) / 8 * 8)); };
-    if (n_wtiles >= 65536) FCPP_LAUNCH((k_plan_sparse<2, 2>), grid8(2), dim3(128), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
-    else FCPP_LAUNCH((k_plan_sparse<4, 2>), grid8(4), dim3(256), 0, st, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (n_wtiles >= 65536)
+        return launch_stage(st, k_plan_sparse<2, 2>, grid8(2), 128, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
+    return launch_stage(st, k_plan_sparse<4, 2>, grid8(4), 256, wtiles, ids, n_wtiles, fields, prims, cst, obs, x, y, kappa, v, fs, partial, 1);
 }
 
 }  // namespace fcpp

@@ -25,14 +25,13 @@
 #include <stdint.h>
 
 #include "fcpp_devfn.h"
+#include "fcpp_launch.h"
 #include "fcpp_speed.h"
 
 namespace fcpp {
 
 static constexpr int SBLOCK = 256, SNWAVE = SBLOCK / 64;
 static_assert(TILE_POINTS == 2 * SBLOCK, "two consecutive samples per thread");
-
-#define SPEED_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // one thread's two consecutive samples j0 = 2 * tid, j0 + 1 of a tile: their caps and the weights of their maps both ways.  A slot
 // beyond the tile is the identity map (c = +inf, w = 0).
@@ -186,18 +185,14 @@ int launch_speed_tiles(hipStream_t st, int64_t n_tiles, const DevTile *tiles, co
                        void *agg_f, void *agg_b, int32_t *status)
 {
     if (n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_speed_tiles, dim3((unsigned)n_tiles), dim3(SBLOCK), 0, st, tiles, paths, rule, in, (Agg *)agg_f, (Agg *)agg_b, status);
-    SPEED_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_speed_tiles, (unsigned)n_tiles, SBLOCK, tiles, paths, rule, in, (Agg *)agg_f, (Agg *)agg_b, status);
 }
 
 int launch_speed_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths, const SpeedRule &rule, const SpeedIn &in,
                        const double *carry_f, const double *carry_b, const int32_t *status, double *v, double *cap)
 {
     if (n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_speed_apply, dim3((unsigned)n_tiles), dim3(SBLOCK), 0, st, tiles, paths, rule, in, carry_f, carry_b, status, v, cap);
-    SPEED_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_speed_apply, (unsigned)n_tiles, SBLOCK, tiles, paths, rule, in, carry_f, carry_b, status, v, cap);
 }
 
 }  // namespace fcpp

@@ -18,6 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_samplefn.h"
 #include "fcpp_swath.h"
 #include "fcpp_swathfn.h"
@@ -27,8 +28,6 @@ namespace fcpp {
 static constexpr int SWAVE = 64;            // the workgroup: one wavefront
 static constexpr int SCHUNK = SWAVE - 1;    // edges per vertex chunk
 static constexpr int SBLOCK = 256;          // the offsets scan
-
-#define SWATH_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // lane `from` (uniform) of v, in every lane
 __device__ __forceinline__ double swath_bcast(double v, int from)
@@ -186,17 +185,13 @@ int launch_swath_count(hipStream_t st, int64_t n, int64_t A, int per_field, cons
                        int32_t *n_lines, double *length, int32_t *status)
 {
     if (n <= 0 || A <= 0) return 0;
-    hipLaunchKernelGGL(k_swath_count, dim3((unsigned)(n * A)), dim3(SWAVE), 0, st, A, per_field, ring_offsets, vert_offsets, x, y, angles, W, first,
-                       min_length, n_swaths, n_lines, length, status);
-    SWATH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_swath_count, (unsigned)(n * A), SWAVE, A, per_field, ring_offsets, vert_offsets, x, y, angles, W, first, min_length, n_swaths,
+                  n_lines, length, status);
 }
 
 int launch_swath_offsets(hipStream_t st, int64_t n, const int32_t *n_swaths, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL((k_path_counts<SBLOCK, SwathCount>), dim3(1), dim3(SBLOCK), 0, st, n, SwathCount{ n_swaths }, out_offsets, err);
-    SWATH_LAUNCH_CHECK();
-    return 0;
+    return launch_path_counts<SBLOCK>(st, n, SwathCount{ n_swaths }, out_offsets, err);
 }
 
 int launch_swath_fill(hipStream_t st, int64_t n, const int64_t *ring_offsets, const int64_t *vert_offsets, const double *x, const double *y,
@@ -204,10 +199,8 @@ int launch_swath_fill(hipStream_t st, int64_t n, const int64_t *ring_offsets, co
                       double *by, int32_t *line, double *length)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_swath_fill, dim3((unsigned)n), dim3(SWAVE), 0, st, ring_offsets, vert_offsets, x, y, angles, W, first, min_length, offsets,
-                       ax, ay, bx, by, line, length);
-    SWATH_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_swath_fill, (unsigned)n, SWAVE, ring_offsets, vert_offsets, x, y, angles, W, first, min_length, offsets, ax, ay, bx, by, line,
+                  length);
 }
 
 }  // namespace fcpp

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_samplefn.h"
 #include "fcpp_traj.h"
 
@@ -31,8 +32,6 @@ namespace fcpp {
 static constexpr int TBLOCK = 256, TNWAVE = TBLOCK / 64;
 static_assert(TILE_POINTS == 2 * TBLOCK, "two consecutive points per thread");
 static constexpr double TRAJ_PI = 3.14159265358979323846;
-
-#define TRAJ_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // one thread's two consecutive points j0 = 2 * tid, j0 + 1 of a tile, after the tile-local scan
 struct TrajLane {
@@ -317,26 +316,20 @@ int launch_traj_tiles(hipStream_t st, int64_t n_tiles, const DevTile *tiles, con
                       const double *v, TrajAgg *agg)
 {
     if (n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_traj_tiles, dim3((unsigned)n_tiles), dim3(TBLOCK), 0, st, tiles, paths, x, y, v, agg);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_traj_tiles, (unsigned)n_tiles, TBLOCK, tiles, paths, x, y, v, agg);
 }
 
 int launch_traj_blocks(hipStream_t st, int64_t n_blocks, const TrajBlock *blocks, const TrajAgg *agg, TrajAgg *pre, TrajAgg *blk)
 {
     if (n_blocks <= 0) return 0;
-    hipLaunchKernelGGL(k_traj_blocks, dim3((unsigned)n_blocks), dim3(64), 0, st, blocks, agg, pre, blk);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_traj_blocks, (unsigned)n_blocks, 64, blocks, agg, pre, blk);
 }
 
 int launch_traj_paths(hipStream_t st, int64_t n_paths, const int64_t *block_first, const TrajAgg *blk, TrajAgg *cin, int64_t *path_first,
                       double *totals)
 {
     if (n_paths <= 0) return 0;
-    hipLaunchKernelGGL(k_traj_paths, dim3((unsigned)n_paths), dim3(64), 0, st, n_paths, block_first, blk, cin, path_first, totals);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_traj_paths, (unsigned)n_paths, 64, n_paths, block_first, blk, cin, path_first, totals);
 }
 
 int launch_traj_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, const DevPath *paths, const int64_t *tile_first,
@@ -344,17 +337,13 @@ int launch_traj_apply(hipStream_t st, int64_t n_tiles, const DevTile *tiles, con
                       const TrajAgg *cin, const int64_t *path_first, double *s, double *t, double *heading)
 {
     if (n_tiles <= 0) return 0;
-    hipLaunchKernelGGL(k_traj_apply, dim3((unsigned)n_tiles), dim3(TBLOCK), 0, st, tiles, paths, tile_first, block_first, x, y, v, fs, pre, cin,
-                       path_first, s, t, heading);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_traj_apply, (unsigned)n_tiles, TBLOCK, tiles, paths, tile_first, block_first, x, y, v, fs, pre, cin, path_first, s, t,
+                  heading);
 }
 
 int launch_traj_counts(hipStream_t st, int64_t n_paths, const double *totals, double dt, int include_end, int64_t *out_offsets, int64_t *err)
 {
-    hipLaunchKernelGGL((k_sample_counts<TBLOCK, TrajTime>), dim3(1), dim3(TBLOCK), 0, st, n_paths, TrajTime{ totals }, dt, include_end, 0, out_offsets, err);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch_sample_counts<TBLOCK>(st, n_paths, TrajTime{ totals }, dt, include_end, 0, out_offsets, err);
 }
 
 int launch_traj_sample(hipStream_t st, int64_t n_paths, const int64_t *offsets, const int64_t *out_offsets, int64_t total_samples, const double *x,
@@ -362,11 +351,8 @@ int launch_traj_sample(hipStream_t st, int64_t n_paths, const int64_t *offsets, 
                        int include_end, double *xs, double *ys, double *vs, double *ss, double *hs, uint32_t *fss, int64_t *src)
 {
     if (total_samples <= 0 || n_paths <= 0) return 0;
-    const int64_t nb = (total_samples + TBLOCK - 1) / TBLOCK;
-    hipLaunchKernelGGL(k_traj_sample, dim3((unsigned)nb), dim3(TBLOCK), 0, st, n_paths, offsets, out_offsets, total_samples, x, y, v, s, t, heading,
-                       fs, dt, include_end, xs, ys, vs, ss, hs, fss, src);
-    TRAJ_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_traj_sample, blocks_for(total_samples, TBLOCK), TBLOCK, n_paths, offsets, out_offsets, total_samples, x, y, v, s, t, heading, fs,
+                  dt, include_end, xs, ys, vs, ss, hs, fss, src);
 }
 
 }  // namespace fcpp

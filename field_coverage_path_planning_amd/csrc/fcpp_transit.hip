@@ -30,6 +30,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fcpp_launch.h"
 #include "fcpp_listfn.h"
 #include "fcpp_samplefn.h"
 #include "fcpp_solvegroupfn.h"
@@ -40,8 +41,6 @@ namespace fcpp {
 static constexpr int TBLOCK = TRANSIT_BLOCK;
 static constexpr int TWAVES = TBLOCK / 64;
 static_assert(TBLOCK == SOLVECLEAR_BLOCK, "solve_clear_group's groups are laid out for that workgroup");
-
-#define TRANSIT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 __global__ __launch_bounds__(TBLOCK) void k_transit_stations(TransitLoops L, TransitTemp T)
 {
@@ -245,25 +244,19 @@ __global__ __launch_bounds__(TBLOCK) void k_transit_fill(int64_t n, TransitRec r
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
-static unsigned transit_grid(int64_t lanes) { return (unsigned)((lanes + TBLOCK - 1) / TBLOCK); }
-
 int launch_transit_stations(hipStream_t st, const TransitLoops &L, const TransitTemp &T)
 {
     if (L.n_fields <= 0) return 0;
-    hipLaunchKernelGGL(k_transit_stations, dim3(transit_grid(L.n_fields * 64)), dim3(TBLOCK), 0, st, L, T);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_transit_stations, blocks_for(L.n_fields * 64, TBLOCK), TBLOCK, L, T);
 }
 
 int launch_transit_sides(hipStream_t st, int mode, int64_t n, int64_t per, const TransitIo &io, double R, const ClearFields &F, const TransitLoops &L,
                          const TransitTemp &T, int64_t *list, unsigned long long *count)
 {
     if (n <= 0 || per <= 0) return 0;
-    const dim3 grid(transit_grid(n * 2 * per));
-    if (mode == 0) hipLaunchKernelGGL(k_transit_sides<0>, grid, dim3(TBLOCK), 0, st, n, per, io, R, F, L, T, list, count);
-    else hipLaunchKernelGGL(k_transit_sides<1>, grid, dim3(TBLOCK), 0, st, n, per, io, R, F, L, T, list, count);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_transit_sides<M()>, blocks_for(n * 2 * per, TBLOCK), TBLOCK, n, per, io, R, F, L, T, list, count);
+    });
 }
 
 int launch_transit_words(hipStream_t st, int mode, int64_t count, const int64_t *list, int64_t n, int64_t per, const TransitIo &io, double R,
@@ -271,42 +264,32 @@ int launch_transit_words(hipStream_t st, int mode, int64_t count, const int64_t 
 {
     if (count <= 0) return 0;
     const int64_t group = TBLOCK / (mode == 0 ? SolveClearGroup<0>::G : SolveClearGroup<1>::G);
-    const dim3 grid((unsigned)((count + group - 1) / group));
-    if (mode == 0) hipLaunchKernelGGL(k_transit_words<0>, grid, dim3(TBLOCK), 0, st, count, list, n, per, io, R, F, L, T);
-    else hipLaunchKernelGGL(k_transit_words<1>, grid, dim3(TBLOCK), 0, st, count, list, n, per, io, R, F, L, T);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_transit_words<M()>, blocks_for(count, group), TBLOCK, count, list, n, per, io, R, F, L, T);
+    });
 }
 
 int launch_transit_pick(hipStream_t st, int64_t n, int64_t per, const TransitIo &io, const TransitLoops &L, const TransitTemp &T)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_transit_pick, dim3((unsigned)n), dim3(TBLOCK), 0, st, n, per, io, L, T);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return launch(st, k_transit_pick, (unsigned)n, TBLOCK, n, per, io, L, T);
 }
 
 int launch_transit_finish(hipStream_t st, int mode, int64_t n, const TransitIo &io, double R, const ClearFields &F, const TransitLoops &L,
                           const TransitTemp &T)
 {
     if (n <= 0) return 0;
-    if (mode == 0) hipLaunchKernelGGL(k_transit_finish<0>, dim3(transit_grid(n)), dim3(TBLOCK), 0, st, n, io, R, F, L, T);
-    else hipLaunchKernelGGL(k_transit_finish<1>, dim3(transit_grid(n)), dim3(TBLOCK), 0, st, n, io, R, F, L, T);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_transit_finish<M()>, blocks_for(n, TBLOCK), TBLOCK, n, io, R, F, L, T);
+    });
 }
 
 int launch_transit_counts(hipStream_t st, int mode, int64_t n, const TransitRec &rec, int64_t n_loops, const int64_t *loop_off, double spacing,
                           int64_t *out_offsets, int64_t *err)
 {
-    if (mode == 0)
-        hipLaunchKernelGGL((k_path_counts<TBLOCK, TransitCount<0>>), dim3(1), dim3(TBLOCK), 0, st, n, TransitCount<0>{ rec, n_loops, loop_off, spacing },
-                           out_offsets, err);
-    else
-        hipLaunchKernelGGL((k_path_counts<TBLOCK, TransitCount<1>>), dim3(1), dim3(TBLOCK), 0, st, n, TransitCount<1>{ rec, n_loops, loop_off, spacing },
-                           out_offsets, err);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch_path_counts<TBLOCK>(st, n, TransitCount<M()>{ rec, n_loops, loop_off, spacing }, out_offsets, err);
+    });
 }
 
 int launch_transit_fill(hipStream_t st, int mode, int64_t n, const TransitRec &rec, const TransitLoops &L, const double *fx, const double *fy,
@@ -314,15 +297,10 @@ int launch_transit_fill(hipStream_t st, int mode, int64_t n, const TransitRec &r
                         double *heading, double *kappa, int8_t *part, int8_t *gear)
 {
     if (n <= 0 || total_samples <= 0) return 0;
-    const dim3 grid(transit_grid(total_samples));
-    if (mode == 0)
-        hipLaunchKernelGGL(k_transit_fill<0>, grid, dim3(TBLOCK), 0, st, n, rec, L, fx, fy, fh, R, spacing, out_offsets, total_samples, x, y, heading, kappa,
-                           part, gear);
-    else
-        hipLaunchKernelGGL(k_transit_fill<1>, grid, dim3(TBLOCK), 0, st, n, rec, L, fx, fy, fh, R, spacing, out_offsets, total_samples, x, y, heading, kappa,
-                           part, gear);
-    TRANSIT_LAUNCH_CHECK();
-    return 0;
+    return by_mode(mode, [&](auto M) {
+        return launch(st, k_transit_fill<M()>, blocks_for(total_samples, TBLOCK), TBLOCK, n, rec, L, fx, fy, fh, R, spacing, out_offsets,
+                      total_samples, x, y, heading, kappa, part, gear);
+    });
 }
 
 }  // namespace fcpp
