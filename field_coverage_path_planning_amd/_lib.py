@@ -186,6 +186,9 @@ PROTOTYPES = [
     ('fcpp_inset_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double] + [_VP] * 6),
     ('fcpp_inset_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double, _VP, _VP, C.c_int64, C.c_int64]
      + [_VP] * 4),
+    ('fcpp_cells_counts', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double] + [_VP] * 8),
+    ('fcpp_cells_fill', C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, _VP, _VP, C.c_int64, C.c_int64]
+     + [_VP] * 6),
     ('fcpp_route_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
     ('fcpp_route_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_conn_clear', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
@@ -249,6 +252,8 @@ PROTOTYPES = [
      + [_VP] * 5 + [C.c_int64] + [_VP] * 6),
     ('fcpp_debug_inset', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_double] + [_VP] * 4
      + [C.c_int64, C.c_int64] + [_VP] * 4),
+    ('fcpp_debug_cells', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double] + [_VP] * 6
+     + [C.c_int64, C.c_int64] + [_VP] * 6),
     ('fcpp_debug_route_transit', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP]),
     ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
     ('fcpp_debug_conn_clear', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]

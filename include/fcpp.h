@@ -305,7 +305,7 @@ int fcpp_batch_point_split(const fcpp_batch *batch, int64_t *quiet_points, int64
 int fcpp_batch_reduce_classes(const fcpp_batch *batch, int64_t *classes_out);
 
 /* ---- standalone operators on caller-supplied paths (CSR offsets, n_paths+1, device) -------
- * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_*, fcpp_route_* and fcpp_field_path_*
+ * Buffers of fcpp_curvature, fcpp_speed_plan, fcpp_trajectory / _counts / _sample, fcpp_dubins_*, fcpp_rs_*, fcpp_swath_*, fcpp_inset_*, fcpp_cells_*, fcpp_route_* and fcpp_field_path_*
  * (tests/test_gpu_guarded.py enforces it for these entries): a device pointer needs only the natural alignment of its element type, an
  * output is written exactly over its stated extent -- every element of it, nothing beside it --, inputs are never written, and an output
  * must not overlap an input or another output except where an entry says so.  The same holds, enforced by
@@ -1149,6 +1149,61 @@ int fcpp_inset_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, i
                     const int64_t *pair_ring_offsets_dev, const int64_t *pair_vert_offsets_dev, int64_t total_rings, int64_t total_verts,
                     int64_t *out_vert_offsets_dev, double *out_x_dev, double *out_y_dev, int32_t *out_src_dev);
 
+/* ---- field cells: a polygon field split along a cut direction into cells that are ordinary fields ----------------------------------------
+ * Build-defined (the reference plans one quadrilateral at one angle).  Standalone like the swath and inset entries, whose field layout it
+ * shares: work area -> CELLS -> angle, swaths, route and path per cell.  Nothing here feeds fcpp_batch_plan.
+ * Input per field: its rings (simple, pairwise disjoint, closed implicitly, either orientation, EVEN-ODD interior; several outer rings are
+ * fine -- an inset can split a field), a cut angle phi (finite, |phi| <= 1e5), events (0 = reflex: a cut at every reflex vertex, the cells
+ * are convex; 1 = extrema: only where the boundary turns back across the cuts, the cells are monotone across the cuts) and min_area >= 0.
+ * THE RULE (csrc/fcpp_cellfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Frame: (s, c) = fc_sincos(phi); every vertex gets u = x c + y s, w = -x s + y c once.  Cuts are segments of constant w.
+ *   - Orientation: a ring's depth is the number of the field's other rings that contain its first vertex (the swath rule's half-open
+ *     crossing test).  Even depth is driven counter-clockwise, odd depth clockwise (shoelace sum in x, y about the ring's first vertex): the
+ *     interior is on the left of every oriented edge.  Vertices keep their field-local input index; oriented edge g leaves vertex g.
+ *   - Rays: with e1 = v - pred, e2 = succ - v in (u, w), v is reflex iff cross(e1, e2) < 0.  In mode extrema v must also be extremal: the
+ *     first vertices backwards and forwards whose w differs from w_v lie on the same side of it.  A +u ray leaves a qualifying v iff
+ *     w_pred > w_v or w_succ < w_v, a -u ray iff w_pred < w_v or w_succ > w_v: the direction lies strictly inside the interior cone.
+ *   - Ray end: over the edges (a, b) not incident to v with w_a != w_b: the edge meets the level at u_a if w_a = w_v, at u_b if w_b = w_v,
+ *     at u_a + (w_v - w_a) / (w_b - w_a) (u_b - u_a) if (w_a < w_v) != (w_b < w_v).  A ray runs inside the field, so only an edge with the
+ *     interior towards it counts: w_b > w_a for a +u ray, w_b < w_a for a -u ray.  The ray ends at the nearest such point strictly ahead;
+ *     ties go to a vertex hit, then to the lowest edge.  A hit at an edge end IS that vertex; otherwise a new node on the edge at (u, w_v).
+ *   - Cuts are undirected: what two facing vertices shoot at each other is kept once.  An input vertex keeps its input x, y bits; a new node
+ *     has x = u c - w s, y = u s + w c.  Rays are numbered 2 v + (0: +u, 1: -u); cuts and new nodes are numbered in ray order.
+ *   - Half-edges: every oriented edge is split at its new nodes, ordered along the edge by w, into boundary pieces, numbered by (edge,
+ *     position); then cut k gives half-edges B + 2 k (from its vertex) and B + 2 k + 1 (back).
+ *   - Successor: arriving at a node, leave by the outgoing half-edge met first when turning clockwise from the direction back along the
+ *     arriving one -- the sharpest left turn, never the arriving half-edge's twin -- by the signs of cross and dot products in (u, w); a
+ *     boundary piece has the direction of its whole edge, a cut (+-1, 0).
+ *   - Cells: from the lowest unused half-edge follow the successor until it returns.  A cell is a simple counter-clockwise ring (flat
+ *     vertices kept) of its half-edges' origins, starting at the lowest.  A field of h holes and k cuts has 1 + k - h cells.  src per vertex:
+ *     the field-local INPUT edge of the boundary piece leaving it, -1 where a cut leaves it; area: half the shoelace sum in x, y about the
+ *     cell's first vertex.  Cells with area <= min_area are not emitted: `dropped` counts them, `dropped_area` sums them in cell order.
+ * Status per field, int32: 0; FCPP_EINVAL -- no ring, a ring with fewer than 3 vertices, a vertex that is not finite (also in the frame), an
+ * edge of length 0; FCPP_EUNSUPPORTED -- more than FCPP_CELLS_MAX_EDGES edges, a ray that meets nothing, two cuts leaving a node the same
+ * way, or a walk that reaches a used half-edge other than its start (touching or crossing rings).  Such a field has no cells, no cuts and
+ * nothing dropped; the other fields of the batch are unaffected.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or input array, an angle that is not finite or beyond 1e5 in
+ * magnitude, events outside {0, 1}, a negative or non-finite min_area; FCPP_ESIZE -- negative sizes, offsets that do not start at 0, decrease,
+ * or do not end at the length of the array they index.  (The offsets and the angles are read back for these checks.)  Both entries
+ * synchronise.  Every table of a field lives in the workgroup's LDS: the entries allocate nothing per field. */
+#define FCPP_CELLS_MAX_EDGES 1024
+#define FCPP_CELLS_REFLEX 0
+#define FCPP_CELLS_EXTREMA 1
+/* Counting pass: angle_dev holds n cut angles.  Writes the CSR offsets fields -> cells and fields -> cell vertices (n + 1 int64 each; the
+ * host pointers: NULL or room for a copy), status, n_cuts, dropped (int32) and dropped_area (float64), n each.  Any output may be NULL. */
+int fcpp_cells_counts(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev,
+                      int64_t n_verts, const double *x_dev, const double *y_dev, const double *angle_dev, int events, double min_area,
+                      int64_t *cell_offsets_dev, int64_t *cell_offsets_host, int64_t *cell_vert_offsets_dev, int64_t *cell_vert_offsets_host,
+                      int32_t *status_dev, int32_t *n_cuts_dev, int32_t *dropped_dev, double *dropped_area_dev);
+/* fcpp_cells_fill writes the cells of the same fields, angles, events and min_area at those offsets: out_vert_offsets_dev (total_cells + 1
+ * int64: cells -> vertices), out_x_dev, out_y_dev (total_verts float64), out_src_dev (int32 per vertex), cell_field_dev (int32 per cell: its
+ * field) and area_dev (float64 per cell).  Any output may be NULL.  A field never writes outside its own ranges. */
+int fcpp_cells_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, int64_t n_rings, const int64_t *vert_offsets_dev, int64_t n_verts,
+                    const double *x_dev, const double *y_dev, const double *angle_dev, int events, double min_area,
+                    const int64_t *cell_offsets_dev, const int64_t *cell_vert_offsets_dev, int64_t total_cells, int64_t total_verts,
+                    int64_t *out_vert_offsets_dev, double *out_x_dev, double *out_y_dev, int32_t *out_src_dev, int32_t *cell_field_dev,
+                    double *area_dev);
+
 /* ---- headland paths: every ring of an inset as ONE sampled, closed, drivable path ------------------------------------------------------------
  * Build-defined.  The rings fcpp_inset_fill writes are bare polygons: straight offset pieces that meet in sharp convex corners, and chords
  * of arcs of radius d around reflex vertices.  This operator turns every ring of a batch (all fields, all passes) into a loop a vehicle of
@@ -1443,6 +1498,15 @@ int fcpp_debug_inset(int64_t n, const int64_t *ring_offsets, int64_t n_rings, co
                      const double *y, int64_t D, const double *dist, double arc_step, int64_t *pair_ring_offsets, int64_t *pair_vert_offsets,
                      int32_t *status, double *gap, int64_t ring_cap, int64_t vert_cap, int64_t *out_vert_offsets, double *out_x, double *out_y,
                      int32_t *out_src);
+/* The field cell rule (csrc/fcpp_cellfn.h) evaluated on the HOST, on host pointers, counts and fill in one call: what the device results are
+ * compared with bit for bit.  cell_offsets, cell_vert_offsets (n + 1), status, n_cuts, dropped, dropped_area (n): any may be NULL.  Cell k of
+ * all is written to out_vert_offsets, cell_field, area while k < cell_cap (and the closing offset when the total fits), vertex v to out_x,
+ * out_y, out_src while v < vert_cap: call once with caps of 0 for the sizes, then with them.  The call's errors as for fcpp_cells_counts.
+ * Fields are handed to the library's host threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_cells(int64_t n, const int64_t *ring_offsets, int64_t n_rings, const int64_t *vert_offsets, int64_t n_verts, const double *x,
+                     const double *y, const double *angle, int events, double min_area, int64_t *cell_offsets, int64_t *cell_vert_offsets,
+                     int32_t *status, int32_t *n_cuts, int32_t *dropped, double *dropped_area, int64_t cell_cap, int64_t vert_cap,
+                     int64_t *out_vert_offsets, double *out_x, double *out_y, int32_t *out_src, int32_t *cell_field, double *area);
 /* The swath router's rule (csrc/fcpp_routefn.h) evaluated on the HOST, on host pointers: fcpp_route_transit's blocks and fcpp_route_solve's
  * results, what the device results are compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets
  * are the host's).  Fields are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */

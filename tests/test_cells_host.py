@@ -1,0 +1,273 @@
+"""CPU-side tests of the field cells: the three entries exist (header, ctypes binding, libfcpp.so), argument errors need no device -- and
+the RULE, through fcpp_debug_cells (csrc/fcpp_cellfn.h on the host: the very expressions the kernels run).
+
+The checker is numpy written from the DEFINITION of a decomposition: the cells partition the field.  An even-odd point-in-polygon test
+written here decides, for 2000 seeded random points per case, in how many cells a point lies and whether it lies in the field; the shoelace
+formula gives the areas.  It shares no code with the library and does not restate the algorithm (rays, half-edges, walks).  Beside it stand
+the cell counts known by hand (tests/cell_cases.py: COUNTS), Euler's count 1 + cuts - holes, and what the two modes promise of a cell:
+convex (reflex), monotone across the cuts (extrema: fcpp_debug_swaths of the cell at its cut angle finds one swath on every line).
+
+Tolerances: 1e-9 m for a vertex on its input edge and 1e-9 m^2 for the cross product of a convex corner, the project's own (tests/
+test_inset_host.py); 1e-9 x the field's area for the sum of the cells' areas against the field's: a rounding bound of two shoelace sums
+over coordinates of up to 120 m, a thousand times what they differ by in fact (under 1e-12 m^2)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from field_coverage_path_planning_amd import _lib as L
+from tests import cell_cases as CC
+from tests.test_swaths_host import pack
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P_TOL = 1e-9
+N_POINTS = 2000
+ENTRIES = {'fcpp_cells_counts': 19, 'fcpp_cells_fill': 21, 'fcpp_debug_cells': 24}
+MODES = (CC.REFLEX, CC.EXTREMA)
+CASES = CC.named_cases()
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+# ---- the checker ------------------------------------------------------------------------------------------------------------------------
+def inside_even_odd(pts, rings):
+    """crossing number of the ray to +x over all rings: (len(pts)) int, 1 inside"""
+    a = np.concatenate(rings)
+    b = np.concatenate([np.roll(r, -1, axis=0) for r in rings])
+    px, py = pts[:, 0, None], pts[:, 1, None]
+    strad = (a[None, :, 1] <= py) != (b[None, :, 1] <= py)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        xc = a[None, :, 0] + (py - a[None, :, 1]) / (b[None, :, 1] - a[None, :, 1]) * (b[None, :, 0] - a[None, :, 0])
+    return ((strad & (xc > px)).sum(axis=1) % 2).astype(np.int64)
+
+
+def shoelace(ring):
+    x, y = ring[:, 0] - ring[0, 0], ring[:, 1] - ring[0, 1]
+    return 0.5 * np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y)
+
+
+def field_area(rings):
+    """even-odd area of disjoint simple rings: a ring counts by the parity of the rings around its first vertex"""
+    total = 0.0
+    for k, r in enumerate(rings):
+        others = [q for j, q in enumerate(rings) if j != k]
+        depth = sum(int(inside_even_odd(r[:1], [q])[0]) for q in others)
+        total += abs(shoelace(r)) * (-1.0 if depth % 2 else 1.0)
+    return total
+
+
+def holes_of(rings):
+    return sum(sum(int(inside_even_odd(r[:1], [q])[0]) for j, q in enumerate(rings) if j != k) % 2 for k, r in enumerate(rings))
+
+
+@pytest.fixture(scope='module')
+def lib():
+    return L.load()
+
+
+@pytest.fixture(scope='module')
+def cut():
+    """fcpp_debug_cells of the named cases in both modes, min_area 0: computed once and left unchanged"""
+    return {ev: CC.HostCells([f for _, f, _ in CASES], [a for _, _, a in CASES], ev) for ev in MODES}
+
+
+# ---- the entries exist ------------------------------------------------------------------------------------------------------------------
+def test_entries_in_header_binding_and_library(lib):
+    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
+    bound = {name: args for name, _, args in L.PROTOTYPES}
+    for name, n_args in ENTRIES.items():
+        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
+        assert m, name
+        assert len(m.group(1).split(',')) == n_args
+        assert hasattr(lib, name) and len(getattr(lib, name).argtypes) == n_args
+        assert len(bound[name]) == n_args
+    assert '#define FCPP_CELLS_MAX_EDGES 1024' in header
+
+
+# ---- the rule ---------------------------------------------------------------------------------------------------------------------------
+def test_cell_counts_known_by_hand(cut):
+    for i, (name, _, angle) in enumerate(CASES):
+        if name in CC.COUNTS:
+            assert angle == 0.0
+            got = tuple(int(cut[ev].co[i + 1] - cut[ev].co[i]) for ev in MODES)
+            assert got == CC.COUNTS[name], (name, got)
+
+
+@pytest.mark.parametrize('ev', MODES)
+def test_status_euler_count_and_areas(cut, ev):
+    h = cut[ev]
+    assert (h.status == 0).all()
+    for i, (name, f, _) in enumerate(CASES):
+        cells = h.cells(i)
+        assert len(cells) + h.dropped[i] == 1 + h.n_cuts[i] - holes_of(f), name
+        assert (h.field[h.co[i]:h.co[i + 1]] == i).all()
+        areas = h.area[h.co[i]:h.co[i + 1]]
+        assert (areas > 0.0).all()
+        for c, a in zip(cells, areas):
+            assert len(c) >= 3 and abs(shoelace(c) - a) <= 1e-9 * max(a, 1.0), name           # counter-clockwise, and the area reported
+        want = field_area(f)
+        err = abs(areas.sum() + h.dropped_area[i] - want)
+        print(name, ev, 'cells', len(cells), 'area error', err)
+        assert err <= 1e-9 * want, (name, err)
+
+
+@pytest.mark.parametrize('ev', MODES)
+def test_cells_partition_the_field(cut, ev):
+    h = cut[ev]
+    for i, (name, f, _) in enumerate(CASES):
+        allv = np.concatenate(f)
+        lo, hi = allv.min(axis=0), allv.max(axis=0)
+        pts = np.random.default_rng(1000 + i).uniform(lo - 0.05 * (hi - lo), hi + 0.05 * (hi - lo), (N_POINTS, 2))
+        want = inside_even_odd(pts, f)
+        got = sum(inside_even_odd(pts, [c]) for c in h.cells(i))
+        assert 0.1 * N_POINTS < want.sum() < N_POINTS
+        assert np.array_equal(got, want), (name, int((got != want).sum()))
+
+
+def test_reflex_cells_are_convex(cut):
+    h = cut[CC.REFLEX]
+    for i, (name, _, _) in enumerate(CASES):
+        for c in h.cells(i):
+            e1, e2 = c - np.roll(c, 1, axis=0), np.roll(c, -1, axis=0) - c
+            assert (e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0] >= -1e-9).all(), name
+
+
+def test_extrema_cells_are_monotone_across_the_cuts(lib, cut):
+    h = cut[CC.EXTREMA]
+    C = int(h.co[-1])
+    ro = np.arange(C + 1, dtype=np.int64)
+    ang = np.ascontiguousarray(h.angle[h.field])
+    n_sw, n_ln, st = (np.full(C, -7, np.int32) for _ in range(3))
+    rc = lib.fcpp_debug_swaths(C, _p(ro), C, _p(h.ovo), len(h.x), _p(h.x), _p(h.y), 1, _p(ang), 1, 0.5, 0.25, 0.0, _p(n_sw), _p(n_ln), None, _p(st),
+                               None, 0, None, None, None, None, None, None)
+    assert rc == 0, lib.fcpp_last_error()
+    assert (st == 0).all() and np.array_equal(n_sw, n_ln) and n_ln.sum() > 10 * C
+    # (the reflex cells of the same fields, being convex, are monotone too; the FIELDS are not: the test can tell)
+    ro_f, vo_f, x_f, y_f = pack([f for _, f, _ in CASES])
+    n = len(CASES)
+    n_sw, n_ln = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rc = lib.fcpp_debug_swaths(n, _p(ro_f), len(vo_f) - 1, _p(vo_f), len(x_f), _p(x_f), _p(y_f), 1, _p(h.angle), 1, 0.5, 0.25, 0.0, _p(n_sw), _p(n_ln),
+                               None, None, None, 0, None, None, None, None, None, None)
+    assert rc == 0 and (n_sw > n_ln).sum() >= 8
+
+
+@pytest.mark.parametrize('ev', MODES)
+def test_sources_and_input_vertices(cut, ev):
+    h = cut[ev]
+    for i, (name, f, _) in enumerate(CASES):
+        v = np.concatenate(f)
+        nxt = np.concatenate([np.roll(np.arange(len(r)), -1) + sum(len(q) for q in f[:k]) for k, r in enumerate(f)])
+        have = set()
+        for c, src in h.cells(i, with_src=True):
+            have |= {(a.tobytes(), b.tobytes()) for a, b in c}
+            on = src >= 0
+            assert on.any() and (src < len(v)).all() and (src >= -1).all()
+            a, b, p = v[src[on]], v[nxt[src[on]]], c[on]
+            t = np.clip(((p - a) * (b - a)).sum(axis=1) / ((b - a) ** 2).sum(axis=1), 0.0, 1.0)
+            assert np.abs(p - (a + t[:, None] * (b - a))).max() <= P_TOL, name
+            # the piece that leaves the vertex runs along that edge: so does the step to the cell's next vertex
+            step = np.roll(c, -1, axis=0)[on] - p
+            cr = step[:, 0] * (b - a)[:, 1] - step[:, 1] * (b - a)[:, 0]
+            assert np.abs(cr).max() <= 1e-9 * max(1.0, np.abs(b - a).max() * np.abs(step).max()), name
+        assert {(a.tobytes(), b.tobytes()) for a, b in v} <= have, name           # the input vertices, with their input bits
+
+
+@pytest.mark.parametrize('ev', MODES)
+def test_a_rectangle_comes_back_as_itself(ev):
+    rect = np.asarray(CC.RECT, dtype=np.float64) + (3.25, -7.5)
+    h = CC.HostCells([rect, rect[::-1]], [0.0, 0.7], ev)
+    assert h.status.tolist() == [0, 0] and h.n_cuts.tolist() == [0, 0] and h.co.tolist() == [0, 1, 2]
+    a, b = h.cells(0, with_src=True), h.cells(1, with_src=True)
+    assert np.array_equal(a[0][0], rect) and a[0][1].tolist() == [0, 1, 2, 3]
+    # the clockwise copy is driven backwards from its first vertex; the piece leaving a vertex is then the input edge that ENDS there
+    back = rect[::-1]
+    assert np.array_equal(b[0][0], np.roll(back[::-1], 1, axis=0)) and b[0][1].tolist() == [3, 2, 1, 0]
+    assert h.area.tolist() == [40.0, 40.0]
+
+
+def test_min_area_drops_the_slivers_of_the_star(cut):
+    i = [name for name, _, _ in CASES].index('star32')
+    f, angle = CASES[i][1], CASES[i][2]
+    want = field_area(f)
+    for ev in MODES:
+        full = cut[ev]
+        areas = full.area[full.co[i]:full.co[i + 1]]
+        slivers = int((areas <= 1e-6).sum())
+        print('mode', ev, 'cells', len(areas), 'slivers', slivers, 'their areas', areas[areas <= 1e-6])
+        assert slivers >= 1 and full.dropped[i] == 0
+        h = CC.HostCells([f], angle, ev, min_area=1e-6)
+        assert h.status[0] == 0 and h.dropped[0] == slivers and h.co[1] == len(areas) - slivers and h.n_cuts[0] == full.n_cuts[i]
+        assert 0.0 <= h.dropped_area[0] <= 1e-6 * slivers and h.dropped_area[0] == areas[areas <= 1e-6].sum()
+        assert np.array_equal(h.area, areas[areas > 1e-6])
+        assert abs(h.area.sum() + h.dropped_area[0] - want) <= 1e-9 * want
+
+
+@pytest.mark.parametrize('ev', MODES)
+def test_statuses_leave_the_neighbours_alone(ev):
+    good = {'rect': CC.RECT, 'you': CC.YOU, 'holed': CC.NAMED['holed_square'], 'star': CC.STAR32, 'tri_ponds': CC.ponds_field(259, kind='triangle')}
+    bad = {'nan': (CC.NAN_FIELD, CC.EINVAL), 'empty': (CC.EMPTY, CC.EINVAL), 'zero_edge': (CC.ZERO_EDGE, CC.EINVAL),
+           'short_ring': (CC.SHORT_RING, CC.EINVAL), 'star1025': (CC.DEVICE_STARS[1025], CC.EUNSUPPORTED),
+           'ponds259': (CC.ponds_field(259), CC.EUNSUPPORTED), 'touching': (CC.TOUCHING, CC.EUNSUPPORTED),
+           'short_and_over': ([CC.DEVICE_STARS[1025], [(0.0, 0.0), (1.0, 1.0)]], CC.EINVAL)}          # (EINVAL wins)
+    names = ['rect', 'nan', 'you', 'empty', 'zero_edge', 'holed', 'short_ring', 'star1025', 'star', 'ponds259', 'touching', 'tri_ponds', 'short_and_over']
+    fields = [good[k] if k in good else bad[k][0] for k in names]
+    ang = np.linspace(-0.4, 0.8, len(names))
+    h = CC.HostCells(fields, ang, ev)
+    for i, k in enumerate(names):
+        if k in bad:
+            assert h.status[i] == bad[k][1], k
+            assert h.co[i + 1] == h.co[i] and h.cvo[i + 1] == h.cvo[i] and h.n_cuts[i] == 0 and h.dropped[i] == 0 and h.dropped_area[i] == 0.0
+            continue
+        solo = CC.HostCells([fields[i]], ang[i], ev)
+        assert h.status[i] == 0 and solo.status[0] == 0 and h.n_cuts[i] == solo.n_cuts[0]
+        sl, vs = slice(h.co[i], h.co[i + 1]), slice(h.cvo[i], h.cvo[i + 1])
+        assert np.array_equal(h.ovo[h.co[i]:h.co[i + 1] + 1] - h.cvo[i], solo.ovo)
+        assert np.array_equal(h.x[vs].view(np.int64), solo.x.view(np.int64)) and np.array_equal(h.y[vs].view(np.int64), solo.y.view(np.int64))
+        assert np.array_equal(h.src[vs], solo.src) and np.array_equal(h.area[sl].view(np.int64), solo.area.view(np.int64))
+        assert (h.field[sl] == i).all()
+    # two ponds that share a corner on the level of a cut: the walk finds them out
+    assert CC.HostCells([CC.TOUCHING_PONDS], 0.0, ev).status[0] == CC.EUNSUPPORTED
+
+
+def test_the_results_do_not_depend_on_the_threads(cut):
+    code = ("import numpy as np\nfrom tests import cell_cases as CC\nc = CC.named_cases()\n"
+            "h = CC.HostCells([f for _, f, _ in c], [a for _, _, a in c], 0)\nimport sys\n"
+            "sys.stdout.write('%d %d %d' % (h.co[-1], h.cvo[-1], int(h.x.view(np.int64).sum() & 0xffffffff)))")
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd=REPO, env=dict(os.environ, FCPP_THREADS='1', PYTHONPATH=REPO))
+    assert r.returncode == 0, r.stderr[-2000:]
+    h = cut[0]
+    assert r.stdout.split() == [str(int(h.co[-1])), str(int(h.cvo[-1])), str(int(h.x.view(np.int64).sum() & 0xffffffff))]
+
+
+# ---- the call's errors ------------------------------------------------------------------------------------------------------------------
+def test_call_errors(lib):
+    ro, vo, x, y = pack([CC.RECT, CC.ELL])
+    ang = np.array([0.0, 0.5])
+    co, cvo = np.zeros(3, np.int64), np.zeros(3, np.int64)
+
+    def call(ro=ro, vo=vo, x=x, y=y, ang=ang, events=1, min_area=0.0, n=2, n_rings=2, n_verts=len(x), caps=(0, 0)):
+        return lib.fcpp_debug_cells(n, _p(ro), n_rings, _p(vo), n_verts, _p(x), _p(y), _p(ang), events, min_area, _p(co), _p(cvo), None, None, None,
+                                    None, caps[0], caps[1], None, None, None, None, None, None)
+
+    assert call() == 0 and co.tolist() == [0, 1, 2]
+    for kw in (dict(ro=None), dict(vo=None), dict(x=None), dict(y=None), dict(ang=None), dict(events=2), dict(events=-1), dict(min_area=-1.0),
+               dict(min_area=np.nan), dict(min_area=np.inf), dict(ang=np.array([0.0, np.nan])), dict(ang=np.array([np.inf, 0.0])),
+               dict(ang=np.array([0.0, 1.0001e5]))):
+        assert call(**kw) == L.EINVAL, kw
+        assert lib.fcpp_last_error()
+    assert call(ang=np.array([1e5, -1e5])) == 0
+    for kw in (dict(n=-1), dict(n_rings=-1), dict(n_verts=-1), dict(caps=(-1, 0)), dict(caps=(0, -1)), dict(ro=np.array([1, 1, 2])),
+               dict(ro=np.array([0, 2, 1])), dict(ro=np.array([0, 1, 3])), dict(vo=np.array([0, 4, 9])), dict(vo=np.array([0, 11, 10])),
+               dict(vo=np.array([1, 4, 10]))):
+        kw = {k: (np.asarray(v, dtype=np.int64) if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
+        assert call(**kw) == L.ESIZE, kw
+    # the device entries check their handle first
+    assert lib.fcpp_cells_counts(None, 2, _p(ro), 2, _p(vo), len(x), _p(x), _p(y), _p(ang), 1, 0.0, None, None, None, None, None, None, None,
+                                 None) == L.EINVAL
+    assert lib.fcpp_cells_fill(None, 2, _p(ro), 2, _p(vo), len(x), _p(x), _p(y), _p(ang), 1, 0.0, _p(co), _p(cvo), 2, 10, None, None, None, None,
+                               None, None) == L.EINVAL
