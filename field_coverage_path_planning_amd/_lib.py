@@ -17,6 +17,7 @@ RING_AS_VERTICES, RING_REVERSED = 0, 1
 KIND_MASK, FLAG_HEADLAND, FLAG_ALAT, FLAG_OUTSIDE, FLAG_OBSTACLE, INDEX_SHIFT = 7, 8, 16, 32, 64, 8
 OUTPUT_PITCH = 24 << 30          # FCPP_OUTPUT_PITCH (include/fcpp.h)
 ROUTE_MAX_SWATHS = 512           # FCPP_ROUTE_MAX_SWATHS
+TOUR_MAX_CELLS, TOUR_MAX_CELL_NODES, TOUR_MAX_NODES = 32, 64, 1024          # FCPP_TOUR_MAX_*
 CLEAR_EDGE_CHUNK = 256           # FCPP_CLEAR_EDGE_CHUNK
 TRANSIT_MAX_STATIONS = 2048      # FCPP_TRANSIT_MAX_STATIONS
 PART_LOOP_RIDE = 5               # FCPP_PART_LOOP_RIDE
@@ -191,6 +192,9 @@ PROTOTYPES = [
      + [_VP] * 6),
     ('fcpp_route_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
     ('fcpp_route_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
+    ('fcpp_cell_tour_transit', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 6 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP]),
+    ('fcpp_cell_tour_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int,
+                                      C.c_double, C.c_int] + [_VP] * 11),
     ('fcpp_conn_clear', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 6),
     ('fcpp_route_transit_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP, C.c_int64,
@@ -256,6 +260,8 @@ PROTOTYPES = [
      + [C.c_int64, C.c_int64] + [_VP] * 6),
     ('fcpp_debug_route_transit', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP]),
     ('fcpp_debug_route', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int, C.c_double, C.c_int] + [_VP] * 8),
+    ('fcpp_debug_cell_tour', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64] + [_VP] * 8 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, _VP, _VP, C.c_int,
+                                      C.c_double, C.c_int] + [_VP] * 11),
     ('fcpp_debug_conn_clear', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 6),
     ('fcpp_debug_route_transit_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP,

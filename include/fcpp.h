@@ -1204,6 +1204,68 @@ int fcpp_cells_fill(fcpp_ctx *ctx, int64_t n, const int64_t *ring_offsets_dev, i
                     int64_t *out_vert_offsets_dev, double *out_x_dev, double *out_y_dev, int32_t *out_src_dev, int32_t *cell_field_dev,
                     double *area_dev);
 
+/* ---- the cell tour: the order of a field's cells and the route of each ----------------------------------------------------------------------
+ * Build-defined (the reference knows no cells).  A generalised travelling-salesman problem per field, batched over fields: each cell offers
+ * a set of nodes, the task is the order of the cells and one node per cell so that inner costs plus joints are least.  The order is a local
+ * search like the swath router's, the node choice for a given order is exact (a layered shortest path).  Standalone; nothing here feeds
+ * fcpp_batch_plan.  Path planning inside ONE field: nothing here orders fields or vehicles.
+ * THE RULE (csrc/fcpp_tourfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Field f owns the cells cell_offsets[f] .. cell_offsets[f + 1], m of them; cell c owns the variants var_offsets[c] .. var_offsets[c + 1],
+ *     V_c of them.  A variant has an in-pose (ix, iy, ih), an out-pose (ox, oy, oh) and an inner cost w (all float64): w is the caller's
+ *     price of driving it.
+ *   - Cell c has N_c = 2 V_c nodes u = 2 v + d.  d = 0: the poses as given; d = 1: the same drive backwards, in-pose (ox, oy, fl(oh + pi)),
+ *     out-pose (ix, iy, fl(ih + pi)); w(u) is the variant's w for both.  A field's nodes are numbered cell by cell, N_f of them.
+ *   - The joint block D of a field, N_f x N_f float64 row-major: D[a][b] = the total fcpp_dubins_solve (mode 0) or fcpp_rs_solve (mode 1)
+ *     gives at `radius` from out(a) to in(b); +inf where a and b belong to one cell.  Block f starts at d_offsets[f] = sum over earlier
+ *     fields of N^2 (int64, n + 1 values).
+ *   - E, X: optional, sum of N_f float64 each, field f's at 2 var_offsets[cell_offsets[f]]: the cost from the field's entry pose to in(b) and
+ *     from out(b) to its exit pose; NULL = zeros.
+ *   - plus(a, b) = fl(a + b) where that is below +inf, else +inf (NaN included).  The cost of an order c_1 .. c_k of the KEPT cells (V_c > 0),
+ *     exact over the nodes: g_1[b] = plus(E[b], w(b)); g_j[b] = plus(min over a in c_(j-1) of plus(g_(j-1)[a], D[a][b]), w(b)), the
+ *     minimiser the lowest a that attains the minimum; cost = min over b in c_k of plus(g_k[b], X[b]), the lowest b.  The backtrack gives
+ *     one node per kept cell.  joint_length: the chosen D entries, with E and X where given, added in driving order from 0.
+ *   - Candidates c = 0 .. n_starts - 1, 1 <= n_starts <= 64: c = 0 the stored order of the kept cells; c = 1 that order reversed; c >= 2
+ *     nearest neighbour from the kept cell floor((c - 2) k / (n_starts - 2)): repeatedly the unvisited kept cell j with the least C[cur][j],
+ *     ties to the lowest j, C[i][j] = min over a in i, b in j of D[a][b] (an entry not below +inf counts as +inf).
+ *   - Improvement in sweeps.  A sweep evaluates EVERY move below on the current order, each by the cost of the moved order under the full
+ *     rule above, takes the one with the least cost, ties to the lowest code, and applies it iff cost < fl(current cost - min_gain);
+ *     otherwise the candidate is finished; it also stops after max_sweeps sweeps.
+ *       Move A, reverse(i, j), 0 <= i < j < k, code i k + j: the ORDER of positions i .. j reversed (a cell's direction is the node choice's).
+ *       Move B, or-opt, needs k > l: the segment of l in {1, 2, 3} cells at position i moved to between positions p and p + 1, p in
+ *         [-1, k - 1] with p < i - 1 or p >= i + l; r = 0 as it is, r = 1 (l >= 2) reversed.  Code k k + (((l - 1) 2 + r) k + i) (k + 1) + (p + 1).
+ *   - Per field: the winner is the candidate with the least final cost, ties to the lowest c; sweeps = the most moves any candidate
+ *     applied; stored = the stored order with node stored_node[c] of every kept cell (int32, local to the cell; NULL = node 0), chained as
+ *     the rule chains: s = plus(E, w), s = plus(plus(s, D), w) per cell, plus(s, X).  cost <= stored always.  order: field-local cell
+ *     indices in driving order, the skipped cells (V_c = 0) behind the kept ones in stored order; node: the chosen local node of every cell
+ *     in cell order, -1 for a skipped cell; skipped: their number.
+ *   - Status, int32: 0; FCPP_EUNSUPPORTED for m > FCPP_TOUR_MAX_CELLS, a cell with N_c > FCPP_TOUR_MAX_CELL_NODES or N_f >
+ *     FCPP_TOUR_MAX_NODES (the field has a block of size 0, the stored order of all its cells, every node -1, costs NaN); FCPP_EINVAL when
+ *     `stored` is not finite (a non-finite pose, w, E or X, or a stored_node outside its cell, which makes it NaN): nothing is improved,
+ *     the order is the stored one, the nodes the stored ones (0 for one outside its cell), cost = stored, joint_length NaN.  The other
+ *     fields are unaffected.  k = 0: an empty tour of cost 0.  k = 1: the cheapest node under E + w + X.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or required array, radius <= 0 or not finite, mode not 0
+ * or 1, n_starts outside 1 .. 64, min_gain negative or not finite, max_sweeps < 0 or > 2^20; FCPP_ESIZE -- negative sizes, offsets that
+ * do not start at 0, decrease or do not end at their total, d_offsets that are not the blocks of the two offset tables.  The offsets are
+ * checked on the host: pass the host copies or NULL to have them read back.  Both entries synchronise; nothing is kept in the context. */
+#define FCPP_TOUR_MAX_CELLS 32
+#define FCPP_TOUR_MAX_CELL_NODES 64
+#define FCPP_TOUR_MAX_NODES 1024
+/* D_dev (d_total = d_offsets[n] float64): every field's joint block from its variants' poses (n_vars each). */
+int fcpp_cell_tour_transit(fcpp_ctx *ctx, int64_t n, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, int64_t n_cells,
+                           const int64_t *var_offsets_dev, const int64_t *var_offsets_host, int64_t n_vars, const double *ix_dev,
+                           const double *iy_dev, const double *ih_dev, const double *ox_dev, const double *oy_dev, const double *oh_dev,
+                           double radius, int mode, const int64_t *d_offsets_dev, const int64_t *d_offsets_host, int64_t d_total, double *D_dev);
+/* w_dev: n_vars float64; stored_node_dev: n_cells int32 or NULL.  order_dev, node_dev: n_cells int32; cost_dev, stored_dev, joint_length_dev
+ * (float64), winner_dev, sweeps_dev, skipped_dev, status_dev (int32): n each; tours_dev: n_starts x n_cells int32, candidate-major, every
+ * candidate's final order laid out like order_dev; costs_dev: n x n_starts float64.  Any output may be NULL. */
+int fcpp_cell_tour_solve(fcpp_ctx *ctx, int64_t n, const int64_t *cell_offsets_dev, const int64_t *cell_offsets_host, int64_t n_cells,
+                         const int64_t *var_offsets_dev, const int64_t *var_offsets_host, int64_t n_vars, const double *w_dev,
+                         const int32_t *stored_node_dev, const int64_t *d_offsets_dev, const int64_t *d_offsets_host, int64_t d_total,
+                         const double *D_dev, const double *E_dev, const double *X_dev, int n_starts, double min_gain, int max_sweeps,
+                         int32_t *order_dev, int32_t *node_dev, double *cost_dev, double *stored_dev, double *joint_length_dev,
+                         int32_t *winner_dev, int32_t *sweeps_dev, int32_t *skipped_dev, int32_t *status_dev, int32_t *tours_dev,
+                         double *costs_dev);
+
 /* ---- headland paths: every ring of an inset as ONE sampled, closed, drivable path ------------------------------------------------------------
  * Build-defined.  The rings fcpp_inset_fill writes are bare polygons: straight offset pieces that meet in sharp convex corners, and chords
  * of arcs of radius d around reflex vertices.  This operator turns every ring of a batch (all fields, all passes) into a loop a vehicle of
@@ -1515,6 +1577,15 @@ int fcpp_debug_route_transit(int64_t n, const int64_t *swath_offsets, int64_t n_
 int fcpp_debug_route(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
                      const double *E, const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *tours, double *costs, int32_t *route,
                      double *cost, int32_t *winner, int32_t *sweeps, int32_t *status, double *stored);
+/* The cell tour's rule (csrc/fcpp_tourfn.h) evaluated on the HOST, on host pointers, transit and solve in one call: what the device
+ * results are compared with bit for bit.  Arguments, outputs and the call's errors as for fcpp_cell_tour_transit / _solve (the offsets are
+ * the host's); D (d_total float64) is an output too and may be NULL like the others.  Fields are handed to the library's host threads; the
+ * results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_cell_tour(int64_t n, const int64_t *cell_offsets, int64_t n_cells, const int64_t *var_offsets, int64_t n_vars, const double *ix,
+                         const double *iy, const double *ih, const double *ox, const double *oy, const double *oh, const double *w,
+                         const int32_t *stored_node, double radius, int mode, const int64_t *d_offsets, int64_t d_total, double *D, const double *E,
+                         const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *order, int32_t *node, double *cost, double *stored,
+                         double *joint_length, int32_t *winner, int32_t *sweeps, int32_t *skipped, int32_t *status, int32_t *tours, double *costs);
 /* The clearance rule (csrc/fcpp_clearfn.h) evaluated on the HOST, on host pointers: what fcpp_conn_clear and fcpp_route_transit_clear are
  * compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets are the host's).  Paths and fields
  * are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
