@@ -288,6 +288,7 @@ PROTOTYPES = [
                                           C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64] + [_VP] * 7),
     ('fcpp_batch_debug_table', C.c_int, [_VP, C.c_int, _VP, C.c_int64, c_i64_p]),
     ('fcpp_ctx_direct_steps', C.c_int, [_VP, c_i64_p, c_i64_p, c_i64_p]),
+    ('fcpp_ctx_cut_rows_passes', C.c_int, [_VP, c_i64_p]),
 ]
 
 _lib = None

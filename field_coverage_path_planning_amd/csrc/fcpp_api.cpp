@@ -1122,6 +1122,13 @@ int fcpp_ctx_direct_steps(const fcpp_ctx *c, int64_t *launched, int64_t *taken, 
     return FCPP_OK;
 }
 
+int fcpp_ctx_cut_rows_passes(const fcpp_ctx *c, int64_t *passes)
+{
+    if (!c || !passes) return fail(FCPP_EINVAL, "bad arguments");
+    *passes = c->cut_rows_passes;
+    return FCPP_OK;
+}
+
 int fcpp_batch_debug_table(const fcpp_batch *b, int table, void *dst, int64_t cap, int64_t *bytes_out)
 {
     if (!b || !bytes_out) return fail(FCPP_EINVAL, "bad arguments");

@@ -168,6 +168,7 @@ struct fcpp_ctx {
     // fcpp_batch_plan's direct step (fcpp_devplan.h: DevTileConsts.direct) is attempted while the last speculative setup's batch qualified for it
     // (or there was none): a caller of batches that do not -- mixed classes, unfusable spans -- pays the empty launch once, not per call
     bool direct_ok = true;
+    int64_t cut_rows_passes = 0;         // direct setups whose counting pass took the row form (fcpp_ctx_cut_rows_passes: tests)
     int64_t direct_steps = 0, direct_taken = 0, direct_fills = 0;      // launched / batches taken / their fill passes enqueued later (fcpp_ctx_direct_steps: tests)
     // fcpp_conn_solve_clear: the pairs its first pass listed in the last call, and the second-pass launches so far (fcpp_ctx_solve_clear_passes: tests)
     int64_t solve_clear_listed = 0, solve_clear_word_launches = 0;

@@ -127,13 +127,15 @@ constexpr int kNotOnDevice = 1;      // try_device_setup: this batch is the host
 //   FCPP_SMALL_BATCH   fields below which `auto` takes the host: 0 sends every batch it can take to the device (tools/fuzz_parity.py)
 //   FCPP_SETUP_EXACT   set: no speculative layout (the checker of it: tests/test_gpu_devplan.py)
 //   FCPP_DIRECT        0: no direct step (the checker of tests/test_gpu_direct_step.py)
+//   FCPP_CUT_ROWS      0: the direct setup's counting pass keeps a wavefront per field, never the row form (k_tile_rows_direct).  A checker
+//                      like FCPP_DIRECT=0, not a tuning knob (tests/test_gpu_cut_rows.py)
 //   FCPP_FIELD_WORK    0: every wave tile planned with k_plan_sparse, every field reduced with k_reduce_stats (the reference of
 //                      k_plan_sparse_fields; the host tiler's path)
 //   FCPP_DENSE_SPAN    0: round 4's per-line runs for fields without obstacles too (TileConsts::span_line_max)
 //   FCPP_HOST_CHUNKS   1: the host path keeps the host's own chunk lists (the checker, tests/test_gpu_devplan.py)
 struct SetupSwitches {
     int64_t small_batch = 16;
-    bool exact_only = false, direct = true, field_work = true, device_chunks = true;
+    bool exact_only = false, direct = true, cut_rows = true, field_work = true, device_chunks = true;
     int64_t span_line_max = INT64_MAX;
     static SetupSwitches read();
 };

@@ -128,7 +128,14 @@ static_assert(sizeof(DevWaveTile) == 64, "a row of the kept wave tiles holds the
 // fields: the records as the device reaches them (s.fields_in after a copy, or the caller's pinned memory).
 // tc.direct (speculative, no obstacle polygons): cst = the batch's kernel constants (the span's closed-form statistics), see DevTileConsts.direct
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
-                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst = nullptr);
+                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst = nullptr, bool cut_rows = true);
+// The counting pass of a direct setup has two forms with the same outputs: a wavefront per field (k_tile_fields_direct) and, from
+// ROWS_MIN_FIELDS fields on, a row of 32 lanes per field, two fields per wavefront (k_tile_rows_direct).  The threshold is the smallest device batch: measured at 64, 256, 1024,
+// 2048 and 4096 fields the row form was nowhere slower than the wave form (DESIGN section 3 has the figures); it stays a named constant
+// because that is a measurement, not a property.  true: launch_devplan_count takes the row form for this setup.
+constexpr int64_t ROWS_MIN_FIELDS = 16;
+// cut_rows: false keeps the wave form (FCPP_CUT_ROWS=0, the checker: SetupSwitches)
+bool devplan_count_in_rows(const DevTileConsts &tc, int64_t n, bool cut_rows);
 // (tc.dense: the counting pass needs the fields' point offsets -- the chunks of every quiet run lie on 512-point boundaries of the batch arrays --:
 // planner, scan of the points, pass, scan of the other columns)
 // sizing only (fcpp_plan_points): k_plan_fields without primitives; counts[PC_POINTS][field] = points of the field

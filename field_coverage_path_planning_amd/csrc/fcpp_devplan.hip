@@ -3,6 +3,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "fcpp_devplan.h"
 #include "fcpp_launch.h"
@@ -729,6 +730,20 @@ struct TileWaveLds {
     uint8_t ins[TW_NW];           // window point w lies inside the geofence with the host's margin
 };
 
+// The row form of the direct counting pass (k_tile_rows_direct: a field per row of TR_LANES lanes): what the closed-form cut and the pack keep of
+// ONE field -- its descriptor (the row's lanes read the same words: LDS, not a load from device memory each), the records of its primitives (a
+// lane each: the closed-form cut takes fields of up to CUT_PRIMS_MAX, and the headline's have 27 -- three headland loops of eight and three
+// reverse fills --, so a row is HALF a wavefront, not a DPP row of sixteen), their starts and their words for the pack
+constexpr int TR_LANES = 32, TR_ROWS = 64 / TR_LANES;
+static_assert(TR_LANES >= CUT_PRIMS_MAX && TR_LANES >= CUT_TILES_MAX, "a lane per primitive, then a lane per candidate tile");
+struct TileRowLds {
+    DevField F;
+    CutPrim cut[TR_LANES];
+    unsigned long long prim_words[TR_LANES * (sizeof(DevPrim) / 8)];
+    int32_t pstart[TR_LANES];
+    __device__ CutPrim *cut_rows() { return cut; }
+};
+
 // statistics entry e is its own entry, not a run; its slot zeroed
 static_assert(sizeof(TilePartial) == 13 * 8, "thirteen 8-byte components");
 __device__ __forceinline__ void init_entry(const DevPlanTables &T, int64_t e)
@@ -763,8 +778,21 @@ __device__ __forceinline__ double2 field_junction(const DevField &F, const DevCo
 // the sparse instances keep their registers (with the dense block compiled in, the counting pass of large batches went from 79 to 108
 // vector registers: four wavefronts per SIMD instead of six)
 // DIRECT: the counting pass of a direct setup (k_tile_fields_direct): write_direct below
-template <bool FILL, bool STAGE, bool DENSE, bool DIRECT>
+// LW: the lanes that work on the field -- the wavefront's 64, or the 32 of a row (k_tile_rows_direct: the direct counting pass of a field
+// the closed-form cut takes; `lane` is then the lane within the row, every ballot, shuffle and sum stays inside the row, and what is uniform
+// over the wavefront elsewhere is uniform over the row)
+template <bool FILL, bool STAGE, bool DENSE, bool DIRECT, int LW = 64>
 struct TilePass {
+    static constexpr bool ROWS = LW == TR_LANES;
+    static_assert(LW == 64 || (ROWS && !FILL && !DENSE && DIRECT && STAGE), "a row: the direct counting pass");
+    using Lds = typename std::conditional<ROWS, TileRowLds, TileWaveLds<STAGE>>::type;
+    __device__ __forceinline__ static int64_t lanes_sum(int64_t v) { if constexpr (ROWS) return off_half_sum(v); else return off_wave_sum(v); }
+    __device__ __forceinline__ static unsigned long long lballot(bool p)           // (the bits of this lane's row)
+    {
+        if constexpr (ROWS) return (__ballot(p) >> (threadIdx.x & (unsigned)(64 - LW))) & ((1ull << (LW & 63)) - 1ull);
+        else return __ballot(p);
+    }
+    template <class V> __device__ __forceinline__ static V lget(V v, int k) { if constexpr (ROWS) return __shfl(v, k, LW); else return __shfl(v, k); }
     // ---- the launch and the field
     const int64_t n;
     const DevTileConsts &tc;
@@ -778,7 +806,7 @@ struct TilePass {
     DevTile *const keep_tiles;
     DevWaveTile *const keep_wtiles;
     const DevPlanTables &T;
-    TileWaveLds<STAGE> &L;
+    Lds &L;
     const int64_t field;
     const int lane;
     const int64_t n_total = F.n_total;
@@ -811,10 +839,13 @@ struct TilePass {
     TilePartial *d_total = nullptr;
     double2 *d_junc = nullptr;
     bool d_early = false;
+    const Pt2 *row_tmpl = nullptr;       // (rows: the wavefront's LDS copy of the turn templates, U-turn then corner; null: not staged)
     // fill pass: the words of the field's descriptor, its fcpp_field_info and its primitives, a word per lane and round
     static constexpr int NFW = (int)(sizeof(DevField) / 8), NIW = (int)(sizeof(fcpp_field_info) / 8), PWD = (int)(sizeof(DevPrim) / 8), PF_ROUNDS = 7;
     static_assert(sizeof(DevField) % 8 == 0 && sizeof(DevPrim) % 8 == 0 && sizeof(fcpp_field_info) % 8 == 0 && NFW <= 64 && NIW <= 64, "copied as 8-byte words, a lane each");
     unsigned long long fw = 0, iw = 0, pw[PF_ROUNDS];
+    static constexpr int FW_ROUNDS = (NFW + TR_LANES - 1) / TR_LANES;
+    unsigned long long fwr[FW_ROUNDS];   // (a row: word lane + 32 j of the descriptor, loaded by the kernel when it staged the descriptor)
     int nwords_p = 0;
     // the path's shape (n_total > 0: path_consts)
     int64_t per = 0, P = 0, gen_main = 0, n_main = 0, need1 = 0, pos = 0;
@@ -841,9 +872,10 @@ struct TilePass {
         int64_t p0 = 0, p1 = 0, t0 = 0, t1 = 0, in_a = 0, in_b = 0, in_c = 0;
         if (two_level && !FILL) {
             // counting pass: the planner's aggregates of the points and the block's point counts are requested here and summed behind the cut
-            pt_part = offset_prefix_part(agg, counts, n, PC_POINTS, field, lane);
-            // (direct: the descriptor's words for the field's pack, a lane each, on their way during the cut as well)
-            if (DIRECT && lane < NFW) fw = reinterpret_cast<const unsigned long long *>(&F)[lane];
+            if constexpr (ROWS) pt_part = offset_prefix_part_half(agg, counts, n, PC_POINTS, field, lane);
+            else pt_part = offset_prefix_part(agg, counts, n, PC_POINTS, field, lane);
+            // (direct: the descriptor's words for the field's pack, a lane each, on their way during the cut as well; a row has them already: fwr)
+            if (DIRECT && !ROWS && lane < NFW) fw = reinterpret_cast<const unsigned long long *>(&F)[lane];
         } else if (two_level) {
             // fill pass: ONE round of loads -- the flags, the blocks' rows of aggregates (every column's first level and total at once), and of the
             // field's own block the counts in front of it, a lane per field.  Within the capacities (no flag up: else the pass ends here) a field
@@ -1341,7 +1373,7 @@ struct TilePass {
             }
         }
         if (!FILL && use_wave && closed()) { use_wave = false; closed_cut(a, G); }
-        if (use_wave) {
+        if constexpr (!ROWS) if (use_wave) {          // (a row is a field of the closed-form cut: row_eligible)
             int64_t wave_pts = 0, inside_cnt = 0;
             const int64_t nt = cut_stretch(a, b, first_entry(), 0, wave_pts, inside_cnt);
             if (nt >= 0) { n_wave = nt; c_wave_pts = wave_pts; c_wave_inside = inside_cnt; }
@@ -1355,6 +1387,14 @@ struct TilePass {
             }
         }
     }
+    // the row form takes the fields whose stretch sparse_stretch hands to the closed-form cut below (at most CUT_PRIMS_MAX primitives: a lane each)
+    // (asked behind span_decision, before anything is written: every other field is the wave form's, from its beginning)
+    __device__ __forceinline__ bool row_eligible() const
+    {
+        const int64_t a = pos;
+        return n_total > 0 && prim_count <= TR_LANES && wave_ok && n_total - a > 0 && !fallback && tc.closed_cut != 0 && a == cut_span_points(F, tc.cut) &&
+               cut_applies(F, tc.cut, a);
+    }
     // round 5: the general stretch of a field with a closed-form span is cut IN CLOSED FORM (fcpp_cutfn.h, the function the host
     // tiler runs): the step lengths the halos are sized from are the primitives' own steps and the distances between their end points
     // -- the primitives a lane each, then the tiles of a candidate cut a lane each -- no point of the stretch is evaluated.  Counting
@@ -1366,7 +1406,8 @@ struct TilePass {
         // trip of its own), requested together with the primitives' records
         CutConsts lc = tc.cut;
         const int nt_all = tc.cut.nu + tc.cut.nc;
-        const bool cut_staged = nt_all <= TW_LDS_TMPL;
+        const bool cut_staged = !ROWS && nt_all <= TW_LDS_TMPL;       // (rows: the kernel has staged them once for the wavefront's four fields)
+        if (ROWS && row_tmpl) { lc.tu = row_tmpl; lc.tc = row_tmpl + tc.cut.nu; }
         Pt2 tp = { 0.0, 0.0 };
         if (cut_staged && lane < nt_all) tp = lane < tc.cut.nu ? tc.cut.tu[lane] : tc.cut.tc[lane - tc.cut.nu];
         // 1. the primitives' records
@@ -1384,7 +1425,7 @@ struct TilePass {
             for (int w = 0; w < PWD; ++w) L.prim_words[lane * PWD + w] = qw[w];
         }
         TSTAMP(15);
-        if (cut_staged) {
+        if constexpr (!ROWS) if (cut_staged) {
             if (lane < nt_all) L.cut_tmpl()[lane] = tp;
             lc.tu = L.cut_tmpl(); lc.tc = L.cut_tmpl() + tc.cut.nu;
             wave_sync();
@@ -1403,7 +1444,7 @@ struct TilePass {
             L.cut_rows()[lane] = cut_prim_rec(q, F, lc, px, py, fx, fy, ex, ey, p_ok);
             L.pstart[lane] = (int32_t)(q.start - n_main);
         }
-        const bool prims_ok = __ballot(lane < prim_count && !p_ok) == 0ull;
+        const bool prims_ok = lballot(lane < prim_count && !p_ok) == 0ull;
         wave_sync();
         TSTAMP(12);
         // 2. the cut: candidate cuts of T near-equal tiles, the tiles of one a lane each; the decisions of cut_field, taken on the first
@@ -1423,9 +1464,9 @@ struct TilePass {
                 int kj = 0, ke = 0;
                 int32_t rj = 0, re = 0;
                 for (int t = 0; t < T; ++t) {
-                    const int64_t j_t = __shfl(s, t) - 1, e_t = __shfl(s + c - 1, t);
+                    const int64_t j_t = lget(s, t) - 1, e_t = lget(s + c - 1, t);
                     const int32_t relj = (int32_t)(j_t - n_main), rele = (int32_t)(e_t - n_main);
-                    const int a_t = __popcll(__ballot(cut_start <= relj)) - 1, b_t = __popcll(__ballot(cut_start <= rele)) - 1;
+                    const int a_t = __popcll(lballot(cut_start <= relj)) - 1, b_t = __popcll(lballot(cut_start <= rele)) - 1;
                     if (lane == t) { kj = a_t; ke = b_t; }
                 }
                 if (lane < T) {
@@ -1434,9 +1475,9 @@ struct TilePass {
                     if (e < Sl) { ke = -2; re = (int32_t)(e - (Sl - F.n_turn)); } else if (e < n_main) { ke = -1; re = (int32_t)(e - Sl); } else re = (int32_t)(e - n_main) - L.cut_rows()[ke < 0 ? 0 : ke].start_rel;
                     code = cut_tile_eval_at(F, lc, pv, prim_count, cap, s, c, kj, rj, ke, re, Hb, Hf, in);
                 }
-                const unsigned long long bad = __ballot(code != 0);
+                const unsigned long long bad = lballot(code != 0);
                 if (bad == 0ull) { nt = (int)T; break; }
-                if (__shfl(code, __builtin_ctzll(bad)) == 1) break;           // a halo too long: the general kernel's
+                if (lget(code, __builtin_ctzll(bad)) == 1) break;           // a halo too long: the general kernel's
             }
         TSTAMP(13);
         if (nt == 0) return;
@@ -1444,12 +1485,12 @@ struct TilePass {
         const int64_t first = s - Hb, last_l = s + c - 1 + Hf;
         int pa_l = 0, pb_l = 0, pf_l = 0;
         for (int t = 0; t < nt; ++t) {
-            const int64_t f_t = __shfl(first, t), l_t = __shfl(last_l, t);
+            const int64_t f_t = lget(first, t), l_t = lget(last_l, t);
             const int32_t rf = (int32_t)((f_t > gen_main ? f_t : gen_main) - n_main), rl = (int32_t)(l_t - n_main), r1 = (int32_t)(f_t - n_main);
-            const int a_t = __popcll(__ballot(cut_start <= rf)) - 1, b_t = __popcll(__ballot(cut_start <= rl)) - 1, f1_t = __popcll(__ballot(cut_start <= r1)) - 1;
+            const int a_t = __popcll(lballot(cut_start <= rf)) - 1, b_t = __popcll(lballot(cut_start <= rl)) - 1, f1_t = __popcll(lballot(cut_start <= r1)) - 1;
             if (lane == t) { pa_l = a_t < 0 ? 0 : a_t; pb_l = b_t < 0 ? 0 : b_t; pf_l = f1_t < 0 ? 0 : f1_t; }
         }
-        const int64_t inside_cnt = __popcll(__ballot(lane < nt && in));
+        const int64_t inside_cnt = __popcll(lballot(lane < nt && in));
         if (lane < nt) {
             WaveTileCut w;
             w.field = field; w.entry = first_entry() + lane; w.s = s; w.c = c; w.Hb = Hb; w.Hf = Hf; w.inside = in;
@@ -1481,7 +1522,7 @@ struct TilePass {
         // boundaries of the batch arrays
         if (span_k > 0) {
             c_runs = 1 + n_quiet; c_span_pts = S;
-            if (!FILL && two_level) pt_off = off_wave_sum(pt_part);      // (counting pass of a speculative setup: the loads of header())
+            if (!FILL && two_level) pt_off = lanes_sum(pt_part);      // (counting pass of a speculative setup: the loads of header())
             const int64_t g0 = pt_off;                           // the span starts the path
             // (counting pass: fuse_spans = fusing is possible for this batch, both alternatives are counted; fill pass: the host's
             // decision -- all fields of field work have fusable spans, or nothing is fused)
@@ -1545,6 +1586,7 @@ struct TilePass {
         static_assert(PC_POINTS == 0 && PC_PRIMS == 1 && PC_TILES == 2 && PC_WAVE == 3 && PC_GENERAL == 4 && PC_STAT == 5 && PC_SPAN == 6 && PC_WORK == 7 && PC_OPEN == 8 &&
                       PC_CLS0 == 9 && PC_CLS3 == 12 && PC_RUNS == 13 && PC_SPAN_PTS == 14 && PC_WAVE_PTS == 15 && PC_WORK_WAVE_PTS == 16 && PC_WAVE_INSIDE == 17 &&
                       PC_WORK_SPAN_PTS == 18 && PC_SPAN_F == 19 && PC_UNFUSABLE == 20 && PC_CHUNKS == 21 && PC_CHUNK_PTS == 22 && PC_COLS == 23, "the row in column order");
+        static_assert(LW >= PC_COLS, "a lane per column");
         int64_t v = 0;
 #pragma unroll
         for (int k = 1; k < PC_COLS; ++k) if (lane == k) v = row[k];
@@ -1560,9 +1602,17 @@ struct TilePass {
     // summed as fill_junction_and_slots sums them (harmless for a field that turns out not to take a pack: nobody reads them)
     __device__ __forceinline__ void write_direct_early()
     {
-        const int64_t off = off_wave_sum(pt_part);
-        if (lane == (int)(offsetof(DevField, pt_off) / 8)) fw = (unsigned long long)off;
-        if (lane < NFW) reinterpret_cast<unsigned long long *>(&d_pack->field)[lane] = fw;
+        const int64_t off = lanes_sum(pt_part);
+        if constexpr (ROWS) {
+#pragma unroll
+            for (int j = 0; j < FW_ROUNDS; ++j) {
+                const int w = lane + TR_LANES * j;
+                if (w < NFW) reinterpret_cast<unsigned long long *>(&d_pack->field)[w] = w == (int)(offsetof(DevField, pt_off) / 8) ? (unsigned long long)off : fwr[j];
+            }
+        } else {
+            if (lane == (int)(offsetof(DevField, pt_off) / 8)) fw = (unsigned long long)off;
+            if (lane < NFW) reinterpret_cast<unsigned long long *>(&d_pack->field)[lane] = fw;
+        }
         DevTile tl;
         tl.field = (int32_t)field; tl.start = 0; tl.count = 0; tl.quiet = 4; tl.stat_tile = 0; tl.idx0 = 0; tl.off0 = 0;
         const double2 junc = field_junction(F, cst);
@@ -1592,7 +1642,7 @@ struct TilePass {
             return;
         }
         if (!d_early) write_direct_early();
-        if (span_k == 0) pt_off = off_wave_sum(pt_part);           // (field_work_and_span sums it for fields with a span only)
+        if (span_k == 0) pt_off = lanes_sum(pt_part);           // (field_work_and_span sums it for fields with a span only)
         if (!wt_in_lanes) {
             // (the window cut: lane 0 wrote the kept rows one after the other; every tile of such a field is kept)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1614,9 +1664,9 @@ struct TilePass {
         const unsigned long long *psrc = reinterpret_cast<const unsigned long long *>(prims);
         unsigned long long *pdst = reinterpret_cast<unsigned long long *>(&P.prims[0][0]);
         for (int t = 0; t < FIELD_WORK_TILES; ++t) {
-            const int p0 = __shfl(my_p0_rel, t), np = __shfl(my_np, t);
-            if (from_lds) for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? L.prim_words[p0 * PW + k] : 0ull;
-            else for (int k = lane; k < TW; k += 64) pdst[t * TW + k] = (k / PW < np) ? psrc[(int64_t)p0 * PW + k] : 0ull;
+            const int p0 = lget(my_p0_rel, t), np = lget(my_np, t);
+            if (from_lds) for (int k = lane; k < TW; k += LW) pdst[t * TW + k] = (k / PW < np) ? L.prim_words[p0 * PW + k] : 0ull;
+            else for (int k = lane; k < TW; k += LW) pdst[t * TW + k] = (k / PW < np) ? psrc[(int64_t)p0 * PW + k] : 0ull;
         }
         if (lane == 0) {
             DevFieldWork w;
@@ -1856,6 +1906,101 @@ __global__ __launch_bounds__(64 * TW_WAVES, 4) void k_tile_fields_direct(int64_t
     tile_fields_body<false, STAGE, false, true>(n, tc, cst, ftmp, ptmp, info, counts, nullptr, totals, agg, nullptr, mirror, keep_tiles, keep_wtiles, DevPlanTables(),
                                                 direct_packs, direct_totals, direct_junc);
 }
+// The ROW form of that pass: workgroups of one wavefront, TWO fields each -- row r (32 lanes) of wavefront w is field 2 w + r.  The work of the
+// closed-form cut is a lane per primitive (27 on the headline's fields: three headland loops), then a lane per candidate tile (four): with a
+// wavefront per field, 4096 fields are 4096 wavefronts of instructions that serve at most 27 lanes of 64, four to a SIMD and in each other's
+// way; here they are 2048, two to a SIMD.  The phases are TilePass's own (LW = 32): what is uniform over the wavefront there is uniform over
+// the row here, loops whose trip counts differ between the rows run to the larger with the finished row masked off (all have static bounds:
+// CUT_TILES_MAX, CUT_PRIMS_MAX), every ballot, shuffle and sum stays inside its row.  It writes, byte for byte, what k_tile_fields_direct writes.
+// A row whose field the closed-form cut does not take (row_eligible: no span, a planner failure, more than CUT_PRIMS_MAX primitives, ...) writes
+// nothing; the wavefront then takes these fields one after the other through the wave form's pass, all 64 lanes, its LDS over the rows'.
+// Like the pass it stands in for it waits for no other workgroup.
+__global__ __launch_bounds__(64) void k_tile_rows_direct(int64_t n, DevTileConsts tc, DevConst cst, const DevField *__restrict__ ftmp, const DevPrim *__restrict__ ptmp,
+                                                         fcpp_field_info *__restrict__ info, int64_t *__restrict__ counts, int64_t *__restrict__ totals,
+                                                         int64_t *__restrict__ agg, int64_t *__restrict__ mirror, DevTile *__restrict__ keep_tiles,
+                                                         DevWaveTile *__restrict__ keep_wtiles, DevFieldPack *__restrict__ direct_packs,
+                                                         TilePartial *__restrict__ direct_totals, double2 *__restrict__ direct_junc)
+{
+    using RowPass = TilePass<false, true, false, true, TR_LANES>;
+    using WavePass = TilePass<false, true, false, true>;
+    struct RowsLds { TileRowLds row[TR_ROWS]; Pt2 tmpl[TW_LDS_TMPL]; };
+    constexpr size_t LDS_BYTES = sizeof(RowsLds) > sizeof(TileWaveLds<true>) ? sizeof(RowsLds) : sizeof(TileWaveLds<true>);
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    RowsLds &R = *reinterpret_cast<RowsLds *>(lds_raw);
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x == 0) { publish_early_points(n, tc.gen, agg, mirror, 0, lane); return; }
+    const int64_t field0 = ((int64_t)blockIdx.x - 1) * TR_ROWS;
+    const int r = lane / TR_LANES, lr = lane & (TR_LANES - 1);
+    const int64_t field = field0 + r;
+    const bool live = field < n;                                  // (the last wavefront of a batch of an odd number of fields has an empty row)
+    const DevPlanTables no_tables = DevPlanTables();
+    constexpr bool FILL = false;                                  // (what the diagnostic build's TSTAMP asks)
+    (void)FILL;
+    TSTAMP(0);
+    // once per wavefront: the turn templates; once per row: the field's descriptor (its words stay in the lanes for the pack)
+    const int nt_all = tc.cut.nu + tc.cut.nc;
+    const bool tmpl_staged = nt_all <= TW_LDS_TMPL;
+    double tpx = 0.0, tpy = 0.0;
+    if (tmpl_staged && lane < nt_all) { const Pt2 *src = lane < tc.cut.nu ? tc.cut.tu + lane : tc.cut.tc + (lane - tc.cut.nu); tpx = src->x; tpy = src->y; }
+    unsigned long long fwr[RowPass::FW_ROUNDS];
+#pragma unroll
+    for (int j = 0; j < RowPass::FW_ROUNDS; ++j) {
+        const int w = lr + TR_LANES * j;
+        fwr[j] = live && w < RowPass::NFW ? reinterpret_cast<const unsigned long long *>(ftmp + field)[w] : 0ull;
+    }
+    if (tmpl_staged && lane < nt_all) { R.tmpl[lane].x = tpx; R.tmpl[lane].y = tpy; }
+#pragma unroll
+    for (int j = 0; j < RowPass::FW_ROUNDS; ++j) {
+        const int w = lr + TR_LANES * j;
+        if (w < RowPass::NFW) reinterpret_cast<unsigned long long *>(&R.row[r].F)[w] = fwr[j];
+    }
+    wave_sync();
+    bool eligible = false;
+    {
+        RowPass p{ n, tc, cst, R.row[r].F, ptmp + field * tc.max_prims, counts, nullptr, totals, agg, keep_tiles, keep_wtiles, no_tables, R.row[r], field, lr };
+        p.d_pack = &direct_packs[field]; p.d_total = &direct_totals[field]; p.d_junc = &direct_junc[field];
+        p.row_tmpl = tmpl_staged ? R.tmpl : nullptr;
+#pragma unroll
+        for (int j = 0; j < RowPass::FW_ROUNDS; ++j) p.fwr[j] = fwr[j];
+        if (live) {
+            p.header(info);
+            TSTAMP(1);
+            if (p.n_total > 0) p.span_decision();
+            eligible = p.row_eligible();
+        }
+        if (eligible) {
+            p.sparse_stretch();
+            p.field_work_and_span();
+            p.reduce_class_and_flags();
+            TSTAMP(37);
+            p.write_counts();
+            p.add_counts_to_aggregates();
+            p.write_direct();
+            TSTAMP(38);
+        }
+    }
+    // the other fields of the wavefront: the wave form's pass from its beginning, a field after the other (wave-uniform: a ballot, its lowest bit)
+    unsigned long long rest = __ballot(live && !eligible);
+    while (rest) {
+        const int rw = __builtin_ctzll(rest) / TR_LANES;
+        rest &= ~(((1ull << TR_LANES) - 1ull) << (TR_LANES * rw));
+        wave_sync();                                              // (the wave form's LDS lies over the rows')
+        const int64_t field = field0 + rw;
+        WavePass p{ n, tc, cst, ftmp[field], ptmp + field * tc.max_prims, counts, nullptr, totals, agg, keep_tiles, keep_wtiles, no_tables,
+                    *reinterpret_cast<TileWaveLds<true> *>(lds_raw), field, lane };
+        p.d_pack = &direct_packs[field]; p.d_total = &direct_totals[field]; p.d_junc = &direct_junc[field];
+        p.header(info);
+        if (p.n_total > 0) {
+            p.span_decision();
+            p.sparse_stretch();
+            p.field_work_and_span();
+        }
+        p.reduce_class_and_flags();
+        p.write_counts();
+        p.add_counts_to_aggregates();
+        p.write_direct();
+    }
+}
 // (Measured and not kept: the fill pass of a large batch held to six wavefronts per SIMD -- 85 registers, 225 spilled, the primitives not staged:
 // cfg5 390 instead of 235 us.)
 
@@ -1873,8 +2018,13 @@ __global__ void k_debug_math(int fn, int64_t n, const double *__restrict__ a, co
 
 }  // namespace
 
+bool devplan_count_in_rows(const DevTileConsts &tc, int64_t n, bool cut_rows)
+{
+    return tc.direct == DIRECT_COUNT && cut_rows && n >= ROWS_MIN_FIELDS;
+}
+
 int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const DevTileConsts &tc, const DevPlanScratch &s, const fcpp_field *fields,
-                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst)
+                         int64_t n_polys, int check_obstacles, int64_t *totals_host, const DevConst *cst, bool cut_rows)
 {
     if (n <= 0) return 0;
     if (tc.direct == DIRECT_COUNT && (!tc.speculative || tc.dense || n_polys > 0 || !cst || !totals_host || !s.direct_packs)) return (int)hipErrorInvalidValue;
@@ -1903,6 +2053,9 @@ int launch_devplan_count(hipStream_t st, int64_t n, const PlanConsts &pc, const 
     // wavefronts per SIMD instead of four; cfg5's 65 536 fields: plan + count 1.30 -> 1.07 ms)
     auto count = [&]() {
         const unsigned grid = blocks_for(n, TW_WAVES);
+        if (devplan_count_in_rows(tc, n, cut_rows))      // (one workgroup more here too)
+            return launch(st, k_tile_rows_direct, blocks_for(n, TR_ROWS) + 1u, 64, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts, s.totals, agg,
+                          totals_host, s.keep_tiles, s.keep_wtiles, s.direct_packs, s.direct_totals, s.direct_junc);
         if (tc.direct == DIRECT_COUNT) {       // (one workgroup more, the first: the early point total -- tile_fields_body)
             const auto kernel = n <= 4096 ? k_tile_fields_direct<true> : k_tile_fields_direct<false>;
             return launch(st, kernel, grid + 1u, 64 * TW_WAVES, n, tcc, *cst, s.fields_tmp, s.prims_tmp, s.info, s.counts, s.totals, agg, totals_host,

@@ -85,6 +85,36 @@ __device__ __forceinline__ int64_t offset_prefix_part(const int64_t *__restrict_
     if (lane < r) v += counts[(int64_t)col * n + (field - r) + lane];
     return v;
 }
+// A field per HALF of a wavefront (k_tile_rows_direct: rows of 32 lanes): the half's sum, in every lane of the half -- the four butterflies
+// of off_wave_sum that stay inside a DPP row of sixteen lanes, then the other row's sum by a shuffle
+__device__ __forceinline__ int64_t off_half_sum(int64_t v)
+{
+    v += off_dpp_mov<0xB1>(v);
+    v += off_dpp_mov<0x4E>(v);
+    v += off_dpp_mov<0x141>(v);
+    v += off_dpp_mov<0x140>(v);
+    v += __shfl_xor(v, 16);
+    return v;
+}
+// ... and lane `lr` of the half's share of prefix(col, field): 32 lanes by two rounds over the aggregates in front of the field's block (four
+// rounds beyond 64 blocks) and over the counts of the block's fields in front of the field -- independent loads, nothing waited for
+__device__ __forceinline__ int64_t offset_prefix_part_half(const int64_t *__restrict__ agg, const int64_t *__restrict__ counts, int64_t n, int col, int64_t field, int lr)
+{
+    static_assert(OFF_B == 2 * 32 && OFF_NB == 4 * 32, "two rounds of 32 lanes per 64 words");
+    const int b = (int)(field / OFF_B), r = (int)(field % OFF_B);
+    int64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int k = lr + 32 * j;
+        if (k < b) v += agg[offset_at(col, k)];
+        if (k < r) v += counts[(int64_t)col * n + (field - r) + k];
+    }
+    if (b > 64) {
+#pragma unroll
+        for (int j = 2; j < 4; ++j) { const int k = lr + 32 * j; if (k < b) v += agg[offset_at(col, k)]; }
+    }
+    return v;
+}
 // this lane's share of total(col)
 __device__ __forceinline__ int64_t offset_total_part(const int64_t *__restrict__ agg, int nblk, int col, int lane)
 {

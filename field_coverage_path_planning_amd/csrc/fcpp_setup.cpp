@@ -147,10 +147,11 @@ fcpp::SetupSwitches fcpp::SetupSwitches::read()
 {
     SetupSwitches sw;
     const char *e_small = getenv("FCPP_SMALL_BATCH"), *e_direct = getenv("FCPP_DIRECT"), *e_fw = getenv("FCPP_FIELD_WORK"), *e_span = getenv("FCPP_DENSE_SPAN"),
-               *e_chunks = getenv("FCPP_HOST_CHUNKS");
+               *e_chunks = getenv("FCPP_HOST_CHUNKS"), *e_rows = getenv("FCPP_CUT_ROWS");
     if (e_small) sw.small_batch = atoll(e_small);
     sw.exact_only = getenv("FCPP_SETUP_EXACT") != nullptr;
     sw.direct = !(e_direct && atoi(e_direct) == 0);
+    sw.cut_rows = !(e_rows && atoi(e_rows) == 0);
     sw.field_work = !(e_fw && atoi(e_fw) == 0);
     sw.span_line_max = e_span && atoll(e_span) <= 0 ? 64 : INT64_MAX;
     sw.device_chunks = !(e_chunks && atoi(e_chunks) != 0);
@@ -523,7 +524,8 @@ struct DeviceSetup {
     int count()
     {
         const int lrc = launch_devplan_count(st, n_fields, pc, tc, s, dev_fields, obstacles ? obstacles->n_polys : 0, obstacles != nullptr, c->plan_totals_host,
-                                             begin.direct ? &b->cst : nullptr);
+                                             begin.direct ? &b->cst : nullptr, sw.cut_rows);
+        if (!lrc && devplan_count_in_rows(tc, n_fields, sw.cut_rows)) ++c->cut_rows_passes;
         return lrc ? launch_failed(lrc, "launch_devplan_count") : FCPP_OK;
     }
 

@@ -57,6 +57,13 @@ class Context:
         L.check(self.lib.fcpp_ctx_direct_steps(self.handle, C.byref(n), C.byref(t), C.byref(f)))
         return n.value, t.value, f.value
 
+    def cut_rows_passes(self):
+        """Direct setups on this context so far whose counting pass took its row form (fcpp_ctx_cut_rows_passes); FCPP_CUT_ROWS=0, read
+        per call, keeps the form of a wavefront per field: its checker."""
+        n = C.c_int64()
+        L.check(self.lib.fcpp_ctx_cut_rows_passes(self.handle, C.byref(n)))
+        return n.value
+
     def reserve_outputs(self, lane_gib=24.0, pitch_gib=24.0):
         """Give the context its output ARENA (fcpp_ctx_reserve_outputs): one device allocation of 4 x pitch + lane, made once -- it takes
         the driver seconds, so it belongs to start-up, not to a plan call -- in which Batch.alloc() then places the five output arrays of

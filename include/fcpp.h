@@ -1696,6 +1696,9 @@ int fcpp_batch_debug_table(const fcpp_batch *batch, int table, void *dst, int64_
    taken: of those, the calls whose batch qualified -- no fill pass and no fcpp_batch_run in the call; fills: fill passes of taken batches
    enqueued since, because somebody asked for the tables or another setup took the plan slot.  Any pointer may be NULL.  Tests. */
 int fcpp_ctx_direct_steps(const fcpp_ctx *ctx, int64_t *launched, int64_t *taken, int64_t *fills);
+/* Direct setups on this context so far whose counting pass took its row form (two fields per wavefront, 32 lanes each; FCPP_CUT_ROWS=0
+   keeps the form of a wavefront per field, which is its checker).  Tests. */
+int fcpp_ctx_cut_rows_passes(const fcpp_ctx *ctx, int64_t *passes);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Diagnostic only: where the time of the device tiler's counting pass goes for one field of the headline batch.  Needs the
 -DFCPP_DIAG_TILE build (build/libfcpp_diag_tile.so, see HISTORY.md) selected with FCPP_LIBRARY; prints the phase stamps (10 ns ticks)
-of field 1000's wavefront: entry, field read, staging, then per wave tile: window + back halo + candidates + record."""
+of field 1000's wavefront: entry, field read, staging, then per wave tile: window + back halo + candidates + record.
+    diag_tile.py          the counting and fill pass of fcpp_batch_create
+    diag_tile.py plan     the direct counting pass of fcpp_batch_plan: its row form (two fields per wavefront), or with FCPP_CUT_ROWS=0 in
+                          the environment the form of a wavefront per field -- run both to set the two chains side by side"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,7 +15,7 @@ LH = np.tile(np.array([[500.0, 200.0]]), (4096, 1))
 table = E.FieldTable.from_rectangles(LH)
 veh, opt = E.make_vehicle(), E.make_options()
 for r in range(5):
-    b = E.Batch(table, veh, opt)
+    b = E.Batch.plan(table, veh, opt)[0] if sys.argv[1:2] == ['plan'] else E.Batch(table, veh, opt)
     torch.cuda.synchronize()
     out = (C.c_uint64 * 40)()
     rc = L.load().fcpp_diag_tile_stamps(out)
