@@ -7,8 +7,7 @@ import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 port, out = sys.argv[1], sys.argv[2]
 os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=port)
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')

@@ -6,6 +6,7 @@ takes a second item (256, 257), the cap and one beyond it, fields of every statu
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import p as _p
 from tests.test_swaths_host import pack, rings_of, rotated
 
 MAX_EDGES = 1024
@@ -107,10 +108,6 @@ def device_cases():
     out.update({'nan': rings_of(NAN_FIELD), 'empty': EMPTY, 'zero_edge': rings_of(ZERO_EDGE), 'short_ring': rings_of(SHORT_RING),
                 'touching': rings_of(TOUCHING), 'touching_ponds': rings_of(TOUCHING_PONDS), 'ponds259': ponds_field(259, kind='diamond'), 'tri_ponds259': ponds_field(259, kind='triangle')})
     return out
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 class HostCells:

@@ -5,6 +5,7 @@ a non-member."""
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import p as _p
 
 KINDS = {'missed': (3, 1), 'overlapped': (4, 4), 'spill': (3, 2), 'covered': (3, 3)}
 REC = np.dtype([('first', np.int64), ('cells', np.int64), ('a_min', np.int32), ('a_max', np.int32), ('b_min', np.int32), ('b_max', np.int32),
@@ -12,10 +13,6 @@ REC = np.dtype([('first', np.int64), ('cells', np.int64), ('a_min', np.int32), (
 assert REC.itemsize == 48
 T = 64                      # the kernels' tile edge
 BLOCK_CELLS = 4096          # the kernels' numbering block
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def members(shape, where):

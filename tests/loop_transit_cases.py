@@ -5,6 +5,7 @@ import functools
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import p as _p
 from tests.test_field_paths_clear_host import driven_pairs, host_paths_clear
 from tests.test_field_paths_host import stored_order
 from tests.test_headland_paths_host import host_hpaths
@@ -23,10 +24,6 @@ PATH_OUTS = (('x', np.float64), ('y', np.float64), ('heading', np.float64), ('ka
 # the scene
 SCENE_R, SCENE_W, SCENE_SPACING, SCENE_STRIDE = 2.0, 4.0, 0.5, 4
 SCENE_INSET, SCENE_RING = 3.0, 2.5
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def arc_length(off, x, y):

@@ -7,6 +7,7 @@ import functools
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import bits, p as _p
 from tests.test_field_paths_host import host_paths, host_solve_full, stored_order, wrap_diff
 from tests.test_headland_paths_host import host_hpaths
 from tests.test_inset_host import HostInset
@@ -21,10 +22,6 @@ SAMPLE_OUTS = COLS + (('slot', np.int32), ('src', np.int64))
 P_TOL = 1e-9          # the connectors' documented bound on where a sampled connector ends [m]
 
 SCENE_W, SCENE_R, SCENE_SPACING, SCENE_STRIDE = 2.0, 1.5, 0.5, 4
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def _cols(pose):
@@ -169,10 +166,6 @@ def oracle(mode, ps, items, radius, stride, entry=None, exit=None):
             continue
         res.append(dict(status=0, skipped=skipped, transit=transit, station=station, joints=recs, kept=[i for i, _, _ in layers]))
     return res
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def check_against_oracle(mode, got, ps, items, radius, stride, entry=None, exit=None):

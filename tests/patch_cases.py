@@ -4,6 +4,7 @@ is the cell's region index within its field, a negative value is no member."""
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import p as _p
 
 REC = np.dtype([('u_min', np.float64), ('w_lo', np.float64), ('K', np.int64), ('B', np.int64), ('first_line', np.int64), ('first_word', np.int64),
                 ('status', np.int32), ('zero', np.int32), ('u_max', np.float64)])
@@ -17,10 +18,6 @@ MI355X_CUS = 256
 MAX_LINES = 1 << 22
 SWATH_KEYS = ('ax', 'ay', 'bx', 'by', 'line', 'length', 'region')
 KEYS = ('frame', 'records', 'totals', 'bitmap', 'line_counts', 'line_offsets', 'swath_offsets') + SWATH_KEYS
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def lab(shape, where=None, value=0):

@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import p as _p
 
 EPS = 2.0 ** -52
 WIDE = np.longdouble
@@ -221,8 +222,6 @@ def check_properties(ps, prm, v, cap, status, slack=0):
 
 
 # ---- the calls ----------------------------------------------------------------------------------------------------------------------------
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def host_speeds(ps, prm, expect=L.OK, want_v=True, want_cap=True, **override):

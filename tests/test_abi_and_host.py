@@ -11,8 +11,7 @@ import pytest
 import oracle as orc
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import REPO
 
 
 def test_library_exports_every_declared_symbol():

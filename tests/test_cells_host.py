@@ -11,25 +11,20 @@ Tolerances: 1e-9 m for a vertex on its input edge and 1e-9 m^2 for the cross pro
 test_inset_host.py); 1e-9 x the field's area for the sum of the cells' areas against the field's: a rounding bound of two shoelace sums
 over coordinates of up to 120 m, a thousand times what they differ by in fact (under 1e-12 m^2)."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests import cell_cases as CC
+from tests.support import REPO, check_entries, lib, p as _p          # noqa: F401 (lib: a fixture)
 from tests.test_swaths_host import pack
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_TOL = 1e-9
 N_POINTS = 2000
 ENTRIES = {'fcpp_cells_counts': 19, 'fcpp_cells_fill': 21, 'fcpp_debug_cells': 24}
 MODES = (CC.REFLEX, CC.EXTREMA)
 CASES = CC.named_cases()
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 # ---- the checker ------------------------------------------------------------------------------------------------------------------------
@@ -64,11 +59,6 @@ def holes_of(rings):
 
 
 @pytest.fixture(scope='module')
-def lib():
-    return L.load()
-
-
-@pytest.fixture(scope='module')
 def cut():
     """fcpp_debug_cells of the named cases in both modes, min_area 0: computed once and left unchanged"""
     return {ev: CC.HostCells([f for _, f, _ in CASES], [a for _, _, a in CASES], ev) for ev in MODES}
@@ -76,14 +66,7 @@ def cut():
 
 # ---- the entries exist ------------------------------------------------------------------------------------------------------------------
 def test_entries_in_header_binding_and_library(lib):
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes) == n_args
-        assert len(bound[name]) == n_args
+    header = check_entries(ENTRIES, lib)
     assert '#define FCPP_CELLS_MAX_EDGES 1024' in header
 
 

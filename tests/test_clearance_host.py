@@ -11,18 +11,18 @@ fcpp_debug_conn_clear / fcpp_debug_route_transit_clear (csrc/fcpp_clearfn.h on t
   * the transit block: symmetry in bits, the penalty added exactly once, the diagonal, penalty 0;
   * the router: on a constructed field the penalised T makes fcpp_debug_route avoid every blocked connector at a larger length; on the
     square of 40 m with the 16 m hole the blocked legs of the routed order are no more than without clearance, both counts as the oracle's."""
-import os
+import functools
 import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import bits as _bits, check_entries, lib, p as _p          # noqa: F401 (lib: a fixture)
 from tests.test_field_paths_host import host_paths
 from tests.test_route_host import HOLED_SQUARE, cut_with_angle, host_lengths, host_route, host_transit, oriented_poses, t_offsets
 from tests.test_swaths_host import pack
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP = 0.01                   # the oracle's sample spacing [m]
 NEAR = 1e-3                   # a chord this close to an edge without crossing it leaves the case undecided [m]
 PENALTY = 1.0e6
@@ -30,17 +30,7 @@ PENALTY = 1.0e6
 ENTRIES = {'fcpp_conn_clear': 21, 'fcpp_route_transit_clear': 24, 'fcpp_debug_conn_clear': 20, 'fcpp_debug_route_transit_clear': 21}
 
 
-@pytest.fixture(scope='module')
-def lib():
-    return L.load()
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+bits = functools.partial(_bits, dtype=np.uint64)          # (this family compares the unsigned view)
 
 
 def poses(p):
@@ -169,13 +159,7 @@ def oracle(xs, ys, field, near_box=None):
 
 # ---- the entries ------------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported(lib):
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    protos = {name: len(args) for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == protos[name], name
-        assert hasattr(lib, name)
+    header = check_entries(ENTRIES, lib)
     m = re.search(r'#define FCPP_CLEAR_EDGE_CHUNK (\d+)\b', header)
     assert m and int(m.group(1)) == L.CLEAR_EDGE_CHUNK
     # the static LDS of a workgroup (48 B per staged edge) stays well below 64 KiB

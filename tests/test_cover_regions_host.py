@@ -3,31 +3,21 @@ against a flood fill written here (tests/cover_region_cases.py: plain numpy / Py
 and the labels after fill, on every shape of the cases module under both connectivities; the named kinds on a hand-made byte grid; the
 records' sums and boxes against numpy; the call's errors; and one end-to-end case through fcpp_debug_polygon_cover.  Every value is an
 integer: every comparison is ==.  tests/test_gpu_cover_regions.py compares the device entries with this twin."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests import cover_region_cases as C
+from tests.support import check_entries
 from tests.test_polygon_cover_host import RECT40, host_cover, layout, swaths
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_cover_regions_counts': 12, 'fcpp_cover_regions_fill': 10, 'fcpp_debug_cover_regions': 12}
 EINVAL, ESIZE = L.EINVAL, L.ESIZE
 SHAPES = C.shapes()
 
 
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    protos = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m and len(m.group(1).split(',')) == n_args == len(protos[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
 
 
 @pytest.mark.parametrize('connectivity', (4, 8))

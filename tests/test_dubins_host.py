@@ -11,16 +11,14 @@ spurious full circle where the library's does not; every comparison below is wri
 Tolerances come from the project, not from what the code gives: positions and lengths 1e-9 m (ulp(5000) = 9e-13),
 headings 1e-12 rad after wrapping (the trajectory tests' H_TOL)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import check_entries
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_TOL, H_TOL = 1e-9, 1e-12
 EDGE = 1e-9             # a pair with an acos / sqrt argument this close to its domain's edge may be left out of the TOTAL comparison
 FRAGILE_CAP = 0.005     # ... at most this share of a run (asserted): the cap of tests/test_gpu_trajectory.py
@@ -156,18 +154,8 @@ def random_pairs(rng, n, R, near):
 
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------------------------
-def _header():
-    hdr = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-
-
 def test_header_declares_the_five_entries():
-    hdr = _header()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, flags=re.S)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args, (name, m.group(1))
-    assert re.search(r'#define\s+FCPP_ABI_VERSION\s+5\b', hdr)      # additions only
+    check_entries(ENTRIES)          # (ABI version 5: additions only)
 
 
 def test_prototypes_bind_them_and_the_library_exports_them():

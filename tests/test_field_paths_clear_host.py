@@ -11,14 +11,12 @@ tests/test_clearance_host.py on the samples.  The one tolerance is the connector
 The scene of the recorded figures: HOLED_SQUARE cut at angle 0 with W = 4 (14 swaths), R = 6, ENTRY and EXIT of
 tests/test_field_paths_host.py: 15 connector legs.  Region: the field grown by 14 m (Dubins; 4 m for Reeds-Shepp) with the pond shrunk by
 1 m, so that every swath end lies strictly inside it."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import check_entries
 from tests.test_clearance_host import host_clear, oracle
 from tests.test_field_paths_host import (ENTRY, EXIT, FIELD_CASES, SAMPLE_KEYS, SAMPLE_TYPES, _cols, _p, count_rule, driven, gear_runs, host_paths,
                                          leg_slices, stored_order)
@@ -27,7 +25,6 @@ from tests.test_route_host import HOLED_SQUARE, R, bits, cut_with_angle, host_le
 from tests.test_solve_clear_host import host_solve_clear
 from tests.test_swaths_host import ELL, HOLE, pack
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_field_path_counts_clear': 41, 'fcpp_field_path_fill_clear': 36, 'fcpp_debug_field_paths_clear': 46,
            'fcpp_ctx_field_path_clear_passes': 3}
 SLOT_OUTS = (('leg_rank', np.int32, ()), ('leg_crossings', np.int32, ()), ('leg_word', np.int32, ()), ('leg_seg', np.float64, (5,)),
@@ -133,15 +130,7 @@ def square():
 
 # ---- 1. the entries --------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
     import inspect
     assert 'clear_of' in inspect.signature(E.field_paths).parameters and 'reshape' in inspect.signature(E.plan_polygon_fields).parameters
     import dataclasses

@@ -12,16 +12,13 @@ import pytest
 from field_coverage_path_planning_amd import cells as CL
 from field_coverage_path_planning_amd import engine as E
 from tests.cell_cases import YOU
+from tests.support import np_of as _np
 
 pytestmark = pytest.mark.gpu
 
 W, R, SPACING = 2.0, 2.0, 0.5
 ANGLES = (0.0, np.pi / 2)
 TURN_COST = 10.0          # [m] per swath, for both plans: without it an angle is chosen by swath LENGTH alone, which is area / W at any angle
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 @pytest.fixture(scope='module')

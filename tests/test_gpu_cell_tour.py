@@ -15,15 +15,12 @@ from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import cells as CL
 from field_coverage_path_planning_amd import engine as E
 from tests import tour_cases as TC
+from tests.support import np_of as _np
 from tests.tour_cases import OUTPUTS, Scene, bits
 
 pytestmark = pytest.mark.gpu
 
 R = 6.0
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def mixed_scene():

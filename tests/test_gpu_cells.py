@@ -16,20 +16,13 @@ import pytest
 from field_coverage_path_planning_amd import cells as CL
 from field_coverage_path_planning_amd import engine as E
 from tests import cell_cases as CC
+from tests.support import bits as _bits, np_of as _np
 
 pytestmark = pytest.mark.gpu
 
 ANGLES = (0.0, 0.5, 0.3, -1.1, np.pi / 2, 2.5, -0.2)
 MODES = (('reflex', CC.REFLEX), ('extrema', CC.EXTREMA))
 N_FULL = 257
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def full_batch():

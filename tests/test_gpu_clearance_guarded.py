@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
-from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import Gpu
 from tests.test_clearance_host import PENALTY, host_clear, host_solve, host_transit_clear
 from tests.test_gpu_clearance import FIVE, REGIONS, WORKS, random_pairs
 from tests.test_route_host import cut_with_angle, host_transit
@@ -24,14 +24,6 @@ pytestmark = pytest.mark.gpu
 R_ELEM, R_TRANSIT, N_PATHS = 4.0, 6.0, 65
 CONN_OUTS = (('crossings', np.int32), ('inside', np.int8), ('first_s', np.float64), ('field_status', np.int32))
 CONN_SUBSETS = [tuple(k for k, _ in CONN_OUTS), ('inside',), ('first_s',), ('crossings', 'field_status')]
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
 
 
 @pytest.fixture

@@ -17,12 +17,9 @@ import pytest
 
 import oracle as orc
 from field_coverage_path_planning_amd import engine as E
+from tests.support import np_of as _np
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _box(x0, y0, x1, y1):

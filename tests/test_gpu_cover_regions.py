@@ -11,6 +11,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests import cover_region_cases as C
+from tests.support import Gpu as BaseGpu
 
 pytestmark = pytest.mark.gpu
 
@@ -27,17 +28,10 @@ def _hp(a):
     return None if a is None else a.ctypes.data
 
 
-class Gpu:
+class Gpu(BaseGpu):
     def __init__(self):
-        import torch
-        self.torch = torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
-        self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
-
-    def up(self, a):
-        return None if a is None else self.torch.as_tensor(a, device=self.dev)
+        super().__init__()
+        self.n_cu = self.torch.cuda.get_device_properties(self.dev).multi_processor_count
 
 
 @pytest.fixture(scope='module')

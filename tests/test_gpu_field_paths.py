@@ -18,6 +18,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import np_of as _np
 from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES, host_paths, stored_order, wrap_diff
 from tests.test_gpu_route import W, batch, field_poses
 from tests import test_leg_paths_pinned as PIN
@@ -29,10 +30,6 @@ pytestmark = pytest.mark.gpu
 
 FIELD_KEYS = ('offsets', 'leg_offsets', 'work', 'transit', 'status')
 DEV_NAMES = dict(offsets='offsets', leg_offsets='leg_offsets', work='work_length', transit='transit_length', status='status')
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def same_bytes(a, b):

@@ -13,6 +13,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests import test_leg_paths_pinned as PIN
+from tests.support import Gpu as BaseGpu, np_of as _np
 from tests.test_clearance_host import host_clear
 from tests.test_field_paths_clear_host import (ALL_CLEAR, ENTRY, EXIT, FIELD_OUTS, HEAD_KEYS, REGION_DUBINS, REGION_RS, SLOT_OUTS, batch_of_65,
                                                driven_pairs, host_paths_clear, routed_order)
@@ -28,18 +29,7 @@ NAN_OK = ('work', 'transit')          # NaN for a failed field: equal as NaN, wh
 HEAD_TYPES = dict(offsets=np.int64, leg_offsets=np.int64, work=np.float64, transit=np.float64, status=np.int32)
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
-
+class Gpu(BaseGpu):
     def up(self, a):
         return None if a is None else self.torch.as_tensor(np.array(a), device=self.dev)          # (a copy: broadcast inputs are read-only)
 

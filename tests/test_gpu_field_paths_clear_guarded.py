@@ -10,6 +10,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import Gpu
 from tests.test_field_paths_clear_host import ENTRY, EXIT, FIELD_OUTS, REGION_DUBINS, REGION_RS, SLOT_OUTS, batch_of_65, host_paths_clear
 from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES
 from tests.test_route_host import HOLED_SQUARE, R, cut_with_angle
@@ -24,14 +25,6 @@ REQUIRED = ('offsets', 'leg_offsets')
 OPTIONAL = tuple(k for k, _ in COUNT_OUTS if k not in REQUIRED)
 COUNT_SUBSETS = [tuple(k for k, _ in COUNT_OUTS)] + [tuple(k for k, _ in COUNT_OUTS if k != drop) for drop in OPTIONAL]
 FILL_SUBSETS = [SAMPLE_KEYS] + [tuple(k for k in SAMPLE_KEYS if k != drop) for drop in SAMPLE_KEYS]
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
 
 
 @pytest.fixture

@@ -19,6 +19,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import bits as _bits, Gpu as BaseGpu, np_of as _np
 from tests.test_dubins_host import host_solve as dubins_host
 from tests.test_gpu_properties import ragged_paths
 from tests.test_gpu_trajectory import _fsw
@@ -34,21 +35,7 @@ from tests.test_swaths_host import host_cut, host_scores
 pytestmark = pytest.mark.gpu
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
-
+class Gpu(BaseGpu):
     def ok(self, rc):
         assert rc == L.OK, self.lib.fcpp_last_error()
 

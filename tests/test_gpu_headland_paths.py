@@ -14,6 +14,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import np_of as _np
 from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES
 from tests.test_headland_paths_host import (DISTS, FAILED, FAILED_STATUS, R_BRIDGE, R_FOLLOW, RING_KEYS, batch, batch_rings, host_hpaths, many_rectangles,
                                             raw_rings)
@@ -23,10 +24,6 @@ from tests import test_leg_paths_pinned as PIN
 pytestmark = pytest.mark.gpu
 
 NAMES = ('offsets', 'offsets_host', 'x', 'y', 'heading', 'kappa', 'part', 'gear', 'leg', 'work', 'transit', 'skipped', 'status', 'leg_offsets')
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def same_bytes(a, b):

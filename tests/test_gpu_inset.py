@@ -18,6 +18,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import bits as _bits, np_of as _np
 from tests.test_inset_host import DUMBBELL, HOLED, HOLED_DISTS, POND_EDGE, SQUARE, HostInset, boundary_distance, spoilt_last_ring
 from tests.test_swaths_host import COMB, ELL, HOLE, RECT, pack, rings_of, star
 
@@ -34,14 +35,6 @@ KINDS = [('rect', RECT), ('ell', ELL), ('ell_hole', [ELL, HOLE]), ('comb', COMB)
     + [('star%d' % m, star(m, m)) for m in (3, 7, 63, 64, 65, 257, 300, 1024)] + [('star1025', star(1025, 1025)), ('nan', NAN_FIELD),
                                                                                     ('empty', SMALL_SQUARE)]
 SMALL_KINDS = [k for k in KINDS if len(np.concatenate(rings_of(k[1]))) <= 64]
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 @pytest.fixture(scope='module')

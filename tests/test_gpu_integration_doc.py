@@ -5,9 +5,9 @@ import re
 
 import numpy as np
 import pytest
+from tests.support import REPO
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_integration_md_stub_runs(golden_plans):

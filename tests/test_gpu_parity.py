@@ -12,6 +12,7 @@ import pytest
 import oracle as orc
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import np_of as _np
 from tests.test_abi_and_host import _specs_from_golden
 from tests.test_oracle_vs_golden import _field_from_golden
 
@@ -23,10 +24,6 @@ VP_NAMES = [n for n, _ in L.Vehicle._fields_]
 
 def _veh(arr):
     return E.make_vehicle(**dict(zip(VP_NAMES, arr)))
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def test_native_library_is_loaded():

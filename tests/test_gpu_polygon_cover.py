@@ -11,6 +11,7 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import Gpu
 from tests.test_polygon_cover_host import (EARLY, FIVE, MANY_CHUNKS, RECT40, RES_RINGS, SQ30, STAR300, W_RINGS, _arc, _zigzag, early_exit_case,
                                             field_chunks, host_cover, layout, line, many_chunks_case, many_rings_case, swaths)
 from tests.test_swaths_host import ELL, HOLE, pack, star
@@ -29,18 +30,6 @@ def _ptr(t):
 
 def _hp(a):
     return None if a is None else a.ctypes.data
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
-
-    def up(self, a):
-        return None if a is None else self.torch.as_tensor(a, device=self.dev)
 
 
 @pytest.fixture(scope='module')

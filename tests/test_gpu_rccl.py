@@ -9,9 +9,9 @@ import sys
 
 import numpy as np
 import pytest
+from tests.support import REPO
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_sharded_job_collectives_over_rccl_on_one_gpu(tmp_path):

@@ -11,6 +11,7 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import np_of as _np
 from tests.test_route_host import HOLED_SQUARE, MIN_GAIN, R, bits, cut_with_angle, host_lengths, host_route, host_transit, oriented_poses
 from tests.test_guarded_host import ROUTE_S, ROUTE_STRIPS, ROUTE_W, assert_permutations
 from tests.test_guarded_host import strip as _strip
@@ -21,10 +22,6 @@ pytestmark = pytest.mark.gpu
 W = ROUTE_W          # _strip(k): a strip of k working widths of ROUTE_W = 3.2
 NAN_FIELD = np.array(ELL, dtype=np.float64)
 NAN_FIELD[3, 0] = np.nan
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 KINDS = [(_strip(65), 0.0), (HOLED_SQUARE, 0.0), (_strip(0.25), 0.0), (_strip(1), 0.0), (_strip(2), 0.0), (_strip(3), 0.0), (_strip(4), 0.0),

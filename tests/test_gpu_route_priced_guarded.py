@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
-from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import Gpu
 from tests.test_clearance_host import INSET_SQUARE, PENALTY
 from tests.test_field_paths_clear_host import ALL_CLEAR
 from tests.test_gpu_route_priced import NINE, NINE_REGION
@@ -17,14 +17,6 @@ from tests.test_route_priced_host import W, host_transit_priced, strip
 from tests.test_swaths_host import pack
 
 pytestmark = pytest.mark.gpu
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
 
 
 @pytest.fixture

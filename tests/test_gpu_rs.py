@@ -7,17 +7,10 @@ import pytest
 
 from field_coverage_path_planning_amd import engine as E
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import bits as _bits, np_of as _np
 from tests.test_rs_host import GEARS, H_TOL, N_RANDOM, P_TOL, RADII, TURNS, host_solve, integrate, random_pairs, wrap
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def _special_pairs():

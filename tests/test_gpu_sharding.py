@@ -7,9 +7,9 @@ import sys
 
 import numpy as np
 import pytest
+from tests.support import REPO
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize('world', [2, 3])

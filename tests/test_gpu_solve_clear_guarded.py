@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
-from field_coverage_path_planning_amd import engine as E
 from tests.guarded import Arena
+from tests.support import Gpu
 from tests.test_gpu_solve_clear import FIELDS, random_pairs
 from tests.test_solve_clear_host import host_solve_clear
 from tests.test_swaths_host import pack
@@ -19,14 +19,6 @@ R = 4.0
 OUTS = (('word', np.int32), ('seg', np.float64), ('len', np.float64), ('rank', np.int32), ('crossings', np.int32), ('field_status', np.int32))
 SUBSETS = [tuple(k for k, _ in OUTS)] + [tuple(k for k, _ in OUTS if k != drop) for drop, _ in OUTS]
 CASE_FIELDS = [FIELDS[0], FIELDS[4], FIELDS[6]]          # 3 edges, a square with a hole, 257 edges: all valid
-
-
-class Gpu:
-    def __init__(self):
-        import torch
-        self.ctx = E.get_context(None)
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.dev = torch.device('cuda', self.ctx.device)
 
 
 @pytest.fixture

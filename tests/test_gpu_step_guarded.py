@@ -30,6 +30,7 @@ from field_coverage_path_planning_amd import engine as E
 from field_coverage_path_planning_amd import workloads as WL
 from tests import test_gpu_parity as T
 from tests.guarded import Arena
+from tests.support import np_of as _np
 from tests.test_gpu_cover import _box
 from tests.test_gpu_guarded import PATH_LENS, gpu, paths      # noqa: F401  (gpu, paths: fixtures)
 
@@ -40,10 +41,6 @@ POINT_STAGES = ('k_plan_quiet_spans', 'k_plan_quiet', 'k_plan_sparse', 'k_plan_s
 C3_F64 = np.frombuffer(bytes([0xC3] * 8), dtype=np.int64)[0]
 C3_U32 = np.frombuffer(bytes([0xC3] * 4), dtype=np.uint32)[0]
 SLOW_VP = T.DEFAULT_VP[:6] + [0.01] + T.DEFAULT_VP[7:]          # max_longitudinal_accel = 0.01: no turn is closed form
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 # ---- 1: the step on an arena ------------------------------------------------------------------------------------------------------------

@@ -8,20 +8,13 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import bits as _bits, np_of as _np
 from tests.test_guarded_host import CAP_FIELDS, EDGE_KINDS, SCORE_ANGLES, assert_edge_shapes, edge_batch
 from tests.test_swaths_host import COMB, ELL, HOLE, OVER_COMB, RECT, host_cut, host_scores, rings_of, star
 
 pytestmark = pytest.mark.gpu
 
 W, FIRST, MIN_LENGTH = 3.2, 1.6, 0.0
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def _square(side, at=(0.0, 0.0)):

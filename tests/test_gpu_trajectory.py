@@ -16,6 +16,7 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import np_of as _np
 from tests.test_abi_and_host import _specs_from_golden
 from tests.test_gpu_parity import DEFAULT_VP, _random_fields, _veh
 
@@ -25,10 +26,6 @@ H_TOL = 1e-12
 XY_TOL = 1e-9
 TINY_CHORD = 1e-9
 TINY_CAP = 0.005
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 # ---- the numpy restatement ------------------------------------------------------------------------------------------------------

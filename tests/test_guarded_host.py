@@ -19,6 +19,7 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests.guarded import FILL_BYTE, GUARD, GUARD_BYTE, Arena, GuardError
+from tests.support import REPO
 from tests.test_dubins_host import host_solve as dubins_host
 from tests.test_dubins_host import random_pairs
 from tests.test_route_host import MIN_GAIN, cut_with_angle, ends, host_route, host_transit
@@ -26,7 +27,6 @@ from tests.test_route_host import R as R_ROUTE
 from tests.test_rs_host import host_solve as rs_host
 from tests.test_swaths_host import comb, host_cut, host_scores, pack, rings_of, star
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, 'field_coverage_path_planning_amd', 'csrc')
 
 

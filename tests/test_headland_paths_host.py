@@ -15,19 +15,17 @@ chord is no longer than its arc), the float64 coordinates put a measured step a 
 non-negative lengths taken in another order moves by at most 700 ulp: 1e-12 relative between the two directions.
 The distance of a followed arc's samples from the TRUE reflex vertex is measured in test_followed_arcs_lie_on_the_reflex_circle (see there)."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import check_entries, p as _p
 from tests.test_field_paths_host import SAMPLE_KEYS, SAMPLE_TYPES, host_solve_full, wrap_diff
 from tests.test_inset_host import HostInset, oriented_edges
 from tests.test_swaths_host import COMB, ELL, HOLE, RECT, star
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_headland_path_counts': 21, 'fcpp_headland_path_fill': 23, 'fcpp_debug_headland_paths': 30}
 RING_KEYS = ('offsets', 'leg_offsets', 'work', 'transit', 'skipped', 'status')
 KIND_NONE, KIND_STRAIGHT, KIND_DUBINS, KIND_RS, KIND_ARC, KIND_SKIPPED = range(6)
@@ -40,10 +38,6 @@ ELL_NAN = [(0, 0), (60, 0), (60, np.nan), (25, 20), (25, 50), (0, 50)]
 SHAPES = [RECT, [ELL, HOLE], COMB, [SQUARE, POND], DUMBBELL, star(300, 300), [ELL_NAN, HOLE]]
 DISTS = (2.0, 6.0, 8.0, 60.0)
 R_FOLLOW, R_BRIDGE = 1.5, 6.0
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def batch(n):
@@ -144,15 +138,7 @@ def results():
 
 # ---- 1: the entries and the call's errors -------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
     for name in ('headland_paths', 'HeadlandPaths'):
         assert hasattr(E, name), name
     assert 'headland_paths' in E.PolygonPlan.__dataclass_fields__ and E.PolygonPlan.__dataclass_fields__['headland_paths'].default is None

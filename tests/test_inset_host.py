@@ -19,9 +19,9 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import REPO, check_entries, lib, p as _p          # noqa: F401 (lib: a fixture)
 from tests.test_swaths_host import COMB, ELL, HOLE, RECT, pack, rings_of, rotated, star
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_TOL = 1e-9
 ARC_STEP = 0.1
 MAX_EDGES = 1024
@@ -56,10 +56,6 @@ def spoilt_last_ring(rings, how):
 
 HOLED = holed_square()
 HOLED_DISTS = (0.5, 1.6, 4.8)          # the holes' insets stay apart at the first two (259 rings); at 4.8 neighbours merge (2 d > 7.5)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 class HostInset:
@@ -180,22 +176,10 @@ def insets():
     return {(n, d): (got.rings(i, j, with_src=True), got.status[i, j], got.gap[i, j]) for i, n in enumerate(names) for j, d in enumerate((1.6, 4.8, 8.0))}
 
 
-@pytest.fixture(scope='module')
-def lib():
-    return L.load()
-
-
 # ---- the entries exist ------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported(lib):
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    header = check_entries(ENTRIES, lib)
     assert re.search(r'#define FCPP_INSET_MAX_EDGES %d\b' % MAX_EDGES, header)
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
     for name in ('polygon_inset', 'headland', 'InsetSet'):
         assert hasattr(E, name), name
 

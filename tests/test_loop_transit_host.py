@@ -9,7 +9,6 @@ rule's C = fl(fl(in + ride) + out) is taken by brute force in numpy over all (l,
 
 The scene (tests/loop_transit_cases.py; the figures are recorded in DESIGN.md section 8): HOLED_SQUARE (40 m, pond 12 .. 28), work area
 its inset by 3 m, W = 4, angle 0, stored order, Dubins R = 2; loops: the ring 2.5 m outside the pond in both directions."""
-import os
 import re
 
 import numpy as np
@@ -18,10 +17,10 @@ import pytest
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
 from tests import loop_transit_cases as C
+from tests.support import check_entries
 from tests.test_clearance_host import host_clear
 from tests.test_route_host import HOLED_SQUARE, bits, host_lengths
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_loop_transit_solve': 46, 'fcpp_loop_transit_counts': 18, 'fcpp_loop_transit_fill': 34, 'fcpp_ctx_loop_transit_passes': 3,
            'fcpp_debug_loop_transits': 53}
 P_TOL = 1e-9
@@ -91,17 +90,9 @@ def check_consequences(mode, frm, to, radius, pf, fields, ls, got, true_s=True):
 
 # ---- 1. the entries --------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    header = check_entries(ENTRIES)
     assert re.search(r'#define FCPP_TRANSIT_MAX_STATIONS %d\b' % L.TRANSIT_MAX_STATIONS, header) and L.TRANSIT_MAX_STATIONS >= 1024
     assert re.search(r'#define FCPP_PART_LOOP_RIDE %d\b' % L.PART_LOOP_RIDE, header) and L.PART_LOOP_RIDE == 5
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), (name, len(m.group(1).split(',')), len(bound[name]))
-        assert hasattr(lib, name)
     import dataclasses
     import inspect
     assert 'loops' in inspect.signature(E.field_paths).parameters and 'detour' in inspect.signature(E.plan_polygon_fields).parameters

@@ -13,26 +13,14 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests import mission_cases as C
+from tests.support import REPO, check_entries, p as _p
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_mission_solve': 34, 'fcpp_mission_counts': 22, 'fcpp_mission_fill': 39, 'fcpp_debug_mission_paths': 43}
 ENDS = [(False, False), (True, False), (False, True), (True, True)]
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data
-
-
 def test_entries_in_header_binding_and_library():
-    text = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    protos = {name: args for name, _, args in L.PROTOTYPES}
-    lib = L.load()
-    assert lib.fcpp_abi_version() == 5
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, text)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(protos[name]), name
-        assert hasattr(lib, name)
+    text = check_entries(ENTRIES)
     assert re.search(r'#define FCPP_MISSION_MAX_STATIONS %d\b' % L.MISSION_MAX_STATIONS, text)
     assert re.search(r'#define FCPP_PART_JOIN %d\b' % L.PART_JOIN, text) and L.PART_JOIN == L.PART_LOOP_RIDE + 1
     rule = open(os.path.join(REPO, 'field_coverage_path_planning_amd', 'csrc', 'fcpp_missionfn.h')).read()

@@ -3,32 +3,22 @@ written in tests/patch_cases.py, which takes (s, c) from the twin's frame so tha
 counts, offsets, `line`, `region` and the end points, all compared with ==, on every shape of the cases module at four angles and two
 joins; the cover property the rule promises, at 1e-9; the call's errors; the region statuses; and one end-to-end case through the host
 twins of the polygon cover and its regions.  tests/test_gpu_patch.py compares the device entries with this twin."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests import cover_region_cases as C
 from tests import patch_cases as P
+from tests.support import check_entries
 from tests.test_polygon_cover_host import RECT40, host_cover, layout, swaths
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_patch_sizes': 17, 'fcpp_patch_counts': 22, 'fcpp_patch_fill': 24, 'fcpp_debug_patch_swaths': 28}
 SHAPES = P.shapes()
 TOL = 1e-9
 
 
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    protos = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m and len(m.group(1).split(',')) == n_args == len(protos[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
 
 
 @pytest.mark.parametrize('join', P.JOINS)

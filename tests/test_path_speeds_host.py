@@ -14,21 +14,13 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from tests import path_speed_cases as S
+from tests.support import REPO, check_entries
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_path_speeds': 14, 'fcpp_debug_path_speeds': 12}
 
 
 def test_entries_in_header_binding_and_library():
-    text = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    protos = {name: args for name, _, args in L.PROTOTYPES}
-    lib = L.load()
-    assert lib.fcpp_abi_version() == 5
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, text)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(protos[name]), name
-        assert hasattr(lib, name)
+    text = check_entries(ENTRIES)
     for name, val in (('REST_START', L.SPEED_REST_START), ('REST_END', L.SPEED_REST_END), ('STOP_AT_CUSPS', L.SPEED_STOP_AT_CUSPS)):
         assert re.search(r'#define FCPP_SPEED_%s %du\b' % (name, val), text)
     assert C.sizeof(L.SpeedParams) == 8 * 15 + 8

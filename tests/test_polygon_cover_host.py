@@ -3,24 +3,17 @@ counts of the 40 x 20 rectangle (checked with numpy against the rule; no cell ce
 the CPU oracle's cover_grid (an independent implementation of fcpp_cover_grid's predicate, which caps = 1 reproduces), the inside bit
 against the oracle's point_in_polygon per ring, the work mask, joints and flat ends, pass ids, failed fields, odd paths and the layout of
 the path table.  tests/test_gpu_polygon_cover.py compares the device entries with this twin bit for bit."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 import oracle as orc
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import check_entries, p as _p
 from tests.test_swaths_host import ELL, HOLE, pack, star
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_polygon_cover_sizes': 14, 'fcpp_polygon_cover': 26, 'fcpp_debug_polygon_cover': 25}
 RECT40 = [(0, 0), (40, 0), (40, 20), (0, 20)]
 EINVAL, EUNSUPPORTED = -1, -3
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def line(x0, y0, x1, y1, m):
@@ -89,14 +82,7 @@ def host_cover(fields, W, res, lay, caps=0, want_grid=True, expect=0):
 
 
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    protos = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m and len(m.group(1).split(',')) == n_args == len(protos[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
 
 
 # ---- the rectangle's known answers ----------------------------------------------------------------------------------------------------------

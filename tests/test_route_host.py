@@ -19,8 +19,8 @@ ON the feasibility edge of the Dubins words; the bits are still equal there, but
 MEASURED on the host twin (square of 40 m with a 16 m hole, angle 0, W = 4, R = 6, 8 starts; test_holed_square_is_routed_better_than_stored
 prints it): Dubins, the stored order costs 585.095 m of connectors, the routed order 254.699 m, ratio 0.435; Reeds-Shepp 374.181 m against
 196.148 m, ratio 0.524."""
+import functools
 import itertools
-import os
 import re
 
 import numpy as np
@@ -28,9 +28,9 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import bits as _bits, check_entries, lib, p as _p          # noqa: F401 (lib: a fixture)
 from tests.test_swaths_host import COMB, ELL, HOLE, RECT, host_cut
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = 6.0
 MIN_GAIN = 1e-9
 MAX_SWATHS = 512
@@ -40,17 +40,7 @@ FIELDS = {'holed_square': HOLED_SQUARE, 'ell_hole': [ELL, HOLE], 'rect': RECT, '
 ENTRIES = {'fcpp_route_transit': 16, 'fcpp_route_solve': 22, 'fcpp_debug_route_transit': 13, 'fcpp_debug_route': 19}
 
 
-@pytest.fixture(scope='module')
-def lib():
-    return L.load()
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+bits = functools.partial(_bits, dtype=np.uint64)          # (this family compares the unsigned view)
 
 
 def t_offsets(soff):
@@ -223,15 +213,8 @@ def ref_candidate(M, m, c, S, min_gain, max_sweeps, improve=True):
 
 # ---- tests ----------------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported(lib):
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    header = check_entries(ENTRIES, lib)
     assert re.search(r'#define FCPP_ROUTE_MAX_SWATHS %d\b' % MAX_SWATHS, header) and L.ROUTE_MAX_SWATHS == MAX_SWATHS
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
     for name in ('swath_transit', 'route_swaths', 'SwathRoute'):
         assert hasattr(E, name), name
     assert 'order' in E.swath_route.__code__.co_varnames and 'route_swaths' in E.swath_route.__doc__

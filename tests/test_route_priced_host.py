@@ -10,27 +10,21 @@ fcpp_debug_route_transit_priced (priced_transit of csrc/fcpp_solveclearfn.h on t
   * edges: m = 0 and 1, a field over the cap, invalid region fields, penalty 0, a field alone and as field 40 of 65, a start in the pond.
 """
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import check_entries, p as _p
 from tests.test_clearance_host import INSET_SQUARE, PENALTY, REGION, WORK, WORK_R, clearance, host_transit_clear
 from tests.test_field_paths_clear_host import ALL_CLEAR, NAN_REGION, NO_RING, REGION_DUBINS, REGION_RS
 from tests.test_route_host import FIELDS, HOLED_SQUARE, bits, cut_with_angle, host_route, host_transit, oriented_poses, t_offsets
 from tests.test_solve_clear_host import host_solve_clear
 from tests.test_swaths_host import pack
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {'fcpp_route_transit_priced': 24, 'fcpp_ctx_route_priced_passes': 3, 'fcpp_debug_route_transit_priced': 21}
 W = 4.0
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def grown(ring, d):
@@ -143,15 +137,7 @@ def scene_cut(name):
 
 # ---- 1. the entries --------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported():
-    lib = L.load()
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
+    check_entries(ENTRIES)
     for fn in (E.swath_transit, E.route_swaths, E.plan_polygon_fields):
         assert inspect.signature(fn).parameters['price_clear'].default is False
     import dataclasses

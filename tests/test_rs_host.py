@@ -25,8 +25,8 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import REPO, check_entries
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_TOL, H_TOL = 1e-9, 1e-12
 EDGE = 1e-9             # a pair with a root / acos argument or a sign test of the restatement this close to its edge may be left out of the EQUALITY
 FRAGILE_CAP = 0.005     # ... at most this share of a run (asserted): the cap of tests/test_dubins_host.py
@@ -218,18 +218,8 @@ def restate(frm, to, R, dtype=np.float64):
 
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------------------------
-def _header():
-    hdr = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-
-
 def test_header_declares_the_five_entries():
-    hdr = _header()
-    for name, n_args in ENTRIES.items():
-        mm = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, flags=re.S)
-        assert mm, name
-        assert len(mm.group(1).split(',')) == n_args, (name, mm.group(1))
-    assert re.search(r'#define\s+FCPP_ABI_VERSION\s+5\b', hdr)      # additions only
+    check_entries(ENTRIES)          # (ABI version 5: additions only)
 
 
 def test_prototypes_bind_them_and_the_library_exports_them():

@@ -11,7 +11,6 @@ stay below 1e3 m and a crossing is three operations).  numpy's sin / cos may dif
 where a vertex lies within an ulp of a line; the random cases below have no such knife edge (test_restatement_has_no_knife_edge asserts the
 margin), the hand-made ones are used at theta = 0 or checked through rotation-invariant quantities."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -19,8 +18,8 @@ import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
+from tests.support import check_entries, lib, p as _p          # noqa: F401 (lib: a fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_TOL = 1e-9
 MAX_CROSSINGS = 64
 THETAS = (0.0, 0.3, 1.1, 2.5)
@@ -76,10 +75,6 @@ def pack(fields):
         ro.append(len(vo) - 1)
     cat = lambda a: np.ascontiguousarray(np.concatenate(a)) if a else np.zeros(0)
     return np.asarray(ro, dtype=np.int64), np.asarray(vo, dtype=np.int64), cat(xs), cat(ys)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
 
 
 def host_scores(fields, angles, W, first=None, min_length=0.0, expect=0):
@@ -179,22 +174,10 @@ SHAPES = {'rect': RECT, 'ell': ELL, 'ell_hole': [ELL, HOLE], 'comb': COMB}
 STARS = {'star7': star(7, 7), 'star300': star(300, 300)}
 
 
-@pytest.fixture(scope='module')
-def lib():
-    return L.load()
-
-
 # ---- the entries exist ------------------------------------------------------------------------------------------------------------------
 def test_entries_are_declared_bound_and_exported(lib):
-    header = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    assert re.search(r'#define FCPP_ABI_VERSION 5\b', header) and lib.fcpp_abi_version() == 5
+    header = check_entries(ENTRIES, lib)
     assert re.search(r'#define FCPP_SWATH_MAX_CROSSINGS %d\b' % MAX_CROSSINGS, header)
-    bound = {name: args for name, _, args in L.PROTOTYPES}
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args == len(bound[name]), name
-        assert hasattr(lib, name)
     for name in ('polygon_fields', 'swath_scores', 'best_swath_angle', 'polygon_swaths', 'swath_route', 'SwathSet'):
         assert hasattr(E, name), name
 

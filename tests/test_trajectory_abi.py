@@ -2,33 +2,20 @@
 the header declares them, the ctypes binding takes the documented argument lists, libfcpp.so exports them, and without a GPU the engine
 raises instead of computing anything on the CPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from field_coverage_path_planning_amd import _lib as L
 from field_coverage_path_planning_amd import engine as E
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import check_entries
 
 # entry -> number of arguments in include/fcpp.h
 ENTRIES = {'fcpp_trajectory': 13, 'fcpp_batch_trajectory': 9, 'fcpp_trajectory_counts': 7, 'fcpp_trajectory_sample': 24}
 
 
-def _header():
-    hdr = open(os.path.join(REPO, 'include', 'fcpp.h')).read()
-    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-
-
 def test_header_declares_the_four_entries():
-    hdr = _header()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, flags=re.S)
-        assert m, name
-        assert len(m.group(1).split(',')) == n_args, (name, m.group(1))
-    assert re.search(r'#define\s+FCPP_ABI_VERSION\s+5\b', hdr)      # additions only
+    check_entries(ENTRIES)          # (ABI version 5: additions only)
 
 
 def test_prototypes_bind_them_with_the_declared_argument_counts():

@@ -1,11 +1,13 @@
 """Scenes, the host twin's wrapper and the numpy oracles of the cell tour (fcpp_debug_cell_tour; the rule: include/fcpp.h), shared by
 tests/test_cell_tour_host.py and the device tests.  A scene is a batch of fields; a field a list of cells; a cell a list of variants
 (in_pose, out_pose, w), poses (x, y, heading)."""
+import functools
 import itertools
 
 import numpy as np
 
 from field_coverage_path_planning_amd import _lib as L
+from tests.support import bits as _bits, p as _p
 
 MIN_GAIN = 1e-9
 OUT_I32 = ('order', 'node', 'winner', 'sweeps', 'skipped', 'status', 'tours')
@@ -13,12 +15,7 @@ OUT_F64 = ('cost', 'stored', 'joint_length', 'costs')
 OUTPUTS = ('order', 'node', 'cost', 'stored', 'joint_length', 'winner', 'sweeps', 'skipped', 'status', 'tours', 'costs')      # the entries' order
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+bits = functools.partial(_bits, dtype=np.uint64)          # (this family compares the unsigned view)
 
 
 class Scene:
