@@ -82,6 +82,23 @@ int swath_fields(fcpp_ctx *c, int64_t n, const int64_t *ring_ptr, const int64_t 
     return rc;
 }
 
+// the swath offsets and the router's block offsets on the host, checked against each other: block i holds (2 m_i)^2 entries, none beyond
+// FCPP_ROUTE_MAX_SWATHS (route_block of fcpp_routefn.h); what the router's entries and the service trips check alike
+int route_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_ptr, const int64_t *soff_host, int64_t n_total, const int64_t *toff_ptr,
+                  const int64_t *toff_host, int64_t t_total, std::vector<int64_t> &soff, std::vector<int64_t> &toff)
+{
+    if (n < 0 || n_total < 0 || t_total < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
+    int rc = host_offsets(c, n, soff_ptr, soff_host, n_total, "swath_offsets", soff);
+    if (rc == FCPP_OK) rc = host_offsets(c, n, toff_ptr, toff_host, t_total, "t_offsets", toff);
+    if (rc) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t m = soff[(size_t)i + 1] - soff[(size_t)i];
+        if (toff[(size_t)i + 1] - toff[(size_t)i] != (m > FCPP_ROUTE_MAX_SWATHS ? 0 : 4 * m * m))
+            return fail(FCPP_ESIZE, "t_offsets do not match the swath counts: block i holds (2 m_i)^2 entries, none for m_i > 512");
+    }
+    return FCPP_OK;
+}
+
 // m angles on the host, read and checked: finite and within fc_sincos' range, or FCPP_EINVAL in the entry's words
 int host_angles(fcpp_ctx *c, int64_t m, const double *ptr, const double *host, const char *text, std::vector<double> &th)
 {

@@ -19,20 +19,6 @@ int route_search(int S, double min_gain, int max_sweeps)
     return FCPP_OK;
 }
 
-// the swath offsets and the block offsets on the host, checked against each other: block i holds (2 m_i)^2 entries, none beyond the cap
-int route_offsets(fcpp_ctx *c, int64_t n, const int64_t *soff_ptr, const int64_t *soff_host, int64_t n_total, const int64_t *toff_ptr,
-                  const int64_t *toff_host, int64_t t_total, std::vector<int64_t> &soff, std::vector<int64_t> &toff)
-{
-    if (n < 0 || n_total < 0 || t_total < 0 || n > INT32_MAX) return fail(FCPP_ESIZE, "bad sizes");
-    int rc = host_offsets(c, n, soff_ptr, soff_host, n_total, "swath_offsets", soff);
-    if (rc == FCPP_OK) rc = host_offsets(c, n, toff_ptr, toff_host, t_total, "t_offsets", toff);
-    if (rc) return rc;
-    for (int64_t i = 0; i < n; ++i)
-        if (toff[(size_t)i + 1] - toff[(size_t)i] != route_block(soff[(size_t)i + 1] - soff[(size_t)i]))
-            return fail(FCPP_ESIZE, "t_offsets do not match the swath counts: block i holds (2 m_i)^2 entries, none for m_i > 512");
-    return FCPP_OK;
-}
-
 int clear_penalty(double penalty)
 {
     if (!(penalty >= 0.0) || !isfinite(penalty)) return fail(FCPP_EINVAL, "penalty must be non-negative and finite");

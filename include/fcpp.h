@@ -1266,6 +1266,53 @@ int fcpp_cell_tour_solve(fcpp_ctx *ctx, int64_t n, const int64_t *cell_offsets_d
                          int32_t *winner_dev, int32_t *sweeps_dev, int32_t *skipped_dev, int32_t *status_dev, int32_t *tours_dev,
                          double *costs_dev);
 
+/* ---- service trips: a routed field split into capacity-limited round trips to a service point ------------------------------------------------
+ * Build-defined (the reference knows no capacity).  A sprayer runs empty, a harvester runs full: after so many metres of work the vehicle
+ * drives to a service point and comes back.  Given the router's candidate tours of a field, the operator decides after which swaths to
+ * leave so that no trip works more than the capacity and the added driving is least -- the split of a "giant tour", an exact dynamic
+ * programme per tour -- over every candidate in both driving directions, and keeps the cheapest.  Standalone; it reads what
+ * fcpp_route_transit (or its _clear / _priced forms) and fcpp_route_solve wrote.  Path planning inside ONE field.
+ * THE RULE (csrc/fcpp_tripfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Field i has m swaths and N = 2 m oriented swaths p = 2 s + d as in the router's rule; T is its N x N transit block, at t_offsets[i].
+ *   - E, X, In, Out: 2 n_total float64 each in the layout of the router's E / X, field i's N values at 2 swath_offsets[i].  In[q]: the
+ *     connector length from the service pose to the start of q; Out[p]: from the end of p to the service pose; E / X: the first trip's way
+ *     in and the last trip's way out, NULL = zeros.  In and Out must not be NULL.
+ *   - tours: n_cand candidate tours, 1 <= n_cand <= 64, candidate-major n_cand x n_total int32 as fcpp_route_solve writes tours_dev.
+ *   - Per field a capacity Q and an optional first capacity Q0 (first_capacity NULL = Q), in metres of work (summed swath length: length,
+ *     n_total float64); stop_cost >= 0: a price per stop, in metres.
+ *   - Variants v = 2 c + r: r = 0 the tour t = tours[c]; r = 1 the same tour driven backwards, t[k] = tours[c][m - 1 - k] ^ 1.  With
+ *     both_ways = 0 only r = 0 exists; the cost row still has 2 n_cand slots, the odd ones NaN.
+ *   - Tables of a variant, all added left to right: w_k = length[t[k] >> 1]; P[0] = 0, P[k + 1] = fl(P[k] + w_k); base = E[t[0]] +
+ *     T[t[0]][t[1]] + .. + T[t[m - 2]][t[m - 1]] + X[t[m - 1]], the router's own cost expression; for 1 <= j <= m - 1 a stop between the
+ *     positions j - 1 and j costs d_j = plus(fl(fl(Out[t[j - 1]] + In[t[j]]) - T[t[j - 1]][t[j]]), stop_cost), plus(a, b) = fl(a + b) where
+ *     that is below +inf, else +inf (NaN included).
+ *   - A trip over the positions i .. j - 1 is feasible iff j == i + 1 or fl(P[j] - P[i]) <= cap_i, cap_0 = Q0, cap_i = Q otherwise.  A swath
+ *     longer than the capacity is therefore a trip of its own, counted in `overfull`: the vehicle refills mid-swath, which this operator
+ *     does not plan.  No field is infeasible.
+ *   - The programme: g[0] = 0; g[j] = plus(d_j, min over feasible i < j of g[i]) for j = 1 .. m - 1, the minimum over the pair (g[i], i) in
+ *     lexicographic order (ties to the lowest i), pred[j] that i; extra = min over i with (i, m) feasible of g[i], the same order; total =
+ *     plus(base, extra).  Rounded addition is monotone, so this is the minimum over all stop sets of the left-to-right rounded sum.
+ *   - Per field the winner is the variant of least total, ties to the lowest v; its trip starts come from backtracking pred from the final
+ *     pick.  tour: the winner's oriented swaths in driving order; trip: per tour position the trip index within the field, from 0, never
+ *     decreasing; n_trips; overfull: the trips whose work exceeds their cap; winner = v; cost = total, base, extra; costs: every variant's
+ *     total.  m = 0: no trip, cost 0.  m = 1: one trip.  A capacity of +inf is valid: one trip, as long as no d_j is negative --
+ *     connector lengths obey the triangle inequality; a caller's table in which a stop PAYS gets that stop.
+ *   - Status, int32: 0; FCPP_EUNSUPPORTED for m > FCPP_ROUTE_MAX_SWATHS (the field has no block); FCPP_EINVAL for a candidate tour that is no
+ *     permutation of the field's swaths, a length that is negative or not finite, a capacity that is NaN or <= 0, candidate 0's base not
+ *     finite.  For both the field gets tour = candidate 0 as given, trip all 0, n_trips = min(m, 1), overfull 0, winner 0 and NaN costs.
+ *     The other fields are unaffected.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or input, n_cand outside 1 .. 64, stop_cost negative or not
+ * finite, both_ways not 0 or 1; FCPP_ESIZE -- sizes or offsets inconsistent in the ways fcpp_route_solve checks them.  The entry synchronises
+ * like fcpp_route_solve and keeps nothing in the context; it may be called per chunk of fields.
+ * tour_dev, trip_dev: n_total int32; n_trips_dev, overfull_dev, winner_dev, status_dev (int32), cost_dev, base_dev, extra_dev (float64): n
+ * each; costs_dev: n x 2 n_cand float64.  Any output may be NULL. */
+int fcpp_trip_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                    const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total, const double *T_dev, const double *length_dev,
+                    const double *E_dev, const double *X_dev, const double *In_dev, const double *Out_dev, int n_cand, const int32_t *tours_dev,
+                    int both_ways, const double *capacity_dev, const double *first_capacity_dev, double stop_cost, int32_t *tour_dev,
+                    int32_t *trip_dev, int32_t *n_trips_dev, int32_t *overfull_dev, int32_t *winner_dev, int32_t *status_dev, double *cost_dev,
+                    double *base_dev, double *extra_dev, double *costs_dev);
+
 /* ---- headland paths: every ring of an inset as ONE sampled, closed, drivable path ------------------------------------------------------------
  * Build-defined.  The rings fcpp_inset_fill writes are bare polygons: straight offset pieces that meet in sharp convex corners, and chords
  * of arcs of radius d around reflex vertices.  This operator turns every ring of a batch (all fields, all passes) into a loop a vehicle of
@@ -1586,6 +1633,14 @@ int fcpp_debug_cell_tour(int64_t n, const int64_t *cell_offsets, int64_t n_cells
                          const int32_t *stored_node, double radius, int mode, const int64_t *d_offsets, int64_t d_total, double *D, const double *E,
                          const double *X, int n_starts, double min_gain, int max_sweeps, int32_t *order, int32_t *node, double *cost, double *stored,
                          double *joint_length, int32_t *winner, int32_t *sweeps, int32_t *skipped, int32_t *status, int32_t *tours, double *costs);
+/* The service trips' rule (csrc/fcpp_tripfn.h) evaluated on the HOST, on host pointers: what fcpp_trip_solve is compared with bit for
+ * bit.  Arguments, outputs and the call's errors as for it (the offsets are the host's).  Fields are handed to the library's host
+ * threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_trip_solve(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
+                          const double *length, const double *E, const double *X, const double *In, const double *Out, int n_cand,
+                          const int32_t *tours, int both_ways, const double *capacity, const double *first_capacity, double stop_cost,
+                          int32_t *tour, int32_t *trip, int32_t *n_trips, int32_t *overfull, int32_t *winner, int32_t *status, double *cost,
+                          double *base, double *extra, double *costs);
 /* The clearance rule (csrc/fcpp_clearfn.h) evaluated on the HOST, on host pointers: what fcpp_conn_clear and fcpp_route_transit_clear are
  * compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets are the host's).  Paths and fields
  * are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
