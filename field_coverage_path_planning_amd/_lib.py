@@ -197,6 +197,8 @@ PROTOTYPES = [
                                       C.c_double, C.c_int] + [_VP] * 11),
     ('fcpp_trip_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 6 + [C.c_int, _VP, C.c_int, _VP, _VP, C.c_double]
      + [_VP] * 10),
+    ('fcpp_fleet_solve', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 4 + [C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_double]
+     + [_VP] * 11),
     ('fcpp_conn_clear', C.c_int, [_VP, C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 6),
     ('fcpp_route_transit_clear', C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, _VP, C.c_int64, _VP, C.c_int64,
@@ -265,6 +267,7 @@ PROTOTYPES = [
     ('fcpp_debug_cell_tour', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64] + [_VP] * 8 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, _VP, _VP, C.c_int,
                                       C.c_double, C.c_int] + [_VP] * 11),
     ('fcpp_debug_trip_solve', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64] + [_VP] * 6 + [C.c_int, _VP, C.c_int, _VP, _VP, C.c_double] + [_VP] * 10),
+    ('fcpp_debug_fleet_solve', C.c_int, [C.c_int64, _VP, C.c_int64, _VP, C.c_int64] + [_VP] * 4 + [C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_double] + [_VP] * 11),
     ('fcpp_debug_conn_clear', C.c_int, [C.c_int, C.c_int64, _VP, _VP, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64]
      + [_VP] * 6),
     ('fcpp_debug_route_transit_clear', C.c_int, [C.c_int64, _VP, C.c_int64] + [_VP] * 5 + [C.c_double, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP,

@@ -173,6 +173,29 @@ def _gather_fields(pf, idx_h):
     return E.PolygonFields(torch.as_tensor(ring_off, device=dev), torch.as_tensor(vert_off, device=dev), pf.x[v].contiguous(), pf.y[v].contiguous())
 
 
+def _regrouped(swathset, tour, group_swath_offsets, group_field):
+    """The swath records of a SwathSet regrouped along each field's `tour` (m_total oriented swaths, field-local) into the groups that own
+    the positions group_swath_offsets[k] .. group_swath_offsets[k + 1] of it -> (the SwathSet whose "fields" are the groups, its records in
+    driving order; the order that drives each group as the tour does).  group_field: the field of every group.  What trip_paths does for
+    the trips and fleet.share_paths for the vehicles' shares."""
+    torch = _torch()
+    ss = swathset
+    dev = ss.a.device
+    m_total = int(tour.numel())
+    tf = group_field
+    field_of = _owners(ss.offsets, m_total)
+    tour = tour.to(torch.int64)
+    g = ss.offsets[field_of] + (tour >> 1)                    # the swath record driven at every tour position
+    tso = group_swath_offsets
+    tso_h = tso.cpu().numpy()
+    group_of = _owners(tso, m_total)
+    groups = E.SwathSet(tso.contiguous(), tso_h, ss.a[g].contiguous(), ss.b[g].contiguous(), ss.line[g].contiguous(), ss.length[g].contiguous(),
+                        ss.status[tf].contiguous(), ss.n_lines[tf].contiguous(), ss.angle[tf].contiguous())
+    at = torch.arange(m_total, dtype=torch.int64, device=dev)
+    order = (2 * (at - tso[group_of]) + (tour & 1)).to(torch.int32)
+    return groups, order
+
+
 def trip_paths(swathset, split, radius, spacing, reversing=False, clear_of=None, device=None):
     """Every trip of a TripSplit as a sampled path (field_paths over the trips) -> TripPaths.  The swath records are regrouped by trip into a
     SwathSet whose "fields" are the trips (TripPaths.swaths), and field_paths drives each one in the tour's order and directions, from the
@@ -183,19 +206,10 @@ def trip_paths(swathset, split, radius, spacing, reversing=False, clear_of=None,
     torch = _torch()
     ss = swathset
     dev = ss.a.device
-    m_total = int(split.offsets_host[-1])
     K = int(split.trip_offsets_host[-1])
     tf = split.trip_field
-    field_of = _owners(ss.offsets, m_total)
-    tour = split.tour.to(torch.int64)
-    g = ss.offsets[field_of] + (tour >> 1)                    # the swath record driven at every tour position
     tso = split.trip_swath_offsets
-    tso_h = tso.cpu().numpy()
-    trip_of = _owners(tso, m_total)
-    trips = E.SwathSet(tso.contiguous(), tso_h, ss.a[g].contiguous(), ss.b[g].contiguous(), ss.line[g].contiguous(), ss.length[g].contiguous(),
-                       ss.status[tf].contiguous(), ss.n_lines[tf].contiguous(), ss.angle[tf].contiguous())
-    at = torch.arange(m_total, dtype=torch.int64, device=dev)
-    order = (2 * (at - tso[trip_of]) + (tour & 1)).to(torch.int32)
+    trips, order = _regrouped(ss, split.tour, tso, tf)
     index = torch.arange(K, dtype=torch.int64, device=dev) - split.trip_offsets[tf]
     first = tso[:-1] - ss.offsets[tf]
     srv = split.service[tf]

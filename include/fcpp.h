@@ -1313,6 +1313,57 @@ int fcpp_trip_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, 
                     int32_t *trip_dev, int32_t *n_trips_dev, int32_t *overfull_dev, int32_t *winner_dev, int32_t *status_dev, double *cost_dev,
                     double *base_dev, double *extra_dev, double *costs_dev);
 
+/* ---- vehicle shares: a routed field divided among K vehicles of one depot, least makespan ---------------------------------------------------
+ * Build-defined.  Given the router's candidate tours of a field, the operator decides which contiguous stretch of which tour each of at
+ * most K vehicles drives, from the depot and back, so that the vehicle that finishes last finishes as early as possible -- and, among the
+ * splits that are as balanced as that, the one of least summed cost.  Two exact dynamic programmes per tour, over every candidate in both
+ * driving directions.  Standalone; it reads what fcpp_route_transit (or its _clear / _priced forms) and fcpp_route_solve wrote.  Path
+ * planning inside ONE field: one depot, one speed and one width for all vehicles.
+ * THE RULE (csrc/fcpp_fleetfn.h, one set of expressions for host and device: the same bits on both).
+ *   - Field i has m swaths and N = 2 m oriented swaths p = 2 s + d as in the router's rule; T is its N x N transit block, at t_offsets[i].
+ *   - In, Out: 2 n_total float64 each in the layout of the router's E / X, field i's N values at 2 swath_offsets[i].  In[q]: the connector
+ *     length from the depot pose to the start of q; Out[p]: from the end of p to the depot.  Neither may be NULL.
+ *   - tours: n_cand candidate tours, 1 <= n_cand <= 64, candidate-major n_cand x n_total int32 as fcpp_route_solve writes tours_dev.
+ *   - vehicles: K per field, int32, 1 <= K <= FCPP_FLEET_MAX_VEHICLES; length: n_total float64, the swaths' work in metres; work_weight
+ *     (omega) >= 0 and finite: the weight of a metre of work against a metre of driving (transit speed / working speed), so that a
+ *     share's cost is proportional to its time.
+ *   - Variants v = 2 c + r, the service trips': r = 0 the tour t = tours[c]; r = 1 the same tour driven backwards, t[k] =
+ *     tours[c][m - 1 - k] ^ 1.  With both_ways = 0 only r = 0 exists; the value rows still have 2 n_cand slots, the odd ones NaN.
+ *   - Tables of a variant: P[0] = 0, P[k + 1] = fl(P[k] + length[t[k] >> 1]); S[0] = 0, S[k] = fl(S[k - 1] + T[t[k - 1]][t[k]]) for k = 1 ..
+ *     m - 1.
+ *   - A share, the positions i .. j - 1 (0 <= i < j <= m) driven by one vehicle from the depot and back, costs c(i, j) =
+ *     plus(fl(fl(In[t[i]] + fl(S[j - 1] - S[i])) + Out[t[j - 1]]), fl(omega * fl(P[j] - P[i]))), plus(a, b) = fl(a + b) where that is below
+ *     +inf, else +inf (NaN included): c is never NaN.
+ *   - Stage 1, the makespan: G_1[j] = c(0, j); G_k[j] = min over k - 1 <= i < j of max(G_(k-1)[i], c(i, j)) for k <= j; M = min over 1 <= k <=
+ *     min(K, m) of G_k[m].  max and min do not round, so M is the exact least, over every split of the tour into AT MOST K non-empty
+ *     contiguous shares, of the largest share cost.  A further vehicle adds its own In and Out and can make things worse: it stays home.
+ *   - Stage 2, the cheapest among the balanced: H_0[0] = 0; H_k[j] = min over the starts i for which H_(k-1)[i] exists and c(i, j) <= M of
+ *     plus(c(i, j), H_(k-1)[i]), the pair (value, i) in lexicographic order (ties to the lowest i), pred_k[j] that i; H_k[j] exists iff such
+ *     an i does.  The variant's sum is the least (H_k[m], k) over the k <= min(K, m) for which it exists; one does, since M is attained.
+ *     Rounded addition is monotone, so this is the least left-to-right rounded sum of share costs over all splits with every share <= M.
+ *   - Per field the winner is the variant of least (M, sum, v), lexicographically; its shares come from backtracking pred.  tour: the
+ *     winner's oriented swaths in driving order; share: per tour position the vehicle index, from 0, never decreasing; n_used: the shares
+ *     used, <= min(K, m); winner = v; makespan = M, total = sum; makespans, totals: every variant's M and sum; share_first: a share's first
+ *     position, -1 beyond n_used; share_cost: c of every share, NaN beyond n_used.  k_stride, max K <= k_stride <= 16, is the row length
+ *     of share_first and share_cost.  m = 0: no share, makespan 0, total 0.
+ *   - Status, int32: 0; FCPP_EUNSUPPORTED for m > FCPP_ROUTE_MAX_SWATHS (the field has no block) or K > FCPP_FLEET_MAX_VEHICLES;
+ *     FCPP_EINVAL for K < 1 or K > k_stride, a candidate tour that is no permutation of the field's swaths, a length that is negative or not
+ *     finite, candidate 0's S[m - 1] not finite.  For both the field is written as fcpp_trip_solve writes a failed one: tour = candidate 0
+ *     as given, share all 0, n_used = min(m, 1), winner 0, share_first 0 for that one share, and every cost NaN.  The other fields are
+ *     unaffected.
+ * Errors of the CALL, found before any kernel runs: FCPP_EINVAL -- a NULL handle or input, n_cand outside 1 .. 64, k_stride outside 1 .. 16,
+ * work_weight negative or not finite, both_ways not 0 or 1; FCPP_ESIZE -- sizes or offsets inconsistent in the ways fcpp_route_solve checks
+ * them.  The entry synchronises like fcpp_route_solve and keeps nothing in the context; it may be called per chunk of fields.
+ * tour_dev, share_dev: n_total int32; n_used_dev, winner_dev, status_dev (int32), makespan_dev, total_dev (float64): n each; makespans_dev,
+ * totals_dev: n x 2 n_cand float64; share_first_dev (int32), share_cost_dev (float64): n x k_stride.  Any output may be NULL. */
+#define FCPP_FLEET_MAX_VEHICLES 16
+int fcpp_fleet_solve(fcpp_ctx *ctx, int64_t n, const int64_t *swath_offsets_dev, const int64_t *swath_offsets_host, int64_t n_total,
+                     const int64_t *t_offsets_dev, const int64_t *t_offsets_host, int64_t t_total, const double *T_dev, const double *length_dev,
+                     const double *In_dev, const double *Out_dev, int n_cand, const int32_t *tours_dev, int both_ways,
+                     const int32_t *vehicles_dev, int k_stride, double work_weight, int32_t *tour_dev, int32_t *share_dev, int32_t *n_used_dev,
+                     int32_t *winner_dev, int32_t *status_dev, double *makespan_dev, double *total_dev, double *makespans_dev,
+                     double *totals_dev, int32_t *share_first_dev, double *share_cost_dev);
+
 /* ---- headland paths: every ring of an inset as ONE sampled, closed, drivable path ------------------------------------------------------------
  * Build-defined.  The rings fcpp_inset_fill writes are bare polygons: straight offset pieces that meet in sharp convex corners, and chords
  * of arcs of radius d around reflex vertices.  This operator turns every ring of a batch (all fields, all passes) into a loop a vehicle of
@@ -1641,6 +1692,14 @@ int fcpp_debug_trip_solve(int64_t n, const int64_t *swath_offsets, int64_t n_tot
                           const int32_t *tours, int both_ways, const double *capacity, const double *first_capacity, double stop_cost,
                           int32_t *tour, int32_t *trip, int32_t *n_trips, int32_t *overfull, int32_t *winner, int32_t *status, double *cost,
                           double *base, double *extra, double *costs);
+/* The vehicle shares' rule (csrc/fcpp_fleetfn.h) evaluated on the HOST, on host pointers: what fcpp_fleet_solve is compared with bit for
+ * bit.  Arguments, outputs and the call's errors as for it (the offsets are the host's).  Fields are handed to the library's host
+ * threads; the results do not depend on their number.  A diagnostic, not a fallback. */
+int fcpp_debug_fleet_solve(int64_t n, const int64_t *swath_offsets, int64_t n_total, const int64_t *t_offsets, int64_t t_total, const double *T,
+                           const double *length, const double *In, const double *Out, int n_cand, const int32_t *tours, int both_ways,
+                           const int32_t *vehicles, int k_stride, double work_weight, int32_t *tour, int32_t *share, int32_t *n_used,
+                           int32_t *winner, int32_t *status, double *makespan, double *total, double *makespans, double *totals,
+                           int32_t *share_first, double *share_cost);
 /* The clearance rule (csrc/fcpp_clearfn.h) evaluated on the HOST, on host pointers: what fcpp_conn_clear and fcpp_route_transit_clear are
  * compared with bit for bit.  Arguments, outputs and the call's errors as for those two (the offsets are the host's).  Paths and fields
  * are handed to the library's host threads; the results do not depend on their number.  Diagnostics, not fallbacks. */
